@@ -3,8 +3,8 @@
 
 Contract (driver): python bench.py --gpus N --steps K --warmup W.  Prints ONE JSON line on rank 0.
 N > 1: one rank per GPU over RCCL.  Launched through torch.distributed.run the ranks are taken from the
-environment; launched plainly (`python bench.py --gpus 8`) the script re-executes itself under
-torch.distributed.run on 127.0.0.1 with a free port.
+environment; launched plainly (`python bench.py --gpus 8`) the script starts itself again as a child process under
+torch.distributed.run on 127.0.0.1 with a free port and waits for it.
 
 A "step" is one pass of the hot path over one batch: sample random actions (device, counter-based) -> step
 kernel (physics + scenario logic + auto-reset of finished episodes) -> frame setup -> frame sort -> raster kernel
@@ -20,18 +20,16 @@ when every GPU's consumer reads its own shard (the reference's multi-GPU mode).
 
 Timing: the K timed steps carry no instrumentation.  The per-kernel figures of `roofline` / `roofline_physics`
 come from a second, untimed loop with HIP events on the gym's stream (mv_profile_begin).
+--dump-outputs DIR (N = 1): right after the timed steps, what their last tick computed goes to DIR/*.npy (dump_outputs); the inputs are
+seeded, so runs with the same arguments can be compared output for output.
 """
 import argparse
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
-
-# HIP deals a process's streams over 4 hardware queues unless told otherwise; a gym holds up to six (the caller's, simulation, copy, episode draws, two pass
-# streams) and the transparency legs make more gyms: streams that land on one queue serialise (r11a / r11b: the legs that make NEW gyms after the main one ran at half
-# their rate -- MegaverseEnv.step_device 7.5 M obs/s against 16.7 M -- until the process had 8 queues; the main loop's rate does not move).  Before HIP starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -201,6 +199,35 @@ def cpu_baseline_mixed(scenarios, obs_w, obs_h, n_env, agents):
                       f"obs {obs_w}x{obs_h}, stepped one after the other on {threads} threads: {steps_total} rounds in {t_total:.1f} s, median of 3"}
 
 
+DUMP_BYTES = 48 << 20   # --dump-outputs: budget of the whole-frame sample (float32); the other arrays are a few KB
+
+
+def dump_outputs(out_dir, gym, n_env, agents, mixed):
+    """--dump-outputs: what the timed path computed in its last tick, as a caller reads it back (the gym's host getters read the entry of
+    the last tick, include/megaverse_hip.h), written as DIR/<name>.npy in float32 / float64:
+      obs_frame_sums     float64 [N*A]         the sum of every RGBA8 byte of each agent frame (all frames)
+      obs_sample         float32 [S, H, W, 4]  S whole frames, a fixed seeded sample of the frame indices (S: as many as DUMP_BYTES holds, at most N*A)
+      obs_sample_frames  float64 [S]           their frame indices (env * A + agent)
+      rewards            float32 [N*A]         the last tick's rewards
+      dones              float32 [N]           the last tick's done flags"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    gym.synchronize()
+    frames = n_env * agents
+    obs = np.stack([gym.get_observation(f // agents, f % agents) for f in range(frames)])
+    n_sample = max(1, min(frames, DUMP_BYTES // (obs[0].size * 4)))
+    sample = np.sort(np.random.default_rng(20240607).choice(frames, size=n_sample, replace=False))
+    rewards = gym.get_last_rewards() if mixed else gym.get_rewards_array()
+    dones = [gym.is_done(e) for e in range(n_env)] if mixed else gym.get_dones()
+    out = {"obs_frame_sums": obs.reshape(frames, -1).sum(axis=1, dtype=np.float64),
+           "obs_sample": obs[sample].astype(np.float32),
+           "obs_sample_frames": sample.astype(np.float64),
+           "rewards": np.asarray(rewards, dtype=np.float32),
+           "dones": np.asarray(dones, dtype=np.float32)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -215,7 +242,7 @@ def respawn_under_torchrun(n):
            "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))   # (a child process: this one has not touched the GPU and only waits)
 
 
 class ObsGather:
@@ -357,7 +384,11 @@ def main():
                          "host copies -- the launcher, the sharding (env_offset / total_envs) and ObsGather as in a real run, no xGMI")
     ap.add_argument("--check-gather", action="store_true",
                     help="after the timed loop rank 0 replays the whole job in ONE gym of N x envs-per-gpu envs and compares its slab with the gathered one")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what their last tick computed (observations, rewards, dones) as DIR/<name>.npy (--gpus 1 only)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus != 1 or args.dry_run):
+        ap.error("--dump-outputs needs --gpus 1 and a device")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_torchrun(args.gpus)
@@ -558,6 +589,8 @@ def main():
     run_steps(step0, args.warmup, do_gather, main_batched)
     step0 += args.warmup
     elapsed = timed(step0, do_gather, main_batched)        # THE timed region: exactly --steps steps, no instrumentation
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, gym, n_env, A, mixed)
     step0 += args.steps
     last_gathered = step0 - 1
     elapsed_no_gather = None
@@ -815,7 +848,6 @@ def main():
                        # leaves its observations in slab j of a ring of that many slabs
                        "pipelined": pipelined, "ticks_per_call": batch if main_batched else 1,
                        **({"ring_slots": ring_slots, "overlapped_passes": bool(pass_overlap)} if main_batched else {}),
-                       "hip_hardware_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
                        # who draws the episodes (mv_host_generator_threads): the host feeder's threads, or 0 = on the device (TowerBuilding; Collect where the
                        # rank's share of the host is under three cores, or MV_COLLECT_DEVICE_GEN=1)
                        **({"host_generator_threads": gym.host_generator_threads()} if hasattr(gym, "host_generator_threads") else {}),

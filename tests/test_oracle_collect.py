@@ -1,25 +1,25 @@
 """CPU tests of the Collect restatement in oracle/ (SURVEY.md §8 row Y): the Perlin noise is pinned against the
-reference's vendored perlin_noise.hpp compiled in place (oracle/_ref); the rest are spec-derived invariants of
+reference's vendored perlin_noise.hpp compiled in place (oracle/_ref; its outputs stored in tests/golden/ref_vectors.npz); the rest are spec-derived invariants of
 scenario_collect.cpp."""
 import numpy as np
 import pytest
 
 import oracle_lib
+import ref_vectors
 from megaverse_amd.rollout import action_masks, sample_actions
 
 
-@pytest.mark.parametrize("seed,octaves", [(0, 1), (1, 3), (123456789, 9), (999999999, 5), (4294967295, 2)])
+@pytest.mark.parametrize("seed,octaves", ref_vectors.PERLIN_CASES)
 def test_perlin_matches_reference_header(seed, octaves):
-    ref = oracle_lib.ref_lib()
-    if ref is None or not hasattr(ref, "mvref_perlin_octave2_01"):
-        pytest.skip("oracle/_ref not built")
-    rng = np.random.default_rng(seed & 0xffff)
-    n = 4000
-    xs = rng.uniform(0, 12, n); ys = rng.uniform(0, 12, n)
-    xs[:64] = np.arange(64) / (42 / 9.9); ys[:64] = np.arange(64)[::-1] / (42 / 0.1)   # the x / fx, z / fz grid of :86-88
-    a, b = np.empty(n), np.empty(n)
+    live = oracle_lib.ref_lib()
+    if live is not None and hasattr(live, "mvref_perlin_octave2_01"):
+        ref_vectors.assert_same_as_stored(ref_vectors.util_vectors(live), [f"perlin_{seed}_{octaves}{k}" for k in ("_xs", "_ys", "")])
+    z = ref_vectors.load()
+    xs, ys, b = z[f"perlin_{seed}_{octaves}_xs"], z[f"perlin_{seed}_{octaves}_ys"], z[f"perlin_{seed}_{octaves}"]
+    n = len(xs)
+    assert n == 4000 and np.array_equal(xs[:64], np.arange(64) / (42 / 9.9)) and np.array_equal(ys[:64], np.arange(64)[::-1] / (42 / 0.1))   # the x / fx, z / fz grid of :86-88
+    a = np.empty(n)
     oracle_lib.lib().mvo_perlin_octave2_01(seed, xs.ctypes.data, ys.ctypes.data, n, octaves, a.ctypes.data)
-    ref.mvref_perlin_octave2_01(seed, xs.ctypes.data, ys.ctypes.data, n, octaves, b.ctypes.data)
     assert np.array_equal(a.view(np.uint64), b.view(np.uint64))
     assert a.min() >= 0.0 and a.max() <= 1.0
 

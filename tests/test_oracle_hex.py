@@ -1,39 +1,32 @@
 """CPU tests of the Hex scenarios' building blocks in oracle/ (SURVEY.md 8f-4).  The honeycomb maze generator (src/libs/mazes in the
 reference tree: vendored, dependency-free) is PINNED: the restatement is compared with the library itself, compiled in place into
-oracle/_ref/libmv_ref_mazes.so with a seeded subclass of its Kruskal (the reference seeds it from std::random_device)."""
-import ctypes as C
-import os
+oracle/_ref/libmv_ref_mazes.so with a seeded subclass of its Kruskal (the reference seeds it from std::random_device); its mazes are
+stored in tests/golden/ref_vectors.npz."""
 
 import numpy as np
 import pytest
 
 import oracle_lib
+import ref_vectors
 
-REF = os.path.join(oracle_lib.ORACLE_DIR, "_ref", "libmv_ref_mazes.so")
-
-
-def maze(fn, size, seed):
-    cells = C.c_int(0)
-    n = fn(size, seed, C.byref(cells), None, None, None, None, None)
-    counts = np.zeros(cells.value, np.int32); to = np.zeros(n, np.int32); xy = np.zeros((n, 4), np.float64)
-    centers = np.zeros((cells.value, 2), np.float64); bounds = np.zeros(4, np.float64)
-    assert fn(size, seed, C.byref(cells), counts.ctypes.data, to.ctypes.data, xy.ctypes.data, centers.ctypes.data, bounds.ctypes.data) == n
-    return cells.value, counts, to, xy, centers, bounds
+maze, bind = ref_vectors.maze, ref_vectors.bind_maze
 
 
-def bind(lib, name):
-    fn = getattr(lib, name)
-    fn.argtypes = [C.c_int, C.c_uint, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    fn.restype = C.c_int
-    return fn
+@pytest.fixture(scope="module")
+def stored_mazes():
+    """tests/golden/ref_vectors.npz: the library's mazes; where oracle/_ref/libmv_ref_mazes.so is built they are first recomputed with it and
+    must be the same bytes"""
+    live = ref_vectors.mazes_lib()
+    if live is not None:
+        ref_vectors.assert_same_as_stored(ref_vectors.maze_vectors(live))
+    return ref_vectors.load()
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref/libmv_ref_mazes.so is built from /root/reference (not present here)")
-@pytest.mark.parametrize("size", [2, 3, 5, 8, 10])
-def test_honeycomb_maze_matches_the_reference_library(size):
-    ref, mine = bind(C.CDLL(REF), "mvref_hex_maze"), bind(oracle_lib.lib(), "mvo_hex_maze")
-    for seed in (0, 1, 12345, 2 ** 31 + 7):
-        a, b = maze(ref, size, seed), maze(mine, size, seed)
+@pytest.mark.parametrize("size", ref_vectors.MAZE_SIZES)
+def test_honeycomb_maze_matches_the_reference_library(stored_mazes, size):
+    mine = bind(oracle_lib.lib(), "mvo_hex_maze")
+    for seed in ref_vectors.MAZE_SEEDS:
+        a, b = ref_vectors.stored_maze(stored_mazes, size, seed), maze(mine, size, seed)
         assert a[0] == b[0] == 3 * size * (size - 1) + 1
         assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])     # borders left per cell and their neighbours, list order included
         assert np.array_equal(a[4], b[4]) and np.array_equal(a[5], b[5])     # cell centres and bounds, bit for bit

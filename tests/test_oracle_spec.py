@@ -1,5 +1,5 @@
 """CPU: pins the oracle (test infrastructure) against everything the reference gives us for this path:
- * the reference's own RNG helpers compiled in place (oracle/_ref, util.hpp:25-56),
+ * the reference's own RNG helpers compiled in place (oracle/_ref, util.hpp:25-56; their outputs stored in tests/golden/ref_vectors.npz),
  * the C++ standard's mt19937 known answer,
  * the reference's own unit-test vector for getCoords (src/test/src/voxel_grid_tests.cpp:25),
  * spec-derived known answers (SURVEY.md 8c "fixtures the build must create itself"),
@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
+import ref_vectors
 from megaverse_amd.rollout import action_masks, sample_actions
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -26,44 +27,40 @@ def test_mt19937_standard_known_answer():
 
 @pytest.fixture(scope="module")
 def ref():
-    r = oracle_lib.ref_lib()
-    if r is None:
-        pytest.skip("oracle/_ref not built (reference tree absent and no prebuilt .so)")
-    return r
+    """tests/golden/ref_vectors.npz: what the reference's util.hpp / math_utils.hpp return for the inputs of tests/ref_vectors.py; where
+    oracle/_ref is built the stored vectors are first recomputed with it and must be the same bytes"""
+    live = ref_vectors.util_lib()
+    if live is not None:
+        ref_vectors.assert_same_as_stored(ref_vectors.util_vectors(live))
+    return ref_vectors.load()
 
 
-@pytest.mark.parametrize("seed", [0, 1, 42, 12345, 2**31 - 1, 4294967295])
+@pytest.mark.parametrize("seed", ref_vectors.RAND_RANGE_SEEDS)
 def test_rand_range_matches_reference_util_hpp(ref, seed):
-    rng = np.random.default_rng(seed)
-    n = 5000
-    lo = rng.integers(-50, 50, n).astype(np.int32)
-    hi = (lo + rng.integers(1, 2000, n)).astype(np.int32)
-    hi[:50] = lo[:50] + 1                       # range of one value still consumes a draw
-    lo[50:60], hi[50:60] = 0, 1 << 30           # the seeding range (megaverse.cpp:66, env.cpp:61)
-    a, b = np.empty(n, np.int32), np.empty(n, np.int32)
+    lo, hi, b = ref[f"rand_range_{seed}_lo"], ref[f"rand_range_{seed}_hi"], ref[f"rand_range_{seed}"]
+    n = len(lo)
+    assert n == 5000 and (hi[:50] == lo[:50] + 1).all() and (lo[50:60] == 0).all() and (hi[50:60] == 1 << 30).all()
+    a = np.empty(n, np.int32)
     oracle_lib.lib().mvo_rand_range_seq(seed, lo.ctypes.data, hi.ctypes.data, n, a.ctypes.data)
-    ref.mvref_rand_range_seq(seed, lo.ctypes.data, hi.ctypes.data, n, b.ctypes.data)
     assert np.array_equal(a, b)
     assert np.all(a >= lo) and np.all(a < hi)
 
 
-@pytest.mark.parametrize("seed", [0, 7, 42, 99999])
+@pytest.mark.parametrize("seed", ref_vectors.FRAND_SEEDS)
 def test_frand_matches_reference_util_hpp(ref, seed):
-    n = 20000
-    a, b = np.empty(n, np.float32), np.empty(n, np.float32)
+    n = ref_vectors.FRAND_N
+    a, b = np.empty(n, np.float32), ref[f"frand_{seed}"]
     oracle_lib.lib().mvo_frand_seq(seed, n, a.ctypes.data)
-    ref.mvref_frand_seq(seed, n, b.ctypes.data)
     assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
     assert a.min() >= 0.0 and a.max() < 1.0
 
 
 def test_env_seed_rule_matches_reference(ref):
     # MegaverseGym::seed: master mt19937(seed) -> randRange(0, 1<<30) per env (megaverse.cpp:60-69)
-    n = 64
+    n = ref_vectors.ENV_SEEDS_N
     lo, hi = np.zeros(n, np.int32), np.full(n, 1 << 30, np.int32)
-    a, b = np.empty(n, np.int32), np.empty(n, np.int32)
+    a, b = np.empty(n, np.int32), ref["env_seeds_42"]
     oracle_lib.lib().mvo_rand_range_seq(42, lo.ctypes.data, hi.ctypes.data, n, a.ctypes.data)
-    ref.mvref_env_seeds(42, n, b.ctypes.data)
     assert np.array_equal(a, b)
 
 
@@ -71,8 +68,9 @@ def test_triangular_number_matches_reference_math_utils_hpp(ref):
     """boxes an Obstacles wall / step / gap needs (platforms.hpp requiresMovableBoxesToTraverse): the oracle's helper against the
     reference's own util/math_utils.hpp:7-10 compiled in place"""
     L = oracle_lib.lib()
+    assert len(ref["triangular"]) == ref_vectors.TRIANGULAR_N == 40
     for n in range(0, 40):
-        assert L.mvo_triangular_number(n) == ref.mvref_triangular_number(n) == n * (n + 1) // 2
+        assert L.mvo_triangular_number(n) == ref["triangular"][n] == n * (n + 1) // 2
 
 
 def test_action_mask_table():
@@ -328,16 +326,14 @@ def test_level_file_tokeniser_matches_the_reference_split_string():
     util/src/string_utils.cpp:10-25: strtok_r, empty pieces never appear); the oracle's split_tokens against the reference function
     compiled in place"""
     import ctypes as C
-    ref = oracle_lib.ref_lib()
-    if ref is None or not hasattr(ref, "mvref_split_string"):
-        pytest.skip("oracle/_ref/libmv_ref_util.so is built from /root/reference (not present here)")
-    ref.mvref_split_string.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
+    live = ref_vectors.util_lib()
+    if live is not None and hasattr(live, "mvref_split_string"):
+        ref_vectors.assert_same_as_stored(ref_vectors.util_vectors(live), ["split_counts", "split_joined"])
+    z = ref_vectors.load()
     mine = oracle_lib.lib().mvo_split_tokens
     mine.argtypes = [C.c_char_p, C.c_char, C.c_char_p, C.c_int]
-    texts = ["; 0\n##########\n#  @ $ . #\n##########\n\n; 1\n####\n#@$.#\n", "\n\n\nabc\n\n\ndef\n", "no newline at all", "", "\n", "a\r\nb\r\n",
-             "; 3\n" + "#" * 40 + "\n" * 7 + "tail"]
-    for t in texts:
-        a, b = C.create_string_buffer(4096), C.create_string_buffer(4096)
-        na = ref.mvref_split_string(t.encode(), b"\n", a, 4096)
-        nb = mine(t.encode(), b"\n", b, 4096)
-        assert na == nb and a.value == b.value, (t, na, nb, a.value, b.value)
+    assert len(z["split_counts"]) == len(ref_vectors.SPLIT_TEXTS)
+    for t, na, want in zip(ref_vectors.SPLIT_TEXTS, z["split_counts"], z["split_joined"]):
+        b = C.create_string_buffer(ref_vectors.SPLIT_CAP)
+        nb = mine(t.encode(), b"\n", b, ref_vectors.SPLIT_CAP)
+        assert na == nb and want == b.value, (t, na, nb, want, b.value)
