@@ -605,7 +605,7 @@ int mv_close(mv_gym *g)
     g->feeder.reset();   // joins the workers before their slots go away
     GymView &gv = g->gv;
     if (gv.dbg) {   // tick phase timing of an instrumented build.  Per env 64 counters: 0..15 sums over all ticks (0..7 phase cycles, 8..12 cast statistics),
-                    // 16..31 the same of the last tick, 32..47 of the env's longest tick, 48..55 launch lifetimes on the 100 MHz clock (mv_step.hip)
+                    // 16..31 the same of the last tick, 32..47 of the env's longest tick, 48..55 launch lifetimes on the 100 MHz clock (mv_step_kernels.h)
         const int N = g->N;
         std::vector<unsigned long long> h((size_t)N * 64);
         if (hipMemcpy(h.data(), gv.dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -1039,11 +1039,7 @@ int mv_reset(mv_gym *g)
         if (g->lastUpload) HIP_TRY(hipStreamWaitEvent(g->stream, g->lastUpload, 0));
         const OutPtrs outs = last_outputs(g);
         const GymView v = view(g, g->parity, &outs);
-        if (g->scenario == SCN_OBSTACLES || g->scenario == SCN_EMPTY) launch_reset_obstacles(v, (const EpisodeBlob *)g->dBlobs, g->dStatus, 1, g->stream);
-        else if (g->scenario == SCN_REARRANGE) launch_reset_rearrange(v, (const RearrangeBlob *)g->dBlobs, g->dStatus, 1, g->stream);
-        else if (g->scenario == SCN_SOKOBAN) launch_reset_sokoban(v, (const SokobanBlob *)g->dBlobs, g->dStatus, 1, g->stream);
-        else if (g->scenario == SCN_HEX_MEMORY || g->scenario == SCN_HEX_EXPLORE) launch_reset_hex(v, (const HexBlob *)g->dBlobs, g->dStatus, 1, g->stream);
-        else launch_reset_collect(v, (const CollectBlob *)g->dBlobs, g->dStatus, 1, g->stream);
+        launch_reset_episodes(v, 1, g->stream);
         HIP_TRY(hipEventRecord(g->stepDone, g->stream));   // (the reset kernel reads the ring too)
         g->lastStep = g->stepDone;
         if (read_back_status(g, g->stepDone)) return -1;  // the second resident episodes go up with the next steps
@@ -1052,7 +1048,7 @@ int mv_reset(mv_gym *g)
         const OutPtrs outs = last_outputs(g);
         const GymView v = view(g, g->parity, &outs);
         launch_tower_draw(v, g->stream);
-        launch_reset(v, 1, g->stream);
+        launch_reset_episodes(v, 1, g->stream);
         launch_tower_draw(v, g->stream);
     }
     HIP_TRY(hipGetLastError());

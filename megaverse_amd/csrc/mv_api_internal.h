@@ -29,34 +29,19 @@
 #include "mv_union.h"
 
 namespace mv {
-void launch_reset(const GymView &gv, int force_all, hipStream_t stream);
 // TowerBuilding: tops every env's ring of drawn episodes up (mv_reset.hip)
 void launch_tower_draw(const GymView &gv, hipStream_t stream);
 void launch_tower_seed(const GymView &gv, const uint32_t *seeds, hipStream_t stream);   // Env::seed for every env's generator
 // Collect, device-drawn episodes (mv_collect_draw.hip): staging slots of envs[i] -> their ring slots slots[i], one launch per 64 episodes
 void launch_collect_blob_copy(const int32_t *envs, const int32_t *slots, int count, const uint8_t *staging, uint8_t *ring, size_t blob_bytes, int spares,
                               hipStream_t stream);
-// step kernels: one 256-thread workgroup per env = the tick (wave 0) + the frame setup of the env's frames for a W x H observation
-// (render = 0: tick only)
-void launch_step(const GymView &gv, hipStream_t stream, int W, int H, int render, hipEvent_t done = nullptr);
-// k ticks + frame setups of every env, one launch (mv_step.hip)
+// The step and reset kernels of gv's scenario (mv_step.hip).  One tick: one workgroup per env = the tick (wave 0) + the frame setup of the env's frames
+// for a W x H observation (render = 0: tick only); done: an event carried by the launch's dispatch packet (TowerBuilding only) -> whether it was.
+bool launch_step(const GymView &gv, hipStream_t stream, int W, int H, int render, hipEvent_t done = nullptr);
+// k <= 8 ticks + frame setups of every env, one launch (one agent per env; several: TowerBuilding); done: completed by the launch
 void launch_step_ticks(const GymView *views, int k, hipStream_t stream, int W, int H, hipEvent_t done = nullptr);
-void launch_step_obstacles(const GymView &gv, hipStream_t stream, int W, int H, int render);
-// k ticks + frame setups of every env (one agent), one launch
-void launch_step_obstacles_ticks(const GymView *views, int k, hipStream_t stream, int W, int H, hipEvent_t done = nullptr);
-void launch_step_rearrange_ticks(const GymView *views, int k, hipStream_t stream, int W, int H, hipEvent_t done = nullptr);
-void launch_step_sokoban_ticks(const GymView *views, int k, hipStream_t stream, int W, int H, hipEvent_t done = nullptr);
-void launch_step_collect_ticks(const GymView *views, int k, hipStream_t stream, int W, int H, hipEvent_t done = nullptr);
-void launch_step_hex_ticks(const GymView *views, int k, hipStream_t stream, int W, int H, hipEvent_t done = nullptr);
-void launch_reset_obstacles(const GymView &gv, const EpisodeBlob *blobs, int *status, int force_all, hipStream_t stream);
-void launch_step_rearrange(const GymView &gv, hipStream_t stream, int W, int H, int render);
-void launch_reset_rearrange(const GymView &gv, const RearrangeBlob *blobs, int *status, int force_all, hipStream_t stream);
-void launch_step_collect(const GymView &gv, hipStream_t stream, int W, int H, int render);
-void launch_step_sokoban(const GymView &gv, hipStream_t stream, int W, int H, int render);
-void launch_reset_sokoban(const GymView &gv, const SokobanBlob *blobs, int *status, int force_all, hipStream_t stream);
-void launch_reset_collect(const GymView &gv, const CollectBlob *blobs, int *status, int force_all, hipStream_t stream);
-void launch_step_hex(const GymView &gv, hipStream_t stream, int W, int H, int render);
-void launch_reset_hex(const GymView &gv, const HexBlob *blobs, int *status, int force_all, hipStream_t stream);
+// every finished (force_all: every) env swaps its next resident episode in
+void launch_reset_episodes(const GymView &gv, int force_all, hipStream_t stream);
 }  // namespace mv
 
 using namespace mv;

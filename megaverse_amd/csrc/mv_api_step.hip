@@ -5,18 +5,6 @@
 
 extern "C" {
 
-// -> whether `done` rides on the launch (TowerBuilding's launcher); otherwise the caller records it
-static bool launch_step_of(const mv_gym *g, const GymView &v, hipStream_t sim, int fused, hipEvent_t done = nullptr)
-{
-    if (g->scenario == SCN_OBSTACLES || g->scenario == SCN_EMPTY) launch_step_obstacles(v, sim, g->w, g->h, fused);
-    else if (g->scenario == SCN_COLLECT) launch_step_collect(v, sim, g->w, g->h, fused);
-    else if (g->scenario == SCN_REARRANGE) launch_step_rearrange(v, sim, g->w, g->h, fused);
-    else if (g->scenario == SCN_SOKOBAN) launch_step_sokoban(v, sim, g->w, g->h, fused);
-    else if (g->scenario == SCN_HEX_MEMORY || g->scenario == SCN_HEX_EXPLORE) launch_step_hex(v, sim, g->w, g->h, fused);
-    else { launch_step(v, sim, g->w, g->h, fused, done); return done != nullptr; }
-    return false;
-}
-
 // One stepping call = k ticks (mv_step: 1; mv_step_n: up to `batch`) of n gyms that share one pair of streams (n = 1: a gym on its own;
 // n > 1: an mv_group, stepped by union launches).  gs[0] is the leader: the stream state that changes with every call -- marks, which stream
 // the last step ran on -- is kept on it and mirrored to the others.  policy != POLICY_NONE: tick j draws its actions inside the step kernel
@@ -100,7 +88,6 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     // One TowerBuilding gym, several rendered ticks with device-drawn actions, nothing timed per tick: ONE step launch runs the k ticks of every
     // env (launch_step_ticks; MV_STEP_TICKS=0: k launches).  Its views are collected in the loop below.
     static const bool ticksOff = getenv("MV_STEP_TICKS") && atoi(getenv("MV_STEP_TICKS")) == 0;
-    const bool obstFamily = L->scenario == SCN_OBSTACLES || L->scenario == SCN_EMPTY;
     // (every scenario with one agent per env; several agents: TowerBuilding only -- two waves per env, launch_step_ticks)
     const bool canMultiTick = !ticksOff && n == 1 && (L->A == 1 || L->scenario == SCN_TOWER) && k >= 2
                                                       && k <= MAX_STEP_TICKS && render && policy != POLICY_NONE && !L->gv.dbg;
@@ -174,19 +161,14 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
                     const int kk = std::min(chunkTicks, k - j0);
                     const GymView *vw = views.data() + j0;
                     hipEvent_t r = j0 + kk == k ? rides : nullptr;
-                    if (obstFamily) launch_step_obstacles_ticks(vw, kk, sim, L->w, L->h, r);
-                    else if (L->scenario == SCN_REARRANGE) launch_step_rearrange_ticks(vw, kk, sim, L->w, L->h, r);
-                    else if (L->scenario == SCN_SOKOBAN) launch_step_sokoban_ticks(vw, kk, sim, L->w, L->h, r);
-                    else if (L->scenario == SCN_COLLECT) launch_step_collect_ticks(vw, kk, sim, L->w, L->h, r);
-                    else if (L->scenario == SCN_HEX_MEMORY || L->scenario == SCN_HEX_EXPLORE) launch_step_hex_ticks(vw, kk, sim, L->w, L->h, r);
-                    else launch_step_ticks(vw, kk, sim, L->w, L->h, r);
+                    launch_step_ticks(vw, kk, sim, L->w, L->h, r);
                 }
                 if (callEv) HIP_TRY(hipEventRecord(callEv[1], sim));
                 simDoneRides = rides != nullptr;
             }
         } else if (n == 1) {
             hipEvent_t rides = j == k - 1 && !evs[j] ? (own ? L->simDone : sideWaits ? L->stepDone : nullptr) : nullptr;
-            const bool rode = launch_step_of(L, views[(size_t)j * n], sim, fused, rides);
+            const bool rode = launch_step(views[(size_t)j * n], sim, L->w, L->h, fused, rides);
             simDoneRides = rode && own;
             stepDoneRodeAlong = rode && !own;
         }

@@ -19,7 +19,7 @@ namespace {
 #ifndef MV_STEP_THREADS
 #define MV_STEP_THREADS 128
 #endif
-constexpr int STEP_THREADS = MV_STEP_THREADS;   // workgroup size of the fused step + frame setup kernels (see mv_step.hip)
+constexpr int STEP_THREADS = MV_STEP_THREADS;   // workgroup size of the fused step + frame setup kernels (see mv_step_kernels.h)
 
 constexpr float TAN_HALF_FOV = 1.19175359f;                       // tan(100deg / 2), env_renderer.hpp:36
 constexpr float TAN_HALF_FOV_Y = 1.19175359f / (128.0f / 72.0f);  // aspect 128/72 is baked into the projection
@@ -204,7 +204,7 @@ __device__ __forceinline__ int depth_class(float d)   // d >= NEAR_Z: 0 .. 63, f
 }
 __device__ __forceinline__ float depth_class_floor(int c) { return __uint_as_float((unsigned)(c + (120 << 2)) << 21); }
 
-// PIPE (the software-pipelined multi-tick step kernels, mv_step.hip: step_ticks_pipe_kernel): this wave sets tick j's frame up WHILE the env's tick wave
+// PIPE (the software-pipelined multi-tick step kernels, mv_step_kernels.h: step_ticks_pipe_body): this wave sets tick j's frame up WHILE the env's tick wave
 // computes tick j + 1; everything read from the simulator state (header, agents, box / object / reward records) is loaded before one workgroup
 // barrier -- in the last round of slots, behind its record loads --, which the tick wave meets before it writes tick j + 1's state back.
 template <int THREADS, bool WAVE_LOCAL, bool PIPE = false>

@@ -1,0 +1,176 @@
+// megaverse_amd/csrc/mv_step_kernels.h -- the bodies of the step and reset kernels, shared by every scenario.
+// A scenario's tick lives in its mv_tick_<scenario>.h, together with a small trait S the bodies are instantiated on:
+//   S::tick<A_MAX>(gv, env[, pipe_wait])   the tick (pipe_wait: scenarios with a software-pipelined kernel only)
+//   S::swap_in(gv, env, force_all)         the episode swap-in of a finished (or forced) env
+//   S::long_lists                          frame lists long enough for the depth sort (mv_frame.h: DepthSortScratch)
+//   S::par_agents                          several agents: every wave of the workgroup takes part in the tick (TowerBuilding)
+// Every __global__ is a one-line entry point over a body in its scenario's mv_step_<scenario>.hip (a launch bound that depends on a template
+// parameter is not applied, and the profiles name the kernels); StepKernels lists them for the launchers (mv_step.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "mv_frame.h"
+#include "mv_types.h"
+
+// the register budget of the one-wave-per-env multi-tick kernels (512 / n VGPRs).  Their waves stay resident for a whole batched call beside the
+// observation passes, and what they hold the passes cannot have: left to itself hipcc takes 236 VGPRs for the TowerBuilding tick (launch bound 64:
+// nothing asks it to be frugal), the one-launch-per-tick kernel does the same work in 97.
+#ifndef MV_STEP_TICKS_WAVES_PER_SIMD
+#define MV_STEP_TICKS_WAVES_PER_SIMD 4
+#endif
+
+namespace mv {
+
+// the depth sort's LDS (N per workgroup), declared only in the instantiations of scenarios with long lists: LDS size sets occupancy
+template <class S, int N>
+__device__ __forceinline__ DepthSortScratch *depth_sort_scratch(int i)
+{
+    if constexpr (S::long_lists) {
+        __shared__ DepthSortScratch s_ds[N];
+        return &s_ds[i];
+    } else {
+        return nullptr;
+    }
+}
+
+// One workgroup per env: wave 0 runs the tick (one wave per env: physics, scenario logic, auto-reset), the others wait at the barrier (S::par_agents:
+// they take their share of the character controllers first); then the workgroup builds the lists of the env's frames (mv_frame.h).  `render` = 0:
+// mv_step_no_render.
+//   one agent:  STEP_THREADS (128) threads work on the env's one frame together.  The tick needs ~150 VGPRs, i.e. 3 waves per SIMD: with
+//               2 waves per env 1024 envs are resident at once (with 4 they take two rounds, and a launch lasts as long as its slowest
+//               tick PER ROUND: measured 41 us vs 25 us);
+//   A agents:   64 min(A, 4) threads, every wave sets up its own frame(s): a frame setup is a chain of dependent loads (~6 us), A of them
+//               one after the other would cost more than the launch the fusion saves.
+template <class S, int A_MAX>
+__device__ __forceinline__ void step_body(const GymView &gv, const int env, int W, int H, int render)
+{
+    constexpr int NS = A_MAX == 1 ? 1 : 4;
+    __shared__ FrameScratch s_fs[NS];
+#ifdef MV_STEP_PRIO
+    __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
+#endif
+    MV_T_BEGIN
+#ifdef MV_TICK_TIMING
+    const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();   // 100 MHz
+#endif
+    if constexpr (S::par_agents && A_MAX > 1) S::template tick<A_MAX, true>(gv, env);
+    else if (threadIdx.x < 64) S::template tick<A_MAX>(gv, env);
+#ifdef MV_TICK_TIMING
+    if (!render && gv.dbg && threadIdx.x == 0) {
+        const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
+        unsigned long long *d = gv.dbg + (size_t)env * 64;
+        d[48] += rt1 - rt0; d[49] += 1; d[50] = rt0; d[51] = rt1;
+        // (tick-only launches: 52..55 = ticks that regenerated the env, longest other tick)
+        if (gv.hdr[env].num_frames == 0) { d[52] += rt1 - rt0; d[53] += 1; }
+        else if (rt1 - rt0 > d[54]) { d[54] = rt1 - rt0; for (int k = 0; k < 16; ++k) d[32 + k] = d[16 + k]; }
+    }
+#endif
+    if (!render) return;
+    __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
+    MV_T(6);           // the whole tick as wave 0 saw it (incl. the generator of a finished env), up to the barrier
+    if constexpr (A_MAX == 1) {
+        frame_setup_body<STEP_THREADS, false>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
+        MV_T(7);   // frame setup
+#ifdef MV_TICK_TIMING
+        if (gv.dbg && threadIdx.x == 0) {
+            const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
+            unsigned long long *d = gv.dbg + (size_t)env * 64;
+            if (!d[49]) { d[52] += rt1 - rt0; d[53] += 1; d[54] = rt0; d[55] = rt1; }
+        }
+#endif
+    } else {
+        const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+        for (int a = wave; a < A; a += nw) frame_setup_body<64, true>(gv, env * A + a, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
+    }
+}
+
+// k consecutive ticks of every env with ONE launch (a batched open-loop call, mv_step_n with a device-side random policy): the envs are
+// independent and every tick draws its own actions, so nothing orders env A's tick j + 1 behind env B's tick j -- only k launches did, each as
+// long as its slowest env, and each having to find room for 1024 two-wave workgroups of ~150 VGPRs beside the observation pass of the previous
+// call (kernel traces, r04l: 70-190 us per step kernel while a pass runs, 20 us alone; the chain of step kernels, not the pass, set the pipelined
+// rate).  Here an env's workgroup becomes resident once and runs tick, frame setup (into slot j's lists), tick, ...: gv[j] is tick j's view
+// (its hand-over slot, its staging outputs, its action index, its cost histogram).  The frame setups of such a launch do not clear the next pass's
+// histogram (lpt_no_clear: inside one launch env 0's clearing would race with the envs that are a tick ahead): every pass that draws from one clears it
+// when its last workgroup has looked its frame up (mv_raster.hip: hist_done; mv_api.hip: take_hist).  An env that finishes swaps its next resident
+// episode in at the tail of its tick as always -- a batched call only ever spans ticks of gyms whose episodes are long (mv_step_n steps the others
+// tick by tick), so the resident episodes outlast it.
+// One agent: ONE wave per env (the single-tick kernel's second wave only helps with the frame setup, and idles through the tick): the
+// workgroups stay resident for the whole call beside the observation passes of the previous one, and every wave of ~150 VGPRs they hold is
+// two or three waves the pass cannot have (measured: 21.1 M obs/s with two waves per env, 22.3 M with one).
+// Several agents (S::par_agents): every wave of the workgroup ticks, then sets up its share of the env's frames.
+template <class S, int A_MAX, class Args>
+__device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
+{
+    constexpr int NS = A_MAX == 1 ? 1 : 4;
+    __shared__ FrameScratch s_fs[NS];
+    const int env = blockIdx.x;
+#ifdef MV_STEP_PRIO
+    __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
+#endif
+    for (int j = 0; j < a.n; ++j) {
+        const GymView &gv = a.view(j);
+        if constexpr (A_MAX == 1) {
+            S::template tick<1>(gv, env);
+            wave_sync();   // the tick's stores before the frame setup's loads (one wave: no barrier needed)
+            frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
+        } else {
+            S::template tick<A_MAX, true>(gv, env);
+            __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
+            const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+            for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
+            __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
+        }
+    }
+}
+
+// Software-pipelined (one agent per env): TWO waves per env.  Wave 0 runs tick j + 1 while wave 1 sets tick j's frame up (mv_frame.h) -- the two halves of a
+// tick's work that step_ticks_body runs back to back in one wave, each a chain of dependent loads and a few thousand vector instructions of ONE wave on its
+// SIMD (48 % of the resident wave's cycles were spent in s_waitcnt, r08z_pmc_SQ2.csv).  The frame setup reads the simulator state in place, so the two waves
+// meet at two workgroup barriers per tick:
+//   A(j): tick j's state is written (wave 0: behind its write-back and the episode swap-in of a finished env; wave 1: before it reads anything)
+//   B(j): tick j's state is read    (wave 1: behind the record loads of its last round of slots; wave 0: before tick j + 1's write-back, the tick's
+// pipe_wait) An iteration lasts max(tick, frame setup) instead of their sum; the last frame setup runs alone.
+template <class S, class Args>
+__device__ __forceinline__ void step_ticks_pipe_body(const Args &a, int W, int H)
+{
+    __shared__ FrameScratch s_fs;
+    const int env = blockIdx.x;
+#ifdef MV_STEP_PRIO
+    __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
+#endif
+    if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0) {
+        for (int j = 0; j < a.n; ++j) {
+            S::template tick<1>(a.view(j), env, j > 0);   // (j > 0: B(j - 1) inside, before the write-back)
+            __syncthreads();                              // A(j)
+        }
+        __syncthreads();                                  // B(n - 1): the last frame setup's
+    } else {
+        for (int j = 0; j < a.n; ++j) {
+            __syncthreads();                              // A(j)
+            frame_setup_body<64, true, true>(a.view(j), env, W, H, s_fs);   // B(j) inside
+        }
+    }
+}
+
+// mv_reset / the refill of a forced reset: every finished (force_all: every) env takes its next resident episode
+template <class S>
+__device__ __forceinline__ void reset_body(const GymView &gv, int force_all)
+{
+    const int env = blockIdx.x;
+    if (env >= gv.num_envs) return;
+    if (!force_all && !gv.hdr[env].done) return;
+    S::swap_in(gv, env, force_all);
+}
+
+// one scenario's entry points (its mv_step_<scenario>.hip); null: the scenario has no such kernel
+struct StepKernels {
+    void (*step)(GymView, int, int, int);                // one agent per env
+    void (*step_agents)(GymView, int, int, int);         // several (agent loops are real loops: one multi-agent build)
+    void (*ticks)(StepTicksArgs8, int, int);             // k ticks, one agent per env
+    void (*ticks_pipe)(StepTicksArgs8, int, int);        // ... software-pipelined
+    void (*ticks_agents)(StepTicksArgs8, int, int);      // k ticks, several agents per env
+    void (*reset)(GymView, int);
+};
+extern const StepKernels tower_kernels, obstacles_kernels, collect_kernels, rearrange_kernels, sokoban_kernels, hex_kernels;
+
+}  // namespace mv

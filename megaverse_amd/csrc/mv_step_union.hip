@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "mv_step_kernels.h"
 #include "mv_tick_collect.h"
 #include "mv_tick_hex.h"
 #include "mv_tick_obstacles.h"
@@ -24,38 +25,43 @@
 
 namespace mv {
 
+// the tick of gv's scenario (uniform per workgroup), as its own step kernels run it on wave 0
 template <int A_MAX>
-__global__ __launch_bounds__(256) void step_union_kernel(UnionStepArgs ua, int W, int H, int render)
+__device__ __forceinline__ void tick_any(const GymView &gv, const int env)
 {
-    __shared__ FrameScratch s_fs[A_MAX == 1 ? 1 : 4];
-    __shared__ DepthSortScratch s_ds[A_MAX == 1 ? 1 : 4];   // (long lists: mv_frame.h)
+    switch (gv.scenario) {
+    case SCN_TOWER: tick_tower::Scenario::tick<A_MAX>(gv, env); break;
+    case SCN_OBSTACLES:
+    case SCN_EMPTY: tick_obstacles::Scenario::tick<A_MAX>(gv, env); break;
+    case SCN_COLLECT: tick_collect::Scenario::tick<A_MAX>(gv, env); break;
+    case SCN_REARRANGE: tick_rearrange::Scenario::tick<A_MAX>(gv, env); break;
+    case SCN_SOKOBAN: tick_sokoban::Scenario::tick<A_MAX>(gv, env); break;
+    default: tick_hex::Scenario::tick<A_MAX>(gv, env); break;   // SCN_HEX_MEMORY, SCN_HEX_EXPLORE
+    }
+}
+// the union kernels' trait (mv_step_kernels.h): any scenario's tick on wave 0, the long lists' LDS
+struct AnyScenario {
+    static constexpr bool long_lists = true, par_agents = false;
+    template <int A_MAX> __device__ __forceinline__ static void tick(const GymView &gv, int env) { tick_any<A_MAX>(gv, env); }
+};
+
+__device__ __forceinline__ int union_gym(const int32_t *first, int n)   // the gym workgroup blockIdx.x belongs to
+{
     int s = 0;
 #pragma unroll
     for (int i = 1; i < MAX_UNION; ++i)
-        if (i < ua.n && (int)blockIdx.x >= ua.first[i]) s = i;
-    const GymView &gv = ua.gv[s];
-    const int env = (int)blockIdx.x - ua.first[s];
-    if (threadIdx.x < 64) {
-        switch (gv.scenario) {   // (uniform per workgroup)
-        case SCN_TOWER: tick_tower::tower_tick<A_MAX>(gv, env); break;
-        case SCN_OBSTACLES:
-        case SCN_EMPTY: tick_obstacles::obstacles_tick<A_MAX>(gv, env); break;
-        case SCN_COLLECT: tick_collect::collect_tick<A_MAX>(gv, env); break;
-        case SCN_REARRANGE: tick_rearrange::rearrange_tick<A_MAX>(gv, env); break;
-        case SCN_SOKOBAN: tick_sokoban::sokoban_tick<A_MAX>(gv, env); break;
-        default: tick_hex::hex_tick<A_MAX>(gv, env); break;   // SCN_HEX_MEMORY, SCN_HEX_EXPLORE
-        }
-    }
-    if (!render) return;
-    __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
-    if (A_MAX == 1) frame_setup_body<STEP_THREADS, false>(gv, env, W, H, s_fs[0], &s_ds[0]);
-    else {
-        const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
-        for (int a = wave; a < A; a += nw) frame_setup_body<64, true>(gv, env * A + a, W, H, s_fs[wave], &s_ds[wave]);
-    }
+        if (i < n && (int)blockIdx.x >= first[i]) s = i;
+    return s;
 }
 
-// k ticks of every env of every gym of the group, the env's workgroup resident for the whole call (cf. mv_step.hip: step_ticks_kernel): tick, frame setup
+template <int A_MAX>
+__global__ __launch_bounds__(256) void step_union_kernel(UnionStepArgs ua, int W, int H, int render)
+{
+    const int s = union_gym(ua.first, ua.n);
+    step_body<AnyScenario, A_MAX>(ua.gv[s], (int)blockIdx.x - ua.first[s], W, H, render);
+}
+
+// k ticks of every env of every gym of the group, the env's workgroup resident for the whole call (cf. mv_step_kernels.h: step_ticks_body): tick, frame setup
 // into tick j's slot, tick, ...  Built for the register budget of the other resident multi-tick kernels (they run beside the observation passes of the
 // previous call, and what they hold the passes cannot have).
 // One wave per env -- except for the gyms with long frame lists (Collect, Hex*: up to 2048 visible primitives): their frame setup is most of their tick, one
@@ -71,27 +77,14 @@ __global__ __launch_bounds__(64 * WAVES, MV_UNION_TICKS_WAVES_PER_SIMD) void ste
 {
     __shared__ FrameScratch s_fs;
     __shared__ DepthSortScratch s_ds;
-    int s = 0;
-#pragma unroll
-    for (int i = 1; i < MAX_UNION; ++i)
-        if (i < ua.n && (int)blockIdx.x >= ua.first[i]) s = i;
+    const int s = union_gym(ua.first, ua.n);
     const int env = (int)blockIdx.x - ua.first[s];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const bool wide = WAVES > 1 && ua.gv[s].vis_stride > VIS_SMALL;   // (uniform over the workgroup)
     if (!wide && wave > 0) return;
     for (int j = 0; j < ua.k; ++j) {
         const GymView gv = tick_view(ua.gv[s], ua.slot_stride[s], j);
-        if (wave == 0) {
-            switch (gv.scenario) {   // (uniform per workgroup)
-            case SCN_TOWER: tick_tower::tower_tick<1>(gv, env); break;
-            case SCN_OBSTACLES:
-            case SCN_EMPTY: tick_obstacles::obstacles_tick<1>(gv, env); break;
-            case SCN_COLLECT: tick_collect::collect_tick<1>(gv, env); break;
-            case SCN_REARRANGE: tick_rearrange::rearrange_tick<1>(gv, env); break;
-            case SCN_SOKOBAN: tick_sokoban::sokoban_tick<1>(gv, env); break;
-            default: tick_hex::hex_tick<1>(gv, env); break;   // SCN_HEX_MEMORY, SCN_HEX_EXPLORE
-            }
-        }
+        if (wave == 0) tick_any<1>(gv, env);
         if (wide) {
             __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
             // (ends with a barrier: the next tick starts when every wave is done with the state)

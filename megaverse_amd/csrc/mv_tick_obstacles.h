@@ -353,5 +353,16 @@ __device__ __forceinline__ void obstacles_tick(const GymView &gv, const int env,
     }
 }
 
+// the step and reset kernels' view of the scenario (mv_step_kernels.h)
+struct Scenario {
+    static constexpr bool long_lists = false, par_agents = false;
+    template <int A_MAX>
+    __device__ __forceinline__ static void tick(const GymView &gv, int env, int pipe_wait = 0) { obstacles_tick<A_MAX>(gv, env, pipe_wait); }
+    __device__ __forceinline__ static void swap_in(const GymView &gv, int env, int force_all)
+    {
+        swap_in_episode(gv, static_cast<const EpisodeBlob *>(gv.blobs), gv.episode_status, env, force_all);
+    }
+};
+
 }  // namespace tick_obstacles
 }  // namespace mv

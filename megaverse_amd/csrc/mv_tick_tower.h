@@ -15,7 +15,7 @@
 //   FallDetectionComponent::step                scenarios/include/scenarios/component_fall_detection.hpp:33-55
 //   TowerBuildingScenario::step + callbacks     scenarios/src/scenario_tower_building.cpp:179-261
 //   Scenario::rewardAgent/rewardTeam            env/include/env/scenario.hpp:259-298
-//   done bookkeeping of VectorEnv::step         env/src/vector_env.cpp:93-105 (the reset itself: mv_reset.hip)
+//   done bookkeeping of VectorEnv::step         env/src/vector_env.cpp:93-105 (the reset itself: reset_kernel)
 //
 // Mapping: ONE WAVEFRONT PER ENV.  The env's colliders (<=16 layout slabs, <=80 movable boxes,
 // <=8 agent capsules) live in VGPRs, two per lane.  A sweep is "every lane casts against its two
@@ -102,7 +102,7 @@ __device__ __forceinline__ void voxel_of(V3 p, int out[3])
 __device__ __forceinline__ bool in_chunk(int x, int y, int z) { return x >= 0 && x < CX && y >= 0 && y < CY && z >= 0 && z < CZ; }
 
 
-// PAR (A_MAX > 1, mv_step.hip): called by ALL waves of the env's workgroup.  The controllers of one env run in action order because agents collide
+// PAR (A_MAX > 1, mv_step_kernels.h): called by ALL waves of the env's workgroup.  The controllers of one env run in action order because agents collide
 // with each other (env.cpp:126) -- but two agents that cannot come within a capsule's width of each other this tick do not care about the order, nor
 // about each other's position at all.  With PAR the waves share the agents out:
 //   * an agent with a neighbour inside (its and the neighbour's speed) x dt + a capsule's width + 0.5 is "near": the near agents run one after the
@@ -113,7 +113,7 @@ __device__ __forceinline__ bool in_chunk(int x, int y, int z) { return x >= 0 &&
 //     sweeps or depenetration, so the results ARE the sequential loop's.  Should a pair fail (a depenetration push longer than the margin), the
 //     env's agents are restored and stepped again in a row.
 // A launch lasts as long as its slowest env: that used to be A controllers in a row, now the env with the largest group of near agents.
-// pipe_wait (wave-uniform; the software-pipelined multi-tick kernel, mv_step.hip: step_ticks_pipe_kernel): the env's second wave is still reading the
+// pipe_wait (wave-uniform; the software-pipelined multi-tick kernel, mv_step_kernels.h: step_ticks_pipe_body): the env's second wave is still reading the
 // state of the previous tick for that tick's frame setup -- this tick computes beside it and meets it at a workgroup barrier before it writes anything
 // the frame setup reads (objects, header, agents; the chunk is the tick's alone).
 template <int A_MAX, bool PAR = false>
@@ -432,6 +432,14 @@ __device__ __forceinline__ void tower_tick(const GymView &gv, const int env, con
     }
 #endif
 }
+
+// the step and reset kernels' view of the scenario (mv_step_kernels.h)
+struct Scenario {
+    static constexpr bool long_lists = false, par_agents = true;
+    template <int A_MAX, bool PAR = false>
+    __device__ __forceinline__ static void tick(const GymView &gv, int env, int pipe_wait = 0) { tower_tick<A_MAX, PAR>(gv, env, pipe_wait); }
+    __device__ __forceinline__ static void swap_in(const GymView &gv, int env, int force_all) { (void)tower_swap_in(gv, env, force_all); }
+};
 
 }  // namespace tick_tower
 }  // namespace mv
