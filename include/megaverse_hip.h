@@ -206,6 +206,8 @@ int mv_debug_set_agent_yaw(mv_gym *g, int32_t env_idx, int32_t agent_idx, float 
 int mv_debug_set_agent_velocity(mv_gym *g, int32_t env_idx, int32_t agent_idx, float hvx, float hvz, float vvel);
 int mv_debug_snapshot_size(const mv_gym *g);
 int mv_debug_snapshot(mv_gym *g, int32_t env_idx, void *out_host);
+/* BoxAGone: env env_idx's platform table, temporary ring, timers and cell map (BoxAGoneState, mv_types.h); out_host == NULL: its size */
+int mv_debug_boxagone_state(mv_gym *g, int32_t env_idx, void *out_host);
 int mv_debug_rng(int32_t device, uint32_t seed, int32_t what, const int32_t *lo, const int32_t *hi, int32_t n, void *out_host);
 int mv_debug_math(int32_t device, int32_t what, const float *a, const float *b, int32_t n, float *out_host);
 /* Host-only (no device): the n-th (1-based) episode an env seeded with env_seed generates for a host-generated

@@ -34,6 +34,9 @@ static const char *SHAPING_KEYS_HEX_EXPLORE[2] = {"teamSpirit", "exploreSolved"}
 static const float SHAPING_DEFAULT_HEX_EXPLORE[2] = {0.0f, 5.0f};
 static const char *SHAPING_KEYS_COLLECT[5] = {"teamSpirit", "collectSingleGood", "collectSingleBad", "collectAll", "collectAbyss"};
 static const float SHAPING_DEFAULT_COLLECT[5] = {0.0f, 1.0f, -1.0f, 5.0f, -0.5f};
+// scenario_box_a_gone.hpp:92-98 (+ teamSpirit 0)
+static const char *SHAPING_KEYS_BOXAGONE[3] = {"teamSpirit", "boxagoneTouchedFloor", "boxagonePerStepReward"};
+static const float SHAPING_DEFAULT_BOXAGONE[3] = {0.0f, -0.1f, 0.01f};
 static const int ACTION_SPACE[6] = {3, 3, 3, 2, 2, 3};                          // env.cpp:33
 
 // ------------------------------------------------------------------------------------------------
@@ -221,6 +224,7 @@ bool scenario_from_name(const std::string &scen, int &scenario, ObstacleConfig &
     else if (scen == "empty") scenario = SCN_EMPTY;                                    // scenarios/init.hpp:34
     else if (scen == "hexmemory") scenario = SCN_HEX_MEMORY;                           // scenarios/init.hpp:47
     else if (scen == "hexexplore") scenario = SCN_HEX_EXPLORE;                         // scenarios/init.hpp:48
+    else if (scen == "boxagone") scenario = SCN_BOXAGONE;                              // scenarios/init.hpp:50
     else return false;
     return true;
 }
@@ -281,7 +285,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     if (!scenario_from_name(scen, scenario, oc))
         return fail("Unknown scenario " + scen
                     + " (this build accelerates: TowerBuilding, ObstaclesEasy/Medium/Hard/Walls/Steps/Lava, Collect, Rearrange, Sokoban, HexMemory, "
-                         "HexExplore, Empty)");
+                         "HexExplore, BoxAGone, Empty)");
     std::vector<std::string> levelFiles;
     if (scenario == SCN_SOKOBAN) {   // SokobanScenario's constructor looks the level files up (scenario_sokoban.cpp:40-78); none is fatal there too
         levelFiles = find_boxoban_level_files();
@@ -305,12 +309,12 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     g->w = cfg->obs_width; g->h = cfg->obs_height;
     g->N = cfg->num_envs; g->A = cfg->num_agents_per_env;
     g->scenario = scenario;
-    g->numShaping = scenario == SCN_TOWER || scenario == SCN_SOKOBAN ? 4 : scenario == SCN_REARRANGE || scenario == SCN_HEX_MEMORY ? 3
+    g->numShaping = scenario == SCN_TOWER || scenario == SCN_SOKOBAN ? 4 : scenario == SCN_REARRANGE || scenario == SCN_HEX_MEMORY || scenario == SCN_BOXAGONE ? 3
                   : scenario == SCN_HEX_EXPLORE ? 2 : scenario == SCN_EMPTY ? 1 : 5;
     g->shapingKeys = scenario == SCN_TOWER ? SHAPING_KEYS_TOWER : scenario == SCN_OBSTACLES ? SHAPING_KEYS_OBST
                    : scenario == SCN_COLLECT ? SHAPING_KEYS_COLLECT : scenario == SCN_SOKOBAN ? SHAPING_KEYS_SOKOBAN
                    : scenario == SCN_HEX_MEMORY ? SHAPING_KEYS_HEX_MEMORY : scenario == SCN_HEX_EXPLORE ? SHAPING_KEYS_HEX_EXPLORE
-                   : scenario == SCN_EMPTY ? SHAPING_KEYS_EMPTY : SHAPING_KEYS_REARRANGE;
+                   : scenario == SCN_EMPTY ? SHAPING_KEYS_EMPTY : scenario == SCN_BOXAGONE ? SHAPING_KEYS_BOXAGONE : SHAPING_KEYS_REARRANGE;
     // Resident episodes per env: two where an episode ends at its time limit only (TowerBuilding, Empty); THREE where a goal can end it early (the exit pad,
     // every diamond collected, the level solved, the arrangement matched, the maze's target found): the host's run-ahead is bounded in TICKS (refill_episodes),
     // the status words are read back every 16th, and a lucky env can finish twice inside that window -- a third resident episode covers it where two starved
@@ -327,13 +331,13 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     gv.num_envs = g->N; gv.num_agents = g->A;
     const bool obstacles = scenario == SCN_OBSTACLES || scenario == SCN_EMPTY, collect = scenario == SCN_COLLECT,
             rearrange = scenario == SCN_REARRANGE, sokoban = scenario == SCN_SOKOBAN;
-    const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE;
-    const bool hostEpisodes = obstacles || collect || rearrange || sokoban || hex;
+    const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE, boxagone = scenario == SCN_BOXAGONE;
+    const bool hostEpisodes = obstacles || collect || rearrange || sokoban || hex || boxagone;
     gv.scenario = scenario;
     gv.box_stride = collect ? COLLECT_MAX_BOXES : MAX_BOXES;
     gv.reward_stride = collect ? COLLECT_MAX_REWARDS : MAX_REWARDS;
     g->blobBytes = collect ? sizeof(CollectBlob) : obstacles ? sizeof(EpisodeBlob) : rearrange ? sizeof(RearrangeBlob)
-                                    : sokoban ? sizeof(SokobanBlob) : hex ? sizeof(HexBlob) : sizeof(TowerBlob);
+                                    : sokoban ? sizeof(SokobanBlob) : hex ? sizeof(HexBlob) : boxagone ? sizeof(BoxAGoneBlob) : sizeof(TowerBlob);
     // ONE arena for all simulator state: a step touches ~8 arrays per env, separate small allocations
     // cost a TLB miss each per wave (measured: 83 % of the physics kernel's time was spent waiting on
     // ~30 memory operations); one large allocation is backed by large pages.
@@ -347,10 +351,11 @@ int mv_create(const mv_config *cfg, mv_gym **out)
                  szRewObj = hostEpisodes ? up(N * (size_t)gv.reward_stride * sizeof(MovableObject)) : 0,
                  szHeight = collect ? up(N * (size_t)HM_BYTES) : 0, szItems = rearrange ? up(N * MAX_ITEMS * sizeof(ArrangementItem))
                                          : 0, szCells = sokoban ? up(N * (size_t)(SOKO_DIM * SOKO_DIM)) : 0,
-                 szHexB = hex ? up(N * (size_t)HEX_MAX_BOXES * sizeof(HexRec)) : 0, szHexO = hex ? up(N * (size_t)HEX_MAX_OBJS * sizeof(HexRec)) : 0,
+                 szHexB = hex || boxagone ? up(N * (size_t)HEX_MAX_BOXES * sizeof(HexRec)) : 0, szHexO = hex ? up(N * (size_t)HEX_MAX_OBJS * sizeof(HexRec)) : 0,
+                 szBag = boxagone ? up(N * sizeof(BoxAGoneState)) : 0,
                                    szBlobs = up(N * g->blobBytes * (size_t)g->spares), szCnt = up((N + 2) * sizeof(int32_t)),
                                                 szGen = hostEpisodes ? 0 : up(N * sizeof(TowerGen));
-    gv.vis_stride = hex ? 2048 : collect ? 1024 : 256;
+    gv.vis_stride = hex ? 2048 : collect || boxagone ? 1024 : 256;   // (BoxAGone: <= 8 + 972 + 24 boxes, all in the world frame)
     if (const char *e = getenv("MV_DEBUG_VIS_STRIDE")) gv.vis_stride = std::min(gv.vis_stride, std::max(8, atoi(e)));   // (tests: provoke ST_VISIBLE)
     gv.debug_redo = getenv("MV_DEBUG_FORCE_REDO") && atoi(getenv("MV_DEBUG_FORCE_REDO")) ? 1 : 0;   // (tests: mv_tick_tower.h's sequential redo)
     gv.spares = g->spares;
@@ -378,7 +383,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     const bool depthSortOn = !(getenv("MV_DEPTH_SORT") && atoi(getenv("MV_DEPTH_SORT")) == 0);
     const size_t szSort = gv.vis_stride > 256 && depthSortOn ? up(NA * (size_t)gv.vis_stride * 40) : 0;
     const size_t total = szSort + szHdr + szBoxes + szObj + szAg + szAct + szRew + szDone + szObjv + szMd + (hostEpisodes ? 0 : szChunk) + szObs + szTerrain +
-                         szRewObj + szHeight + szItems + szCells + szHexB + szHexO + szBlobs + szCnt + szGen + (size_t)g->slots * szParity + szHist;
+                         szRewObj + szHeight + szItems + szCells + szHexB + szHexO + szBag + szBlobs + szCnt + szGen + (size_t)g->slots * szParity + szHist;
     {
         hipError_t e_ = hipMalloc((void **)&g->arena, total);
         if (e_ != hipSuccess) {
@@ -416,6 +421,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
         if (rearrange) { gv.items = (ArrangementItem *)p; p += szItems; }
         if (sokoban) { gv.soko_cells = p; p += szCells; }
         if (hex) { gv.hex_boxes = (HexRec *)p; p += szHexB; gv.hex_objs = (HexRec *)p; p += szHexO; }
+        if (boxagone) { gv.hex_boxes = (HexRec *)p; p += szHexB; gv.bag = (BoxAGoneState *)p; p += szBag; }
         gv.lpt_hist = (int32_t *)p; p += szHist;
         gv.sort_scratch = szSort ? p : nullptr; p += szSort;
         gv.depth_sort = 0;
@@ -454,7 +460,8 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     g->hRewards.assign(NA, 0.0f); g->hTrueObj.assign(NA, 0.0f); g->hDone.assign(N, 0);
 
     // headers: float params + unseeded envs take their seed from random_device (env.hpp:169)
-    float episodeLen = sokoban ? 80.0f : 60.0f, lookLimit = 0.2f;   // scenario.hpp:225-232; Sokoban: scenario_sokoban.hpp:49-53
+    // scenario.hpp:225-232; Sokoban: scenario_sokoban.hpp:49-53; BoxAGone: scenario_box_a_gone.hpp:82-87
+    float episodeLen = sokoban ? 80.0f : boxagone ? 300.0f : 60.0f, lookLimit = boxagone ? 0.75f : 0.2f;
     for (int k = 0; k < cfg->num_params; ++k) {
         const char *key = cfg->param_keys[k];
         const float v = cfg->param_vals[k];
@@ -489,7 +496,10 @@ int mv_create(const mv_config *cfg, mv_gym **out)
         // An env needs a fresh resident episode at every reset.  Two are kept resident, and the consumed counts are read back
         // every 16th step -- unless episodes can time out within a few ticks (a small or negative episodeLengthSec: the Obstacles
         // family never goes below 35 s per platform, the others take the parameter as is -- TowerBuilding adds 4 s per object), then after every step.
-        const float minLenSec = scenario == SCN_OBSTACLES ? std::max(episodeLen, 35.0f) : episodeLen;
+        // BoxAGone ends as soon as every agent is on the floor: for a random or idle agent after 30-60 ticks, never under 20 (it lands on its spawn
+        // platform, leaves it or waits for it to vanish, falls at least 6.8 units -- 15 ticks from rest -- then doneWithTimer's 0.3 s): 1.3 s, whatever
+        // episodeLengthSec says.  With counts read back every 16th tick (and up to max(32, 4 k) ticks late) an env finished twice inside the refill window.
+        const float minLenSec = scenario == SCN_OBSTACLES ? std::max(episodeLen, 35.0f) : scenario == SCN_BOXAGONE ? std::min(episodeLen, 1.3f) : episodeLen;
         g->statusPeriod = minLenSec * 15.0f >= 64.0f ? 16 : 1;
         if (const char *e = getenv("MV_STATUS_PERIOD")) g->statusPeriod = std::max(1, atoi(e));   // (tests: provoke starvation)
     }
@@ -565,6 +575,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
                                                      : scenario == SCN_SOKOBAN ? SHAPING_DEFAULT_SOKOBAN[k]
                                                      : scenario == SCN_HEX_MEMORY ? SHAPING_DEFAULT_HEX_MEMORY[k]
                                                      : scenario == SCN_HEX_EXPLORE ? SHAPING_DEFAULT_HEX_EXPLORE[k]
+                                                     : scenario == SCN_BOXAGONE ? SHAPING_DEFAULT_BOXAGONE[k]
                                                      : scenario == SCN_EMPTY ? 0.0f
                                                      : (k == 4 ? oc.carried_object_to_exit : SHAPING_DEFAULT_OBST[k]);
         ha[i].carrying = -1; ha[i].jump_speed = 10.0f; ha[i].m00 = 1.0f; ha[i].m22 = 1.0f;

@@ -139,12 +139,12 @@ int mv_debug_snapshot(mv_gym *g, int32_t env, void *out)
     if (e == hipSuccess && g->gv.heightmap) e = hipMemcpy(s->heightmap, g->gv.heightmap + (size_t)env * HM_BYTES, sizeof s->heightmap, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { delete s; return fail(std::string("mv_debug_snapshot: ") + hipGetErrorString(e)); }
     if (h.scenario == SCN_REARRANGE) h.num_terrain = 0;   // (the header reuses it for the item count, reported as num_items)
-    if (e == hipSuccess && g->gv.hex_boxes) {   // Hex*: the header's box / collider / reward counts describe the hex lists
+    if (e == hipSuccess && g->gv.hex_boxes) {   // Hex*, BoxAGone: the header's box / collider / reward counts describe the hex lists
         s->hex_num_boxes = h.num_boxes; s->hex_num_objs = h.num_rewards;
         s->hex_target[0] = h.hex_target[0]; s->hex_target[1] = 0.0f; s->hex_target[2] = h.hex_target[1];
         e = hipMemcpy(s->hex_boxes, g->gv.hex_boxes + (size_t)env * HEX_MAX_BOXES,
                       (size_t)std::min(h.num_boxes, (int)HEX_MAX_BOXES) * sizeof(HexRec), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(s->hex_objs, g->gv.hex_objs + (size_t)env * HEX_MAX_OBJS,
+        if (e == hipSuccess && g->gv.hex_objs) e = hipMemcpy(s->hex_objs, g->gv.hex_objs + (size_t)env * HEX_MAX_OBJS,
             (size_t)std::min(h.num_rewards, (int)HEX_MAX_OBJS) * sizeof(HexRec), hipMemcpyDeviceToHost);
         if (e != hipSuccess) { delete s; return fail(std::string("mv_debug_snapshot: ") + hipGetErrorString(e)); }
         h.num_boxes = 0; h.num_rewards = 0; h.num_terrain = 0;
@@ -197,11 +197,11 @@ int mv_debug_generate_episode(const char *scenario_name, int32_t num_agents, int
     int scenario = SCN_TOWER;
     ObstacleConfig oc;
     if (!scenario_name || !scenario_from_name(lower(scenario_name), scenario, oc) || scenario == SCN_TOWER || scenario == SCN_SOKOBAN || scenario == SCN_EMPTY)
-        return fail("mv_debug_generate_episode: the Obstacles family, Collect, Rearrange, HexMemory and HexExplore (Sokoban: mv_debug_generate_sokoban)");
+        return fail("mv_debug_generate_episode: the Obstacles family, Collect, Rearrange, HexMemory, HexExplore and BoxAGone (Sokoban: mv_debug_generate_sokoban)");
     if (num_agents < 1 || num_agents > MAX_AGENTS || n < 1) return fail("mv_debug_generate_episode: bad arguments");
     const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE;
-    const size_t bytes = scenario == SCN_COLLECT ? sizeof(CollectBlob) : scenario == SCN_REARRANGE
-                                                          ? sizeof(RearrangeBlob) : hex ? sizeof(HexBlob) : sizeof(EpisodeBlob);
+    const size_t bytes = scenario == SCN_COLLECT ? sizeof(CollectBlob) : scenario == SCN_REARRANGE ? sizeof(RearrangeBlob)
+                         : hex ? sizeof(HexBlob) : scenario == SCN_BOXAGONE ? sizeof(BoxAGoneBlob) : sizeof(EpisodeBlob);
     if (!out) return (int)bytes;
     if ((size_t)out_bytes < bytes) return fail("mv_debug_generate_episode: buffer too small");
     std::mt19937 rng;
@@ -213,10 +213,25 @@ int mv_debug_generate_episode(const char *scenario_name, int32_t num_agents, int
         else if (scenario == SCN_HEX_MEMORY) generate_hex_memory_episode(rng, num_agents, base_episode_len, *reinterpret_cast<HexBlob *>(buf.data()));
         else if (scenario == SCN_HEX_EXPLORE) generate_hex_explore_episode(rng, num_agents, base_episode_len, *reinterpret_cast<HexBlob *>(buf.data()));
         else if (scenario == SCN_REARRANGE) generate_rearrange_episode(rng, num_agents, base_episode_len, *reinterpret_cast<RearrangeBlob *>(buf.data()));
+        else if (scenario == SCN_BOXAGONE) generate_boxagone_episode(rng, num_agents, base_episode_len, *reinterpret_cast<BoxAGoneBlob *>(buf.data()));
         else generate_obstacles_episode(rng, oc, num_agents, base_episode_len, *reinterpret_cast<EpisodeBlob *>(buf.data()));
     }
     std::memcpy(out, buf.data(), bytes);
     return (int)bytes;
+}
+
+// Test hook: env `env`'s BoxAGoneState (mv_types.h: platform table, temporary ring, timers, cell map) as the device holds it, after everything
+// enqueued so far.  out = null: returns the record's size.
+int mv_debug_boxagone_state(mv_gym *g, int32_t env, void *out)
+{
+    if (check(g)) return -1;
+    if (g->scenario != SCN_BOXAGONE || !g->gv.bag) return fail("mv_debug_boxagone_state: not a BoxAGone gym");
+    if (!out) return (int)sizeof(BoxAGoneState);
+    if (env < 0 || env >= g->N) return fail("mv_debug_boxagone_state: bad env");
+    HIP_TRY(hipStreamSynchronize(g->simStream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    HIP_TRY(hipMemcpy(out, g->gv.bag + env, sizeof(BoxAGoneState), hipMemcpyDeviceToHost));
+    return (int)sizeof(BoxAGoneState);
 }
 
 // Host-only test hook: drives an EpisodeFeeder (worker pool, per-env ordering, recycle) without a device and checks

@@ -146,6 +146,11 @@ void EpisodeFeeder::generate(int env)
         else generate_hex_explore_episode(rng_[env], num_agents_, base_len_, b);
         b.seq = seq;
         used = offsetof(HexBlob, boxes) + size_t(b.num_boxes) * sizeof(HexRec);   // the box list is last: used prefix only
+    } else if (scenario_ == SCN_BOXAGONE) {
+        BoxAGoneBlob &b = *reinterpret_cast<BoxAGoneBlob *>(slot);
+        generate_boxagone_episode(rng_[env], num_agents_, base_len_, b);
+        b.seq = seq;
+        used = offsetof(BoxAGoneBlob, platforms) + size_t(b.num_platforms) * sizeof(BagPlatform);   // the platform list is last: used prefix only
     } else {
         CollectBlob &b = *reinterpret_cast<CollectBlob *>(slot);
         generate_collect_episode(rng_[env], num_agents_, base_len_, b);

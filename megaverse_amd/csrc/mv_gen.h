@@ -41,6 +41,9 @@ void generate_rearrange_episode(std::mt19937 &rng, int num_agents, float base_ep
 void generate_hex_explore_episode(std::mt19937 &rng, int num_agents, float base_episode_len, HexBlob &out);
 void generate_hex_memory_episode(std::mt19937 &rng, int num_agents, float base_episode_len, HexBlob &out);
 
+// Advances `rng` exactly like Env::reset + BoxAGoneScenario::reset + spawnAgents + addEpisodeDrawables and fills `out`.
+void generate_boxagone_episode(std::mt19937 &rng, int num_agents, float base_episode_len, BoxAGoneBlob &out);
+
 // Sokoban keeps state across episodes: the shuffled levels of the file picked last (SokobanScenario::levels)
 struct SokobanLevels {
     std::vector<std::vector<std::string>> pending;

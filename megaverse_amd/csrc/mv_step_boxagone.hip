@@ -1,0 +1,19 @@
+// megaverse_amd/csrc/mv_step_boxagone.hip -- the step and reset kernels of BoxAGone: entry points over the shared bodies (mv_step_kernels.h)
+// for the scenario's tick (mv_tick_boxagone.h: what it replaces, how it maps onto a wavefront).
+#include <hip/hip_runtime.h>
+
+#include "mv_step_kernels.h"
+#include "mv_tick_boxagone.h"
+
+namespace mv {
+
+using S = tick_boxagone::Scenario;
+
+template <int A_MAX> __global__ __launch_bounds__(256) void step_boxagone_kernel(GymView gv, int W, int H, int render) { step_body<S, A_MAX>(gv, blockIdx.x, W, H, render); }
+template <class Args> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_boxagone_ticks_kernel(Args a, int W, int H) { step_ticks_body<S, 1>(a, W, H); }
+__global__ __launch_bounds__(64) void reset_boxagone_kernel(GymView gv, int force_all) { reset_body<S>(gv, force_all); }
+
+const StepKernels boxagone_kernels = {step_boxagone_kernel<1>, step_boxagone_kernel<MAX_AGENTS>, step_boxagone_ticks_kernel<StepTicksArgs8>,
+                                      nullptr, nullptr, reset_boxagone_kernel};
+
+}  // namespace mv

@@ -37,7 +37,8 @@ enum : int { ST_STARVED = 1, ST_CANDIDATES = 2, ST_VISIBLE = 4, ST_CHUNK = 8 };
 
 enum : int { SCN_TOWER = 0, SCN_OBSTACLES = 1, SCN_COLLECT = 2, SCN_REARRANGE = 3, SCN_SOKOBAN = 4,
              SCN_EMPTY = 5,     // Empty runs on the Obstacles kernels (one slab, no terrain) with fall detection off
-             SCN_HEX_MEMORY = 6, SCN_HEX_EXPLORE = 7 };
+             SCN_HEX_MEMORY = 6, SCN_HEX_EXPLORE = 7,
+             SCN_BOXAGONE = 8 };   // its drawables are world-space HexRec records like the Hex scenarios' (mv_tick_boxagone.h)
 enum : int { HEX_PILLAR = 0, HEX_DIAMOND = 1, HEX_SPHERE = 2 };                       // scenario_hex_memory.cpp:163-168 ShapeType
 enum : int { SOKO_DIM = 32, SOKO_WALL = 1, SOKO_GOAL = 2 };                            // Sokoban level cells (scenario_sokoban.cpp:28-33)
 enum : int { MAX_ITEMS = 8, NUM_STATIC = 9 };                                         // Rearrange: arrangement items, static colliding boxes
@@ -178,6 +179,7 @@ struct GymView {
     // mv_raster.hip: hist_done)
     int32_t lpt_no_clear;
     struct TowerGen *tower_gen;// [N] TowerBuilding: where each env's episode generator stands (mv_reset_device.h: tower_draw); its resident episodes are `blobs` (TowerBlob)
+    struct BoxAGoneState *bag; // [N] BoxAGone: platform table, temporary ring, cell map (its drawables: hex_boxes)
 };
 
 // The n <= 8 consecutive ticks of a multi-tick step launch (mv_step.hip: step_ticks_kernel, and every mv_step_*.hip), the same envs in all of them: their views
@@ -324,5 +326,56 @@ struct alignas(16) CollectBlob {
     int8_t heightmap[HM_BYTES];
     LayoutBox boxes[COLLECT_MAX_BOXES];
 };
+
+// BoxAGone (scenario_box_a_gone.{hpp,cpp}): a 24 x 8 x 24 room at voxel size 2, 2-3 levels of up to 18 x 18 thin platforms.  Capacities (the reference has
+// none): 3 levels x 18 x 18 platforms, plus 3 A temporary ones, per env.
+enum : int { BAG_ROOM = 24, BAG_MAX_LEVELS = 3, BAG_LEVEL_CELLS = 18, BAG_MAX_PLATFORMS = 972, BAG_MAX_TEMPS = 3 * MAX_AGENTS, BAG_MAX_LAYOUT = 8,
+             BAG_TABLE = 976 };   // (BAG_MAX_PLATFORMS rounded up to 16: the tick reads the timers 16 at a time)
+static_assert(BAG_MAX_PLATFORMS == BAG_MAX_LEVELS * BAG_LEVEL_CELLS * BAG_LEVEL_CELLS && BAG_TABLE >= BAG_MAX_PLATFORMS && BAG_TABLE % 16 == 0,
+              "BoxAGone: at most 3 x 18 x 18 platforms per env");
+static_assert(BAG_MAX_LAYOUT + BAG_MAX_PLATFORMS + BAG_MAX_TEMPS <= HEX_MAX_BOXES, "BoxAGone: every drawable box has a HexRec slot");
+// platform status (BoxAGoneState::plat[i].state >> 4): on its cell / visited -- moved away, a temporary one took its place, its timer runs /
+// its timer ran out -- gone, and its grid cell with it
+enum : int { BAG_PRESENT = 0, BAG_VISITED = 1, BAG_REMOVED = 2 };
+
+struct alignas(4) BagPlatform {   // 4 B: cell x, y (the level's height), z; level (0..2) | status << 4 (device table only)
+    int8_t x, y, z, state;
+};
+
+// BoxAGone episode (mv_gen_boxagone.cpp -> mv_step_boxagone.hip).  `platforms` comes last: only the used prefix travels.
+struct alignas(16) BoxAGoneBlob {
+    int32_t seq;
+    int32_t num_boxes, num_platforms, num_levels;
+    int32_t level_y[4];                  // the levels' heights (voxels)
+    float episode_len;
+    int32_t pad[3];
+    float spawn[MAX_AGENTS][3];          // agentStartingPositions: the cell centre * voxel size
+    float yaw_frand[MAX_AGENTS];
+    LayoutBox boxes[BAG_MAX_LAYOUT];     // the room's merged slabs, in voxels
+    BagPlatform platforms[BAG_MAX_PLATFORMS];
+};
+
+// a temporary (green) platform: the platform whose place it took last (-1: none yet), how often a timer has sent it away (+600 per axis) since, its
+// current scale (x = z, y): 1.05 x the platform's, then x 1.03 per tick in the last 5 ticks of every timer that holds it
+struct alignas(16) BagTemp {
+    int32_t plat, away;
+    float sxz, sy;
+};
+
+// BoxAGone per-env state (GymView::bag).  The reference's std::map<RigidBody *, PlatformState> is `ticks` / `tslot` per platform (ticks > 0: a live
+// state); its std::deque of temporary platforms only ever rotates (take back(), push it to the front): `takes` counts the takes, take number t gets
+// temporary platform 3 A - 1 - t mod 3 A.
+struct alignas(16) BoxAGoneState {
+    int32_t num_platforms, num_levels, takes, finished;
+    int32_t level_y[4];
+    float sec_before[MAX_AGENTS];                             // AgentState::secondsBeforeTouchedFloor
+    int32_t last_platform[MAX_AGENTS];                        // AgentState::lastPlatform (-1: none)
+    BagTemp temps[BAG_MAX_TEMPS];
+    BagPlatform plat[BAG_TABLE];
+    uint8_t ticks[BAG_TABLE];                                 // PlatformState::remainingTicks
+    uint8_t tslot[BAG_TABLE];                                 // PlatformState::temporaryPlatform
+    int16_t cell[BAG_MAX_LEVELS][BAG_ROOM][BAG_ROOM];         // [level][x][z] -> platform index, -1: none
+};
+static_assert(sizeof(BoxAGoneState) % 16 == 0, "BoxAGoneState: 16-byte rows");
 
 }  // namespace mv

@@ -63,6 +63,7 @@ SYMBOLS = [
     ("mv_debug_set_agent_pos", C.c_int, [_P, _I, _I, _F, _F, _F]),
     ("mv_debug_set_agent_yaw", C.c_int, [_P, _I, _I, _F, _F]), ("mv_debug_set_agent_velocity", C.c_int, [_P, _I, _I, _F, _F, _F]),
     ("mv_debug_snapshot_size", C.c_int, [_P]), ("mv_debug_snapshot", C.c_int, [_P, _I, _P]),
+    ("mv_debug_boxagone_state", C.c_int, [_P, _I, _P]),
     ("mv_debug_rng", C.c_int, [_I, _U, _I, _P, _P, _I, _P]),
     ("mv_debug_math", C.c_int, [_I, _I, _P, _P, _I, _P]),
     ("mv_debug_generate_episode", C.c_int, [C.c_char_p, _I, _I, _I, _F, _P, _I]),
@@ -380,6 +381,14 @@ class MegaverseGym:
 
     def debug_set_agent_velocity(self, env_idx, agent_idx, hvx, hvz, vvel):
         self._ck(self._lib.mv_debug_set_agent_velocity(self._g, int(env_idx), int(agent_idx), float(hvx), float(hvz), float(vvel)))
+
+    def debug_boxagone_state(self, env_idx):
+        """BoxAGone: env env_idx's BoxAGoneState (mv_types.h) as raw bytes -- platform table, temporary ring, timers, cell map."""
+        n = self._lib.mv_debug_boxagone_state(self._g, int(env_idx), None)
+        self._ck(n)
+        buf = np.zeros(n, np.uint8)
+        self._ck(self._lib.mv_debug_boxagone_state(self._g, int(env_idx), buf.ctypes.data))
+        return buf
 
     def debug_snapshot_bytes(self, env_idx):
         n = self._lib.mv_debug_snapshot_size(self._g)

@@ -20,9 +20,9 @@ from .extension import MegaverseGym, set_megaverse_log_level
 
 MEGAVERSE8 = ['TowerBuilding', 'ObstaclesEasy', 'ObstaclesHard', 'Collect', 'Sokoban', 'HexMemory', 'HexExplore', 'Rearrange']
 OBSTACLES_MULTITASK = ['ObstaclesWalls', 'ObstaclesSteps', 'ObstaclesLava', 'ObstaclesEasy', 'ObstaclesHard']
-# what libmegaverse_hip.so can construct (mv_create): every scenario of the reference's multi-task sets
+# what libmegaverse_hip.so can construct (mv_create): every scenario of the reference's multi-task sets, Empty and BoxAGone
 SUPPORTED_SCENARIOS = ['TowerBuilding', 'ObstaclesEasy', 'ObstaclesMedium', 'ObstaclesHard', 'ObstaclesWalls', 'ObstaclesSteps', 'ObstaclesLava',
-                       'Collect', 'Sokoban', 'HexMemory', 'HexExplore', 'Rearrange', 'Empty']
+                       'Collect', 'Sokoban', 'HexMemory', 'HexExplore', 'Rearrange', 'Empty', 'BoxAGone']
 _warned_unsupported = False
 
 

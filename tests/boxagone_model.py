@@ -1,0 +1,230 @@
+"""Python restatement of the BoxAGone scenario for its tests: the episode generator (Env::reset + BoxAGoneScenario::reset + spawnAgents,
+env.cpp:57-76, scenario_box_a_gone.cpp:41-95, scenario_default.hpp:80-97) with mt19937 / randRange / frand / std::shuffle as libstdc++ computes
+them, and BoxAGoneScenario::step's logic (scenario_box_a_gone.cpp:97-171) on the device's state records (mv_types.h: BoxAGoneBlob,
+BoxAGoneState)."""
+import numpy as np
+
+MAX_AGENTS = 8
+ROOM, MAX_LEVELS, MAX_PLATFORMS, TABLE, MAX_TEMPS, MAX_LAYOUT = 24, 3, 972, 976, 24, 8
+PRESENT, VISITED, REMOVED = 0, 1, 2
+F32 = np.float32
+PLAT_HXZ = F32(F32(0.42) * F32(2.0))
+PLAT_HY = F32(PLAT_HXZ * F32(0.045))
+DT = F32(F32(1.0) / F32(15.0))
+
+LAYOUT_BOX = np.dtype([("min", "<i4", 3), ("type", "<i4"), ("max", "<i4", 3), ("slot", "<i4")])
+PLATFORM = np.dtype([("x", "i1"), ("y", "i1"), ("z", "i1"), ("state", "i1")])
+BLOB = np.dtype([
+    ("seq", "<i4"), ("num_boxes", "<i4"), ("num_platforms", "<i4"), ("num_levels", "<i4"), ("level_y", "<i4", 4), ("episode_len", "<f4"),
+    ("pad", "<i4", 3), ("spawn", "<f4", (MAX_AGENTS, 3)), ("yaw_frand", "<f4", MAX_AGENTS), ("boxes", LAYOUT_BOX, MAX_LAYOUT),
+    ("platforms", PLATFORM, MAX_PLATFORMS),
+])
+TEMP = np.dtype([("plat", "<i4"), ("away", "<i4"), ("sxz", "<f4"), ("sy", "<f4")])
+STATE = np.dtype([
+    ("num_platforms", "<i4"), ("num_levels", "<i4"), ("takes", "<i4"), ("finished", "<i4"), ("level_y", "<i4", 4),
+    ("sec_before", "<f4", MAX_AGENTS), ("last_platform", "<i4", MAX_AGENTS), ("temps", TEMP, MAX_TEMPS), ("plat", PLATFORM, TABLE),
+    ("ticks", "u1", TABLE), ("tslot", "u1", TABLE), ("cell", "<i2", (MAX_LEVELS, ROOM, ROOM)),
+])
+assert BLOB.itemsize % 16 == 0 and STATE.itemsize % 16 == 0
+
+
+class MT19937:
+    """std::mt19937 ([rand.predef])"""
+
+    def __init__(self, seed=5489):
+        self.seed(seed)
+
+    def seed(self, s):
+        mt = [0] * 624
+        mt[0] = s & 0xFFFFFFFF
+        for i in range(1, 624):
+            mt[i] = (1812433253 * (mt[i - 1] ^ (mt[i - 1] >> 30)) + i) & 0xFFFFFFFF
+        self.mt, self.i = mt, 624
+
+    def __call__(self):
+        if self.i >= 624:
+            mt = self.mt
+            for k in range(624):
+                y = (mt[k] & 0x80000000) | (mt[(k + 1) % 624] & 0x7FFFFFFF)
+                mt[k] = mt[(k + 397) % 624] ^ (y >> 1) ^ (0x9908B0DF if y & 1 else 0)
+            self.i = 0
+        y = self.mt[self.i]
+        self.i += 1
+        y ^= y >> 11
+        y ^= (y << 7) & 0x9D2C5680
+        y ^= (y << 15) & 0xEFC60000
+        y ^= y >> 18
+        return y & 0xFFFFFFFF
+
+
+def uniform_below(rng, n):
+    """uniform_int_distribution over [0, n) with a 32-bit engine: libstdc++'s multiply-shift with rejection (Lemire)"""
+    product = rng() * n
+    low = product & 0xFFFFFFFF
+    if low < n:
+        threshold = ((1 << 32) - n) % n
+        while low < threshold:
+            product = rng() * n
+            low = product & 0xFFFFFFFF
+    return product >> 32
+
+
+def rand_range(lo, hi, rng):
+    """randRange(lo, hi): uniform_int_distribution<>{lo, hi - 1} (util.hpp:30-33)"""
+    return lo + uniform_below(rng, hi - lo)
+
+
+def frand(rng):
+    """frand: uniform_real_distribution<float>{0, 1} -- generate_canonical<float, 24>: float(x) / 2^32, kept below 1"""
+    r = F32(F32(rng()) / F32(4294967296.0))
+    return r if r < F32(1.0) else np.nextafter(F32(1.0), F32(0.0))
+
+
+def shuffle(seq, rng):
+    """std::shuffle as libstdc++ does it with a 32-bit engine: two swap positions per draw when the range allows it"""
+    n = len(seq)
+    if n < 2:
+        return
+    if ((1 << 32) - 1) // n >= n:
+        i = 1
+        if n % 2 == 0:
+            j = uniform_below(rng, 2)
+            seq[i], seq[j] = seq[j], seq[i]
+            i += 1
+        while i != n:
+            r = i + 1
+            x = uniform_below(rng, r * (r + 1))
+            a, b = x // (r + 1), x % (r + 1)
+            seq[i], seq[a] = seq[a], seq[i]
+            i += 1
+            seq[i], seq[b] = seq[b], seq[i]
+            i += 1
+        return
+    for i in range(1, n):
+        j = uniform_below(rng, i + 1)
+        seq[i], seq[j] = seq[j], seq[i]
+
+
+ROOM_BOXES = [((0, 0, 0), (24, 1, 24)), ((0, 1, 0), (24, 8, 1)), ((0, 1, 1), (1, 8, 24)), ((23, 1, 1), (24, 8, 24)), ((1, 1, 23), (23, 8, 24))]
+
+
+def generate(rng, num_agents, base_len=300.0):
+    """one episode from the env's stream `rng` (advanced in place), as the BoxAGoneBlob the host generator fills (seq = 0)"""
+    out = np.zeros(1, BLOB)[0]
+    rng.seed(rand_range(0, 1 << 30, rng))
+    for k, (lo, hi) in enumerate(ROOM_BOXES):   # floor, then the walls as the greedy (y, z, x) merge finds them
+        out["boxes"][k]["min"], out["boxes"][k]["max"], out["boxes"][k]["type"] = lo, hi, 3
+    out["num_boxes"] = len(ROOM_BOXES)
+    num_levels = rand_range(2, 4, rng)
+    plats, spawns, h = [], [], 1
+    for level in range(num_levels):
+        h += rand_range(2, 4, rng)
+        length, width = rand_range(10, 19, rng), rand_range(10, 19, rng)
+        sx, sz = 12 - length // 2, 12 - width // 2
+        skip = F32(frand(rng) * F32(0.2))
+        out["level_y"][level] = h
+        for x in range(sx, sx + length):
+            for z in range(sz, sz + width):
+                if frand(rng) < skip:
+                    continue
+                plats.append((x, h, z, level))
+                if level == num_levels - 1:
+                    spawns.append(tuple(F32((F32(v) + F32(0.5)) * F32(2.0)) for v in (x, h, z)))
+    out["num_levels"], out["num_platforms"] = num_levels, len(plats)
+    for i, p in enumerate(plats):
+        out["platforms"][i] = p
+    while len(spawns) < num_agents:
+        spawns.append(spawns[0])
+    shuffle(spawns, rng)
+    for i in range(num_agents):
+        out["spawn"][i] = spawns[i]
+    out["episode_len"] = base_len
+    for i in range(num_agents):
+        out["yaw_frand"][i] = frand(rng)
+    return out
+
+
+def blob_bytes(b):
+    """the generator's record, zero past the used platforms (the part a test compares)"""
+    return np.array([b]).view(np.uint8)
+
+
+def platform_status(st, p):
+    return (int(st["plat"][p]["state"]) >> 4) & 15
+
+
+def platform_level(st, p):
+    return int(st["plat"][p]["state"]) & 15
+
+
+def agent_cell(pos):
+    t = (F32(pos[0]), F32(F32(pos[1]) + F32(0.05)), F32(pos[2]))
+    return tuple(int(np.floor(F32(v / F32(2.0))) ) for v in t)
+
+
+def on_ground(agent):
+    eps = F32(np.finfo(np.float32).eps)
+    return abs(F32(agent["vvel"])) < eps and abs(F32(agent["voffset"])) < eps
+
+
+def step(st, agents, shaping, episode_sec, episode_len, num_agents):
+    """BoxAGoneScenario::step on a copy of state record `st` (before the tick), given the agents after the tick's physics (snapshot records) and
+    their shaping coefficients: -> (new state, rewards[A] as float32, touching, episode_sec after the tick, done)"""
+    st = st.copy()
+    A = num_agents
+    rewards = np.zeros(A, np.float32)
+    touching = 0
+    for i in range(A):
+        cx, cy, cz = agent_cell(agents[i]["pos"])
+        floor = cy < 3
+        key = 1 if floor else 2
+        s = shaping[i]
+        r = F32(F32(0.0) + F32(s[key] * F32(F32(1.0) * F32(F32(1) - s[0]))))
+        r = F32(r + F32(F32(F32(s[key] * s[0]) * F32(1.0)) / F32(1.0)))
+        rewards[i] = r
+        if floor:
+            touching += 1
+        else:
+            st["sec_before"][i] = episode_sec
+        p = -1
+        for lv in range(int(st["num_levels"])):
+            if st["level_y"][lv] == cy and 0 <= cx < ROOM and 0 <= cz < ROOM:
+                p = int(st["cell"][lv][cx][cz])
+        if p >= 0 and platform_status(st, p) != REMOVED and on_ground(agents[i]) and p != st["last_platform"][i]:
+            lp = int(st["last_platform"][i])
+            if lp >= 0 and st["ticks"][lp] > 0:
+                st["ticks"][lp] = min(int(st["ticks"][lp]), 3)
+            if platform_status(st, p) == PRESENT:
+                nt = 3 * A
+                slot = nt - 1 - int(st["takes"]) % nt
+                st["takes"] += 1
+                st["ticks"][p], st["tslot"][p] = 15, slot
+                st["plat"][p]["state"] = platform_level(st, p) | (VISITED << 4)
+                st["temps"][slot] = (p, 0, F32(PLAT_HXZ * F32(1.05)), F32(PLAT_HY * F32(1.05)))
+            st["last_platform"][i] = p
+    for p in np.nonzero(st["ticks"])[0]:   # the map's order does not matter: growth and expiry commute
+        t = int(st["ticks"][p]) - 1
+        st["ticks"][p] = t
+        slot = int(st["tslot"][p])
+        if t <= 0:
+            st["temps"][slot]["away"] += 1
+            st["plat"][p]["state"] = platform_level(st, p) | (REMOVED << 4)
+        elif t <= 5:
+            st["temps"][slot]["sxz"] = F32(st["temps"][slot]["sxz"] * F32(1.03))
+            st["temps"][slot]["sy"] = F32(st["temps"][slot]["sy"] * F32(1.03))
+    sec = F32(episode_sec)
+    if touching >= A and not st["finished"]:
+        st["finished"] = 1
+        sec = max(sec, F32(F32(episode_len) - F32(0.3)))
+    sec = F32(sec + DT)
+    return st, rewards, touching, sec, bool(sec >= F32(episode_len))
+
+
+def true_objective(st, num_agents, episode_len):
+    if num_agents > 1:
+        best, best_agent = F32(0.0), 0
+        for i in range(num_agents):
+            if st["sec_before"][i] > best:
+                best_agent, best = i, st["sec_before"][i]
+        return np.array([1.0 if i == best_agent else 0.0 for i in range(num_agents)], np.float32)
+    return np.array([F32(st["sec_before"][0] / F32(episode_len))], np.float32)
