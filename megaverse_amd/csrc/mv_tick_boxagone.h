@@ -10,9 +10,10 @@
 //   VectorEnv::step done bookkeeping + Env::reset of finished envs (env/src/vector_env.cpp:93-105): the swap-in below takes the episode the host
 //   generator (mv_gen_boxagone.cpp) left resident in HBM.
 //
-// One wavefront per env, NC = 2 colliders per lane: k = 0 the room's merged slabs (lanes 0..7) and the other agents' capsules (lanes 32..39); k = 1
-// what is near the agent being stepped -- the 3 x 3 cells around it on every level (lanes 0..26, through the cell map: a present platform is a box)
-// and every temporary platform that stands somewhere (lanes 27..50).  A capsule moves less than a cell per tick (<= 0.3 horizontally) and a
+// One wavefront per env, NC = 2 colliders per lane: k = 0 the room's merged slabs (lanes 0..7); k = 1 what is near the agent being stepped -- the
+// 3 x 3 cells around it on every level (lanes 0..26, through the cell map: a present platform is a box), every temporary platform that stands
+// somewhere (lanes 27..50) -- and the other agents' capsules (lanes 51..58).  Slot order (lane + 64 k) is the reference's collision-object order
+// (room, platforms in generation order, temporary platforms, agents), which decides sweep ties and which penetration is recovered first.  A capsule moves less than a cell per tick (<= 0.3 horizontally) and a
 // platform, grown or not, reaches at most 1.03 from its cell's centre: nothing outside those cells can be touched.
 // The platforms' state -- the reference's std::map<RigidBody *, PlatformState> and std::deque of temporary platforms -- is BoxAGoneState
 // (mv_types.h): the scenario logic runs on lane 0, agent by agent, as the reference does; the timers then count down 16 platforms per lane.
@@ -39,7 +40,8 @@ constexpr float PLAT_HXZ = 0.42f * VOXEL;                   // objSize: a platfo
 constexpr float PLAT_HY = PLAT_HXZ * 0.045f;                //   (scenario_box_a_gone.cpp:189-191)
 constexpr float AWAY = 300.0f * VOXEL;                      // "basically remove from the scene" (:137, :150)
 constexpr int TEMP_TICKS = 15;                              // PlatformState::remainingTicks of a new state (:126)
-constexpr int NEAR_LANES = 27, TEMP_LANE0 = 27;
+constexpr int NEAR_LANES = 27, TEMP_LANE0 = 27, CAP_LANE0 = TEMP_LANE0 + BAG_MAX_TEMPS;
+static_assert(CAP_LANE0 + MAX_AGENTS <= 64, "BoxAGone: the capsules' lanes");
 __device__ constexpr unsigned LEVEL_COLORS[3] = {0xffb400u, 0x2eb5d0u, 0xd468eeu};   // ORANGE, BLUE, VIOLET (:63)
 constexpr unsigned GREEN = 0x3bb372u, LAYOUT_WHITE = 0xffffffu;                      // env/const.hpp:26-51
 
@@ -168,7 +170,7 @@ __device__ __forceinline__ void boxagone_tick(const GymView &gv, const int env)
     BoxAGoneState *st = gv.bag + env;
     HexRec *recs = gv.hex_boxes + (size_t)env * HEX_MAX_BOXES;
 
-    // ---- wave-resident scene: the room's slabs (k = 0, lanes < nb); per agent below: capsules (k = 0, lanes 32..39), what is near (k = 1)
+    // ---- wave-resident scene: the room's slabs (k = 0, lanes < nb); per agent below: what is near, then the capsules (k = 1)
     Col col[NC];
 #pragma unroll
     for (int k = 0; k < NC; ++k) { col[k].kind = 0; col[k].lo = col[k].hi = v3(0, 0, 0); }
@@ -192,15 +194,6 @@ __device__ __forceinline__ void boxagone_tick(const GymView &gv, const int env)
     // ---- physics, agent by agent (nothing moves but the agents during this phase)
 #pragma unroll 1
     for (int i = 0; i < A; ++i) {
-        if (A_MAX > 1 && lane >= 32 && lane < 32 + MAX_AGENTS) {   // agent capsules
-            const int j = lane - 32;
-            col[0].kind = 0;
-            if (j < A && j != i) {
-                col[0].kind = 2;
-                col[0].lo = v3(s_ag[j].pos[0], s_ag[j].pos[1], s_ag[j].pos[2]);
-                col[0].hi = v3(2 * CAP_HH, 0.0f, 0.0f);
-            }
-        }
         col[1].kind = 0;
         if (lane < NEAR_LANES) {   // the 3 x 3 cells around the agent on every level: present platforms
             const int level = lane / 9, cx = (int)floorf(s_ag[i].pos[0] / VOXEL) + (lane % 9) / 3 - 1, cz = (int)floorf(s_ag[i].pos[2] / VOXEL) + lane % 3 - 1;
@@ -214,6 +207,13 @@ __device__ __forceinline__ void boxagone_tick(const GymView &gv, const int env)
         } else if (lane < TEMP_LANE0 + nt) {   // temporary platforms that stand on a platform's cell
             const BagTemp t = st->temps[lane - TEMP_LANE0];
             if (t.plat >= 0 && t.away == 0) box_col(col[1], recs[nb + np + (lane - TEMP_LANE0)]);
+        } else if (A_MAX > 1 && lane >= CAP_LANE0 && lane < CAP_LANE0 + A) {   // the other agents' capsules
+            const int j = lane - CAP_LANE0;
+            if (j != i) {
+                col[1].kind = 2;
+                col[1].lo = v3(s_ag[j].pos[0], s_ag[j].pos[1], s_ag[j].pos[2]);
+                col[1].hi = v3(2 * CAP_HH, 0.0f, 0.0f);
+            }
         }
         AgentState a;
         phys_load(a, s_ag[i]);

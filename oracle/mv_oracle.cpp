@@ -24,6 +24,7 @@
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -31,6 +32,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 #ifdef __linux__
 #include <pthread.h>
@@ -80,7 +82,8 @@ static const float CARRY_SCALE = 0.78f;               // :63
 enum { CX = 32, CY = 16, CZ = 32, CHUNK = CX * CY * CZ };
 enum { MAX_BOXES = 1024, MAX_OBJECTS = 80, MAX_AGENTS = 8, MAX_TERRAIN = 16, MAX_REWARDS = 96, MAX_SHAPING = 8 };
 enum { HM_DIM = 42 };   // Collect heightfield: maxWidth == maxLength == 42 (scenario_collect.cpp:63)
-enum { SCN_TOWER = 0, SCN_OBSTACLES = 1, SCN_COLLECT = 2, SCN_REARRANGE = 3, SCN_SOKOBAN = 4, SCN_EMPTY = 5, SCN_HEX_MEMORY = 6, SCN_HEX_EXPLORE = 7 };
+enum { SCN_TOWER = 0, SCN_OBSTACLES = 1, SCN_COLLECT = 2, SCN_REARRANGE = 3, SCN_SOKOBAN = 4, SCN_EMPTY = 5, SCN_HEX_MEMORY = 6, SCN_HEX_EXPLORE = 7,
+       SCN_BOX_A_GONE = 8 };
 enum { HEX_MAX_BOXES = 2048, HEX_MAX_OBJS = 128, HEX_FRAMES = 3 };   // Hex*: float boxes (floor, walls, edgings, landmarks), collectables
 enum { HEX_PILLAR = 0, HEX_DIAMOND = 1, HEX_SPHERE = 2 };            // scenario_hex_memory.cpp:163-168 ShapeType
 enum { SOKO_DIM = 32, SOKO_WALL = 1, SOKO_GOAL = 2 };   // Sokoban level cells (scenario_sokoban.cpp:28-33), levels up to 32 x 32
@@ -217,6 +220,9 @@ static const char *SHAPING_KEYS_HEX_EXPLORE[2] = {"teamSpirit", "exploreSolved"}
 static const float SHAPING_DEFAULT_HEX_EXPLORE[2] = {0.0f, 5.0f};
 static const char *SHAPING_KEYS_COLLECT[5] = {"teamSpirit", "collectSingleGood", "collectSingleBad", "collectAll", "collectAbyss"};
 static const float SHAPING_DEFAULT_COLLECT[5] = {0.0f, 1.0f, -1.0f, 5.0f, -0.5f};
+// scenario_box_a_gone.hpp:81-87 (+ teamSpirit 0)
+static const char *SHAPING_KEYS_BOX_A_GONE[3] = {"teamSpirit", "boxagoneTouchedFloor", "boxagonePerStepReward"};
+static const float SHAPING_DEFAULT_BOX_A_GONE[3] = {0.0f, -0.1f, 0.01f};
 
 enum { PT_EMPTY = 0, PT_WALL, PT_LAVA, PT_STEP, PT_GAP, PT_START, PT_EXIT, PT_TRANSITION };
 struct ObstacleParams {  // scenario_obstacles.hpp:46-68 defaults, overridden per registered name :94-268
@@ -255,6 +261,22 @@ struct Env {
     std::vector<HexBox> hexBoxes;
     std::vector<HexObj> hexObjs;
     V3 hexTarget = V3{0, 0, 0};                                                     // HexExplore rewardObjectCoords
+    // BoxAGone (scenario_box_a_gone.{hpp,cpp}): hexBoxes holds the room's slabs, then one record per disappearing platform (generation
+    // order), then the 3 A temporary platforms, all in the world frame and rewritten from the RigidBody poses below after every change.
+    // numPlatforms holds the platform count, solved the scenario's `finished`.
+    struct BagPlatform { int x, y, z, level; V3 tr; int temp; };   // disappearingPlatforms + the platform RigidBody's translation (scale:
+                                                                   // objScale, never changes); temp: the temporary that took its place (-1)
+    struct BagTemp { V3 tr, sc; int plat; V3 base; };              // a temporary RigidBody's translation and scaling; plat: the platform it
+                                                                   // was put on last (-1: none), base: its translation then
+    struct BagPlatformState { int remainingTicks; int coords[3]; int temporaryPlatform; };   // PlatformState, scenario_box_a_gone.hpp:31-36
+    int bagRoomBoxes = 0, bagNumLevels = 0, bagLevelY[4] = {0, 0, 0, 0}, bagFinished = 0;
+    std::vector<BagPlatform> bagPlatforms;
+    std::vector<BagTemp> bagTemps;
+    std::map<int, BagPlatformState> bagStates;                      // platformStates (keyed by platform index: creation order)
+    std::deque<int> bagExtra;                                       // extraPlatforms
+    std::map<std::tuple<int, int, int>, int> bagGrid;               // vg.grid's voxels that hold a disappearing platform
+    int bagLast[MAX_AGENTS];                                        // AgentState::lastPlatform (-1: nullptr)
+    float bagSecBefore[MAX_AGENTS];                                 // AgentState::secondsBeforeTouchedFloor
     // Collect: numPlatforms holds numPositiveRewards, highestTower holds positiveRewardsCollected (scenario_collect.hpp:76)
     std::vector<int8_t> heightmap = std::vector<int8_t>(HM_DIM * HM_DIM, -1);   // [x * HM_DIM + z]: top solid y of the column, -1 = no voxels
     TerrainBox terrain[MAX_TERRAIN];
@@ -1597,6 +1619,119 @@ static void empty_generate(Env &e)
     spawn_agents(e, std::vector<C3>(size_t(e.numAgents), C3{1, 1, 1}));   // agentStartingPositions, scenario_empty.cpp:20-23
 }
 
+// BoxAGone -- scenario_box_a_gone.{hpp,cpp}.  voxelSize 2 (hpp:95), platformSize 24 (hpp:96).
+static const float BAG_VOXEL = 2.0f, BAG_AWAY = 300.0f * 2.0f;   // "basically remove from the scene": + (300, 300, 300) * voxelSize (cpp:136, :151)
+static const unsigned BAG_LEVEL_COLORS[3] = {0xffb400, 0x2eb5d0, 0xd468ee};   // ORANGE, BLUE, VIOLET (cpp:54); const.hpp:25-56
+static const unsigned COLOR_LAYOUT_DEFAULT = 0xffffff;                         // LAYOUT_DEFAULT = WHITE, const.hpp:51
+
+static V3 bag_obj_scale()
+{   // addDisappearingPlatforms, cpp:312-314: btBoxShape(1, 1, 1) scaled by (objSize, objSize * thicknessRatio, objSize)
+    const float objSize = 0.42f * BAG_VOXEL, thicknessRatio = 0.045f;
+    return v3(objSize, objSize * thicknessRatio, objSize);
+}
+
+static Env::HexBox bag_box(V3 tr, V3 sc, unsigned color)
+{
+    Env::HexBox b; b.frame = -1; b.collide = 1; b.color = color;
+    b.lo = v3(tr.x - sc.x, tr.y - sc.y, tr.z - sc.z); b.hi = v3(tr.x + sc.x, tr.y + sc.y, tr.z + sc.z);
+    return b;
+}
+
+// the platforms' and temporaries' records from their RigidBody poses (after reset and after every step)
+static void bag_sync_boxes(Env &e)
+{
+    const V3 sc = bag_obj_scale();
+    const size_t np = e.bagPlatforms.size();
+    e.hexBoxes.resize(size_t(e.bagRoomBoxes) + np + e.bagTemps.size());
+    for (size_t i = 0; i < np; ++i) {
+        const Env::BagPlatform &p = e.bagPlatforms[i];
+        e.hexBoxes[size_t(e.bagRoomBoxes) + i] = bag_box(p.tr, sc, BAG_LEVEL_COLORS[p.level % 3]);
+    }
+    for (size_t t = 0; t < e.bagTemps.size(); ++t)
+        e.hexBoxes[size_t(e.bagRoomBoxes) + np + t] = bag_box(e.bagTemps[t].tr, e.bagTemps[t].sc, COLOR_GREEN);
+}
+
+// BoxAGoneScenario::reset (cpp:154-209) + spawnAgents (scenario_default.hpp:80-97) + addEpisodeDrawables (cpp:298-346)
+static void boxagone_generate(Env &e)
+{
+    hex_common_reset(e);
+    e.bagStates.clear(); e.bagExtra.clear(); e.bagGrid.clear(); e.bagPlatforms.clear(); e.bagTemps.clear();
+    e.bagFinished = 0;
+    for (int k = 0; k < 4; ++k) e.bagLevelY[k] = 0;
+    for (int i = 0; i < MAX_AGENTS; ++i) { e.bagLast[i] = -1; e.bagSecBefore[i] = 0.0f; }
+
+    // BoxAGonePlatform: an EmptyPlatform whose init() is fixed (cpp:131-135: 24 x 8 x 24, no draw), WALLS_ALL; generate() = addFloor + addWalls
+    // (platforms.hpp:167-190).  vg.addPlatform(..., true) puts every voxel in the grid as solid + opaque in LAYOUT_DEFAULT; they are drawn
+    // and collide as the merged boxes (addDrawablesAndCollisionObjectsFromVoxelGrid, scaled by the voxel size)
+    const int L = 24, H = 8, W = 24;
+    fill_box(e, 0, 0, 0, L, 1, W, VX_SOLID | VX_OPAQUE);           // floor
+    fill_box(e, 0, 0, 0, 1, H, W, VX_SOLID | VX_OPAQUE);           // WALLS_SOUTH
+    fill_box(e, L - 1, 0, 0, L, H, W, VX_SOLID | VX_OPAQUE);       // WALLS_NORTH
+    fill_box(e, 0, 0, 0, L, H, 1, VX_SOLID | VX_OPAQUE);           // WALLS_EAST
+    fill_box(e, 0, 0, W - 1, L, H, W, VX_SOLID | VX_OPAQUE);       // WALLS_WEST
+    merge_boxes(e);
+    for (int i = 0; i < e.numBoxes; ++i) {
+        const Box &b = e.boxes[i];
+        Env::HexBox hb; hb.frame = -1; hb.collide = 1; hb.color = COLOR_LAYOUT_DEFAULT;
+        hb.lo = v3(float(b.min[0]) * BAG_VOXEL, float(b.min[1]) * BAG_VOXEL, float(b.min[2]) * BAG_VOXEL);
+        hb.hi = v3(float(b.max[0]) * BAG_VOXEL, float(b.max[1]) * BAG_VOXEL, float(b.max[2]) * BAG_VOXEL);
+        e.hexBoxes.push_back(hb);
+    }
+    e.bagRoomBoxes = e.numBoxes;
+    e.numBoxes = 0;   // (the room lives in hexBoxes; the chunk only served the merge)
+    std::fill(e.chunk.begin(), e.chunk.end(), 0);
+    e.L = L; e.H = H; e.W = W;
+    e.layoutColor = COLOR_LAYOUT_DEFAULT; e.wallColor = COLOR_LAYOUT_DEFAULT; e.drawWalls = 1;
+
+    // the levels (cpp:172-203)
+    const int numLevels = randRange(2, 4, e.rng);
+    std::vector<F3> spawnPositions;
+    int currLevelHeight = 1;
+    for (int level = 0; level < numLevels; ++level) {
+        currLevelHeight += randRange(2, 4, e.rng);
+        const int offset = 24 / 2;
+        const int levelLength = randRange(10, 19, e.rng);
+        const int levelWidth = randRange(10, 19, e.rng);
+        const int startX = offset - levelLength / 2, startZ = offset - levelWidth / 2;
+        const float skipProb = frand(e.rng) * 0.2f;
+        e.bagLevelY[level] = currLevelHeight;
+        for (int x = startX; x < startX + levelLength; ++x)
+            for (int z = startZ; z < startZ + levelWidth; ++z) {
+                if (frand(e.rng) < skipProb) continue;
+                Env::BagPlatform p;
+                p.x = x; p.y = currLevelHeight; p.z = z; p.level = level; p.temp = -1;
+                p.tr = v3((float(x) + 0.5f) * BAG_VOXEL, (float(currLevelHeight) + 0.5f) * BAG_VOXEL, (float(z) + 0.5f) * BAG_VOXEL);
+                e.bagPlatforms.push_back(p);
+                if (level == numLevels - 1) {
+                    const V3 v = v3(float(x) + 0.5f, float(currLevelHeight) + 0.5f, float(z) + 0.5f) * BAG_VOXEL;
+                    spawnPositions.push_back(F3{v.x, v.y, v.z});
+                }
+            }
+    }
+    e.bagNumLevels = numLevels;
+    // (an empty top level -- >= 100 cells each skipped with p <= 0.2 -- would index an empty vector in the reference: never happens; the room's
+    // centre instead of undefined behaviour)
+    if (spawnPositions.empty()) spawnPositions.push_back(F3{24.0f, 2.0f, 24.0f});
+    while (int(spawnPositions.size()) < e.numAgents) spawnPositions.push_back(spawnPositions[0]);
+    std::shuffle(spawnPositions.begin(), spawnPositions.end(), e.rng);
+    spawn_agents_at(e, spawnPositions);   // agentStartingPositions (cpp:293-296) + (0.5, 0, 0.5), one frand per agent
+
+    // addDisappearingPlatforms (cpp:310-346): the platforms' voxels hold their RigidBody; 3 A temporary (green) ones 600 away, in the deque
+    for (size_t i = 0; i < e.bagPlatforms.size(); ++i) {
+        const Env::BagPlatform &p = e.bagPlatforms[i];
+        e.bagGrid[std::make_tuple(p.x, p.y, p.z)] = int(i);
+    }
+    for (int i = 0; i < e.numAgents * 3; ++i) {
+        Env::BagTemp t;
+        t.tr = v3(300, 300, 300) * BAG_VOXEL; t.sc = bag_obj_scale(); t.plat = -1; t.base = t.tr;
+        e.bagTemps.push_back(t);
+        e.bagExtra.push_back(i);
+    }
+    bag_sync_boxes(e);
+    e.numPlatforms = int(e.bagPlatforms.size());
+    e.episodeLen = e.p_episodeLengthSec;
+}
+
 static void env_reset(Env &e)
 {
     // ---- Env::reset, env/src/env.cpp:57-76 ; EnvState::reset env.hpp:135-151
@@ -1610,6 +1745,7 @@ static void env_reset(Env &e)
     else if (e.scenario == SCN_EMPTY) empty_generate(e);
     else if (e.scenario == SCN_HEX_MEMORY) hex_memory_generate(e, uint32_t(seed));
     else if (e.scenario == SCN_HEX_EXPLORE) hex_explore_generate(e, uint32_t(seed));
+    else if (e.scenario == SCN_BOX_A_GONE) boxagone_generate(e);
     else sokoban_generate(e);
 }
 
@@ -1808,8 +1944,10 @@ static void build_colliders(const Env &e, int self, Colliders &out)
         c.lo = v3(float(b.min[0]) * vs, float(b.min[1]) * vs - CAP_HH, float(b.min[2]) * vs);
         c.hi = v3(float(b.max[0]) * vs, float(b.max[1]) * vs + CAP_HH, float(b.max[2]) * vs);
     }
-    if (e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE)
-        for (const Env::HexBox &b : e.hexBoxes) {   // floor (addStaticCollidingBox) and walls (btBoxShape(1,1,1) child of the wall box)
+    // Hex*: floor (addStaticCollidingBox) and walls (btBoxShape(1,1,1) child of the wall box).  BoxAGone: the room, then every platform and
+    // every temporary platform wherever it is (no culling), the agents last
+    if (e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE || e.scenario == SCN_BOX_A_GONE)
+        for (const Env::HexBox &b : e.hexBoxes) {
             if (!b.collide) continue;
             Collider &c = out.c[out.n++];
             c.kind = b.frame < 0 ? 1 : 3; c.frame = b.frame;
@@ -2262,6 +2400,81 @@ static void sokoban_step(Env &e)
 // ------------------------------------------------------------------------------------------------
 // Env::step -- env/src/env.cpp:83-152
 // ------------------------------------------------------------------------------------------------
+// BoxAGoneScenario::step, scenario_box_a_gone.cpp:211-291
+static void boxagone_step(Env &e)
+{
+    int agentsTouchingFloor = 0;
+    for (int i = 0; i < e.numAgents; ++i) {
+        const Agent &a = e.agents[i];
+        const V3 t = v3(a.pos.x, a.pos.y + 0.05f, a.pos.z);   // absoluteTransformation().translation()
+        const int coords[3] = {int(floorf(t.x / BAG_VOXEL)), int(floorf(t.y / BAG_VOXEL)), int(floorf(t.z / BAG_VOXEL))};   // getCoords, origin 0
+        const bool touchesFloor = coords[1] < 3;
+        // rewardTeam with teamAffinity(i) == i: the team is agent i alone (scenario.hpp:259-307)
+        const int key = touchesFloor ? 1 : 2;   // boxagoneTouchedFloor / boxagonePerStepReward
+        reward_agent(e, key, i, 1.0f * (1 - e.agents[i].shaping[0]));
+        e.agents[i].last_reward += e.agents[i].shaping[key] * e.agents[i].shaping[0] * 1.0f / float(1);
+        if (touchesFloor) ++agentsTouchingFloor;
+        else e.bagSecBefore[i] = e.episodeSec;
+
+        const auto voxel = e.bagGrid.find(std::make_tuple(coords[0], coords[1], coords[2]));
+        if (voxel == e.bagGrid.end() || !on_ground(a)) continue;
+        const int plat = voxel->second;
+        if (plat == e.bagLast[i]) continue;
+        // visited a new platform: the previous one's timer goes down to 3 at most
+        const auto last = e.bagStates.find(e.bagLast[i]);
+        if (last != e.bagStates.end()) last->second.remainingTicks = std::min(last->second.remainingTicks, 3);
+        if (!e.bagStates.count(plat)) {   // a new PlatformState: the back of the deque takes the platform's place, the platform goes away
+            const int ticks = 15;
+            const int temporaryPlatform = e.bagExtra.back();
+            e.bagStates[plat] = Env::BagPlatformState{ticks, {coords[0], coords[1], coords[2]}, temporaryPlatform};
+            e.bagExtra.pop_back();
+            e.bagExtra.push_front(temporaryPlatform);
+            Env::BagPlatform &p = e.bagPlatforms[size_t(plat)];
+            Env::BagTemp &tp = e.bagTemps[size_t(temporaryPlatform)];
+            tp.sc = bag_obj_scale() * 1.05f;   // resetTransformation, scale(platformSc * 1.05f), translate(platformTr)
+            tp.tr = p.tr;
+            tp.plat = plat; tp.base = tp.tr;
+            p.temp = temporaryPlatform;
+            p.tr = p.tr + v3(BAG_AWAY, BAG_AWAY, BAG_AWAY);
+        }
+        e.bagLast[i] = plat;
+    }
+
+    for (auto iter = e.bagStates.begin(); iter != e.bagStates.end();) {
+        Env::BagPlatformState &state = iter->second;
+        Env::BagTemp &tempPlatform = e.bagTemps[size_t(state.temporaryPlatform)];
+        --state.remainingTicks;
+        if (state.remainingTicks <= 0) {
+            tempPlatform.tr = tempPlatform.tr + v3(BAG_AWAY, BAG_AWAY, BAG_AWAY);
+            e.bagGrid.erase(std::make_tuple(state.coords[0], state.coords[1], state.coords[2]));
+            iter = e.bagStates.erase(iter);
+        } else {
+            if (state.remainingTicks <= 5) tempPlatform.sc = tempPlatform.sc * 1.03f;
+            ++iter;
+        }
+    }
+    bag_sync_boxes(e);
+
+    if (agentsTouchingFloor >= e.numAgents && !e.bagFinished) {
+        e.bagFinished = 1;
+        e.solved = 1;
+        e.episodeSec = std::max(e.episodeSec, e.episodeLen - 0.3f);   // doneWithTimer(), scenario.hpp:114-117
+    }
+}
+
+// BoxAGoneScenario::trueObjective, scenario_box_a_gone.hpp:57-72
+static float boxagone_true_objective(const Env &e, int agentIdx)
+{
+    if (e.numAgents > 1) {   // last man standing wins
+        float maxSecondsBeforeTouchingFloor = 0.0f;
+        int bestAgent = 0;
+        for (int i = 0; i < e.numAgents; ++i)
+            if (e.bagSecBefore[i] > maxSecondsBeforeTouchingFloor) bestAgent = i, maxSecondsBeforeTouchingFloor = e.bagSecBefore[i];
+        return agentIdx == bestAgent ? 1.0f : 0.0f;
+    }
+    return e.bagSecBefore[agentIdx] / e.p_episodeLengthSec;   // episodeLengthSec(): the float parameter
+}
+
 static void env_step(Env &e)
 {
     const float dt = DT;
@@ -2311,7 +2524,8 @@ static void env_step(Env &e)
     for (int i = 0; i < e.numAgents; ++i) player_step(e, i, dt);
 
     // scenario->step(): objectStacking, fallDetection, zone reward (scenario_tower_building.cpp:179-199)
-    const bool hex = e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE;
+    // (BoxAGone: no ObjectStackingComponent; its FallDetectionComponent is never stepped, scenario_box_a_gone.cpp:211-291)
+    const bool hex = e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE || e.scenario == SCN_BOX_A_GONE;
     for (int i = 0; i < e.numAgents; ++i)
         if (e.scenario != SCN_SOKOBAN && e.scenario != SCN_EMPTY && !hex && (e.agents[i].action & (1 << 8))) on_interact(e, i);   // (Sokoban, Empty, Hex*: no ObjectStackingComponent)
 
@@ -2389,6 +2603,8 @@ static void env_step(Env &e)
                         o.alive = 0;
                     }
         }
+    } else if (e.scenario == SCN_BOX_A_GONE) {
+        boxagone_step(e);
     } else if (e.scenario == SCN_EMPTY) {
         // EmptyScenario::step() {} (scenario_empty.hpp:22)
     } else if (e.scenario == SCN_SOKOBAN) {
@@ -2504,7 +2720,7 @@ static void build_prims(const Env &e, int viewer, std::vector<Prim> &out)
             out.push_back(p);
         }
     }
-    if (e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE) {
+    if (e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE || e.scenario == SCN_BOX_A_GONE) {   // (BoxAGone: no hexObjs)
         for (const Env::HexBox &b : e.hexBoxes) {
             Prim p; p.kind = 1; p.frame = b.frame < 0 ? -1 : MAX_AGENTS + b.frame; p.lo = b.lo; p.hi = b.hi; p.color = b.color;
             out.push_back(p);
@@ -3066,7 +3282,9 @@ struct Gym {
             if (envs[i]->done) {
                 done[i] = 1;
                 for (int a = 0; a < numAgents; ++a)
-                    trueObjective[size_t(i) * numAgents + a] = envs[i]->scenario == SCN_TOWER ? float(envs[i]->highestTower) : float(envs[i]->solved);   // scenario_collect.hpp:42
+                    trueObjective[size_t(i) * numAgents + a] = envs[i]->scenario == SCN_TOWER ? float(envs[i]->highestTower)
+                                                             : envs[i]->scenario == SCN_BOX_A_GONE ? boxagone_true_objective(*envs[i], a)
+                                                             : float(envs[i]->solved);   // scenario_collect.hpp:42
                 env_reset(*envs[i]);
             } else done[i] = 0;
         }
@@ -3108,6 +3326,7 @@ mvo_gym *mvo_create(const char *scenario, int w, int h, int num_envs, int num_ag
     else if (s == "empty") scen = SCN_EMPTY;           // scenarios/init.hpp:34
     else if (s == "hexmemory") scen = SCN_HEX_MEMORY;  // scenarios/init.hpp:47-48
     else if (s == "hexexplore") scen = SCN_HEX_EXPLORE;
+    else if (s == "boxagone") scen = SCN_BOX_A_GONE;   // scenarios/init.hpp:50
     else { fprintf(stderr, "mv_oracle: unknown scenario %s\n", s.c_str()); return nullptr; }
     if (num_agents_per_env < 1 || num_agents_per_env > MAX_AGENTS || num_envs < 1) return nullptr;
     auto *g = new mvo_gym();
@@ -3129,6 +3348,7 @@ mvo_gym *mvo_create(const char *scenario, int w, int h, int num_envs, int num_ag
         auto e = std::make_unique<Env>();
         e->numAgents = num_agents_per_env;
         if (scen == SCN_SOKOBAN) { e->p_episodeLengthSec = 80.0f; e->sokoFiles = &g->sokoFiles; }   // scenario_sokoban.hpp:49-53
+        if (scen == SCN_BOX_A_GONE) { e->p_episodeLengthSec = 300.0f; e->p_verticalLookLimitRad = 0.75f; }   // scenario_box_a_gone.hpp:74-79
         for (int k = 0; k < n_params; ++k) {
             if (!strcmp(keys[k], "episodeLengthSec")) e->p_episodeLengthSec = vals[k];
             if (!strcmp(keys[k], "verticalLookLimitRad")) e->p_verticalLookLimitRad = vals[k];
@@ -3140,11 +3360,12 @@ mvo_gym *mvo_create(const char *scenario, int w, int h, int num_envs, int num_ag
         }
         e->scenario = scen;
         e->op = op;
-        e->numShaping = scen == SCN_TOWER || scen == SCN_SOKOBAN ? 4 : scen == SCN_REARRANGE || scen == SCN_HEX_MEMORY ? 3
+        e->numShaping = scen == SCN_TOWER || scen == SCN_SOKOBAN ? 4 : scen == SCN_REARRANGE || scen == SCN_HEX_MEMORY || scen == SCN_BOX_A_GONE ? 3
                       : scen == SCN_HEX_EXPLORE ? 2 : scen == SCN_EMPTY ? 1 : 5;   // Empty: teamSpirit only
         e->shapingKeys = scen == SCN_TOWER ? SHAPING_KEYS_TOWER : scen == SCN_OBSTACLES ? SHAPING_KEYS_OBST
                        : scen == SCN_COLLECT ? SHAPING_KEYS_COLLECT : scen == SCN_SOKOBAN ? SHAPING_KEYS_SOKOBAN
-                       : scen == SCN_HEX_MEMORY ? SHAPING_KEYS_HEX_MEMORY : scen == SCN_HEX_EXPLORE ? SHAPING_KEYS_HEX_EXPLORE : SHAPING_KEYS_REARRANGE;
+                       : scen == SCN_HEX_MEMORY ? SHAPING_KEYS_HEX_MEMORY : scen == SCN_HEX_EXPLORE ? SHAPING_KEYS_HEX_EXPLORE
+                       : scen == SCN_BOX_A_GONE ? SHAPING_KEYS_BOX_A_GONE : SHAPING_KEYS_REARRANGE;
         for (int a = 0; a < MAX_AGENTS; ++a) {
             std::memset(e->agents[a].shaping, 0, sizeof e->agents[a].shaping);
             for (int k = 0; k < e->numShaping; ++k)
@@ -3154,6 +3375,7 @@ mvo_gym *mvo_create(const char *scenario, int w, int h, int num_envs, int num_ag
                                         : scen == SCN_SOKOBAN ? SHAPING_DEFAULT_SOKOBAN[k]
                                         : scen == SCN_HEX_MEMORY ? SHAPING_DEFAULT_HEX_MEMORY[k]
                                         : scen == SCN_HEX_EXPLORE ? SHAPING_DEFAULT_HEX_EXPLORE[k]
+                                        : scen == SCN_BOX_A_GONE ? SHAPING_DEFAULT_BOX_A_GONE[k]
                                         : (k == 4 ? carriedDefault : SHAPING_DEFAULT_OBST[k]);
         }
         g->envs.push_back(std::move(e));
@@ -3330,7 +3552,7 @@ void mvo_snapshot(mvo_gym *g, int env, void *out)
         s->items[i][0] = e.items[i].shape; s->items[i][1] = (int32_t)e.items[i].color;
         s->items[i][2] = e.items[i].off[0]; s->items[i][3] = e.items[i].off[1]; s->items[i][4] = e.items[i].off[2];
     }
-    if (e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE) {
+    if (e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE || e.scenario == SCN_BOX_A_GONE) {
         s->hex_num_boxes = int(e.hexBoxes.size()); s->hex_num_objs = int(e.hexObjs.size());
         s->hex_target[0] = e.hexTarget.x; s->hex_target[1] = e.hexTarget.y; s->hex_target[2] = e.hexTarget.z;
         for (size_t i = 0; i < e.hexBoxes.size() && i < HEX_MAX_BOXES; ++i) {
@@ -3345,6 +3567,52 @@ void mvo_snapshot(mvo_gym *g, int env, void *out)
     }
     std::memcpy(out, s, sizeof *s);
     delete s;
+}
+
+/* BoxAGone: the device's BoxAGoneState record (megaverse_amd/csrc/mv_types.h), derived from the oracle's containers: the platform table
+ * (cell, level | status << 4: 0 on its cell, 1 a temporary one took its place, 2 its voxel left the grid), every live PlatformState's
+ * remainingTicks, the temporary that took each platform's place, the temporaries (platform they were put on last, times sent away since,
+ * scale), AgentState per agent and the cell map [level][x][z] -> platform. */
+struct BagStateRec {
+    int32_t num_platforms, num_levels, takes, finished;
+    int32_t level_y[4];
+    float sec_before[MAX_AGENTS];
+    int32_t last_platform[MAX_AGENTS];
+    struct { int32_t plat, away; float sxz, sy; } temps[3 * MAX_AGENTS];
+    int8_t plat[976][4];
+    uint8_t ticks[976], tslot[976];
+    int16_t cell[3][24][24];
+};
+
+int mvo_debug_boxagone_state(mvo_gym *g, int env, void *out)
+{
+    if (!g || env < 0 || env >= g->numEnvs || g->envs[size_t(env)]->scenario != SCN_BOX_A_GONE) return -1;
+    if (!out) return (int)sizeof(BagStateRec);
+    const Env &e = *g->envs[size_t(env)];
+    auto *r = new BagStateRec();
+    std::memset(r, 0, sizeof *r);
+    r->num_platforms = int(e.bagPlatforms.size()); r->num_levels = e.bagNumLevels; r->finished = e.bagFinished;
+    for (int k = 0; k < 4; ++k) r->level_y[k] = e.bagLevelY[k];
+    for (int i = 0; i < MAX_AGENTS; ++i) { r->sec_before[i] = e.bagSecBefore[i]; r->last_platform[i] = e.bagLast[i]; }
+    for (size_t t = 0; t < e.bagTemps.size(); ++t) {
+        const Env::BagTemp &tp = e.bagTemps[t];
+        r->temps[t].plat = tp.plat; r->temps[t].away = int(lroundf((tp.tr.x - tp.base.x) / BAG_AWAY));
+        r->temps[t].sxz = tp.sc.x; r->temps[t].sy = tp.sc.y;
+    }
+    std::memset(r->cell, 0xff, sizeof r->cell);
+    for (size_t i = 0; i < e.bagPlatforms.size() && i < 976; ++i) {
+        const Env::BagPlatform &p = e.bagPlatforms[i];
+        const int status = p.temp < 0 ? 0 : e.bagGrid.count(std::make_tuple(p.x, p.y, p.z)) ? 1 : 2;
+        r->plat[i][0] = (int8_t)p.x; r->plat[i][1] = (int8_t)p.y; r->plat[i][2] = (int8_t)p.z; r->plat[i][3] = (int8_t)(p.level | status << 4);
+        const auto st = e.bagStates.find(int(i));
+        r->ticks[i] = st == e.bagStates.end() ? 0 : (uint8_t)st->second.remainingTicks;
+        r->tslot[i] = p.temp < 0 ? 0 : (uint8_t)p.temp;
+        r->takes += p.temp >= 0;
+        r->cell[p.level][p.x][p.z] = (int16_t)i;
+    }
+    std::memcpy(out, r, sizeof *r);
+    delete r;
+    return (int)sizeof(BagStateRec);
 }
 
 // ---- spec helpers ----

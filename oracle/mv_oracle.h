@@ -7,7 +7,7 @@
  *
  * What this is: a dependency-free CPU restatement of the reference's
  * VectorEnv::step() path for the scenarios TowerBuilding, Obstacles{Easy,Medium,Hard,Walls,Steps,Lava},
- * Collect, Rearrange, Sokoban, HexMemory, HexExplore and Empty
+ * Collect, Rearrange, Sokoban, HexMemory, HexExplore, BoxAGone and Empty
  *   reference: src/libs/env/src/vector_env.cpp:89-120 (step/reset order)
  *              src/libs/env/src/env.cpp:57-152          (Env::reset/step)
  *              src/libs/env/src/kinematic_character_controller.cpp (controller)
@@ -82,6 +82,9 @@ void mvo_debug_set_agent_yaw(mvo_gym *g, int env_idx, int agent_idx, float c, fl
 void mvo_debug_set_agent_velocity(mvo_gym *g, int env_idx, int agent_idx, float hvx, float hvz, float vvel);
 int mvo_snapshot_size(mvo_gym *g);
 void mvo_snapshot(mvo_gym *g, int env_idx, void *out);
+/* BoxAGone: the device's BoxAGoneState record (platform table, timers, temporary platforms, cell map) derived from the oracle's own
+ * containers; out = NULL: returns its size; -1: not a BoxAGone gym or bad env */
+int mvo_debug_boxagone_state(mvo_gym *g, int env_idx, void *out);
 
 /* ---- spec-level helpers exposed for known-answer tests ---- */
 /* Collect landscape noise: siv::PerlinNoise(seed).accumulatedOctaveNoise2D_0_1 (util/perlin_noise.hpp:315-318) */

@@ -228,3 +228,16 @@ def true_objective(st, num_agents, episode_len):
                 best_agent, best = i, st["sec_before"][i]
         return np.array([1.0 if i == best_agent else 0.0 for i in range(num_agents)], np.float32)
     return np.array([F32(st["sec_before"][0] / F32(episode_len))], np.float32)
+
+
+
+def forward_actions(seed, step, n):
+    """-> int32 [n, 6] multi-discrete actions of a policy that walks across the platforms: always forward, a jump every other tick on average,
+    a turn now and then, no looking up or down (the layout of megaverse_amd.rollout.sample_actions)"""
+    from megaverse_amd.rollout import sample_actions
+    a = sample_actions(seed, step, n)
+    out = np.zeros_like(a)
+    out[:, 1] = 1                                           # forward
+    out[:, 2] = np.where(a[:, 5] == 0, a[:, 2], 0)          # turn left / right, a third of the time at most
+    out[:, 3] = a[:, 3]                                     # jump
+    return out

@@ -74,6 +74,7 @@ def lib():
         L.mvo_set_action_masks.argtypes = [C.c_void_p, C.c_void_p]
         L.mvo_snapshot_size.argtypes = [C.c_void_p]
         L.mvo_snapshot.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.mvo_debug_boxagone_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.mvo_mt19937_nth.argtypes = [C.c_uint32, C.c_int]
         L.mvo_mt19937_nth.restype = C.c_uint32
         L.mvo_rand_range_seq.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -166,7 +167,8 @@ class OracleGym:
                   "memoryCollectGood", "memoryCollectBad", "exploreSolved",
                   "collectSingleGood", "collectSingleBad", "collectAll", "collectAbyss",
                   "rearrangeOneMoreObjectCorrectPosition", "rearrangeAllObjectsCorrectPosition",
-                  "sokobanBoxOnTarget", "sokobanBoxLeavesTarget", "sokobanAllBoxesOnTarget"):
+                  "sokobanBoxOnTarget", "sokobanBoxLeavesTarget", "sokobanAllBoxesOnTarget",
+                  "boxagoneTouchedFloor", "boxagonePerStepReward"):
             f = C.c_int(0)
             v = self.L.mvo_get_reward_shaping(self.g, env_idx, agent_idx, k.encode(), C.byref(f))
             if f.value:
@@ -185,6 +187,14 @@ class OracleGym:
         assert self.L.mvo_snapshot_size(self.g) == SNAP.itemsize, (self.L.mvo_snapshot_size(self.g), SNAP.itemsize)
         buf = np.zeros(1, SNAP)
         self.L.mvo_snapshot(self.g, env_idx, buf.ctypes.data)
+        return buf[0]
+
+    def boxagone_state(self, env_idx):
+        """BoxAGone: the device's BoxAGoneState record (tests/boxagone_model.STATE) as the oracle's containers describe it"""
+        import boxagone_model
+        assert self.L.mvo_debug_boxagone_state(self.g, env_idx, None) == boxagone_model.STATE.itemsize
+        buf = np.zeros(1, boxagone_model.STATE)
+        assert self.L.mvo_debug_boxagone_state(self.g, env_idx, buf.ctypes.data) == boxagone_model.STATE.itemsize
         return buf[0]
 
     def close(self):

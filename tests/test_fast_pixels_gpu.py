@@ -60,7 +60,7 @@ def test_fast_pixels_within_tolerance(hip, scenario, A, W, H):
 # the scenarios the matrix above leaves out (wall caps / goal pads / pushable boxes of Sokoban, the bare Empty room, the other
 # Obstacles variants' walls, steps and lava slabs), at the headline size and at a ragged one
 @pytest.mark.parametrize("scenario,A", [("Sokoban", 2), ("Empty", 2), ("ObstaclesMedium", 1), ("ObstaclesWalls", 2), ("ObstaclesSteps", 1),
-                                        ("ObstaclesLava", 2)])
+                                        ("ObstaclesLava", 2), ("BoxAGone", 2)])
 @pytest.mark.parametrize("W,H", [(128, 128), (48, 20)])
 def test_fast_pixels_within_tolerance_other_scenarios(hip, scenario, A, W, H):
     _fast_vs_oracle(scenario, A, W, H)
@@ -94,7 +94,7 @@ def test_fast_hires_within_tolerance(hip):
 
 @pytest.mark.parametrize("scenario,N,A,W,H", [("TowerBuilding", 1024, 1, 128, 128), ("TowerBuilding", 512, 4, 128, 128),
                                               ("ObstaclesHard", 512, 1, 128, 128), ("Collect", 256, 1, 64, 64),
-                                              ("HexMemory", 256, 2, 64, 64)])
+                                              ("HexMemory", 256, 2, 64, 64), ("BoxAGone", 1024, 1, 128, 128)])
 def test_fast_equals_exact_within_tolerance_at_full_size(hip, scenario, N, A, W, H):
     """BASELINE.json sizes, the whole slab (against the oracle's raster: sampled envs, tests/test_full_size_oracle_gpu.py): the same gym rendered by both kernels after a rollout with natural
     auto-resets; every frame of the slab compared."""
@@ -117,7 +117,7 @@ def test_fast_equals_exact_within_tolerance_at_full_size(hip, scenario, N, A, W,
 
 @pytest.mark.parametrize("scenario,N,A,W,H", [("TowerBuilding", 64, 1, 128, 128), ("TowerBuilding", 16, 4, 128, 72), ("ObstaclesHard", 32, 2, 64, 64),
                                               ("Rearrange", 16, 2, 128, 128), ("Collect", 16, 2, 128, 128), ("HexMemory", 8, 2, 128, 128),
-                                              ("HexExplore", 8, 1, 50, 30), ("Sokoban", 16, 1, 33, 17)])
+                                              ("HexExplore", 8, 1, 50, 30), ("Sokoban", 16, 1, 33, 17), ("BoxAGone", 16, 2, 128, 128)])
 def test_pixels_per_lane_variants_agree(hip, monkeypatch, scenario, N, A, W, H):
     """raster_fast_kernel with one and with two pixels per lane (tiles of 16 x 4 / 16 x 8 pixels): the per-pixel arithmetic is the same and
     the culling is conservative, so every byte of the slab must be equal (MV_FAST_PPL is read at every launch)."""
@@ -138,7 +138,7 @@ def test_pixels_per_lane_variants_agree(hip, monkeypatch, scenario, N, A, W, H):
 @pytest.mark.parametrize("scenario,N,A,W,H,ppl", [("TowerBuilding", 1024, 1, 128, 128, "2"), ("TowerBuilding", 256, 4, 128, 128, "2"), ("TowerBuilding", 128, 1, 128, 72, "1"),
                                                   ("TowerBuilding", 64, 2, 64, 64, ""), ("ObstaclesHard", 256, 2, 128, 128, ""), ("ObstaclesLava", 64, 1, 50, 30, "2"),
                                                   ("Sokoban", 128, 1, 128, 128, ""), ("Rearrange", 64, 2, 128, 128, ""), ("Empty", 64, 1, 33, 17, "1"),
-                                                  ("Empty", 128, 2, 128, 128, "")])
+                                                  ("Empty", 128, 2, 128, 128, ""), ("BoxAGone", 256, 1, 128, 128, "")])
 def test_planar_tiles_change_no_byte(hip, monkeypatch, scenario, N, A, W, H, ppl):
     """raster_fast_kernel's planar-tile path (a tile that one face of one world box covers: one reciprocal per pixel, face constants wave-uniform)
     against the general path (MV_PLANAR=0, read at every launch) on the same state: the classification has a margin far above the rounding of
@@ -171,7 +171,7 @@ def test_planar_tiles_change_no_byte(hip, monkeypatch, scenario, N, A, W, H, ppl
 
 
 @pytest.mark.parametrize("scenario,N,A,W,H", [("HexMemory", 96, 1, 128, 128), ("HexExplore", 64, 2, 128, 128), ("HexMemory", 128, 1, 64, 64), ("Collect", 128, 1, 128, 128),
-                                              ("Collect", 64, 2, 50, 30), ("HexExplore", 40, 1, 33, 17)])
+                                              ("Collect", 64, 2, 50, 30), ("HexExplore", 40, 1, 33, 17), ("BoxAGone", 128, 1, 128, 128)])
 def test_depth_classes_change_no_byte(hip, monkeypatch, scenario, N, A, W, H):
     """long lists (Collect, Hex): the frame setup deals the visible primitives into depth classes, nearest first, and the observation pass stops walking
     the list where everything nearer has covered a tile (mv_frame.h: DepthSortScratch; raster_glist_body) -- against a gym whose lists stay as found

@@ -94,7 +94,8 @@ def test_collect_rewards_are_integers_of_the_shaping_table_and_diamonds_only_dis
 
 
 @pytest.mark.parametrize("scenario,A,W,H", [("TowerBuilding", 2, 64, 64), ("ObstaclesHard", 1, 64, 36), ("Collect", 2, 48, 48), ("Rearrange", 2, 64, 64),
-                                            ("Sokoban", 1, 64, 64), ("HexMemory", 2, 40, 24), ("HexExplore", 1, 40, 24), ("Empty", 2, 33, 17)])
+                                            ("Sokoban", 1, 64, 64), ("HexMemory", 2, 40, 24), ("HexExplore", 1, 40, 24), ("Empty", 2, 33, 17),
+                                            ("BoxAGone", 2, 64, 36)])
 def test_tiled_raster_equals_brute_force(scenario, A, W, H, monkeypatch):
     """the tile-culled software raster bench.py times as the CPU baseline's raster leg draws the image of the brute-force checker, byte for byte:
     the culling rectangles are conservative, the per-pixel arithmetic and the draw order are the same code"""
