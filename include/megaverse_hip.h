@@ -208,6 +208,10 @@ int mv_debug_snapshot_size(const mv_gym *g);
 int mv_debug_snapshot(mv_gym *g, int32_t env_idx, void *out_host);
 /* BoxAGone: env env_idx's platform table, temporary ring, timers and cell map (BoxAGoneState, mv_types.h); out_host == NULL: its size */
 int mv_debug_boxagone_state(mv_gym *g, int32_t env_idx, void *out_host);
+/* Football: env env_idx's ball (FootballState, mv_types.h); out_host == NULL: its size.  The setter places the ball (position, drawn radius, velocity,
+   angular velocity, pending force) for known-answer tests. */
+int mv_debug_football_state(mv_gym *g, int32_t env_idx, void *out_host);
+int mv_debug_set_football_state(mv_gym *g, int32_t env_idx, const void *in_host);
 int mv_debug_rng(int32_t device, uint32_t seed, int32_t what, const int32_t *lo, const int32_t *hi, int32_t n, void *out_host);
 int mv_debug_math(int32_t device, int32_t what, const float *a, const float *b, int32_t n, float *out_host);
 /* Host-only (no device): the n-th (1-based) episode an env seeded with env_seed generates for a host-generated
@@ -223,6 +227,9 @@ int mv_debug_feeder_selftest(const char *scenario, int32_t num_envs, int32_t num
 /* Host-only: the first n episodes of the Sokoban level generator (scenario_sokoban.cpp:80-170; its kernels come next) as n
  * packed records; out == NULL: record size.  Returns n, -1 on error. */
 int mv_debug_generate_sokoban(int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes);
+/* Host-only (no device): Football's episodes 1..n of an env seeded with env_seed, as n FootballBlob records (mv_types.h); out == NULL: one record's
+   size.  Returns n. */
+int mv_debug_generate_football(int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes);
 
 /* Collect's episode generator as it runs on the DEVICE (megaverse_amd/csrc/mv_collect_draw.h; the product's feeder uses it where mv_host_generator_threads
  * says 0 for a Collect gym).  _host: the same code compiled for the CPU, no device needed -- the n-th episode of an env seeded

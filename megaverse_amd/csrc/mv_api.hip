@@ -225,6 +225,7 @@ bool scenario_from_name(const std::string &scen, int &scenario, ObstacleConfig &
     else if (scen == "hexmemory") scenario = SCN_HEX_MEMORY;                           // scenarios/init.hpp:47
     else if (scen == "hexexplore") scenario = SCN_HEX_EXPLORE;                         // scenarios/init.hpp:48
     else if (scen == "boxagone") scenario = SCN_BOXAGONE;                              // scenarios/init.hpp:50
+    else if (scen == "football") scenario = SCN_FOOTBALL;                              // scenarios/init.hpp:51
     else return false;
     return true;
 }
@@ -285,7 +286,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     if (!scenario_from_name(scen, scenario, oc))
         return fail("Unknown scenario " + scen
                     + " (this build accelerates: TowerBuilding, ObstaclesEasy/Medium/Hard/Walls/Steps/Lava, Collect, Rearrange, Sokoban, HexMemory, "
-                         "HexExplore, BoxAGone, Empty)");
+                         "HexExplore, BoxAGone, Football, Empty)");
     std::vector<std::string> levelFiles;
     if (scenario == SCN_SOKOBAN) {   // SokobanScenario's constructor looks the level files up (scenario_sokoban.cpp:40-78); none is fatal there too
         levelFiles = find_boxoban_level_files();
@@ -310,16 +311,16 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     g->N = cfg->num_envs; g->A = cfg->num_agents_per_env;
     g->scenario = scenario;
     g->numShaping = scenario == SCN_TOWER || scenario == SCN_SOKOBAN ? 4 : scenario == SCN_REARRANGE || scenario == SCN_HEX_MEMORY || scenario == SCN_BOXAGONE ? 3
-                  : scenario == SCN_HEX_EXPLORE ? 2 : scenario == SCN_EMPTY ? 1 : 5;
+                  : scenario == SCN_HEX_EXPLORE ? 2 : scenario == SCN_EMPTY || scenario == SCN_FOOTBALL ? 1 : 5;
     g->shapingKeys = scenario == SCN_TOWER ? SHAPING_KEYS_TOWER : scenario == SCN_OBSTACLES ? SHAPING_KEYS_OBST
                    : scenario == SCN_COLLECT ? SHAPING_KEYS_COLLECT : scenario == SCN_SOKOBAN ? SHAPING_KEYS_SOKOBAN
                    : scenario == SCN_HEX_MEMORY ? SHAPING_KEYS_HEX_MEMORY : scenario == SCN_HEX_EXPLORE ? SHAPING_KEYS_HEX_EXPLORE
-                   : scenario == SCN_EMPTY ? SHAPING_KEYS_EMPTY : scenario == SCN_BOXAGONE ? SHAPING_KEYS_BOXAGONE : SHAPING_KEYS_REARRANGE;
-    // Resident episodes per env: two where an episode ends at its time limit only (TowerBuilding, Empty); THREE where a goal can end it early (the exit pad,
+                   : scenario == SCN_EMPTY || scenario == SCN_FOOTBALL ? SHAPING_KEYS_EMPTY : scenario == SCN_BOXAGONE ? SHAPING_KEYS_BOXAGONE : SHAPING_KEYS_REARRANGE;
+    // Resident episodes per env: two where an episode ends at its time limit only (TowerBuilding, Empty, Football); THREE where a goal can end it early (the exit pad,
     // every diamond collected, the level solved, the arrangement matched, the maze's target found): the host's run-ahead is bounded in TICKS (refill_episodes),
     // the status words are read back every 16th, and a lucky env can finish twice inside that window -- a third resident episode covers it where two starved
     // (ADVICE r05).
-    g->spares = scenario == SCN_TOWER || scenario == SCN_EMPTY ? 2 : 3;
+    g->spares = scenario == SCN_TOWER || scenario == SCN_EMPTY || scenario == SCN_FOOTBALL ? 2 : 3;
     g->envOffset = cfg->total_envs > 0 ? cfg->env_offset : 0;
     g->envStride = cfg->total_envs > 0 && cfg->env_stride > 1 ? cfg->env_stride : 1;
     g->gv.sample_on = 0; g->gv.sample_seed = g->gv.sample_step = 0;
@@ -331,13 +332,13 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     gv.num_envs = g->N; gv.num_agents = g->A;
     const bool obstacles = scenario == SCN_OBSTACLES || scenario == SCN_EMPTY, collect = scenario == SCN_COLLECT,
             rearrange = scenario == SCN_REARRANGE, sokoban = scenario == SCN_SOKOBAN;
-    const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE, boxagone = scenario == SCN_BOXAGONE;
-    const bool hostEpisodes = obstacles || collect || rearrange || sokoban || hex || boxagone;
+    const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE, boxagone = scenario == SCN_BOXAGONE, football = scenario == SCN_FOOTBALL;
+    const bool hostEpisodes = obstacles || collect || rearrange || sokoban || hex || boxagone || football;
     gv.scenario = scenario;
     gv.box_stride = collect ? COLLECT_MAX_BOXES : MAX_BOXES;
     gv.reward_stride = collect ? COLLECT_MAX_REWARDS : MAX_REWARDS;
     g->blobBytes = collect ? sizeof(CollectBlob) : obstacles ? sizeof(EpisodeBlob) : rearrange ? sizeof(RearrangeBlob)
-                                    : sokoban ? sizeof(SokobanBlob) : hex ? sizeof(HexBlob) : boxagone ? sizeof(BoxAGoneBlob) : sizeof(TowerBlob);
+                                    : sokoban ? sizeof(SokobanBlob) : hex ? sizeof(HexBlob) : boxagone ? sizeof(BoxAGoneBlob) : football ? sizeof(FootballBlob) : sizeof(TowerBlob);
     // ONE arena for all simulator state: a step touches ~8 arrays per env, separate small allocations
     // cost a TLB miss each per wave (measured: 83 % of the physics kernel's time was spent waiting on
     // ~30 memory operations); one large allocation is backed by large pages.
@@ -351,8 +352,9 @@ int mv_create(const mv_config *cfg, mv_gym **out)
                  szRewObj = hostEpisodes ? up(N * (size_t)gv.reward_stride * sizeof(MovableObject)) : 0,
                  szHeight = collect ? up(N * (size_t)HM_BYTES) : 0, szItems = rearrange ? up(N * MAX_ITEMS * sizeof(ArrangementItem))
                                          : 0, szCells = sokoban ? up(N * (size_t)(SOKO_DIM * SOKO_DIM)) : 0,
-                 szHexB = hex || boxagone ? up(N * (size_t)HEX_MAX_BOXES * sizeof(HexRec)) : 0, szHexO = hex ? up(N * (size_t)HEX_MAX_OBJS * sizeof(HexRec)) : 0,
-                 szBag = boxagone ? up(N * sizeof(BoxAGoneState)) : 0,
+                 szHexB = hex || boxagone || football ? up(N * (size_t)HEX_MAX_BOXES * sizeof(HexRec)) : 0,
+                 szHexO = hex || football ? up(N * (size_t)HEX_MAX_OBJS * sizeof(HexRec)) : 0,
+                 szBag = boxagone ? up(N * sizeof(BoxAGoneState)) : 0, szFb = football ? up(N * sizeof(FootballState)) : 0,
                                    szBlobs = up(N * g->blobBytes * (size_t)g->spares), szCnt = up((N + 2) * sizeof(int32_t)),
                                                 szGen = hostEpisodes ? 0 : up(N * sizeof(TowerGen));
     gv.vis_stride = hex ? 2048 : collect || boxagone ? 1024 : 256;   // (BoxAGone: <= 8 + 972 + 24 boxes, all in the world frame)
@@ -383,7 +385,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     const bool depthSortOn = !(getenv("MV_DEPTH_SORT") && atoi(getenv("MV_DEPTH_SORT")) == 0);
     const size_t szSort = gv.vis_stride > 256 && depthSortOn ? up(NA * (size_t)gv.vis_stride * 40) : 0;
     const size_t total = szSort + szHdr + szBoxes + szObj + szAg + szAct + szRew + szDone + szObjv + szMd + (hostEpisodes ? 0 : szChunk) + szObs + szTerrain +
-                         szRewObj + szHeight + szItems + szCells + szHexB + szHexO + szBag + szBlobs + szCnt + szGen + (size_t)g->slots * szParity + szHist;
+                         szRewObj + szHeight + szItems + szCells + szHexB + szHexO + szBag + szFb + szBlobs + szCnt + szGen + (size_t)g->slots * szParity + szHist;
     {
         hipError_t e_ = hipMalloc((void **)&g->arena, total);
         if (e_ != hipSuccess) {
@@ -422,6 +424,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
         if (sokoban) { gv.soko_cells = p; p += szCells; }
         if (hex) { gv.hex_boxes = (HexRec *)p; p += szHexB; gv.hex_objs = (HexRec *)p; p += szHexO; }
         if (boxagone) { gv.hex_boxes = (HexRec *)p; p += szHexB; gv.bag = (BoxAGoneState *)p; p += szBag; }
+        if (football) { gv.hex_boxes = (HexRec *)p; p += szHexB; gv.hex_objs = (HexRec *)p; p += szHexO; gv.fb = (FootballState *)p; p += szFb; }
         gv.lpt_hist = (int32_t *)p; p += szHist;
         gv.sort_scratch = szSort ? p : nullptr; p += szSort;
         gv.depth_sort = 0;

@@ -196,8 +196,9 @@ int mv_debug_generate_episode(const char *scenario_name, int32_t num_agents, int
 {
     int scenario = SCN_TOWER;
     ObstacleConfig oc;
-    if (!scenario_name || !scenario_from_name(lower(scenario_name), scenario, oc) || scenario == SCN_TOWER || scenario == SCN_SOKOBAN || scenario == SCN_EMPTY)
-        return fail("mv_debug_generate_episode: the Obstacles family, Collect, Rearrange, HexMemory, HexExplore and BoxAGone (Sokoban: mv_debug_generate_sokoban)");
+    if (!scenario_name || !scenario_from_name(lower(scenario_name), scenario, oc) || scenario == SCN_TOWER || scenario == SCN_SOKOBAN || scenario == SCN_EMPTY
+        || scenario == SCN_FOOTBALL)
+        return fail("mv_debug_generate_episode: the Obstacles family, Collect, Rearrange, HexMemory, HexExplore and BoxAGone (Sokoban: mv_debug_generate_sokoban, Football: mv_debug_generate_football)");
     if (num_agents < 1 || num_agents > MAX_AGENTS || n < 1) return fail("mv_debug_generate_episode: bad arguments");
     const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE;
     const size_t bytes = scenario == SCN_COLLECT ? sizeof(CollectBlob) : scenario == SCN_REARRANGE ? sizeof(RearrangeBlob)
@@ -240,7 +241,8 @@ int mv_debug_feeder_selftest(const char *scenario_name, int32_t num_envs, int32_
 {
     int scenario = SCN_TOWER;
     ObstacleConfig oc;
-    if (!scenario_name || !scenario_from_name(lower(scenario_name), scenario, oc) || scenario == SCN_TOWER || scenario == SCN_SOKOBAN || scenario == SCN_EMPTY)
+    if (!scenario_name || !scenario_from_name(lower(scenario_name), scenario, oc) || scenario == SCN_TOWER || scenario == SCN_SOKOBAN || scenario == SCN_EMPTY
+        || scenario == SCN_FOOTBALL)
         return fail("mv_debug_feeder_selftest: the Obstacles family, Collect, Rearrange, HexMemory and HexExplore");
     const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE;
     const size_t bytes = scenario == SCN_COLLECT ? sizeof(CollectBlob) : scenario == SCN_REARRANGE
@@ -310,6 +312,50 @@ int mv_debug_feeder_selftest(const char *scenario_name, int32_t num_envs, int32_
 
 // Host-only test hook for the Sokoban generator: the first `n` episodes an env
 // seeded with env_seed generates from the level files under $BOXOBAN_LEVELS, as n consecutive SokobanBlob records.
+// Host-only test hook: episodes 1..n an env seeded with `env_seed` generates for Football, as the FootballBlob records the reset kernel consumes.
+// out = null: returns the record's size.
+int mv_debug_generate_football(int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes)
+{
+    if (!out) return (int)sizeof(FootballBlob);
+    if (num_agents < 1 || num_agents > MAX_AGENTS || n < 1 || (size_t)out_bytes < (size_t)n * sizeof(FootballBlob))
+        return fail("mv_debug_generate_football: bad arguments");
+    std::mt19937 rng;
+    rng.seed((unsigned long)env_seed);
+    for (int i = 0; i < n; ++i) generate_football_episode(rng, num_agents, base_episode_len, reinterpret_cast<FootballBlob *>(out)[i]);
+    return n;
+}
+
+// Test hooks: env `env`'s FootballState (mv_types.h: the ball) as the device holds it after everything enqueued so far; and a ball placed by a test
+// (position, velocity, angular velocity, pending force; its drawing record follows).  out = null: returns the record's size.
+int mv_debug_football_state(mv_gym *g, int32_t env, void *out)
+{
+    if (check(g)) return -1;
+    if (g->scenario != SCN_FOOTBALL || !g->gv.fb) return fail("mv_debug_football_state: not a Football gym");
+    if (!out) return (int)sizeof(FootballState);
+    if (env < 0 || env >= g->N) return fail("mv_debug_football_state: bad env");
+    HIP_TRY(hipStreamSynchronize(g->simStream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    HIP_TRY(hipMemcpy(out, g->gv.fb + env, sizeof(FootballState), hipMemcpyDeviceToHost));
+    return (int)sizeof(FootballState);
+}
+
+int mv_debug_set_football_state(mv_gym *g, int32_t env, const void *in)
+{
+    if (check(g)) return -1;
+    if (g->scenario != SCN_FOOTBALL || !g->gv.fb) return fail("mv_debug_set_football_state: not a Football gym");
+    if (env < 0 || env >= g->N || !in) return fail("mv_debug_set_football_state: bad arguments");
+    FootballState s;
+    std::memcpy(&s, in, sizeof s);
+    HexRec r;
+    r.a[0] = s.pos[0]; r.a[1] = s.pos[1]; r.a[2] = s.pos[2]; r.meta = HEX_SPHERE;
+    r.b[0] = s.radius; r.b[1] = s.radius; r.b[2] = s.radius; r.color = 0xffb400;   // (mv_tick_football.h: ball_rec)
+    if (sim_join(g)) return -1;
+    HIP_TRY(hipMemcpyAsync(g->gv.fb + env, &s, sizeof s, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(g->gv.hex_objs + (size_t)env * HEX_MAX_OBJS, &r, sizeof r, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));   // (s, r: host stack)
+    return 0;
+}
+
 int mv_debug_generate_sokoban(int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes)
 {
     if (!out) return (int)sizeof(SokobanBlob);

@@ -408,6 +408,8 @@ int mv_group_create(mv_gym *const *gyms, int32_t n, mv_group **out)
         for (int j = 0; j < i; ++j) if (gyms[j] == g) return fail("mv_group_create: the same gym twice");
         if (g->scenario == SCN_BOXAGONE)   // (its tick is not in the union kernels, mv_step_union.hip: tick_any)
             return fail("mv_group_create: BoxAGone cannot be stepped in a group of gyms; step it as a gym of its own (MultiTaskGym: MV_MULTITASK_UNION=0)");
+        if (g->scenario == SCN_FOOTBALL)   // (nor is Football's)
+            return fail("mv_group_create: Football cannot be stepped in a group of gyms; step it as a gym of its own (MultiTaskGym: MV_MULTITASK_UNION=0)");
         if (g->device != L->device || g->w != L->w || g->h != L->h || g->A != L->A || g->stream != L->stream || g->pipelined != L->pipelined)
             return fail("mv_group_create: the gyms of a group share device, observation size, agents per env, stream (mv_set_stream first) and pipelining");
     }

@@ -151,6 +151,11 @@ void EpisodeFeeder::generate(int env)
         generate_boxagone_episode(rng_[env], num_agents_, base_len_, b);
         b.seq = seq;
         used = offsetof(BoxAGoneBlob, platforms) + size_t(b.num_platforms) * sizeof(BagPlatform);   // the platform list is last: used prefix only
+    } else if (scenario_ == SCN_FOOTBALL) {
+        FootballBlob &b = *reinterpret_cast<FootballBlob *>(slot);
+        generate_football_episode(rng_[env], num_agents_, base_len_, b);
+        b.seq = seq;
+        used = sizeof(FootballBlob);
     } else {
         CollectBlob &b = *reinterpret_cast<CollectBlob *>(slot);
         generate_collect_episode(rng_[env], num_agents_, base_len_, b);

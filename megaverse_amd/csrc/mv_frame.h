@@ -255,10 +255,10 @@ __device__ __forceinline__ void frame_setup_body(const GymView &gv, const int fr
         s_cam[tid] = cam;
     }
     const int scen = hdr->scenario;
-    // Hex scenarios, and BoxAGone: its room, platforms and temporary platforms are HexRec records too, all in the world frame, rewritten by its tick
-    // (mv_tick_boxagone.h).  The three wall-frame cameras it is given are unused (meta & 15 == 0 on every record); a flag of its own for the record
-    // list costs TowerBuilding's and Collect's multi-agent step kernels a VGPR each.
-    const bool hex = scen == SCN_HEX_MEMORY || scen == SCN_HEX_EXPLORE || scen == SCN_BOXAGONE;
+    // Hex scenarios, BoxAGone and Football: their rooms, platforms, temporary platforms and the ball are HexRec records too, all in the world frame,
+    // rewritten by their ticks (mv_tick_boxagone.h, mv_tick_football.h).  The three wall-frame cameras they are given are unused (meta & 15 == 0 on
+    // every box); a flag of their own for the record list costs TowerBuilding's and Collect's multi-agent step kernels a VGPR each.
+    const bool hex = scen == SCN_HEX_MEMORY || scen == SCN_HEX_EXPLORE || scen == SCN_BOXAGONE || scen == SCN_FOOTBALL;
     if (hex && tid >= MAX_AGENTS && tid < MAX_CAMS) s_cam[tid] = hex_frame(tid - MAX_AGENTS);
     sync();
     if (tid < A || (hex && tid >= MAX_AGENTS && tid < MAX_CAMS)) {

@@ -44,6 +44,9 @@ void generate_hex_memory_episode(std::mt19937 &rng, int num_agents, float base_e
 // Advances `rng` exactly like Env::reset + BoxAGoneScenario::reset + spawnAgents + addEpisodeDrawables and fills `out`.
 void generate_boxagone_episode(std::mt19937 &rng, int num_agents, float base_episode_len, BoxAGoneBlob &out);
 
+// Advances `rng` exactly like Env::reset + FootballScenario::reset + spawnAgents + addEpisodeDrawables and fills `out`.
+void generate_football_episode(std::mt19937 &rng, int num_agents, float base_episode_len, FootballBlob &out);
+
 // Sokoban keeps state across episodes: the shuffled levels of the file picked last (SokobanScenario::levels)
 struct SokobanLevels {
     std::vector<std::vector<std::string>> pending;

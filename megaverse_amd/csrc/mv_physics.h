@@ -37,9 +37,11 @@ constexpr float OBJ_COLL_HALF = 0.39f * 1.15f;
 constexpr float OBJ_COLL_YOFF = -0.05f;
 
 struct Col {
-    int kind;   // 0 none, 1 box (bounds already grown by CAP_HH in y), 2 vertical capsule, 3 + k (OBB builds only): box in hex wall frame k
+    int kind;   // 0 none, 1 box (bounds already grown by CAP_HH in y), 2 vertical capsule, 3 + k (OBB builds only): box in hex wall frame k,
+                // COL_BALL (BALL builds only): a sphere -- lo = its centre, hi.x = CAP_HH, hi.y = CAP_R + its radius (the capsule's Minkowski sum with it)
     V3 lo, hi;
 };
+constexpr int COL_BALL = 7;
 
 // Hex scenarios: the three directions a honeycomb's walls run in, as rotations about Y (mv_gen_hex.cpp); frame k: local = Ry^T world
 __device__ __forceinline__ V3 hex_to_local(int k, V3 p)
@@ -176,15 +178,18 @@ __shared__ unsigned s_cast_dbg[8];
 #else
 #define MV_CAST_ITERS(n) do { } while (0)
 #endif
-template <bool OBB = false>
+template <bool OBB = false, bool BALL = false>
 __device__ __forceinline__ bool convex_cast(const Col &col, V3 p, V3 d, float &fraction, V3 &normal, int *iters = nullptr)
 {
-    const bool boxLike = col.kind != 2;
+    static_assert(!(OBB && BALL), "a ball and hex wall frames: never in one build");
+    const bool ball = BALL && col.kind == COL_BALL;
+    const bool boxLike = col.kind != 2 && !ball;
+    const float capR = ball ? col.hi.y : 2 * CAP_R;
     const int fr = col.kind - 3;
     if (OBB && col.kind >= 3) { p = hex_to_local(fr, p); d = hex_to_local(fr, d); }
     float lambda = 0.0f, lastLambda = 0.0f;
     int numIter = 0;
-    Raw c = boxLike ? raw_box(p, col.lo, col.hi, CAP_R) : raw_capsule(p, col.lo, col.hi.x, 2 * CAP_R);
+    Raw c = boxLike ? raw_box(p, col.lo, col.hi, CAP_R) : raw_capsule(p, col.lo, col.hi.x, capR);
     float dist = c.dist + ALLOWED_CCD_PEN;
     float proj = -dot(d, c.v);   // |v| times Bullet's projected velocity
     if (proj <= SIMD_EPS * c.d) return false;
@@ -197,7 +202,7 @@ __device__ __forceinline__ bool convex_cast(const Col &col, V3 p, V3 d, float &f
         if (lambda <= lastLambda) return false;
         lastLambda = lambda;
         const V3 x = v3(p.x + lambda * d.x, p.y + lambda * d.y, p.z + lambda * d.z);
-        c = boxLike ? raw_box(x, col.lo, col.hi, CAP_R) : raw_capsule(x, col.lo, col.hi.x, 2 * CAP_R);
+        c = boxLike ? raw_box(x, col.lo, col.hi, CAP_R) : raw_capsule(x, col.lo, col.hi.x, capR);
         dist = c.dist + ALLOWED_CCD_PEN;
         MV_CAST_ITERS(numIter + 1);
         if (++numIter > CAST_MAX_ITER) return false;
@@ -214,10 +219,10 @@ __device__ __forceinline__ bool convex_cast(const Col &col, V3 p, V3 d, float &f
 // of the collider somewhere on the path, i.e. the centre within CAP_R - 0.039 of the (grown) box: impossible when the path's bounding box,
 // widened by the full CAP_R, misses the box.  Exact (it only ever skips casts that return false), and it keeps the correctly rounded sqrt and
 // divide of a first iteration away from the many colliders that are nowhere near the agent.
-template <bool OBB = false>
+template <bool OBB = false, bool BALL = false>
 __device__ __forceinline__ bool cast_can_hit(const Col &col, V3 p, V3 d)
 {
-    if (col.kind == 2) return true;
+    if (col.kind == 2 || (BALL && col.kind == COL_BALL)) return true;
     if (OBB && col.kind >= 3) { p = hex_to_local(col.kind - 3, p); d = hex_to_local(col.kind - 3, d); }
     const V3 q = v3(p.x + d.x, p.y + d.y, p.z + d.z);
     return fmin_sel(p.x, q.x) - CAP_R <= col.hi.x && fmax_sel(p.x, q.x) + CAP_R >= col.lo.x &&
@@ -226,7 +231,7 @@ __device__ __forceinline__ bool cast_can_hit(const Col &col, V3 p, V3 d)
 }
 
 // closest accepted hit over all colliders of the wave; ties resolved towards the lowest slot
-template <int NC, bool OBB = false>
+template <int NC, bool OBB = false, bool BALL = false>
 __device__ __forceinline__ bool sweep(const Col (&col)[NC], V3 from, V3 to, V3 up, float minSlopeDot, float &fraction,
                                       V3 &normal)
 {
@@ -245,9 +250,9 @@ __device__ __forceinline__ bool sweep(const Col (&col)[NC], V3 from, V3 to, V3 u
 #endif
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
-        if (col[k].kind != 0 && cast_can_hit<OBB>(col[k], from, d)) {
+        if (col[k].kind != 0 && cast_can_hit<OBB, BALL>(col[k], from, d)) {
             float f; V3 n;
-            if (convex_cast<OBB>(col[k], from, d, f, n MV_ITS_ARG) && (len2(n) > 0.0001f) && (f < 1.0f) && !(dot(up, n) < minSlopeDot)) {
+            if (convex_cast<OBB, BALL>(col[k], from, d, f, n MV_ITS_ARG) && (len2(n) > 0.0001f) && (f < 1.0f) && !(dot(up, n) < minSlopeDot)) {
                 fb[k] = __float_as_uint(f);
                 nn[k] = n;
             }
@@ -292,7 +297,7 @@ __device__ __forceinline__ bool sweep(const Col (&col)[NC], V3 from, V3 to, V3 u
 
 // push out of the first (lowest slot) collider that is penetrated deeper than MAX_PEN_DEPTH.  Every lane only needs the signed distance of
 // its colliders; the contact normal is normalised for the winner alone (one divide per call; same values as closest().n)
-template <int NC, bool OBB = false>
+template <int NC, bool OBB = false, bool BALL = false>
 __device__ __forceinline__ bool recover_from_penetration(const Col (&col)[NC], V3 &pos)
 {
     Raw c[NC];
@@ -304,6 +309,7 @@ __device__ __forceinline__ bool recover_from_penetration(const Col (&col)[NC], V
         if (col[k].kind == 1) c[k] = raw_box(pos, col[k].lo, col[k].hi, CAP_R);
         else if (OBB && col[k].kind >= 3) c[k] = raw_box(hex_to_local(col[k].kind - 3, pos), col[k].lo, col[k].hi, CAP_R);
         else if (col[k].kind == 2) c[k] = raw_capsule(pos, col[k].lo, col[k].hi.x, 2 * CAP_R);
+        else if (BALL && col[k].kind == COL_BALL) c[k] = raw_capsule(pos, col[k].lo, col[k].hi.x, col[k].hi.y);
         if (col[k].kind != 0) pen[k] = c[k].dist < -MAX_PEN_DEPTH;
     }
     // lowest slot first: slot = lane + 64 * k
@@ -332,23 +338,23 @@ __device__ __forceinline__ bool recover_from_penetration(const Col (&col)[NC], V
 
 // "while (recover()) { if (++n > 4) break; }" == at most five calls.  Written as straight-line
 // predicated code: no wave-level op (ballot/shuffle) sits inside a loop with a data-dependent exit.
-template <int NC, bool OBB = false>
+template <int NC, bool OBB = false, bool BALL = false>
 __device__ __forceinline__ void recover_up_to_5(const Col (&col)[NC], V3 &pos)
 {
     bool more = true;
 #pragma unroll 1
     for (int it = 0; it < 5; ++it)   // (a counted loop, not five copies: the tick's code is ~100 KB as it is; `more` is wave-uniform)
-        if (more) more = recover_from_penetration<NC, OBB>(col, pos);
+        if (more) more = recover_from_penetration<NC, OBB, BALL>(col, pos);
 }
 // the same, telling `seen` every position on the way (player_step's reach: two opposite pushes can leave the capsule where it started -- the
 // positions in between were still occupied)
-template <int NC, bool OBB, class Seen>
+template <int NC, bool OBB, bool BALL, class Seen>
 __device__ __forceinline__ void recover_up_to_5(const Col (&col)[NC], V3 &pos, Seen seen)
 {
     bool more = true;
 #pragma unroll 1
     for (int it = 0; it < 5; ++it)
-        if (more) { more = recover_from_penetration<NC, OBB>(col, pos); seen(pos); }
+        if (more) { more = recover_from_penetration<NC, OBB, BALL>(col, pos); seen(pos); }
 }
 
 __device__ __forceinline__ bool on_ground(const AgentState &a) { return (fabsf(a.vvel) < SIMD_EPS) && (fabsf(a.voffset) < SIMD_EPS); }
@@ -389,7 +395,8 @@ __device__ __forceinline__ V3 lerp3(V3 a, V3 b, float rt)
 // reach2 (optional): the largest squared HORIZONTAL distance from the start position of any point the controller sweeps between or stands on this
 // tick -- every sweep runs between two of the points recorded here, so the capsule's axis never leaves that circle (mv_tick_tower.h: which agents of
 // an env can run their controllers at the same time).  Recording it changes nothing else.
-template <int NC, bool OBB = false>
+// BALL: the colliders may hold a sphere (COL_BALL: Football's ball; only its kernels are built with it)
+template <int NC, bool OBB = false, bool BALL = false>
 __device__ __forceinline__ void player_step(AgentState &a, const Col (&col)[NC], float dt, float *reach2 = nullptr)
 {
     V3 cur = v3(a.pos[0], a.pos[1], a.pos[2]);
@@ -413,12 +420,12 @@ __device__ __forceinline__ void player_step(AgentState &a, const Col (&col)[NC],
         target = v3(cur.x, cur.y + stepHeight + (a.voffset > 0.0f ? a.voffset : 0.0f), cur.z);
         cur = target;
         float f; V3 n;
-        if (sweep<NC, OBB>(col, start, target, v3(0, -1, 0), MAX_SLOPE_COS, f, n)) {
+        if (sweep<NC, OBB, BALL>(col, start, target, v3(0, -1, 0), MAX_SLOPE_COS, f, n)) {
             if (dot(n, UP) > 0.0f) {
                 a.step_offset = stepHeight * f;
                 cur = lerp3(cur, target, f);
             }
-            recover_up_to_5<NC, OBB>(col, cur, reached);
+            recover_up_to_5<NC, OBB, BALL>(col, cur, reached);
             target = cur;
             if (a.voffset > 0) { a.voffset = 0.0f; a.vvel = 0.0f; a.step_offset = STEP_HEIGHT; }
         } else {
@@ -440,7 +447,7 @@ __device__ __forceinline__ void player_step(AgentState &a, const Col (&col)[NC],
                 const V3 negDir = cur - target;
                 float f = 1.0f; V3 n = v3(0, 0, 0);
                 bool hit = false;
-                if (!(cur.x == target.x && cur.y == target.y && cur.z == target.z)) hit = sweep<NC, OBB>(col, cur, target, negDir, 0.0f, f, n);
+                if (!(cur.x == target.x && cur.y == target.y && cur.z == target.z)) hit = sweep<NC, OBB, BALL>(col, cur, target, negDir, 0.0f, f, n);
                 if (!hit) active = false;
                 else {
                     V3 dir = target - cur;
@@ -479,7 +486,7 @@ __device__ __forceinline__ void player_step(AgentState &a, const Col (&col)[NC],
         if (downVel > 0.0f && downVel > FALL_SPEED && (wasOnGround || !a.was_jumping)) downVel = FALL_SPEED;
         target = v3(target.x, target.y - (a.step_offset + downVel * dt), target.z);
         float f; V3 n;
-        if (sweep<NC, OBB>(col, cur, target, UP, MAX_SLOPE_COS, f, n)) {
+        if (sweep<NC, OBB, BALL>(col, cur, target, UP, MAX_SLOPE_COS, f, n)) {
             cur = lerp3(cur, target, f);
             a.vvel = 0.0f; a.voffset = 0.0f; a.was_jumping = 0;
         } else cur = target;
@@ -489,7 +496,7 @@ __device__ __forceinline__ void player_step(AgentState &a, const Col (&col)[NC],
     a.hvx = (cur.x - original.x) / dt;
     a.hvz = (cur.z - original.z) / dt;
 
-    recover_up_to_5<NC, OBB>(col, cur, reached);
+    recover_up_to_5<NC, OBB, BALL>(col, cur, reached);
     reached(cur);
     if (reach2) *reach2 = r2;
     a.pos[0] = cur.x; a.pos[1] = cur.y; a.pos[2] = cur.z;

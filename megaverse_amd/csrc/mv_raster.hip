@@ -2596,7 +2596,7 @@ int launch_raster_batch(const GymView *views, uint32_t *const *obs, const Publis
         }
         return 0;
     }
-    const bool shapes = gv.scenario == SCN_REARRANGE;
+    const bool shapes = gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL;   // (scaled shapes: Rearrange's items, Football's ball)
     if (np == 2) {
         if (shapes) launch_done(raster_fast_batch_kernel<VIS_SMALL, true, 6, 2>, grid, block, dyn, stream, done, a, W, H, split);
         else launch_done(raster_fast_batch_kernel<VIS_SMALL, false, 7, 2>, grid, block, dyn, stream, done, a, W, H, split);
@@ -2620,7 +2620,7 @@ int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t st
         const size_t dyn = (size_t)(W + H) * sizeof(float4) + (size_t)W * sizeof(float) + (size_t)H * sizeof(float2);
         const int np = fast_pixels_per_lane(W, H, gv.vis_stride > VIS_SMALL);
         const int split = fast_split(W, H, np, frames, gv.vis_stride > VIS_SMALL);
-        // variants: <= 256 visible primitives, + scaled shapes (Rearrange), <= 1024 through the scalar cache (Collect), <= 2048 + scaled shapes + wall frames
+        // variants: <= 256 visible primitives, + scaled shapes (Rearrange, Football), <= 1024 through the scalar cache (Collect), <= 2048 + scaled shapes + wall frames
         // (Hex*); the short-list ones are built for 8 waves per SIMD with one pixel per lane (64 VGPRs), for 7 with two (72; with the scaled shapes: 6, 80)
         using KernelFn = void (*)(FastArgs, uint32_t *, int, int, int);
         FastArgs fa = fast_args_of(gv, publish);
@@ -2631,11 +2631,11 @@ int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t st
         if (np == 2)
             fn = hexScen ? raster_glist_kernel<VIS_XL, true, GLIST_WAVES_NP2, true, 2> : gv.vis_stride > VIS_SMALL
                     ? raster_glist_kernel<VIS_LARGE, false, GLIST_WAVES_NP2, false, 2>
-               : gv.scenario == SCN_REARRANGE ? raster_fast_kernel<VIS_SMALL, true, 6, false, 2> : raster_fast_kernel<VIS_SMALL, false, 7, false, 2>;
+               : gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL ? raster_fast_kernel<VIS_SMALL, true, 6, false, 2> : raster_fast_kernel<VIS_SMALL, false, 7, false, 2>;
         else
             fn = hexScen ? raster_glist_kernel<VIS_XL, true, GLIST_WAVES_NP1, true, 1> : gv.vis_stride > VIS_SMALL
                     ? raster_glist_kernel<VIS_LARGE, false, GLIST_WAVES_NP1, false, 1>
-               : gv.scenario == SCN_REARRANGE ? raster_fast_kernel<VIS_SMALL, true, 8> : raster_fast_kernel<VIS_SMALL, false, 8>;
+               : gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL ? raster_fast_kernel<VIS_SMALL, true, 8> : raster_fast_kernel<VIS_SMALL, false, 8>;
         const int ftiles = ((W + TILE_W - 1) / TILE_W) * ((H + TILE_H * np - 1) / (TILE_H * np));
         // Fine-grained tail.  The SIMD's arbiter serves its OLDEST wave first: workgroups finish roughly in launch order whatever they cost (wave life
         // by decile of the launch order, frames in random order: 18 us for the first tenth, 35 us for the eighth, all started within 0.3 us -- r05b),
@@ -2665,7 +2665,7 @@ int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t st
     if (gv.scenario == SCN_HEX_MEMORY || gv.scenario == SCN_HEX_EXPLORE) hipLaunchKernelGGL((raster_kernel<VIS_XL, true>),
         grid, block, dyn, stream, gv, obs, W, H, split, gv.lpt_order);
     else if (gv.vis_stride > VIS_SMALL) hipLaunchKernelGGL((raster_kernel<VIS_LARGE, false>), grid, block, dyn, stream, gv, obs, W, H, split, gv.lpt_order);
-    else if (gv.scenario == SCN_REARRANGE) hipLaunchKernelGGL((raster_kernel<VIS_SMALL, true>), grid, block, dyn, stream, gv, obs, W, H, split, gv.lpt_order);
+    else if (gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL) hipLaunchKernelGGL((raster_kernel<VIS_SMALL, true>), grid, block, dyn, stream, gv, obs, W, H, split, gv.lpt_order);
     else hipLaunchKernelGGL((raster_kernel<VIS_SMALL, false>), grid, block, dyn, stream, gv, obs, W, H, split, gv.lpt_order);
     if (done) (void)hipEventRecord(done, stream);
     return 0;

@@ -33,6 +33,7 @@ static const StepKernels &kernels_of(int scenario)
     case SCN_REARRANGE: return rearrange_kernels;
     case SCN_SOKOBAN: return sokoban_kernels;
     case SCN_BOXAGONE: return boxagone_kernels;
+    case SCN_FOOTBALL: return football_kernels;
     default: return hex_kernels;   // SCN_HEX_MEMORY, SCN_HEX_EXPLORE
     }
 }

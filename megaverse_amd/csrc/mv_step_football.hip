@@ -1,0 +1,19 @@
+// megaverse_amd/csrc/mv_step_football.hip -- the step and reset kernels of Football: entry points over the shared bodies (mv_step_kernels.h)
+// for the scenario's tick (mv_tick_football.h: what it replaces, how it maps onto a wavefront).  The only kernels built with the ball collider.
+#include <hip/hip_runtime.h>
+
+#include "mv_step_kernels.h"
+#include "mv_tick_football.h"
+
+namespace mv {
+
+using S = tick_football::Scenario;
+
+template <int A_MAX> __global__ __launch_bounds__(256) void step_football_kernel(GymView gv, int W, int H, int render) { step_body<S, A_MAX>(gv, blockIdx.x, W, H, render); }
+template <class Args> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_football_ticks_kernel(Args a, int W, int H) { step_ticks_body<S, 1>(a, W, H); }
+__global__ __launch_bounds__(64) void reset_football_kernel(GymView gv, int force_all) { reset_body<S>(gv, force_all); }
+
+const StepKernels football_kernels = {step_football_kernel<1>, step_football_kernel<MAX_AGENTS>, step_football_ticks_kernel<StepTicksArgs8>,
+                                      nullptr, nullptr, reset_football_kernel};
+
+}  // namespace mv

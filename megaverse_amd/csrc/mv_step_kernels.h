@@ -171,6 +171,7 @@ struct StepKernels {
     void (*ticks_agents)(StepTicksArgs8, int, int);      // k ticks, several agents per env
     void (*reset)(GymView, int);
 };
-extern const StepKernels tower_kernels, obstacles_kernels, collect_kernels, rearrange_kernels, sokoban_kernels, hex_kernels, boxagone_kernels;
+extern const StepKernels tower_kernels, obstacles_kernels, collect_kernels, rearrange_kernels, sokoban_kernels, hex_kernels, boxagone_kernels,
+                          football_kernels;
 
 }  // namespace mv

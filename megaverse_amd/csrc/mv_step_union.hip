@@ -36,7 +36,7 @@ __device__ __forceinline__ void tick_any(const GymView &gv, const int env)
     case SCN_COLLECT: tick_collect::Scenario::tick<A_MAX>(gv, env); break;
     case SCN_REARRANGE: tick_rearrange::Scenario::tick<A_MAX>(gv, env); break;
     case SCN_SOKOBAN: tick_sokoban::Scenario::tick<A_MAX>(gv, env); break;
-    default: tick_hex::Scenario::tick<A_MAX>(gv, env); break;   // SCN_HEX_MEMORY, SCN_HEX_EXPLORE (never BoxAGone: mv_group_create refuses it)
+    default: tick_hex::Scenario::tick<A_MAX>(gv, env); break;   // SCN_HEX_MEMORY, SCN_HEX_EXPLORE (never BoxAGone or Football: mv_group_create refuses them)
     }
 }
 // the union kernels' trait (mv_step_kernels.h): any scenario's tick on wave 0, the long lists' LDS

@@ -38,7 +38,8 @@ enum : int { ST_STARVED = 1, ST_CANDIDATES = 2, ST_VISIBLE = 4, ST_CHUNK = 8 };
 enum : int { SCN_TOWER = 0, SCN_OBSTACLES = 1, SCN_COLLECT = 2, SCN_REARRANGE = 3, SCN_SOKOBAN = 4,
              SCN_EMPTY = 5,     // Empty runs on the Obstacles kernels (one slab, no terrain) with fall detection off
              SCN_HEX_MEMORY = 6, SCN_HEX_EXPLORE = 7,
-             SCN_BOXAGONE = 8 };   // its drawables are world-space HexRec records like the Hex scenarios' (mv_tick_boxagone.h)
+             SCN_BOXAGONE = 8,     // its drawables are world-space HexRec records like the Hex scenarios' (mv_tick_boxagone.h)
+             SCN_FOOTBALL = 9 };   // the same: the room's boxes and the ball (mv_tick_football.h)
 enum : int { HEX_PILLAR = 0, HEX_DIAMOND = 1, HEX_SPHERE = 2 };                       // scenario_hex_memory.cpp:163-168 ShapeType
 enum : int { SOKO_DIM = 32, SOKO_WALL = 1, SOKO_GOAL = 2 };                            // Sokoban level cells (scenario_sokoban.cpp:28-33)
 enum : int { MAX_ITEMS = 8, NUM_STATIC = 9 };                                         // Rearrange: arrangement items, static colliding boxes
@@ -180,6 +181,7 @@ struct GymView {
     int32_t lpt_no_clear;
     struct TowerGen *tower_gen;// [N] TowerBuilding: where each env's episode generator stands (mv_reset_device.h: tower_draw); its resident episodes are `blobs` (TowerBlob)
     struct BoxAGoneState *bag; // [N] BoxAGone: platform table, temporary ring, cell map (its drawables: hex_boxes)
+    struct FootballState *fb;  // [N] Football: the ball (its drawables: hex_boxes, hex_objs)
 };
 
 // The n <= 8 consecutive ticks of a multi-tick step launch (mv_step.hip: step_ticks_kernel, and every mv_step_*.hip), the same envs in all of them: their views
@@ -377,5 +379,31 @@ struct alignas(16) BoxAGoneState {
     int16_t cell[BAG_MAX_LEVELS][BAG_ROOM][BAG_ROOM];         // [level][x][z] -> platform index, -1: none
 };
 static_assert(sizeof(BoxAGoneState) % 16 == 0, "BoxAGoneState: 16-byte rows");
+
+// Football (scenario_football.{hpp,cpp}): an EmptyPlatform room of 14..23 x 3..6 x 12..23 voxels (voxel size 1) with all four walls, and a ball.
+enum : int { FB_MAX_LAYOUT = 8 };
+
+// Football episode (mv_gen_football.cpp -> mv_step_football.hip)
+struct alignas(16) FootballBlob {
+    int32_t seq;
+    int32_t num_boxes, length, width;
+    int32_t height;
+    float episode_len;
+    int32_t pad[2];
+    float spawn[MAX_AGENTS][3];          // agentSpawnPoints: (x, 1, z), voxel units
+    float yaw_frand[MAX_AGENTS];
+    LayoutBox boxes[FB_MAX_LAYOUT];      // the room's merged slabs, in voxels
+};
+
+// Football per-env state (GymView::fb): the ball of the stated sequential-impulse model (mv_tick_football.h).  Orientation is not
+// kept: a uniform sphere looks the same at every one.  `contacts` and `kicks` are this tick's (tests): bit j of contacts = agent j's capsule, bit 8 + b =
+// room box b.
+struct alignas(16) FootballState {
+    float pos[3]; float radius;          // centre; the drawn radius (0.5 on the frame after a reset, then 1.0)
+    float vel[3]; int32_t kicks;         // linear velocity; kicks applied at the end of this tick
+    float ang[3]; int32_t contacts;      // angular velocity; contacts of this tick's solve
+    float force[3]; int32_t pad;         // the force pending for the next tick's integration (applyForce)
+};
+static_assert(sizeof(FootballState) == 64, "FootballState: 64 B");
 
 }  // namespace mv

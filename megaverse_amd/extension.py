@@ -64,11 +64,13 @@ SYMBOLS = [
     ("mv_debug_set_agent_yaw", C.c_int, [_P, _I, _I, _F, _F]), ("mv_debug_set_agent_velocity", C.c_int, [_P, _I, _I, _F, _F, _F]),
     ("mv_debug_snapshot_size", C.c_int, [_P]), ("mv_debug_snapshot", C.c_int, [_P, _I, _P]),
     ("mv_debug_boxagone_state", C.c_int, [_P, _I, _P]),
+    ("mv_debug_football_state", C.c_int, [_P, _I, _P]), ("mv_debug_set_football_state", C.c_int, [_P, _I, _P]),
     ("mv_debug_rng", C.c_int, [_I, _U, _I, _P, _P, _I, _P]),
     ("mv_debug_math", C.c_int, [_I, _I, _P, _P, _I, _P]),
     ("mv_debug_generate_episode", C.c_int, [C.c_char_p, _I, _I, _I, _F, _P, _I]),
     ("mv_debug_feeder_selftest", C.c_int, [C.c_char_p, _I, _I, _I, _I]),
     ("mv_debug_generate_sokoban", C.c_int, [_I, _I, _I, _F, _P, _I]),
+    ("mv_debug_generate_football", C.c_int, [_I, _I, _I, _F, _P, _I]),
     ("mv_debug_collect_draw_host", C.c_int, [_I, _I, _I, _F, _P, _I]),
     ("mv_debug_collect_draw_device", C.c_int, [_I, _I, _P, _I, _I, _F, _P, C.c_int64, _P]),
 ]
@@ -389,6 +391,22 @@ class MegaverseGym:
         buf = np.zeros(n, np.uint8)
         self._ck(self._lib.mv_debug_boxagone_state(self._g, int(env_idx), buf.ctypes.data))
         return buf
+
+    def debug_football_state(self, env_idx):
+        """Football: env env_idx's ball as a dict of numpy values (FootballState, mv_types.h): pos, radius (drawn), vel, kicks, ang, contacts, force."""
+        n = self._lib.mv_debug_football_state(self._g, int(env_idx), None)
+        self._ck(n)
+        buf = np.zeros(n, np.uint8)
+        self._ck(self._lib.mv_debug_football_state(self._g, int(env_idx), buf.ctypes.data))
+        f, i = buf.view(np.float32), buf.view(np.int32)
+        return {"pos": f[0:3].copy(), "radius": f[3], "vel": f[4:7].copy(), "kicks": int(i[7]), "ang": f[8:11].copy(), "contacts": int(i[11]),
+                "force": f[12:15].copy()}
+
+    def debug_set_football_state(self, env_idx, pos, vel=(0.0, 0.0, 0.0), ang=(0.0, 0.0, 0.0), force=(0.0, 0.0, 0.0), radius=1.0):
+        """Football: place env env_idx's ball -- centre, velocity, angular velocity, the force pending for the next tick, drawn radius."""
+        buf = np.zeros(16, np.float32)
+        buf[0:3], buf[3], buf[4:7], buf[8:11], buf[12:15] = pos, radius, vel, ang, force
+        self._ck(self._lib.mv_debug_set_football_state(self._g, int(env_idx), buf.ctypes.data))
 
     def debug_snapshot_bytes(self, env_idx):
         n = self._lib.mv_debug_snapshot_size(self._g)

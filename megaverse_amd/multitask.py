@@ -33,9 +33,10 @@ class MultiTaskGym:
             raise ValueError("num_envs must be a multiple of the number of scenarios")
         self.scenarios = list(scenarios)
         union = os.environ.get("MV_MULTITASK_UNION", "1") != "0" and S <= 8
-        if union and any(str(n).casefold() == "boxagone" for n in self.scenarios):   # (mv_group_create refuses it as well)
-            raise ValueError("MultiTaskGym: BoxAGone cannot be stepped in a group of gyms (the union kernels have no BoxAGone tick); "
-                             "set MV_MULTITASK_UNION=0 for one gym per scenario, or step it as a MegaverseEnv of its own")
+        for name in ("BoxAGone", "Football"):   # (mv_group_create refuses them as well)
+            if union and any(str(n).casefold() == name.casefold() for n in self.scenarios):
+                raise ValueError(f"MultiTaskGym: {name} cannot be stepped in a group of gyms (the union kernels have no {name} tick); "
+                                 "set MV_MULTITASK_UNION=0 for one gym per scenario, or step it as a MegaverseEnv of its own")
         self.w, self.h, self.num_envs, self.num_agents_per_env = int(w), int(h), int(num_envs), int(num_agents_per_env)
         self.per_task = num_envs // S
         total = total_envs if total_envs > 0 else num_envs
