@@ -106,7 +106,7 @@ int mv_step_no_render(mv_gym *g);                   /* physics/logic/auto-reset 
  * outputs -- or, with mv_set_output_ring, every tick's.  k may exceed the internal batch (mv_recommended_ticks_per_call; MV_PIPE_BATCH overrides its sizing): the call splits it. */
 int mv_step_n(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32_t first_step_index);
 /* Rollout rings (no reference counterpart: its learner copies each step's observation out of the gym, megaverse_env.py:121-130): tick
- * number t since this call leaves its observations in obs[t % count] ([count][N*A][h][w][4]), its rewards in rewards[t % count] ([count][N*A])
+ * number t since this call leaves its observations in obs[t % count] ([count][N*A][h][w][4]; planar layout: [count][N*A][3][h][w]), its rewards in rewards[t % count] ([count][N*A])
  * and its dones in dones[t % count] ([count][N]); a NULL ring keeps that output where it was.  count = 0 switches back to the single
  * slab / arrays.  Host getters (mv_get_observation, mv_get_last_rewards, ...) read the entry of the last tick. */
 int mv_set_output_ring(mv_gym *g, int32_t count, void *obs, float *rewards, uint8_t *dones);
@@ -145,7 +145,7 @@ int mv_get_true_objectives(mv_gym *g, float *out);  /* [N*A] */
 /* getObservation(), :139-143: (h, w, 4) uint8, rows bottom-up like glReadPixels.  The reference
  * returns a view of host memory; here the frame lives in HBM: copy one frame out ... */
 int mv_get_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, uint8_t *out_host);
-/* ... or take the device slab [N*A][h][w][4] (valid until mv_close; rewritten by every step) */
+/* ... or take the device slab [N*A][h][w][4] -- [N*A][3][h][w] in the planar layout, mv_set_obs_layout (valid until mv_close; rewritten by every step) */
 void *mv_obs_device_ptr(mv_gym *g);
 void *mv_rewards_device_ptr(mv_gym *g);             /* float [N*A] */
 void *mv_dones_device_ptr(mv_gym *g);               /* uint8 [N] */
@@ -162,6 +162,17 @@ int mv_set_stream(mv_gym *g, void *hip_stream);
 enum { MV_PIXELS_EXACT = 0, MV_PIXELS_FAST = 1 };
 int mv_set_pixel_mode(mv_gym *g, int32_t mode);
 int mv_get_pixel_mode(const mv_gym *g);
+
+/* Layout of the observation slab (no reference counterpart: its learner drops alpha and transposes every frame, megaverse_env.py:121-130).
+ * MV_OBS_RGBA (default): [N*A][h][w][4] RGBA8, alpha 255.  MV_OBS_RGB_PLANAR: [N*A][3][h][w] uint8, planes R, G, B -- what a learner's conv net
+ * consumes, written by the observation pass itself (3 bytes per pixel instead of 4); rows bottom-up in both.  The layout sets the frame's size
+ * everywhere one appears: the owned slab, what mv_set_obs_buffer expects, the entry stride of mv_set_output_ring's observation ring (planar buffers:
+ * 16-byte aligned where w % 16 == 0, 4-byte where w % 4 == 0).  mv_get_observation returns (h, w, 4) RGBA with alpha 255 in both layouts; the hires frames (mv_draw_hires) stay RGBA.
+ * Valid before the gym's first mv_reset, mv_render, mv_set_obs_buffer or mv_set_output_ring, and not on a gym in a group; mv_group_create
+ * refuses gyms whose layouts differ.  mv_get_obs_layout: the layout, -1 for no gym. */
+enum { MV_OBS_RGBA = 0, MV_OBS_RGB_PLANAR = 1 };
+int mv_set_obs_layout(mv_gym *g, int32_t layout);
+int mv_get_obs_layout(const mv_gym *g);
 
 /* One-step-ahead pipelining (no reference counterpart).  On (default): the step kernels run on an internal stream,
  * and the step of tick t + 1 may overlap the observation pass of tick t whenever nothing the caller enqueued on its stream feeds

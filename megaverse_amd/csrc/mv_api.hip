@@ -86,7 +86,7 @@ OutPtrs outputs_of(const mv_gym *g, unsigned long long tick)
     OutPtrs o{g->obs, g->gv.rewards, g->gv.done};
     if (g->ringCount > 0) {
         const size_t r = (size_t)(tick % (unsigned long long)g->ringCount), NA = (size_t)g->N * g->A;
-        if (g->ringObs) o.obs = reinterpret_cast<uint32_t *>(g->ringObs + r * NA * (size_t)g->w * g->h * 4);
+        if (g->ringObs) o.obs = reinterpret_cast<uint32_t *>(g->ringObs + r * NA * g->frameBytes());
         if (g->ringRewards) o.rewards = g->ringRewards + r * NA;
         if (g->ringDone) o.done = g->ringDone + r * (size_t)g->N;
     }
@@ -347,7 +347,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
                  szObj = up(N * MAX_OBJECTS * sizeof(MovableObject)), szAg = up(NA * sizeof(AgentState)),
                  szChunk = up(N * (size_t)CHUNK_BYTES), szAct = up(NA * sizeof(int32_t)), szRew = up(NA * sizeof(float)),
                  szDone = up(N), szObjv = up(NA * sizeof(float)), szMd = up(NA * 6 * sizeof(int32_t)),
-                 szObs = up(NA * (size_t)g->w * g->h * 4);
+                 szObs = up(NA * frame_bytes(g->w, g->h, MV_OBS_RGBA));   // (the larger layout: mv_set_obs_layout may come later)
     const size_t szTerrain = obstacles ? up(N * MAX_TERRAIN * sizeof(TerrainBox)) : 0,
                  szRewObj = hostEpisodes ? up(N * (size_t)gv.reward_stride * sizeof(MovableObject)) : 0,
                  szHeight = collect ? up(N * (size_t)HM_BYTES) : 0, szItems = rearrange ? up(N * MAX_ITEMS * sizeof(ArrangementItem))
@@ -741,9 +741,27 @@ int mv_set_stream(mv_gym *g, void *s)
 int mv_set_obs_buffer(mv_gym *g, void *p)
 {
     if (check(g)) return -1;
+    if (p && g->obsLayout == MV_OBS_RGB_PLANAR && (uintptr_t)p % planar_alignment(g->w))
+        return fail("mv_set_obs_buffer: a planar slab of this width must be " + std::to_string(planar_alignment(g->w)) + "-byte aligned");
     g->obs = p ? (uint32_t *)p : g->ownedObs;
+    g->layoutFixed = true;
     return 0;
 }
+
+int mv_set_obs_layout(mv_gym *g, int32_t layout)
+{
+    if (check(g)) return -1;
+    if (layout != MV_OBS_RGBA && layout != MV_OBS_RGB_PLANAR) return fail("mv_set_obs_layout: layout must be MV_OBS_RGBA (0) or MV_OBS_RGB_PLANAR (1)");
+    if (g->inGroup) return fail("mv_set_obs_layout: the gym belongs to a group (set the layout before mv_group_create)");
+    if (g->layoutFixed)
+        return fail("mv_set_obs_layout: call it before the gym's first mv_reset, mv_render, mv_set_obs_buffer or mv_set_output_ring");
+    g->obsLayout = layout;
+    g->gv.obs_layout = layout;
+    for (GymView &v : g->gvp) v.obs_layout = layout;   // (every launch's view is a slot's: view())
+    return 0;
+}
+
+int mv_get_obs_layout(const mv_gym *g) { return g && !g->closed ? g->obsLayout : -1; }
 
 int mv_set_pixel_mode(mv_gym *g, int32_t mode)
 {
@@ -818,6 +836,7 @@ int mv_render(mv_gym *g)
     HIP_TRY(hipSetDevice(g->device));
     if (sim_join(g)) return -1;
     if (take_hist(g, g->stream, true)) return -1;
+    g->layoutFixed = true;
     if (launch_raster(view(g, g->parity), last_outputs(g).obs, g->w, g->h, g->stream, nullptr, g->fastPixels))
         return fail("mv_render: observation size above 1024x1024");
     HIP_TRY(hipGetLastError());
@@ -1037,6 +1056,7 @@ int mv_reset(mv_gym *g)
     if (check(g)) return -1;
     HIP_TRY(hipSetDevice(g->device));
     if (sim_join(g)) return -1;
+    g->layoutFixed = true;
     if (flush_device_actions(g)) return -1;   // (a buffer handed over before the reset is read now, not by whatever step comes after it)
     if (g->hostEpisodes()) {
         // the periodic status read-back may be up to 15 ticks old: an env that auto-reset since then has consumed its
@@ -1129,7 +1149,10 @@ int mv_set_output_ring(mv_gym *g, int32_t count, void *obs, float *rewards, uint
 {
     if (check(g)) return -1;
     if (count < 0 || (count > 0 && !obs && !rewards && !dones)) return fail("mv_set_output_ring: count >= 0 and at least one ring required");
+    if (count > 0 && obs && g->obsLayout == MV_OBS_RGB_PLANAR && (uintptr_t)obs % planar_alignment(g->w))
+        return fail("mv_set_output_ring: a planar ring of this width must be " + std::to_string(planar_alignment(g->w)) + "-byte aligned");
     if (sim_join(g)) return -1;   // (ticks in flight keep the pointers they were given)
+    g->layoutFixed = true;
     g->ringCount = count; g->ringTick = 0;
     g->ringObs = count ? (uint8_t *)obs : nullptr; g->ringRewards = count ? rewards : nullptr; g->ringDone = count ? dones : nullptr;
     g->mirrorsFresh = false;
@@ -1219,10 +1242,24 @@ int mv_get_observation(mv_gym *g, int32_t env, int32_t agent, uint8_t *out)
 {
     if (check(g)) return -1;
     if (env < 0 || env >= g->N || agent < 0 || agent >= g->A) return fail("mv_get_observation: index out of range");
-    const size_t frameBytes = (size_t)g->w * g->h * 4;
-    HIP_TRY(hipMemcpyAsync(out, (const uint8_t *)last_outputs(g).obs + ((size_t)env * g->A + agent) * frameBytes,
-            frameBytes, hipMemcpyDeviceToHost, g->stream));
+    const size_t frameBytes = g->frameBytes();
+    const uint8_t *src = (const uint8_t *)last_outputs(g).obs + ((size_t)env * g->A + agent) * frameBytes;
+    if (g->obsLayout == MV_OBS_RGBA) {
+        HIP_TRY(hipMemcpyAsync(out, src, frameBytes, hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        return 0;
+    }
+    // planar: the frame's three planes, interleaved into (h, w, 4) RGBA with alpha 255 -- the reference's contract in every layout
+    const size_t px = (size_t)g->w * g->h;
+    static thread_local std::vector<uint8_t> staged;
+    staged.resize(frameBytes);
+    const uint8_t *planes = staged.data();
+    HIP_TRY(hipMemcpyAsync(staged.data(), src, frameBytes, hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
+    for (size_t i = 0; i < px; ++i) {
+        const uint8_t r = planes[i], gg = planes[px + i], b = planes[2 * px + i];
+        out[4 * i] = r; out[4 * i + 1] = gg; out[4 * i + 2] = b; out[4 * i + 3] = 255;
+    }
     return 0;
 }
 
@@ -1250,8 +1287,9 @@ int mv_draw_hires(mv_gym *g)
     }
     if (sim_join(g)) return -1;
     if (take_hist(g, g->stream, true)) return -1;
-    if (launch_raster(view(g, g->parity), g->hiresObs, g->hiresW, g->hiresH, g->stream, nullptr,
-        g->fastPixels)) return fail("mv_draw_hires: render size above 1024x1024");
+    GymView v = view(g, g->parity);
+    v.obs_layout = MV_OBS_RGBA;   // (the hires frames are RGBA in every layout)
+    if (launch_raster(v, g->hiresObs, g->hiresW, g->hiresH, g->stream, nullptr, g->fastPixels)) return fail("mv_draw_hires: render size above 1024x1024");
     HIP_TRY(hipGetLastError());
     return 0;
 }

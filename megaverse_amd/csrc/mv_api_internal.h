@@ -48,6 +48,10 @@ using namespace mv;
 
 
 namespace mvapi {
+// the bytes of one w x h observation frame in a layout (include/megaverse_hip.h: mv_set_obs_layout)
+inline size_t frame_bytes(int w, int h, int layout) { return (size_t)w * h * (layout == MV_OBS_RGB_PLANAR ? 3 : 4); }
+// the alignment a planar slab of w-pixel rows needs: its 16-byte stores (w % 16 == 0: whole tile rows), its dword stores (w % 4 == 0), else bytes
+inline size_t planar_alignment(int w) { return w % 16 == 0 ? 16 : w % 4 == 0 ? 4 : 1; }
 extern thread_local std::string g_err;   // mv_last_error()
 inline int fail(const std::string &msg)
 {
@@ -128,6 +132,10 @@ struct mv_gym {
     uint32_t *obs = nullptr, *ownedObs = nullptr, *hiresObs = nullptr;
     int hiresW = 0, hiresH = 0;
     int fastPixels = 1;                          // mv_set_pixel_mode: 1 = raster_fast_kernel (default), 0 = bit-exact raster_kernel
+    // mv_set_obs_layout: MV_OBS_RGBA (default) or MV_OBS_RGB_PLANAR; fixed by the first reset / render / obs buffer / output ring (layoutFixed)
+    int obsLayout = MV_OBS_RGBA;
+    bool layoutFixed = false;
+    size_t frameBytes() const { return frame_bytes(w, h, obsLayout); }   // one observation frame in this gym's layout
     // host mirrors
     int32_t *hActions[2] = {nullptr, nullptr};   // pinned staging, double buffered
     hipEvent_t actionsCopied[2] = {nullptr, nullptr};

@@ -412,6 +412,7 @@ int mv_group_create(mv_gym *const *gyms, int32_t n, mv_group **out)
             return fail("mv_group_create: Football cannot be stepped in a group of gyms; step it as a gym of its own (MultiTaskGym: MV_MULTITASK_UNION=0)");
         if (g->device != L->device || g->w != L->w || g->h != L->h || g->A != L->A || g->stream != L->stream || g->pipelined != L->pipelined)
             return fail("mv_group_create: the gyms of a group share device, observation size, agents per env, stream (mv_set_stream first) and pipelining");
+        if (g->obsLayout != L->obsLayout) return fail("mv_group_create: the gyms of a group share their observation layout (mv_set_obs_layout)");
     }
     HIP_TRY(hipSetDevice(L->device));
     for (int i = 0; i < n; ++i) {   // nothing in flight on the streams a member is about to leave

@@ -35,9 +35,11 @@
 #include <algorithm>
 #include <cstring>
 #include <numeric>
+#include <type_traits>
 #include <vector>
 #include <stdio.h>
 
+#include "../../include/megaverse_hip.h"
 #include "mv_frame.h"
 #include "mv_math.h"
 #include "mv_raster.h"
@@ -286,7 +288,95 @@ __global__ __launch_bounds__(1024) void frame_order_kernel(GymView gv, int frame
     for (int f = tid; f < frames; f += 1024) order[atomicAdd(&s_start[gv.lpt_bucket[f]], 1)] = f;
 }
 
-template <int MAXVIS, bool SHAPES>   // SHAPES: the frame may hold scaled spheres / capsules / cylinders (Rearrange)
+namespace {
+
+// Where the short-list pass's pixels go: the frame as a BUFFER (four scalar registers: base, size), a pixel's place in it a 32-bit byte offset -- one
+// v_mad_i32_i24 per pixel where the 64-bit address arithmetic of a global store took three vector instructions; `edgeless`: the frame is whole tiles
+// (every BASELINE size is), so no pixel needs its "inside the frame?" compares.  (A store beyond the frame's bytes would be dropped by the buffer's range
+// check.)
+// CHW (mv_set_obs_layout: MV_OBS_RGB_PLANAR): the frame is three planes of W x H bytes, R, G, B -- `W4` is then a plane row's bytes (W) and `plane` a
+// plane's (W x H).  Everything that knows the layout is here and in clear_tile (frame_out, put_px); the tile code hands pixels over.
+template <bool CHW>
+struct PixOutT {
+    __amdgpu_buffer_rsrc_t rsrc;
+    int W, H, W4;
+    bool edgeless;
+    int plane;
+};
+typedef PixOutT<false> PixOut;
+#ifndef MV_PIXEL_PLAIN
+constexpr int PIXEL_AUX = 2;   // nt
+#else
+constexpr int PIXEL_AUX = 0;
+#endif
+// The planar layout's stores are PLAIN: a wave's plane row is 16 bytes, where an RGBA row is 64, and non-temporal pieces that small reach memory as partial
+// lines -- measured (TowerBuilding, 1024 envs, 128 x 128, step_n(16)): WRITE_SIZE 2.56 x the algorithmic 3 bytes per pixel with nt stores, 1.60 x with
+// plain ones (which the L2 merges with the neighbouring tiles' pieces); 9.2 against 22.9 M obs/s.  (-DMV_PLANAR_PIXEL_AUX=2: nt, the comparison.)
+#ifndef MV_PLANAR_PIXEL_AUX
+#define MV_PLANAR_PIXEL_AUX 0
+#endif
+constexpr int PLANAR_AUX = MV_PLANAR_PIXEL_AUX;
+
+// frame `frame` of a slab in the layout as a buffer (RGBA: W H words; CHW: 3 W H bytes)
+template <bool CHW>
+__device__ __forceinline__ PixOutT<CHW> frame_out(uint32_t *obs, int frame, int W, int H, bool edgeless)
+{
+    PixOutT<CHW> po;
+    const unsigned bytes = CHW ? 3u * W * H : 4u * W * H;
+    po.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char *>(obs) + (size_t)frame * bytes, /*stride*/ 0, (int)bytes, 0x00020000);
+    po.W = W; po.H = H; po.W4 = CHW ? W : 4 * W;
+    po.edgeless = edgeless;
+    po.plane = W * H;
+    return po;
+}
+
+__device__ __forceinline__ void put_px(const PixOut &po, int px, int py, unsigned rgba)
+{
+    const unsigned off = (unsigned)(__mul24(py, po.W4) + px * 4);
+    if (__builtin_expect(po.edgeless, 1)) __builtin_amdgcn_raw_buffer_store_b32(rgba, po.rsrc, off, 0, PIXEL_AUX);
+    else {
+        asm volatile("" ::: "memory");   // (keeps the two stores apart: merged, the compares run for every pixel and their result is or-ed with `edgeless`)
+        if (px < po.W && py < po.H) __builtin_amdgcn_raw_buffer_store_b32(rgba, po.rsrc, off, 0, PIXEL_AUX);
+    }
+}
+
+// The planar layout.  Four neighbouring lanes hold four neighbouring pixels of one row (every tile row is 16 or 32 lanes wide and starts at a multiple of 16
+// pixels, so a pixel's place in its quad of lanes is px & 3): the quad's four RGBA words are transposed as a 4 x 4 byte matrix -- two quad permutations,
+// two byte selects -- after which quad lane c holds plane c's four bytes of the quad's pixels and stores them as one dword (lane 3 holds the alphas and
+// stores nothing).  Where W % 4 != 0 a plane row's quads are not dword-aligned: every lane stores its three bytes.  (Every lane of the wave must take
+// part: the callers reach this in wave-uniform control flow, and the stores are masked after the exchange.)
+__device__ __forceinline__ unsigned quad_transpose_bytes(unsigned x, int q)
+{
+    // quad_perm [2,3,0,1]: the partner two lanes away; lanes 0, 1 keep bytes 0, 1 of both words, lanes 2, 3 bytes 2, 3
+    const unsigned y = (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0x4e, 0xf, 0xf, false);
+    const unsigned s = __builtin_amdgcn_perm(y, x, q < 2 ? 0x05040100u : 0x03020706u);
+    // quad_perm [1,0,3,2]: the neighbour; even lanes take byte 0 / 2 of both, odd lanes byte 1 / 3
+    const unsigned z = (unsigned)__builtin_amdgcn_mov_dpp((int)s, 0xb1, 0xf, 0xf, false);
+    return __builtin_amdgcn_perm(z, s, (q & 1) ? 0x03070105u : 0x06020400u);
+}
+
+__device__ __forceinline__ void put_px(const PixOutT<true> &po, int px, int py, unsigned rgba)
+{
+    const unsigned row = (unsigned)__mul24(py, po.W);
+    if ((po.W & 3) == 0) {   // (uniform)
+        const int q = px & 3;
+        const unsigned t = quad_transpose_bytes(rgba, q);
+        const unsigned off = (unsigned)__mul24(q, po.plane) + row + (unsigned)(px - q);
+        if (q < 3 && (po.edgeless || (px < po.W && py < po.H))) __builtin_amdgcn_raw_buffer_store_b32(t, po.rsrc, off, 0, PLANAR_AUX);
+        return;
+    }
+    if (px < po.W && py < po.H) {
+        const unsigned off = row + (unsigned)px;
+        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)rgba, po.rsrc, off, 0, PLANAR_AUX);
+        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(rgba >> 8), po.rsrc, off + (unsigned)po.plane, 0, PLANAR_AUX);
+        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(rgba >> 16), po.rsrc, off + 2u * (unsigned)po.plane, 0, PLANAR_AUX);
+    }
+}
+
+}  // namespace
+
+// CHW: the planar layout (mv_set_obs_layout; PixOutT above)
+template <int MAXVIS, bool SHAPES, bool CHW = false>   // SHAPES: the frame may hold scaled spheres / capsules / cylinders (Rearrange)
 __global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : MAXVIS <= 256 ? 5 : MAXVIS <= 1024 ? 2
                              : 1) void raster_kernel(GymView gv, uint32_t *obs, int W, int H, int split, const int *order)
 {
@@ -396,8 +486,10 @@ __global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : M
         const int px = tx0 + (lane & (TILE_W - 1)), pyBase = ty0 + (lane / TILE_W);
         if (anyMask == 0ull) {   // nothing can be seen through this tile: clear colour (0,0,0), alpha 255
 #pragma unroll
-            for (int k = 0; k < PPL; ++k)
-                if (px < W && pyBase + TILE_H * k < H) out[(size_t)(pyBase + TILE_H * k) * W + px] = 0xff000000u;
+            for (int k = 0; k < PPL; ++k) {
+                if constexpr (CHW) put_px(frame_out<true>(obs, frame, W, H, false), px, pyBase + TILE_H * k, 0xff000000u);
+                else if (px < W && pyBase + TILE_H * k < H) out[(size_t)(pyBase + TILE_H * k) * W + px] = 0xff000000u;
+            }
             continue;
         }
         const int pxc = min(px, W - 1);
@@ -515,7 +607,8 @@ __global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : M
                 rgba = ch[0] | (ch[1] << 8) | (ch[2] << 16) | 0xff000000u;
             }
             const int py = pyBase + TILE_H * k;
-            if (px < W && py < H) out[(size_t)py * W + px] = rgba;
+            if constexpr (CHW) put_px(frame_out<true>(obs, frame, W, H, false), px, py, rgba);
+            else if (px < W && py < H) out[(size_t)py * W + px] = rgba;
         }
     }
 }
@@ -562,30 +655,6 @@ constexpr float SPEC_COS2 = 0.97f * 0.97f;
 #else
 #define PIXEL_STORE(dst, v) ((dst) = (v))
 #endif
-
-// Where the short-list pass's pixels go: the frame as a BUFFER (four scalar registers: base, size), a pixel's place in it a 32-bit byte offset -- one
-// v_mad_i32_i24 per pixel where the 64-bit address arithmetic of a global store took three vector instructions; `edgeless`: the frame is whole tiles
-// (every BASELINE size is), so no pixel needs its "inside the frame?" compares.  (A store beyond the frame's bytes would be dropped by the buffer's range
-// check.)
-struct PixOut {
-    __amdgpu_buffer_rsrc_t rsrc;
-    int W, H, W4;
-    bool edgeless;
-};
-#ifndef MV_PIXEL_PLAIN
-constexpr int PIXEL_AUX = 2;   // nt
-#else
-constexpr int PIXEL_AUX = 0;
-#endif
-__device__ __forceinline__ void put_px(const PixOut &po, int px, int py, unsigned rgba)
-{
-    const unsigned off = (unsigned)(__mul24(py, po.W4) + px * 4);
-    if (__builtin_expect(po.edgeless, 1)) __builtin_amdgcn_raw_buffer_store_b32(rgba, po.rsrc, off, 0, PIXEL_AUX);
-    else {
-        asm volatile("" ::: "memory");   // (keeps the two stores apart: merged, the compares run for every pixel and their result is or-ed with `edgeless`)
-        if (px < po.W && py < po.H) __builtin_amdgcn_raw_buffer_store_b32(rgba, po.rsrc, off, 0, PIXEL_AUX);
-    }
-}
 
 struct FastArgs {   // what raster_fast_kernel needs of the GymView (fewer live SGPRs than the whole view)
     const unsigned char *vis_hdr;
@@ -1232,9 +1301,9 @@ __device__ __forceinline__ void classify_tiles(uint4 *s_tile, float4 *s_line, co
 // the pixels of `n` neighbouring tiles of one tile row (first pixel (tx0, ty0)) that the face of axis k (the one towards the eye) of the world box at list
 // position `pos` covers: the face's constants and the rows' ray terms once, per tile the columns' terms and the pixels -- planar_tile's arithmetic, operation
 // for operation
-template <int NP, bool SPEC>
+template <int NP, bool SPEC, class PO>
 __device__ __forceinline__ void planar_run(int pos, int k, int n, const float4 *s_vis, const float *s_hdr, const float4 *s_col, const float4 *s_row,
-                                           const float2 *s_rowq, const float *s_colq, float nzk, int tx0, int ty0, int lane, const PixOut &po)
+                                           const float2 *s_rowq, const float *s_colq, float nzk, int tx0, int ty0, int lane, const PO &po)
 {
     const int W = po.W, H = po.H;
     const float lok = uniform_f32(reinterpret_cast<const float *>(s_vis)[8 * pos + k]),
@@ -1272,9 +1341,9 @@ __device__ __forceinline__ void planar_run(int pos, int k, int n, const float4 *
 }
 
 // the pixels of a tile that the face of axis k (the one towards the eye) of the world box at list position `pos` covers
-template <int NP, bool SPEC>
+template <int NP, bool SPEC, class PO>
 __device__ __forceinline__ void planar_tile(int pos, int k, const float4 *s_vis, const float *s_hdr, const float4 *s_col, const float4 *s_row,
-                                            const float2 *s_rowq, const float *s_colq, float nzk, int px, int py0, const PixOut &po)
+                                            const float2 *s_rowq, const float *s_colq, float nzk, int px, int py0, const PO &po)
 {
     const int W = po.W, H = po.H;
     const float lok = uniform_f32(reinterpret_cast<const float *>(s_vis)[8 * pos + k]),
@@ -1324,6 +1393,23 @@ __device__ __forceinline__ void clear_tile(const PixOut &po, int tx0, int ty0, i
         if (px < po.W && py < po.H) __builtin_amdgcn_raw_buffer_store_b32(c, po.rsrc, (unsigned)(__mul24(py, po.W4) + px * 4), 0, PIXEL_AUX);
     }
 }
+// ... planar: a tile row of one plane is 16 zero bytes -- one 16-byte store per plane and row (3 TH lanes) where plane rows are 16-byte aligned, else the
+// pixels one by one
+template <int NP>
+__device__ __forceinline__ void clear_tile(const PixOutT<true> &po, int tx0, int ty0, int lane)
+{
+    constexpr int TH = TILE_H * NP;
+    if ((po.W & 15) == 0 && tx0 + TILE_W <= po.W) {   // (uniform)
+        const int c = lane / TH, row = ty0 + (lane - c * TH);
+        const v4u_t z = {0u, 0u, 0u, 0u};
+        if (c < 3 && row < po.H)
+            __builtin_amdgcn_raw_buffer_store_b128(z, po.rsrc, (unsigned)(__mul24(c, po.plane) + __mul24(row, po.W) + tx0), 0, PLANAR_AUX);
+        return;
+    }
+    const int px = tx0 + (lane & (TILE_W - 1)), py0 = ty0 + lane / TILE_W;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) put_px(po, px, py0 + TILE_H * j, 0xff000000u);
+}
 
 // A covered tile with company: ONE world box whose face covers the tile (as in planar_tile) and, in front of it or not, boxes of other frames of reference
 // whose rectangles meet the tile -- the viewer's time bar along the bottom row of tiles of every frame (scenario_default.hpp:137-145,164-169), the object it
@@ -1331,11 +1417,11 @@ __device__ __forceinline__ void clear_tile(const PixOut &po, int tx0, int ty0, i
 // recover its entry axis per pixel; here the face's depth comes as in planar_tile -- the same product the slab test forms, so the same depth key -- the other
 // boxes are intersected by the very function the general path uses (other_box), the nearest wins by the same key comparison, and the pixel is shaded by
 // phong_tail with the face's constants or, where another box won, by the general path's fast_shade: the same bytes (test_planar_tiles_change_no_byte).
-template <bool SHAPES, unsigned POS_MASK, int NP>
+template <bool SHAPES, unsigned POS_MASK, int NP, class PO>
 __device__ __forceinline__ void overlay_tile(int posA, int k, unsigned long long rest, const float4 *s_vis,
                                              const float *s_hdr, const float *camv, int viewer, const float4 *s_col,
                                              const float4 *s_row, const float2 *s_rowq, const float *s_colq,
-                                                     float nzm0, float nzm1, float nzm2, int px, int py0, const PixOut &po)
+                                                     float nzm0, float nzm1, float nzm2, int px, int py0, const PO &po)
 {
     const int W = po.W, H = po.H;
     const float lok = uniform_f32(reinterpret_cast<const float *>(s_vis)[8 * posA + k]),
@@ -1382,11 +1468,11 @@ __device__ __forceinline__ void overlay_tile(int posA, int k, unsigned long long
 // The general path for a tile of a classified frame: its list is ONE culling round (at most 64 primitives) and the tile's candidates -- mv0, not empty -- came
 // out of the classification, so the rays are set up at once and there is no loop over rounds (the same arithmetic, in the same order, as the loop in
 // raster_fast_body).
-template <bool SHAPES, unsigned POS_MASK, int NP>
+template <bool SHAPES, unsigned POS_MASK, int NP, class PO>
 __device__ __forceinline__ void general_tile(unsigned long long mv0, unsigned long long wb0, unsigned signs, const float4 *s_vis,
                                              const float *s_hdr, const float *camv, int viewer, const float4 *s_col,
                                              const float4 *s_row, const float2 *s_rowq, const float *s_colq,
-                                                     float nzm0, float nzm1, float nzm2, int px, int py0, const PixOut &po)
+                                                     float nzm0, float nzm1, float nzm2, int px, int py0, const PO &po)
 {
     const int W = po.W, H = po.H;
     const int pxc = min(px, W - 1);
@@ -1461,12 +1547,12 @@ constexpr int glist_lds_bytes(int maxvis) { return 9 * maxvis + 4 * FH_FLOATS; }
 #define RT_COUNT(i, n) do { } while (0)
 #endif
 // a classified tile -- or, LISTED, an entry of the drawing order: a run of up to eight planar / empty neighbours of a tile row -- by its class (classify_tiles)
-template <bool SHAPES, unsigned POS_MASK, int NP, bool LISTED>
+template <bool SHAPES, unsigned POS_MASK, int NP, bool LISTED, class PO>
 __device__ __forceinline__ void classified_tile(const FastArgs &fa, const int u, const int tx0, const int ty0, const uint4 *s_tile,
                                                 const float4 *s_vis, const float *s_hdr, const float *camv, int viewer,
                                             const float4 *s_col, const float4 *s_row, const float2 *s_rowq,
                                                     const float *s_colq, float nzm0, float nzm1, float nzm2, unsigned long long wb0,
-                                            int lane, const PixOut &po)
+                                            int lane, const PO &po)
 {
     const unsigned info = (unsigned)__builtin_amdgcn_readfirstlane(s_tile[u].w), tclass = info & 7u;
     const int run = LISTED ? (int)(((unsigned)__builtin_amdgcn_readfirstlane(s_tile[u].z) >> 3) & 15u) : 1;
@@ -1523,7 +1609,7 @@ __device__ __forceinline__ void classified_tile(const FastArgs &fa, const int u,
                                        viewer, s_col, s_row, s_rowq, s_colq, nzm0, nzm1, nzm2, px, py0, po);
 }
 
-template <int MAXVIS, bool SHAPES, bool HEXF, int NP, bool CLS = true, int NT = 256>   // CLS: with the tile classification
+template <int MAXVIS, bool SHAPES, bool HEXF, int NP, bool CLS = true, int NT = 256, bool CHW = false>   // CLS: with the tile classification; CHW: PixOutT
 __device__ __forceinline__ void raster_fast_body(const FastArgs &fa, uint32_t *obs, int W, int H, int split, int blk, unsigned char *lds)
 {
     constexpr unsigned POS_MASK = MAXVIS - 1;
@@ -1558,10 +1644,13 @@ __device__ __forceinline__ void raster_fast_body(const FastArgs &fa, uint32_t *o
     uint32_t *out = obs + (size_t)frame * W * H;
     const int tilesX = (W + TILE_W - 1) / TILE_W, tilesY = (H + TH - 1) / TH;
     const int numTiles = tilesX * tilesY;
-    PixOut po;
-    po.rsrc = __builtin_amdgcn_make_buffer_rsrc(out, /*stride*/ 0, W * H * 4, 0x00020000);
-    po.W = W; po.H = H; po.W4 = 4 * W;
-    po.edgeless = (W % TILE_W) == 0 && (H % TH) == 0;
+    PixOutT<CHW> po;
+    if constexpr (CHW) po = frame_out<true>(obs, frame, W, H, (W % TILE_W) == 0 && (H % TH) == 0);
+    else {
+        po.rsrc = __builtin_amdgcn_make_buffer_rsrc(out, /*stride*/ 0, W * H * 4, 0x00020000);
+        po.W = W; po.H = H; po.W4 = 4 * W;
+        po.edgeless = (W % TILE_W) == 0 && (H % TH) == 0;
+    }
 
     // What the first round of 64 list positions needs is the same for every tile of the frame: this lane's primitive's rectangle and the
     // world-box mask stay in registers (two VGPRs, two SGPRs) instead of costing two dependent LDS round trips per tile (most frames of the
@@ -1617,10 +1706,21 @@ __device__ __forceinline__ void raster_fast_body(const FastArgs &fa, uint32_t *o
             unsigned c = 0xff000000u;
             asm volatile("" : "+v"(c));
             const v4u_t v = {c, c, c, c};
+            if constexpr (CHW) {   // ... planar: plane c's TH rows of 16 bytes, by threads c TH .. c TH + TH - 1 of the tile's (the last TH idle)
+                const v4u_t z = {0u, 0u, 0u, 0u};
+                const int c = sub / TH;
+                const unsigned inoff = (unsigned)__mul24(c, po.plane) + (unsigned)__mul24(sub - c * TH, po.W);
+                if (c < 3)
+                    for (int e = tid / CPT; e < nE; e += NT / CPT) {
+                        const unsigned txy = s_txy[s_empty[e]];
+                        __builtin_amdgcn_raw_buffer_store_b128(z, po.rsrc, (unsigned)__mul24((int)(txy >> 16), po.W) + (txy & 0xffffu) + inoff, 0, PLANAR_AUX);
+                    }
+            } else {
             const unsigned inoff = (unsigned)__mul24(sub >> 2, po.W4) + (unsigned)(sub & 3) * 16u;
             for (int e = tid / CPT; e < nE; e += NT / CPT) {
                 const unsigned txy = s_txy[s_empty[e]];
                 __builtin_amdgcn_raw_buffer_store_b128(v, po.rsrc, (unsigned)__mul24((int)(txy >> 16), po.W4) + (txy & 0xffffu) * 4u + inoff, 0, PIXEL_AUX);
+            }
             }
             if (wave == 0) { RT_COUNT(0, nE); RT_COUNT(1, nE); }
         }
@@ -1845,7 +1945,7 @@ __device__ __forceinline__ unsigned long long cull_round_g(const short4 *s_rect,
     return __ballot(v);
 }
 
-template <int MAXVIS, bool SHAPES, bool HEXF, int NP>
+template <int MAXVIS, bool SHAPES, bool HEXF, int NP, bool CHW = false>
 __device__ __forceinline__ void raster_glist_body(const FastArgs &fa, uint32_t *obs, int W, int H, int split, int blk, unsigned char *lds)
 {
     // the long-list pass's tile: GT_W x GT_H pixels of one wave (x NP rows of them); 32 x 2: every row a wave stores is one whole 128-byte line
@@ -1874,6 +1974,8 @@ __device__ __forceinline__ void raster_glist_body(const FastArgs &fa, uint32_t *
     const int tilesX = (W + GT_W - 1) / GT_W, tilesY = (H + TH - 1) / TH;
     const int numTiles = tilesX * tilesY;
     const int lx = lane & (GT_W - 1), ly = lane / GT_W;
+    PixOutT<true> pc;   // (CHW: the frame's planes as a buffer; the RGBA stores below are the global stores they were)
+    if constexpr (CHW) pc = frame_out<true>(obs, frame, W, H, false);
 
     // the workgroup's tiles are handed out one at a time, as in raster_fast_body (a wave that always drew the same tile column lived as long as the
     // most crowded one); u = 4 j + w is tile (j split + part) 4 + w of the frame
@@ -1917,7 +2019,8 @@ __device__ __forceinline__ void raster_glist_body(const FastArgs &fa, uint32_t *
 #pragma unroll
             for (int j = 0; j < NP; ++j) {
                 const int py = py0 + GT_H * j;
-                if (px < W && py < H) PIXEL_STORE(out[(unsigned)(py * W + px)], 0xff000000u);
+                if constexpr (CHW) put_px(pc, px, py, 0xff000000u);
+                else if (px < W && py < H) PIXEL_STORE(out[(unsigned)(py * W + px)], 0xff000000u);
             }
             continue;
         }
@@ -2034,24 +2137,26 @@ __device__ __forceinline__ void raster_glist_body(const FastArgs &fa, uint32_t *
             }
             RT_COUNT(3, __popcll(__ballot(best[j].d <= KEY_FAR)));   // pixels with a hit
             const int py = py0 + GT_H * j;
-            if (px < W && py < H) PIXEL_STORE(out[(unsigned)(py * W + px)], rgba);
+            if constexpr (CHW) put_px(pc, px, py, rgba);
+            else if (px < W && py < H) PIXEL_STORE(out[(unsigned)(py * W + px)], rgba);
         }
     }
 }
 
-template <int MAXVIS, bool SHAPES, int WAVES, bool HEXF, int NP>
+// (CHW, every kernel below: the planar layout -- PixOutT; the launch code picks the instantiation by GymView::obs_layout)
+template <int MAXVIS, bool SHAPES, int WAVES, bool HEXF, int NP, bool CHW = false>
 __global__ __launch_bounds__(256, WAVES) void raster_glist_kernel(FastArgs fa, uint32_t *obs, int W, int H, int split)
 {
     __shared__ __attribute__((aligned(16))) unsigned char s_buf[glist_lds_bytes(MAXVIS)];
-    raster_glist_body<MAXVIS, SHAPES, HEXF, NP>(fa, obs, W, H, split, (int)blockIdx.x, s_buf);
+    raster_glist_body<MAXVIS, SHAPES, HEXF, NP, CHW>(fa, obs, W, H, split, (int)blockIdx.x, s_buf);
 }
 
 // WAVES: waves per SIMD the variant is compiled for (register budget 512 / WAVES)
-template <int MAXVIS, bool SHAPES, int WAVES, bool HEXF = false, int NP = 1, int NT = 256>
+template <int MAXVIS, bool SHAPES, int WAVES, bool HEXF = false, int NP = 1, int NT = 256, bool CHW = false>
 __global__ __launch_bounds__(NT, WAVES) void raster_fast_kernel(FastArgs fa, uint32_t *obs, int W, int H, int split)
 {
     __shared__ __attribute__((aligned(16))) unsigned char s_buf[fast_lds_bytes(MAXVIS)];
-    raster_fast_body<MAXVIS, SHAPES, HEXF, NP, true, NT>(fa, obs, W, H, split, (int)blockIdx.x, s_buf);
+    raster_fast_body<MAXVIS, SHAPES, HEXF, NP, true, NT, CHW>(fa, obs, W, H, split, (int)blockIdx.x, s_buf);
 }
 
 // The observation pass of several gyms of one job with one launch (mv_group): workgroup b belongs to gym s with first[s] <= b < first[s + 1]
@@ -2064,7 +2169,7 @@ struct UnionRasterArgs {
     FastArgs fa[MAX_UNION];
 };
 
-template <int MAXVIS, bool SHAPES, int WAVES, bool HEXF, int NP>
+template <int MAXVIS, bool SHAPES, int WAVES, bool HEXF, int NP, bool CHW = false>
 __global__ __launch_bounds__(256, WAVES) void raster_fast_union_kernel(UnionRasterArgs ua, int W, int H, int split)
 {
     int s = 0;
@@ -2072,7 +2177,7 @@ __global__ __launch_bounds__(256, WAVES) void raster_fast_union_kernel(UnionRast
     for (int i = 1; i < MAX_UNION; ++i)
         if (i < ua.n && (int)blockIdx.x >= ua.first[i]) s = i;
     __shared__ __attribute__((aligned(16))) unsigned char s_buf[fast_lds_bytes(MAXVIS)];
-    raster_fast_body<MAXVIS, SHAPES, HEXF, NP>(ua.fa[s], ua.obs[s], W, H, split, (int)blockIdx.x - ua.first[s], s_buf);
+    raster_fast_body<MAXVIS, SHAPES, HEXF, NP, true, 256, CHW>(ua.fa[s], ua.obs[s], W, H, split, (int)blockIdx.x - ua.first[s], s_buf);
 }
 
 // The observation passes of the k ticks of ONE batched call (mv_step_n) with one launch: workgroups are dealt tick by tick, every tick in its own cost order
@@ -2114,7 +2219,7 @@ __device__ __forceinline__ FastArgs ticks_raster_args(const TicksRasterArgs &a, 
     return f;
 }
 
-template <int MAXVIS, bool SHAPES, int WAVES, int NP, int NT = 256>
+template <int MAXVIS, bool SHAPES, int WAVES, int NP, int NT = 256, bool CHW = false>
 __global__ __launch_bounds__(NT, WAVES) void raster_fast_batch_kernel(TicksRasterArgs a, int W, int H, int split)
 {
     int j = 0, r = (int)blockIdx.x;
@@ -2124,11 +2229,11 @@ __global__ __launch_bounds__(NT, WAVES) void raster_fast_batch_kernel(TicksRaste
     __shared__ __attribute__((aligned(16))) unsigned char s_buf[fast_lds_bytes(MAXVIS)];
     FastArgs fa = ticks_raster_args(a, j);
     fa.pub_n = 0;
-    raster_fast_body<MAXVIS, SHAPES, false, NP, true, NT>(fa, a.obs[j], W, H, split, r, s_buf);
+    raster_fast_body<MAXVIS, SHAPES, false, NP, true, NT, CHW>(fa, a.obs[j], W, H, split, r, s_buf);
 }
 
 // (the long-list variant of raster_fast_batch_kernel: the k passes of one batched call of a Collect / Hex gym)
-template <int MAXVIS, bool SHAPES, int WAVES, bool HEXF, int NP>
+template <int MAXVIS, bool SHAPES, int WAVES, bool HEXF, int NP, bool CHW = false>
 __global__ __launch_bounds__(256, WAVES) void raster_glist_batch_kernel(TicksRasterArgs a, int W, int H, int split)
 {
     int j = 0, r = (int)blockIdx.x;
@@ -2138,10 +2243,10 @@ __global__ __launch_bounds__(256, WAVES) void raster_glist_batch_kernel(TicksRas
     __shared__ __attribute__((aligned(16))) unsigned char s_buf[glist_lds_bytes(MAXVIS)];
     FastArgs fa = ticks_raster_args(a, j);
     fa.pub_n = 0;
-    raster_glist_body<MAXVIS, SHAPES, HEXF, NP>(fa, a.obs[j], W, H, split, r, s_buf);
+    raster_glist_body<MAXVIS, SHAPES, HEXF, NP, CHW>(fa, a.obs[j], W, H, split, r, s_buf);
 }
 
-template <int MAXVIS, bool SHAPES, int WAVES, bool HEXF, int NP>
+template <int MAXVIS, bool SHAPES, int WAVES, bool HEXF, int NP, bool CHW = false>
 __global__ __launch_bounds__(256, WAVES) void raster_glist_union_kernel(UnionRasterArgs ua, int W, int H, int split)
 {
     int s = 0;
@@ -2149,7 +2254,7 @@ __global__ __launch_bounds__(256, WAVES) void raster_glist_union_kernel(UnionRas
     for (int i = 1; i < MAX_UNION; ++i)
         if (i < ua.n && (int)blockIdx.x >= ua.first[i]) s = i;
     __shared__ __attribute__((aligned(16))) unsigned char s_buf[glist_lds_bytes(MAXVIS)];
-    raster_glist_body<MAXVIS, SHAPES, HEXF, NP>(ua.fa[s], ua.obs[s], W, H, split, (int)blockIdx.x - ua.first[s], s_buf);
+    raster_glist_body<MAXVIS, SHAPES, HEXF, NP, CHW>(ua.fa[s], ua.obs[s], W, H, split, (int)blockIdx.x - ua.first[s], s_buf);
 }
 
 // Both list lengths in ONE launch: the short-list body (records in LDS) for the gyms with up to 256 visible primitives per frame, the long-list
@@ -2169,7 +2274,7 @@ struct UnionRasterAllArgs {
 #ifndef MV_UNION_CLS
 #define MV_UNION_CLS (NPS >= 2)
 #endif
-template <int WAVES, int NPS>
+template <int WAVES, int NPS, bool CHW = false>
 __global__ __launch_bounds__(256, WAVES) void raster_union_all_kernel(UnionRasterAllArgs a, int W, int H)
 {
     int s = 0;
@@ -2179,9 +2284,9 @@ __global__ __launch_bounds__(256, WAVES) void raster_union_all_kernel(UnionRaste
     constexpr int LDS = fast_lds_bytes(VIS_SMALL) > glist_lds_bytes(VIS_XL) ? fast_lds_bytes(VIS_SMALL) : glist_lds_bytes(VIS_XL);
     __shared__ __attribute__((aligned(16))) unsigned char s_buf[LDS];
     const int blk = (int)blockIdx.x - a.u.first[s];
-    if (a.large[s]) raster_glist_body<VIS_XL, true, true, 1>(a.u.fa[s], a.u.obs[s], W, H, a.split_large, blk, s_buf);
+    if (a.large[s]) raster_glist_body<VIS_XL, true, true, 1, CHW>(a.u.fa[s], a.u.obs[s], W, H, a.split_large, blk, s_buf);
     // (no tile classification: this kernel's LDS is the long-list body's, and occupancy is what it lives on)
-    else raster_fast_body<VIS_SMALL, true, false, NPS, MV_UNION_CLS>(a.u.fa[s], a.u.obs[s], W, H, a.split_small, blk, s_buf);
+    else raster_fast_body<VIS_SMALL, true, false, NPS, MV_UNION_CLS, 256, CHW>(a.u.fa[s], a.u.obs[s], W, H, a.split_small, blk, s_buf);
 }
 
 // The observation passes of the k ticks of ONE batched group call (mv_group_step: n gyms -- scenarios -- x k ticks) with one launch: what
@@ -2224,7 +2329,7 @@ __device__ __forceinline__ FastArgs union_batch_args(const UnionBatchArgs &a, in
     return f;
 }
 
-template <int WAVES, int NPS>
+template <int WAVES, int NPS, bool CHW = false>
 __global__ __launch_bounds__(256, WAVES) void raster_union_batch_kernel(UnionBatchArgs a, int W, int H)
 {
     int j = 0, r = (int)blockIdx.x;
@@ -2242,8 +2347,8 @@ __global__ __launch_bounds__(256, WAVES) void raster_union_batch_kernel(UnionBat
     __shared__ __attribute__((aligned(16))) unsigned char s_buf[LDS];
     FastArgs fa = union_batch_args(a, s, j);
     fa.pub_n = 0;
-    if (a.large[s]) raster_glist_body<VIS_XL, true, true, 1>(fa, a.obs[j][s], W, H, a.split_large, blk, s_buf);
-    else raster_fast_body<VIS_SMALL, true, false, NPS, MV_UNION_CLS>(fa, a.obs[j][s], W, H, a.split_small, blk, s_buf);
+    if (a.large[s]) raster_glist_body<VIS_XL, true, true, 1, CHW>(fa, a.obs[j][s], W, H, a.split_large, blk, s_buf);
+    else raster_fast_body<VIS_SMALL, true, false, NPS, MV_UNION_CLS, 256, CHW>(fa, a.obs[j][s], W, H, a.split_small, blk, s_buf);
 }
 
 #ifdef MV_RASTER_TIMING
@@ -2434,12 +2539,21 @@ static void launch_done(K kernel, dim3 grid, dim3 block, size_t dyn, hipStream_t
     else hipLaunchKernelGGL(kernel, grid, block, dyn, stream, args...);
 }
 
+// The observation layout is the last template parameter (CHW) of every observation kernel: a launcher states its choice of variant ONCE, as `pick`, a
+// generic lambda of the layout (std::integral_constant<bool, CHW>), and by_layout instantiates it for both layouts and returns the gym's kernel.
+template <class Pick>
+static auto by_layout(int layout, Pick pick)
+{
+    return layout == MV_OBS_RGB_PLANAR ? pick(std::true_type{}) : pick(std::false_type{});
+}
+
 int launch_raster_union(const GymView *views, uint32_t *const *obs, const PublishTo *publish, int n, int W,
                         int H, hipStream_t stream, hipEvent_t between, hipEvent_t done)
 {
     if (W > MAX_W || H > MAX_H || n > MAX_UNION) return -1;
     const size_t dyn = (size_t)(W + H) * sizeof(float4) + (size_t)W * sizeof(float) + (size_t)H * sizeof(float2);
     const int np = fast_pixels_per_lane(W, H);
+    const int layout = n > 0 ? views[0].obs_layout : MV_OBS_RGBA;   // (the gyms of a group share their layout: mv_group_create)
     int unionFrames[2] = {0, 0};
     for (int i = 0; i < n; ++i) unionFrames[views[i].vis_stride > VIS_SMALL ? 1 : 0] += views[i].num_envs * views[i].num_agents;
     if (between) (void)hipEventRecord(between, stream);
@@ -2461,8 +2575,10 @@ int launch_raster_union(const GymView *views, uint32_t *const *obs, const Publis
             }
         for (int i = a.u.n; i <= MAX_UNION; ++i) a.u.first[i] = wgs;
         for (int i = a.u.n; i < MAX_UNION; ++i) a.large[i] = 0;
-        if (np == 2) launch_done(raster_union_all_kernel<6, 2>, dim3(wgs), dim3(256), dyn, stream, done, a, W, H);
-        else launch_done(raster_union_all_kernel<7, 1>, dim3(wgs), dim3(256), dyn, stream, done, a, W, H);
+        const auto fn = by_layout(layout, [&](auto chw) {
+            return np == 2 ? raster_union_all_kernel<6, 2, decltype(chw)::value> : raster_union_all_kernel<7, 1, decltype(chw)::value>;
+        });
+        launch_done(fn, dim3(wgs), dim3(256), dyn, stream, done, a, W, H);
         return 0;
     }
     for (int large = 1; large >= 0; --large) {   // the expensive frames first
@@ -2482,14 +2598,12 @@ int launch_raster_union(const GymView *views, uint32_t *const *obs, const Publis
         }
         if (!ua.n) continue;
         for (int i = ua.n; i <= MAX_UNION; ++i) ua.first[i] = wgs;
-        if (large) {
-            if (lnp == 2) hipLaunchKernelGGL((raster_glist_union_kernel<VIS_XL, true, GLIST_WAVES_NP2, true, 2>),
-                dim3(wgs), dim3(256), dyn, stream, ua, W, H, split);
-            else hipLaunchKernelGGL((raster_glist_union_kernel<VIS_XL, true, GLIST_WAVES_NP1, true, 1>), dim3(wgs), dim3(256), dyn, stream, ua, W, H, split);
-        } else {
-            if (lnp == 2) hipLaunchKernelGGL((raster_fast_union_kernel<VIS_SMALL, true, 6, false, 2>), dim3(wgs), dim3(256), dyn, stream, ua, W, H, split);
-            else hipLaunchKernelGGL((raster_fast_union_kernel<VIS_SMALL, true, 8, false, 1>), dim3(wgs), dim3(256), dyn, stream, ua, W, H, split);
-        }
+        const auto fn = by_layout(layout, [&](auto chw) {
+            constexpr bool C = decltype(chw)::value;
+            return large ? (lnp == 2 ? raster_glist_union_kernel<VIS_XL, true, GLIST_WAVES_NP2, true, 2, C> : raster_glist_union_kernel<VIS_XL, true, GLIST_WAVES_NP1, true, 1, C>)
+                         : (lnp == 2 ? raster_fast_union_kernel<VIS_SMALL, true, 6, false, 2, C> : raster_fast_union_kernel<VIS_SMALL, true, 8, false, 1, C>);
+        });
+        launch_done(fn, dim3(wgs), dim3(256), dyn, stream, nullptr, ua, W, H, split);
     }
     if (done) (void)hipEventRecord(done, stream);   // (one or two launches: recorded behind them)
     return 0;
@@ -2551,8 +2665,10 @@ int launch_raster_union_batch(const GymView *views, uint32_t *const *obs, const 
         }
     for (int i = a.n; i <= MAX_UNION; ++i) a.first[i] = wgs;
     a.per_tick = wgs;
-    if (np == 2) launch_done(raster_union_batch_kernel<6, 2>, dim3(wgs * k), dim3(256), dyn, stream, done, a, W, H);
-    else launch_done(raster_union_batch_kernel<7, 1>, dim3(wgs * k), dim3(256), dyn, stream, done, a, W, H);
+    const auto fn = by_layout(views[0].obs_layout, [&](auto chw) {   // (the gyms of a group share their layout: mv_group_create)
+        return np == 2 ? raster_union_batch_kernel<6, 2, decltype(chw)::value> : raster_union_batch_kernel<7, 1, decltype(chw)::value>;
+    });
+    launch_done(fn, dim3(wgs * k), dim3(256), dyn, stream, done, a, W, H);
     return 0;
 }
 
@@ -2586,24 +2702,16 @@ int launch_raster_batch(const GymView *views, uint32_t *const *obs, const Publis
         a.pub_done[j] = publish ? publish[j].done : nullptr;
     }
     const dim3 grid(k * frames * split), block(256);
-    if (longList) {   // the long-list variants (records through the scalar cache)
-        if (np == 2) {
-            if (hexScen) launch_done(raster_glist_batch_kernel<VIS_XL, true, GLIST_WAVES_NP2, true, 2>, grid, block, dyn, stream, done, a, W, H, split);
-            else launch_done(raster_glist_batch_kernel<VIS_LARGE, false, GLIST_WAVES_NP2, false, 2>, grid, block, dyn, stream, done, a, W, H, split);
-        } else {
-            if (hexScen) launch_done(raster_glist_batch_kernel<VIS_XL, true, GLIST_WAVES_NP1, true, 1>, grid, block, dyn, stream, done, a, W, H, split);
-            else launch_done(raster_glist_batch_kernel<VIS_LARGE, false, GLIST_WAVES_NP1, false, 1>, grid, block, dyn, stream, done, a, W, H, split);
-        }
-        return 0;
-    }
     const bool shapes = gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL;   // (scaled shapes: Rearrange's items, Football's ball)
-    if (np == 2) {
-        if (shapes) launch_done(raster_fast_batch_kernel<VIS_SMALL, true, 6, 2>, grid, block, dyn, stream, done, a, W, H, split);
-        else launch_done(raster_fast_batch_kernel<VIS_SMALL, false, 7, 2>, grid, block, dyn, stream, done, a, W, H, split);
-    } else {
-        if (shapes) launch_done(raster_fast_batch_kernel<VIS_SMALL, true, 8, 1>, grid, block, dyn, stream, done, a, W, H, split);
-        else launch_done(raster_fast_batch_kernel<VIS_SMALL, false, 8, 1>, grid, block, dyn, stream, done, a, W, H, split);
-    }
+    const auto fn = by_layout(gv.obs_layout, [&](auto chw) {
+        constexpr bool C = decltype(chw)::value;
+        if (longList)   // the long-list variants (records through the scalar cache)
+            return np == 2 ? (hexScen ? raster_glist_batch_kernel<VIS_XL, true, GLIST_WAVES_NP2, true, 2, C> : raster_glist_batch_kernel<VIS_LARGE, false, GLIST_WAVES_NP2, false, 2, C>)
+                           : (hexScen ? raster_glist_batch_kernel<VIS_XL, true, GLIST_WAVES_NP1, true, 1, C> : raster_glist_batch_kernel<VIS_LARGE, false, GLIST_WAVES_NP1, false, 1, C>);
+        return np == 2 ? (shapes ? raster_fast_batch_kernel<VIS_SMALL, true, 6, 2, 256, C> : raster_fast_batch_kernel<VIS_SMALL, false, 7, 2, 256, C>)
+                       : (shapes ? raster_fast_batch_kernel<VIS_SMALL, true, 8, 1, 256, C> : raster_fast_batch_kernel<VIS_SMALL, false, 8, 1, 256, C>);
+    });
+    launch_done(fn, grid, block, dyn, stream, done, a, W, H, split);
     return 0;
 }
 
@@ -2627,15 +2735,15 @@ int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t st
         // (Collect, measured and rejected: a 1024-entry launch for the frames above 256 visible primitives + a 256-entry launch for the rest,
         // 75 + 69 us against 107 us for the single 1024-entry launch: each launch pays its own tail, and the cones, not occupancy, dominate)
         const bool hexScen = gv.scenario == SCN_HEX_MEMORY || gv.scenario == SCN_HEX_EXPLORE;
-        KernelFn fn;
-        if (np == 2)
-            fn = hexScen ? raster_glist_kernel<VIS_XL, true, GLIST_WAVES_NP2, true, 2> : gv.vis_stride > VIS_SMALL
-                    ? raster_glist_kernel<VIS_LARGE, false, GLIST_WAVES_NP2, false, 2>
-               : gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL ? raster_fast_kernel<VIS_SMALL, true, 6, false, 2> : raster_fast_kernel<VIS_SMALL, false, 7, false, 2>;
-        else
-            fn = hexScen ? raster_glist_kernel<VIS_XL, true, GLIST_WAVES_NP1, true, 1> : gv.vis_stride > VIS_SMALL
-                    ? raster_glist_kernel<VIS_LARGE, false, GLIST_WAVES_NP1, false, 1>
-               : gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL ? raster_fast_kernel<VIS_SMALL, true, 8> : raster_fast_kernel<VIS_SMALL, false, 8>;
+        const bool shapes = gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL, large = gv.vis_stride > VIS_SMALL;
+        const KernelFn fn = by_layout(gv.obs_layout, [&](auto chw) -> KernelFn {
+            constexpr bool C = decltype(chw)::value;
+            if (np == 2)
+                return hexScen ? raster_glist_kernel<VIS_XL, true, GLIST_WAVES_NP2, true, 2, C> : large ? raster_glist_kernel<VIS_LARGE, false, GLIST_WAVES_NP2, false, 2, C>
+                     : shapes ? raster_fast_kernel<VIS_SMALL, true, 6, false, 2, 256, C> : raster_fast_kernel<VIS_SMALL, false, 7, false, 2, 256, C>;
+            return hexScen ? raster_glist_kernel<VIS_XL, true, GLIST_WAVES_NP1, true, 1, C> : large ? raster_glist_kernel<VIS_LARGE, false, GLIST_WAVES_NP1, false, 1, C>
+                 : shapes ? raster_fast_kernel<VIS_SMALL, true, 8, false, 1, 256, C> : raster_fast_kernel<VIS_SMALL, false, 8, false, 1, 256, C>;
+        });
         const int ftiles = ((W + TILE_W - 1) / TILE_W) * ((H + TILE_H * np - 1) / (TILE_H * np));
         // Fine-grained tail.  The SIMD's arbiter serves its OLDEST wave first: workgroups finish roughly in launch order whatever they cost (wave life
         // by decile of the launch order, frames in random order: 18 us for the first tenth, 35 us for the eighth, all started within 0.3 us -- r05b),
@@ -2662,11 +2770,13 @@ int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t st
     int split = 4;
     while (split > 1 && tiles < 4 * split * 2) split >>= 1;   // keep at least two tiles per wave
     const dim3 grid(frames * split), block(256);
-    if (gv.scenario == SCN_HEX_MEMORY || gv.scenario == SCN_HEX_EXPLORE) hipLaunchKernelGGL((raster_kernel<VIS_XL, true>),
-        grid, block, dyn, stream, gv, obs, W, H, split, gv.lpt_order);
-    else if (gv.vis_stride > VIS_SMALL) hipLaunchKernelGGL((raster_kernel<VIS_LARGE, false>), grid, block, dyn, stream, gv, obs, W, H, split, gv.lpt_order);
-    else if (gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL) hipLaunchKernelGGL((raster_kernel<VIS_SMALL, true>), grid, block, dyn, stream, gv, obs, W, H, split, gv.lpt_order);
-    else hipLaunchKernelGGL((raster_kernel<VIS_SMALL, false>), grid, block, dyn, stream, gv, obs, W, H, split, gv.lpt_order);
+    const bool hexScen = gv.scenario == SCN_HEX_MEMORY || gv.scenario == SCN_HEX_EXPLORE, shapes = gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL;
+    const auto fn = by_layout(gv.obs_layout, [&](auto chw) {
+        constexpr bool C = decltype(chw)::value;
+        return hexScen ? raster_kernel<VIS_XL, true, C> : gv.vis_stride > VIS_SMALL ? raster_kernel<VIS_LARGE, false, C>
+             : shapes ? raster_kernel<VIS_SMALL, true, C> : raster_kernel<VIS_SMALL, false, C>;
+    });
+    launch_done(fn, grid, block, dyn, stream, nullptr, gv, obs, W, H, split, (const int *)gv.lpt_order);
     if (done) (void)hipEventRecord(done, stream);
     return 0;
 }

@@ -81,7 +81,8 @@ def all_gather_scalars(rewards, dones, group=None):
 
 
 def all_gather_observations(local_obs, out=None, group=None):
-    """local_obs: uint8 [n_local*A, H, W, 4] -> job-wide slab [world*n_local*A, H, W, 4] (RCCL on GPUs)."""
+    """local_obs: a uint8 slab of frames in either layout -- [n_local*A, H, W, 4] RGBA, or [n_local*A, 3, H, W] (obs_layout='chw') -- ->
+    the job-wide slab [world*n_local*A, ...] of the same frame shape (RCCL on GPUs; nothing here depends on the frame's shape)."""
     import torch
     import torch.distributed as dist
     world = dist.get_world_size(group)

@@ -52,6 +52,7 @@ SYMBOLS = [
     ("mv_true_objectives_device_ptr", _P, [_P]),
     ("mv_set_obs_buffer", C.c_int, [_P, _P]), ("mv_set_stream", C.c_int, [_P, _P]),
     ("mv_set_pixel_mode", C.c_int, [_P, _I]), ("mv_get_pixel_mode", C.c_int, [_P]),
+    ("mv_set_obs_layout", C.c_int, [_P, _I]), ("mv_get_obs_layout", C.c_int, [_P]),
     ("mv_set_render_resolution", C.c_int, [_P, _I, _I]), ("mv_draw_hires", C.c_int, [_P]),
     ("mv_get_hires_observation", C.c_int, [_P, _I, _I, _P]), ("mv_draw_overview", C.c_int, [_P]),
     ("mv_num_reward_shaping_keys", C.c_int, [_P]), ("mv_reward_shaping_key", C.c_char_p, [_P, _I]),
@@ -354,6 +355,18 @@ class MegaverseGym:
 
     def pixel_mode(self):
         return "fast" if self._lib.mv_get_pixel_mode(self._g) == 1 else "exact"
+
+    def set_obs_layout(self, layout):
+        """the observation slab's layout (include/megaverse_hip.h: mv_set_obs_layout): 'rgba' ([N*A][h][w][4], the default) or 'chw' ([N*A][3][h][w]
+        uint8, planes R, G, B, written so by the observation pass); before the gym's first reset / render / set_obs_buffer / set_output_ring"""
+        if isinstance(layout, str):
+            if layout not in ("rgba", "chw"):
+                raise ValueError(f"set_obs_layout: {layout!r}: the layouts are 'rgba' and 'chw'")
+            layout = 0 if layout == "rgba" else 1
+        self._ck(self._lib.mv_set_obs_layout(self._g, int(layout)))
+
+    def obs_layout(self):
+        return "chw" if self._lib.mv_get_obs_layout(self._g) == 1 else "rgba"
 
     def set_pipelining(self, on):
         """one-step-ahead pipelining of the step kernels against the observation pass (include/megaverse_hip.h); on by default"""

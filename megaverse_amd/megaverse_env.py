@@ -11,7 +11,9 @@ Differences, all additive:
   * ``step_batched`` / ``step_device`` / ``observations_tensor`` return one device tensor instead of O(num_agents)
     numpy views (the Python loops at megaverse_env.py:121-130,138-141 cap the reference well below
     the GPU's rate);
-  * gym and cv2 are optional.
+  * gym and cv2 are optional;
+  * ``obs_layout="chw"`` (opt-in): the observation pass writes the frames as (3, H, W) planes itself, so the device tensors are contiguous and the
+    host copy moves 3 bytes per pixel instead of 4 (include/megaverse_hip.h: mv_set_obs_layout).
 """
 import numpy as np
 
@@ -50,8 +52,11 @@ def make_env_multitask(multitask_name, task_idx, num_envs, num_agents_per_env, n
 
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
-                 img_w=128, img_h=72, device=0, env_offset=0, total_envs=0):
+                 img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba"):
+        if obs_layout not in ("rgba", "chw"):
+            raise ValueError("obs_layout must be 'rgba' (frames written as (H, W, 4) RGBA, handed out as a permuted view) or 'chw' (written as (3, H, W))")
         scenario_name = scenario_name.casefold()
+        self.obs_layout = obs_layout
         self.scenario_name = scenario_name
         self.is_multiagent = True
         set_megaverse_log_level(2)
@@ -73,6 +78,8 @@ class MegaverseEnv:
 
         self.env = MegaverseGym(self.scenario_name, self.img_w, self.img_h, num_envs, num_agents_per_env, num_simulation_threads,
                                 use_vulkan, float_params, device=device, env_offset=env_offset, total_envs=total_envs)
+        if obs_layout == "chw":
+            self.env.set_obs_layout("chw")
         self.default_shaping_scheme = self.env.get_reward_shaping(0, 0)
         self.action_space = self.generate_action_space(self.env.action_space_sizes())
         self.observation_space = spaces.Box(0, 255, (self.channels, self.img_h, self.img_w), dtype=np.uint8)
@@ -97,15 +104,18 @@ class MegaverseEnv:
         return [frames[i] for i in range(self.num_agents)]
 
     def observations_numpy(self):
-        """(num_agents, 3, H, W) uint8 on the host: ONE D2H copy of the RGBA slab into a pinned buffer (PCIe: ~64 MB per step at 1024 x 128 x 128 -- the
-        reference's getObservation is a view of host memory, megaverse.cpp:139-143, here the frames live in HBM), returned as a transposed view of it like
-        the reference's np.transpose(obs[:, :, :3], (2, 0, 1)) (megaverse_env.py:121-130); valid until the next call"""
+        """(num_agents, 3, H, W) uint8 on the host: ONE D2H copy of the slab into a pinned buffer (the reference's getObservation is a view of host
+        memory, megaverse.cpp:139-143, here the frames live in HBM).  obs_layout 'rgba': the RGBA slab, 4 bytes per pixel (PCIe: ~64 MB per step at
+        1024 x 128 x 128), returned as a transposed view of it like the reference's np.transpose(obs[:, :, :3], (2, 0, 1)) (megaverse_env.py:121-130);
+        'chw': the planes, 3 bytes per pixel (~48 MB), returned as they are.  Valid until the next call"""
         torch = self._torch()
-        slab = self.observations_tensor(rgba=True)
+        slab = self.observations_tensor(rgba=self.obs_layout == "rgba")   # (obs_layout 'chw': the planes themselves, 3 bytes per pixel)
         if self._host_obs is None:
             self._host_obs = torch.empty(slab.shape, dtype=torch.uint8, pin_memory=True)
         self._host_obs.copy_(slab, non_blocking=True)
         torch.cuda.current_stream(slab.device).synchronize()
+        if self.obs_layout == "chw":
+            return self._host_obs.numpy()
         return self._host_obs.numpy()[..., :3].transpose(0, 3, 1, 2)
 
     def reset(self):
@@ -134,14 +144,22 @@ class MegaverseEnv:
 
     def observations_tensor(self, rgba=False):
         """uint8 CUDA tensor viewing the HBM observation slab written by the raster kernel:
-        (num_agents, 3, H, W) (a permuted view, no copy) or (num_agents, H, W, 4) if rgba."""
+        (num_agents, 3, H, W) (a permuted view, no copy; obs_layout 'chw': the contiguous slab itself) or (num_agents, H, W, 4) if rgba
+        (obs_layout 'rgba' only: a 'chw' slab has no alpha to hand out -- ValueError)."""
         torch = self._torch()
+        if rgba and self.obs_layout == "chw":
+            raise ValueError("observations_tensor(rgba=True): this env writes its frames as (3, H, W) planes (obs_layout='chw')")
         if self._obs_tensor is None:
-            self._obs_tensor = torch.empty((self.num_agents, self.img_h, self.img_w, 4), dtype=torch.uint8, device=f'cuda:{self.device}')
+            shape = (self.num_agents, 3, self.img_h, self.img_w) if self.obs_layout == "chw" else (self.num_agents, self.img_h, self.img_w, 4)
+            self._obs_tensor = torch.empty(shape, dtype=torch.uint8, device=f'cuda:{self.device}')
             self.env.set_obs_buffer(self._obs_tensor.data_ptr())
             self.env.render()
         self.env.synchronize()
-        if rgba:
+        return self._obs_view() if not rgba else self._obs_tensor
+
+    def _obs_view(self):
+        """the slab as (num_agents, 3, H, W)"""
+        if self.obs_layout == "chw":
             return self._obs_tensor
         return self._obs_tensor[..., :3].permute(0, 3, 1, 2)
 
@@ -187,7 +205,7 @@ class MegaverseEnv:
                 self.env.set_actions_batched(actions)
         self.env.step()
         del held
-        return self._obs_tensor[..., :3].permute(0, 3, 1, 2), self._dev_out[0], self._dev_out[1]
+        return self._obs_view(), self._dev_out[0], self._dev_out[1]
 
     # ---- rendering (megaverse_env.py:164-184): returns the tiled BGR image, shows it if cv2 exists ----
     def convert_obs(self, obs):

@@ -27,8 +27,13 @@ MEGAVERSE_IN_SCOPE = MEGAVERSE8   # (older name)
 
 class MultiTaskGym:
     def __init__(self, scenarios, w, h, num_envs, num_agents_per_env, num_simulation_threads=4, float_params=None, device=0,
-                 env_offset=0, total_envs=0):
+                 env_offset=0, total_envs=0, obs_layout="rgba"):
+        """obs_layout: 'rgba' -- frames [h, w, 4] -- or 'chw' -- [3, h, w], written so by the observation pass (include/megaverse_hip.h:
+        mv_set_obs_layout); attach / attach_tensor / set_output_ring allocate and check frames of that shape"""
         S = len(scenarios)
+        if obs_layout not in ("rgba", "chw"):
+            raise ValueError("obs_layout must be 'rgba' or 'chw'")
+        self.obs_layout = obs_layout
         if num_envs % S:
             raise ValueError("num_envs must be a multiple of the number of scenarios")
         self.scenarios = list(scenarios)
@@ -43,6 +48,8 @@ class MultiTaskGym:
         self.gyms = [MegaverseGym(name, w, h, self.per_task, num_agents_per_env, num_simulation_threads, False, float_params or {},
                                   device=device, env_offset=env_offset + k, total_envs=total, env_stride=S)
                      for k, name in enumerate(self.scenarios)]
+        for g in self.gyms:
+            g.set_obs_layout(obs_layout)
         self.union = os.environ.get("MV_MULTITASK_UNION", "1") != "0" and len(self.gyms) <= 8
         if not self.union:
             for g in self.gyms:   # the sub-gyms overlap each other, one stream each: a second (simulation) stream per gym only
@@ -58,13 +65,18 @@ class MultiTaskGym:
     def attach(self, torch_device):
         import torch
         A = self.num_agents_per_env
-        return self.attach_tensor(torch.empty((self.num_envs * A, self.h, self.w, 4), dtype=torch.uint8, device=torch_device))
+        return self.attach_tensor(torch.empty((self.num_envs * A,) + self.frame_shape(), dtype=torch.uint8, device=torch_device))
+
+    def frame_shape(self):
+        """one observation frame: (h, w, 4), or (3, h, w) with obs_layout='chw'"""
+        return (3, self.h, self.w) if self.obs_layout == "chw" else (self.h, self.w, 4)
 
     def attach_tensor(self, obs):
-        """render into the caller's [num_envs * A, h, w, 4] uint8 slab (one stream per scenario, created on first use)"""
+        """render into the caller's [num_envs * A, h, w, 4] uint8 slab -- [num_envs * A, 3, h, w] with obs_layout='chw' (one stream per scenario,
+        created on first use)"""
         import torch
         A, n = self.num_agents_per_env, self.per_task
-        assert tuple(obs.shape) == (self.num_envs * A, self.h, self.w, 4) and obs.dtype == torch.uint8 and obs.is_contiguous()
+        assert tuple(obs.shape) == (self.num_envs * A,) + self.frame_shape() and obs.dtype == torch.uint8 and obs.is_contiguous()
         if self.union:
             if self._group is None:   # one stream for all of them: torch's current one
                 cur = torch.cuda.current_stream(obs.device).cuda_stream
@@ -76,14 +88,14 @@ class MultiTaskGym:
             for k, g in enumerate(self.gyms):
                 g.set_stream(self._streams[k].cuda_stream)
         self._obs = obs
-        frame_bytes = self.h * self.w * 4
+        frame_bytes = int(np.prod(self.frame_shape()))
         for k, g in enumerate(self.gyms):
             g.set_obs_buffer(obs.data_ptr() + k * n * A * frame_bytes)
         return obs
 
     def set_output_ring(self, count):
         """Rollout rings, one set per scenario (mv_set_output_ring): tick t of sub-gym k leaves its observations in ``ring_obs[k][t % count]``
-        ([count, n_k * A, h, w, 4] uint8), its rewards in ``ring_rewards[k][t % count]`` and its dones in ``ring_dones[k][t % count]``.  With rings at
+        ([count, n_k * A, h, w, 4] uint8; obs_layout='chw': [count, n_k * A, 3, h, w]), its rewards in ``ring_rewards[k][t % count]`` and its dones in ``ring_dones[k][t % count]``.  With rings at
         least as deep as a call (of 2 ... 8 ticks; up to 1024 envs in the group), ``step_n`` is TWO launches for all scenarios and all of its ticks (one union
         step launch, one union observation launch); otherwise two launches per tick.  count = 0: back to the shared slab.  -> (ring_obs, ring_rewards, ring_dones), lists of CUDA tensors."""
         import torch
@@ -94,7 +106,7 @@ class MultiTaskGym:
             return None
         dev = self._obs.device if self._obs is not None else torch.device("cuda", self.gyms[0].device if hasattr(self.gyms[0], "device") else 0)
         A, n = self.num_agents_per_env, self.per_task
-        self.ring_obs = [torch.zeros((count, n * A, self.h, self.w, 4), dtype=torch.uint8, device=dev) for _ in self.gyms]
+        self.ring_obs = [torch.zeros((count, n * A) + self.frame_shape(), dtype=torch.uint8, device=dev) for _ in self.gyms]
         self.ring_rewards = [torch.zeros((count, n * A), dtype=torch.float32, device=dev) for _ in self.gyms]
         self.ring_dones = [torch.zeros((count, n), dtype=torch.uint8, device=dev) for _ in self.gyms]
         torch.cuda.synchronize(dev)

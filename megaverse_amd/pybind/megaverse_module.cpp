@@ -156,6 +156,13 @@ public:
         return dones;
     }
     std::uintptr_t obs_device_ptr() const { return reinterpret_cast<std::uintptr_t>(mv_obs_device_ptr(gym_)); }
+    // the slab's layout (mv_set_obs_layout): "rgba" ([N*A][h][w][4], default) or "chw" ([N*A][3][h][w]); before the first reset
+    void set_obs_layout(const std::string &layout)
+    {
+        if (layout != "rgba" && layout != "chw") throw std::runtime_error("set_obs_layout: 'rgba' or 'chw'");
+        check(mv_set_obs_layout(gym_, layout == "chw" ? MV_OBS_RGB_PLANAR : MV_OBS_RGBA));
+    }
+    std::string obs_layout() const { return mv_get_obs_layout(gym_) == MV_OBS_RGB_PLANAR ? "chw" : "rgba"; }
 
 private:
     mv_gym *gym_ = nullptr;
@@ -191,5 +198,7 @@ PYBIND11_MODULE(megaverse, m)
         .def("close", &Gym::close)
         .def("set_actions_batched", &Gym::set_actions_batched)
         .def("get_dones", &Gym::get_dones)
-        .def("obs_device_ptr", &Gym::obs_device_ptr);
+        .def("obs_device_ptr", &Gym::obs_device_ptr)
+        .def("set_obs_layout", &Gym::set_obs_layout)
+        .def("obs_layout", &Gym::obs_layout);
 }
