@@ -199,6 +199,44 @@ int mv_set_reward_shaping(mv_gym *g, int32_t env_idx, int32_t agent_idx, const c
 
 int mv_synchronize(mv_gym *g);
 
+/* Episode log (opt-in; no reference counterpart in the simulator: the reference's learner wrapper sums every agent's rewards on the host, tick by tick, and
+ * reports them when the env is done -- megaverse_rl/megaverse_utils.py:61-86).  With the log on a gym keeps, on the device, a running return per agent
+ * (double ret[N*A]) and a running length per env (int32 len[N]), both zero after mv_set_episode_log and after every mv_reset.  Every stepped tick (mv_step,
+ * mv_step_no_render, each tick of mv_step_n / mv_step_many / mv_group_step), in tick order: ret[i] += (double)reward[i], len[e] += 1; then every env that
+ * is done appends one record per agent, in agent order, and its ret and len go back to zero.  Records therefore stand in ascending (end_tick, agent) order,
+ * and the log of a run is reproducible byte for byte.  end_tick counts the ticks stepped since the last mv_reset (the first tick after it is 0);
+ * true_objective is what the finishing tick recorded.  Episodes cut by mv_reset are not logged; an episode that was running when the log was switched on is
+ * counted from that tick.  The log is a linear device buffer of `capacity` records: a record that does not fit is dropped and counted (the accumulators
+ * are reset all the same), and -- like every fixed capacity here -- reported once, by a later stepping call that returns 1; draining makes room and
+ * re-arms the report.
+ * mv_set_episode_log: capacity > 0 allocates and switches on (again: from zero accumulators and an empty buffer), 0 switches off and frees; valid between
+ * calls at any time, also on a gym in a group (every member keeps its own log).  Rewards, dones, true objectives and observations are what they are
+ * without the log.
+ * Currency: every stepping call leaves the log up to date at its end, ordered on the caller's stream with the call's other outputs (one small launch per
+ * call and gym; a call of more ticks than the internal batch: one per chunk).  Nothing is deferred -- the deferral bound is 0 ticks -- so
+ * mv_flush_episode_log has nothing to enqueue today; callers that read the device pointers should still call it, it is where a deferred update would go.
+ * mv_episode_log_count / mv_drain_episode_log flush, synchronise the caller's stream and read; drain copies the oldest max_records records out, removes
+ * them (the rest moves to the front) and returns how many it copied.  dropped: records lost since the log was switched on.
+ * Device pointers (valid until mv_set_episode_log / mv_close): the records, the header {uint32 count, uint32 dropped, 2 x uint32 internal}, ret, len.
+ * mv_arena_bytes includes the log. */
+typedef struct mv_episode_record {
+    int32_t agent;          /* env * A + agent, local to the gym */
+    int32_t length;         /* ticks, the finishing tick included */
+    uint32_t end_tick;      /* ticks stepped since the last mv_reset, before the finishing tick */
+    float true_objective;
+    double ret;             /* float64 sum of the episode's float32 rewards */
+} mv_episode_record;       /* 24 bytes */
+int mv_set_episode_log(mv_gym *g, int32_t capacity);
+int mv_get_episode_log_capacity(const mv_gym *g);   /* 0: off; -1: no gym */
+int mv_flush_episode_log(mv_gym *g);
+int mv_episode_log_count(mv_gym *g, uint32_t *count, uint32_t *dropped);
+int mv_drain_episode_log(mv_gym *g, mv_episode_record *out_host, int32_t max_records, uint32_t *dropped);
+void *mv_episode_log_records_device_ptr(mv_gym *g);   /* mv_episode_record [capacity] */
+void *mv_episode_log_count_device_ptr(mv_gym *g);     /* uint32 [4]: count, dropped, internal */
+void *mv_episode_returns_device_ptr(mv_gym *g);       /* double [N*A] */
+void *mv_episode_lengths_device_ptr(mv_gym *g);       /* int32 [N] */
+int64_t mv_ticks_since_reset(const mv_gym *g);        /* what the next tick's end_tick would be; -1: no gym */
+
 /* In-stream kernel timing with HIP events on the gym's own stream (bench.py roofline leg, in a loop of its own: never inside
  * the timed region).  After mv_profile_begin the next max_steps calls of mv_step record events around the launches;
  * mv_profile_end synchronises and returns the mean milliseconds and sample count per interval: [0] step kernel (physics + logic +
@@ -248,6 +286,11 @@ int mv_debug_generate_football(int32_t num_agents, int32_t env_seed, int32_t n, 
  * receives the n-th of each (count x the record size), *ms_per_launch the mean duration of a launch of `count` wavefronts.  Replaces CollectScenario::reset +
  * createLandscape + addEpisodeDrawables (scenario_collect.cpp:20-161,190-214), siv::PerlinNoise (perlin_noise.hpp:118-126,315-318). */
 int mv_debug_collect_draw_host(int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes);
+/* Host-only (no device): the episode log's per-tick body (megaverse_amd/csrc/mv_episode_log.h, the source the kernel runs) over k ticks of N envs x A
+ * agents: rewards [k][N*A], dones [k][N], true_objectives [k][N*A]; first_tick: the first tick's end_tick.  In and out: ret [N*A], len [N], *count, *dropped,
+ * and records, a buffer of `capacity` mv_episode_record of which *count are valid on entry. */
+int mv_debug_episode_log_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
+                              uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped);
 int mv_debug_collect_draw_device(int32_t device, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n, float base_episode_len, void *out,
                                  int64_t out_bytes, float *ms_per_launch);
 

@@ -678,6 +678,7 @@ int mv_close(mv_gym *g)
         }
         (void)hipFree(gv.dbg);
     }
+    episode_log_free(g);
     if (g->arena) (void)hipFree(g->arena);
     if (g->hiresObs) (void)hipFree(g->hiresObs);
     if (g->hBlobs) (void)(g->blobsOnDevice ? hipFree(g->hBlobs) : hipHostFree(g->hBlobs));
@@ -860,6 +861,7 @@ int check_status_flags(mv_gym *g)
         "uploaded now); ";
     if (flags & ST_CANDIDATES) msg += "collision candidate list overflow (more than 128 bodies around one agent); ";
     if (flags & ST_VISIBLE) msg += "a frame had more visible primitives than the raster keeps (256; Collect 1024; Hex* 2048): the excess was not drawn; ";
+    if (flags & elog::ST_EPISODE_LOG) msg += "the episode log is full: finished episodes are being dropped (counted; drain it, or give it a larger capacity); ";
     if (flags & ST_CHUNK) msg += "an object placement outside the 32 x 16 x 32 voxel chunk was refused (the reference's grid is unbounded); ";
     if (gen & GEN_SLABS) msg += "a generated layout merged into more slabs than an episode record holds (128, Collect 1024): the excess was dropped; ";
     if (gen & GEN_TERRAIN) msg += "more than 16 terrain boxes in a generated episode; ";
@@ -1086,6 +1088,7 @@ int mv_reset(mv_gym *g)
         launch_tower_draw(v, g->stream);
     }
     HIP_TRY(hipGetLastError());
+    if (episode_log_reset(g)) return -1;   // (episodes cut by a reset are not logged)
     g->wasReset = true;
     g->mirrorsFresh = false;
     if (mv_render(g)) return -1;

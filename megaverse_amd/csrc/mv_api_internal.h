@@ -27,6 +27,7 @@
 #include "mv_rng.h"
 #include "mv_types.h"
 #include "mv_union.h"
+#include "mv_episode_log.h"
 
 namespace mv {
 // TowerBuilding: tops every env's ring of drawn episodes up (mv_reset.hip)
@@ -187,6 +188,16 @@ struct mv_gym {
     hipEvent_t lastUpload = nullptr;                // the most recent batch (mv_reset: the caller's stream waits for it too)
     bool uploadNotOnUser = false;                   // ... and a step that runs on the caller's stream has not waited for it yet
     size_t uploadRing = 0;
+    // mv_set_episode_log: returns / lengths summed on the device, one record per agent of a finished env (mv_episode_log.h).  One allocation:
+    // header, ret [N*A], len [N], records [logCapacity]; updated by one launch per stepping call on the caller's stream.
+    int logCapacity = 0;                         // 0: off
+    uint8_t *logMem = nullptr;
+    size_t logBytes = 0;
+    elog::Header *logHdr = nullptr;
+    double *logRet = nullptr;
+    int32_t *logLen = nullptr;
+    elog::Record *logRecords = nullptr;
+    uint32_t ticksSinceReset = 0;                // ticks stepped since the last mv_reset: a record's end_tick
     // in-stream profiling
     std::vector<hipEvent_t> profEvents;          // 5 per profiled tick: [0] [1] around the step kernel (its stream), [2] [3] [4] before the
                                                  // observation pass, between frame sort and raster, after the raster (the caller's stream)
@@ -217,4 +228,8 @@ int refill_episodes(mv_gym *g, int k);   // k: the ticks of the stepping call th
 int read_back_status(mv_gym *g, hipEvent_t after);   // after: an event recorded behind the kernel whose status words are wanted
 int flush_device_actions(mv_gym *g);
 void group_detach(mv_gym *g);   // (mv_api_step.hip)
+// the episode log of g brought up to the k ticks just enqueued: views[j * stride] is tick j's view (its staged outputs); on the caller's stream (mv_episode_log.hip)
+int episode_log_update(mv_gym *g, const GymView *views, int stride, int k);
+int episode_log_reset(mv_gym *g);   // mv_reset: accumulators to zero, the records stay
+void episode_log_free(mv_gym *g);   // mv_close
 }  // namespace mvapi

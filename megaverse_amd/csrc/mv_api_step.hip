@@ -16,7 +16,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
 {
     mv_gym *const L = gs[0];
     int batch = L->batch;
-    bool mustWait = false, allFast = true, anyHostEpisodes = false;
+    bool mustWait = false, allFast = true, anyHostEpisodes = false, anyLog = false;
     for (int i = 0; i < n; ++i) {
         mv_gym *g = gs[i];
         if (check(g)) return -1;
@@ -25,6 +25,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
         mustWait = mustWait || g->simMustWaitUser;
         allFast = allFast && g->fastPixels != 0;
         anyHostEpisodes = anyHostEpisodes || g->hostEpisodes();
+        anyLog = anyLog || g->logCapacity > 0;
     }
     if (k < 1 || k > batch) return fail("mv_step_n: 1 <= k <= " + std::to_string(batch) + " (MV_PIPE_BATCH) required");
     HIP_TRY(hipSetDevice(L->device));
@@ -38,6 +39,9 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     // the two queue hand-overs, ~10 us each, would be pure cost): the step runs on the caller's stream like everything else.
     const bool own = L->pipelined != 0 && !(mustWait && k == 1);
     hipStream_t sim = own ? L->simStream : L->stream;
+    // The step kernels stage rewards / dones / true objectives in their hand-over slot and the caller's stream publishes them -- or, not pipelined, write the
+    // public arrays themselves.  With an episode log (mv_set_episode_log) they always stage: the log reads every tick of the call from the slots.
+    const bool staged = own || anyLog;
     if (own) {
         // The simulation stream may reuse a slot group once the observation passes that read it are done: the END of the call PIPE_GROUPS calls
         // ago (userMark, completed by that call's last pass, see below).  When the caller's stream feeds the simulation (reset / render / device
@@ -139,7 +143,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
             OutPtrs &o = outs[(size_t)j * n + i];
             o = outputs_of(g, g->ringTick++);
             GymView &v = views[(size_t)j * n + i];
-            v = view(g, g->parity, own ? nullptr : &o);
+            v = view(g, g->parity, staged ? nullptr : &o);
             if (j == 0 && g->gv.sample_on == POLICY_NONE) v.md_actions = g->mdActions;
             if (groupBatch) v.lpt_no_clear = 1;   // (the passes clear their histograms themselves: mv_raster.hip, hist_done)
             if (n > 1) { ua.first[i] = envs; ua.gv[i] = v; envs += g->N; }
@@ -261,12 +265,12 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
             pubs[i] = PublishTo{o.rewards, o.done, gs[i]->gv.true_objective};
             obsPtrs[i] = o.obs;
             // (the fast observation pass publishes with its first workgroups)
-            if (own && (!render || !allFast) && publish_outputs(gs[i], gs[i]->group * gs[i]->batch + j, o)) return -1;
+            if (staged && (!render || !allFast) && publish_outputs(gs[i], gs[i]->group * gs[i]->batch + j, o)) return -1;
         }
         // the call's last pass completes this call's mark (what the simulation stream waits for before it reuses the slot group)
         hipEvent_t mark = own && j == k - 1 ? L->userMark[L->markCount % PIPE_GROUPS] : nullptr;
         if (render && batchRaster) {
-            const bool pubInRaster = own;
+            const bool pubInRaster = staged;
             chunkPubs.push_back(pubs[0]);
             chunkObs.push_back(obsPtrs[0]);
             // (0: off, launch_raster_batch declines)
@@ -310,7 +314,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
                 for (size_t q = 0; q < (size_t)n * k; ++q) gs[q % (size_t)n]->histClean[(size_t)views[q].lpt_parity] = 1;
             }
         } else if (render) {
-            const bool pubInRaster = own && allFast;
+            const bool pubInRaster = staged && allFast;
             if (n > 1 && allFast) {
                 if (launch_raster_union(&views[(size_t)j * n], obsPtrs.data(), pubInRaster ? pubs.data() : nullptr,
                     n, L->w, L->h, L->stream, evs[j] ? evs[j][3] : nullptr, mark))
@@ -327,6 +331,13 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
         } else if (mark) HIP_TRY(hipEventRecord(mark, L->stream));
         if (evs[j]) HIP_TRY(hipEventRecord(evs[j][4], L->stream));
     }
+    // ---- the episode logs: one launch per gym for the call's k ticks, on the caller's stream behind the call's publication.  It reads the call's slots, so
+    // the mark that lets the simulation stream reuse them is recorded again behind it.
+    for (int i = 0; i < n; ++i) {
+        if (gs[i]->logCapacity > 0 && episode_log_update(gs[i], views.data() + i, n, k)) return -1;
+        gs[i]->ticksSinceReset += (uint32_t)k;
+    }
+    if (anyLog && own) HIP_TRY(hipEventRecord(L->userMark[L->markCount % PIPE_GROUPS], L->stream));
     if (own) {
         ++L->markCount;
         for (int i = 0; i < n; ++i) gs[i]->markCount = L->markCount;
@@ -515,7 +526,7 @@ int mv_recommended_pass_overlap(const mv_gym *g)
     return 1;
 }
 
-int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)g->arenaBytes : 0; }
+int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes) : 0; }
 
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index)
 {   // several gyms of one job (MultiTaskGym: one per scenario, one stream each) stepped by one call: at eight sub-gyms the per-call cost of

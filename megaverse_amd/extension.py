@@ -74,7 +74,47 @@ SYMBOLS = [
     ("mv_debug_generate_football", C.c_int, [_I, _I, _I, _F, _P, _I]),
     ("mv_debug_collect_draw_host", C.c_int, [_I, _I, _I, _F, _P, _I]),
     ("mv_debug_collect_draw_device", C.c_int, [_I, _I, _P, _I, _I, _F, _P, C.c_int64, _P]),
+    ("mv_set_episode_log", C.c_int, [_P, _I]), ("mv_get_episode_log_capacity", C.c_int, [_P]), ("mv_flush_episode_log", C.c_int, [_P]),
+    ("mv_episode_log_count", C.c_int, [_P, C.POINTER(_U), C.POINTER(_U)]), ("mv_drain_episode_log", C.c_int, [_P, _P, _I, C.POINTER(_U)]),
+    ("mv_episode_log_records_device_ptr", _P, [_P]), ("mv_episode_log_count_device_ptr", _P, [_P]),
+    ("mv_episode_returns_device_ptr", _P, [_P]), ("mv_episode_lengths_device_ptr", _P, [_P]), ("mv_ticks_since_reset", C.c_int64, [_P]),
+    ("mv_debug_episode_log_host", C.c_int, [_P, _P, _P, _I, _I, _I, _I, _U, _P, _P, _P, C.POINTER(_U), C.POINTER(_U)]),
 ]
+
+# mv_episode_record (include/megaverse_hip.h): one finished episode of one agent, 24 bytes
+EPISODE_RECORD_DTYPE = np.dtype({"names": ["agent", "length", "end_tick", "true_objective", "ret"],
+                                 "formats": ["<i4", "<i4", "<u4", "<f4", "<f8"], "offsets": [0, 4, 8, 12, 16], "itemsize": 24})
+
+
+class _DeviceArray:
+    """a device pointer as something torch.as_tensor takes (the CUDA array interface): no copy, the gym keeps the memory"""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+def debug_episode_log_host(rewards, dones, true_objectives, agents_per_env, capacity, first_tick=0, state=None):
+    """mv_debug_episode_log_host: the episode log's per-tick body on the CPU (no device).  rewards / true_objectives [k][N*A] float32, dones [k][N] uint8.
+    state: what an earlier call returned (carried on), or None for a log just switched on.  -> state = {'ret', 'len', 'records', 'count', 'dropped'};
+    state['records'][:state['count']] is the log."""
+    lib = load_library()
+    rewards = np.ascontiguousarray(rewards, np.float32)
+    dones = np.ascontiguousarray(dones, np.uint8)
+    true_objectives = np.ascontiguousarray(true_objectives, np.float32)
+    k, N = dones.shape
+    A = int(agents_per_env)
+    if rewards.shape != (k, N * A) or true_objectives.shape != (k, N * A):
+        raise ValueError("debug_episode_log_host: rewards and true_objectives are [k][N*A], dones [k][N]")
+    if state is None:
+        state = {"ret": np.zeros(N * A, np.float64), "len": np.zeros(N, np.int32), "records": np.zeros(max(int(capacity), 0), EPISODE_RECORD_DTYPE),
+                 "count": 0, "dropped": 0}
+    count, dropped = _U(state["count"]), _U(state["dropped"])
+    if lib.mv_debug_episode_log_host(rewards.ctypes.data, dones.ctypes.data, true_objectives.ctypes.data, k, N, A, int(capacity), int(first_tick) & 0xFFFFFFFF,
+                                     state["ret"].ctypes.data, state["len"].ctypes.data, state["records"].ctypes.data,
+                                     C.byref(count), C.byref(dropped)) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    state["count"], state["dropped"] = int(count.value), int(dropped.value)
+    return state
 
 
 def library_path():
@@ -311,6 +351,65 @@ class MegaverseGym:
 
     def arena_bytes(self):
         return int(self._lib.mv_arena_bytes(self._g))
+
+    # ---- episode log (include/megaverse_hip.h: mv_set_episode_log; no reference counterpart) ----
+    def set_episode_log(self, capacity):
+        """capacity > 0: per-agent returns and per-env lengths are summed on the device and every finished env appends one record per agent to a device
+        buffer of `capacity` records, in (end_tick, agent) order; 0: off"""
+        self._ck(self._lib.mv_set_episode_log(self._g, int(capacity)))
+
+    def episode_log_capacity(self):
+        return int(self._lib.mv_get_episode_log_capacity(self._g))
+
+    def flush_episode_log(self):
+        self._ck(self._lib.mv_flush_episode_log(self._g))
+
+    def episode_log_count(self):
+        """-> (records in the buffer, records dropped since the log was switched on); synchronises the gym's stream"""
+        count, dropped = _U(), _U()
+        self._ck(self._lib.mv_episode_log_count(self._g, C.byref(count), C.byref(dropped)))
+        return int(count.value), int(dropped.value)
+
+    def drain_episode_log(self, max_records=None):
+        """the oldest max_records (default: all) records as a numpy array of EPISODE_RECORD_DTYPE, removed from the device buffer; synchronises the gym's
+        stream.  self.episode_log_dropped: the records lost to a full buffer since the log was switched on."""
+        if max_records is None:
+            max_records = self.episode_log_capacity()
+        out = np.zeros(max(int(max_records), 0), EPISODE_RECORD_DTYPE)
+        dropped = _U()
+        n = self._ck(self._lib.mv_drain_episode_log(self._g, out.ctypes.data if out.size else None, out.size, C.byref(dropped)))
+        self.episode_log_dropped = int(dropped.value)
+        return out[:n]
+
+    def ticks_since_reset(self):
+        return int(self._lib.mv_ticks_since_reset(self._g))
+
+    def episode_returns_device_ptr(self):
+        return int(self._lib.mv_episode_returns_device_ptr(self._g) or 0)
+
+    def episode_lengths_device_ptr(self):
+        return int(self._lib.mv_episode_lengths_device_ptr(self._g) or 0)
+
+    def episode_log_records_device_ptr(self):
+        return int(self._lib.mv_episode_log_records_device_ptr(self._g) or 0)
+
+    def episode_log_count_device_ptr(self):
+        return int(self._lib.mv_episode_log_count_device_ptr(self._g) or 0)
+
+    def episode_returns_tensor(self):
+        """float64 CUDA tensor [num_envs * num_agents_per_env]: the running returns, a view of the gym's memory (valid in the order of the gym's stream,
+        until set_episode_log / close)"""
+        import torch
+        if not self.episode_returns_device_ptr():
+            raise RuntimeError("the episode log is off (set_episode_log)")
+        return torch.as_tensor(_DeviceArray(self.episode_returns_device_ptr(), (self.num_envs * self.num_agents_per_env,), "<f8"), device=f"cuda:{self.device}")
+
+    def episode_lengths_tensor(self):
+        """int32 CUDA tensor [num_envs]: the running episode lengths in ticks (a view, like episode_returns_tensor)"""
+        import torch
+        if not self.episode_lengths_device_ptr():
+            raise RuntimeError("the episode log is off (set_episode_log)")
+        return torch.as_tensor(_DeviceArray(self.episode_lengths_device_ptr(), (self.num_envs,), "<i4"), device=f"cuda:{self.device}")
 
     def render(self):
         self._ck(self._lib.mv_render(self._g))

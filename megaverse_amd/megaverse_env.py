@@ -52,7 +52,7 @@ def make_env_multitask(multitask_name, task_idx, num_envs, num_agents_per_env, n
 
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
-                 img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba"):
+                 img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0):
         if obs_layout not in ("rgba", "chw"):
             raise ValueError("obs_layout must be 'rgba' (frames written as (H, W, 4) RGBA, handed out as a permuted view) or 'chw' (written as (3, H, W))")
         scenario_name = scenario_name.casefold()
@@ -80,6 +80,11 @@ class MegaverseEnv:
                                 use_vulkan, float_params, device=device, env_offset=env_offset, total_envs=total_envs)
         if obs_layout == "chw":
             self.env.set_obs_layout("chw")
+        # episode_log = capacity > 0: returns, lengths and true objectives of finished episodes are collected on the device (mv_set_episode_log) and read
+        # with self.env.drain_episode_log() -- what the fast paths (step_device, env.step_n) otherwise leave to the caller
+        self.episode_log = int(episode_log)
+        if self.episode_log > 0:
+            self.env.set_episode_log(self.episode_log)
         self.default_shaping_scheme = self.env.get_reward_shaping(0, 0)
         self.action_space = self.generate_action_space(self.env.action_space_sizes())
         self.observation_space = spaces.Box(0, 255, (self.channels, self.img_h, self.img_w), dtype=np.uint8)

@@ -17,7 +17,10 @@ import os
 
 import numpy as np
 
-from .extension import GymGroup, MegaverseGym
+from .extension import EPISODE_RECORD_DTYPE, GymGroup, MegaverseGym
+
+# MultiTaskGym.drain_episode_log: a sub-gym's record (extension.EPISODE_RECORD_DTYPE) + the task it came from; agent in the batch's numbering
+MULTITASK_EPISODE_DTYPE = np.dtype([("task", "<i4")] + [(n, EPISODE_RECORD_DTYPE.fields[n][0]) for n in EPISODE_RECORD_DTYPE.names])
 
 # megaverse_env.py:18-21 of the reference: the eight scenarios of its multi-task benchmark, all available on the HIP path
 # (Sokoban reads Boxoban level files: $BOXOBAN_LEVELS, as in the reference)
@@ -124,6 +127,38 @@ class MultiTaskGym:
     def set_pixel_mode(self, mode):
         for g in self.gyms:
             g.set_pixel_mode(mode)
+
+    # ---- episode log (include/megaverse_hip.h: mv_set_episode_log): every sub-gym keeps its own
+    def set_episode_log(self, capacity):
+        """`capacity` records per scenario (0: off)"""
+        for g in self.gyms:
+            g.set_episode_log(capacity)
+
+    def flush_episode_log(self):
+        for g in self.gyms:
+            g.flush_episode_log()
+
+    def episode_log_count(self):
+        """-> (records waiting, records dropped), summed over the scenarios"""
+        counts = [g.episode_log_count() for g in self.gyms]
+        return sum(c for c, _ in counts), sum(d for _, d in counts)
+
+    def drain_episode_log(self):
+        """every sub-gym's records as ONE array of MULTITASK_EPISODE_DTYPE: `task` is the sub-gym, `agent` is global_env * A + a with the batch's env
+        numbering (the inverse of locate: local env j of task k is global env j * S + k), sorted by (end_tick, agent).  end_tick counts each
+        sub-gym's own ticks since its reset -- the same for all of them when they are reset and stepped together."""
+        S, A = len(self.gyms), self.num_agents_per_env
+        parts = []
+        for k, g in enumerate(self.gyms):
+            r = g.drain_episode_log()
+            out = np.zeros(r.size, MULTITASK_EPISODE_DTYPE)
+            for n in EPISODE_RECORD_DTYPE.names:
+                out[n] = r[n]
+            out["task"] = k
+            out["agent"] = ((r["agent"] // A) * S + k) * A + r["agent"] % A
+            parts.append(out)
+        allr = np.concatenate(parts) if parts else np.zeros(0, MULTITASK_EPISODE_DTYPE)
+        return allr[np.lexsort((allr["agent"], allr["end_tick"]))]
 
     def locate(self, env_idx):
         """global env index -> (sub-gym, local env index)"""

@@ -163,6 +163,25 @@ public:
         check(mv_set_obs_layout(gym_, layout == "chw" ? MV_OBS_RGB_PLANAR : MV_OBS_RGBA));
     }
     std::string obs_layout() const { return mv_get_obs_layout(gym_) == MV_OBS_RGB_PLANAR ? "chw" : "rgba"; }
+    // the episode log (mv_set_episode_log): returns / lengths summed on the device, one record per agent of a finished env
+    void set_episode_log(int capacity) { check(mv_set_episode_log(gym_, capacity)); }
+    void flush_episode_log() { check(mv_flush_episode_log(gym_)); }
+    py::tuple episode_log_count()
+    {
+        uint32_t count = 0, dropped = 0;
+        check(mv_episode_log_count(gym_, &count, &dropped));
+        return py::make_tuple(count, dropped);
+    }
+    py::array_t<mv_episode_record> drain_episode_log()
+    {   // every record waiting, as a structured array (fields agent, length, end_tick, true_objective, ret)
+        uint32_t count = 0, dropped = 0;
+        check(mv_episode_log_count(gym_, &count, &dropped));
+        py::array_t<mv_episode_record> out(count);
+        if (count) check(mv_drain_episode_log(gym_, out.mutable_data(), (int32_t)count, &dropped));
+        return out;
+    }
+    std::uintptr_t episode_returns_device_ptr() const { return reinterpret_cast<std::uintptr_t>(mv_episode_returns_device_ptr(gym_)); }
+    std::uintptr_t episode_lengths_device_ptr() const { return reinterpret_cast<std::uintptr_t>(mv_episode_lengths_device_ptr(gym_)); }
 
 private:
     mv_gym *gym_ = nullptr;
@@ -175,6 +194,7 @@ int visible_device_count() { return mv_device_count(); }
 
 PYBIND11_MODULE(megaverse, m)
 {
+    PYBIND11_NUMPY_DTYPE(mv_episode_record, agent, length, end_tick, true_objective, ret);
     m.doc() = "Megaverse Python bindings (MI355X HIP back end)";
     m.def("set_megaverse_log_level", [](int level) { g_log_level = level; }, "accepted for API parity: the HIP library does not log");
     py::class_<Gym>(m, "MegaverseGym")
@@ -200,5 +220,11 @@ PYBIND11_MODULE(megaverse, m)
         .def("get_dones", &Gym::get_dones)
         .def("obs_device_ptr", &Gym::obs_device_ptr)
         .def("set_obs_layout", &Gym::set_obs_layout)
-        .def("obs_layout", &Gym::obs_layout);
+        .def("obs_layout", &Gym::obs_layout)
+        .def("set_episode_log", &Gym::set_episode_log)
+        .def("flush_episode_log", &Gym::flush_episode_log)
+        .def("episode_log_count", &Gym::episode_log_count)
+        .def("drain_episode_log", &Gym::drain_episode_log)
+        .def("episode_returns_device_ptr", &Gym::episode_returns_device_ptr)
+        .def("episode_lengths_device_ptr", &Gym::episode_lengths_device_ptr);
 }

@@ -118,6 +118,41 @@ class Wrapper:
         self._finish_episodes(rewards, dones, infos)
         return obs, rewards, dones, np.zeros_like(dones), infos
 
+    def step_device(self, actions=None):
+        """The gymnasium 5-tuple with device tensors and no host read: (obs uint8 (num_agents, 3, H, W), rewards float32 [num_agents], terminated uint8
+        [num_agents], truncated uint8 [num_agents] (zeros), infos = [] ), all CUDA, valid in the order of the env's stream until the next step
+        (MegaverseEnv.step_device).  The episode bookkeeping step() / step_batched() do on the host runs on the device instead (the env's episode log,
+        switched on here with room for 64 episodes per agent unless the env was made with episode_log=capacity): collect it with drain_episode_stats()."""
+        env = self.env
+        if env.env.episode_log_capacity() <= 0:
+            env.episode_log = 64 * self.num_agents
+            env.env.set_episode_log(env.episode_log)
+        obs, rewards, dones_env = env.step_device(actions)
+        terminated = dones_env.repeat_interleave(env.num_agents_per_env)
+        return obs, rewards, terminated, terminated.new_zeros(terminated.shape), []
+
+    def drain_episode_stats(self):
+        """The episodes that finished since the last drain (steps taken through step_device, or env.env.step_n): one dict per finished agent, in (end_tick,
+        agent) order, with exactly the keys _finish_episodes fills -- `true_objective`, `episode_extra_stats` with `z_<scenario>_true_objective`,
+        `z_<scenario>_reward` (the same float64 sum, bit for bit) and `z_approx_total_training_steps` -- plus `agent`, `length` (ticks) and `end_tick`
+        (ticks since the reset).  One host synchronisation per drain instead of one per step.  With increase_team_spirit the annealing is applied here, at
+        drain time: later than the reference (which anneals on the step that finishes the episode) by at most one drain interval, and
+        z_approx_total_training_steps is the value at drain time."""
+        records = self.env.env.drain_episode_log()
+        scenario = self.env.scenario_name.casefold()
+        steps_so_far = self.training_info.get("approx_total_training_steps", 0)
+        team_spirit = min(steps_so_far / self.max_team_spirit_steps, 1.0) if self.increase_team_spirit else None
+        out = []
+        for agent, length, end_tick, true_objective, ret in records.tolist():
+            stats = {f"z_{scenario}_true_objective": true_objective, f"z_{scenario}_reward": ret, "z_approx_total_training_steps": steps_so_far}
+            if team_spirit is not None:
+                shaping = self.get_current_reward_shaping(agent)
+                shaping["teamSpirit"] = team_spirit
+                self.set_reward_shaping(shaping, agent)
+                stats["teamSpirit"] = team_spirit
+            out.append({"true_objective": true_objective, "episode_extra_stats": stats, "agent": agent, "length": length, "end_tick": end_tick})
+        return out
+
     def render(self, *args, **kwargs):
         return self.env.render(*args, **kwargs)
 
