@@ -79,8 +79,23 @@ int mv_sample_random_actions(mv_gym *g, uint32_t seed, uint32_t step_index);
 /* which generator mv_sample_random_actions / mv_step_n draw from: MV_POLICY_MULTIDISCRETE (default; = action_space.sample(),
  * megaverse_env.py:110-112) or MV_POLICY_SINGLE_BIT = Action(1 << randRange(0, NumActions)), the reference's own benchmark policy
  * (src/apps/megaverse_test_app.cpp:140-147); host twins: megaverse_amd/rollout.py */
-enum { MV_POLICY_NONE = 0, MV_POLICY_MULTIDISCRETE = 1, MV_POLICY_SINGLE_BIT = 2 };
+enum { MV_POLICY_NONE = 0, MV_POLICY_MULTIDISCRETE = 1, MV_POLICY_SINGLE_BIT = 2,
+       MV_POLICY_SEQUENCE = 3 };   /* mv_step_n / mv_group_step only: replay the action ring, mv_set_action_ring */
 int mv_set_sample_policy(mv_gym *g, int32_t policy);
+/* Action rings (no reference counterpart: its callers set every agent's action every tick, megaverse.cpp:100-116): the one INPUT of a batched call, as
+ * mv_set_output_ring holds its outputs.  device_actions: [count][N*A][6] int32 multi-discrete actions in device memory, encoding and agent order as for
+ * mv_set_actions_device; count = 0 detaches.  Nothing is launched and nothing is copied: the step kernels of a call with policy MV_POLICY_SEQUENCE read the
+ * caller's buffer -- tick j of mv_step_n / mv_group_step(k, MV_POLICY_SEQUENCE, seed, first_step_index) acts on entry (first_step_index + j) % count, in
+ * uint32 arithmetic (the stateless indexing the random policies use for (seed, first_step_index + j); seed is ignored; count = 1 is action repeat).  Such a
+ * call takes every batched launch path the random policies take, under the same conditions, and falls back to tick-by-tick launches where they do; a
+ * pending mv_set_actions* buffer is superseded for its ticks, as the random policies supersede it.  Without a ring (in a group: on every member, each
+ * keeps its own) the call is an error.  mv_step, mv_step_many, MV_POLICY_NONE and the random policies ignore the ring; mv_set_sample_policy does not accept
+ * MV_POLICY_SEQUENCE.
+ * Ordering: this call is the one ordering point.  Whatever the caller enqueued on the gym's stream before it -- the kernel that filled the ring -- is ordered
+ * before the next step launch; the calls after that one pipeline freely (replaying a static script costs no dependency).  A caller that rewrites entries
+ * calls mv_set_action_ring again with the same arguments.  An entry a call reads must stay unchanged until the caller's stream has passed the end of that
+ * call.  The buffer is the caller's; mv_reset leaves the ring attached. */
+int mv_set_action_ring(mv_gym *g, int32_t count, const int32_t *device_actions);
 /* step several gyms of one job with one call (no reference counterpart: its multi-task runs are separate processes,
  * the scripts under megaverse_rl/runs): for each gym, optionally mv_sample_random_actions(seed, step_index), then mv_step / mv_step_no_render */
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index);
@@ -249,6 +264,9 @@ int mv_profile_end(mv_gym *g, float *avg_ms4, int32_t *counts4);
 /* test hooks: packed state snapshot of one env (layout in DESIGN.md, same bytes as the oracle's
  * mvo_snapshot) and the raw device RNG streams */
 int mv_debug_set_agent_pos(mv_gym *g, int32_t env_idx, int32_t agent_idx, float x, float y, float z); /* teleport (fall-detection tests) */
+/* out[0] / out[1]: the step launches / observation launches (one per launcher call: a batched pass is one, an exact-mode pass with its frame sort is one) that
+ * stepping calls have enqueued for this gym so far; for a member of a group: the group's.  Tells the batched paths from the tick-by-tick ones, whose bytes are the same. */
+int mv_debug_launch_counts(mv_gym *g, int64_t out[2]);
 /* scripted single-step physics cases (tests/test_canonical_poses*.py): the yaw basis from (cos, sin) as DefaultKinematicAgent's spawn builds it
  * (agent.cpp:42-46), and the controller's velocities */
 int mv_debug_set_agent_yaw(mv_gym *g, int32_t env_idx, int32_t agent_idx, float c, float s);

@@ -1139,6 +1139,19 @@ int mv_set_actions_device(mv_gym *g, const int32_t *device_actions)
     return 0;
 }
 
+int mv_set_action_ring(mv_gym *g, int32_t count, const int32_t *device_actions)
+{
+    if (check(g)) return -1;
+    if (count < 0 || (count > 0 && !device_actions)) return fail("mv_set_action_ring: count >= 0 and, with count > 0, a device pointer required");
+    // No launch, no copy: the step kernels of MV_POLICY_SEQUENCE calls read the caller's buffer (mv_actions.h: action_of through GymView::md_actions).  This
+    // call is the ordering point: what the caller's stream holds now -- the kernel that filled the ring -- comes before the next step launch; calls after
+    // that one pipeline as with the random policies (a static script is no dependency on the caller's stream).
+    g->actRing = count ? device_actions : nullptr;
+    g->actRingCount = count;
+    g->simMustWaitUser = true;
+    return 0;
+}
+
 int mv_set_sample_policy(mv_gym *g, int32_t policy)
 {
     if (check(g)) return -1;

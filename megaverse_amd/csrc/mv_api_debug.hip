@@ -69,6 +69,15 @@ struct Snap {
 };
 #pragma pack(pop)
 
+int mv_debug_launch_counts(mv_gym *g, int64_t out[2])
+{
+    if (check(g)) return -1;
+    if (!out) return fail("mv_debug_launch_counts: null pointer");
+    const mv_gym *c = g->inGroup && !g->inGroup->gyms.empty() ? g->inGroup->gyms[0] : g;   // (a group's launches are counted on its leader)
+    out[0] = c->launchCount[0]; out[1] = c->launchCount[1];
+    return 0;
+}
+
 int mv_debug_set_agent_pos(mv_gym *g, int32_t env, int32_t agent, float x, float y, float z)
 {
     if (check(g)) return -1;

@@ -110,6 +110,11 @@ struct mv_gym {
     std::vector<GymView> gvp;                    // [slots] gv with the buffers of each slot swapped in
     GymView gv{};
     const int32_t *mdActions = nullptr;          // mv_set_actions_device: the caller's multi-discrete buffer, read by the next step kernel
+    // mv_set_action_ring: the caller's [actRingCount][N*A][6] multi-discrete actions; an MV_POLICY_SEQUENCE call reads entry (first_step_index + j) % count in tick j
+    const int32_t *actRing = nullptr;
+    int actRingCount = 0;
+    // mv_debug_launch_counts: step launches and observation launches the stepping calls have enqueued (kept on the leader of a group)
+    long long launchCount[2] = {0, 0};
     // mv_set_pass_overlap(1), ring at least two calls deep: the one-launch observation passes of consecutive batched calls go to two internal streams
     // in turn, so that the passes of call c + 1 start -- their step launch permitting -- while those of call c drain (a launch ends with its last
     // workgroups finishing alone, and the next one could not begin before: ~7 % of a 1024-env call).  The caller's stream waits for every call's

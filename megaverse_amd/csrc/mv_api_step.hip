@@ -9,7 +9,8 @@ extern "C" {
 // n > 1: an mv_group, stepped by union launches).  gs[0] is the leader: the stream state that changes with every call -- marks, which stream
 // the last step ran on -- is kept on it and mirrored to the others.  policy != POLICY_NONE: tick j draws its actions inside the step kernel
 // from (seed, first_index + j); POLICY_NONE: the first tick acts on what mv_set_actions* left, the following ones on cleared actions
-// (env.cpp:141-142 clears them after every tick).
+// (env.cpp:141-142 clears them after every tick).  POLICY_SEQUENCE: tick j acts on entry (first_index + j) % count of every gym's action ring
+// (mv_set_action_ring) -- to the kernels a POLICY_NONE tick with a multi-discrete pointer of its own, so every launch path the random policies open is open.
 // kCall: the ticks of the CALLER's call this chunk belongs to (mv_step_n splits a call of more than `batch` ticks): what the ring contract of
 // the overlapped passes is stated in (include/megaverse_hip.h).
 static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, uint32_t seed, uint32_t first_index, int kCall)
@@ -26,6 +27,9 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
         allFast = allFast && g->fastPixels != 0;
         anyHostEpisodes = anyHostEpisodes || g->hostEpisodes();
         anyLog = anyLog || g->logCapacity > 0;
+        if (policy == POLICY_SEQUENCE && (!g->actRing || g->actRingCount < 1))
+            return fail(n > 1 ? "mv_group_step: MV_POLICY_SEQUENCE: gym " + std::to_string(i) + " of the group has no action ring (mv_set_action_ring)"
+                              : std::string("mv_step_n: MV_POLICY_SEQUENCE: the gym has no action ring (mv_set_action_ring)"));
     }
     if (k < 1 || k > batch) return fail("mv_step_n: 1 <= k <= " + std::to_string(batch) + " (MV_PIPE_BATCH) required");
     HIP_TRY(hipSetDevice(L->device));
@@ -135,7 +139,8 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
         int envs = 0;
         for (int i = 0; i < n; ++i) {
             mv_gym *g = gs[i];
-            if (policy != POLICY_NONE) { g->gv.sample_on = policy; g->gv.sample_seed = seed; g->gv.sample_step = first_index + (uint32_t)j; }
+            if (policy == POLICY_SEQUENCE) g->gv.sample_on = POLICY_NONE;
+            else if (policy != POLICY_NONE) { g->gv.sample_on = policy; g->gv.sample_seed = seed; g->gv.sample_step = first_index + (uint32_t)j; }
             else { g->gv.sample_on = (j == 0 && g->samplePending) ? g->samplePolicy : (int)POLICY_NONE; }
             g->parity = g->group * g->batch + j;
             // (this pass's frame setup fills the next cost histogram; one launch per tick: and clears the one after)
@@ -144,7 +149,9 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
             o = outputs_of(g, g->ringTick++);
             GymView &v = views[(size_t)j * n + i];
             v = view(g, g->parity, staged ? nullptr : &o);
-            if (j == 0 && g->gv.sample_on == POLICY_NONE) v.md_actions = g->mdActions;
+            if (policy == POLICY_SEQUENCE)
+                v.md_actions = g->actRing + (size_t)action_ring_entry(first_index, j, (uint32_t)g->actRingCount) * ((size_t)g->N * g->A * 6);
+            else if (j == 0 && g->gv.sample_on == POLICY_NONE) v.md_actions = g->mdActions;
             if (groupBatch) v.lpt_no_clear = 1;   // (the passes clear their histograms themselves: mv_raster.hip, hist_done)
             if (n > 1) { ua.first[i] = envs; ua.gv[i] = v; envs += g->N; }
         }
@@ -166,6 +173,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
                     const GymView *vw = views.data() + j0;
                     hipEvent_t r = j0 + kk == k ? rides : nullptr;
                     launch_step_ticks(vw, kk, sim, L->w, L->h, r);
+                    ++L->launchCount[0];
                 }
                 if (callEv) HIP_TRY(hipEventRecord(callEv[1], sim));
                 simDoneRides = rides != nullptr;
@@ -173,6 +181,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
         } else if (n == 1) {
             hipEvent_t rides = j == k - 1 && !evs[j] ? (own ? L->simDone : sideWaits ? L->stepDone : nullptr) : nullptr;
             const bool rode = launch_step(views[(size_t)j * n], sim, L->w, L->h, fused, rides);
+            ++L->launchCount[0];
             simDoneRides = rode && own;
             stepDoneRodeAlong = rode && !own;
         }
@@ -180,19 +189,29 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
             if (j == k - 1) {   // every tick's views are collected: one launch for the k ticks of all n gyms
                 UnionTicksArgs ta;
                 ta.n = n; ta.k = k;
+                ta.act_first = first_index;
                 for (int i = 0; i < n; ++i) {
                     ta.first[i] = ua.first[i];
                     ta.gv[i] = views[(size_t)i];   // tick 0's
                     ta.slot_stride[i] = (int64_t)((const uint8_t *)views[(size_t)n + i].vis_prims - (const uint8_t *)views[(size_t)i].vis_prims);
+                    const bool seq = policy == POLICY_SEQUENCE;   // (the kernel derives tick j's entry itself: it holds tick 0's view only)
+                    ta.act_base[i] = seq ? gs[i]->actRing : nullptr;
+                    ta.act_count[i] = seq ? (uint32_t)gs[i]->actRingCount : 0u;
+                    ta.act_stride[i] = gs[i]->N * gs[i]->A * 6;
                 }
                 for (int i = n; i <= MAX_UNION; ++i) ta.first[i] = envs;
-                for (int i = n; i < MAX_UNION; ++i) { ta.gv[i] = views[0]; ta.slot_stride[i] = 0; }
+                for (int i = n; i < MAX_UNION; ++i) {
+                    ta.gv[i] = views[0]; ta.slot_stride[i] = 0;
+                    ta.act_base[i] = nullptr; ta.act_count[i] = 0; ta.act_stride[i] = 0;
+                }
                 launch_step_union_ticks(ta, sim, L->w, L->h, own ? L->simDone : nullptr);
+                ++L->launchCount[0];
                 simDoneRides = own;
             }
         } else {
             for (int i = n; i <= MAX_UNION; ++i) ua.first[i] = envs;
             launch_step_union(ua, sim, L->w, L->h, fused);
+            ++L->launchCount[0];
         }
         if (evs[j]) HIP_TRY(hipEventRecord(evs[j][1], sim));
         simDoneRodeAlong = simDoneRodeAlong || simDoneRides;
@@ -281,6 +300,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
                 if (callEv) { HIP_TRY(hipEventRecord(callEv[2], L->stream)); HIP_TRY(hipEventRecord(callEv[3], L->stream)); }
                 int r = cn >= 2 ? launch_raster_batch(&views[(size_t)chunkFirst], chunkObs.data(), pubInRaster ? chunkPubs.data()
                                                       : nullptr, cn, L->w, L->h, overlap && cn == k ? passOn : L->stream, mark) : 1;
+                if (r == 0) ++L->launchCount[1];
                 if (r == 0 && overlap && cn == k) HIP_TRY(hipStreamWaitEvent(L->stream, mark, 0));   // the caller's stream sees the call's outputs as always
                 if (r < 0) return fail("mv_step: observation size above 1024x1024");
                 if (r == 0)   // (every pass of the one-launch kernel leaves its cost histogram zero)
@@ -292,6 +312,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
                             nullptr, 1, /*setup_done=*/1, pubInRaster ? &chunkPubs[q] : nullptr,
                                           q == cn - 1 ? mark : nullptr))
                             return fail("mv_step: observation size above 1024x1024");
+                        ++L->launchCount[1];
                         // (self_clear, mv_raster.hip)
                         if (views[(size_t)chunkFirst + q].lpt_no_clear) L->histClean[(size_t)views[(size_t)chunkFirst + q].lpt_parity] = 1;
                     }
@@ -310,6 +331,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
                 const int r = launch_raster_union_batch(views.data(), allObs.data(), allPubs.data(), k, n, L->w, L->h, L->stream, mark);
                 if (r != 0) return fail(r == -2 ? "mv_group_step: the hand-over slots of a batched call are not one slot apart (internal)"
                     : "mv_group_step: observation size above 1024x1024");
+                ++L->launchCount[1];
                 // (every pass leaves its cost histogram zero)
                 for (size_t q = 0; q < (size_t)n * k; ++q) gs[q % (size_t)n]->histClean[(size_t)views[q].lpt_parity] = 1;
             }
@@ -319,12 +341,14 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
                 if (launch_raster_union(&views[(size_t)j * n], obsPtrs.data(), pubInRaster ? pubs.data() : nullptr,
                     n, L->w, L->h, L->stream, evs[j] ? evs[j][3] : nullptr, mark))
                     return fail("mv_step: observation size above 1024x1024");
+                ++L->launchCount[1];
             } else {
                 for (int i = 0; i < n; ++i) {
                     const GymView &v = views[(size_t)j * n + i];
                     if (launch_raster(v, obsPtrs[i], L->w, L->h, L->stream, evs[j] && i == 0 ? evs[j][3] : nullptr, gs[i]->fastPixels, /*setup_done=*/1,
                                       pubInRaster ? &pubs[i] : nullptr, i == n - 1 ? mark : nullptr))
                         return fail("mv_step: observation size above 1024x1024");
+                    ++L->launchCount[1];
                     if (v.lpt_no_clear && gs[i]->fastPixels) gs[i]->histClean[(size_t)v.lpt_parity] = 1;   // (self_clear, mv_raster.hip)
                 }
             }
@@ -368,7 +392,7 @@ int mv_step_no_render(mv_gym *g) { return step_impl(g, false, 1, POLICY_NONE, 0,
 int mv_step_n(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32_t first_step_index)
 {
     if (check(g)) return -1;
-    if (policy != MV_POLICY_NONE && policy != MV_POLICY_MULTIDISCRETE && policy != MV_POLICY_SINGLE_BIT) return fail("mv_step_n: unknown policy");
+    if (policy < MV_POLICY_NONE || policy > MV_POLICY_SEQUENCE) return fail("mv_step_n: unknown policy");
     if (k < 1) return fail("mv_step_n: k >= 1 required");
     int rc = 0;
     // Episodes that can end within a few ticks (statusPeriod 1: the refill protocol looks at the consumed counts after every tick) are
@@ -472,7 +496,7 @@ int mv_group_destroy(mv_group *grp)
 int mv_group_step(mv_group *grp, int32_t k, int32_t render, int32_t policy, uint32_t seed, uint32_t first_step_index)
 {
     if (!grp || grp->gyms.empty()) return fail("mv_group_step: the group is gone (a member was closed)");
-    if (policy != MV_POLICY_NONE && policy != MV_POLICY_MULTIDISCRETE && policy != MV_POLICY_SINGLE_BIT) return fail("mv_group_step: unknown policy");
+    if (policy < MV_POLICY_NONE || policy > MV_POLICY_SEQUENCE) return fail("mv_group_step: unknown policy");
     if (k < 1) return fail("mv_group_step: k >= 1 required");
     // A call's chunks: what every member's slot groups hold, and at most MAX_GROUP_TICKS -- the two-launch batched path's limit
     // (raster_union_batch_applicable): a chunk

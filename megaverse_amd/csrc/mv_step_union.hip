@@ -83,7 +83,9 @@ __global__ __launch_bounds__(64 * WAVES, MV_UNION_TICKS_WAVES_PER_SIMD) void ste
     const bool wide = WAVES > 1 && ua.gv[s].vis_stride > VIS_SMALL;   // (uniform over the workgroup)
     if (!wide && wave > 0) return;
     for (int j = 0; j < ua.k; ++j) {
-        const GymView gv = tick_view(ua.gv[s], ua.slot_stride[s], j);
+        GymView gv = tick_view(ua.gv[s], ua.slot_stride[s], j);
+        if (ua.act_count[s])   // (uniform: an action ring is replayed, this tick's entry)
+            gv.md_actions = ua.act_base[s] + (size_t)action_ring_entry(ua.act_first, j, ua.act_count[s]) * (size_t)ua.act_stride[s];
         if (wave == 0) tick_any<1>(gv, env);
         if (wide) {
             __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
@@ -112,6 +114,8 @@ void launch_step_union_ticks(const UnionTicksArgs &ua0, hipStream_t stream, int 
             for (int i = 0; i < ua0.n; ++i)
                 if ((ua0.gv[i].vis_stride > VIS_SMALL) == (pass == (longFirst == 2 ? 1 : 0))) {
                     ua.gv[m] = ua0.gv[i]; ua.slot_stride[m] = ua0.slot_stride[i]; ua.first[m] = envs;
+                    // (a gym's action ring moves with it)
+                    ua.act_base[m] = ua0.act_base[i]; ua.act_count[m] = ua0.act_count[i]; ua.act_stride[m] = ua0.act_stride[i];
                     envs += ua0.first[i + 1] - ua0.first[i];
                     ++m;
                 }

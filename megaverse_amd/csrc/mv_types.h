@@ -30,7 +30,11 @@ enum : int { FRAME_HDR_BYTES = 1024 };
 // one more than there are slots (a pass clears the next; GymView::lpt_hists).
 enum : int { PIPE_GROUPS = 3, PIPE_BATCH_MAX = 16 };
 // where a tick's actions come from (GymView::sample_on): the action array, or drawn inside the step kernel (mv_actions.h)
-enum : int { POLICY_NONE = 0, POLICY_MULTIDISCRETE = 1, POLICY_SINGLE_BIT = 2 };
+// POLICY_SEQUENCE is the host's (mv_api_step.hip): tick j reads entry (first + j) % count of the gym's action ring through md_actions; a kernel sees POLICY_NONE
+enum : int { POLICY_NONE = 0, POLICY_MULTIDISCRETE = 1, POLICY_SINGLE_BIT = 2, POLICY_SEQUENCE = 3 };
+// the action-ring entry tick j of a call that starts at `first` acts on (include/megaverse_hip.h: mv_set_action_ring): stateless, in uint32 like the
+// random policies' step index
+__host__ __device__ inline uint32_t action_ring_entry(uint32_t first, int j, uint32_t count) { return (first + (uint32_t)j) % count; }
 
 // error flags a kernel raises in episode_status[N + 1]; mv_step reports them (mv_api.hip: check_status_flags)
 enum : int { ST_STARVED = 1, ST_CANDIDATES = 2, ST_VISIBLE = 4, ST_CHUNK = 8 };

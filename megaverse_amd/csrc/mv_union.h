@@ -21,10 +21,16 @@ static_assert(sizeof(UnionStepArgs) + 16 <= 4096, "UnionStepArgs + (W, H, render
 // hand-over slot -- ten buffers, all `slot_stride` bytes further per tick (mv_api.hip carves a gym's slots out of its arena one after the other) --, its
 // action index and its cost histogram (consecutive, modulo their number): derived in the kernel (mv_types.h: tick_view), not passed (k x n views do not fit the
 // 4 KB of kernel arguments).
+// A call that replays an action ring (MV_POLICY_SEQUENCE): tick j of gym s reads its multi-discrete actions at act_base[s] + entry * act_stride[s] int32s,
+// entry = (act_first + j) % act_count[s] (mv_types.h: action_ring_entry); act_count[s] = 0: the gym's actions are tick 0's view's, as for every other call.
 struct UnionTicksArgs {
     int32_t n, k;
     int32_t first[MAX_UNION + 1];
+    uint32_t act_first;
     int64_t slot_stride[MAX_UNION];
+    const int32_t *act_base[MAX_UNION];
+    uint32_t act_count[MAX_UNION];
+    int32_t act_stride[MAX_UNION];
     GymView gv[MAX_UNION];
 };
 static_assert(sizeof(UnionTicksArgs) + 16 <= 4096, "UnionTicksArgs + (W, H) must fit the 4 KB kernel-argument segment");

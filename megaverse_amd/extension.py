@@ -40,6 +40,7 @@ SYMBOLS = [
     ("mv_group_create", C.c_int, [_P, _I, C.POINTER(_P)]), ("mv_group_step", C.c_int, [_P, _I, _I, _I, _U, _U]), ("mv_group_destroy", C.c_int, [_P]),
     ("mv_step", C.c_int, [_P]), ("mv_step_no_render", C.c_int, [_P]), ("mv_render", C.c_int, [_P]),
     ("mv_step_n", C.c_int, [_P, _I, _I, _U, _U]), ("mv_set_sample_policy", C.c_int, [_P, _I]),
+    ("mv_set_action_ring", C.c_int, [_P, _I, _P]), ("mv_debug_launch_counts", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("mv_set_output_ring", C.c_int, [_P, _I, _P, _P, _P]),
     ("mv_set_pass_overlap", C.c_int, [_P, _I]),
     ("mv_recommended_ticks_per_call", C.c_int, [_P]), ("mv_recommended_pass_overlap", C.c_int, [_P]), ("mv_arena_bytes", C.c_int64, [_P]),
@@ -319,11 +320,24 @@ class MegaverseGym:
     def step_no_render(self):
         self._ckw(self._lib.mv_step_no_render(self._g))
 
-    POLICIES = {"none": 0, "multidiscrete": 1, "single-bit": 2}
+    POLICIES = {"none": 0, "multidiscrete": 1, "single-bit": 2, "sequence": 3}
 
     def step_n(self, k, policy="multidiscrete", seed=0, first_step_index=0):
-        """k open-loop ticks (each stepped and rendered) with one call; tick j draws its actions from (policy, seed, first_step_index + j)"""
+        """k open-loop ticks (each stepped and rendered) with one call; tick j draws its actions from (policy, seed, first_step_index + j) --
+        policy 'sequence': it acts on entry (first_step_index + j) % count of the action ring (set_action_ring), seed is ignored"""
         self._ckw(self._lib.mv_step_n(self._g, int(k), int(self.POLICIES.get(policy, policy)), int(seed) & 0xFFFFFFFF, int(first_step_index) & 0xFFFFFFFF))
+
+    def set_action_ring(self, count, device_ptr=0):
+        """int32 [count, num_agents, 6] multi-discrete actions in device memory for step_n(..., 'sequence') (include/megaverse_hip.h: mv_set_action_ring);
+        count = 0 detaches.  Nothing is launched or copied: the step kernels read the caller's buffer, which the caller keeps alive.  The call orders what
+        the gym's stream holds so far -- the kernel that filled the ring -- before the next step; after rewriting entries, call it again."""
+        self._ck(self._lib.mv_set_action_ring(self._g, int(count), _P(int(device_ptr) or None)))
+
+    def debug_launch_counts(self):
+        """-> (step launches, observation launches) the stepping calls have enqueued for this gym -- in a group: for the group -- so far (a test hook)"""
+        out = (C.c_int64 * 2)()
+        self._ck(self._lib.mv_debug_launch_counts(self._g, out))
+        return int(out[0]), int(out[1])
 
     def set_sample_policy(self, policy):
         """'multidiscrete' (action_space.sample()) or 'single-bit' (the reference's megaverse_test_app policy) for sample_random_actions"""

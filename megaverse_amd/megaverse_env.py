@@ -50,6 +50,22 @@ def make_env_multitask(multitask_name, task_idx, num_envs, num_agents_per_env, n
     return MegaverseEnv(scenario, num_envs, num_agents_per_env, num_simulation_threads, use_vulkan, params)
 
 
+def check_sequence_actions(actions, num_agents):
+    """MegaverseEnv.step_sequence's argument check (no device needed): [k >= 1, num_agents, 6] -- an integer numpy array, or a CUDA int32 tensor -> k"""
+    is_tensor = hasattr(actions, 'data_ptr')
+    if not is_tensor:
+        actions = np.asarray(actions)
+    shape = tuple(actions.shape)
+    if len(shape) != 3 or shape[0] < 1 or shape[1:] != (int(num_agents), 6):
+        raise ValueError(f'step_sequence: actions must be [k >= 1, num_agents = {int(num_agents)}, 6], got {shape}')
+    if is_tensor:
+        if str(actions.dtype) != 'torch.int32' or not actions.is_cuda:
+            raise ValueError(f'step_sequence: a tensor of actions must be int32 and on the device, got {actions.dtype} on {actions.device}')
+    elif actions.dtype.kind not in 'iu':
+        raise ValueError(f'step_sequence: actions must be integers, got {actions.dtype}')
+    return int(shape[0])
+
+
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
                  img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0):
@@ -91,6 +107,7 @@ class MegaverseEnv:
         self._obs_tensor = None
         self._host_obs = None
         self._dev_out = None
+        self._seq = None   # step_sequence: (k, obs ring, rewards ring, dones ring, actions) while its rings are attached
 
     @staticmethod
     def generate_action_space(action_space_sizes):
@@ -128,6 +145,7 @@ class MegaverseEnv:
         return self.observations()
 
     def step(self, actions):
+        self._leave_sequence()
         self.env.set_actions_batched(np.asarray(actions, dtype=np.int32).reshape(self.num_agents, -1))
         self.env.step()
         dones_env = self.env.get_dones().astype(bool)
@@ -154,6 +172,7 @@ class MegaverseEnv:
         torch = self._torch()
         if rgba and self.obs_layout == "chw":
             raise ValueError("observations_tensor(rgba=True): this env writes its frames as (3, H, W) planes (obs_layout='chw')")
+        self._leave_sequence()
         if self._obs_tensor is None:
             shape = (self.num_agents, 3, self.img_h, self.img_w) if self.obs_layout == "chw" else (self.num_agents, self.img_h, self.img_w, 4)
             self._obs_tensor = torch.empty(shape, dtype=torch.uint8, device=f'cuda:{self.device}')
@@ -171,6 +190,7 @@ class MegaverseEnv:
     def step_batched(self, actions=None):
         """actions: int32 [num_agents, 6] (numpy, or a CUDA torch tensor) or None (keep what was set).
         Returns (obs uint8 CUDA view (num_agents,3,H,W), rewards float32 np [num_agents], dones bool np [num_envs])."""
+        self._leave_sequence()
         if self._obs_tensor is None:
             self.observations_tensor()   # (allocates: before the action buffer is handed over, not between hand-over and step)
         held = None
@@ -197,6 +217,7 @@ class MegaverseEnv:
         torch = self._torch()
         if self._obs_tensor is None:
             self.observations_tensor()
+        self._leave_sequence()
         if self._dev_out is None:
             dev = self._obs_tensor.device
             self._dev_out = (torch.zeros(self.num_agents, dtype=torch.float32, device=dev), torch.zeros(self.num_envs, dtype=torch.uint8, device=dev))
@@ -211,6 +232,47 @@ class MegaverseEnv:
         self.env.step()
         del held
         return self._obs_view(), self._dev_out[0], self._dev_out[1]
+
+    def _leave_sequence(self):
+        """step_sequence's rings are attached: back to the single slab and arrays, the slab brought up to date"""
+        if self._seq is None:
+            return
+        self._seq = None
+        self._dev_out = None
+        self.env.set_output_ring(0)
+        self.env.set_action_ring(0)
+        self.env.render()
+
+    def step_sequence(self, actions):
+        """k ticks on GIVEN actions as batched calls (mv_set_action_ring + mv_step_n with MV_POLICY_SEQUENCE): replaying a recorded trajectory, a scripted
+        test, an open-loop plan, action repeat.  actions: [k, num_agents, 6] -- an integer numpy array, or an int32 CUDA tensor (read in place: unchanged until
+        the stream has passed this call).  -> (obs uint8 [k, num_agents, 3, H, W], rewards float32 [k, num_agents], dones uint8 [k, num_envs]): CUDA tensors,
+        entry j what tick j left, valid in the order of the gym's stream until the next stepping call (rings this env owns, as step_device's outputs).  k
+        may exceed what one call holds: it is stepped in chunks of recommended_ticks_per_call().  No host synchronisation."""
+        k = check_sequence_actions(actions, self.num_agents)
+        torch = self._torch()
+        dev = torch.device(f'cuda:{self.device}')
+        if hasattr(actions, 'data_ptr'):
+            held = actions.contiguous()
+        else:
+            held = torch.as_tensor(np.ascontiguousarray(actions, dtype=np.int32)).to(dev)
+        if self._seq is None or self._seq[0] != k:
+            if self._obs_tensor is None:
+                self.observations_tensor()   # (the env's own slab exists before the rings take its place)
+            frame = (3, self.img_h, self.img_w) if self.obs_layout == 'chw' else (self.img_h, self.img_w, 4)
+            rings = (torch.zeros((k, self.num_agents) + frame, dtype=torch.uint8, device=dev), torch.zeros((k, self.num_agents), dtype=torch.float32, device=dev),
+                     torch.zeros((k, self.num_envs), dtype=torch.uint8, device=dev))
+            self._dev_out = None   # (step_device attaches its own one-entry ring again)
+            self.env.set_output_ring(k, rings[0].data_ptr(), rings[1].data_ptr(), rings[2].data_ptr())   # tick j of a call -> entry j: every call is k ticks
+        else:
+            rings = self._seq[1:4]
+        self._seq = (k,) + tuple(rings) + (held,)   # (the actions stay alive until the next call replaces them)
+        self.env.set_action_ring(k, held.data_ptr())
+        chunk = max(1, self.env.recommended_ticks_per_call())
+        for done in range(0, k, chunk):
+            self.env.step_n(min(chunk, k - done), 'sequence', 0, done)
+        obs = rings[0] if self.obs_layout == 'chw' else rings[0][..., :3].permute(0, 1, 4, 2, 3)
+        return obs, rings[1], rings[2]
 
     # ---- rendering (megaverse_env.py:164-184): returns the tiled BGR image, shows it if cv2 exists ----
     def convert_obs(self, obs):

@@ -28,6 +28,26 @@ MEGAVERSE8 = ["TowerBuilding", "ObstaclesEasy", "ObstaclesHard", "Collect", "Sok
 MEGAVERSE_IN_SCOPE = MEGAVERSE8   # (older name)
 
 
+def split_action_ring(actions, num_scenarios, agents_per_env):
+    """[count, num_envs * A, 6] actions in the batch's global env numbering -> one [count, n_k * A, 6] array per sub-gym, by MultiTaskGym.locate's rule (global
+    env i is local env i // S of sub-gym i % S).  numpy arrays and torch tensors alike (views: the caller makes them contiguous)."""
+    S, A = int(num_scenarios), int(agents_per_env)
+    count = actions.shape[0]
+    per_task = actions.shape[1] // (S * A)
+    byenv = actions.reshape(count, per_task, S, A, 6)
+    return [byenv[:, :, k].reshape(count, per_task * A, 6) for k in range(S)]
+
+
+def check_action_ring(actions, num_envs, agents_per_env):
+    """MultiTaskGym.set_action_ring's argument check (no device needed): a [count >= 1, num_envs * A, 6] int32 numpy array or tensor -> count"""
+    shape = tuple(getattr(actions, "shape", ()))
+    if len(shape) != 3 or shape[0] < 1 or shape[1:] != (int(num_envs) * int(agents_per_env), 6):
+        raise ValueError(f"set_action_ring: actions must be [count >= 1, num_envs * agents_per_env = {int(num_envs) * int(agents_per_env)}, 6], got {shape}")
+    if str(actions.dtype).split(".")[-1] != "int32":
+        raise ValueError(f"set_action_ring: actions must be int32, got {actions.dtype}")
+    return int(shape[0])
+
+
 class MultiTaskGym:
     def __init__(self, scenarios, w, h, num_envs, num_agents_per_env, num_simulation_threads=4, float_params=None, device=0,
                  env_offset=0, total_envs=0, obs_layout="rgba"):
@@ -63,6 +83,7 @@ class MultiTaskGym:
         self._handles = None
         self._sample = None
         self.ring_obs = self.ring_rewards = self.ring_dones = None
+        self.action_rings = None
 
     # ---- plumbing: torch owns the slab and the streams
     def attach(self, torch_device):
@@ -116,6 +137,26 @@ class MultiTaskGym:
         for k, g in enumerate(self.gyms):
             g.set_output_ring(count, self.ring_obs[k].data_ptr(), self.ring_rewards[k].data_ptr(), self.ring_dones[k].data_ptr())
         return self.ring_obs, self.ring_rewards, self.ring_dones
+
+    def set_action_ring(self, actions):
+        """Action rings for step_n(..., policy='sequence') (mv_set_action_ring): `actions` is ONE int32 [count, num_envs * A, 6] array -- numpy, or a CUDA
+        tensor -- in the batch's global env numbering; every sub-gym gets its own contiguous [count, n_k * A, 6] part (locate's rule), kept alive in
+        ``action_rings``.  None detaches.  Call it again after changing the actions: the parts are copies."""
+        if actions is None:
+            for g in self.gyms:
+                g.set_action_ring(0)
+            self.action_rings = None
+            return None
+        count = check_action_ring(actions, self.num_envs, self.num_agents_per_env)
+        import torch
+        dev = self._obs.device if self._obs is not None else torch.device("cuda", self.gyms[0].device)
+        if not hasattr(actions, "data_ptr"):
+            actions = torch.as_tensor(np.ascontiguousarray(actions))
+        actions = actions.to(dev)
+        self.action_rings = [p.contiguous() for p in split_action_ring(actions, len(self.gyms), self.num_agents_per_env)]
+        for g, ring in zip(self.gyms, self.action_rings):   # (the copies run on torch's current stream: the gyms' stream, attach_tensor)
+            g.set_action_ring(count, ring.data_ptr())
+        return self.action_rings
 
     def recommended_ticks_per_call(self):
         """the k to ask step_n for: what every member recommends (mv_recommended_ticks_per_call), at most 8 -- the two-launch group call's limit"""
@@ -198,8 +239,12 @@ class MultiTaskGym:
         """k open-loop ticks of every scenario with one call (union launches; mv_group_step); without the union (MV_MULTITASK_UNION=0, or more
         scenarios than a group holds): k single steps of every sub-gym"""
         if not self.union:
+            if policy == "sequence":   # (every sub-gym replays its own ring)
+                for g in self.gyms:
+                    g.step_n(k, "sequence", 0, first_step_index)
+                return
             if policy != "multidiscrete":
-                raise ValueError("MultiTaskGym.step_n without union launches supports the 'multidiscrete' policy only")
+                raise ValueError("MultiTaskGym.step_n without union launches supports the 'multidiscrete' and 'sequence' policies only")
             for j in range(int(k)):
                 self.sample_random_actions(seed, int(first_step_index) + j)
                 self.step()

@@ -57,3 +57,9 @@ def action_masks(actions):
         masks[nz] |= (1 << (idx + a[..., i][nz])).astype(np.int32)
         idx += size - 1
     return masks
+
+
+def action_ring_entry(first_step_index, j, count):
+    """Host twin of the action ring's indexing (include/megaverse_hip.h: mv_set_action_ring; mv_types.h: action_ring_entry): tick j of
+    mv_step_n(k, MV_POLICY_SEQUENCE, seed, first_step_index) acts on this entry -- (first_step_index + j) % count, the sum taken in uint32."""
+    return ((int(first_step_index) + int(j)) & 0xFFFFFFFF) % int(count)
