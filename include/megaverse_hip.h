@@ -96,6 +96,30 @@ int mv_set_sample_policy(mv_gym *g, int32_t policy);
  * calls mv_set_action_ring again with the same arguments.  An entry a call reads must stay unchanged until the caller's stream has passed the end of that
  * call.  The buffer is the caller's; mv_reset leaves the ring attached. */
 int mv_set_action_ring(mv_gym *g, int32_t count, const int32_t *device_actions);
+/* Forks (no reference counterpart: its envs are separate objects that cannot be copied, env.hpp).  src_of: int32 [N].  src_of[d] = s, 0 <= s < N, s != d:
+ * env d leaves its running episode and continues env s's, from s's current state.  src_of[d] = -1 or d: env d is left alone.  One launch gathers, for
+ * every such d, env s's EPISODE STATE -- every per-env array a tick or a frame setup reads or writes, whole strides: EnvHeader (but the fields below),
+ * boxes, objects, every agent's AgentState (reward-shaping coefficients and total_reward included: a fork inherits its source's reward function), the
+ * scenario's own arrays (voxel chunk, terrain, reward objects, heightmap, arrangement items, Sokoban cells, hex boxes and objects, BoxAGoneState,
+ * FootballState) and, with the episode log on, the agents' running returns and the env's running length (env d's cut episode writes no record, as with
+ * mv_reset; the record at the fork's end covers the episode from s's start).  Env d keeps its IDENTITY: next_seed, seed_is_env_seed, episodes_consumed and
+ * starved of its header, its status words, its ring of resident next episodes and its generator -- when the forked episode ends, env d takes the next
+ * episode of its OWN sequence, the one it would have taken had its own episode ended; the episode feeder and the refill protocol see nothing unusual.
+ * Not touched: the public rewards / dones / true objectives, the output rings and the observation slab (they describe the last stepped tick; mv_render after
+ * a fork draws the forked envs' current views), pending actions.
+ * Ordering: the call is an ordering point, as mv_set_actions_device is.  The copy runs behind every step launch enqueued so far and behind whatever the
+ * caller enqueued on the gym's stream (the kernel that wrote the map); the next step launch runs behind the copy.  The device form never synchronises
+ * with the host, and the map is read when the copy runs: keep it unchanged until then (in stream order: until the next stepping call has been enqueued).
+ * Invalid entries: a source may serve any number of destinations but may not itself be a destination in the same call (an in-place gather cannot honour a
+ * chain), and an index must be -1 or 0 .. N - 1.  mv_fork_envs_host validates on the host: -1 with text, nothing forked.  The device form cannot: the
+ * kernel skips every entry involved (those envs stay as they were), applies the valid ones and raises a status bit, which the NEXT stepping call reports
+ * once as return 1 with a warning, like every capacity condition -- that call waits for the status words behind the fork (the one host wait the device
+ * form costs, paid there; the host form costs none).
+ * Refused (-1): no gym, a closed gym, before the first mv_reset, a null map, and a gym that belongs to an mv_group (its streams are the group's; forks
+ * inside groups, across gyms, and permutation maps -- a source that is also a destination -- are out of scope). */
+int mv_fork_envs(mv_gym *g, const int32_t *device_src_of);   /* map in device memory, read in the order of the gym's stream */
+int mv_fork_envs_host(mv_gym *g, const int32_t *src_of);     /* map in host memory: validated here, copied, then as above */
+int64_t mv_fork_bytes_per_env(const mv_gym *g);              /* bytes a fork reads and writes per destination (the episode log's included when it is on); -1: no gym */
 /* step several gyms of one job with one call (no reference counterpart: its multi-task runs are separate processes,
  * the scripts under megaverse_rl/runs): for each gym, optionally mv_sample_random_actions(seed, step_index), then mv_step / mv_step_no_render */
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index);
@@ -309,6 +333,11 @@ int mv_debug_collect_draw_host(int32_t num_agents, int32_t env_seed, int32_t n, 
  * and records, a buffer of `capacity` mv_episode_record of which *count are valid on entry. */
 int mv_debug_episode_log_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
                               uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped);
+/* Host-only (no device): the rule of a fork map (megaverse_amd/csrc/mv_fork.h, the source the kernel and mv_fork_envs_host run) applied to every entry of
+ * src_of [N]: resolved[d] = the source env d would continue from, or -1 (left alone, or skipped); invalid[d] = 1 where the entry is invalid. */
+int mv_debug_fork_plan_host(const int32_t *src_of, int32_t N, int32_t *resolved /* [N]: s or -1 */, int32_t *invalid /* [N]: 0/1 */);
+/* out_host [N]: how many episodes of its own sequence every env has taken so far (a fork leaves the destination's count alone) */
+int mv_debug_episodes_consumed(mv_gym *g, int32_t *out_host);
 int mv_debug_collect_draw_device(int32_t device, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n, float base_episode_len, void *out,
                                  int64_t out_bytes, float *ms_per_launch);
 

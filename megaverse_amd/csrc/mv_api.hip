@@ -425,6 +425,29 @@ int mv_create(const mv_config *cfg, mv_gym **out)
         if (hex) { gv.hex_boxes = (HexRec *)p; p += szHexB; gv.hex_objs = (HexRec *)p; p += szHexO; }
         if (boxagone) { gv.hex_boxes = (HexRec *)p; p += szHexB; gv.bag = (BoxAGoneState *)p; p += szBag; }
         if (football) { gv.hex_boxes = (HexRec *)p; p += szHexB; gv.hex_objs = (HexRec *)p; p += szHexO; gv.fb = (FootballState *)p; p += szFb; }
+        // The episode state of an env, for mv_fork_envs (mv_fork.h): EVERY per-env array carved above that a tick or a frame setup reads or writes, whole
+        // strides.  A new per-env array belongs here -- or, if it is part of what makes an env that env (its seed chain, its resident episodes, its place in
+        // the refill protocol: episode_status, blobs, tower_gen, and the header fields of fork::IDENTITY_DWORDS), on the identity list of DESIGN.md 3.8.  Not
+        // state: actions (a tick's input, cleared by it), rewards / done / true_objective (public outputs of the last stepped tick), the hand-over slots.
+        {
+            fork::Table &ft = g->forkTable;
+            ft = fork::Table{};
+            ft.hdr = gv.hdr;
+            fork::table_add(ft, gv.boxes, (size_t)gv.box_stride * sizeof(LayoutBox));
+            fork::table_add(ft, gv.objects, MAX_OBJECTS * sizeof(MovableObject));
+            fork::table_add(ft, gv.agents, (size_t)g->A * sizeof(AgentState));
+            fork::table_add(ft, gv.chunk, CHUNK_BYTES);
+            fork::table_add(ft, gv.terrain, MAX_TERRAIN * sizeof(TerrainBox));
+            fork::table_add(ft, gv.rewards_obj, (size_t)gv.reward_stride * sizeof(MovableObject));
+            fork::table_add(ft, gv.heightmap, HM_BYTES);
+            fork::table_add(ft, gv.items, MAX_ITEMS * sizeof(ArrangementItem));
+            fork::table_add(ft, gv.soko_cells, SOKO_DIM * SOKO_DIM);
+            fork::table_add(ft, gv.hex_boxes, HEX_MAX_BOXES * sizeof(HexRec));
+            fork::table_add(ft, gv.hex_objs, HEX_MAX_OBJS * sizeof(HexRec));
+            fork::table_add(ft, gv.bag, sizeof(BoxAGoneState));
+            fork::table_add(ft, gv.fb, sizeof(FootballState));
+            static_assert(13 + 2 <= fork::MAX_ARRAYS, "the table holds every per-env array and the episode log's two");
+        }
         gv.lpt_hist = (int32_t *)p; p += szHist;
         gv.sort_scratch = szSort ? p : nullptr; p += szSort;
         gv.depth_sort = 0;
@@ -679,6 +702,10 @@ int mv_close(mv_gym *g)
         (void)hipFree(gv.dbg);
     }
     episode_log_free(g);
+    if (g->dForkMap) (void)hipFree(g->dForkMap);
+    if (g->hForkMap) (void)hipHostFree(g->hForkMap);
+    for (hipEvent_t &e : g->forkMapCopied) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    g->dForkMap = g->hForkMap = nullptr; g->forkTable = fork::Table{};
     if (g->arena) (void)hipFree(g->arena);
     if (g->hiresObs) (void)hipFree(g->hiresObs);
     if (g->hBlobs) (void)(g->blobsOnDevice ? hipFree(g->hBlobs) : hipHostFree(g->hBlobs));
@@ -863,6 +890,8 @@ int check_status_flags(mv_gym *g)
     if (flags & ST_VISIBLE) msg += "a frame had more visible primitives than the raster keeps (256; Collect 1024; Hex* 2048): the excess was not drawn; ";
     if (flags & elog::ST_EPISODE_LOG) msg += "the episode log is full: finished episodes are being dropped (counted; drain it, or give it a larger capacity); ";
     if (flags & ST_CHUNK) msg += "an object placement outside the 32 x 16 x 32 voxel chunk was refused (the reference's grid is unbounded); ";
+    if (flags & ST_FORK) msg += "mv_fork_envs skipped invalid entries of its map (an index out of range, or a chain of forks: a source that is itself a "
+        "destination); those envs were left as they were; ";
     if (gen & GEN_SLABS) msg += "a generated layout merged into more slabs than an episode record holds (128, Collect 1024): the excess was dropped; ";
     if (gen & GEN_TERRAIN) msg += "more than 16 terrain boxes in a generated episode; ";
     if (gen & GEN_OBJECTS) msg += "more than 80 movable boxes in a generated episode; ";
@@ -987,7 +1016,8 @@ int refill_episodes(mv_gym *g, int k)
         // / 36-38.
         // r08x4, three runs each, this scheme / the 32-call bound: ObstaclesHard 512 envs 20.9 / 21.5, Empty 38.9 / 39.6: what the bound costs.)
         const int bound = std::max(32, 4 * k);
-        if (g->statusPeriod > 1 && g->pendingAge < bound && hipEventQuery(g->statusCopied) == hipErrorNotReady) {
+        // (a fork from a device map: its skipped entries are reported by THIS call -- the words behind the fork kernel are waited for)
+        if (!g->forkReportDue && g->statusPeriod > 1 && g->pendingAge < bound && hipEventQuery(g->statusCopied) == hipErrorNotReady) {
             (void)hipGetLastError();   // ("not ready" is an answer, not an error to report at the end of the step)
             g->pendingAge += k;
             // (no fresh counts: but envs known to be short of an episode whose successor was not generated yet -- or had just sent one: one episode per env and
@@ -1001,6 +1031,7 @@ int refill_episodes(mv_gym *g, int k)
         g->statusPending = false;
         g->pendingAge = 0;
     }
+    g->forkReportDue = false;   // (no read-back pending: mv_reset / mv_seed took the words synchronously)
     const int N = g->N;
     const bool starved = (g->hStatus[N + 1] & ST_STARVED) != 0;
     if (starved && g->hostEpisodes()) {   // recover: take the current counts and upload synchronously below

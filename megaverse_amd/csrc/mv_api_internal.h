@@ -2,6 +2,7 @@
 //   mv_api.hip        create / close, seeding, reset, actions, output rings, getters, reward shaping (MegaverseGym's methods but step)
 //   mv_api_step.hip   stepping: pipelining, batched calls, overlapped passes, groups (union launches), in-stream profiling
 //   mv_api_debug.hip  test hooks: snapshots, pose setters, host-side generators, RNG / arithmetic probes
+//   mv_fork.hip       env forks: the gather-copy kernel and its entry points
 // The C ABI itself is include/megaverse_hip.h; nothing here is exported under a C name.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,6 +29,7 @@
 #include "mv_types.h"
 #include "mv_union.h"
 #include "mv_episode_log.h"
+#include "mv_fork.h"
 
 namespace mv {
 // TowerBuilding: tops every env's ring of drawn episodes up (mv_reset.hip)
@@ -203,6 +205,14 @@ struct mv_gym {
     int32_t *logLen = nullptr;
     elog::Record *logRecords = nullptr;
     uint32_t ticksSinceReset = 0;                // ticks stepped since the last mv_reset: a record's end_tick
+    // mv_fork_envs: the per-env arrays that make up an env's episode state (filled by mv_create where it carves the arena; mv_fork.h), the host form's copy of
+    // its map (device + pinned staging, allocated at its first use), and "the next stepping call waits for the status words": a device map may have held
+    // invalid entries, which only the kernel saw (ST_FORK)
+    fork::Table forkTable{};
+    int32_t *dForkMap = nullptr, *hForkMap = nullptr;   // [2][N] each
+    hipEvent_t forkMapCopied[2] = {nullptr, nullptr};
+    unsigned long long forkMapUses = 0;
+    bool forkReportDue = false;
     // in-stream profiling
     std::vector<hipEvent_t> profEvents;          // 5 per profiled tick: [0] [1] around the step kernel (its stream), [2] [3] [4] before the
                                                  // observation pass, between frame sort and raster, after the raster (the caller's stream)

@@ -41,6 +41,8 @@ SYMBOLS = [
     ("mv_step", C.c_int, [_P]), ("mv_step_no_render", C.c_int, [_P]), ("mv_render", C.c_int, [_P]),
     ("mv_step_n", C.c_int, [_P, _I, _I, _U, _U]), ("mv_set_sample_policy", C.c_int, [_P, _I]),
     ("mv_set_action_ring", C.c_int, [_P, _I, _P]), ("mv_debug_launch_counts", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("mv_fork_envs", C.c_int, [_P, _P]), ("mv_fork_envs_host", C.c_int, [_P, _P]), ("mv_debug_fork_plan_host", C.c_int, [_P, _I, _P, _P]),
+    ("mv_debug_episodes_consumed", C.c_int, [_P, _P]), ("mv_fork_bytes_per_env", C.c_int64, [_P]),
     ("mv_set_output_ring", C.c_int, [_P, _I, _P, _P, _P]),
     ("mv_set_pass_overlap", C.c_int, [_P, _I]),
     ("mv_recommended_ticks_per_call", C.c_int, [_P]), ("mv_recommended_pass_overlap", C.c_int, [_P]), ("mv_arena_bytes", C.c_int64, [_P]),
@@ -116,6 +118,30 @@ def debug_episode_log_host(rewards, dones, true_objectives, agents_per_env, capa
         raise RuntimeError(lib.mv_last_error().decode())
     state["count"], state["dropped"] = int(count.value), int(dropped.value)
     return state
+
+
+def debug_fork_plan_host(src_of):
+    """mv_debug_fork_plan_host: the rule of a fork map on the CPU (no device) -> (resolved int32 [N]: the source of entry d, or -1; invalid uint8-like [N])"""
+    lib = load_library()
+    m = np.ascontiguousarray(src_of, np.int32).reshape(-1)
+    resolved, invalid = np.full(m.size, -9, np.int32), np.full(m.size, -9, np.int32)
+    if m.size and lib.mv_debug_fork_plan_host(m.ctypes.data, m.size, resolved.ctypes.data, invalid.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return resolved, invalid
+
+
+def check_fork_map(src_of, num_envs):
+    """the argument check of MegaverseGym.fork_envs: a CUDA int32 tensor of shape (num_envs,) -> 'device'; anything else -> a contiguous int32 numpy array"""
+    if hasattr(src_of, 'data_ptr'):
+        if tuple(src_of.shape) != (int(num_envs),) or str(src_of.dtype) != 'torch.int32' or not src_of.is_cuda or not src_of.is_contiguous():
+            raise ValueError(f'fork_envs: a tensor map must be a contiguous int32 CUDA tensor of shape ({int(num_envs)},), '
+                             f'got {src_of.dtype} {tuple(src_of.shape)} on {src_of.device}')
+        return 'device'
+    m = np.asarray(src_of)
+    if m.shape != (int(num_envs),) or m.dtype.kind not in 'iu':
+        raise ValueError(f'fork_envs: the map must be {int(num_envs)} integers (src_of[d] = the env that env d continues from, -1 or d: left alone), '
+                         f'got {m.dtype} {m.shape}')
+    return np.ascontiguousarray(m, dtype=np.int32)
 
 
 def library_path():
@@ -208,6 +234,7 @@ class MegaverseGym:
         self._g = handle
         self.w, self.h, self.num_envs, self.num_agents_per_env, self.device = int(w), int(h), int(num_envs), int(num_agents_per_env), int(device)
         self.render_w, self.render_h = 768, 432
+        self._fork_held = None   # fork_envs: the caller's device map, kept until the next step has been enqueued
 
     def _ck(self, rc):
         if rc < 0:
@@ -243,6 +270,7 @@ class MegaverseGym:
 
     def step(self):
         self._ckw(self._lib.mv_step(self._g))
+        self._fork_held = None
 
     def is_done(self, env_idx):
         return bool(self._ck(self._lib.mv_is_done(self._g, int(env_idx))))
@@ -319,6 +347,7 @@ class MegaverseGym:
 
     def step_no_render(self):
         self._ckw(self._lib.mv_step_no_render(self._g))
+        self._fork_held = None
 
     POLICIES = {"none": 0, "multidiscrete": 1, "single-bit": 2, "sequence": 3}
 
@@ -326,6 +355,20 @@ class MegaverseGym:
         """k open-loop ticks (each stepped and rendered) with one call; tick j draws its actions from (policy, seed, first_step_index + j) --
         policy 'sequence': it acts on entry (first_step_index + j) % count of the action ring (set_action_ring), seed is ignored"""
         self._ckw(self._lib.mv_step_n(self._g, int(k), int(self.POLICIES.get(policy, policy)), int(seed) & 0xFFFFFFFF, int(first_step_index) & 0xFFFFFFFF))
+        self._fork_held = None
+
+    def fork_envs(self, src_of):
+        """Env forks (include/megaverse_hip.h: mv_fork_envs): src_of[d] = s makes env d leave its running episode and continue env s's from s's current
+        state; -1 or d leaves env d alone.  Env d keeps its own seed chain and resident next episodes.  A contiguous int32 CUDA tensor of shape (num_envs,) is
+        read in place, in the order of the gym's stream, without a host synchronisation (it is held until the next step; an invalid entry is skipped and
+        reported by the next stepping call as a warning); a numpy array or a sequence is validated on the host first (RuntimeError, nothing forked).  A
+        source may serve many destinations but may not be a destination in the same call."""
+        m = check_fork_map(src_of, self.num_envs)
+        if isinstance(m, str):
+            self._ck(self._lib.mv_fork_envs(self._g, _P(int(src_of.data_ptr()))))
+            self._fork_held = src_of
+        else:
+            self._ck(self._lib.mv_fork_envs_host(self._g, m.ctypes.data))
 
     def set_action_ring(self, count, device_ptr=0):
         """int32 [count, num_agents, 6] multi-discrete actions in device memory for step_n(..., 'sequence') (include/megaverse_hip.h: mv_set_action_ring);
@@ -533,6 +576,16 @@ class MegaverseGym:
         buf = np.zeros(16, np.float32)
         buf[0:3], buf[3], buf[4:7], buf[8:11], buf[12:15] = pos, radius, vel, ang, force
         self._ck(self._lib.mv_debug_set_football_state(self._g, int(env_idx), buf.ctypes.data))
+
+    def fork_bytes_per_env(self):
+        """bytes a fork copies per destination env: the size of an env's episode state"""
+        return int(self._lib.mv_fork_bytes_per_env(self._g))
+
+    def debug_episodes_consumed(self):
+        """int32 [num_envs]: the episodes of its own sequence every env has taken so far (a test hook; synchronises)"""
+        out = np.zeros(self.num_envs, np.int32)
+        self._ck(self._lib.mv_debug_episodes_consumed(self._g, out.ctypes.data))
+        return out
 
     def debug_snapshot_bytes(self, env_idx):
         n = self._lib.mv_debug_snapshot_size(self._g)

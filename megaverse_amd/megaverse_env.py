@@ -233,6 +233,24 @@ class MegaverseEnv:
         del held
         return self._obs_view(), self._dev_out[0], self._dev_out[1]
 
+    def fork(self, src_env, dst_envs=None):
+        """env src_env's running episode continues in every env of dst_envs as well (default: in all others) -- MegaverseGym.fork_envs with the map built
+        here: N candidate plans branch from one situation, then step_sequence plays them.  The destinations keep their own next episodes.  Outputs are
+        untouched: they still describe the last stepped tick."""
+        src_env = int(src_env)
+        if not 0 <= src_env < self.num_envs:
+            raise ValueError(f'fork: src_env must be within 0 .. {self.num_envs - 1}, got {src_env}')
+        m = np.full(self.num_envs, -1, np.int32)
+        if dst_envs is None:
+            m[:] = src_env
+        else:
+            d = np.asarray(list(dst_envs), dtype=np.int64).reshape(-1)
+            if d.size and (d.min() < 0 or d.max() >= self.num_envs):
+                raise ValueError(f'fork: dst_envs must be within 0 .. {self.num_envs - 1}')
+            m[d] = src_env
+        m[src_env] = -1
+        self.env.fork_envs(m)
+
     def _leave_sequence(self):
         """step_sequence's rings are attached: back to the single slab and arrays, the slab brought up to date"""
         if self._seq is None:
