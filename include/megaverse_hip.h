@@ -120,6 +120,39 @@ int mv_set_action_ring(mv_gym *g, int32_t count, const int32_t *device_actions);
 int mv_fork_envs(mv_gym *g, const int32_t *device_src_of);   /* map in device memory, read in the order of the gym's stream */
 int mv_fork_envs_host(mv_gym *g, const int32_t *src_of);     /* map in host memory: validated here, copied, then as above */
 int64_t mv_fork_bytes_per_env(const mv_gym *g);              /* bytes a fork reads and writes per destination (the episode log's included when it is on); -1: no gym */
+/* Masked resets (no reference counterpart: VectorEnv::reset resets every env, vector_env.cpp:110-120).  mask: one byte per env, [N]; a torch.bool tensor is
+ * such a mask.  mask[e] != 0: env e abandons its running episode and takes the NEXT EPISODE OF ITS OWN SEQUENCE -- the one it would have taken had its
+ * episode ended at this point: episodes_consumed + 1, its own seed chain, its own ring slot (a fork destination keeps its identity, so this is how it hands
+ * a forked episode back).  mask[e] == 0: env e is untouched, byte for byte.
+ * State: a flagged env ends up exactly where mv_reset would have put it at this moment -- every per-env array the scenario's swap-in writes under mv_reset
+ * (header, boxes, objects, agents, the scenario's own arrays) and its status word; its entries of the public rewards and dones (the current entry of an
+ * output ring where one is attached) and its pending actions are cleared as mv_reset clears them; its true objectives stay what they were, as under
+ * mv_reset.  A pending mv_set_actions_device buffer is read first, as in mv_reset; unflagged envs keep their actions.  An all-zero mask changes no byte of
+ * the gym; an all-ones mask leaves every env as mv_reset does.
+ * What it is not: a whole-gym reset.  mv_ticks_since_reset keeps counting, output rings stay attached and their tick count is not rewound.
+ * Episode log (when on): the cut episode of a flagged env writes no record; its agents' running returns and its running length go to zero; nothing else in
+ * the log changes, neither records nor counts.
+ * Observation: render != 0: behind the swap-in the call runs the observation pass where mv_render would draw, so flagged envs show their new episode's first
+ * view as an auto-reset tick's observation does; the pass draws every frame of the gym, and the unflagged envs' frames come out byte-identical because their
+ * state did not change.  render == 0: the slab is not touched.
+ * Ordering: the call is an ordering point, as mv_fork_envs is.  It runs behind every step launch enqueued so far and behind whatever the caller enqueued on
+ * the gym's stream (the kernel that wrote the mask); the next step launch runs behind it.  The device form never waits on the host: the mask is read when
+ * the kernel runs -- keep it unchanged until then (in stream order: until the next stepping call has been enqueued).
+ * Episodes, three cases.  (1) Device-drawn episodes (TowerBuilding): the rings are topped up in front of the swap-in and behind it, as in mv_reset, on the
+ * stream, in both forms: no host wait, no starvation.  (2) Host-fed gyms (every other scenario; Collect too, wherever its episodes are drawn: they reach the
+ * ring through the host's refill protocol), host form: the call takes the current consumed counts synchronously, as mv_reset does, and makes sure every
+ * flagged env has an unconsumed episode resident before the launch: it never starves, however often it is repeated.  (3) Host-fed gyms, device form: no
+ * host wait, so only resident episodes count (two or three per env; right behind mv_reset one, the rest arrive with the next stepping calls).  A flagged env whose ring holds no unconsumed episode is LEFT AS IT IS (its log
+ * accumulators too) and the starvation bit is raised; the next stepping call waits for the status words behind the launch, reports it once as return 1 with a
+ * warning and recovers the ring, as it does for an env that finished twice; a refill pass is forced so that the host replaces the consumed episodes promptly.
+ * An all-zero mask: the host form sees it on the host and returns behind the flush of pending device actions -- nothing is launched, nothing drawn; the device
+ * form cannot know, so it launches as always (every wave exits) and, with render != 0, redraws the whole gym, byte for byte what it was.
+ * The first call on a gym -- either form -- allocates 3 N bytes of device memory and 2 N pinned bytes (the host form's copy of its mask, which flagged envs
+ * took an episode): that one call may wait on the host inside the allocator; "never waits on the host" holds for every call after it.
+ * Members of an mv_group are supported: the call follows mv_reset's path, which is valid for them.
+ * Refused (-1 with text): no gym, a closed gym, before the first mv_reset, a null mask. */
+int mv_reset_envs(mv_gym *g, const uint8_t *device_mask, int32_t render);   /* mask [N] in device memory, read in the order of the gym's stream */
+int mv_reset_envs_host(mv_gym *g, const uint8_t *mask, int32_t render);     /* mask [N] in host memory */
 /* step several gyms of one job with one call (no reference counterpart: its multi-task runs are separate processes,
  * the scripts under megaverse_rl/runs): for each gym, optionally mv_sample_random_actions(seed, step_index), then mv_step / mv_step_no_render */
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index);
@@ -333,6 +366,9 @@ int mv_debug_collect_draw_host(int32_t num_agents, int32_t env_seed, int32_t n, 
  * and records, a buffer of `capacity` mv_episode_record of which *count are valid on entry. */
 int mv_debug_episode_log_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
                               uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped);
+/* Host-only (no device): the episode log's masked clear (megaverse_amd/csrc/mv_episode_log.h: episode_log_cut, the source mv_reset_envs' kernel runs) over N
+ * envs x A agents: where mask[e] != 0, ret[e * A .. e * A + A - 1] and len[e] go to zero; everything else stays. */
+int mv_debug_episode_log_cut_host(const uint8_t *mask, int32_t N, int32_t A, double *ret, int32_t *len);
 /* Host-only (no device): the rule of a fork map (megaverse_amd/csrc/mv_fork.h, the source the kernel and mv_fork_envs_host run) applied to every entry of
  * src_of [N]: resolved[d] = the source env d would continue from, or -1 (left alone, or skipped); invalid[d] = 1 where the entry is invalid. */
 int mv_debug_fork_plan_host(const int32_t *src_of, int32_t N, int32_t *resolved /* [N]: s or -1 */, int32_t *invalid /* [N]: 0/1 */);

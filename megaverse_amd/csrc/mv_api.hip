@@ -706,6 +706,10 @@ int mv_close(mv_gym *g)
     if (g->hForkMap) (void)hipHostFree(g->hForkMap);
     for (hipEvent_t &e : g->forkMapCopied) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     g->dForkMap = g->hForkMap = nullptr; g->forkTable = fork::Table{};
+    if (g->dResetMask) (void)hipFree(g->dResetMask);
+    if (g->hResetMask) (void)hipHostFree(g->hResetMask);
+    for (hipEvent_t &e : g->resetMaskCopied) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    g->dResetMask = g->hResetMask = nullptr;
     if (g->arena) (void)hipFree(g->arena);
     if (g->hiresObs) (void)hipFree(g->hiresObs);
     if (g->hBlobs) (void)(g->blobsOnDevice ? hipFree(g->hBlobs) : hipHostFree(g->hBlobs));
@@ -1016,8 +1020,9 @@ int refill_episodes(mv_gym *g, int k)
         // / 36-38.
         // r08x4, three runs each, this scheme / the 32-call bound: ObstaclesHard 512 envs 20.9 / 21.5, Empty 38.9 / 39.6: what the bound costs.)
         const int bound = std::max(32, 4 * k);
-        // (a fork from a device map: its skipped entries are reported by THIS call -- the words behind the fork kernel are waited for)
-        if (!g->forkReportDue && g->statusPeriod > 1 && g->pendingAge < bound && hipEventQuery(g->statusCopied) == hipErrorNotReady) {
+        // (statusReportDue -- a fork from a device map, or a masked reset from a device mask on a host-fed gym: what only the kernel saw, skipped entries or a
+        // starved env, is reported by THIS call -- the words behind that kernel are waited for)
+        if (!g->statusReportDue && g->statusPeriod > 1 && g->pendingAge < bound && hipEventQuery(g->statusCopied) == hipErrorNotReady) {
             (void)hipGetLastError();   // ("not ready" is an answer, not an error to report at the end of the step)
             g->pendingAge += k;
             // (no fresh counts: but envs known to be short of an episode whose successor was not generated yet -- or had just sent one: one episode per env and
@@ -1031,7 +1036,7 @@ int refill_episodes(mv_gym *g, int k)
         g->statusPending = false;
         g->pendingAge = 0;
     }
-    g->forkReportDue = false;   // (no read-back pending: mv_reset / mv_seed took the words synchronously)
+    g->statusReportDue = false;   // (no read-back pending: mv_reset / mv_seed took the words synchronously)
     const int N = g->N;
     const bool starved = (g->hStatus[N + 1] & ST_STARVED) != 0;
     if (starved && g->hostEpisodes()) {   // recover: take the current counts and upload synchronously below

@@ -3,6 +3,7 @@
 //   mv_api_step.hip   stepping: pipelining, batched calls, overlapped passes, groups (union launches), in-stream profiling
 //   mv_api_debug.hip  test hooks: snapshots, pose setters, host-side generators, RNG / arithmetic probes
 //   mv_fork.hip       env forks: the gather-copy kernel and its entry points
+//   mv_reset_envs.hip masked env resets: the host protocol around the reset_masked kernels (mv_step_kernels.h)
 // The C ABI itself is include/megaverse_hip.h; nothing here is exported under a C name.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -45,6 +46,8 @@ bool launch_step(const GymView &gv, hipStream_t stream, int W, int H, int render
 void launch_step_ticks(const GymView *views, int k, hipStream_t stream, int W, int H, hipEvent_t done = nullptr);
 // every finished (force_all: every) env swaps its next resident episode in
 void launch_reset_episodes(const GymView &gv, int force_all, hipStream_t stream);
+// mv_reset_envs: the envs mask [num_envs] flags take their next resident episode; applied [num_envs]: 1 / 0 for every flagged env, whether it did
+void launch_reset_envs(const GymView &gv, const uint8_t *mask, uint8_t *applied, hipStream_t stream);
 }  // namespace mv
 
 using namespace mv;
@@ -206,13 +209,19 @@ struct mv_gym {
     elog::Record *logRecords = nullptr;
     uint32_t ticksSinceReset = 0;                // ticks stepped since the last mv_reset: a record's end_tick
     // mv_fork_envs: the per-env arrays that make up an env's episode state (filled by mv_create where it carves the arena; mv_fork.h), the host form's copy of
-    // its map (device + pinned staging, allocated at its first use), and "the next stepping call waits for the status words": a device map may have held
-    // invalid entries, which only the kernel saw (ST_FORK)
+    // its map (device + pinned staging, allocated at its first use)
     fork::Table forkTable{};
     int32_t *dForkMap = nullptr, *hForkMap = nullptr;   // [2][N] each
     hipEvent_t forkMapCopied[2] = {nullptr, nullptr};
     unsigned long long forkMapUses = 0;
-    bool forkReportDue = false;
+    // "the next stepping call waits for the status words" (refill_episodes): something only a kernel saw has to be reported by that call -- a fork's device map
+    // may have held invalid entries (ST_FORK), a masked reset from a device mask may have found a host-fed env without a resident episode (ST_STARVED)
+    bool statusReportDue = false;
+    // mv_reset_envs: [3][N] bytes of device memory -- the host form's copy of its mask, double buffered, and `applied` (which flagged envs took an episode) --
+    // and the pinned staging of the two mask halves, allocated at the first use
+    uint8_t *dResetMask = nullptr, *hResetMask = nullptr;
+    hipEvent_t resetMaskCopied[2] = {nullptr, nullptr};
+    unsigned long long resetMaskUses = 0;
     // in-stream profiling
     std::vector<hipEvent_t> profEvents;          // 5 per profiled tick: [0] [1] around the step kernel (its stream), [2] [3] [4] before the
                                                  // observation pass, between frame sort and raster, after the raster (the caller's stream)

@@ -53,6 +53,17 @@ MV_ELOG_HD bool episode_log_tick(double &ret, int32_t &len, float reward, uint8_
     return true;
 }
 
+// mv_reset_envs, one agent i of a gym with A agents per env: where the mask flags the agent's env -- and, applied given, the env did take its next episode
+// (mv_step_kernels.h: reset_masked_body) -- the episode is cut: the agent's running return goes to zero, the env's running length too (stored by the env's
+// first agent), and no record is written; every other env keeps both
+MV_ELOG_HD void episode_log_cut(const uint8_t *mask, const uint8_t *applied, int32_t A, int32_t i, double *ret, int32_t *len)
+{
+    const int32_t e = i / A;
+    if (!mask[e] || (applied && !applied[e])) return;
+    ret[i] = 0.0;
+    if (i == e * A) len[e] = 0;
+}
+
 // the record of place `pos` in the log's order: kept if the buffer holds it
 MV_ELOG_HD void episode_log_store(Record *records, uint32_t capacity, uint64_t pos, const Record &rec)
 {
@@ -96,6 +107,7 @@ inline int max_ticks_per_launch(int64_t agents)
 }
 
 void launch_episode_log(const Args &a, hipStream_t stream);   // mv_episode_log.hip
+void launch_episode_log_cut(const uint8_t *mask, const uint8_t *applied, int32_t N, int32_t A, double *ret, int32_t *len, hipStream_t stream);   // the masked clear of mv_reset_envs
 
 }  // namespace elog
 }  // namespace mv

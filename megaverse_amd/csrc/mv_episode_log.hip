@@ -161,6 +161,20 @@ void launch_episode_log(const Args &a, hipStream_t stream)
     else hipLaunchKernelGGL(episode_log_kernel<MAX_TICKS>, dim3(1), dim3(THREADS), 0, stream, a);
 }
 
+// mv_reset_envs with the log on: one thread per agent clears what the mask flags (mv_episode_log.h: episode_log_cut).  ret is doubles, len dwords, an agent's
+// slot is its own whatever the agent count: nothing here depends on A being even.
+__global__ __launch_bounds__(256) void episode_log_cut_kernel(const uint8_t *__restrict__ mask, const uint8_t *__restrict__ applied, int32_t N, int32_t A, double *ret, int32_t *len)
+{
+    const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < N * A) episode_log_cut(mask, applied, A, i, ret, len);
+}
+
+void launch_episode_log_cut(const uint8_t *mask, const uint8_t *applied, int32_t N, int32_t A, double *ret, int32_t *len, hipStream_t stream)
+{
+    const int n = N * A;
+    hipLaunchKernelGGL(episode_log_cut_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, mask, applied, N, A, ret, len);
+}
+
 }  // namespace elog
 }  // namespace mv
 
@@ -327,6 +341,14 @@ int mv_debug_episode_log_host(const float *rewards, const uint8_t *dones, const 
     }
     *count = h.count;
     *dropped = h.dropped;
+    return 0;
+}
+
+// The masked clear of mv_reset_envs compiled for the CPU (no device): episode_log_cut over every agent of N envs x A agents.
+int mv_debug_episode_log_cut_host(const uint8_t *mask, int32_t N, int32_t A, double *ret, int32_t *len)
+{
+    if (!mask || !ret || !len || N < 1 || A < 1) return fail("mv_debug_episode_log_cut_host: bad arguments");
+    for (int32_t i = 0; i < N * A; ++i) mv::elog::episode_log_cut(mask, nullptr, A, i, ret, len);
     return 0;
 }
 

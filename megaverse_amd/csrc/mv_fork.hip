@@ -153,7 +153,7 @@ int fork_launch(mv_gym *g, const int32_t *device_map, const int32_t *host_map)
         // (refill_episodes), so that it is that call which reports ST_FORK: a host wait there, none here.
         HIP_TRY(hipEventRecord(g->userNow, g->stream));
         if (read_back_status(g, g->userNow)) return -1;
-        g->forkReportDue = true;
+        g->statusReportDue = true;
     }
     return 0;
 }

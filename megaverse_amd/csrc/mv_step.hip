@@ -19,9 +19,10 @@ template <class Args> __global__ __launch_bounds__(256, 3) void step_ticks_agent
 template <class Args> __global__ __launch_bounds__(128, MV_STEP_TICKS_WAVES_PER_SIMD) void step_ticks_pipe_kernel(Args a, int W, int H) { step_ticks_pipe_body<S>(a, W, H); }
 // (the draws that refill the rings run in front of it: tower_draw_kernel, mv_reset.hip)
 __global__ __launch_bounds__(64) void reset_kernel(GymView gv, int force_all) { reset_body<S>(gv, force_all); }
+__global__ __launch_bounds__(64) void reset_masked_kernel(GymView gv, const uint8_t *mask, uint8_t *applied) { reset_masked_body<S>(gv, mask, applied); }
 
 const StepKernels tower_kernels = {step_kernel<1>, step_kernel<MAX_AGENTS>, step_ticks_kernel<StepTicksArgs8>, step_ticks_pipe_kernel<StepTicksArgs8>,
-                                   step_ticks_agents_kernel<StepTicksArgs8>, reset_kernel};
+                                   step_ticks_agents_kernel<StepTicksArgs8>, reset_kernel, reset_masked_kernel};
 
 static const StepKernels &kernels_of(int scenario)
 {
@@ -83,6 +84,11 @@ bool launch_step(const GymView &gv, hipStream_t stream, int W, int H, int render
 void launch_reset_episodes(const GymView &gv, int force_all, hipStream_t stream)
 {
     hipLaunchKernelGGL(kernels_of(gv.scenario).reset, dim3(gv.num_envs), dim3(64), 0, stream, gv, force_all);
+}
+
+void launch_reset_envs(const GymView &gv, const uint8_t *mask, uint8_t *applied, hipStream_t stream)
+{
+    hipLaunchKernelGGL(kernels_of(gv.scenario).reset_masked, dim3(gv.num_envs), dim3(64), 0, stream, gv, mask, applied);
 }
 
 }  // namespace mv

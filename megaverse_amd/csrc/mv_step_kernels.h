@@ -162,6 +162,21 @@ __device__ __forceinline__ void reset_body(const GymView &gv, int force_all)
     S::swap_in(gv, env, force_all);
 }
 
+// mv_reset_envs: the envs a mask [num_envs] flags leave their episode and take their next resident one, as every env does under mv_reset (force_all = 1).
+// One wavefront per env.  The env's mask byte is loaded once and made uniform; an unflagged wave leaves behind that one load, so a sparse mask costs a launch
+// of waves that exit, not mv_reset's.  applied [num_envs]: a flagged env's wave leaves 1 where it took an episode, 0 where none was resident (ST_STARVED: the
+// env stays as it was) -- what the episode log's masked clear goes by; the bytes of unflagged envs are not written.
+template <class S>
+__device__ __forceinline__ void reset_masked_body(const GymView &gv, const uint8_t *__restrict__ mask, uint8_t *__restrict__ applied)
+{
+    const int env = blockIdx.x;
+    if (env >= gv.num_envs) return;
+    if (__builtin_amdgcn_readfirstlane((int)mask[env]) == 0) return;
+    const int before = gv.hdr[env].episodes_consumed;
+    S::swap_in(gv, env, 1);
+    if (threadIdx.x == 0) applied[env] = gv.hdr[env].episodes_consumed != before ? 1 : 0;   // (lane 0 stored the count: its own store, read back in order)
+}
+
 // one scenario's entry points (its mv_step_<scenario>.hip); null: the scenario has no such kernel
 struct StepKernels {
     void (*step)(GymView, int, int, int);                // one agent per env
@@ -170,6 +185,7 @@ struct StepKernels {
     void (*ticks_pipe)(StepTicksArgs8, int, int);        // ... software-pipelined
     void (*ticks_agents)(StepTicksArgs8, int, int);      // k ticks, several agents per env
     void (*reset)(GymView, int);
+    void (*reset_masked)(GymView, const uint8_t *, uint8_t *);   // mv_reset_envs: the envs a mask flags
 };
 extern const StepKernels tower_kernels, obstacles_kernels, collect_kernels, rearrange_kernels, sokoban_kernels, hex_kernels, boxagone_kernels,
                           football_kernels;

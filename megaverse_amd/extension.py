@@ -43,6 +43,7 @@ SYMBOLS = [
     ("mv_set_action_ring", C.c_int, [_P, _I, _P]), ("mv_debug_launch_counts", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("mv_fork_envs", C.c_int, [_P, _P]), ("mv_fork_envs_host", C.c_int, [_P, _P]), ("mv_debug_fork_plan_host", C.c_int, [_P, _I, _P, _P]),
     ("mv_debug_episodes_consumed", C.c_int, [_P, _P]), ("mv_fork_bytes_per_env", C.c_int64, [_P]),
+    ("mv_reset_envs", C.c_int, [_P, _P, _I]), ("mv_reset_envs_host", C.c_int, [_P, _P, _I]), ("mv_debug_episode_log_cut_host", C.c_int, [_P, _I, _I, _P, _P]),
     ("mv_set_output_ring", C.c_int, [_P, _I, _P, _P, _P]),
     ("mv_set_pass_overlap", C.c_int, [_P, _I]),
     ("mv_recommended_ticks_per_call", C.c_int, [_P]), ("mv_recommended_pass_overlap", C.c_int, [_P]), ("mv_arena_bytes", C.c_int64, [_P]),
@@ -144,6 +145,36 @@ def check_fork_map(src_of, num_envs):
     return np.ascontiguousarray(m, dtype=np.int32)
 
 
+def debug_episode_log_cut_host(mask, agents_per_env, ret, length):
+    """mv_debug_episode_log_cut_host: the episode log's masked clear on the CPU (no device).  mask [N] (non-zero: cut), ret float64 [N*A] and length
+    int32 [N] are changed in place: a flagged env's running returns and running length go to zero."""
+    lib = load_library()
+    m = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+    A = int(agents_per_env)
+    if ret.dtype != np.float64 or length.dtype != np.int32 or ret.shape != (m.size * A,) or length.shape != (m.size,) \
+            or not ret.flags.c_contiguous or not length.flags.c_contiguous:
+        raise ValueError("debug_episode_log_cut_host: ret is a contiguous float64 [N*A], length a contiguous int32 [N]")
+    if lib.mv_debug_episode_log_cut_host(m.ctypes.data, m.size, A, ret.ctypes.data, length.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+
+
+def check_reset_mask(mask, num_envs):
+    """the argument check of MegaverseGym.reset_envs: a CUDA bool / uint8 tensor (or anything with data_ptr()) of shape (num_envs,) -> 'device'; anything else
+    -> a contiguous uint8 numpy array, one byte per env"""
+    n = int(num_envs)
+    if hasattr(mask, 'data_ptr'):
+        contiguous = getattr(mask, 'is_contiguous', None)
+        if tuple(getattr(mask, 'shape', ())) != (n,) or str(getattr(mask, 'dtype', None)) not in ('torch.bool', 'torch.uint8') \
+                or not getattr(mask, 'is_cuda', False) or not (callable(contiguous) and contiguous()):
+            raise ValueError(f'reset_envs: a tensor mask must be a contiguous bool or uint8 CUDA tensor of shape ({n},), '
+                             f"got {getattr(mask, 'dtype', None)} {tuple(getattr(mask, 'shape', ()))} on {getattr(mask, 'device', 'an unknown device')}")
+        return 'device'
+    m = np.asarray(mask)
+    if m.shape != (n,) or m.dtype.kind not in 'bu' or (m.dtype.kind == 'u' and m.dtype.itemsize != 1):
+        raise ValueError(f'reset_envs: the mask must be {n} bools (or uint8: non-zero = reset this env), got {m.dtype} {m.shape}')
+    return np.ascontiguousarray(m != 0, dtype=np.uint8)
+
+
 def library_path():
     return _build.LIB
 
@@ -235,6 +266,7 @@ class MegaverseGym:
         self.w, self.h, self.num_envs, self.num_agents_per_env, self.device = int(w), int(h), int(num_envs), int(num_agents_per_env), int(device)
         self.render_w, self.render_h = 768, 432
         self._fork_held = None   # fork_envs: the caller's device map, kept until the next step has been enqueued
+        self._reset_held = None  # reset_envs: the caller's device mask, likewise
 
     def _ck(self, rc):
         if rc < 0:
@@ -270,7 +302,7 @@ class MegaverseGym:
 
     def step(self):
         self._ckw(self._lib.mv_step(self._g))
-        self._fork_held = None
+        self._fork_held = self._reset_held = None
 
     def is_done(self, env_idx):
         return bool(self._ck(self._lib.mv_is_done(self._g, int(env_idx))))
@@ -347,7 +379,7 @@ class MegaverseGym:
 
     def step_no_render(self):
         self._ckw(self._lib.mv_step_no_render(self._g))
-        self._fork_held = None
+        self._fork_held = self._reset_held = None
 
     POLICIES = {"none": 0, "multidiscrete": 1, "single-bit": 2, "sequence": 3}
 
@@ -355,7 +387,7 @@ class MegaverseGym:
         """k open-loop ticks (each stepped and rendered) with one call; tick j draws its actions from (policy, seed, first_step_index + j) --
         policy 'sequence': it acts on entry (first_step_index + j) % count of the action ring (set_action_ring), seed is ignored"""
         self._ckw(self._lib.mv_step_n(self._g, int(k), int(self.POLICIES.get(policy, policy)), int(seed) & 0xFFFFFFFF, int(first_step_index) & 0xFFFFFFFF))
-        self._fork_held = None
+        self._fork_held = self._reset_held = None
 
     def fork_envs(self, src_of):
         """Env forks (include/megaverse_hip.h: mv_fork_envs): src_of[d] = s makes env d leave its running episode and continue env s's from s's current
@@ -369,6 +401,18 @@ class MegaverseGym:
             self._fork_held = src_of
         else:
             self._ck(self._lib.mv_fork_envs_host(self._g, m.ctypes.data))
+
+    def reset_envs(self, mask, render=True):
+        """Masked resets (include/megaverse_hip.h: mv_reset_envs): every env whose mask entry is set abandons its running episode and takes the next episode
+        of its own sequence; the others are untouched.  A contiguous torch.bool / uint8 CUDA tensor of shape (num_envs,) is read in place, in the order of
+        the gym's stream, without a host synchronisation (it is held until the next step); a numpy array or a sequence of bools goes through the host form,
+        which makes sure every flagged env has an episode resident.  render: draw the observations behind the reset, where step() leaves them."""
+        m = check_reset_mask(mask, self.num_envs)
+        if isinstance(m, str):
+            self._ckw(self._lib.mv_reset_envs(self._g, _P(int(mask.data_ptr())), int(bool(render))))
+            self._reset_held = mask
+        else:
+            self._ckw(self._lib.mv_reset_envs_host(self._g, m.ctypes.data, int(bool(render))))
 
     def set_action_ring(self, count, device_ptr=0):
         """int32 [count, num_agents, 6] multi-discrete actions in device memory for step_n(..., 'sequence') (include/megaverse_hip.h: mv_set_action_ring);

@@ -251,6 +251,17 @@ class MegaverseEnv:
         m[src_env] = -1
         self.env.fork_envs(m)
 
+    def reset_envs(self, env_ids, render=True):
+        """the envs of env_ids abandon their running episode and start the next one of their own sequence (MegaverseGym.reset_envs with the mask built
+        here); the others are untouched.  What a learner's own time limit, a curriculum, or a planner handing its fork destinations back needs.  With render
+        the observations of those envs are redrawn where step_device / step_batched leave observations; rewards and dones of the reset envs read zero."""
+        ids = np.asarray(list(env_ids), dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= self.num_envs):
+            raise ValueError(f'reset_envs: env_ids must be within 0 .. {self.num_envs - 1}')
+        m = np.zeros(self.num_envs, np.bool_)
+        m[ids] = True
+        self.env.reset_envs(m, render)
+
     def _leave_sequence(self):
         """step_sequence's rings are attached: back to the single slab and arrays, the slab brought up to date"""
         if self._seq is None:

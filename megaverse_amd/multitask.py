@@ -223,6 +223,23 @@ class MultiTaskGym:
         for g in self.gyms:
             g.reset()
 
+    def reset_envs(self, mask, render=True):
+        """Masked resets (MegaverseGym.reset_envs; mv_reset_envs follows mv_reset's path, so members of a group are served): `mask` holds one bool per env in
+        the batch's global numbering -- a numpy array / sequence (host form) or a bool / uint8 CUDA tensor (device form) -- and is dealt to the sub-gyms by
+        locate's rule (global env i is local env i // S of sub-gym i % S).  The parts of a tensor are copies made on torch's current stream, the gyms'."""
+        S = len(self.gyms)
+        if hasattr(mask, "data_ptr"):
+            if tuple(mask.shape) != (self.num_envs,):
+                raise ValueError(f"reset_envs: the mask must have shape ({self.num_envs},), got {tuple(mask.shape)}")
+            parts = [mask.reshape(self.per_task, S)[:, k].contiguous() for k in range(S)]
+        else:
+            m = np.asarray(mask)
+            if m.shape != (self.num_envs,):
+                raise ValueError(f"reset_envs: the mask must be {self.num_envs} bools, got {m.dtype} {m.shape}")
+            parts = [np.ascontiguousarray(m.reshape(self.per_task, S)[:, k]) for k in range(S)]
+        for g, part in zip(self.gyms, parts):
+            g.reset_envs(part, render)
+
     def set_actions(self, env_idx, agent_idx, actions):
         g, j = self.locate(env_idx)
         g.set_actions(j, agent_idx, actions)
