@@ -116,10 +116,39 @@ int mv_set_action_ring(mv_gym *g, int32_t count, const int32_t *device_actions);
  * once as return 1 with a warning, like every capacity condition -- that call waits for the status words behind the fork (the one host wait the device
  * form costs, paid there; the host form costs none).
  * Refused (-1): no gym, a closed gym, before the first mv_reset, a null map, and a gym that belongs to an mv_group (its streams are the group's; forks
- * inside groups, across gyms, and permutation maps -- a source that is also a destination -- are out of scope). */
+ * inside groups and across gyms are out of scope; a map in which a source is also a destination -- a chain, a swap, a cycle -- is what mv_resample_envs
+ * below takes). */
 int mv_fork_envs(mv_gym *g, const int32_t *device_src_of);   /* map in device memory, read in the order of the gym's stream */
 int mv_fork_envs_host(mv_gym *g, const int32_t *src_of);     /* map in host memory: validated here, copied, then as above */
 int64_t mv_fork_bytes_per_env(const mv_gym *g);              /* bytes a fork reads and writes per destination (the episode log's included when it is on); -1: no gym */
+/* Resampling (no reference counterpart): a fork map without the fork's restriction.  src_of: int32 [N], read as by mv_fork_envs, and
+ *     new state of env d = the state env src_of[d] had BEFORE the call
+ * for ANY map: chains, swaps, cycles, a source that serves many envs, a source that is overwritten itself -- what a population method (sequential Monte
+ * Carlo, Go-Explore's selection, evolutionary search) does when it resamples N envs from the same N envs.  src_of[d] = -1 or d: env d is left alone.
+ * What moves is the fork's EPISODE STATE, what stays is the fork's IDENTITY (above): after a swap each of the two envs continues the other's episode and,
+ * when that ends, takes the next episode of its OWN sequence.  Not touched, as under a fork: the public rewards / dones / true objectives, the output rings,
+ * the observation slab, pending actions.
+ * How: two launches on one stream.  An env is STAGED when its entry is valid and another valid entry names it as a source: its old state is still needed
+ * while its new one arrives.  Phase 1 reads, for every valid d, env src_of[d] from the live arrays and writes env d's live arrays -- or, where d is staged,
+ * slot d of a staging arena; phase 2 copies every staged env's slot to its live arrays.  No live env that phase 1 reads is written in phase 1 (whoever is
+ * read is named, and a named env with a valid entry is staged), phase 2 touches no other env, and the launch boundary is the barrier.  A map that is a valid
+ * fork map stages nobody and leaves exactly what mv_fork_envs leaves.
+ * Memory: the staging arena holds N x (bytes per env, header and the episode log's accumulators included -- whether the log is on or not, so that switching
+ * it on later needs nothing) plus a byte per env.  The first call on a gym -- either form -- allocates it: that one call may wait on the host inside the
+ * allocator, no later one does.  It is counted in mv_arena_bytes from then on and freed by mv_close.
+ * Ordering: that of mv_fork_envs, word for word.  The call is an ordering point; the copy runs behind every step launch enqueued so far and behind whatever
+ * the caller enqueued on the gym's stream (the kernel that wrote the map -- torch.multinomial, say); the next step launch runs behind the copy.  The device
+ * form runs on the caller's stream, never synchronises with the host and always enqueues both launches; keep the map unchanged until the next stepping call
+ * has been enqueued.  The host form sees the whole plan: a map that leaves every env alone launches nothing, one that stages nobody launches phase 1 alone;
+ * where mv_fork_envs_host may go to the simulation stream, so may it.
+ * Invalid entries: an index that is neither -1 nor 0 .. N - 1, and nothing else.  An invalid entry names nobody.  mv_resample_envs_host: -1 with text,
+ * nothing copied.  The device form skips that entry -- the env stays as it was, and every entry that names that env still receives its pre-call state --
+ * and raises a status bit of its own, which the NEXT stepping call reports once as return 1 with a warning that names mv_resample_envs (that call waits
+ * for the status words, as after mv_fork_envs).
+ * Refused (-1 with text): no gym, a closed gym, before the first mv_reset, a null map, a gym that belongs to an mv_group. */
+int mv_resample_envs(mv_gym *g, const int32_t *device_src_of);   /* map [N] in device memory, read in the order of the gym's stream */
+int mv_resample_envs_host(mv_gym *g, const int32_t *src_of);     /* map [N] in host memory: validated here, copied, then as above */
+int64_t mv_resample_staging_bytes(const mv_gym *g);              /* 0 before the first call; -1: no gym */
 /* Masked resets (no reference counterpart: VectorEnv::reset resets every env, vector_env.cpp:110-120).  mask: one byte per env, [N]; a torch.bool tensor is
  * such a mask.  mask[e] != 0: env e abandons its running episode and takes the NEXT EPISODE OF ITS OWN SEQUENCE -- the one it would have taken had its
  * episode ended at this point: episodes_consumed + 1, its own seed chain, its own ring slot (a fork destination keeps its identity, so this is how it hands
@@ -372,6 +401,15 @@ int mv_debug_episode_log_cut_host(const uint8_t *mask, int32_t N, int32_t A, dou
 /* Host-only (no device): the rule of a fork map (megaverse_amd/csrc/mv_fork.h, the source the kernel and mv_fork_envs_host run) applied to every entry of
  * src_of [N]: resolved[d] = the source env d would continue from, or -1 (left alone, or skipped); invalid[d] = 1 where the entry is invalid. */
 int mv_debug_fork_plan_host(const int32_t *src_of, int32_t N, int32_t *resolved /* [N]: s or -1 */, int32_t *invalid /* [N]: 0/1 */);
+/* Host-only (no device): the rule of a resampling map (megaverse_amd/csrc/mv_fork.h, the source the kernels and mv_resample_envs_host run) applied to every
+ * entry of src_of [N]: resolved[d] = the source whose pre-call state env d takes, or -1 (left alone, or skipped); staged[d] = 1 where env d's new state goes
+ * through the staging arena; invalid[d] = 1 where the entry is out of range.  The tabulated O(N) plan is checked against the per-entry form. */
+int mv_debug_resample_plan_host(const int32_t *src_of, int32_t N, int32_t *resolved /* [N]: s or -1 */, int32_t *staged /* [N]: 0/1 */,
+                                int32_t *invalid /* [N]: 0/1 */);
+/* Host-only (no device): the two phases of mv_resample_envs over state[N][bytes_per_env] in host memory, with a temporary staging array, decided per env by
+ * the code the kernels use; invalid entries are skipped.  order: the envs of each phase are visited ascending (0), descending (1) or in a fixed
+ * pseudo-random order (2) -- the result does not depend on it. */
+int mv_debug_resample_apply_host(const int32_t *src_of, int32_t N, int32_t bytes_per_env, uint8_t *state, int32_t order);
 /* out_host [N]: how many episodes of its own sequence every env has taken so far (a fork leaves the destination's count alone) */
 int mv_debug_episodes_consumed(mv_gym *g, int32_t *out_host);
 int mv_debug_collect_draw_device(int32_t device, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n, float base_episode_len, void *out,

@@ -706,6 +706,8 @@ int mv_close(mv_gym *g)
     if (g->hForkMap) (void)hipHostFree(g->hForkMap);
     for (hipEvent_t &e : g->forkMapCopied) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     g->dForkMap = g->hForkMap = nullptr; g->forkTable = fork::Table{};
+    if (g->resampleArena) (void)hipFree(g->resampleArena);
+    g->resampleArena = nullptr; g->resampleBytes = 0;
     if (g->dResetMask) (void)hipFree(g->dResetMask);
     if (g->hResetMask) (void)hipHostFree(g->hResetMask);
     for (hipEvent_t &e : g->resetMaskCopied) { if (e) (void)hipEventDestroy(e); e = nullptr; }
@@ -896,6 +898,8 @@ int check_status_flags(mv_gym *g)
     if (flags & ST_CHUNK) msg += "an object placement outside the 32 x 16 x 32 voxel chunk was refused (the reference's grid is unbounded); ";
     if (flags & ST_FORK) msg += "mv_fork_envs skipped invalid entries of its map (an index out of range, or a chain of forks: a source that is itself a "
         "destination); those envs were left as they were; ";
+    if (flags & ST_RESAMPLE) msg += "mv_resample_envs skipped entries of its map whose index is out of range (-1, or 0 .. num_envs - 1); those envs were left as "
+        "they were; ";
     if (gen & GEN_SLABS) msg += "a generated layout merged into more slabs than an episode record holds (128, Collect 1024): the excess was dropped; ";
     if (gen & GEN_TERRAIN) msg += "more than 16 terrain boxes in a generated episode; ";
     if (gen & GEN_OBJECTS) msg += "more than 80 movable boxes in a generated episode; ";

@@ -2,7 +2,8 @@
 //   mv_api.hip        create / close, seeding, reset, actions, output rings, getters, reward shaping (MegaverseGym's methods but step)
 //   mv_api_step.hip   stepping: pipelining, batched calls, overlapped passes, groups (union launches), in-stream profiling
 //   mv_api_debug.hip  test hooks: snapshots, pose setters, host-side generators, RNG / arithmetic probes
-//   mv_fork.hip       env forks: the gather-copy kernel and its entry points
+//   mv_fork.hip       env forks: the gather-copy kernel and its entry points; the entry points of env resampling
+//   mv_resample.hip   env resampling: the two kernels of the staged copy
 //   mv_reset_envs.hip masked env resets: the host protocol around the reset_masked kernels (mv_step_kernels.h)
 // The C ABI itself is include/megaverse_hip.h; nothing here is exported under a C name.
 #pragma once
@@ -214,6 +215,10 @@ struct mv_gym {
     int32_t *dForkMap = nullptr, *hForkMap = nullptr;   // [2][N] each
     hipEvent_t forkMapCopied[2] = {nullptr, nullptr};
     unsigned long long forkMapUses = 0;
+    // mv_resample_envs: the staging arena (fork::Staging: a second slice per env of every array of the table, the episode log's included, and one plan byte
+    // per env), allocated at the first call and counted in mv_arena_bytes from then on
+    uint8_t *resampleArena = nullptr;
+    size_t resampleBytes = 0;
     // "the next stepping call waits for the status words" (refill_episodes): something only a kernel saw has to be reported by that call -- a fork's device map
     // may have held invalid entries (ST_FORK), a masked reset from a device mask may have found a host-fed env without a resident episode (ST_STARVED)
     bool statusReportDue = false;

@@ -71,6 +71,47 @@ inline void fork_plan(const int32_t *src_of, int32_t N, int32_t *resolved, std::
     }
 }
 
+// ---- the rule of a RESAMPLING map (include/megaverse_hip.h: mv_resample_envs): new state of env d = the state env src_of[d] had before the call, for ANY
+// map -- chains, swaps, cycles, a source that is overwritten itself.  Entry d is left alone (-1 or d), invalid (an index out of range: that alone), or valid.
+MV_FORK_HD int32_t resample_source(const int32_t *src_of, int32_t N, int32_t d)
+{
+    const int32_t s = src_of[d];
+    if (leaves_alone(s, d)) return LEAVE;
+    return s < 0 || s >= N ? (int32_t)INVALID : s;
+}
+// Env d is STAGED when its entry is valid and another valid entry names d as its source: its old state is still needed while its new one arrives.  ("Another
+// valid entry names d" is named_as_source as it stands: an entry i != d that holds d holds an index in range and does not leave env i alone -- and an invalid
+// entry holds no env's index, so it names nobody.)
+// The copy has two phases, and these two functions are what decides them, for the kernels (mv_resample.hip) and the host hooks alike.  Phase 1, every valid d:
+// env src_of[d]'s LIVE state goes to env d's live arrays (d is not staged: nobody reads them) or to slot d of the staging arena (d is staged).  Phase 2,
+// every staged d: slot d goes to env d's live arrays.  No live env that phase 1 reads is written in phase 1 -- an env that is read is named, and a named
+// env with a valid entry is staged by definition -- and phase 2 touches env d alone.
+enum : int { TO_NOWHERE = 0, TO_LIVE = 1, TO_STAGING = 2 };
+MV_FORK_HD int phase1_target(int32_t resolved, bool named) { return resolved < 0 ? (int)TO_NOWHERE : named ? (int)TO_STAGING : (int)TO_LIVE; }
+MV_FORK_HD bool phase2_copies(int target) { return target == TO_STAGING; }   // (target: what phase 1 left in the env's byte of the plan)
+
+// the whole rule for entry d, one entry at a time (the kernel's form; O(N) per entry on the host) -> phase1_target; resolved: the source, LEAVE or INVALID
+MV_FORK_HD int resample_resolve(const int32_t *src_of, int32_t N, int32_t d, int32_t *resolved)
+{
+    const int32_t s = resample_source(src_of, N, d);
+    *resolved = s;
+    return phase1_target(s, s >= 0 && named_as_source(src_of, N, d, 0, 1));
+}
+
+// ... and for every entry at once in O(N), for the host form: target[d] = phase1_target.  mv_debug_resample_plan_host checks it against resample_resolve.
+inline void resample_plan(const int32_t *src_of, int32_t N, int32_t *resolved, std::vector<uint8_t> &target)
+{
+    target.assign((size_t)(N > 0 ? N : 0), 0);   // (first pass: "named", as in fork_plan)
+    for (int32_t i = 0; i < N; ++i) {
+        const int32_t s = resample_source(src_of, N, i);
+        if (s >= 0) target[(size_t)s] = 1;
+    }
+    for (int32_t d = 0; d < N; ++d) {
+        resolved[d] = resample_source(src_of, N, d);
+        target[(size_t)d] = (uint8_t)phase1_target(resolved[d], target[(size_t)d] != 0);
+    }
+}
+
 // ---- the episode state of one env
 enum : int { MAX_ARRAYS = 16 };
 // A launch covers (destination env) x RANGES ranges of the env's state, THREADS threads each: three envs of a Hex gym (~73 KB each) still make 12
@@ -126,6 +167,41 @@ static_assert(CHUNK_BYTES % 16 == 0 && HM_BYTES % 16 == 0 && (SOKO_DIM * SOKO_DI
 
 // one launch: every valid entry of src_of applied, ST_FORK raised in status[N + 1] for an invalid one (mv_fork.hip)
 void launch_fork(const Table &t, const int32_t *device_src_of, int32_t N, int32_t *status, hipStream_t stream);
+
+// ---- the staging arena of mv_resample_envs: a second home for every staged env's incoming state, laid out like the live arrays -- the header slice [N],
+// then one slice [N][bytes] per array of the table, each from a 16-byte boundary, so that a row of array k has the alignment it has in the live array --
+// and the plan, one byte per env (phase1_target), which phase 1 writes and phase 2 reads.
+struct Staging {
+    EnvHeader *hdr;
+    uint8_t *plan;                 // [N]
+    uint8_t *a[MAX_ARRAYS];        // array k of the table: [N][t.a[k].bytes]
+};
+inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+// bytes of the arena for N envs of table t plus `extra` further bytes per env, each array rounded as above (the episode log's accumulators: the arena is
+// sized once, for a log that may be switched on later)
+inline size_t staging_bytes(const Table &t, int32_t N, size_t extra_a, size_t extra_b)
+{
+    size_t b = round16((size_t)N * sizeof(EnvHeader)) + round16((size_t)N);
+    for (int k = 0; k < t.count; ++k) b += round16((size_t)N * t.a[k].bytes);
+    return b + round16((size_t)N * extra_a) + round16((size_t)N * extra_b);
+}
+inline Staging staging_carve(const Table &t, int32_t N, uint8_t *arena)
+{
+    Staging st{};
+    st.hdr = (EnvHeader *)arena;
+    arena += round16((size_t)N * sizeof(EnvHeader));
+    st.plan = arena;
+    arena += round16((size_t)N);
+    for (int k = 0; k < t.count; ++k) {
+        st.a[k] = arena;
+        arena += round16((size_t)N * t.a[k].bytes);
+    }
+    return st;
+}
+
+// two launches on one stream, the launch boundary between them the barrier: phase 1 (every valid entry: live -> live or staging; the plan bytes; ST_RESAMPLE
+// in status[N + 1] for an invalid entry) and, unless the caller knows that nobody is staged, phase 2 (staging -> live)   (mv_resample.hip)
+void launch_resample(const Table &t, const Staging &st, const int32_t *device_src_of, int32_t N, int32_t *status, bool phase2, hipStream_t stream);
 
 }  // namespace fork
 }  // namespace mv

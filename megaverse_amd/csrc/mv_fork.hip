@@ -1,5 +1,7 @@
 // megaverse_amd/csrc/mv_fork.hip -- env forks: the gather-copy kernel and the C ABI in front of it (include/megaverse_hip.h: mv_fork_envs, mv_fork_envs_host,
-// mv_debug_fork_plan_host).  The rule of a fork map and the table of an env's episode state are mv_fork.h's; DESIGN.md 3.8 says what moves and what stays.
+// mv_debug_fork_plan_host), and the C ABI of env resampling (mv_resample_envs*: any map, through a staged copy in two launches -- the kernels are
+// mv_resample.hip's), which shares the fork's checks, its copy of a host map and its place in the streams' order.  The rules of both maps and the table of an
+// env's episode state are mv_fork.h's; DESIGN.md 3.8 says what moves and what stays.
 #include "mv_api_internal.h"
 
 namespace mv {
@@ -116,9 +118,18 @@ int fork_check(mv_gym *g, const void *map, const char *who)
 // A HOST map depends on nothing the caller enqueued: where the steps are pipelined and nothing on the caller's stream feeds the simulation (no reset, render or
 // setter since the last step; no episode log, whose accumulators are the caller's stream's), map and copy go to the SIMULATION stream itself, in order
 // between the step launches -- the passes of the last call are not waited for, and the next call pipelines as if nothing had happened.
-int fork_launch(mv_gym *g, const int32_t *device_map, const int32_t *host_map)
+// mv_resample_envs takes the same path with its own launches (RESAMPLE: both phases; RESAMPLE_UNSTAGED: the host form saw that no env is staged); its first
+// call allocates the staging arena, sized for the episode log whether it is on or not, so that switching it on later changes nothing here.
+enum LaunchKind { FORK, RESAMPLE, RESAMPLE_UNSTAGED };
+int fork_launch(mv_gym *g, const int32_t *device_map, const int32_t *host_map, LaunchKind kind = FORK)
 {
     HIP_TRY(hipSetDevice(g->device));
+    if (kind != FORK && !g->resampleArena) {
+        const size_t bytes = fork::staging_bytes(g->forkTable, g->N, (size_t)g->A * sizeof(double), sizeof(int32_t));
+        hipError_t e_ = hipMalloc((void **)&g->resampleArena, bytes);
+        if (e_ != hipSuccess) { g->resampleArena = nullptr; return fail("mv_resample_envs: hipMalloc of " + std::to_string(bytes) + " bytes of staging: " + hipGetErrorString(e_)); }
+        g->resampleBytes = bytes;
+    }
     const bool onSim = host_map && g->pipelined && g->simOnOwnStream && g->simDoneValid && !g->simMustWaitUser && g->logCapacity == 0;
     hipStream_t s = onSim ? g->simStream : g->stream;
     if (!onSim && sim_join(g)) return -1;
@@ -144,13 +155,14 @@ int fork_launch(mv_gym *g, const int32_t *device_map, const int32_t *host_map)
         fork::table_add(t, g->logRet, (size_t)g->A * sizeof(double));
         fork::table_add(t, g->logLen, sizeof(int32_t));
     }
-    fork::launch_fork(t, device_map, g->N, g->dStatus, s);
+    if (kind == FORK) fork::launch_fork(t, device_map, g->N, g->dStatus, s);
+    else fork::launch_resample(t, fork::staging_carve(t, g->N, g->resampleArena), device_map, g->N, g->dStatus, kind == RESAMPLE, s);
     HIP_TRY(hipGetLastError());
     if (host_map) HIP_TRY(hipEventRecord(g->forkMapCopied[(int)((g->forkMapUses - 1) & 1ull)], s));
     if (onSim) HIP_TRY(hipEventRecord(g->simDone, s));   // (what the caller's stream, a reset or a render waits for: now behind the copy)
     if (!host_map) {
         // Only the kernel knows whether it skipped an entry.  The status words travel back behind it, and the next stepping call waits for them
-        // (refill_episodes), so that it is that call which reports ST_FORK: a host wait there, none here.
+        // (refill_episodes), so that it is that call which reports ST_FORK / ST_RESAMPLE: a host wait there, none here.
         HIP_TRY(hipEventRecord(g->userNow, g->stream));
         if (read_back_status(g, g->userNow)) return -1;
         g->statusReportDue = true;
@@ -227,6 +239,82 @@ int mv_fork_envs_host(mv_gym *g, const int32_t *src_of)
     }
     if (!any) return 0;
     return fork_launch(g, nullptr, src_of);
+}
+
+int mv_debug_resample_plan_host(const int32_t *src_of, int32_t N, int32_t *resolved, int32_t *staged, int32_t *invalid)
+{
+    if (!src_of || N < 0 || !resolved || !staged || !invalid) return fail("mv_debug_resample_plan_host: null argument");
+    std::vector<int32_t> plan((size_t)N);
+    std::vector<uint8_t> target;
+    fork::resample_plan(src_of, N, plan.data(), target);   // (the host form's tabulated rule)
+    for (int32_t d = 0; d < N; ++d) {
+        int32_t s = 0;
+        const int tgt = fork::resample_resolve(src_of, N, d, &s);   // (the kernel's)
+        if (s != plan[(size_t)d] || tgt != (int)target[(size_t)d])
+            return fail("mv_debug_resample_plan_host: resample_plan and resample_resolve disagree on entry " + std::to_string(d));
+        resolved[d] = s >= 0 ? s : -1;
+        staged[d] = fork::phase2_copies(tgt) ? 1 : 0;
+        invalid[d] = s == fork::INVALID ? 1 : 0;
+    }
+    return 0;
+}
+
+// The two phases over a host byte array, one "env" of bytes_per_env bytes after the other, with a temporary staging array and plan: where phase 1 writes and
+// what phase 2 copies is decided by the functions the kernels use (mv_fork.h: resample_resolve -> phase1_target, phase2_copies).  The envs of each phase are
+// visited in ascending (0), descending (1) or a fixed pseudo-random (2) order: the phases' hazard argument says the result cannot depend on it.
+int mv_debug_resample_apply_host(const int32_t *src_of, int32_t N, int32_t bytes_per_env, uint8_t *state, int32_t order)
+{
+    if (!src_of || N < 0 || bytes_per_env < 0 || !state) return fail("mv_debug_resample_apply_host: null argument");
+    if (order < 0 || order > 2) return fail("mv_debug_resample_apply_host: order is 0 (ascending), 1 (descending) or 2 (pseudo-random)");
+    std::vector<int32_t> visit((size_t)N);
+    for (int32_t i = 0; i < N; ++i) visit[(size_t)i] = order == 1 ? N - 1 - i : i;
+    if (order == 2) {
+        uint32_t x = 0x9E3779B9u;
+        for (int32_t i = N - 1; i > 0; --i) {   // Fisher-Yates with a fixed LCG
+            x = x * 1664525u + 1013904223u;
+            std::swap(visit[(size_t)i], visit[(size_t)((x >> 8) % (uint32_t)(i + 1))]);
+        }
+    }
+    const size_t B = (size_t)bytes_per_env;
+    std::vector<uint8_t> staging((size_t)N * B), plan((size_t)N, (uint8_t)fork::TO_NOWHERE);
+    for (int32_t d : visit) {   // phase 1
+        int32_t s = 0;
+        const int tgt = fork::resample_resolve(src_of, N, d, &s);
+        plan[(size_t)d] = (uint8_t)tgt;
+        if (tgt == fork::TO_NOWHERE) continue;
+        std::memcpy((tgt == fork::TO_STAGING ? staging.data() : state) + (size_t)d * B, state + (size_t)s * B, B);
+    }
+    for (int32_t d : visit)     // phase 2
+        if (fork::phase2_copies(plan[(size_t)d])) std::memcpy(state + (size_t)d * B, staging.data() + (size_t)d * B, B);
+    return 0;
+}
+
+int64_t mv_resample_staging_bytes(const mv_gym *g) { return !g || g->closed ? -1 : (int64_t)g->resampleBytes; }
+
+int mv_resample_envs(mv_gym *g, const int32_t *device_src_of)
+{
+    if (fork_check(g, device_src_of, "mv_resample_envs")) return -1;
+    return fork_launch(g, device_src_of, nullptr, RESAMPLE);
+}
+
+int mv_resample_envs_host(mv_gym *g, const int32_t *src_of)
+{
+    if (fork_check(g, src_of, "mv_resample_envs_host")) return -1;
+    const int32_t N = g->N;
+    bool any = false, staged = false;
+    static thread_local std::vector<int32_t> plan;
+    static thread_local std::vector<uint8_t> target;
+    plan.resize((size_t)N);
+    fork::resample_plan(src_of, N, plan.data(), target);
+    for (int32_t d = 0; d < N; ++d) {
+        if (plan[(size_t)d] == fork::INVALID)
+            return fail("mv_resample_envs_host: entry " + std::to_string(d) + " = " + std::to_string(src_of[d]) + " is out of range (-1, or 0 .. "
+                        + std::to_string(N - 1) + "); nothing was copied");
+        any = any || plan[(size_t)d] >= 0;
+        staged = staged || fork::phase2_copies(target[(size_t)d]);
+    }
+    if (!any) return 0;
+    return fork_launch(g, nullptr, src_of, staged ? RESAMPLE : RESAMPLE_UNSTAGED);
 }
 
 }  // extern "C"

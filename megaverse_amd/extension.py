@@ -43,6 +43,8 @@ SYMBOLS = [
     ("mv_set_action_ring", C.c_int, [_P, _I, _P]), ("mv_debug_launch_counts", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("mv_fork_envs", C.c_int, [_P, _P]), ("mv_fork_envs_host", C.c_int, [_P, _P]), ("mv_debug_fork_plan_host", C.c_int, [_P, _I, _P, _P]),
     ("mv_debug_episodes_consumed", C.c_int, [_P, _P]), ("mv_fork_bytes_per_env", C.c_int64, [_P]),
+    ("mv_resample_envs", C.c_int, [_P, _P]), ("mv_resample_envs_host", C.c_int, [_P, _P]), ("mv_resample_staging_bytes", C.c_int64, [_P]),
+    ("mv_debug_resample_plan_host", C.c_int, [_P, _I, _P, _P, _P]), ("mv_debug_resample_apply_host", C.c_int, [_P, _I, _I, _P, _I]),
     ("mv_reset_envs", C.c_int, [_P, _P, _I]), ("mv_reset_envs_host", C.c_int, [_P, _P, _I]), ("mv_debug_episode_log_cut_host", C.c_int, [_P, _I, _I, _P, _P]),
     ("mv_set_output_ring", C.c_int, [_P, _I, _P, _P, _P]),
     ("mv_set_pass_overlap", C.c_int, [_P, _I]),
@@ -129,6 +131,31 @@ def debug_fork_plan_host(src_of):
     if m.size and lib.mv_debug_fork_plan_host(m.ctypes.data, m.size, resolved.ctypes.data, invalid.ctypes.data) != 0:
         raise RuntimeError(lib.mv_last_error().decode())
     return resolved, invalid
+
+
+def debug_resample_plan_host(src_of):
+    """mv_debug_resample_plan_host: the rule of a resampling map on the CPU (no device) -> (resolved int32 [N]: the source of entry d, or -1; staged [N]: 1
+    where env d's new state goes through the staging arena; invalid [N]: 1 where the index is out of range)"""
+    lib = load_library()
+    m = np.ascontiguousarray(src_of, np.int32).reshape(-1)
+    resolved, staged, invalid = (np.full(m.size, -9, np.int32) for _ in range(3))
+    if m.size and lib.mv_debug_resample_plan_host(m.ctypes.data, m.size, resolved.ctypes.data, staged.ctypes.data, invalid.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return resolved, staged, invalid
+
+
+def debug_resample_apply_host(src_of, state, order=0):
+    """mv_debug_resample_apply_host: the two phases of mv_resample_envs on the CPU (no device) over state, a uint8 array [N][bytes per env] -> the state
+    after the call (a copy).  order: 0 / 1 / 2 = the envs of each phase ascending / descending / in a fixed pseudo-random order."""
+    lib = load_library()
+    m = np.ascontiguousarray(src_of, np.int32).reshape(-1)
+    state = np.asarray(state)
+    if state.dtype != np.uint8 or state.ndim != 2 or state.shape[0] != m.size:
+        raise ValueError("debug_resample_apply_host: state is a uint8 array [N][bytes per env], N the length of the map")
+    out = np.array(state, order="C", copy=True)   # (never None for ctypes, even where it is empty)
+    if m.size and lib.mv_debug_resample_apply_host(m.ctypes.data, m.size, out.shape[1], out.ctypes.data, int(order)) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
 
 
 def check_fork_map(src_of, num_envs):
@@ -401,6 +428,25 @@ class MegaverseGym:
             self._fork_held = src_of
         else:
             self._ck(self._lib.mv_fork_envs_host(self._g, m.ctypes.data))
+
+    def resample_envs(self, src_of):
+        """Resampling (include/megaverse_hip.h: mv_resample_envs): env d's new state is the state env src_of[d] had before the call, for any map -- chains,
+        swaps, cycles, a source that is overwritten itself; -1 or d leaves env d alone.  Every env keeps its own seed chain and resident next episodes.  The
+        argument is fork_envs': a contiguous int32 CUDA tensor of shape (num_envs,) is read in place, in the order of the gym's stream, without a host
+        synchronisation (it is held until the next step; an index out of range is skipped and reported by the next stepping call as a warning); a numpy
+        array or a sequence is validated on the host first (RuntimeError, nothing copied)."""
+        m = check_fork_map(src_of, self.num_envs)
+        if isinstance(m, str):
+            self._ck(self._lib.mv_resample_envs(self._g, _P(int(src_of.data_ptr()))))
+            held = self._fork_held if isinstance(self._fork_held, list) else [self._fork_held]
+            held.append(src_of)   # (calls may follow each other without a step: every map is kept)
+            self._fork_held = held
+        else:
+            self._ck(self._lib.mv_resample_envs_host(self._g, m.ctypes.data))
+
+    def resample_staging_bytes(self):
+        """bytes of resample_envs' staging arena: 0 before the first call"""
+        return int(self._lib.mv_resample_staging_bytes(self._g))
 
     def reset_envs(self, mask, render=True):
         """Masked resets (include/megaverse_hip.h: mv_reset_envs): every env whose mask entry is set abandons its running episode and takes the next episode

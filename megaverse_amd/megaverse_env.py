@@ -251,6 +251,21 @@ class MegaverseEnv:
         m[src_env] = -1
         self.env.fork_envs(m)
 
+    def resample(self, src_of):
+        """every env d continues from the state env src_of[d] had before the call (MegaverseGym.resample_envs): any map of num_envs entries -- chains,
+        swaps, cycles, sources that are overwritten themselves; -1 or d leaves env d alone.  The resampling step of a population method: a CUDA int32
+        tensor (the output of torch.multinomial, cast) is applied without a host synchronisation.  Envs keep their own next episodes; outputs are untouched."""
+        self.env.resample_envs(src_of)
+
+    def swap(self, a, b):
+        """envs a and b exchange their running episodes (resample with the two-entry map); each keeps its own next episodes"""
+        a, b = int(a), int(b)
+        if not (0 <= a < self.num_envs and 0 <= b < self.num_envs):
+            raise ValueError(f'swap: envs must be within 0 .. {self.num_envs - 1}, got {a}, {b}')
+        m = np.full(self.num_envs, -1, np.int32)
+        m[a], m[b] = b, a
+        self.env.resample_envs(m)
+
     def reset_envs(self, env_ids, render=True):
         """the envs of env_ids abandon their running episode and start the next one of their own sequence (MegaverseGym.reset_envs with the mask built
         here); the others are untouched.  What a learner's own time limit, a curriculum, or a planner handing its fork destinations back needs.  With render
