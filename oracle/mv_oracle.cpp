@@ -83,7 +83,7 @@ enum { CX = 32, CY = 16, CZ = 32, CHUNK = CX * CY * CZ };
 enum { MAX_BOXES = 1024, MAX_OBJECTS = 80, MAX_AGENTS = 8, MAX_TERRAIN = 16, MAX_REWARDS = 96, MAX_SHAPING = 8 };
 enum { HM_DIM = 42 };   // Collect heightfield: maxWidth == maxLength == 42 (scenario_collect.cpp:63)
 enum { SCN_TOWER = 0, SCN_OBSTACLES = 1, SCN_COLLECT = 2, SCN_REARRANGE = 3, SCN_SOKOBAN = 4, SCN_EMPTY = 5, SCN_HEX_MEMORY = 6, SCN_HEX_EXPLORE = 7,
-       SCN_BOX_A_GONE = 8 };
+       SCN_BOX_A_GONE = 8, SCN_FOOTBALL = 9 };
 enum { HEX_MAX_BOXES = 2048, HEX_MAX_OBJS = 128, HEX_FRAMES = 3 };   // Hex*: float boxes (floor, walls, edgings, landmarks), collectables
 enum { HEX_PILLAR = 0, HEX_DIAMOND = 1, HEX_SPHERE = 2 };            // scenario_hex_memory.cpp:163-168 ShapeType
 enum { SOKO_DIM = 32, SOKO_WALL = 1, SOKO_GOAL = 2 };   // Sokoban level cells (scenario_sokoban.cpp:28-33), levels up to 32 x 32
@@ -277,6 +277,10 @@ struct Env {
     std::map<std::tuple<int, int, int>, int> bagGrid;               // vg.grid's voxels that hold a disappearing platform
     int bagLast[MAX_AGENTS];                                        // AgentState::lastPlatform (-1: nullptr)
     float bagSecBefore[MAX_AGENTS];                                 // AgentState::secondsBeforeTouchedFloor
+    // Football (scenario_football.{hpp,cpp}): hexBoxes holds the room's boxes (world frame, voxel size 1), hexObjs[0] is the ball's drawable, rewritten
+    // from `ball` after every change.  The ball is the stated model of DESIGN.md section 7, not Bullet's bits.
+    struct Ball { V3 pos, vel, ang, force; float radius; int kicks, contacts; };   // radius: the DRAWN one (0.5 until the first tick); contacts:
+    Ball ball = Ball{V3{0, 0, 0}, V3{0, 0, 0}, V3{0, 0, 0}, V3{0, 0, 0}, 0.0f, 0, 0};   // capsule j -> bit j, room box k -> bit 8 + k, this tick
     // Collect: numPlatforms holds numPositiveRewards, highestTower holds positiveRewardsCollected (scenario_collect.hpp:76)
     std::vector<int8_t> heightmap = std::vector<int8_t>(HM_DIM * HM_DIM, -1);   // [x * HM_DIM + z]: top solid y of the column, -1 = no voxels
     TerrainBox terrain[MAX_TERRAIN];
@@ -1732,6 +1736,69 @@ static void boxagone_generate(Env &e)
     e.episodeLen = e.p_episodeLengthSec;
 }
 
+// Football -- scenario_football.{hpp,cpp}.  The ball: btSphereShape(2.0) on an Object3D scaled by 0.5 at (5, 5, 5) (cpp:117-122); collision radius 1.
+static const float FB_BALL_R = 1.0f;
+static const unsigned COLOR_ORANGE = 0xffb400;   // const.hpp:25-56
+
+// the ball's drawable (DrawableType::Sphere, cpp:140): hexObjs[0] from the ball's pose and drawn radius
+static void football_sync_ball(Env &e)
+{
+    Env::HexObj o;
+    o.pos = e.ball.pos; o.scale = v3(e.ball.radius, e.ball.radius, e.ball.radius);
+    o.shape = HEX_SPHERE; o.good = 0; o.alive = 0; o.color = COLOR_ORANGE; o.vox[0] = o.vox[1] = o.vox[2] = 0;
+    e.hexObjs.assign(1, o);
+}
+
+// FootballScenario::reset (cpp:112-129) + spawnAgents (scenario_default.hpp:80-97) + addEpisodeDrawables (cpp:136-141)
+static void football_generate(Env &e)
+{
+    hex_common_reset(e);
+    // the ball is created first (it draws nothing from the stream): at rest, nothing pending; its Object3D still carries the 0.5 scale
+    e.ball = Env::Ball{v3(5.0f, 5.0f, 5.0f), v3(0, 0, 0), v3(0, 0, 0), v3(0, 0, 0), 0.5f, 0, 0};
+
+    // FootballLayout::init (cpp:15-22): length, width (EmptyPlatform leaves it -1), height; generate() = addFloor + addWalls, WALLS_ALL
+    // (platforms.hpp:167-190); vg.addPlatform(..., true): every voxel solid + opaque in LAYOUT_DEFAULT, merged like every layout
+    const int L = randRange(14, 24, e.rng);
+    const int W = randRange(12, 24, e.rng);
+    const int H = randRange(3, 7, e.rng);
+    fill_box(e, 0, 0, 0, L, 1, W, VX_SOLID | VX_OPAQUE);           // floor
+    fill_box(e, 0, 0, 0, 1, H, W, VX_SOLID | VX_OPAQUE);           // WALLS_SOUTH
+    fill_box(e, L - 1, 0, 0, L, H, W, VX_SOLID | VX_OPAQUE);       // WALLS_NORTH
+    fill_box(e, 0, 0, 0, L, H, 1, VX_SOLID | VX_OPAQUE);           // WALLS_EAST
+    fill_box(e, 0, 0, W - 1, L, H, W, VX_SOLID | VX_OPAQUE);       // WALLS_WEST
+    merge_boxes(e);
+    for (int i = 0; i < e.numBoxes; ++i) {   // addDrawablesAndCollisionObjectsFromVoxelGrid(vg, ..., 1): voxel size 1
+        const Box &b = e.boxes[i];
+        Env::HexBox hb; hb.frame = -1; hb.collide = 1; hb.color = COLOR_LAYOUT_DEFAULT;
+        hb.lo = v3(float(b.min[0]), float(b.min[1]), float(b.min[2]));
+        hb.hi = v3(float(b.max[0]), float(b.max[1]), float(b.max[2]));
+        e.hexBoxes.push_back(hb);
+    }
+    e.numBoxes = 0;   // (the room lives in hexBoxes; the chunk only served the merge)
+    std::fill(e.chunk.begin(), e.chunk.end(), 0);
+    e.L = L; e.H = H; e.W = W;
+    e.layoutColor = COLOR_LAYOUT_DEFAULT; e.wallColor = COLOR_LAYOUT_DEFAULT; e.drawWalls = 1;
+
+    // Platform::agentSpawnPoints (platforms.hpp:221-244): ten draws of a free column per agent, y = occupancy (0) + 1
+    std::vector<C3> spawns;
+    std::set<std::pair<int, int>> used;
+    for (int i = 0; i < e.numAgents; ++i)
+        for (int attempt = 0; attempt < 10; ++attempt) {
+            const int x = randRange(1, L - 1, e.rng);
+            const int z = randRange(1, W - 1, e.rng);
+            if (used.count({x, z})) continue;
+            used.insert({x, z});
+            spawns.push_back(C3{x, 1, z});
+            break;
+        }
+    // (an agent left without a point -- ten taken columns in a row -- would index past the reference's vector; the first agent's point instead)
+    if (spawns.empty()) spawns.push_back(C3{1, 1, 1});
+    spawn_agents(e, spawns);   // one frand per agent
+
+    football_sync_ball(e);
+    e.episodeLen = e.p_episodeLengthSec;
+}
+
 static void env_reset(Env &e)
 {
     // ---- Env::reset, env/src/env.cpp:57-76 ; EnvState::reset env.hpp:135-151
@@ -1746,6 +1813,7 @@ static void env_reset(Env &e)
     else if (e.scenario == SCN_HEX_MEMORY) hex_memory_generate(e, uint32_t(seed));
     else if (e.scenario == SCN_HEX_EXPLORE) hex_explore_generate(e, uint32_t(seed));
     else if (e.scenario == SCN_BOX_A_GONE) boxagone_generate(e);
+    else if (e.scenario == SCN_FOOTBALL) football_generate(e);
     else sokoban_generate(e);
 }
 
@@ -1754,9 +1822,11 @@ static void env_reset(Env &e)
 // axis-aligned box == the capsule CENTRE against the box grown by CAP_HH in +-y, rounded by r.
 // ------------------------------------------------------------------------------------------------
 struct Collider {
-    int kind;    // 0 none, 1 box (lo/hi already grown in y by CAP_HH), 2 vertical capsule (other agent), 3 box in hex wall frame `frame`
+    int kind;    // 0 none, 1 box (lo/hi already grown in y by CAP_HH), 2 vertical capsule (other agent), 3 box in hex wall frame `frame`,
+                 // 4 sphere (Football's ball)
     int frame;
-    V3 lo, hi;   // box bounds; capsule: lo = centre, hi.x = segment half-length
+    V3 lo, hi;   // box bounds; capsule: lo = centre, hi.x = segment half-length; sphere: lo = centre, hi.x = CAP_HH, hi.y = CAP_R + its radius
+                 // (the capsule's Minkowski sum with it: the capsule's CENTRE against a vertical segment through the sphere's centre)
 };
 
 struct Closest {
@@ -1817,6 +1887,7 @@ static Closest closest(const Collider &col, V3 p, float rBox, float rCap)
         c.n = hex_to_world(col.frame, c.n);
         return c;
     }
+    if (col.kind == 4) return closest_capsule(p, col.lo, col.hi.x, col.hi.y);
     return closest_capsule(p, col.lo, col.hi.x, rCap);
 }
 
@@ -1880,11 +1951,12 @@ static Raw raw_capsule(V3 p, V3 centre, float halfLen, float r)
 // normal rotated back once).  megaverse_amd/csrc/mv_physics.h: convex_cast is the same arithmetic, operation for operation.
 static bool convex_cast(const Collider &col, V3 p, V3 d, float *fraction, V3 *normal)
 {
-    const bool boxLike = col.kind != 2;
+    const bool boxLike = col.kind != 2 && col.kind != 4;
+    const float capR = col.kind == 4 ? col.hi.y : 2 * CAP_R;   // summed radii: another agent's capsule / the ball
     if (col.kind == 3) { p = hex_to_local(col.frame, p); d = hex_to_local(col.frame, d); }
     float lambda = 0.0f, lastLambda = 0.0f;
     int numIter = 0;
-    Raw c = boxLike ? raw_box(p, col.lo, col.hi, CAP_R) : raw_capsule(p, col.lo, col.hi.x, 2 * CAP_R);
+    Raw c = boxLike ? raw_box(p, col.lo, col.hi, CAP_R) : raw_capsule(p, col.lo, col.hi.x, capR);
     float dist = c.dist + ALLOWED_CCD_PEN;
     float proj = -dot(d, c.v);   // |v| times Bullet's projected velocity
     if (proj <= SIMD_EPS * c.d) return false;
@@ -1897,7 +1969,7 @@ static bool convex_cast(const Collider &col, V3 p, V3 d, float *fraction, V3 *no
         if (lambda <= lastLambda) return false;
         lastLambda = lambda;
         const V3 x = v3(p.x + lambda * d.x, p.y + lambda * d.y, p.z + lambda * d.z);
-        c = boxLike ? raw_box(x, col.lo, col.hi, CAP_R) : raw_capsule(x, col.lo, col.hi.x, 2 * CAP_R);
+        c = boxLike ? raw_box(x, col.lo, col.hi, CAP_R) : raw_capsule(x, col.lo, col.hi.x, capR);
         dist = c.dist + ALLOWED_CCD_PEN;
         if (++numIter > CAST_MAX_ITER) return false;
     }
@@ -1932,9 +2004,33 @@ static V3 item_collision_half(int shape)
 }
 
 // Collider order == index order used for tie-breaks: layout boxes, (Rearrange: static boxes, target items), movable boxes, agents.
+// Football: the ball, the agents, the room's boxes.
 static void build_colliders(const Env &e, int self, Colliders &out)
 {
     out.n = 0;
+    if (e.scenario == SCN_FOOTBALL) {
+        // Football is the one scenario whose agents do not come last.  Env::reset's object order: the ball (FootballScenario::reset), the agents
+        // (spawnAgents), the room's boxes (addEpisodeDrawables) -- it decides sweep ties and which penetration is recovered first
+        Collider &b = out.c[out.n++];
+        b.kind = 4; b.frame = -1;
+        b.lo = e.ball.pos;
+        b.hi = v3(CAP_HH, CAP_R + FB_BALL_R, 0);
+        for (int i = 0; i < e.numAgents; ++i) {
+            if (i == self) continue;
+            Collider &c = out.c[out.n++];
+            c.kind = 2; c.frame = -1;
+            c.lo = e.agents[i].pos;
+            c.hi = v3(2 * CAP_HH, 0, 0);
+        }
+        for (const Env::HexBox &hb : e.hexBoxes) {
+            if (!hb.collide) continue;
+            Collider &c = out.c[out.n++];
+            c.kind = 1; c.frame = -1;
+            c.lo = v3(hb.lo.x, hb.lo.y - CAP_HH, hb.lo.z);
+            c.hi = v3(hb.hi.x, hb.hi.y + CAP_HH, hb.hi.z);
+        }
+        return;
+    }
     for (int i = 0; i < e.numBoxes; ++i) {
         if (!(e.boxes[i].type & VX_SOLID)) continue;  // layout_utils.cpp:42-49
         Collider &c = out.c[out.n++];
@@ -2475,6 +2571,152 @@ static float boxagone_true_objective(const Env &e, int agentIdx)
     return e.bagSecBefore[agentIdx] / e.p_episodeLengthSec;   // episodeLengthSec(): the float parameter
 }
 
+// ---- Football's ball: the STATED sequential-impulse model of DESIGN.md section 7 (one sphere, mass 1, among fixed bodies), in place of
+// btDiscreteDynamicsWorld::stepSimulation [3P], which is not restated bit for bit.  Constants: Bullet 2.89's defaults as the reference leaves them.
+static const float FB_GRAVITY_Y = -10.0f;                 // btDiscreteDynamicsWorld's default gravity (0, -10, 0)
+static const float FB_INERTIA = 1.6f;                     // 2/5 m r^2 at the unscaled radius 2 (calculateLocalInertia runs before syncPose scales)
+static const float FB_INV_INERTIA = 1.0f / FB_INERTIA;
+static const float FB_FRICTION = 0.5f * 0.5f;             // ball 0.5 (cpp:42) x box / capsule 0.5
+static const float FB_ROLLING = 0.1f * 0.5f, FB_SPINNING = 0.1f * 0.5f;   // cpp:43-44 x the other body's friction
+static const float FB_BREAKING = 0.02f;                   // gContactBreakingThreshold
+static const float FB_ERP = 0.2f, FB_ERP2 = 0.8f, FB_SPLIT_THRESHOLD = -0.04f;   // btContactSolverInfo
+static const int FB_ITERATIONS = 10;                      // m_numIterations
+static const float FB_SQRT12 = 0.7071067811865475244f;    // SIMDSQRT12
+static const float FB_KICK_DIST = 1.8f, FB_KICK_FORCE = 70.0f;   // scenario_football.cpp:154-157
+
+static V3 cross3(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+
+struct FbContact {
+    V3 n;                 // unit normal from the other body to the ball
+    float gap;            // signed distance at the start pose
+    V3 slipDir, armXslip; // the friction direction and (contact arm) x (friction direction); the arm is -n (radius 1)
+    V3 roll1, roll2;      // btPlaneSpace1(n)
+    float frictionMass;   // 1 / (1/m + |arm x dir|^2 / I)
+    float target, pushTarget;   // velocity along n the normal row / the split-impulse row asks for
+    float normalImp = 0, frictionImp = 0, pushImp = 0, rollImp[3] = {0, 0, 0};   // accumulated
+};
+
+static void fb_plane_space(V3 n, V3 *p, V3 *q)
+{   // [3P] btPlaneSpace1
+    if (fabsf(n.z) > FB_SQRT12) {
+        const float a = n.y * n.y + n.z * n.z, k = 1.0f / sqrtf(a);
+        *p = v3(0.0f, -n.z * k, n.y * k);
+        *q = v3(a * k, -n.x * p->z, n.x * p->y);
+    } else {
+        const float a = n.x * n.x + n.y * n.y, k = 1.0f / sqrtf(a);
+        *p = v3(-n.y * k, n.x * k, 0.0f);
+        *q = v3(-n.z * p->y, n.z * p->x, a * k);
+    }
+}
+
+static FbContact fb_contact(const Raw &r, V3 v, V3 w)
+{
+    FbContact c;
+    c.n = r.v * (1.0f / r.d);
+    c.gap = r.dist;
+    const V3 arm = v3(-c.n.x, -c.n.y, -c.n.z);
+    const V3 pointVel = v + cross3(w, arm);
+    const V3 slip = pointVel - c.n * dot(c.n, pointVel);
+    const float slip2 = len2(slip);
+    fb_plane_space(c.n, &c.roll1, &c.roll2);
+    c.slipDir = slip2 > FLT_EPSILON ? slip * (1.0f / sqrtf(slip2)) : c.roll1;
+    c.armXslip = cross3(arm, c.slipDir);
+    c.frictionMass = 1.0f / (1.0f + FB_INV_INERTIA * len2(c.armXslip));
+    // a gap allows an approach of gap / dt; a shallow penetration is recovered in the velocity at ERP, a deep one by the split push at ERP2
+    if (c.gap > 0.0f) c.target = -c.gap / DT;
+    else if (c.gap > FB_SPLIT_THRESHOLD) c.target = -c.gap * FB_ERP / DT;
+    else c.target = 0.0f;
+    c.pushTarget = c.gap > FB_SPLIT_THRESHOLD ? 0.0f : -c.gap * FB_ERP2 / DT;
+    return c;
+}
+
+static float fb_clamp(float x, float lim) { return std::min(std::max(x, -lim), lim); }
+
+// one tick of the ball, before the controllers: the agents are where the previous tick left them
+static void football_ball_step(Env &e)
+{
+    Env::Ball &b = e.ball;
+    // 1. v += dt (g + F / m), F = 0
+    V3 v = v3(b.vel.x + (b.force.x + 0.0f) * DT, b.vel.y + (b.force.y + FB_GRAVITY_Y) * DT, b.vel.z + (b.force.z + 0.0f) * DT);
+    V3 w = b.ang;
+    b.force = v3(0, 0, 0);
+    // 2. contacts at the start pose: every agent's capsule, then every room box
+    const V3 start = b.pos;
+    std::vector<FbContact> contacts;
+    int bits = 0;
+    for (int j = 0; j < e.numAgents; ++j) {
+        const Raw r = raw_capsule(start, e.agents[j].pos, CAP_HH, FB_BALL_R + CAP_R);
+        if (r.dist <= FB_BREAKING) { contacts.push_back(fb_contact(r, v, w)); bits |= 1 << j; }
+    }
+    for (size_t k = 0; k < e.hexBoxes.size(); ++k) {
+        const Raw r = raw_box(start, e.hexBoxes[k].lo, e.hexBoxes[k].hi, FB_BALL_R);
+        if (r.dist <= FB_BREAKING) { contacts.push_back(fb_contact(r, v, w)); bits |= 1 << (8 + int(k)); }
+    }
+    // 3. the solver: per iteration every normal row, then every friction row, then every spinning / rolling row
+    for (int it = 0; it < FB_ITERATIONS; ++it) {
+        for (FbContact &c : contacts) {
+            const float total = std::max(c.normalImp + (c.target - dot(c.n, v)), 0.0f);
+            const float applied = total - c.normalImp;
+            c.normalImp = total;
+            v = v + c.n * applied;
+        }
+        for (FbContact &c : contacts) {
+            if (!(c.normalImp > 0.0f)) continue;
+            const float slipSpeed = dot(c.slipDir, v) + dot(c.armXslip, w);
+            const float total = fb_clamp(c.frictionImp + (0.0f - slipSpeed * c.frictionMass), FB_FRICTION * c.normalImp);
+            const float applied = total - c.frictionImp;
+            c.frictionImp = total;
+            v = v + c.slipDir * applied;
+            w = w + c.armXslip * (FB_INV_INERTIA * applied);
+        }
+        for (FbContact &c : contacts) {
+            if (!(c.normalImp > 0.0f)) continue;
+            const V3 axes[3] = {c.n, c.roll1, c.roll2};
+            for (int a = 0; a < 3; ++a) {
+                const float mu = a == 0 ? FB_SPINNING : FB_ROLLING;
+                const float lim = std::min(mu * c.normalImp, mu);
+                const float total = fb_clamp(c.rollImp[a] + (0.0f - dot(axes[a], w) * FB_INERTIA), lim);
+                const float applied = total - c.rollImp[a];
+                c.rollImp[a] = total;
+                w = w + axes[a] * (FB_INV_INERTIA * applied);
+            }
+        }
+    }
+    V3 push = v3(0, 0, 0);   // split impulse: position only
+    for (int it = 0; it < FB_ITERATIONS; ++it)
+        for (FbContact &c : contacts) {
+            if (!(c.pushTarget > 0.0f)) continue;
+            const float total = std::max(c.pushImp + (c.pushTarget - dot(c.n, push)), 0.0f);
+            const float applied = total - c.pushImp;
+            c.pushImp = total;
+            push = push + c.n * applied;
+        }
+    // 4. p += dt (v_push + v)
+    b.pos = v3((start.x + push.x * DT) + v.x * DT, (start.y + push.y * DT) + v.y * DT, (start.z + push.z * DT) + v.z * DT);
+    b.vel = v; b.ang = w;
+    b.contacts = bits;
+    b.radius = FB_BALL_R;   // MotionState::setWorldTransform rebuilds the drawable's transformation without the 0.5 scale
+}
+
+// FootballScenario::step, scenario_football.cpp:143-163: applyForce accumulates; the world integrates and clears it in the next tick
+static void football_kicks(Env &e)
+{
+    int kicks = 0;
+    for (int i = 0; i < e.numAgents; ++i) {
+        if (!(e.agents[i].action & (1 << 8))) continue;
+        const V3 t = v3(e.agents[i].pos.x, e.agents[i].pos.y + 0.05f, e.agents[i].pos.z);   // transformation().translation()
+        const V3 d = e.ball.pos - t;
+        const float len = sqrtf(len2(d));
+        if (len < FB_KICK_DIST) {
+            const float inv = 1.0f / len;
+            e.ball.force = v3(e.ball.force.x + FB_KICK_FORCE * (d.x * inv), e.ball.force.y + FB_KICK_FORCE * 0.5f, e.ball.force.z + FB_KICK_FORCE * (d.z * inv));
+            ++kicks;
+        }
+    }
+    e.ball.kicks = kicks;
+    football_sync_ball(e);
+}
+
 static void env_step(Env &e)
 {
     const float dt = DT;
@@ -2520,12 +2762,14 @@ static void env_step(Env &e)
         }
     }
 
-    // bWorld.stepSimulation(dt, 1, dt): controllers run in agent order (env.cpp:126)
+    // bWorld.stepSimulation(dt, 1, dt): the dynamic bodies first (Football's ball: the stated model), then the actions -- the controllers, in agent
+    // order (env.cpp:126) -- against the ball's NEW pose
+    if (e.scenario == SCN_FOOTBALL) football_ball_step(e);
     for (int i = 0; i < e.numAgents; ++i) player_step(e, i, dt);
 
     // scenario->step(): objectStacking, fallDetection, zone reward (scenario_tower_building.cpp:179-199)
     // (BoxAGone: no ObjectStackingComponent; its FallDetectionComponent is never stepped, scenario_box_a_gone.cpp:211-291)
-    const bool hex = e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE || e.scenario == SCN_BOX_A_GONE;
+    const bool hex = e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE || e.scenario == SCN_BOX_A_GONE || e.scenario == SCN_FOOTBALL;   // (Football: neither component)
     for (int i = 0; i < e.numAgents; ++i)
         if (e.scenario != SCN_SOKOBAN && e.scenario != SCN_EMPTY && !hex && (e.agents[i].action & (1 << 8))) on_interact(e, i);   // (Sokoban, Empty, Hex*: no ObjectStackingComponent)
 
@@ -2605,6 +2849,8 @@ static void env_step(Env &e)
         }
     } else if (e.scenario == SCN_BOX_A_GONE) {
         boxagone_step(e);
+    } else if (e.scenario == SCN_FOOTBALL) {
+        football_kicks(e);
     } else if (e.scenario == SCN_EMPTY) {
         // EmptyScenario::step() {} (scenario_empty.hpp:22)
     } else if (e.scenario == SCN_SOKOBAN) {
@@ -2720,7 +2966,7 @@ static void build_prims(const Env &e, int viewer, std::vector<Prim> &out)
             out.push_back(p);
         }
     }
-    if (e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE || e.scenario == SCN_BOX_A_GONE) {   // (BoxAGone: no hexObjs)
+    if (e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE || e.scenario == SCN_BOX_A_GONE || e.scenario == SCN_FOOTBALL) {   // (BoxAGone: no hexObjs; Football: the ball)
         for (const Env::HexBox &b : e.hexBoxes) {
             Prim p; p.kind = 1; p.frame = b.frame < 0 ? -1 : MAX_AGENTS + b.frame; p.lo = b.lo; p.hi = b.hi; p.color = b.color;
             out.push_back(p);
@@ -3284,6 +3530,7 @@ struct Gym {
                 for (int a = 0; a < numAgents; ++a)
                     trueObjective[size_t(i) * numAgents + a] = envs[i]->scenario == SCN_TOWER ? float(envs[i]->highestTower)
                                                              : envs[i]->scenario == SCN_BOX_A_GONE ? boxagone_true_objective(*envs[i], a)
+                                                             : envs[i]->scenario == SCN_FOOTBALL ? 0.0f   // Scenario::trueObjective's default
                                                              : float(envs[i]->solved);   // scenario_collect.hpp:42
                 env_reset(*envs[i]);
             } else done[i] = 0;
@@ -3327,6 +3574,7 @@ mvo_gym *mvo_create(const char *scenario, int w, int h, int num_envs, int num_ag
     else if (s == "hexmemory") scen = SCN_HEX_MEMORY;  // scenarios/init.hpp:47-48
     else if (s == "hexexplore") scen = SCN_HEX_EXPLORE;
     else if (s == "boxagone") scen = SCN_BOX_A_GONE;   // scenarios/init.hpp:50
+    else if (s == "football") scen = SCN_FOOTBALL;     // scenarios/init.hpp:51
     else { fprintf(stderr, "mv_oracle: unknown scenario %s\n", s.c_str()); return nullptr; }
     if (num_agents_per_env < 1 || num_agents_per_env > MAX_AGENTS || num_envs < 1) return nullptr;
     auto *g = new mvo_gym();
@@ -3361,7 +3609,7 @@ mvo_gym *mvo_create(const char *scenario, int w, int h, int num_envs, int num_ag
         e->scenario = scen;
         e->op = op;
         e->numShaping = scen == SCN_TOWER || scen == SCN_SOKOBAN ? 4 : scen == SCN_REARRANGE || scen == SCN_HEX_MEMORY || scen == SCN_BOX_A_GONE ? 3
-                      : scen == SCN_HEX_EXPLORE ? 2 : scen == SCN_EMPTY ? 1 : 5;   // Empty: teamSpirit only
+                      : scen == SCN_HEX_EXPLORE ? 2 : scen == SCN_EMPTY || scen == SCN_FOOTBALL ? 1 : 5;   // Empty, Football: teamSpirit only
         e->shapingKeys = scen == SCN_TOWER ? SHAPING_KEYS_TOWER : scen == SCN_OBSTACLES ? SHAPING_KEYS_OBST
                        : scen == SCN_COLLECT ? SHAPING_KEYS_COLLECT : scen == SCN_SOKOBAN ? SHAPING_KEYS_SOKOBAN
                        : scen == SCN_HEX_MEMORY ? SHAPING_KEYS_HEX_MEMORY : scen == SCN_HEX_EXPLORE ? SHAPING_KEYS_HEX_EXPLORE
@@ -3552,7 +3800,7 @@ void mvo_snapshot(mvo_gym *g, int env, void *out)
         s->items[i][0] = e.items[i].shape; s->items[i][1] = (int32_t)e.items[i].color;
         s->items[i][2] = e.items[i].off[0]; s->items[i][3] = e.items[i].off[1]; s->items[i][4] = e.items[i].off[2];
     }
-    if (e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE || e.scenario == SCN_BOX_A_GONE) {
+    if (e.scenario == SCN_HEX_MEMORY || e.scenario == SCN_HEX_EXPLORE || e.scenario == SCN_BOX_A_GONE || e.scenario == SCN_FOOTBALL) {
         s->hex_num_boxes = int(e.hexBoxes.size()); s->hex_num_objs = int(e.hexObjs.size());
         s->hex_target[0] = e.hexTarget.x; s->hex_target[1] = e.hexTarget.y; s->hex_target[2] = e.hexTarget.z;
         for (size_t i = 0; i < e.hexBoxes.size() && i < HEX_MAX_BOXES; ++i) {
@@ -3561,7 +3809,7 @@ void mvo_snapshot(mvo_gym *g, int env, void *out)
         }
         for (size_t i = 0; i < e.hexObjs.size() && i < HEX_MAX_OBJS; ++i) {
             const Env::HexObj &o = e.hexObjs[i];
-            const int meta = o.shape | (o.good << 4) | (o.alive << 8) | (((o.vox[0] + 128) & 255) << 12) | (((o.vox[2] + 128) & 255) << 20);
+            const int meta = e.scenario == SCN_FOOTBALL ? o.shape : o.shape | (o.good << 4) | (o.alive << 8) | (((o.vox[0] + 128) & 255) << 12) | (((o.vox[2] + 128) & 255) << 20);
             s->hex_objs[i] = SnapHeader::HexRec{{o.pos.x, o.pos.y, o.pos.z}, meta, {o.scale.x, o.scale.y, o.scale.z}, int32_t(o.color)};
         }
     }
@@ -3613,6 +3861,46 @@ int mvo_debug_boxagone_state(mvo_gym *g, int env, void *out)
     std::memcpy(out, r, sizeof *r);
     delete r;
     return (int)sizeof(BagStateRec);
+}
+
+/* Football: the device's FootballState record (megaverse_amd/csrc/mv_types.h): the ball's centre, drawn radius, velocity, this tick's kicks,
+ * angular velocity, this tick's contact bits, the force pending for the next tick. */
+struct FbStateRec {
+    float pos[3], radius, vel[3];
+    int32_t kicks;
+    float ang[3];
+    int32_t contacts;
+    float force[3];
+    int32_t pad;
+};
+static_assert(sizeof(FbStateRec) == 64, "FootballState: 64 B");
+
+int mvo_debug_football_state(mvo_gym *g, int env, void *out)
+{
+    if (!g || env < 0 || env >= g->numEnvs || g->envs[size_t(env)]->scenario != SCN_FOOTBALL) return -1;
+    if (!out) return (int)sizeof(FbStateRec);
+    const Env::Ball &b = g->envs[size_t(env)]->ball;
+    FbStateRec r;
+    std::memset(&r, 0, sizeof r);
+    r.pos[0] = b.pos.x; r.pos[1] = b.pos.y; r.pos[2] = b.pos.z; r.radius = b.radius;
+    r.vel[0] = b.vel.x; r.vel[1] = b.vel.y; r.vel[2] = b.vel.z; r.kicks = b.kicks;
+    r.ang[0] = b.ang.x; r.ang[1] = b.ang.y; r.ang[2] = b.ang.z; r.contacts = b.contacts;
+    r.force[0] = b.force.x; r.force[1] = b.force.y; r.force[2] = b.force.z;
+    std::memcpy(out, &r, sizeof r);
+    return (int)sizeof(FbStateRec);
+}
+
+/* test hook: a ball placed by a test (the whole record; the drawn record follows) */
+int mvo_debug_set_football_state(mvo_gym *g, int env, const void *in)
+{
+    if (!g || !in || env < 0 || env >= g->numEnvs || g->envs[size_t(env)]->scenario != SCN_FOOTBALL) return -1;
+    FbStateRec r;
+    std::memcpy(&r, in, sizeof r);
+    Env &e = *g->envs[size_t(env)];
+    e.ball = Env::Ball{v3(r.pos[0], r.pos[1], r.pos[2]), v3(r.vel[0], r.vel[1], r.vel[2]), v3(r.ang[0], r.ang[1], r.ang[2]),
+                       v3(r.force[0], r.force[1], r.force[2]), r.radius, r.kicks, r.contacts};
+    football_sync_ball(e);
+    return 0;
 }
 
 // ---- spec helpers ----

@@ -7,7 +7,7 @@
  *
  * What this is: a dependency-free CPU restatement of the reference's
  * VectorEnv::step() path for the scenarios TowerBuilding, Obstacles{Easy,Medium,Hard,Walls,Steps,Lava},
- * Collect, Rearrange, Sokoban, HexMemory, HexExplore, BoxAGone and Empty
+ * Collect, Rearrange, Sokoban, HexMemory, HexExplore, BoxAGone, Football (its ball: the stated model of DESIGN.md section 7) and Empty
  *   reference: src/libs/env/src/vector_env.cpp:89-120 (step/reset order)
  *              src/libs/env/src/env.cpp:57-152          (Env::reset/step)
  *              src/libs/env/src/kinematic_character_controller.cpp (controller)
@@ -85,6 +85,11 @@ void mvo_snapshot(mvo_gym *g, int env_idx, void *out);
 /* BoxAGone: the device's BoxAGoneState record (platform table, timers, temporary platforms, cell map) derived from the oracle's own
  * containers; out = NULL: returns its size; -1: not a BoxAGone gym or bad env */
 int mvo_debug_boxagone_state(mvo_gym *g, int env_idx, void *out);
+/* Football: the device's 64-byte FootballState record (pos, radius, vel, kicks, ang, contacts, force, pad) with this tick's kick count and
+ * contact bits (capsule j -> bit j, room box k -> bit 8 + k); out = NULL: returns its size; -1: not a Football gym or bad env.  The setter
+ * places a ball (the whole record) and rewrites its drawn record, like mv_debug_set_football_state. */
+int mvo_debug_football_state(mvo_gym *g, int env_idx, void *out);
+int mvo_debug_set_football_state(mvo_gym *g, int env_idx, const void *in);
 
 /* ---- spec-level helpers exposed for known-answer tests ---- */
 /* Collect landscape noise: siv::PerlinNoise(seed).accumulatedOctaveNoise2D_0_1 (util/perlin_noise.hpp:315-318) */

@@ -75,6 +75,8 @@ def lib():
         L.mvo_snapshot_size.argtypes = [C.c_void_p]
         L.mvo_snapshot.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.mvo_debug_boxagone_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.mvo_debug_football_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.mvo_debug_set_football_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.mvo_mt19937_nth.argtypes = [C.c_uint32, C.c_int]
         L.mvo_mt19937_nth.restype = C.c_uint32
         L.mvo_rand_range_seq.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -196,6 +198,21 @@ class OracleGym:
         buf = np.zeros(1, boxagone_model.STATE)
         assert self.L.mvo_debug_boxagone_state(self.g, env_idx, buf.ctypes.data) == boxagone_model.STATE.itemsize
         return buf[0]
+
+    def football_state(self, env_idx):
+        """Football: the device's FootballState record (tests/football_model.STATE) of the oracle's ball"""
+        import football_model
+        assert self.L.mvo_debug_football_state(self.g, env_idx, None) == football_model.STATE.itemsize
+        buf = np.zeros(1, football_model.STATE)
+        assert self.L.mvo_debug_football_state(self.g, env_idx, buf.ctypes.data) == football_model.STATE.itemsize
+        return buf[0]
+
+    def set_football_state(self, env_idx, pos, vel=(0.0, 0.0, 0.0), ang=(0.0, 0.0, 0.0), force=(0.0, 0.0, 0.0), radius=1.0):
+        """Football: place the ball (same arguments as MegaverseGym.debug_set_football_state); its drawn record follows"""
+        import football_model
+        s = np.zeros(1, football_model.STATE)
+        s["pos"], s["vel"], s["ang"], s["force"], s["radius"] = pos, vel, ang, force, radius
+        assert self.L.mvo_debug_set_football_state(self.g, env_idx, s.ctypes.data) == 0
 
     def close(self):
         if self.g:

@@ -58,9 +58,9 @@ def test_fast_pixels_within_tolerance(hip, scenario, A, W, H):
 
 
 # the scenarios the matrix above leaves out (wall caps / goal pads / pushable boxes of Sokoban, the bare Empty room, the other
-# Obstacles variants' walls, steps and lava slabs), at the headline size and at a ragged one
+# Obstacles variants' walls, steps and lava slabs, Football's room and ball), at the headline size and at a ragged one
 @pytest.mark.parametrize("scenario,A", [("Sokoban", 2), ("Empty", 2), ("ObstaclesMedium", 1), ("ObstaclesWalls", 2), ("ObstaclesSteps", 1),
-                                        ("ObstaclesLava", 2), ("BoxAGone", 2)])
+                                        ("ObstaclesLava", 2), ("BoxAGone", 2), ("Football", 2)])
 @pytest.mark.parametrize("W,H", [(128, 128), (48, 20)])
 def test_fast_pixels_within_tolerance_other_scenarios(hip, scenario, A, W, H):
     _fast_vs_oracle(scenario, A, W, H)

@@ -68,10 +68,10 @@ def frames_of(g, A, e):
 
 # ---- 1. against the oracle, exact pixels ---------------------------------------------------------------------------------------------------------------
 ORACLE_CASES = {"tower_a1": ("TowerBuilding", 1), "tower_a3": ("TowerBuilding", 3), "obstacles_easy_a2": ("ObstaclesEasy", 2), "collect": ("Collect", 1),
-                "rearrange": ("Rearrange", 1), "sokoban": ("Sokoban", 1), "hex_memory": ("HexMemory", 1), "boxagone": ("BoxAGone", 1)}
+                "rearrange": ("Rearrange", 1), "sokoban": ("Sokoban", 1), "hex_memory": ("HexMemory", 1), "boxagone": ("BoxAGone", 1), "football": ("Football", 2)}
 
 
-def check_against_oracle(hg, og, A, e, src, what, boxagone=False):
+def check_against_oracle(hg, og, A, e, src, what, boxagone=False, football=False):
     """env e of the gym == env src of the oracle: state, rewards, dones, true objectives, frames"""
     assert diff_snapshots(og.snapshot(src), hip_snapshot(hg, e), A) == [], f"{what}: state of env {e} against the oracle's env {src}"
     if boxagone:
@@ -79,6 +79,10 @@ def check_against_oracle(hg, og, A, e, src, what, boxagone=False):
         so, sh = og.boxagone_state(src), hg.debug_boxagone_state(e).view(M.STATE)[0]
         bad = [n for n in M.STATE.names if so[n].tobytes() != sh[n].tobytes()]
         assert not bad, f"{what}: BoxAGone state of env {e}: {bad}"
+    if football:
+        from football_cases import record
+        so, sh = og.football_state(src), record(hg.debug_football_state(e))
+        assert so.tobytes() == sh.tobytes(), f"{what}: Football's ball of env {e}: {so} vs {sh}"
     rew, done, tobj = hg.get_rewards_array(), hg.get_dones(), hg.get_true_objectives()
     assert rew[e * A:(e + 1) * A].tobytes() == og.get_last_rewards()[src * A:(src + 1) * A].tobytes(), f"{what}: rewards of env {e}"
     assert int(done[e]) == int(og.get_dones()[src]), f"{what}: done of env {e}"
@@ -112,7 +116,7 @@ def test_fork_against_the_oracle(hip, case, monkeypatch):
         oracle_act(og, A, script[t]); og.step()
         assert not hg.get_dones().any() and not og.get_dones().any(), f"an env finished inside the window (tick {t})"
         for e in range(N):
-            check_against_oracle(hg, og, A, e, COLS[e], f"{case}, tick {t}", boxagone=scenario == "BoxAGone")
+            check_against_oracle(hg, og, A, e, COLS[e], f"{case}, tick {t}", boxagone=scenario == "BoxAGone", football=scenario == "Football")
         for d in DESTINATIONS:
             assert raw(hg, d) == raw(hg, COLS[d]), f"{case}, tick {t}: env {d} is not byte for byte its source {COLS[d]}"
     hg.close(); og.close()

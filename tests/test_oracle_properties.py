@@ -116,3 +116,31 @@ def test_tiled_raster_equals_brute_force(scenario, A, W, H, monkeypatch):
         assert brute[..., :3].max() > 0
         assert np.array_equal(brute, tiled), f"{scenario} round {rnd}: {int((brute != tiled).any(axis=-1).sum())} pixels differ"
     g.close()
+
+
+def test_tiled_raster_equals_brute_force_football():
+    """Football: the same, with the ball in view -- every env's agent 0 stands three units from the ball and looks at it (orange pixels are
+    counted), on the frame after the reset (drawn radius 0.5) and after ticks (radius 1.0, the ball falling, then resting)"""
+    import football_cases as FC
+    N, A, W, H = 4, 2, 64, 36
+    g = oracle_lib.OracleGym("Football", W, H, N, A, 2, False, {})
+    g.seed(9); g.reset()
+    for rnd in range(3):
+        for e in range(N):
+            ball = g.football_state(e)["pos"]
+            pos = (float(ball[0]) + 3.0, max(float(ball[1]) - 0.46, FC.REST_Y), float(ball[2]) + 0.5 * e)
+            g.debug_set_agent_pos(e, 0, *pos)
+            g.debug_set_agent_yaw(e, 0, *FC.facing(pos, ball))
+            g.debug_set_agent_velocity(e, 0, 0.0, 0.0, 0.0)
+        g.set_raster(False); g.render()
+        brute = np.stack([g.get_observation(e, a).copy() for e in range(N) for a in range(A)])
+        g.set_raster(True); g.render()
+        tiled = np.stack([g.get_observation(e, a).copy() for e in range(N) for a in range(A)])
+        rgb = brute[::A, :, :, :3].astype(np.int16)   # agent 0's frames
+        orange = (rgb[..., 0] - rgb[..., 2] > 60) & (rgb[..., 0] >= rgb[..., 1]) & (rgb[..., 1] >= rgb[..., 2])
+        assert orange.reshape(N, -1).sum(axis=1).min() >= 20, orange.reshape(N, -1).sum(axis=1)
+        assert np.array_equal(brute, tiled), f"Football round {rnd}: {int((brute != tiled).any(axis=-1).sum())} pixels differ"
+        for st in range(8):
+            g.set_action_masks(action_masks(sample_actions(3, 8 * rnd + st, N * A)))
+            g.step_norender()
+    g.close()

@@ -73,11 +73,11 @@ def device_map(m):
 
 # ---- 1. against the oracle, exact pixels ---------------------------------------------------------------------------------------------------------------
 ORACLE_CASES = {"tower_a1": ("TowerBuilding", 1, "perm"), "tower_a3": ("TowerBuilding", 3, "perm"), "obstacles_easy_a2": ("ObstaclesEasy", 2, "perm"),
-                "sokoban": ("Sokoban", 1, "perm"), "hex_memory": ("HexMemory", 1, "perm"), "boxagone": ("BoxAGone", 1, "perm"),
+                "sokoban": ("Sokoban", 1, "perm"), "hex_memory": ("HexMemory", 1, "perm"), "boxagone": ("BoxAGone", 1, "perm"), "football": ("Football", 2, "perm"),
                 "tower_a1_draw": ("TowerBuilding", 1, "draw")}
 
 
-def check_against_oracle(hg, og, A, e, src, what, boxagone=False):
+def check_against_oracle(hg, og, A, e, src, what, boxagone=False, football=False):
     """env e of the gym == env src of the oracle: state, rewards, dones, true objectives, frames"""
     assert diff_snapshots(og.snapshot(src), hip_snapshot(hg, e), A) == [], f"{what}: state of env {e} against the oracle's env {src}"
     if boxagone:
@@ -85,6 +85,10 @@ def check_against_oracle(hg, og, A, e, src, what, boxagone=False):
         so, sh = og.boxagone_state(src), hg.debug_boxagone_state(e).view(M.STATE)[0]
         bad = [n for n in M.STATE.names if so[n].tobytes() != sh[n].tobytes()]
         assert not bad, f"{what}: BoxAGone state of env {e}: {bad}"
+    if football:
+        from football_cases import record
+        so, sh = og.football_state(src), record(hg.debug_football_state(e))
+        assert so.tobytes() == sh.tobytes(), f"{what}: Football's ball of env {e}: {so} vs {sh}"
     rew, done, tobj = hg.get_rewards_array(), hg.get_dones(), hg.get_true_objectives()
     assert rew[e * A:(e + 1) * A].tobytes() == og.get_last_rewards()[src * A:(src + 1) * A].tobytes(), f"{what}: rewards of env {e}"
     assert int(done[e]) == int(og.get_dones()[src]), f"{what}: done of env {e}"
@@ -117,7 +121,7 @@ def test_resample_against_the_oracle(hip, case, monkeypatch):
         oracle_act(og, A, script[t]); og.step()
         assert not hg.get_dones().any() and not og.get_dones().any(), f"an env finished inside the window (tick {t})"
         for e in range(N):
-            check_against_oracle(hg, og, A, e, cols[e], f"{case}, tick {t}", boxagone=scenario == "BoxAGone")
+            check_against_oracle(hg, og, A, e, cols[e], f"{case}, tick {t}", boxagone=scenario == "BoxAGone", football=scenario == "Football")
     for e in range(N):   # envs that drew the same source run one episode, byte for byte
         for f in range(e):
             assert (raw(hg, e) == raw(hg, f)) == (cols[e] == cols[f]), f"{case}: envs {f} and {e}"

@@ -63,7 +63,7 @@ def device_mask(mask):
 # ---- 1. against the oracle, every scenario family ------------------------------------------------------------------------------------------------------
 ORACLE_CASES = {"tower_a1": ("TowerBuilding", 1), "tower_a2": ("TowerBuilding", 2), "obstacles_easy": ("ObstaclesEasy", 1), "collect": ("Collect", 1),
                 "rearrange": ("Rearrange", 1), "sokoban": ("Sokoban", 1), "hex_memory": ("HexMemory", 1), "boxagone": ("BoxAGone", 1),
-                "empty": ("Empty", 1)}   # (Football: the oracle has no such scenario -- test_masked_reset_football below)
+                "empty": ("Empty", 1), "football": ("Football", 2)}   # (Football against its generator's episodes and twin gyms too: test_masked_reset_football below)
 
 
 def capture(og, scenario, A):
@@ -72,6 +72,8 @@ def capture(og, scenario, A):
            "frames": np.stack([og.get_observation(e, a).copy() for e in range(N) for a in range(A)])}
     if scenario == "BoxAGone":
         out["bag"] = [og.boxagone_state(e) for e in range(N)]
+    if scenario == "Football":
+        out["ball"] = [og.football_state(e) for e in range(N)]
     return out
 
 
@@ -117,6 +119,10 @@ def check_env(hg, ref, scenario, A, e, what):
         so, sh = ref["bag"][e], hg.debug_boxagone_state(e).view(M.STATE)[0]
         bad = [n for n in M.STATE.names if so[n].tobytes() != sh[n].tobytes()]
         assert not bad, f"{what}: BoxAGone state of env {e}: {bad}"
+    if scenario == "Football":
+        from football_cases import record
+        so, sh = ref["ball"][e], record(hg.debug_football_state(e))
+        assert so.tobytes() == sh.tobytes(), f"{what}: Football's ball of env {e}: {so} vs {sh}"
     rew, done, tobj = hg.get_rewards_array(), hg.get_dones(), hg.get_true_objectives()
     s = slice(e * A, (e + 1) * A)
     assert rew[s].view(np.uint32).tolist() == ref["rewards"][s].view(np.uint32).tolist(), f"{what}: rewards of env {e}"
@@ -159,8 +165,8 @@ def football_state(g, e):
 
 @pytest.mark.parametrize("mask_name", sorted(MASKS))
 def test_masked_reset_football(hip, mask_name):
-    """1, Football.  The CPU oracle has no Football scenario (tests/test_football_gpu.py pins it to tests/football_model.py instead), so the case takes
-    the references that exist: right behind the reset a flagged env is the SECOND episode tests/football_model.py generates from that env's seed stream, ball
+    """1, Football, beside its oracle case above: the references from before the oracle knew the scenario -- right behind the reset a flagged env is
+    the SECOND episode tests/football_model.py generates from that env's seed stream, ball
     at rest in its reset state (the check test_football_gpu.py makes of a fresh episode); and behind the reset and every one of the 12 later ticks a flagged
     env is, byte for byte, the env of a twin gym that was reset as a whole at tick 7 and an unflagged env the env of a twin that was left alone: snapshot,
     ball state, rewards, dones, true objectives, exact-mode pixels"""
