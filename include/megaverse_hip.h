@@ -206,6 +206,26 @@ int mv_step_no_render(mv_gym *g);                   /* physics/logic/auto-reset 
  * MV_POLICY_NONE: the first tick acts on what mv_set_actions* left, the others on cleared actions.  The public arrays hold the LAST tick's
  * outputs -- or, with mv_set_output_ring, every tick's.  k may exceed the internal batch (mv_recommended_ticks_per_call; MV_PIPE_BATCH overrides its sizing): the call splits it. */
 int mv_step_n(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32_t first_step_index);
+/* Render modes of a batched call (no reference counterpart: VectorEnv::step always renders, vector_env.cpp:103-107).  A planner that scores candidates by
+ * return reads none of the k frames mv_step_n draws, one that feeds a value net only the last; the observation pass is the larger half of a call.
+ * MV_RENDER_EVERY: mv_step_n, call for call and launch for launch.
+ * MV_RENDER_NONE: the k ticks run -- physics, scenario logic, auto-reset, episode swap-in, refill protocol, status read-backs, episode log -- and nothing is
+ * drawn.  Rewards and dones of every tick go where mv_step_n puts them: entry t % count of attached rings, else the public arrays (the last tick's stay); the
+ * true objectives of envs that finished are published in tick order.  The observation slab and every entry of an observation ring are not written, not one
+ * byte; the ring's tick count advances by k as always, so a later rendered call lands in the entries it would have.  mv_render afterwards draws the current state.
+ * MV_RENDER_LAST: as MV_RENDER_NONE, and tick k - 1 of the whole call (also where the call is split into chunks) is drawn into its own place -- ring entry
+ * t % count, or the slab -- in the gym's pixel mode and layout, byte for byte what MV_RENDER_EVERY would have left there.
+ * Launches: one step launch per 8 ticks that sets no frame up (MV_RENDER_LAST: the drawn tick's frame setup runs inside the last one), one launch that
+ * publishes the rewards / dones / true objectives of all the call's ticks, MV_RENDER_LAST: one observation launch (it publishes nothing).  Shapes without a
+ * multi-tick step kernel -- several agents outside TowerBuilding, MV_POLICY_NONE, MV_STEP_TICKS=0, gyms stepped tick by tick because their episodes can end
+ * within a few ticks -- take one tick-only launch per tick, as mv_step_no_render does.  Every scenario and every policy works in every mode.
+ * Ordering: mv_step_n's.  The caller's stream sees the call's rewards and dones behind the call; the simulation stream reuses the call's hand-over slots only
+ * after the publication and the episode log's update have read them.  mv_set_pass_overlap does not apply to MV_RENDER_LAST / MV_RENDER_NONE calls: they run
+ * as without it, and a following MV_RENDER_EVERY call starts a new overlapped sequence.
+ * Groups: mv_group_step keeps its own render flag (0 / 1); render modes for groups are not provided.
+ * Refused (-1 with text): an unknown mode; everything mv_step_n refuses; a gym in a group. */
+enum { MV_RENDER_EVERY = 0, MV_RENDER_LAST = 1, MV_RENDER_NONE = 2 };
+int mv_step_n_render(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32_t first_step_index, int32_t render_mode);
 /* Rollout rings (no reference counterpart: its learner copies each step's observation out of the gym, megaverse_env.py:121-130): tick
  * number t since this call leaves its observations in obs[t % count] ([count][N*A][h][w][4]; planar layout: [count][N*A][3][h][w]), its rewards in rewards[t % count] ([count][N*A])
  * and its dones in dones[t % count] ([count][N]); a NULL ring keeps that output where it was.  count = 0 switches back to the single

@@ -60,6 +60,31 @@ __global__ void publish_kernel(const float *s_rew, const uint8_t *s_done, const 
     if (i < n_envs) done[i] = s_done[i];
 }
 
+// The k ticks of one stepping call that drew nothing per tick (mv_step_n_render: MV_RENDER_NONE / MV_RENDER_LAST) with ONE launch: thread i carries agent i's
+// staged rewards (and env i's dones) of every tick to that tick's destination, in ascending tick order -- without rings every tick's destination is the public
+// array and the last tick's value stays -- and records the true objective of every tick that finished the env, the latest last (publish_kernel, k times).
+struct PublishTicksArgs {
+    int32_t k, n_envs, A, pad;
+    const float *s_rew[PIPE_BATCH_MAX];
+    const uint8_t *s_done[PIPE_BATCH_MAX];
+    const float *s_true[PIPE_BATCH_MAX];
+    float *rew[PIPE_BATCH_MAX];
+    uint8_t *done[PIPE_BATCH_MAX];
+    float *true_obj;
+};
+__global__ __launch_bounds__(256) void publish_ticks_kernel(PublishTicksArgs a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_envs * a.A) return;
+    const int e = i / a.A;
+    for (int j = 0; j < a.k; ++j) {
+        a.rew[j][i] = a.s_rew[j][i];
+        const uint8_t d = a.s_done[j][e];
+        if (d) a.true_obj[i] = a.s_true[j][i];
+        if (i < a.n_envs) a.done[j][i] = a.s_done[j][i];
+    }
+}
+
 __global__ void clear_flags_kernel(int *word, int reported) { atomicAnd(word, ~reported); }   // only the bits that were reported: a bit raised since stays
 __global__ void set_shaping_kernel(AgentState *agents, int idx, int key, float v) { agents[idx].shaping[key] = v; }
 
@@ -178,6 +203,24 @@ int publish_outputs(mv_gym *g, int q, const OutPtrs &o)   // on the caller's str
     const int n = g->N * g->A;
     hipLaunchKernelGGL(publish_kernel, dim3((n + 255) / 256), dim3(256), 0, g->stream, v.rewards, v.done, v.true_objective, o.rewards, o.done,
                        g->gv.true_objective, g->N, g->A);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int publish_ticks(mv_gym *g, int q0, const OutPtrs *outs, int stride, int k)   // on the caller's stream
+{
+    PublishTicksArgs a;
+    a.k = k; a.n_envs = g->N; a.A = g->A; a.pad = 0;
+    for (int j = 0; j < (int)PIPE_BATCH_MAX; ++j) {
+        const int jj = std::min(j, k - 1);
+        const GymView &v = g->gvp[q0 + jj];
+        const OutPtrs &o = outs[(size_t)jj * stride];
+        a.s_rew[j] = v.rewards; a.s_done[j] = v.done; a.s_true[j] = v.true_objective;
+        a.rew[j] = o.rewards; a.done[j] = o.done;
+    }
+    a.true_obj = g->gv.true_objective;
+    const int n = g->N * g->A;
+    hipLaunchKernelGGL(publish_ticks_kernel, dim3((n + 255) / 256), dim3(256), 0, g->stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -45,6 +45,8 @@ void launch_collect_blob_copy(const int32_t *envs, const int32_t *slots, int cou
 bool launch_step(const GymView &gv, hipStream_t stream, int W, int H, int render, hipEvent_t done = nullptr);
 // k <= 8 ticks + frame setups of every env, one launch (one agent per env; several: TowerBuilding); done: completed by the launch
 void launch_step_ticks(const GymView *views, int k, hipStream_t stream, int W, int H, hipEvent_t done = nullptr);
+// k <= 8 ticks of every env, one launch; frame setups only for the ticks whose bit is set in frame_mask (mv_step_n_render: MV_RENDER_NONE / MV_RENDER_LAST)
+void launch_step_ticks_sim(const GymView *views, int k, unsigned frame_mask, hipStream_t stream, int W, int H, hipEvent_t done = nullptr);
 // every finished (force_all: every) env swaps its next resident episode in
 void launch_reset_episodes(const GymView &gv, int force_all, hipStream_t stream);
 // mv_reset_envs: the envs mask [num_envs] flags take their next resident episode; applied [num_envs]: 1 / 0 for every flagged env, whether it did
@@ -250,6 +252,8 @@ int tower_join(mv_gym *g);
 int tower_draw_before(mv_gym *g, hipStream_t sim);
 int tower_draw_after(mv_gym *g, hipEvent_t after, int ticks);
 int publish_outputs(mv_gym *g, int q, const OutPtrs &o);   // on the caller's stream
+// the staged outputs of the k ticks in slots q0 .. q0 + k - 1 -> outs[j * stride], one launch on the caller's stream (calls that draw no tick, or the last)
+int publish_ticks(mv_gym *g, int q0, const OutPtrs *outs, int stride, int k);
 bool scenario_from_name(const std::string &scen, int &scenario, ObstacleConfig &oc);
 int check_status_flags(mv_gym *g);
 int finish_with_warning(mv_gym *g);

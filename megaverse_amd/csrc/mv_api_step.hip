@@ -1,5 +1,6 @@
 // megaverse_amd/csrc/mv_api_step.hip -- stepping: MegaverseGym::step (megaverse.cpp:118-121 -> VectorEnv::step, vector_env.cpp:89-108) as kernel sequencing on
-// two streams -- one-step-ahead pipelining, batched calls (mv_step_n: one step launch + one observation launch per call), overlapped passes, groups of gyms
+// two streams -- one-step-ahead pipelining, batched calls (mv_step_n: one step launch + one observation launch per call; mv_step_n_render: the same ticks with
+// none of them drawn, or the last only), overlapped passes, groups of gyms
 // stepped with union launches (mv_group_*), several gyms per call (mv_step_many) -- and the in-stream kernel timing (mv_profile_*).  DESIGN.md 3.4, 3.6.
 #include "mv_api_internal.h"
 
@@ -13,7 +14,12 @@ extern "C" {
 // (mv_set_action_ring) -- to the kernels a POLICY_NONE tick with a multi-discrete pointer of its own, so every launch path the random policies open is open.
 // kCall: the ticks of the CALLER's call this chunk belongs to (mv_step_n splits a call of more than `batch` ticks): what the ring contract of
 // the overlapped passes is stated in (include/megaverse_hip.h).
-static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, uint32_t seed, uint32_t first_index, int kCall)
+// quiet (mv_step_n_render; one gym, render = false): QUIET_NONE: no tick of the chunk is drawn; QUIET_LAST: tick k - 1 alone is (the last chunk of an
+// MV_RENDER_LAST call) -- its frame setup in the step launch, one observation launch for it.  Either way the ticks go out as ONE launch per 8 that sets no other
+// frame up (launch_step_ticks_sim) wherever the rendered call has its one-launch step, and their rewards / dones / true objectives are published by ONE launch
+// for the chunk (publish_ticks).  QUIET_OFF: everything as `render` says, launch for launch.
+enum : int { QUIET_OFF = 0, QUIET_NONE = 1, QUIET_LAST = 2 };
+static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, uint32_t seed, uint32_t first_index, int kCall, int quiet = QUIET_OFF)
 {
     mv_gym *const L = gs[0];
     int batch = L->batch;
@@ -103,6 +109,12 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     const bool canBatchRaster = canMultiTick && render && allFast && n == 1 && k >= 2 && L->ringObs && L->ringCount >= k;
     // timing (mv_profile_begin): a batched call that takes both one-launch paths is timed as a whole -- one entry, events around the step
     // launch and around the raster launch, k ticks -- so that the figures are those of the launches the product runs; otherwise tick by tick
+    // The same shapes, no tick drawn or the last one only: the launches whose ticks set no frame up.  (Everything else -- several agents outside TowerBuilding,
+    // MV_STEP_TICKS=0, instrumented builds, MV_POLICY_NONE, calls of one tick: what gyms with few-tick episodes are stepped in -- takes the single-tick
+    // launches with fused = 0, as mv_step_no_render does; fused = 1 for the drawn tick.)
+    const bool simTicks = quiet != QUIET_OFF && !ticksOff && n == 1 && (L->A == 1 || L->scenario == SCN_TOWER) && k >= 2 && k <= MAX_STEP_TICKS
+                          && policy != POLICY_NONE && !L->gv.dbg;
+    const bool drawLast = quiet == QUIET_LAST;
     const bool profiling = render && L->profCount < L->profMax;
     hipEvent_t *callEv = nullptr;
     if (profiling && canMultiTick && canBatchRaster && k <= MAX_STEP_TICKS) {
@@ -144,7 +156,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
             else { g->gv.sample_on = (j == 0 && g->samplePending) ? g->samplePolicy : (int)POLICY_NONE; }
             g->parity = g->group * g->batch + j;
             // (this pass's frame setup fills the next cost histogram; one launch per tick: and clears the one after)
-            if (render && take_hist(g, sim, !(multiTick || groupBatch))) return -1;
+            if ((render || (drawLast && j == k - 1)) && take_hist(g, sim, !(multiTick || groupBatch || simTicks))) return -1;
             OutPtrs &o = outs[(size_t)j * n + i];
             o = outputs_of(g, g->ringTick++);
             GymView &v = views[(size_t)j * n + i];
@@ -178,9 +190,22 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
                 if (callEv) HIP_TRY(hipEventRecord(callEv[1], sim));
                 simDoneRides = rides != nullptr;
             }
+        } else if (simTicks) {
+            if (drawLast && j == k - 1) views[(size_t)j].lpt_no_clear = 1;   // (the drawn tick's pass clears its histogram itself, as behind launch_step_ticks)
+            if (j == k - 1) {
+                hipEvent_t rides = own ? L->simDone : nullptr;
+                const int chunkTicks = 8;   // (StepTicksArgs8)
+                for (int j0 = 0; j0 < k; j0 += chunkTicks) {
+                    const int kk = std::min(chunkTicks, k - j0);
+                    const bool last = j0 + kk == k;
+                    launch_step_ticks_sim(views.data() + j0, kk, last && drawLast ? 1u << (kk - 1) : 0u, sim, L->w, L->h, last ? rides : nullptr);
+                    ++L->launchCount[0];
+                }
+                simDoneRides = rides != nullptr;
+            }
         } else if (n == 1) {
             hipEvent_t rides = j == k - 1 && !evs[j] ? (own ? L->simDone : sideWaits ? L->stepDone : nullptr) : nullptr;
-            const bool rode = launch_step(views[(size_t)j * n], sim, L->w, L->h, fused, rides);
+            const bool rode = launch_step(views[(size_t)j * n], sim, L->w, L->h, drawLast && j == k - 1 ? 1 : fused, rides);
             ++L->launchCount[0];
             simDoneRides = rode && own;
             stepDoneRodeAlong = rode && !own;
@@ -277,6 +302,8 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     std::vector<PublishTo> chunkPubs;
     std::vector<uint32_t *> chunkObs;
     int chunkFirst = 0;
+    // (no tick drawn, or the last only: the chunk's staged outputs with one launch, in front of the drawn tick's pass -- which publishes nothing)
+    if (quiet != QUIET_OFF && staged && publish_ticks(L, L->group * L->batch, outs.data(), n, k)) return -1;
     for (int j = 0; j < k; ++j) {
         if (evs[j]) HIP_TRY(hipEventRecord(evs[j][2], L->stream));
         for (int i = 0; i < n; ++i) {
@@ -284,7 +311,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
             pubs[i] = PublishTo{o.rewards, o.done, gs[i]->gv.true_objective};
             obsPtrs[i] = o.obs;
             // (the fast observation pass publishes with its first workgroups)
-            if (staged && (!render || !allFast) && publish_outputs(gs[i], gs[i]->group * gs[i]->batch + j, o)) return -1;
+            if (quiet == QUIET_OFF && staged && (!render || !allFast) && publish_outputs(gs[i], gs[i]->group * gs[i]->batch + j, o)) return -1;
         }
         // the call's last pass completes this call's mark (what the simulation stream waits for before it reuses the slot group)
         hipEvent_t mark = own && j == k - 1 ? L->userMark[L->markCount % PIPE_GROUPS] : nullptr;
@@ -352,6 +379,12 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
                     if (v.lpt_no_clear && gs[i]->fastPixels) gs[i]->histClean[(size_t)v.lpt_parity] = 1;   // (self_clear, mv_raster.hip)
                 }
             }
+        } else if (drawLast && j == k - 1) {   // the one drawn tick: its lists were set up inside the step launch
+            const GymView &v = views[(size_t)j];
+            if (launch_raster(v, obsPtrs[0], L->w, L->h, L->stream, nullptr, L->fastPixels, /*setup_done=*/1, nullptr, mark))
+                return fail("mv_step_n_render: observation size above 1024x1024");
+            ++L->launchCount[1];
+            if (v.lpt_no_clear && L->fastPixels) L->histClean[(size_t)v.lpt_parity] = 1;   // (self_clear, mv_raster.hip)
         } else if (mark) HIP_TRY(hipEventRecord(mark, L->stream));
         if (evs[j]) HIP_TRY(hipEventRecord(evs[j][4], L->stream));
     }
@@ -380,10 +413,10 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     return rc;
 }
 
-static int step_impl(mv_gym *g, bool render, int k, int policy, uint32_t seed, uint32_t first_index, int kCall = 0)
+static int step_impl(mv_gym *g, bool render, int k, int policy, uint32_t seed, uint32_t first_index, int kCall = 0, int quiet = QUIET_OFF)
 {
     if (g && g->inGroup) return fail("this gym belongs to an mv_group: step the group (mv_group_step)");
-    return step_gyms(&g, 1, render, k, policy, seed, first_index, kCall > 0 ? kCall : k);
+    return step_gyms(&g, 1, render, k, policy, seed, first_index, kCall > 0 ? kCall : k, quiet);
 }
 
 int mv_step(mv_gym *g) { return step_impl(g, true, 1, POLICY_NONE, 0, 0); }
@@ -391,17 +424,32 @@ int mv_step_no_render(mv_gym *g) { return step_impl(g, false, 1, POLICY_NONE, 0,
 
 int mv_step_n(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32_t first_step_index)
 {
-    if (check(g)) return -1;
-    if (policy < MV_POLICY_NONE || policy > MV_POLICY_SEQUENCE) return fail("mv_step_n: unknown policy");
-    if (k < 1) return fail("mv_step_n: k >= 1 required");
+    return mv_step_n_render(g, k, policy, seed, first_step_index, MV_RENDER_EVERY);
+}
+
+int mv_step_n_render(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32_t first_step_index, int32_t render_mode)
+{
+    const bool every = render_mode == MV_RENDER_EVERY;
+    const char *const me = every ? "mv_step_n" : "mv_step_n_render";   // (MV_RENDER_EVERY is mv_step_n, its texts included)
+    if (check(g)) { if (!every) g_err = "mv_step_n_render: " + g_err; return -1; }
+    if (render_mode != MV_RENDER_EVERY && render_mode != MV_RENDER_LAST && render_mode != MV_RENDER_NONE)
+        return fail("mv_step_n_render: unknown render mode (MV_RENDER_EVERY, MV_RENDER_LAST, MV_RENDER_NONE)");
+    if (policy < MV_POLICY_NONE || policy > MV_POLICY_SEQUENCE) return fail(std::string(me) + ": unknown policy");
+    if (k < 1) return fail(std::string(me) + ": k >= 1 required");
+    if (!every) {
+        if (g->inGroup) return fail("mv_step_n_render: this gym belongs to an mv_group: step the group (mv_group_step keeps its own render flag)");
+        if (!g->wasReset) return fail("mv_step_n_render: call mv_reset first");
+    }
     int rc = 0;
     // Episodes that can end within a few ticks (statusPeriod 1: the refill protocol looks at the consumed counts after every tick) are
     // stepped one tick per call; otherwise `batch` ticks at a time.
     const int chunk = g->statusPeriod <= 1 ? 1 : g->batch;
     for (int done = 0; done < k; done += chunk) {
         const int n = std::min(chunk, k - done);
-        const int r = step_impl(g, true, n, policy, seed, first_step_index + (uint32_t)done, k);
-        if (r < 0) return -1;
+        // (MV_RENDER_LAST: tick k - 1 of the whole call is the one drawn -- the last tick of the last chunk)
+        const int quiet = every ? QUIET_OFF : render_mode == MV_RENDER_LAST && done + n == k ? QUIET_LAST : QUIET_NONE;
+        const int r = step_impl(g, every, n, policy, seed, first_step_index + (uint32_t)done, k, quiet);
+        if (r < 0) { if (!every && g_err.compare(0, 17, "mv_step_n_render:") != 0) g_err = "mv_step_n_render: " + g_err; return -1; }
         if (r > 0) { g->warning += (g->warning.empty() ? "" : " | ") + g_err; rc = 1; }   // (every chunk's warning text is kept)
     }
     if (rc) { g_err = g->warning; g->warning.clear(); }

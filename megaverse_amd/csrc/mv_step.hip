@@ -17,12 +17,17 @@ template <int A_MAX> __global__ __launch_bounds__(256) void step_kernel(GymView 
 template <class Args> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_ticks_kernel(Args a, int W, int H) { step_ticks_body<S, 1>(a, W, H); }
 template <class Args> __global__ __launch_bounds__(256, 3) void step_ticks_agents_kernel(Args a, int W, int H) { step_ticks_body<S, MAX_AGENTS>(a, W, H); }
 template <class Args> __global__ __launch_bounds__(128, MV_STEP_TICKS_WAVES_PER_SIMD) void step_ticks_pipe_kernel(Args a, int W, int H) { step_ticks_pipe_body<S>(a, W, H); }
+// (ticks that set no frame up; FRAMES: a mask says which ticks do -- step_ticks_sim_body)
+template <class Args, bool FRAMES> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_ticks_sim_kernel(Args a, int W, int H) { step_ticks_sim_body<S, 1, Args, FRAMES>(a, W, H); }
+template <class Args, bool FRAMES> __global__ __launch_bounds__(256, 3) void step_ticks_sim_agents_kernel(Args a, int W, int H) { step_ticks_sim_body<S, MAX_AGENTS, Args, FRAMES>(a, W, H); }
 // (the draws that refill the rings run in front of it: tower_draw_kernel, mv_reset.hip)
 __global__ __launch_bounds__(64) void reset_kernel(GymView gv, int force_all) { reset_body<S>(gv, force_all); }
 __global__ __launch_bounds__(64) void reset_masked_kernel(GymView gv, const uint8_t *mask, uint8_t *applied) { reset_masked_body<S>(gv, mask, applied); }
 
 const StepKernels tower_kernels = {step_kernel<1>, step_kernel<MAX_AGENTS>, step_ticks_kernel<StepTicksArgs8>, step_ticks_pipe_kernel<StepTicksArgs8>,
-                                   step_ticks_agents_kernel<StepTicksArgs8>, reset_kernel, reset_masked_kernel};
+                                   step_ticks_agents_kernel<StepTicksArgs8>, reset_kernel, reset_masked_kernel,
+                                   step_ticks_sim_kernel<StepTicksArgs8, false>, step_ticks_sim_kernel<StepTicksArgs8, true>,
+                                   step_ticks_sim_agents_kernel<StepTicksArgs8, false>, step_ticks_sim_agents_kernel<StepTicksArgs8, true>};
 
 static const StepKernels &kernels_of(int scenario)
 {
@@ -69,6 +74,21 @@ void launch_step_ticks(const GymView *views, int k, hipStream_t stream, int W, i
     if (gv.num_agents > 1) hipExtLaunchKernelGGL(K.ticks_agents, dim3(gv.num_envs), dim3(64 * std::min(gv.num_agents, 2)), 0, stream, nullptr, done, 0, a, W, H);
     else if (K.ticks_pipe && step_pipe_enabled(gv)) hipExtLaunchKernelGGL(K.ticks_pipe, dim3(gv.num_envs), dim3(128), 0, stream, nullptr, done, 0, a, W, H);
     else hipExtLaunchKernelGGL(K.ticks, dim3(gv.num_envs), dim3(64), 0, stream, nullptr, done, 0, a, W, H);
+}
+
+// k <= 8 ticks of every env with one launch, frame setups only for the ticks whose bit is set in frame_mask (0: the kernels without any frame setup).  The
+// shapes launch_step_ticks has, but for the two-wave pipelined kernels: they exist to overlap a tick with the previous tick's frame setup.
+void launch_step_ticks_sim(const GymView *views, int k, unsigned frame_mask, hipStream_t stream, int W, int H, hipEvent_t done)
+{
+    const GymView &gv = views[0];
+    const StepKernels &K = kernels_of(gv.scenario);
+    StepTicksArgs8 a;
+    a.n = k; a.pad = (int32_t)(frame_mask & ((1u << k) - 1u));
+    for (int j = 0; j < 8; ++j) a.gv[j] = views[std::min(j, k - 1)];
+    if (gv.num_agents > 1)
+        hipExtLaunchKernelGGL(a.pad ? K.ticks_sim_agents_frames : K.ticks_sim_agents, dim3(gv.num_envs), dim3(64 * std::min(gv.num_agents, 2)), 0, stream,
+                              nullptr, done, 0, a, W, H);
+    else hipExtLaunchKernelGGL(a.pad ? K.ticks_sim_frames : K.ticks_sim, dim3(gv.num_envs), dim3(64), 0, stream, nullptr, done, 0, a, W, H);
 }
 
 // done: an event that completes with the launch, carried by its dispatch packet (cf. mv_raster.h) -- TowerBuilding's launch only; -> whether it rides

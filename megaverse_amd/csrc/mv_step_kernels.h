@@ -123,6 +123,54 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
     }
 }
 
+// The resident multi-tick step for ticks that set no frame up (mv_step_n_render, MV_RENDER_NONE / MV_RENDER_LAST): as step_ticks_body -- one workgroup per env,
+// resident for the launch's <= 8 ticks, one wave per env for one agent, every wave ticking for S::par_agents -- but tick j's frame setup runs only where bit j
+// of the launch's mask (StepTicksArgs8::pad: a kernel argument, uniform) is set.  FRAMES = false (the mask is zero: a call that draws nothing, or a chunk in
+// front of the drawn tick's): no frame setup at all -- neither FrameScratch nor the depth sort's LDS is declared, since LDS and registers held by resident step
+// waves are what the passes beside them lose; with several agents the barrier behind the frame setups guards nothing and is gone, the one behind the tick stays
+// (tick j + 1 reads what the other waves' tick j wrote).  FRAMES = true: the last chunk of an MV_RENDER_LAST call, bit n - 1 set.
+template <class S, int A_MAX, class Args, bool FRAMES>
+__device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
+{
+    const int env = blockIdx.x;
+#ifdef MV_STEP_PRIO
+    __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
+#endif
+    if constexpr (!FRAMES) {
+        for (int j = 0; j < a.n; ++j) {
+            const GymView &gv = a.view(j);
+            if constexpr (A_MAX == 1) {
+                S::template tick<1>(gv, env);
+                wave_sync();       // the tick's stores before the next tick's loads (one wave: no barrier needed)
+            } else {
+                S::template tick<A_MAX, true>(gv, env);
+                __syncthreads();   // the tick's stores (same CU: same L1) before the next tick's loads
+            }
+        }
+    } else {
+        constexpr int NS = A_MAX == 1 ? 1 : 4;
+        __shared__ FrameScratch s_fs[NS];
+        const uint32_t mask = (uint32_t)a.pad;
+        for (int j = 0; j < a.n; ++j) {
+            const GymView &gv = a.view(j);
+            const bool frames = (mask >> j) & 1u;
+            if constexpr (A_MAX == 1) {
+                S::template tick<1>(gv, env);
+                wave_sync();   // the tick's stores before the frame setup's / the next tick's loads
+                if (frames) frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
+            } else {
+                S::template tick<A_MAX, true>(gv, env);
+                __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's / the next tick's loads
+                if (frames) {
+                    const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+                    for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
+                    __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
+                }
+            }
+        }
+    }
+}
+
 // Software-pipelined (one agent per env): TWO waves per env.  Wave 0 runs tick j + 1 while wave 1 sets tick j's frame up (mv_frame.h) -- the two halves of a
 // tick's work that step_ticks_body runs back to back in one wave, each a chain of dependent loads and a few thousand vector instructions of ONE wave on its
 // SIMD (48 % of the resident wave's cycles were spent in s_waitcnt, r08z_pmc_SQ2.csv).  The frame setup reads the simulator state in place, so the two waves
@@ -186,6 +234,11 @@ struct StepKernels {
     void (*ticks_agents)(StepTicksArgs8, int, int);      // k ticks, several agents per env
     void (*reset)(GymView, int);
     void (*reset_masked)(GymView, const uint8_t *, uint8_t *);   // mv_reset_envs: the envs a mask flags
+    // k ticks that set no frame up, and k ticks whose frame setups follow a mask (step_ticks_sim_body): one agent per env; several (TowerBuilding)
+    void (*ticks_sim)(StepTicksArgs8, int, int);
+    void (*ticks_sim_frames)(StepTicksArgs8, int, int);
+    void (*ticks_sim_agents)(StepTicksArgs8, int, int);
+    void (*ticks_sim_agents_frames)(StepTicksArgs8, int, int);
 };
 extern const StepKernels tower_kernels, obstacles_kernels, collect_kernels, rearrange_kernels, sokoban_kernels, hex_kernels, boxagone_kernels,
                           football_kernels;

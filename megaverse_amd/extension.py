@@ -39,7 +39,7 @@ SYMBOLS = [
     ("mv_step_many", C.c_int, [_P, _I, _I, _I, _U, _U]),
     ("mv_group_create", C.c_int, [_P, _I, C.POINTER(_P)]), ("mv_group_step", C.c_int, [_P, _I, _I, _I, _U, _U]), ("mv_group_destroy", C.c_int, [_P]),
     ("mv_step", C.c_int, [_P]), ("mv_step_no_render", C.c_int, [_P]), ("mv_render", C.c_int, [_P]),
-    ("mv_step_n", C.c_int, [_P, _I, _I, _U, _U]), ("mv_set_sample_policy", C.c_int, [_P, _I]),
+    ("mv_step_n", C.c_int, [_P, _I, _I, _U, _U]), ("mv_step_n_render", C.c_int, [_P, _I, _I, _U, _U, _I]), ("mv_set_sample_policy", C.c_int, [_P, _I]),
     ("mv_set_action_ring", C.c_int, [_P, _I, _P]), ("mv_debug_launch_counts", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("mv_fork_envs", C.c_int, [_P, _P]), ("mv_fork_envs_host", C.c_int, [_P, _P]), ("mv_debug_fork_plan_host", C.c_int, [_P, _I, _P, _P]),
     ("mv_debug_episodes_consumed", C.c_int, [_P, _P]), ("mv_fork_bytes_per_env", C.c_int64, [_P]),
@@ -200,6 +200,18 @@ def check_reset_mask(mask, num_envs):
     if m.shape != (n,) or m.dtype.kind not in 'bu' or (m.dtype.kind == 'u' and m.dtype.itemsize != 1):
         raise ValueError(f'reset_envs: the mask must be {n} bools (or uint8: non-zero = reset this env), got {m.dtype} {m.shape}')
     return np.ascontiguousarray(m != 0, dtype=np.uint8)
+
+
+# include/megaverse_hip.h: MV_RENDER_EVERY / MV_RENDER_LAST / MV_RENDER_NONE, by the names step_n(render=...) takes
+RENDER_MODES = {"every": 0, "last": 1, "none": 2}
+
+
+def render_mode_of(render):
+    """the argument check of MegaverseGym.step_n's render: 'every' | 'last' | 'none' -> MV_RENDER_*"""
+    try:
+        return RENDER_MODES[render]
+    except (KeyError, TypeError):
+        raise ValueError(f"step_n: render must be one of {sorted(RENDER_MODES)}, got {render!r}") from None
 
 
 def library_path():
@@ -410,10 +422,15 @@ class MegaverseGym:
 
     POLICIES = {"none": 0, "multidiscrete": 1, "single-bit": 2, "sequence": 3}
 
-    def step_n(self, k, policy="multidiscrete", seed=0, first_step_index=0):
+    def step_n(self, k, policy="multidiscrete", seed=0, first_step_index=0, render="every"):
         """k open-loop ticks (each stepped and rendered) with one call; tick j draws its actions from (policy, seed, first_step_index + j) --
-        policy 'sequence': it acts on entry (first_step_index + j) % count of the action ring (set_action_ring), seed is ignored"""
-        self._ckw(self._lib.mv_step_n(self._g, int(k), int(self.POLICIES.get(policy, policy)), int(seed) & 0xFFFFFFFF, int(first_step_index) & 0xFFFFFFFF))
+        policy 'sequence': it acts on entry (first_step_index + j) % count of the action ring (set_action_ring), seed is ignored.
+        render (include/megaverse_hip.h: mv_step_n_render): 'every' (default: mv_step_n itself); 'none': the ticks run, rewards and dones go where they
+        always go, nothing is drawn and no byte of the observation slab or ring is written; 'last': as 'none', and the call's last tick is drawn into its
+        own place."""
+        mode = render_mode_of(render)
+        args = (self._g, int(k), int(self.POLICIES.get(policy, policy)), int(seed) & 0xFFFFFFFF, int(first_step_index) & 0xFFFFFFFF)
+        self._ckw(self._lib.mv_step_n(*args) if mode == 0 else self._lib.mv_step_n_render(*args, mode))
         self._fork_held = self._reset_held = None
 
     def fork_envs(self, src_of):

@@ -18,7 +18,7 @@ Differences, all additive:
 import numpy as np
 
 from . import spaces
-from .extension import MegaverseGym, set_megaverse_log_level
+from .extension import MegaverseGym, render_mode_of, set_megaverse_log_level
 
 MEGAVERSE8 = ['TowerBuilding', 'ObstaclesEasy', 'ObstaclesHard', 'Collect', 'Sokoban', 'HexMemory', 'HexExplore', 'Rearrange']
 OBSTACLES_MULTITASK = ['ObstaclesWalls', 'ObstaclesSteps', 'ObstaclesLava', 'ObstaclesEasy', 'ObstaclesHard']
@@ -107,7 +107,7 @@ class MegaverseEnv:
         self._obs_tensor = None
         self._host_obs = None
         self._dev_out = None
-        self._seq = None   # step_sequence: (k, obs ring, rewards ring, dones ring, actions) while its rings are attached
+        self._seq = None   # step_sequence: ((k, render), obs ring or None, rewards ring, dones ring, actions) while its rings are attached
 
     @staticmethod
     def generate_action_space(action_space_sizes):
@@ -287,12 +287,16 @@ class MegaverseEnv:
         self.env.set_action_ring(0)
         self.env.render()
 
-    def step_sequence(self, actions):
+    def step_sequence(self, actions, render="every"):
         """k ticks on GIVEN actions as batched calls (mv_set_action_ring + mv_step_n with MV_POLICY_SEQUENCE): replaying a recorded trajectory, a scripted
         test, an open-loop plan, action repeat.  actions: [k, num_agents, 6] -- an integer numpy array, or an int32 CUDA tensor (read in place: unchanged until
         the stream has passed this call).  -> (obs uint8 [k, num_agents, 3, H, W], rewards float32 [k, num_agents], dones uint8 [k, num_envs]): CUDA tensors,
         entry j what tick j left, valid in the order of the gym's stream until the next stepping call (rings this env owns, as step_device's outputs).  k
-        may exceed what one call holds: it is stepped in chunks of recommended_ticks_per_call().  No host synchronisation."""
+        may exceed what one call holds: it is stepped in chunks of recommended_ticks_per_call().  No host synchronisation.
+        render (mv_step_n_render): 'every' as above; 'last': only the last tick is drawn, obs is [1, num_agents, 3, H, W] (a one-entry ring: nothing is
+        allocated for the ticks that are not drawn); 'none': nothing is drawn, obs is None and no observation ring exists.  Rewards and dones are the full
+        [k, ...] in every mode."""
+        mode = render_mode_of(render)
         k = check_sequence_actions(actions, self.num_agents)
         torch = self._torch()
         dev = torch.device(f'cuda:{self.device}')
@@ -300,21 +304,34 @@ class MegaverseEnv:
             held = actions.contiguous()
         else:
             held = torch.as_tensor(np.ascontiguousarray(actions, dtype=np.int32)).to(dev)
-        if self._seq is None or self._seq[0] != k:
+        if self._seq is None or self._seq[0] != (k, render):
             if self._obs_tensor is None:
                 self.observations_tensor()   # (the env's own slab exists before the rings take its place)
-            frame = (3, self.img_h, self.img_w) if self.obs_layout == 'chw' else (self.img_h, self.img_w, 4)
-            rings = (torch.zeros((k, self.num_agents) + frame, dtype=torch.uint8, device=dev), torch.zeros((k, self.num_agents), dtype=torch.float32, device=dev),
-                     torch.zeros((k, self.num_envs), dtype=torch.uint8, device=dev))
+            rings = (torch.zeros((k, self.num_agents), dtype=torch.float32, device=dev), torch.zeros((k, self.num_envs), dtype=torch.uint8, device=dev))
             self._dev_out = None   # (step_device attaches its own one-entry ring again)
-            self.env.set_output_ring(k, rings[0].data_ptr(), rings[1].data_ptr(), rings[2].data_ptr())   # tick j of a call -> entry j: every call is k ticks
+            # tick j of a call -> entry j: every call is k ticks
+            if render == "every":
+                frame = (3, self.img_h, self.img_w) if self.obs_layout == 'chw' else (self.img_h, self.img_w, 4)
+                rings = (torch.zeros((k, self.num_agents) + frame, dtype=torch.uint8, device=dev),) + rings
+                self.env.set_output_ring(k, rings[0].data_ptr(), rings[1].data_ptr(), rings[2].data_ptr())
+            else:   # ('last': the one drawn tick goes to the env's own slab -- a NULL ring keeps that output where it was)
+                rings = (None,) + rings
+                self.env.set_output_ring(k, 0, rings[1].data_ptr(), rings[2].data_ptr())
         else:
             rings = self._seq[1:4]
-        self._seq = (k,) + tuple(rings) + (held,)   # (the actions stay alive until the next call replaces them)
+        self._seq = ((k, render),) + tuple(rings) + (held,)   # (the actions stay alive until the next call replaces them)
         self.env.set_action_ring(k, held.data_ptr())
         chunk = max(1, self.env.recommended_ticks_per_call())
-        for done in range(0, k, chunk):
-            self.env.step_n(min(chunk, k - done), 'sequence', 0, done)
+        if render == "every":
+            for done in range(0, k, chunk):
+                self.env.step_n(min(chunk, k - done), 'sequence', 0, done)
+        else:   # (one call: which tick is the last is the call's to know; the library splits it)
+            self.env.step_n(k, 'sequence', 0, 0, render=render)
+        if mode == 2:
+            return None, rings[1], rings[2]
+        if mode == 1:
+            slab = self._obs_tensor.view((1, self.num_agents) + tuple(self._obs_tensor.shape[1:]))
+            return (slab if self.obs_layout == 'chw' else slab[..., :3].permute(0, 1, 4, 2, 3)), rings[1], rings[2]
         obs = rings[0] if self.obs_layout == 'chw' else rings[0][..., :3].permute(0, 1, 4, 2, 3)
         return obs, rings[1], rings[2]
 

@@ -254,7 +254,8 @@ class MultiTaskGym:
 
     def step_n(self, k, policy="multidiscrete", seed=0, first_step_index=0):
         """k open-loop ticks of every scenario with one call (union launches; mv_group_step); without the union (MV_MULTITASK_UNION=0, or more
-        scenarios than a group holds): k single steps of every sub-gym"""
+        scenarios than a group holds): k single steps of every sub-gym.  Every tick is drawn: groups keep their own render=True/False (GymGroup.step,
+        mv_group_step); the render modes of MegaverseGym.step_n ('last' / 'none') are a single gym's."""
         if not self.union:
             if policy == "sequence":   # (every sub-gym replays its own ring)
                 for g in self.gyms:
