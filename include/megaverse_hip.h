@@ -182,6 +182,32 @@ int64_t mv_resample_staging_bytes(const mv_gym *g);              /* 0 before the
  * Refused (-1 with text): no gym, a closed gym, before the first mv_reset, a null mask. */
 int mv_reset_envs(mv_gym *g, const uint8_t *device_mask, int32_t render);   /* mask [N] in device memory, read in the order of the gym's stream */
 int mv_reset_envs_host(mv_gym *g, const uint8_t *mask, int32_t render);     /* mask [N] in host memory */
+/* Step masks (no reference counterpart: VectorEnv::step steps every env, vector_env.cpp:89-108).  mask: one byte per env, [N]; a torch.bool tensor is such a
+ * mask, as in mv_reset_envs.  mask[e] != 0: env e steps.  mask[e] == 0: env e is FROZEN.  The mask stays attached, like an action ring, until it is detached
+ * (NULL) or replaced, and every tick of every later stepping call reads it: mv_step, mv_step_no_render, mv_step_n, mv_step_n_render in all three render modes,
+ * every policy.  With no mask attached everything is what it is without these calls, byte for byte and launch for launch.
+ * A frozen env on a tick: no byte of its episode state changes -- header (episode clock included), boxes, objects, agents, the scenario's own arrays, its
+ * status word, episodes_consumed, its ring of resident episodes, TowerBuilding's generator.  It takes no episode and cannot starve; a pending starved swap-in
+ * stays pending.  Its rewards are +0.0f and its done is 0, in the public arrays and in every ring entry of that tick; its true objectives stay what they were.
+ * Its actions for that tick -- pending mv_set_actions*, the action-ring entry, the random draw (counter-based: nothing to advance) -- are ignored and
+ * discarded: they do not wait for the thaw.  Tick indices stay the gym's: tick j of a call uses first_step_index + j for the envs that step, whatever is
+ * frozen; mv_ticks_since_reset and the output rings' tick count advance as always.
+ * Episode log (when on): a frozen tick adds nothing to the env's running returns or length and writes no record; a record written later has length = the
+ * ticks the env actually stepped, end_tick in the gym's tick count.
+ * Observation: drawn as always where the mode draws at all, from the unchanged state: a frozen env's frame is its current view, byte-identical to its
+ * previous one, time bar included.  (The frame setup and the raster of a frozen frame are not skipped.)
+ * Everything else acts regardless of the mask: mv_reset resets every env and leaves the mask attached; mv_reset_envs, mv_fork_envs* and mv_resample_envs*
+ * treat frozen envs like any other -- a frozen env as a fork source is a savepoint that keeps.
+ * Ordering: the call is an ordering point, as mv_set_action_ring is: whatever the caller enqueued on the gym's stream before it is ordered before the next
+ * step launch; the calls after that one pipeline freely.  Neither form waits on the host.  Device form: nothing is copied; the buffer is the caller's and
+ * stays unchanged until the caller's stream has passed the end of the last call that reads it; after rewriting it, call mv_set_step_mask again.  Host form:
+ * the bytes go to a gym-owned device buffer (allocated at first use, counted in mv_arena_bytes, freed by mv_close), by a copy ordered behind every step
+ * launch enqueued so far: a step kernel running ahead on the simulation stream never sees a half-written mask.
+ * Valid before the first mv_reset.  Refused (-1 with text): no gym, a closed gym, a gym in an mv_group; mv_group_create and mv_step_many refuse a gym with a
+ * mask attached (the union launches read none). */
+int mv_set_step_mask(mv_gym *g, const uint8_t *device_mask);   /* [N] in device memory; NULL detaches */
+int mv_set_step_mask_host(mv_gym *g, const uint8_t *mask);     /* [N] in host memory; NULL detaches */
+int mv_get_step_mask(const mv_gym *g);                         /* 0: none, 1: device form, 2: host form; -1: no gym */
 /* step several gyms of one job with one call (no reference counterpart: its multi-task runs are separate processes,
  * the scripts under megaverse_rl/runs): for each gym, optionally mv_sample_random_actions(seed, step_index), then mv_step / mv_step_no_render */
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index);
@@ -415,6 +441,10 @@ int mv_debug_collect_draw_host(int32_t num_agents, int32_t env_seed, int32_t n, 
  * and records, a buffer of `capacity` mv_episode_record of which *count are valid on entry. */
 int mv_debug_episode_log_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
                               uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped);
+/* ... with a step mask (mv_set_step_mask): step_mask [N] or NULL; the envs it freezes skip all k ticks.  NULL: mv_debug_episode_log_host, byte for byte. */
+int mv_debug_episode_log_masked_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A,
+                                     int32_t capacity, uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped,
+                                     const uint8_t *step_mask /* [N] or NULL */);
 /* Host-only (no device): the episode log's masked clear (megaverse_amd/csrc/mv_episode_log.h: episode_log_cut, the source mv_reset_envs' kernel runs) over N
  * envs x A agents: where mask[e] != 0, ret[e * A .. e * A + A - 1] and len[e] go to zero; everything else stays. */
 int mv_debug_episode_log_cut_host(const uint8_t *mask, int32_t N, int32_t A, double *ret, int32_t *len);

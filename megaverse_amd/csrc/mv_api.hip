@@ -755,6 +755,7 @@ int mv_close(mv_gym *g)
     if (g->hResetMask) (void)hipHostFree(g->hResetMask);
     for (hipEvent_t &e : g->resetMaskCopied) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     g->dResetMask = g->hResetMask = nullptr;
+    step_mask_free(g);
     if (g->arena) (void)hipFree(g->arena);
     if (g->hiresObs) (void)hipFree(g->hiresObs);
     if (g->hBlobs) (void)(g->blobsOnDevice ? hipFree(g->hBlobs) : hipHostFree(g->hBlobs));

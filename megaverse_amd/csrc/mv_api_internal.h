@@ -5,6 +5,7 @@
 //   mv_fork.hip       env forks: the gather-copy kernel and its entry points; the entry points of env resampling
 //   mv_resample.hip   env resampling: the two kernels of the staged copy
 //   mv_reset_envs.hip masked env resets: the host protocol around the reset_masked kernels (mv_step_kernels.h)
+//   mv_step_mask.hip  step masks: attaching and detaching the bytes that freeze envs (mv_step_kernels.h: frozen_tick)
 // The C ABI itself is include/megaverse_hip.h; nothing here is exported under a C name.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -229,6 +230,15 @@ struct mv_gym {
     uint8_t *dResetMask = nullptr, *hResetMask = nullptr;
     hipEvent_t resetMaskCopied[2] = {nullptr, nullptr};
     unsigned long long resetMaskUses = 0;
+    // mv_set_step_mask: the [N] bytes the step kernels read (GymView::step_mask through the stepping calls' views), null: no mask.  Form 1: the caller's
+    // buffer.  Form 2: dStepMask, gym-owned, allocated at the host form's first use and counted in mv_arena_bytes; its bytes travel through pinned staging
+    // buffers, each free again once the event behind its copy has completed (looked at with hipEventQuery: the call never waits on the host).
+    const uint8_t *stepMask = nullptr;
+    int stepMaskForm = 0;
+    uint8_t *dStepMask = nullptr;
+    size_t stepMaskBytes = 0;
+    struct MaskStaging { uint8_t *host; hipEvent_t copied; };
+    std::vector<MaskStaging> stepMaskStaging;
     // in-stream profiling
     std::vector<hipEvent_t> profEvents;          // 5 per profiled tick: [0] [1] around the step kernel (its stream), [2] [3] [4] before the
                                                  // observation pass, between frame sort and raster, after the raster (the caller's stream)
@@ -265,4 +275,5 @@ void group_detach(mv_gym *g);   // (mv_api_step.hip)
 int episode_log_update(mv_gym *g, const GymView *views, int stride, int k);
 int episode_log_reset(mv_gym *g);   // mv_reset: accumulators to zero, the records stay
 void episode_log_free(mv_gym *g);   // mv_close
+void step_mask_free(mv_gym *g);     // mv_close (mv_step_mask.hip)
 }  // namespace mvapi

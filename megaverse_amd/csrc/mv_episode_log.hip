@@ -64,13 +64,15 @@ __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
     const int NA = a.N * a.A, chunks = (NA + THREADS - 1) / THREADS;
     const uint32_t base = a.hdr->count;     // (thread 0 rewrites the header behind the last barrier)
     // the first chunk -- the only one up to 1024 agents -- is read once, here, for both passes over it
+    // (mv_set_step_mask) `in` below: the agent exists AND its env steps in this launch (episode_log_steps) -- the agents of a frozen env are passed over like
+    // the threads beyond the last agent: no done bit, no tick, and their running return is not written
     AgentTicks<KT> first_chunk;
-    load_agent(a, tid, tid < NA ? tid / a.A : 0, tid < NA, first_chunk);
+    load_agent(a, tid, tid < NA ? tid / a.A : 0, tid < NA && episode_log_steps(a.step_mask, tid / a.A), first_chunk);
 
     // ---- 1. finished agents per (tick, chunk, wave)
     for (int c = 0; c < chunks; ++c) {
         const int i = c * THREADS + tid;
-        const bool in = i < NA;
+        const bool in = i < NA && episode_log_steps(a.step_mask, i / a.A);
         const int e = in ? i / a.A : 0;
         uint32_t done = first_chunk.done;
         if (c > 0) {
@@ -119,7 +121,7 @@ __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
     // ---- 3. the ticks of every agent, in order; the records of the finishing ones
     for (int c = 0; c < chunks; ++c) {
         const int i = c * THREADS + tid;
-        const bool in = i < NA;
+        const bool in = i < NA && episode_log_steps(a.step_mask, i / a.A);
         const int e = in ? i / a.A : 0;
         AgentTicks<KT> v = first_chunk;
         if (c > 0) load_agent(a, i, e, in, v);
@@ -137,6 +139,7 @@ __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
     // and every one of them read len[e] above: nobody stores it before all have (the barrier), then one thread per env walks the env's ticks again.
     __syncthreads();
     for (int e = tid; e < a.N; e += THREADS) {
+        if (!episode_log_steps(a.step_mask, e)) continue;   // (a frozen env's length stays)
         uint8_t d[KT];
 #pragma unroll
         for (int t = 0; t < KT; ++t) d[t] = a.done[t < a.k ? t : a.k - 1][e];
@@ -199,6 +202,7 @@ int episode_log_update(mv_gym *g, const GymView *views, int stride, int k)
         a.first_tick = g->ticksSinceReset + (uint32_t)j0;
         a.hdr = g->logHdr; a.ret = g->logRet; a.len = g->logLen; a.records = g->logRecords;
         a.status = g->dStatus ? g->dStatus + g->N + 1 : nullptr;
+        a.step_mask = g->stepMask;
         launch_episode_log(a, g->stream);
     }
     HIP_TRY(hipGetLastError());
@@ -311,9 +315,10 @@ int64_t mv_ticks_since_reset(const mv_gym *g) { return g && !g->closed ? (int64_
 
 
 // The kernel's per-tick body compiled for the CPU (no device): k ticks of N envs x A agents through episode_log_tick in (tick, agent) order.
-// count, dropped, ret [N*A] and len [N] in and out; records: the buffer of `capacity` records, *count of them valid on entry.
-int mv_debug_episode_log_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
-                              uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped)
+// count, dropped, ret [N*A] and len [N] in and out; records: the buffer of `capacity` records, *count of them valid on entry.  step_mask [N] or null: the
+// envs it freezes skip every one of the k ticks (episode_log_steps).
+int mv_debug_episode_log_masked_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
+                                     uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped, const uint8_t *step_mask)
 {
     using namespace mv::elog;
     if (!rewards || !dones || !true_objectives || !ret || !len || !records || !count || !dropped || k < 0 || N < 1 || A < 1 || capacity < 1)
@@ -325,6 +330,7 @@ int mv_debug_episode_log_host(const float *rewards, const uint8_t *dones, const 
     for (int t = 0; t < k; ++t) {
         uint32_t placed = 0;
         for (int e = 0; e < N; ++e) {
+            if (!episode_log_steps(step_mask, e)) continue;
             int32_t after = len[e];
             for (int a = 0; a < A; ++a) {
                 const size_t i = (size_t)e * A + a;
@@ -342,6 +348,13 @@ int mv_debug_episode_log_host(const float *rewards, const uint8_t *dones, const 
     *count = h.count;
     *dropped = h.dropped;
     return 0;
+}
+
+// ... without a step mask: every env steps
+int mv_debug_episode_log_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
+                              uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped)
+{
+    return mv_debug_episode_log_masked_host(rewards, dones, true_objectives, k, N, A, capacity, first_tick, ret, len, records, count, dropped, nullptr);
 }
 
 // The masked clear of mv_reset_envs compiled for the CPU (no device): episode_log_cut over every agent of N envs x A agents.

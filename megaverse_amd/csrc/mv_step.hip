@@ -24,23 +24,36 @@ template <class Args, bool FRAMES> __global__ __launch_bounds__(256, 3) void ste
 __global__ __launch_bounds__(64) void reset_kernel(GymView gv, int force_all) { reset_body<S>(gv, force_all); }
 __global__ __launch_bounds__(64) void reset_masked_kernel(GymView gv, const uint8_t *mask, uint8_t *applied) { reset_masked_body<S>(gv, mask, applied); }
 
+// the same entry points for views with a step mask (mv_set_step_mask): the MASKED instantiations of the bodies (mv_step_kernels.h)
+template <int A_MAX> __global__ __launch_bounds__(256) void step_kernel_masked(GymView gv, int W, int H, int render) { step_body<S, A_MAX, true>(gv, blockIdx.x, W, H, render); }
+template <class Args> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_ticks_kernel_masked(Args a, int W, int H) { step_ticks_body<S, 1, true>(a, W, H); }
+template <class Args> __global__ __launch_bounds__(256, 3) void step_ticks_agents_kernel_masked(Args a, int W, int H) { step_ticks_body<S, MAX_AGENTS, true>(a, W, H); }
+template <class Args> __global__ __launch_bounds__(128, MV_STEP_TICKS_WAVES_PER_SIMD) void step_ticks_pipe_kernel_masked(Args a, int W, int H) { step_ticks_pipe_body<S, true>(a, W, H); }
+template <class Args, bool FRAMES> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_ticks_sim_kernel_masked(Args a, int W, int H) { step_ticks_sim_body<S, 1, Args, FRAMES, true>(a, W, H); }
+template <class Args, bool FRAMES> __global__ __launch_bounds__(256, 3) void step_ticks_sim_agents_kernel_masked(Args a, int W, int H) { step_ticks_sim_body<S, MAX_AGENTS, Args, FRAMES, true>(a, W, H); }
+
 const StepKernels tower_kernels = {step_kernel<1>, step_kernel<MAX_AGENTS>, step_ticks_kernel<StepTicksArgs8>, step_ticks_pipe_kernel<StepTicksArgs8>,
                                    step_ticks_agents_kernel<StepTicksArgs8>, reset_kernel, reset_masked_kernel,
                                    step_ticks_sim_kernel<StepTicksArgs8, false>, step_ticks_sim_kernel<StepTicksArgs8, true>,
                                    step_ticks_sim_agents_kernel<StepTicksArgs8, false>, step_ticks_sim_agents_kernel<StepTicksArgs8, true>};
+const StepKernels tower_kernels_masked = {step_kernel_masked<1>, step_kernel_masked<MAX_AGENTS>, step_ticks_kernel_masked<StepTicksArgs8>, step_ticks_pipe_kernel_masked<StepTicksArgs8>,
+                                   step_ticks_agents_kernel_masked<StepTicksArgs8>, reset_kernel, reset_masked_kernel,
+                                   step_ticks_sim_kernel_masked<StepTicksArgs8, false>, step_ticks_sim_kernel_masked<StepTicksArgs8, true>,
+                                   step_ticks_sim_agents_kernel_masked<StepTicksArgs8, false>, step_ticks_sim_agents_kernel_masked<StepTicksArgs8, true>};
 
-static const StepKernels &kernels_of(int scenario)
+// masked: the view carries a step mask (mv_set_step_mask) -- the MASKED instantiations; the gyms without one launch the kernels they always launched
+static const StepKernels &kernels_of(int scenario, bool masked = false)
 {
     switch (scenario) {
-    case SCN_TOWER: return tower_kernels;
+    case SCN_TOWER: return masked ? tower_kernels_masked : tower_kernels;
     case SCN_OBSTACLES:
-    case SCN_EMPTY: return obstacles_kernels;
-    case SCN_COLLECT: return collect_kernels;
-    case SCN_REARRANGE: return rearrange_kernels;
-    case SCN_SOKOBAN: return sokoban_kernels;
-    case SCN_BOXAGONE: return boxagone_kernels;
-    case SCN_FOOTBALL: return football_kernels;
-    default: return hex_kernels;   // SCN_HEX_MEMORY, SCN_HEX_EXPLORE
+    case SCN_EMPTY: return masked ? obstacles_kernels_masked : obstacles_kernels;
+    case SCN_COLLECT: return masked ? collect_kernels_masked : collect_kernels;
+    case SCN_REARRANGE: return masked ? rearrange_kernels_masked : rearrange_kernels;
+    case SCN_SOKOBAN: return masked ? sokoban_kernels_masked : sokoban_kernels;
+    case SCN_BOXAGONE: return masked ? boxagone_kernels_masked : boxagone_kernels;
+    case SCN_FOOTBALL: return masked ? football_kernels_masked : football_kernels;
+    default: return masked ? hex_kernels_masked : hex_kernels;   // SCN_HEX_MEMORY, SCN_HEX_EXPLORE
     }
 }
 
@@ -65,7 +78,7 @@ static bool step_pipe_enabled(const GymView &gv)
 void launch_step_ticks(const GymView *views, int k, hipStream_t stream, int W, int H, hipEvent_t done)
 {
     const GymView &gv = views[0];
-    const StepKernels &K = kernels_of(gv.scenario);
+    const StepKernels &K = kernels_of(gv.scenario, gv.step_mask != nullptr);
     StepTicksArgs8 a;   // (k <= 8: the views are the launch's arguments)
     a.n = k; a.pad = 0;
     for (int j = 0; j < 8; ++j) a.gv[j] = views[std::min(j, k - 1)];
@@ -81,7 +94,7 @@ void launch_step_ticks(const GymView *views, int k, hipStream_t stream, int W, i
 void launch_step_ticks_sim(const GymView *views, int k, unsigned frame_mask, hipStream_t stream, int W, int H, hipEvent_t done)
 {
     const GymView &gv = views[0];
-    const StepKernels &K = kernels_of(gv.scenario);
+    const StepKernels &K = kernels_of(gv.scenario, gv.step_mask != nullptr);
     StepTicksArgs8 a;
     a.n = k; a.pad = (int32_t)(frame_mask & ((1u << k) - 1u));
     for (int j = 0; j < 8; ++j) a.gv[j] = views[std::min(j, k - 1)];
@@ -94,7 +107,7 @@ void launch_step_ticks_sim(const GymView *views, int k, unsigned frame_mask, hip
 // done: an event that completes with the launch, carried by its dispatch packet (cf. mv_raster.h) -- TowerBuilding's launch only; -> whether it rides
 bool launch_step(const GymView &gv, hipStream_t stream, int W, int H, int render, hipEvent_t done)
 {
-    const StepKernels &K = kernels_of(gv.scenario);
+    const StepKernels &K = kernels_of(gv.scenario, gv.step_mask != nullptr);
     if (gv.scenario != SCN_TOWER) done = nullptr;
     const dim3 grid(gv.num_envs), block(gv.num_agents == 1 ? STEP_THREADS : 64 * std::min(gv.num_agents, 4));
     hipExtLaunchKernelGGL(gv.num_agents == 1 ? K.step : K.step_agents, grid, block, 0, stream, nullptr, done, 0, gv, W, H, render);

@@ -4,6 +4,7 @@
 //   S::swap_in(gv, env, force_all)         the episode swap-in of a finished (or forced) env
 //   S::long_lists                          frame lists long enough for the depth sort (mv_frame.h: DepthSortScratch)
 //   S::par_agents                          several agents: every wave of the workgroup takes part in the tick (TowerBuilding)
+// No tick knows about step masks (mv_set_step_mask): the MASKED instantiations of the bodies choose between S::tick and frozen_tick, below.
 // Every __global__ is a one-line entry point over a body in its scenario's mv_step_<scenario>.hip (a launch bound that depends on a template
 // parameter is not applied, and the profiles name the kernels); StepKernels lists them for the launchers (mv_step.hip).
 #pragma once
@@ -33,6 +34,54 @@ __device__ __forceinline__ DepthSortScratch *depth_sort_scratch(int i)
     }
 }
 
+// ---- mv_set_step_mask: frozen envs.  Whether env stands still in the ticks of this launch: its mask byte, loaded once and made uniform (as
+// reset_masked_body's).  The env is the workgroup, so every wave of it takes the same side of the choice and every barrier stays workgroup-uniform.  Every view
+// of a multi-tick launch carries the same mask (mv_api_step.hip; the buffer does not change while a call that reads it is in flight: include/megaverse_hip.h),
+// so such a launch asks once, through its first view.
+// Every body has a template parameter MASKED, and every step kernel two instantiations: the one a gym without a mask launches (MASKED = false) contains no
+// line of this -- it is the kernel it was, instruction for instruction -- and the one the launchers pick when the view carries a mask (mv_step.hip:
+// kernels_of).  In the masked one a frozen env takes a path of its own at the top of the body; the envs that step run the code they always ran.
+// profiles/step_mask_resources.txt has both instantiations' registers, scratch and LDS beside the parent's.
+__device__ __forceinline__ bool env_frozen(const GymView &gv, int env)
+{
+    return gv.step_mask != nullptr && __builtin_amdgcn_readfirstlane((int)gv.step_mask[env]) == 0;
+}
+
+// The tick of a frozen env, for every scenario: what a tick stages for its consumers says "nothing happened" -- the A rewards +0.0f, done 0 -- and the
+// actions the tick would have consumed are cleared as a tick clears them (env.cpp:141-142: they do not wait for the thaw).  No byte of the env's state, its
+// status word or its ring of episodes is read or written.  Called by every thread of the workgroup; the env's first threads store.
+__device__ __forceinline__ void frozen_tick(const GymView &gv, int env)
+{
+    const int A = gv.num_agents;
+    if ((int)threadIdx.x < A) {
+        gv.rewards[(size_t)env * A + threadIdx.x] = 0.0f;
+        gv.actions[(size_t)env * A + threadIdx.x] = 0;
+    }
+    if (threadIdx.x == 0) gv.done[env] = 0;
+}
+
+// The ticks of a frozen env in a multi-tick launch (one wave per env for one agent, every wave of the workgroup for several): frozen_tick, then the frame
+// setup of the ticks whose bit is set in `frames` -- from the unchanged state, so the frames come out as they were -- between the barriers the stepping
+// envs' loop has around it.
+template <class S, int A_MAX, int NS, class Args>
+__device__ __forceinline__ void frozen_ticks(const Args &a, int env, int W, int H, uint32_t frames, FrameScratch *s_fs)
+{
+    for (int j = 0; j < a.n; ++j) {
+        const GymView &gv = a.view(j);
+        frozen_tick(gv, env);
+        if (!((frames >> j) & 1u)) continue;
+        if constexpr (A_MAX == 1) {
+            wave_sync();
+            frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
+        } else {
+            __syncthreads();
+            const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+            for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
+            __syncthreads();
+        }
+    }
+}
+
 // One workgroup per env: wave 0 runs the tick (one wave per env: physics, scenario logic, auto-reset), the others wait at the barrier (S::par_agents:
 // they take their share of the character controllers first); then the workgroup builds the lists of the env's frames (mv_frame.h).  `render` = 0:
 // mv_step_no_render.
@@ -41,7 +90,7 @@ __device__ __forceinline__ DepthSortScratch *depth_sort_scratch(int i)
 //               tick PER ROUND: measured 41 us vs 25 us);
 //   A agents:   64 min(A, 4) threads, every wave sets up its own frame(s): a frame setup is a chain of dependent loads (~6 us), A of them
 //               one after the other would cost more than the launch the fusion saves.
-template <class S, int A_MAX>
+template <class S, int A_MAX, bool MASKED = false>
 __device__ __forceinline__ void step_body(const GymView &gv, const int env, int W, int H, int render)
 {
     constexpr int NS = A_MAX == 1 ? 1 : 4;
@@ -49,6 +98,17 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
 #ifdef MV_STEP_PRIO
     __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
 #endif
+    if constexpr (MASKED) if (env_frozen(gv, env)) {   // (mv_set_step_mask) the frozen tick, then the env's frames as below, from the unchanged state
+        frozen_tick(gv, env);
+        if (!render) return;
+        __syncthreads();
+        if constexpr (A_MAX == 1) frame_setup_body<STEP_THREADS, false>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
+        else {
+            const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+            for (int a = wave; a < A; a += nw) frame_setup_body<64, true>(gv, env * A + a, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
+        }
+        return;
+    }
     MV_T_BEGIN
 #ifdef MV_TICK_TIMING
     const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();   // 100 MHz
@@ -98,7 +158,7 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
 // workgroups stay resident for the whole call beside the observation passes of the previous one, and every wave of ~150 VGPRs they hold is
 // two or three waves the pass cannot have (measured: 21.1 M obs/s with two waves per env, 22.3 M with one).
 // Several agents (S::par_agents): every wave of the workgroup ticks, then sets up its share of the env's frames.
-template <class S, int A_MAX, class Args>
+template <class S, int A_MAX, bool MASKED = false, class Args>
 __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
 {
     constexpr int NS = A_MAX == 1 ? 1 : 4;
@@ -107,6 +167,7 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
 #ifdef MV_STEP_PRIO
     __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
 #endif
+    if constexpr (MASKED) if (env_frozen(a.view(0), env)) { frozen_ticks<S, A_MAX, NS>(a, env, W, H, ~0u, s_fs); return; }   // (mv_set_step_mask)
     for (int j = 0; j < a.n; ++j) {
         const GymView &gv = a.view(j);
         if constexpr (A_MAX == 1) {
@@ -129,7 +190,7 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
 // front of the drawn tick's): no frame setup at all -- neither FrameScratch nor the depth sort's LDS is declared, since LDS and registers held by resident step
 // waves are what the passes beside them lose; with several agents the barrier behind the frame setups guards nothing and is gone, the one behind the tick stays
 // (tick j + 1 reads what the other waves' tick j wrote).  FRAMES = true: the last chunk of an MV_RENDER_LAST call, bit n - 1 set.
-template <class S, int A_MAX, class Args, bool FRAMES>
+template <class S, int A_MAX, class Args, bool FRAMES, bool MASKED = false>
 __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
 {
     const int env = blockIdx.x;
@@ -137,6 +198,10 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
     __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
 #endif
     if constexpr (!FRAMES) {
+        if constexpr (MASKED) if (env_frozen(a.view(0), env)) {   // (mv_set_step_mask) a frozen env's waves leave behind one mask load and n tiny stores
+            for (int j = 0; j < a.n; ++j) frozen_tick(a.view(j), env);
+            return;
+        }
         for (int j = 0; j < a.n; ++j) {
             const GymView &gv = a.view(j);
             if constexpr (A_MAX == 1) {
@@ -151,6 +216,7 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
         constexpr int NS = A_MAX == 1 ? 1 : 4;
         __shared__ FrameScratch s_fs[NS];
         const uint32_t mask = (uint32_t)a.pad;
+        if constexpr (MASKED) if (env_frozen(a.view(0), env)) { frozen_ticks<S, A_MAX, NS>(a, env, W, H, mask, s_fs); return; }   // (mv_set_step_mask)
         for (int j = 0; j < a.n; ++j) {
             const GymView &gv = a.view(j);
             const bool frames = (mask >> j) & 1u;
@@ -178,7 +244,7 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
 //   A(j): tick j's state is written (wave 0: behind its write-back and the episode swap-in of a finished env; wave 1: before it reads anything)
 //   B(j): tick j's state is read    (wave 1: behind the record loads of its last round of slots; wave 0: before tick j + 1's write-back, the tick's
 // pipe_wait) An iteration lasts max(tick, frame setup) instead of their sum; the last frame setup runs alone.
-template <class S, class Args>
+template <class S, bool MASKED = false, class Args>
 __device__ __forceinline__ void step_ticks_pipe_body(const Args &a, int W, int H)
 {
     __shared__ FrameScratch s_fs;
@@ -187,6 +253,15 @@ __device__ __forceinline__ void step_ticks_pipe_body(const Args &a, int W, int H
     __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
 #endif
     if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0) {
+        if constexpr (MASKED) if (env_frozen(a.view(0), env)) {   // (mv_set_step_mask) the frozen ticks at the barriers of the stepping ones; wave 1 sets the frames up as always
+            for (int j = 0; j < a.n; ++j) {
+                if (j > 0) __syncthreads();               // B(j - 1): inside a tick (pipe_wait), here in the open
+                frozen_tick(a.view(j), env);
+                __syncthreads();                          // A(j)
+            }
+            __syncthreads();                              // B(n - 1)
+            return;
+        }
         for (int j = 0; j < a.n; ++j) {
             S::template tick<1>(a.view(j), env, j > 0);   // (j > 0: B(j - 1) inside, before the write-back)
             __syncthreads();                              // A(j)
@@ -240,7 +315,10 @@ struct StepKernels {
     void (*ticks_sim_agents)(StepTicksArgs8, int, int);
     void (*ticks_sim_agents_frames)(StepTicksArgs8, int, int);
 };
+// (<scenario>_kernels_masked: the MASKED instantiations of the step entries, for views with a step mask; the reset entries are the same kernels)
 extern const StepKernels tower_kernels, obstacles_kernels, collect_kernels, rearrange_kernels, sokoban_kernels, hex_kernels, boxagone_kernels,
                           football_kernels;
+extern const StepKernels tower_kernels_masked, obstacles_kernels_masked, collect_kernels_masked, rearrange_kernels_masked, sokoban_kernels_masked,
+                          hex_kernels_masked, boxagone_kernels_masked, football_kernels_masked;
 
 }  // namespace mv

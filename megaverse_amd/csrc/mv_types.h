@@ -189,6 +189,9 @@ struct GymView {
     struct TowerGen *tower_gen;// [N] TowerBuilding: where each env's episode generator stands (mv_reset_device.h: tower_draw); its resident episodes are `blobs` (TowerBlob)
     struct BoxAGoneState *bag; // [N] BoxAGone: platform table, temporary ring, cell map (its drawables: hex_boxes)
     struct FootballState *fb;  // [N] Football: the ball (its drawables: hex_boxes, hex_objs)
+    // mv_set_step_mask: [N] bytes, 0 = the env is frozen -- this tick leaves its state alone (mv_step_kernels.h: frozen_tick); null: no mask, every env
+    // steps.  Set by the stepping calls only (mv_api_step.hip): the views of resets, forks and the union launches leave it null.
+    const uint8_t *step_mask;
 };
 
 // The n <= 8 consecutive ticks of a multi-tick step launch (mv_step.hip: step_ticks_kernel, and every mv_step_*.hip), the same envs in all of them: their views

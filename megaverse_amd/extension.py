@@ -85,6 +85,8 @@ SYMBOLS = [
     ("mv_episode_log_records_device_ptr", _P, [_P]), ("mv_episode_log_count_device_ptr", _P, [_P]),
     ("mv_episode_returns_device_ptr", _P, [_P]), ("mv_episode_lengths_device_ptr", _P, [_P]), ("mv_ticks_since_reset", C.c_int64, [_P]),
     ("mv_debug_episode_log_host", C.c_int, [_P, _P, _P, _I, _I, _I, _I, _U, _P, _P, _P, C.POINTER(_U), C.POINTER(_U)]),
+    ("mv_set_step_mask", C.c_int, [_P, _P]), ("mv_set_step_mask_host", C.c_int, [_P, _P]), ("mv_get_step_mask", C.c_int, [_P]),
+    ("mv_debug_episode_log_masked_host", C.c_int, [_P, _P, _P, _I, _I, _I, _I, _U, _P, _P, _P, C.POINTER(_U), C.POINTER(_U), _P]),
 ]
 
 # mv_episode_record (include/megaverse_hip.h): one finished episode of one agent, 24 bytes
@@ -103,6 +105,16 @@ def debug_episode_log_host(rewards, dones, true_objectives, agents_per_env, capa
     """mv_debug_episode_log_host: the episode log's per-tick body on the CPU (no device).  rewards / true_objectives [k][N*A] float32, dones [k][N] uint8.
     state: what an earlier call returned (carried on), or None for a log just switched on.  -> state = {'ret', 'len', 'records', 'count', 'dropped'};
     state['records'][:state['count']] is the log."""
+    return _episode_log_host(False, None, rewards, dones, true_objectives, agents_per_env, capacity, first_tick, state)
+
+
+def debug_episode_log_masked_host(step_mask, rewards, dones, true_objectives, agents_per_env, capacity, first_tick=0, state=None):
+    """mv_debug_episode_log_masked_host: debug_episode_log_host with a step mask (mv_set_step_mask) -- step_mask: [N] raw bytes, the envs whose byte is 0
+    skip all k ticks; None: the hook's NULL mask, every env steps."""
+    return _episode_log_host(True, step_mask, rewards, dones, true_objectives, agents_per_env, capacity, first_tick, state)
+
+
+def _episode_log_host(masked, step_mask, rewards, dones, true_objectives, agents_per_env, capacity, first_tick, state):
     lib = load_library()
     rewards = np.ascontiguousarray(rewards, np.float32)
     dones = np.ascontiguousarray(dones, np.uint8)
@@ -115,9 +127,16 @@ def debug_episode_log_host(rewards, dones, true_objectives, agents_per_env, capa
         state = {"ret": np.zeros(N * A, np.float64), "len": np.zeros(N, np.int32), "records": np.zeros(max(int(capacity), 0), EPISODE_RECORD_DTYPE),
                  "count": 0, "dropped": 0}
     count, dropped = _U(state["count"]), _U(state["dropped"])
-    if lib.mv_debug_episode_log_host(rewards.ctypes.data, dones.ctypes.data, true_objectives.ctypes.data, k, N, A, int(capacity), int(first_tick) & 0xFFFFFFFF,
-                                     state["ret"].ctypes.data, state["len"].ctypes.data, state["records"].ctypes.data,
-                                     C.byref(count), C.byref(dropped)) != 0:
+    args = (rewards.ctypes.data, dones.ctypes.data, true_objectives.ctypes.data, k, N, A, int(capacity), int(first_tick) & 0xFFFFFFFF,
+            state["ret"].ctypes.data, state["len"].ctypes.data, state["records"].ctypes.data, C.byref(count), C.byref(dropped))
+    if not masked:
+        rc = lib.mv_debug_episode_log_host(*args)
+    else:
+        m = None if step_mask is None else np.ascontiguousarray(step_mask, np.uint8).reshape(-1)   # (the raw bytes: any non-zero byte steps)
+        if m is not None and m.size != N:
+            raise ValueError("debug_episode_log_masked_host: step_mask is [N] bytes")
+        rc = lib.mv_debug_episode_log_masked_host(*args, None if m is None else m.ctypes.data)
+    if rc != 0:
         raise RuntimeError(lib.mv_last_error().decode())
     state["count"], state["dropped"] = int(count.value), int(dropped.value)
     return state
@@ -185,21 +204,33 @@ def debug_episode_log_cut_host(mask, agents_per_env, ret, length):
         raise RuntimeError(lib.mv_last_error().decode())
 
 
-def check_reset_mask(mask, num_envs):
-    """the argument check of MegaverseGym.reset_envs: a CUDA bool / uint8 tensor (or anything with data_ptr()) of shape (num_envs,) -> 'device'; anything else
-    -> a contiguous uint8 numpy array, one byte per env"""
+def _check_env_mask(mask, num_envs, who, non_zero):
+    """one byte per env, for `who`: a CUDA bool / uint8 tensor (or anything with data_ptr()) of shape (num_envs,) -> 'device'; anything else -> a contiguous
+    uint8 numpy array; non_zero: what a set byte means, for the error text"""
     n = int(num_envs)
     if hasattr(mask, 'data_ptr'):
         contiguous = getattr(mask, 'is_contiguous', None)
         if tuple(getattr(mask, 'shape', ())) != (n,) or str(getattr(mask, 'dtype', None)) not in ('torch.bool', 'torch.uint8') \
                 or not getattr(mask, 'is_cuda', False) or not (callable(contiguous) and contiguous()):
-            raise ValueError(f'reset_envs: a tensor mask must be a contiguous bool or uint8 CUDA tensor of shape ({n},), '
+            raise ValueError(f'{who}: a tensor mask must be a contiguous bool or uint8 CUDA tensor of shape ({n},), '
                              f"got {getattr(mask, 'dtype', None)} {tuple(getattr(mask, 'shape', ()))} on {getattr(mask, 'device', 'an unknown device')}")
         return 'device'
     m = np.asarray(mask)
     if m.shape != (n,) or m.dtype.kind not in 'bu' or (m.dtype.kind == 'u' and m.dtype.itemsize != 1):
-        raise ValueError(f'reset_envs: the mask must be {n} bools (or uint8: non-zero = reset this env), got {m.dtype} {m.shape}')
+        raise ValueError(f'{who}: the mask must be {n} bools (or uint8: non-zero = {non_zero}), got {m.dtype} {m.shape}')
     return np.ascontiguousarray(m != 0, dtype=np.uint8)
+
+
+def check_reset_mask(mask, num_envs):
+    """the argument check of MegaverseGym.reset_envs: a CUDA bool / uint8 tensor (or anything with data_ptr()) of shape (num_envs,) -> 'device'; anything else
+    -> a contiguous uint8 numpy array, one byte per env"""
+    return _check_env_mask(mask, num_envs, 'reset_envs', 'reset this env')
+
+
+def check_step_mask(mask, num_envs):
+    """the argument check of MegaverseGym.set_step_mask: None (detach) -> None; otherwise check_reset_mask's rules -- a contiguous bool / uint8 CUDA tensor of
+    shape (num_envs,) -> 'device'; anything else -> a contiguous uint8 numpy array, one byte per env (non-zero: the env steps, 0: it is frozen)"""
+    return None if mask is None else _check_env_mask(mask, num_envs, 'set_step_mask', 'the env steps')
 
 
 # include/megaverse_hip.h: MV_RENDER_EVERY / MV_RENDER_LAST / MV_RENDER_NONE, by the names step_n(render=...) takes
@@ -306,6 +337,7 @@ class MegaverseGym:
         self.render_w, self.render_h = 768, 432
         self._fork_held = None   # fork_envs: the caller's device map, kept until the next step has been enqueued
         self._reset_held = None  # reset_envs: the caller's device mask, likewise
+        self._step_mask_held = None  # set_step_mask: the caller's device mask, kept until it is replaced or detached
 
     def _ck(self, rc):
         if rc < 0:
@@ -476,6 +508,28 @@ class MegaverseGym:
             self._reset_held = mask
         else:
             self._ckw(self._lib.mv_reset_envs_host(self._g, m.ctypes.data, int(bool(render))))
+
+    STEP_MASK_FORMS = ("none", "device", "host")
+
+    def set_step_mask(self, mask):
+        """Step masks (include/megaverse_hip.h: mv_set_step_mask): mask[e] non-zero: env e steps; 0: env e is frozen -- every tick of every later stepping
+        call leaves its state alone, reports reward 0 and done 0 for it and discards its actions -- until the mask is replaced or detached (None).  A
+        contiguous torch.bool / uint8 CUDA tensor of shape (num_envs,) is read in place by the step kernels (the gym holds a reference; after rewriting it,
+        call this again); a numpy array or a sequence of bools is copied to a buffer of the gym's.  Neither form waits on the host."""
+        m = check_step_mask(mask, self.num_envs)
+        if m is None:
+            self._ck(self._lib.mv_set_step_mask(self._g, None))
+            self._step_mask_held = None
+        elif isinstance(m, str):
+            self._ck(self._lib.mv_set_step_mask(self._g, _P(int(mask.data_ptr()))))
+            self._step_mask_held = mask
+        else:
+            self._ck(self._lib.mv_set_step_mask_host(self._g, m.ctypes.data))
+            self._step_mask_held = None
+
+    def step_mask(self):
+        """-> 'none' | 'device' | 'host': the form of the step mask attached (set_step_mask)"""
+        return self.STEP_MASK_FORMS[self._ck(self._lib.mv_get_step_mask(self._g))]
 
     def set_action_ring(self, count, device_ptr=0):
         """int32 [count, num_agents, 6] multi-discrete actions in device memory for step_n(..., 'sequence') (include/megaverse_hip.h: mv_set_action_ring);

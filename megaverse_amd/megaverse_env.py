@@ -108,6 +108,7 @@ class MegaverseEnv:
         self._host_obs = None
         self._dev_out = None
         self._seq = None   # step_sequence: ((k, render), obs ring or None, rewards ring, dones ring, actions) while its rings are attached
+        self._frozen = np.zeros(self.num_envs, np.bool_)   # freeze / thaw: the envs this env keeps frozen through a host step mask
 
     @staticmethod
     def generate_action_space(action_space_sizes):
@@ -276,6 +277,34 @@ class MegaverseEnv:
         m = np.zeros(self.num_envs, np.bool_)
         m[ids] = True
         self.env.reset_envs(m, render)
+
+    def set_step_mask(self, mask):
+        """Step masks (MegaverseGym.set_step_mask): mask[e] true: env e steps; false: env e is frozen -- step, step_batched, step_device and step_sequence
+        leave its state alone, report reward 0 and done 0 for it and discard its actions, and its observation stays its current view -- until the mask is
+        replaced or detached (None).  A bool / uint8 CUDA tensor is read in place (rewrite it, then call this again); a numpy array or a sequence is copied.
+        freeze / thaw keep a mask of their own: a mask set here replaces it."""
+        self.env.set_step_mask(mask)
+        self._frozen[:] = False
+
+    def _env_ids(self, env_ids, who):
+        ids = np.asarray(list(env_ids), dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= self.num_envs):
+            raise ValueError(f'{who}: env_ids must be within 0 .. {self.num_envs - 1}')
+        return ids
+
+    def freeze(self, env_ids):
+        """the envs of env_ids stand still from the next tick on (a host step mask this env keeps): savepoints to fork from, envs whose evaluation episode
+        is over, envs whose action is not ready.  Envs frozen earlier stay frozen."""
+        self._frozen[self._env_ids(env_ids, 'freeze')] = True
+        self.env.set_step_mask(~self._frozen)
+
+    def thaw(self, env_ids=None):
+        """the envs of env_ids (default: all) step again; with none left frozen the mask is detached"""
+        if env_ids is None:
+            self._frozen[:] = False
+        else:
+            self._frozen[self._env_ids(env_ids, 'thaw')] = False
+        self.env.set_step_mask(~self._frozen if self._frozen.any() else None)
 
     def _leave_sequence(self):
         """step_sequence's rings are attached: back to the single slab and arrays, the slab brought up to date"""
