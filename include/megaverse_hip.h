@@ -208,6 +208,46 @@ int mv_reset_envs_host(mv_gym *g, const uint8_t *mask, int32_t render);     /* m
 int mv_set_step_mask(mv_gym *g, const uint8_t *device_mask);   /* [N] in device memory; NULL detaches */
 int mv_set_step_mask_host(mv_gym *g, const uint8_t *mask);     /* [N] in host memory; NULL detaches */
 int mv_get_step_mask(const mv_gym *g);                         /* 0: none, 1: device form, 2: host form; -1: no gym */
+/* Env stores (no reference counterpart): an env's episode state saved into a RECORD of a caller-owned store, and a record loaded back into any env -- of
+ * this gym, or of another gym of the same configuration.  A savepoint no longer costs a live env: a search keeps as many states as the store has slots, and
+ * a state can leave its gym -- to another gym, another GPU's shard, host memory or a file (the store is plain memory: copy it).
+ * A STORE is caller-owned device memory: `slots` records of mv_env_record_bytes(g) bytes each, 16-byte aligned; a torch.uint8 tensor [slots, record_bytes]
+ * is one.  The gym never allocates, frees or remembers it, and mv_arena_bytes counts nothing for it.
+ * A RECORD (megaverse_amd/csrc/mv_env_store.h states the layout once): a 64-byte record header {magic, format version, layout word, record bytes, flags};
+ * the whole EnvHeader (the identity's dwords are stored too; a load ignores them); every per-env array of the fork's episode state, in the table's order,
+ * each from a 16-byte boundary with its whole stride; the episode log's accumulators, double ret[A] and int32 len -- always present; a header flag says
+ * whether the log was on at save time, and they are written as zero when it was off.
+ * The LAYOUT WORD is a hash of the format version, the scenario (id and name: the six Obstacles variants differ), the agents per env, the observation width
+ * and height, every float parameter's key and value, and every state array's bytes per env.  Two gyms with the same word can exchange records.  It does not
+ * depend on num_envs, the seed, the pixel mode, the observation layout, the env sharding or the episode log.
+ * slot_of: int32 [N].
+ * mv_save_envs: slot_of[e] = m, 0 <= m < slots, writes env e's current episode state into record m; -1: env e is not saved.  Nothing in the gym changes, not
+ * one byte.  Invalid: an index out of range, and two envs that name one slot -- both entries are invalid, neither is written.  A record is written whole or
+ * not at all.
+ * mv_load_envs: slot_of[d] = m makes env d leave its running episode and continue record m's; -1 leaves env d alone; any number of envs may load one record.
+ * What is written is what mv_fork_envs writes into a destination -- the header without the identity's dwords, every state array, and, where the gym's log
+ * is on, the accumulators: the record's if it was saved with the log on, else zero, so that the episode counts from the load, as when the log is switched
+ * on mid-episode.  What stays is the fork's identity list, word for word (above).  Not touched: the public rewards, dones and true objectives, the output
+ * rings, the observation slab, pending actions, the step mask -- a frozen env can be loaded into, like a fork destination.  Invalid: an index out of range,
+ * and a RECORD THAT DOES NOT START WITH the magic, this format version, this gym's layout word and this record size -- a slot never written, a record of
+ * another configuration.  Such an entry changes no byte of its env.  Only the kernel can make that check, so both load forms rely on it.  The header is a
+ * guard against accidents, not an authenticator: the bytes behind a header that matches are trusted.
+ * Invalid entries: the host forms validate the map on the host (-1 with text, nothing copied; a map of -1s launches nothing).  A kernel skips an invalid
+ * entry and raises a status bit; the NEXT stepping call reports it once as return 1 with a warning that names mv_save_envs / mv_load_envs.  That call waits
+ * for the status words behind the launch: the one host wait the device forms cost -- and mv_load_envs_host too, since record headers are visible on the
+ * device only.  mv_save_envs_host validates everything on the host and costs none.
+ * Ordering: mv_fork_envs' rules.  Every form runs on the gym's (the caller's) stream -- the store is the caller's memory -- behind every step launch
+ * enqueued so far and behind the episode log's last update; the next step launch runs behind it (it overwrites what a save reads and reads what a load
+ * writes).  Nothing else is ordered behind a save: the caller's stream sees the record complete.  No form waits on the host.  Map and store stay unchanged
+ * until the launch has run -- in stream order: until the next stepping call has been enqueued.  Host maps travel through the forks' pinned double buffer.
+ * Refused (-1 with text): no gym, a closed gym, before the first mv_reset, a null map or store, slots <= 0, a store that is not 16-byte aligned, a gym in an
+ * mv_group.  Out of scope: groups, records across format versions, compression. */
+int64_t mv_env_record_bytes(const mv_gym *g);    /* a multiple of 16; -1: no gym */
+uint64_t mv_env_record_layout(const mv_gym *g);  /* two gyms with the same word can exchange records; 0: no gym */
+int mv_save_envs(mv_gym *g, const int32_t *device_slot_of, void *device_store, int32_t slots);
+int mv_save_envs_host(mv_gym *g, const int32_t *slot_of, void *device_store, int32_t slots);
+int mv_load_envs(mv_gym *g, const int32_t *device_slot_of, const void *device_store, int32_t slots);
+int mv_load_envs_host(mv_gym *g, const int32_t *slot_of, const void *device_store, int32_t slots);
 /* step several gyms of one job with one call (no reference counterpart: its multi-task runs are separate processes,
  * the scripts under megaverse_rl/runs): for each gym, optionally mv_sample_random_actions(seed, step_index), then mv_step / mv_step_no_render */
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index);
@@ -460,6 +500,20 @@ int mv_debug_resample_plan_host(const int32_t *src_of, int32_t N, int32_t *resol
  * the code the kernels use; invalid entries are skipped.  order: the envs of each phase are visited ascending (0), descending (1) or in a fixed
  * pseudo-random order (2) -- the result does not depend on it. */
 int mv_debug_resample_apply_host(const int32_t *src_of, int32_t N, int32_t bytes_per_env, uint8_t *state, int32_t order);
+/* Host-only (no device): the rule of an env-store map (megaverse_amd/csrc/mv_env_store.h, the source the kernels and the host forms run) applied to every
+ * entry of slot_of [N] for a store of `slots` records: is_save != 0: mv_save_envs' rule (out of range, or a slot named twice: invalid), else mv_load_envs'
+ * (out of range only).  resolved[e] = the slot, or -1 (not named, or skipped).  The tabulated host rule is checked against the per-entry rule. */
+int mv_debug_env_store_plan_host(const int32_t *slot_of, int32_t N, int32_t slots, int32_t is_save, int32_t *resolved /* [N] */, int32_t *invalid /* [N] */);
+/* Host-only (no device): a record's layout for `count` state arrays of array_bytes[k] bytes per env and A agents: offsets [count + 3] = where the EnvHeader,
+ * each array, ret and len lie -> the record's bytes. */
+int64_t mv_debug_env_record_layout_host(const uint32_t *array_bytes, int32_t count, int32_t A, uint32_t *offsets);
+/* Host-only (no device): an env in host memory -- its 128-byte EnvHeader, its `count` arrays, double ret[A], int32 len, one behind the other -- packed into
+ * a record / a record unpacked into such an env, by the functions the kernels use.  log_on: whether the (saving / loading) gym's episode log is on.  Unpack
+ * returns 1 and changes nothing when the record's header does not match (layout_word, the record size these arrays imply, the format). */
+int mv_debug_env_record_pack_host(const uint32_t *array_bytes, int32_t count, int32_t A, uint64_t layout_word, int32_t log_on, const uint8_t *env_state_in,
+                                  uint8_t *record_out);
+int mv_debug_env_record_unpack_host(const uint32_t *array_bytes, int32_t count, int32_t A, uint64_t layout_word, int32_t log_on, const uint8_t *record_in,
+                                    uint8_t *env_state_inout);
 /* out_host [N]: how many episodes of its own sequence every env has taken so far (a fork leaves the destination's count alone) */
 int mv_debug_episodes_consumed(mv_gym *g, int32_t *out_host);
 int mv_debug_collect_draw_device(int32_t device, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n, float base_episode_len, void *out,

@@ -544,6 +544,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     }
     g->obst = oc;
     g->baseEpisodeLen = episodeLen;
+    g->envRecordLayout = env_record_layout_word(g, scen, cfg);
     {   // status words (episodes consumed, error flags) travel back on a side stream for every scenario
         bool ok = hipHostMalloc((void **)&g->hStatus, (N + 2) * sizeof(int), hipHostMallocDefault) == hipSuccess &&
                   hipStreamCreateWithFlags(&g->copyStream, hipStreamNonBlocking) == hipSuccess &&
@@ -944,6 +945,8 @@ int check_status_flags(mv_gym *g)
         "destination); those envs were left as they were; ";
     if (flags & ST_RESAMPLE) msg += "mv_resample_envs skipped entries of its map whose index is out of range (-1, or 0 .. num_envs - 1); those envs were left as "
         "they were; ";
+    if (flags & ST_ENV_STORE) msg += "mv_save_envs / mv_load_envs skipped entries of its map (an index out of range; a save slot that two envs name; a load from a "
+        "record that this gym did not write: a slot never saved, or a record of another configuration); those records and envs were left as they were; ";
     if (gen & GEN_SLABS) msg += "a generated layout merged into more slabs than an episode record holds (128, Collect 1024): the excess was dropped; ";
     if (gen & GEN_TERRAIN) msg += "more than 16 terrain boxes in a generated episode; ";
     if (gen & GEN_OBJECTS) msg += "more than 80 movable boxes in a generated episode; ";

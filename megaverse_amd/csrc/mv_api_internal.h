@@ -5,6 +5,7 @@
 //   mv_fork.hip       env forks: the gather-copy kernel and its entry points; the entry points of env resampling
 //   mv_resample.hip   env resampling: the two kernels of the staged copy
 //   mv_reset_envs.hip masked env resets: the host protocol around the reset_masked kernels (mv_step_kernels.h)
+//   mv_env_store.hip  env stores: the save / load kernels, their entry points and host-only hooks
 //   mv_step_mask.hip  step masks: attaching and detaching the bytes that freeze envs (mv_step_kernels.h: frozen_tick)
 // The C ABI itself is include/megaverse_hip.h; nothing here is exported under a C name.
 #pragma once
@@ -222,6 +223,8 @@ struct mv_gym {
     // per env), allocated at the first call and counted in mv_arena_bytes from then on
     uint8_t *resampleArena = nullptr;
     size_t resampleBytes = 0;
+    // mv_save_envs / mv_load_envs: the layout word of this gym's records (mv_env_store.h); the gym owns no store
+    uint64_t envRecordLayout = 0;
     // "the next stepping call waits for the status words" (refill_episodes): something only a kernel saw has to be reported by that call -- a fork's device map
     // may have held invalid entries (ST_FORK), a masked reset from a device mask may have found a host-fed env without a resident episode (ST_STARVED)
     bool statusReportDue = false;
@@ -276,4 +279,10 @@ int episode_log_update(mv_gym *g, const GymView *views, int stride, int k);
 int episode_log_reset(mv_gym *g);   // mv_reset: accumulators to zero, the records stay
 void episode_log_free(mv_gym *g);   // mv_close
 void step_mask_free(mv_gym *g);     // mv_close (mv_step_mask.hip)
+// mv_fork.hip, shared with mv_env_store.hip: what every fork / resample / env-store form refuses (what: "forks", "env stores": for the text about groups), and
+// a host map's way to the device through the pinned double buffer
+int fork_check(mv_gym *g, const void *map, const char *who, const char *what = "forks");
+int stage_fork_map(mv_gym *g, const int32_t *host_map, hipStream_t s, const int32_t **device_map);
+// mv_env_store.hip: the layout word of g's records (mv_create, once the table and the parameters are known)
+uint64_t env_record_layout_word(const mv_gym *g, const std::string &scenario_name, const mv_config *cfg);
 }  // namespace mvapi

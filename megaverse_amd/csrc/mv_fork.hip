@@ -97,17 +97,43 @@ void launch_fork(const Table &t, const int32_t *device_src_of, int32_t N, int32_
 }  // namespace fork
 }  // namespace mv
 
-namespace {
+namespace mvapi {
 
-// what every form refuses: no gym, a closed one, a null map, a gym that was never reset, a member of a group
-int fork_check(mv_gym *g, const void *map, const char *who)
+// what every form refuses: no gym, a closed one, a null map, a gym that was never reset, a member of a group   (shared with mv_env_store.hip)
+int fork_check(mv_gym *g, const void *map, const char *who, const char *what)
 {
     if (check(g)) return -1;
     if (!map) return fail(std::string(who) + ": null map");
     if (!g->wasReset) return fail(std::string(who) + ": call mv_reset first (there is no episode to continue)");
-    if (g->inGroup) return fail(std::string(who) + ": the gym belongs to an mv_group (its streams are the group's): forks inside groups are not supported");
+    if (g->inGroup) return fail(std::string(who) + ": the gym belongs to an mv_group (its streams are the group's): " + what + " inside groups are not supported");
     return 0;
 }
+
+// a host map's way to the device: through the map's device copy and its pinned staging, double buffered (allocated at the first use), on stream s.  The
+// caller records forkMapCopied[(forkMapUses - 1) & 1] behind the launch that reads *device_map.   (shared with mv_env_store.hip)
+int stage_fork_map(mv_gym *g, const int32_t *host_map, hipStream_t s, const int32_t **device_map)
+{
+    const size_t bytes = (size_t)g->N * sizeof(int32_t);
+    if (!g->dForkMap) {
+        HIP_TRY(hipMalloc((void **)&g->dForkMap, 2 * bytes));
+        HIP_TRY(hipHostMalloc((void **)&g->hForkMap, 2 * bytes, hipHostMallocDefault));
+        for (hipEvent_t &e : g->forkMapCopied) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        g->forkMapUses = 0;
+    }
+    const int b = (int)(g->forkMapUses & 1ull);
+    // (the copy and the launch that used this half two calls ago: long done -- the staging is the host's to write again, the device half the stream's)
+    if (g->forkMapUses >= 2) HIP_TRY(hipEventSynchronize(g->forkMapCopied[b]));
+    int32_t *h = g->hForkMap + (size_t)b * g->N, *d = g->dForkMap + (size_t)b * g->N;
+    std::memcpy(h, host_map, bytes);
+    HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+    *device_map = d;
+    ++g->forkMapUses;
+    return 0;
+}
+
+}  // namespace mvapi
+
+namespace {
 
 // The launch.
 // A DEVICE map was written by something on the caller's stream, so the copy runs there: behind everything the caller enqueued (the kernel that wrote the
@@ -133,23 +159,7 @@ int fork_launch(mv_gym *g, const int32_t *device_map, const int32_t *host_map, L
     const bool onSim = host_map && g->pipelined && g->simOnOwnStream && g->simDoneValid && !g->simMustWaitUser && g->logCapacity == 0;
     hipStream_t s = onSim ? g->simStream : g->stream;
     if (!onSim && sim_join(g)) return -1;
-    if (host_map) {
-        const size_t bytes = (size_t)g->N * sizeof(int32_t);
-        if (!g->dForkMap) {   // first use: the map's device copy and its pinned staging, double buffered
-            HIP_TRY(hipMalloc((void **)&g->dForkMap, 2 * bytes));
-            HIP_TRY(hipHostMalloc((void **)&g->hForkMap, 2 * bytes, hipHostMallocDefault));
-            for (hipEvent_t &e : g->forkMapCopied) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            g->forkMapUses = 0;
-        }
-        const int b = (int)(g->forkMapUses & 1ull);
-        // (the copy and the launch that used this half two calls ago: long done -- the staging is the host's to write again, the device half the stream's)
-        if (g->forkMapUses >= 2) HIP_TRY(hipEventSynchronize(g->forkMapCopied[b]));
-        int32_t *h = g->hForkMap + (size_t)b * g->N, *d = g->dForkMap + (size_t)b * g->N;
-        std::memcpy(h, host_map, bytes);
-        HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-        device_map = d;
-        ++g->forkMapUses;
-    }
+    if (host_map && stage_fork_map(g, host_map, s, &device_map)) return -1;
     fork::Table t = g->forkTable;
     if (g->logCapacity > 0) {   // the running returns and lengths: a fork's record covers the episode from its source's start (mv_episode_log.h)
         fork::table_add(t, g->logRet, (size_t)g->A * sizeof(double));

@@ -38,8 +38,8 @@ __host__ __device__ inline uint32_t action_ring_entry(uint32_t first, int j, uin
 
 // error flags a kernel raises in episode_status[N + 1]; mv_step reports them (mv_api.hip: check_status_flags)
 // (16 is the episode log's, mv_episode_log.h: ST_EPISODE_LOG); ST_FORK: mv_fork_envs skipped an invalid entry of a device map (mv_fork.h);
-// ST_RESAMPLE: mv_resample_envs skipped an entry out of range
-enum : int { ST_STARVED = 1, ST_CANDIDATES = 2, ST_VISIBLE = 4, ST_CHUNK = 8, ST_FORK = 32, ST_RESAMPLE = 64 };
+// ST_RESAMPLE: mv_resample_envs skipped an entry out of range; ST_ENV_STORE: mv_save_envs / mv_load_envs skipped an entry (mv_env_store.h)
+enum : int { ST_STARVED = 1, ST_CANDIDATES = 2, ST_VISIBLE = 4, ST_CHUNK = 8, ST_FORK = 32, ST_RESAMPLE = 64, ST_ENV_STORE = 128 };
 
 enum : int { SCN_TOWER = 0, SCN_OBSTACLES = 1, SCN_COLLECT = 2, SCN_REARRANGE = 3, SCN_SOKOBAN = 4,
              SCN_EMPTY = 5,     // Empty runs on the Obstacles kernels (one slab, no terrain) with fall detection off

@@ -45,6 +45,12 @@ SYMBOLS = [
     ("mv_debug_episodes_consumed", C.c_int, [_P, _P]), ("mv_fork_bytes_per_env", C.c_int64, [_P]),
     ("mv_resample_envs", C.c_int, [_P, _P]), ("mv_resample_envs_host", C.c_int, [_P, _P]), ("mv_resample_staging_bytes", C.c_int64, [_P]),
     ("mv_debug_resample_plan_host", C.c_int, [_P, _I, _P, _P, _P]), ("mv_debug_resample_apply_host", C.c_int, [_P, _I, _I, _P, _I]),
+    ("mv_env_record_bytes", C.c_int64, [_P]), ("mv_env_record_layout", C.c_uint64, [_P]),
+    ("mv_save_envs", C.c_int, [_P, _P, _P, _I]), ("mv_save_envs_host", C.c_int, [_P, _P, _P, _I]),
+    ("mv_load_envs", C.c_int, [_P, _P, _P, _I]), ("mv_load_envs_host", C.c_int, [_P, _P, _P, _I]),
+    ("mv_debug_env_store_plan_host", C.c_int, [_P, _I, _I, _I, _P, _P]), ("mv_debug_env_record_layout_host", C.c_int64, [_P, _I, _I, _P]),
+    ("mv_debug_env_record_pack_host", C.c_int, [_P, _I, _I, C.c_uint64, _I, _P, _P]),
+    ("mv_debug_env_record_unpack_host", C.c_int, [_P, _I, _I, C.c_uint64, _I, _P, _P]),
     ("mv_reset_envs", C.c_int, [_P, _P, _I]), ("mv_reset_envs_host", C.c_int, [_P, _P, _I]), ("mv_debug_episode_log_cut_host", C.c_int, [_P, _I, _I, _P, _P]),
     ("mv_set_output_ring", C.c_int, [_P, _I, _P, _P, _P]),
     ("mv_set_pass_overlap", C.c_int, [_P, _I]),
@@ -177,18 +183,82 @@ def debug_resample_apply_host(src_of, state, order=0):
     return out
 
 
-def check_fork_map(src_of, num_envs):
-    """the argument check of MegaverseGym.fork_envs: a CUDA int32 tensor of shape (num_envs,) -> 'device'; anything else -> a contiguous int32 numpy array"""
+def check_fork_map(src_of, num_envs, who='fork_envs', meaning='src_of[d] = the env that env d continues from, -1 or d: left alone'):
+    """the argument check of MegaverseGym.fork_envs (and, with their own who / meaning, of save_envs / load_envs): a CUDA int32 tensor of shape (num_envs,)
+    -> 'device'; anything else -> a contiguous int32 numpy array"""
     if hasattr(src_of, 'data_ptr'):
         if tuple(src_of.shape) != (int(num_envs),) or str(src_of.dtype) != 'torch.int32' or not src_of.is_cuda or not src_of.is_contiguous():
-            raise ValueError(f'fork_envs: a tensor map must be a contiguous int32 CUDA tensor of shape ({int(num_envs)},), '
+            raise ValueError(f'{who}: a tensor map must be a contiguous int32 CUDA tensor of shape ({int(num_envs)},), '
                              f'got {src_of.dtype} {tuple(src_of.shape)} on {src_of.device}')
         return 'device'
     m = np.asarray(src_of)
     if m.shape != (int(num_envs),) or m.dtype.kind not in 'iu':
-        raise ValueError(f'fork_envs: the map must be {int(num_envs)} integers (src_of[d] = the env that env d continues from, -1 or d: left alone), '
+        raise ValueError(f'{who}: the map must be {int(num_envs)} integers ({meaning}), '
                          f'got {m.dtype} {m.shape}')
     return np.ascontiguousarray(m, dtype=np.int32)
+
+
+def check_env_store(store, record_bytes, who='save_envs'):
+    """the argument check of MegaverseGym.save_envs / load_envs for the store: a contiguous CUDA uint8 tensor [slots, record_bytes] -> slots"""
+    if not hasattr(store, 'data_ptr') or str(store.dtype) != 'torch.uint8' or not store.is_cuda:
+        raise ValueError(f'{who}: the store must be a torch.uint8 CUDA tensor of shape (slots, {int(record_bytes)}) (new_env_store makes one)')
+    if store.dim() != 2 or int(store.shape[1]) != int(record_bytes) or int(store.shape[0]) < 1:
+        raise ValueError(f'{who}: the store must have shape (slots, {int(record_bytes)}) -- one record of env_record_bytes() bytes per slot -- '
+                         f'got {tuple(store.shape)}')
+    if not store.is_contiguous():
+        raise ValueError(f'{who}: the store must be contiguous (its records are read and written in place)')
+    return int(store.shape[0])
+
+
+def debug_env_store_plan_host(slot_of, slots, is_save):
+    """mv_debug_env_store_plan_host: the rule of a save_envs / load_envs map on the CPU (no device) -> (resolved int32 [N]: the slot of entry e, or -1;
+    invalid [N])"""
+    lib = load_library()
+    m = np.ascontiguousarray(slot_of, np.int32).reshape(-1)
+    resolved, invalid = np.full(m.size, -9, np.int32), np.full(m.size, -9, np.int32)
+    if m.size and lib.mv_debug_env_store_plan_host(m.ctypes.data, m.size, int(slots), int(bool(is_save)), resolved.ctypes.data, invalid.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return resolved, invalid
+
+
+def debug_env_record_layout_host(array_bytes, agents_per_env):
+    """mv_debug_env_record_layout_host -> (record bytes, offsets uint32 [count + 3]: the EnvHeader, each array, ret, len)"""
+    lib = load_library()
+    b = np.ascontiguousarray(array_bytes, np.uint32).reshape(-1)
+    off = np.zeros(b.size + 3, np.uint32)
+    n = lib.mv_debug_env_record_layout_host(b.ctypes.data if b.size else off.ctypes.data, b.size, int(agents_per_env), off.ctypes.data)
+    if n < 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return int(n), off
+
+
+def debug_env_record_pack_host(array_bytes, agents_per_env, layout_word, log_on, env_state):
+    """mv_debug_env_record_pack_host: env_state (uint8: the 128-byte EnvHeader, the arrays, double ret[A], int32 len, without gaps) -> the record (uint8)"""
+    lib = load_library()
+    b = np.ascontiguousarray(array_bytes, np.uint32).reshape(-1)
+    env = np.ascontiguousarray(env_state, np.uint8).reshape(-1)
+    if env.size != 128 + int(b.sum()) + 8 * int(agents_per_env) + 4:
+        raise ValueError("debug_env_record_pack_host: env_state is the EnvHeader, the arrays, ret[A] and len, one behind the other")
+    record = np.full(debug_env_record_layout_host(b, agents_per_env)[0], 0xEE, np.uint8)
+    if lib.mv_debug_env_record_pack_host(b.ctypes.data if b.size else record.ctypes.data, b.size, int(agents_per_env), int(layout_word), int(bool(log_on)),
+                                         env.ctypes.data, record.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return record
+
+
+def debug_env_record_unpack_host(array_bytes, agents_per_env, layout_word, log_on, record, env_state):
+    """mv_debug_env_record_unpack_host: the record into a copy of env_state -> (refused: bool, the env afterwards)"""
+    lib = load_library()
+    b = np.ascontiguousarray(array_bytes, np.uint32).reshape(-1)
+    env = np.array(env_state, dtype=np.uint8, order="C", copy=True).reshape(-1)
+    rec = np.ascontiguousarray(record, np.uint8).reshape(-1)
+    if env.size != 128 + int(b.sum()) + 8 * int(agents_per_env) + 4 or rec.size != debug_env_record_layout_host(b, agents_per_env)[0]:
+        raise ValueError("debug_env_record_unpack_host: wrong size of env_state or record")
+    rc = lib.mv_debug_env_record_unpack_host(b.ctypes.data if b.size else rec.ctypes.data, b.size, int(agents_per_env), int(layout_word), int(bool(log_on)),
+                                             rec.ctypes.data, env.ctypes.data)
+    if rc < 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return rc == 1, env
 
 
 def debug_episode_log_cut_host(mask, agents_per_env, ret, length):
@@ -338,6 +408,7 @@ class MegaverseGym:
         self._fork_held = None   # fork_envs: the caller's device map, kept until the next step has been enqueued
         self._reset_held = None  # reset_envs: the caller's device mask, likewise
         self._step_mask_held = None  # set_step_mask: the caller's device mask, kept until it is replaced or detached
+        self._store_held = []    # save_envs / load_envs: the caller's stores and device maps, kept until the next step has been enqueued
 
     def _ck(self, rc):
         if rc < 0:
@@ -374,6 +445,7 @@ class MegaverseGym:
     def step(self):
         self._ckw(self._lib.mv_step(self._g))
         self._fork_held = self._reset_held = None
+        self._store_held = []
 
     def is_done(self, env_idx):
         return bool(self._ck(self._lib.mv_is_done(self._g, int(env_idx))))
@@ -451,6 +523,7 @@ class MegaverseGym:
     def step_no_render(self):
         self._ckw(self._lib.mv_step_no_render(self._g))
         self._fork_held = self._reset_held = None
+        self._store_held = []
 
     POLICIES = {"none": 0, "multidiscrete": 1, "single-bit": 2, "sequence": 3}
 
@@ -464,6 +537,7 @@ class MegaverseGym:
         args = (self._g, int(k), int(self.POLICIES.get(policy, policy)), int(seed) & 0xFFFFFFFF, int(first_step_index) & 0xFFFFFFFF)
         self._ckw(self._lib.mv_step_n(*args) if mode == 0 else self._lib.mv_step_n_render(*args, mode))
         self._fork_held = self._reset_held = None
+        self._store_held = []
 
     def fork_envs(self, src_of):
         """Env forks (include/megaverse_hip.h: mv_fork_envs): src_of[d] = s makes env d leave its running episode and continue env s's from s's current
@@ -492,6 +566,49 @@ class MegaverseGym:
             self._fork_held = held
         else:
             self._ck(self._lib.mv_resample_envs_host(self._g, m.ctypes.data))
+
+    # ---- env stores (include/megaverse_hip.h: mv_save_envs / mv_load_envs) ----
+    def env_record_bytes(self):
+        """bytes of one record of an env store: a multiple of 16"""
+        return int(self._ck(self._lib.mv_env_record_bytes(self._g)))
+
+    def env_record_layout(self):
+        """the layout word of this gym's records: two gyms with the same word can exchange records"""
+        return int(self._lib.mv_env_record_layout(self._g))
+
+    def new_env_store(self, slots):
+        """a zeroed store of `slots` records on the gym's device: a torch.uint8 tensor [slots, env_record_bytes()].  The caller owns it."""
+        import torch
+        if int(slots) < 1:
+            raise ValueError(f'new_env_store: slots must be positive, got {slots}')
+        return torch.zeros((int(slots), self.env_record_bytes()), dtype=torch.uint8, device=f'cuda:{self.device}')
+
+    def _env_store_call(self, who, meaning, device_form, host_form, slot_of, store):
+        slots = check_env_store(store, self.env_record_bytes(), who)
+        m = check_fork_map(slot_of, self.num_envs, who, meaning)
+        if isinstance(m, str):
+            self._ck(device_form(self._g, _P(int(slot_of.data_ptr())), _P(int(store.data_ptr())), slots))
+            self._store_held.append(slot_of)
+        else:
+            self._ck(host_form(self._g, m.ctypes.data, _P(int(store.data_ptr())), slots))
+        self._store_held.append(store)
+
+    def save_envs(self, slot_of, store):
+        """Env stores (include/megaverse_hip.h: mv_save_envs): slot_of[e] = m writes env e's current episode state into record m of store, a contiguous
+        torch.uint8 CUDA tensor [slots, env_record_bytes()] (new_env_store); -1: env e is not saved.  Nothing in the gym changes.  The map takes
+        fork_envs' rule: a contiguous int32 CUDA tensor of shape (num_envs,) is read in place, in the order of the gym's stream, without a host
+        synchronisation (an invalid entry -- out of range, or a slot that two envs name -- is skipped and reported by the next stepping call as a warning);
+        a numpy array or a sequence is validated on the host first (RuntimeError, nothing copied).  Map and store are held until the next step."""
+        self._env_store_call('save_envs', 'slot_of[e] = the record env e is saved into, -1: not saved', self._lib.mv_save_envs, self._lib.mv_save_envs_host,
+                             slot_of, store)
+
+    def load_envs(self, slot_of, store):
+        """Env stores (include/megaverse_hip.h: mv_load_envs): slot_of[d] = m makes env d leave its running episode and continue record m's; -1 leaves env d
+        alone; many envs may load one record.  Env d keeps its own seed chain and resident next episodes, as a fork destination does.  A record that this
+        gym's configuration did not write -- a zeroed slot, another scenario or parameter set -- is skipped, the env stays as it was, and the next stepping
+        call reports it as a warning (in both forms: record headers are visible on the device only).  The arguments are save_envs'."""
+        self._env_store_call('load_envs', 'slot_of[d] = the record env d continues from, -1: left alone', self._lib.mv_load_envs, self._lib.mv_load_envs_host,
+                             slot_of, store)
 
     def resample_staging_bytes(self):
         """bytes of resample_envs' staging arena: 0 before the first call"""

@@ -267,6 +267,31 @@ class MegaverseEnv:
         m[a], m[b] = b, a
         self.env.resample_envs(m)
 
+    def _store_map(self, who, env_ids, slots):
+        ids = self._env_ids(env_ids, who)
+        if len(set(ids.tolist())) != ids.size:
+            raise ValueError(f'{who}: env_ids names an env twice')
+        sl = ids if slots is None else np.asarray(list(slots), dtype=np.int64).reshape(-1)
+        if sl.shape != ids.shape:
+            raise ValueError(f'{who}: slots must name one record per env of env_ids')
+        m = np.full(self.num_envs, -1, np.int32)
+        m[ids] = sl
+        return m
+
+    def new_store(self, slots):
+        """a zeroed env store of `slots` records (MegaverseGym.new_env_store): a torch.uint8 CUDA tensor the caller owns"""
+        return self.env.new_env_store(slots)
+
+    def save(self, env_ids, store, slots=None):
+        """the running episodes of the envs of env_ids are saved into the records `slots` of store (default: record e for env e) -- MegaverseGym.save_envs
+        with the map built here.  A savepoint that costs no live env: a search keeps as many states as the store has records.  The gym is unchanged."""
+        self.env.save_envs(self._store_map('save', env_ids, slots), store)
+
+    def load(self, env_ids, store, slots=None):
+        """the envs of env_ids leave their running episodes and continue the records `slots` of store (default: record e for env e) -- MegaverseGym.load_envs
+        with the map built here.  The envs keep their own next episodes; outputs are untouched: they still describe the last stepped tick."""
+        self.env.load_envs(self._store_map('load', env_ids, slots), store)
+
     def reset_envs(self, env_ids, render=True):
         """the envs of env_ids abandon their running episode and start the next one of their own sequence (MegaverseGym.reset_envs with the mask built
         here); the others are untouched.  What a learner's own time limit, a curriculum, or a planner handing its fork destinations back needs.  With render
