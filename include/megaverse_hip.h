@@ -208,6 +208,38 @@ int mv_reset_envs_host(mv_gym *g, const uint8_t *mask, int32_t render);     /* m
 int mv_set_step_mask(mv_gym *g, const uint8_t *device_mask);   /* [N] in device memory; NULL detaches */
 int mv_set_step_mask_host(mv_gym *g, const uint8_t *mask);     /* [N] in host memory; NULL detaches */
 int mv_get_step_mask(const mv_gym *g);                         /* 0: none, 1: device form, 2: host form; -1: no gym */
+/* Episode budgets (no reference counterpart: VectorEnv::step resets a finished env on the spot and steps on, vector_env.cpp:89-108).  Per env e the gym owns an
+ * int32 left[e]:  < 0: unlimited -- what every env is without these calls;  > 0: the env may still finish that many episodes;  0: the env is HALTED.
+ * Tick t, env e, left[e] as it stands before the tick (megaverse_amd/csrc/mv_episode_budget.h states the rule for kernels and host alike):
+ *   the env steps  <=>  (no step mask attached or mask[e] != 0) and left[e] != 0.
+ *   An env that steps runs today's tick, byte for byte: rewards, done = 1, the true objective, the auto-reset swap-in, episodes_consumed; the observation is
+ *   the first frame of the next episode, as always.  If that tick staged done and left[e] > 0, left[e] goes down by one.
+ *   An env that does not step runs the frozen tick of the step masks, word for word (above): rewards +0.0f, done 0, its action entries cleared, no other byte
+ *   of the env, its status word, its resident episodes or TowerBuilding's generator read or written; frames, where the mode draws, from the unchanged state.
+ * So an env with budget b finishes exactly b episodes and then waits, frozen, on the first frame of its next episode -- also in the middle of a resident
+ * multi-tick launch: a mask changes at an ordering point, a budget inside the kernel.  A halted env takes nothing from the refill protocol and cannot starve.
+ * Every stepping entry and policy honours it: mv_step, mv_step_no_render, mv_step_n, mv_step_n_render in all three render modes.
+ * The values are COPIED into a gym-owned device array (allocated at first use with the halted count and the episode log's mirror, counted in mv_arena_bytes,
+ * freed by mv_close): the kernels write that array, the caller's buffer is read once, in the order of the gym's stream.  NULL detaches: every env is
+ * unlimited again and the gym launches what it launched before.  Attaching again replaces every value (the "resume" operation).  A value of 0 halts the env
+ * from the next tick.
+ * Episode log (when on): a halted tick adds nothing to returns or length and writes no record; the finishing tick's record is written as always; after a
+ * re-attach the next episode's length counts from its own first stepped tick.  Switching the log on with a budget attached is fine.
+ * Nothing else touches a budget: mv_reset resets every env and leaves budgets attached and unchanged; mv_reset_envs, mv_fork_envs*, mv_resample_envs* and
+ * mv_load_envs* treat halted envs like any other and do not change left -- an episode cut by a reset or overwritten by a fork or load reported no done and is
+ * not counted; a halted fork destination stays frozen on its new state.
+ * Ordering: mv_set_step_mask's.  The call is an ordering point behind every step launch enqueued so far and behind the episode log's last update, and in
+ * front of the next step launch; neither form waits on the host; the host form goes through pinned staging buffers of the gym's.
+ * Valid before the first mv_reset.  Refused (-1 with text): no gym, a closed gym, a gym in an mv_group; mv_group_create and mv_step_many refuse a gym with a
+ * budget attached (the union launches read none). */
+int mv_set_episode_budget(mv_gym *g, const int32_t *device_budget);   /* [N] int32 in device memory; NULL detaches */
+int mv_set_episode_budget_host(mv_gym *g, const int32_t *budget);     /* [N] int32 in host memory; NULL detaches */
+int mv_get_episode_budget(const mv_gym *g);                           /* 0: none, 1: attached; -1: no gym */
+/* the gym-owned int32 [N] of remaining budgets, valid on the gym's stream after any stepping call; NULL when no budget is attached */
+void *mv_episode_budget_device_ptr(mv_gym *g);
+/* a uint32: the number of envs with left == 0 -- set by the attach, kept by the step kernels: one 4-byte read decides "everybody is done"; NULL likewise */
+void *mv_halted_count_device_ptr(mv_gym *g);
+int mv_halted_count(mv_gym *g, int32_t *out);                         /* the same value on the host; waits for the gym's stream, like mv_episode_log_count */
 /* Env stores (no reference counterpart): an env's episode state saved into a RECORD of a caller-owned store, and a record loaded back into any env -- of
  * this gym, or of another gym of the same configuration.  A savepoint no longer costs a live env: a search keeps as many states as the store has slots, and
  * a state can leave its gym -- to another gym, another GPU's shard, host memory or a file (the store is plain memory: copy it).
@@ -485,6 +517,15 @@ int mv_debug_episode_log_host(const float *rewards, const uint8_t *dones, const 
 int mv_debug_episode_log_masked_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A,
                                      int32_t capacity, uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped,
                                      const uint8_t *step_mask /* [N] or NULL */);
+/* ... and an episode budget (mv_set_episode_budget): left [N] or NULL, in and out -- the log's mirror of the budgets, advanced by the rule tick by tick; the
+ * ticks of a halted env are skipped like a frozen env's.  left = NULL: mv_debug_episode_log_masked_host, byte for byte. */
+int mv_debug_episode_log_budget_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A,
+                                     int32_t capacity, uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped,
+                                     const uint8_t *step_mask /* [N] or NULL */, int32_t *left /* [N] or NULL */);
+/* Host-only (no device): the rule of episode budgets (megaverse_amd/csrc/mv_episode_budget.h) over k ticks of N envs.  dones [k][N]: what tick t stages for
+ * env e if it steps; mask [N] or NULL; left_in [N].  steps_out [k][N]: 1 where the env steps in the tick; left_out [N]: the budgets behind the last tick. */
+int mv_debug_episode_budget_host(const uint8_t *dones, const uint8_t *mask, const int32_t *left_in, int32_t k, int32_t N, uint8_t *steps_out,
+                                 int32_t *left_out);
 /* Host-only (no device): the episode log's masked clear (megaverse_amd/csrc/mv_episode_log.h: episode_log_cut, the source mv_reset_envs' kernel runs) over N
  * envs x A agents: where mask[e] != 0, ret[e * A .. e * A + A - 1] and len[e] go to zero; everything else stays. */
 int mv_debug_episode_log_cut_host(const uint8_t *mask, int32_t N, int32_t A, double *ret, int32_t *len);

@@ -757,6 +757,7 @@ int mv_close(mv_gym *g)
     for (hipEvent_t &e : g->resetMaskCopied) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     g->dResetMask = g->hResetMask = nullptr;
     step_mask_free(g);
+    episode_budget_free(g);
     if (g->arena) (void)hipFree(g->arena);
     if (g->hiresObs) (void)hipFree(g->hiresObs);
     if (g->hBlobs) (void)(g->blobsOnDevice ? hipFree(g->hBlobs) : hipHostFree(g->hBlobs));

@@ -7,6 +7,7 @@
 //   mv_reset_envs.hip masked env resets: the host protocol around the reset_masked kernels (mv_step_kernels.h)
 //   mv_env_store.hip  env stores: the save / load kernels, their entry points and host-only hooks
 //   mv_step_mask.hip  step masks: attaching and detaching the bytes that freeze envs (mv_step_kernels.h: frozen_tick)
+//   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 // The C ABI itself is include/megaverse_hip.h; nothing here is exported under a C name.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +34,7 @@
 #include "mv_types.h"
 #include "mv_union.h"
 #include "mv_episode_log.h"
+#include "mv_episode_budget.h"
 #include "mv_fork.h"
 
 namespace mv {
@@ -242,6 +244,16 @@ struct mv_gym {
     size_t stepMaskBytes = 0;
     struct MaskStaging { uint8_t *host; hipEvent_t copied; };
     std::vector<MaskStaging> stepMaskStaging;
+    // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
+    // budgetLeft [N], what the step kernels read and write (GymView::budget, through the stepping calls' views, while budgetOn); budgetHalted, the count of
+    // zeros in it; budgetMirror [N], the episode log's own copy, advanced by the log's update tick by tick.  The host form's values travel through pinned
+    // staging buffers like the step mask's.
+    int32_t *budgetLeft = nullptr, *budgetMirror = nullptr;
+    uint32_t *budgetHalted = nullptr;
+    bool budgetOn = false;
+    size_t budgetBytes = 0;
+    struct BudgetStaging { int32_t *host; hipEvent_t copied; };
+    std::vector<BudgetStaging> budgetStaging;
     // in-stream profiling
     std::vector<hipEvent_t> profEvents;          // 5 per profiled tick: [0] [1] around the step kernel (its stream), [2] [3] [4] before the
                                                  // observation pass, between frame sort and raster, after the raster (the caller's stream)
@@ -279,6 +291,8 @@ int episode_log_update(mv_gym *g, const GymView *views, int stride, int k);
 int episode_log_reset(mv_gym *g);   // mv_reset: accumulators to zero, the records stay
 void episode_log_free(mv_gym *g);   // mv_close
 void step_mask_free(mv_gym *g);     // mv_close (mv_step_mask.hip)
+void episode_budget_free(mv_gym *g);   // mv_close (mv_episode_budget.hip)
+int episode_budget_seed_mirror(mv_gym *g);   // mv_set_episode_log: the log's mirror from the live array (mv_episode_budget.hip)
 // mv_fork.hip, shared with mv_env_store.hip: what every fork / resample / env-store form refuses (what: "forks", "env stores": for the text about groups), and
 // a host map's way to the device through the pinned double buffer
 int fork_check(mv_gym *g, const void *map, const char *who, const char *what = "forks");

@@ -56,6 +56,8 @@ MV_ELOG_HD bool episode_log_tick(double &ret, int32_t &len, float reward, uint8_
 // mv_set_step_mask: whether env e steps in the ticks of this launch.  A frozen env's tick adds nothing to the running returns of its agents or to its running
 // length, and writes no record (its staged rewards are +0.0f and its staged done 0, mv_step_kernels.h: frozen_tick -- the length is what would move): the
 // kernel and the host twin skip episode_log_tick, and the kernel's length pass, where this says no.  One mask per launch: it does not change within a call.
+// (An episode budget, mv_set_episode_budget, halts an env in the middle of a call: the log walks a mirror of the budgets through the call's staged dones by
+// the rule of mv_episode_budget.h and skips the halted ticks in the same way -- Args::budget, mv_episode_log.hip: load_done.)
 MV_ELOG_HD bool episode_log_steps(const uint8_t *step_mask, int32_t e) { return !step_mask || step_mask[e] != 0; }
 
 // mv_reset_envs, one agent i of a gym with A agents per env: where the mask flags the agent's env -- and, applied given, the env did take its next episode
@@ -102,6 +104,7 @@ struct Args {
     Record *records;   // [capacity]
     int *status;       // the gym's status word (ST_EPISODE_LOG), or null
     const uint8_t *step_mask;   // [N] the call's step mask (episode_log_steps), or null
+    int32_t *budget;            // [N] the log's mirror of the episode budgets (mv_set_episode_budget), advanced by the launch tick by tick, or null
 };
 
 // ticks one launch may cover for N*A agents (the LDS cells of MAX_GROUPS)

@@ -15,6 +15,7 @@
 // At 1024 agents x 16 ticks that is 16 x (4 + 1 + 4) KiB read, four barriers and 256 cells: a launch's latency.
 #include "mv_api_internal.h"
 #include "mv_episode_log.h"
+#include "mv_episode_budget.h"
 
 namespace mv {
 namespace elog {
@@ -29,33 +30,54 @@ __device__ __forceinline__ uint32_t lanes_below(unsigned long long ballot)
 template <int KT>
 struct AgentTicks {
     uint32_t done;              // bit t: the agent's env finished in tick t
+    uint32_t steps;             // bit t: the agent's env stepped in tick t (mv_set_episode_budget; without a budget: every bit)
     float reward[KT], objective[KT];
     double ret;
     int32_t len;
 };
 
-template <int KT>
+// The done bits of env e over the launch's ticks and, BUDGET (mv_set_episode_budget): the ticks the env stepped in -- the rule of mv_episode_budget.h walked
+// over the staged dones from the log's mirror of the env's budget; left: the mirror behind the launch's last tick.  A tick the env did not step in staged
+// done 0 (mv_step_kernels.h: frozen_tick); its bit is cleared all the same.
+template <int KT, bool BUDGET>
+__device__ __forceinline__ void load_done(const Args &a, int e, bool in, uint32_t &done, uint32_t &steps, int32_t &left)
+{
+    uint8_t d[KT];
+#pragma unroll
+    for (int t = 0; t < KT; ++t) d[t] = a.done[t < a.k ? t : a.k - 1][e];
+    done = 0; steps = ~0u; left = -1;
+    if constexpr (BUDGET) { left = a.budget[e]; steps = 0; }
+#pragma unroll
+    for (int t = 0; t < KT; ++t) {
+        if constexpr (BUDGET) {
+            if (t < a.k && budget::episode_budget_steps(1, left)) {
+                steps |= 1u << t;
+                (void)budget::episode_budget_spend(left, d[t]);
+            }
+        }
+        if (in && t < a.k && d[t] && ((steps >> t) & 1u)) done |= 1u << t;
+    }
+}
+
+template <int KT, bool BUDGET>
 __device__ __forceinline__ void load_agent(const Args &a, int i, int e, bool in, AgentTicks<KT> &v)
 {
     const int ii = in ? i : 0;
-    uint8_t d[KT];
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
         const int tt = t < a.k ? t : a.k - 1;
-        d[t] = a.done[tt][e];
         v.reward[t] = a.rewards[tt][ii];
         v.objective[t] = a.true_objective[tt][ii];
     }
     v.ret = a.ret[ii];
     v.len = a.len[e];
-    v.done = 0;
-#pragma unroll
-    for (int t = 0; t < KT; ++t)
-        if (in && t < a.k && d[t]) v.done |= 1u << t;
+    int32_t left;
+    load_done<KT, BUDGET>(a, e, in, v.done, v.steps, left);
 }
 
 // KT: the ticks the launch is compiled for (k <= KT; 1: a single-tick call, 16: a batched call's worth)
-template <int KT>
+// BUDGET: the gym has an episode budget attached (a.budget: the log's mirror); the instantiations without contain no line of it
+template <int KT, bool BUDGET>
 __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
 {
     __shared__ uint32_t cell[MAX_GROUPS];   // [tick][chunk][wave]: finished agents, then (after the scan) records in the cells before
@@ -67,7 +89,7 @@ __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
     // (mv_set_step_mask) `in` below: the agent exists AND its env steps in this launch (episode_log_steps) -- the agents of a frozen env are passed over like
     // the threads beyond the last agent: no done bit, no tick, and their running return is not written
     AgentTicks<KT> first_chunk;
-    load_agent(a, tid, tid < NA ? tid / a.A : 0, tid < NA && episode_log_steps(a.step_mask, tid / a.A), first_chunk);
+    load_agent<KT, BUDGET>(a, tid, tid < NA ? tid / a.A : 0, tid < NA && episode_log_steps(a.step_mask, tid / a.A), first_chunk);
 
     // ---- 1. finished agents per (tick, chunk, wave)
     for (int c = 0; c < chunks; ++c) {
@@ -76,12 +98,9 @@ __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
         const int e = in ? i / a.A : 0;
         uint32_t done = first_chunk.done;
         if (c > 0) {
-            done = 0;
-#pragma unroll
-            for (int t = 0; t < KT; ++t) {
-                const int tt = t < a.k ? t : a.k - 1;
-                if (a.done[tt][e] != 0 && in && t < a.k) done |= 1u << t;
-            }
+            uint32_t steps;
+            int32_t left;
+            load_done<KT, BUDGET>(a, e, in, done, steps, left);
         }
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
@@ -124,13 +143,13 @@ __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
         const bool in = i < NA && episode_log_steps(a.step_mask, i / a.A);
         const int e = in ? i / a.A : 0;
         AgentTicks<KT> v = first_chunk;
-        if (c > 0) load_agent(a, i, e, in, v);
+        if (c > 0) load_agent<KT, BUDGET>(a, i, e, in, v);
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
             const bool d = ((v.done >> t) & 1u) != 0;
             const unsigned long long b = __ballot(d);
             Record rec;
-            if (in && t < a.k && episode_log_tick(v.ret, v.len, v.reward[t], d ? 1 : 0, i, a.first_tick + (uint32_t)t, v.objective[t], rec))
+            if (in && t < a.k && ((v.steps >> t) & 1u) && episode_log_tick(v.ret, v.len, v.reward[t], d ? 1 : 0, i, a.first_tick + (uint32_t)t, v.objective[t], rec))
                 episode_log_store(a.records, a.capacity, (uint64_t)base + cell[(t * chunks + c) * WAVES + wave] + lanes_below(b), rec);
         }
         if (in) a.ret[i] = v.ret;
@@ -140,14 +159,15 @@ __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
     __syncthreads();
     for (int e = tid; e < a.N; e += THREADS) {
         if (!episode_log_steps(a.step_mask, e)) continue;   // (a frozen env's length stays)
-        uint8_t d[KT];
-#pragma unroll
-        for (int t = 0; t < KT; ++t) d[t] = a.done[t < a.k ? t : a.k - 1][e];
+        uint32_t done, steps;
+        int32_t left;
+        load_done<KT, BUDGET>(a, e, true, done, steps, left);
         int32_t len = a.len[e];
 #pragma unroll
         for (int t = 0; t < KT; ++t)
-            if (t < a.k) len = d[t] ? 0 : len + 1;
+            if (t < a.k && ((steps >> t) & 1u)) len = ((done >> t) & 1u) ? 0 : len + 1;
         a.len[e] = len;
+        if constexpr (BUDGET) a.budget[e] = left;   // (the mirror: what the step kernels' array held behind the launch's last tick)
     }
     if (tid == 0) {
         Header h = *a.hdr;
@@ -159,9 +179,16 @@ __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
 void launch_episode_log(const Args &a, hipStream_t stream)
 {
     if (a.k < 1 || a.k > MAX_TICKS) return;   // (load_agent reads tick k - 1 for the ticks beyond k)
-    if (a.k == 1) hipLaunchKernelGGL(episode_log_kernel<1>, dim3(1), dim3(THREADS), 0, stream, a);
-    else if (a.k <= 4) hipLaunchKernelGGL(episode_log_kernel<4>, dim3(1), dim3(THREADS), 0, stream, a);
-    else hipLaunchKernelGGL(episode_log_kernel<MAX_TICKS>, dim3(1), dim3(THREADS), 0, stream, a);
+    const dim3 grid(1), block(THREADS);
+    if (a.budget) {
+        if (a.k == 1) hipLaunchKernelGGL((episode_log_kernel<1, true>), grid, block, 0, stream, a);
+        else if (a.k <= 4) hipLaunchKernelGGL((episode_log_kernel<4, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((episode_log_kernel<MAX_TICKS, true>), grid, block, 0, stream, a);
+    } else {
+        if (a.k == 1) hipLaunchKernelGGL((episode_log_kernel<1, false>), grid, block, 0, stream, a);
+        else if (a.k <= 4) hipLaunchKernelGGL((episode_log_kernel<4, false>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((episode_log_kernel<MAX_TICKS, false>), grid, block, 0, stream, a);
+    }
 }
 
 // mv_reset_envs with the log on: one thread per agent clears what the mask flags (mv_episode_log.h: episode_log_cut).  ret is doubles, len dwords, an agent's
@@ -203,6 +230,7 @@ int episode_log_update(mv_gym *g, const GymView *views, int stride, int k)
         a.hdr = g->logHdr; a.ret = g->logRet; a.len = g->logLen; a.records = g->logRecords;
         a.status = g->dStatus ? g->dStatus + g->N + 1 : nullptr;
         a.step_mask = g->stepMask;
+        a.budget = g->budgetOn ? g->budgetMirror : nullptr;
         launch_episode_log(a, g->stream);
     }
     HIP_TRY(hipGetLastError());
@@ -265,7 +293,7 @@ int mv_set_episode_log(mv_gym *g, int32_t capacity)
     g->logRecords = (Record *)(g->logMem + szHdr + szRet + szLen);
     HIP_TRY(hipMemsetAsync(g->logMem, 0, szHdr + szRet + szLen, g->stream));
     g->logCapacity = capacity;
-    return 0;
+    return episode_budget_seed_mirror(g);   // (mv_set_episode_budget: a budget attached while the log was off)
 }
 
 int mv_get_episode_log_capacity(const mv_gym *g) { return g && !g->closed ? g->logCapacity : -1; }
@@ -316,9 +344,11 @@ int64_t mv_ticks_since_reset(const mv_gym *g) { return g && !g->closed ? (int64_
 
 // The kernel's per-tick body compiled for the CPU (no device): k ticks of N envs x A agents through episode_log_tick in (tick, agent) order.
 // count, dropped, ret [N*A] and len [N] in and out; records: the buffer of `capacity` records, *count of them valid on entry.  step_mask [N] or null: the
-// envs it freezes skip every one of the k ticks (episode_log_steps).
-int mv_debug_episode_log_masked_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
-                                     uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped, const uint8_t *step_mask)
+// envs it freezes skip every one of the k ticks (episode_log_steps).  left [N] or null (mv_set_episode_budget), in and out: the log's mirror of the budgets,
+// advanced tick by tick by the rule of mv_episode_budget.h -- a tick of a halted env is skipped like a frozen one's.
+int mv_debug_episode_log_budget_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
+                                     uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped, const uint8_t *step_mask,
+                                     int32_t *left)
 {
     using namespace mv::elog;
     if (!rewards || !dones || !true_objectives || !ret || !len || !records || !count || !dropped || k < 0 || N < 1 || A < 1 || capacity < 1)
@@ -331,6 +361,7 @@ int mv_debug_episode_log_masked_host(const float *rewards, const uint8_t *dones,
         uint32_t placed = 0;
         for (int e = 0; e < N; ++e) {
             if (!episode_log_steps(step_mask, e)) continue;
+            if (left && !mv::budget::episode_budget_steps(1, left[e])) continue;
             int32_t after = len[e];
             for (int a = 0; a < A; ++a) {
                 const size_t i = (size_t)e * A + a;
@@ -342,12 +373,20 @@ int mv_debug_episode_log_masked_host(const float *rewards, const uint8_t *dones,
                 after = l;
             }
             len[e] = after;
+            if (left) (void)mv::budget::episode_budget_spend(left[e], dones[(size_t)t * N + e]);
         }
         (void)episode_log_commit(h, (uint32_t)capacity, placed);
     }
     *count = h.count;
     *dropped = h.dropped;
     return 0;
+}
+
+// ... without a budget
+int mv_debug_episode_log_masked_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
+                                     uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped, const uint8_t *step_mask)
+{
+    return mv_debug_episode_log_budget_host(rewards, dones, true_objectives, k, N, A, capacity, first_tick, ret, len, records, count, dropped, step_mask, nullptr);
 }
 
 // ... without a step mask: every env steps

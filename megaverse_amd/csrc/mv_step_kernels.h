@@ -4,12 +4,14 @@
 //   S::swap_in(gv, env, force_all)         the episode swap-in of a finished (or forced) env
 //   S::long_lists                          frame lists long enough for the depth sort (mv_frame.h: DepthSortScratch)
 //   S::par_agents                          several agents: every wave of the workgroup takes part in the tick (TowerBuilding)
-// No tick knows about step masks (mv_set_step_mask): the MASKED instantiations of the bodies choose between S::tick and frozen_tick, below.
+// No tick knows about step masks (mv_set_step_mask) or episode budgets (mv_set_episode_budget): the MASKED instantiations of the bodies choose between
+// S::tick and frozen_tick, below.
 // Every __global__ is a one-line entry point over a body in its scenario's mv_step_<scenario>.hip (a launch bound that depends on a template
 // parameter is not applied, and the profiles name the kernels); StepKernels lists them for the launchers (mv_step.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mv_episode_budget.h"
 #include "mv_frame.h"
 #include "mv_types.h"
 
@@ -34,14 +36,14 @@ __device__ __forceinline__ DepthSortScratch *depth_sort_scratch(int i)
     }
 }
 
-// ---- mv_set_step_mask: frozen envs.  Whether env stands still in the ticks of this launch: its mask byte, loaded once and made uniform (as
-// reset_masked_body's).  The env is the workgroup, so every wave of it takes the same side of the choice and every barrier stays workgroup-uniform.  Every view
+// ---- mv_set_step_mask: frozen envs.  Whether the mask lets env step in the ticks of this launch: its mask byte, loaded once and made uniform (as
+// reset_masked_body's).  The env is the workgroup, so every wave of it takes the same side of a choice and every barrier stays workgroup-uniform.  Every view
 // of a multi-tick launch carries the same mask (mv_api_step.hip; the buffer does not change while a call that reads it is in flight: include/megaverse_hip.h),
-// so such a launch asks once, through its first view.
-// Every body has a template parameter MASKED, and every step kernel two instantiations: the one a gym without a mask launches (MASKED = false) contains no
-// line of this -- it is the kernel it was, instruction for instruction -- and the one the launchers pick when the view carries a mask (mv_step.hip:
-// kernels_of).  In the masked one a frozen env takes a path of its own at the top of the body; the envs that step run the code they always ran.
-// profiles/step_mask_resources.txt has both instantiations' registers, scratch and LDS beside the parent's.
+// so the BYTE is asked once per launch, through the first view.  The choice between the scenario's tick and frozen_tick is made per tick (env_left, below:
+// mask and episode budget decide together); an env the mask freezes takes the frozen side on every tick of the launch.
+// Every body has a template parameter MASKED, and every step kernel two instantiations: the one a gym without mask or budget launches (MASKED = false)
+// contains no line of this -- it is the kernel it was, instruction for instruction -- and the one the launchers pick when the view carries a mask or a budget
+// (mv_step.hip: kernels_of).  profiles/step_mask_resources.txt and profiles/episode_budget_resources.txt have both instantiations' registers, scratch and LDS.
 __device__ __forceinline__ bool env_frozen(const GymView &gv, int env)
 {
     return gv.step_mask != nullptr && __builtin_amdgcn_readfirstlane((int)gv.step_mask[env]) == 0;
@@ -60,25 +62,33 @@ __device__ __forceinline__ void frozen_tick(const GymView &gv, int env)
     if (threadIdx.x == 0) gv.done[env] = 0;
 }
 
-// The ticks of a frozen env in a multi-tick launch (one wave per env for one agent, every wave of the workgroup for several): frozen_tick, then the frame
-// setup of the ticks whose bit is set in `frames` -- from the unchanged state, so the frames come out as they were -- between the barriers the stepping
-// envs' loop has around it.
-template <class S, int A_MAX, int NS, class Args>
-__device__ __forceinline__ void frozen_ticks(const Args &a, int env, int W, int H, uint32_t frames, FrameScratch *s_fs)
+// ---- mv_set_episode_budget: envs that halt themselves (mv_episode_budget.h has the rule).  Where a step mask is one answer per launch, a budget is one
+// PER TICK: an env whose tick j staged done with one episode left does not step in tick j + 1 of the same resident launch.  The MASKED bodies therefore carry
+// one uniform register through the launch's ticks, read once at the top (env_left):
+//     0    the env does not step in the next tick: frozen by the mask for the whole launch, or halted;
+//   < 0    it steps and has nothing to spend (no budget attached, or unlimited);
+//   > 0    it steps and may still finish that many episodes.
+// and choose per tick between S::tick and frozen_tick, between the same barriers.  Behind a tick that stepped, budget_after_tick reads the done that tick
+// staged and spends.  Every wave of the workgroup keeps its own copy and sees the same dones behind the same barriers, so the choice stays workgroup-uniform;
+// nobody reads left[env] from memory again within the launch, and the next launch on the stream reads what thread 0 stored.
+__device__ __forceinline__ int32_t env_left(const GymView &gv, int env)
 {
-    for (int j = 0; j < a.n; ++j) {
-        const GymView &gv = a.view(j);
-        frozen_tick(gv, env);
-        if (!((frames >> j) & 1u)) continue;
-        if constexpr (A_MAX == 1) {
-            wave_sync();
-            frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
-        } else {
-            __syncthreads();
-            const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
-            for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
-            __syncthreads();
-        }
+    if (env_frozen(gv, env)) return 0;   // (never stored: budget_after_tick runs behind stepped ticks only)
+    return gv.budget != nullptr ? __builtin_amdgcn_readfirstlane(gv.budget[env]) : -1;
+}
+
+// Behind a tick of `gv` that env stepped in, and behind what orders that tick's stores before this load (wave_sync: one wave; the workgroup's barrier:
+// several): the staged done, uniform (as reset_masked_body reads a count back); where it spends, thread 0 stores the env's budget and, when this tick
+// halted the env, counts it (a vector atomic).
+__device__ __forceinline__ void budget_after_tick(const GymView &gv, int env, int32_t &left)
+{
+    if (left <= 0) return;
+    const int done = __builtin_amdgcn_readfirstlane((int)gv.done[env]);
+    if (!done) return;
+    const bool halted = budget::episode_budget_spend(left, done);
+    if (threadIdx.x == 0) {
+        gv.budget[env] = left;
+        if (halted) atomicAdd(gv.halted, 1u);
     }
 }
 
@@ -98,7 +108,8 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
 #ifdef MV_STEP_PRIO
     __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
 #endif
-    if constexpr (MASKED) if (env_frozen(gv, env)) {   // (mv_set_step_mask) the frozen tick, then the env's frames as below, from the unchanged state
+    [[maybe_unused]] int32_t left = -1;
+    if constexpr (MASKED) if ((left = env_left(gv, env)) == 0) {   // (mv_set_step_mask, mv_set_episode_budget) the frozen tick, then the env's frames as below, from the unchanged state
         frozen_tick(gv, env);
         if (!render) return;
         __syncthreads();
@@ -115,6 +126,10 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
 #endif
     if constexpr (S::par_agents && A_MAX > 1) S::template tick<A_MAX, true>(gv, env);
     else if (threadIdx.x < 64) S::template tick<A_MAX>(gv, env);
+    if constexpr (MASKED) if (left > 0) {   // (mv_set_episode_budget; uniform)
+        __syncthreads();   // every wave has read left[env] before thread 0 stores it, and the tick's staged done is written
+        budget_after_tick(gv, env, left);
+    }
 #ifdef MV_TICK_TIMING
     if (!render && gv.dbg && threadIdx.x == 0) {
         const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
@@ -167,16 +182,22 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
 #ifdef MV_STEP_PRIO
     __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
 #endif
-    if constexpr (MASKED) if (env_frozen(a.view(0), env)) { frozen_ticks<S, A_MAX, NS>(a, env, W, H, ~0u, s_fs); return; }   // (mv_set_step_mask)
+    [[maybe_unused]] int32_t left = -1;   // (mv_set_step_mask, mv_set_episode_budget: env_left)
+    if constexpr (MASKED) left = env_left(a.view(0), env);
     for (int j = 0; j < a.n; ++j) {
         const GymView &gv = a.view(j);
+        const bool steps = !MASKED || left != 0;   // (uniform; without MASKED: a constant)
         if constexpr (A_MAX == 1) {
-            S::template tick<1>(gv, env);
+            if (steps) S::template tick<1>(gv, env);
+            else frozen_tick(gv, env);
             wave_sync();   // the tick's stores before the frame setup's loads (one wave: no barrier needed)
+            if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
             frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
         } else {
-            S::template tick<A_MAX, true>(gv, env);
+            if (steps) S::template tick<A_MAX, true>(gv, env);
+            else frozen_tick(gv, env);
             __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
+            if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
             const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
             for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
             __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
@@ -197,36 +218,44 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
 #ifdef MV_STEP_PRIO
     __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
 #endif
+    // (mv_set_step_mask, mv_set_episode_budget: env_left.  An env that is frozen or halted when a FRAMES = false launch starts leaves behind the loads of
+    // env_left and n tiny stores)
+    [[maybe_unused]] int32_t left = -1;
+    if constexpr (MASKED) left = env_left(a.view(0), env);
     if constexpr (!FRAMES) {
-        if constexpr (MASKED) if (env_frozen(a.view(0), env)) {   // (mv_set_step_mask) a frozen env's waves leave behind one mask load and n tiny stores
-            for (int j = 0; j < a.n; ++j) frozen_tick(a.view(j), env);
-            return;
-        }
         for (int j = 0; j < a.n; ++j) {
             const GymView &gv = a.view(j);
+            const bool steps = !MASKED || left != 0;   // (uniform; without MASKED: a constant)
             if constexpr (A_MAX == 1) {
-                S::template tick<1>(gv, env);
+                if (steps) S::template tick<1>(gv, env);
+                else frozen_tick(gv, env);
                 wave_sync();       // the tick's stores before the next tick's loads (one wave: no barrier needed)
             } else {
-                S::template tick<A_MAX, true>(gv, env);
+                if (steps) S::template tick<A_MAX, true>(gv, env);
+                else frozen_tick(gv, env);
                 __syncthreads();   // the tick's stores (same CU: same L1) before the next tick's loads
             }
+            if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
         }
     } else {
         constexpr int NS = A_MAX == 1 ? 1 : 4;
         __shared__ FrameScratch s_fs[NS];
         const uint32_t mask = (uint32_t)a.pad;
-        if constexpr (MASKED) if (env_frozen(a.view(0), env)) { frozen_ticks<S, A_MAX, NS>(a, env, W, H, mask, s_fs); return; }   // (mv_set_step_mask)
         for (int j = 0; j < a.n; ++j) {
             const GymView &gv = a.view(j);
             const bool frames = (mask >> j) & 1u;
+            const bool steps = !MASKED || left != 0;   // (uniform; without MASKED: a constant)
             if constexpr (A_MAX == 1) {
-                S::template tick<1>(gv, env);
+                if (steps) S::template tick<1>(gv, env);
+                else frozen_tick(gv, env);
                 wave_sync();   // the tick's stores before the frame setup's / the next tick's loads
+                if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
                 if (frames) frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
             } else {
-                S::template tick<A_MAX, true>(gv, env);
+                if (steps) S::template tick<A_MAX, true>(gv, env);
+                else frozen_tick(gv, env);
                 __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's / the next tick's loads
+                if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
                 if (frames) {
                     const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
                     for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
@@ -253,17 +282,18 @@ __device__ __forceinline__ void step_ticks_pipe_body(const Args &a, int W, int H
     __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
 #endif
     if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0) {
-        if constexpr (MASKED) if (env_frozen(a.view(0), env)) {   // (mv_set_step_mask) the frozen ticks at the barriers of the stepping ones; wave 1 sets the frames up as always
-            for (int j = 0; j < a.n; ++j) {
+        // (mv_set_step_mask, mv_set_episode_budget: env_left) a tick that does not step is the frozen tick at the barriers of a stepping one -- both barriers
+        // of the iteration on either side of the choice; wave 1 sets the frames up as always, and only this wave needs to know what is left
+        [[maybe_unused]] int32_t left = -1;
+        if constexpr (MASKED) left = env_left(a.view(0), env);
+        for (int j = 0; j < a.n; ++j) {
+            if (!MASKED || left != 0) {
+                S::template tick<1>(a.view(j), env, j > 0);   // (j > 0: B(j - 1) inside, before the write-back)
+                if constexpr (MASKED) if (left > 0) { wave_sync(); budget_after_tick(a.view(j), env, left); }   // (this wave's own stores)
+            } else {
                 if (j > 0) __syncthreads();               // B(j - 1): inside a tick (pipe_wait), here in the open
                 frozen_tick(a.view(j), env);
-                __syncthreads();                          // A(j)
             }
-            __syncthreads();                              // B(n - 1)
-            return;
-        }
-        for (int j = 0; j < a.n; ++j) {
-            S::template tick<1>(a.view(j), env, j > 0);   // (j > 0: B(j - 1) inside, before the write-back)
             __syncthreads();                              // A(j)
         }
         __syncthreads();                                  // B(n - 1): the last frame setup's

@@ -192,6 +192,11 @@ struct GymView {
     // mv_set_step_mask: [N] bytes, 0 = the env is frozen -- this tick leaves its state alone (mv_step_kernels.h: frozen_tick); null: no mask, every env
     // steps.  Set by the stepping calls only (mv_api_step.hip): the views of resets, forks and the union launches leave it null.
     const uint8_t *step_mask;
+    // mv_set_episode_budget: [N] episodes each env may still finish (< 0: unlimited, 0: halted -- its ticks are frozen ticks), written by the MASKED step
+    // bodies behind a tick that staged done (mv_step_kernels.h: budget_after_tick), and the count of halted envs they keep; null: no budget.  Set by the
+    // stepping calls only, like step_mask.
+    int32_t *budget;
+    uint32_t *halted;
 };
 
 // The n <= 8 consecutive ticks of a multi-tick step launch (mv_step.hip: step_ticks_kernel, and every mv_step_*.hip), the same envs in all of them: their views

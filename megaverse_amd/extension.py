@@ -93,6 +93,10 @@ SYMBOLS = [
     ("mv_debug_episode_log_host", C.c_int, [_P, _P, _P, _I, _I, _I, _I, _U, _P, _P, _P, C.POINTER(_U), C.POINTER(_U)]),
     ("mv_set_step_mask", C.c_int, [_P, _P]), ("mv_set_step_mask_host", C.c_int, [_P, _P]), ("mv_get_step_mask", C.c_int, [_P]),
     ("mv_debug_episode_log_masked_host", C.c_int, [_P, _P, _P, _I, _I, _I, _I, _U, _P, _P, _P, C.POINTER(_U), C.POINTER(_U), _P]),
+    ("mv_set_episode_budget", C.c_int, [_P, _P]), ("mv_set_episode_budget_host", C.c_int, [_P, _P]), ("mv_get_episode_budget", C.c_int, [_P]),
+    ("mv_episode_budget_device_ptr", _P, [_P]), ("mv_halted_count_device_ptr", _P, [_P]), ("mv_halted_count", C.c_int, [_P, C.POINTER(_I)]),
+    ("mv_debug_episode_log_budget_host", C.c_int, [_P, _P, _P, _I, _I, _I, _I, _U, _P, _P, _P, C.POINTER(_U), C.POINTER(_U), _P, _P]),
+    ("mv_debug_episode_budget_host", C.c_int, [_P, _P, _P, _I, _I, _P, _P]),
 ]
 
 # mv_episode_record (include/megaverse_hip.h): one finished episode of one agent, 24 bytes
@@ -120,7 +124,31 @@ def debug_episode_log_masked_host(step_mask, rewards, dones, true_objectives, ag
     return _episode_log_host(True, step_mask, rewards, dones, true_objectives, agents_per_env, capacity, first_tick, state)
 
 
-def _episode_log_host(masked, step_mask, rewards, dones, true_objectives, agents_per_env, capacity, first_tick, state):
+def debug_episode_log_budget_host(step_mask, left, rewards, dones, true_objectives, agents_per_env, capacity, first_tick=0, state=None):
+    """mv_debug_episode_log_budget_host: debug_episode_log_masked_host with an episode budget (mv_set_episode_budget) -- left: int32 [N], the log's mirror of
+    the budgets, advanced IN PLACE tick by tick (it must be a contiguous int32 numpy array); None: the hook's NULL, no budget."""
+    if left is not None and not (isinstance(left, np.ndarray) and left.dtype == np.int32 and left.flags.c_contiguous and left.ndim == 1):
+        raise ValueError("debug_episode_log_budget_host: left is a contiguous int32 numpy array [N], advanced in place")
+    return _episode_log_host(True, step_mask, rewards, dones, true_objectives, agents_per_env, capacity, first_tick, state, budget=(left,))
+
+
+def debug_episode_budget_host(dones, mask, left):
+    """mv_debug_episode_budget_host: the rule of episode budgets on the CPU (no device).  dones [k][N]: what tick t stages for env e if it steps; mask [N]
+    bytes or None; left int32 [N] -> (steps uint8 [k][N]: 1 where the env steps in the tick, left int32 [N] behind the last tick)"""
+    lib = load_library()
+    dones = np.ascontiguousarray(dones, np.uint8)
+    k, N = dones.shape
+    left = np.ascontiguousarray(left, np.int32).reshape(-1)
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+    if left.size != N or (m is not None and m.size != N):
+        raise ValueError("debug_episode_budget_host: dones is [k][N], mask and left are [N]")
+    steps, out = np.full((k, N), 9, np.uint8), np.full(N, -9, np.int32)
+    if lib.mv_debug_episode_budget_host(dones.ctypes.data, None if m is None else m.ctypes.data, left.ctypes.data, k, N, steps.ctypes.data, out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return steps, out
+
+
+def _episode_log_host(masked, step_mask, rewards, dones, true_objectives, agents_per_env, capacity, first_tick, state, budget=None):
     lib = load_library()
     rewards = np.ascontiguousarray(rewards, np.float32)
     dones = np.ascontiguousarray(dones, np.uint8)
@@ -141,7 +169,13 @@ def _episode_log_host(masked, step_mask, rewards, dones, true_objectives, agents
         m = None if step_mask is None else np.ascontiguousarray(step_mask, np.uint8).reshape(-1)   # (the raw bytes: any non-zero byte steps)
         if m is not None and m.size != N:
             raise ValueError("debug_episode_log_masked_host: step_mask is [N] bytes")
-        rc = lib.mv_debug_episode_log_masked_host(*args, None if m is None else m.ctypes.data)
+        if budget is None:
+            rc = lib.mv_debug_episode_log_masked_host(*args, None if m is None else m.ctypes.data)
+        else:
+            left = budget[0]
+            if left is not None and left.size != N:
+                raise ValueError("debug_episode_log_budget_host: left is [N]")
+            rc = lib.mv_debug_episode_log_budget_host(*args, None if m is None else m.ctypes.data, None if left is None else left.ctypes.data)
     if rc != 0:
         raise RuntimeError(lib.mv_last_error().decode())
     state["count"], state["dropped"] = int(count.value), int(dropped.value)
@@ -303,6 +337,29 @@ def check_step_mask(mask, num_envs):
     return None if mask is None else _check_env_mask(mask, num_envs, 'set_step_mask', 'the env steps')
 
 
+def check_episode_budget(budget, num_envs):
+    """the argument check of MegaverseGym.set_episode_budget: None (detach) -> None; an int -> that value for every env; a contiguous torch.int32 CUDA tensor
+    of shape (num_envs,) (or anything with data_ptr()) -> 'device'; anything else -> a contiguous int32 numpy array, one value per env"""
+    n = int(num_envs)
+    if budget is None:
+        return None
+    if isinstance(budget, (int, np.integer)) and not isinstance(budget, (bool, np.bool_)):
+        if not -2 ** 31 <= int(budget) < 2 ** 31:
+            raise ValueError(f'set_episode_budget: {budget} is not an int32')
+        return np.full(n, int(budget), np.int32)
+    if hasattr(budget, 'data_ptr'):
+        contiguous = getattr(budget, 'is_contiguous', None)
+        if tuple(getattr(budget, 'shape', ())) != (n,) or str(getattr(budget, 'dtype', None)) != 'torch.int32' \
+                or not getattr(budget, 'is_cuda', False) or not (callable(contiguous) and contiguous()):
+            raise ValueError(f'set_episode_budget: a tensor budget must be a contiguous int32 CUDA tensor of shape ({n},), '
+                             f"got {getattr(budget, 'dtype', None)} {tuple(getattr(budget, 'shape', ()))} on {getattr(budget, 'device', 'an unknown device')}")
+        return 'device'
+    b = np.asarray(budget)
+    if b.shape != (n,) or b.dtype.kind not in 'iu' or (b.size and (b.min() < -2 ** 31 or b.max() >= 2 ** 31)):
+        raise ValueError(f'set_episode_budget: the budget must be {n} int32 values (< 0: unlimited, 0: halted), got {b.dtype} {b.shape}')
+    return np.ascontiguousarray(b, dtype=np.int32)
+
+
 # include/megaverse_hip.h: MV_RENDER_EVERY / MV_RENDER_LAST / MV_RENDER_NONE, by the names step_n(render=...) takes
 RENDER_MODES = {"every": 0, "last": 1, "none": 2}
 
@@ -408,6 +465,7 @@ class MegaverseGym:
         self._fork_held = None   # fork_envs: the caller's device map, kept until the next step has been enqueued
         self._reset_held = None  # reset_envs: the caller's device mask, likewise
         self._step_mask_held = None  # set_step_mask: the caller's device mask, kept until it is replaced or detached
+        self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
         self._store_held = []    # save_envs / load_envs: the caller's stores and device maps, kept until the next step has been enqueued
 
     def _ck(self, rc):
@@ -444,7 +502,7 @@ class MegaverseGym:
 
     def step(self):
         self._ckw(self._lib.mv_step(self._g))
-        self._fork_held = self._reset_held = None
+        self._fork_held = self._reset_held = self._budget_held = None
         self._store_held = []
 
     def is_done(self, env_idx):
@@ -522,7 +580,7 @@ class MegaverseGym:
 
     def step_no_render(self):
         self._ckw(self._lib.mv_step_no_render(self._g))
-        self._fork_held = self._reset_held = None
+        self._fork_held = self._reset_held = self._budget_held = None
         self._store_held = []
 
     POLICIES = {"none": 0, "multidiscrete": 1, "single-bit": 2, "sequence": 3}
@@ -536,7 +594,7 @@ class MegaverseGym:
         mode = render_mode_of(render)
         args = (self._g, int(k), int(self.POLICIES.get(policy, policy)), int(seed) & 0xFFFFFFFF, int(first_step_index) & 0xFFFFFFFF)
         self._ckw(self._lib.mv_step_n(*args) if mode == 0 else self._lib.mv_step_n_render(*args, mode))
-        self._fork_held = self._reset_held = None
+        self._fork_held = self._reset_held = self._budget_held = None
         self._store_held = []
 
     def fork_envs(self, src_of):
@@ -647,6 +705,47 @@ class MegaverseGym:
     def step_mask(self):
         """-> 'none' | 'device' | 'host': the form of the step mask attached (set_step_mask)"""
         return self.STEP_MASK_FORMS[self._ck(self._lib.mv_get_step_mask(self._g))]
+
+    def set_episode_budget(self, budget):
+        """Episode budgets (include/megaverse_hip.h: mv_set_episode_budget): env e may finish budget[e] more episodes (< 0: unlimited) and then HALTS on the
+        device -- in the middle of a batched call too -- frozen on the first frame of its next episode: reward 0, done 0, its state untouched.  An int gives
+        every env that value; a contiguous torch.int32 CUDA tensor of shape (num_envs,) is read once, in the order of the gym's stream (the gym holds a
+        reference until the next stepping call has been enqueued; leave it unchanged until the stream has passed the attach); a numpy array or a
+        list is copied through a staging buffer; None detaches.  Attaching again replaces every value.  Neither form waits on the host."""
+        b = check_episode_budget(budget, self.num_envs)
+        if b is None:
+            self._ck(self._lib.mv_set_episode_budget(self._g, None))
+        elif isinstance(b, str):
+            self._ck(self._lib.mv_set_episode_budget(self._g, _P(int(budget.data_ptr()))))
+            self._budget_held = budget   # (the attach kernel reads it in the order of the gym's stream, which need not be torch's current one)
+        else:
+            self._ck(self._lib.mv_set_episode_budget_host(self._g, b.ctypes.data))
+
+    def has_episode_budget(self):
+        return self._ck(self._lib.mv_get_episode_budget(self._g)) == 1
+
+    def episode_budget(self):
+        """int32 CUDA tensor [num_envs]: what every env may still finish (0: halted), a view of the gym's memory, valid in the order of the gym's stream
+        after any stepping call"""
+        import torch
+        ptr = int(self._lib.mv_episode_budget_device_ptr(self._g) or 0)
+        if not ptr:
+            raise RuntimeError("no episode budget attached (set_episode_budget)")
+        return torch.as_tensor(_DeviceArray(ptr, (self.num_envs,), "<i4"), device=f"cuda:{self.device}")
+
+    def halted_count_tensor(self):
+        """uint32 as an int32 CUDA tensor [1]: the number of halted envs (a view, like episode_budget)"""
+        import torch
+        ptr = int(self._lib.mv_halted_count_device_ptr(self._g) or 0)
+        if not ptr:
+            raise RuntimeError("no episode budget attached (set_episode_budget)")
+        return torch.as_tensor(_DeviceArray(ptr, (1,), "<i4"), device=f"cuda:{self.device}")
+
+    def halted_count(self):
+        """-> the number of halted envs; synchronises the gym's stream"""
+        out = _I()
+        self._ck(self._lib.mv_halted_count(self._g, C.byref(out)))
+        return int(out.value)
 
     def set_action_ring(self, count, device_ptr=0):
         """int32 [count, num_agents, 6] multi-discrete actions in device memory for step_n(..., 'sequence') (include/megaverse_hip.h: mv_set_action_ring);

@@ -331,6 +331,58 @@ class MegaverseEnv:
             self._frozen[self._env_ids(env_ids, 'thaw')] = False
         self.env.set_step_mask(~self._frozen if self._frozen.any() else None)
 
+    def set_episode_budget(self, budget):
+        """Episode budgets (MegaverseGym.set_episode_budget): env e may finish budget[e] more episodes (an int: every env that many; < 0: unlimited) and then
+        halts on the device, frozen on the first frame of its next episode -- inside a batched call too; None detaches.  Setting it again replaces every
+        value: the halted envs resume."""
+        self.env.set_episode_budget(budget)
+
+    def halted(self):
+        """bool CUDA tensor [num_envs]: the envs whose budget is spent (episode_budget() == 0), in the order of the gym's stream"""
+        self._torch()
+        return self.env.episode_budget() == 0
+
+    def run_episodes(self, episodes=1, policy="random", render="none", max_ticks=None, actions=None, seed=0):
+        """Every env runs exactly `episodes` episodes and stops where its last one ends -- the unbiased evaluation protocol, as batched calls: the episode log
+        is switched on if it is off, the budget attached, and calls of recommended_ticks_per_call() ticks follow until every env has halted (the halted count
+        is read once per call, not per tick) or max_ticks ticks have been stepped.  policy: 'random' (the device-side multi-discrete policy, `seed`) or
+        'sequence' (actions: [count, num_agents, 6], replayed modulo count, as step_sequence takes them).  render: 'none' | 'last' | 'every'
+        (MegaverseGym.step_n).  -> the drained records (EPISODE_RECORD_DTYPE): episodes x num_envs x agents of them when nobody ran out of ticks -- in
+        front of them whatever a log that was already on still held: drain it first where that matters.  The
+        budget stays attached and every env halted: set_episode_budget resumes or detaches."""
+        if policy not in ("random", "sequence"):
+            raise ValueError("run_episodes: policy is 'random' or 'sequence'")
+        if int(episodes) < 1:
+            raise ValueError("run_episodes: episodes >= 1")
+        render_mode_of(render)
+        self._leave_sequence()
+        if self._obs_tensor is None:
+            self.observations_tensor()
+        held = None
+        if policy == "sequence":
+            if actions is None:
+                raise ValueError("run_episodes: policy='sequence' replays `actions` [count, num_agents, 6]")
+            count = check_sequence_actions(actions, self.num_agents)
+            torch = self._torch()
+            held = actions.contiguous() if hasattr(actions, 'data_ptr') else \
+                torch.as_tensor(np.ascontiguousarray(actions, dtype=np.int32)).to(torch.device(f'cuda:{self.device}'))
+            self.env.set_action_ring(count, held.data_ptr())
+        if self.env.episode_log_capacity() <= 0:
+            self.env.set_episode_log(int(episodes) * self.num_envs * self.num_agents_per_env)
+        self.env.set_episode_budget(int(episodes))
+        chunk, tick = max(1, self.env.recommended_ticks_per_call()), 0
+        while max_ticks is None or tick < int(max_ticks):
+            k = chunk if max_ticks is None else min(chunk, int(max_ticks) - tick)
+            self.env.step_n(k, 'sequence' if policy == "sequence" else 'multidiscrete', seed, tick, render=render)
+            tick += k
+            if self.env.halted_count() == self.num_envs:
+                break
+        records = self.env.drain_episode_log()
+        if held is not None:
+            self.env.set_action_ring(0)
+        del held
+        return records
+
     def _leave_sequence(self):
         """step_sequence's rings are attached: back to the single slab and arrays, the slab brought up to date"""
         if self._seq is None:

@@ -158,6 +158,13 @@ class MultiTaskGym:
             g.set_action_ring(count, ring.data_ptr())
         return self.action_rings
 
+    def set_episode_budget(self, budget):
+        """episode budgets (MegaverseGym.set_episode_budget) are per gym: a group's union launches read none, and the library refuses"""
+        if self._group is not None and budget is not None:
+            self.gyms[0].set_episode_budget(budget if isinstance(budget, (int, np.integer)) else 1)   # (raises, with the library's text)
+        raise RuntimeError("MultiTaskGym.set_episode_budget: mv_group_create and mv_step_many refuse a gym with an episode budget attached "
+                           "(mv_set_episode_budget): the union launches read none; step such a gym on its own")
+
     def recommended_ticks_per_call(self):
         """the k to ask step_n for: what every member recommends (mv_recommended_ticks_per_call), at most 8 -- the two-launch group call's limit"""
         return max(1, min([8] + [g.recommended_ticks_per_call() for g in self.gyms]))

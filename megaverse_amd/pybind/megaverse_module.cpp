@@ -182,6 +182,24 @@ public:
     }
     std::uintptr_t episode_returns_device_ptr() const { return reinterpret_cast<std::uintptr_t>(mv_episode_returns_device_ptr(gym_)); }
     std::uintptr_t episode_lengths_device_ptr() const { return reinterpret_cast<std::uintptr_t>(mv_episode_lengths_device_ptr(gym_)); }
+    // episode budgets (mv_set_episode_budget): env e may finish budget[e] more episodes (< 0: unlimited) and then halts on the device; None detaches
+    void set_episode_budget(const py::object &budget)
+    {
+        if (budget.is_none()) { check(mv_set_episode_budget_host(gym_, nullptr)); return; }
+        if (py::isinstance<py::bool_>(budget)) throw std::runtime_error("set_episode_budget: an int, a sequence of ints (one per env) or None");   // (a bool is an int to Python)
+        std::vector<int32_t> b = py::isinstance<py::int_>(budget) ? std::vector<int32_t>((size_t)envs_, budget.cast<int32_t>()) : budget.cast<std::vector<int32_t>>();
+        if ((int)b.size() != envs_) throw std::runtime_error("set_episode_budget: one value per env");
+        check(mv_set_episode_budget_host(gym_, b.data()));
+    }
+    bool has_episode_budget() const { return mv_get_episode_budget(gym_) == 1; }
+    int halted_count()
+    {
+        int32_t n = 0;
+        check(mv_halted_count(gym_, &n));
+        return n;
+    }
+    std::uintptr_t episode_budget_device_ptr() const { return reinterpret_cast<std::uintptr_t>(mv_episode_budget_device_ptr(gym_)); }
+    std::uintptr_t halted_count_device_ptr() const { return reinterpret_cast<std::uintptr_t>(mv_halted_count_device_ptr(gym_)); }
 
 private:
     mv_gym *gym_ = nullptr;
@@ -226,5 +244,10 @@ PYBIND11_MODULE(megaverse, m)
         .def("episode_log_count", &Gym::episode_log_count)
         .def("drain_episode_log", &Gym::drain_episode_log)
         .def("episode_returns_device_ptr", &Gym::episode_returns_device_ptr)
-        .def("episode_lengths_device_ptr", &Gym::episode_lengths_device_ptr);
+        .def("episode_lengths_device_ptr", &Gym::episode_lengths_device_ptr)
+        .def("set_episode_budget", &Gym::set_episode_budget)
+        .def("has_episode_budget", &Gym::has_episode_budget)
+        .def("halted_count", &Gym::halted_count)
+        .def("episode_budget_device_ptr", &Gym::episode_budget_device_ptr)
+        .def("halted_count_device_ptr", &Gym::halted_count_device_ptr);
 }
