@@ -485,6 +485,14 @@ int mv_debug_football_state(mv_gym *g, int32_t env_idx, void *out_host);
 int mv_debug_set_football_state(mv_gym *g, int32_t env_idx, const void *in_host);
 int mv_debug_rng(int32_t device, uint32_t seed, int32_t what, const int32_t *lo, const int32_t *hi, int32_t n, void *out_host);
 int mv_debug_math(int32_t device, int32_t what, const float *a, const float *b, int32_t n, float *out_host);
+/* Host-only (no device): what the observation pass takes from the host per launch instead of computing it per workgroup (megaverse_amd/csrc/mv_raster.h:
+ * RasterConsts, raster_ray_table) for a W x H observation -- consts[4] = sx, ox, sy, oy (ray abscissa = sx i + ox, sy j + oy), *tiles_x_inv =
+ * the reciprocal of the tiles per row (mv_debug_raster_div_host's magic), dcx[W] / dcy[H] the abscissae of every column / row as the gym's
+ * device table holds them.  Any pointer may be NULL (dcx and dcy are written together or not at all). */
+int mv_debug_raster_consts_host(int32_t W, int32_t H, float *consts, uint32_t *tiles_x_inv, float *dcx, float *dcy);
+/* Host-only: the reciprocal form of the pass's integer divisions -- *magic = ceil(2^32 / d) (0 for d = 1, which has none in 32 bits), q[n] = (n * magic) >> 32
+ * (n where magic is 0) for n < n_end: == n / d in the kernels' range, tile indices below 2^16 and d <= 64. */
+int mv_debug_raster_div_host(uint32_t d, uint32_t n_end, uint32_t *magic, uint32_t *q);
 /* Host-only (no device): the n-th (1-based) episode an env seeded with env_seed generates for a host-generated
  * scenario (Obstacles family, Collect), as the raw blob the reset kernel swaps in.  Returns the blob size in
  * bytes (out == NULL: size query only), -1 on error.  Replaces Env::reset's scenario->reset() + spawnAgents

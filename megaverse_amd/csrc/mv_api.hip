@@ -408,7 +408,10 @@ int mv_create(const mv_config *cfg, mv_gym **out)
                  szLpt = up(NA * sizeof(int32_t)) + up((NA + 1) * sizeof(int32_t)) + up(NA * (size_t)FRAME_HDR_BYTES)
                             + up((size_t)LPT_BUCKETS * LPT_SUBS * lpt_sub_capacity(NA) * sizeof(int32_t));
     // per slot: frame lists, headers, cost lists, and the staging copies of rewards / dones / true objectives
-    const size_t szParity = szVisP + szVisR + szVisC + szLpt + szRew + szDone + szObjv;
+    // (+ the frame-order table of the slot's tick, GymView::lpt_forder; MV_FRAME_ORDER=0: none, every workgroup of a pass looks its frame up in the histogram)
+    const bool frameOrderOn = !(getenv("MV_FRAME_ORDER") && atoi(getenv("MV_FRAME_ORDER")) == 0);
+    const size_t szFOrder = frameOrderOn ? up(NA * sizeof(int32_t)) : 0;
+    const size_t szParity = szVisP + szVisR + szVisC + szLpt + szRew + szDone + szObjv + szFOrder;
     // Ticks per call of mv_step_n (`batch`; a gym holds PIPE_GROUPS x batch hand-over slots of szParity bytes each): 16 -- one tail of the one-launch
     // observation pass per 16 ticks, measured against 8: TowerBuilding 1024 envs 26.6 -> 28.3 M obs/s -- where the 48 slots that takes stay under 2.25 GiB,
     // else 8 (a Hex frame's slot is 80 KB: 3.8 GB per 1024 frames at 16, 1.9 GB at 8 -- and 16 buys it nothing: 9.32 / 9.40 M obs/s, r09k; Collect's 42 KB: 2.1
@@ -427,8 +430,11 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     // long lists: the list as found, before the frame setup deals it into depth classes (mv_frame.h: DepthSortScratch); MV_DEPTH_SORT=0: lists stay as found
     const bool depthSortOn = !(getenv("MV_DEPTH_SORT") && atoi(getenv("MV_DEPTH_SORT")) == 0);
     const size_t szSort = gv.vis_stride > 256 && depthSortOn ? up(NA * (size_t)gv.vis_stride * 40) : 0;
+    // the observation's ray abscissae (GymView::ray_tab); MV_RAY_TABLE=0: the pass computes them per workgroup (A/B measurements, tests)
+    const bool rayTabOn = !(getenv("MV_RAY_TABLE") && atoi(getenv("MV_RAY_TABLE")) == 0);
+    const size_t szRay = rayTabOn ? up((size_t)(g->w + g->h) * sizeof(float)) : 0;
     const size_t total = szSort + szHdr + szBoxes + szObj + szAg + szAct + szRew + szDone + szObjv + szMd + (hostEpisodes ? 0 : szChunk) + szObs + szTerrain +
-                         szRewObj + szHeight + szItems + szCells + szHexB + szHexO + szBag + szFb + szBlobs + szCnt + szGen + (size_t)g->slots * szParity + szHist;
+                         szRewObj + szHeight + szItems + szCells + szHexB + szHexO + szBag + szFb + szBlobs + szCnt + szGen + (size_t)g->slots * szParity + szHist + szRay;
     {
         hipError_t e_ = hipMalloc((void **)&g->arena, total);
         if (e_ != hipSuccess) {
@@ -493,6 +499,14 @@ int mv_create(const mv_config *cfg, mv_gym **out)
         }
         gv.lpt_hist = (int32_t *)p; p += szHist;
         gv.sort_scratch = szSort ? p : nullptr; p += szSort;
+        if (szRay) {
+            std::vector<float> tab((size_t)(g->w + g->h));
+            raster_ray_table(g->w, g->h, tab.data());
+            hipError_t e_ = hipMemcpy(p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
+            if (e_ != hipSuccess) { mv_destroy(g); return fail(std::string("mv_create: ray table upload: ") + hipGetErrorString(e_)); }
+            gv.ray_tab = (const float *)p; gv.ray_w = g->w; gv.ray_h = g->h;
+            p += szRay;
+        }
         gv.depth_sort = 0;
         for (int q = 0; q < g->slots; ++q) {   // gv.rewards / done / true_objective stay the public arrays; the slot views write their own
             GymView &v = g->gvp[q];
@@ -507,6 +521,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
             v.rewards = (float *)p; p += szRew;
             v.done = p; p += szDone;
             v.true_objective = (float *)p; p += szObjv;
+            v.lpt_forder = szFOrder ? (int32_t *)p : nullptr; p += szFOrder;
         }
     }
     if (getenv("MV_TICK_TIMING") && atoi(getenv("MV_TICK_TIMING"))) {   // (an instrumented build, -DMV_TICK_TIMING: phase cycle sums, printed by mv_close)

@@ -418,4 +418,28 @@ int mv_debug_math(int32_t device, int32_t what, const float *a, const float *b, 
     return 0;
 }
 
+int mv_debug_raster_consts_host(int32_t W, int32_t H, float *consts, uint32_t *tiles_x_inv, float *dcx, float *dcy)
+{
+    if (W < 1 || H < 1 || W > 1024 || H > 1024) return fail("mv_debug_raster_consts_host: size must be within 1..1024");
+    const RasterConsts rc = raster_launch_consts(W, H);
+    if (consts) { consts[0] = rc.sx; consts[1] = rc.ox; consts[2] = rc.sy; consts[3] = rc.oy; }
+    if (tiles_x_inv) *tiles_x_inv = rc.tiles_x_inv;
+    if (dcx && dcy) {
+        std::vector<float> tab((size_t)(W + H));
+        raster_ray_table(W, H, tab.data());
+        std::memcpy(dcx, tab.data(), (size_t)W * sizeof(float));
+        std::memcpy(dcy, tab.data() + W, (size_t)H * sizeof(float));
+    }
+    return 0;
+}
+
+int mv_debug_raster_div_host(uint32_t d, uint32_t n_end, uint32_t *magic, uint32_t *q)
+{
+    if (d < 1) return fail("mv_debug_raster_div_host: d >= 1");
+    const uint32_t m = raster_div_magic(d);
+    if (magic) *magic = m;
+    if (q) for (uint32_t n = 0; n < n_end; ++n) q[n] = raster_div_by_magic(n, m);   // (the kernels' div_magic: __umulhi)
+    return 0;
+}
+
 }  // extern "C"

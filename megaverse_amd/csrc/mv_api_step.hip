@@ -181,14 +181,19 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
                 if (callEv) HIP_TRY(hipEventRecord(callEv[0], sim));
                 // (completed by the last launch's own dispatch packet: no marker behind it on the simulation stream)
                 hipEvent_t rides = own && !callEv ? L->simDone : nullptr;
+                const bool frameOrder = allFast && views[0].lpt_forder != nullptr;   // (fast pixels: the exact kernel has its own sort; MV_FRAME_ORDER=0: no table)
                 const int chunkTicks = 8;   // (a launch holds the views of up to 8 ticks as its arguments, mv_types.h: StepTicksArgs8)
                 for (int j0 = 0; j0 < k; j0 += chunkTicks) {
                     const int kk = std::min(chunkTicks, k - j0);
                     const GymView *vw = views.data() + j0;
-                    hipEvent_t r = j0 + kk == k ? rides : nullptr;
+                    // (with the frame-order table its kernel is the call's last on this stream: the event rides on that packet)
+                    hipEvent_t r = j0 + kk == k && !frameOrder ? rides : nullptr;
                     launch_step_ticks(vw, kk, sim, L->w, L->h, r);
                     ++L->launchCount[0];
                 }
+                // one frame-order table per tick, once, where every workgroup of the call's passes used to derive its frame from the tick's histogram
+                // (mv_raster.h); the kernel also zeroes the histograms: the passes neither count themselves in nor clear (histClean: set where they are enqueued)
+                if (frameOrder) launch_frame_order_ticks(views.data(), k, sim, rides);
                 if (callEv) HIP_TRY(hipEventRecord(callEv[1], sim));
                 simDoneRides = rides != nullptr;
             }

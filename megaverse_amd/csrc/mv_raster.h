@@ -36,4 +36,22 @@ bool raster_union_batch_applicable(int k, int n, int W, int H);
 int launch_raster_union_batch(const GymView *views, uint32_t *const *obs, const PublishTo *publish, int k,
                               int n, int W, int H, hipStream_t stream, hipEvent_t done = nullptr);
 
+// The frame-order tables of the k <= MAX_STEP_TICKS ticks of a batched one-gym call, on the stream of its step launches and directly behind them: one small
+// kernel writes order[position] = frame into every tick's GymView::lpt_forder (not null) and zeroes the tick's cost histogram; the views are marked
+// (lpt_forder_on) so that the passes launched from them read the table.  done: completes with the kernel, carried by its dispatch packet.
+void launch_frame_order_ticks(GymView *views, int k, hipStream_t stream, hipEvent_t done = nullptr);
+
+// What the fast kernels need of the observation size alone, computed ONCE on the host -- with the single-precision expressions the kernels used to
+// evaluate in every workgroup, operation for operation (IEEE division is correctly rounded on both sides, the host build contracts nothing): the same bits
+// (tests/test_launch_constants.py).
+// sx, ox, sy, oy: a ray's camera-space abscissae as affine functions of the pixel, dcx = sx i + ox, dcy = sy j + oy (classify_tiles);
+// tiles_x_inv: raster_div_magic(tilesX), the reciprocal of tile / tilesX
+struct RasterConsts { float sx, ox, sy, oy; uint32_t tiles_x_inv; };
+RasterConsts raster_launch_consts(int W, int H);
+// dcx[W] then dcy[H]: the abscissae themselves, as the prologue's tables hold them (GymView::ray_tab)
+void raster_ray_table(int W, int H, float *out);
+// n / d as a multiplication: m = ceil(2^32 / d), n / d == (n m) >> 32 while n d < 2^32.  d = 1 has no such m in 32 bits: 0 stands for it (n / 1 = n).
+inline uint32_t raster_div_magic(uint32_t d) { return d <= 1u ? 0u : (uint32_t)((0x100000000ull + d - 1u) / d); }
+inline uint32_t raster_div_by_magic(uint32_t n, uint32_t m) { return m ? (uint32_t)(((uint64_t)n * m) >> 32) : n; }
+
 }  // namespace mv

@@ -288,6 +288,76 @@ __global__ __launch_bounds__(1024) void frame_order_kernel(GymView gv, int frame
     for (int f = tid; f < frames; f += 1024) order[atomicAdd(&s_start[gv.lpt_bucket[f]], 1)] = f;
 }
 
+// ---- the fast pass's frame order as a table, one workgroup per tick of a batched call (launch_frame_order_ticks).  What every workgroup of a pass used to
+// derive for itself in fast_prologue -- the prefix sum over the 256 cost bins, bin 255 first, and within a bin its LPT_SUBS lists one after the other in
+// arrival order -- is written out once: order[position] = frame for all `frames` positions, the very order fast_prologue's look-up gives.  Then the tick's
+// histogram is zeroed (every thread's loads from it returned before the barriers in front of the zeroing), so that the step launch that counts into it next
+// -- a later kernel on the same stream -- finds it clean.  One thread per bin; a position finds its (bin, sub-list) by binary search over the 1024 running ends.
+struct FrameOrderTicksArgs {
+    int32_t k, frames;
+    int32_t *hist[MAX_STEP_TICKS];         // tick t's histogram [256][LPT_SUBS]
+    const int32_t *list[MAX_STEP_TICKS];   // ... its lists [256][LPT_SUBS][lpt_sub_capacity(frames)]
+    int32_t *order[MAX_STEP_TICKS];        // ... its table [frames]
+};
+
+__global__ __launch_bounds__(LPT_BUCKETS) void frame_order_ticks_kernel(FrameOrderTicksArgs a)
+{
+    static_assert(LPT_SUBS == 4 && LPT_BUCKETS == 256, "one thread per bin, its counters as one int4");
+    constexpr int ENDS = LPT_BUCKETS * LPT_SUBS;
+    __shared__ int s_end[ENDS], s_wsum[LPT_BUCKETS / 64];
+    const int t = (int)blockIdx.x;
+    if (t >= a.k) return;
+    int32_t *hist = a.hist[t];
+    const int32_t *list = a.list[t];
+    int32_t *order = a.order[t];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int4 c0 = *reinterpret_cast<const int4 *>(hist + (LPT_BUCKETS - 1 - tid) * LPT_SUBS);   // thread tid: bin 255 - tid
+    const int h = (c0.x + c0.y) + (c0.z + c0.w);
+    int x = h;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) s_wsum[wave] = x;
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += s_wsum[w];
+    const int start = base + x - h;
+    s_end[4 * tid] = start + c0.x;
+    s_end[4 * tid + 1] = start + c0.x + c0.y;
+    s_end[4 * tid + 2] = start + c0.x + c0.y + c0.z;
+    s_end[4 * tid + 3] = start + h;
+    __syncthreads();
+    const int total = min(s_end[ENDS - 1], a.frames), cap = lpt_sub_capacity(a.frames);
+    for (int pos = tid; pos < total; pos += LPT_BUCKETS) {
+        int lo = 0, hi = ENDS - 1;   // the first entry whose running end lies beyond pos (there is one: pos < total)
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (s_end[mid] > pos) hi = mid; else lo = mid + 1;
+        }
+        const int off = pos - (lo ? s_end[lo - 1] : 0), bin = LPT_BUCKETS - 1 - (lo >> 2), sub = lo & 3;
+        order[pos] = off < cap ? list[(size_t)(bin * LPT_SUBS + sub) * cap + off] : 0;
+    }
+    for (int pos = total + tid; pos < a.frames; pos += LPT_BUCKETS) order[pos] = 0;   // (never: every frame of a tick is in a list)
+    for (int i = tid; i < ENDS; i += LPT_BUCKETS) hist[i] = 0;
+}
+
+void launch_frame_order_ticks(GymView *views, int k, hipStream_t stream, hipEvent_t done)
+{
+    FrameOrderTicksArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.k = k; a.frames = views[0].num_envs * views[0].num_agents;
+    for (int j = 0; j < k; ++j) {
+        a.hist[j] = views[j].lpt_hist + (size_t)views[j].lpt_parity * (LPT_BUCKETS * LPT_SUBS);
+        a.list[j] = views[j].lpt_list;
+        a.order[j] = views[j].lpt_forder;
+        views[j].lpt_forder_on = 1;
+    }
+    if (done) hipExtLaunchKernelGGL(frame_order_ticks_kernel, dim3(k), dim3(LPT_BUCKETS), 0, stream, nullptr, done, 0, a);
+    else hipLaunchKernelGGL(frame_order_ticks_kernel, dim3(k), dim3(LPT_BUCKETS), 0, stream, a);
+}
+
 namespace {
 
 // Where the short-list pass's pixels go: the frame as a BUFFER (four scalar registers: base, size), a pixel's place in it a 32-bit byte offset -- one
@@ -296,14 +366,21 @@ namespace {
 // check.)
 // CHW (mv_set_obs_layout: MV_OBS_RGB_PLANAR): the frame is three planes of W x H bytes, R, G, B -- `W4` is then a plane row's bytes (W) and `plane` a
 // plane's (W x H).  Everything that knows the layout is here and in clear_tile (frame_out, put_px); the tile code hands pixels over.
-template <bool CHW>
+// WHOLE: "the frame is whole tiles" as a property of the TYPE -- the launcher picks the kernel variant (whole_tiles) -- so that the whole-tile code holds
+// no clamp of a pixel's column or row, no compare with W or H and no store under a saved exec mask at all; `edgeless` is the same fact at run time, for the
+// variants that serve every size.
+template <bool CHW, bool WHOLE = false>
 struct PixOutT {
+    static constexpr bool whole = WHOLE;
     __amdgpu_buffer_rsrc_t rsrc;
     int W, H, W4;
     bool edgeless;
     int plane;
 };
 typedef PixOutT<false> PixOut;
+// a pixel's column / row as an index into the ray tables: clamped to the frame where a tile may hang over its edge
+template <class PO> __device__ __forceinline__ int col_in(const PO &po, int px) { return PO::whole ? px : min(px, po.W - 1); }
+template <class PO> __device__ __forceinline__ int row_in(const PO &po, int py) { return PO::whole ? py : min(py, po.H - 1); }
 #ifndef MV_PIXEL_PLAIN
 constexpr int PIXEL_AUX = 2;   // nt
 #else
@@ -330,10 +407,11 @@ __device__ __forceinline__ PixOutT<CHW> frame_out(uint32_t *obs, int frame, int 
     return po;
 }
 
-__device__ __forceinline__ void put_px(const PixOut &po, int px, int py, unsigned rgba)
+template <bool WHOLE>
+__device__ __forceinline__ void put_px(const PixOutT<false, WHOLE> &po, int px, int py, unsigned rgba)
 {
     const unsigned off = (unsigned)(__mul24(py, po.W4) + px * 4);
-    if (__builtin_expect(po.edgeless, 1)) __builtin_amdgcn_raw_buffer_store_b32(rgba, po.rsrc, off, 0, PIXEL_AUX);
+    if (WHOLE || __builtin_expect(po.edgeless, 1)) __builtin_amdgcn_raw_buffer_store_b32(rgba, po.rsrc, off, 0, PIXEL_AUX);
     else {
         asm volatile("" ::: "memory");   // (keeps the two stores apart: merged, the compares run for every pixel and their result is or-ed with `edgeless`)
         if (px < po.W && py < po.H) __builtin_amdgcn_raw_buffer_store_b32(rgba, po.rsrc, off, 0, PIXEL_AUX);
@@ -682,6 +760,15 @@ struct FastArgs {   // what raster_fast_kernel needs of the GymView (fewer live 
     // 1: tiles that one face of one world box covers take the planar path (planar_tile / overlay_tile); 0: every tile takes the general one (MV_PLANAR=0,
     // comparisons); 2: no overlay_tile
     int planar;
+    // Functions of the observation size alone, from the host (mv_raster.h: RasterConsts -- the expressions the kernels used to evaluate per workgroup, the
+    // same bits): the pixel -> ray abscissa maps of classify_tiles, the reciprocal of tile / tilesX; and the abscissae themselves, dcx[W] then dcy[H] in device
+    // memory (GymView::ray_tab; null: the prologue computes them, as it always did)
+    float sx, ox, sy, oy;
+    unsigned tilesXinv;
+    const float *ray_tab;
+    // this tick's frames in cost order, written once by frame_order_ticks_kernel (GymView::lpt_forder): the prologue reads order[position] -- no histogram
+    // read, no prefix sum, no hist_done count, no zeroing (the order kernel zeroed the histogram).  null: every workgroup walks the histogram, as always.
+    const int *order;
 };
 
 // true_objective is only ever recorded by a finishing env (vector_env.cpp:96-101): the others keep the value of their last episode
@@ -695,6 +782,9 @@ __device__ __forceinline__ void fast_publish(const FastArgs &fa, int blk)
     if (fa.stage_done[e]) fa.pub_true[i] = fa.stage_true[i];
     if (i < fa.pub_n / fa.num_agents) fa.pub_done[i] = fa.stage_done[i];
 }
+
+// n / d by d's reciprocal from the host (mv_raster.h: raster_div_magic; 0: d = 1, uniform)
+__device__ __forceinline__ unsigned div_magic(unsigned n, unsigned m) { return m ? __umulhi(n, m) : n; }
 
 // a wave-uniform 64-bit value that came through LDS, back into SGPRs (so that loops over its bits are scalar loops)
 __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v)
@@ -918,7 +1008,9 @@ __device__ __forceinline__ FastFrame fast_prologue(const FastArgs &fa, int blk, 
             if (b < split * head) frames = head;
             else { b -= split * head; first = head; split = fa.tail_split; frames = q; }
         }
-        const int per = 8 * split, group = b / per, r = b - group * per;   // b: this workgroup's index within its segment of its gym's part of the grid
+        // b: this workgroup's index within its segment of its gym's part of the grid.  (split is a power of two -- fast_split, TAIL_SPLIT; the launchers check
+        // it, pow2_split -- so b / per is a shift)
+        const int per = 8 * split, group = b >> (__ffs(per) - 1), r = b - group * per;
         position = group * 8 + (r & 7); part = r >> 3;
         if (group * 8 + 8 > frames) { const int nf = frames - group * 8; position = group * 8 + r % nf; part = r / nf; }
         position += first;
@@ -926,6 +1018,11 @@ __device__ __forceinline__ FastFrame fast_prologue(const FastArgs &fa, int blk, 
     // position -> frame, most expensive frames first: the frame setup left every frame in the list of its cost bin; prefix-sum the 256 bin
     // counts (bin 255 first) and take entry (position - start) of the bin whose range holds `position`
     __shared__ int s_wsum[4], s_frame, s_lastWG;
+    int frame;
+    if (fa.order) {   // (uniform) the tick's frame-order table: one load from a uniform address, nothing to publish, no barrier
+        frame = __builtin_amdgcn_readfirstlane(fa.order[position]);
+        if (tid == 0) s_lastWG = 0;   // (read behind the prologue's barrier)
+    } else {
     {
         static_assert(LPT_SUBS == 4, "the bin's counters are read as one int4");
         // (one thread per cost bin; a 512-thread workgroup's other waves only keep the barriers company)
@@ -964,8 +1061,9 @@ __device__ __forceinline__ FastFrame fast_prologue(const FastArgs &fa, int blk, 
 #else
     if (tid == 0) s_lastWG = fa.hist_done != nullptr && __hip_atomic_fetch_add(fa.hist_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == fa.wg_total - 1;
 #endif
-    const int frame = __builtin_amdgcn_readfirstlane(s_frame);
-    const int viewer = frame % A;
+    frame = __builtin_amdgcn_readfirstlane(s_frame);
+    }
+    const int viewer = A == 1 ? 0 : frame % A;
     const float *gh = reinterpret_cast<const float *>(fa.vis_hdr + (size_t)frame * FRAME_HDR_BYTES);
     const int nVis = __builtin_amdgcn_readfirstlane(min(__float_as_int(gh[FH_COUNT]), (int)MAXVIS));
 
@@ -983,15 +1081,20 @@ __device__ __forceinline__ FastFrame fast_prologue(const FastArgs &fa, int blk, 
         const short4 *rs = fa.vis_rects + (size_t)frame * fa.vis_stride;
         for (int i = tid; i < nVis; i += NT) s_rect[i] = rs[i];
         const float *c = gh + FH_CAM + FH_CAM_STRIDE * viewer + 3;   // (same arithmetic as the exact kernel: rays are bit-identical)
-        for (int i = tid; i < W; i += NT) {
-            const float dcx = (((float(i) + 0.5f) / float(W)) * 2.0f - 1.0f) * TAN_HALF_FOV;
-            s_col[i] = make_float4(dcx, c[0] * dcx, c[3] * dcx, c[6] * dcx);
-            s_colq[i] = dcx * dcx;
-        }
-        for (int j = tid; j < H; j += NT) {
-            const float dcy = (((float(j) + 0.5f) / float(H)) * 2.0f - 1.0f) * TAN_HALF_FOV_Y;
+        // (the abscissae are functions of the size alone: from the host's table where the launch has one -- the same bits, raster_ray_table -- and only their
+        // products with this frame's camera are formed here)
+        const float *rt = fa.ray_tab;   // (uniform)
+        const auto col = [&](int i, float dcx) { s_col[i] = make_float4(dcx, c[0] * dcx, c[3] * dcx, c[6] * dcx); s_colq[i] = dcx * dcx; };
+        const auto row = [&](int j, float dcy) {
             s_row[j] = make_float4(dcy, c[1] * dcy, c[4] * dcy, c[7] * dcy);
             s_rowq[j] = make_float2(dcy * dcy + 1.0f, 4.0f * dcy - 2.0f);
+        };
+        if (rt) {
+            for (int i = tid; i < W; i += NT) col(i, rt[i]);
+            for (int j = tid; j < H; j += NT) row(j, rt[W + j]);
+        } else {
+            for (int i = tid; i < W; i += NT) col(i, (((float(i) + 0.5f) / float(W)) * 2.0f - 1.0f) * TAN_HALF_FOV);
+            for (int j = tid; j < H; j += NT) row(j, (((float(j) + 0.5f) / float(H)) * 2.0f - 1.0f) * TAN_HALF_FOV_Y);
         }
     }
     __syncthreads();
@@ -1086,8 +1189,8 @@ constexpr int CLS_MAX_TILES = 128;   // tiles of one workgroup that can be class
 // moved into the class word) and its first pixel in s_txy[u] (x | y << 16) -- so that the workgroup draws its tiles most expensive class first from a compact
 // list, and clears the empty ones -- 43 % of a TowerBuilding frame's tiles (r07d census) -- with all its threads at once instead of handing them out one by
 // one.
-template <int TH, int NT>
-__device__ __forceinline__ void classify_tiles(uint4 *s_tile, float4 *s_line, const float4 *s_vis, const short4 *s_rect,
+template <int TH, int NT, bool WHOLE = false>   // WHOLE: the frame is whole tiles (PixOutT)
+__device__ __forceinline__ void classify_tiles(const FastArgs &fa, uint4 *s_tile, float4 *s_line, const float4 *s_vis, const short4 *s_rect,
                                                const float *s_hdr, const float *camv, int nVis, unsigned long long wb0,
                                                int W, int H, int part, int split, int tilesX, int numTiles,
                                                        int perWG, bool overlayOn, int *s_cnt, unsigned *s_txy, bool bulkClear)
@@ -1098,8 +1201,8 @@ __device__ __forceinline__ void classify_tiles(uint4 *s_tile, float4 *s_line, co
     if (tid < CLS_MAX_TILES) s_tile[tid] = make_uint4(0u, 0u, 0u, 0u);
     if (tid < 8) s_cnt[tid] = 0;
     // the ray's world components as affine functions of the pixel: d_a(i, j) = A_a i + B_a j + C_a  (dc = (((i + .5) / W) 2 - 1) TAN, ..., -1)
-    const float sx = 2.0f * TAN_HALF_FOV / float(W), ox = (1.0f / float(W) - 1.0f) * TAN_HALF_FOV;
-    const float sy = 2.0f * TAN_HALF_FOV_Y / float(H), oy = (1.0f / float(H) - 1.0f) * TAN_HALF_FOV_Y;
+    // (sx = 2 TAN / W, ox = (1 / W - 1) TAN, ...: the launch's constants, from the host -- four divisions per workgroup here once)
+    const float sx = fa.sx, ox = fa.ox, sy = fa.sy, oy = fa.oy;
     // this lane as an edge task: lane 16 s + q, q = 4 f + e: face axis k = f, edge axis m one of the two others (e >> 1), hi bound (e & 1)
     const int q = lane & 15, es = lane >> 4;
     const int ek = min(q >> 2, 2);
@@ -1121,9 +1224,9 @@ __device__ __forceinline__ void classify_tiles(uint4 *s_tile, float4 *s_line, co
         const int u = 64 * c + lane;
         const int tile = ((u >> 2) * split + part) * 4 + (u & 3);
         tvalid[c] = u < perWG && tile < numTiles;
-        const int tyi = tile / tilesX, txi = tile - tyi * tilesX;
+        const int tyi = (int)div_magic((unsigned)tile, fa.tilesXinv), txi = tile - tyi * tilesX;   // (tile / tilesX: the tile loop's reciprocal)
         tX0[c] = txi * TILE_W; tY0[c] = tyi * TH;
-        tX1[c] = min(tX0[c] + TILE_W, W) - 1; tY1[c] = min(tY0[c] + TH, H) - 1;
+        tX1[c] = (WHOLE ? tX0[c] + TILE_W : min(tX0[c] + TILE_W, W)) - 1; tY1[c] = (WHOLE ? tY0[c] + TH : min(tY0[c] + TH, H)) - 1;
         mlo[c] = mhi[c] = cover[c] = 0u;
     }
     for (int base = PPR * wave; base < nVis; base += 16) {   // the waves share the list out: PPR positions per wave and round
@@ -1305,7 +1408,6 @@ template <int NP, bool SPEC, class PO>
 __device__ __forceinline__ void planar_run(int pos, int k, int n, const float4 *s_vis, const float *s_hdr, const float4 *s_col, const float4 *s_row,
                                            const float2 *s_rowq, const float *s_colq, float nzk, int tx0, int ty0, int lane, const PO &po)
 {
-    const int W = po.W, H = po.H;
     const float lok = uniform_f32(reinterpret_cast<const float *>(s_vis)[8 * pos + k]),
                                   hik = uniform_f32(reinterpret_cast<const float *>(s_vis)[8 * pos + 4 + k]);
     const float plane = lok > 0.0f ? lok : hik;   // the face towards the eye
@@ -1320,13 +1422,13 @@ __device__ __forceinline__ void planar_run(int pos, int k, int n, const float4 *
     float2 rq[NP];
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-        const int pyc = min(py0 + TILE_H * j, H - 1);
+        const int pyc = row_in(po, py0 + TILE_H * j);
         rowk[j] = reinterpret_cast<const float *>(s_row)[4 * pyc + 1 + k];
         rq[j] = s_rowq[pyc];
     }
 #pragma unroll 1
     for (int q = 0; q < n; ++q) {
-        const int px = tx0 + TILE_W * q + lx, pxc = min(px, W - 1);
+        const int px = tx0 + TILE_W * q + lx, pxc = col_in(po, px);
         const float colk = reinterpret_cast<const float *>(s_col)[4 * pxc + 1 + k];
         const float cq = s_colq[pxc];
 #pragma unroll
@@ -1345,7 +1447,6 @@ template <int NP, bool SPEC, class PO>
 __device__ __forceinline__ void planar_tile(int pos, int k, const float4 *s_vis, const float *s_hdr, const float4 *s_col, const float4 *s_row,
                                             const float2 *s_rowq, const float *s_colq, float nzk, int px, int py0, const PO &po)
 {
-    const int W = po.W, H = po.H;
     const float lok = uniform_f32(reinterpret_cast<const float *>(s_vis)[8 * pos + k]),
                                   hik = uniform_f32(reinterpret_cast<const float *>(s_vis)[8 * pos + 4 + k]);
     const float plane = lok > 0.0f ? lok : hik;   // the face towards the eye
@@ -1353,12 +1454,12 @@ __device__ __forceinline__ void planar_tile(int pos, int k, const float4 *s_vis,
     const float cr = float((color >> 16) & 255u), cg = float((color >> 8) & 255u), cb = float(color & 255u);
     const float lk = uniform_f32(s_hdr[FH_LREL + k]);   // the light along k, relative to the eye (frame 0: world axes)
     const float lks = plane > 0.0f ? lk : 0.0f - lk;    // sgn (Lrel_k - t d_k) = t |d_k| - (d_k < 0 ? -Lrel_k : Lrel_k), and d_k has the plane offset's sign
-    const int pxc = min(px, W - 1);
+    const int pxc = col_in(po, px);
     const float colk = reinterpret_cast<const float *>(s_col)[4 * pxc + 1 + k];
     const float cq = s_colq[pxc];
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-        const int py = py0 + TILE_H * j, pyc = min(py, H - 1);
+        const int py = py0 + TILE_H * j, pyc = row_in(po, py);
         const float rowk = reinterpret_cast<const float *>(s_row)[4 * pyc + 1 + k];
         const float2 rq = s_rowq[pyc];
         const float dk = (colk + rowk) + nzk;                 // the ray's component along k: the same sum the general path forms
@@ -1372,18 +1473,18 @@ __device__ __forceinline__ void planar_tile(int pos, int k, const float4 *s_vis,
 // a tile nothing can be seen through: the clear colour (0, 0, 0), alpha 255 -- 16 pixels of a row are 64 bytes: four lanes per row write 16 bytes each
 // (a quarter of the store instructions of one dword per pixel) where the frame's rows allow it
 typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
-template <int NP>
-__device__ __forceinline__ void clear_tile(const PixOut &po, int tx0, int ty0, int lane)
+template <int NP, bool WHOLE>
+__device__ __forceinline__ void clear_tile(const PixOutT<false, WHOLE> &po, int tx0, int ty0, int lane)
 {
     constexpr int TH = TILE_H * NP;
     // (lane and colour are laundered: what is derived from them is formed here, per tile -- hoisted out of the tile loop it costs the kernel registers it does
     // not have at seven waves per SIMD)
     unsigned c = 0xff000000u;
     asm volatile("" : "+v"(lane), "+v"(c));
-    if ((po.W & 3) == 0 && tx0 + TILE_W <= po.W) {   // (uniform; the frame's base is 16-byte aligned: raster_fast_body checks)
+    if (WHOLE || ((po.W & 3) == 0 && tx0 + TILE_W <= po.W)) {   // (uniform; the frame's base is 16-byte aligned: raster_fast_body checks)
         const int row = ty0 + (lane >> 2), col = tx0 + 4 * (lane & 3);
         const v4u_t v = {c, c, c, c};
-        if (lane < 4 * TH && row < po.H) __builtin_amdgcn_raw_buffer_store_b128(v, po.rsrc, (unsigned)(__mul24(row, po.W4) + col * 4), 0, PIXEL_AUX);
+        if (lane < 4 * TH && (WHOLE || row < po.H)) __builtin_amdgcn_raw_buffer_store_b128(v, po.rsrc, (unsigned)(__mul24(row, po.W4) + col * 4), 0, PIXEL_AUX);
         return;
     }
     const int px = tx0 + (lane & (TILE_W - 1)), py0 = ty0 + lane / TILE_W;
@@ -1423,7 +1524,6 @@ __device__ __forceinline__ void overlay_tile(int posA, int k, unsigned long long
                                              const float4 *s_row, const float2 *s_rowq, const float *s_colq,
                                                      float nzm0, float nzm1, float nzm2, int px, int py0, const PO &po)
 {
-    const int W = po.W, H = po.H;
     const float lok = uniform_f32(reinterpret_cast<const float *>(s_vis)[8 * posA + k]),
                                   hik = uniform_f32(reinterpret_cast<const float *>(s_vis)[8 * posA + 4 + k]);
     const float plane = lok > 0.0f ? lok : hik;
@@ -1431,12 +1531,12 @@ __device__ __forceinline__ void overlay_tile(int posA, int k, unsigned long long
     const float cr = float((color >> 16) & 255u), cg = float((color >> 8) & 255u), cb = float(color & 255u);
     const float lk = uniform_f32(s_hdr[FH_LREL + k]);
     const float lks = plane > 0.0f ? lk : 0.0f - lk;
-    const int pxc = min(px, W - 1);
+    const int pxc = col_in(po, px);
     const float4 cx = s_col[pxc];
     const float cq = s_colq[pxc];
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-        const int py = py0 + TILE_H * j, pyc = min(py, H - 1);
+        const int py = py0 + TILE_H * j, pyc = row_in(po, py);
         const float4 ry = s_row[pyc];
         const float2 rq = s_rowq[pyc];
         const V3 dw = v3((cx.y + ry.y) + nzm0, (cx.z + ry.z) + nzm1, (cx.w + ry.w) + nzm2);
@@ -1474,8 +1574,7 @@ __device__ __forceinline__ void general_tile(unsigned long long mv0, unsigned lo
                                              const float4 *s_row, const float2 *s_rowq, const float *s_colq,
                                                      float nzm0, float nzm1, float nzm2, int px, int py0, const PO &po)
 {
-    const int W = po.W, H = po.H;
-    const int pxc = min(px, W - 1);
+    const int pxc = col_in(po, px);
     const float4 cx = s_col[pxc];
     const float cq = s_colq[pxc];
     const float dcx = cx.x;
@@ -1484,7 +1583,7 @@ __device__ __forceinline__ void general_tile(unsigned long long mv0, unsigned lo
     unsigned best[NP];
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-        const int pyc = min(py0 + TILE_H * j, H - 1);
+        const int pyc = row_in(po, py0 + TILE_H * j);
         const float4 ry = s_row[pyc];
         const float2 rq = s_rowq[pyc];
         dcy[j] = ry.x;
@@ -1609,7 +1708,8 @@ __device__ __forceinline__ void classified_tile(const FastArgs &fa, const int u,
                                        viewer, s_col, s_row, s_rowq, s_colq, nzm0, nzm1, nzm2, px, py0, po);
 }
 
-template <int MAXVIS, bool SHAPES, bool HEXF, int NP, bool CLS = true, int NT = 256, bool CHW = false>   // CLS: with the tile classification; CHW: PixOutT
+// CLS: with the tile classification; CHW, WHOLE: PixOutT (WHOLE: RGBA only -- the planar layout keeps its one variant)
+template <int MAXVIS, bool SHAPES, bool HEXF, int NP, bool CLS = true, int NT = 256, bool CHW = false, bool WHOLE = false>
 __device__ __forceinline__ void raster_fast_body(const FastArgs &fa, uint32_t *obs, int W, int H, int split, int blk, unsigned char *lds)
 {
     constexpr unsigned POS_MASK = MAXVIS - 1;
@@ -1644,12 +1744,13 @@ __device__ __forceinline__ void raster_fast_body(const FastArgs &fa, uint32_t *o
     uint32_t *out = obs + (size_t)frame * W * H;
     const int tilesX = (W + TILE_W - 1) / TILE_W, tilesY = (H + TH - 1) / TH;
     const int numTiles = tilesX * tilesY;
-    PixOutT<CHW> po;
+    static_assert(!(CHW && WHOLE), "the whole-tile variants are RGBA");
+    PixOutT<CHW, WHOLE> po;
     if constexpr (CHW) po = frame_out<true>(obs, frame, W, H, (W % TILE_W) == 0 && (H % TH) == 0);
     else {
         po.rsrc = __builtin_amdgcn_make_buffer_rsrc(out, /*stride*/ 0, W * H * 4, 0x00020000);
         po.W = W; po.H = H; po.W4 = 4 * W;
-        po.edgeless = (W % TILE_W) == 0 && (H % TH) == 0;
+        po.edgeless = WHOLE || ((W % TILE_W) == 0 && (H % TH) == 0);   // (WHOLE: whole_tiles(W, H, NP) held at the launch)
     }
 
     // What the first round of 64 list positions needs is the same for every tile of the frame: this lane's primitive's rectangle and the
@@ -1666,7 +1767,8 @@ __device__ __forceinline__ void raster_fast_body(const FastArgs &fa, uint32_t *o
     static_assert(!PLANAR || (MAXVIS == 256 && CLS_MAX_TILES == 128), "classification tables: 256 edge functions + 128 tiles = 192 records");
     float4 *s_line = s_vis + 2 * 64;
     uint4 *s_tile = reinterpret_cast<uint4 *>(s_vis + 2 * 64 + 256);
-    const int perWG = (numTiles - part * 4 + 4 * split - 1) / (4 * split) * 4;   // this workgroup's tiles, rounded up to four per turn of its waves
+    // this workgroup's tiles, rounded up to four per turn of its waves (/ (4 split): split is a power of two, fast_prologue)
+    const int perWG = ((numTiles - part * 4 + 4 * split - 1) >> (__ffs(4 * split) - 1)) * 4;
     // (uniform over the workgroup; few tiles do not repay the pass over the list)
     const bool cls = PLANAR && fa.planar && nVis <= 64 && perWG <= CLS_MAX_TILES && perWG >= 32;
     __shared__ int s_next;   // the tile loop's hand-out counter (below)
@@ -1680,12 +1782,12 @@ __device__ __forceinline__ void raster_fast_body(const FastArgs &fa, uint32_t *o
 #endif
     constexpr bool LISTED = PLANAR && MV_TILE_LIST != 0;
     // whole tiles, rows of whole 16-byte groups: the empty tiles are cleared by all threads together (below) and stay out of the list
-    const bool bulk = LISTED && po.edgeless && (W & 3) == 0;
-    if (PLANAR && cls && !LISTED) classify_tiles<TH, NT>(s_tile, s_line, s_vis, s_rect, s_hdr, camv, nVis, wb0, W, H,
+    const bool bulk = LISTED && (WHOLE || (po.edgeless && (W & 3) == 0));
+    if (PLANAR && cls && !LISTED) classify_tiles<TH, NT, WHOLE>(fa, s_tile, s_line, s_vis, s_rect, s_hdr, camv, nVis, wb0, W, H,
         part, split, tilesX, numTiles, perWG, fa.planar != 2, s_cnt, s_txy, true);
     else if (PLANAR && cls) {
         // (ends with a barrier)
-        classify_tiles<TH, NT>(s_tile, s_line, s_vis, s_rect, s_hdr, camv, nVis, wb0, W, H, part, split,
+        classify_tiles<TH, NT, WHOLE>(fa, s_tile, s_line, s_vis, s_rect, s_hdr, camv, nVis, wb0, W, H, part, split,
                                tilesX, numTiles, perWG, fa.planar != 2, s_cnt, s_txy, bulk);
         const int c0 = s_cnt[0], c1 = s_cnt[1], c2 = s_cnt[2], c3 = s_cnt[3], nE = s_cnt[4];
         nList = __builtin_amdgcn_readfirstlane(c0 + c1 + c2 + c3 + (bulk ? 0 : nE));
@@ -1745,15 +1847,14 @@ __device__ __forceinline__ void raster_fast_body(const FastArgs &fa, uint32_t *o
             classified_tile<SHAPES, POS_MASK, NP, LISTED>(fa, u, (int)(txy & 0xffffu), (int)(txy >> 16), s_tile, s_vis, s_hdr,
                                                           camv, viewer, s_col, s_row, s_rowq, s_colq, nzm0, nzm1, nzm2, wb0, lane, po);
         }
-    // tile / tilesX == umulhi(tile, ceil(2^32 / tilesX)) while tile * tilesX < 2^32
-    const unsigned tilesXinv = (unsigned)((0x100000000ull + (unsigned)tilesX - 1u) / (unsigned)tilesX);
+    const unsigned tilesXinv = fa.tilesXinv;   // (tile / tilesX == div_magic(tile, the host's reciprocal) while tile * tilesX < 2^32; RasterConsts)
     for (int u = wave; !(LISTED && cls); u = __builtin_amdgcn_readfirstlane(unext)) {
         const int tile = ((u >> 2) * split + part) * 4 + (u & 3);
         if (tile >= numTiles) break;   // (u grows with every request: every later tile of this wave is out of range, too)
         if (lane == 0) unext = atomicAdd(&s_next, 1);
-        const int ty = (int)__umulhi((unsigned)tile, tilesXinv), tx = tile - ty * tilesX;
+        const int ty = (int)div_magic((unsigned)tile, tilesXinv), tx = tile - ty * tilesX;
         const int tx0 = tx * TILE_W, ty0 = ty * TH;
-        const int tx1 = min(tx0 + TILE_W, W) - 1, ty1 = min(ty0 + TH, H) - 1;
+        const int tx1 = (WHOLE ? tx0 + TILE_W : min(tx0 + TILE_W, W)) - 1, ty1 = (WHOLE ? ty0 + TH : min(ty0 + TH, H)) - 1;
         if (PLANAR && !LISTED && cls) {   // (MV_TILE_LIST=0: the classified tiles in frame order)
             classified_tile<SHAPES, POS_MASK, NP, LISTED>(fa, u, tx0, ty0, s_tile, s_vis, s_hdr, camv, viewer,
                                                           s_col, s_row, s_rowq, s_colq, nzm0, nzm1, nzm2, wb0, lane, po);
@@ -1764,7 +1865,7 @@ __device__ __forceinline__ void raster_fast_body(const FastArgs &fa, uint32_t *o
         int lpx = lane;
         asm volatile("" : "+v"(lpx));
         const int px = tx0 + (lpx & (TILE_W - 1)), py0 = ty0 + lpx / TILE_W;
-        const int pxc = min(px, W - 1);
+        const int pxc = col_in(po, px);
         {   // tile culling: one primitive per lane, four integer compares against its screen rectangle
             int l2 = lane;
             asm volatile("" : "+v"(l2));   // (the rectangle's address is formed here, per tile: kept across the loop it was spilled at seven waves per SIMD)
@@ -1811,7 +1912,7 @@ __device__ __forceinline__ void raster_fast_body(const FastArgs &fa, uint32_t *o
                 dcx = cx.x;
 #pragma unroll
                 for (int j = 0; j < NP; ++j) {
-                    const int pyc = min(py0 + TILE_H * j, H - 1);
+                    const int pyc = row_in(po, py0 + TILE_H * j);
                     const float4 ry = s_row[pyc];
                     const float2 rq = s_rowq[pyc];
                     dcy[j] = ry.x;
@@ -2152,11 +2253,11 @@ __global__ __launch_bounds__(256, WAVES) void raster_glist_kernel(FastArgs fa, u
 }
 
 // WAVES: waves per SIMD the variant is compiled for (register budget 512 / WAVES)
-template <int MAXVIS, bool SHAPES, int WAVES, bool HEXF = false, int NP = 1, int NT = 256, bool CHW = false>
+template <int MAXVIS, bool SHAPES, int WAVES, bool HEXF = false, int NP = 1, int NT = 256, bool CHW = false, bool WHOLE = false>
 __global__ __launch_bounds__(NT, WAVES) void raster_fast_kernel(FastArgs fa, uint32_t *obs, int W, int H, int split)
 {
     __shared__ __attribute__((aligned(16))) unsigned char s_buf[fast_lds_bytes(MAXVIS)];
-    raster_fast_body<MAXVIS, SHAPES, HEXF, NP, true, NT, CHW>(fa, obs, W, H, split, (int)blockIdx.x, s_buf);
+    raster_fast_body<MAXVIS, SHAPES, HEXF, NP, true, NT, CHW, WHOLE>(fa, obs, W, H, split, (int)blockIdx.x, s_buf);
 }
 
 // The observation pass of several gyms of one job with one launch (mv_group): workgroup b belongs to gym s with first[s] <= b < first[s + 1]
@@ -2208,10 +2309,13 @@ __device__ __forceinline__ FastArgs ticks_raster_args(const TicksRasterArgs &a, 
     f.vis_prims = reinterpret_cast<const Prim *>(reinterpret_cast<const unsigned char *>(f.vis_prims) + d);
     f.vis_rects = reinterpret_cast<const short4 *>(reinterpret_cast<const unsigned char *>(f.vis_rects) + d);
     f.list = reinterpret_cast<const int *>(reinterpret_cast<const unsigned char *>(f.list) + d);
+    if (f.order) f.order = reinterpret_cast<const int *>(reinterpret_cast<const unsigned char *>(f.order) + d);
     f.stage_rewards = reinterpret_cast<const float *>(reinterpret_cast<const unsigned char *>(f.stage_rewards) + d);
     f.stage_true = reinterpret_cast<const float *>(reinterpret_cast<const unsigned char *>(f.stage_true) + d);
     f.stage_done += d;
-    const int par = (a.parity0 + t) % a.hists;
+    // (the launcher declines a gym without histograms: 1 <= hists, parity0 < hists -- the loop ends)
+    int par = a.parity0 + t;   // (parity0 + t) % hists: t <= MAX_STEP_TICKS, a few scalar subtractions where the division was ~20 instructions
+    while (par >= a.hists) par -= a.hists;
     f.hist = a.hist_base + par * (LPT_BUCKETS * LPT_SUBS);
     f.hist_done = a.done_base ? a.done_base + par : nullptr;
     f.pub_rewards = a.pub_rewards[t];
@@ -2219,7 +2323,7 @@ __device__ __forceinline__ FastArgs ticks_raster_args(const TicksRasterArgs &a, 
     return f;
 }
 
-template <int MAXVIS, bool SHAPES, int WAVES, int NP, int NT = 256, bool CHW = false>
+template <int MAXVIS, bool SHAPES, int WAVES, int NP, int NT = 256, bool CHW = false, bool WHOLE = false>
 __global__ __launch_bounds__(NT, WAVES) void raster_fast_batch_kernel(TicksRasterArgs a, int W, int H, int split)
 {
     int j = 0, r = (int)blockIdx.x;
@@ -2229,7 +2333,7 @@ __global__ __launch_bounds__(NT, WAVES) void raster_fast_batch_kernel(TicksRaste
     __shared__ __attribute__((aligned(16))) unsigned char s_buf[fast_lds_bytes(MAXVIS)];
     FastArgs fa = ticks_raster_args(a, j);
     fa.pub_n = 0;
-    raster_fast_body<MAXVIS, SHAPES, false, NP, true, NT, CHW>(fa, a.obs[j], W, H, split, r, s_buf);
+    raster_fast_body<MAXVIS, SHAPES, false, NP, true, NT, CHW, WHOLE>(fa, a.obs[j], W, H, split, r, s_buf);
 }
 
 // (the long-list variant of raster_fast_batch_kernel: the k passes of one batched call of a Collect / Hex gym)
@@ -2458,7 +2562,24 @@ static void rdbg_dump()
 // last workgroup has looked its frame up (FastArgs::hist_done); `workgroups`: the launch's grid
 static void self_clear(struct FastArgs &fa, const GymView &gv, int workgroups);
 
-static FastArgs fast_args_of(const GymView &gv, const PublishTo *publish)
+RasterConsts raster_launch_consts(int W, int H)
+{
+    RasterConsts c;
+    // (classify_tiles' expressions, as they stood there)
+    c.sx = 2.0f * TAN_HALF_FOV / float(W); c.ox = (1.0f / float(W) - 1.0f) * TAN_HALF_FOV;
+    c.sy = 2.0f * TAN_HALF_FOV_Y / float(H); c.oy = (1.0f / float(H) - 1.0f) * TAN_HALF_FOV_Y;
+    c.tiles_x_inv = raster_div_magic((uint32_t)((W + TILE_W - 1) / TILE_W));
+    return c;
+}
+
+void raster_ray_table(int W, int H, float *out)
+{
+    // (fast_prologue's expressions, as they stand there)
+    for (int i = 0; i < W; ++i) out[i] = (((float(i) + 0.5f) / float(W)) * 2.0f - 1.0f) * TAN_HALF_FOV;
+    for (int j = 0; j < H; ++j) out[W + j] = (((float(j) + 0.5f) / float(H)) * 2.0f - 1.0f) * TAN_HALF_FOV_Y;
+}
+
+static FastArgs fast_args_of(const GymView &gv, const PublishTo *publish, int W, int H)
 {
     const int frames = gv.num_envs * gv.num_agents;
     FastArgs fa;
@@ -2473,6 +2594,10 @@ static FastArgs fast_args_of(const GymView &gv, const PublishTo *publish)
     fa.planar = pe && *pe ? atoi(pe) : 1;   // (2: classified, but without overlay_tile; 3: without the sign-specialised slab tests -- comparisons)
     fa.tail_div = 0; fa.tail_split = 0;
     fa.hist_done = nullptr; fa.wg_total = 0;
+    const RasterConsts rc = raster_launch_consts(W, H);
+    fa.sx = rc.sx; fa.ox = rc.ox; fa.sy = rc.sy; fa.oy = rc.oy; fa.tilesXinv = rc.tiles_x_inv;
+    fa.ray_tab = gv.ray_tab && gv.ray_w == W && gv.ray_h == H ? gv.ray_tab : nullptr;
+    fa.order = gv.lpt_forder_on ? gv.lpt_forder : nullptr;   // (the call's step launches were followed by launch_frame_order_ticks)
 #ifdef MV_RASTER_TIMING
     if (!g_rdbg && hipMalloc((void **)&g_rdbg, (size_t)(16384 * 4 * 8 + 64) * 8) == hipSuccess) { (void)hipMemset(g_rdbg,
         0, (size_t)(16384 * 4 * 8 + 64) * 8); atexit(rdbg_dump); }
@@ -2483,7 +2608,7 @@ static FastArgs fast_args_of(const GymView &gv, const PublishTo *publish)
 
 static void self_clear(FastArgs &fa, const GymView &gv, int workgroups)
 {
-    if (!gv.lpt_no_clear) return;
+    if (!gv.lpt_no_clear || fa.order) return;   // (with the frame-order table nobody reads the histogram here, and its kernel zeroed it)
     fa.hist_done = gv.lpt_hist + (size_t)gv.lpt_hists * (LPT_BUCKETS * LPT_SUBS) + gv.lpt_parity;   // (the counters lie behind the histograms)
     fa.wg_total = workgroups;
 }
@@ -2496,6 +2621,12 @@ static void self_clear(FastArgs &fa, const GymView &gv, int workgroups)
 // (In the one-launch passes of a batched call -- `batch` -- the long lists take two as well: eight passes' worth of workgroups keep the chip full at the lower
 // occupancy, and half as many tiles pay the per-tile work.  r07g/h, one / two pixels per lane: HexMemory 8.0 / 9.2 M obs/s, HexExplore 8.5 / 10.1, Collect 12.2
 // / 14.1, Collect 128 x 72 15.3 / 16.8; one pass per launch: HexMemory 6.9 / 6.95, Collect 11.2 / 9.3.)
+// fast_split doubles from 1, 2 or 4 and halves: a power of two, which the kernels' b / (8 split) relies on -- checked where a split reaches a launch
+static bool pow2_split(int split) { return split >= 1 && (split & (split - 1)) == 0; }
+
+// whole tiles (16 x 4 np pixels): the size the WHOLE variants of the short-list kernels are for (PixOutT) -- every BASELINE size
+static bool whole_tiles(int W, int H, int np) { return W % TILE_W == 0 && H % (TILE_H * np) == 0; }
+
 static int fast_pixels_per_lane(int W, int H, bool longList = false, bool batch = false)
 {
     const char *e = getenv("MV_FAST_PPL");
@@ -2523,6 +2654,7 @@ static int fast_split(int W, int H, int np, int frames, bool longList = false, b
     int split = lo;
     while (split < hi && split < want) split <<= 1;
     while (split > 1 && ftiles < 4 * split * (longList ? 1 : 2)) split >>= 1;
+    if (!pow2_split(split)) split = 1;   // (never: doubled from 1, 2 or 4, then halved -- the kernels shift by it)
     return split;
 }
 
@@ -2568,7 +2700,7 @@ int launch_raster_union(const GymView *views, uint32_t *const *obs, const Publis
                 if ((views[i].vis_stride > VIS_SMALL) != (large != 0)) continue;
                 a.u.first[a.u.n] = wgs;
                 a.u.obs[a.u.n] = obs[i];
-                a.u.fa[a.u.n] = fast_args_of(views[i], publish ? &publish[i] : nullptr);
+                a.u.fa[a.u.n] = fast_args_of(views[i], publish ? &publish[i] : nullptr, W, H);
                 a.large[a.u.n] = large;
                 wgs += views[i].num_envs * views[i].num_agents * (large ? a.split_large : a.split_small);
                 ++a.u.n;
@@ -2592,7 +2724,7 @@ int launch_raster_union(const GymView *views, uint32_t *const *obs, const Publis
             if (isLarge != (large != 0)) continue;
             ua.first[ua.n] = wgs;
             ua.obs[ua.n] = obs[i];
-            ua.fa[ua.n] = fast_args_of(views[i], publish ? &publish[i] : nullptr);
+            ua.fa[ua.n] = fast_args_of(views[i], publish ? &publish[i] : nullptr, W, H);
             wgs += views[i].num_envs * views[i].num_agents * split;
             ++ua.n;
         }
@@ -2645,7 +2777,7 @@ int launch_raster_union_batch(const GymView *views, uint32_t *const *obs, const 
             const int frames = v0.num_envs * v0.num_agents, split = large ? a.split_large : a.split_small;
             a.first[q] = wgs;
             a.large[q] = large;
-            a.fa[q] = fast_args_of(v0, publish ? &publish[i] : nullptr);
+            a.fa[q] = fast_args_of(v0, publish ? &publish[i] : nullptr, W, H);
             a.fa[q].wg_total = frames * split;
             a.hists[q] = v0.lpt_hists; a.parity0[q] = v0.lpt_parity;
             a.hist_base[q] = v0.lpt_hist;
@@ -2693,8 +2825,10 @@ int launch_raster_batch(const GymView *views, uint32_t *const *obs, const Publis
     a.hists = gv.lpt_hists; a.parity0 = gv.lpt_parity;
     a.slot_stride = slotStride;
     a.hist_base = gv.lpt_hist;
-    a.done_base = gv.lpt_no_clear ? gv.lpt_hist + (size_t)gv.lpt_hists * (LPT_BUCKETS * LPT_SUBS) : nullptr;
-    a.fa = fast_args_of(gv, publish ? &publish[0] : nullptr);
+    if (gv.lpt_hists < 1 || gv.lpt_parity < 0 || gv.lpt_parity >= gv.lpt_hists || !pow2_split(split)) return 1;   // (ticks_raster_args, fast_prologue)
+    a.fa = fast_args_of(gv, publish ? &publish[0] : nullptr, W, H);
+    // (with the frame-order table the passes neither count themselves in nor clear: done_base stays null)
+    a.done_base = gv.lpt_no_clear && !a.fa.order ? gv.lpt_hist + (size_t)gv.lpt_hists * (LPT_BUCKETS * LPT_SUBS) : nullptr;
     a.fa.wg_total = frames * split;
     for (int j = 0; j < k; ++j) {
         a.obs[j] = obs[j];
@@ -2708,6 +2842,10 @@ int launch_raster_batch(const GymView *views, uint32_t *const *obs, const Publis
         if (longList)   // the long-list variants (records through the scalar cache)
             return np == 2 ? (hexScen ? raster_glist_batch_kernel<VIS_XL, true, GLIST_WAVES_NP2, true, 2, C> : raster_glist_batch_kernel<VIS_LARGE, false, GLIST_WAVES_NP2, false, 2, C>)
                            : (hexScen ? raster_glist_batch_kernel<VIS_XL, true, GLIST_WAVES_NP1, true, 1, C> : raster_glist_batch_kernel<VIS_LARGE, false, GLIST_WAVES_NP1, false, 1, C>);
+        if constexpr (!C)
+            if (whole_tiles(W, H, np))   // (RGBA, whole tiles: the variants without edge handling)
+                return np == 2 ? (shapes ? raster_fast_batch_kernel<VIS_SMALL, true, 6, 2, 256, false, true> : raster_fast_batch_kernel<VIS_SMALL, false, 7, 2, 256, false, true>)
+                               : (shapes ? raster_fast_batch_kernel<VIS_SMALL, true, 8, 1, 256, false, true> : raster_fast_batch_kernel<VIS_SMALL, false, 8, 1, 256, false, true>);
         return np == 2 ? (shapes ? raster_fast_batch_kernel<VIS_SMALL, true, 6, 2, 256, C> : raster_fast_batch_kernel<VIS_SMALL, false, 7, 2, 256, C>)
                        : (shapes ? raster_fast_batch_kernel<VIS_SMALL, true, 8, 1, 256, C> : raster_fast_batch_kernel<VIS_SMALL, false, 8, 1, 256, C>);
     });
@@ -2731,13 +2869,17 @@ int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t st
         // variants: <= 256 visible primitives, + scaled shapes (Rearrange, Football), <= 1024 through the scalar cache (Collect), <= 2048 + scaled shapes + wall frames
         // (Hex*); the short-list ones are built for 8 waves per SIMD with one pixel per lane (64 VGPRs), for 7 with two (72; with the scaled shapes: 6, 80)
         using KernelFn = void (*)(FastArgs, uint32_t *, int, int, int);
-        FastArgs fa = fast_args_of(gv, publish);
+        FastArgs fa = fast_args_of(gv, publish, W, H);
         // (Collect, measured and rejected: a 1024-entry launch for the frames above 256 visible primitives + a 256-entry launch for the rest,
         // 75 + 69 us against 107 us for the single 1024-entry launch: each launch pays its own tail, and the cones, not occupancy, dominate)
         const bool hexScen = gv.scenario == SCN_HEX_MEMORY || gv.scenario == SCN_HEX_EXPLORE;
         const bool shapes = gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL, large = gv.vis_stride > VIS_SMALL;
         const KernelFn fn = by_layout(gv.obs_layout, [&](auto chw) -> KernelFn {
             constexpr bool C = decltype(chw)::value;
+            if constexpr (!C)
+                if (!hexScen && !large && whole_tiles(W, H, np))   // (RGBA, short lists, whole tiles: the variants without edge handling)
+                    return np == 2 ? (shapes ? raster_fast_kernel<VIS_SMALL, true, 6, false, 2, 256, false, true> : raster_fast_kernel<VIS_SMALL, false, 7, false, 2, 256, false, true>)
+                                   : (shapes ? raster_fast_kernel<VIS_SMALL, true, 8, false, 1, 256, false, true> : raster_fast_kernel<VIS_SMALL, false, 8, false, 1, 256, false, true>);
             if (np == 2)
                 return hexScen ? raster_glist_kernel<VIS_XL, true, GLIST_WAVES_NP2, true, 2, C> : large ? raster_glist_kernel<VIS_LARGE, false, GLIST_WAVES_NP2, false, 2, C>
                      : shapes ? raster_fast_kernel<VIS_SMALL, true, 6, false, 2, 256, C> : raster_fast_kernel<VIS_SMALL, false, 7, false, 2, 256, C>;
@@ -2754,6 +2896,7 @@ int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t st
         // pieces --, the frame's cost as the last pass's classification found it fed back into the cost bins, wave priorities by remaining work, a whole
         // frame per eight-wave workgroup.)
         constexpr int TAIL_DIV = 8, TAIL_SPLIT = 8;
+        static_assert((TAIL_SPLIT & (TAIL_SPLIT - 1)) == 0, "fast_prologue: b / (8 split) is a shift");
         // (split 2: a launch that fills the chip; 512 frames in four pieces each: 12.0 M obs/s with the tail cut finer, 12.4 without, r05i)
         if (split <= 2 && gv.vis_stride <= VIS_SMALL && ftiles >= 16 * TAIL_SPLIT && tail_frames(frames, TAIL_DIV) > 0) {
             const int q = tail_frames(frames, TAIL_DIV);

@@ -197,6 +197,15 @@ struct GymView {
     // stepping calls only, like step_mask.
     int32_t *budget;
     uint32_t *halted;
+    // The ray abscissae of a ray_w x ray_h observation, dcx[ray_w] then dcy[ray_h] (mv_raster.h: raster_ray_table fills them on the host at mv_create):
+    // functions of the size alone, which the fast pass's prologue loads instead of dividing per workgroup.  null, or another size (hires): it computes them.
+    const float *ray_tab;
+    int32_t ray_w, ray_h;
+    // [N*A] per hand-over slot: this tick's frames in the cost order of the fast pass -- bin 255 first, within a bin sub-list 0..3 in arrival order -- written
+    // once per tick by frame_order_ticks_kernel behind the step launches of a batched call (mv_raster.h: launch_frame_order_ticks), which also zeroes the tick's
+    // histogram; lpt_forder_on = 1 in the views of such a call: its passes read order[position] instead of walking the histogram.  null: MV_FRAME_ORDER=0.
+    int32_t *lpt_forder;
+    int32_t lpt_forder_on;
 };
 
 // The n <= 8 consecutive ticks of a multi-tick step launch (mv_step.hip: step_ticks_kernel, and every mv_step_*.hip), the same envs in all of them: their views
@@ -227,6 +236,7 @@ __host__ __device__ inline GymView tick_view(const GymView &base, int64_t slot_s
     v.lpt_order = (int32_t *)((uint8_t *)base.lpt_order + d);
     v.vis_hdr = base.vis_hdr + d;
     v.lpt_list = (int32_t *)((uint8_t *)base.lpt_list + d);
+    v.lpt_forder = base.lpt_forder ? (int32_t *)((uint8_t *)base.lpt_forder + d) : nullptr;
     v.rewards = (float *)((uint8_t *)base.rewards + d);
     v.done = base.done + d;
     v.true_objective = (float *)((uint8_t *)base.true_objective + d);
@@ -242,7 +252,8 @@ inline bool slot_stride_of(const GymView *views, int k, int64_t &stride)
         const GymView w = tick_view(views[0], stride, j);
         if (views[j].vis_prims != w.vis_prims || views[j].vis_hdr != w.vis_hdr || views[j].lpt_list != w.lpt_list
             || views[j].rewards != w.rewards || views[j].done != w.done ||
-            views[j].true_objective != w.true_objective || views[j].lpt_parity != w.lpt_parity || views[j].lpt_no_clear != w.lpt_no_clear)
+            views[j].true_objective != w.true_objective || views[j].lpt_parity != w.lpt_parity || views[j].lpt_no_clear != w.lpt_no_clear
+            || views[j].lpt_forder != w.lpt_forder || views[j].lpt_forder_on != w.lpt_forder_on)
             return false;
     }
     return true;

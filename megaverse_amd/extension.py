@@ -97,6 +97,7 @@ SYMBOLS = [
     ("mv_episode_budget_device_ptr", _P, [_P]), ("mv_halted_count_device_ptr", _P, [_P]), ("mv_halted_count", C.c_int, [_P, C.POINTER(_I)]),
     ("mv_debug_episode_log_budget_host", C.c_int, [_P, _P, _P, _I, _I, _I, _I, _U, _P, _P, _P, C.POINTER(_U), C.POINTER(_U), _P, _P]),
     ("mv_debug_episode_budget_host", C.c_int, [_P, _P, _P, _I, _I, _P, _P]),
+    ("mv_debug_raster_consts_host", C.c_int, [_I, _I, _P, _P, _P, _P]), ("mv_debug_raster_div_host", C.c_int, [_U, _U, _P, _P]),
 ]
 
 # mv_episode_record (include/megaverse_hip.h): one finished episode of one agent, 24 bytes
