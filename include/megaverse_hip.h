@@ -195,7 +195,7 @@ int mv_reset_envs_host(mv_gym *g, const uint8_t *mask, int32_t render);     /* m
  * Episode log (when on): a frozen tick adds nothing to the env's running returns or length and writes no record; a record written later has length = the
  * ticks the env actually stepped, end_tick in the gym's tick count.
  * Observation: drawn as always where the mode draws at all, from the unchanged state: a frozen env's frame is its current view, byte-identical to its
- * previous one, time bar included.  (The frame setup and the raster of a frozen frame are not skipped.)
+ * previous one, time bar included.  (The frame setup and the raster of a frozen frame are not skipped; mv_set_draw_mask, below, skips both.)
  * Everything else acts regardless of the mask: mv_reset resets every env and leaves the mask attached; mv_reset_envs, mv_fork_envs* and mv_resample_envs*
  * treat frozen envs like any other -- a frozen env as a fork source is a savepoint that keeps.
  * Ordering: the call is an ordering point, as mv_set_action_ring is: whatever the caller enqueued on the gym's stream before it is ordered before the next
@@ -208,6 +208,30 @@ int mv_reset_envs_host(mv_gym *g, const uint8_t *mask, int32_t render);     /* m
 int mv_set_step_mask(mv_gym *g, const uint8_t *device_mask);   /* [N] in device memory; NULL detaches */
 int mv_set_step_mask_host(mv_gym *g, const uint8_t *mask);     /* [N] in host memory; NULL detaches */
 int mv_get_step_mask(const mv_gym *g);                         /* 0: none, 1: device form, 2: host form; -1: no gym */
+/* Draw masks (no reference counterpart: the reference draws every env of every step).  mask: one byte per env, [N]; a torch.bool tensor is such a mask.
+ * mask[e] != 0: env e is drawn as it is without these calls.  mask[e] == 0: env e is UNDRAWN: in every observation pass the gym enqueues while the mask is
+ * attached, none of env e's A frames is set up or drawn, and no byte of their rows is written, in either observation layout (mv_set_obs_layout).  The rows keep
+ * whatever they held: in an output ring the entry of `count` ticks ago, in the slab the last frame drawn there, or the caller's own bytes -- stale rows are
+ * the caller's to tell apart; the gym carries nothing over between hand-over slots or ring entries.
+ * Which passes: mv_step; mv_step_n and mv_step_n_render in every mode and policy (MV_RENDER_LAST draws the masked-in envs of the last tick; MV_RENDER_NONE
+ * draws nothing, as always); the frame behind mv_reset; mv_reset_envs(..., render = 1); mv_render.  mv_draw_hires ignores the mask: it draws every env.
+ * Nothing else changes.  Physics, scenario logic, auto-reset and refill; rewards, dones and true objectives, and where and when they are published (the fast
+ * pass publishes them with its first workgroups, whatever the mask says: also with an all-zero mask); the episode log, the status words and the capacity
+ * flags are the bytes an unmasked twin produces.  An undrawn frame has no list and so raises no ST_VISIBLE.
+ * The mask belongs to the env SLOT, like a budget: mv_fork_envs*, mv_resample_envs*, mv_load_envs*, mv_reset and mv_reset_envs move or replace state and leave
+ * the mask alone.  It composes with step masks and budgets: a frozen and undrawn env costs one mask load in the step launch and workgroups that leave behind
+ * their frame look-up in the pass.  The mask stays attached until it is detached (NULL) or replaced.  With no mask attached (and neither step mask nor budget)
+ * the gym launches the step kernels it launched before; the pass kernels differ by one uniform branch per workgroup.
+ * Scheduling only, not pixels: undrawn frames are the cheapest in the pass's cost order and fill its finely cut tail segment first.
+ * Ordering: mv_set_step_mask's.  Both forms are ordering points: whatever the caller enqueued on the gym's stream before the call is ordered before the next
+ * step launch; neither form waits on the host.  Device form: nothing is copied; the buffer is the caller's and stays unchanged until the caller's stream has
+ * passed the end of the last call that reads it; after rewriting it, call mv_set_draw_mask again.  Host form: the bytes go to a gym-owned device buffer
+ * (allocated at first use, counted in mv_arena_bytes, freed by mv_close) through pinned staging, by a copy ordered behind every step launch enqueued so far.
+ * Valid before the first mv_reset.  Refused (-1 with text): no gym, a closed gym, a gym in an mv_group; mv_group_create and mv_step_many refuse a gym with a
+ * draw mask attached (the union launches read none). */
+int mv_set_draw_mask(mv_gym *g, const uint8_t *device_mask);   /* [N] in device memory, read in place; NULL detaches */
+int mv_set_draw_mask_host(mv_gym *g, const uint8_t *mask);     /* [N] in host memory, copied through a pinned staging buffer; NULL detaches */
+int mv_get_draw_mask(const mv_gym *g);                         /* 0: none, 1: device form, 2: host form; -1: no gym */
 /* Episode budgets (no reference counterpart: VectorEnv::step resets a finished env on the spot and steps on, vector_env.cpp:89-108).  Per env e the gym owns an
  * int32 left[e]:  < 0: unlimited -- what every env is without these calls;  > 0: the env may still finish that many episodes;  0: the env is HALTED.
  * Tick t, env e, left[e] as it stands before the tick (megaverse_amd/csrc/mv_episode_budget.h states the rule for kernels and host alike):

@@ -772,6 +772,7 @@ int mv_close(mv_gym *g)
     for (hipEvent_t &e : g->resetMaskCopied) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     g->dResetMask = g->hResetMask = nullptr;
     step_mask_free(g);
+    draw_mask_free(g);
     episode_budget_free(g);
     if (g->arena) (void)hipFree(g->arena);
     if (g->hiresObs) (void)hipFree(g->hiresObs);
@@ -932,7 +933,9 @@ int mv_render(mv_gym *g)
     if (sim_join(g)) return -1;
     if (take_hist(g, g->stream, true)) return -1;
     g->layoutFixed = true;
-    if (launch_raster(view(g, g->parity), last_outputs(g).obs, g->w, g->h, g->stream, nullptr, g->fastPixels))
+    GymView v = view(g, g->parity);
+    v.draw_mask = g->drawMask;   // (mv_set_draw_mask: also the frame behind mv_reset and mv_reset_envs(render = 1), which come through here)
+    if (launch_raster(v, last_outputs(g).obs, g->w, g->h, g->stream, nullptr, g->fastPixels))
         return fail("mv_render: observation size above 1024x1024");
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1407,7 +1410,7 @@ int mv_draw_hires(mv_gym *g)
     if (sim_join(g)) return -1;
     if (take_hist(g, g->stream, true)) return -1;
     GymView v = view(g, g->parity);
-    v.obs_layout = MV_OBS_RGBA;   // (the hires frames are RGBA in every layout)
+    v.obs_layout = MV_OBS_RGBA;   // (the hires frames are RGBA in every layout; the view carries no draw mask: every env is drawn)
     if (launch_raster(v, g->hiresObs, g->hiresW, g->hiresH, g->stream, nullptr, g->fastPixels)) return fail("mv_draw_hires: render size above 1024x1024");
     HIP_TRY(hipGetLastError());
     return 0;

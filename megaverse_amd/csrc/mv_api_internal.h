@@ -7,6 +7,7 @@
 //   mv_reset_envs.hip masked env resets: the host protocol around the reset_masked kernels (mv_step_kernels.h)
 //   mv_env_store.hip  env stores: the save / load kernels, their entry points and host-only hooks
 //   mv_step_mask.hip  step masks: attaching and detaching the bytes that freeze envs (mv_step_kernels.h: frozen_tick)
+//   mv_draw_mask.hip  draw masks: attaching and detaching the bytes that leave envs' frames out of the observation passes (mv_frame.h: frame_skip)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 // The C ABI itself is include/megaverse_hip.h; nothing here is exported under a C name.
 #pragma once
@@ -244,6 +245,13 @@ struct mv_gym {
     size_t stepMaskBytes = 0;
     struct MaskStaging { uint8_t *host; hipEvent_t copied; };
     std::vector<MaskStaging> stepMaskStaging;
+    // mv_set_draw_mask: the [N] bytes the frame setups read (GymView::draw_mask through the views of the stepping calls and of mv_render), null: no mask.  The
+    // forms, the gym-owned buffer and the staging are the step mask's.
+    const uint8_t *drawMask = nullptr;
+    int drawMaskForm = 0;
+    uint8_t *dDrawMask = nullptr;
+    size_t drawMaskBytes = 0;
+    std::vector<MaskStaging> drawMaskStaging;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
     // budgetLeft [N], what the step kernels read and write (GymView::budget, through the stepping calls' views, while budgetOn); budgetHalted, the count of
     // zeros in it; budgetMirror [N], the episode log's own copy, advanced by the log's update tick by tick.  The host form's values travel through pinned
@@ -291,6 +299,7 @@ int episode_log_update(mv_gym *g, const GymView *views, int stride, int k);
 int episode_log_reset(mv_gym *g);   // mv_reset: accumulators to zero, the records stay
 void episode_log_free(mv_gym *g);   // mv_close
 void step_mask_free(mv_gym *g);     // mv_close (mv_step_mask.hip)
+void draw_mask_free(mv_gym *g);     // mv_close (mv_draw_mask.hip)
 void episode_budget_free(mv_gym *g);   // mv_close (mv_episode_budget.hip)
 int episode_budget_seed_mirror(mv_gym *g);   // mv_set_episode_log: the log's mirror from the live array (mv_episode_budget.hip)
 // mv_fork.hip, shared with mv_env_store.hip: what every fork / resample / env-store form refuses (what: "forks", "env stores": for the text about groups), and

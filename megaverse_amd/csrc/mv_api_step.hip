@@ -162,6 +162,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
             GymView &v = views[(size_t)j * n + i];
             v = view(g, g->parity, staged ? nullptr : &o);
             v.step_mask = g->stepMask;   // (mv_set_step_mask; a group's members have none)
+            v.draw_mask = g->drawMask;   // (mv_set_draw_mask; likewise)
             if (g->budgetOn) { v.budget = g->budgetLeft; v.halted = g->budgetHalted; }   // (mv_set_episode_budget; likewise)
             if (policy == POLICY_SEQUENCE)
                 v.md_actions = g->actRing + (size_t)action_ring_entry(first_index, j, (uint32_t)g->actRingCount) * ((size_t)g->N * g->A * 6);
@@ -496,6 +497,7 @@ int mv_group_create(mv_gym *const *gyms, int32_t n, mv_group **out)
         if (check(g)) return -1;
         if (g->inGroup) return fail("mv_group_create: a gym already belongs to a group");
         if (g->stepMask) return fail("mv_group_create: a gym has a step mask attached (mv_set_step_mask): the union launches read none; detach it first");
+        if (g->drawMask) return fail("mv_group_create: a gym has a draw mask attached (mv_set_draw_mask): the union launches read none; detach it first");
         if (g->budgetOn) return fail("mv_group_create: a gym has an episode budget attached (mv_set_episode_budget): the union launches read none; detach it first");
         for (int j = 0; j < i; ++j) if (gyms[j] == g) return fail("mv_group_create: the same gym twice");
         if (g->scenario == SCN_BOXAGONE)   // (its tick is not in the union kernels, mv_step_union.hip: tick_any)
@@ -607,7 +609,7 @@ int mv_recommended_pass_overlap(const mv_gym *g)
     return 1;
 }
 
-int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMaskBytes + g->budgetBytes) : 0; }
+int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMaskBytes + g->drawMaskBytes + g->budgetBytes) : 0; }
 
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index)
 {   // several gyms of one job (MultiTaskGym: one per scenario, one stream each) stepped by one call: at eight sub-gyms the per-call cost of
@@ -619,6 +621,9 @@ int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample,
     for (int i = 0; i < n; ++i)   // (refused before any gym is stepped: the sub-gyms never get out of step with each other)
         if (gyms[i] && !gyms[i]->closed && gyms[i]->stepMask)
             return fail("mv_step_many: gym " + std::to_string(i) + " has a step mask attached (mv_set_step_mask): step it on its own, or detach the mask first");
+    for (int i = 0; i < n; ++i)
+        if (gyms[i] && !gyms[i]->closed && gyms[i]->drawMask)
+            return fail("mv_step_many: gym " + std::to_string(i) + " has a draw mask attached (mv_set_draw_mask): step it on its own, or detach the mask first");
     for (int i = 0; i < n; ++i)
         if (gyms[i] && !gyms[i]->closed && gyms[i]->budgetOn)
             return fail("mv_step_many: gym " + std::to_string(i) + " has an episode budget attached (mv_set_episode_budget): step it on its own, or detach the budget first");

@@ -596,5 +596,36 @@ __device__ __forceinline__ void frame_setup_body(const GymView &gv, const int fr
     sync();   // the LDS scratch above is reused by the next frame of this workgroup (fused step + setup kernels)
 }
 
+// ---- mv_set_draw_mask: the frame setup of a frame nobody draws, in frame_setup_body's place (same THREADS / WAVE_LOCAL / PIPE, called by the same threads).
+// It keeps the pass's bookkeeping whole and touches nothing else -- no camera, no list, no rectangle, no depth sort, no ST_VISIBLE:
+//   * the frame is marked undrawn where each pass kernel reads its list length: vis_count[frame] (the exact kernel) and the header's FH_COUNT (the fast ones).
+//     FRAME_UNDRAWN is negative and survives the min(count, MAXVIS) of both prologues, whose copies then run zero times; the workgroups of such a frame
+//     return behind their frame look-up, before they write a pixel (mv_raster.hip);
+//   * the frame files itself in cost bin 0 -- lpt_bucket, the returning atomic on lpt_hist, its lpt_list entry -- as the cheapest frame there is: every pass
+//     kernel, frame_order_kernel and frame_order_ticks_kernel still see a permutation of ALL frames (a bin's sub-list holds at most the frames of its residue
+//     class mod LPT_SUBS: lpt_sub_capacity);
+//   * frame 0 keeps its duty of clearing the next pass's histogram;
+//   * the barriers of the path it replaces that somebody ELSE waits at: PIPE's B(j) (the tick wave's), and the closing sync().
+constexpr int FRAME_UNDRAWN = -1;
+template <int THREADS, bool WAVE_LOCAL, bool PIPE = false>
+__device__ __forceinline__ void frame_skip(const GymView &gv, const int frame)
+{
+    static_assert(!WAVE_LOCAL || THREADS == 64, "a wave-local frame setup is one wavefront");
+    auto sync = [] { if (WAVE_LOCAL) wave_sync(); else __syncthreads(); };
+    const int tid = WAVE_LOCAL ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
+    if (PIPE) __syncthreads();   // B(j): nothing of the state is read here, the tick wave may write the next tick's
+    if (tid == 0) {
+        const int sub = frame & (LPT_SUBS - 1);
+        gv.vis_count[frame] = FRAME_UNDRAWN;
+        gv.lpt_bucket[frame] = 0;
+        const int binPlace = atomicAdd(&gv.lpt_hist[(gv.lpt_parity * LPT_BUCKETS + 0) * LPT_SUBS + sub], 1);
+        reinterpret_cast<float *>(gv.vis_hdr + (size_t)frame * FRAME_HDR_BYTES)[FH_COUNT] = __int_as_float(FRAME_UNDRAWN);
+        gv.lpt_list[(size_t)sub * lpt_sub_capacity(gv.num_envs * gv.num_agents) + binPlace] = frame;
+    }
+    if (frame == 0 && !gv.lpt_no_clear)
+        for (int i = tid; i < LPT_BUCKETS * LPT_SUBS; i += THREADS) gv.lpt_hist[((gv.lpt_parity + 1) % gv.lpt_hists) * (LPT_BUCKETS * LPT_SUBS) + i] = 0;
+    sync();
+}
+
 }  // namespace
 }  // namespace mv

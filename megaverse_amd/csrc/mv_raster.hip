@@ -248,10 +248,18 @@ __device__ __forceinline__ V3 safe_inv(V3 d)
 
 
 // ---- pass 1 as a kernel of its own (mv_reset, mv_render, hires): one workgroup per frame (mv_frame.h)
+// MASKED (mv_set_draw_mask): the instantiation the launcher picks for a view with a draw mask -- the env's byte, loaded once and uniform over the workgroup; an
+// undrawn env's frames take the short path (mv_frame.h: frame_skip).  A view without one launches the kernel it always launched.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void frame_setup_kernel(GymView gv, int W, int H)
 {
     __shared__ FrameScratch s_fs;
     __shared__ DepthSortScratch s_ds;
+    if constexpr (MASKED)
+        if (__builtin_amdgcn_readfirstlane((int)gv.draw_mask[(int)blockIdx.x / gv.num_agents]) == 0) {
+            frame_skip<256, false>(gv, blockIdx.x);
+            return;
+        }
     frame_setup_body<256, false>(gv, blockIdx.x, W, H, s_fs, &s_ds);
 }
 
@@ -514,6 +522,7 @@ __global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : M
 
     // ---- this frame's visible list (frame_setup_kernel) and the colour tables
     const int nVis = min(gv.vis_count[frame], (int)MAXVIS);
+    if (__builtin_amdgcn_readfirstlane(nVis) < 0) return;   // (mv_set_draw_mask) an undrawn frame, mv_frame.h: frame_skip -- uniform over the workgroup; no pixel is written
     {
         const uint4 *src = reinterpret_cast<const uint4 *>(reinterpret_cast<const Prim *>(gv.vis_prims) + (size_t)frame * gv.vis_stride);
         uint4 *dst = reinterpret_cast<uint4 *>(s_vis);
@@ -1736,6 +1745,9 @@ __device__ __forceinline__ void raster_fast_body(const FastArgs &fa, uint32_t *o
     fast_publish(fa, blk);
     const FastFrame ff = fast_prologue<MAXVIS, false, NT>(fa, blk, W, H, split, s_vis, s_rect, s_hdr, s_col, s_row, s_rowq, s_colq);
     RT_MARK(1);
+    // (mv_set_draw_mask) an undrawn frame, as its header says (mv_frame.h: frame_skip): the workgroup has published, looked its frame up, counted itself in
+    // and -- the pass's last -- zeroed the histogram; it leaves before it writes a pixel.  nVis is a uniform scalar: every wave takes the same side.
+    if (ff.nVis < 0) return;
     const int frame = ff.frame, part = ff.part, viewer = ff.viewer, nVis = ff.nVis;
     split = ff.split;   // (fine-grained tail: this workgroup's frame may be cut into more pieces than the launch's nominal number)
 
@@ -2073,7 +2085,10 @@ __device__ __forceinline__ void raster_glist_body(const FastArgs &fa, uint32_t *
     const float nzm0 = uniform_f32(-camv[3 + 2]), nzm1 = uniform_f32(-camv[3 + 5]), nzm2 = uniform_f32(-camv[3 + 8]);
     uint32_t *out = obs + (size_t)frame * W * H;
     const int tilesX = (W + GT_W - 1) / GT_W, tilesY = (H + TH - 1) / TH;
-    const int numTiles = tilesX * tilesY;
+    // (mv_set_draw_mask) an undrawn frame, as its header says (mv_frame.h: frame_skip), has no tiles: the workgroup has published, looked its frame up, counted
+    // itself in and -- the pass's last -- zeroed the histogram; its waves leave the tile loop at its first test, before they write a pixel.  (nVis is a
+    // uniform scalar and this a scalar select; an early return here cost the two-pixel variants a wave per SIMD.)
+    const int numTiles = nVis < 0 ? 0 : tilesX * tilesY;
     const int lx = lane & (GT_W - 1), ly = lane / GT_W;
     PixOutT<true> pc;   // (CHW: the frame's planes as a buffer; the RGBA stores below are the global stores they were)
     if constexpr (CHW) pc = frame_out<true>(obs, frame, W, H, false);
@@ -2859,7 +2874,7 @@ int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t st
     if (W > MAX_W || H > MAX_H) return -1;
     const int tiles = ((W + TILE_W - 1) / TILE_W) * ((H + TILE_H * PPL - 1) / (TILE_H * PPL));
     const int frames = gv.num_envs * gv.num_agents;
-    if (!setup_done) hipLaunchKernelGGL(frame_setup_kernel, dim3(frames), dim3(256), 0, stream, gv, W, H);
+    if (!setup_done) hipLaunchKernelGGL(gv.draw_mask ? frame_setup_kernel<true> : frame_setup_kernel<false>, dim3(frames), dim3(256), 0, stream, gv, W, H);
     if (!fast) hipLaunchKernelGGL(frame_order_kernel, dim3(1), dim3(1024), 0, stream, gv, frames, gv.lpt_order);   // (fast: no sort kernel)
     if (between) (void)hipEventRecord(between, stream);
     if (fast) {

@@ -5,7 +5,7 @@
 //   S::long_lists                          frame lists long enough for the depth sort (mv_frame.h: DepthSortScratch)
 //   S::par_agents                          several agents: every wave of the workgroup takes part in the tick (TowerBuilding)
 // No tick knows about step masks (mv_set_step_mask) or episode budgets (mv_set_episode_budget): the MASKED instantiations of the bodies choose between
-// S::tick and frozen_tick, below.
+// S::tick and frozen_tick, below.  They also choose between frame_setup_body and frame_skip (mv_frame.h) for the envs a draw mask (mv_set_draw_mask) leaves out.
 // Every __global__ is a one-line entry point over a body in its scenario's mv_step_<scenario>.hip (a launch bound that depends on a template
 // parameter is not applied, and the profiles name the kernels); StepKernels lists them for the launchers (mv_step.hip).
 #pragma once
@@ -92,6 +92,28 @@ __device__ __forceinline__ void budget_after_tick(const GymView &gv, int env, in
     }
 }
 
+// ---- mv_set_draw_mask: undrawn envs.  Whether env's A frames are set up in this launch: its mask byte, loaded once per launch and made uniform, as
+// env_frozen's -- the env is the workgroup, so every wave takes the same side and every barrier stays workgroup-uniform; every view of a multi-tick launch
+// carries the same mask, so the byte is asked through the first view.  Only the MASKED instantiations ask (the launchers pick them for a view with a step
+// mask, a budget or a draw mask): an undrawn env's frames take frame_skip (mv_frame.h) between the barriers frame_setup_body would have met.  Nothing of the
+// tick depends on it: rewards, dones, state, status words and the episode log are those of a drawn env.
+__device__ __forceinline__ bool env_drawn(const GymView &gv, int env)
+{
+    return gv.draw_mask == nullptr || __builtin_amdgcn_readfirstlane((int)gv.draw_mask[env]) != 0;
+}
+
+// every frame of an undrawn env, in the shape the body's frame setups have: ONE = true: the workgroup (THREADS threads; WAVE_LOCAL: its one wave) shares the
+// env's one frame; false: every wave takes its share of the env's A frames
+template <bool ONE, int THREADS, bool WAVE_LOCAL>
+__device__ __forceinline__ void env_frames_skip(const GymView &gv, int env)
+{
+    if constexpr (ONE) frame_skip<THREADS, WAVE_LOCAL>(gv, env);
+    else {
+        const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+        for (int a = wave; a < A; a += nw) frame_skip<64, true>(gv, env * A + a);
+    }
+}
+
 // One workgroup per env: wave 0 runs the tick (one wave per env: physics, scenario logic, auto-reset), the others wait at the barrier (S::par_agents:
 // they take their share of the character controllers first); then the workgroup builds the lists of the env's frames (mv_frame.h).  `render` = 0:
 // mv_step_no_render.
@@ -113,6 +135,7 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
         frozen_tick(gv, env);
         if (!render) return;
         __syncthreads();
+        if (!env_drawn(gv, env)) { env_frames_skip<A_MAX == 1, STEP_THREADS, false>(gv, env); return; }   // (mv_set_draw_mask; uniform)
         if constexpr (A_MAX == 1) frame_setup_body<STEP_THREADS, false>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
         else {
             const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
@@ -143,6 +166,7 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
     if (!render) return;
     __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
     MV_T(6);           // the whole tick as wave 0 saw it (incl. the generator of a finished env), up to the barrier
+    if constexpr (MASKED) if (!env_drawn(gv, env)) { env_frames_skip<A_MAX == 1, STEP_THREADS, false>(gv, env); return; }   // (mv_set_draw_mask; uniform)
     if constexpr (A_MAX == 1) {
         frame_setup_body<STEP_THREADS, false>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
         MV_T(7);   // frame setup
@@ -184,6 +208,8 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
 #endif
     [[maybe_unused]] int32_t left = -1;   // (mv_set_step_mask, mv_set_episode_budget: env_left)
     if constexpr (MASKED) left = env_left(a.view(0), env);
+    [[maybe_unused]] bool drawn = true;   // (mv_set_draw_mask: env_drawn)
+    if constexpr (MASKED) drawn = env_drawn(a.view(0), env);
     for (int j = 0; j < a.n; ++j) {
         const GymView &gv = a.view(j);
         const bool steps = !MASKED || left != 0;   // (uniform; without MASKED: a constant)
@@ -192,14 +218,17 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
             else frozen_tick(gv, env);
             wave_sync();   // the tick's stores before the frame setup's loads (one wave: no barrier needed)
             if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
-            frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
+            if (!MASKED || drawn) frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
+            else env_frames_skip<true, 64, true>(gv, env);
         } else {
             if (steps) S::template tick<A_MAX, true>(gv, env);
             else frozen_tick(gv, env);
             __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
             if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
-            const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
-            for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
+            if (!MASKED || drawn) {
+                const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+                for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
+            } else env_frames_skip<false, 64, true>(gv, env);
             __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
         }
     }
@@ -241,6 +270,8 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
         constexpr int NS = A_MAX == 1 ? 1 : 4;
         __shared__ FrameScratch s_fs[NS];
         const uint32_t mask = (uint32_t)a.pad;
+        [[maybe_unused]] bool drawn = true;   // (mv_set_draw_mask: env_drawn)
+        if constexpr (MASKED) drawn = env_drawn(a.view(0), env);
         for (int j = 0; j < a.n; ++j) {
             const GymView &gv = a.view(j);
             const bool frames = (mask >> j) & 1u;
@@ -250,15 +281,20 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
                 else frozen_tick(gv, env);
                 wave_sync();   // the tick's stores before the frame setup's / the next tick's loads
                 if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
-                if (frames) frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
+                if (frames) {
+                    if (!MASKED || drawn) frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
+                    else env_frames_skip<true, 64, true>(gv, env);
+                }
             } else {
                 if (steps) S::template tick<A_MAX, true>(gv, env);
                 else frozen_tick(gv, env);
                 __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's / the next tick's loads
                 if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
                 if (frames) {
-                    const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
-                    for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
+                    if (!MASKED || drawn) {
+                        const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+                        for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
+                    } else env_frames_skip<false, 64, true>(gv, env);
                     __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
                 }
             }
@@ -298,9 +334,12 @@ __device__ __forceinline__ void step_ticks_pipe_body(const Args &a, int W, int H
         }
         __syncthreads();                                  // B(n - 1): the last frame setup's
     } else {
+        [[maybe_unused]] bool drawn = true;   // (mv_set_draw_mask: env_drawn; only this wave needs to know)
+        if constexpr (MASKED) drawn = env_drawn(a.view(0), env);
         for (int j = 0; j < a.n; ++j) {
             __syncthreads();                              // A(j)
-            frame_setup_body<64, true, true>(a.view(j), env, W, H, s_fs);   // B(j) inside
+            if (!MASKED || drawn) frame_setup_body<64, true, true>(a.view(j), env, W, H, s_fs);   // B(j) inside
+            else frame_skip<64, true, true>(a.view(j), env);                                      // ... likewise
         }
     }
 }

@@ -206,6 +206,10 @@ struct GymView {
     // histogram; lpt_forder_on = 1 in the views of such a call: its passes read order[position] instead of walking the histogram.  null: MV_FRAME_ORDER=0.
     int32_t *lpt_forder;
     int32_t lpt_forder_on;
+    // mv_set_draw_mask: [N] bytes, 0 = none of the env's A frames is set up or drawn -- the frame setup takes frame_skip (mv_frame.h), the pass's workgroups
+    // leave behind their frame look-up (mv_raster.hip), the env's rows in the observation slab or ring keep what they held; null: no mask, every env is drawn.
+    // Set by the stepping calls and mv_render (mv_api_step.hip, mv_api.hip); the views of mv_draw_hires and of the union launches leave it null.
+    const uint8_t *draw_mask;
 };
 
 // The n <= 8 consecutive ticks of a multi-tick step launch (mv_step.hip: step_ticks_kernel, and every mv_step_*.hip), the same envs in all of them: their views

@@ -98,6 +98,7 @@ SYMBOLS = [
     ("mv_debug_episode_log_budget_host", C.c_int, [_P, _P, _P, _I, _I, _I, _I, _U, _P, _P, _P, C.POINTER(_U), C.POINTER(_U), _P, _P]),
     ("mv_debug_episode_budget_host", C.c_int, [_P, _P, _P, _I, _I, _P, _P]),
     ("mv_debug_raster_consts_host", C.c_int, [_I, _I, _P, _P, _P, _P]), ("mv_debug_raster_div_host", C.c_int, [_U, _U, _P, _P]),
+    ("mv_set_draw_mask", C.c_int, [_P, _P]), ("mv_set_draw_mask_host", C.c_int, [_P, _P]), ("mv_get_draw_mask", C.c_int, [_P]),
 ]
 
 # mv_episode_record (include/megaverse_hip.h): one finished episode of one agent, 24 bytes
@@ -338,6 +339,11 @@ def check_step_mask(mask, num_envs):
     return None if mask is None else _check_env_mask(mask, num_envs, 'set_step_mask', 'the env steps')
 
 
+def check_draw_mask(mask, num_envs):
+    """the argument check of MegaverseGym.set_draw_mask: check_step_mask's rules (non-zero: the env's frames are drawn, 0: they are neither set up nor drawn)"""
+    return None if mask is None else _check_env_mask(mask, num_envs, 'set_draw_mask', 'the env is drawn')
+
+
 def check_episode_budget(budget, num_envs):
     """the argument check of MegaverseGym.set_episode_budget: None (detach) -> None; an int -> that value for every env; a contiguous torch.int32 CUDA tensor
     of shape (num_envs,) (or anything with data_ptr()) -> 'device'; anything else -> a contiguous int32 numpy array, one value per env"""
@@ -466,6 +472,7 @@ class MegaverseGym:
         self._fork_held = None   # fork_envs: the caller's device map, kept until the next step has been enqueued
         self._reset_held = None  # reset_envs: the caller's device mask, likewise
         self._step_mask_held = None  # set_step_mask: the caller's device mask, kept until it is replaced or detached
+        self._draw_mask_held = None  # set_draw_mask: the caller's device mask, kept until it is replaced or detached
         self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
         self._store_held = []    # save_envs / load_envs: the caller's stores and device maps, kept until the next step has been enqueued
 
@@ -706,6 +713,28 @@ class MegaverseGym:
     def step_mask(self):
         """-> 'none' | 'device' | 'host': the form of the step mask attached (set_step_mask)"""
         return self.STEP_MASK_FORMS[self._ck(self._lib.mv_get_step_mask(self._g))]
+
+    def set_draw_mask(self, mask):
+        """Draw masks (include/megaverse_hip.h: mv_set_draw_mask): mask[e] non-zero: env e is drawn as always; 0: none of env e's frames is set up or drawn
+        by any later observation pass -- step, step_n in every render mode, the frame behind reset and reset_envs(render=True), render -- and no byte of
+        their rows in the observation slab or ring is written: the rows keep what they held.  Physics, rewards, dones and the episode log are those of a
+        drawn env.  Until the mask is replaced or detached (None).  A contiguous torch.bool / uint8 CUDA tensor of shape (num_envs,) is read in place (the gym
+        holds a reference; after rewriting it, call this again); a numpy array or a sequence of bools is copied to a buffer of the gym's.  Neither form
+        waits on the host.  draw_hires ignores the mask."""
+        m = check_draw_mask(mask, self.num_envs)
+        if m is None:
+            self._ck(self._lib.mv_set_draw_mask(self._g, None))
+            self._draw_mask_held = None
+        elif isinstance(m, str):
+            self._ck(self._lib.mv_set_draw_mask(self._g, _P(int(mask.data_ptr()))))
+            self._draw_mask_held = mask
+        else:
+            self._ck(self._lib.mv_set_draw_mask_host(self._g, m.ctypes.data))
+            self._draw_mask_held = None
+
+    def draw_mask(self):
+        """-> 'none' | 'device' | 'host': the form of the draw mask attached (set_draw_mask)"""
+        return self.STEP_MASK_FORMS[self._ck(self._lib.mv_get_draw_mask(self._g))]
 
     def set_episode_budget(self, budget):
         """Episode budgets (include/megaverse_hip.h: mv_set_episode_budget): env e may finish budget[e] more episodes (< 0: unlimited) and then HALTS on the

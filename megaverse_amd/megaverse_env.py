@@ -331,6 +331,23 @@ class MegaverseEnv:
             self._frozen[self._env_ids(env_ids, 'thaw')] = False
         self.env.set_step_mask(~self._frozen if self._frozen.any() else None)
 
+    def set_draw_mask(self, mask):
+        """Draw masks (MegaverseGym.set_draw_mask): mask[e] true: env e is drawn as always; false: its frames are neither set up nor drawn and its rows in the
+        observation slab or ring keep what they held -- everything else about its ticks is unchanged -- until the mask is replaced or detached (None).  A bool
+        / uint8 CUDA tensor is read in place (rewrite it, then call this again); a numpy array or a sequence is copied."""
+        self.env.set_draw_mask(mask)
+
+    def draw_only(self, env_ids):
+        """only the envs of env_ids are drawn from the next observation pass on (a host draw mask): the leaves a search feeds to its value net, the few envs
+        whose video is recorded"""
+        m = np.zeros(self.num_envs, np.bool_)
+        m[self._env_ids(env_ids, 'draw_only')] = True
+        self.env.set_draw_mask(m)
+
+    def draw_all(self):
+        """every env is drawn again: the draw mask is detached"""
+        self.env.set_draw_mask(None)
+
     def set_episode_budget(self, budget):
         """Episode budgets (MegaverseGym.set_episode_budget): env e may finish budget[e] more episodes (an int: every env that many; < 0: unlimited) and then
         halts on the device, frozen on the first frame of its next episode -- inside a batched call too; None detaches.  Setting it again replaces every

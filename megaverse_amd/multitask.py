@@ -165,6 +165,13 @@ class MultiTaskGym:
         raise RuntimeError("MultiTaskGym.set_episode_budget: mv_group_create and mv_step_many refuse a gym with an episode budget attached "
                            "(mv_set_episode_budget): the union launches read none; step such a gym on its own")
 
+    def set_draw_mask(self, mask):
+        """draw masks (MegaverseGym.set_draw_mask) are per gym: a group's union launches read none, and the library refuses"""
+        if self._group is not None and mask is not None:
+            self.gyms[0].set_draw_mask(np.ones(self.gyms[0].num_envs, np.bool_))   # (raises, with the library's text)
+        raise RuntimeError("MultiTaskGym.set_draw_mask: mv_group_create and mv_step_many refuse a gym with a draw mask attached "
+                           "(mv_set_draw_mask): the union launches read none; step such a gym on its own")
+
     def recommended_ticks_per_call(self):
         """the k to ask step_n for: what every member recommends (mv_recommended_ticks_per_call), at most 8 -- the two-launch group call's limit"""
         return max(1, min([8] + [g.recommended_ticks_per_call() for g in self.gyms]))
