@@ -232,6 +232,33 @@ int mv_get_step_mask(const mv_gym *g);                         /* 0: none, 1: de
 int mv_set_draw_mask(mv_gym *g, const uint8_t *device_mask);   /* [N] in device memory, read in place; NULL detaches */
 int mv_set_draw_mask_host(mv_gym *g, const uint8_t *mask);     /* [N] in host memory, copied through a pinned staging buffer; NULL detaches */
 int mv_get_draw_mask(const mv_gym *g);                         /* 0: none, 1: device form, 2: host form; -1: no gym */
+/* State observations (no reference counterpart: the reference hands out pixels, rewards and dones).  One row of MV_STATE_OBS_FLOATS = 16 float32 per agent,
+ * agent-major [N*A][16], taken from the env's state AFTER the tick, auto-reset included: a tick that finished an episode shows the first state of the next
+ * episode, as its frame does.  Columns (megaverse_amd/csrc/mv_state_obs.h states them for kernels and host alike):
+ *    0..2  position x, y, z      3..6  yaw basis m00, m02, m20, m22      7  pitch      8, 9  horizontal velocity x, z      10  vertical velocity
+ *    11  1.0f while the agent carries an object, else 0.0f      12, 13  the env's episode time and episode length in seconds      14  the agent's total
+ *    reward of the episode      15  +0.0f (reserved)
+ * Values are copied, not recomputed: every bit is the bit of the simulator's state.
+ * The buffer is one more ring beside mv_set_output_ring's three: [entries][N*A][16], entries = the output ring's count at the moment of the call, or 1 without
+ * a ring; tick t goes to the entry its rewards go to.  While a buffer is attached mv_set_output_ring is refused: detach the state observations first.
+ * Which ticks: every tick of every stepping call -- mv_step, mv_step_no_render, mv_step_n and mv_step_n_render in every mode and policy, MV_RENDER_NONE
+ * included -- whether the env stepped or was frozen (mv_set_step_mask) or halted (mv_set_episode_budget: it reports its unchanged state) and whether it is drawn
+ * (mv_set_draw_mask) or not.  The rows are visible on the gym's stream when the call's rewards and dones are; nothing waits on the host.  mv_reset,
+ * mv_reset_envs(..., render = 1) and mv_render refresh the rows of the last tick's entry from the current state (mv_reset_envs: the flagged envs' rows only;
+ * the others keep theirs).  Forks, resampling and loads move state and touch no output: the next stepping call or mv_render shows it, as for frames.
+ * Nothing else changes: rewards, dones, true objectives, pixels, the episode log and the status words are those of a gym without a buffer.  With a buffer
+ * attached the step launches are the instantiations a step mask selects, and every stepping call enqueues one more small launch on the gym's stream; a gym that
+ * never attaches one launches exactly what it launched before.
+ * Ordering: mv_set_step_mask's.  The call is an ordering point and never waits on the host; the buffer is the caller's and must stay valid until the caller's
+ * stream has passed the end of the last call that writes it.  Attaching again replaces the buffer; NULL detaches.  Valid before the first mv_reset.
+ * Refused (-1 with text): no gym, a closed gym, a gym in an mv_group; mv_group_create and mv_step_many refuse a gym with state observations attached (the
+ * union launches write none).  mv_get_state_observation: the last tick's row of one agent, after waiting for the gym's stream; refused with nothing attached.
+ * mv_debug_state_obs_host: the record on the CPU, from the bytes of one AgentState (128) and one EnvHeader (128) of megaverse_amd/csrc/mv_types.h: no device. */
+enum { MV_STATE_OBS_FLOATS = 16 };
+int mv_set_state_obs(mv_gym *g, float *device_buf);   /* [max(1, ring count)][N*A][16] float32 in device memory; NULL detaches */
+int mv_get_state_obs(const mv_gym *g);                /* 0: none, else the number of entries; -1: no gym */
+int mv_get_state_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, float *out_host16);  /* last tick's row; waits for the gym's stream */
+int mv_debug_state_obs_host(const void *agent_state, const void *env_header, float *out16);      /* the pack function, on the host */
 /* Episode budgets (no reference counterpart: VectorEnv::step resets a finished env on the spot and steps on, vector_env.cpp:89-108).  Per env e the gym owns an
  * int32 left[e]:  < 0: unlimited -- what every env is without these calls;  > 0: the env may still finish that many episodes;  0: the env is HALTED.
  * Tick t, env e, left[e] as it stands before the tick (megaverse_amd/csrc/mv_episode_budget.h states the rule for kernels and host alike):
@@ -353,6 +380,7 @@ int mv_step_n_render(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32
  * and its dones in dones[t % count] ([count][N]); a NULL ring keeps that output where it was.  count = 0 switches back to the single
  * slab / arrays.  Host getters (mv_get_observation, mv_get_last_rewards, ...) read the entry of the last tick. */
 int mv_set_output_ring(mv_gym *g, int32_t count, void *obs, float *rewards, uint8_t *dones);
+int mv_get_output_ring(const mv_gym *g);   /* the ring's count, 0: no ring (what mv_set_state_obs sizes its buffer by); -1: no gym */
 /* Overlapped observation passes (opt-in).  With rings for all three outputs at least TWO calls deep (count >= 2 k, k = the ticks of one mv_step_n call,
  * also where k exceeds the internal batch; otherwise the call runs as without the option) the one-launch observation passes of consecutive
  * mv_step_n calls run on two internal streams in turn: the passes of call c + 1 begin while the last workgroups of call c's drain.  The caller's

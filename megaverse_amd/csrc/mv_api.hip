@@ -773,6 +773,7 @@ int mv_close(mv_gym *g)
     g->dResetMask = g->hResetMask = nullptr;
     step_mask_free(g);
     draw_mask_free(g);
+    state_obs_free(g);
     episode_budget_free(g);
     if (g->arena) (void)hipFree(g->arena);
     if (g->hiresObs) (void)hipFree(g->hiresObs);
@@ -929,6 +930,14 @@ int mv_seed(mv_gym *g, int32_t seed)
 int mv_render(mv_gym *g)
 {
     if (check(g)) return -1;
+    if (render_frames(g)) return -1;
+    return state_obs_refresh(g, nullptr);   // (mv_set_state_obs: the last tick's rows from the current state, as its frames; also behind mv_reset)
+}
+
+}  // extern "C"
+
+int mvapi::render_frames(mv_gym *g)
+{
     HIP_TRY(hipSetDevice(g->device));
     if (sim_join(g)) return -1;
     if (take_hist(g, g->stream, true)) return -1;
@@ -940,8 +949,6 @@ int mv_render(mv_gym *g)
     HIP_TRY(hipGetLastError());
     return 0;
 }
-
-}  // extern "C"
 
 namespace mvapi {
 // ---- status flags ----------------------------------------------------------------------------------------------------
@@ -1270,6 +1277,8 @@ int mv_set_sample_policy(mv_gym *g, int32_t policy)
 int mv_set_output_ring(mv_gym *g, int32_t count, void *obs, float *rewards, uint8_t *dones)
 {
     if (check(g)) return -1;
+    if (g->stateObs)   // (the state buffer is one more ring of the count it was attached under)
+        return fail("mv_set_output_ring: state observations are attached (mv_set_state_obs), sized by the ring count they were attached under: detach the state observations first");
     if (count < 0 || (count > 0 && !obs && !rewards && !dones)) return fail("mv_set_output_ring: count >= 0 and at least one ring required");
     if (count > 0 && obs && g->obsLayout == MV_OBS_RGB_PLANAR && (uintptr_t)obs % planar_alignment(g->w))
         return fail("mv_set_output_ring: a planar ring of this width must be " + std::to_string(planar_alignment(g->w)) + "-byte aligned");
@@ -1279,6 +1288,13 @@ int mv_set_output_ring(mv_gym *g, int32_t count, void *obs, float *rewards, uint
     g->ringObs = count ? (uint8_t *)obs : nullptr; g->ringRewards = count ? rewards : nullptr; g->ringDone = count ? dones : nullptr;
     g->mirrorsFresh = false;
     return 0;
+}
+
+int mv_get_output_ring(const mv_gym *g)
+{
+    if (!g) return fail("mv_get_output_ring: null gym handle");
+    if (g->closed) return fail("mv_get_output_ring: gym is closed");
+    return g->ringCount;
 }
 
 int mv_set_pass_overlap(mv_gym *g, int32_t on)

@@ -8,6 +8,7 @@
 //   mv_env_store.hip  env stores: the save / load kernels, their entry points and host-only hooks
 //   mv_step_mask.hip  step masks: attaching and detaching the bytes that freeze envs (mv_step_kernels.h: frozen_tick)
 //   mv_draw_mask.hip  draw masks: attaching and detaching the bytes that leave envs' frames out of the observation passes (mv_frame.h: frame_skip)
+//   mv_state_obs.hip  state observations: attaching the caller's buffer, the staging rows, their publication and refresh (mv_state_obs.h: the record)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 // The C ABI itself is include/megaverse_hip.h; nothing here is exported under a C name.
 #pragma once
@@ -252,6 +253,11 @@ struct mv_gym {
     uint8_t *dDrawMask = nullptr;
     size_t drawMaskBytes = 0;
     std::vector<MaskStaging> drawMaskStaging;
+    // mv_set_state_obs: the caller's [stateEntries][N*A][16] float32 buffer (null: off; stateEntries: the output ring's count when it was attached, or 1) and
+    // the gym's staging rows [slots][N*A][16], allocated at the first attach and kept until mv_close -- not part of the arena, not counted in mv_arena_bytes.
+    // While attached, gvp[q].state_obs points at slot q's rows: the stepping calls' views carry it to the MASKED step kernels.
+    float *stateObs = nullptr, *stateStage = nullptr;
+    int stateEntries = 0;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
     // budgetLeft [N], what the step kernels read and write (GymView::budget, through the stepping calls' views, while budgetOn); budgetHalted, the count of
     // zeros in it; budgetMirror [N], the episode log's own copy, advanced by the log's update tick by tick.  The host form's values travel through pinned
@@ -301,6 +307,14 @@ void episode_log_free(mv_gym *g);   // mv_close
 void step_mask_free(mv_gym *g);     // mv_close (mv_step_mask.hip)
 void draw_mask_free(mv_gym *g);     // mv_close (mv_draw_mask.hip)
 void episode_budget_free(mv_gym *g);   // mv_close (mv_episode_budget.hip)
+// mv_state_obs.hip: tick `tick`'s entry of the caller's buffer (the entry outputs_of gives its rewards); the staged rows of the k ticks in slots q0 .. q0 + k - 1
+// -> dst[j], one launch on the caller's stream; the last tick's entry gathered from the current state (mask: device bytes [N], only the flagged envs' rows;
+// null: every row; nothing attached: no launch), on the caller's stream behind sim_join
+float *state_obs_entry(const mv_gym *g, unsigned long long tick);
+int state_obs_publish(mv_gym *g, int q0, float *const *dst, int k);
+int state_obs_refresh(mv_gym *g, const uint8_t *device_mask);
+void state_obs_free(mv_gym *g);        // mv_close
+int render_frames(mv_gym *g);          // mv_render without the state rows' refresh (mv_api.hip; mv_reset_envs refreshes the flagged envs' rows only)
 int episode_budget_seed_mirror(mv_gym *g);   // mv_set_episode_log: the log's mirror from the live array (mv_episode_budget.hip)
 // mv_fork.hip, shared with mv_env_store.hip: what every fork / resample / env-store form refuses (what: "forks", "env stores": for the text about groups), and
 // a host map's way to the device through the pinned double buffer

@@ -96,6 +96,8 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     // short runs use short calls instead, bench.py's --batch.)
     std::vector<GymView> views((size_t)n * k);
     std::vector<OutPtrs> outs((size_t)n * k);
+    float *stateDst[PIPE_BATCH_MAX];   // (mv_set_state_obs; one gym: a group's members have none) tick j's entry of the caller's buffer
+    const bool stateOn = n == 1 && L->stateObs != nullptr;
     hipEvent_t *evs[PIPE_BATCH_MAX];
     // ---- the k step kernels, back to back on the simulation stream
     bool simDoneRodeAlong = false;   // (the last step kernel's dispatch packet completes simDone itself)
@@ -158,6 +160,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
             // (this pass's frame setup fills the next cost histogram; one launch per tick: and clears the one after)
             if ((render || (drawLast && j == k - 1)) && take_hist(g, sim, !(multiTick || groupBatch || simTicks))) return -1;
             OutPtrs &o = outs[(size_t)j * n + i];
+            if (stateOn) stateDst[j] = state_obs_entry(g, g->ringTick);   // (the same tick counter: the entry the tick's rewards go to)
             o = outputs_of(g, g->ringTick++);
             GymView &v = views[(size_t)j * n + i];
             v = view(g, g->parity, staged ? nullptr : &o);
@@ -402,7 +405,11 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
         if (gs[i]->logCapacity > 0 && episode_log_update(gs[i], views.data() + i, n, k)) return -1;
         gs[i]->ticksSinceReset += (uint32_t)k;
     }
-    if (anyLog && own) HIP_TRY(hipEventRecord(L->userMark[L->markCount % PIPE_GROUPS], L->stream));
+    // ---- the state observations (mv_set_state_obs): one launch for the call's k ticks, staged rows -> the caller's buffer, in the log's place and for the
+    // log's reason under the same rule: it reads the call's slots, so the mark is recorded again behind it (with overlapped passes the mark was completed on
+    // the pass stream, and the slot group could be reused under the copy).  Every stepping call stages and publishes this way, pipelined or not.
+    if (stateOn && state_obs_publish(L, L->group * L->batch, stateDst, k)) return -1;
+    if ((anyLog || stateOn) && own) HIP_TRY(hipEventRecord(L->userMark[L->markCount % PIPE_GROUPS], L->stream));
     if (own) {
         ++L->markCount;
         for (int i = 0; i < n; ++i) gs[i]->markCount = L->markCount;
@@ -499,6 +506,7 @@ int mv_group_create(mv_gym *const *gyms, int32_t n, mv_group **out)
         if (g->stepMask) return fail("mv_group_create: a gym has a step mask attached (mv_set_step_mask): the union launches read none; detach it first");
         if (g->drawMask) return fail("mv_group_create: a gym has a draw mask attached (mv_set_draw_mask): the union launches read none; detach it first");
         if (g->budgetOn) return fail("mv_group_create: a gym has an episode budget attached (mv_set_episode_budget): the union launches read none; detach it first");
+        if (g->stateObs) return fail("mv_group_create: a gym has state observations attached (mv_set_state_obs): the union launches write none; detach them first");
         for (int j = 0; j < i; ++j) if (gyms[j] == g) return fail("mv_group_create: the same gym twice");
         if (g->scenario == SCN_BOXAGONE)   // (its tick is not in the union kernels, mv_step_union.hip: tick_any)
             return fail("mv_group_create: BoxAGone cannot be stepped in a group of gyms; step it as a gym of its own (MultiTaskGym: MV_MULTITASK_UNION=0)");
@@ -627,6 +635,9 @@ int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample,
     for (int i = 0; i < n; ++i)
         if (gyms[i] && !gyms[i]->closed && gyms[i]->budgetOn)
             return fail("mv_step_many: gym " + std::to_string(i) + " has an episode budget attached (mv_set_episode_budget): step it on its own, or detach the budget first");
+    for (int i = 0; i < n; ++i)
+        if (gyms[i] && !gyms[i]->closed && gyms[i]->stateObs)
+            return fail("mv_step_many: gym " + std::to_string(i) + " has state observations attached (mv_set_state_obs): step it on its own, or detach them first");
     for (int i = 0; i < n; ++i) {
         int r = sample ? mv_sample_random_actions(gyms[i], seed, step_index) : 0;
         if (r == 0) r = step_impl(gyms[i], render != 0, 1, POLICY_NONE, 0, 0);

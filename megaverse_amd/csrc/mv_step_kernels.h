@@ -5,7 +5,8 @@
 //   S::long_lists                          frame lists long enough for the depth sort (mv_frame.h: DepthSortScratch)
 //   S::par_agents                          several agents: every wave of the workgroup takes part in the tick (TowerBuilding)
 // No tick knows about step masks (mv_set_step_mask) or episode budgets (mv_set_episode_budget): the MASKED instantiations of the bodies choose between
-// S::tick and frozen_tick, below.  They also choose between frame_setup_body and frame_skip (mv_frame.h) for the envs a draw mask (mv_set_draw_mask) leaves out.
+// S::tick and frozen_tick, below.  They also choose between frame_setup_body and frame_skip (mv_frame.h) for the envs a draw mask (mv_set_draw_mask) leaves out,
+// and store the agents' state rows behind every tick of a view that carries staging rows for them (mv_set_state_obs: state_obs_write).
 // Every __global__ is a one-line entry point over a body in its scenario's mv_step_<scenario>.hip (a launch bound that depends on a template
 // parameter is not applied, and the profiles name the kernels); StepKernels lists them for the launchers (mv_step.hip).
 #pragma once
@@ -13,6 +14,7 @@
 
 #include "mv_episode_budget.h"
 #include "mv_frame.h"
+#include "mv_state_obs.h"
 #include "mv_types.h"
 
 // the register budget of the one-wave-per-env multi-tick kernels (512 / n VGPRs).  Their waves stay resident for a whole batched call beside the
@@ -114,6 +116,30 @@ __device__ __forceinline__ void env_frames_skip(const GymView &gv, int env)
     }
 }
 
+// ---- mv_set_state_obs: the agents' state rows of this tick (mv_state_obs.h has the record).  Called by every thread of the workgroup BEHIND what orders the
+// tick's stores before the frame setup's loads (wave_sync: one wave; the workgroup's barrier: several) -- the rows are loads of the same state -- and on either
+// side of every choice above: a frozen or halted env reports its unchanged state, an undrawn env what a drawn one reports, a tick without frame setup what one
+// with it does.  One exception needs no such ordering: the frozen path of step_body calls it straight behind frozen_tick, with no barrier -- frozen_tick
+// writes rewards, actions and done only, and the state the rows load was written by an earlier launch.
+// gv.state_obs is a kernel argument, so the branch is uniform; the env's first wave stores, lane l the word l of the env's 16 A (one round of 64 lanes up to
+// four agents, two up to eight): consecutive lanes, consecutive dwords.  Nothing waits for the stores: the launch's end publishes them to the copy on the
+// caller's stream.  Only the MASKED instantiations call it (the launchers pick them for a view with non-null rows).
+// The store itself is a function of its own that is NOT inlined: inlined, its few registers were live across the tick loop of kernels that are held to 128
+// (168) VGPRs by their launch bounds, and the allocator answered with up to 80 bytes more scratch per lane -- for every user of the MASKED kernels, with or
+// without rows attached (TowerBuilding's one-agent MV_RENDER_LAST kernel: 168 -> 248 bytes); as a call behind the uniform branch it costs those kernels at
+// most 16 bytes (profiles/state_obs_resources.txt).
+static __device__ __attribute__((noinline)) void state_obs_store(uint32_t *rows, const AgentState *agents, const EnvHeader *hdr, int words)
+{
+    for (int l = threadIdx.x; l < words; l += 64) rows[l] = state_obs_word(agents + (l >> 4), hdr, l & (STATE_OBS_FLOATS - 1));
+}
+template <int A_MAX>
+__device__ __forceinline__ void state_obs_write(const GymView &gv, int env)
+{
+    if (gv.state_obs == nullptr || threadIdx.x >= 64) return;
+    const int A = A_MAX == 1 ? 1 : gv.num_agents, words = STATE_OBS_FLOATS * A;   // (one agent: known when the kernel is compiled)
+    state_obs_store(reinterpret_cast<uint32_t *>(gv.state_obs) + (size_t)env * words, gv.agents + (size_t)env * A, gv.hdr + env, words);
+}
+
 // One workgroup per env: wave 0 runs the tick (one wave per env: physics, scenario logic, auto-reset), the others wait at the barrier (S::par_agents:
 // they take their share of the character controllers first); then the workgroup builds the lists of the env's frames (mv_frame.h).  `render` = 0:
 // mv_step_no_render.
@@ -133,6 +159,7 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
     [[maybe_unused]] int32_t left = -1;
     if constexpr (MASKED) if ((left = env_left(gv, env)) == 0) {   // (mv_set_step_mask, mv_set_episode_budget) the frozen tick, then the env's frames as below, from the unchanged state
         frozen_tick(gv, env);
+        state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs: the unchanged state, as the last launch left it)
         if (!render) return;
         __syncthreads();
         if (!env_drawn(gv, env)) { env_frames_skip<A_MAX == 1, STEP_THREADS, false>(gv, env); return; }   // (mv_set_draw_mask; uniform)
@@ -163,9 +190,16 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
         else if (rt1 - rt0 > d[54]) { d[54] = rt1 - rt0; for (int k = 0; k < 16; ++k) d[32 + k] = d[16 + k]; }
     }
 #endif
-    if (!render) return;
+    if (!render) {
+        if constexpr (MASKED) if (gv.state_obs != nullptr) {   // (mv_set_state_obs; uniform) a tick without frame setup reports its rows too
+            __syncthreads();   // the tick's stores before the rows' loads
+            state_obs_write<A_MAX>(gv, env);
+        }
+        return;
+    }
     __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
     MV_T(6);           // the whole tick as wave 0 saw it (incl. the generator of a finished env), up to the barrier
+    if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
     if constexpr (MASKED) if (!env_drawn(gv, env)) { env_frames_skip<A_MAX == 1, STEP_THREADS, false>(gv, env); return; }   // (mv_set_draw_mask; uniform)
     if constexpr (A_MAX == 1) {
         frame_setup_body<STEP_THREADS, false>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
@@ -218,6 +252,7 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
             else frozen_tick(gv, env);
             wave_sync();   // the tick's stores before the frame setup's loads (one wave: no barrier needed)
             if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
+            if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
             if (!MASKED || drawn) frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
             else env_frames_skip<true, 64, true>(gv, env);
         } else {
@@ -225,6 +260,7 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
             else frozen_tick(gv, env);
             __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
             if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
+            if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
             if (!MASKED || drawn) {
                 const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
                 for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
@@ -265,6 +301,10 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
                 __syncthreads();   // the tick's stores (same CU: same L1) before the next tick's loads
             }
             if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
+            if constexpr (MASKED) if (gv.state_obs != nullptr) {   // (mv_set_state_obs; uniform)
+                state_obs_write<A_MAX>(gv, env);
+                if constexpr (A_MAX > 1) __syncthreads();   // the rows' loads before the other waves' next tick changes the state
+            }
         }
     } else {
         constexpr int NS = A_MAX == 1 ? 1 : 4;
@@ -281,6 +321,7 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
                 else frozen_tick(gv, env);
                 wave_sync();   // the tick's stores before the frame setup's / the next tick's loads
                 if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
+                if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
                 if (frames) {
                     if (!MASKED || drawn) frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
                     else env_frames_skip<true, 64, true>(gv, env);
@@ -290,12 +331,15 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
                 else frozen_tick(gv, env);
                 __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's / the next tick's loads
                 if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
+                if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
                 if (frames) {
                     if (!MASKED || drawn) {
                         const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
                         for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
                     } else env_frames_skip<false, 64, true>(gv, env);
                     __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
+                } else if constexpr (MASKED) {
+                    if (gv.state_obs != nullptr) __syncthreads();   // (mv_set_state_obs; uniform) the rows' loads before the other waves' next tick changes the state
                 }
             }
         }
@@ -331,6 +375,8 @@ __device__ __forceinline__ void step_ticks_pipe_body(const Args &a, int W, int H
                 frozen_tick(a.view(j), env);
             }
             __syncthreads();                              // A(j)
+            // (mv_set_state_obs) tick j's rows: behind A(j), in front of tick j + 1, whose write-back comes behind B(j) and is this wave's own
+            if constexpr (MASKED) state_obs_write<1>(a.view(j), env);
         }
         __syncthreads();                                  // B(n - 1): the last frame setup's
     } else {

@@ -210,6 +210,10 @@ struct GymView {
     // leave behind their frame look-up (mv_raster.hip), the env's rows in the observation slab or ring keep what they held; null: no mask, every env is drawn.
     // Set by the stepping calls and mv_render (mv_api_step.hip, mv_api.hip); the views of mv_draw_hires and of the union launches leave it null.
     const uint8_t *draw_mask;
+    // mv_set_state_obs: [N*A][16] float32, this tick's staging rows of the state observations (mv_state_obs.h has the record): behind the tick the MASKED step
+    // bodies store every agent's row here (mv_step_kernels.h: state_obs_write), and one launch per stepping call carries the rows to the caller's buffer
+    // (mv_state_obs.hip).  null: off.  A field of the per-slot views (mv_gym::gvp), so tick_view leaves it alone; the union launches never see a non-null one.
+    float *state_obs;
 };
 
 // The n <= 8 consecutive ticks of a multi-tick step launch (mv_step.hip: step_ticks_kernel, and every mv_step_*.hip), the same envs in all of them: their views

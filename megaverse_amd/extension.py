@@ -99,7 +99,29 @@ SYMBOLS = [
     ("mv_debug_episode_budget_host", C.c_int, [_P, _P, _P, _I, _I, _P, _P]),
     ("mv_debug_raster_consts_host", C.c_int, [_I, _I, _P, _P, _P, _P]), ("mv_debug_raster_div_host", C.c_int, [_U, _U, _P, _P]),
     ("mv_set_draw_mask", C.c_int, [_P, _P]), ("mv_set_draw_mask_host", C.c_int, [_P, _P]), ("mv_get_draw_mask", C.c_int, [_P]),
+    ("mv_set_state_obs", C.c_int, [_P, _P]), ("mv_get_state_obs", C.c_int, [_P]), ("mv_get_state_observation", C.c_int, [_P, _I, _I, _P]),
+    ("mv_debug_state_obs_host", C.c_int, [_P, _P, _P]), ("mv_get_output_ring", C.c_int, [_P]),
 ]
+
+# include/megaverse_hip.h: MV_STATE_OBS_FLOATS and the columns of a state-observation row (mv_set_state_obs), name -> index
+MV_STATE_OBS_FLOATS = 16
+STATE_OBS_FIELDS = {name: i for i, name in enumerate((
+    "pos_x", "pos_y", "pos_z", "m00", "m02", "m20", "m22", "pitch", "hvx", "hvz", "vvel", "carrying", "episode_sec", "episode_len", "total_reward",
+    "reserved"))}
+
+
+def debug_state_obs_host(agent_state, env_header):
+    """mv_debug_state_obs_host: the state-observation record on the CPU (no device): the 128 bytes of one AgentState and the 128 bytes of one EnvHeader
+    (megaverse_amd/csrc/mv_types.h) -> the agent's row, float32 [16]"""
+    lib = load_library()
+    a = np.ascontiguousarray(np.frombuffer(bytes(agent_state), np.uint8))
+    h = np.ascontiguousarray(np.frombuffer(bytes(env_header), np.uint8))
+    if a.size != 128 or h.size != 128:
+        raise ValueError("debug_state_obs_host: an AgentState and an EnvHeader are 128 bytes each")
+    out = np.empty(MV_STATE_OBS_FLOATS, np.float32)
+    if lib.mv_debug_state_obs_host(a.ctypes.data, h.ctypes.data, out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
 
 # mv_episode_record (include/megaverse_hip.h): one finished episode of one agent, 24 bytes
 EPISODE_RECORD_DTYPE = np.dtype({"names": ["agent", "length", "end_tick", "true_objective", "ret"],
@@ -344,6 +366,21 @@ def check_draw_mask(mask, num_envs):
     return None if mask is None else _check_env_mask(mask, num_envs, 'set_draw_mask', 'the env is drawn')
 
 
+def check_state_obs(buf, entries, num_rows, device):
+    """the argument check of MegaverseGym.set_state_obs for a tensor: contiguous torch.float32 of shape (entries, num_rows, 16) on CUDA device `device`;
+    entries None: any number of entries (the check made before the gym is asked for its ring count)"""
+    got = tuple(getattr(buf, 'shape', ()))
+    shape = ((got[0] if len(got) == 3 else 1) if entries is None else int(entries), int(num_rows), MV_STATE_OBS_FLOATS)
+    contiguous = getattr(buf, 'is_contiguous', None)
+    dev = getattr(buf, 'device', None)
+    index = getattr(dev, 'index', None)
+    if not hasattr(buf, 'data_ptr') or got != shape or str(getattr(buf, 'dtype', None)) != 'torch.float32' \
+            or not getattr(buf, 'is_cuda', False) or not (callable(contiguous) and contiguous()) or (index is not None and int(index) != int(device)):
+        raise ValueError(f'set_state_obs: the buffer must be a contiguous float32 CUDA tensor of shape {shape} on device {int(device)}, '
+                         f"got {getattr(buf, 'dtype', type(buf).__name__)} {tuple(getattr(buf, 'shape', ()))} on {dev if dev is not None else 'no device'}")
+    return buf
+
+
 def check_episode_budget(budget, num_envs):
     """the argument check of MegaverseGym.set_episode_budget: None (detach) -> None; an int -> that value for every env; a contiguous torch.int32 CUDA tensor
     of shape (num_envs,) (or anything with data_ptr()) -> 'device'; anything else -> a contiguous int32 numpy array, one value per env"""
@@ -473,6 +510,7 @@ class MegaverseGym:
         self._reset_held = None  # reset_envs: the caller's device mask, likewise
         self._step_mask_held = None  # set_step_mask: the caller's device mask, kept until it is replaced or detached
         self._draw_mask_held = None  # set_draw_mask: the caller's device mask, kept until it is replaced or detached
+        self._state_obs = None       # set_state_obs: the attached tensor
         self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
         self._store_held = []    # save_envs / load_envs: the caller's stores and device maps, kept until the next step has been enqueued
 
@@ -735,6 +773,40 @@ class MegaverseGym:
     def draw_mask(self):
         """-> 'none' | 'device' | 'host': the form of the draw mask attached (set_draw_mask)"""
         return self.STEP_MASK_FORMS[self._ck(self._lib.mv_get_draw_mask(self._g))]
+
+    def set_state_obs(self, buf=True):
+        """State observations (include/megaverse_hip.h: mv_set_state_obs): every tick of every later stepping call -- in every render mode, 'none' included --
+        leaves one row of 16 float32 per agent (STATE_OBS_FIELDS: pose, velocities, carrying, episode time, total reward; the state AFTER the tick, bit for
+        bit) in entry t % entries of a float32 CUDA tensor [entries, num_envs * num_agents, 16], entries = the output ring's count, or 1 without a ring: the
+        entry the tick's rewards go to.  True allocates the tensor on the gym's device and returns it; a tensor is checked (ValueError) and attached; None
+        detaches.  Nothing waits on the host; the rows are visible on the gym's stream when the call's rewards are.  While attached, set_output_ring is
+        refused."""
+        if buf is None:
+            self._ck(self._lib.mv_set_state_obs(self._g, None))
+            self._state_obs = None
+            return None
+        rows = self.num_envs * self.num_agents_per_env
+        if buf is not True:
+            check_state_obs(buf, None, rows, self.device)   # (what needs no gym first: the library stays untouched by a tensor that is wrong anyway)
+        entries = max(1, self._ck(self._lib.mv_get_output_ring(self._g)))   # (the library's own count: the depth it will write)
+        if buf is True:
+            import torch
+            buf = torch.zeros((entries, rows, MV_STATE_OBS_FLOATS), dtype=torch.float32, device=f'cuda:{self.device}')
+        else:
+            check_state_obs(buf, entries, rows, self.device)
+        self._ck(self._lib.mv_set_state_obs(self._g, _P(int(buf.data_ptr()))))
+        self._state_obs = buf
+        return buf
+
+    def state_obs(self):
+        """-> the tensor set_state_obs attached, or None"""
+        return self._state_obs
+
+    def get_state_observation(self, env_idx, agent_idx):
+        """-> numpy float32 [16]: the last tick's row of one agent (waits for the gym's stream)"""
+        out = np.empty(MV_STATE_OBS_FLOATS, np.float32)
+        self._ck(self._lib.mv_get_state_observation(self._g, int(env_idx), int(agent_idx), out.ctypes.data))
+        return out
 
     def set_episode_budget(self, budget):
         """Episode budgets (include/megaverse_hip.h: mv_set_episode_budget): env e may finish budget[e] more episodes (< 0: unlimited) and then HALTS on the

@@ -18,7 +18,7 @@ Differences, all additive:
 import numpy as np
 
 from . import spaces
-from .extension import MegaverseGym, render_mode_of, set_megaverse_log_level
+from .extension import MegaverseGym, STATE_OBS_FIELDS, render_mode_of, set_megaverse_log_level
 
 MEGAVERSE8 = ['TowerBuilding', 'ObstaclesEasy', 'ObstaclesHard', 'Collect', 'Sokoban', 'HexMemory', 'HexExplore', 'Rearrange']
 OBSTACLES_MULTITASK = ['ObstaclesWalls', 'ObstaclesSteps', 'ObstaclesLava', 'ObstaclesEasy', 'ObstaclesHard']
@@ -68,7 +68,7 @@ def check_sequence_actions(actions, num_agents):
 
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
-                 img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0):
+                 img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False):
         if obs_layout not in ("rgba", "chw"):
             raise ValueError("obs_layout must be 'rgba' (frames written as (H, W, 4) RGBA, handed out as a permuted view) or 'chw' (written as (3, H, W))")
         scenario_name = scenario_name.casefold()
@@ -101,6 +101,11 @@ class MegaverseEnv:
         self.episode_log = int(episode_log)
         if self.episode_log > 0:
             self.env.set_episode_log(self.episode_log)
+        # state_obs: every tick leaves one row of 16 float32 per agent (STATE_OBS_FIELDS: pose, velocities, carrying, episode time, total reward) in a CUDA
+        # tensor (mv_set_state_obs), read with self.state_obs() -- in every render mode, without a host wait
+        self._state_on = bool(state_obs)
+        if self._state_on:
+            self.env.set_state_obs(True)
         self.default_shaping_scheme = self.env.get_reward_shaping(0, 0)
         self.action_space = self.generate_action_space(self.env.action_space_sizes())
         self.observation_space = spaces.Box(0, 255, (self.channels, self.img_h, self.img_w), dtype=np.uint8)
@@ -109,6 +114,28 @@ class MegaverseEnv:
         self._dev_out = None
         self._seq = None   # step_sequence: ((k, render), obs ring or None, rewards ring, dones ring, actions) while its rings are attached
         self._frozen = np.zeros(self.num_envs, np.bool_)   # freeze / thaw: the envs this env keeps frozen through a host step mask
+
+    STATE_OBS_FIELDS = STATE_OBS_FIELDS   # column name -> index of a state_obs() row (the table MegaverseGym shares)
+
+    def state_obs(self):
+        """the last tick's state observations: float32 (num_agents, 16) on the device, columns STATE_OBS_FIELDS -- a view of the attached buffer, valid in
+        the order of the gym's stream until the next stepping call; no host wait.  After step_sequence: its last tick's rows (self.env.state_obs() has all k
+        entries, entry j what tick j left).  Ask again after every call: when step_device or step_sequence swap the env's output rings, the buffer is
+        detached and a NEW tensor of the new depth attached (_set_output_ring) -- a view held from before such a call is no longer written.  Needs
+        MegaverseEnv(..., state_obs=True)."""
+        buf = self.env.state_obs()
+        if buf is None:
+            raise RuntimeError("state_obs: create the env with state_obs=True")
+        return buf[self._seq[0][0] - 1 if self._seq is not None else 0]
+
+    def _set_output_ring(self, count, *ptrs):
+        """the env's own output rings change (step_device, step_sequence): the state buffer is one more ring of the same depth and the library refuses a ring
+        change while it is attached, so it is detached around the change and a buffer of the new depth attached"""
+        if self._state_on:
+            self.env.set_state_obs(None)
+        self.env.set_output_ring(count, *ptrs)
+        if self._state_on:
+            self.env.set_state_obs(True)
 
     @staticmethod
     def generate_action_space(action_space_sizes):
@@ -222,7 +249,7 @@ class MegaverseEnv:
         if self._dev_out is None:
             dev = self._obs_tensor.device
             self._dev_out = (torch.zeros(self.num_agents, dtype=torch.float32, device=dev), torch.zeros(self.num_envs, dtype=torch.uint8, device=dev))
-            self.env.set_output_ring(1, self._obs_tensor.data_ptr(), self._dev_out[0].data_ptr(), self._dev_out[1].data_ptr())
+            self._set_output_ring(1, self._obs_tensor.data_ptr(), self._dev_out[0].data_ptr(), self._dev_out[1].data_ptr())
         held = None
         if actions is not None:
             if hasattr(actions, 'data_ptr'):   # (the lifetime rule of step_batched)
@@ -406,7 +433,7 @@ class MegaverseEnv:
             return
         self._seq = None
         self._dev_out = None
-        self.env.set_output_ring(0)
+        self._set_output_ring(0)
         self.env.set_action_ring(0)
         self.env.render()
 
@@ -436,10 +463,10 @@ class MegaverseEnv:
             if render == "every":
                 frame = (3, self.img_h, self.img_w) if self.obs_layout == 'chw' else (self.img_h, self.img_w, 4)
                 rings = (torch.zeros((k, self.num_agents) + frame, dtype=torch.uint8, device=dev),) + rings
-                self.env.set_output_ring(k, rings[0].data_ptr(), rings[1].data_ptr(), rings[2].data_ptr())
+                self._set_output_ring(k, rings[0].data_ptr(), rings[1].data_ptr(), rings[2].data_ptr())
             else:   # ('last': the one drawn tick goes to the env's own slab -- a NULL ring keeps that output where it was)
                 rings = (None,) + rings
-                self.env.set_output_ring(k, 0, rings[1].data_ptr(), rings[2].data_ptr())
+                self._set_output_ring(k, 0, rings[1].data_ptr(), rings[2].data_ptr())
         else:
             rings = self._seq[1:4]
         self._seq = ((k, render),) + tuple(rings) + (held,)   # (the actions stay alive until the next call replaces them)

@@ -172,6 +172,11 @@ class MultiTaskGym:
         raise RuntimeError("MultiTaskGym.set_draw_mask: mv_group_create and mv_step_many refuse a gym with a draw mask attached "
                            "(mv_set_draw_mask): the union launches read none; step such a gym on its own")
 
+    def set_state_obs(self, buf=True):
+        """state observations (MegaverseGym.set_state_obs) are per gym: a group's union launches write none, and the library refuses"""
+        raise RuntimeError("MultiTaskGym.set_state_obs: mv_group_create and mv_step_many refuse a gym with state observations attached "
+                           "(mv_set_state_obs): the union launches write none; step such a gym on its own")
+
     def recommended_ticks_per_call(self):
         """the k to ask step_n for: what every member recommends (mv_recommended_ticks_per_call), at most 8 -- the two-launch group call's limit"""
         return max(1, min([8] + [g.recommended_ticks_per_call() for g in self.gyms]))
