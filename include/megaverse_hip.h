@@ -182,6 +182,36 @@ int64_t mv_resample_staging_bytes(const mv_gym *g);              /* 0 before the
  * Refused (-1 with text): no gym, a closed gym, before the first mv_reset, a null mask. */
 int mv_reset_envs(mv_gym *g, const uint8_t *device_mask, int32_t render);   /* mask [N] in device memory, read in the order of the gym's stream */
 int mv_reset_envs_host(mv_gym *g, const uint8_t *mask, int32_t render);     /* mask [N] in host memory */
+/* Level seeds (the per-env form of mv_seed; no reference counterpart: MegaverseGym::seed re-seeds every env from one master stream, megaverse.cpp:60-69).
+ * seeds: int32 [N].  seeds[e] >= 0: env e receives Env::seed(seeds[e]) (env.cpp:52-55) -- the value mv_seed hands an env from its master stream ([0, 2^30)
+ * there, any non-negative int32 here; megaverse_amd.distributed.env_seeds(S, N) lists mv_seed(S)'s).  seeds[e] < 0: env e is left alone, byte for byte: its
+ * resident episodes and its place in the refill protocol do not move.
+ * Meaning, in both forms: exactly mv_seed's, per env.  The env's RUNNING episode goes on untouched; the episodes drawn ahead from its old stream are
+ * dropped; its generator restarts, so that its next reset -- an auto-reset, mv_reset, mv_reset_envs -- plays the first episode of the new stream and the ones
+ * after it follow that chain.  Two envs given the same seed play the same level sequence; mv_seed_envs* followed by mv_reset_envs* on the same envs means
+ * "start level s in env d now".  Valid before the first mv_reset, where it acts as mv_seed for the chosen envs.
+ * IDENTITY: an env slot's episode stream is what forks, resampling, loads and masked resets leave alone (mv_fork_envs above); this call is the one that
+ * REPLACES it.  Nothing else of the slot moves: episodes_consumed keeps counting, the episode log's running returns, masks, budgets and state observations
+ * need nothing.
+ * Sokoban keeps its per-env shuffled level list (SokobanScenario::levels) across Env::seed, as under mv_seed and in the reference: only what the flagged
+ * envs' ahead-of-time draws took from it is put back.  A Sokoban env's levels therefore depend on how far its list was advanced, not on the seed alone.
+ * Ordering: both forms are ordering points on the gym's stream, like mv_reset_envs: behind every step launch enqueued so far and behind whatever the caller
+ * enqueued there (the kernel that wrote a device array), in front of the next step launch and the next episode draw.
+ * Device-drawn gyms (TowerBuilding), both forms: no host wait.  One launch re-seeds the flagged envs' generators and empties their rings, the draw launch
+ * behind it makes the new streams' first episodes resident in stream order.  The device array is read when the kernel runs: keep it unchanged until then
+ * (in stream order: until the next stepping call has been enqueued).  The host form copies its array through a pinned staging pair (allocated by the first
+ * call, which may wait inside the allocator).
+ * Host-fed gyms (every other scenario), host form: the generators live in the host's episode feeder, which needs the flagged envs' current consumed
+ * counts: the call WAITS ON THE HOST for everything enqueued on the gym's streams, as mv_seed does.  It then wipes the flagged envs' rings alone, restarts
+ * their streams in the feeder (every other env's queued, in-flight and ready episodes are untouched) and, before it returns, uploads the first episode of
+ * the new stream for every flagged env: a reset of either form that follows never starves, however many seed / reset pairs follow each other without a
+ * stepping call.  With every entry negative the call returns 0, waits for nothing and launches nothing.  Returns 1 with a warning like a stepping call
+ * where the refill pass meets a capacity flag.
+ * Host-fed gyms, device form: refused (-1 with text, nothing changed): the generators live on the host -- use mv_seed_envs_host.
+ * Members of an mv_group are supported, as by mv_reset_envs.
+ * Refused (-1 with text): no gym, a closed gym, a null array. */
+int mv_seed_envs(mv_gym *g, const int32_t *device_seeds);   /* seeds [N] in device memory, read in the order of the gym's stream */
+int mv_seed_envs_host(mv_gym *g, const int32_t *seeds);     /* seeds [N] in host memory */
 /* Step masks (no reference counterpart: VectorEnv::step steps every env, vector_env.cpp:89-108).  mask: one byte per env, [N]; a torch.bool tensor is such a
  * mask, as in mv_reset_envs.  mask[e] != 0: env e steps.  mask[e] == 0: env e is FROZEN.  The mask stays attached, like an action ring, until it is detached
  * (NULL) or replaced, and every tick of every later stepping call reads it: mv_step, mv_step_no_render, mv_step_n, mv_step_n_render in all three render modes,
@@ -555,6 +585,14 @@ int mv_debug_generate_episode(const char *scenario, int32_t num_agents, int32_t 
  * time; replaces the serial Env::reset inside VectorEnv::step, vector_env.cpp:93-105) for `rounds` episodes per env
  * and compares each delivered episode with sequential generation.  0 = identical. */
 int mv_debug_feeder_selftest(const char *scenario, int32_t num_envs, int32_t num_agents, int32_t threads, int32_t rounds);
+/* Host-only (no device): drives the episode feeder through a script of re-seeds (EpisodeFeeder::reseed_envs, what mv_seed_envs_host calls) and takes, and
+ * compares every delivered episode with straight sequential generation from the same seeds (Sokoban: with the level list carried across a re-seed).
+ * env_seeds [num_envs]: the initial Env::seed values.  script: n_ops x {op, env, value} -- op 0: take env's next episode (wait_ready, compare, recycle);
+ * op 1: put (env, value) on the pending re-seed list; op 2: one reseed_envs call with that list.  out (or NULL): the delivered records, one per take in
+ * script order; used_out (or NULL): the bytes of each the feeder reports as used.  Returns the number of takes, -1 with text on a difference or an error;
+ * script == NULL and out == NULL: the record size. */
+int mv_debug_feeder_reseed_script(const char *scenario, int32_t num_envs, int32_t num_agents, int32_t threads, const int32_t *env_seeds,
+                                  const int32_t *script, int32_t n_ops, void *out, int64_t out_bytes, int32_t *used_out);
 /* Host-only: the first n episodes of the Sokoban level generator (scenario_sokoban.cpp:80-170; its kernels come next) as n
  * packed records; out == NULL: record size.  Returns n, -1 on error. */
 int mv_debug_generate_sokoban(int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes);

@@ -5,6 +5,7 @@
 //   mv_fork.hip       env forks: the gather-copy kernel and its entry points; the entry points of env resampling
 //   mv_resample.hip   env resampling: the two kernels of the staged copy
 //   mv_reset_envs.hip masked env resets: the host protocol around the reset_masked kernels (mv_step_kernels.h)
+//   mv_seed_envs.hip  level seeds: Env::seed for chosen envs -- the staging of the seed words, the host-fed gyms' protocol, the feeder's host-only hook
 //   mv_env_store.hip  env stores: the save / load kernels, their entry points and host-only hooks
 //   mv_step_mask.hip  step masks: attaching and detaching the bytes that freeze envs (mv_step_kernels.h: frozen_tick)
 //   mv_draw_mask.hip  draw masks: attaching and detaching the bytes that leave envs' frames out of the observation passes (mv_frame.h: frame_skip)
@@ -43,6 +44,7 @@ namespace mv {
 // TowerBuilding: tops every env's ring of drawn episodes up (mv_reset.hip)
 void launch_tower_draw(const GymView &gv, hipStream_t stream);
 void launch_tower_seed(const GymView &gv, const uint32_t *seeds, hipStream_t stream);   // Env::seed for every env's generator
+void launch_tower_seed_envs(const GymView &gv, const int32_t *seeds, hipStream_t stream);   // mv_seed_envs: ... for the envs whose seeds[env] >= 0
 // Collect, device-drawn episodes (mv_collect_draw.hip): staging slots of envs[i] -> their ring slots slots[i], one launch per 64 episodes
 void launch_collect_blob_copy(const int32_t *envs, const int32_t *slots, int count, const uint8_t *staging, uint8_t *ring, size_t blob_bytes, int spares,
                               hipStream_t stream);
@@ -237,6 +239,10 @@ struct mv_gym {
     uint8_t *dResetMask = nullptr, *hResetMask = nullptr;
     hipEvent_t resetMaskCopied[2] = {nullptr, nullptr};
     unsigned long long resetMaskUses = 0;
+    // mv_seed_envs_host: [2][N] seed words of device memory and their pinned staging, double buffered like the reset mask's, allocated at the first use
+    int32_t *dSeedEnvs = nullptr, *hSeedEnvs = nullptr;
+    hipEvent_t seedEnvsCopied[2] = {nullptr, nullptr};
+    unsigned long long seedEnvsUses = 0;
     // mv_set_step_mask: the [N] bytes the step kernels read (GymView::step_mask through the stepping calls' views), null: no mask.  Form 1: the caller's
     // buffer.  Form 2: dStepMask, gym-owned, allocated at the host form's first use and counted in mv_arena_bytes; its bytes travel through pinned staging
     // buffers, each free again once the event behind its copy has completed (looked at with hipEventQuery: the call never waits on the host).
@@ -307,6 +313,7 @@ void episode_log_free(mv_gym *g);   // mv_close
 void step_mask_free(mv_gym *g);     // mv_close (mv_step_mask.hip)
 void draw_mask_free(mv_gym *g);     // mv_close (mv_draw_mask.hip)
 void episode_budget_free(mv_gym *g);   // mv_close (mv_episode_budget.hip)
+void seed_envs_free(mv_gym *g);        // mv_close (mv_seed_envs.hip)
 // mv_state_obs.hip: tick `tick`'s entry of the caller's buffer (the entry outputs_of gives its rewards); the staged rows of the k ticks in slots q0 .. q0 + k - 1
 // -> dst[j], one launch on the caller's stream; the last tick's entry gathered from the current state (mask: device bytes [N], only the flagged envs' rows;
 // null: every row; nothing attached: no launch), on the caller's stream behind sim_join

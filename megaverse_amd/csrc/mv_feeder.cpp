@@ -14,7 +14,7 @@ void launch_collect_draw(void *states, const int32_t *envs, int count, uint8_t *
 EpisodeFeeder::EpisodeFeeder(int scenario, const ObstacleConfig &cfg, int num_envs, int num_agents, float base_episode_len, uint8_t *slots,
                              size_t slot_bytes, int device, int num_threads, std::vector<std::string> level_files, bool device_gen)
     : scenario_{scenario}, num_envs_{num_envs}, num_agents_{num_agents}, device_{device}, cfg_{cfg}, base_len_{base_episode_len},
-      slots_{slots}, slot_bytes_{slot_bytes}, rng_(num_envs), next_seq_(num_envs, 1), ready_seq_(num_envs), used_bytes_(num_envs, 0),
+      slots_{slots}, slot_bytes_{slot_bytes}, rng_(num_envs), next_seq_(num_envs, 1), ready_seq_(num_envs), used_bytes_(num_envs, 0), busy_(num_envs, 0),
       soko_files_{std::move(level_files)}, soko_levels_(scenario == SCN_SOKOBAN ? num_envs : 0), soko_undo_(scenario == SCN_SOKOBAN ? num_envs : 0),
       device_gen_{device_gen && scenario == SCN_COLLECT}, seeds_(num_envs, 0)
 {
@@ -63,21 +63,38 @@ bool EpisodeFeeder::upload_states()
     return hipMemcpy(d_states_, st.data(), st.size() * sizeof(cdraw::GenState), hipMemcpyHostToDevice) == hipSuccess;
 }
 
+bool EpisodeFeeder::upload_states_of(const std::vector<uint8_t> &named)
+{   // one copy per run of consecutive named envs (every env named: one copy); the other envs' states are the device's, the host holds no copy of them
+    std::vector<cdraw::GenState> st;
+    for (int i = 0; i < num_envs_;) {
+        if (!named[(size_t)i]) { ++i; continue; }
+        const int first = i;
+        st.clear();
+        for (; i < num_envs_ && named[(size_t)i]; ++i) st.push_back(cdraw::GenState{seeds_[i], 1, next_seq_[i], 0});
+        if (hipMemcpy(static_cast<cdraw::GenState *>(d_states_) + first, st.data(), st.size() * sizeof(cdraw::GenState), hipMemcpyHostToDevice) != hipSuccess)
+            return false;
+    }
+    return true;
+}
+
+void EpisodeFeeder::undo_sokoban(int i, int first_seq)
+{   // episodes first_seq .. next_seq - 1 were generated ahead and are dropped: undo what they took
+    std::deque<SokoUndo> &undo = soko_undo_[i];
+    for (int q = next_seq_[i] - 1; q >= first_seq && !undo.empty(); --q) {
+        if (undo.back().reloaded) soko_levels_[i].pending.clear();
+        else soko_levels_[i].pending.push_back(std::move(undo.back().level));
+        undo.pop_back();
+    }
+    undo.clear();
+}
+
 void EpisodeFeeder::reseed(const std::vector<uint32_t> &values, const std::vector<int> &first_seq)
 {
     std::unique_lock<std::mutex> lk(mu_);
     tasks_.clear();                                           // not started yet: their episodes would come from the old streams
     cv_done_.wait(lk, [this] { return in_flight_ == 0; });    // started ones finish first (they own rng_[env])
     for (int i = 0; i < num_envs_; ++i) {
-        if (scenario_ == SCN_SOKOBAN) {   // episodes first_seq .. next_seq - 1 were generated ahead and are dropped: undo what they took
-            std::deque<SokoUndo> &undo = soko_undo_[i];
-            for (int q = next_seq_[i] - 1; q >= first_seq[i] && !undo.empty(); --q) {
-                if (undo.back().reloaded) soko_levels_[i].pending.clear();
-                else soko_levels_[i].pending.push_back(std::move(undo.back().level));
-                undo.pop_back();
-            }
-            undo.clear();
-        }
+        if (scenario_ == SCN_SOKOBAN) undo_sokoban(i, first_seq[i]);
         rng_[i].seed((unsigned long)values[i]);               // Env::seed, env.cpp:52-55
         seeds_[i] = values[i];
         next_seq_[i] = first_seq[i];
@@ -85,6 +102,42 @@ void EpisodeFeeder::reseed(const std::vector<uint32_t> &values, const std::vecto
         tasks_.push_back(Task{i, nullptr});
     }
     if (device_gen_ && !failed() && !upload_states()) failed_.store(true, std::memory_order_release);   // (no batch is in flight: the states are the host's to write)
+    lk.unlock();
+    cv_task_.notify_all();
+}
+
+void EpisodeFeeder::reseed_envs(const std::vector<int> &envs, const std::vector<uint32_t> &values, const std::vector<int> &first_seq)
+{
+    if (envs.empty()) return;
+    std::vector<uint8_t> named((size_t)num_envs_, 0);
+    for (int e : envs) named[(size_t)e] = 1;
+    std::unique_lock<std::mutex> lk(mu_);
+    // not started yet: their episodes would come from the old streams.  The event a dropped task waited for -- the upload that still reads the env's slot --
+    // is kept for the task that takes its place.
+    std::vector<hipEvent_t> after((size_t)num_envs_, nullptr);
+    for (auto t = tasks_.begin(); t != tasks_.end();) {
+        if (!named[(size_t)t->env]) { ++t; continue; }
+        after[(size_t)t->env] = t->after;
+        t = tasks_.erase(t);
+    }
+    // started ones finish first (they own rng_[env]); the device worker's batch is one launch over all of its envs, and the states are the host's to write
+    // only with no batch in flight
+    cv_done_.wait(lk, [&] {
+        if (device_gen_) return in_flight_ == 0;
+        for (int e : envs) if (busy_[(size_t)e]) return false;
+        return true;
+    });
+    for (size_t k = 0; k < envs.size(); ++k) {
+        const int i = envs[k];
+        if (scenario_ == SCN_SOKOBAN) undo_sokoban(i, first_seq[k]);
+        rng_[i].seed((unsigned long)values[k]);               // Env::seed, env.cpp:52-55
+        seeds_[i] = values[k];
+        next_seq_[i] = first_seq[k];
+        ready_seq_[i].store(0, std::memory_order_release);
+    }
+    if (device_gen_ && !failed() && !upload_states_of(named)) failed_.store(true, std::memory_order_release);   // (no batch is in flight)
+    for (int i = 0; i < num_envs_; ++i)   // (one task per env, whatever the list named twice)
+        if (named[(size_t)i]) tasks_.push_back(Task{i, after[(size_t)i]});
     lk.unlock();
     cv_task_.notify_all();
 }
@@ -232,12 +285,14 @@ void EpisodeFeeder::worker_main()
             t = tasks_.front();
             tasks_.pop_front();
             ++in_flight_;
+            busy_[(size_t)t.env] = 1;
         }
         if (t.after) (void)hipEventSynchronize(t.after);   // the slot is still the source of an in-flight upload
         generate(t.env);
         {
             std::lock_guard<std::mutex> lk(mu_);
             --in_flight_;
+            busy_[(size_t)t.env] = 0;
         }
         cv_done_.notify_all();
     }

@@ -40,6 +40,11 @@ public:
     // generating `first_seq[i]` (the sequence number the device expects next) for every env.
     void reseed(const std::vector<uint32_t> &values, const std::vector<int> &first_seq);
 
+    // Env::seed for the envs of `envs` only (values[k], first_seq[k] belong to envs[k]; an env named twice takes its last entry): reseed() for a subset.
+    // Their not-yet-started tasks are dropped, their generations in flight are finished first, Sokoban's undo runs for them alone and, in device mode,
+    // their GenState is written with no batch in flight.  Every other env's queued, in-flight and ready episodes are untouched.
+    void reseed_envs(const std::vector<int> &envs, const std::vector<uint32_t> &values, const std::vector<int> &first_seq);
+
     // Blocks until episode `seq` of `env` is complete in its slot; returns the slot and how many bytes of it are used.
     const uint8_t *wait_ready(int env, int seq, size_t *used_bytes);
 
@@ -73,6 +78,7 @@ private:
     std::condition_variable cv_task_, cv_done_;
     std::deque<Task> tasks_;
     int in_flight_ = 0;
+    std::vector<uint8_t> busy_;                  // under mu_: a worker is generating env i's episode (what reseed_envs waits for)
     bool stop_ = false;
     std::vector<std::thread> workers_;
     std::atomic<bool> failed_{false};
@@ -91,6 +97,8 @@ private:
     int32_t *h_list_ = nullptr, *d_list_ = nullptr, *h_flags_ = nullptr, *d_flags_ = nullptr;
     hipStream_t gen_stream_ = nullptr;
     bool upload_states();   // next_seq_ / seeds -> d_states_ (reseed, under mu_ with no batch in flight)
+    bool upload_states_of(const std::vector<uint8_t> &named);   // ... of the envs named[i] != 0 alone (reseed_envs, likewise)
+    void undo_sokoban(int env, int first_seq);   // (under mu_, env idle) what env's episodes first_seq .. next_seq - 1 took from its level list is put back
     std::vector<uint32_t> seeds_;
 };
 

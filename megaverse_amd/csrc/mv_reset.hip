@@ -45,6 +45,20 @@ __global__ void tower_seed_kernel(GymView gv, const uint32_t *seeds)
     for (int q = 0; q < gv.spares; ++q) ring[q].seq = 0;
 }
 
+// mv_seed_envs: Env::seed for the envs whose seed word is not negative, one lane per env; an env with a negative word is left alone, byte for byte
+__global__ void tower_seed_envs_kernel(GymView gv, const int32_t *seeds)
+{
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= gv.num_envs) return;
+    const int32_t s = seeds[env];
+    if (s < 0) return;
+    TowerGen tg;
+    tg.seed = (uint32_t)s; tg.seed_is_env_seed = 1; tg.generated = gv.hdr[env].episodes_consumed; tg.pad = 0;
+    gv.tower_gen[env] = tg;
+    TowerBlob *ring = const_cast<TowerBlob *>(reinterpret_cast<const TowerBlob *>(gv.blobs)) + (size_t)env * gv.spares;
+    for (int q = 0; q < gv.spares; ++q) ring[q].seq = 0;
+}
+
 void launch_tower_draw(const GymView &gv, hipStream_t stream)
 {
     hipLaunchKernelGGL(tower_draw_kernel, dim3(gv.num_envs), dim3(64), 0, stream, gv);
@@ -53,6 +67,11 @@ void launch_tower_draw(const GymView &gv, hipStream_t stream)
 void launch_tower_seed(const GymView &gv, const uint32_t *seeds, hipStream_t stream)
 {
     hipLaunchKernelGGL(tower_seed_kernel, dim3((gv.num_envs + 255) / 256), dim3(256), 0, stream, gv, seeds);
+}
+
+void launch_tower_seed_envs(const GymView &gv, const int32_t *seeds, hipStream_t stream)
+{
+    hipLaunchKernelGGL(tower_seed_envs_kernel, dim3((gv.num_envs + 255) / 256), dim3(256), 0, stream, gv, seeds);
 }
 
 }  // namespace mv

@@ -1,0 +1,257 @@
+// megaverse_amd/csrc/mv_seed_envs.hip -- level seeds: the host side of mv_seed_envs / mv_seed_envs_host (include/megaverse_hip.h): Env::seed for chosen envs.
+// TowerBuilding's generators live on the device: the masked seed kernel is tower_seed_envs_kernel (mv_reset.hip), next to mv_seed's.  Every other scenario's
+// live in the episode feeder (mv_feeder.h: reseed_envs); of the device this file only wipes the flagged envs' rings (ring_wipe_envs_kernel below) and sends
+// the new streams' first episodes up through the refill protocol (mv_api.hip: refill_episodes).  DESIGN.md 3.15 has the contract.
+#include <cstddef>
+
+#include "mv_api_internal.h"
+
+namespace {
+
+// Host-fed gyms: the episodes resident in a flagged env's ring were drawn from its old stream -- sequence number 0 matches nothing (every record of every
+// scenario begins with its int32 seq: mv_types.h).  One lane per ring slot of every env.
+__global__ void ring_wipe_envs_kernel(uint8_t *blobs, size_t blob_bytes, int spares, int num_envs, const int32_t *seeds)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_envs * spares) return;
+    if (seeds[i / spares] < 0) return;
+    *reinterpret_cast<int32_t *>(blobs + (size_t)i * blob_bytes) = 0;
+}
+
+int seed_envs_check(mv_gym *g, const void *seeds, const char *who)
+{
+    if (check(g)) return -1;
+    if (!seeds) return fail(std::string(who) + ": null seeds");
+    return 0;
+}
+
+// first use of the host form: two halves of N seed words on the device, their pinned staging, an event per half.  Nothing is cleared: a half is written
+// before it is read.
+int seed_envs_buffers(mv_gym *g)
+{
+    if (g->dSeedEnvs) return 0;
+    const size_t N = (size_t)g->N;
+    HIP_TRY(hipMalloc((void **)&g->dSeedEnvs, 2 * N * sizeof(int32_t)));
+    HIP_TRY(hipHostMalloc((void **)&g->hSeedEnvs, 2 * N * sizeof(int32_t), hipHostMallocDefault));
+    for (hipEvent_t &e : g->seedEnvsCopied) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    g->seedEnvsUses = 0;
+    return 0;
+}
+
+// the host's seed words -> the device half whose turn it is, on the caller's stream.  The half's event is recorded here, behind the copy, with the use that
+// is counted here -- whatever becomes of the launch that follows, the event of this use exists -- and seed_envs_staged records it again behind the kernel
+// that read the device half.
+int stage_seeds(mv_gym *g, const int32_t *host_seeds, const int32_t **device_seeds)
+{
+    if (seed_envs_buffers(g)) return -1;
+    const size_t N = (size_t)g->N;
+    const int b = (int)(g->seedEnvsUses & 1ull);
+    // (the copy and the launch that used this half two calls ago: long done -- the staging is the host's to write again, the device half the stream's)
+    if (g->seedEnvsUses >= 2) HIP_TRY(hipEventSynchronize(g->seedEnvsCopied[b]));
+    int32_t *h = g->hSeedEnvs + (size_t)b * N, *d = g->dSeedEnvs + (size_t)b * N;
+    std::memcpy(h, host_seeds, N * sizeof(int32_t));
+    HIP_TRY(hipMemcpyAsync(d, h, N * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipEventRecord(g->seedEnvsCopied[b], g->stream));
+    *device_seeds = d;
+    ++g->seedEnvsUses;
+    return 0;
+}
+int seed_envs_staged(mv_gym *g)
+{
+    HIP_TRY(hipEventRecord(g->seedEnvsCopied[(int)((g->seedEnvsUses - 1) & 1ull)], g->stream));
+    return 0;
+}
+
+// TowerBuilding, both forms, on the CALLER's stream like mv_seed's launches: behind whatever the caller enqueued there (the kernel that wrote a device
+// array), behind every step launch enqueued so far (sim_join) and the last draw launch (tower_join); the next step launch waits for all of it
+// (simMustWaitUser), and every later draw launch is ordered behind that step.  No host wait: the draw behind the seed kernel makes the new streams' first
+// episodes resident in stream order.
+int seed_envs_tower(mv_gym *g, const int32_t *device_seeds, const int32_t *host_seeds)
+{
+    HIP_TRY(hipSetDevice(g->device));
+    if (sim_join(g) || tower_join(g)) return -1;
+    if (host_seeds && stage_seeds(g, host_seeds, &device_seeds)) return -1;
+    launch_tower_seed_envs(g->gv, device_seeds, g->stream);
+    launch_tower_draw(g->gv, g->stream);
+    HIP_TRY(hipGetLastError());
+    if (host_seeds && seed_envs_staged(g)) return -1;
+    return 0;
+}
+
+// Host-fed gyms, host form.  The generators are the feeder's, and it needs the sequence number the device expects next of every flagged env: the current
+// consumed counts, taken as mv_seed takes them -- with a host wait for everything enqueued.  Then, for the flagged envs alone: their rings are wiped on the
+// device, they count as "consumed everything uploaded", the feeder restarts their streams (reseed_envs), and the refill pass that follows finds them with
+// nothing resident and therefore WAITS for their next episode -- the first of the new stream -- and uploads it (upload_pass: `must`): a reset of either form
+// that comes next finds it there, however many seed / reset pairs follow each other without a stepping call.
+int seed_envs_host_fed(mv_gym *g, const int32_t *host_seeds)
+{
+    const int N = g->N;
+    std::vector<int> envs, first;
+    std::vector<uint32_t> values;
+    for (int e = 0; e < N; ++e)
+        if (host_seeds[e] >= 0) { envs.push_back(e); values.push_back((uint32_t)host_seeds[e]); }
+    if (envs.empty()) return 0;   // nobody flagged: nothing to wait for, nothing to launch
+    HIP_TRY(hipSetDevice(g->device));
+    if (sim_join(g)) return -1;
+    HIP_TRY(hipStreamSynchronize(g->simStream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    HIP_TRY(hipStreamSynchronize(g->copyStream));
+    // the current counts, not the last periodic read-back
+    HIP_TRY(hipMemcpy(g->hStatus, g->dStatus, (size_t)(N + 2) * sizeof(int), hipMemcpyDeviceToHost));
+    g->statusPending = false;
+    g->pendingAge = 0;
+    g->stepsSinceStatus = 0;
+    const int32_t *device_seeds = nullptr;
+    if (stage_seeds(g, host_seeds, &device_seeds)) return -1;
+    const int slots = N * g->spares;
+    hipLaunchKernelGGL(ring_wipe_envs_kernel, dim3((slots + 255) / 256), dim3(256), 0, g->stream, g->dBlobs, g->blobBytes, g->spares, N, device_seeds);
+    HIP_TRY(hipGetLastError());
+    if (seed_envs_staged(g)) return -1;
+    HIP_TRY(hipStreamSynchronize(g->stream));   // (the uploads below travel on other streams: the wipe is done before the first of them starts)
+    for (int e : envs) {
+        g->uploaded[(size_t)e] = g->hStatus[e];
+        first.push_back(g->hStatus[e] + 1);
+    }
+    g->feeder->reseed_envs(envs, values, first);
+    g->refillForce = true;
+    if (refill_episodes(g, 1) < 0) return -1;   // every flagged env has the first episode of its new stream resident
+    return finish_with_warning(g);
+}
+
+}  // namespace
+
+void mvapi::seed_envs_free(mv_gym *g)
+{
+    if (g->dSeedEnvs) (void)hipFree(g->dSeedEnvs);
+    if (g->hSeedEnvs) (void)hipHostFree(g->hSeedEnvs);
+    for (hipEvent_t &e : g->seedEnvsCopied) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    g->dSeedEnvs = g->hSeedEnvs = nullptr;
+}
+
+extern "C" {
+
+int mv_seed_envs(mv_gym *g, const int32_t *device_seeds)
+{
+    if (seed_envs_check(g, device_seeds, "mv_seed_envs")) return -1;
+    if (g->hostEpisodes())
+        return fail("mv_seed_envs: this scenario's episode generators live on the host, which cannot read a device array without waiting for it: "
+                    "use mv_seed_envs_host (the device form serves TowerBuilding, whose generators live on the device)");
+    return seed_envs_tower(g, device_seeds, nullptr);
+}
+
+int mv_seed_envs_host(mv_gym *g, const int32_t *seeds)
+{
+    if (seed_envs_check(g, seeds, "mv_seed_envs_host")) return -1;
+    return g->hostEpisodes() ? seed_envs_host_fed(g, seeds) : seed_envs_tower(g, nullptr, seeds);
+}
+
+// Host-only test hook: drives an EpisodeFeeder without a device through a script and checks every episode it delivers against straight sequential
+// generation -- a model generator per env, re-seeded where the script re-seeds the env (Sokoban: its level list is carried across the re-seed, advanced by
+// the delivered episodes alone).  script: n_ops x {op, env, value}.  op 0: take env's next episode (wait_ready, compare, copy to out, recycle).  op 1: put
+// (env, value) on the pending re-seed list.  op 2: one reseed_envs call with the pending list.  out (may be null): one record of record_bytes per take, in
+// script order; used_out (may be null): the bytes of each the feeder reported as used.  Returns the number of takes; out == null && script == null: the
+// record size.
+int mv_debug_feeder_reseed_script(const char *scenario_name, int32_t num_envs, int32_t num_agents, int32_t threads, const int32_t *env_seeds,
+                                  const int32_t *script, int32_t n_ops, void *out, int64_t out_bytes, int32_t *used_out)
+{
+    int scenario = SCN_TOWER;
+    ObstacleConfig oc;
+    if (!scenario_name || !scenario_from_name(lower(scenario_name), scenario, oc) || scenario == SCN_TOWER)
+        return fail("mv_debug_feeder_reseed_script: a host-generated scenario");
+    const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE;
+    const size_t bytes = scenario == SCN_COLLECT ? sizeof(CollectBlob) : scenario == SCN_REARRANGE ? sizeof(RearrangeBlob) : scenario == SCN_SOKOBAN
+                         ? sizeof(SokobanBlob) : hex ? sizeof(HexBlob) : scenario == SCN_BOXAGONE ? sizeof(BoxAGoneBlob) : scenario == SCN_FOOTBALL
+                         ? sizeof(FootballBlob) : sizeof(EpisodeBlob);
+    if (!script && !out) return (int)bytes;
+    if (num_envs < 1 || num_agents < 1 || num_agents > MAX_AGENTS || !env_seeds || !script || n_ops < 0)
+        return fail("mv_debug_feeder_reseed_script: bad arguments");
+    std::vector<std::string> files;
+    if (scenario == SCN_SOKOBAN) {
+        files = find_boxoban_level_files();
+        if (files.empty()) return fail("mv_debug_feeder_reseed_script: no Boxoban levels found (BOXOBAN_LEVELS)");
+    }
+    const float len = 60.0f;
+    std::vector<uint8_t> slots((size_t)num_envs * bytes, 0), want(bytes);
+    std::vector<std::mt19937> rng((size_t)num_envs);
+    std::vector<SokobanLevels> levels(scenario == SCN_SOKOBAN ? (size_t)num_envs : 0);
+    std::vector<int> consumed((size_t)num_envs, 0);
+    std::vector<uint32_t> seeds((size_t)num_envs);
+    for (int i = 0; i < num_envs; ++i) {
+        if (env_seeds[i] < 0) return fail("mv_debug_feeder_reseed_script: a negative seed");
+        seeds[(size_t)i] = (uint32_t)env_seeds[i];
+        rng[(size_t)i].seed((unsigned long)seeds[(size_t)i]);
+    }
+    EpisodeFeeder feeder(scenario, oc, num_envs, num_agents, len, slots.data(), bytes, 0, threads, files);
+    feeder.reseed(seeds, std::vector<int>((size_t)num_envs, 1));
+    std::vector<int> pendEnvs, pendFirst;
+    std::vector<uint32_t> pendValues;
+    int takes = 0;
+    for (int k = 0; k < n_ops; ++k) {
+        const int op = script[3 * k], env = script[3 * k + 1], value = script[3 * k + 2];
+        if (op == 2) {
+            for (size_t j = 0; j < pendEnvs.size(); ++j) rng[(size_t)pendEnvs[j]].seed((unsigned long)pendValues[j]);
+            feeder.reseed_envs(pendEnvs, pendValues, pendFirst);
+            pendEnvs.clear(); pendValues.clear(); pendFirst.clear();
+            continue;
+        }
+        if (env < 0 || env >= num_envs || (op != 0 && op != 1) || (op == 1 && value < 0)) return fail("mv_debug_feeder_reseed_script: bad script entry");
+        if (op == 1) {
+            pendEnvs.push_back(env); pendValues.push_back((uint32_t)value); pendFirst.push_back(consumed[(size_t)env] + 1);
+            continue;
+        }
+        const int seq = consumed[(size_t)env] + 1;
+        size_t used = 0;
+        const uint8_t *got = feeder.wait_ready(env, seq, &used);
+        if (!got) return fail("mv_debug_feeder_reseed_script: episode not delivered");
+        if (used > bytes) return fail("mv_debug_feeder_reseed_script: used bytes out of range");
+        std::memset(want.data(), 0, bytes);
+        std::mt19937 &r = rng[(size_t)env];
+        bool same = false;
+        if (hex) {   // the box list comes last and only its used prefix is meaningful
+            HexBlob &b = *reinterpret_cast<HexBlob *>(want.data());
+            if (scenario == SCN_HEX_MEMORY) generate_hex_memory_episode(r, num_agents, len, b);
+            else generate_hex_explore_episode(r, num_agents, len, b);
+            b.seq = seq;
+            const HexBlob &a = *reinterpret_cast<const HexBlob *>(got);
+            same = used == offsetof(HexBlob, boxes) + sizeof(HexRec) * (size_t)b.num_boxes && !std::memcmp(&a, &b, offsetof(HexBlob, objs)) &&
+                   !std::memcmp(a.objs, b.objs, sizeof(HexRec) * (size_t)b.num_objs) && !std::memcmp(a.boxes, b.boxes, sizeof(HexRec) * (size_t)b.num_boxes);
+        } else if (scenario == SCN_COLLECT) {   // (its generator clears what it uses: the counts, then the used prefix of every list)
+            CollectBlob &b = *reinterpret_cast<CollectBlob *>(want.data());
+            generate_collect_episode(r, num_agents, len, b);
+            b.seq = seq;
+            const CollectBlob &a = *reinterpret_cast<const CollectBlob *>(got);
+            same = a.seq == b.seq && a.num_boxes == b.num_boxes && a.num_objects == b.num_objects && a.num_rewards == b.num_rewards &&
+                   a.num_positive == b.num_positive && a.layout_color == b.layout_color && a.wall_color == b.wall_color &&
+                   !std::memcmp(a.dim, b.dim, sizeof a.dim) && !std::memcmp(&a.episode_len, &b.episode_len, sizeof(float)) &&
+                   !std::memcmp(a.boxes, b.boxes, sizeof(LayoutBox) * (size_t)b.num_boxes) && !std::memcmp(a.heightmap, b.heightmap, sizeof a.heightmap) &&
+                   !std::memcmp(a.objects, b.objects, sizeof(MovableObject) * (size_t)b.num_objects) &&
+                   !std::memcmp(a.rewards, b.rewards, sizeof(MovableObject) * (size_t)b.num_rewards) &&
+                   !std::memcmp(a.spawn, b.spawn, sizeof a.spawn) && !std::memcmp(a.yaw_frand, b.yaw_frand, sizeof(float) * (size_t)num_agents);
+        } else {   // (these generators clear the whole record first: every byte compares)
+            if (scenario == SCN_REARRANGE) generate_rearrange_episode(r, num_agents, len, *reinterpret_cast<RearrangeBlob *>(want.data()));
+            else if (scenario == SCN_BOXAGONE) generate_boxagone_episode(r, num_agents, len, *reinterpret_cast<BoxAGoneBlob *>(want.data()));
+            else if (scenario == SCN_FOOTBALL) generate_football_episode(r, num_agents, len, *reinterpret_cast<FootballBlob *>(want.data()));
+            else if (scenario == SCN_EMPTY) generate_empty_episode(r, num_agents, len, *reinterpret_cast<EpisodeBlob *>(want.data()));
+            else if (scenario == SCN_SOKOBAN) {
+                if (!generate_sokoban_episode(r, levels[(size_t)env], files, num_agents, len, *reinterpret_cast<SokobanBlob *>(want.data())))
+                    return fail("mv_debug_feeder_reseed_script: unreadable level file");
+            } else generate_obstacles_episode(r, oc, num_agents, len, *reinterpret_cast<EpisodeBlob *>(want.data()));
+            *reinterpret_cast<int32_t *>(want.data()) = seq;
+            same = !std::memcmp(got, want.data(), bytes);
+        }
+        if (!same)
+            return fail("mv_debug_feeder_reseed_script: episode " + std::to_string(seq) + " of env " + std::to_string(env) +
+                        " differs from sequential generation (script entry " + std::to_string(k) + ")");
+        if (out) {
+            if ((int64_t)((size_t)(takes + 1) * bytes) > out_bytes) return fail("mv_debug_feeder_reseed_script: buffer too small");
+            std::memcpy(static_cast<uint8_t *>(out) + (size_t)takes * bytes, got, bytes);
+        }
+        if (used_out) used_out[takes] = (int32_t)used;
+        ++takes;
+        ++consumed[(size_t)env];
+        feeder.recycle(env, nullptr);
+    }
+    return takes;
+}
+
+}  // extern "C"

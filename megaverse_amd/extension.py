@@ -52,6 +52,8 @@ SYMBOLS = [
     ("mv_debug_env_record_pack_host", C.c_int, [_P, _I, _I, C.c_uint64, _I, _P, _P]),
     ("mv_debug_env_record_unpack_host", C.c_int, [_P, _I, _I, C.c_uint64, _I, _P, _P]),
     ("mv_reset_envs", C.c_int, [_P, _P, _I]), ("mv_reset_envs_host", C.c_int, [_P, _P, _I]), ("mv_debug_episode_log_cut_host", C.c_int, [_P, _I, _I, _P, _P]),
+    ("mv_seed_envs", C.c_int, [_P, _P]), ("mv_seed_envs_host", C.c_int, [_P, _P]),
+    ("mv_debug_feeder_reseed_script", C.c_int, [C.c_char_p, _I, _I, _I, _P, _P, _I, _P, C.c_int64, _P]),
     ("mv_set_output_ring", C.c_int, [_P, _I, _P, _P, _P]),
     ("mv_set_pass_overlap", C.c_int, [_P, _I]),
     ("mv_recommended_ticks_per_call", C.c_int, [_P]), ("mv_recommended_pass_overlap", C.c_int, [_P]), ("mv_arena_bytes", C.c_int64, [_P]),
@@ -404,6 +406,77 @@ def check_episode_budget(budget, num_envs):
     return np.ascontiguousarray(b, dtype=np.int32)
 
 
+def check_env_seeds(seeds, num_envs):
+    """the argument check of MegaverseGym.seed_envs (include/megaverse_hip.h: mv_seed_envs).  A contiguous torch.int32 CUDA tensor of shape (num_envs,) (or
+    anything with data_ptr()) -> 'device'.  Anything else -> a contiguous int32 numpy array, one word per env, negative = "leave this env alone": a dict
+    {env: seed}; a sequence or array of num_envs ints in which None, like a negative entry, leaves the env alone."""
+    n = int(num_envs)
+    if hasattr(seeds, 'data_ptr'):
+        contiguous = getattr(seeds, 'is_contiguous', None)
+        if tuple(getattr(seeds, 'shape', ())) != (n,) or str(getattr(seeds, 'dtype', None)) != 'torch.int32' \
+                or not getattr(seeds, 'is_cuda', False) or not (callable(contiguous) and contiguous()):
+            raise ValueError(f'seed_envs: a tensor of seeds must be a contiguous int32 CUDA tensor of shape ({n},), '
+                             f"got {getattr(seeds, 'dtype', None)} {tuple(getattr(seeds, 'shape', ()))} on {getattr(seeds, 'device', 'an unknown device')}")
+        return 'device'
+
+    def word(v, what):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f'seed_envs: {what} must be an int, got {v!r}')
+        if not -2 ** 31 <= int(v) < 2 ** 31:
+            raise ValueError(f'seed_envs: {what} = {v} is not an int32')
+        return int(v)
+
+    out = np.full(n, -1, np.int32)
+    if isinstance(seeds, dict):
+        for e, v in seeds.items():
+            e = word(e, 'an env index')
+            if not 0 <= e < n:
+                raise ValueError(f'seed_envs: env {e} is not within 0 .. {n - 1}')
+            if v is not None:
+                out[e] = word(v, f'the seed of env {e}')
+        return out
+    if isinstance(seeds, np.ndarray):
+        if seeds.shape != (n,) or (seeds.dtype.kind not in 'iu' and seeds.dtype != object):
+            raise ValueError(f'seed_envs: the seeds must be {n} ints (negative or None: leave the env alone), got {seeds.dtype} {seeds.shape}')
+        if seeds.dtype != object:
+            if seeds.size and (seeds.min() < -2 ** 31 or seeds.max() >= 2 ** 31):
+                raise ValueError('seed_envs: a seed is not an int32')
+            return np.ascontiguousarray(seeds, dtype=np.int32)
+    try:
+        items = list(seeds)
+    except TypeError:
+        raise ValueError(f'seed_envs: {n} ints, a dict {{env: seed}} or an int32 CUDA tensor, got {type(seeds).__name__}') from None
+    if len(items) != n:
+        raise ValueError(f'seed_envs: the seeds must be {n} ints (negative or None: leave the env alone), got {len(items)}')
+    for e, v in enumerate(items):
+        if v is not None:
+            out[e] = word(v, f'the seed of env {e}')
+    return out
+
+
+def debug_feeder_reseed_script(scenario, num_agents, threads, env_seeds, script):
+    """mv_debug_feeder_reseed_script: the episode feeder driven without a device.  env_seeds: the envs' initial seeds; script: a list of ('take', env),
+    ('seed', env, value) and ('commit',) -- a commit is ONE reseed_envs call with the seeds listed since the last.  Every delivered episode is compared
+    inside with straight sequential generation (RuntimeError on a difference).  -> [(env, the record's bytes, the bytes the feeder reports as used)] per take"""
+    lib = load_library()
+    seeds = np.ascontiguousarray(env_seeds, np.int32).reshape(-1)
+    ops = np.zeros((len(script), 3), np.int32)
+    for k, op in enumerate(script):
+        ops[k] = {'take': (0, op[1] if len(op) > 1 else 0, 0), 'seed': (1, op[1] if len(op) > 1 else 0, op[2] if len(op) > 2 else 0), 'commit': (2, 0, 0)}[op[0]]
+    takes = int((ops[:, 0] == 0).sum())
+    size = lib.mv_debug_feeder_reseed_script(scenario.encode(), 1, 1, 1, None, None, 0, None, 0, None)
+    if size < 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    out = np.zeros((max(1, takes), size), np.uint8)
+    used = np.zeros(max(1, takes), np.int32)
+    rc = lib.mv_debug_feeder_reseed_script(scenario.encode(), seeds.size, int(num_agents), int(threads), seeds.ctypes.data, ops.ctypes.data, len(script),
+                                           out.ctypes.data, out.nbytes, used.ctypes.data)
+    if rc < 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    envs = ops[ops[:, 0] == 0, 1]
+    return [(int(envs[i]), out[i].tobytes(), int(used[i])) for i in range(rc)]
+
+
 # include/megaverse_hip.h: MV_RENDER_EVERY / MV_RENDER_LAST / MV_RENDER_NONE, by the names step_n(render=...) takes
 RENDER_MODES = {"every": 0, "last": 1, "none": 2}
 
@@ -505,9 +578,11 @@ class MegaverseGym:
             raise RuntimeError("mv_create: " + self._lib.mv_last_error().decode())
         self._g = handle
         self.w, self.h, self.num_envs, self.num_agents_per_env, self.device = int(w), int(h), int(num_envs), int(num_agents_per_env), int(device)
+        self.scenario = str(scenario)
         self.render_w, self.render_h = 768, 432
         self._fork_held = None   # fork_envs: the caller's device map, kept until the next step has been enqueued
         self._reset_held = None  # reset_envs: the caller's device mask, likewise
+        self._seed_held = []     # seed_envs: the caller's device seeds, likewise (calls may follow each other without a step: every tensor is kept)
         self._step_mask_held = None  # set_step_mask: the caller's device mask, kept until it is replaced or detached
         self._draw_mask_held = None  # set_draw_mask: the caller's device mask, kept until it is replaced or detached
         self._state_obs = None       # set_state_obs: the attached tensor
@@ -550,6 +625,7 @@ class MegaverseGym:
         self._ckw(self._lib.mv_step(self._g))
         self._fork_held = self._reset_held = self._budget_held = None
         self._store_held = []
+        self._seed_held = []
 
     def is_done(self, env_idx):
         return bool(self._ck(self._lib.mv_is_done(self._g, int(env_idx))))
@@ -628,6 +704,7 @@ class MegaverseGym:
         self._ckw(self._lib.mv_step_no_render(self._g))
         self._fork_held = self._reset_held = self._budget_held = None
         self._store_held = []
+        self._seed_held = []
 
     POLICIES = {"none": 0, "multidiscrete": 1, "single-bit": 2, "sequence": 3}
 
@@ -642,6 +719,7 @@ class MegaverseGym:
         self._ckw(self._lib.mv_step_n(*args) if mode == 0 else self._lib.mv_step_n_render(*args, mode))
         self._fork_held = self._reset_held = self._budget_held = None
         self._store_held = []
+        self._seed_held = []
 
     def fork_envs(self, src_of):
         """Env forks (include/megaverse_hip.h: mv_fork_envs): src_of[d] = s makes env d leave its running episode and continue env s's from s's current
@@ -729,6 +807,24 @@ class MegaverseGym:
             self._reset_held = mask
         else:
             self._ckw(self._lib.mv_reset_envs_host(self._g, m.ctypes.data, int(bool(render))))
+
+    def episodes_drawn_on_device(self):
+        """True for TowerBuilding, whose episode generators live on the device (the gyms that take seed_envs' device form); every other scenario's live
+        in the host's episode feeder"""
+        return self.scenario.casefold() == "towerbuilding"
+
+    def seed_envs(self, seeds):
+        """Level seeds (include/megaverse_hip.h: mv_seed_envs): env e restarts its episode stream from seeds[e] -- Env::seed, the value seed() hands an env
+        from its master stream (megaverse_amd.distributed.env_seeds lists them).  Its running episode goes on; its NEXT reset -- an auto-reset, reset(),
+        reset_envs -- plays the first episode of the new stream.  seeds: num_envs ints (negative or None: the env is left alone), a dict {env: seed}, or
+        a contiguous int32 CUDA tensor of shape (num_envs,), which is read in place in the order of the gym's stream without a host synchronisation
+        (TowerBuilding only: every other scenario's generators live on the host and take the host forms, which wait for the device)."""
+        m = check_env_seeds(seeds, self.num_envs)
+        if isinstance(m, str):
+            self._ck(self._lib.mv_seed_envs(self._g, _P(int(seeds.data_ptr()))))
+            self._seed_held.append(seeds)
+        else:
+            self._ckw(self._lib.mv_seed_envs_host(self._g, m.ctypes.data))
 
     STEP_MASK_FORMS = ("none", "device", "host")
 

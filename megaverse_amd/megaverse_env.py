@@ -330,6 +330,33 @@ class MegaverseEnv:
         m[ids] = True
         self.env.reset_envs(m, render)
 
+    def _seed_words(self, env_ids, seeds, who):
+        ids = np.asarray(list(env_ids), dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= self.num_envs):
+            raise ValueError(f'{who}: env_ids must be within 0 .. {self.num_envs - 1}')
+        if isinstance(seeds, (int, np.integer)) and not isinstance(seeds, (bool, np.bool_)):
+            seeds = [int(seeds)] * ids.size
+        vals = np.asarray(list(seeds)).reshape(-1)
+        if vals.shape != ids.shape or (vals.size and vals.dtype.kind not in 'iu') or (vals.size and (vals.min() < 0 or vals.max() >= 2 ** 31)):
+            raise ValueError(f'{who}: seeds must be one non-negative int32 per env of env_ids (or one int for all of them)')
+        return {int(e): int(v) for e, v in zip(ids, vals)}, ids
+
+    def seed_envs(self, env_ids, seeds):
+        """the envs of env_ids restart their level stream from seeds (one per env, or one int for all of them) -- MegaverseGym.seed_envs with the words
+        built here.  Their running episodes go on; their next reset plays the first level of the new stream.  An env named twice takes its last seed."""
+        words, _ = self._seed_words(env_ids, seeds, 'seed_envs')
+        self.env.seed_envs(words)
+
+    def start_levels(self, env_ids, seeds, render=True):
+        """the envs of env_ids start level seeds[k] NOW: seed_envs, then reset_envs on the same envs.  Two envs given the same seed play the same level
+        sequence; calling this again with the same seeds replays the levels.  What level replay, a held-out level set and "every candidate gets the same
+        fresh level" need.  With render the observations of those envs are redrawn; their rewards and dones read zero."""
+        words, ids = self._seed_words(env_ids, seeds, 'start_levels')
+        self.env.seed_envs(words)
+        m = np.zeros(self.num_envs, np.bool_)
+        m[ids] = True
+        self.env.reset_envs(m, render)
+
     def set_step_mask(self, mask):
         """Step masks (MegaverseGym.set_step_mask): mask[e] true: env e steps; false: env e is frozen -- step, step_batched, step_device and step_sequence
         leave its state alone, report reward 0 and done 0 for it and discard its actions, and its observation stays its current view -- until the mask is

@@ -17,7 +17,7 @@ import os
 
 import numpy as np
 
-from .extension import EPISODE_RECORD_DTYPE, GymGroup, MegaverseGym
+from .extension import EPISODE_RECORD_DTYPE, GymGroup, MegaverseGym, check_env_seeds
 
 # MultiTaskGym.drain_episode_log: a sub-gym's record (extension.EPISODE_RECORD_DTYPE) + the task it came from; agent in the batch's numbering
 MULTITASK_EPISODE_DTYPE = np.dtype([("task", "<i4")] + [(n, EPISODE_RECORD_DTYPE.fields[n][0]) for n in EPISODE_RECORD_DTYPE.names])
@@ -259,6 +259,24 @@ class MultiTaskGym:
         for g, part in zip(self.gyms, parts):
             g.reset_envs(part, render)
 
+    def seed_envs(self, seeds):
+        """Level seeds (MegaverseGym.seed_envs; members of a group are served like reset_envs'): `seeds` in the batch's global numbering -- num_envs ints
+        (negative or None: leave the env alone), a dict {env: seed}, or an int32 CUDA tensor (TowerBuilding members only) -- dealt to the sub-gyms by
+        locate's rule.  The parts of a tensor are copies made on torch's current stream, the gyms'."""
+        S = len(self.gyms)
+        if hasattr(seeds, "data_ptr"):
+            check_env_seeds(seeds, self.num_envs)
+            host_fed = [g.scenario for g in self.gyms if not g.episodes_drawn_on_device()]
+            if host_fed:   # (refused before the first member is touched)
+                raise RuntimeError(f"MultiTaskGym.seed_envs: a tensor takes mv_seed_envs' device form, which {', '.join(host_fed)} refuse (their episode "
+                                   "generators live on the host): pass the seeds as a numpy array, a sequence or a dict (mv_seed_envs_host)")
+            parts = [seeds.reshape(self.per_task, S)[:, k].contiguous() for k in range(S)]
+        else:
+            m = check_env_seeds(seeds, self.num_envs)
+            parts = [np.ascontiguousarray(m.reshape(self.per_task, S)[:, k]) for k in range(S)]
+        for g, part in zip(self.gyms, parts):
+            g.seed_envs(part)
+
     def set_actions(self, env_idx, agent_idx, actions):
         g, j = self.locate(env_idx)
         g.set_actions(j, agent_idx, actions)
@@ -287,6 +305,12 @@ class MultiTaskGym:
                 self.step()
             return
         self._ensure_group().step(k, True, policy, seed, first_step_index)
+        self._release_seeds()
+
+    def _release_seeds(self):
+        """a stepping call has been enqueued: the members' device seeds (seed_envs with a tensor: per-member copies) have been read in stream order"""
+        for g in self.gyms:
+            g._seed_held = []
 
     def step(self):
         import ctypes as C
@@ -294,6 +318,7 @@ class MultiTaskGym:
             seed, idx = self._sample if self._sample else (0, 0)
             self._ensure_group().step(1, True, "multidiscrete" if self._sample else "none", seed, idx)
             self._sample = None
+            self._release_seeds()
             return
         if self._handles is None:
             self._handles = (C.c_void_p * len(self.gyms))(*[g._g for g in self.gyms])
@@ -301,6 +326,7 @@ class MultiTaskGym:
         seed, idx = self._sample if self._sample else (0, 0)
         rc = lib.mv_step_many(self._handles, len(self.gyms), 1, 1 if self._sample else 0, seed, idx)
         self._sample = None   # (every sub-gym was stepped, whatever one of them reports: nothing to retry)
+        self._release_seeds()
         if rc < 0:
             raise RuntimeError(lib.mv_last_error().decode())
         if rc > 0:

@@ -198,6 +198,31 @@ public:
         check(mv_halted_count(gym_, &n));
         return n;
     }
+    // level seeds (mv_seed_envs_host): env e restarts its episode stream from seeds[e] (Env::seed); a negative entry or None leaves the env alone; a dict
+    // {env: seed} names the envs it seeds
+    void seed_envs(const py::object &seeds)
+    {
+        std::vector<int32_t> words((size_t)envs_, -1);
+        auto word = [](const py::handle &v) {
+            if (py::isinstance<py::bool_>(v) || !py::isinstance<py::int_>(v)) throw std::runtime_error("seed_envs: a seed is an int");
+            return v.cast<int32_t>();
+        };
+        if (py::isinstance<py::dict>(seeds)) {
+            for (const auto &kv : seeds.cast<py::dict>()) {
+                const int e = word(kv.first);
+                if (e < 0 || e >= envs_) throw std::runtime_error("seed_envs: an env index out of range");
+                if (!kv.second.is_none()) words[(size_t)e] = word(kv.second);
+            }
+        } else {
+            const py::sequence seq = seeds.cast<py::sequence>();
+            if ((int)py::len(seq) != envs_) throw std::runtime_error("seed_envs: one value per env");
+            for (int e = 0; e < envs_; ++e) {
+                const py::object v = seq[(size_t)e];
+                if (!v.is_none()) words[(size_t)e] = word(v);
+            }
+        }
+        check_or_warn(mv_seed_envs_host(gym_, words.data()));
+    }
     std::uintptr_t episode_budget_device_ptr() const { return reinterpret_cast<std::uintptr_t>(mv_episode_budget_device_ptr(gym_)); }
     std::uintptr_t halted_count_device_ptr() const { return reinterpret_cast<std::uintptr_t>(mv_halted_count_device_ptr(gym_)); }
 
@@ -249,5 +274,6 @@ PYBIND11_MODULE(megaverse, m)
         .def("has_episode_budget", &Gym::has_episode_budget)
         .def("halted_count", &Gym::halted_count)
         .def("episode_budget_device_ptr", &Gym::episode_budget_device_ptr)
-        .def("halted_count_device_ptr", &Gym::halted_count_device_ptr);
+        .def("halted_count_device_ptr", &Gym::halted_count_device_ptr)
+        .def("seed_envs", &Gym::seed_envs);
 }
