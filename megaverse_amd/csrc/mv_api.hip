@@ -104,6 +104,20 @@ int check(mv_gym *g)
     return 0;
 }
 
+int attach_check(mv_gym *g, const char *who, const char *noun)
+{
+    if (check(g)) { g_err = std::string(who) + ": " + g_err; return -1; }
+    if (g->inGroup) return fail(std::string(who) + ": this gym belongs to an mv_group, whose union launches read no " + noun);
+    return 0;
+}
+
+int getter_check(const mv_gym *g, const char *who)
+{
+    if (!g) return fail(std::string(who) + ": null gym handle");
+    if (g->closed) return fail(std::string(who) + ": gym is closed");
+    return 0;
+}
+
 // Where a tick's public outputs go: the observation slab and the reward / done arrays -- or, with mv_set_output_ring, entry (tick % count)
 // of the caller's rings.  true_objective is state (only a finishing env records it, vector_env.cpp:96-101): never ringed.
 OutPtrs outputs_of(const mv_gym *g, unsigned long long tick)
@@ -761,21 +775,17 @@ int mv_close(mv_gym *g)
         (void)hipFree(gv.dbg);
     }
     episode_log_free(g);
-    if (g->dForkMap) (void)hipFree(g->dForkMap);
-    if (g->hForkMap) (void)hipHostFree(g->hForkMap);
-    for (hipEvent_t &e : g->forkMapCopied) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    g->dForkMap = g->hForkMap = nullptr; g->forkTable = fork::Table{};
+    g->forkMapPair.release();
+    g->forkTable = fork::Table{};
     if (g->resampleArena) (void)hipFree(g->resampleArena);
     g->resampleArena = nullptr; g->resampleBytes = 0;
-    if (g->dResetMask) (void)hipFree(g->dResetMask);
-    if (g->hResetMask) (void)hipHostFree(g->hResetMask);
-    for (hipEvent_t &e : g->resetMaskCopied) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    g->dResetMask = g->hResetMask = nullptr;
-    step_mask_free(g);
-    draw_mask_free(g);
+    g->resetMaskPair.release();
+    if (g->resetApplied) (void)hipFree(g->resetApplied);
+    g->resetApplied = nullptr;
+    g->seedEnvsPair.release();
+    env_masks_free(g);
     state_obs_free(g);
     episode_budget_free(g);
-    seed_envs_free(g);
     if (g->arena) (void)hipFree(g->arena);
     if (g->hiresObs) (void)hipFree(g->hiresObs);
     if (g->hBlobs) (void)(g->blobsOnDevice ? hipFree(g->hBlobs) : hipHostFree(g->hBlobs));
@@ -894,14 +904,7 @@ int mv_seed(mv_gym *g, int32_t seed)
         if (rel >= 0 && rel % g->envStride == 0 && rel / g->envStride < g->N) seeds[rel / g->envStride] = (uint32_t)noise;
     }
     if (g->hostEpisodes()) {   // Env::seed (env.cpp:52-55) on the host-side episode generators
-        HIP_TRY(hipStreamSynchronize(g->simStream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        HIP_TRY(hipStreamSynchronize(g->copyStream));
-        // the current counts, not the last periodic read-back
-        HIP_TRY(hipMemcpy(g->hStatus, g->dStatus, (size_t)(g->N + 2) * sizeof(int), hipMemcpyDeviceToHost));
-        g->statusPending = false;
-        g->pendingAge = 0;
-        g->stepsSinceStatus = 0;
+        if (sync_status_words(g)) return -1;
         std::vector<int> first(g->N);
         for (int i = 0; i < g->N; ++i) {
             // the episodes resident on the device were drawn from the old stream: the ring is wiped (sequence number 0 matches
@@ -944,7 +947,7 @@ int mvapi::render_frames(mv_gym *g)
     if (take_hist(g, g->stream, true)) return -1;
     g->layoutFixed = true;
     GymView v = view(g, g->parity);
-    v.draw_mask = g->drawMask;   // (mv_set_draw_mask: also the frame behind mv_reset and mv_reset_envs(render = 1), which come through here)
+    v.draw_mask = g->drawMask.live;   // (mv_set_draw_mask: also the frame behind mv_reset and mv_reset_envs(render = 1), which come through here)
     if (launch_raster(v, last_outputs(g).obs, g->w, g->h, g->stream, nullptr, g->fastPixels))
         return fail("mv_render: observation size above 1024x1024");
     HIP_TRY(hipGetLastError());
@@ -1118,6 +1121,7 @@ int refill_episodes(mv_gym *g, int k)
     const int N = g->N;
     const bool starved = (g->hStatus[N + 1] & ST_STARVED) != 0;
     if (starved && g->hostEpisodes()) {   // recover: take the current counts and upload synchronously below
+        // (not sync_status_words: the caller's stream is left alone where the simulation ran on its own, the flag word is kept, the bookkeeping stays)
         HIP_TRY(hipStreamSynchronize(g->simStream));
         // (closed-loop / unpipelined steps run on the caller's stream, which may be a non-blocking one)
         if (!g->simOnOwnStream) HIP_TRY(hipStreamSynchronize(g->stream));
@@ -1135,6 +1139,19 @@ int refill_episodes(mv_gym *g, int k)
         g->refillForce = false;
     }
     return check_status_flags(g) < 0 ? -1 : 0;
+}
+
+// the current consumed counts, not the last periodic read-back (mv_seed, mv_reset, the host forms of mv_reset_envs and mv_seed_envs on host-fed gyms)
+int sync_status_words(mv_gym *g)
+{
+    HIP_TRY(hipStreamSynchronize(g->simStream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    HIP_TRY(hipStreamSynchronize(g->copyStream));
+    HIP_TRY(hipMemcpy(g->hStatus, g->dStatus, (size_t)(g->N + 2) * sizeof(int), hipMemcpyDeviceToHost));
+    g->statusPending = false;
+    g->pendingAge = 0;
+    g->stepsSinceStatus = 0;
+    return 0;
 }
 
 // after a step / reset kernel: read the status words back without touching the step path
@@ -1177,13 +1194,7 @@ int mv_reset(mv_gym *g)
     if (g->hostEpisodes()) {
         // the periodic status read-back may be up to 15 ticks old: an env that auto-reset since then has consumed its
         // resident episode without the host knowing -- take the current counts before deciding what to upload
-        HIP_TRY(hipStreamSynchronize(g->simStream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        HIP_TRY(hipStreamSynchronize(g->copyStream));
-        HIP_TRY(hipMemcpy(g->hStatus, g->dStatus, (size_t)(g->N + 2) * sizeof(int), hipMemcpyDeviceToHost));
-        g->statusPending = false;
-        g->pendingAge = 0;
-        g->stepsSinceStatus = 0;
+        if (sync_status_words(g)) return -1;
         g->refillForce = true;
         if (refill_episodes(g, 1) < 0) return -1;       // every env has an unconsumed episode resident
         if (g->lastUpload) HIP_TRY(hipStreamWaitEvent(g->stream, g->lastUpload, 0));

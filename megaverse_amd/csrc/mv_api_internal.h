@@ -5,12 +5,13 @@
 //   mv_fork.hip       env forks: the gather-copy kernel and its entry points; the entry points of env resampling
 //   mv_resample.hip   env resampling: the two kernels of the staged copy
 //   mv_reset_envs.hip masked env resets: the host protocol around the reset_masked kernels (mv_step_kernels.h)
-//   mv_seed_envs.hip  level seeds: Env::seed for chosen envs -- the staging of the seed words, the host-fed gyms' protocol, the feeder's host-only hook
+//   mv_seed_envs.hip  level seeds: Env::seed for chosen envs -- the two launch protocols (device-drawn, host-fed), the feeder's host-only hook
 //   mv_env_store.hip  env stores: the save / load kernels, their entry points and host-only hooks
-//   mv_step_mask.hip  step masks: attaching and detaching the bytes that freeze envs (mv_step_kernels.h: frozen_tick)
-//   mv_draw_mask.hip  draw masks: attaching and detaching the bytes that leave envs' frames out of the observation passes (mv_frame.h: frame_skip)
+//   mv_env_masks.hip  step masks and draw masks: attaching and detaching the bytes that freeze envs (mv_step_kernels.h: frozen_tick) and the bytes that leave
+//                     envs' frames out of the observation passes (mv_frame.h: frame_skip)
 //   mv_state_obs.hip  state observations: attaching the caller's buffer, the staging rows, their publication and refresh (mv_state_obs.h: the record)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
+// mv_staging.h holds the two ways the host forms' values reach the device (StagingPool, StagingPair).
 // The C ABI itself is include/megaverse_hip.h; nothing here is exported under a C name.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -82,6 +83,20 @@ using namespace mvapi;
         hipError_t e_ = (expr);                                                                        \
         if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));          \
     } while (0)
+
+#include "mv_staging.h"
+
+namespace mvapi {
+// An attached per-env byte mask (mv_env_masks.hip: step masks, draw masks).  live: the [N] bytes the kernels read, null: no mask.  Form 1: the caller's
+// buffer.  Form 2: owned, the gym's, allocated at the host form's first use and counted in mv_arena_bytes; its bytes travel through the pool.
+struct EnvMask {
+    const uint8_t *live = nullptr;
+    int form = 0;
+    uint8_t *owned = nullptr;
+    size_t ownedBytes = 0;
+    StagingPool pool;
+};
+}  // namespace mvapi
 
 static_assert(PIPE_GROUPS == 3, "userMark events are created one by one in mv_create");
 struct mv_gym;
@@ -219,12 +234,10 @@ struct mv_gym {
     int32_t *logLen = nullptr;
     elog::Record *logRecords = nullptr;
     uint32_t ticksSinceReset = 0;                // ticks stepped since the last mv_reset: a record's end_tick
-    // mv_fork_envs: the per-env arrays that make up an env's episode state (filled by mv_create where it carves the arena; mv_fork.h), the host form's copy of
-    // its map (device + pinned staging, allocated at its first use)
+    // mv_fork_envs: the per-env arrays that make up an env's episode state (filled by mv_create where it carves the arena; mv_fork.h), the host forms' way to
+    // the device for their [N] map words (also mv_resample_envs_host's and the env stores')
     fork::Table forkTable{};
-    int32_t *dForkMap = nullptr, *hForkMap = nullptr;   // [2][N] each
-    hipEvent_t forkMapCopied[2] = {nullptr, nullptr};
-    unsigned long long forkMapUses = 0;
+    StagingPair forkMapPair;
     // mv_resample_envs: the staging arena (fork::Staging: a second slice per env of every array of the table, the episode log's included, and one plan byte
     // per env), allocated at the first call and counted in mv_arena_bytes from then on
     uint8_t *resampleArena = nullptr;
@@ -234,31 +247,16 @@ struct mv_gym {
     // "the next stepping call waits for the status words" (refill_episodes): something only a kernel saw has to be reported by that call -- a fork's device map
     // may have held invalid entries (ST_FORK), a masked reset from a device mask may have found a host-fed env without a resident episode (ST_STARVED)
     bool statusReportDue = false;
-    // mv_reset_envs: [3][N] bytes of device memory -- the host form's copy of its mask, double buffered, and `applied` (which flagged envs took an episode) --
-    // and the pinned staging of the two mask halves, allocated at the first use
-    uint8_t *dResetMask = nullptr, *hResetMask = nullptr;
-    hipEvent_t resetMaskCopied[2] = {nullptr, nullptr};
-    unsigned long long resetMaskUses = 0;
-    // mv_seed_envs_host: [2][N] seed words of device memory and their pinned staging, double buffered like the reset mask's, allocated at the first use
-    int32_t *dSeedEnvs = nullptr, *hSeedEnvs = nullptr;
-    hipEvent_t seedEnvsCopied[2] = {nullptr, nullptr};
-    unsigned long long seedEnvsUses = 0;
-    // mv_set_step_mask: the [N] bytes the step kernels read (GymView::step_mask through the stepping calls' views), null: no mask.  Form 1: the caller's
-    // buffer.  Form 2: dStepMask, gym-owned, allocated at the host form's first use and counted in mv_arena_bytes; its bytes travel through pinned staging
-    // buffers, each free again once the event behind its copy has completed (looked at with hipEventQuery: the call never waits on the host).
-    const uint8_t *stepMask = nullptr;
-    int stepMaskForm = 0;
-    uint8_t *dStepMask = nullptr;
-    size_t stepMaskBytes = 0;
-    struct MaskStaging { uint8_t *host; hipEvent_t copied; };
-    std::vector<MaskStaging> stepMaskStaging;
-    // mv_set_draw_mask: the [N] bytes the frame setups read (GymView::draw_mask through the views of the stepping calls and of mv_render), null: no mask.  The
-    // forms, the gym-owned buffer and the staging are the step mask's.
-    const uint8_t *drawMask = nullptr;
-    int drawMaskForm = 0;
-    uint8_t *dDrawMask = nullptr;
-    size_t drawMaskBytes = 0;
-    std::vector<MaskStaging> drawMaskStaging;
+    // mv_reset_envs: the host form's [N] mask bytes on their way to the device, and `applied` [N] (which flagged envs took an episode: device bytes of both
+    // forms, allocated at the first use)
+    StagingPair resetMaskPair;
+    uint8_t *resetApplied = nullptr;
+    // mv_seed_envs_host: its [N] seed words on their way to the device
+    StagingPair seedEnvsPair;
+    // mv_set_step_mask: the bytes the step kernels read (GymView::step_mask through the stepping calls' views)
+    EnvMask stepMask;
+    // mv_set_draw_mask: the bytes the frame setups read (GymView::draw_mask through the views of the stepping calls and of mv_render)
+    EnvMask drawMask;
     // mv_set_state_obs: the caller's [stateEntries][N*A][16] float32 buffer (null: off; stateEntries: the output ring's count when it was attached, or 1) and
     // the gym's staging rows [slots][N*A][16], allocated at the first attach and kept until mv_close -- not part of the arena, not counted in mv_arena_bytes.
     // While attached, gvp[q].state_obs points at slot q's rows: the stepping calls' views carry it to the MASKED step kernels.
@@ -266,14 +264,13 @@ struct mv_gym {
     int stateEntries = 0;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
     // budgetLeft [N], what the step kernels read and write (GymView::budget, through the stepping calls' views, while budgetOn); budgetHalted, the count of
-    // zeros in it; budgetMirror [N], the episode log's own copy, advanced by the log's update tick by tick.  The host form's values travel through pinned
-    // staging buffers like the step mask's.
+    // zeros in it; budgetMirror [N], the episode log's own copy, advanced by the log's update tick by tick.  The host form's values travel through a pool of
+    // N + 1 words: the budgets and the halted count.
     int32_t *budgetLeft = nullptr, *budgetMirror = nullptr;
     uint32_t *budgetHalted = nullptr;
     bool budgetOn = false;
     size_t budgetBytes = 0;
-    struct BudgetStaging { int32_t *host; hipEvent_t copied; };
-    std::vector<BudgetStaging> budgetStaging;
+    StagingPool budgetPool;
     // in-stream profiling
     std::vector<hipEvent_t> profEvents;          // 5 per profiled tick: [0] [1] around the step kernel (its stream), [2] [3] [4] before the
                                                  // observation pass, between frame sort and raster, after the raster (the caller's stream)
@@ -287,6 +284,9 @@ namespace mvapi {
 struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; };
 std::string lower(const char *s);
 int check(mv_gym *g);
+// what every form of a persistent attachment refuses: no gym, a closed one, a member of a group (the union launches read no <noun>)
+int attach_check(mv_gym *g, const char *who, const char *noun);
+int getter_check(const mv_gym *g, const char *who);   // the mv_get_* form getters: no gym, a closed one
 OutPtrs outputs_of(const mv_gym *g, unsigned long long tick);
 OutPtrs last_outputs(const mv_gym *g);   // of the last tick (reset / render / getters)
 int refresh_mirrors(mv_gym *g);
@@ -304,16 +304,16 @@ int check_status_flags(mv_gym *g);
 int finish_with_warning(mv_gym *g);
 int refill_episodes(mv_gym *g, int k);   // k: the ticks of the stepping call that is about to be enqueued
 int read_back_status(mv_gym *g, hipEvent_t after);   // after: an event recorded behind the kernel whose status words are wanted
+// the current consumed counts, not the last periodic read-back: a host wait for everything enqueued, the status words copied, no read-back pending
+int sync_status_words(mv_gym *g);
 int flush_device_actions(mv_gym *g);
 void group_detach(mv_gym *g);   // (mv_api_step.hip)
 // the episode log of g brought up to the k ticks just enqueued: views[j * stride] is tick j's view (its staged outputs); on the caller's stream (mv_episode_log.hip)
 int episode_log_update(mv_gym *g, const GymView *views, int stride, int k);
 int episode_log_reset(mv_gym *g);   // mv_reset: accumulators to zero, the records stay
 void episode_log_free(mv_gym *g);   // mv_close
-void step_mask_free(mv_gym *g);     // mv_close (mv_step_mask.hip)
-void draw_mask_free(mv_gym *g);     // mv_close (mv_draw_mask.hip)
+void env_masks_free(mv_gym *g);     // mv_close (mv_env_masks.hip)
 void episode_budget_free(mv_gym *g);   // mv_close (mv_episode_budget.hip)
-void seed_envs_free(mv_gym *g);        // mv_close (mv_seed_envs.hip)
 // mv_state_obs.hip: tick `tick`'s entry of the caller's buffer (the entry outputs_of gives its rewards); the staged rows of the k ticks in slots q0 .. q0 + k - 1
 // -> dst[j], one launch on the caller's stream; the last tick's entry gathered from the current state (mask: device bytes [N], only the flagged envs' rows;
 // null: every row; nothing attached: no launch), on the caller's stream behind sim_join
@@ -323,10 +323,8 @@ int state_obs_refresh(mv_gym *g, const uint8_t *device_mask);
 void state_obs_free(mv_gym *g);        // mv_close
 int render_frames(mv_gym *g);          // mv_render without the state rows' refresh (mv_api.hip; mv_reset_envs refreshes the flagged envs' rows only)
 int episode_budget_seed_mirror(mv_gym *g);   // mv_set_episode_log: the log's mirror from the live array (mv_episode_budget.hip)
-// mv_fork.hip, shared with mv_env_store.hip: what every fork / resample / env-store form refuses (what: "forks", "env stores": for the text about groups), and
-// a host map's way to the device through the pinned double buffer
+// mv_fork.hip, shared with mv_env_store.hip: what every fork / resample / env-store form refuses (what: "forks", "env stores": for the text about groups)
 int fork_check(mv_gym *g, const void *map, const char *who, const char *what = "forks");
-int stage_fork_map(mv_gym *g, const int32_t *host_map, hipStream_t s, const int32_t **device_map);
 // mv_env_store.hip: the layout word of g's records (mv_create, once the table and the parameters are known)
 uint64_t env_record_layout_word(const mv_gym *g, const std::string &scenario_name, const mv_config *cfg);
 }  // namespace mvapi

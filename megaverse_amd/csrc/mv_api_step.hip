@@ -164,8 +164,8 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
             o = outputs_of(g, g->ringTick++);
             GymView &v = views[(size_t)j * n + i];
             v = view(g, g->parity, staged ? nullptr : &o);
-            v.step_mask = g->stepMask;   // (mv_set_step_mask; a group's members have none)
-            v.draw_mask = g->drawMask;   // (mv_set_draw_mask; likewise)
+            v.step_mask = g->stepMask.live;   // (mv_set_step_mask; a group's members have none)
+            v.draw_mask = g->drawMask.live;   // (mv_set_draw_mask; likewise)
             if (g->budgetOn) { v.budget = g->budgetLeft; v.halted = g->budgetHalted; }   // (mv_set_episode_budget; likewise)
             if (policy == POLICY_SEQUENCE)
                 v.md_actions = g->actRing + (size_t)action_ring_entry(first_index, j, (uint32_t)g->actRingCount) * ((size_t)g->N * g->A * 6);
@@ -503,8 +503,8 @@ int mv_group_create(mv_gym *const *gyms, int32_t n, mv_group **out)
         mv_gym *g = gyms[i];
         if (check(g)) return -1;
         if (g->inGroup) return fail("mv_group_create: a gym already belongs to a group");
-        if (g->stepMask) return fail("mv_group_create: a gym has a step mask attached (mv_set_step_mask): the union launches read none; detach it first");
-        if (g->drawMask) return fail("mv_group_create: a gym has a draw mask attached (mv_set_draw_mask): the union launches read none; detach it first");
+        if (g->stepMask.live) return fail("mv_group_create: a gym has a step mask attached (mv_set_step_mask): the union launches read none; detach it first");
+        if (g->drawMask.live) return fail("mv_group_create: a gym has a draw mask attached (mv_set_draw_mask): the union launches read none; detach it first");
         if (g->budgetOn) return fail("mv_group_create: a gym has an episode budget attached (mv_set_episode_budget): the union launches read none; detach it first");
         if (g->stateObs) return fail("mv_group_create: a gym has state observations attached (mv_set_state_obs): the union launches write none; detach them first");
         for (int j = 0; j < i; ++j) if (gyms[j] == g) return fail("mv_group_create: the same gym twice");
@@ -617,7 +617,7 @@ int mv_recommended_pass_overlap(const mv_gym *g)
     return 1;
 }
 
-int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMaskBytes + g->drawMaskBytes + g->budgetBytes) : 0; }
+int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMask.ownedBytes + g->drawMask.ownedBytes + g->budgetBytes) : 0; }
 
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index)
 {   // several gyms of one job (MultiTaskGym: one per scenario, one stream each) stepped by one call: at eight sub-gyms the per-call cost of
@@ -627,10 +627,10 @@ int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample,
     int rc = 0;
     std::string msgs;
     for (int i = 0; i < n; ++i)   // (refused before any gym is stepped: the sub-gyms never get out of step with each other)
-        if (gyms[i] && !gyms[i]->closed && gyms[i]->stepMask)
+        if (gyms[i] && !gyms[i]->closed && gyms[i]->stepMask.live)
             return fail("mv_step_many: gym " + std::to_string(i) + " has a step mask attached (mv_set_step_mask): step it on its own, or detach the mask first");
     for (int i = 0; i < n; ++i)
-        if (gyms[i] && !gyms[i]->closed && gyms[i]->drawMask)
+        if (gyms[i] && !gyms[i]->closed && gyms[i]->drawMask.live)
             return fail("mv_step_many: gym " + std::to_string(i) + " has a draw mask attached (mv_set_draw_mask): step it on its own, or detach the mask first");
     for (int i = 0; i < n; ++i)
         if (gyms[i] && !gyms[i]->closed && gyms[i]->budgetOn)

@@ -231,12 +231,12 @@ int store_check(mv_gym *g, const void *map, const void *device_store, int32_t sl
 // caller enqueued (the kernel that wrote the map, whatever filled or still reads the store), behind every step launch enqueued so far (sim_join) and behind
 // the episode log's last update, which lives on this stream.  The next step launch waits for it (simMustWaitUser: it overwrites what a save reads and reads
 // what a load writes); nothing else is ordered behind a save, and the caller's stream sees the record complete.  No host synchronisation.  A host map
-// travels through the forks' pinned double buffer.
+// travels through the forks' staging pair (mv_staging.h).
 int store_launch(mv_gym *g, bool save, const int32_t *device_map, const int32_t *host_map, void *device_store, int32_t slots, bool read_back)
 {
     HIP_TRY(hipSetDevice(g->device));
     if (sim_join(g)) return -1;
-    if (host_map && stage_fork_map(g, host_map, g->stream, &device_map)) return -1;
+    if (host_map && g->forkMapPair.stage(host_map, (size_t)g->N * sizeof(int32_t), g->stream, &device_map)) return -1;
     const store::Layout L = store::layout_of(g->forkTable, g->A);
     const bool logOn = g->logCapacity > 0;
     if (save) store::launch_save(g->forkTable, L, g->envRecordLayout, logOn ? g->logRet : nullptr, logOn ? g->logLen : nullptr, device_map, g->N,
@@ -244,7 +244,7 @@ int store_launch(mv_gym *g, bool save, const int32_t *device_map, const int32_t 
     else store::launch_load(g->forkTable, L, g->envRecordLayout, logOn ? g->logRet : nullptr, logOn ? g->logLen : nullptr, device_map, g->N,
                             (const uint8_t *)device_store, slots, g->dStatus, g->stream);
     HIP_TRY(hipGetLastError());
-    if (host_map) HIP_TRY(hipEventRecord(g->forkMapCopied[(int)((g->forkMapUses - 1) & 1ull)], g->stream));
+    if (host_map && g->forkMapPair.mark(g->stream)) return -1;
     if (read_back) {
         // Only the kernel knows whether it skipped an entry -- of a device map, or (both load forms) one whose record's header does not match.  The status
         // words travel back behind it, and the next stepping call waits for them and reports ST_ENV_STORE: a host wait there, none here.

@@ -26,14 +26,6 @@ __global__ __launch_bounds__(256) void episode_budget_attach_kernel(const int32_
 
 namespace {
 
-// what every form refuses: no gym, a closed one, a member of a group (the union launches read no budget)
-int budget_check(mv_gym *g, const char *who)
-{
-    if (check(g)) { g_err = std::string(who) + ": " + g_err; return -1; }
-    if (g->inGroup) return fail(std::string(who) + ": this gym belongs to an mv_group, whose union launches read no episode budget");
-    return 0;
-}
-
 int budget_alloc(mv_gym *g, const char *who)
 {
     if (g->budgetLeft) return 0;
@@ -43,25 +35,6 @@ int budget_alloc(mv_gym *g, const char *who)
     g->budgetHalted = (uint32_t *)(g->budgetLeft + N);
     g->budgetMirror = g->budgetLeft + N + 1;
     g->budgetBytes = bytes;
-    return 0;
-}
-
-// a pinned staging buffer nothing in flight reads: one whose copy has completed (asked, not waited for), else a new one
-int budget_staging(mv_gym *g, mv_gym::BudgetStaging *&out)
-{
-    out = nullptr;
-    for (mv_gym::BudgetStaging &s : g->budgetStaging)
-        if (hipEventQuery(s.copied) == hipSuccess) { out = &s; break; }
-    (void)hipGetLastError();   // (hipErrorNotReady of the queries, on every path: it must not surface in a later call's hipGetLastError)
-    if (out) return 0;
-    mv_gym::BudgetStaging s{nullptr, nullptr};
-    HIP_TRY(hipHostMalloc((void **)&s.host, ((size_t)g->N + 1) * sizeof(int32_t), hipHostMallocDefault));   // (the N budgets and the halted count: what one copy brings)
-    {
-        hipError_t e_ = hipEventCreateWithFlags(&s.copied, hipEventDisableTiming);
-        if (e_ != hipSuccess) { (void)hipHostFree(s.host); return fail(std::string("mv_set_episode_budget_host: hipEventCreate: ") + hipGetErrorString(e_)); }
-    }
-    g->budgetStaging.push_back(s);
-    out = &g->budgetStaging.back();
     return 0;
 }
 
@@ -77,11 +50,7 @@ int budget_detach(mv_gym *g)
 
 void mvapi::episode_budget_free(mv_gym *g)
 {
-    for (mv_gym::BudgetStaging &s : g->budgetStaging) {
-        if (s.copied) (void)hipEventDestroy(s.copied);
-        if (s.host) (void)hipHostFree(s.host);
-    }
-    g->budgetStaging.clear();
+    g->budgetPool.release();
     if (g->budgetLeft) (void)hipFree(g->budgetLeft);
     g->budgetLeft = g->budgetMirror = nullptr; g->budgetHalted = nullptr;
     g->budgetBytes = 0; g->budgetOn = false;
@@ -100,7 +69,7 @@ extern "C" {
 
 int mv_set_episode_budget(mv_gym *g, const int32_t *device_budget)
 {
-    if (budget_check(g, "mv_set_episode_budget")) return -1;
+    if (attach_check(g, "mv_set_episode_budget", "episode budget")) return -1;
     if (!device_budget) return budget_detach(g);
     HIP_TRY(hipSetDevice(g->device));
     if (budget_alloc(g, "mv_set_episode_budget")) return -1;
@@ -117,39 +86,35 @@ int mv_set_episode_budget(mv_gym *g, const int32_t *device_budget)
 
 int mv_set_episode_budget_host(mv_gym *g, const int32_t *budget)
 {
-    if (budget_check(g, "mv_set_episode_budget_host")) return -1;
+    if (attach_check(g, "mv_set_episode_budget_host", "episode budget")) return -1;
     if (!budget) return budget_detach(g);
     HIP_TRY(hipSetDevice(g->device));
     if (budget_alloc(g, "mv_set_episode_budget_host")) return -1;
-    mv_gym::BudgetStaging *s = nullptr;
-    if (budget_staging(g, s)) return -1;
     // left [N] and the halted count lie behind each other: one copy brings both, a second one the mirror
     const size_t N = (size_t)g->N;
-    std::memcpy(s->host, budget, N * sizeof(int32_t));
+    StagingPool::Buffer *s = nullptr;
+    if (g->budgetPool.take((N + 1) * sizeof(int32_t), "mv_set_episode_budget_host", s)) return -1;
+    int32_t *host = static_cast<int32_t *>(s->host);
+    std::memcpy(host, budget, N * sizeof(int32_t));
     uint32_t zeros = 0;
     for (size_t e = 0; e < N; ++e) zeros += budget[e] == 0 ? 1u : 0u;
-    std::memcpy(s->host + N, &zeros, sizeof zeros);
+    std::memcpy(host + N, &zeros, sizeof zeros);
     if (sim_join(g)) return -1;   // (the order: as the device form's)
-    HIP_TRY(hipMemcpyAsync(g->budgetLeft, s->host, (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(g->budgetMirror, s->host, N * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(g->budgetLeft, host, (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(g->budgetMirror, host, N * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
     HIP_TRY(hipEventRecord(s->copied, g->stream));
     g->budgetOn = true;
     return 0;
 }
 
-int mv_get_episode_budget(const mv_gym *g)
-{
-    if (!g) return fail("mv_get_episode_budget: null gym handle");
-    if (g->closed) return fail("mv_get_episode_budget: gym is closed");
-    return g->budgetOn ? 1 : 0;
-}
+int mv_get_episode_budget(const mv_gym *g) { return getter_check(g, "mv_get_episode_budget") ? -1 : g->budgetOn ? 1 : 0; }
 
 void *mv_episode_budget_device_ptr(mv_gym *g) { return g && !g->closed && g->budgetOn ? (void *)g->budgetLeft : nullptr; }
 void *mv_halted_count_device_ptr(mv_gym *g) { return g && !g->closed && g->budgetOn ? (void *)g->budgetHalted : nullptr; }
 
 int mv_halted_count(mv_gym *g, int32_t *out)
 {
-    if (budget_check(g, "mv_halted_count")) return -1;
+    if (attach_check(g, "mv_halted_count", "episode budget")) return -1;
     if (!out) return fail("mv_halted_count: null output");
     if (!g->budgetOn) return fail("mv_halted_count: no episode budget attached (mv_set_episode_budget)");
     HIP_TRY(hipSetDevice(g->device));

@@ -229,7 +229,7 @@ int episode_log_update(mv_gym *g, const GymView *views, int stride, int k)
         a.first_tick = g->ticksSinceReset + (uint32_t)j0;
         a.hdr = g->logHdr; a.ret = g->logRet; a.len = g->logLen; a.records = g->logRecords;
         a.status = g->dStatus ? g->dStatus + g->N + 1 : nullptr;
-        a.step_mask = g->stepMask;
+        a.step_mask = g->stepMask.live;
         a.budget = g->budgetOn ? g->budgetMirror : nullptr;
         launch_episode_log(a, g->stream);
     }

@@ -109,28 +109,6 @@ int fork_check(mv_gym *g, const void *map, const char *who, const char *what)
     return 0;
 }
 
-// a host map's way to the device: through the map's device copy and its pinned staging, double buffered (allocated at the first use), on stream s.  The
-// caller records forkMapCopied[(forkMapUses - 1) & 1] behind the launch that reads *device_map.   (shared with mv_env_store.hip)
-int stage_fork_map(mv_gym *g, const int32_t *host_map, hipStream_t s, const int32_t **device_map)
-{
-    const size_t bytes = (size_t)g->N * sizeof(int32_t);
-    if (!g->dForkMap) {
-        HIP_TRY(hipMalloc((void **)&g->dForkMap, 2 * bytes));
-        HIP_TRY(hipHostMalloc((void **)&g->hForkMap, 2 * bytes, hipHostMallocDefault));
-        for (hipEvent_t &e : g->forkMapCopied) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        g->forkMapUses = 0;
-    }
-    const int b = (int)(g->forkMapUses & 1ull);
-    // (the copy and the launch that used this half two calls ago: long done -- the staging is the host's to write again, the device half the stream's)
-    if (g->forkMapUses >= 2) HIP_TRY(hipEventSynchronize(g->forkMapCopied[b]));
-    int32_t *h = g->hForkMap + (size_t)b * g->N, *d = g->dForkMap + (size_t)b * g->N;
-    std::memcpy(h, host_map, bytes);
-    HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-    *device_map = d;
-    ++g->forkMapUses;
-    return 0;
-}
-
 }  // namespace mvapi
 
 namespace {
@@ -159,7 +137,7 @@ int fork_launch(mv_gym *g, const int32_t *device_map, const int32_t *host_map, L
     const bool onSim = host_map && g->pipelined && g->simOnOwnStream && g->simDoneValid && !g->simMustWaitUser && g->logCapacity == 0;
     hipStream_t s = onSim ? g->simStream : g->stream;
     if (!onSim && sim_join(g)) return -1;
-    if (host_map && stage_fork_map(g, host_map, s, &device_map)) return -1;
+    if (host_map && g->forkMapPair.stage(host_map, (size_t)g->N * sizeof(int32_t), s, &device_map)) return -1;
     fork::Table t = g->forkTable;
     if (g->logCapacity > 0) {   // the running returns and lengths: a fork's record covers the episode from its source's start (mv_episode_log.h)
         fork::table_add(t, g->logRet, (size_t)g->A * sizeof(double));
@@ -168,7 +146,7 @@ int fork_launch(mv_gym *g, const int32_t *device_map, const int32_t *host_map, L
     if (kind == FORK) fork::launch_fork(t, device_map, g->N, g->dStatus, s);
     else fork::launch_resample(t, fork::staging_carve(t, g->N, g->resampleArena), device_map, g->N, g->dStatus, kind == RESAMPLE, s);
     HIP_TRY(hipGetLastError());
-    if (host_map) HIP_TRY(hipEventRecord(g->forkMapCopied[(int)((g->forkMapUses - 1) & 1ull)], s));
+    if (host_map && g->forkMapPair.mark(s)) return -1;
     if (onSim) HIP_TRY(hipEventRecord(g->simDone, s));   // (what the caller's stream, a reset or a render waits for: now behind the copy)
     if (!host_map) {
         // Only the kernel knows whether it skipped an entry.  The status words travel back behind it, and the next stepping call waits for them

@@ -14,19 +14,6 @@ int reset_envs_check(mv_gym *g, const void *mask, const char *who)
     return 0;
 }
 
-// first use: the device bytes (two halves for the host form's mask, then `applied`) and the pinned staging of the two halves.  Nothing is cleared: a half
-// is written before it is read, and `applied[e]` is written for every flagged env and read for flagged envs only.
-int reset_envs_buffers(mv_gym *g)
-{
-    if (g->dResetMask) return 0;
-    const size_t N = (size_t)g->N;
-    HIP_TRY(hipMalloc((void **)&g->dResetMask, 3 * N));
-    HIP_TRY(hipHostMalloc((void **)&g->hResetMask, 2 * N, hipHostMallocDefault));
-    for (hipEvent_t &e : g->resetMaskCopied) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    g->resetMaskUses = 0;
-    return 0;
-}
-
 // The launches, on the CALLER's stream like mv_reset's: behind whatever the caller enqueued there (the kernel that wrote a device mask), behind every step
 // launch enqueued so far (sim_join) and behind the episode log's last update, which lives on that stream; the next step launch waits for all of it
 // (simMustWaitUser).  The swap-in writes the public rewards / dones of the last tick (the current output-ring entry), as mv_reset's does.
@@ -48,35 +35,20 @@ int reset_envs_launch(mv_gym *g, const uint8_t *device_mask, const uint8_t *host
         for (size_t e = 0; e < N && !any; ++e) any = host_mask[e] != 0;
         if (!any) return 0;
     }
-    if (reset_envs_buffers(g)) return -1;
+    // (first use; not cleared: `applied[e]` is written for every flagged env and read for flagged envs only)
+    if (!g->resetApplied) HIP_TRY(hipMalloc((void **)&g->resetApplied, N));
     if (g->hostEpisodes() && host_mask) {
         // (the periodic read-back may be ticks old, and an earlier masked reset may have consumed episodes since: the current counts, then the uploads)
-        HIP_TRY(hipStreamSynchronize(g->simStream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        HIP_TRY(hipStreamSynchronize(g->copyStream));
-        HIP_TRY(hipMemcpy(g->hStatus, g->dStatus, (N + 2) * sizeof(int), hipMemcpyDeviceToHost));
-        g->statusPending = false;
-        g->pendingAge = 0;
-        g->stepsSinceStatus = 0;
+        if (sync_status_words(g)) return -1;
         g->refillForce = true;
         if (refill_episodes(g, 1) < 0) return -1;   // every env has an unconsumed episode resident
     }
-    if (host_mask) {
-        const int b = (int)(g->resetMaskUses & 1ull);
-        // (the copy and the launch that used this half two calls ago: long done -- the staging is the host's to write again, the device half the stream's)
-        if (g->resetMaskUses >= 2) HIP_TRY(hipEventSynchronize(g->resetMaskCopied[b]));
-        uint8_t *h = g->hResetMask + (size_t)b * N, *d = g->dResetMask + (size_t)b * N;
-        std::memcpy(h, host_mask, N);
-        HIP_TRY(hipMemcpyAsync(d, h, N, hipMemcpyHostToDevice, g->stream));
-        device_mask = d;
-        ++g->resetMaskUses;
-    }
-    uint8_t *applied = g->dResetMask + 2 * N;
+    if (host_mask && g->resetMaskPair.stage(host_mask, N, g->stream, &device_mask)) return -1;
     const OutPtrs outs = last_outputs(g);
     const GymView v = view(g, g->parity, &outs);
     if (g->hostEpisodes()) {
         if (g->lastUpload) HIP_TRY(hipStreamWaitEvent(g->stream, g->lastUpload, 0));   // (uploads in flight: a stream wait, not a host wait)
-        launch_reset_envs(v, device_mask, applied, g->stream);
+        launch_reset_envs(v, device_mask, g->resetApplied, g->stream);
         HIP_TRY(hipEventRecord(g->stepDone, g->stream));   // (the kernel reads the ring: no upload overlaps it)
         g->lastStep = g->stepDone;
         if (read_back_status(g, g->stepDone)) return -1;
@@ -85,13 +57,13 @@ int reset_envs_launch(mv_gym *g, const uint8_t *device_mask, const uint8_t *host
     } else {
         if (tower_join(g)) return -1;
         launch_tower_draw(v, g->stream);
-        launch_reset_envs(v, device_mask, applied, g->stream);
+        launch_reset_envs(v, device_mask, g->resetApplied, g->stream);
         launch_tower_draw(v, g->stream);
     }
     HIP_TRY(hipGetLastError());
-    if (host_mask) HIP_TRY(hipEventRecord(g->resetMaskCopied[(int)((g->resetMaskUses - 1) & 1ull)], g->stream));
+    if (host_mask && g->resetMaskPair.mark(g->stream)) return -1;
     if (g->logCapacity > 0) {   // the cut episodes write no record: their running returns and lengths go to zero, nothing else of the log moves
-        elog::launch_episode_log_cut(device_mask, applied, g->N, g->A, g->logRet, g->logLen, g->stream);
+        elog::launch_episode_log_cut(device_mask, g->resetApplied, g->N, g->A, g->logRet, g->logLen, g->stream);
         HIP_TRY(hipGetLastError());
     }
     g->mirrorsFresh = false;

@@ -25,43 +25,6 @@ int seed_envs_check(mv_gym *g, const void *seeds, const char *who)
     return 0;
 }
 
-// first use of the host form: two halves of N seed words on the device, their pinned staging, an event per half.  Nothing is cleared: a half is written
-// before it is read.
-int seed_envs_buffers(mv_gym *g)
-{
-    if (g->dSeedEnvs) return 0;
-    const size_t N = (size_t)g->N;
-    HIP_TRY(hipMalloc((void **)&g->dSeedEnvs, 2 * N * sizeof(int32_t)));
-    HIP_TRY(hipHostMalloc((void **)&g->hSeedEnvs, 2 * N * sizeof(int32_t), hipHostMallocDefault));
-    for (hipEvent_t &e : g->seedEnvsCopied) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    g->seedEnvsUses = 0;
-    return 0;
-}
-
-// the host's seed words -> the device half whose turn it is, on the caller's stream.  The half's event is recorded here, behind the copy, with the use that
-// is counted here -- whatever becomes of the launch that follows, the event of this use exists -- and seed_envs_staged records it again behind the kernel
-// that read the device half.
-int stage_seeds(mv_gym *g, const int32_t *host_seeds, const int32_t **device_seeds)
-{
-    if (seed_envs_buffers(g)) return -1;
-    const size_t N = (size_t)g->N;
-    const int b = (int)(g->seedEnvsUses & 1ull);
-    // (the copy and the launch that used this half two calls ago: long done -- the staging is the host's to write again, the device half the stream's)
-    if (g->seedEnvsUses >= 2) HIP_TRY(hipEventSynchronize(g->seedEnvsCopied[b]));
-    int32_t *h = g->hSeedEnvs + (size_t)b * N, *d = g->dSeedEnvs + (size_t)b * N;
-    std::memcpy(h, host_seeds, N * sizeof(int32_t));
-    HIP_TRY(hipMemcpyAsync(d, h, N * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipEventRecord(g->seedEnvsCopied[b], g->stream));
-    *device_seeds = d;
-    ++g->seedEnvsUses;
-    return 0;
-}
-int seed_envs_staged(mv_gym *g)
-{
-    HIP_TRY(hipEventRecord(g->seedEnvsCopied[(int)((g->seedEnvsUses - 1) & 1ull)], g->stream));
-    return 0;
-}
-
 // TowerBuilding, both forms, on the CALLER's stream like mv_seed's launches: behind whatever the caller enqueued there (the kernel that wrote a device
 // array), behind every step launch enqueued so far (sim_join) and the last draw launch (tower_join); the next step launch waits for all of it
 // (simMustWaitUser), and every later draw launch is ordered behind that step.  No host wait: the draw behind the seed kernel makes the new streams' first
@@ -70,11 +33,11 @@ int seed_envs_tower(mv_gym *g, const int32_t *device_seeds, const int32_t *host_
 {
     HIP_TRY(hipSetDevice(g->device));
     if (sim_join(g) || tower_join(g)) return -1;
-    if (host_seeds && stage_seeds(g, host_seeds, &device_seeds)) return -1;
+    if (host_seeds && g->seedEnvsPair.stage(host_seeds, (size_t)g->N * sizeof(int32_t), g->stream, &device_seeds)) return -1;
     launch_tower_seed_envs(g->gv, device_seeds, g->stream);
     launch_tower_draw(g->gv, g->stream);
     HIP_TRY(hipGetLastError());
-    if (host_seeds && seed_envs_staged(g)) return -1;
+    if (host_seeds && g->seedEnvsPair.mark(g->stream)) return -1;
     return 0;
 }
 
@@ -93,20 +56,13 @@ int seed_envs_host_fed(mv_gym *g, const int32_t *host_seeds)
     if (envs.empty()) return 0;   // nobody flagged: nothing to wait for, nothing to launch
     HIP_TRY(hipSetDevice(g->device));
     if (sim_join(g)) return -1;
-    HIP_TRY(hipStreamSynchronize(g->simStream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    HIP_TRY(hipStreamSynchronize(g->copyStream));
-    // the current counts, not the last periodic read-back
-    HIP_TRY(hipMemcpy(g->hStatus, g->dStatus, (size_t)(N + 2) * sizeof(int), hipMemcpyDeviceToHost));
-    g->statusPending = false;
-    g->pendingAge = 0;
-    g->stepsSinceStatus = 0;
+    if (sync_status_words(g)) return -1;
     const int32_t *device_seeds = nullptr;
-    if (stage_seeds(g, host_seeds, &device_seeds)) return -1;
+    if (g->seedEnvsPair.stage(host_seeds, (size_t)g->N * sizeof(int32_t), g->stream, &device_seeds)) return -1;
     const int slots = N * g->spares;
     hipLaunchKernelGGL(ring_wipe_envs_kernel, dim3((slots + 255) / 256), dim3(256), 0, g->stream, g->dBlobs, g->blobBytes, g->spares, N, device_seeds);
     HIP_TRY(hipGetLastError());
-    if (seed_envs_staged(g)) return -1;
+    if (g->seedEnvsPair.mark(g->stream)) return -1;
     HIP_TRY(hipStreamSynchronize(g->stream));   // (the uploads below travel on other streams: the wipe is done before the first of them starts)
     for (int e : envs) {
         g->uploaded[(size_t)e] = g->hStatus[e];
@@ -119,14 +75,6 @@ int seed_envs_host_fed(mv_gym *g, const int32_t *host_seeds)
 }
 
 }  // namespace
-
-void mvapi::seed_envs_free(mv_gym *g)
-{
-    if (g->dSeedEnvs) (void)hipFree(g->dSeedEnvs);
-    if (g->hSeedEnvs) (void)hipHostFree(g->hSeedEnvs);
-    for (hipEvent_t &e : g->seedEnvsCopied) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    g->dSeedEnvs = g->hSeedEnvs = nullptr;
-}
 
 extern "C" {
 

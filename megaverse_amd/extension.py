@@ -828,21 +828,24 @@ class MegaverseGym:
 
     STEP_MASK_FORMS = ("none", "device", "host")
 
+    def _set_env_mask(self, check, set_fn, set_host_fn, held_attr, mask):
+        """set_step_mask / set_draw_mask: None detaches, a CUDA tensor is attached in place and held, anything else goes through the host form.  set_fn,
+        set_host_fn: the library calls' names (the library is not touched before the mask has passed its check)"""
+        m = check(mask, self.num_envs)
+        if isinstance(m, str):
+            self._ck(getattr(self._lib, set_fn)(self._g, _P(int(mask.data_ptr()))))
+        elif m is None:
+            self._ck(getattr(self._lib, set_fn)(self._g, None))
+        else:
+            self._ck(getattr(self._lib, set_host_fn)(self._g, m.ctypes.data))
+        setattr(self, held_attr, mask if isinstance(m, str) else None)
+
     def set_step_mask(self, mask):
         """Step masks (include/megaverse_hip.h: mv_set_step_mask): mask[e] non-zero: env e steps; 0: env e is frozen -- every tick of every later stepping
         call leaves its state alone, reports reward 0 and done 0 for it and discards its actions -- until the mask is replaced or detached (None).  A
         contiguous torch.bool / uint8 CUDA tensor of shape (num_envs,) is read in place by the step kernels (the gym holds a reference; after rewriting it,
         call this again); a numpy array or a sequence of bools is copied to a buffer of the gym's.  Neither form waits on the host."""
-        m = check_step_mask(mask, self.num_envs)
-        if m is None:
-            self._ck(self._lib.mv_set_step_mask(self._g, None))
-            self._step_mask_held = None
-        elif isinstance(m, str):
-            self._ck(self._lib.mv_set_step_mask(self._g, _P(int(mask.data_ptr()))))
-            self._step_mask_held = mask
-        else:
-            self._ck(self._lib.mv_set_step_mask_host(self._g, m.ctypes.data))
-            self._step_mask_held = None
+        self._set_env_mask(check_step_mask, 'mv_set_step_mask', 'mv_set_step_mask_host', '_step_mask_held', mask)
 
     def step_mask(self):
         """-> 'none' | 'device' | 'host': the form of the step mask attached (set_step_mask)"""
@@ -855,16 +858,7 @@ class MegaverseGym:
         drawn env.  Until the mask is replaced or detached (None).  A contiguous torch.bool / uint8 CUDA tensor of shape (num_envs,) is read in place (the gym
         holds a reference; after rewriting it, call this again); a numpy array or a sequence of bools is copied to a buffer of the gym's.  Neither form
         waits on the host.  draw_hires ignores the mask."""
-        m = check_draw_mask(mask, self.num_envs)
-        if m is None:
-            self._ck(self._lib.mv_set_draw_mask(self._g, None))
-            self._draw_mask_held = None
-        elif isinstance(m, str):
-            self._ck(self._lib.mv_set_draw_mask(self._g, _P(int(mask.data_ptr()))))
-            self._draw_mask_held = mask
-        else:
-            self._ck(self._lib.mv_set_draw_mask_host(self._g, m.ctypes.data))
-            self._draw_mask_held = None
+        self._set_env_mask(check_draw_mask, 'mv_set_draw_mask', 'mv_set_draw_mask_host', '_draw_mask_held', mask)
 
     def draw_mask(self):
         """-> 'none' | 'device' | 'host': the form of the draw mask attached (set_draw_mask)"""
