@@ -405,6 +405,37 @@ int mv_step_n(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32_t firs
  * Refused (-1 with text): an unknown mode; everything mv_step_n refuses; a gym in a group. */
 enum { MV_RENDER_EVERY = 0, MV_RENDER_LAST = 1, MV_RENDER_NONE = 2 };
 int mv_step_n_render(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32_t first_step_index, int32_t render_mode);
+/* Macro steps (no reference counterpart: it is the action-repeat / frame-skip wrapper a learner writes around VectorEnv::step, vector_env.cpp:89-108 --
+ * "for _ in range(k): obs, r, d = env.step(a); total += r; if d: break" -- per env, as one operation).  One decision is held for up to k ticks, every env
+ * stops at its own first done, and the call leaves ONE reward (the sum), ONE done and ONE frame.
+ * device_actions: [N*A][6] int32, encoded as for mv_set_actions_device, held on every tick of the call the env steps in -- to the kernels an action ring of
+ * count 1; the caller's attached ring (mv_set_action_ring), if any, stays attached and untouched; a pending mv_set_actions* buffer is superseded as
+ * MV_POLICY_SEQUENCE supersedes it.  The kernels read it in place: it stays unchanged until the caller's stream has passed the end of the call.
+ * device_ticks: NULL (every env: k) or int32 [N], clamped to [0, k]; 0: the env does not step in this call.  Copied once, in stream order, into a gym-owned
+ * array tl [N] (allocated at first use, counted in mv_arena_bytes, freed by mv_close): the kernels write that array.
+ * The rule (megaverse_amd/csrc/mv_macro_step.h states it for kernels and host alike), tl[e] set at the call's start:
+ *   env e steps in a tick  <=>  mask and budget let it (mv_set_step_mask, mv_set_episode_budget: their rule, unchanged) and tl[e] > 0;
+ *   behind a tick the env stepped in, tl[e] goes down by one, and to 0 if that tick staged done; the budget is spent as always -- a user budget keeps
+ *   counting episodes over macro steps;
+ *   an env that does not step runs the frozen tick of the step masks, word for word.
+ * So an env's macro step ends on the tick that finished its episode; that tick ran whole, auto-reset included, and the env stands on the first frame of its
+ * next episode -- also in the middle of a resident multi-tick launch, across the launches of one chunk and across the chunks of a call whose k exceeds the
+ * internal batch (the call splits as mv_step_n does).
+ * Outputs, one set per CALL: reward[a] is the fp32 left fold s = r_0; s = s + r_j over the call's k per-tick values in tick order (a frozen tick's is +0.0f;
+ * nothing reassociated or contracted: a float32 loop reproduces it bit for bit); done[e] is the OR over the call's ticks; true objectives are published for
+ * the envs that finished, as MV_RENDER_NONE / MV_RENDER_LAST calls publish them.  MV_RENDER_LAST draws the frame of the call's last tick for every env, the
+ * ones that stopped early included (their new episode's first frame), in the gym's pixel mode and layout; MV_RENDER_NONE writes no byte of the slab or an
+ * observation ring.  With an output ring attached the call fills ONE entry and the ring's position advances by one -- a ring of 16 holds 16 consecutive
+ * decisions; every stepping call advances the position by the entries it wrote, so interleaving with mv_step_n stays well defined.  mv_ticks_since_reset
+ * advances by k.  State observations (mv_set_state_obs): each agent's row goes into that same entry and holds the state behind the call's last tick.
+ * Episode log: a tick the env did not step in adds nothing to returns or length; records as always.
+ * Launches: the MASKED step kernels, as one launch per 8 ticks wherever mv_step_n_render has its one-launch step; one launch that sets tl, one that folds
+ * the call's hand-over slots into the entry (per chunk; a later chunk continues the fold from the entry, in order); MV_RENDER_LAST: one observation launch.
+ * Ordering: mv_step_n_render's.  The device form never waits on the host; the host form goes through pinned staging buffers of the gym's.
+ * Refused (-1 with text): everything mv_step_n_render refuses; a gym in an mv_group; k < 1; MV_RENDER_EVERY (a decision has one frame); null actions.
+ * Out of scope: groups, discounting inside the fold, reward clipping. */
+int mv_macro_step(mv_gym *g, int32_t k, const int32_t *device_actions, const int32_t *device_ticks, int32_t render_mode);
+int mv_macro_step_host(mv_gym *g, int32_t k, const int32_t *actions, const int32_t *ticks, int32_t render_mode);
 /* Rollout rings (no reference counterpart: its learner copies each step's observation out of the gym, megaverse_env.py:121-130): tick
  * number t since this call leaves its observations in obs[t % count] ([count][N*A][h][w][4]; planar layout: [count][N*A][3][h][w]), its rewards in rewards[t % count] ([count][N*A])
  * and its dones in dones[t % count] ([count][N]); a NULL ring keeps that output where it was.  count = 0 switches back to the single
@@ -620,10 +651,23 @@ int mv_debug_episode_log_masked_host(const float *rewards, const uint8_t *dones,
 int mv_debug_episode_log_budget_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A,
                                      int32_t capacity, uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped,
                                      const uint8_t *step_mask /* [N] or NULL */, int32_t *left /* [N] or NULL */);
+/* ... and a macro step (mv_macro_step): tl [N] or NULL, in and out -- the log's mirror of the ticks left in the macro step the k ticks belong to (the caller
+ * sets it to the call's clamped ticks), advanced by the rule of megaverse_amd/csrc/mv_macro_step.h; a tick the env does not step in is skipped.  tl = NULL:
+ * mv_debug_episode_log_budget_host, byte for byte. */
+int mv_debug_episode_log_macro_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A,
+                                    int32_t capacity, uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped,
+                                    const uint8_t *step_mask /* [N] or NULL */, int32_t *left /* [N] or NULL */, int32_t *tl /* [N] or NULL */);
 /* Host-only (no device): the rule of episode budgets (megaverse_amd/csrc/mv_episode_budget.h) over k ticks of N envs.  dones [k][N]: what tick t stages for
  * env e if it steps; mask [N] or NULL; left_in [N].  steps_out [k][N]: 1 where the env steps in the tick; left_out [N]: the budgets behind the last tick. */
 int mv_debug_episode_budget_host(const uint8_t *dones, const uint8_t *mask, const int32_t *left_in, int32_t k, int32_t N, uint8_t *steps_out,
                                  int32_t *left_out);
+/* Host-only (no device): the rule of macro steps (megaverse_amd/csrc/mv_macro_step.h) over the k ticks of one call of N envs.  dones, mask, left_in as above
+ * (left_in: -1 where there is no budget); ticks_in [N] or NULL (every env: k), clamped to [0, k].  steps_out [k][N]: 1 where the env steps in the tick;
+ * left_out [N], ticks_out [N]: the budgets and the ticks left behind the last tick. */
+int mv_debug_macro_rule_host(const uint8_t *dones, const uint8_t *mask, const int32_t *left_in, const int32_t *ticks_in, int32_t k, int32_t N,
+                             uint8_t *steps_out, int32_t *left_out, int32_t *ticks_out);
+/* Host-only (no device): the fold of a macro step's rewards (mv_macro_step.h: macro_fold): values [k][n] -> out [n], s = v_0; s = s + v_t in tick order. */
+int mv_debug_macro_fold_host(const float *values, int32_t k, int32_t n, float *out);
 /* Host-only (no device): the episode log's masked clear (megaverse_amd/csrc/mv_episode_log.h: episode_log_cut, the source mv_reset_envs' kernel runs) over N
  * envs x A agents: where mask[e] != 0, ret[e * A .. e * A + A - 1] and len[e] go to zero; everything else stays. */
 int mv_debug_episode_log_cut_host(const uint8_t *mask, int32_t N, int32_t A, double *ret, int32_t *len);

@@ -786,6 +786,7 @@ int mv_close(mv_gym *g)
     env_masks_free(g);
     state_obs_free(g);
     episode_budget_free(g);
+    macro_step_free(g);
     if (g->arena) (void)hipFree(g->arena);
     if (g->hiresObs) (void)hipFree(g->hiresObs);
     if (g->hBlobs) (void)(g->blobsOnDevice ? hipFree(g->hBlobs) : hipHostFree(g->hBlobs));

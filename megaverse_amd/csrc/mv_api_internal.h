@@ -11,6 +11,7 @@
 //                     envs' frames out of the observation passes (mv_frame.h: frame_skip)
 //   mv_state_obs.hip  state observations: attaching the caller's buffer, the staging rows, their publication and refresh (mv_state_obs.h: the record)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
+//   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
 // mv_staging.h holds the two ways the host forms' values reach the device (StagingPool, StagingPair).
 // The C ABI itself is include/megaverse_hip.h; nothing here is exported under a C name.
 #pragma once
@@ -39,6 +40,7 @@
 #include "mv_union.h"
 #include "mv_episode_log.h"
 #include "mv_episode_budget.h"
+#include "mv_macro_step.h"
 #include "mv_fork.h"
 
 namespace mv {
@@ -95,6 +97,15 @@ struct EnvMask {
     uint8_t *owned = nullptr;
     size_t ownedBytes = 0;
     StagingPool pool;
+};
+}  // namespace mvapi
+
+namespace mvapi {
+// One chunk of a macro step (mv_macro_step; mv_api_step.hip: step_gyms): the actions every tick of the call holds, and where the chunk stands in the call --
+// the first chunk starts the call's one output entry, the last one completes it.
+struct MacroCall {
+    const int32_t *actions;   // [N*A][6] device memory
+    bool first, last;
 };
 }  // namespace mvapi
 
@@ -271,6 +282,14 @@ struct mv_gym {
     bool budgetOn = false;
     size_t budgetBytes = 0;
     StagingPool budgetPool;
+    // mv_macro_step: one gym-owned allocation (mv_macro_step.h: macro_step_words), made at first use and counted in mv_arena_bytes -- macroTl [N], the ticks
+    // each env may still step in the call in flight, what the step kernels read and write (GymView::macro_tl, through the views of a macro step's ticks only);
+    // macroMirror [N], the episode log's own copy; macroTicks [N] and macroActions [N*A][6], where the host form's values land (through a pool of N + 6 N A
+    // words).  macroCall: the chunk that is being enqueued, null outside mv_macro_step.
+    int32_t *macroTl = nullptr, *macroMirror = nullptr, *macroTicks = nullptr, *macroActions = nullptr;
+    size_t macroBytes = 0;
+    StagingPool macroPool;
+    const MacroCall *macroCall = nullptr;
     // in-stream profiling
     std::vector<hipEvent_t> profEvents;          // 5 per profiled tick: [0] [1] around the step kernel (its stream), [2] [3] [4] before the
                                                  // observation pass, between frame sort and raster, after the raster (the caller's stream)
@@ -314,6 +333,12 @@ int episode_log_reset(mv_gym *g);   // mv_reset: accumulators to zero, the recor
 void episode_log_free(mv_gym *g);   // mv_close
 void env_masks_free(mv_gym *g);     // mv_close (mv_env_masks.hip)
 void episode_budget_free(mv_gym *g);   // mv_close (mv_episode_budget.hip)
+void macro_step_free(mv_gym *g);       // mv_close (mv_macro_step.hip)
+// mv_macro_step.hip: the staged outputs of the k ticks in slots q0 .. q0 + k - 1 folded into ONE entry o -- rewards summed in tick order (mv_macro_step.h:
+// macro_fold), dones OR-ed, true objectives as publish_ticks -- with one launch on the caller's stream; cont: the entry holds the fold of the call's earlier chunks
+int publish_macro(mv_gym *g, int q0, const OutPtrs &o, int k, bool cont);
+// mv_api_step.hip: one chunk (<= batch ticks) of a macro step of kCall ticks; quiet: QUIET_NONE / QUIET_LAST of step_gyms
+int step_macro_chunk(mv_gym *g, int k, int kCall, bool draw_last, const MacroCall &mc);
 // mv_state_obs.hip: tick `tick`'s entry of the caller's buffer (the entry outputs_of gives its rewards); the staged rows of the k ticks in slots q0 .. q0 + k - 1
 // -> dst[j], one launch on the caller's stream; the last tick's entry gathered from the current state (mask: device bytes [N], only the flagged envs' rows;
 // null: every row; nothing attached: no launch), on the caller's stream behind sim_join

@@ -18,8 +18,12 @@ extern "C" {
 // MV_RENDER_LAST call) -- its frame setup in the step launch, one observation launch for it.  Either way the ticks go out as ONE launch per 8 that sets no other
 // frame up (launch_step_ticks_sim) wherever the rendered call has its one-launch step, and their rewards / dones / true objectives are published by ONE launch
 // for the chunk (publish_ticks).  QUIET_OFF: everything as `render` says, launch for launch.
+// mc (mv_macro_step; one gym, a quiet mode, POLICY_SEQUENCE): the chunk belongs to a macro step.  Every tick holds mc->actions -- to the kernels an action ring
+// of count 1; the gym's own ring is not looked at -- every view carries the gym's ticks-left array, so the MASKED kernels are launched; all k ticks share ONE
+// output entry, which publish_macro folds the chunk's slots into in publish_ticks' place, and the ring's position moves on by one behind the call's last chunk.
 enum : int { QUIET_OFF = 0, QUIET_NONE = 1, QUIET_LAST = 2 };
-static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, uint32_t seed, uint32_t first_index, int kCall, int quiet = QUIET_OFF)
+static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, uint32_t seed, uint32_t first_index, int kCall, int quiet = QUIET_OFF,
+                     const MacroCall *mc = nullptr)
 {
     mv_gym *const L = gs[0];
     int batch = L->batch;
@@ -33,7 +37,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
         allFast = allFast && g->fastPixels != 0;
         anyHostEpisodes = anyHostEpisodes || g->hostEpisodes();
         anyLog = anyLog || g->logCapacity > 0;
-        if (policy == POLICY_SEQUENCE && (!g->actRing || g->actRingCount < 1))
+        if (policy == POLICY_SEQUENCE && !mc && (!g->actRing || g->actRingCount < 1))
             return fail(n > 1 ? "mv_group_step: MV_POLICY_SEQUENCE: gym " + std::to_string(i) + " of the group has no action ring (mv_set_action_ring)"
                               : std::string("mv_step_n: MV_POLICY_SEQUENCE: the gym has no action ring (mv_set_action_ring)"));
     }
@@ -51,7 +55,8 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     hipStream_t sim = own ? L->simStream : L->stream;
     // The step kernels stage rewards / dones / true objectives in their hand-over slot and the caller's stream publishes them -- or, not pipelined, write the
     // public arrays themselves.  With an episode log (mv_set_episode_log) they always stage: the log reads every tick of the call from the slots.
-    const bool staged = own || anyLog;
+    // A macro step always stages: its publication folds the slots of the call's ticks into one entry.
+    const bool staged = own || anyLog || mc != nullptr;
     if (own) {
         // The simulation stream may reuse a slot group once the observation passes that read it are done: the END of the call PIPE_GROUPS calls
         // ago (userMark, completed by that call's last pass, see below).  When the caller's stream feeds the simulation (reset / render / device
@@ -161,13 +166,14 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
             if ((render || (drawLast && j == k - 1)) && take_hist(g, sim, !(multiTick || groupBatch || simTicks))) return -1;
             OutPtrs &o = outs[(size_t)j * n + i];
             if (stateOn) stateDst[j] = state_obs_entry(g, g->ringTick);   // (the same tick counter: the entry the tick's rewards go to)
-            o = outputs_of(g, g->ringTick++);
+            o = outputs_of(g, mc ? g->ringTick : g->ringTick++);   // (mv_macro_step: one entry for the whole call; the position moves on behind its last chunk)
             GymView &v = views[(size_t)j * n + i];
             v = view(g, g->parity, staged ? nullptr : &o);
             v.step_mask = g->stepMask.live;   // (mv_set_step_mask; a group's members have none)
             v.draw_mask = g->drawMask.live;   // (mv_set_draw_mask; likewise)
             if (g->budgetOn) { v.budget = g->budgetLeft; v.halted = g->budgetHalted; }   // (mv_set_episode_budget; likewise)
-            if (policy == POLICY_SEQUENCE)
+            if (mc) { v.macro_tl = g->macroTl; v.md_actions = mc->actions; }   // (mv_macro_step: the held actions, the envs' ticks left)
+            else if (policy == POLICY_SEQUENCE)
                 v.md_actions = g->actRing + (size_t)action_ring_entry(first_index, j, (uint32_t)g->actRingCount) * ((size_t)g->N * g->A * 6);
             else if (j == 0 && g->gv.sample_on == POLICY_NONE) v.md_actions = g->mdActions;
             if (groupBatch) v.lpt_no_clear = 1;   // (the passes clear their histograms themselves: mv_raster.hip, hist_done)
@@ -314,7 +320,9 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     std::vector<uint32_t *> chunkObs;
     int chunkFirst = 0;
     // (no tick drawn, or the last only: the chunk's staged outputs with one launch, in front of the drawn tick's pass -- which publishes nothing)
-    if (quiet != QUIET_OFF && staged && publish_ticks(L, L->group * L->batch, outs.data(), n, k)) return -1;
+    // (mv_macro_step: folded into the call's one entry)
+    if (quiet != QUIET_OFF && staged && (mc ? publish_macro(L, L->group * L->batch, outs[0], k, !mc->first) : publish_ticks(L, L->group * L->batch, outs.data(), n, k)))
+        return -1;
     for (int j = 0; j < k; ++j) {
         if (evs[j]) HIP_TRY(hipEventRecord(evs[j][2], L->stream));
         for (int i = 0; i < n; ++i) {
@@ -408,7 +416,10 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     // ---- the state observations (mv_set_state_obs): one launch for the call's k ticks, staged rows -> the caller's buffer, in the log's place and for the
     // log's reason under the same rule: it reads the call's slots, so the mark is recorded again behind it (with overlapped passes the mark was completed on
     // the pass stream, and the slot group could be reused under the copy).  Every stepping call stages and publishes this way, pipelined or not.
-    if (stateOn && state_obs_publish(L, L->group * L->batch, stateDst, k)) return -1;
+    // (mv_macro_step: one entry per call -- the rows behind the call's last tick, with its last chunk)
+    if (stateOn && mc) { if (mc->last && state_obs_publish(L, L->group * L->batch + k - 1, stateDst + (k - 1), 1)) return -1; }
+    else if (stateOn && state_obs_publish(L, L->group * L->batch, stateDst, k)) return -1;
+    if (mc && mc->last) ++L->ringTick;
     if ((anyLog || stateOn) && own) HIP_TRY(hipEventRecord(L->userMark[L->markCount % PIPE_GROUPS], L->stream));
     if (own) {
         ++L->markCount;
@@ -473,6 +484,14 @@ int mv_step_n_render(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32
 
 // ---- groups: several gyms of one job stepped with union launches (mv_step_union.hip, mv_raster.hip: launch_raster_union)
 }  // extern "C"
+// mv_macro_step (mv_macro_step.hip): one chunk of its ticks.  The episode log's update finds the chunk through the gym (mv_episode_log.hip).
+int mvapi::step_macro_chunk(mv_gym *g, int k, int kCall, bool draw_last, const MacroCall &mc)
+{
+    g->macroCall = &mc;
+    const int r = step_gyms(&g, 1, false, k, POLICY_SEQUENCE, 0, 0, kCall, draw_last ? QUIET_LAST : QUIET_NONE, &mc);
+    g->macroCall = nullptr;
+    return r;
+}
 void mvapi::group_detach(mv_gym *g)
 {   // back to the gym's own simulation stream and events (they were kept aside while it was a member)
     if (!g->inGroup) return;
@@ -617,7 +636,7 @@ int mv_recommended_pass_overlap(const mv_gym *g)
     return 1;
 }
 
-int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMask.ownedBytes + g->drawMask.ownedBytes + g->budgetBytes) : 0; }
+int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMask.ownedBytes + g->drawMask.ownedBytes + g->budgetBytes + g->macroBytes) : 0; }
 
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index)
 {   // several gyms of one job (MultiTaskGym: one per scenario, one stream each) stepped by one call: at eight sub-gyms the per-call cost of

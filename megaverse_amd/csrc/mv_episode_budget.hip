@@ -1,6 +1,6 @@
 // megaverse_amd/csrc/mv_episode_budget.hip -- episode budgets: the host side of mv_set_episode_budget / mv_set_episode_budget_host and their read-outs
 // (include/megaverse_hip.h), the attach kernel, and the rule's host twin mv_debug_episode_budget_host.  The rule is mv_episode_budget.h; the step kernels
-// apply it tick by tick (mv_step_kernels.h: env_left, budget_after_tick) and the episode log walks a mirror of it (mv_episode_log.hip: load_done);
+// apply it tick by tick (mv_step_kernels.h: env_left, after_tick) and the episode log walks a mirror of it (mv_episode_log.hip: load_done);
 // DESIGN.md 3.12 says where these calls stand in the streams' order.
 #include "mv_api_internal.h"
 #include "mv_episode_budget.h"

@@ -105,6 +105,7 @@ struct Args {
     int *status;       // the gym's status word (ST_EPISODE_LOG), or null
     const uint8_t *step_mask;   // [N] the call's step mask (episode_log_steps), or null
     int32_t *budget;            // [N] the log's mirror of the episode budgets (mv_set_episode_budget), advanced by the launch tick by tick, or null
+    int32_t *macro_tl;          // [N] the log's mirror of the ticks left in a macro step (mv_macro_step, mv_macro_step.h), advanced likewise, or null
 };
 
 // ticks one launch may cover for N*A agents (the LDS cells of MAX_GROUPS)

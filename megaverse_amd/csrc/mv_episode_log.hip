@@ -16,6 +16,7 @@
 #include "mv_api_internal.h"
 #include "mv_episode_log.h"
 #include "mv_episode_budget.h"
+#include "mv_macro_step.h"
 
 namespace mv {
 namespace elog {
@@ -39,27 +40,38 @@ struct AgentTicks {
 // The done bits of env e over the launch's ticks and, BUDGET (mv_set_episode_budget): the ticks the env stepped in -- the rule of mv_episode_budget.h walked
 // over the staged dones from the log's mirror of the env's budget; left: the mirror behind the launch's last tick.  A tick the env did not step in staged
 // done 0 (mv_step_kernels.h: frozen_tick); its bit is cleared all the same.
-template <int KT, bool BUDGET>
-__device__ __forceinline__ void load_done(const Args &a, int e, bool in, uint32_t &done, uint32_t &steps, int32_t &left)
+// RULE_MACRO (mv_macro_step: the call's ticks are a macro step's): the rule of mv_macro_step.h walked in the same way from the log's mirror of the envs' ticks
+// left, beside the budget's (a.budget: null when the gym has none); tl: that mirror behind the launch's last tick.
+enum : int { RULE_NONE = 0, RULE_BUDGET = 1, RULE_MACRO = 2 };
+template <int KT, int RULE>
+__device__ __forceinline__ void load_done(const Args &a, int e, bool in, uint32_t &done, uint32_t &steps, int32_t &left, int32_t &tl)
 {
     uint8_t d[KT];
 #pragma unroll
     for (int t = 0; t < KT; ++t) d[t] = a.done[t < a.k ? t : a.k - 1][e];
-    done = 0; steps = ~0u; left = -1;
-    if constexpr (BUDGET) { left = a.budget[e]; steps = 0; }
+    done = 0; steps = ~0u; left = -1; tl = -1;
+    if constexpr (RULE == RULE_BUDGET) { left = a.budget[e]; steps = 0; }
+    if constexpr (RULE == RULE_MACRO) { left = a.budget ? a.budget[e] : -1; tl = a.macro_tl[e]; steps = 0; }
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
-        if constexpr (BUDGET) {
+        if constexpr (RULE == RULE_BUDGET) {
             if (t < a.k && budget::episode_budget_steps(1, left)) {
                 steps |= 1u << t;
                 (void)budget::episode_budget_spend(left, d[t]);
+            }
+        }
+        if constexpr (RULE == RULE_MACRO) {
+            if (t < a.k && macro::macro_steps(1, left, tl)) {
+                steps |= 1u << t;
+                (void)budget::episode_budget_spend(left, d[t]);
+                tl = macro::macro_after_tick(tl, d[t]);
             }
         }
         if (in && t < a.k && d[t] && ((steps >> t) & 1u)) done |= 1u << t;
     }
 }
 
-template <int KT, bool BUDGET>
+template <int KT, int RULE>
 __device__ __forceinline__ void load_agent(const Args &a, int i, int e, bool in, AgentTicks<KT> &v)
 {
     const int ii = in ? i : 0;
@@ -71,13 +83,14 @@ __device__ __forceinline__ void load_agent(const Args &a, int i, int e, bool in,
     }
     v.ret = a.ret[ii];
     v.len = a.len[e];
-    int32_t left;
-    load_done<KT, BUDGET>(a, e, in, v.done, v.steps, left);
+    int32_t left, tl;
+    load_done<KT, RULE>(a, e, in, v.done, v.steps, left, tl);
 }
 
 // KT: the ticks the launch is compiled for (k <= KT; 1: a single-tick call, 16: a batched call's worth)
-// BUDGET: the gym has an episode budget attached (a.budget: the log's mirror); the instantiations without contain no line of it
-template <int KT, bool BUDGET>
+// RULE: RULE_BUDGET: the gym has an episode budget attached (a.budget: the log's mirror); RULE_MACRO: the ticks belong to a macro step (a.macro_tl: the log's
+// mirror of the ticks left; a.budget or null); RULE_NONE: neither -- the instantiations without contain no line of either
+template <int KT, int RULE>
 __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
 {
     __shared__ uint32_t cell[MAX_GROUPS];   // [tick][chunk][wave]: finished agents, then (after the scan) records in the cells before
@@ -89,7 +102,7 @@ __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
     // (mv_set_step_mask) `in` below: the agent exists AND its env steps in this launch (episode_log_steps) -- the agents of a frozen env are passed over like
     // the threads beyond the last agent: no done bit, no tick, and their running return is not written
     AgentTicks<KT> first_chunk;
-    load_agent<KT, BUDGET>(a, tid, tid < NA ? tid / a.A : 0, tid < NA && episode_log_steps(a.step_mask, tid / a.A), first_chunk);
+    load_agent<KT, RULE>(a, tid, tid < NA ? tid / a.A : 0, tid < NA && episode_log_steps(a.step_mask, tid / a.A), first_chunk);
 
     // ---- 1. finished agents per (tick, chunk, wave)
     for (int c = 0; c < chunks; ++c) {
@@ -99,8 +112,8 @@ __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
         uint32_t done = first_chunk.done;
         if (c > 0) {
             uint32_t steps;
-            int32_t left;
-            load_done<KT, BUDGET>(a, e, in, done, steps, left);
+            int32_t left, tl;
+            load_done<KT, RULE>(a, e, in, done, steps, left, tl);
         }
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
@@ -143,7 +156,7 @@ __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
         const bool in = i < NA && episode_log_steps(a.step_mask, i / a.A);
         const int e = in ? i / a.A : 0;
         AgentTicks<KT> v = first_chunk;
-        if (c > 0) load_agent<KT, BUDGET>(a, i, e, in, v);
+        if (c > 0) load_agent<KT, RULE>(a, i, e, in, v);
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
             const bool d = ((v.done >> t) & 1u) != 0;
@@ -160,14 +173,18 @@ __global__ __launch_bounds__(THREADS) void episode_log_kernel(const Args a)
     for (int e = tid; e < a.N; e += THREADS) {
         if (!episode_log_steps(a.step_mask, e)) continue;   // (a frozen env's length stays)
         uint32_t done, steps;
-        int32_t left;
-        load_done<KT, BUDGET>(a, e, true, done, steps, left);
+        int32_t left, tl;
+        load_done<KT, RULE>(a, e, true, done, steps, left, tl);
         int32_t len = a.len[e];
 #pragma unroll
         for (int t = 0; t < KT; ++t)
             if (t < a.k && ((steps >> t) & 1u)) len = ((done >> t) & 1u) ? 0 : len + 1;
         a.len[e] = len;
-        if constexpr (BUDGET) a.budget[e] = left;   // (the mirror: what the step kernels' array held behind the launch's last tick)
+        if constexpr (RULE == RULE_BUDGET) a.budget[e] = left;   // (the mirror: what the step kernels' array held behind the launch's last tick)
+        if constexpr (RULE == RULE_MACRO) {                      // (both mirrors)
+            if (a.budget) a.budget[e] = left;
+            a.macro_tl[e] = tl;
+        }
     }
     if (tid == 0) {
         Header h = *a.hdr;
@@ -180,14 +197,18 @@ void launch_episode_log(const Args &a, hipStream_t stream)
 {
     if (a.k < 1 || a.k > MAX_TICKS) return;   // (load_agent reads tick k - 1 for the ticks beyond k)
     const dim3 grid(1), block(THREADS);
-    if (a.budget) {
-        if (a.k == 1) hipLaunchKernelGGL((episode_log_kernel<1, true>), grid, block, 0, stream, a);
-        else if (a.k <= 4) hipLaunchKernelGGL((episode_log_kernel<4, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((episode_log_kernel<MAX_TICKS, true>), grid, block, 0, stream, a);
+    if (a.macro_tl) {
+        if (a.k == 1) hipLaunchKernelGGL((episode_log_kernel<1, RULE_MACRO>), grid, block, 0, stream, a);
+        else if (a.k <= 4) hipLaunchKernelGGL((episode_log_kernel<4, RULE_MACRO>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((episode_log_kernel<MAX_TICKS, RULE_MACRO>), grid, block, 0, stream, a);
+    } else if (a.budget) {
+        if (a.k == 1) hipLaunchKernelGGL((episode_log_kernel<1, RULE_BUDGET>), grid, block, 0, stream, a);
+        else if (a.k <= 4) hipLaunchKernelGGL((episode_log_kernel<4, RULE_BUDGET>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((episode_log_kernel<MAX_TICKS, RULE_BUDGET>), grid, block, 0, stream, a);
     } else {
-        if (a.k == 1) hipLaunchKernelGGL((episode_log_kernel<1, false>), grid, block, 0, stream, a);
-        else if (a.k <= 4) hipLaunchKernelGGL((episode_log_kernel<4, false>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((episode_log_kernel<MAX_TICKS, false>), grid, block, 0, stream, a);
+        if (a.k == 1) hipLaunchKernelGGL((episode_log_kernel<1, RULE_NONE>), grid, block, 0, stream, a);
+        else if (a.k <= 4) hipLaunchKernelGGL((episode_log_kernel<4, RULE_NONE>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((episode_log_kernel<MAX_TICKS, RULE_NONE>), grid, block, 0, stream, a);
     }
 }
 
@@ -231,6 +252,7 @@ int episode_log_update(mv_gym *g, const GymView *views, int stride, int k)
         a.status = g->dStatus ? g->dStatus + g->N + 1 : nullptr;
         a.step_mask = g->stepMask.live;
         a.budget = g->budgetOn ? g->budgetMirror : nullptr;
+        a.macro_tl = g->macroCall ? g->macroMirror : nullptr;   // (mv_macro_step: the ticks of a macro step)
         launch_episode_log(a, g->stream);
     }
     HIP_TRY(hipGetLastError());
@@ -346,9 +368,10 @@ int64_t mv_ticks_since_reset(const mv_gym *g) { return g && !g->closed ? (int64_
 // count, dropped, ret [N*A] and len [N] in and out; records: the buffer of `capacity` records, *count of them valid on entry.  step_mask [N] or null: the
 // envs it freezes skip every one of the k ticks (episode_log_steps).  left [N] or null (mv_set_episode_budget), in and out: the log's mirror of the budgets,
 // advanced tick by tick by the rule of mv_episode_budget.h -- a tick of a halted env is skipped like a frozen one's.
-int mv_debug_episode_log_budget_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
-                                     uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped, const uint8_t *step_mask,
-                                     int32_t *left)
+// (tl [N] or null, in and out: mv_macro_step -- the log's mirror of the ticks left in the macro step the k ticks belong to, mv_macro_step.h)
+int mv_debug_episode_log_macro_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
+                                    uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped, const uint8_t *step_mask,
+                                    int32_t *left, int32_t *tl)
 {
     using namespace mv::elog;
     if (!rewards || !dones || !true_objectives || !ret || !len || !records || !count || !dropped || k < 0 || N < 1 || A < 1 || capacity < 1)
@@ -362,6 +385,7 @@ int mv_debug_episode_log_budget_host(const float *rewards, const uint8_t *dones,
         for (int e = 0; e < N; ++e) {
             if (!episode_log_steps(step_mask, e)) continue;
             if (left && !mv::budget::episode_budget_steps(1, left[e])) continue;
+            if (tl && !mv::macro::macro_steps(1, -1, tl[e])) continue;
             int32_t after = len[e];
             for (int a = 0; a < A; ++a) {
                 const size_t i = (size_t)e * A + a;
@@ -374,12 +398,21 @@ int mv_debug_episode_log_budget_host(const float *rewards, const uint8_t *dones,
             }
             len[e] = after;
             if (left) (void)mv::budget::episode_budget_spend(left[e], dones[(size_t)t * N + e]);
+            if (tl) tl[e] = mv::macro::macro_after_tick(tl[e], dones[(size_t)t * N + e]);
         }
         (void)episode_log_commit(h, (uint32_t)capacity, placed);
     }
     *count = h.count;
     *dropped = h.dropped;
     return 0;
+}
+
+// ... outside a macro step
+int mv_debug_episode_log_budget_host(const float *rewards, const uint8_t *dones, const float *true_objectives, int32_t k, int32_t N, int32_t A, int32_t capacity,
+                                     uint32_t first_tick, double *ret, int32_t *len, void *records, uint32_t *count, uint32_t *dropped, const uint8_t *step_mask,
+                                     int32_t *left)
+{
+    return mv_debug_episode_log_macro_host(rewards, dones, true_objectives, k, N, A, capacity, first_tick, ret, len, records, count, dropped, step_mask, left, nullptr);
 }
 
 // ... without a budget

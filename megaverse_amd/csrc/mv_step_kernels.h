@@ -14,6 +14,7 @@
 
 #include "mv_episode_budget.h"
 #include "mv_frame.h"
+#include "mv_macro_step.h"
 #include "mv_state_obs.h"
 #include "mv_types.h"
 
@@ -70,23 +71,47 @@ __device__ __forceinline__ void frozen_tick(const GymView &gv, int env)
 //     0    the env does not step in the next tick: frozen by the mask for the whole launch, or halted;
 //   < 0    it steps and has nothing to spend (no budget attached, or unlimited);
 //   > 0    it steps and may still finish that many episodes.
-// and choose per tick between S::tick and frozen_tick, between the same barriers.  Behind a tick that stepped, budget_after_tick reads the done that tick
+// and choose per tick between S::tick and frozen_tick, between the same barriers.  Behind a tick that stepped, after_tick reads the done that tick
 // staged and spends.  Every wave of the workgroup keeps its own copy and sees the same dones behind the same barriers, so the choice stays workgroup-uniform;
 // nobody reads left[env] from memory again within the launch, and the next launch on the stream reads what thread 0 stored.
 __device__ __forceinline__ int32_t env_left(const GymView &gv, int env)
 {
-    if (env_frozen(gv, env)) return 0;   // (never stored: budget_after_tick runs behind stepped ticks only)
+    if (env_frozen(gv, env)) return 0;   // (never stored: after_tick runs behind stepped ticks only)
     return gv.budget != nullptr ? __builtin_amdgcn_readfirstlane(gv.budget[env]) : -1;
 }
 
-// Behind a tick of `gv` that env stepped in, and behind what orders that tick's stores before this load (wave_sync: one wave; the workgroup's barrier:
-// several): the staged done, uniform (as reset_masked_body reads a count back); where it spends, thread 0 stores the env's budget and, when this tick
-// halted the env, counts it (a vector atomic).
-__device__ __forceinline__ void budget_after_tick(const GymView &gv, int env, int32_t &left)
+// ---- mv_macro_step: envs whose macro step is over (mv_macro_step.h has the rule).  A second uniform value beside `left`, carried through the launch's ticks in
+// the same way and read once at the top (env_tl):
+//     0    the env's macro step is over -- its own k ticks are spent, or a tick of this call finished its episode: it does not step in the next tick;
+//   < 0    no macro step in flight (the view carries no array): nothing to count;
+//   > 0    it may step in that many more ticks of the call.
+// An env steps in a tick when left != 0 and tl != 0 (env_steps); behind a tick that stepped, after_tick counts tl down, or clears it where the tick staged
+// done, and thread 0 stores it for the next launch of the call.
+__device__ __forceinline__ int32_t env_tl(const GymView &gv, int env)
 {
-    if (left <= 0) return;
+    return gv.macro_tl != nullptr ? __builtin_amdgcn_readfirstlane(gv.macro_tl[env]) : -1;
+}
+__device__ __forceinline__ bool env_steps(int32_t left, int32_t tl) { return macro::macro_steps(1, left, tl); }   // (the mask: inside left, env_left)
+
+// after_tick's macro half for the one-tick-per-launch kernels, which keep nothing of it across the tick: one thread reads tl and the staged done again and
+// stores.  Not inlined, for state_obs_store's reason (below): inlined, it cost the Obstacles family's kernel six VGPRs and a wave per SIMD.
+static __device__ __attribute__((noinline)) void macro_tick_store(int32_t *tl, const uint8_t *done)
+{
+    *tl = macro::macro_after_tick(*tl, (int)*done);
+}
+
+// Behind a tick of `gv` that env stepped in, and behind what orders that tick's stores before this load (wave_sync: one wave; the workgroup's barrier:
+// several): the staged done, uniform (as reset_masked_body reads a count back); thread 0 stores the ticks the env's macro step has left (mv_macro_step) and,
+// where the budget spends, the env's budget and, when this tick halted the env, counts it (a vector atomic).
+__device__ __forceinline__ void after_tick(const GymView &gv, int env, int32_t &left, int32_t &tl)
+{
+    if (left <= 0 && tl <= 0) return;
     const int done = __builtin_amdgcn_readfirstlane((int)gv.done[env]);
-    if (!done) return;
+    if (tl > 0) {
+        tl = macro::macro_after_tick(tl, done);
+        if (threadIdx.x == 0) gv.macro_tl[env] = tl;
+    }
+    if (!done || left <= 0) return;
     const bool halted = budget::episode_budget_spend(left, done);
     if (threadIdx.x == 0) {
         gv.budget[env] = left;
@@ -157,7 +182,7 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
     __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
 #endif
     [[maybe_unused]] int32_t left = -1;
-    if constexpr (MASKED) if ((left = env_left(gv, env)) == 0) {   // (mv_set_step_mask, mv_set_episode_budget) the frozen tick, then the env's frames as below, from the unchanged state
+    if constexpr (MASKED) if ((left = env_tl(gv, env) == 0 ? 0 : env_left(gv, env)) == 0) {   // (mv_set_step_mask, mv_set_episode_budget) the frozen tick, then the env's frames as below, from the unchanged state
         frozen_tick(gv, env);
         state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs: the unchanged state, as the last launch left it)
         if (!render) return;
@@ -176,9 +201,13 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
 #endif
     if constexpr (S::par_agents && A_MAX > 1) S::template tick<A_MAX, true>(gv, env);
     else if (threadIdx.x < 64) S::template tick<A_MAX>(gv, env);
-    if constexpr (MASKED) if (left > 0) {   // (mv_set_episode_budget; uniform)
-        __syncthreads();   // every wave has read left[env] before thread 0 stores it, and the tick's staged done is written
-        budget_after_tick(gv, env, left);
+    if constexpr (MASKED) if (left > 0 || gv.macro_tl != nullptr) {   // (mv_set_episode_budget, mv_macro_step; uniform)
+        __syncthreads();   // every wave has read left[env] and tl[env] before thread 0 stores them, and the tick's staged done is written
+        [[maybe_unused]] int32_t none = -1;
+        after_tick(gv, env, left, none);
+        // (one tick per launch: tl is not kept across the tick -- this kernel's registers are the tick's -- but read again behind it, by the one thread that
+        // stores it)
+        if (gv.macro_tl != nullptr && threadIdx.x == 0) macro_tick_store(gv.macro_tl + env, gv.done + env);
     }
 #ifdef MV_TICK_TIMING
     if (!render && gv.dbg && threadIdx.x == 0) {
@@ -240,18 +269,18 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
 #ifdef MV_STEP_PRIO
     __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
 #endif
-    [[maybe_unused]] int32_t left = -1;   // (mv_set_step_mask, mv_set_episode_budget: env_left)
-    if constexpr (MASKED) left = env_left(a.view(0), env);
+    [[maybe_unused]] int32_t left = -1, tl = -1;   // (mv_set_step_mask, mv_set_episode_budget: env_left; mv_macro_step: env_tl)
+    if constexpr (MASKED) { left = env_left(a.view(0), env); tl = env_tl(a.view(0), env); }
     [[maybe_unused]] bool drawn = true;   // (mv_set_draw_mask: env_drawn)
     if constexpr (MASKED) drawn = env_drawn(a.view(0), env);
     for (int j = 0; j < a.n; ++j) {
         const GymView &gv = a.view(j);
-        const bool steps = !MASKED || left != 0;   // (uniform; without MASKED: a constant)
+        const bool steps = !MASKED || env_steps(left, tl);   // (uniform; without MASKED: a constant)
         if constexpr (A_MAX == 1) {
             if (steps) S::template tick<1>(gv, env);
             else frozen_tick(gv, env);
             wave_sync();   // the tick's stores before the frame setup's loads (one wave: no barrier needed)
-            if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
+            if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
             if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
             if (!MASKED || drawn) frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
             else env_frames_skip<true, 64, true>(gv, env);
@@ -259,7 +288,7 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
             if (steps) S::template tick<A_MAX, true>(gv, env);
             else frozen_tick(gv, env);
             __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
-            if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
+            if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
             if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
             if (!MASKED || drawn) {
                 const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
@@ -285,12 +314,12 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
 #endif
     // (mv_set_step_mask, mv_set_episode_budget: env_left.  An env that is frozen or halted when a FRAMES = false launch starts leaves behind the loads of
     // env_left and n tiny stores)
-    [[maybe_unused]] int32_t left = -1;
-    if constexpr (MASKED) left = env_left(a.view(0), env);
+    [[maybe_unused]] int32_t left = -1, tl = -1;   // (mv_macro_step: env_tl)
+    if constexpr (MASKED) { left = env_left(a.view(0), env); tl = env_tl(a.view(0), env); }
     if constexpr (!FRAMES) {
         for (int j = 0; j < a.n; ++j) {
             const GymView &gv = a.view(j);
-            const bool steps = !MASKED || left != 0;   // (uniform; without MASKED: a constant)
+            const bool steps = !MASKED || env_steps(left, tl);   // (uniform; without MASKED: a constant)
             if constexpr (A_MAX == 1) {
                 if (steps) S::template tick<1>(gv, env);
                 else frozen_tick(gv, env);
@@ -300,7 +329,7 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
                 else frozen_tick(gv, env);
                 __syncthreads();   // the tick's stores (same CU: same L1) before the next tick's loads
             }
-            if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
+            if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
             if constexpr (MASKED) if (gv.state_obs != nullptr) {   // (mv_set_state_obs; uniform)
                 state_obs_write<A_MAX>(gv, env);
                 if constexpr (A_MAX > 1) __syncthreads();   // the rows' loads before the other waves' next tick changes the state
@@ -315,12 +344,12 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
         for (int j = 0; j < a.n; ++j) {
             const GymView &gv = a.view(j);
             const bool frames = (mask >> j) & 1u;
-            const bool steps = !MASKED || left != 0;   // (uniform; without MASKED: a constant)
+            const bool steps = !MASKED || env_steps(left, tl);   // (uniform; without MASKED: a constant)
             if constexpr (A_MAX == 1) {
                 if (steps) S::template tick<1>(gv, env);
                 else frozen_tick(gv, env);
                 wave_sync();   // the tick's stores before the frame setup's / the next tick's loads
-                if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
+                if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
                 if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
                 if (frames) {
                     if (!MASKED || drawn) frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
@@ -330,7 +359,7 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
                 if (steps) S::template tick<A_MAX, true>(gv, env);
                 else frozen_tick(gv, env);
                 __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's / the next tick's loads
-                if constexpr (MASKED) if (steps) budget_after_tick(gv, env, left);
+                if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
                 if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
                 if (frames) {
                     if (!MASKED || drawn) {
@@ -364,12 +393,12 @@ __device__ __forceinline__ void step_ticks_pipe_body(const Args &a, int W, int H
     if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0) {
         // (mv_set_step_mask, mv_set_episode_budget: env_left) a tick that does not step is the frozen tick at the barriers of a stepping one -- both barriers
         // of the iteration on either side of the choice; wave 1 sets the frames up as always, and only this wave needs to know what is left
-        [[maybe_unused]] int32_t left = -1;
-        if constexpr (MASKED) left = env_left(a.view(0), env);
+        [[maybe_unused]] int32_t left = -1, tl = -1;   // (mv_macro_step: env_tl)
+        if constexpr (MASKED) { left = env_left(a.view(0), env); tl = env_tl(a.view(0), env); }
         for (int j = 0; j < a.n; ++j) {
-            if (!MASKED || left != 0) {
+            if (!MASKED || env_steps(left, tl)) {
                 S::template tick<1>(a.view(j), env, j > 0);   // (j > 0: B(j - 1) inside, before the write-back)
-                if constexpr (MASKED) if (left > 0) { wave_sync(); budget_after_tick(a.view(j), env, left); }   // (this wave's own stores)
+                if constexpr (MASKED) if (left > 0 || tl > 0) { wave_sync(); after_tick(a.view(j), env, left, tl); }   // (this wave's own stores)
             } else {
                 if (j > 0) __syncthreads();               // B(j - 1): inside a tick (pipe_wait), here in the open
                 frozen_tick(a.view(j), env);

@@ -193,7 +193,7 @@ struct GymView {
     // steps.  Set by the stepping calls only (mv_api_step.hip): the views of resets, forks and the union launches leave it null.
     const uint8_t *step_mask;
     // mv_set_episode_budget: [N] episodes each env may still finish (< 0: unlimited, 0: halted -- its ticks are frozen ticks), written by the MASKED step
-    // bodies behind a tick that staged done (mv_step_kernels.h: budget_after_tick), and the count of halted envs they keep; null: no budget.  Set by the
+    // bodies behind a tick that staged done (mv_step_kernels.h: after_tick), and the count of halted envs they keep; null: no budget.  Set by the
     // stepping calls only, like step_mask.
     int32_t *budget;
     uint32_t *halted;
@@ -214,6 +214,10 @@ struct GymView {
     // bodies store every agent's row here (mv_step_kernels.h: state_obs_write), and one launch per stepping call carries the rows to the caller's buffer
     // (mv_state_obs.hip).  null: off.  A field of the per-slot views (mv_gym::gvp), so tick_view leaves it alone; the union launches never see a non-null one.
     float *state_obs;
+    // mv_macro_step: [N] ticks each env may still step in this call (0: its macro step is over -- its ticks are frozen ticks), written by the MASKED step
+    // bodies behind every tick the env stepped in (mv_step_kernels.h: after_tick; mv_macro_step.h has the rule); null: no macro step in flight.  Set by the
+    // views of a macro step's ticks only (mv_api_step.hip).
+    int32_t *macro_tl;
 };
 
 // The n <= 8 consecutive ticks of a multi-tick step launch (mv_step.hip: step_ticks_kernel, and every mv_step_*.hip), the same envs in all of them: their views

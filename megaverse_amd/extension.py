@@ -103,6 +103,9 @@ SYMBOLS = [
     ("mv_set_draw_mask", C.c_int, [_P, _P]), ("mv_set_draw_mask_host", C.c_int, [_P, _P]), ("mv_get_draw_mask", C.c_int, [_P]),
     ("mv_set_state_obs", C.c_int, [_P, _P]), ("mv_get_state_obs", C.c_int, [_P]), ("mv_get_state_observation", C.c_int, [_P, _I, _I, _P]),
     ("mv_debug_state_obs_host", C.c_int, [_P, _P, _P]), ("mv_get_output_ring", C.c_int, [_P]),
+    ("mv_macro_step", C.c_int, [_P, _I, _P, _P, _I]), ("mv_macro_step_host", C.c_int, [_P, _I, _P, _P, _I]),
+    ("mv_debug_episode_log_macro_host", C.c_int, [_P, _P, _P, _I, _I, _I, _I, _U, _P, _P, _P, C.POINTER(_U), C.POINTER(_U), _P, _P, _P]),
+    ("mv_debug_macro_rule_host", C.c_int, [_P, _P, _P, _P, _I, _I, _P, _P, _P]), ("mv_debug_macro_fold_host", C.c_int, [_P, _I, _I, _P]),
 ]
 
 # include/megaverse_hip.h: MV_STATE_OBS_FLOATS and the columns of a state-observation row (mv_set_state_obs), name -> index
@@ -158,6 +161,16 @@ def debug_episode_log_budget_host(step_mask, left, rewards, dones, true_objectiv
     return _episode_log_host(True, step_mask, rewards, dones, true_objectives, agents_per_env, capacity, first_tick, state, budget=(left,))
 
 
+def debug_episode_log_macro_host(step_mask, left, tl, rewards, dones, true_objectives, agents_per_env, capacity, first_tick=0, state=None):
+    """mv_debug_episode_log_macro_host: debug_episode_log_budget_host for the k ticks of one macro step (mv_macro_step) -- tl: int32 [N], the log's mirror of
+    the envs' ticks left, set by the caller to the call's clamped ticks and advanced IN PLACE tick by tick (a contiguous int32 numpy array); None: the
+    hook's NULL, no macro step"""
+    for name, v in (("left", left), ("tl", tl)):
+        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == np.int32 and v.flags.c_contiguous and v.ndim == 1):
+            raise ValueError(f"debug_episode_log_macro_host: {name} is a contiguous int32 numpy array [N], advanced in place")
+    return _episode_log_host(True, step_mask, rewards, dones, true_objectives, agents_per_env, capacity, first_tick, state, budget=(left, tl))
+
+
 def debug_episode_budget_host(dones, mask, left):
     """mv_debug_episode_budget_host: the rule of episode budgets on the CPU (no device).  dones [k][N]: what tick t stages for env e if it steps; mask [N]
     bytes or None; left int32 [N] -> (steps uint8 [k][N]: 1 where the env steps in the tick, left int32 [N] behind the last tick)"""
@@ -172,6 +185,65 @@ def debug_episode_budget_host(dones, mask, left):
     if lib.mv_debug_episode_budget_host(dones.ctypes.data, None if m is None else m.ctypes.data, left.ctypes.data, k, N, steps.ctypes.data, out.ctypes.data) != 0:
         raise RuntimeError(lib.mv_last_error().decode())
     return steps, out
+
+
+def debug_macro_rule_host(dones, mask, left, ticks):
+    """mv_debug_macro_rule_host: the rule of macro steps on the CPU (no device), one call of k ticks.  dones [k][N]: what tick t stages for env e if it steps;
+    mask [N] bytes or None; left int32 [N] or None (no budget: -1 for every env); ticks int32 [N] or None (every env: k) -> (steps uint8 [k][N]: 1 where
+    the env steps in the tick, left int32 [N] and ticks left int32 [N] behind the last tick)"""
+    lib = load_library()
+    dones = np.ascontiguousarray(dones, np.uint8)
+    k, N = dones.shape
+    left = np.full(N, -1, np.int32) if left is None else np.ascontiguousarray(left, np.int32).reshape(-1)
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+    t = None if ticks is None else np.ascontiguousarray(ticks, np.int32).reshape(-1)
+    if left.size != N or (m is not None and m.size != N) or (t is not None and t.size != N):
+        raise ValueError("debug_macro_rule_host: dones is [k][N], mask, left and ticks are [N]")
+    steps, left_out, ticks_out = np.full((k, N), 9, np.uint8), np.full(N, -9, np.int32), np.full(N, -9, np.int32)
+    if lib.mv_debug_macro_rule_host(dones.ctypes.data, None if m is None else m.ctypes.data, left.ctypes.data, None if t is None else t.ctypes.data, k, N,
+                                    steps.ctypes.data, left_out.ctypes.data, ticks_out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return steps, left_out, ticks_out
+
+
+def debug_macro_fold_host(values):
+    """mv_debug_macro_fold_host: the fold of a macro step's rewards on the CPU (no device): values float32 [k][n] -> float32 [n], s = v_0; s = s + v_t in
+    tick order"""
+    lib = load_library()
+    v = np.ascontiguousarray(values, np.float32)
+    if v.ndim != 2 or v.shape[0] < 1 or v.shape[1] < 1:
+        raise ValueError("debug_macro_fold_host: values is [k][n], k >= 1, n >= 1")
+    out = np.empty(v.shape[1], np.float32)
+    if lib.mv_debug_macro_fold_host(v.ctypes.data, v.shape[0], v.shape[1], out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
+
+def check_macro_step_args(actions, ticks, num_envs, num_agents):
+    """the argument check of MegaverseGym.macro_step: actions [num_envs * num_agents, 6] and ticks [num_envs] or None, both int32 -- either contiguous CUDA
+    tensors (-> 'device': read in place) or host arrays (-> contiguous int32 numpy arrays); the two must be of the same kind"""
+    na, n = int(num_envs) * int(num_agents), int(num_envs)
+
+    def one(x, shape, what):
+        if hasattr(x, 'data_ptr'):
+            contiguous = getattr(x, 'is_contiguous', None)
+            if tuple(getattr(x, 'shape', ())) != shape or str(getattr(x, 'dtype', None)) != 'torch.int32' \
+                    or not getattr(x, 'is_cuda', False) or not (callable(contiguous) and contiguous()):
+                raise ValueError(f'macro_step: a tensor of {what} must be a contiguous int32 CUDA tensor of shape {shape}, '
+                                 f"got {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', 'an unknown device')}")
+            return 'device'
+        b = np.asarray(x)
+        if b.shape != shape or b.dtype.kind not in 'iu' or (b.size and (b.min() < -2 ** 31 or b.max() >= 2 ** 31)):
+            raise ValueError(f'macro_step: {what} must be int32 values of shape {shape}, got {b.dtype} {b.shape}')
+        return np.ascontiguousarray(b, dtype=np.int32)
+
+    if actions is None:
+        raise ValueError('macro_step: actions are required')
+    a = one(actions, (na, 6), 'actions')
+    t = None if ticks is None else one(ticks, (n,), 'ticks')
+    if t is not None and isinstance(a, str) != isinstance(t, str):
+        raise ValueError('macro_step: actions and ticks must both be CUDA tensors or both be host arrays')
+    return a, t
 
 
 def _episode_log_host(masked, step_mask, rewards, dones, true_objectives, agents_per_env, capacity, first_tick, state, budget=None):
@@ -201,7 +273,14 @@ def _episode_log_host(masked, step_mask, rewards, dones, true_objectives, agents
             left = budget[0]
             if left is not None and left.size != N:
                 raise ValueError("debug_episode_log_budget_host: left is [N]")
-            rc = lib.mv_debug_episode_log_budget_host(*args, None if m is None else m.ctypes.data, None if left is None else left.ctypes.data)
+            if len(budget) > 1:   # (debug_episode_log_macro_host)
+                tl = budget[1]
+                if tl is not None and tl.size != N:
+                    raise ValueError("debug_episode_log_macro_host: tl is [N]")
+                rc = lib.mv_debug_episode_log_macro_host(*args, None if m is None else m.ctypes.data, None if left is None else left.ctypes.data,
+                                                         None if tl is None else tl.ctypes.data)
+            else:
+                rc = lib.mv_debug_episode_log_budget_host(*args, None if m is None else m.ctypes.data, None if left is None else left.ctypes.data)
     if rc != 0:
         raise RuntimeError(lib.mv_last_error().decode())
     state["count"], state["dropped"] = int(count.value), int(dropped.value)
@@ -586,6 +665,7 @@ class MegaverseGym:
         self._step_mask_held = None  # set_step_mask: the caller's device mask, kept until it is replaced or detached
         self._draw_mask_held = None  # set_draw_mask: the caller's device mask, kept until it is replaced or detached
         self._state_obs = None       # set_state_obs: the attached tensor
+        self._macro_held = None      # macro_step: the caller's device tensors of the last call, read in stream order: kept until the next macro step
         self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
         self._store_held = []    # save_envs / load_envs: the caller's stores and device maps, kept until the next step has been enqueued
 
@@ -720,6 +800,26 @@ class MegaverseGym:
         self._fork_held = self._reset_held = self._budget_held = None
         self._store_held = []
         self._seed_held = []
+
+    def macro_step(self, k, actions, ticks=None, render="last"):
+        """A macro step (include/megaverse_hip.h: mv_macro_step): the actions -- int32 [num_agents, 6], multi-discrete -- are held for up to k ticks, every
+        env stops at its own first done (it then stands on the first frame of its next episode), and the call leaves ONE set of outputs: the rewards summed
+        in tick order (fp32, left to right), the dones OR-ed, and with render='last' the frame behind the call's last tick ('none': nothing is drawn).  With
+        an output ring the call fills one entry.  ticks: None (every env: k) or int32 [num_envs], clamped to [0, k] -- env e holds its action for ticks[e]
+        ticks; 0: it does not step.  Contiguous int32 CUDA tensors are read in place, in the order of the gym's stream, without a host synchronisation (the
+        gym holds a reference until the next stepping call has been enqueued; leave them unchanged until the stream has passed the call); numpy arrays or
+        lists are copied through a staging buffer.  render='every' is refused: a decision has one frame."""
+        mode = render_mode_of(render)
+        a, t = check_macro_step_args(actions, ticks, self.num_envs, self.num_agents_per_env)
+        if isinstance(a, str):
+            rc = self._lib.mv_macro_step(self._g, int(k), _P(int(actions.data_ptr())), None if t is None else _P(int(ticks.data_ptr())), mode)
+        else:
+            rc = self._lib.mv_macro_step_host(self._g, int(k), a.ctypes.data, None if t is None else t.ctypes.data, mode)
+        self._ckw(rc)
+        self._fork_held = self._reset_held = self._budget_held = None
+        self._store_held = []
+        self._seed_held = []
+        self._macro_held = (actions, ticks) if isinstance(a, str) else None   # (read in the order of the gym's stream, which need not be torch's current one)
 
     def fork_envs(self, src_of):
         """Env forks (include/megaverse_hip.h: mv_fork_envs): src_of[d] = s makes env d leave its running episode and continue env s's from s's current

@@ -68,7 +68,12 @@ def check_sequence_actions(actions, num_agents):
 
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
-                 img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False):
+                 img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1):
+        if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
+            raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
+        # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
+        # env stops at its own first done, rewards are the sums, dones the ORs, the observation the frame behind the last tick.  1: every path as it always was.
+        self.frame_skip = int(frame_skip)
         if obs_layout not in ("rgba", "chw"):
             raise ValueError("obs_layout must be 'rgba' (frames written as (H, W, 4) RGBA, handed out as a permuted view) or 'chw' (written as (3, H, W))")
         scenario_name = scenario_name.casefold()
@@ -172,10 +177,22 @@ class MegaverseEnv:
         self.env.reset()
         return self.observations()
 
+    def _held_actions(self, actions, who):
+        """what a frame_skip > 1 step hands to macro_step: a CUDA tensor as int32 [num_agents, 6] (a converted copy where needed), anything else as numpy"""
+        if actions is None:
+            raise ValueError(f"{who}: with frame_skip > 1 the call holds its actions for the macro step: actions=None (keep what was set) has nothing to hold")
+        if hasattr(actions, 'data_ptr'):
+            torch = self._torch()
+            return actions.to(dtype=torch.int32).contiguous().reshape(self.num_agents, 6)
+        return np.asarray(actions, dtype=np.int32).reshape(self.num_agents, 6)
+
     def step(self, actions):
         self._leave_sequence()
-        self.env.set_actions_batched(np.asarray(actions, dtype=np.int32).reshape(self.num_agents, -1))
-        self.env.step()
+        if self.frame_skip > 1:
+            self.env.macro_step(self.frame_skip, self._held_actions(actions, 'step'), render="last")
+        else:
+            self.env.set_actions_batched(np.asarray(actions, dtype=np.int32).reshape(self.num_agents, -1))
+            self.env.step()
         dones_env = self.env.get_dones().astype(bool)
         A = self.num_agents_per_env
         dones = np.repeat(dones_env, A).tolist()          # (megaverse_env.py:149-150: the env's done, once per agent)
@@ -221,6 +238,9 @@ class MegaverseEnv:
         self._leave_sequence()
         if self._obs_tensor is None:
             self.observations_tensor()   # (allocates: before the action buffer is handed over, not between hand-over and step)
+        if self.frame_skip > 1:
+            self.env.macro_step(self.frame_skip, self._held_actions(actions, 'step_batched'), render="last")
+            return self.observations_tensor(), self.env.get_rewards_array(), self.env.get_dones().astype(bool)
         held = None
         if actions is not None:
             if hasattr(actions, 'data_ptr'):
@@ -250,6 +270,9 @@ class MegaverseEnv:
             dev = self._obs_tensor.device
             self._dev_out = (torch.zeros(self.num_agents, dtype=torch.float32, device=dev), torch.zeros(self.num_envs, dtype=torch.uint8, device=dev))
             self._set_output_ring(1, self._obs_tensor.data_ptr(), self._dev_out[0].data_ptr(), self._dev_out[1].data_ptr())
+        if self.frame_skip > 1:
+            self.env.macro_step(self.frame_skip, self._held_actions(actions, 'step_device'), render="last")   # (the gym holds the tensors it reads)
+            return self._obs_view(), self._dev_out[0], self._dev_out[1]
         held = None
         if actions is not None:
             if hasattr(actions, 'data_ptr'):   # (the lifetime rule of step_batched)
@@ -259,6 +282,28 @@ class MegaverseEnv:
                 self.env.set_actions_batched(actions)
         self.env.step()
         del held
+        return self._obs_view(), self._dev_out[0], self._dev_out[1]
+
+    def macro_step(self, actions, k=None, ticks=None, render="last"):
+        """One decision held for up to k ticks (default: this env's frame_skip) -- MegaverseGym.macro_step with step_device's outputs and no host
+        synchronisation: (obs uint8 (num_agents, 3, H, W), rewards float32 [num_agents], dones uint8 [num_envs]), CUDA tensors valid in the order of the gym's
+        stream until the next step.  Every env stops at its own first done; rewards are the call's sums (fp32, in tick order), dones the ORs, obs the frame
+        behind the call's last tick (render='none': obs is what it was).  ticks: None, or int32 [num_envs] -- env e holds its action for min(ticks[e], k)
+        ticks, 0: it does not step (options, dynamic frame skip, "wait d ticks"); a CUDA tensor of actions takes a CUDA tensor of ticks, a host array a host
+        array."""
+        torch = self._torch()
+        if self._obs_tensor is None:
+            self.observations_tensor()
+        self._leave_sequence()
+        if self._dev_out is None:
+            dev = self._obs_tensor.device
+            self._dev_out = (torch.zeros(self.num_agents, dtype=torch.float32, device=dev), torch.zeros(self.num_envs, dtype=torch.uint8, device=dev))
+            self._set_output_ring(1, self._obs_tensor.data_ptr(), self._dev_out[0].data_ptr(), self._dev_out[1].data_ptr())
+        if ticks is not None and hasattr(ticks, 'data_ptr'):
+            ticks = ticks.to(dtype=torch.int32).contiguous()
+        elif ticks is not None:
+            ticks = np.asarray(ticks, dtype=np.int32).reshape(self.num_envs)
+        self.env.macro_step(self.frame_skip if k is None else int(k), self._held_actions(actions, 'macro_step'), ticks=ticks, render=render)
         return self._obs_view(), self._dev_out[0], self._dev_out[1]
 
     def fork(self, src_env, dst_envs=None):

@@ -158,6 +158,12 @@ class MultiTaskGym:
             g.set_action_ring(count, ring.data_ptr())
         return self.action_rings
 
+    def macro_step(self, k, actions, ticks=None, render="last"):
+        """macro steps (MegaverseGym.macro_step) are per gym: mv_macro_step refuses a gym in an mv_group, and a multi-task batch has no call that holds one
+        decision over k ticks of every sub-gym -- not provided"""
+        raise RuntimeError("MultiTaskGym.macro_step: not provided -- mv_macro_step refuses a gym that belongs to an mv_group (the union launches know no "
+                           "macro steps); use one MegaverseGym per task and call its macro_step")
+
     def set_episode_budget(self, budget):
         """episode budgets (MegaverseGym.set_episode_budget) are per gym: a group's union launches read none, and the library refuses"""
         if self._group is not None and budget is not None:

@@ -223,6 +223,19 @@ public:
         }
         check_or_warn(mv_seed_envs_host(gym_, words.data()));
     }
+    // macro steps (mv_macro_step_host): the actions [num_envs * num_agents_per_env][6] are held for up to k ticks, every env stops at its own first done,
+    // one summed reward, one done and (render = "last") one frame per call; ticks: None (every env: k) or one int per env, clamped to [0, k]
+    void macro_step(int k, py::array_t<int32_t, py::array::c_style | py::array::forcecast> actions, const py::object &ticks, const std::string &render)
+    {
+        if (render != "last" && render != "none") throw std::runtime_error("macro_step: render is 'last' or 'none' (a decision has one frame)");
+        if (actions.size() != py::ssize_t(envs_) * agents_ * 6) throw std::runtime_error("macro_step: expected num_envs * num_agents_per_env * 6 action values");
+        std::vector<int32_t> t;
+        if (!ticks.is_none()) {
+            t = ticks.cast<std::vector<int32_t>>();
+            if ((int)t.size() != envs_) throw std::runtime_error("macro_step: one ticks value per env");
+        }
+        check_or_warn(mv_macro_step_host(gym_, k, actions.data(), ticks.is_none() ? nullptr : t.data(), render == "last" ? MV_RENDER_LAST : MV_RENDER_NONE));
+    }
     std::uintptr_t episode_budget_device_ptr() const { return reinterpret_cast<std::uintptr_t>(mv_episode_budget_device_ptr(gym_)); }
     std::uintptr_t halted_count_device_ptr() const { return reinterpret_cast<std::uintptr_t>(mv_halted_count_device_ptr(gym_)); }
 
@@ -275,5 +288,6 @@ PYBIND11_MODULE(megaverse, m)
         .def("halted_count", &Gym::halted_count)
         .def("episode_budget_device_ptr", &Gym::episode_budget_device_ptr)
         .def("halted_count_device_ptr", &Gym::halted_count_device_ptr)
-        .def("seed_envs", &Gym::seed_envs);
+        .def("seed_envs", &Gym::seed_envs)
+        .def("macro_step", &Gym::macro_step, py::arg("k"), py::arg("actions"), py::arg("ticks") = py::none(), py::arg("render") = "last");
 }

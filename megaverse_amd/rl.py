@@ -41,6 +41,9 @@ class Wrapper:
         self.increase_team_spirit = increase_team_spirit
         self.max_team_spirit_steps = max_team_spirit_steps
         self.training_info = {}          # TrainingInfoInterface: the learner writes approx_total_training_steps here
+        # MegaverseEnv(..., frame_skip=k): every step of this wrapper is then one macro step -- k ticks at most, rewards summed, one frame -- and the
+        # bookkeeping below counts decisions, as the reference's does under a frame-skip wrapper
+        self.frame_skip = getattr(env, "frame_skip", 1)
 
     def set_training_info(self, training_info):
         self.training_info = training_info
@@ -163,7 +166,7 @@ class Wrapper:
 def make_megaverse(env_name, cfg=None, env_config=None, render_mode: Optional[str] = None, **kwargs):
     """Sample-Factory env factory with the reference's signature (megaverse_utils.py:96-122): `env_name` is a scenario or a
     `multitask_*` set (the worker index picks the task), `cfg` carries the megaverse_* options (megaverse_params.py:23-54).  Extra
-    keyword arguments (img_w, img_h, device, params, ...) go to MegaverseEnv."""
+    keyword arguments (img_w, img_h, device, params, frame_skip, ...) go to MegaverseEnv."""
     cfg = cfg or DEFAULT_CFG
     sim = dict(num_envs=cfg.megaverse_num_envs_per_instance, num_agents_per_env=cfg.megaverse_num_agents_per_env,
                num_simulation_threads=cfg.megaverse_num_simulation_threads, use_vulkan=cfg.megaverse_use_vulkan)
