@@ -262,6 +262,31 @@ int mv_get_step_mask(const mv_gym *g);                         /* 0: none, 1: de
 int mv_set_draw_mask(mv_gym *g, const uint8_t *device_mask);   /* [N] in device memory, read in place; NULL detaches */
 int mv_set_draw_mask_host(mv_gym *g, const uint8_t *mask);     /* [N] in host memory, copied through a pinned staging buffer; NULL detaches */
 int mv_get_draw_mask(const mv_gym *g);                         /* 0: none, 1: device form, 2: host form; -1: no gym */
+/* Still frames (no reference counterpart: the reference draws every env of every step).  An env that did not step -- frozen by a step mask, halted by its
+ * episode budget, stopped inside a macro step -- has the state it had, and drawing it again leaves the bytes the last drawing left.  on != 0: in every later
+ * observation pass of the stepping calls (mv_step; mv_step_n and mv_step_n_render in every mode and policy; mv_macro_step) an env's A frames are set up and
+ * drawn only where the env's state may have changed since its frames were drawn last.  Otherwise no frame is set up and no ray is cast, and the env's rows
+ * show the frame drawn last: in the single observation slab they are left alone; in an output ring (mv_set_output_ring with an observation ring) the rows of
+ * the tick's entry are copied on the device from the entry that holds the env's latest frame, by ONE launch per stepping call behind the call's passes (a
+ * source row is read once and stored to every still entry of the call).
+ * The promise: rewards, dones, true objectives, state, status words, the episode log, state observations and EVERY BYTE of every observation row are those
+ * of a twin gym with the option off.  Undrawn rows of a draw mask (mv_set_draw_mask) stay untouched as always, and such an env counts as not drawn.
+ * The rule (megaverse_amd/csrc/mv_still_frames.h states it for kernels and host alike): one byte `stale` per env, all 1 when the option is switched on.  A
+ * tick the env stepped in sets it, with or without a pass (MV_RENDER_NONE ticks, the undrawn ticks of MV_RENDER_LAST); a pass that draws the env clears it; a
+ * frozen, halted or macro-stopped tick leaves it alone.  Every call that can change an env's state, or what or where the gym draws, sets ALL bytes with one
+ * memset on the gym's stream: mv_reset, mv_reset_envs*, mv_fork_envs*, mv_resample_envs*, mv_load_envs*, mv_seed, mv_render, mv_set_obs_buffer,
+ * mv_set_output_ring, mv_set_obs_layout, mv_set_pixel_mode, mv_set_render_resolution and the mv_debug_set_* setters.  Conservative on purpose: a planner that
+ * forks every iteration redraws its frozen root once per iteration.  Within one call an env's passes are a drawn prefix followed by a still suffix.
+ * A caller that writes into observation rows itself must not expect a still env's rows to be drawn over.
+ * Default: off, and a gym that never switches it on launches the kernels it launched, argument for argument.  While on, the step launches are the MASKED
+ * kernels, never the two-wave software-pipelined one, and with an observation ring attached overlapped passes (mv_set_pass_overlap) are not taken: pass c + 1
+ * on its side stream could draw into the entry the carry of call c is still reading when the ring is exactly two calls deep.  mv_set_pass_overlap stays
+ * accepted; the calls simply run in order.  mv_draw_hires ignores the option.
+ * Ordering: mv_set_draw_mask's.  Switching it on or off is an ordering point and never waits on the host.  The gym's arrays (N bytes and N*A int32) are
+ * allocated when the option is first switched on, counted in mv_arena_bytes and freed by mv_close.
+ * Refused (-1 with text): no gym, a closed gym, a gym in an mv_group; mv_group_create and mv_step_many refuse a gym that has it on. */
+int mv_set_still_frames(mv_gym *g, int32_t on);
+int mv_get_still_frames(const mv_gym *g);                      /* 0: off, 1: on; -1: no gym */
 /* State observations (no reference counterpart: the reference hands out pixels, rewards and dones).  One row of MV_STATE_OBS_FLOATS = 16 float32 per agent,
  * agent-major [N*A][16], taken from the env's state AFTER the tick, auto-reset included: a tick that finished an episode shows the first state of the next
  * episode, as its frame does.  Columns (megaverse_amd/csrc/mv_state_obs.h states them for kernels and host alike):
@@ -668,6 +693,17 @@ int mv_debug_macro_rule_host(const uint8_t *dones, const uint8_t *mask, const in
                              uint8_t *steps_out, int32_t *left_out, int32_t *ticks_out);
 /* Host-only (no device): the fold of a macro step's rewards (mv_macro_step.h: macro_fold): values [k][n] -> out [n], s = v_0; s = s + v_t in tick order. */
 int mv_debug_macro_fold_host(const float *values, int32_t k, int32_t n, float *out);
+/* Host-only (no device): the rule of still frames (megaverse_amd/csrc/mv_still_frames.h) over k ticks of N envs.  steps [k][N]: 1 where the env steps in the
+ * tick; has_pass [k]: 1 where the tick has an observation pass; draw_mask [N] or NULL; stale_in [N].  verdict_out [k][N]: 0 no pass, 1 drawn, -1 user-undrawn,
+ * -2 still; stale_out [N]: the bytes behind the last tick. */
+int mv_debug_still_rule_host(const uint8_t *steps, const uint8_t *has_pass, const uint8_t *draw_mask, const uint8_t *stale_in, int32_t k, int32_t N,
+                             int32_t *verdict_out, uint8_t *stale_out);
+/* Host-only (no device): the carry of still frames (mv_still_frames.h: still_carry_plan, the plan mv_set_still_frames' carry launch walks) over the k rendered
+ * ticks of one call.  verdict [k][frames]: what the passes read for the frame (>= 0: drawn, -1: user-undrawn, -2: still); entries [k]: the ring entry of each
+ * tick, 0 .. R - 1; ring_bytes [R][frames][frame_bytes], copied in place; home [frames], in and out: the entry that holds each frame's latest bytes (-1:
+ * none). */
+int mv_debug_still_carry_host(const int32_t *verdict, const int32_t *entries, int32_t k, int32_t frames, int32_t R, int32_t frame_bytes,
+                              uint8_t *ring_bytes, int32_t *home);
 /* Host-only (no device): the episode log's masked clear (megaverse_amd/csrc/mv_episode_log.h: episode_log_cut, the source mv_reset_envs' kernel runs) over N
  * envs x A agents: where mask[e] != 0, ret[e * A .. e * A + A - 1] and len[e] go to zero; everything else stays. */
 int mv_debug_episode_log_cut_host(const uint8_t *mask, int32_t N, int32_t A, double *ret, int32_t *len);

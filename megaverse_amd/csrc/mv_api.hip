@@ -787,6 +787,7 @@ int mv_close(mv_gym *g)
     state_obs_free(g);
     episode_budget_free(g);
     macro_step_free(g);
+    still_frames_free(g);
     if (g->arena) (void)hipFree(g->arena);
     if (g->hiresObs) (void)hipFree(g->hiresObs);
     if (g->hBlobs) (void)(g->blobsOnDevice ? hipFree(g->hBlobs) : hipHostFree(g->hBlobs));
@@ -852,6 +853,7 @@ int mv_set_obs_buffer(mv_gym *g, void *p)
     if (check(g)) return -1;
     if (p && g->obsLayout == MV_OBS_RGB_PLANAR && (uintptr_t)p % planar_alignment(g->w))
         return fail("mv_set_obs_buffer: a planar slab of this width must be " + std::to_string(planar_alignment(g->w)) + "-byte aligned");
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     g->obs = p ? (uint32_t *)p : g->ownedObs;
     g->layoutFixed = true;
     return 0;
@@ -864,6 +866,7 @@ int mv_set_obs_layout(mv_gym *g, int32_t layout)
     if (g->inGroup) return fail("mv_set_obs_layout: the gym belongs to a group (set the layout before mv_group_create)");
     if (g->layoutFixed)
         return fail("mv_set_obs_layout: call it before the gym's first mv_reset, mv_render, mv_set_obs_buffer or mv_set_output_ring");
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     g->obsLayout = layout;
     g->gv.obs_layout = layout;
     for (GymView &v : g->gvp) v.obs_layout = layout;   // (every launch's view is a slot's: view())
@@ -876,6 +879,7 @@ int mv_set_pixel_mode(mv_gym *g, int32_t mode)
 {
     if (check(g)) return -1;
     if (mode != MV_PIXELS_EXACT && mode != MV_PIXELS_FAST) return fail("mv_set_pixel_mode: mode must be MV_PIXELS_EXACT (0) or MV_PIXELS_FAST (1)");
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     g->fastPixels = mode;
     return 0;
 }
@@ -897,6 +901,7 @@ int mv_seed(mv_gym *g, int32_t seed)
 {   // MegaverseGym::seed, megaverse.cpp:60-69: master rng -> one randRange(0, 1<<30) per env
     if (check(g)) return -1;
     HIP_TRY(hipSetDevice(g->device));
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     g->rng.seed((unsigned long)seed);
     std::vector<uint32_t> seeds(g->N);
     for (int i = 0; i < g->totalEnvs; ++i) {
@@ -935,6 +940,7 @@ int mv_seed(mv_gym *g, int32_t seed)
 int mv_render(mv_gym *g)
 {
     if (check(g)) return -1;
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     if (render_frames(g)) return -1;
     return state_obs_refresh(g, nullptr);   // (mv_set_state_obs: the last tick's rows from the current state, as its frames; also behind mv_reset)
 }
@@ -1190,6 +1196,7 @@ int mv_reset(mv_gym *g)
     if (check(g)) return -1;
     HIP_TRY(hipSetDevice(g->device));
     if (sim_join(g)) return -1;
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     g->layoutFixed = true;
     if (flush_device_actions(g)) return -1;   // (a buffer handed over before the reset is read now, not by whatever step comes after it)
     if (g->hostEpisodes()) {
@@ -1296,6 +1303,7 @@ int mv_set_output_ring(mv_gym *g, int32_t count, void *obs, float *rewards, uint
     if (count > 0 && obs && g->obsLayout == MV_OBS_RGB_PLANAR && (uintptr_t)obs % planar_alignment(g->w))
         return fail("mv_set_output_ring: a planar ring of this width must be " + std::to_string(planar_alignment(g->w)) + "-byte aligned");
     if (sim_join(g)) return -1;   // (ticks in flight keep the pointers they were given)
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     g->layoutFixed = true;
     g->ringCount = count; g->ringTick = 0;
     g->ringObs = count ? (uint8_t *)obs : nullptr; g->ringRewards = count ? rewards : nullptr; g->ringDone = count ? dones : nullptr;
@@ -1423,6 +1431,7 @@ int mv_set_render_resolution(mv_gym *g, int32_t w, int32_t h)
 {
     if (check(g)) return -1;
     if (w < 1 || h < 1) return fail("mv_set_render_resolution: bad size");
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     g->renderW = w; g->renderH = h;
     return 0;
 }

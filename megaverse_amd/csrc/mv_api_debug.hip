@@ -1,6 +1,7 @@
 // megaverse_amd/csrc/mv_api_debug.hip -- test hooks of the C ABI (include/megaverse_hip.h: mv_debug_*): state snapshots in the oracle's layout, pose setters,
 // the host-side episode generators and the feeder without a device, the device's RNG helpers and single fp32 operations.  Used by tests/ only.
 #include "mv_api_internal.h"
+#include "mv_still_frames.h"
 
 __global__ void set_agent_pos_kernel(AgentState *agents, int idx, float x, float y,
                                      float z) { agents[idx].pos[0] = x; agents[idx].pos[1] = y; agents[idx].pos[2] = z; }
@@ -83,6 +84,7 @@ int mv_debug_set_agent_pos(mv_gym *g, int32_t env, int32_t agent, float x, float
     if (check(g)) return -1;
     if (env < 0 || env >= g->N || agent < 0 || agent >= g->A) return fail("mv_debug_set_agent_pos: index out of range");
     if (sim_join(g)) return -1;
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     hipLaunchKernelGGL(set_agent_pos_kernel, dim3(1), dim3(1), 0, g->stream, g->gv.agents, env * g->A + agent, x, y, z);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -93,6 +95,7 @@ int mv_debug_set_agent_yaw(mv_gym *g, int32_t env, int32_t agent, float c, float
     if (check(g)) return -1;
     if (env < 0 || env >= g->N || agent < 0 || agent >= g->A) return fail("mv_debug_set_agent_yaw: index out of range");
     if (sim_join(g)) return -1;
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     hipLaunchKernelGGL(set_agent_yaw_kernel, dim3(1), dim3(1), 0, g->stream, g->gv.agents, env * g->A + agent, c, s);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -103,6 +106,7 @@ int mv_debug_set_agent_velocity(mv_gym *g, int32_t env, int32_t agent, float hvx
     if (check(g)) return -1;
     if (env < 0 || env >= g->N || agent < 0 || agent >= g->A) return fail("mv_debug_set_agent_velocity: index out of range");
     if (sim_join(g)) return -1;
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     hipLaunchKernelGGL(set_agent_velocity_kernel, dim3(1), dim3(1), 0, g->stream, g->gv.agents, env * g->A + agent, hvx, hvz, vvel);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -359,6 +363,7 @@ int mv_debug_set_football_state(mv_gym *g, int32_t env, const void *in)
     r.a[0] = s.pos[0]; r.a[1] = s.pos[1]; r.a[2] = s.pos[2]; r.meta = HEX_SPHERE;
     r.b[0] = s.radius; r.b[1] = s.radius; r.b[2] = s.radius; r.color = 0xffb400;   // (mv_tick_football.h: ball_rec)
     if (sim_join(g)) return -1;
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     HIP_TRY(hipMemcpyAsync(g->gv.fb + env, &s, sizeof s, hipMemcpyHostToDevice, g->stream));
     HIP_TRY(hipMemcpyAsync(g->gv.hex_objs + (size_t)env * HEX_MAX_OBJS, &r, sizeof r, hipMemcpyHostToDevice, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));   // (s, r: host stack)
@@ -439,6 +444,47 @@ int mv_debug_raster_div_host(uint32_t d, uint32_t n_end, uint32_t *magic, uint32
     const uint32_t m = raster_div_magic(d);
     if (magic) *magic = m;
     if (q) for (uint32_t n = 0; n < n_end; ++n) q[n] = raster_div_by_magic(n, m);   // (the kernels' div_magic: __umulhi)
+    return 0;
+}
+
+// The rule of mv_still_frames.h compiled for the CPU (no device): k ticks of N envs, in the order the MASKED step bodies apply it -- behind the tick's `steps`
+// choice, then behind the frame choice of a tick that has a pass.
+int mv_debug_still_rule_host(const uint8_t *steps, const uint8_t *has_pass, const uint8_t *draw_mask, const uint8_t *stale_in, int32_t k, int32_t N,
+                             int32_t *verdict_out, uint8_t *stale_out)
+{
+    if (!steps || !has_pass || !stale_in || !verdict_out || !stale_out || k < 0 || N < 1) return fail("mv_debug_still_rule_host: bad arguments");
+    for (int32_t e = 0; e < N; ++e) {
+        int stale = stale_in[e] != 0 ? 1 : 0;
+        for (int32_t t = 0; t < k; ++t) {
+            stale = mv::still::still_after_tick(stale, steps[(size_t)t * N + e] != 0);
+            int v = mv::still::VERDICT_NO_PASS;
+            if (has_pass[t]) {
+                v = mv::still::still_verdict(draw_mask ? (int)draw_mask[e] : 1, stale);
+                stale = mv::still::still_after_frames(stale, v);
+            }
+            verdict_out[(size_t)t * N + e] = v;
+        }
+        stale_out[e] = (uint8_t)stale;
+    }
+    return 0;
+}
+
+// The carry of mv_still_frames.h compiled for the CPU (no device): every frame's plan, then its copies in tick order, each from the plan's source entry.
+int mv_debug_still_carry_host(const int32_t *verdict, const int32_t *entries, int32_t k, int32_t frames, int32_t R, int32_t frame_bytes,
+                              uint8_t *ring_bytes, int32_t *home)
+{
+    if (!verdict || !entries || !ring_bytes || !home || k < 0 || k > (int32_t)PIPE_BATCH_MAX || frames < 1 || R < 1 || frame_bytes < 1)
+        return fail("mv_debug_still_carry_host: bad arguments (k <= 16)");
+    for (int32_t j = 0; j < k; ++j)
+        if (entries[j] < 0 || entries[j] >= R) return fail("mv_debug_still_carry_host: entry out of range");
+    const size_t fb = (size_t)frame_bytes, eb = (size_t)frames * fb;
+    for (int32_t f = 0; f < frames; ++f) {
+        int32_t src[PIPE_BATCH_MAX];
+        const int32_t h = home[f];
+        home[f] = mv::still::still_carry_plan(verdict + f, (size_t)frames, entries, k, h >= 0 && h < R ? h : -1, src);
+        for (int32_t j = 0; j < k; ++j)
+            if (src[j] >= 0) std::memcpy(ring_bytes + (size_t)entries[j] * eb + (size_t)f * fb, ring_bytes + (size_t)src[j] * eb + (size_t)f * fb, fb);
+    }
     return 0;
 }
 

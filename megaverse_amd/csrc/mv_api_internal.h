@@ -12,6 +12,7 @@
 //   mv_state_obs.hip  state observations: attaching the caller's buffer, the staging rows, their publication and refresh (mv_state_obs.h: the record)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 //   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
+//   mv_still_frames.hip  still frames: switching the option, the memset behind calls that change what frames show, the carry launch (mv_still_frames.h: the rule)
 // mv_staging.h holds the two ways the host forms' values reach the device (StagingPool, StagingPair).
 // The C ABI itself is include/megaverse_hip.h; nothing here is exported under a C name.
 #pragma once
@@ -290,6 +291,13 @@ struct mv_gym {
     size_t macroBytes = 0;
     StagingPool macroPool;
     const MacroCall *macroCall = nullptr;
+    // mv_set_still_frames: one gym-owned allocation (mv_still_frames.h: still_frames_bytes), made when the option is first switched on, kept until mv_close
+    // and counted in mv_arena_bytes -- stillHome [N*A], the ring entry that holds each frame's latest drawn bytes (the carry launch's own), and stillStale [N],
+    // what the step kernels read and write (GymView::still, through the stepping calls' views, while stillOn).
+    int32_t *stillHome = nullptr;
+    uint8_t *stillStale = nullptr;
+    size_t stillBytes = 0;
+    bool stillOn = false;
     // in-stream profiling
     std::vector<hipEvent_t> profEvents;          // 5 per profiled tick: [0] [1] around the step kernel (its stream), [2] [3] [4] before the
                                                  // observation pass, between frame sort and raster, after the raster (the caller's stream)
@@ -334,6 +342,12 @@ void episode_log_free(mv_gym *g);   // mv_close
 void env_masks_free(mv_gym *g);     // mv_close (mv_env_masks.hip)
 void episode_budget_free(mv_gym *g);   // mv_close (mv_episode_budget.hip)
 void macro_step_free(mv_gym *g);       // mv_close (mv_macro_step.hip)
+// mv_still_frames.hip.  touch: every env stale -- one memset on the caller's stream, for every call that can change an env's state or what or where the gym
+// draws (off: nothing).  carry: the rows of the still frames of one stepping call's n rendered ticks (views[j * stride], outs[j * stride]) from the ring
+// entries that hold them, one launch on the caller's stream behind the call's passes
+void still_frames_free(mv_gym *g);     // mv_close
+int still_frames_touch(mv_gym *g);
+int still_frames_carry(mv_gym *g, const GymView *views, const OutPtrs *outs, int stride, int n);
 // mv_macro_step.hip: the staged outputs of the k ticks in slots q0 .. q0 + k - 1 folded into ONE entry o -- rewards summed in tick order (mv_macro_step.h:
 // macro_fold), dones OR-ed, true objectives as publish_ticks -- with one launch on the caller's stream; cont: the entry holds the fold of the call's earlier chunks
 int publish_macro(mv_gym *g, int q0, const OutPtrs &o, int k, bool cont);

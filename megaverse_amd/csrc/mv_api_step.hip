@@ -172,6 +172,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
             v.step_mask = g->stepMask.live;   // (mv_set_step_mask; a group's members have none)
             v.draw_mask = g->drawMask.live;   // (mv_set_draw_mask; likewise)
             if (g->budgetOn) { v.budget = g->budgetLeft; v.halted = g->budgetHalted; }   // (mv_set_episode_budget; likewise)
+            if (g->stillOn) v.still = g->stillStale;   // (mv_set_still_frames; likewise)
             if (mc) { v.macro_tl = g->macroTl; v.md_actions = mc->actions; }   // (mv_macro_step: the held actions, the envs' ticks left)
             else if (policy == POLICY_SEQUENCE)
                 v.md_actions = g->actRing + (size_t)action_ring_entry(first_index, j, (uint32_t)g->actRingCount) * ((size_t)g->N * g->A * 6);
@@ -304,7 +305,10 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     // The ring is two CALLS deep, in the caller's ticks per call (a call of 16 ticks runs as two chunks of 8: the second-next chunk's passes would overwrite
     // what the consumer of the previous CALL -- enqueued after both of its chunks -- may still be reading), and rewards / dones have rings of
     // their own (two passes in flight would both publish the single arrays, in either order).
-    const bool overlap = batchRaster && own && !callEv && L->passOverlap && L->passStream[0]
+    // (mv_set_still_frames with an output ring: the calls run in order -- pass c + 1 on its side stream could draw into the entry that carry c, on the
+    // caller's stream, is still reading when the ring is exactly two calls deep)
+    const bool carry = n == 1 && L->stillOn && L->ringObs != nullptr && (render || drawLast);
+    const bool overlap = batchRaster && own && !callEv && !carry && L->passOverlap && L->passStream[0]
             && L->ringCount >= 2 * std::max(k, kCall) && L->ringRewards && L->ringDone &&
                          k <= MAX_STEP_TICKS && L->baseEpisodeLen * 15.0f > float(2 * k + 2);
     hipStream_t passOn = L->stream;
@@ -419,8 +423,15 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     // (mv_macro_step: one entry per call -- the rows behind the call's last tick, with its last chunk)
     if (stateOn && mc) { if (mc->last && state_obs_publish(L, L->group * L->batch + k - 1, stateDst + (k - 1), 1)) return -1; }
     else if (stateOn && state_obs_publish(L, L->group * L->batch, stateDst, k)) return -1;
+    // ---- the still frames' carry (mv_set_still_frames, an output ring): one launch for the call's rendered ticks, behind their passes, in the log's place
+    // and under the log's rule -- it reads the verdicts from the call's slots, so the mark is recorded again behind it.
+    if (carry) {
+        const int first = render ? 0 : k - 1;   // (MV_RENDER_LAST, a macro step: the one rendered tick)
+        if (still_frames_carry(L, views.data() + first, outs.data() + first, 1, k - first)) return -1;
+        ++L->launchCount[1];
+    }
     if (mc && mc->last) ++L->ringTick;
-    if ((anyLog || stateOn) && own) HIP_TRY(hipEventRecord(L->userMark[L->markCount % PIPE_GROUPS], L->stream));
+    if ((anyLog || stateOn || carry) && own) HIP_TRY(hipEventRecord(L->userMark[L->markCount % PIPE_GROUPS], L->stream));
     if (own) {
         ++L->markCount;
         for (int i = 0; i < n; ++i) gs[i]->markCount = L->markCount;
@@ -524,6 +535,7 @@ int mv_group_create(mv_gym *const *gyms, int32_t n, mv_group **out)
         if (g->inGroup) return fail("mv_group_create: a gym already belongs to a group");
         if (g->stepMask.live) return fail("mv_group_create: a gym has a step mask attached (mv_set_step_mask): the union launches read none; detach it first");
         if (g->drawMask.live) return fail("mv_group_create: a gym has a draw mask attached (mv_set_draw_mask): the union launches read none; detach it first");
+        if (g->stillOn) return fail("mv_group_create: a gym has still frames switched on (mv_set_still_frames): the union launches read no stale bytes; switch them off first");
         if (g->budgetOn) return fail("mv_group_create: a gym has an episode budget attached (mv_set_episode_budget): the union launches read none; detach it first");
         if (g->stateObs) return fail("mv_group_create: a gym has state observations attached (mv_set_state_obs): the union launches write none; detach them first");
         for (int j = 0; j < i; ++j) if (gyms[j] == g) return fail("mv_group_create: the same gym twice");
@@ -636,7 +648,7 @@ int mv_recommended_pass_overlap(const mv_gym *g)
     return 1;
 }
 
-int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMask.ownedBytes + g->drawMask.ownedBytes + g->budgetBytes + g->macroBytes) : 0; }
+int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMask.ownedBytes + g->drawMask.ownedBytes + g->budgetBytes + g->macroBytes + g->stillBytes) : 0; }
 
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index)
 {   // several gyms of one job (MultiTaskGym: one per scenario, one stream each) stepped by one call: at eight sub-gyms the per-call cost of
@@ -651,6 +663,9 @@ int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample,
     for (int i = 0; i < n; ++i)
         if (gyms[i] && !gyms[i]->closed && gyms[i]->drawMask.live)
             return fail("mv_step_many: gym " + std::to_string(i) + " has a draw mask attached (mv_set_draw_mask): step it on its own, or detach the mask first");
+    for (int i = 0; i < n; ++i)
+        if (gyms[i] && !gyms[i]->closed && gyms[i]->stillOn)
+            return fail("mv_step_many: gym " + std::to_string(i) + " has still frames switched on (mv_set_still_frames): step it on its own, or switch them off first");
     for (int i = 0; i < n; ++i)
         if (gyms[i] && !gyms[i]->closed && gyms[i]->budgetOn)
             return fail("mv_step_many: gym " + std::to_string(i) + " has an episode budget attached (mv_set_episode_budget): step it on its own, or detach the budget first");

@@ -236,6 +236,7 @@ int store_launch(mv_gym *g, bool save, const int32_t *device_map, const int32_t 
 {
     HIP_TRY(hipSetDevice(g->device));
     if (sim_join(g)) return -1;
+    if (!save && still_frames_touch(g)) return -1;   // (mv_set_still_frames: a load makes every env stale)
     if (host_map && g->forkMapPair.stage(host_map, (size_t)g->N * sizeof(int32_t), g->stream, &device_map)) return -1;
     const store::Layout L = store::layout_of(g->forkTable, g->A);
     const bool logOn = g->logCapacity > 0;

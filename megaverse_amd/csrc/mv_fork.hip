@@ -128,6 +128,7 @@ enum LaunchKind { FORK, RESAMPLE, RESAMPLE_UNSTAGED };
 int fork_launch(mv_gym *g, const int32_t *device_map, const int32_t *host_map, LaunchKind kind = FORK)
 {
     HIP_TRY(hipSetDevice(g->device));
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     if (kind != FORK && !g->resampleArena) {
         const size_t bytes = fork::staging_bytes(g->forkTable, g->N, (size_t)g->A * sizeof(double), sizeof(int32_t));
         hipError_t e_ = hipMalloc((void **)&g->resampleArena, bytes);

@@ -606,9 +606,11 @@ __device__ __forceinline__ void frame_setup_body(const GymView &gv, const int fr
 //     class mod LPT_SUBS: lpt_sub_capacity);
 //   * frame 0 keeps its duty of clearing the next pass's histogram;
 //   * the barriers of the path it replaces that somebody ELSE waits at: PIPE's B(j) (the tick wave's), and the closing sync().
+// marker: the negative count the frame is marked with -- FRAME_UNDRAWN, or mv_still_frames.h's FRAME_STILL for a frame whose env did not change since it was
+// drawn last (mv_set_still_frames): the passes treat both alike, the carry launch (mv_still_frames.hip) tells them apart.
 constexpr int FRAME_UNDRAWN = -1;
 template <int THREADS, bool WAVE_LOCAL, bool PIPE = false>
-__device__ __forceinline__ void frame_skip(const GymView &gv, const int frame)
+__device__ __forceinline__ void frame_skip(const GymView &gv, const int frame, const int marker = FRAME_UNDRAWN)
 {
     static_assert(!WAVE_LOCAL || THREADS == 64, "a wave-local frame setup is one wavefront");
     auto sync = [] { if (WAVE_LOCAL) wave_sync(); else __syncthreads(); };
@@ -616,10 +618,10 @@ __device__ __forceinline__ void frame_skip(const GymView &gv, const int frame)
     if (PIPE) __syncthreads();   // B(j): nothing of the state is read here, the tick wave may write the next tick's
     if (tid == 0) {
         const int sub = frame & (LPT_SUBS - 1);
-        gv.vis_count[frame] = FRAME_UNDRAWN;
+        gv.vis_count[frame] = marker;
         gv.lpt_bucket[frame] = 0;
         const int binPlace = atomicAdd(&gv.lpt_hist[(gv.lpt_parity * LPT_BUCKETS + 0) * LPT_SUBS + sub], 1);
-        reinterpret_cast<float *>(gv.vis_hdr + (size_t)frame * FRAME_HDR_BYTES)[FH_COUNT] = __int_as_float(FRAME_UNDRAWN);
+        reinterpret_cast<float *>(gv.vis_hdr + (size_t)frame * FRAME_HDR_BYTES)[FH_COUNT] = __int_as_float(marker);
         gv.lpt_list[(size_t)sub * lpt_sub_capacity(gv.num_envs * gv.num_agents) + binPlace] = frame;
     }
     if (frame == 0 && !gv.lpt_no_clear)

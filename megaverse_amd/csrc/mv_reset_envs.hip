@@ -28,6 +28,7 @@ int reset_envs_launch(mv_gym *g, const uint8_t *device_mask, const uint8_t *host
 {
     HIP_TRY(hipSetDevice(g->device));
     if (sim_join(g)) return -1;
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     if (flush_device_actions(g)) return -1;   // (a buffer handed over before the call is read now, as in mv_reset; the swap-in clears the flagged envs' actions only)
     const size_t N = (size_t)g->N;
     if (host_mask) {   // nobody flagged: nothing to do, nothing to wait for

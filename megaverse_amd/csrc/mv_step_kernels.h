@@ -5,7 +5,8 @@
 //   S::long_lists                          frame lists long enough for the depth sort (mv_frame.h: DepthSortScratch)
 //   S::par_agents                          several agents: every wave of the workgroup takes part in the tick (TowerBuilding)
 // No tick knows about step masks (mv_set_step_mask) or episode budgets (mv_set_episode_budget): the MASKED instantiations of the bodies choose between
-// S::tick and frozen_tick, below.  They also choose between frame_setup_body and frame_skip (mv_frame.h) for the envs a draw mask (mv_set_draw_mask) leaves out,
+// S::tick and frozen_tick, below.  They also choose between frame_setup_body and frame_skip (mv_frame.h) for the envs a draw mask (mv_set_draw_mask) leaves out
+// and for the envs that did not change since their frames were drawn last (mv_set_still_frames: env_stale),
 // and store the agents' state rows behind every tick of a view that carries staging rows for them (mv_set_state_obs: state_obs_write).
 // Every __global__ is a one-line entry point over a body in its scenario's mv_step_<scenario>.hip (a launch bound that depends on a template
 // parameter is not applied, and the profiles name the kernels); StepKernels lists them for the launchers (mv_step.hip).
@@ -16,6 +17,7 @@
 #include "mv_frame.h"
 #include "mv_macro_step.h"
 #include "mv_state_obs.h"
+#include "mv_still_frames.h"
 #include "mv_types.h"
 
 // the register budget of the one-wave-per-env multi-tick kernels (512 / n VGPRs).  Their waves stay resident for a whole batched call beside the
@@ -131,15 +133,32 @@ __device__ __forceinline__ bool env_drawn(const GymView &gv, int env)
 
 // every frame of an undrawn env, in the shape the body's frame setups have: ONE = true: the workgroup (THREADS threads; WAVE_LOCAL: its one wave) shares the
 // env's one frame; false: every wave takes its share of the env's A frames
+// marker: FRAME_UNDRAWN, or FRAME_STILL (mv_set_still_frames, below)
 template <bool ONE, int THREADS, bool WAVE_LOCAL>
-__device__ __forceinline__ void env_frames_skip(const GymView &gv, int env)
+__device__ __forceinline__ void env_frames_skip(const GymView &gv, int env, int marker = FRAME_UNDRAWN)
 {
-    if constexpr (ONE) frame_skip<THREADS, WAVE_LOCAL>(gv, env);
+    if constexpr (ONE) frame_skip<THREADS, WAVE_LOCAL>(gv, env, marker);
     else {
         const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
-        for (int a = wave; a < A; a += nw) frame_skip<64, true>(gv, env * A + a);
+        for (int a = wave; a < A; a += nw) frame_skip<64, true>(gv, env * A + a, marker);
     }
 }
+
+// ---- mv_set_still_frames: envs whose frames are not drawn again (mv_still_frames.h has the rule).  A third uniform value beside `left` and `tl`, carried
+// through the launch's ticks in the same way and read once at the top (env_stale):
+//   < 0    the option is off (the view carries no array): the env is drawn on every pass, nothing is stored;
+//     0    the env's state is what its frames were last drawn from: a pass of this launch takes frame_skip with FRAME_STILL;
+//   > 0    the state may have changed: the next pass sets the frames up and draws them.
+// It is updated behind the tick's `steps` choice (still_after_tick) and behind the frame choice (still_after_frames); thread 0 stores it at the launch's end
+// where it changed -- the env is the workgroup, nobody else reads or writes its byte, and the next launch on the stream reads what was stored.  An env the
+// draw mask leaves out stays as stale as it was.  The store is a call that is not inlined, for state_obs_store's reason.
+__device__ __forceinline__ int env_stale(const GymView &gv, int env)
+{
+    return gv.still != nullptr ? __builtin_amdgcn_readfirstlane((int)gv.still[env]) : -1;
+}
+static __device__ __attribute__((noinline)) void still_store(uint8_t *stale, int v) { *stale = (uint8_t)v; }
+// the marker of the frames of an env that is not set up in a pass: the draw mask's, else the still frames'
+__device__ __forceinline__ int skip_marker(bool drawn) { return drawn ? still::FRAME_STILL : FRAME_UNDRAWN; }
 
 // ---- mv_set_state_obs: the agents' state rows of this tick (mv_state_obs.h has the record).  Called by every thread of the workgroup BEHIND what orders the
 // tick's stores before the frame setup's loads (wave_sync: one wave; the workgroup's barrier: several) -- the rows are loads of the same state -- and on either
@@ -186,8 +205,12 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
         frozen_tick(gv, env);
         state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs: the unchanged state, as the last launch left it)
         if (!render) return;
+        // (mv_set_still_frames) read by every wave IN FRONT of the barrier, stored by thread 0 behind it: no wave reads what this launch stored
+        const int stale = env_stale(gv, env);
         __syncthreads();
         if (!env_drawn(gv, env)) { env_frames_skip<A_MAX == 1, STEP_THREADS, false>(gv, env); return; }   // (mv_set_draw_mask; uniform)
+        if (stale == 0) { env_frames_skip<A_MAX == 1, STEP_THREADS, false>(gv, env, still::FRAME_STILL); return; }   // (mv_set_still_frames; uniform)
+        if (stale > 0 && threadIdx.x == 0) still_store(gv.still + env, 0);
         if constexpr (A_MAX == 1) frame_setup_body<STEP_THREADS, false>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
         else {
             const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
@@ -220,6 +243,7 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
     }
 #endif
     if (!render) {
+        if constexpr (MASKED) if (gv.still != nullptr && threadIdx.x == 0) still_store(gv.still + env, 1);   // (mv_set_still_frames: the env stepped, no pass follows)
         if constexpr (MASKED) if (gv.state_obs != nullptr) {   // (mv_set_state_obs; uniform) a tick without frame setup reports its rows too
             __syncthreads();   // the tick's stores before the rows' loads
             state_obs_write<A_MAX>(gv, env);
@@ -229,7 +253,13 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
     __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
     MV_T(6);           // the whole tick as wave 0 saw it (incl. the generator of a finished env), up to the barrier
     if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
-    if constexpr (MASKED) if (!env_drawn(gv, env)) { env_frames_skip<A_MAX == 1, STEP_THREADS, false>(gv, env); return; }   // (mv_set_draw_mask; uniform)
+    // (mv_set_still_frames: the env stepped -- stale where the draw mask leaves it out, drawn and fresh otherwise; nobody reads the byte in this launch)
+    if constexpr (MASKED) if (!env_drawn(gv, env)) {   // (mv_set_draw_mask; uniform)
+        if (gv.still != nullptr && threadIdx.x == 0) still_store(gv.still + env, 1);
+        env_frames_skip<A_MAX == 1, STEP_THREADS, false>(gv, env);
+        return;
+    }
+    if constexpr (MASKED) if (gv.still != nullptr && threadIdx.x == 0) still_store(gv.still + env, 0);
     if constexpr (A_MAX == 1) {
         frame_setup_body<STEP_THREADS, false>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
         MV_T(7);   // frame setup
@@ -273,30 +303,38 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
     if constexpr (MASKED) { left = env_left(a.view(0), env); tl = env_tl(a.view(0), env); }
     [[maybe_unused]] bool drawn = true;   // (mv_set_draw_mask: env_drawn)
     if constexpr (MASKED) drawn = env_drawn(a.view(0), env);
+    [[maybe_unused]] int stale = -1, stale0 = -1;   // (mv_set_still_frames: env_stale)
+    if constexpr (MASKED) stale = stale0 = env_stale(a.view(0), env);
     for (int j = 0; j < a.n; ++j) {
         const GymView &gv = a.view(j);
         const bool steps = !MASKED || env_steps(left, tl);   // (uniform; without MASKED: a constant)
+        if constexpr (MASKED) stale = still::still_after_tick(stale, steps);
         if constexpr (A_MAX == 1) {
             if (steps) S::template tick<1>(gv, env);
             else frozen_tick(gv, env);
             wave_sync();   // the tick's stores before the frame setup's loads (one wave: no barrier needed)
             if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
             if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
-            if (!MASKED || drawn) frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
-            else env_frames_skip<true, 64, true>(gv, env);
+            if (!MASKED || (drawn && stale != 0)) {
+                frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
+                if constexpr (MASKED) stale = still::still_after_frames(stale, still::VERDICT_DRAWN);
+            } else env_frames_skip<true, 64, true>(gv, env, skip_marker(drawn));
         } else {
             if (steps) S::template tick<A_MAX, true>(gv, env);
             else frozen_tick(gv, env);
             __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
             if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
             if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
-            if (!MASKED || drawn) {
+            if (!MASKED || (drawn && stale != 0)) {
                 const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
                 for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
-            } else env_frames_skip<false, 64, true>(gv, env);
+                if constexpr (MASKED) stale = still::still_after_frames(stale, still::VERDICT_DRAWN);
+            } else env_frames_skip<false, 64, true>(gv, env, skip_marker(drawn));
             __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
         }
     }
+    // (every wave read the byte in front of the loop's first barrier)
+    if constexpr (MASKED) if (stale != stale0 && threadIdx.x == 0) still_store(a.view(0).still + env, stale);
 }
 
 // The resident multi-tick step for ticks that set no frame up (mv_step_n_render, MV_RENDER_NONE / MV_RENDER_LAST): as step_ticks_body -- one workgroup per env,
@@ -316,10 +354,13 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
     // env_left and n tiny stores)
     [[maybe_unused]] int32_t left = -1, tl = -1;   // (mv_macro_step: env_tl)
     if constexpr (MASKED) { left = env_left(a.view(0), env); tl = env_tl(a.view(0), env); }
+    [[maybe_unused]] int stale = -1, stale0 = -1;   // (mv_set_still_frames: env_stale; FRAMES = false only ever sets it)
+    if constexpr (MASKED) stale = stale0 = env_stale(a.view(0), env);
     if constexpr (!FRAMES) {
         for (int j = 0; j < a.n; ++j) {
             const GymView &gv = a.view(j);
             const bool steps = !MASKED || env_steps(left, tl);   // (uniform; without MASKED: a constant)
+            if constexpr (MASKED) stale = still::still_after_tick(stale, steps);
             if constexpr (A_MAX == 1) {
                 if (steps) S::template tick<1>(gv, env);
                 else frozen_tick(gv, env);
@@ -345,6 +386,7 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
             const GymView &gv = a.view(j);
             const bool frames = (mask >> j) & 1u;
             const bool steps = !MASKED || env_steps(left, tl);   // (uniform; without MASKED: a constant)
+            if constexpr (MASKED) stale = still::still_after_tick(stale, steps);
             if constexpr (A_MAX == 1) {
                 if (steps) S::template tick<1>(gv, env);
                 else frozen_tick(gv, env);
@@ -352,8 +394,10 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
                 if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
                 if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
                 if (frames) {
-                    if (!MASKED || drawn) frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
-                    else env_frames_skip<true, 64, true>(gv, env);
+                    if (!MASKED || (drawn && stale != 0)) {
+                        frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
+                        if constexpr (MASKED) stale = still::still_after_frames(stale, still::VERDICT_DRAWN);
+                    } else env_frames_skip<true, 64, true>(gv, env, skip_marker(drawn));
                 }
             } else {
                 if (steps) S::template tick<A_MAX, true>(gv, env);
@@ -362,10 +406,11 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
                 if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
                 if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
                 if (frames) {
-                    if (!MASKED || drawn) {
+                    if (!MASKED || (drawn && stale != 0)) {
                         const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
                         for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
-                    } else env_frames_skip<false, 64, true>(gv, env);
+                        if constexpr (MASKED) stale = still::still_after_frames(stale, still::VERDICT_DRAWN);
+                    } else env_frames_skip<false, 64, true>(gv, env, skip_marker(drawn));
                     __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
                 } else if constexpr (MASKED) {
                     if (gv.state_obs != nullptr) __syncthreads();   // (mv_set_state_obs; uniform) the rows' loads before the other waves' next tick changes the state
@@ -373,6 +418,8 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
             }
         }
     }
+    // (every wave read the byte in front of the loops' first barrier)
+    if constexpr (MASKED) if (stale != stale0 && threadIdx.x == 0) still_store(a.view(0).still + env, stale);
 }
 
 // Software-pipelined (one agent per env): TWO waves per env.  Wave 0 runs tick j + 1 while wave 1 sets tick j's frame up (mv_frame.h) -- the two halves of a

@@ -218,6 +218,10 @@ struct GymView {
     // bodies behind every tick the env stepped in (mv_step_kernels.h: after_tick; mv_macro_step.h has the rule); null: no macro step in flight.  Set by the
     // views of a macro step's ticks only (mv_api_step.hip).
     int32_t *macro_tl;
+    // mv_set_still_frames: [N] stale bytes, != 0 = the env's state may have changed since its frames were drawn last (mv_still_frames.h has the rule): set by
+    // the MASKED step bodies behind every tick the env stepped in, cleared where they set its frames up; an env whose byte is 0 takes frame_skip with
+    // FRAME_STILL.  null: off, every env is drawn on every pass.  Set by the stepping calls only (mv_api_step.hip); the union launches never see a non-null one.
+    uint8_t *still;
 };
 
 // The n <= 8 consecutive ticks of a multi-tick step launch (mv_step.hip: step_ticks_kernel, and every mv_step_*.hip), the same envs in all of them: their views

@@ -106,6 +106,8 @@ SYMBOLS = [
     ("mv_macro_step", C.c_int, [_P, _I, _P, _P, _I]), ("mv_macro_step_host", C.c_int, [_P, _I, _P, _P, _I]),
     ("mv_debug_episode_log_macro_host", C.c_int, [_P, _P, _P, _I, _I, _I, _I, _U, _P, _P, _P, C.POINTER(_U), C.POINTER(_U), _P, _P, _P]),
     ("mv_debug_macro_rule_host", C.c_int, [_P, _P, _P, _P, _I, _I, _P, _P, _P]), ("mv_debug_macro_fold_host", C.c_int, [_P, _I, _I, _P]),
+    ("mv_set_still_frames", C.c_int, [_P, _I]), ("mv_get_still_frames", C.c_int, [_P]),
+    ("mv_debug_still_rule_host", C.c_int, [_P, _P, _P, _P, _I, _I, _P, _P]), ("mv_debug_still_carry_host", C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
 ]
 
 # include/megaverse_hip.h: MV_STATE_OBS_FLOATS and the columns of a state-observation row (mv_set_state_obs), name -> index
@@ -217,6 +219,42 @@ def debug_macro_fold_host(values):
     if lib.mv_debug_macro_fold_host(v.ctypes.data, v.shape[0], v.shape[1], out.ctypes.data) != 0:
         raise RuntimeError(lib.mv_last_error().decode())
     return out
+
+
+def debug_still_rule_host(steps, has_pass, draw_mask, stale):
+    """mv_debug_still_rule_host: the rule of still frames on the CPU (no device).  steps [k][N]: 1 where the env steps in the tick; has_pass [k]: 1 where the
+    tick has an observation pass; draw_mask [N] or None; stale [N].  -> (verdict int32 [k][N]: 0 no pass, 1 drawn, -1 user-undrawn, -2 still; stale uint8 [N]
+    behind the last tick)"""
+    lib = load_library()
+    steps = np.ascontiguousarray(steps, dtype=np.uint8)
+    has_pass = np.ascontiguousarray(has_pass, dtype=np.uint8)
+    stale = np.ascontiguousarray(stale, dtype=np.uint8)
+    m = None if draw_mask is None else np.ascontiguousarray(draw_mask, dtype=np.uint8)
+    if steps.ndim != 2 or has_pass.shape != (steps.shape[0],) or stale.shape != (steps.shape[1],) or (m is not None and m.shape != stale.shape):
+        raise ValueError("debug_still_rule_host: steps is [k][N], has_pass [k], draw_mask and stale are [N]")
+    k, N = steps.shape
+    verdict, out = np.zeros((k, N), np.int32), np.zeros(N, np.uint8)
+    if lib.mv_debug_still_rule_host(steps.ctypes.data, has_pass.ctypes.data, None if m is None else m.ctypes.data, stale.ctypes.data, k, N,
+                                    verdict.ctypes.data, out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return verdict, out
+
+
+def debug_still_carry_host(verdict, entries, ring, home):
+    """mv_debug_still_carry_host: the carry of still frames on the CPU (no device), one call.  verdict int32 [k][frames]: what the passes read (>= 0 drawn,
+    -1 user-undrawn, -2 still); entries [k]: each rendered tick's ring entry; ring: contiguous uint8 [R][frames][frame_bytes], copied IN PLACE; home:
+    contiguous int32 [frames], advanced IN PLACE."""
+    lib = load_library()
+    verdict = np.ascontiguousarray(verdict, dtype=np.int32)
+    entries = np.ascontiguousarray(entries, dtype=np.int32)
+    for name, a, dt in (("ring", ring, np.uint8), ("home", home, np.int32)):
+        if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous:
+            raise ValueError(f"debug_still_carry_host: {name} is a contiguous {np.dtype(dt).name} numpy array, changed in place")
+    if verdict.ndim != 2 or ring.ndim != 3 or entries.shape != (verdict.shape[0],) or ring.shape[1] != verdict.shape[1] or home.shape != (verdict.shape[1],):
+        raise ValueError("debug_still_carry_host: verdict is [k][frames], entries [k], ring [R][frames][frame_bytes], home [frames]")
+    if lib.mv_debug_still_carry_host(verdict.ctypes.data, entries.ctypes.data, verdict.shape[0], verdict.shape[1], ring.shape[0], ring.shape[2],
+                                     ring.ctypes.data, home.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
 
 
 def check_macro_step_args(actions, ticks, num_envs, num_agents):
@@ -963,6 +1001,19 @@ class MegaverseGym:
     def draw_mask(self):
         """-> 'none' | 'device' | 'host': the form of the draw mask attached (set_draw_mask)"""
         return self.STEP_MASK_FORMS[self._ck(self._lib.mv_get_draw_mask(self._g))]
+
+    def set_still_frames(self, on=True):
+        """Still frames (include/megaverse_hip.h: mv_set_still_frames): while on, every later observation pass of step, step_n (every render mode) and
+        macro_step sets up and draws an env's frames only where the env's state may have changed since they were drawn last -- an env frozen by a step mask,
+        halted by its budget or stopped inside a macro step is not ray-cast again.  Its rows show the frame drawn last: in the observation slab they are left
+        alone, in an output ring they are copied on the device from the entry that holds it.  Every observation byte, reward, done and log record equals
+        those of a gym with the option off.  reset, reset_envs, fork_envs, resample_envs, load_envs, seed, render and the setters that change what or where
+        the gym draws make every env due again.  Never waits on the host; draw_hires ignores it; groups refuse a gym that has it on."""
+        self._ck(self._lib.mv_set_still_frames(self._g, 1 if on else 0))
+
+    def still_frames(self):
+        """-> bool: whether still frames are switched on (set_still_frames)"""
+        return self._ck(self._lib.mv_get_still_frames(self._g)) != 0
 
     def set_state_obs(self, buf=True):
         """State observations (include/megaverse_hip.h: mv_set_state_obs): every tick of every later stepping call -- in every render mode, 'none' included --

@@ -68,7 +68,8 @@ def check_sequence_actions(actions, num_agents):
 
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
-                 img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1):
+                 img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1,
+                 still_frames=False):
         if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
         # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
@@ -111,6 +112,10 @@ class MegaverseEnv:
         self._state_on = bool(state_obs)
         if self._state_on:
             self.env.set_state_obs(True)
+        # still_frames: envs that did not change -- frozen, halted by a budget, stopped inside a macro step -- are not drawn again (mv_set_still_frames); every
+        # observation byte stays what it is without the option
+        if still_frames:
+            self.env.set_still_frames(True)
         self.default_shaping_scheme = self.env.get_reward_shaping(0, 0)
         self.action_space = self.generate_action_space(self.env.action_space_sizes())
         self.observation_space = spaces.Box(0, 255, (self.channels, self.img_h, self.img_w), dtype=np.uint8)
@@ -435,6 +440,12 @@ class MegaverseEnv:
         observation slab or ring keep what they held -- everything else about its ticks is unchanged -- until the mask is replaced or detached (None).  A bool
         / uint8 CUDA tensor is read in place (rewrite it, then call this again); a numpy array or a sequence is copied."""
         self.env.set_draw_mask(mask)
+
+    def set_still_frames(self, on=True):
+        """Still frames (MegaverseGym.set_still_frames): while on, envs whose state did not change since their frames were drawn last -- frozen (freeze),
+        halted by a budget, stopped inside a macro step -- are not drawn again; their observations stay byte for byte what drawing them would leave.  No
+        host wait."""
+        self.env.set_still_frames(on)
 
     def draw_only(self, env_ids):
         """only the envs of env_ids are drawn from the next observation pass on (a host draw mask): the leaves a search feeds to its value net, the few envs
