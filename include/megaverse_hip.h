@@ -314,6 +314,35 @@ int mv_set_state_obs(mv_gym *g, float *device_buf);   /* [max(1, ring count)][N*
 int mv_get_state_obs(const mv_gym *g);                /* 0: none, else the number of entries; -1: no gym */
 int mv_get_state_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, float *out_host16);  /* last tick's row; waits for the gym's stream */
 int mv_debug_state_obs_host(const void *agent_state, const void *env_header, float *out16);      /* the pack function, on the host */
+/* Scene observations (no reference counterpart), the per-ENV counterpart of the state observations: one row of MV_SCENE_OBS_FLOATS = 32 float32 per env,
+ * [N][32], taken from the env's state AFTER the tick, auto-reset included -- the level, the goal and the ball that the per-agent rows leave out.  Two
+ * conversions: "copied" moves the 32 bits (a -0.0f or a NaN's payload survives); "int" converts an int32 with (float), exactly (every value is far below 2^24).
+ * Columns (megaverse_amd/csrc/mv_scene_obs.h states them for kernels and host alike, with the units):
+ *    0  the scenario family id (SCN_*), int      1..3  the room's L, H, W in voxels, int      4  num_frames, int      5, 6  episode time and length in seconds,
+ *    copied      7  the env's episode counter: it changes exactly on the ticks the env takes a new episode, int      8  solved, int      9  highest_tower
+ *    (TowerBuilding: the tower; Collect: the +1 diamonds collected), int      10  bz_reward, copied      11..14  num_objects, num_rewards, num_platforms,
+ *    num_terrain, int      15  +0.0f (reserved)
+ *    16..31 by scenario, +0.0f wherever nothing is listed and for every scenario not listed:
+ *      TowerBuilding   16..19  the building zone: min x, max x, min z, max z, int
+ *      Obstacles*      16  the number of exit terrain boxes, int      17..19, 20..22  min and max (exclusive) of the first one in voxels, zeros when there is
+ *                      none, int      23  the diamonds still there, int
+ *      HexExplore      16, 17  x, z of the target, copied
+ *      Football        16..18  the ball's position      19  its drawn radius      20..22  its velocity, all copied      23  this tick's kicks, int
+ *                      24..26  its angular velocity, copied      27  this tick's contact bits, int      28..30  the pending force, copied
+ * Buffer, ticks, visibility, refresh (mv_reset, mv_reset_envs(..., render = 1): the flagged envs' rows only, mv_render), what forks / resampling / loads / seeds
+ * leave alone, ordering and refusals are mv_set_state_obs's, with [entries][N][32] for [entries][N*A][16]: frozen, halted, macro-stopped, undrawn and still envs
+ * report too; mv_macro_step leaves its last tick's rows; mv_set_output_ring is refused while attached; mv_group_create and mv_step_many refuse a gym that has
+ * it attached.  A stepping call enqueues ONE publication launch on the gym's stream for whichever of the two records are attached, both included
+ * (mv_debug_launch_counts counts it in out[1]).  A gym that attaches neither launches exactly what it launched before.  The staging rows are counted in
+ * mv_arena_bytes from the first attach on.
+ * mv_debug_scene_obs_host: the record on the CPU, from the bytes of one EnvHeader (128), 16 TerrainBox (32 each), rewards_len <= 96 MovableObject (4 each) and
+ * one FootballState (64) of megaverse_amd/csrc/mv_types.h; inputs the scenario does not read may be NULL: no device. */
+enum { MV_SCENE_OBS_FLOATS = 32 };
+int mv_set_scene_obs(mv_gym *g, float *device_buf);     /* [max(1, ring count)][N][32] float32 in device memory; NULL detaches */
+int mv_get_scene_obs(const mv_gym *g);                  /* 0: none, else the number of entries; -1: no gym */
+int mv_get_scene_observation(mv_gym *g, int32_t env_idx, float *out_host32);   /* last tick's row; waits for the gym's stream */
+int mv_debug_scene_obs_host(int32_t scenario, const void *env_header, const void *terrain16, const void *rewards, int32_t rewards_len,
+                            const void *football_state, float *out32);         /* the pack function on the host; unused inputs may be NULL */
 /* Episode budgets (no reference counterpart: VectorEnv::step resets a finished env on the spot and steps on, vector_env.cpp:89-108).  Per env e the gym owns an
  * int32 left[e]:  < 0: unlimited -- what every env is without these calls;  > 0: the env may still finish that many episodes;  0: the env is HALTED.
  * Tick t, env e, left[e] as it stands before the tick (megaverse_amd/csrc/mv_episode_budget.h states the rule for kernels and host alike):
@@ -606,8 +635,8 @@ int mv_profile_end(mv_gym *g, float *avg_ms4, int32_t *counts4);
 /* test hooks: packed state snapshot of one env (layout in DESIGN.md, same bytes as the oracle's
  * mvo_snapshot) and the raw device RNG streams */
 int mv_debug_set_agent_pos(mv_gym *g, int32_t env_idx, int32_t agent_idx, float x, float y, float z); /* teleport (fall-detection tests) */
-/* out[0] / out[1]: the step launches / observation launches (one per launcher call: a batched pass is one, an exact-mode pass with its frame sort is one) that
- * stepping calls have enqueued for this gym so far; for a member of a group: the group's.  Tells the batched paths from the tick-by-tick ones, whose bytes are the same. */
+/* out[0] / out[1]: the step launches / observation launches (one per launcher call: a batched pass is one, an exact-mode pass with its frame sort is one; the
+ * still frames' carry and the one publication launch of state / scene observations count here too) that stepping calls have enqueued for this gym so far; for a member of a group: the group's.  Tells the batched paths from the tick-by-tick ones, whose bytes are the same. */
 int mv_debug_launch_counts(mv_gym *g, int64_t out[2]);
 /* scripted single-step physics cases (tests/test_canonical_poses*.py): the yaw basis from (cos, sin) as DefaultKinematicAgent's spawn builds it
  * (agent.cpp:42-46), and the controller's velocities */

@@ -785,6 +785,7 @@ int mv_close(mv_gym *g)
     g->seedEnvsPair.release();
     env_masks_free(g);
     state_obs_free(g);
+    scene_obs_free(g);
     episode_budget_free(g);
     macro_step_free(g);
     still_frames_free(g);
@@ -942,7 +943,8 @@ int mv_render(mv_gym *g)
     if (check(g)) return -1;
     if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     if (render_frames(g)) return -1;
-    return state_obs_refresh(g, nullptr);   // (mv_set_state_obs: the last tick's rows from the current state, as its frames; also behind mv_reset)
+    if (state_obs_refresh(g, nullptr)) return -1;   // (mv_set_state_obs: the last tick's rows from the current state, as its frames; also behind mv_reset)
+    return scene_obs_refresh(g, nullptr);           // (mv_set_scene_obs: likewise)
 }
 
 }  // extern "C"
@@ -1299,6 +1301,8 @@ int mv_set_output_ring(mv_gym *g, int32_t count, void *obs, float *rewards, uint
     if (check(g)) return -1;
     if (g->stateObs)   // (the state buffer is one more ring of the count it was attached under)
         return fail("mv_set_output_ring: state observations are attached (mv_set_state_obs), sized by the ring count they were attached under: detach the state observations first");
+    if (g->sceneObs)
+        return fail("mv_set_output_ring: scene observations are attached (mv_set_scene_obs), sized by the ring count they were attached under: detach the scene observations first");
     if (count < 0 || (count > 0 && !obs && !rewards && !dones)) return fail("mv_set_output_ring: count >= 0 and at least one ring required");
     if (count > 0 && obs && g->obsLayout == MV_OBS_RGB_PLANAR && (uintptr_t)obs % planar_alignment(g->w))
         return fail("mv_set_output_ring: a planar ring of this width must be " + std::to_string(planar_alignment(g->w)) + "-byte aligned");

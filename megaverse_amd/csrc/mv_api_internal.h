@@ -10,6 +10,7 @@
 //   mv_env_masks.hip  step masks and draw masks: attaching and detaching the bytes that freeze envs (mv_step_kernels.h: frozen_tick) and the bytes that leave
 //                     envs' frames out of the observation passes (mv_frame.h: frame_skip)
 //   mv_state_obs.hip  state observations: attaching the caller's buffer, the staging rows, their publication and refresh (mv_state_obs.h: the record)
+//   mv_scene_obs.hip  scene observations: the per-env counterpart, and the one publication launch both records share (mv_scene_obs.h: the record)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 //   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
 //   mv_still_frames.hip  still frames: switching the option, the memset behind calls that change what frames show, the carry launch (mv_still_frames.h: the rule)
@@ -274,6 +275,12 @@ struct mv_gym {
     // While attached, gvp[q].state_obs points at slot q's rows: the stepping calls' views carry it to the MASKED step kernels.
     float *stateObs = nullptr, *stateStage = nullptr;
     int stateEntries = 0;
+    // mv_set_scene_obs: the caller's [sceneEntries][N][32] float32 buffer (null: off; sceneEntries as stateEntries) and the gym's staging rows [slots][N][32],
+    // allocated at the first attach, kept until mv_close and counted in mv_arena_bytes from then on (sceneBytes).  While attached, gvp[q].scene_obs points at
+    // slot q's rows.
+    float *sceneObs = nullptr, *sceneStage = nullptr;
+    int sceneEntries = 0;
+    size_t sceneBytes = 0;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
     // budgetLeft [N], what the step kernels read and write (GymView::budget, through the stepping calls' views, while budgetOn); budgetHalted, the count of
     // zeros in it; budgetMirror [N], the episode log's own copy, advanced by the log's update tick by tick.  The host form's values travel through a pool of
@@ -360,6 +367,15 @@ float *state_obs_entry(const mv_gym *g, unsigned long long tick);
 int state_obs_publish(mv_gym *g, int q0, float *const *dst, int k);
 int state_obs_refresh(mv_gym *g, const uint8_t *device_mask);
 void state_obs_free(mv_gym *g);        // mv_close
+// mv_scene_obs.hip, likewise for the scene rows.  scene_obs_publish: the stepping call's ONE publication launch of a gym with scene observations -- it carries
+// the state rows too when both records are attached (state_dst: tick j's entries of the state buffer, null: that record is off; state_obs_publish is the
+// launch of a gym with state observations alone) -- the staged rows of the k ticks in slots q0 .. q0 + k - 1 -> dst[j], on the caller's stream;
+// scene_obs_refresh: the last tick's entry gathered from the current state (mask as state_obs_refresh's), behind sim_join
+float *scene_obs_entry(const mv_gym *g, unsigned long long tick);
+int scene_obs_publish(mv_gym *g, int q0, float *const *scene_dst, float *const *state_dst, int k);
+int scene_obs_refresh(mv_gym *g, const uint8_t *device_mask);
+void scene_obs_free(mv_gym *g);        // mv_close
+size_t state_obs_words(const mv_gym *g);   // (mv_state_obs.hip)
 int render_frames(mv_gym *g);          // mv_render without the state rows' refresh (mv_api.hip; mv_reset_envs refreshes the flagged envs' rows only)
 int episode_budget_seed_mirror(mv_gym *g);   // mv_set_episode_log: the log's mirror from the live array (mv_episode_budget.hip)
 // mv_fork.hip, shared with mv_env_store.hip: what every fork / resample / env-store form refuses (what: "forks", "env stores": for the text about groups)

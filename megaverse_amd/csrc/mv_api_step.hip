@@ -103,6 +103,8 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     std::vector<OutPtrs> outs((size_t)n * k);
     float *stateDst[PIPE_BATCH_MAX];   // (mv_set_state_obs; one gym: a group's members have none) tick j's entry of the caller's buffer
     const bool stateOn = n == 1 && L->stateObs != nullptr;
+    float *sceneDst[PIPE_BATCH_MAX];   // (mv_set_scene_obs; likewise)
+    const bool sceneOn = n == 1 && L->sceneObs != nullptr;
     hipEvent_t *evs[PIPE_BATCH_MAX];
     // ---- the k step kernels, back to back on the simulation stream
     bool simDoneRodeAlong = false;   // (the last step kernel's dispatch packet completes simDone itself)
@@ -166,6 +168,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
             if ((render || (drawLast && j == k - 1)) && take_hist(g, sim, !(multiTick || groupBatch || simTicks))) return -1;
             OutPtrs &o = outs[(size_t)j * n + i];
             if (stateOn) stateDst[j] = state_obs_entry(g, g->ringTick);   // (the same tick counter: the entry the tick's rewards go to)
+            if (sceneOn) sceneDst[j] = scene_obs_entry(g, g->ringTick);
             o = outputs_of(g, mc ? g->ringTick : g->ringTick++);   // (mv_macro_step: one entry for the whole call; the position moves on behind its last chunk)
             GymView &v = views[(size_t)j * n + i];
             v = view(g, g->parity, staged ? nullptr : &o);
@@ -421,8 +424,15 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
     // log's reason under the same rule: it reads the call's slots, so the mark is recorded again behind it (with overlapped passes the mark was completed on
     // the pass stream, and the slot group could be reused under the copy).  Every stepping call stages and publishes this way, pipelined or not.
     // (mv_macro_step: one entry per call -- the rows behind the call's last tick, with its last chunk)
-    if (stateOn && mc) { if (mc->last && state_obs_publish(L, L->group * L->batch + k - 1, stateDst + (k - 1), 1)) return -1; }
-    else if (stateOn && state_obs_publish(L, L->group * L->batch, stateDst, k)) return -1;
+    // (mv_set_scene_obs: the per-env rows travel the same way, in the same place; with both records attached ONE launch carries both.  The publication
+    // launch is counted with the call's pass launches, mv_debug_launch_counts.)
+    if (stateOn || sceneOn) {
+        const int q0 = L->group * L->batch + (mc ? k - 1 : 0), first = mc ? k - 1 : 0, kk = mc ? 1 : k;
+        if (!mc || mc->last) {
+            if (sceneOn ? scene_obs_publish(L, q0, sceneDst + first, stateOn ? stateDst + first : nullptr, kk) : state_obs_publish(L, q0, stateDst + first, kk)) return -1;
+            ++L->launchCount[1];
+        }
+    }
     // ---- the still frames' carry (mv_set_still_frames, an output ring): one launch for the call's rendered ticks, behind their passes, in the log's place
     // and under the log's rule -- it reads the verdicts from the call's slots, so the mark is recorded again behind it.
     if (carry) {
@@ -431,7 +441,7 @@ static int step_gyms(mv_gym *const *gs, int n, bool render, int k, int policy, u
         ++L->launchCount[1];
     }
     if (mc && mc->last) ++L->ringTick;
-    if ((anyLog || stateOn || carry) && own) HIP_TRY(hipEventRecord(L->userMark[L->markCount % PIPE_GROUPS], L->stream));
+    if ((anyLog || stateOn || sceneOn || carry) && own) HIP_TRY(hipEventRecord(L->userMark[L->markCount % PIPE_GROUPS], L->stream));
     if (own) {
         ++L->markCount;
         for (int i = 0; i < n; ++i) gs[i]->markCount = L->markCount;
@@ -538,6 +548,7 @@ int mv_group_create(mv_gym *const *gyms, int32_t n, mv_group **out)
         if (g->stillOn) return fail("mv_group_create: a gym has still frames switched on (mv_set_still_frames): the union launches read no stale bytes; switch them off first");
         if (g->budgetOn) return fail("mv_group_create: a gym has an episode budget attached (mv_set_episode_budget): the union launches read none; detach it first");
         if (g->stateObs) return fail("mv_group_create: a gym has state observations attached (mv_set_state_obs): the union launches write none; detach them first");
+        if (g->sceneObs) return fail("mv_group_create: a gym has scene observations attached (mv_set_scene_obs): the union launches write none; detach them first");
         for (int j = 0; j < i; ++j) if (gyms[j] == g) return fail("mv_group_create: the same gym twice");
         if (g->scenario == SCN_BOXAGONE)   // (its tick is not in the union kernels, mv_step_union.hip: tick_any)
             return fail("mv_group_create: BoxAGone cannot be stepped in a group of gyms; step it as a gym of its own (MultiTaskGym: MV_MULTITASK_UNION=0)");
@@ -648,7 +659,7 @@ int mv_recommended_pass_overlap(const mv_gym *g)
     return 1;
 }
 
-int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMask.ownedBytes + g->drawMask.ownedBytes + g->budgetBytes + g->macroBytes + g->stillBytes) : 0; }
+int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMask.ownedBytes + g->drawMask.ownedBytes + g->budgetBytes + g->macroBytes + g->stillBytes + g->sceneBytes) : 0; }
 
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index)
 {   // several gyms of one job (MultiTaskGym: one per scenario, one stream each) stepped by one call: at eight sub-gyms the per-call cost of
@@ -672,6 +683,9 @@ int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample,
     for (int i = 0; i < n; ++i)
         if (gyms[i] && !gyms[i]->closed && gyms[i]->stateObs)
             return fail("mv_step_many: gym " + std::to_string(i) + " has state observations attached (mv_set_state_obs): step it on its own, or detach them first");
+    for (int i = 0; i < n; ++i)
+        if (gyms[i] && !gyms[i]->closed && gyms[i]->sceneObs)
+            return fail("mv_step_many: gym " + std::to_string(i) + " has scene observations attached (mv_set_scene_obs): step it on its own, or detach them first");
     for (int i = 0; i < n; ++i) {
         int r = sample ? mv_sample_random_actions(gyms[i], seed, step_index) : 0;
         if (r == 0) r = step_impl(gyms[i], render != 0, 1, POLICY_NONE, 0, 0);

@@ -1,0 +1,141 @@
+// megaverse_amd/csrc/mv_scene_obs.h -- scene observations (include/megaverse_hip.h: mv_set_scene_obs): the per-ENV record, stated once for the kernels that
+// write it (mv_step_kernels.h: scene_obs_write; mv_scene_obs.hip: the gather behind a reset or mv_render) and for the host hook the tests compare it with
+// (mv_debug_scene_obs_host).  One row of MV_SCENE_OBS_FLOATS = 32 float32 per env, [N][32], taken from the env's state AFTER the tick -- auto-reset included:
+// a tick that finished an episode shows the next episode's level, as its frame does.
+// Two conversions:  copied -- the 32 bits are moved (a -0.0f, a NaN's payload, a denormal survive);  int -- an int32 converted with (float): every value
+// here is far below 2^24, so the conversion is exact.
+// Common block, every scenario:
+//    0      GymView::scenario (SCN_*)        int         8      solved                                                     int
+//    1..3   L, H, W                          int         9      highest_tower (TowerBuilding: the tower; Collect: the +1   int
+//    4      num_frames                       int                diamonds collected, mv_types.h)
+//    5, 6   episode_sec, episode_len         copied      10     bz_reward                                                  copied
+//    7      episodes_consumed: changes       int         11..14 num_objects, num_rewards, num_platforms, num_terrain       int
+//           exactly on the ticks the env takes a new episode     15     +0.0f (reserved)
+// Scenario block, columns 16..31: +0.0f wherever nothing is listed, and for every scenario not listed (Collect, Rearrange, Sokoban, HexMemory, BoxAGone, Empty):
+//    TowerBuilding     16..19  bz[0..3]: the building zone's min x, max x, min z, max z                                     int
+//    SCN_OBSTACLES     16      the number of terrain boxes i < num_terrain with type & TERRAIN_EXIT                        int
+//                      17..19, 20..22  min[3], max[3] of the FIRST such box (lowest i), as stored; zeros when there is none int
+//                      23      the number of reward objects i < num_rewards whose diamond is still there: state != 0 --    int
+//                              mv_tick_obstacles.h loads `state` into rwActive, tests it for truth, clears it on pick-up and writes it back
+//    HexExplore        16, 17  hex_target[0..1]: x, z of the reward object                                                  copied
+//    Football          16..30  the first 15 words of FootballState, in order: pos[3], radius, vel[3] copied; kicks int; ang[3] copied; contacts int;
+//                              force[3] copied
+// Units, against pos_x / pos_y / pos_z of a state-observation row (STATE_OBS_FIELDS), which are world units: TowerBuilding, the Obstacles family and Football
+// run at voxel size 1 (mv_tick_football.h; BoxAGone and Sokoban, which have no columns here, at 2), so a voxel coordinate v of columns 1..3 and 16..22 is the
+// world coordinate v: a box [min, max) covers world [min, max) on each axis, max exclusive, and an agent stands in it when min <= floor(pos) < max.  Football's
+// pos / vel / ang / force and HexExplore's target are world units already.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "mv_types.h"
+
+namespace mv {
+
+enum : int { SCENE_OBS_FLOATS = 32, SCENE_OBS_SCENARIO_COL = 16 };
+
+static_assert(offsetof(EnvHeader, H) == 4 && offsetof(EnvHeader, W) == 8 && offsetof(EnvHeader, bz) == 12, "scene observations: L, H, W, bz[4] are EnvHeader's words 0..6");
+static_assert(offsetof(EnvHeader, episode_len) == offsetof(EnvHeader, episode_sec) + 4, "scene observations: columns 5, 6 are adjacent words of EnvHeader");
+static_assert(offsetof(EnvHeader, num_rewards) == offsetof(EnvHeader, num_terrain) + 4 && offsetof(EnvHeader, num_platforms) == offsetof(EnvHeader, num_terrain) + 8,
+              "scene observations: num_terrain, num_rewards, num_platforms are adjacent words of EnvHeader");
+static_assert(offsetof(FootballState, kicks) == 28 && offsetof(FootballState, contacts) == 44 && offsetof(FootballState, force) == 48,
+              "scene observations: Football's columns 16..30 are FootballState's words 0..14, kicks word 7, contacts word 11");
+static_assert(offsetof(TerrainBox, max) == 16, "scene observations: a terrain box is min[3], type, max[3], pad");
+
+// the two predicates of the Obstacles columns
+__host__ __device__ inline bool scene_obs_is_exit(int32_t terrain_type) { return (terrain_type & TERRAIN_EXIT) != 0; }
+__host__ __device__ inline bool scene_obs_diamond_there(int8_t reward_state) { return reward_state != 0; }   // (mv_tick_obstacles.h: rwActive)
+
+// what the Obstacles columns need of the env's lists: the step kernels' wave fills it with ballots (mv_step_kernels.h: scene_obs_store), the host twin and the
+// gather kernel with the loops below -- counts and an index, so both ways give the same integers
+struct SceneObsScan {
+    int32_t exits, first_exit, diamonds;   // first_exit: -1 when exits == 0
+};
+__host__ __device__ inline SceneObsScan scene_obs_scan(const EnvHeader *h, const TerrainBox *terrain, const MovableObject *rewards)
+{
+    SceneObsScan s = {0, -1, 0};
+    for (int i = 0; i < h->num_terrain; ++i)
+        if (scene_obs_is_exit(terrain[i].type)) { if (s.exits++ == 0) s.first_exit = i; }
+    for (int i = 0; i < h->num_rewards; ++i) s.diamonds += scene_obs_diamond_there(rewards[i].state) ? 1 : 0;
+    return s;
+}
+
+__host__ __device__ inline uint32_t scene_obs_bits_of_int(int32_t v)
+{
+    const float f = (float)v;
+    uint32_t w;
+    __builtin_memcpy(&w, &f, sizeof w);
+    return w;
+}
+__host__ __device__ inline uint32_t scene_obs_bits_at(const void *p, int byte)
+{
+    uint32_t w;
+    __builtin_memcpy(&w, (const char *)p + byte, sizeof w);
+    return w;
+}
+
+// columns 1..14 -> the byte offset of the column's word in EnvHeader
+__host__ __device__ inline int scene_obs_header_offset(int f)
+{
+    switch (f) {
+    case 1: return (int)offsetof(EnvHeader, L);
+    case 2: return (int)offsetof(EnvHeader, H);
+    case 3: return (int)offsetof(EnvHeader, W);
+    case 4: return (int)offsetof(EnvHeader, num_frames);
+    case 5: return (int)offsetof(EnvHeader, episode_sec);
+    case 6: return (int)offsetof(EnvHeader, episode_len);
+    case 7: return (int)offsetof(EnvHeader, episodes_consumed);
+    case 8: return (int)offsetof(EnvHeader, solved);
+    case 9: return (int)offsetof(EnvHeader, highest_tower);
+    case 10: return (int)offsetof(EnvHeader, bz_reward);
+    case 11: return (int)offsetof(EnvHeader, num_objects);
+    case 12: return (int)offsetof(EnvHeader, num_rewards);
+    case 13: return (int)offsetof(EnvHeader, num_platforms);
+    default: return (int)offsetof(EnvHeader, num_terrain);
+    }
+}
+
+// column f (0..31) of one env's row, as its 32 bits.  terrain, rewards: the env's lists, read where scenario == SCN_OBSTACLES only (scan: their reductions,
+// likewise); fb: the env's ball, read where scenario == SCN_FOOTBALL only.  The others may be anything.  Every column is decided first -- where its word
+// lives and how it is converted; the scenario is uniform, the rest is arithmetic on the column -- and then loaded with ONE load: the 32 lanes of a wave that
+// write a row stay together instead of taking 32 paths with a load each.
+__host__ __device__ inline uint32_t scene_obs_word(int scenario, const EnvHeader *h, const TerrainBox *terrain, const MovableObject *rewards,
+                                                   const FootballState *fb, const SceneObsScan &scan, int f)
+{
+    (void)rewards;   // (its reduction is scan.diamonds)
+    enum { ZERO, COPIED, INT, VALUE };
+    int kind = ZERO, off = 0;
+    int32_t value = 0;
+    const void *src = h;
+    const int c = f - SCENE_OBS_SCENARIO_COL;   // 0..15 in the scenario block
+    if (f == 0) { kind = VALUE; value = scenario; }
+    else if (f < 15) { kind = f == 5 || f == 6 || f == 10 ? COPIED : INT; off = scene_obs_header_offset(f); }
+    else if (f == 15) kind = ZERO;
+    else if (scenario == SCN_TOWER) {
+        if (c < 4) { kind = INT; off = (int)offsetof(EnvHeader, bz) + 4 * c; }
+    } else if (scenario == SCN_OBSTACLES) {
+        if (c == 0) { kind = VALUE; value = scan.exits; }
+        else if (c == 7) { kind = VALUE; value = scan.diamonds; }
+        else if (c <= 6 && scan.first_exit >= 0) { kind = INT; src = terrain + scan.first_exit; off = c <= 3 ? 4 * (c - 1) : (int)offsetof(TerrainBox, max) + 4 * (c - 4); }
+    } else if (scenario == SCN_HEX_EXPLORE) {
+        if (c < 2) { kind = COPIED; off = (int)offsetof(EnvHeader, hex_target) + 4 * c; }
+    } else if (scenario == SCN_FOOTBALL) {
+        if (c < 15) { kind = c == 7 || c == 11 ? INT : COPIED; src = fb; off = 4 * c; }   // kicks, contacts: int
+    }
+    uint32_t w = 0u;
+    if (kind == COPIED || kind == INT) w = scene_obs_bits_at(src, off);
+    if (kind == INT) w = scene_obs_bits_of_int((int32_t)w);
+    if (kind == VALUE) w = scene_obs_bits_of_int(value);
+    return w;
+}
+
+// one env's row, on the host: the loops
+__host__ __device__ inline void scene_obs_pack(int scenario, const EnvHeader *h, const TerrainBox *terrain, const MovableObject *rewards, const FootballState *fb,
+                                               uint32_t *out32)
+{
+    SceneObsScan scan = {0, -1, 0};
+    if (scenario == SCN_OBSTACLES) scan = scene_obs_scan(h, terrain, rewards);
+    for (int f = 0; f < SCENE_OBS_FLOATS; ++f) out32[f] = scene_obs_word(scenario, h, terrain, rewards, fb, scan, f);
+}
+
+}  // namespace mv

@@ -7,7 +7,8 @@
 // No tick knows about step masks (mv_set_step_mask) or episode budgets (mv_set_episode_budget): the MASKED instantiations of the bodies choose between
 // S::tick and frozen_tick, below.  They also choose between frame_setup_body and frame_skip (mv_frame.h) for the envs a draw mask (mv_set_draw_mask) leaves out
 // and for the envs that did not change since their frames were drawn last (mv_set_still_frames: env_stale),
-// and store the agents' state rows behind every tick of a view that carries staging rows for them (mv_set_state_obs: state_obs_write).
+// and store the agents' state rows behind every tick of a view that carries staging rows for them (mv_set_state_obs: state_obs_write), and the env's scene
+// row likewise (mv_set_scene_obs: scene_obs_write).
 // Every __global__ is a one-line entry point over a body in its scenario's mv_step_<scenario>.hip (a launch bound that depends on a template
 // parameter is not applied, and the profiles name the kernels); StepKernels lists them for the launchers (mv_step.hip).
 #pragma once
@@ -16,6 +17,7 @@
 #include "mv_episode_budget.h"
 #include "mv_frame.h"
 #include "mv_macro_step.h"
+#include "mv_scene_obs.h"
 #include "mv_state_obs.h"
 #include "mv_still_frames.h"
 #include "mv_types.h"
@@ -184,6 +186,36 @@ __device__ __forceinline__ void state_obs_write(const GymView &gv, int env)
     state_obs_store(reinterpret_cast<uint32_t *>(gv.state_obs) + (size_t)env * words, gv.agents + (size_t)env * A, gv.hdr + env, words);
 }
 
+// ---- mv_set_scene_obs: the env's scene row of this tick (mv_scene_obs.h has the record): 32 words per ENV, at exactly the sites of state_obs_write and under
+// its ordering rule -- the row is loads of the state the tick wrote.  gv.scene_obs is a kernel argument, so the branch is uniform; the env's first wave writes,
+// lanes 0..31 one column each: one 128-byte store per env.  The Obstacles family's two reductions are the wave's: every lane tests one terrain box (at most
+// MAX_TERRAIN = 16) and one ballot gives the exit count (popcount) and the first exit (first set lane); the diamonds are counted in rounds of 64 lanes (at most
+// COLLECT_MAX_REWARDS = 96 reward slots: two rounds), a ballot and a popcount each.  The results are uniform integers, the ones scene_obs_scan's loops give.
+// The store is a call that is NOT inlined, for state_obs_store's reason.  Only the MASKED instantiations call it.
+static __device__ __attribute__((noinline)) void scene_obs_store(uint32_t *row, int scenario, const EnvHeader *hdr, const TerrainBox *terrain,
+                                                                 const MovableObject *rewards, const FootballState *fb)
+{
+    const int lane = threadIdx.x;   // (the env's first wave: 0..63, all of them here)
+    SceneObsScan scan = {0, -1, 0};
+    if (scenario == SCN_OBSTACLES) {   // (uniform)
+        const int nt = min(hdr->num_terrain, (int)MAX_TERRAIN), nr = min(hdr->num_rewards, (int)COLLECT_MAX_REWARDS);
+        const unsigned long long ex = __ballot(lane < nt && scene_obs_is_exit(terrain[lane].type));
+        scan.exits = __popcll(ex);
+        scan.first_exit = ex ? __ffsll(ex) - 1 : -1;
+        for (int base = 0; base < nr; base += 64)
+            scan.diamonds += __popcll(__ballot(base + lane < nr && scene_obs_diamond_there(rewards[base + lane].state)));
+    }
+    if (lane < SCENE_OBS_FLOATS) row[lane] = scene_obs_word(scenario, hdr, terrain, rewards, fb, scan, lane);
+}
+__device__ __forceinline__ void scene_obs_write(const GymView &gv, int env)
+{
+    if (gv.scene_obs == nullptr || threadIdx.x >= 64) return;
+    scene_obs_store(reinterpret_cast<uint32_t *>(gv.scene_obs) + (size_t)env * SCENE_OBS_FLOATS, gv.scenario, gv.hdr + env, gv.terrain + (size_t)env * MAX_TERRAIN,
+                    gv.rewards_obj + (size_t)env * gv.reward_stride, gv.fb + env);
+}
+// whether a view carries rows of either record (uniform): the extra barriers of the ticks without frame setup
+__device__ __forceinline__ bool obs_rows_on(const GymView &gv) { return gv.state_obs != nullptr || gv.scene_obs != nullptr; }
+
 // One workgroup per env: wave 0 runs the tick (one wave per env: physics, scenario logic, auto-reset), the others wait at the barrier (S::par_agents:
 // they take their share of the character controllers first); then the workgroup builds the lists of the env's frames (mv_frame.h).  `render` = 0:
 // mv_step_no_render.
@@ -203,7 +235,7 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
     [[maybe_unused]] int32_t left = -1;
     if constexpr (MASKED) if ((left = env_tl(gv, env) == 0 ? 0 : env_left(gv, env)) == 0) {   // (mv_set_step_mask, mv_set_episode_budget) the frozen tick, then the env's frames as below, from the unchanged state
         frozen_tick(gv, env);
-        state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs: the unchanged state, as the last launch left it)
+        state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env);   // (mv_set_state_obs: the unchanged state, as the last launch left it)
         if (!render) return;
         // (mv_set_still_frames) read by every wave IN FRONT of the barrier, stored by thread 0 behind it: no wave reads what this launch stored
         const int stale = env_stale(gv, env);
@@ -244,15 +276,15 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
 #endif
     if (!render) {
         if constexpr (MASKED) if (gv.still != nullptr && threadIdx.x == 0) still_store(gv.still + env, 1);   // (mv_set_still_frames: the env stepped, no pass follows)
-        if constexpr (MASKED) if (gv.state_obs != nullptr) {   // (mv_set_state_obs; uniform) a tick without frame setup reports its rows too
+        if constexpr (MASKED) if (obs_rows_on(gv)) {   // (mv_set_state_obs, mv_set_scene_obs; uniform) a tick without frame setup reports its rows too
             __syncthreads();   // the tick's stores before the rows' loads
-            state_obs_write<A_MAX>(gv, env);
+            state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env);
         }
         return;
     }
     __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
     MV_T(6);           // the whole tick as wave 0 saw it (incl. the generator of a finished env), up to the barrier
-    if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
+    if constexpr (MASKED) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); }   // (mv_set_state_obs, mv_set_scene_obs)
     // (mv_set_still_frames: the env stepped -- stale where the draw mask leaves it out, drawn and fresh otherwise; nobody reads the byte in this launch)
     if constexpr (MASKED) if (!env_drawn(gv, env)) {   // (mv_set_draw_mask; uniform)
         if (gv.still != nullptr && threadIdx.x == 0) still_store(gv.still + env, 1);
@@ -314,7 +346,7 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
             else frozen_tick(gv, env);
             wave_sync();   // the tick's stores before the frame setup's loads (one wave: no barrier needed)
             if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
-            if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
+            if constexpr (MASKED) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); }   // (mv_set_state_obs, mv_set_scene_obs)
             if (!MASKED || (drawn && stale != 0)) {
                 frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
                 if constexpr (MASKED) stale = still::still_after_frames(stale, still::VERDICT_DRAWN);
@@ -324,7 +356,7 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
             else frozen_tick(gv, env);
             __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
             if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
-            if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
+            if constexpr (MASKED) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); }   // (mv_set_state_obs, mv_set_scene_obs)
             if (!MASKED || (drawn && stale != 0)) {
                 const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
                 for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
@@ -371,8 +403,8 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
                 __syncthreads();   // the tick's stores (same CU: same L1) before the next tick's loads
             }
             if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
-            if constexpr (MASKED) if (gv.state_obs != nullptr) {   // (mv_set_state_obs; uniform)
-                state_obs_write<A_MAX>(gv, env);
+            if constexpr (MASKED) if (obs_rows_on(gv)) {   // (mv_set_state_obs, mv_set_scene_obs; uniform)
+                state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env);
                 if constexpr (A_MAX > 1) __syncthreads();   // the rows' loads before the other waves' next tick changes the state
             }
         }
@@ -392,7 +424,7 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
                 else frozen_tick(gv, env);
                 wave_sync();   // the tick's stores before the frame setup's / the next tick's loads
                 if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
-                if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
+                if constexpr (MASKED) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); }   // (mv_set_state_obs, mv_set_scene_obs)
                 if (frames) {
                     if (!MASKED || (drawn && stale != 0)) {
                         frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
@@ -404,7 +436,7 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
                 else frozen_tick(gv, env);
                 __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's / the next tick's loads
                 if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
-                if constexpr (MASKED) state_obs_write<A_MAX>(gv, env);   // (mv_set_state_obs)
+                if constexpr (MASKED) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); }   // (mv_set_state_obs, mv_set_scene_obs)
                 if (frames) {
                     if (!MASKED || (drawn && stale != 0)) {
                         const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
@@ -413,7 +445,7 @@ __device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
                     } else env_frames_skip<false, 64, true>(gv, env, skip_marker(drawn));
                     __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
                 } else if constexpr (MASKED) {
-                    if (gv.state_obs != nullptr) __syncthreads();   // (mv_set_state_obs; uniform) the rows' loads before the other waves' next tick changes the state
+                    if (obs_rows_on(gv)) __syncthreads();   // (mv_set_state_obs, mv_set_scene_obs; uniform) the rows' loads before the other waves' next tick changes the state
                 }
             }
         }
@@ -451,8 +483,8 @@ __device__ __forceinline__ void step_ticks_pipe_body(const Args &a, int W, int H
                 frozen_tick(a.view(j), env);
             }
             __syncthreads();                              // A(j)
-            // (mv_set_state_obs) tick j's rows: behind A(j), in front of tick j + 1, whose write-back comes behind B(j) and is this wave's own
-            if constexpr (MASKED) state_obs_write<1>(a.view(j), env);
+            // (mv_set_state_obs, mv_set_scene_obs) tick j's rows: behind A(j), in front of tick j + 1, whose write-back comes behind B(j) and is this wave's own
+            if constexpr (MASKED) { state_obs_write<1>(a.view(j), env); scene_obs_write(a.view(j), env); }
         }
         __syncthreads();                                  // B(n - 1): the last frame setup's
     } else {

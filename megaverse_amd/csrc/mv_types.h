@@ -214,6 +214,10 @@ struct GymView {
     // bodies store every agent's row here (mv_step_kernels.h: state_obs_write), and one launch per stepping call carries the rows to the caller's buffer
     // (mv_state_obs.hip).  null: off.  A field of the per-slot views (mv_gym::gvp), so tick_view leaves it alone; the union launches never see a non-null one.
     float *state_obs;
+    // mv_set_scene_obs: [N][32] float32, this tick's staging rows of the scene observations (mv_scene_obs.h has the record), the per-ENV counterpart of
+    // state_obs: behind the tick the MASKED step bodies store the env's row here (mv_step_kernels.h: scene_obs_write), and the stepping call's one publication
+    // launch carries the rows to the caller's buffer (mv_scene_obs.hip).  null: off.  A field of the per-slot views (mv_gym::gvp), like state_obs.
+    float *scene_obs;
     // mv_macro_step: [N] ticks each env may still step in this call (0: its macro step is over -- its ticks are frozen ticks), written by the MASKED step
     // bodies behind every tick the env stepped in (mv_step_kernels.h: after_tick; mv_macro_step.h has the rule); null: no macro step in flight.  Set by the
     // views of a macro step's ticks only (mv_api_step.hip).

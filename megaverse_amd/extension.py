@@ -103,6 +103,8 @@ SYMBOLS = [
     ("mv_set_draw_mask", C.c_int, [_P, _P]), ("mv_set_draw_mask_host", C.c_int, [_P, _P]), ("mv_get_draw_mask", C.c_int, [_P]),
     ("mv_set_state_obs", C.c_int, [_P, _P]), ("mv_get_state_obs", C.c_int, [_P]), ("mv_get_state_observation", C.c_int, [_P, _I, _I, _P]),
     ("mv_debug_state_obs_host", C.c_int, [_P, _P, _P]), ("mv_get_output_ring", C.c_int, [_P]),
+    ("mv_set_scene_obs", C.c_int, [_P, _P]), ("mv_get_scene_obs", C.c_int, [_P]), ("mv_get_scene_observation", C.c_int, [_P, _I, _P]),
+    ("mv_debug_scene_obs_host", C.c_int, [_I, _P, _P, _P, _I, _P, _P]),
     ("mv_macro_step", C.c_int, [_P, _I, _P, _P, _I]), ("mv_macro_step_host", C.c_int, [_P, _I, _P, _P, _I]),
     ("mv_debug_episode_log_macro_host", C.c_int, [_P, _P, _P, _I, _I, _I, _I, _U, _P, _P, _P, C.POINTER(_U), C.POINTER(_U), _P, _P, _P]),
     ("mv_debug_macro_rule_host", C.c_int, [_P, _P, _P, _P, _I, _I, _P, _P, _P]), ("mv_debug_macro_fold_host", C.c_int, [_P, _I, _I, _P]),
@@ -127,6 +129,48 @@ def debug_state_obs_host(agent_state, env_header):
         raise ValueError("debug_state_obs_host: an AgentState and an EnvHeader are 128 bytes each")
     out = np.empty(MV_STATE_OBS_FLOATS, np.float32)
     if lib.mv_debug_state_obs_host(a.ctypes.data, h.ctypes.data, out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
+
+# include/megaverse_hip.h: MV_SCENE_OBS_FLOATS and the columns of a scene-observation row (mv_set_scene_obs).  SCENE_OBS_FIELDS: columns 0..15, the same for every
+# scenario, name -> index; SCENE_OBS_SCENARIO_FIELDS: scenario name -> {column name: index} for columns 16..31 ({}: the scenario has none, its block is +0.0f).
+# Voxel coordinates (room_*, bz_*, exit_*) are world coordinates at voxel size 1: comparable with pos_x / pos_y / pos_z of STATE_OBS_FIELDS as they are.
+MV_SCENE_OBS_FLOATS = 32
+SCENE_OBS_FIELDS = {name: i for i, name in enumerate((
+    "scenario", "room_l", "room_h", "room_w", "num_frames", "episode_sec", "episode_len", "episodes_consumed", "solved", "highest_tower", "bz_reward",
+    "num_objects", "num_rewards", "num_platforms", "num_terrain", "reserved"))}
+_SCENE_TOWER = {"bz_min_x": 16, "bz_max_x": 17, "bz_min_z": 18, "bz_max_z": 19}
+_SCENE_OBSTACLES = {"num_exits": 16, "exit_min_x": 17, "exit_min_y": 18, "exit_min_z": 19, "exit_max_x": 20, "exit_max_y": 21, "exit_max_z": 22,
+                    "diamonds_left": 23}
+_SCENE_HEX_EXPLORE = {"target_x": 16, "target_z": 17}
+_SCENE_FOOTBALL = {"ball_x": 16, "ball_y": 17, "ball_z": 18, "ball_radius": 19, "ball_vx": 20, "ball_vy": 21, "ball_vz": 22, "kicks": 23,
+                   "ball_wx": 24, "ball_wy": 25, "ball_wz": 26, "contacts": 27, "ball_fx": 28, "ball_fy": 29, "ball_fz": 30}
+SCENE_OBS_SCENARIO_FIELDS = {
+    "TowerBuilding": _SCENE_TOWER, "ObstaclesEasy": _SCENE_OBSTACLES, "ObstaclesMedium": _SCENE_OBSTACLES, "ObstaclesHard": _SCENE_OBSTACLES,
+    "ObstaclesWalls": _SCENE_OBSTACLES, "ObstaclesSteps": _SCENE_OBSTACLES, "ObstaclesLava": _SCENE_OBSTACLES, "HexExplore": _SCENE_HEX_EXPLORE,
+    "Football": _SCENE_FOOTBALL, "Collect": {}, "Sokoban": {}, "HexMemory": {}, "Rearrange": {}, "Empty": {}, "BoxAGone": {}}
+
+
+def debug_scene_obs_host(scenario, env_header, terrain=None, rewards=None, football_state=None):
+    """mv_debug_scene_obs_host: the scene-observation record on the CPU (no device): the SCN_* family id, the 128 bytes of one EnvHeader, the 512 bytes of 16
+    TerrainBox, 4 bytes per MovableObject of the reward list (at most 96) and the 64 bytes of one FootballState (megaverse_amd/csrc/mv_types.h; what the
+    scenario does not read may be None) -> the env's row, float32 [32]"""
+    lib = load_library()
+    def raw(x, size, what):
+        if x is None:
+            return None
+        b = np.ascontiguousarray(np.frombuffer(bytes(x), np.uint8))
+        if size is not None and b.size != size:
+            raise ValueError(f"debug_scene_obs_host: {what} is {size} bytes")
+        return b
+    h, t, f = raw(env_header, 128, "an EnvHeader"), raw(terrain, 512, "a terrain list"), raw(football_state, 64, "a FootballState")
+    r = raw(rewards, None, "a reward list")
+    if h is None or (r is not None and r.size % 4):
+        raise ValueError("debug_scene_obs_host: an EnvHeader is required, and a reward list is 4 bytes per object")
+    ptr = lambda b: None if b is None or b.size == 0 else b.ctypes.data   # noqa: E731
+    out = np.empty(MV_SCENE_OBS_FLOATS, np.float32)
+    if lib.mv_debug_scene_obs_host(int(scenario), ptr(h), ptr(t), ptr(r), 0 if r is None else r.size // 4, ptr(f), out.ctypes.data) != 0:
         raise RuntimeError(lib.mv_last_error().decode())
     return out
 
@@ -500,6 +544,21 @@ def check_state_obs(buf, entries, num_rows, device):
     return buf
 
 
+def check_scene_obs(buf, entries, num_envs, device):
+    """the argument check of MegaverseGym.set_scene_obs for a tensor: contiguous torch.float32 of shape (entries, num_envs, 32) on CUDA device `device`;
+    entries None: any number of entries (the check made before the gym is asked for its ring count)"""
+    got = tuple(getattr(buf, 'shape', ()))
+    shape = ((got[0] if len(got) == 3 else 1) if entries is None else int(entries), int(num_envs), MV_SCENE_OBS_FLOATS)
+    contiguous = getattr(buf, 'is_contiguous', None)
+    dev = getattr(buf, 'device', None)
+    index = getattr(dev, 'index', None)
+    if not hasattr(buf, 'data_ptr') or got != shape or str(getattr(buf, 'dtype', None)) != 'torch.float32' \
+            or not getattr(buf, 'is_cuda', False) or not (callable(contiguous) and contiguous()) or (index is not None and int(index) != int(device)):
+        raise ValueError(f'set_scene_obs: the buffer must be a contiguous float32 CUDA tensor of shape {shape} on device {int(device)}, '
+                         f"got {getattr(buf, 'dtype', type(buf).__name__)} {tuple(getattr(buf, 'shape', ()))} on {dev if dev is not None else 'no device'}")
+    return buf
+
+
 def check_episode_budget(budget, num_envs):
     """the argument check of MegaverseGym.set_episode_budget: None (detach) -> None; an int -> that value for every env; a contiguous torch.int32 CUDA tensor
     of shape (num_envs,) (or anything with data_ptr()) -> 'device'; anything else -> a contiguous int32 numpy array, one value per env"""
@@ -703,6 +762,8 @@ class MegaverseGym:
         self._step_mask_held = None  # set_step_mask: the caller's device mask, kept until it is replaced or detached
         self._draw_mask_held = None  # set_draw_mask: the caller's device mask, kept until it is replaced or detached
         self._state_obs = None       # set_state_obs: the attached tensor
+        self._scene_obs = None       # set_scene_obs: the attached tensor
+        self._ring_ticks = 0         # ticks stepped through this object since set_output_ring (the library's own count: which entry the last tick went to)
         self._macro_held = None      # macro_step: the caller's device tensors of the last call, read in stream order: kept until the next macro step
         self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
         self._store_held = []    # save_envs / load_envs: the caller's stores and device maps, kept until the next step has been enqueued
@@ -741,6 +802,7 @@ class MegaverseGym:
 
     def step(self):
         self._ckw(self._lib.mv_step(self._g))
+        self._ring_ticks += 1
         self._fork_held = self._reset_held = self._budget_held = None
         self._store_held = []
         self._seed_held = []
@@ -820,6 +882,7 @@ class MegaverseGym:
 
     def step_no_render(self):
         self._ckw(self._lib.mv_step_no_render(self._g))
+        self._ring_ticks += 1
         self._fork_held = self._reset_held = self._budget_held = None
         self._store_held = []
         self._seed_held = []
@@ -835,6 +898,7 @@ class MegaverseGym:
         mode = render_mode_of(render)
         args = (self._g, int(k), int(self.POLICIES.get(policy, policy)), int(seed) & 0xFFFFFFFF, int(first_step_index) & 0xFFFFFFFF)
         self._ckw(self._lib.mv_step_n(*args) if mode == 0 else self._lib.mv_step_n_render(*args, mode))
+        self._ring_ticks += int(k)
         self._fork_held = self._reset_held = self._budget_held = None
         self._store_held = []
         self._seed_held = []
@@ -854,6 +918,7 @@ class MegaverseGym:
         else:
             rc = self._lib.mv_macro_step_host(self._g, int(k), a.ctypes.data, None if t is None else t.ctypes.data, mode)
         self._ckw(rc)
+        self._ring_ticks += 1
         self._fork_held = self._reset_held = self._budget_held = None
         self._store_held = []
         self._seed_held = []
@@ -1043,6 +1108,46 @@ class MegaverseGym:
         """-> the tensor set_state_obs attached, or None"""
         return self._state_obs
 
+    def set_scene_obs(self, buf=True):
+        """Scene observations (include/megaverse_hip.h: mv_set_scene_obs), the per-env counterpart of set_state_obs: every tick of every later stepping call
+        leaves one row of 32 float32 per ENV (SCENE_OBS_FIELDS: room, episode time and counter, solved, tower, counts; SCENE_OBS_SCENARIO_FIELDS: the
+        building zone, the exit pad and the diamonds left, the hex target, the ball; the state AFTER the tick) in entry t % entries of a float32 CUDA tensor
+        [entries, num_envs, 32], entries = the output ring's count, or 1 without a ring.  True allocates the tensor on the gym's device and returns it; a
+        tensor is checked (ValueError) and attached; None detaches.  Nothing waits on the host.  While attached, set_output_ring is refused."""
+        if buf is None:
+            self._ck(self._lib.mv_set_scene_obs(self._g, None))
+            self._scene_obs = None
+            return None
+        if buf is not True:
+            check_scene_obs(buf, None, self.num_envs, self.device)   # (what needs no gym first)
+        entries = max(1, self._ck(self._lib.mv_get_output_ring(self._g)))
+        if buf is True:
+            import torch
+            buf = torch.zeros((entries, self.num_envs, MV_SCENE_OBS_FLOATS), dtype=torch.float32, device=f'cuda:{self.device}')
+        else:
+            check_scene_obs(buf, entries, self.num_envs, self.device)
+        self._ck(self._lib.mv_set_scene_obs(self._g, _P(int(buf.data_ptr()))))
+        self._scene_obs = buf
+        return buf
+
+    def scene_obs_ring(self):
+        """-> the tensor set_scene_obs attached, [entries, num_envs, 32] (entry t % entries: what tick t left), or None"""
+        return self._scene_obs
+
+    def scene_obs(self):
+        """-> the entry of the last tick, (num_envs, 32): a view of the attached tensor, valid in the order of the gym's stream; None with nothing attached.
+        With an output ring: the entry the last tick stepped through this object went to (scene_obs_ring has them all)"""
+        if self._scene_obs is None:
+            return None
+        entries = int(self._scene_obs.shape[0])   # (ticks stepped by calling the library directly, past this object, are not counted)
+        return self._scene_obs[(max(1, self._ring_ticks) - 1) % entries]
+
+    def get_scene_observation(self, env_idx):
+        """-> numpy float32 [32]: the last tick's row of one env (waits for the gym's stream)"""
+        out = np.empty(MV_SCENE_OBS_FLOATS, np.float32)
+        self._ck(self._lib.mv_get_scene_observation(self._g, int(env_idx), out.ctypes.data))
+        return out
+
     def get_state_observation(self, env_idx, agent_idx):
         """-> numpy float32 [16]: the last tick's row of one agent (waits for the gym's stream)"""
         out = np.empty(MV_STATE_OBS_FLOATS, np.float32)
@@ -1109,6 +1214,7 @@ class MegaverseGym:
     def set_output_ring(self, count, obs_ptr=0, rewards_ptr=0, dones_ptr=0):
         """tick t leaves its outputs in entry t % count of the given device rings (0 = keep that output in its single array)"""
         self._ck(self._lib.mv_set_output_ring(self._g, int(count), _P(int(obs_ptr) or None), _P(int(rewards_ptr) or None), _P(int(dones_ptr) or None)))
+        self._ring_ticks = 0
 
     def set_pass_overlap(self, on=True):
         """with a ring at least two calls deep, the observation passes of consecutive step_n calls overlap (include/megaverse_hip.h: mv_set_pass_overlap);

@@ -18,7 +18,7 @@ Differences, all additive:
 import numpy as np
 
 from . import spaces
-from .extension import MegaverseGym, STATE_OBS_FIELDS, render_mode_of, set_megaverse_log_level
+from .extension import MegaverseGym, SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS, STATE_OBS_FIELDS, render_mode_of, set_megaverse_log_level
 
 MEGAVERSE8 = ['TowerBuilding', 'ObstaclesEasy', 'ObstaclesHard', 'Collect', 'Sokoban', 'HexMemory', 'HexExplore', 'Rearrange']
 OBSTACLES_MULTITASK = ['ObstaclesWalls', 'ObstaclesSteps', 'ObstaclesLava', 'ObstaclesEasy', 'ObstaclesHard']
@@ -69,7 +69,7 @@ def check_sequence_actions(actions, num_agents):
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
                  img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1,
-                 still_frames=False):
+                 still_frames=False, scene_obs=False):
         if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
         # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
@@ -116,6 +116,11 @@ class MegaverseEnv:
         # observation byte stays what it is without the option
         if still_frames:
             self.env.set_still_frames(True)
+        # scene_obs: every tick leaves one row of 32 float32 per ENV (SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS: level, goal and ball) in a CUDA tensor
+        # (mv_set_scene_obs), read with self.scene_obs()
+        self._scene_on = bool(scene_obs)
+        if self._scene_on:
+            self.env.set_scene_obs(True)
         self.default_shaping_scheme = self.env.get_reward_shaping(0, 0)
         self.action_space = self.generate_action_space(self.env.action_space_sizes())
         self.observation_space = spaces.Box(0, 255, (self.channels, self.img_h, self.img_w), dtype=np.uint8)
@@ -138,14 +143,29 @@ class MegaverseEnv:
             raise RuntimeError("state_obs: create the env with state_obs=True")
         return buf[self._seq[0][0] - 1 if self._seq is not None else 0]
 
+    SCENE_OBS_FIELDS = SCENE_OBS_FIELDS                     # column name -> index of a scene_obs() row, columns 0..15 (the tables MegaverseGym shares)
+    SCENE_OBS_SCENARIO_FIELDS = SCENE_OBS_SCENARIO_FIELDS   # scenario name -> {column name: index}, columns 16..31
+
+    def scene_obs(self):
+        """the last tick's scene observations: float32 (num_envs, 32) on the device, columns SCENE_OBS_FIELDS and SCENE_OBS_SCENARIO_FIELDS[scenario] -- a view
+        of the attached buffer, under state_obs()'s rules: ask again after every call.  Needs MegaverseEnv(..., scene_obs=True)."""
+        buf = self.env.scene_obs_ring()
+        if buf is None:
+            raise RuntimeError("scene_obs: create the env with scene_obs=True")
+        return buf[self._seq[0][0] - 1 if self._seq is not None else 0]
+
     def _set_output_ring(self, count, *ptrs):
         """the env's own output rings change (step_device, step_sequence): the state buffer is one more ring of the same depth and the library refuses a ring
         change while it is attached, so it is detached around the change and a buffer of the new depth attached"""
         if self._state_on:
             self.env.set_state_obs(None)
+        if self._scene_on:
+            self.env.set_scene_obs(None)
         self.env.set_output_ring(count, *ptrs)
         if self._state_on:
             self.env.set_state_obs(True)
+        if self._scene_on:
+            self.env.set_scene_obs(True)
 
     @staticmethod
     def generate_action_space(action_space_sizes):
