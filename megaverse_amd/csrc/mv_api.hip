@@ -104,10 +104,10 @@ int check(mv_gym *g)
     return 0;
 }
 
-int attach_check(mv_gym *g, const char *who, const char *noun)
+int attach_check(mv_gym *g, const char *who, const GymOption &opt)
 {
     if (check(g)) { g_err = std::string(who) + ": " + g_err; return -1; }
-    if (g->inGroup) return fail(std::string(who) + ": this gym belongs to an mv_group, whose union launches read no " + noun);
+    if (g->inGroup) return fail(std::string(who) + ": this gym belongs to an mv_group, whose union launches " + opt.memberNone);
     return 0;
 }
 
@@ -784,8 +784,7 @@ int mv_close(mv_gym *g)
     g->resetApplied = nullptr;
     g->seedEnvsPair.release();
     env_masks_free(g);
-    state_obs_free(g);
-    scene_obs_free(g);
+    obs_rows_free(g);
     episode_budget_free(g);
     macro_step_free(g);
     still_frames_free(g);
@@ -943,8 +942,7 @@ int mv_render(mv_gym *g)
     if (check(g)) return -1;
     if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     if (render_frames(g)) return -1;
-    if (state_obs_refresh(g, nullptr)) return -1;   // (mv_set_state_obs: the last tick's rows from the current state, as its frames; also behind mv_reset)
-    return scene_obs_refresh(g, nullptr);           // (mv_set_scene_obs: likewise)
+    return obs_rows_refresh(g, nullptr);   // (mv_set_state_obs, mv_set_scene_obs: the last tick's rows from the current state, as its frames; also behind mv_reset)
 }
 
 }  // extern "C"
@@ -956,7 +954,8 @@ int mvapi::render_frames(mv_gym *g)
     if (take_hist(g, g->stream, true)) return -1;
     g->layoutFixed = true;
     GymView v = view(g, g->parity);
-    v.draw_mask = g->drawMask.live;   // (mv_set_draw_mask: also the frame behind mv_reset and mv_reset_envs(render = 1), which come through here)
+    // (not fill_view_options: a pass reads the draw mask alone, and mv_render draws still frames too.  Also the frame behind mv_reset and mv_reset_envs(render = 1))
+    v.draw_mask = g->drawMask.live;
     if (launch_raster(v, last_outputs(g).obs, g->w, g->h, g->stream, nullptr, g->fastPixels))
         return fail("mv_render: observation size above 1024x1024");
     HIP_TRY(hipGetLastError());
@@ -1299,9 +1298,9 @@ int mv_set_sample_policy(mv_gym *g, int32_t policy)
 int mv_set_output_ring(mv_gym *g, int32_t count, void *obs, float *rewards, uint8_t *dones)
 {
     if (check(g)) return -1;
-    if (g->stateObs)   // (the state buffer is one more ring of the count it was attached under)
+    if (g->stateRows.buf)   // (the state buffer is one more ring of the count it was attached under)
         return fail("mv_set_output_ring: state observations are attached (mv_set_state_obs), sized by the ring count they were attached under: detach the state observations first");
-    if (g->sceneObs)
+    if (g->sceneRows.buf)
         return fail("mv_set_output_ring: scene observations are attached (mv_set_scene_obs), sized by the ring count they were attached under: detach the scene observations first");
     if (count < 0 || (count > 0 && !obs && !rewards && !dones)) return fail("mv_set_output_ring: count >= 0 and at least one ring required");
     if (count > 0 && obs && g->obsLayout == MV_OBS_RGB_PLANAR && (uintptr_t)obs % planar_alignment(g->w))

@@ -9,11 +9,12 @@
 //   mv_env_store.hip  env stores: the save / load kernels, their entry points and host-only hooks
 //   mv_env_masks.hip  step masks and draw masks: attaching and detaching the bytes that freeze envs (mv_step_kernels.h: frozen_tick) and the bytes that leave
 //                     envs' frames out of the observation passes (mv_frame.h: frame_skip)
-//   mv_state_obs.hip  state observations: attaching the caller's buffer, the staging rows, their publication and refresh (mv_state_obs.h: the record)
-//   mv_scene_obs.hip  scene observations: the per-env counterpart, and the one publication launch both records share (mv_scene_obs.h: the record)
+//   mv_obs_rows.hip   state and scene observations: attaching the caller's buffers, the staging rows, the one publication launch both records share, their
+//                     refresh (mv_state_obs.h, mv_scene_obs.h: the records)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 //   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
 //   mv_still_frames.hip  still frames: switching the option, the memset behind calls that change what frames show, the carry launch (mv_still_frames.h: the rule)
+// The persistent per-gym options are stated once, below mv_gym: gym_options (who refuses what, in which words) and fill_view_options (what a view carries).
 // mv_staging.h holds the two ways the host forms' values reach the device (StagingPool, StagingPair).
 // The C ABI itself is include/megaverse_hip.h; nothing here is exported under a C name.
 #pragma once
@@ -108,6 +109,20 @@ namespace mvapi {
 struct MacroCall {
     const int32_t *actions;   // [N*A][6] device memory
     bool first, last;
+};
+}  // namespace mvapi
+
+namespace mvapi {
+// One row record of a gym (mv_obs_rows.hip: state observations [N*A][16], scene observations [N][32]).  buf: the caller's [entries][words] float32 buffer (null:
+// off; entries: the output ring's count when it was attached, or 1); stage: the gym's staging rows [slots][words], allocated at the first attach and kept
+// until mv_close (stageBytes; not part of the arena).  While attached, the record's field of gvp[q] points at slot q's rows: the stepping calls' views carry it
+// to the MASKED step kernels.
+struct ObsRows {
+    float *buf = nullptr, *stage = nullptr;
+    int entries = 0;
+    size_t stageBytes = 0, words = 0;   // words: of one entry, the whole gym's rows
+    // tick `tick`'s entry of the caller's buffer: the entry its rewards go to (outputs_of)
+    float *entry(unsigned long long tick) const { return buf + (size_t)(tick % (unsigned long long)entries) * words; }
 };
 }  // namespace mvapi
 
@@ -270,17 +285,8 @@ struct mv_gym {
     EnvMask stepMask;
     // mv_set_draw_mask: the bytes the frame setups read (GymView::draw_mask through the views of the stepping calls and of mv_render)
     EnvMask drawMask;
-    // mv_set_state_obs: the caller's [stateEntries][N*A][16] float32 buffer (null: off; stateEntries: the output ring's count when it was attached, or 1) and
-    // the gym's staging rows [slots][N*A][16], allocated at the first attach and kept until mv_close -- not part of the arena, not counted in mv_arena_bytes.
-    // While attached, gvp[q].state_obs points at slot q's rows: the stepping calls' views carry it to the MASKED step kernels.
-    float *stateObs = nullptr, *stateStage = nullptr;
-    int stateEntries = 0;
-    // mv_set_scene_obs: the caller's [sceneEntries][N][32] float32 buffer (null: off; sceneEntries as stateEntries) and the gym's staging rows [slots][N][32],
-    // allocated at the first attach, kept until mv_close and counted in mv_arena_bytes from then on (sceneBytes).  While attached, gvp[q].scene_obs points at
-    // slot q's rows.
-    float *sceneObs = nullptr, *sceneStage = nullptr;
-    int sceneEntries = 0;
-    size_t sceneBytes = 0;
+    // mv_set_state_obs, mv_set_scene_obs (ObsRows).  The scene rows' staging is counted in mv_arena_bytes from its allocation on, the state rows' is not.
+    ObsRows stateRows, sceneRows;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
     // budgetLeft [N], what the step kernels read and write (GymView::budget, through the stepping calls' views, while budgetOn); budgetHalted, the count of
     // zeros in it; budgetMirror [N], the episode log's own copy, advanced by the log's update tick by tick.  The host form's values travel through a pool of
@@ -313,13 +319,46 @@ struct mv_gym {
 };
 
 namespace mvapi {
+// ---- The persistent per-gym options, stated once: one descriptor each, in the order every refusal walks them.  A new option is one row here and one line in
+// fill_view_options.
+struct GymOption {
+    const char *setter;       // the entry point that attaches it
+    const char *has;          // mv_group_create / mv_step_many: "a gym has <has> (<setter>)"
+    const char *unionNone;    // mv_group_create: "the union launches <unionNone>"
+    const char *detach;       // mv_group_create: "<detach>"
+    const char *detachMany;   // mv_step_many: "step it on its own, or <detachMany>"
+    const char *memberNone;   // attach_check: "whose union launches <memberNone>"
+    bool (*on)(const mv_gym *);
+};
+enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_COUNT };
+#define MV_OPT_ON(expr) +[](const mv_gym *g) -> bool { return expr; }
+inline constexpr GymOption gym_options[OPT_COUNT] = {
+    {"mv_set_step_mask", "a step mask attached", "read none", "detach it first", "detach the mask first", "read no step mask", MV_OPT_ON(g->stepMask.live)},
+    {"mv_set_draw_mask", "a draw mask attached", "read none", "detach it first", "detach the mask first", "read no draw mask", MV_OPT_ON(g->drawMask.live)},
+    {"mv_set_still_frames", "still frames switched on", "read no stale bytes", "switch them off first", "switch them off first", "read no stale bytes", MV_OPT_ON(g->stillOn)},
+    {"mv_set_episode_budget", "an episode budget attached", "read none", "detach it first", "detach the budget first", "read no episode budget", MV_OPT_ON(g->budgetOn)},
+    {"mv_set_state_obs", "state observations attached", "write none", "detach them first", "detach them first", "write no state observations", MV_OPT_ON(g->stateRows.buf)},
+    {"mv_set_scene_obs", "scene observations attached", "write none", "detach them first", "detach them first", "write no scene observations", MV_OPT_ON(g->sceneRows.buf)},
+};
+#undef MV_OPT_ON
+// What a stepping call's view of g carries of the options (the rows of the two records are fields of the per-slot views already: mv_gym::gvp); macro: the view
+// belongs to a macro step's tick (mv_macro_step) and carries the envs' ticks left.  A group's members have none of them (mv_group_create).
+inline void fill_view_options(GymView &v, const mv_gym *g, bool macro)
+{
+    v.step_mask = g->stepMask.live;
+    v.draw_mask = g->drawMask.live;
+    if (g->budgetOn) { v.budget = g->budgetLeft; v.halted = g->budgetHalted; }
+    if (g->stillOn) v.still = g->stillStale;
+    if (macro) v.macro_tl = g->macroTl;
+}
+
 // Where a tick's public outputs go: the observation slab and the reward / done arrays -- or, with mv_set_output_ring, entry (tick % count)
 // of the caller's rings.  true_objective is state (only a finishing env records it, vector_env.cpp:96-101): never ringed.
 struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; };
 std::string lower(const char *s);
 int check(mv_gym *g);
-// what every form of a persistent attachment refuses: no gym, a closed one, a member of a group (the union launches read no <noun>)
-int attach_check(mv_gym *g, const char *who, const char *noun);
+// what every form of a persistent attachment refuses: no gym, a closed one, a member of a group (the union launches read or write none of what opt attaches)
+int attach_check(mv_gym *g, const char *who, const GymOption &opt);
 int getter_check(const mv_gym *g, const char *who);   // the mv_get_* form getters: no gym, a closed one
 OutPtrs outputs_of(const mv_gym *g, unsigned long long tick);
 OutPtrs last_outputs(const mv_gym *g);   // of the last tick (reset / render / getters)
@@ -360,22 +399,13 @@ int still_frames_carry(mv_gym *g, const GymView *views, const OutPtrs *outs, int
 int publish_macro(mv_gym *g, int q0, const OutPtrs &o, int k, bool cont);
 // mv_api_step.hip: one chunk (<= batch ticks) of a macro step of kCall ticks; quiet: QUIET_NONE / QUIET_LAST of step_gyms
 int step_macro_chunk(mv_gym *g, int k, int kCall, bool draw_last, const MacroCall &mc);
-// mv_state_obs.hip: tick `tick`'s entry of the caller's buffer (the entry outputs_of gives its rewards); the staged rows of the k ticks in slots q0 .. q0 + k - 1
-// -> dst[j], one launch on the caller's stream; the last tick's entry gathered from the current state (mask: device bytes [N], only the flagged envs' rows;
-// null: every row; nothing attached: no launch), on the caller's stream behind sim_join
-float *state_obs_entry(const mv_gym *g, unsigned long long tick);
-int state_obs_publish(mv_gym *g, int q0, float *const *dst, int k);
-int state_obs_refresh(mv_gym *g, const uint8_t *device_mask);
-void state_obs_free(mv_gym *g);        // mv_close
-// mv_scene_obs.hip, likewise for the scene rows.  scene_obs_publish: the stepping call's ONE publication launch of a gym with scene observations -- it carries
-// the state rows too when both records are attached (state_dst: tick j's entries of the state buffer, null: that record is off; state_obs_publish is the
-// launch of a gym with state observations alone) -- the staged rows of the k ticks in slots q0 .. q0 + k - 1 -> dst[j], on the caller's stream;
-// scene_obs_refresh: the last tick's entry gathered from the current state (mask as state_obs_refresh's), behind sim_join
-float *scene_obs_entry(const mv_gym *g, unsigned long long tick);
-int scene_obs_publish(mv_gym *g, int q0, float *const *scene_dst, float *const *state_dst, int k);
-int scene_obs_refresh(mv_gym *g, const uint8_t *device_mask);
-void scene_obs_free(mv_gym *g);        // mv_close
-size_t state_obs_words(const mv_gym *g);   // (mv_state_obs.hip)
+// mv_obs_rows.hip.  publish: the stepping call's ONE publication launch for both records -- the staged rows of the k ticks in slots q0 .. q0 + k - 1 -> the
+// entries of ticks tick0 .. tick0 + k - 1 of the caller's buffers, on the caller's stream; -> 1: launched, 0: no record attached.  refresh: the last tick's
+// entries gathered from the current state (mask: device bytes [N], only the flagged envs' rows; null: every row; nothing attached: no launch), on the caller's
+// stream behind sim_join
+int obs_rows_publish(mv_gym *g, int q0, unsigned long long tick0, int k);
+int obs_rows_refresh(mv_gym *g, const uint8_t *device_mask);
+void obs_rows_free(mv_gym *g);         // mv_close
 int render_frames(mv_gym *g);          // mv_render without the state rows' refresh (mv_api.hip; mv_reset_envs refreshes the flagged envs' rows only)
 int episode_budget_seed_mirror(mv_gym *g);   // mv_set_episode_log: the log's mirror from the live array (mv_episode_budget.hip)
 // mv_fork.hip, shared with mv_env_store.hip: what every fork / resample / env-store form refuses (what: "forks", "env stores": for the text about groups)

@@ -62,7 +62,7 @@ extern "C" {
 
 int mv_set_step_mask(mv_gym *g, const uint8_t *device_mask)
 {
-    if (attach_check(g, "mv_set_step_mask", "step mask")) return -1;
+    if (attach_check(g, "mv_set_step_mask", gym_options[OPT_STEP_MASK])) return -1;
     // No launch, no copy: the step kernels read the caller's buffer.  This call is the ordering point, as mv_set_action_ring is: what the caller's stream holds
     // now -- the kernel that wrote the mask -- comes before the next step launch; the calls after that one pipeline freely.
     return set_device(g, g->stepMask, device_mask);
@@ -70,7 +70,7 @@ int mv_set_step_mask(mv_gym *g, const uint8_t *device_mask)
 
 int mv_set_step_mask_host(mv_gym *g, const uint8_t *mask)
 {
-    if (attach_check(g, "mv_set_step_mask_host", "step mask")) return -1;
+    if (attach_check(g, "mv_set_step_mask_host", gym_options[OPT_STEP_MASK])) return -1;
     return mask ? set_host(g, g->stepMask, mask, "mv_set_step_mask_host") : set_device(g, g->stepMask, nullptr);
 }
 
@@ -78,7 +78,7 @@ int mv_get_step_mask(const mv_gym *g) { return getter_check(g, "mv_get_step_mask
 
 int mv_set_draw_mask(mv_gym *g, const uint8_t *device_mask)
 {
-    if (attach_check(g, "mv_set_draw_mask", "draw mask")) return -1;
+    if (attach_check(g, "mv_set_draw_mask", gym_options[OPT_DRAW_MASK])) return -1;
     // No launch, no copy: the frame setups read the caller's buffer.  This call is the ordering point, as mv_set_step_mask is: what the caller's stream holds
     // now -- the kernel that wrote the mask -- comes before the next step launch (the frame setups of mv_render and of the frame behind a reset run on the
     // caller's stream itself); the calls after that one pipeline freely.
@@ -87,7 +87,7 @@ int mv_set_draw_mask(mv_gym *g, const uint8_t *device_mask)
 
 int mv_set_draw_mask_host(mv_gym *g, const uint8_t *mask)
 {
-    if (attach_check(g, "mv_set_draw_mask_host", "draw mask")) return -1;
+    if (attach_check(g, "mv_set_draw_mask_host", gym_options[OPT_DRAW_MASK])) return -1;
     return mask ? set_host(g, g->drawMask, mask, "mv_set_draw_mask_host") : set_device(g, g->drawMask, nullptr);
 }
 

@@ -69,7 +69,7 @@ extern "C" {
 
 int mv_set_episode_budget(mv_gym *g, const int32_t *device_budget)
 {
-    if (attach_check(g, "mv_set_episode_budget", "episode budget")) return -1;
+    if (attach_check(g, "mv_set_episode_budget", gym_options[OPT_EPISODE_BUDGET])) return -1;
     if (!device_budget) return budget_detach(g);
     HIP_TRY(hipSetDevice(g->device));
     if (budget_alloc(g, "mv_set_episode_budget")) return -1;
@@ -86,7 +86,7 @@ int mv_set_episode_budget(mv_gym *g, const int32_t *device_budget)
 
 int mv_set_episode_budget_host(mv_gym *g, const int32_t *budget)
 {
-    if (attach_check(g, "mv_set_episode_budget_host", "episode budget")) return -1;
+    if (attach_check(g, "mv_set_episode_budget_host", gym_options[OPT_EPISODE_BUDGET])) return -1;
     if (!budget) return budget_detach(g);
     HIP_TRY(hipSetDevice(g->device));
     if (budget_alloc(g, "mv_set_episode_budget_host")) return -1;
@@ -114,7 +114,7 @@ void *mv_halted_count_device_ptr(mv_gym *g) { return g && !g->closed && g->budge
 
 int mv_halted_count(mv_gym *g, int32_t *out)
 {
-    if (attach_check(g, "mv_halted_count", "episode budget")) return -1;
+    if (attach_check(g, "mv_halted_count", gym_options[OPT_EPISODE_BUDGET])) return -1;
     if (!out) return fail("mv_halted_count: null output");
     if (!g->budgetOn) return fail("mv_halted_count: no episode budget attached (mv_set_episode_budget)");
     HIP_TRY(hipSetDevice(g->device));

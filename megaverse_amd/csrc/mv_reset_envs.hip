@@ -70,7 +70,7 @@ int reset_envs_launch(mv_gym *g, const uint8_t *device_mask, const uint8_t *host
     g->mirrorsFresh = false;
     // every frame of the gym: the unflagged envs' state did not change, so their frames come out as they were; of the state rows (mv_set_state_obs) and scene rows (mv_set_scene_obs) only the
     // flagged envs' are refreshed (device_mask: the caller's, or the half this call's copy went to -- read in stream order)
-    if (render && (render_frames(g) || state_obs_refresh(g, device_mask) || scene_obs_refresh(g, device_mask))) return -1;
+    if (render && (render_frames(g) || obs_rows_refresh(g, device_mask))) return -1;
     return finish_with_warning(g);
 }
 

@@ -1,5 +1,5 @@
 // megaverse_amd/csrc/mv_scene_obs.h -- scene observations (include/megaverse_hip.h: mv_set_scene_obs): the per-ENV record, stated once for the kernels that
-// write it (mv_step_kernels.h: scene_obs_write; mv_scene_obs.hip: the gather behind a reset or mv_render) and for the host hook the tests compare it with
+// write it (mv_step_kernels.h: scene_obs_write; mv_obs_rows.hip: the gather behind a reset or mv_render) and for the host hook the tests compare it with
 // (mv_debug_scene_obs_host).  One row of MV_SCENE_OBS_FLOATS = 32 float32 per env, [N][32], taken from the env's state AFTER the tick -- auto-reset included:
 // a tick that finished an episode shows the next episode's level, as its frame does.
 // Two conversions:  copied -- the 32 bits are moved (a -0.0f, a NaN's payload, a denormal survive);  int -- an int32 converted with (float): every value

@@ -1,5 +1,5 @@
 // megaverse_amd/csrc/mv_state_obs.h -- state observations (include/megaverse_hip.h: mv_set_state_obs): the record, stated once for the kernels that write
-// it (mv_step_kernels.h: state_obs_write; mv_state_obs.hip: the gather behind a reset or mv_render) and for the host hook the tests compare it with
+// it (mv_step_kernels.h: state_obs_write; mv_obs_rows.hip: the gather behind a reset or mv_render) and for the host hook the tests compare it with
 // (mv_debug_state_obs_host).  One row of MV_STATE_OBS_FLOATS = 16 float32 per agent, agent-major [N*A][16], taken from the env's state AFTER the tick --
 // auto-reset included: a tick that finished an episode shows the first state of the next one, as its frame does:
 //    0..2   pos[0..2]                 AgentState          8, 9   hvx, hvz                        AgentState

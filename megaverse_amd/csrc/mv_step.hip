@@ -41,7 +41,7 @@ const StepKernels tower_kernels_masked = {step_kernel_masked<1>, step_kernel_mas
                                    step_ticks_sim_kernel_masked<StepTicksArgs8, false>, step_ticks_sim_kernel_masked<StepTicksArgs8, true>,
                                    step_ticks_sim_agents_kernel_masked<StepTicksArgs8, false>, step_ticks_sim_agents_kernel_masked<StepTicksArgs8, true>};
 
-// masked: the view carries a step mask (mv_set_step_mask), an episode budget (mv_set_episode_budget) a draw mask (mv_set_draw_mask), staging rows for state observations (mv_set_state_obs) or scene observations (mv_set_scene_obs), a macro step's ticks left (mv_macro_step) or stale bytes (mv_set_still_frames) -- the MASKED instantiations; the gyms without one launch the kernels they always launched
+// masked: view_has_options (mv_types.h)
 static const StepKernels &kernels_of(int scenario, bool masked = false)
 {
     switch (scenario) {
@@ -78,7 +78,7 @@ static bool step_pipe_enabled(const GymView &gv)
 void launch_step_ticks(const GymView *views, int k, hipStream_t stream, int W, int H, hipEvent_t done)
 {
     const GymView &gv = views[0];
-    const StepKernels &K = kernels_of(gv.scenario, gv.step_mask != nullptr || gv.budget != nullptr || gv.draw_mask != nullptr || gv.state_obs != nullptr || gv.scene_obs != nullptr || gv.macro_tl != nullptr || gv.still != nullptr);
+    const StepKernels &K = kernels_of(gv.scenario, view_has_options(gv));
     StepTicksArgs8 a;   // (k <= 8: the views are the launch's arguments)
     a.n = k; a.pad = 0;
     for (int j = 0; j < 8; ++j) a.gv[j] = views[std::min(j, k - 1)];
@@ -95,7 +95,7 @@ void launch_step_ticks(const GymView *views, int k, hipStream_t stream, int W, i
 void launch_step_ticks_sim(const GymView *views, int k, unsigned frame_mask, hipStream_t stream, int W, int H, hipEvent_t done)
 {
     const GymView &gv = views[0];
-    const StepKernels &K = kernels_of(gv.scenario, gv.step_mask != nullptr || gv.budget != nullptr || gv.draw_mask != nullptr || gv.state_obs != nullptr || gv.scene_obs != nullptr || gv.macro_tl != nullptr || gv.still != nullptr);
+    const StepKernels &K = kernels_of(gv.scenario, view_has_options(gv));
     StepTicksArgs8 a;
     a.n = k; a.pad = (int32_t)(frame_mask & ((1u << k) - 1u));
     for (int j = 0; j < 8; ++j) a.gv[j] = views[std::min(j, k - 1)];
@@ -108,7 +108,7 @@ void launch_step_ticks_sim(const GymView *views, int k, unsigned frame_mask, hip
 // done: an event that completes with the launch, carried by its dispatch packet (cf. mv_raster.h) -- TowerBuilding's launch only; -> whether it rides
 bool launch_step(const GymView &gv, hipStream_t stream, int W, int H, int render, hipEvent_t done)
 {
-    const StepKernels &K = kernels_of(gv.scenario, gv.step_mask != nullptr || gv.budget != nullptr || gv.draw_mask != nullptr || gv.state_obs != nullptr || gv.scene_obs != nullptr || gv.macro_tl != nullptr || gv.still != nullptr);
+    const StepKernels &K = kernels_of(gv.scenario, view_has_options(gv));
     if (gv.scenario != SCN_TOWER) done = nullptr;
     const dim3 grid(gv.num_envs), block(gv.num_agents == 1 ? STEP_THREADS : 64 * std::min(gv.num_agents, 4));
     hipExtLaunchKernelGGL(gv.num_agents == 1 ? K.step : K.step_agents, grid, block, 0, stream, nullptr, done, 0, gv, W, H, render);

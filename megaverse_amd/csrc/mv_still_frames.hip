@@ -132,7 +132,7 @@ extern "C" {
 
 int mv_set_still_frames(mv_gym *g, int32_t on)
 {
-    if (attach_check(g, "mv_set_still_frames", "stale bytes")) return -1;
+    if (attach_check(g, "mv_set_still_frames", gym_options[OPT_STILL_FRAMES])) return -1;
     if (!on) {
         // The step launches enqueued so far keep the views they were given; the next one is drawn whole again.  The arrays stay until mv_close.
         g->stillOn = false;

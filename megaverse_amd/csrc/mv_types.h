@@ -212,11 +212,11 @@ struct GymView {
     const uint8_t *draw_mask;
     // mv_set_state_obs: [N*A][16] float32, this tick's staging rows of the state observations (mv_state_obs.h has the record): behind the tick the MASKED step
     // bodies store every agent's row here (mv_step_kernels.h: state_obs_write), and one launch per stepping call carries the rows to the caller's buffer
-    // (mv_state_obs.hip).  null: off.  A field of the per-slot views (mv_gym::gvp), so tick_view leaves it alone; the union launches never see a non-null one.
+    // (mv_obs_rows.hip).  null: off.  A field of the per-slot views (mv_gym::gvp), so tick_view leaves it alone; the union launches never see a non-null one.
     float *state_obs;
     // mv_set_scene_obs: [N][32] float32, this tick's staging rows of the scene observations (mv_scene_obs.h has the record), the per-ENV counterpart of
     // state_obs: behind the tick the MASKED step bodies store the env's row here (mv_step_kernels.h: scene_obs_write), and the stepping call's one publication
-    // launch carries the rows to the caller's buffer (mv_scene_obs.hip).  null: off.  A field of the per-slot views (mv_gym::gvp), like state_obs.
+    // launch carries the rows to the caller's buffer (mv_obs_rows.hip).  null: off.  A field of the per-slot views (mv_gym::gvp), like state_obs.
     float *scene_obs;
     // mv_macro_step: [N] ticks each env may still step in this call (0: its macro step is over -- its ticks are frozen ticks), written by the MASKED step
     // bodies behind every tick the env stepped in (mv_step_kernels.h: after_tick; mv_macro_step.h has the rule); null: no macro step in flight.  Set by the
@@ -227,6 +227,12 @@ struct GymView {
     // FRAME_STILL.  null: off, every env is drawn on every pass.  Set by the stepping calls only (mv_api_step.hip); the union launches never see a non-null one.
     uint8_t *still;
 };
+// The view carries a per-gym option -- a step mask, an episode budget, a draw mask, staging rows of state or scene observations, a macro step's ticks left,
+// stale bytes: its launches take the MASKED instantiations of the step bodies; the gyms without one launch the kernels they always launched (mv_step.hip).
+__host__ inline bool view_has_options(const GymView &gv)
+{
+    return gv.step_mask || gv.budget || gv.draw_mask || gv.state_obs || gv.scene_obs || gv.macro_tl || gv.still;
+}
 
 // The n <= 8 consecutive ticks of a multi-tick step launch (mv_step.hip: step_ticks_kernel, and every mv_step_*.hip), the same envs in all of them: their views
 // BY VALUE as the launch's arguments -- 2.6 KB of the 4 KB kernel-argument segment; the kernels read a tick's view with scalar loads on demand, its fields do

@@ -532,29 +532,25 @@ def check_draw_mask(mask, num_envs):
 def check_state_obs(buf, entries, num_rows, device):
     """the argument check of MegaverseGym.set_state_obs for a tensor: contiguous torch.float32 of shape (entries, num_rows, 16) on CUDA device `device`;
     entries None: any number of entries (the check made before the gym is asked for its ring count)"""
-    got = tuple(getattr(buf, 'shape', ()))
-    shape = ((got[0] if len(got) == 3 else 1) if entries is None else int(entries), int(num_rows), MV_STATE_OBS_FLOATS)
-    contiguous = getattr(buf, 'is_contiguous', None)
-    dev = getattr(buf, 'device', None)
-    index = getattr(dev, 'index', None)
-    if not hasattr(buf, 'data_ptr') or got != shape or str(getattr(buf, 'dtype', None)) != 'torch.float32' \
-            or not getattr(buf, 'is_cuda', False) or not (callable(contiguous) and contiguous()) or (index is not None and int(index) != int(device)):
-        raise ValueError(f'set_state_obs: the buffer must be a contiguous float32 CUDA tensor of shape {shape} on device {int(device)}, '
-                         f"got {getattr(buf, 'dtype', type(buf).__name__)} {tuple(getattr(buf, 'shape', ()))} on {dev if dev is not None else 'no device'}")
-    return buf
+    return _check_obs_rows(buf, entries, num_rows, MV_STATE_OBS_FLOATS, device, 'set_state_obs')
 
 
 def check_scene_obs(buf, entries, num_envs, device):
     """the argument check of MegaverseGym.set_scene_obs for a tensor: contiguous torch.float32 of shape (entries, num_envs, 32) on CUDA device `device`;
     entries None: any number of entries (the check made before the gym is asked for its ring count)"""
+    return _check_obs_rows(buf, entries, num_envs, MV_SCENE_OBS_FLOATS, device, 'set_scene_obs')
+
+
+def _check_obs_rows(buf, entries, num_rows, floats, device, who):
+    """check_state_obs / check_scene_obs: a row record's tensor, (entries, num_rows, floats), for the setter `who`"""
     got = tuple(getattr(buf, 'shape', ()))
-    shape = ((got[0] if len(got) == 3 else 1) if entries is None else int(entries), int(num_envs), MV_SCENE_OBS_FLOATS)
+    shape = ((got[0] if len(got) == 3 else 1) if entries is None else int(entries), int(num_rows), floats)
     contiguous = getattr(buf, 'is_contiguous', None)
     dev = getattr(buf, 'device', None)
     index = getattr(dev, 'index', None)
     if not hasattr(buf, 'data_ptr') or got != shape or str(getattr(buf, 'dtype', None)) != 'torch.float32' \
             or not getattr(buf, 'is_cuda', False) or not (callable(contiguous) and contiguous()) or (index is not None and int(index) != int(device)):
-        raise ValueError(f'set_scene_obs: the buffer must be a contiguous float32 CUDA tensor of shape {shape} on device {int(device)}, '
+        raise ValueError(f'{who}: the buffer must be a contiguous float32 CUDA tensor of shape {shape} on device {int(device)}, '
                          f"got {getattr(buf, 'dtype', type(buf).__name__)} {tuple(getattr(buf, 'shape', ()))} on {dev if dev is not None else 'no device'}")
     return buf
 
@@ -1087,21 +1083,23 @@ class MegaverseGym:
         entry the tick's rewards go to.  True allocates the tensor on the gym's device and returns it; a tensor is checked (ValueError) and attached; None
         detaches.  Nothing waits on the host; the rows are visible on the gym's stream when the call's rewards are.  While attached, set_output_ring is
         refused."""
+        self._state_obs = self._set_obs_rows(buf, 'mv_set_state_obs', check_state_obs, self.num_envs * self.num_agents_per_env, MV_STATE_OBS_FLOATS)
+        return self._state_obs
+
+    def _set_obs_rows(self, buf, setter, checker, rows, floats):
+        """set_state_obs / set_scene_obs: attach (True: allocate) or detach (None) one row record's tensor [entries, rows, floats] -> the tensor, or None"""
         if buf is None:
-            self._ck(self._lib.mv_set_state_obs(self._g, None))
-            self._state_obs = None
+            self._ck(getattr(self._lib, setter)(self._g, None))
             return None
-        rows = self.num_envs * self.num_agents_per_env
         if buf is not True:
-            check_state_obs(buf, None, rows, self.device)   # (what needs no gym first: the library stays untouched by a tensor that is wrong anyway)
+            checker(buf, None, rows, self.device)   # (what needs no gym first: the library stays untouched by a tensor that is wrong anyway)
         entries = max(1, self._ck(self._lib.mv_get_output_ring(self._g)))   # (the library's own count: the depth it will write)
         if buf is True:
             import torch
-            buf = torch.zeros((entries, rows, MV_STATE_OBS_FLOATS), dtype=torch.float32, device=f'cuda:{self.device}')
+            buf = torch.zeros((entries, rows, floats), dtype=torch.float32, device=f'cuda:{self.device}')
         else:
-            check_state_obs(buf, entries, rows, self.device)
-        self._ck(self._lib.mv_set_state_obs(self._g, _P(int(buf.data_ptr()))))
-        self._state_obs = buf
+            checker(buf, entries, rows, self.device)
+        self._ck(getattr(self._lib, setter)(self._g, _P(int(buf.data_ptr()))))
         return buf
 
     def state_obs(self):
@@ -1114,21 +1112,8 @@ class MegaverseGym:
         building zone, the exit pad and the diamonds left, the hex target, the ball; the state AFTER the tick) in entry t % entries of a float32 CUDA tensor
         [entries, num_envs, 32], entries = the output ring's count, or 1 without a ring.  True allocates the tensor on the gym's device and returns it; a
         tensor is checked (ValueError) and attached; None detaches.  Nothing waits on the host.  While attached, set_output_ring is refused."""
-        if buf is None:
-            self._ck(self._lib.mv_set_scene_obs(self._g, None))
-            self._scene_obs = None
-            return None
-        if buf is not True:
-            check_scene_obs(buf, None, self.num_envs, self.device)   # (what needs no gym first)
-        entries = max(1, self._ck(self._lib.mv_get_output_ring(self._g)))
-        if buf is True:
-            import torch
-            buf = torch.zeros((entries, self.num_envs, MV_SCENE_OBS_FLOATS), dtype=torch.float32, device=f'cuda:{self.device}')
-        else:
-            check_scene_obs(buf, entries, self.num_envs, self.device)
-        self._ck(self._lib.mv_set_scene_obs(self._g, _P(int(buf.data_ptr()))))
-        self._scene_obs = buf
-        return buf
+        self._scene_obs = self._set_obs_rows(buf, 'mv_set_scene_obs', check_scene_obs, self.num_envs, MV_SCENE_OBS_FLOATS)
+        return self._scene_obs
 
     def scene_obs_ring(self):
         """-> the tensor set_scene_obs attached, [entries, num_envs, 32] (entry t % entries: what tick t left), or None"""

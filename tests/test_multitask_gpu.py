@@ -151,3 +151,77 @@ def test_a_grouped_gym_is_stepped_through_its_group_only(hip, monkeypatch):
     g1.sample_random_actions(3, 4); g1.step()
     assert g1.get_dones().shape == (4,)
     grp.close(); g1.close(); g3.close()
+
+
+# The six persistent per-gym options in the order every refusal walks them: how the option is switched on (its setter's device form), then three whole texts --
+# the setter called on a group member, mv_group_create with the option on, mv_step_many with the option on gym 1 -- each as the library's source spelled it
+# out before the texts were built from one table.  (GymGroup puts "mv_group_create: " in front of the library's text.)
+OPTION_REFUSALS = [
+    ("step mask", lambda g, t: g.set_step_mask(t.ones(2, dtype=t.bool, device="cuda")),
+     "mv_set_step_mask: this gym belongs to an mv_group, whose union launches read no step mask",
+     "mv_group_create: mv_group_create: a gym has a step mask attached (mv_set_step_mask): the union launches read none; detach it first",
+     "mv_step_many: gym 1 has a step mask attached (mv_set_step_mask): step it on its own, or detach the mask first"),
+    ("draw mask", lambda g, t: g.set_draw_mask(t.ones(2, dtype=t.bool, device="cuda")),
+     "mv_set_draw_mask: this gym belongs to an mv_group, whose union launches read no draw mask",
+     "mv_group_create: mv_group_create: a gym has a draw mask attached (mv_set_draw_mask): the union launches read none; detach it first",
+     "mv_step_many: gym 1 has a draw mask attached (mv_set_draw_mask): step it on its own, or detach the mask first"),
+    ("still frames", lambda g, t: g.set_still_frames(True),
+     "mv_set_still_frames: this gym belongs to an mv_group, whose union launches read no stale bytes",
+     "mv_group_create: mv_group_create: a gym has still frames switched on (mv_set_still_frames): the union launches read no stale bytes; switch them off first",
+     "mv_step_many: gym 1 has still frames switched on (mv_set_still_frames): step it on its own, or switch them off first"),
+    ("episode budget", lambda g, t: g.set_episode_budget(t.ones(2, dtype=t.int32, device="cuda")),
+     "mv_set_episode_budget: this gym belongs to an mv_group, whose union launches read no episode budget",
+     "mv_group_create: mv_group_create: a gym has an episode budget attached (mv_set_episode_budget): the union launches read none; detach it first",
+     "mv_step_many: gym 1 has an episode budget attached (mv_set_episode_budget): step it on its own, or detach the budget first"),
+    ("state observations", lambda g, t: g.set_state_obs(True),
+     "mv_set_state_obs: this gym belongs to an mv_group, whose union launches write no state observations",
+     "mv_group_create: mv_group_create: a gym has state observations attached (mv_set_state_obs): the union launches write none; detach them first",
+     "mv_step_many: gym 1 has state observations attached (mv_set_state_obs): step it on its own, or detach them first"),
+    ("scene observations", lambda g, t: g.set_scene_obs(True),
+     "mv_set_scene_obs: this gym belongs to an mv_group, whose union launches write no scene observations",
+     "mv_group_create: mv_group_create: a gym has scene observations attached (mv_set_scene_obs): the union launches write none; detach them first",
+     "mv_step_many: gym 1 has scene observations attached (mv_set_scene_obs): step it on its own, or detach them first"),
+]
+
+
+def test_option_refusal_texts(hip):
+    """Every persistent option is refused in the same three places, each with a text of its own: whole texts, per option, and with two options on the one
+    that comes first in the table -- mv_step_many walks option by option (gym 1's draw mask before gym 0's scene observations), mv_group_create gym by gym."""
+    import ctypes as C
+    import torch
+    from megaverse_amd.extension import GymGroup, MegaverseGym
+    gyms = [MegaverseGym("TowerBuilding", 32, 32, 2, 1, 1, False, {}) for _ in range(3)]
+    for g in gyms:
+        g.seed(1); g.reset()
+    lib, (member, plain, opt) = gyms[0]._lib, gyms
+    grp = GymGroup([member])
+    handles = (C.c_void_p * 2)(plain._g, opt._g)
+
+    def refusal(call):
+        with pytest.raises(RuntimeError) as e:
+            call()
+        return str(e.value)
+
+    def step_many():
+        if lib.mv_step_many(handles, 2, 1, 0, 0, 0) < 0:
+            raise RuntimeError(lib.mv_last_error().decode())
+
+    for name, switch_on, on_member, on_create, on_many in OPTION_REFUSALS:
+        assert refusal(lambda: switch_on(member, torch)) == on_member, name
+        switch_on(opt, torch)
+        assert refusal(lambda: GymGroup([plain, opt])) == on_create, name
+        assert refusal(step_many) == on_many, name
+        opt.set_step_mask(None); opt.set_draw_mask(None); opt.set_still_frames(False); opt.set_episode_budget(None)
+        opt.set_state_obs(None); opt.set_scene_obs(None)
+    # two options on: the table's order
+    opt.set_scene_obs(True); opt.set_draw_mask(torch.ones(2, dtype=torch.bool, device="cuda"))
+    assert refusal(lambda: GymGroup([plain, opt])) == OPTION_REFUSALS[1][3]
+    assert refusal(step_many) == OPTION_REFUSALS[1][4]
+    plain.set_scene_obs(True)   # (gym 0 has the later option, gym 1 the earlier one)
+    assert refusal(step_many) == OPTION_REFUSALS[1][4]
+    assert refusal(lambda: GymGroup([plain, opt])) == OPTION_REFUSALS[5][3]
+    plain.set_scene_obs(None); opt.set_scene_obs(None); opt.set_draw_mask(None)
+    step_many()   # (nothing attached any more: the call goes through)
+    grp.close()
+    for g in gyms:
+        g.close()

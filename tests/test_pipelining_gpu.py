@@ -526,3 +526,31 @@ def test_overlapped_passes_with_a_late_consumer(hip, k, R, rings):
     for e in range(N):
         assert a.debug_snapshot_bytes(e).tobytes() == b.debug_snapshot_bytes(e).tobytes(), e
     a.close(); b.close()
+
+
+@pytest.mark.parametrize("ring", [8, 0])
+def test_timed_calls_take_the_launches_they_time(hip, ring):
+    """mv_profile_begin and the launch rule: a batched call that takes both one-launch paths (a ring at least k deep) is timed as a whole -- still ONE step
+    launch and ONE observation launch, one entry that covers its k ticks; any other call is timed tick by tick -- k step launches and k passes while entries
+    are left, and again the call's usual launches once they have run out."""
+    import torch
+    N, S, k = 7, 32, 4
+    g = MegaverseGym("TowerBuilding", S, S, N, 1, 1, False, {})
+    g.set_pixel_mode("fast"); g.seed(3); g.reset()
+    if ring:
+        obs = torch.zeros((ring, N, S, S, 4), dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+        g.set_output_ring(ring, obs.data_ptr())
+
+    def launches(st):
+        before = g.debug_launch_counts()
+        g.step_n(k, "multidiscrete", 5, st)
+        after = g.debug_launch_counts()
+        return after[0] - before[0], after[1] - before[1]
+
+    g.profile_begin(3)
+    assert launches(0) == ((1, 1) if ring else (k, k))
+    timed = g.profile_end()
+    assert timed["step"][1] == (k if ring else 3) and timed["raster"][1] == timed["step"][1]   # (ticks covered: one entry of k ticks, or the three entries)
+    assert launches(k) == ((1, 1) if ring else (1, k))   # (untimed: the resident step launch; without a ring one pass per tick)
+    g.close()
