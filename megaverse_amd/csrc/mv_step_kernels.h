@@ -224,6 +224,18 @@ __device__ __forceinline__ bool obs_rows_on(const GymView &gv) { return gv.state
 //               tick PER ROUND: measured 41 us vs 25 us);
 //   A agents:   64 min(A, 4) threads, every wave sets up its own frame(s): a frame setup is a chain of dependent loads (~6 us), A of them
 //               one after the other would cost more than the launch the fusion saves.
+// step_body's frame setup, on its frozen path and on its stepping one: STEP_THREADS threads on the env's one frame, or up to four waves over its A frames
+template <class S, int A_MAX>
+__device__ __forceinline__ void step_frames_setup(const GymView &gv, int env, int W, int H, FrameScratch *s_fs)
+{
+    constexpr int NS = A_MAX == 1 ? 1 : 4;
+    if constexpr (A_MAX == 1) frame_setup_body<STEP_THREADS, false>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
+    else {
+        const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+        for (int a = wave; a < A; a += nw) frame_setup_body<64, true>(gv, env * A + a, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
+    }
+}
+
 template <class S, int A_MAX, bool MASKED = false>
 __device__ __forceinline__ void step_body(const GymView &gv, const int env, int W, int H, int render)
 {
@@ -243,11 +255,7 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
         if (!env_drawn(gv, env)) { env_frames_skip<A_MAX == 1, STEP_THREADS, false>(gv, env); return; }   // (mv_set_draw_mask; uniform)
         if (stale == 0) { env_frames_skip<A_MAX == 1, STEP_THREADS, false>(gv, env, still::FRAME_STILL); return; }   // (mv_set_still_frames; uniform)
         if (stale > 0 && threadIdx.x == 0) still_store(gv.still + env, 0);
-        if constexpr (A_MAX == 1) frame_setup_body<STEP_THREADS, false>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
-        else {
-            const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
-            for (int a = wave; a < A; a += nw) frame_setup_body<64, true>(gv, env * A + a, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
-        }
+        step_frames_setup<S, A_MAX>(gv, env, W, H, s_fs);
         return;
     }
     MV_T_BEGIN
@@ -292,8 +300,8 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
         return;
     }
     if constexpr (MASKED) if (gv.still != nullptr && threadIdx.x == 0) still_store(gv.still + env, 0);
+    step_frames_setup<S, A_MAX>(gv, env, W, H, s_fs);
     if constexpr (A_MAX == 1) {
-        frame_setup_body<STEP_THREADS, false>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
         MV_T(7);   // frame setup
 #ifdef MV_TICK_TIMING
         if (gv.dbg && threadIdx.x == 0) {
@@ -302,11 +310,79 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
             if (!d[49]) { d[52] += rt1 - rt0; d[53] += 1; d[54] = rt0; d[55] = rt1; }
         }
 #endif
-    } else {
-        const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
-        for (int a = wave; a < A; a += nw) frame_setup_body<64, true>(gv, env * A + a, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
     }
 }
+
+// ---- the resident multi-tick bodies' per-env option state: the uniform values above (env_left, env_tl, env_drawn, env_stale), loaded once per launch through
+// its first view, carried through its ticks -- every wave of the workgroup its own copy, the same behind the same barriers -- and stored where they changed:
+// left and tl by after_tick behind the tick that changed them, stale at the launch's end (env_options_store).  An instantiation that does not use a member
+// leaves nothing of it behind: neither the load nor the register (the kernels without frame setup never ask for drawn).
+struct EnvOptions {
+    int32_t left = -1, tl = -1;    // (mv_set_step_mask, mv_set_episode_budget: env_left; mv_macro_step: env_tl)
+    bool drawn = true;             // (mv_set_draw_mask: env_drawn)
+    int stale = -1, stale0 = -1;   // (mv_set_still_frames: env_stale; stale0: what the launch found)
+};
+template <bool MASKED>
+__device__ __forceinline__ EnvOptions env_options_load(const GymView &gv, int env)
+{
+    EnvOptions o;
+    if constexpr (MASKED) { o.left = env_left(gv, env); o.tl = env_tl(gv, env); o.drawn = env_drawn(gv, env); o.stale = o.stale0 = env_stale(gv, env); }
+    return o;
+}
+// in front of a tick: whether env steps in it (uniform; without MASKED: a constant), and stale behind that choice
+template <bool MASKED>
+__device__ __forceinline__ bool env_options_tick(EnvOptions &o)
+{
+    const bool steps = !MASKED || env_steps(o.left, o.tl);
+    if constexpr (MASKED) o.stale = still::still_after_tick(o.stale, steps);
+    return steps;
+}
+// (every wave read the byte in front of the loop's first barrier)
+template <bool MASKED>
+__device__ __forceinline__ void env_options_store(const GymView &gv, int env, const EnvOptions &o)
+{
+    if constexpr (MASKED) if (o.stale != o.stale0 && threadIdx.x == 0) still_store(gv.still + env, o.stale);
+}
+
+// ---- where the agent count enters a resident body: the tick's template arguments (in the body itself: a tick that is inlined through one more function comes
+// out of hipcc with its instructions in another order, and a few unmasked kernels with another s_waitcnt count), and the helpers below.
+// The barrier behind a tick: the tick's stores before the frame setup's / the next tick's loads.  One wave: no barrier needed; several: the workgroup's (same
+// CU: same L1)
+template <int A_MAX>
+__device__ __forceinline__ void tick_barrier()
+{
+    if constexpr (A_MAX == 1) wave_sync();
+    else __syncthreads();
+}
+// FrameScratch (N per workgroup), declared only in the instantiations that can set a frame up: LDS held by resident step waves is what the passes lose
+template <int N>
+__device__ __forceinline__ FrameScratch &frame_scratch(int i)
+{
+    __shared__ FrameScratch s_fs[N];
+    return s_fs[i];
+}
+// The env's frames of one tick: the one wave on the env's one frame, or every wave on its share of the env's A frames; an env the draw mask leaves out or whose
+// state did not change takes env_frames_skip instead (uniform), and a drawn setup clears stale
+template <class S, int A_MAX, bool MASKED>
+__device__ __forceinline__ void env_frames(const GymView &gv, int env, int W, int H, EnvOptions &o)
+{
+    constexpr int NS = A_MAX == 1 ? 1 : 4;
+    if (!MASKED || (o.drawn && o.stale != 0)) {
+        if constexpr (A_MAX == 1) frame_setup_body<64, true>(gv, env, W, H, frame_scratch<NS>(0), depth_sort_scratch<S, NS>(0));
+        else {
+            const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+            for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, frame_scratch<NS>(wave), depth_sort_scratch<S, NS>(wave));
+        }
+        if constexpr (MASKED) o.stale = still::still_after_frames(o.stale, still::VERDICT_DRAWN);
+    } else env_frames_skip<A_MAX == 1, 64, true>(gv, env, skip_marker(o.drawn));
+}
+
+// which ticks of a resident launch set their frames up
+enum : int {
+    FRAMES_NONE,      // none (the launch's mask is zero: a call that draws nothing, or a chunk in front of the drawn tick's)
+    FRAMES_BY_MASK,   // tick j where bit j of the launch's mask (StepTicksArgs8::pad: a kernel argument, uniform) is set: the last chunk of an MV_RENDER_LAST call
+    FRAMES_ALL        // every tick (mv_step_n with MV_RENDER_EVERY)
+};
 
 // k consecutive ticks of every env with ONE launch (a batched open-loop call, mv_step_n with a device-side random policy): the envs are
 // independent and every tick draws its own actions, so nothing orders env A's tick j + 1 behind env B's tick j -- only k launches did, each as
@@ -322,136 +398,38 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
 // workgroups stay resident for the whole call beside the observation passes of the previous one, and every wave of ~150 VGPRs they hold is
 // two or three waves the pass cannot have (measured: 21.1 M obs/s with two waves per env, 22.3 M with one).
 // Several agents (S::par_agents): every wave of the workgroup ticks, then sets up its share of the env's frames.
-template <class S, int A_MAX, bool MASKED = false, class Args>
+// FRAMES (mv_step_n_render: MV_RENDER_NONE / MV_RENDER_LAST simulate ticks that set no frame up): FRAMES_NONE declares neither FrameScratch nor the depth
+// sort's LDS, since LDS and registers held by resident step waves are what the passes beside them lose; with several agents the barrier behind the frame setups
+// guards nothing and is gone, the one behind the tick stays (tick j + 1 reads what the other waves' tick j wrote).  An env that is frozen or halted when such a
+// launch starts leaves behind the loads of env_left and n tiny stores.
+template <class S, int A_MAX, class Args, int FRAMES, bool MASKED = false>
 __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
 {
-    constexpr int NS = A_MAX == 1 ? 1 : 4;
-    __shared__ FrameScratch s_fs[NS];
     const int env = blockIdx.x;
 #ifdef MV_STEP_PRIO
     __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
 #endif
-    [[maybe_unused]] int32_t left = -1, tl = -1;   // (mv_set_step_mask, mv_set_episode_budget: env_left; mv_macro_step: env_tl)
-    if constexpr (MASKED) { left = env_left(a.view(0), env); tl = env_tl(a.view(0), env); }
-    [[maybe_unused]] bool drawn = true;   // (mv_set_draw_mask: env_drawn)
-    if constexpr (MASKED) drawn = env_drawn(a.view(0), env);
-    [[maybe_unused]] int stale = -1, stale0 = -1;   // (mv_set_still_frames: env_stale)
-    if constexpr (MASKED) stale = stale0 = env_stale(a.view(0), env);
+    EnvOptions o = env_options_load<MASKED>(a.view(0), env);
+    [[maybe_unused]] const uint32_t mask = FRAMES == FRAMES_ALL ? ~0u : (uint32_t)a.pad;
     for (int j = 0; j < a.n; ++j) {
         const GymView &gv = a.view(j);
-        const bool steps = !MASKED || env_steps(left, tl);   // (uniform; without MASKED: a constant)
-        if constexpr (MASKED) stale = still::still_after_tick(stale, steps);
-        if constexpr (A_MAX == 1) {
-            if (steps) S::template tick<1>(gv, env);
-            else frozen_tick(gv, env);
-            wave_sync();   // the tick's stores before the frame setup's loads (one wave: no barrier needed)
-            if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
-            if constexpr (MASKED) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); }   // (mv_set_state_obs, mv_set_scene_obs)
-            if (!MASKED || (drawn && stale != 0)) {
-                frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
-                if constexpr (MASKED) stale = still::still_after_frames(stale, still::VERDICT_DRAWN);
-            } else env_frames_skip<true, 64, true>(gv, env, skip_marker(drawn));
-        } else {
-            if (steps) S::template tick<A_MAX, true>(gv, env);
-            else frozen_tick(gv, env);
-            __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
-            if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
-            if constexpr (MASKED) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); }   // (mv_set_state_obs, mv_set_scene_obs)
-            if (!MASKED || (drawn && stale != 0)) {
-                const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
-                for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
-                if constexpr (MASKED) stale = still::still_after_frames(stale, still::VERDICT_DRAWN);
-            } else env_frames_skip<false, 64, true>(gv, env, skip_marker(drawn));
-            __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
+        const bool frames = FRAMES != FRAMES_NONE && ((mask >> j) & 1u);   // (uniform; FRAMES_NONE, FRAMES_ALL: a constant)
+        const bool steps = env_options_tick<MASKED>(o);
+        if (!steps) frozen_tick(gv, env);
+        else if constexpr (A_MAX == 1) S::template tick<1>(gv, env);
+        else S::template tick<A_MAX, true>(gv, env);   // (S::par_agents: every wave of the workgroup ticks)
+        tick_barrier<A_MAX>();
+        if constexpr (MASKED) if (steps) after_tick(gv, env, o.left, o.tl);
+        // (mv_set_state_obs, mv_set_scene_obs) the ticks of a launch without any frame setup reach their rows only where the view carries some (uniform)
+        if constexpr (MASKED) if (FRAMES != FRAMES_NONE || obs_rows_on(gv)) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); }
+        if (frames) {
+            env_frames<S, A_MAX, MASKED>(gv, env, W, H, o);
+            if constexpr (A_MAX > 1) __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
+        } else if constexpr (MASKED && A_MAX > 1) {
+            if (obs_rows_on(gv)) __syncthreads();   // (uniform) the rows' loads before the other waves' next tick changes the state
         }
     }
-    // (every wave read the byte in front of the loop's first barrier)
-    if constexpr (MASKED) if (stale != stale0 && threadIdx.x == 0) still_store(a.view(0).still + env, stale);
-}
-
-// The resident multi-tick step for ticks that set no frame up (mv_step_n_render, MV_RENDER_NONE / MV_RENDER_LAST): as step_ticks_body -- one workgroup per env,
-// resident for the launch's <= 8 ticks, one wave per env for one agent, every wave ticking for S::par_agents -- but tick j's frame setup runs only where bit j
-// of the launch's mask (StepTicksArgs8::pad: a kernel argument, uniform) is set.  FRAMES = false (the mask is zero: a call that draws nothing, or a chunk in
-// front of the drawn tick's): no frame setup at all -- neither FrameScratch nor the depth sort's LDS is declared, since LDS and registers held by resident step
-// waves are what the passes beside them lose; with several agents the barrier behind the frame setups guards nothing and is gone, the one behind the tick stays
-// (tick j + 1 reads what the other waves' tick j wrote).  FRAMES = true: the last chunk of an MV_RENDER_LAST call, bit n - 1 set.
-template <class S, int A_MAX, class Args, bool FRAMES, bool MASKED = false>
-__device__ __forceinline__ void step_ticks_sim_body(const Args &a, int W, int H)
-{
-    const int env = blockIdx.x;
-#ifdef MV_STEP_PRIO
-    __builtin_amdgcn_s_setprio(MV_STEP_PRIO);
-#endif
-    // (mv_set_step_mask, mv_set_episode_budget: env_left.  An env that is frozen or halted when a FRAMES = false launch starts leaves behind the loads of
-    // env_left and n tiny stores)
-    [[maybe_unused]] int32_t left = -1, tl = -1;   // (mv_macro_step: env_tl)
-    if constexpr (MASKED) { left = env_left(a.view(0), env); tl = env_tl(a.view(0), env); }
-    [[maybe_unused]] int stale = -1, stale0 = -1;   // (mv_set_still_frames: env_stale; FRAMES = false only ever sets it)
-    if constexpr (MASKED) stale = stale0 = env_stale(a.view(0), env);
-    if constexpr (!FRAMES) {
-        for (int j = 0; j < a.n; ++j) {
-            const GymView &gv = a.view(j);
-            const bool steps = !MASKED || env_steps(left, tl);   // (uniform; without MASKED: a constant)
-            if constexpr (MASKED) stale = still::still_after_tick(stale, steps);
-            if constexpr (A_MAX == 1) {
-                if (steps) S::template tick<1>(gv, env);
-                else frozen_tick(gv, env);
-                wave_sync();       // the tick's stores before the next tick's loads (one wave: no barrier needed)
-            } else {
-                if (steps) S::template tick<A_MAX, true>(gv, env);
-                else frozen_tick(gv, env);
-                __syncthreads();   // the tick's stores (same CU: same L1) before the next tick's loads
-            }
-            if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
-            if constexpr (MASKED) if (obs_rows_on(gv)) {   // (mv_set_state_obs, mv_set_scene_obs; uniform)
-                state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env);
-                if constexpr (A_MAX > 1) __syncthreads();   // the rows' loads before the other waves' next tick changes the state
-            }
-        }
-    } else {
-        constexpr int NS = A_MAX == 1 ? 1 : 4;
-        __shared__ FrameScratch s_fs[NS];
-        const uint32_t mask = (uint32_t)a.pad;
-        [[maybe_unused]] bool drawn = true;   // (mv_set_draw_mask: env_drawn)
-        if constexpr (MASKED) drawn = env_drawn(a.view(0), env);
-        for (int j = 0; j < a.n; ++j) {
-            const GymView &gv = a.view(j);
-            const bool frames = (mask >> j) & 1u;
-            const bool steps = !MASKED || env_steps(left, tl);   // (uniform; without MASKED: a constant)
-            if constexpr (MASKED) stale = still::still_after_tick(stale, steps);
-            if constexpr (A_MAX == 1) {
-                if (steps) S::template tick<1>(gv, env);
-                else frozen_tick(gv, env);
-                wave_sync();   // the tick's stores before the frame setup's / the next tick's loads
-                if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
-                if constexpr (MASKED) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); }   // (mv_set_state_obs, mv_set_scene_obs)
-                if (frames) {
-                    if (!MASKED || (drawn && stale != 0)) {
-                        frame_setup_body<64, true>(gv, env, W, H, s_fs[0], depth_sort_scratch<S, NS>(0));
-                        if constexpr (MASKED) stale = still::still_after_frames(stale, still::VERDICT_DRAWN);
-                    } else env_frames_skip<true, 64, true>(gv, env, skip_marker(drawn));
-                }
-            } else {
-                if (steps) S::template tick<A_MAX, true>(gv, env);
-                else frozen_tick(gv, env);
-                __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's / the next tick's loads
-                if constexpr (MASKED) if (steps) after_tick(gv, env, left, tl);
-                if constexpr (MASKED) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); }   // (mv_set_state_obs, mv_set_scene_obs)
-                if (frames) {
-                    if (!MASKED || (drawn && stale != 0)) {
-                        const int A = gv.num_agents, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
-                        for (int q = wave; q < A; q += nw) frame_setup_body<64, true>(gv, env * A + q, W, H, s_fs[wave], depth_sort_scratch<S, NS>(wave));
-                        if constexpr (MASKED) stale = still::still_after_frames(stale, still::VERDICT_DRAWN);
-                    } else env_frames_skip<false, 64, true>(gv, env, skip_marker(drawn));
-                    __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
-                } else if constexpr (MASKED) {
-                    if (obs_rows_on(gv)) __syncthreads();   // (mv_set_state_obs, mv_set_scene_obs; uniform) the rows' loads before the other waves' next tick changes the state
-                }
-            }
-        }
-    }
-    // (every wave read the byte in front of the loops' first barrier)
-    if constexpr (MASKED) if (stale != stale0 && threadIdx.x == 0) still_store(a.view(0).still + env, stale);
+    env_options_store<MASKED>(a.view(0), env, o);
 }
 
 // Software-pipelined (one agent per env): TWO waves per env.  Wave 0 runs tick j + 1 while wave 1 sets tick j's frame up (mv_frame.h) -- the two halves of a
@@ -471,13 +449,13 @@ __device__ __forceinline__ void step_ticks_pipe_body(const Args &a, int W, int H
 #endif
     if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0) {
         // (mv_set_step_mask, mv_set_episode_budget: env_left) a tick that does not step is the frozen tick at the barriers of a stepping one -- both barriers
-        // of the iteration on either side of the choice; wave 1 sets the frames up as always, and only this wave needs to know what is left
-        [[maybe_unused]] int32_t left = -1, tl = -1;   // (mv_macro_step: env_tl)
-        if constexpr (MASKED) { left = env_left(a.view(0), env); tl = env_tl(a.view(0), env); }
+        // of the iteration on either side of the choice; wave 1 sets the frames up as always, and only this wave needs to know what is left (mv_macro_step:
+        // env_tl, likewise; never launched with still frames: mv_step.hip)
+        EnvOptions o = env_options_load<MASKED>(a.view(0), env);
         for (int j = 0; j < a.n; ++j) {
-            if (!MASKED || env_steps(left, tl)) {
+            if (env_options_tick<MASKED>(o)) {
                 S::template tick<1>(a.view(j), env, j > 0);   // (j > 0: B(j - 1) inside, before the write-back)
-                if constexpr (MASKED) if (left > 0 || tl > 0) { wave_sync(); after_tick(a.view(j), env, left, tl); }   // (this wave's own stores)
+                if constexpr (MASKED) if (o.left > 0 || o.tl > 0) { wave_sync(); after_tick(a.view(j), env, o.left, o.tl); }   // (this wave's own stores)
             } else {
                 if (j > 0) __syncthreads();               // B(j - 1): inside a tick (pipe_wait), here in the open
                 frozen_tick(a.view(j), env);
@@ -488,11 +466,10 @@ __device__ __forceinline__ void step_ticks_pipe_body(const Args &a, int W, int H
         }
         __syncthreads();                                  // B(n - 1): the last frame setup's
     } else {
-        [[maybe_unused]] bool drawn = true;   // (mv_set_draw_mask: env_drawn; only this wave needs to know)
-        if constexpr (MASKED) drawn = env_drawn(a.view(0), env);
+        const bool drawn = env_options_load<MASKED>(a.view(0), env).drawn;   // (mv_set_draw_mask: env_drawn; only this wave needs to know)
         for (int j = 0; j < a.n; ++j) {
             __syncthreads();                              // A(j)
-            if (!MASKED || drawn) frame_setup_body<64, true, true>(a.view(j), env, W, H, s_fs);   // B(j) inside
+            if (drawn) frame_setup_body<64, true, true>(a.view(j), env, W, H, s_fs);   // B(j) inside
             else frame_skip<64, true, true>(a.view(j), env);                                      // ... likewise
         }
     }
@@ -532,7 +509,7 @@ struct StepKernels {
     void (*ticks_agents)(StepTicksArgs8, int, int);      // k ticks, several agents per env
     void (*reset)(GymView, int);
     void (*reset_masked)(GymView, const uint8_t *, uint8_t *);   // mv_reset_envs: the envs a mask flags
-    // k ticks that set no frame up, and k ticks whose frame setups follow a mask (step_ticks_sim_body): one agent per env; several (TowerBuilding)
+    // k ticks that set no frame up, and k ticks whose frame setups follow a mask (step_ticks_body: FRAMES_NONE, FRAMES_BY_MASK): one agent per env; several (TowerBuilding)
     void (*ticks_sim)(StepTicksArgs8, int, int);
     void (*ticks_sim_frames)(StepTicksArgs8, int, int);
     void (*ticks_sim_agents)(StepTicksArgs8, int, int);

@@ -10,18 +10,18 @@ namespace mv {
 using S = tick_obstacles::Scenario;
 
 template <int A_MAX> __global__ __launch_bounds__(256) void step_obstacles_kernel(GymView gv, int W, int H, int render) { step_body<S, A_MAX>(gv, blockIdx.x, W, H, render); }
-template <class Args> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_obstacles_ticks_kernel(Args a, int W, int H) { step_ticks_body<S, 1>(a, W, H); }
+template <class Args> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_obstacles_ticks_kernel(Args a, int W, int H) { step_ticks_body<S, 1, Args, FRAMES_ALL>(a, W, H); }
 template <class Args> __global__ __launch_bounds__(128, MV_STEP_TICKS_WAVES_PER_SIMD) void step_obstacles_ticks_pipe_kernel(Args a, int W, int H) { step_ticks_pipe_body<S>(a, W, H); }
-// (ticks that set no frame up; FRAMES: a mask says which ticks do -- step_ticks_sim_body)
-template <class Args, bool FRAMES> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_obstacles_ticks_sim_kernel(Args a, int W, int H) { step_ticks_sim_body<S, 1, Args, FRAMES>(a, W, H); }
+// (ticks that set no frame up; FRAMES: a mask says which ticks do -- step_ticks_body: FRAMES_NONE, FRAMES_BY_MASK)
+template <class Args, bool FRAMES> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_obstacles_ticks_sim_kernel(Args a, int W, int H) { step_ticks_body<S, 1, Args, FRAMES ? FRAMES_BY_MASK : FRAMES_NONE>(a, W, H); }
 __global__ __launch_bounds__(64) void reset_obstacles_kernel(GymView gv, int force_all) { reset_body<S>(gv, force_all); }
 __global__ __launch_bounds__(64) void reset_masked_obstacles_kernel(GymView gv, const uint8_t *mask, uint8_t *applied) { reset_masked_body<S>(gv, mask, applied); }
 
 // the same entry points for views with a step mask (mv_set_step_mask): the MASKED instantiations of the bodies (mv_step_kernels.h)
 template <int A_MAX> __global__ __launch_bounds__(256) void step_obstacles_kernel_masked(GymView gv, int W, int H, int render) { step_body<S, A_MAX, true>(gv, blockIdx.x, W, H, render); }
-template <class Args> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_obstacles_ticks_kernel_masked(Args a, int W, int H) { step_ticks_body<S, 1, true>(a, W, H); }
+template <class Args> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_obstacles_ticks_kernel_masked(Args a, int W, int H) { step_ticks_body<S, 1, Args, FRAMES_ALL, true>(a, W, H); }
 template <class Args> __global__ __launch_bounds__(128, MV_STEP_TICKS_WAVES_PER_SIMD) void step_obstacles_ticks_pipe_kernel_masked(Args a, int W, int H) { step_ticks_pipe_body<S, true>(a, W, H); }
-template <class Args, bool FRAMES> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_obstacles_ticks_sim_kernel_masked(Args a, int W, int H) { step_ticks_sim_body<S, 1, Args, FRAMES, true>(a, W, H); }
+template <class Args, bool FRAMES> __global__ __launch_bounds__(64, MV_STEP_TICKS_WAVES_PER_SIMD) void step_obstacles_ticks_sim_kernel_masked(Args a, int W, int H) { step_ticks_body<S, 1, Args, FRAMES ? FRAMES_BY_MASK : FRAMES_NONE, true>(a, W, H); }
 
 const StepKernels obstacles_kernels = {step_obstacles_kernel<1>, step_obstacles_kernel<MAX_AGENTS>, step_obstacles_ticks_kernel<StepTicksArgs8>,
                                        step_obstacles_ticks_pipe_kernel<StepTicksArgs8>, nullptr, reset_obstacles_kernel, reset_masked_obstacles_kernel,

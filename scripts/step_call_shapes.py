@@ -335,6 +335,94 @@ def status_period_one(r):
     single_ticks(r, g, 2)
 
 
+def stagger(g, ends):
+    """TowerBuilding adds 4 s per object to episodeLengthSec: the clocks are read off the scene rows, and env e is stepped, undrawn, until its episode ends
+    on its ends[e]-th tick from here (-1: the env is left alone)"""
+    g.set_scene_obs(True)
+    g.render()   # (refreshes the rows)
+    rows = np.stack([g.get_scene_observation(e) for e in range(N)])
+    g.set_scene_obs(None)
+    left = np.zeros(N, np.int64)
+    for e in range(N):
+        sec, dt = np.float32(rows[e, 5]), np.float32(1.0) / np.float32(15.0)   # (columns 5, 6: episode_sec, episode_len; the tick's own fp32 sum)
+        while ends[e] >= 0 and sec < rows[e, 6]:
+            sec, left[e] = np.float32(sec + dt), left[e] + 1
+        left[e] = max(left[e] - 1 - ends[e], 0)
+    st = 0
+    while (left > 0).any():
+        k = int(min(left[left > 0].min(), 64))
+        g.set_step_mask(left > 0)
+        g.step_n(k, "multidiscrete", 5, st, render="none")
+        st += k
+        left = np.where(left > 0, left - k, 0)
+    g.set_step_mask(None)
+
+
+def every_option(r, scenario="TowerBuilding", A=1, still=True, params=None, ends=None):
+    """a gym with every option on at once: a step mask that freezes two envs, an episode budget of 1 on one env and 2 on another, a draw mask that leaves one
+    env out, still frames, state and scene rows, the episode log, an output ring of 16.  ends: the ticks the envs' episodes end on (stagger)"""
+    g = r.gym(scenario, A=A, ring=16, params={"episodeLengthSec": 4.3} if params is None else params)
+    g.set_episode_log(64)
+    if ends is not None:
+        stagger(g, ends)
+    g.set_step_mask(np.array([1, 1, 0, 1, 1, 0, 1], bool))
+    g.set_episode_budget(np.array([-1, 1, -1, 2, -1, -1, -1], np.int32))
+    g.set_draw_mask(np.array([1, 1, 1, 1, 0, 1, 1], bool))
+    if still:
+        g.set_still_frames(True)
+    g.set_state_obs(True)
+    g.set_scene_obs(True)
+    return g
+
+
+def every_option_done(r, g):
+    r.add(g.episode_budget(), np.array([g.halted_count()], np.int64))   # (halted_count waits for the gym's stream)
+
+
+def every_option_step_n(r, A, render):
+    """8 calls of 9 ticks: a launch of 8 ticks and one of 1, the carried option state crosses the boundary through memory; then a rendered call"""
+    g = every_option(r, A=A, ends=(9 + 7, 18 + 3, -1, 27 + 7, 36 + 8, -1, 45 + 0))   # (the end of a launch of 8, the launch of 1, a call's first tick, inside)
+    batched(r, g, (9,) * 8, render=render)
+    batched(r, g, (3,))
+    every_option_done(r, g)
+
+
+def every_option_macro(r, A):
+    """8 macro steps of up to 11 ticks with per-env ticks 0, 1 and above k, render 'last' and 'none' in turn; then a rendered call"""
+    g = every_option(r, A=A, ends=(-1, 3, -1, 11 + 8, 22 + 3, -1, 12 + 1))   # (in the env's own ticks)
+    act = (np.arange(N * A * 6).reshape(N * A, 6) % np.array([3, 3, 3, 2, 2, 3])).astype(np.int32)
+    for c in range(8):
+        r.call(g, g.macro_step, 11, act, np.array([0, 1, 11, 12, 15, 5, 3], np.int32), render="last" if c % 2 == 0 else "none")
+    batched(r, g, (3,))
+    every_option_done(r, g)
+
+
+def every_option_obstacles(r, pipe):
+    """ObstaclesEasy, one agent, the two-wave kernel forced on or off (still frames off: a gym with them never launches it)"""
+    before = os.environ.get("MV_STEP_PIPE")
+    os.environ["MV_STEP_PIPE"] = pipe   # (read at every launch)
+    try:
+        g = every_option(r, "ObstaclesEasy", still=False, params={})
+        batched(r, g, (9, 9, 9))
+        batched(r, g, (9,), render="last")
+        every_option_done(r, g)
+        for x in r.gyms:
+            x.synchronize()
+    finally:
+        if before is None:
+            del os.environ["MV_STEP_PIPE"]
+        else:
+            os.environ["MV_STEP_PIPE"] = before
+
+
+for _A in (1, 3):
+    for _render in ("every", "last", "none"):
+        shape(lambda r, A=_A, render=_render: every_option_step_n(r, A, render)).__name__ = f"every_option_k9_{_render}_a{_A}"
+    shape(lambda r, A=_A: every_option_macro(r, A)).__name__ = f"every_option_macro_11_a{_A}"
+for _pipe in ("1", "0"):
+    shape(lambda r, pipe=_pipe: every_option_obstacles(r, pipe)).__name__ = f"every_option_obstacles_pipe_{_pipe}"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="", help="run the shape of this name, or the shapes whose name contains this")
