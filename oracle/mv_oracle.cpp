@@ -33,6 +33,7 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 #ifdef __linux__
 #include <pthread.h>
@@ -114,6 +115,23 @@ static inline V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b
 static inline V3 operator*(V3 a, float s) { return v3(a.x * s, a.y * s, a.z * s); }
 static inline float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 static inline float len2(V3 a) { return dot(a, a); }
+
+// The render model below is stated once, templated on its scalar type: float is the oracle's raster (the code the HIP kernels restate, operation for
+// operation), double is the reference the fp32 results are judged against (mvo_render_f64 / mvo_explain_f64).  VecOf<T>: the vector of scalar T.
+struct V3d {
+    double x, y, z;
+};
+static inline V3d operator+(V3d a, V3d b) { return V3d{a.x + b.x, a.y + b.y, a.z + b.z}; }
+static inline V3d operator-(V3d a, V3d b) { return V3d{a.x - b.x, a.y - b.y, a.z - b.z}; }
+static inline V3d operator*(V3d a, double s) { return V3d{a.x * s, a.y * s, a.z * s}; }
+static inline double dot(V3d a, V3d b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+static inline double len2(V3d a) { return dot(a, a); }
+template <class T> struct VecOf;
+template <> struct VecOf<float> { using type = V3; };
+template <> struct VecOf<double> { using type = V3d; };
+template <class T> struct StateVec;   // a vector of the fp32 state in the scalar type T (exact; float: the record itself, not a copy put together again)
+template <> struct StateVec<float> { static const V3 &of(const V3 &v) { return v; } };
+template <> struct StateVec<double> { static V3d of(const V3 &v) { return V3d{double(v.x), double(v.y), double(v.z)}; } };
 
 // ------------------------------------------------------------------------------------------------
 // fp32 sin/cos used wherever a result feeds state or pixels (cephes-style minimax polynomials,
@@ -1284,15 +1302,20 @@ static void hex_maze_generate(HexMaze &m, int size, uint32_t kruskal_seed)
 // -30 or 90 degrees; (cos, sin) are literals so that neither libm nor constant folding is involved (the reference's 90 degrees is
 // float(M_PI_2), cos = -4.4e-8: we use exactly 0).  Frame k: local = Ry(r)^T world, Ry(r) = [[c, 0, s], [0, 1, 0], [-s, 0, c]].
 static const float HEX_ROT[HEX_FRAMES][2] = {{0.8660254f, 0.5f}, {0.8660254f, -0.5f}, {0.0f, 1.0f}};
-static inline V3 hex_to_local(int k, V3 p)
+static const double HEX_ROT_F64[HEX_FRAMES][2] = {{0.86602540378443865, 0.5}, {0.86602540378443865, -0.5}, {0.0, 1.0}};   // the float64 reference's: cos 30 deg itself
+static inline void hex_rot(int k, float *c, float *s) { *c = HEX_ROT[k][0]; *s = HEX_ROT[k][1]; }
+static inline void hex_rot(int k, double *c, double *s) { *c = HEX_ROT_F64[k][0]; *s = HEX_ROT_F64[k][1]; }
+template <class V> static inline V hex_to_local(int k, V p)
 {
-    const float c = HEX_ROT[k][0], s = HEX_ROT[k][1];
-    return v3(c * p.x - s * p.z, p.y, s * p.x + c * p.z);
+    decltype(p.x) c, s;
+    hex_rot(k, &c, &s);
+    return V{c * p.x - s * p.z, p.y, s * p.x + c * p.z};
 }
-static inline V3 hex_to_world(int k, V3 p)
+template <class V> static inline V hex_to_world(int k, V p)
 {
-    const float c = HEX_ROT[k][0], s = HEX_ROT[k][1];
-    return v3(c * p.x + s * p.z, p.y, c * p.z - s * p.x);
+    decltype(p.x) c, s;
+    hex_rot(k, &c, &s);
+    return V{c * p.x + s * p.z, p.y, c * p.z - s * p.x};
 }
 
 struct HexParams {   // HexagonalMazeComponent members after reset(), component_hexagonal_maze.cpp:20-44
@@ -2279,22 +2302,49 @@ static void player_step(Env &e, int idx, float dt)
 // ------------------------------------------------------------------------------------------------
 // Agent frames
 // ------------------------------------------------------------------------------------------------
-struct Cam {
-    V3 eye;
-    float c[3][3];  // columns = camera right / up / back in world space
+template <class T> struct CamT {
+    typename VecOf<T>::type eye;
+    T c[3][3];  // columns = camera right / up / back in world space
+};
+using Cam = CamT<float>;
+
+// The render model's constants in the scalar type T.  float: the literals the fp32 code has always had (the HIP kernels hold the same ones); double: the
+// model's own values (tan 50 deg, 128 / 72, 0.01, 0x55 / 255 ...), not the fp32 roundings of them.
+template <class T> struct RenderK;
+template <> struct RenderK<float> {
+    static constexpr float TAN_X = 1.19175359f, TAN_Y = 1.19175359f / (128.0f / 72.0f), ZNEAR = 0.01f, ZFAR = 120.0f;
+    static constexpr float EYE_REST = 0.05f, EYE_UP = 0.41f, LIT = 0.001f;
+    static constexpr float AMB = float(0x55) / 255.0f, DIF = float(0xbb) / 255.0f, LCOL = float(0xaa) / 255.0f;
+    static void sincos(float x, float *s, float *c) { mv_sincos(x, s, c); }   // the fp32 polynomial both sides use
+    static float pow300(float x)
+    {
+        const float x2 = x * x, x4 = x2 * x2, x8 = x4 * x4, x16 = x8 * x8, x32 = x16 * x16, x64 = x32 * x32,
+                    x128 = x64 * x64, x256 = x128 * x128;
+        return ((x256 * x32) * x8) * x4;
+    }
+};
+template <> struct RenderK<double> {
+    static constexpr double TAN_X = 1.19175359259420995870530807, TAN_Y = TAN_X / (128.0 / 72.0), ZNEAR = 0.01, ZFAR = 120.0;
+    static constexpr double EYE_REST = 0.05, EYE_UP = 0.41, LIT = 0.001;
+    static constexpr double AMB = double(0x55) / 255.0, DIF = double(0xbb) / 255.0, LCOL = double(0xaa) / 255.0;
+    static void sincos(double x, double *s, double *c) { *s = std::sin(x); *c = std::cos(x); }
+    static double pow300(double x) { return std::pow(x, 300.0); }
 };
 
-static Cam camera_of(const Agent &a)
+// The agent's pose is state and taken as given (position, yaw basis, pitch: fp32, converted exactly); everything derived from it is in T.
+template <class T> static CamT<T> camera_of_t(const Agent &a)
 {   // agent.cpp:33 (+0.41), :95 (+0.05), :110-126 (pitch about local X)
-    Cam cam;
-    cam.eye = v3(a.pos.x, (a.pos.y + 0.05f) + 0.41f, a.pos.z);
-    float sp, cp;
-    mv_sincos(a.pitch, &sp, &cp);
-    cam.c[0][0] = a.m00; cam.c[0][1] = a.m02 * sp; cam.c[0][2] = a.m02 * cp;
-    cam.c[1][0] = 0.0f;  cam.c[1][1] = cp;         cam.c[1][2] = -sp;
-    cam.c[2][0] = a.m20; cam.c[2][1] = a.m22 * sp; cam.c[2][2] = a.m22 * cp;
+    CamT<T> cam;
+    cam.eye = typename VecOf<T>::type{T(a.pos.x), (T(a.pos.y) + RenderK<T>::EYE_REST) + RenderK<T>::EYE_UP, T(a.pos.z)};
+    T sp, cp;
+    RenderK<T>::sincos(T(a.pitch), &sp, &cp);
+    const T m00 = a.m00, m02 = a.m02, m20 = a.m20, m22 = a.m22;
+    cam.c[0][0] = m00;  cam.c[0][1] = m02 * sp; cam.c[0][2] = m02 * cp;
+    cam.c[1][0] = T(0); cam.c[1][1] = cp;       cam.c[1][2] = -sp;
+    cam.c[2][0] = m20;  cam.c[2][1] = m22 * sp; cam.c[2][2] = m22 * cp;
     return cam;
 }
+static Cam camera_of(const Agent &a) { return camera_of_t<float>(a); }
 
 static V3 cam_to_world(const Cam &cam, V3 v)
 {
@@ -2918,9 +2968,9 @@ static void env_step(Env &e)
 // set at :200-203; projection = env_renderer.hpp:34-38 (hfov 100, aspect 128/72 regardless of
 // the framebuffer size).
 // ------------------------------------------------------------------------------------------------
-static const float TAN_HALF_FOV = 1.19175359f;                      // tan(50 deg)
-static const float TAN_HALF_FOV_Y = 1.19175359f / (128.0f / 72.0f);
-static const float NEAR_Z = 0.01f, FAR_Z = 120.0f;
+static const float TAN_HALF_FOV = RenderK<float>::TAN_X;                      // tan(50 deg)
+static const float TAN_HALF_FOV_Y = RenderK<float>::TAN_Y;
+static const float NEAR_Z = RenderK<float>::ZNEAR;
 
 struct Prim {
     int kind;   // 1 = box in frame `frame`, 2 = vertical capsule in world, 3 = cone in world (lo = apex, hi = (radius, height, +1 apex up / -1 apex down)),
@@ -3080,66 +3130,78 @@ static void build_prims(const Env &e, int viewer, std::vector<Prim> &out)
 
 // slab test; returns entry t and entry-face normal (back faces culled: the camera inside a
 // box sees nothing of it)
-static bool ray_box(V3 o, V3 d, V3 lo, V3 hi, float *t_out, V3 *n_out)
+template <class T, class V = typename VecOf<T>::type> static bool ray_box(V o, V d, V lo, V hi, T *t_out, V *n_out)
 {
-    float tEnter = -INFINITY, tExit = INFINITY;
+    T tEnter = -INFINITY, tExit = INFINITY;
     int axis = -1;
-    const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z}, l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
+    const T oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z}, l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
     for (int k = 0; k < 3; ++k) {
-        if (dd[k] == 0.0f) {
+        if (dd[k] == T(0)) {
             if (oo[k] < l[k] || oo[k] > h[k]) return false;
         } else {
-            const float inv = 1.0f / dd[k];
-            const float t1 = (l[k] - oo[k]) * inv, t2 = (h[k] - oo[k]) * inv;
-            const float tn = std::min(t1, t2), tf = std::max(t1, t2);
+            const T inv = T(1) / dd[k];
+            const T t1 = (l[k] - oo[k]) * inv, t2 = (h[k] - oo[k]) * inv;
+            const T tn = std::min(t1, t2), tf = std::max(t1, t2);
             if (tn > tEnter) { tEnter = tn; axis = k; }
             tExit = std::min(tExit, tf);
         }
     }
-    if (axis < 0 || tEnter > tExit || tEnter < NEAR_Z || tEnter > FAR_Z) return false;
-    V3 n = v3(0, 0, 0);
-    const float sgn = dd[axis] > 0 ? -1.0f : 1.0f;
+    if (axis < 0 || tEnter > tExit || tEnter < RenderK<T>::ZNEAR || tEnter > RenderK<T>::ZFAR) return false;
+    V n = V{T(0), T(0), T(0)};
+    const T sgn = dd[axis] > 0 ? T(-1) : T(1);
     if (axis == 0) n.x = sgn; else if (axis == 1) n.y = sgn; else n.z = sgn;
     *t_out = tEnter; *n_out = n;
     return true;
 }
 
-// vertical capsule (radius r, segment half-length hl): cylinder side + two spheres
-static bool ray_capsule(V3 o, V3 d, V3 c, float r, float hl, float *t_out, V3 *n_out)
+// The discriminant of a quadratic's reduced form.  The float64 reference can ask for it moved by `bias` times the size of its two terms, which is how
+// mvo_explain_f64 asks what an fp32 evaluation -- whose B B and A C are each rounded -- may have seen at grazing incidence; bias is 0 wherever a
+// frame is drawn, and the fp32 code takes none.
+template <class T> static inline T disc_of(T A, T B, T C, T bias)
 {
+    T disc = B * B - A * C;
+    if constexpr (std::is_same<T, double>::value) disc += bias * (B * B + std::abs(A * C));
+    else (void)bias;
+    return disc;
+}
+
+// vertical capsule (radius r, segment half-length hl): cylinder side + two spheres
+template <class T, class V = typename VecOf<T>::type> static bool ray_capsule(V o, V d, V c, T r, T hl, T *t_out, V *n_out, T bias = T(0))
+{
+    const T NEAR_Z = RenderK<T>::ZNEAR, FAR_Z = RenderK<T>::ZFAR;
     bool hit = false;
-    float best = INFINITY; V3 bn = v3(0, 0, 0);
-    const float ox = o.x - c.x, oz = o.z - c.z;
-    const float A = d.x * d.x + d.z * d.z;
-    if (A > 0.0f) {
-        const float B = ox * d.x + oz * d.z;
-        const float C = (ox * ox + oz * oz) - r * r;
-        const float disc = B * B - A * C;
-        if (disc >= 0.0f) {
-            const float t = (-B - sqrtf(disc)) / A;
-            const float y = o.y + t * d.y;
+    T best = INFINITY; V bn = V{T(0), T(0), T(0)};
+    const T ox = o.x - c.x, oz = o.z - c.z;
+    const T A = d.x * d.x + d.z * d.z;
+    if (A > T(0)) {
+        const T B = ox * d.x + oz * d.z;
+        const T C = (ox * ox + oz * oz) - r * r;
+        const T disc = disc_of(A, B, C, bias);
+        if (disc >= T(0)) {
+            const T t = (-B - std::sqrt(disc)) / A;
+            const T y = o.y + t * d.y;
             if (t >= NEAR_Z && t <= FAR_Z && y >= c.y - hl && y <= c.y + hl) {
                 hit = true; best = t;
-                const float inv = 1.0f / r;
-                bn = v3((ox + t * d.x) * inv, 0.0f, (oz + t * d.z) * inv);
+                const T inv = T(1) / r;
+                bn = V{(ox + t * d.x) * inv, T(0), (oz + t * d.z) * inv};
             }
         }
     }
     for (int s = 0; s < 2; ++s) {
-        const float cy = s == 0 ? c.y - hl : c.y + hl;
-        const float oy = o.y - cy;
-        const float A3 = (d.x * d.x + d.y * d.y) + d.z * d.z;
-        const float B3 = (ox * d.x + oy * d.y) + oz * d.z;
-        const float C3 = ((ox * ox + oy * oy) + oz * oz) - r * r;
-        const float disc = B3 * B3 - A3 * C3;
-        if (disc >= 0.0f) {
-            const float t = (-B3 - sqrtf(disc)) / A3;
-            const float y = o.y + t * d.y;
+        const T cy = s == 0 ? c.y - hl : c.y + hl;
+        const T oy = o.y - cy;
+        const T A3 = (d.x * d.x + d.y * d.y) + d.z * d.z;
+        const T B3 = (ox * d.x + oy * d.y) + oz * d.z;
+        const T C3 = ((ox * ox + oy * oy) + oz * oz) - r * r;
+        const T disc = disc_of(A3, B3, C3, bias);
+        if (disc >= T(0)) {
+            const T t = (-B3 - std::sqrt(disc)) / A3;
+            const T y = o.y + t * d.y;
             const bool capSide = s == 0 ? (y <= cy) : (y >= cy);
             if (t >= NEAR_Z && t <= FAR_Z && capSide && t < best) {
                 hit = true; best = t;
-                const float inv = 1.0f / r;
-                bn = v3((ox + t * d.x) * inv, (oy + t * d.y) * inv, (oz + t * d.z) * inv);
+                const T inv = T(1) / r;
+                bn = V{(ox + t * d.x) * inv, (oy + t * d.y) * inv, (oz + t * d.z) * inv};
             }
         }
     }
@@ -3148,28 +3210,29 @@ static bool ray_capsule(V3 o, V3 d, V3 c, float r, float hl, float *t_out, V3 *n
 }
 
 // Unit capped cylinder (Primitives::cylinderSolid(.., halfLength 0.5, CapEnds), render_utils.cpp:30): radius 1, |y| <= hl.
-static bool ray_cylinder_unit(V3 o, V3 d, float hl, float *t_out, V3 *n_out)
+template <class T, class V = typename VecOf<T>::type> static bool ray_cylinder_unit(V o, V d, T hl, T *t_out, V *n_out, T bias = T(0))
 {
+    const T NEAR_Z = RenderK<T>::ZNEAR, FAR_Z = RenderK<T>::ZFAR;
     bool hit = false;
-    float best = INFINITY; V3 bn = v3(0, 0, 0);
-    const float A = d.x * d.x + d.z * d.z;
-    if (A > 0.0f) {
-        const float B = o.x * d.x + o.z * d.z;
-        const float C = (o.x * o.x + o.z * o.z) - 1.0f;
-        const float disc = B * B - A * C;
-        if (disc >= 0.0f) {
-            const float t = (-B - sqrtf(disc)) / A;
-            const float y = o.y + t * d.y;
-            if (t >= NEAR_Z && t <= FAR_Z && y >= -hl && y <= hl) { hit = true; best = t; bn = v3(o.x + t * d.x, 0.0f, o.z + t * d.z); }
+    T best = INFINITY; V bn = V{T(0), T(0), T(0)};
+    const T A = d.x * d.x + d.z * d.z;
+    if (A > T(0)) {
+        const T B = o.x * d.x + o.z * d.z;
+        const T C = (o.x * o.x + o.z * o.z) - T(1);
+        const T disc = disc_of(A, B, C, bias);
+        if (disc >= T(0)) {
+            const T t = (-B - std::sqrt(disc)) / A;
+            const T y = o.y + t * d.y;
+            if (t >= NEAR_Z && t <= FAR_Z && y >= -hl && y <= hl) { hit = true; best = t; bn = V{o.x + t * d.x, T(0), o.z + t * d.z}; }
         }
     }
     for (int s = 0; s < 2; ++s) {   // caps: entered from outside only (back faces are culled)
-        const float cy = s == 0 ? -hl : hl;
-        const bool entering = s == 0 ? (d.y > 0.0f && o.y < cy) : (d.y < 0.0f && o.y > cy);
+        const T cy = s == 0 ? -hl : hl;
+        const bool entering = s == 0 ? (d.y > T(0) && o.y < cy) : (d.y < T(0) && o.y > cy);
         if (!entering) continue;
-        const float t = (cy - o.y) / d.y;
-        const float x = o.x + t * d.x, z = o.z + t * d.z;
-        if (t >= NEAR_Z && t <= FAR_Z && x * x + z * z <= 1.0f && t < best) { hit = true; best = t; bn = v3(0.0f, s == 0 ? -1.0f : 1.0f, 0.0f); }
+        const T t = (cy - o.y) / d.y;
+        const T x = o.x + t * d.x, z = o.z + t * d.z;
+        if (t >= NEAR_Z && t <= FAR_Z && x * x + z * z <= T(1) && t < best) { hit = true; best = t; bn = V{T(0), s == 0 ? T(-1) : T(1), T(0)}; }
     }
     if (hit) { *t_out = best; *n_out = bn; }
     return hit;
@@ -3177,76 +3240,70 @@ static bool ray_cylinder_unit(V3 o, V3 d, float hl, float *t_out, V3 *n_out)
 
 // kinds 4 / 5 / 6: the ray is taken into the shape's unit space (the scale is diagonal, so t is unchanged), the unit-space
 // normal comes back through the inverse-transpose scale
-static bool ray_scaled_shape(int kind, V3 o, V3 d, V3 centre, V3 scale, float *t_out, V3 *n_out)
+template <class T, class V = typename VecOf<T>::type> static bool ray_scaled_shape(int kind, V o, V d, V centre, V scale, T *t_out, V *n_out, T bias = T(0))
 {
-    const V3 oo = v3((o.x - centre.x) / scale.x, (o.y - centre.y) / scale.y, (o.z - centre.z) / scale.z);
-    const V3 dd = v3(d.x / scale.x, d.y / scale.y, d.z / scale.z);
-    V3 nl;
+    const V oo = V{(o.x - centre.x) / scale.x, (o.y - centre.y) / scale.y, (o.z - centre.z) / scale.z};
+    const V dd = V{d.x / scale.x, d.y / scale.y, d.z / scale.z};
+    V nl;
     bool hit;
-    if (kind == 6) hit = ray_cylinder_unit(oo, dd, 0.5f, t_out, &nl);
-    else hit = ray_capsule(oo, dd, v3(0, 0, 0), 1.0f, kind == 5 ? 1.0f : 0.0f, t_out, &nl);
+    if (kind == 6) hit = ray_cylinder_unit<T>(oo, dd, T(0.5), t_out, &nl, bias);
+    else hit = ray_capsule<T>(oo, dd, V{T(0), T(0), T(0)}, T(1), kind == 5 ? T(1) : T(0), t_out, &nl, bias);
     if (!hit) return false;
-    V3 n = v3(nl.x / scale.x, nl.y / scale.y, nl.z / scale.z);
-    n = n * (1.0f / sqrtf(len2(n)));
+    V n = V{nl.x / scale.x, nl.y / scale.y, nl.z / scale.z};
+    n = n * (T(1) / std::sqrt(len2(n)));
     *n_out = n;
     return true;
 }
 
 // Open cone (no base cap, Primitives::coneSolid without CapEnd): apex a, axis +-y (dirSign +1: apex up),
 // height h, base radius r.  Only the outside is visible (back-face culling).
-static bool ray_cone(V3 o, V3 d, V3 a, float r, float h, float dirSign, float *t_out, V3 *n_out)
+template <class T, class V = typename VecOf<T>::type> static bool ray_cone(V o, V d, V a, T r, T h, T dirSign, T *t_out, V *n_out, T bias = T(0))
 {
-    const float k = (r / h) * (r / h);
-    const float ox = o.x - a.x, oz = o.z - a.z;
-    const float s0 = dirSign * (a.y - o.y);      // distance from the apex along the axis at t = 0
-    const float ds = -dirSign * d.y;             // its derivative
-    const float A = (d.x * d.x + d.z * d.z) - k * (ds * ds);
-    const float B = (ox * d.x + oz * d.z) - k * (s0 * ds);
-    const float C = (ox * ox + oz * oz) - k * (s0 * s0);
-    if (A == 0.0f) return false;
-    const float disc = B * B - A * C;
-    if (!(disc >= 0.0f)) return false;
-    const float sq = sqrtf(disc);
+    const T NEAR_Z = RenderK<T>::ZNEAR, FAR_Z = RenderK<T>::ZFAR;
+    const T k = (r / h) * (r / h);
+    const T ox = o.x - a.x, oz = o.z - a.z;
+    const T s0 = dirSign * (a.y - o.y);      // distance from the apex along the axis at t = 0
+    const T ds = -dirSign * d.y;             // its derivative
+    const T A = (d.x * d.x + d.z * d.z) - k * (ds * ds);
+    const T B = (ox * d.x + oz * d.z) - k * (s0 * ds);
+    const T C = (ox * ox + oz * oz) - k * (s0 * s0);
+    if (A == T(0)) return false;
+    const T disc = disc_of(A, B, C, bias);
+    if (!(disc >= T(0))) return false;
+    const T sq = std::sqrt(disc);
     bool hit = false;
-    float best = INFINITY; V3 bn = v3(0, 0, 0);
+    T best = INFINITY; V bn = V{T(0), T(0), T(0)};
     for (int i = 0; i < 2; ++i) {
-        const float t = (i == 0 ? (-B - sq) : (-B + sq)) / A;
-        const float s = s0 + t * ds;
-        if (!(t >= NEAR_Z && t <= FAR_Z && s >= 0.0f && s <= h && t < best)) continue;
-        const float px = ox + t * d.x, pz = oz + t * d.z;
-        V3 n = v3(px, dirSign * (k * s), pz);
-        if (!(dot(n, d) < 0.0f)) continue;       // back face
-        const float l2 = len2(n);
-        if (!(l2 > 0.0f)) continue;
-        n = n * (1.0f / sqrtf(l2));
+        const T t = (i == 0 ? (-B - sq) : (-B + sq)) / A;
+        const T s = s0 + t * ds;
+        if (!(t >= NEAR_Z && t <= FAR_Z && s >= T(0) && s <= h && t < best)) continue;
+        const T px = ox + t * d.x, pz = oz + t * d.z;
+        V n = V{px, dirSign * (k * s), pz};
+        if (!(dot(n, d) < T(0))) continue;       // back face
+        const T l2 = len2(n);
+        if (!(l2 > T(0))) continue;
+        n = n * (T(1) / std::sqrt(l2));
         hit = true; best = t; bn = n;
     }
     if (hit) { *t_out = best; *n_out = bn; }
     return hit;
 }
 
-static inline V3 mat_mul(const float m[3][3], V3 v)
+template <class T, class V = typename VecOf<T>::type> static inline V mat_mul(const T (&m)[3][3], V v)
 {
-    return v3((m[0][0] * v.x + m[0][1] * v.y) + m[0][2] * v.z, (m[1][0] * v.x + m[1][1] * v.y) + m[1][2] * v.z,
-              (m[2][0] * v.x + m[2][1] * v.y) + m[2][2] * v.z);
+    return V{(m[0][0] * v.x + m[0][1] * v.y) + m[0][2] * v.z, (m[1][0] * v.x + m[1][1] * v.y) + m[1][2] * v.z,
+             (m[2][0] * v.x + m[2][1] * v.y) + m[2][2] * v.z};
 }
-static inline V3 mat_tmul(const float m[3][3], V3 v)
+template <class T, class V = typename VecOf<T>::type> static inline V mat_tmul(const T (&m)[3][3], V v)
 {
-    return v3((m[0][0] * v.x + m[1][0] * v.y) + m[2][0] * v.z, (m[0][1] * v.x + m[1][1] * v.y) + m[2][1] * v.z,
-              (m[0][2] * v.x + m[1][2] * v.y) + m[2][2] * v.z);
-}
-
-static inline float pow300(float x)
-{
-    const float x2 = x * x, x4 = x2 * x2, x8 = x4 * x4, x16 = x8 * x8, x32 = x16 * x16, x64 = x32 * x32,
-                x128 = x64 * x64, x256 = x128 * x128;
-    return ((x256 * x32) * x8) * x4;
+    return V{(m[0][0] * v.x + m[1][0] * v.y) + m[2][0] * v.z, (m[0][1] * v.x + m[1][1] * v.y) + m[2][1] * v.z,
+             (m[0][2] * v.x + m[1][2] * v.y) + m[2][2] * v.z};
 }
 
-static inline uint8_t to_u8(float v)
+template <class T> static inline uint8_t to_u8(T v)
 {
-    v = std::min(std::max(v, 0.0f), 1.0f);
-    return (uint8_t)(int)floorf(v * 255.0f + 0.5f);
+    v = std::min(std::max(v, T(0)), T(1));
+    return (uint8_t)(int)std::floor(v * T(255) + T(0.5));
 }
 
 // Conservative screen rectangle of a primitive's bounding box for the tiled raster below: the projection of the part of the box in front of the
@@ -3301,93 +3358,127 @@ static ScreenRect prim_screen_rect(const Prim &p, const Cam *cams, int viewer, i
     return r;
 }
 
+// One viewer's frame in the scalar type T: every agent's camera, and the two halves of a pixel -- which primitive (of build_prims: fp32 state, taken as
+// given) a ray meets, where and with what normal (hit), and the colour of that point (shade).  (It holds no pointer and is handed to nothing that is not
+// inlined, so a frame's constants stay in registers across the pixel loop's byte stores.)
+template <class T> struct RenderFrame {
+    using V = typename VecOf<T>::type;
+    CamT<T> cams[MAX_AGENTS];
+    V originIn[MAX_AGENTS], hexOrigin[HEX_FRAMES];   // ray origins in every agent frame / wall frame are per-frame constants
+    int viewer;
+    T discBias = T(0);   // (disc_of: the float64 reference's explain only)
+
+    __attribute__((always_inline)) inline RenderFrame(const Env &e, int viewer_) : viewer(viewer_)
+    {
+        for (int k = 0; k < e.numAgents; ++k) cams[k] = camera_of_t<T>(e.agents[k]);
+        const CamT<T> &cam = cams[viewer];
+        for (int k = 0; k < e.numAgents; ++k) originIn[k] = mat_tmul(cams[k].c, cam.eye - cams[k].eye);
+        for (int k = 0; k < HEX_FRAMES; ++k) hexOrigin[k] = hex_to_local(k, cam.eye);
+    }
+
+    // the ray through the screen point (sx, sy), in pixels from the frame's bottom-left corner (a pixel's centre: i + 0.5, j + 0.5): its direction in the
+    // viewer's camera space (dc) and in world space (dw)
+    void ray(T sx, T sy, int W, int H, V *dc, V *dw) const
+    {
+        const T xn = (sx / T(W)) * T(2) - T(1);
+        const T yn = (sy / T(H)) * T(2) - T(1);
+        *dc = V{xn * RenderK<T>::TAN_X, yn * RenderK<T>::TAN_Y, T(-1)};
+        *dw = mat_mul(cams[viewer].c, *dc);
+    }
+
+    // n ends up in the viewer's camera space
+    __attribute__((always_inline)) inline bool hit(const Prim &p, V dc, V dw, T *t_out, V *n_out) const
+    {
+        const CamT<T> &cam = cams[viewer];
+        const V &lo = StateVec<T>::of(p.lo), &hi = StateVec<T>::of(p.hi);
+        const V zero = V{T(0), T(0), T(0)};
+        T t; V n;
+        bool got;
+        if (p.kind == 2) {
+            got = ray_capsule(cam.eye, dw, lo, hi.x, hi.y, &t, &n, discBias);
+            if (got) n = mat_tmul(cam.c, n);
+        } else if (p.kind == 3) {
+            got = ray_cone(cam.eye, dw, lo, hi.x, hi.y, hi.z, &t, &n, discBias);
+            if (got) n = mat_tmul(cam.c, n);
+        } else if (p.kind >= 4) {
+            if (p.frame < 0) {
+                got = ray_scaled_shape(p.kind, cam.eye, dw, lo, hi, &t, &n, discBias);
+                if (got) n = mat_tmul(cam.c, n);
+            } else if (p.frame == viewer) {
+                got = ray_scaled_shape(p.kind, zero, dc, lo, hi, &t, &n, discBias);
+            } else {
+                const V dk = mat_tmul(cams[p.frame].c, dw);
+                got = ray_scaled_shape(p.kind, originIn[p.frame], dk, lo, hi, &t, &n, discBias);
+                if (got) n = mat_tmul(cam.c, mat_mul(cams[p.frame].c, n));
+            }
+        } else if (p.frame >= MAX_AGENTS) {   // hex wall frame: a rotation about Y around the world origin
+            const int k = p.frame - MAX_AGENTS;
+            got = ray_box(hexOrigin[k], hex_to_local(k, dw), lo, hi, &t, &n);
+            if (got) n = mat_tmul(cam.c, hex_to_world(k, n));
+        } else if (p.frame < 0) {
+            got = ray_box(cam.eye, dw, lo, hi, &t, &n);
+            if (got) n = mat_tmul(cam.c, n);
+        } else if (p.frame == viewer) {
+            got = ray_box(zero, dc, lo, hi, &t, &n);
+        } else {
+            const V dk = mat_tmul(cams[p.frame].c, dw);
+            got = ray_box(originIn[p.frame], dk, lo, hi, &t, &n);
+            if (got) n = mat_tmul(cam.c, mat_mul(cams[p.frame].c, n));
+        }
+        if (got) { *t_out = t; *n_out = n; }
+        return got;
+    }
+
+    // Phong: the point dc * t of a surface of colour `color` with normal n (camera space), lit from LIGHT (camera space)
+    __attribute__((always_inline)) inline void shade(V dc, T t, V n, unsigned color, uint8_t *px) const
+    {
+        const V LIGHT = V{T(0), T(4), T(2)};
+        const T AMB = RenderK<T>::AMB, DIF = RenderK<T>::DIF, LCOL = RenderK<T>::LCOL;
+        const V P = dc * t;  // camera-space position
+        V Ld = LIGHT - P;
+        Ld = Ld * (T(1) / std::sqrt(len2(Ld)));
+        const T intensity = std::max(T(0), dot(n, Ld));
+        T spec = T(0);
+        if (intensity > RenderK<T>::LIT) {
+            // reflect(-L, N) = -L + 2 (N.L) N
+            const T k2 = T(2) * dot(n, Ld);
+            const V R = V{k2 * n.x - Ld.x, k2 * n.y - Ld.y, k2 * n.z - Ld.z};
+            V Vd = V{-P.x, -P.y, -P.z};
+            Vd = Vd * (T(1) / std::sqrt(len2(Vd)));
+            spec = RenderK<T>::pow300(std::max(T(0), dot(Vd, R)));
+            spec = std::min(std::max(spec, T(0)), T(1));
+        }
+        const T col[3] = {T((color >> 16) & 255) / T(255), T((color >> 8) & 255) / T(255), T(color & 255) / T(255)};
+        for (int ch = 0; ch < 3; ++ch) {
+            const T v = (AMB * col[ch] + (DIF * col[ch]) * LCOL * intensity) + spec;
+            px[ch] = to_u8(v);
+        }
+        px[3] = 255;
+    }
+};
+
 static void render_agent(const Env &e, int viewer, int W, int H, uint8_t *out, bool tiled = false)
 {
     std::vector<Prim> prims;
     build_prims(e, viewer, prims);
-    Cam cams[MAX_AGENTS];
-    for (int k = 0; k < e.numAgents; ++k) cams[k] = camera_of(e.agents[k]);
-    const Cam &cam = cams[viewer];
-
-    // ray origins/rotations into every agent frame are per-frame constants
-    V3 originIn[MAX_AGENTS];
-    for (int k = 0; k < e.numAgents; ++k) originIn[k] = mat_tmul(cams[k].c, cam.eye - cams[k].eye);
-
-    V3 hexOrigin[HEX_FRAMES];
-    for (int k = 0; k < HEX_FRAMES; ++k) hexOrigin[k] = hex_to_local(k, cam.eye);
-
-    const V3 LIGHT = v3(0.0f, 4.0f, 2.0f);
-    const float AMB = float(0x55) / 255.0f, DIF = float(0xbb) / 255.0f, LCOL = float(0xaa) / 255.0f;
+    const RenderFrame<float> fr(e, viewer);
+    const Cam *cams = fr.cams;
 
     // one pixel against the primitives list[0 .. n) (indices into prims, ascending: ties keep the draw order)
     auto pixel = [&](int i, int j, const int *list, int n) {
-            const float xn = ((float(i) + 0.5f) / float(W)) * 2.0f - 1.0f;
-            const float yn = ((float(j) + 0.5f) / float(H)) * 2.0f - 1.0f;
-            const V3 dc = v3(xn * TAN_HALF_FOV, yn * TAN_HALF_FOV_Y, -1.0f);
-            const V3 dw = mat_mul(cam.c, dc);
+            V3 dc, dw;
+            fr.ray(float(i) + 0.5f, float(j) + 0.5f, W, H, &dc, &dw);
 
             float best = INFINITY; V3 bestN = v3(0, 0, 0); unsigned bestColor = 0; bool any = false;
             for (int li = 0; li < n; ++li) {
                 const Prim &p = prims[(size_t)list[li]];
-                float t; V3 n;  // n ends up in the viewer's camera space
-                bool hit;
-                if (p.kind == 2) {
-                    hit = ray_capsule(cam.eye, dw, p.lo, p.hi.x, p.hi.y, &t, &n);
-                    if (hit) n = mat_tmul(cam.c, n);
-                } else if (p.kind == 3) {
-                    hit = ray_cone(cam.eye, dw, p.lo, p.hi.x, p.hi.y, p.hi.z, &t, &n);
-                    if (hit) n = mat_tmul(cam.c, n);
-                } else if (p.kind >= 4) {
-                    if (p.frame < 0) {
-                        hit = ray_scaled_shape(p.kind, cam.eye, dw, p.lo, p.hi, &t, &n);
-                        if (hit) n = mat_tmul(cam.c, n);
-                    } else if (p.frame == viewer) {
-                        hit = ray_scaled_shape(p.kind, v3(0, 0, 0), dc, p.lo, p.hi, &t, &n);
-                    } else {
-                        const V3 dk = mat_tmul(cams[p.frame].c, dw);
-                        hit = ray_scaled_shape(p.kind, originIn[p.frame], dk, p.lo, p.hi, &t, &n);
-                        if (hit) n = mat_tmul(cam.c, mat_mul(cams[p.frame].c, n));
-                    }
-                } else if (p.frame >= MAX_AGENTS) {   // hex wall frame: a rotation about Y around the world origin
-                    const int k = p.frame - MAX_AGENTS;
-                    hit = ray_box(hexOrigin[k], hex_to_local(k, dw), p.lo, p.hi, &t, &n);
-                    if (hit) n = mat_tmul(cam.c, hex_to_world(k, n));
-                } else if (p.frame < 0) {
-                    hit = ray_box(cam.eye, dw, p.lo, p.hi, &t, &n);
-                    if (hit) n = mat_tmul(cam.c, n);
-                } else if (p.frame == viewer) {
-                    hit = ray_box(v3(0, 0, 0), dc, p.lo, p.hi, &t, &n);
-                } else {
-                    const V3 dk = mat_tmul(cams[p.frame].c, dw);
-                    hit = ray_box(originIn[p.frame], dk, p.lo, p.hi, &t, &n);
-                    if (hit) n = mat_tmul(cam.c, mat_mul(cams[p.frame].c, n));
-                }
-                if (hit && t < best) { best = t; bestN = n; bestColor = p.color; any = true; }
+                float t; V3 nn;
+                if (fr.hit(p, dc, dw, &t, &nn) && t < best) { best = t; bestN = nn; bestColor = p.color; any = true; }
             }
 
             uint8_t *px = out + (size_t(j) * W + i) * 4;
             if (!any) { px[0] = px[1] = px[2] = 0; px[3] = 255; return; }
-            const V3 P = dc * best;  // camera-space position
-            V3 Ld = LIGHT - P;
-            Ld = Ld * (1.0f / sqrtf(len2(Ld)));
-            const float intensity = std::max(0.0f, dot(bestN, Ld));
-            float spec = 0.0f;
-            if (intensity > 0.001f) {
-                // reflect(-L, N) = -L + 2 (N.L) N
-                const float k2 = 2.0f * dot(bestN, Ld);
-                const V3 R = v3(k2 * bestN.x - Ld.x, k2 * bestN.y - Ld.y, k2 * bestN.z - Ld.z);
-                V3 Vd = v3(-P.x, -P.y, -P.z);
-                Vd = Vd * (1.0f / sqrtf(len2(Vd)));
-                spec = pow300(std::max(0.0f, dot(Vd, R)));
-                spec = std::min(std::max(spec, 0.0f), 1.0f);
-            }
-            const float col[3] = {float((bestColor >> 16) & 255) / 255.0f, float((bestColor >> 8) & 255) / 255.0f,
-                                  float(bestColor & 255) / 255.0f};
-            for (int ch = 0; ch < 3; ++ch) {
-                const float v = (AMB * col[ch] + (DIF * col[ch]) * LCOL * intensity) + spec;
-                px[ch] = to_u8(v);
-            }
-            px[3] = 255;
+            fr.shade(dc, best, bestN, bestColor, px);
     };
 
     std::vector<int> all(prims.size());
@@ -3414,6 +3505,91 @@ static void render_agent(const Env &e, int viewer, int W, int H, uint8_t *out, b
             for (int j = ty; j <= y1; ++j)
                 for (int i = tx; i <= x1; ++i) pixel(i, j, list.data(), (int)list.size());
         }
+}
+
+// ---- the float64 reference of the render model (mvo_render_f64, mvo_explain_f64): the same RenderFrame, instantiated in double.  State in (poses,
+// primitive bounds, colours: fp32, converted exactly), everything after it in double: std::sin / std::cos of the pitch, rays, hit tests, nearest hit,
+// Phong with pow(x, 300), bytes.  Brute force: every primitive against every pixel; ties keep the draw order, as in the fp32 raster.
+static void render_f64(const Env &e, int viewer, int W, int H, uint8_t *rgba, int32_t *primOut)
+{
+    std::vector<Prim> prims;
+    build_prims(e, viewer, prims);
+    const RenderFrame<double> fr(e, viewer);
+    for (int j = 0; j < H; ++j)
+        for (int i = 0; i < W; ++i) {
+            V3d dc, dw;
+            fr.ray(double(i) + 0.5, double(j) + 0.5, W, H, &dc, &dw);
+            double best = INFINITY; V3d bestN = V3d{0, 0, 0}; int bestP = -1;
+            for (size_t pi = 0; pi < prims.size(); ++pi) {
+                double t; V3d n;
+                if (fr.hit(prims[pi], dc, dw, &t, &n) && t < best) { best = t; bestN = n; bestP = (int)pi; }
+            }
+            uint8_t *px = rgba + (size_t(j) * W + i) * 4;
+            if (bestP < 0) { px[0] = px[1] = px[2] = 0; px[3] = 255; }
+            else fr.shade(dc, best, bestN, prims[(size_t)bestP].color, px);
+            if (primOut) primOut[size_t(j) * W + i] = bestP;
+        }
+}
+
+// What an fp32 evaluation of pixel (x, y) may legitimately show: at the pixel's centre and at the eight points delta_px away from it in x, in y and in
+// both, the shaded colour of every primitive whose hit lies within t_best (1 + eps_t) of that probe's nearest hit (the background where nothing is
+// hit).  A curved primitive's hit comes from a quadratic whose discriminant B B - A C an fp32 evaluation forms from two rounded products of rounded sums:
+// near a silhouette, where the two cancel, its error of a few 2^-24 (B B + |A C|) moves the root by the SQUARE ROOT of that -- 2^-10 of the distance,
+// not 2^-23 -- and with it the point whose normal is shaded (a cone one pixel wide, a cone's apex: any azimuth).  So every probe is evaluated three
+// times: with the discriminants as they are, and moved by +-EXPLAIN_DISC_BIAS (B B + |A C|), 2^-20: sixteen roundings of 2^-24.  The colours only the
+// moved evaluations give are marked (fourth byte 254, else 255): they bound what such a pixel may show, they do not enumerate it.
+// Distinct colours only, at most MVO_EXPLAIN_MAX stored per pixel; counts[i] is the number found (> MVO_EXPLAIN_MAX: the list is cut).
+static const double EXPLAIN_DISC_BIAS = 0x1p-20;
+static void explain_f64(const Env &e, int viewer, int W, int H, int n, const int32_t *xy, double deltaPx, double epsT, uint8_t *colors, int32_t *counts)
+{
+    std::vector<Prim> prims;
+    build_prims(e, viewer, prims);
+    RenderFrame<double> fr(e, viewer);
+    std::vector<double> ts(prims.size());
+    std::vector<V3d> ns(prims.size());
+    std::vector<char> plainHit(9 * prims.size());
+    for (int q = 0; q < n; ++q) {
+        uint8_t *out = colors + (size_t)q * MVO_EXPLAIN_MAX * 4;
+        int cnt = 0;
+        auto add = [&](const uint8_t *c) {
+            for (int k = 0; k < std::min(cnt, (int)MVO_EXPLAIN_MAX); ++k)
+                if (!memcmp(out + 4 * k, c, 3)) return;
+            if (cnt < MVO_EXPLAIN_MAX) memcpy(out + 4 * cnt, c, 4);
+            ++cnt;
+        };
+        const int probes = deltaPx > 0.0 ? 9 : 1;
+        for (int pr = 0; pr < 3 * probes; ++pr) {   // probe 0 is the centre; every probe with the curved primitives' discriminants as they are, raised and lowered
+            fr.discBias = (pr / probes == 0 ? 0.0 : pr / probes == 1 ? EXPLAIN_DISC_BIAS : -EXPLAIN_DISC_BIAS);
+            static const int OFF[9][2] = {{0, 0}, {-1, 0}, {1, 0}, {0, -1}, {0, 1}, {-1, -1}, {1, -1}, {-1, 1}, {1, 1}};
+            V3d dc, dw;
+            fr.ray(double(xy[2 * q]) + 0.5 + OFF[pr % probes][0] * deltaPx, double(xy[2 * q + 1]) + 0.5 + OFF[pr % probes][1] * deltaPx, W, H, &dc, &dw);
+            double best = INFINITY;
+            for (size_t pi = 0; pi < prims.size(); ++pi) {
+                if (!fr.hit(prims[pi], dc, dw, &ts[pi], &ns[pi])) ts[pi] = INFINITY;
+                best = std::min(best, ts[pi]);
+            }
+            const uint8_t group = pr < probes ? 255 : 254;   // the fourth byte: 255 a candidate of the model as it is, 254 one with moved discriminants
+            uint8_t c[4] = {0, 0, 0, group};
+            if (best == INFINITY) add(c);
+            for (size_t pi = 0; pi < prims.size(); ++pi) {
+                const bool isHit = ts[pi] != INFINITY;
+                if (isHit && ts[pi] <= best * (1.0 + epsT)) { fr.shade(dc, ts[pi], ns[pi], prims[pi].color, c); c[3] = group; add(c); }
+                if (pr < probes) plainHit[(size_t)pr * prims.size() + pi] = isHit;
+                else if (isHit != (bool)plainHit[(size_t)(pr % probes) * prims.size() + pi] && (!isHit || ts[pi] <= best * (1.0 + epsT))) {
+                    // grazing: the ray meets this primitive or not depending on the rounding of its discriminant.  There an fp32 evaluation's choice of
+                    // root and its normal are not determined: the primitive's colour from unlit to fully lit (no highlight) bounds what it shows
+                    const unsigned col = prims[pi].color;
+                    for (int lit = 0; lit < 2; ++lit) {
+                        const double k = RenderK<double>::AMB + (lit ? RenderK<double>::DIF * RenderK<double>::LCOL : 0.0);
+                        c[0] = to_u8(k * double((col >> 16) & 255) / 255.0); c[1] = to_u8(k * double((col >> 8) & 255) / 255.0);
+                        c[2] = to_u8(k * double(col & 255) / 255.0); c[3] = 254;
+                        add(c);
+                    }
+                }
+            }
+        }
+        counts[q] = cnt;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3673,6 +3849,18 @@ void mvo_step(mvo_gym *g) { g->step(true); }
 void mvo_step_norender(mvo_gym *g) { g->step(false); }
 void mvo_render(mvo_gym *g) { g->render(); }
 void mvo_set_raster(mvo_gym *g, int tiled) { g->tiledRaster = tiled != 0; }
+void mvo_render_f64(mvo_gym *g, int env, int agent, uint8_t *out_rgba, int32_t *out_prim) { render_f64(*g->envs[env], agent, g->w, g->h, out_rgba, out_prim); }
+void mvo_explain_f64(mvo_gym *g, int env, int agent, int n, const int32_t *xy, double delta_px, double eps_t, uint8_t *out_colors, int32_t *out_counts)
+{
+    explain_f64(*g->envs[env], agent, g->w, g->h, n, xy, delta_px, eps_t, out_colors, out_counts);
+}
+int mvo_prim_table(mvo_gym *g, int env, int agent, int max, int32_t *out_kind_frame)
+{
+    std::vector<Prim> prims;
+    build_prims(*g->envs[env], agent, prims);
+    for (int i = 0; i < (int)prims.size() && i < max; ++i) { out_kind_frame[2 * i] = prims[(size_t)i].kind; out_kind_frame[2 * i + 1] = prims[(size_t)i].frame; }
+    return (int)prims.size();
+}
 int mvo_is_done(mvo_gym *g, int env) { return g->done[env]; }
 void mvo_get_dones(mvo_gym *g, uint8_t *out) { for (int i = 0; i < g->numEnvs; ++i) out[i] = g->done[i]; }   /* all envs' done flags with one call (full-size parity tests) */
 void mvo_render_env(mvo_gym *g, int env)   /* the frames of ONE env's agents (full-size parity tests sample a few envs: the brute-force raster of all 1024 would take minutes) */

@@ -66,6 +66,25 @@ void mvo_step_norender(mvo_gym *g);
 void mvo_render(mvo_gym *g);
 void mvo_set_raster(mvo_gym *g, int tiled);      /* 1: tile-culled software raster (byte-identical image; bench.py's timing leg), 0 (default): brute force */
 void mvo_render_env(mvo_gym *g, int env_idx);   /* only this env's agents' frames */
+
+/* ---- the float64 reference of the render model: the raster's own code (one template, mv_oracle.cpp: RenderFrame) evaluated in double on the fp32 state
+ * as it stands -- camera through std::sin / std::cos, rays, hit tests, nearest hit, Phong with pow(x, 300), bytes; the model's constants are its own
+ * values (tan 50 deg, 128 / 72, 0.01, 120), not their fp32 roundings.  Brute force, every primitive against every pixel.  Frames are w x h of mvo_create,
+ * rows bottom-up like mvo_get_observation. */
+/* the frame at the pixel centres: out_rgba [h * w * 4], out_prim [h * w]: index of the winning primitive in the frame's draw list, -1 for a miss (may be NULL) */
+void mvo_render_f64(mvo_gym *g, int env_idx, int agent_idx, uint8_t *out_rgba, int32_t *out_prim);
+/* n listed pixels, xy [n][2] = (column, row): every colour an evaluation may show that errs by at most delta_px in where the ray goes and eps_t (relative)
+ * in depth -- at the centre and the eight points +-delta_px from it in x, in y and in both (delta_px = 0: the centre alone), the shaded colour of EVERY
+ * primitive whose hit depth is within t_best (1 + eps_t) of that probe's nearest hit; the background (0, 0, 0, 255) for a probe that hits nothing.
+ * Every probe is evaluated again with the discriminants of the curved primitives' quadratics moved by +-2^-20 of their terms (what fp32 rounding of
+ * B B - A C can do to a grazing hit: mv_oracle.cpp, explain_f64); colours only those evaluations give carry 254 in their fourth byte, all others 255.
+ * out_colors [n][MVO_EXPLAIN_MAX][4]: the distinct colours; out_counts [n]: how many were found (above MVO_EXPLAIN_MAX: the stored list is cut) */
+#define MVO_EXPLAIN_MAX 64
+void mvo_explain_f64(mvo_gym *g, int env_idx, int agent_idx, int n, const int32_t *xy, double delta_px, double eps_t, uint8_t *out_colors,
+                     int32_t *out_counts);
+/* the frame's draw list as (kind, frame) pairs -- kind 1 box, 2 capsule, 3 cone, 4 / 5 / 6 scaled sphere / capsule / cylinder; frame -1 world, k < 8 agent k's
+ * camera, 8 + k hex wall orientation k -- for the indices of out_prim; returns the list's length, writes at most max pairs */
+int mvo_prim_table(mvo_gym *g, int env_idx, int agent_idx, int max, int32_t *out_kind_frame);
 void mvo_get_dones(mvo_gym *g, uint8_t *out);    /* [N] */
 
 int mvo_is_done(mvo_gym *g, int env_idx);

@@ -10,6 +10,7 @@ ORACLE_DIR = os.path.join(ROOT, "oracle")
 
 MAX_BOXES, MAX_OBJECTS, MAX_AGENTS, CHUNK = 1024, 80, 8, 32 * 16 * 32
 MAX_TERRAIN, MAX_REWARDS, MAX_SHAPING, HM_DIM = 16, 96, 8, 42
+EXPLAIN_MAX = 64   # MVO_EXPLAIN_MAX: candidate colours kept per pixel by mvo_explain_f64
 
 SNAP_AGENT = np.dtype([
     ("pos", "<f4", 3), ("basis", "<f4", 4), ("pitch", "<f4"), ("hv", "<f4", 2), ("vvel", "<f4"), ("voffset", "<f4"),
@@ -60,6 +61,11 @@ def lib():
         L.mvo_get_dones.argtypes = [C.c_void_p, C.c_void_p]
         L.mvo_render_env.argtypes = [C.c_void_p, C.c_int]
         L.mvo_set_raster.argtypes = [C.c_void_p, C.c_int]
+        L.mvo_render_f64.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.mvo_render_f64.restype = None
+        L.mvo_explain_f64.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        L.mvo_explain_f64.restype = None
+        L.mvo_prim_table.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.mvo_get_last_rewards.argtypes = [C.c_void_p, C.c_void_p]
         L.mvo_true_objective.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.mvo_true_objective.restype = C.c_float
@@ -149,6 +155,30 @@ class OracleGym:
 
     def render_env(self, env_idx): self.L.mvo_render_env(self.g, int(env_idx))
     def set_raster(self, tiled): self.L.mvo_set_raster(self.g, 1 if tiled else 0)
+
+    def render_f64(self, env_idx, agent_idx):
+        """the float64 reference's frame -> (rgba [h, w, 4] uint8, prim [h, w] int32: the winning primitive's index in the draw list, -1 for a miss)"""
+        rgba = np.zeros((self.h, self.w, 4), np.uint8)
+        prim = np.full((self.h, self.w), -2, np.int32)
+        self.L.mvo_render_f64(self.g, int(env_idx), int(agent_idx), rgba.ctypes.data, prim.ctypes.data)
+        return rgba, prim
+
+    def explain_f64(self, env_idx, agent_idx, xy, delta_px, eps_t):
+        """xy [n, 2] = (column, row) -> (colours [n, EXPLAIN_MAX, 4] uint8, counts [n]): every colour the float64 reference allows at these pixels for an
+        evaluation off by at most delta_px in the ray's screen position and eps_t (relative) in depth; colours[i, :counts[i]] are valid"""
+        xy = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
+        assert ((xy >= 0) & (xy < [self.w, self.h])).all(), "pixel outside the frame"
+        colors = np.zeros((len(xy), EXPLAIN_MAX, 4), np.uint8)
+        counts = np.zeros(len(xy), np.int32)
+        self.L.mvo_explain_f64(self.g, int(env_idx), int(agent_idx), len(xy), xy.ctypes.data, float(delta_px), float(eps_t), colors.ctypes.data, counts.ctypes.data)
+        return colors, counts
+
+    def prim_table(self, env_idx, agent_idx):
+        """the frame's draw list as [n, 2] = (kind, frame) rows, indexed by render_f64's prim"""
+        n = self.L.mvo_prim_table(self.g, int(env_idx), int(agent_idx), 0, None)
+        out = np.zeros((n, 2), np.int32)
+        assert self.L.mvo_prim_table(self.g, int(env_idx), int(agent_idx), n, out.ctypes.data) == n
+        return out
 
     def get_last_rewards(self):
         out = np.zeros(self.num_envs * self.num_agents_per_env, np.float32)

@@ -5,7 +5,8 @@ pixels".  The tolerance, per frame set compared:
     centre lies within rounding of a silhouette edge or of a depth tie between two surfaces;
   * at most PIX_ANY of the pixels may differ at all (a byte that rounds the other way);
   * alpha is always 255.
-Discrete state is untouched by the pixel mode (the step kernels are the same), which the last test checks."""
+Discrete state is untouched by the pixel mode (the step kernels are the same), which the last test checks.
+Where the outliers ARE is judged pixel by pixel against a float64 reference in test_pixel_reference.py / test_pixel_reference_gpu.py (tests/pixel_reference.py)."""
 import numpy as np
 import pytest
 
