@@ -343,6 +343,36 @@ int mv_get_scene_obs(const mv_gym *g);                  /* 0: none, else the num
 int mv_get_scene_observation(mv_gym *g, int32_t env_idx, float *out_host32);   /* last tick's row; waits for the gym's stream */
 int mv_debug_scene_obs_host(int32_t scenario, const void *env_header, const void *terrain16, const void *rewards, int32_t rewards_len,
                             const void *football_state, float *out32);         /* the pack function on the host; unused inputs may be NULL */
+/* Depth observations (no reference counterpart: the reference reads colours back and leaves its depth buffer on the card).  One value per pixel of every frame
+ * an observation pass draws: the ray parameter t of the pixel's nearest hit, the very float the shading works from.  Every ray has the camera-space direction
+ * (x, y, -1) and every primitive frame keeps t, so t is the PLANAR camera-space depth -z_cam in world units, within [0.01, 120]; 0 where the ray hits nothing
+ * (the black background).  A frame's record is ONE plane [H][W] in the frame's own pixel order -- row 0 is the bottom row -- whatever mv_set_obs_layout says.
+ * Formats: MV_DEPTH_F32, the bits of t; MV_DEPTH_F16, t rounded to nearest-even.  megaverse_amd/csrc/mv_depth_obs.h states the rule for kernels and host alike.
+ * The buffer is one more ring beside mv_set_output_ring's three: [entries][N*A][H][W] of float or __half, 4-byte aligned, entries = the output ring's count at
+ * the moment of the call, or 1 without a ring; a frame's plane goes to the entry the frame goes to.  While a buffer is attached mv_set_output_ring is refused.
+ * Which passes: every one that draws frames -- mv_step, every tick of mv_step_n, the last tick of MV_RENDER_LAST and of mv_macro_step(..., MV_RENDER_LAST), the
+ * frame behind mv_reset and mv_reset_envs*(..., render = 1), mv_render.  Where no frame is drawn no byte of the buffer is written: mv_step_no_render,
+ * MV_RENDER_NONE, the undrawn ticks of MV_RENDER_LAST; an env a draw mask leaves out keeps its planes as it keeps its rows.  Forks, resampling, loads and seeds
+ * touch no plane; mv_draw_hires ignores the option.
+ * How: in exact pixel mode the pass itself stores both outputs, one trace and no further launch.  In fast pixel mode (the default) the fast kernels stay what
+ * they are and ONE launch per drawn tick follows the call's passes on the gym's stream (counted in out[1] of mv_debug_launch_counts): the exact trace without
+ * the shading, frames in identity order.  Both forms give the same bits.  With a buffer attached a call's passes are not overlapped with the next call's
+ * (mv_set_pass_overlap stays accepted).  Colours, rewards, dones, rows and the log are those of a gym without a buffer, and a gym that never attaches one
+ * launches exactly what it launched before.
+ * Ordering: mv_set_state_obs's.  The call is an ordering point and never waits on the host; the buffer is the caller's, written in place, and must stay valid
+ * until the caller's stream has passed the end of the last call that writes it.  Attaching again replaces it; NULL detaches.  mv_close forgets the pointer.
+ * Refused (-1 with text): no gym, a closed gym, a gym in an mv_group, an unknown format, a gym with still frames switched on (and mv_set_still_frames while a
+ * buffer is attached: nothing carries a still frame's plane between ring entries); mv_set_output_ring and mv_set_render_resolution while attached;
+ * mv_group_create and mv_step_many refuse a gym that has one attached (the union launches write none).
+ * mv_get_depth_observation: one agent's plane in the LAST TICK's entry, widened to float32, after waiting for the gym's stream -- where that tick drew no
+ * frame (MV_RENDER_NONE, mv_step_no_render) the entry holds what it held: an older tick's plane in a ring, or the caller's bytes.
+ * mv_debug_depth_pack_host: the pack rule on the CPU: n values t with hit[i] != 0 where the ray hit -> n float32 or n half words; no device. */
+enum { MV_DEPTH_F32 = 0, MV_DEPTH_F16 = 1 };
+int mv_set_depth_obs(mv_gym *g, void *device_buf, int32_t format);   /* [max(1, ring count)][N*A][H][W] float / __half in device memory; NULL detaches */
+int mv_get_depth_obs(const mv_gym *g);                               /* 0: none, else the number of entries; -1: no gym */
+int mv_get_depth_format(const mv_gym *g);                            /* MV_DEPTH_*; -1: none attached */
+int mv_get_depth_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, float *out_host);   /* [H][W] float32; waits for the gym's stream */
+int mv_debug_depth_pack_host(const float *t, const uint8_t *hit, int32_t n, int32_t format, void *out);   /* the pack function, on the host */
 /* Episode budgets (no reference counterpart: VectorEnv::step resets a finished env on the spot and steps on, vector_env.cpp:89-108).  Per env e the gym owns an
  * int32 left[e]:  < 0: unlimited -- what every env is without these calls;  > 0: the env may still finish that many episodes;  0: the env is HALTED.
  * Tick t, env e, left[e] as it stands before the tick (megaverse_amd/csrc/mv_episode_budget.h states the rule for kernels and host alike):

@@ -129,6 +129,7 @@ OutPtrs outputs_of(const mv_gym *g, unsigned long long tick)
         if (g->ringRewards) o.rewards = g->ringRewards + r * NA;
         if (g->ringDone) o.done = g->ringDone + r * (size_t)g->N;
     }
+    o.depth = g->depth.entry(tick);   // (mv_set_depth_obs: attached under this ring count, or under none: entry 0)
     return o;
 }
 OutPtrs last_outputs(const mv_gym *g) { return outputs_of(g, g->ringTick ? g->ringTick - 1 : 0); }   // of the last tick (reset / render / getters)
@@ -785,6 +786,7 @@ int mv_close(mv_gym *g)
     g->seedEnvsPair.release();
     env_masks_free(g);
     obs_rows_free(g);
+    g->depth = DepthObs();   // (mv_set_depth_obs: the buffer is the caller's -- forgotten, not freed)
     episode_budget_free(g);
     macro_step_free(g);
     still_frames_free(g);
@@ -956,8 +958,11 @@ int mvapi::render_frames(mv_gym *g)
     GymView v = view(g, g->parity);
     // (not fill_view_options: a pass reads the draw mask alone, and mv_render draws still frames too.  Also the frame behind mv_reset and mv_reset_envs(render = 1))
     v.draw_mask = g->drawMask.live;
-    if (launch_raster(v, last_outputs(g).obs, g->w, g->h, g->stream, nullptr, g->fastPixels))
+    // (mv_set_depth_obs: an exact pass stores the depth planes itself, a fast pass is followed by the depth launch)
+    const OutPtrs o = last_outputs(g);
+    if (launch_raster(v, o.obs, g->w, g->h, g->stream, nullptr, g->fastPixels, 0, nullptr, nullptr, g->fastPixels ? nullptr : o.depth, g->depth.format))
         return fail("mv_render: observation size above 1024x1024");
+    if (g->fastPixels && depth_obs_follow(g, v, o.depth, "mv_render") < 0) return -1;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1300,6 +1305,8 @@ int mv_set_output_ring(mv_gym *g, int32_t count, void *obs, float *rewards, uint
     if (check(g)) return -1;
     if (g->stateRows.buf)   // (the state buffer is one more ring of the count it was attached under)
         return fail("mv_set_output_ring: state observations are attached (mv_set_state_obs), sized by the ring count they were attached under: detach the state observations first");
+    if (g->depth.buf)
+        return fail("mv_set_output_ring: depth observations are attached (mv_set_depth_obs), sized by the ring count they were attached under: detach the depth observations first");
     if (g->sceneRows.buf)
         return fail("mv_set_output_ring: scene observations are attached (mv_set_scene_obs), sized by the ring count they were attached under: detach the scene observations first");
     if (count < 0 || (count > 0 && !obs && !rewards && !dones)) return fail("mv_set_output_ring: count >= 0 and at least one ring required");
@@ -1434,6 +1441,8 @@ int mv_set_render_resolution(mv_gym *g, int32_t w, int32_t h)
 {
     if (check(g)) return -1;
     if (w < 1 || h < 1) return fail("mv_set_render_resolution: bad size");
+    if (g->depth.buf)   // (mv_draw_hires writes no depth: the planes stay those of the observation size they were attached under)
+        return fail("mv_set_render_resolution: depth observations are attached (mv_set_depth_obs), whose planes are of the observation size: detach the depth observations first");
     if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     g->renderW = w; g->renderH = h;
     return 0;

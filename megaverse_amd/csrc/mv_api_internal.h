@@ -11,6 +11,8 @@
 //                     envs' frames out of the observation passes (mv_frame.h: frame_skip)
 //   mv_obs_rows.hip   state and scene observations: attaching the caller's buffers, the staging rows, the one publication launch both records share, their
 //                     refresh (mv_state_obs.h, mv_scene_obs.h: the records)
+//   mv_depth_obs.hip  depth observations: attaching the caller's buffer, the launch behind a pass that gives every drawn frame its depth plane
+//                     (mv_depth_obs.h: the record; mv_raster.hip: the kernels)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 //   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
 //   mv_still_frames.hip  still frames: switching the option, the memset behind calls that change what frames show, the carry launch (mv_still_frames.h: the rule)
@@ -123,6 +125,18 @@ struct ObsRows {
     size_t stageBytes = 0, words = 0;   // words: of one entry, the whole gym's rows
     // tick `tick`'s entry of the caller's buffer: the entry its rewards go to (outputs_of)
     float *entry(unsigned long long tick) const { return buf + (size_t)(tick % (unsigned long long)entries) * words; }
+};
+}  // namespace mvapi
+
+namespace mvapi {
+// The depth planes of a gym (mv_depth_obs.hip).  buf: the caller's [entries][N*A][H][W] buffer of float or __half (null: off; entries: the output ring's count
+// when it was attached, or 1); format: MV_DEPTH_F32 / MV_DEPTH_F16; entryBytes: one entry, the whole gym's planes.
+struct DepthObs {
+    void *buf = nullptr;
+    int format = 0, entries = 0;
+    size_t entryBytes = 0;
+    // tick `tick`'s entry of the caller's buffer: the entry its frames go to (outputs_of)
+    void *entry(unsigned long long tick) const { return buf ? (uint8_t *)buf + (size_t)(tick % (unsigned long long)entries) * entryBytes : nullptr; }
 };
 }  // namespace mvapi
 
@@ -287,6 +301,8 @@ struct mv_gym {
     EnvMask drawMask;
     // mv_set_state_obs, mv_set_scene_obs (ObsRows).  The scene rows' staging is counted in mv_arena_bytes from its allocation on, the state rows' is not.
     ObsRows stateRows, sceneRows;
+    // mv_set_depth_obs: the caller's depth planes, written by the passes of a gym in exact pixel mode and by a launch behind the passes of one in fast mode
+    DepthObs depth;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
     // budgetLeft [N], what the step kernels read and write (GymView::budget, through the stepping calls' views, while budgetOn); budgetHalted, the count of
     // zeros in it; budgetMirror [N], the episode log's own copy, advanced by the log's update tick by tick.  The host form's values travel through a pool of
@@ -330,7 +346,7 @@ struct GymOption {
     const char *memberNone;   // attach_check: "whose union launches <memberNone>"
     bool (*on)(const mv_gym *);
 };
-enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_COUNT };
+enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_DEPTH_OBS, OPT_COUNT };
 #define MV_OPT_ON(expr) +[](const mv_gym *g) -> bool { return expr; }
 inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_step_mask", "a step mask attached", "read none", "detach it first", "detach the mask first", "read no step mask", MV_OPT_ON(g->stepMask.live)},
@@ -339,6 +355,7 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_episode_budget", "an episode budget attached", "read none", "detach it first", "detach the budget first", "read no episode budget", MV_OPT_ON(g->budgetOn)},
     {"mv_set_state_obs", "state observations attached", "write none", "detach them first", "detach them first", "write no state observations", MV_OPT_ON(g->stateRows.buf)},
     {"mv_set_scene_obs", "scene observations attached", "write none", "detach them first", "detach them first", "write no scene observations", MV_OPT_ON(g->sceneRows.buf)},
+    {"mv_set_depth_obs", "depth observations attached", "write none", "detach them first", "detach them first", "write no depth observations", MV_OPT_ON(g->depth.buf)},
 };
 #undef MV_OPT_ON
 // What a stepping call's view of g carries of the options (the rows of the two records are fields of the per-slot views already: mv_gym::gvp); macro: the view
@@ -354,7 +371,8 @@ inline void fill_view_options(GymView &v, const mv_gym *g, bool macro)
 
 // Where a tick's public outputs go: the observation slab and the reward / done arrays -- or, with mv_set_output_ring, entry (tick % count)
 // of the caller's rings.  true_objective is state (only a finishing env records it, vector_env.cpp:96-101): never ringed.
-struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; };
+// depth (mv_set_depth_obs): the entry's depth planes, null with no buffer attached.
+struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; void *depth = nullptr; };
 std::string lower(const char *s);
 int check(mv_gym *g);
 // what every form of a persistent attachment refuses: no gym, a closed one, a member of a group (the union launches read or write none of what opt attaches)
@@ -406,6 +424,9 @@ int step_macro_chunk(mv_gym *g, int k, int kCall, bool draw_last, const MacroCal
 int obs_rows_publish(mv_gym *g, int q0, unsigned long long tick0, int k);
 int obs_rows_refresh(mv_gym *g, const uint8_t *device_mask);
 void obs_rows_free(mv_gym *g);         // mv_close
+// mv_depth_obs.hip: the depth planes of the frames a FAST pass of view v has just drawn into the entry `planes` (OutPtrs::depth), one launch on the caller's
+// stream behind the pass (an exact pass stores them itself: launch_raster's depth argument); -> 1: launched, 0: nothing attached or planes null
+int depth_obs_follow(mv_gym *g, const GymView &v, void *planes, const char *who);
 int render_frames(mv_gym *g);          // mv_render without the state rows' refresh (mv_api.hip; mv_reset_envs refreshes the flagged envs' rows only)
 int episode_budget_seed_mirror(mv_gym *g);   // mv_set_episode_log: the log's mirror from the live array (mv_episode_budget.hip)
 // mv_fork.hip, shared with mv_env_store.hip: what every fork / resample / env-store form refuses (what: "forks", "env stores": for the text about groups)

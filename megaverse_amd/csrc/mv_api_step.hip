@@ -45,7 +45,7 @@ struct StepCall {
     bool drawLast;            // QUIET_LAST: tick k - 1 is drawn
     bool sideWaits;           // (not pipelined) a draw launch, a status read-back or an upload will wait for this call: an event behind the ticks
     bool overlap;             // the one pass launch goes to a pass stream (mv_set_pass_overlap): passOn
-    bool rows, carry;         // followers: the row records' publication, the still frames' carry (the log: per gym, logCapacity)
+    bool rows, carry, depth;  // followers: the row records' publication, the still frames' carry, the depth planes behind fast passes (the log: per gym, logCapacity)
     bool timeCall, timeTicks;   // timing (mv_profile_begin): ONE entry for the whole call (callEv), or one per tick for the first tickEvs ticks (tickEv);
     hipEvent_t *callEv = nullptr, *tickEv = nullptr;   // reserve_timing takes the entries, behind the checks and the refill as always
     int tickEvs = 0;
@@ -128,13 +128,17 @@ struct StepCall {
         // (mv_set_still_frames with an output ring: the calls run in order -- pass c + 1 on its side stream could draw into the entry that carry c, on the
         // caller's stream, is still reading when the ring is exactly two calls deep)
         carry = n == 1 && L->stillOn && L->ringObs != nullptr && (r.render || drawLast);
+        // (mv_set_depth_obs, fast pixels: one depth launch per drawn tick behind the call's passes, reading the tick's frame lists from the call's slots -- an exact
+        // pass stores the planes itself, one_pass; a group's members have none)
+        depth = n == 1 && L->depth.buf != nullptr && L->fastPixels != 0 && (r.render || drawLast);
         // overlapped passes (mv_set_pass_overlap): this call's one launch goes to an internal stream
         // (an env must not finish in two consecutive calls: their passes may publish its true objective in either order -- episodes of at least
         // baseEpisodeLen seconds, 15 ticks each)
         // The ring is two CALLS deep, in the caller's ticks per call (a call of 16 ticks runs as two chunks of 8: the second-next chunk's passes would overwrite
         // what the consumer of the previous CALL -- enqueued after both of its chunks -- may still be reading), and rewards / dones have rings of
         // their own (two passes in flight would both publish the single arrays, in either order).
-        overlap = pass == PASS_BATCH && own && !timeCall && !carry && L->passOverlap && L->passStream[0]
+        // (no depth follower either: its reads of the call's slots and the next call's reuse of them stay ordered by the mark on the caller's stream)
+        overlap = pass == PASS_BATCH && own && !timeCall && !carry && !depth && L->passOverlap && L->passStream[0]
                 && L->ringCount >= 2 * std::max(k, r.kCall) && L->ringRewards && L->ringDone && L->baseEpisodeLen * 15.0f > float(2 * k + 2);
         views.resize((size_t)n * k); outs.resize((size_t)n * k);
         return 0;
@@ -371,9 +375,10 @@ struct StepCall {
 
     // ... then publication and passes, by pass path.  One gym's pass of one tick, its lists set up inside the step launch (a fast pass whose view says
     // lpt_no_clear leaves its cost histogram zero: self_clear, mv_raster.hip):
-    int one_pass(mv_gym *g, const GymView &v, uint32_t *obs, hipEvent_t between, const PublishTo *pub, hipEvent_t done, const char *who)
+    // (mv_set_depth_obs: an EXACT pass stores the tick's depth planes itself -- planes: OutPtrs::depth of the tick; a fast pass gets none, followers_and_mark)
+    int one_pass(mv_gym *g, const GymView &v, uint32_t *obs, hipEvent_t between, const PublishTo *pub, hipEvent_t done, const char *who, void *planes = nullptr)
     {
-        if (launch_raster(v, obs, L->w, L->h, L->stream, between, g->fastPixels, /*setup_done=*/1, pub, done))
+        if (launch_raster(v, obs, L->w, L->h, L->stream, between, g->fastPixels, /*setup_done=*/1, pub, done, g->fastPixels ? nullptr : planes, g->depth.format))
             return fail(std::string(who) + ": observation size above 1024x1024");
         ++L->launchCount[1];
         if (v.lpt_no_clear && g->fastPixels) g->histClean[(size_t)v.lpt_parity] = 1;
@@ -403,7 +408,8 @@ struct StepCall {
                 ++L->launchCount[1];
             } else
                 for (int i = 0; i < n; ++i)
-                    if (one_pass(gs[i], vj[i], obsPtrs[i], e && i == 0 ? e[3] : nullptr, pubInRaster ? &pubs[i] : nullptr, i == n - 1 ? done : nullptr, "mv_step")) return -1;
+                    if (one_pass(gs[i], vj[i], obsPtrs[i], e && i == 0 ? e[3] : nullptr, pubInRaster ? &pubs[i] : nullptr, i == n - 1 ? done : nullptr, "mv_step",
+                                 outs[(size_t)j * n + i].depth)) return -1;
             if (e) HIP_TRY(hipEventRecord(e[4], L->stream));
         }
         return 0;
@@ -456,7 +462,7 @@ struct StepCall {
     {
         const int q0 = L->group * L->batch;
         if (staged && (r.mc ? publish_macro(L, q0, outs[0], k, !r.mc->first) : publish_ticks(L, q0, outs.data(), n, k))) return -1;
-        if (drawLast) return one_pass(L, views[(size_t)k - 1], outs[(size_t)k - 1].obs, nullptr, nullptr, mark(), "mv_step_n_render");
+        if (drawLast) return one_pass(L, views[(size_t)k - 1], outs[(size_t)k - 1].obs, nullptr, nullptr, mark(), "mv_step_n_render", outs[(size_t)k - 1].depth);
         if (own) HIP_TRY(hipEventRecord(mark(), L->stream));
         return 0;
     }
@@ -487,8 +493,16 @@ struct StepCall {
             if (still_frames_carry(L, views.data() + first, outs.data() + first, 1, k - first)) return -1;
             ++L->launchCount[1];
         }
+        // the depth planes behind fast passes (mv_set_depth_obs): one launch per drawn tick, the exact trace without the shading over the tick's frame lists in
+        // the call's slots, into the entry the tick's frames went to
+        if (depth)
+            for (int j = r.render ? 0 : k - 1; j < k; ++j) {
+                const int rc = depth_obs_follow(L, views[(size_t)j], outs[(size_t)j].depth, "mv_step");
+                if (rc < 0) return -1;
+                L->launchCount[1] += rc;
+            }
         if (mc && mc->last) ++L->ringTick;
-        if ((anyLog || rows || carry) && own) HIP_TRY(hipEventRecord(mark(), L->stream));
+        if ((anyLog || rows || carry || depth) && own) HIP_TRY(hipEventRecord(mark(), L->stream));
         if (own) {
             ++L->markCount;
             for (int i = 0; i < n; ++i) gs[i]->markCount = L->markCount;

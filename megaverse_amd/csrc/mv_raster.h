@@ -15,8 +15,15 @@ namespace mv {
 struct PublishTo { float *rewards; uint8_t *done; float *true_objective; };
 // done: an event that completes when the pass does.  The fast kernels carry it as the completion signal of their own dispatch packet
 // (hipExtLaunchKernelGGL's stop event) -- a separate hipEventRecord is one more packet the queue works off between two passes, ~5 us.
+// depth (mv_set_depth_obs; fast = 0 only, null: none): the gym's depth entry [N*A][H][W] in depth_format (mv_depth_obs.h) -- the exact pass becomes the
+// instantiation that stores the nearest hit's t beside the colours: one trace, two outputs, no further launch.  A fast pass stores no depth: its kernels stay
+// what they are, and the caller follows it with launch_raster_depth.
 int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t stream, hipEvent_t between = nullptr, int fast = 1, int setup_done = 0,
-                  const PublishTo *publish = nullptr, hipEvent_t done = nullptr);
+                  const PublishTo *publish = nullptr, hipEvent_t done = nullptr, void *depth = nullptr, int depth_format = 0);
+
+// The depth planes of every frame of gv -- its lists already set up -- with one launch of the exact kernel's depth-only form: the trace and the depth store,
+// no shading.  Frames in identity order; an undrawn or still frame (mv_frame.h: frame_skip) writes nothing.  -1: W / H too large, no plane, unknown format.
+int launch_raster_depth(const GymView &gv, void *depth, int depth_format, int W, int H, hipStream_t stream);
 
 // the fast observation pass of n gyms of one job (frame lists already built by their step kernels) with at most two launches; publish: n
 // entries or null; -1 if W / H / n are too large

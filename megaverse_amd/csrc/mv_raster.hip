@@ -40,6 +40,7 @@
 #include <stdio.h>
 
 #include "../../include/megaverse_hip.h"
+#include "mv_depth_obs.h"
 #include "mv_frame.h"
 #include "mv_math.h"
 #include "mv_raster.h"
@@ -459,13 +460,37 @@ __device__ __forceinline__ void put_px(const PixOutT<true> &po, int px, int py, 
     }
 }
 
+// What the exact kernel's body leaves behind (mv_depth_obs.h: the depth record).  OUT_RGB: the frame's colours -- raster_kernel, as it always was.
+// OUT_RGBD: the same bytes, and the nearest hit's t of every pixel in the frame's depth plane: one trace, two outputs.  OUT_DEPTH: the trace and the depth
+// store alone -- no normal, no Phong, no colour tables (raster_depth_kernel).
+enum : int { OUT_RGB = 0, OUT_RGBD = 1, OUT_DEPTH = 2 };
+
+// One pixel's depth value into its frame's plane [H][W] (the RGBA store's bounds: px < W && py < H).  Every lane of the wave takes part -- the callers reach
+// this in wave-uniform control flow, the stores are masked after the exchange.  DEPTH_F16, W even: a plane row starts dword-aligned and neighbouring lanes own
+// neighbouring columns (a tile row is 16 lanes and starts at a multiple of 16 pixels), so the even lane takes its neighbour's half (quad_perm [1,0,3,2]) and
+// stores both as ONE dword; px even and W even mean px + 1 < W wherever px < W.  W odd: rows start at either half of a dword -- every lane stores its two bytes.
+__device__ __forceinline__ void put_depth(void *plane, int format, int W, int H, int px, int py, float t, bool hit)
+{
+    const bool in = px < W && py < H;
+    const size_t at = (size_t)py * W + px;
+    if (format == DEPTH_F16) {   // (uniform)
+        const unsigned mine = depth_bits_f16(t, hit);
+        if ((W & 1) == 0) {   // (uniform)
+            const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)mine, 0xb1, 0xf, 0xf, false);
+            if (in && (px & 1) == 0) reinterpret_cast<uint32_t *>(plane)[at >> 1] = mine | (other << 16);
+        } else if (in) reinterpret_cast<uint16_t *>(plane)[at] = (uint16_t)mine;
+    } else if (in) reinterpret_cast<uint32_t *>(plane)[at] = depth_bits_f32(t, hit);
+}
+
 }  // namespace
 
+// The exact observation pass of one frame part: tile cull, nearest hit with the draw-order tie rule, Phong.  OUT: what it stores (above); depth / depth_format:
+// the gym's depth entry (frame f's plane at f W H values) and its format, read where OUT != OUT_RGB; order: null (OUT != OUT_RGB only): position = frame.
 // CHW: the planar layout (mv_set_obs_layout; PixOutT above)
-template <int MAXVIS, bool SHAPES, bool CHW = false>   // SHAPES: the frame may hold scaled spheres / capsules / cylinders (Rearrange)
-__global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : MAXVIS <= 256 ? 5 : MAXVIS <= 1024 ? 2
-                             : 1) void raster_kernel(GymView gv, uint32_t *obs, int W, int H, int split, const int *order)
+template <int MAXVIS, bool SHAPES, bool CHW, int OUT>   // SHAPES: the frame may hold scaled spheres / capsules / cylinders (Rearrange)
+__device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, void *depth, int depth_format, int W, int H, int split, const int *order)
 {
+    constexpr bool RGB = OUT != OUT_DEPTH, DEPTH = OUT != OUT_RGB;
     constexpr int ROUNDS = MAXVIS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];   // column/row ray tables
     __shared__ Prim s_vis[MAXVIS];       // this frame's visible list
@@ -490,7 +515,8 @@ __global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : M
         const int frames = gridDim.x / split;
         if (group * 8 + 8 > frames) { const int b = blockIdx.x - group * per; const int nf = frames - group * 8; frame = group * 8 + b % nf; part = b / nf; }
     }
-    frame = order[frame];   // `frame` so far was a position in the cost-sorted order (most expensive first)
+    if constexpr (!DEPTH) frame = order[frame];   // `frame` so far was a position in the cost-sorted order (most expensive first)
+    else if (order) frame = order[frame];         // (the depth modes accept no order: position = frame)
     const int env = frame / A, viewer = frame - env * A;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
@@ -529,10 +555,12 @@ __global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : M
         for (int i = tid; i < nVis * 2; i += 256) dst[i] = src[i];
         const short4 *rs = reinterpret_cast<const short4 *>(gv.vis_rects) + (size_t)frame * gv.vis_stride;
         for (int i = tid; i < nVis; i += 256) s_rect[i] = rs[i];
-        const float AMB = float(0x55) / 255.0f, DIF = float(0xbb) / 255.0f, LCOL = float(0xaa) / 255.0f;
-        const float c = float(tid) / 255.0f;
-        s_lutA[tid] = AMB * c;
-        s_lutD[tid] = (DIF * c) * LCOL;
+        if constexpr (RGB) {
+            const float AMB = float(0x55) / 255.0f, DIF = float(0xbb) / 255.0f, LCOL = float(0xaa) / 255.0f;
+            const float c = float(tid) / 255.0f;
+            s_lutA[tid] = AMB * c;
+            s_lutD[tid] = (DIF * c) * LCOL;
+        }
     }
     __syncthreads();   // cameras (incl. origin), ray tables, list, colour tables complete
 
@@ -541,7 +569,8 @@ __global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : M
     const int tilesX = (W + TILE_W - 1) / TILE_W, tilesY = (H + TILE_H * PPL - 1) / (TILE_H * PPL);
     const int numTiles = tilesX * tilesY;
     const float LIGHT[3] = {0.0f, 4.0f, 2.0f};
-    uint32_t *out = obs + (size_t)frame * W * H;
+    uint32_t *out = RGB ? obs + (size_t)frame * W * H : nullptr;   // (depth only: no colour slab)
+    void *plane = DEPTH ? reinterpret_cast<unsigned char *>(depth) + (size_t)frame * depth_plane_bytes(W, H, depth_format) : nullptr;   // (this frame's depth plane)
 
     const float nzm[3] = {-cam.c[2], -cam.c[5], -cam.c[8]};   // c_k2 * (-1)
 
@@ -574,8 +603,11 @@ __global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : M
         if (anyMask == 0ull) {   // nothing can be seen through this tile: clear colour (0,0,0), alpha 255
 #pragma unroll
             for (int k = 0; k < PPL; ++k) {
-                if constexpr (CHW) put_px(frame_out<true>(obs, frame, W, H, false), px, pyBase + TILE_H * k, 0xff000000u);
-                else if (px < W && pyBase + TILE_H * k < H) out[(size_t)(pyBase + TILE_H * k) * W + px] = 0xff000000u;
+                if constexpr (RGB) {
+                    if constexpr (CHW) put_px(frame_out<true>(obs, frame, W, H, false), px, pyBase + TILE_H * k, 0xff000000u);
+                    else if (px < W && pyBase + TILE_H * k < H) out[(size_t)(pyBase + TILE_H * k) * W + px] = 0xff000000u;
+                }
+                if constexpr (DEPTH) put_depth(plane, depth_format, W, H, px, pyBase + TILE_H * k, 0.0f, false);
             }
             continue;
         }
@@ -640,6 +672,9 @@ __global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : M
         // ---- Phong (Magnum Shaders::Phong, uniforms of magnum_env_renderer.cpp:200-203)
 #pragma unroll
         for (int k = 0; k < PPL; ++k) {
+            const int py = pyBase + TILE_H * k;
+            if constexpr (DEPTH) put_depth(plane, depth_format, W, H, px, py, best[k], bestPos[k] >= 0);   // best[k]: the float the shading works from
+            if constexpr (!RGB) continue;
             unsigned rgba = 0xff000000u;
             if (bestPos[k] >= 0) {
                 const Prim &q = s_vis[bestPos[k]];
@@ -693,11 +728,36 @@ __global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : M
                 }
                 rgba = ch[0] | (ch[1] << 8) | (ch[2] << 16) | 0xff000000u;
             }
-            const int py = pyBase + TILE_H * k;
             if constexpr (CHW) put_px(frame_out<true>(obs, frame, W, H, false), px, py, rgba);
             else if (px < W && py < H) out[(size_t)py * W + px] = rgba;
         }
     }
+}
+
+// The exact observation pass (mv_set_pixel_mode exact): raster_body's colours.
+template <int MAXVIS, bool SHAPES, bool CHW = false>
+__global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : MAXVIS <= 256 ? 5 : MAXVIS <= 1024 ? 2
+                             : 1) void raster_kernel(GymView gv, uint32_t *obs, int W, int H, int split, const int *order)
+{
+    raster_body<MAXVIS, SHAPES, CHW, OUT_RGB>(gv, obs, nullptr, 0, W, H, split, order);
+}
+
+// Waves per SIMD the depth kernels are built for: the occupancy the compiler reports for them when built WITHOUT a bound (min waves 1).  The figures of that
+// unbounded build: depth only 51 / 58 VGPRs with the short lists (plain / scaled shapes) -- 8 waves; the long lists are bound by their LDS (3 waves, 1 wave) at 54 /
+// 68 VGPRs.  Colours + depth: 69..73 / 76..77 VGPRs with the short lists -- 7 waves, 6 with the scaled shapes; the long lists again by their LDS.  Built WITH these
+// bounds -- the library's build, the table of profiles/depth_obs_resources.txt -- the depth-only kernels take 52 / 59 / 53 / 68 VGPRs at the same occupancies.
+constexpr int depth_waves(int maxvis, bool shapes, bool depthOnly)
+{
+    return maxvis > 1024 ? 1 : maxvis > 256 ? 3 : depthOnly ? 8 : shapes ? 6 : 7;
+}
+
+// Depth observations (mv_set_depth_obs): the exact pass with a depth plane beside the colours (DEPTH_ONLY = false: the pass of a gym in exact pixel mode, one
+// trace for both outputs) or with the depth plane alone (DEPTH_ONLY = true: the follower behind a fast pass, whose kernels stay what they are).
+template <int MAXVIS, bool SHAPES, bool DEPTH_ONLY, bool CHW = false>
+__global__ __launch_bounds__(256, depth_waves(MAXVIS, SHAPES, DEPTH_ONLY)) void raster_depth_kernel(GymView gv, uint32_t *obs, void *depth, int depth_format,
+                                                                                                   int W, int H, int split, const int *order)
+{
+    raster_body<MAXVIS, SHAPES, CHW, DEPTH_ONLY ? OUT_DEPTH : OUT_RGBD>(gv, obs, depth, depth_format, W, H, split, order);
 }
 
 // =====================================================================================================================
@@ -2868,11 +2928,38 @@ int launch_raster_batch(const GymView *views, uint32_t *const *obs, const Publis
     return 0;
 }
 
+// The exact branch's choice of variant and of workgroups per frame, stated once for raster_kernel and both forms of raster_depth_kernel.
+static int exact_split(int W, int H)
+{
+    const int tiles = ((W + TILE_W - 1) / TILE_W) * ((H + TILE_H * PPL - 1) / (TILE_H * PPL));
+    int split = 4;
+    while (split > 1 && tiles < 4 * split * 2) split >>= 1;   // keep at least two tiles per wave
+    return split;
+}
+static size_t exact_dyn_lds(int W, int H) { return (size_t)(W + H) * sizeof(float4) + (size_t)(W + H) * sizeof(float); }
+// pick(<MAXVIS>, <SHAPES>) -> the kernel for gv's lists: <= 256 visible primitives, + scaled shapes (Rearrange, Football), <= 1024 (Collect), <= 2048 + shapes (Hex*)
+template <class Pick>
+static auto by_list(const GymView &gv, Pick pick)
+{
+    const bool hexScen = gv.scenario == SCN_HEX_MEMORY || gv.scenario == SCN_HEX_EXPLORE, shapes = gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL;
+    return hexScen ? pick(std::integral_constant<int, VIS_XL>{}, std::true_type{}) : gv.vis_stride > VIS_SMALL ? pick(std::integral_constant<int, VIS_LARGE>{}, std::false_type{})
+         : shapes ? pick(std::integral_constant<int, VIS_SMALL>{}, std::true_type{}) : pick(std::integral_constant<int, VIS_SMALL>{}, std::false_type{});
+}
+
+int launch_raster_depth(const GymView &gv, void *depth, int depth_format, int W, int H, hipStream_t stream)
+{
+    if (W > MAX_W || H > MAX_H || !depth || !depth_format_known(depth_format)) return -1;
+    const int frames = gv.num_envs * gv.num_agents, split = exact_split(W, H);
+    const auto fn = by_list(gv, [](auto maxvis, auto shapes) { return raster_depth_kernel<decltype(maxvis)::value, decltype(shapes)::value, true>; });
+    hipLaunchKernelGGL(fn, dim3(frames * split), dim3(256), exact_dyn_lds(W, H), stream, gv, (uint32_t *)nullptr, depth, depth_format, W, H, split, (const int *)nullptr);
+    return 0;
+}
+
 int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t stream, hipEvent_t between,
-                  int fast, int setup_done, const PublishTo *publish, hipEvent_t done)
+                  int fast, int setup_done, const PublishTo *publish, hipEvent_t done, void *depth, int depth_format)
 {
     if (W > MAX_W || H > MAX_H) return -1;
-    const int tiles = ((W + TILE_W - 1) / TILE_W) * ((H + TILE_H * PPL - 1) / (TILE_H * PPL));
+    if (!fast && depth && !depth_format_known(depth_format)) return -1;   // (before anything is enqueued; mv_set_depth_obs lets no other format through)
     const int frames = gv.num_envs * gv.num_agents;
     if (!setup_done) hipLaunchKernelGGL(gv.draw_mask ? frame_setup_kernel<true> : frame_setup_kernel<false>, dim3(frames), dim3(256), 0, stream, gv, W, H);
     if (!fast) hipLaunchKernelGGL(frame_order_kernel, dim3(1), dim3(1024), 0, stream, gv, frames, gv.lpt_order);   // (fast: no sort kernel)
@@ -2924,17 +3011,20 @@ int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t st
         launch_done(fn, dim3(frames * split), dim3(256), dyn, stream, done, fa, obs, W, H, split);
         return 0;
     }
-    const size_t dyn = (size_t)(W + H) * sizeof(float4) + (size_t)(W + H) * sizeof(float);
-    int split = 4;
-    while (split > 1 && tiles < 4 * split * 2) split >>= 1;   // keep at least two tiles per wave
+    const size_t dyn = exact_dyn_lds(W, H);
+    const int split = exact_split(W, H);
     const dim3 grid(frames * split), block(256);
-    const bool hexScen = gv.scenario == SCN_HEX_MEMORY || gv.scenario == SCN_HEX_EXPLORE, shapes = gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL;
-    const auto fn = by_layout(gv.obs_layout, [&](auto chw) {
-        constexpr bool C = decltype(chw)::value;
-        return hexScen ? raster_kernel<VIS_XL, true, C> : gv.vis_stride > VIS_SMALL ? raster_kernel<VIS_LARGE, false, C>
-             : shapes ? raster_kernel<VIS_SMALL, true, C> : raster_kernel<VIS_SMALL, false, C>;
-    });
-    launch_done(fn, grid, block, dyn, stream, nullptr, gv, obs, W, H, split, (const int *)gv.lpt_order);
+    if (depth) {   // (mv_set_depth_obs: one trace, two outputs)
+        const auto fn = by_layout(gv.obs_layout, [&](auto chw) {
+            return by_list(gv, [](auto maxvis, auto shapes) { return raster_depth_kernel<decltype(maxvis)::value, decltype(shapes)::value, false, decltype(chw)::value>; });
+        });
+        launch_done(fn, grid, block, dyn, stream, nullptr, gv, obs, depth, depth_format, W, H, split, (const int *)gv.lpt_order);
+    } else {
+        const auto fn = by_layout(gv.obs_layout, [&](auto chw) {
+            return by_list(gv, [](auto maxvis, auto shapes) { return raster_kernel<decltype(maxvis)::value, decltype(shapes)::value, decltype(chw)::value>; });
+        });
+        launch_done(fn, grid, block, dyn, stream, nullptr, gv, obs, W, H, split, (const int *)gv.lpt_order);
+    }
     if (done) (void)hipEventRecord(done, stream);
     return 0;
 }

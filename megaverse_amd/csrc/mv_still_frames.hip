@@ -139,6 +139,8 @@ int mv_set_still_frames(mv_gym *g, int32_t on)
         g->simMustWaitUser = true;
         return 0;
     }
+    if (g->depth.buf)   // (a still frame's rows are carried from the entry that holds them; nothing carries its depth plane)
+        return fail("mv_set_still_frames: depth observations are attached (mv_set_depth_obs), and a still frame's depth plane would not be carried: detach the depth observations first");
     HIP_TRY(hipSetDevice(g->device));
     if (still_alloc(g)) return -1;
     // Every env stale, no frame has a home: on the caller's stream, behind every step launch enqueued so far; the next step launch waits for it.  This call is

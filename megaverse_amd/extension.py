@@ -110,7 +110,52 @@ SYMBOLS = [
     ("mv_debug_macro_rule_host", C.c_int, [_P, _P, _P, _P, _I, _I, _P, _P, _P]), ("mv_debug_macro_fold_host", C.c_int, [_P, _I, _I, _P]),
     ("mv_set_still_frames", C.c_int, [_P, _I]), ("mv_get_still_frames", C.c_int, [_P]),
     ("mv_debug_still_rule_host", C.c_int, [_P, _P, _P, _P, _I, _I, _P, _P]), ("mv_debug_still_carry_host", C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    ("mv_set_depth_obs", C.c_int, [_P, _P, _I]), ("mv_get_depth_obs", C.c_int, [_P]), ("mv_get_depth_format", C.c_int, [_P]),
+    ("mv_get_depth_observation", C.c_int, [_P, _I, _I, _P]), ("mv_debug_depth_pack_host", C.c_int, [_P, _P, _I, _I, _P]),
 ]
+
+# include/megaverse_hip.h: the formats of a depth plane (mv_set_depth_obs), torch dtype name -> MV_DEPTH_*
+MV_DEPTH_F32, MV_DEPTH_F16 = 0, 1
+DEPTH_FORMATS = {"float32": MV_DEPTH_F32, "float16": MV_DEPTH_F16}
+
+
+def depth_format_of(dtype):
+    """a torch dtype, a numpy dtype or its name ('float32', 'float16', 'torch.float16', np.float16 ...) -> MV_DEPTH_F32 / MV_DEPTH_F16 (ValueError otherwise)"""
+    name = getattr(dtype, "__name__", None) if isinstance(dtype, type) else None
+    name = (name or str(dtype)).replace("torch.", "").replace("half", "float16")
+    if name not in DEPTH_FORMATS:
+        raise ValueError(f"set_depth_obs: dtype must be float32 or float16, got {dtype!r}")
+    return DEPTH_FORMATS[name]
+
+
+def debug_depth_pack_host(t, hit, fmt):
+    """mv_debug_depth_pack_host: the pack rule of a depth plane on the CPU (no device): float32 t [n], hit [n] (non-zero: the ray hit) -> numpy float32 [n]
+    (MV_DEPTH_F32) or float16 [n] (MV_DEPTH_F16), 0 where nothing was hit"""
+    lib = load_library()
+    t = np.ascontiguousarray(t, np.float32).ravel()
+    hit = np.ascontiguousarray(hit, np.uint8).ravel()
+    if t.size != hit.size:
+        raise ValueError("debug_depth_pack_host: t and hit differ in length")
+    out = np.empty(t.size, np.float16 if int(fmt) == MV_DEPTH_F16 else np.float32)
+    if lib.mv_debug_depth_pack_host(t.ctypes.data, hit.ctypes.data, int(t.size), int(fmt), out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
+
+def check_depth_obs(buf, entries, num_frames, h, w, fmt, device):
+    """the argument check of MegaverseGym.set_depth_obs for a tensor: contiguous torch.float32 / torch.float16 (as fmt says) of shape (entries, num_frames, h,
+    w) on CUDA device `device`; entries None: any number of entries (the check made before the gym is asked for its ring count)"""
+    got = tuple(getattr(buf, 'shape', ()))
+    shape = ((got[0] if len(got) == 4 else 1) if entries is None else int(entries), int(num_frames), int(h), int(w))
+    want = 'torch.float16' if int(fmt) == MV_DEPTH_F16 else 'torch.float32'
+    contiguous = getattr(buf, 'is_contiguous', None)
+    dev = getattr(buf, 'device', None)
+    index = getattr(dev, 'index', None)
+    if not hasattr(buf, 'data_ptr') or got != shape or str(getattr(buf, 'dtype', None)) != want \
+            or not getattr(buf, 'is_cuda', False) or not (callable(contiguous) and contiguous()) or (index is not None and int(index) != int(device)):
+        raise ValueError(f'set_depth_obs: the buffer must be a contiguous {want[6:]} CUDA tensor of shape {shape} on device {int(device)}, '
+                         f"got {getattr(buf, 'dtype', type(buf).__name__)} {tuple(getattr(buf, 'shape', ()))} on {dev if dev is not None else 'no device'}")
+    return buf
 
 # include/megaverse_hip.h: MV_STATE_OBS_FLOATS and the columns of a state-observation row (mv_set_state_obs), name -> index
 MV_STATE_OBS_FLOATS = 16
@@ -759,6 +804,7 @@ class MegaverseGym:
         self._draw_mask_held = None  # set_draw_mask: the caller's device mask, kept until it is replaced or detached
         self._state_obs = None       # set_state_obs: the attached tensor
         self._scene_obs = None       # set_scene_obs: the attached tensor
+        self._depth_obs = None       # set_depth_obs: the attached tensor
         self._ring_ticks = 0         # ticks stepped through this object since set_output_ring (the library's own count: which entry the last tick went to)
         self._macro_held = None      # macro_step: the caller's device tensors of the last call, read in stream order: kept until the next macro step
         self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
@@ -1131,6 +1177,52 @@ class MegaverseGym:
         """-> numpy float32 [32]: the last tick's row of one env (waits for the gym's stream)"""
         out = np.empty(MV_SCENE_OBS_FLOATS, np.float32)
         self._ck(self._lib.mv_get_scene_observation(self._g, int(env_idx), out.ctypes.data))
+        return out
+
+    def set_depth_obs(self, buf=True, dtype=None):
+        """Depth observations (include/megaverse_hip.h: mv_set_depth_obs): every frame a later observation pass draws -- step, every tick of step_n, the last
+        tick of render='last' and of macro_step(render='last'), the frame behind reset and reset_envs(render=True), render -- leaves its per-pixel camera
+        depth (planar, world units, 0: no surface; row 0 is the bottom row) in entry t % entries of a CUDA tensor [entries, num_envs * num_agents, H, W] of
+        float32 or float16, entries = the output ring's count, or 1 without a ring: the entry the frame goes to.  True allocates the tensor on the gym's
+        device and returns it, in dtype (torch.float32, the default, or torch.float16; their names are accepted too); a tensor is checked (ValueError) and
+        attached -- its own dtype decides the format; None detaches.  Nothing waits on the host.
+        While attached, set_output_ring, set_render_resolution and set_still_frames(True) are refused."""
+        if buf is None:
+            self._ck(self._lib.mv_set_depth_obs(self._g, None, MV_DEPTH_F32))
+            self._depth_obs = None
+            return None
+        frames = self.num_envs * self.num_agents_per_env
+        if dtype is None:   # (the default: torch.float32, named without importing torch where nothing is allocated)
+            dtype = "float32"
+        fmt = depth_format_of(dtype if buf is True else getattr(buf, 'dtype', dtype))
+        if buf is not True:
+            check_depth_obs(buf, None, frames, self.h, self.w, fmt, self.device)   # (what needs no gym first)
+        entries = max(1, self._ck(self._lib.mv_get_output_ring(self._g)))
+        if buf is True:
+            import torch
+            buf = torch.zeros((entries, frames, self.h, self.w), dtype=torch.float16 if fmt == MV_DEPTH_F16 else torch.float32, device=f'cuda:{self.device}')
+        else:
+            check_depth_obs(buf, entries, frames, self.h, self.w, fmt, self.device)
+        self._ck(self._lib.mv_set_depth_obs(self._g, _P(int(buf.data_ptr())), fmt))
+        self._depth_obs = buf
+        return buf
+
+    def depth_obs_ring(self):
+        """-> the tensor set_depth_obs attached, [entries, num_envs * num_agents, H, W] (entry t % entries: the planes of tick t's frames), or None"""
+        return self._depth_obs
+
+    def depth_obs(self):
+        """-> the entry of the last tick, (num_envs * num_agents, H, W): a view of the attached tensor, valid in the order of the gym's stream; None with
+        nothing attached.  A tick that drew no frame wrote nothing there.  With an output ring: the entry the last tick stepped through this object went to"""
+        if self._depth_obs is None:
+            return None
+        entries = int(self._depth_obs.shape[0])
+        return self._depth_obs[(max(1, self._ring_ticks) - 1) % entries]
+
+    def get_depth_observation(self, env_idx, agent_idx):
+        """-> numpy float32 [H, W]: the depth plane of one agent in the last tick's entry, float16 widened (waits for the gym's stream)"""
+        out = np.empty((self.h, self.w), np.float32)
+        self._ck(self._lib.mv_get_depth_observation(self._g, int(env_idx), int(agent_idx), out.ctypes.data))
         return out
 
     def get_state_observation(self, env_idx, agent_idx):

@@ -69,7 +69,7 @@ def check_sequence_actions(actions, num_agents):
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
                  img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1,
-                 still_frames=False, scene_obs=False):
+                 still_frames=False, scene_obs=False, depth_obs=False):
         if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
         # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
@@ -121,6 +121,13 @@ class MegaverseEnv:
         self._scene_on = bool(scene_obs)
         if self._scene_on:
             self.env.set_scene_obs(True)
+        # depth_obs (True: float32, "float16"): every drawn frame leaves its per-pixel camera depth in a CUDA tensor (mv_set_depth_obs), read with
+        # self.depth_obs(); the gym observation space stays the RGB one
+        if depth_obs is not False and depth_obs is not True and depth_obs not in ("float16", "float32"):
+            raise ValueError(f"depth_obs must be False, True or 'float16', got {depth_obs!r}")
+        self._depth_dtype = None if depth_obs is False else "float32" if depth_obs is True else depth_obs
+        if self._depth_dtype:
+            self.env.set_depth_obs(True, self._depth_dtype)
         self.default_shaping_scheme = self.env.get_reward_shaping(0, 0)
         self.action_space = self.generate_action_space(self.env.action_space_sizes())
         self.observation_space = spaces.Box(0, 255, (self.channels, self.img_h, self.img_w), dtype=np.uint8)
@@ -154,6 +161,16 @@ class MegaverseEnv:
             raise RuntimeError("scene_obs: create the env with scene_obs=True")
         return buf[self._seq[0][0] - 1 if self._seq is not None else 0]
 
+    def depth_obs(self):
+        """the last tick's depth planes: float32 or float16 (num_envs, num_agents_per_env, H, W) on the device -- planar camera depth in world units, 0 where a
+        ray hits nothing, row 0 the bottom row -- a view of the attached buffer, under state_obs()'s rules: ask again after every call.  A tick that drew no
+        frame wrote nothing.  Needs MegaverseEnv(..., depth_obs=True | "float16")."""
+        buf = self.env.depth_obs_ring()
+        if buf is None:
+            raise RuntimeError("depth_obs: create the env with depth_obs=True")
+        entry = buf[self._seq[0][0] - 1 if self._seq is not None else 0]
+        return entry.view(self.num_envs, self.num_agents_per_env, self.img_h, self.img_w)
+
     def _set_output_ring(self, count, *ptrs):
         """the env's own output rings change (step_device, step_sequence): the state buffer is one more ring of the same depth and the library refuses a ring
         change while it is attached, so it is detached around the change and a buffer of the new depth attached"""
@@ -161,7 +178,11 @@ class MegaverseEnv:
             self.env.set_state_obs(None)
         if self._scene_on:
             self.env.set_scene_obs(None)
+        if self._depth_dtype:
+            self.env.set_depth_obs(None)
         self.env.set_output_ring(count, *ptrs)
+        if self._depth_dtype:
+            self.env.set_depth_obs(True, self._depth_dtype)
         if self._state_on:
             self.env.set_state_obs(True)
         if self._scene_on:

@@ -178,6 +178,11 @@ class MultiTaskGym:
         raise RuntimeError("MultiTaskGym.set_draw_mask: mv_group_create and mv_step_many refuse a gym with a draw mask attached "
                            "(mv_set_draw_mask): the union launches read none; step such a gym on its own")
 
+    def set_depth_obs(self, buf=True, dtype=None):
+        """depth observations (MegaverseGym.set_depth_obs) are per gym: a group's union launches write none, and the library refuses"""
+        raise RuntimeError("MultiTaskGym.set_depth_obs: mv_group_create and mv_step_many refuse a gym with depth observations attached "
+                           "(mv_set_depth_obs): the union launches write none; step such a gym on its own")
+
     def set_state_obs(self, buf=True):
         """state observations (MegaverseGym.set_state_obs) are per gym: a group's union launches write none, and the library refuses"""
         raise RuntimeError("MultiTaskGym.set_state_obs: mv_group_create and mv_step_many refuse a gym with state observations attached "
