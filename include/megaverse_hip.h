@@ -682,6 +682,23 @@ int mv_debug_football_state(mv_gym *g, int32_t env_idx, void *out_host);
 int mv_debug_set_football_state(mv_gym *g, int32_t env_idx, const void *in_host);
 int mv_debug_rng(int32_t device, uint32_t seed, int32_t what, const int32_t *lo, const int32_t *hi, int32_t n, void *out_host);
 int mv_debug_math(int32_t device, int32_t what, const float *a, const float *b, int32_t n, float *out_host);
+/* The character controller's physics (megaverse_amd/csrc/mv_physics.h) on caller-given colliders, without a gym: one 64-lane wave per record runs the
+ * templates the step kernels run, in the instantiation `variant` names -- MV_PHYS_NC1 Rearrange, MV_PHYS_NC2 TowerBuilding / Collect / BoxAGone,
+ * MV_PHYS_NC4 Obstacles / Sokoban, MV_PHYS_HEX the Hex scenarios (boxes in wall frames), MV_PHYS_BALL Football (the ball).  Packed host records, 4-byte
+ * fields.  cols: n_cols <= 64 NC of {int32 kind; float lo[3]; float hi[3]} in slot order (lane l of the wave holds slots l + 64 k; the lowest slot wins
+ * ties): kind 0 none, 1 a box whose bounds are already grown by the capsule's half height in y, 2 another agent's capsule (lo = centre, hi[0] = segment
+ * half length), 3 + f (MV_PHYS_HEX only) a box in hex wall frame f = 0..2, 7 (MV_PHYS_BALL only) the ball (lo = centre, hi[0] = the capsule's half
+ * height, hi[1] = capsule radius + ball radius).  A kind the variant's kernels never hold is refused.
+ *   mv_debug_sweep: {from[3], to[3], up[3], minSlopeDot} -> {int32 hit; float fraction; float normal[3]} (a miss: 0, 1.0, zeros);
+ *   mv_debug_recover: a position [3] -> {int32 pushes; float pos_after_each[5][3]}, the push-out's at most five pushes (entries from `pushes` on repeat
+ *     the last position);
+ *   mv_debug_player_step: {pos[3], hvx, hvz, vvel, voffset, step_offset, jump_speed, int32 was_jumping, float reach2} -> the same record after one
+ *     controller step of 1/15 s (reach2 is ignored on input).
+ * Each call allocates, launches once, synchronises, copies back and frees.  All inputs must be finite. */
+enum { MV_PHYS_NC1 = 0, MV_PHYS_NC2 = 1, MV_PHYS_NC4 = 2, MV_PHYS_HEX = 3, MV_PHYS_BALL = 4 };
+int mv_debug_sweep(int32_t device, int32_t variant, const void *cols, int32_t n_cols, const void *queries, int32_t n_queries, void *out_host);
+int mv_debug_recover(int32_t device, int32_t variant, const void *cols, int32_t n_cols, const float *positions, int32_t n, void *out_host);
+int mv_debug_player_step(int32_t device, int32_t variant, const void *cols, int32_t n_cols, const void *agents_in, int32_t n, void *agents_out_host);
 /* Host-only (no device): what the observation pass takes from the host per launch instead of computing it per workgroup (megaverse_amd/csrc/mv_raster.h:
  * RasterConsts, raster_ray_table) for a W x H observation -- consts[4] = sx, ox, sy, oy (ray abscissa = sx i + ox, sy j + oy), *tiles_x_inv =
  * the reciprocal of the tiles per row (mv_debug_raster_div_host's magic), dcx[W] / dcy[H] the abscissae of every column / row as the gym's

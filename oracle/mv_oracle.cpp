@@ -2198,15 +2198,18 @@ static V3 lerp3(V3 a, V3 b, float rt)
 
 // kinematic_character_controller.cpp:519-602 (preStep + playerStep) with stepUp :223-304,
 // stepForwardAndStrafe :337-393, stepDown :400-442, updateTargetPositionBasedOnCollision :313-329
-static void player_step(Env &e, int idx, float dt)
+// reach2 / fwdSweeps (optional, mvo_debug_player_step): what the device's player_step reports as reach2 -- the largest squared horizontal distance from
+// the start of any point swept between or stood on -- and the sweeps stepForwardAndStrafe's plain loop ran.  Recording them changes nothing else.
+static void player_step(Agent &a, const Colliders &cs, float dt, float *reach2 = nullptr, int *fwdSweeps = nullptr)
 {
-    Agent &a = e.agents[idx];
-    Colliders cs;
-    build_colliders(e, idx, cs);
-
     V3 cur = a.pos, target = a.pos;
     const V3 original = cur;
     const V3 UP = v3(0, 1, 0);
+    float r2 = 0.0f;
+    int sweeps = 0;
+    auto reached = [&](V3 p) {
+        if (reach2) { const float dx = p.x - original.x, dz = p.z - original.z; const float v = dx * dx + dz * dz; r2 = (r2 < v) ? v : r2; }
+    };
 
     const bool wasOnGround = on_ground(a);
     a.vvel -= GRAVITY * dt;
@@ -2228,6 +2231,7 @@ static void player_step(Env &e, int idx, float dt)
             }
             int loops = 0;
             while (recover_from_penetration(cs, cur)) {
+                reached(cur);
                 if (++loops > 4) break;
             }
             target = cur;
@@ -2237,17 +2241,19 @@ static void player_step(Env &e, int idx, float dt)
             cur = target;
         }
     }
+    reached(cur);
 
     // ---- stepForwardAndStrafe
     {
         const V3 hv = v3(a.hvx, 0, a.hvz);
         target = v3(cur.x + hv.x * dt, cur.y + hv.y * dt, cur.z + hv.z * dt);
+        reached(target);
         int maxIter = 10;
         while (maxIter-- > 0) {
             const V3 negDir = cur - target;
             float f = 1.0f; V3 n = v3(0, 0, 0);
             bool hit = false;
-            if (!(cur.x == target.x && cur.y == target.y && cur.z == target.z)) hit = sweep(cs, cur, target, negDir, 0.0f, &f, &n);
+            if (!(cur.x == target.x && cur.y == target.y && cur.z == target.z)) { hit = sweep(cs, cur, target, negDir, 0.0f, &f, &n); ++sweeps; }
             if (!hit) break;
             // updateTargetPositionBasedOnCollision
             V3 dir = target - cur;
@@ -2267,6 +2273,7 @@ static void player_step(Env &e, int idx, float dt)
                 cd = cd * (1.0f / sqrtf(dist2));
                 if (dot(cd, hv) <= 0.0f) { target = cur; break; }
             } else { target = cur; break; }
+            reached(target);
         }
         cur = target;
     }
@@ -2283,13 +2290,18 @@ static void player_step(Env &e, int idx, float dt)
         } else cur = target;
     }
 
+    reached(cur);
     a.hvx = (cur.x - original.x) / dt;
     a.hvz = (cur.z - original.z) / dt;
 
     int loops = 0;
     while (recover_from_penetration(cs, cur)) {
+        reached(cur);
         if (++loops > 4) break;
     }
+    reached(cur);
+    if (reach2) *reach2 = r2;
+    if (fwdSweeps) *fwdSweeps = sweeps;
     a.pos = cur;
 
     const float speed = sqrtf(a.hvx * a.hvx + a.hvz * a.hvz);
@@ -2297,6 +2309,13 @@ static void player_step(Env &e, int idx, float dt)
         if (speed - NORMAL_DECEL * dt < 0) { a.hvx = 0; a.hvz = 0; }
         else { const float k = (speed - NORMAL_DECEL * dt) / speed; a.hvx *= k; a.hvz *= k; }
     }
+}
+
+static void player_step(Env &e, int idx, float dt)
+{
+    Colliders cs;
+    build_colliders(e, idx, cs);
+    player_step(e.agents[idx], cs, dt);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4157,6 +4176,89 @@ int mvo_split_tokens(const char *text, char delim, char *out, int cap)
     for (size_t i = 0; i < tokens.size(); ++i) { if (i) joined += '\x1f'; joined += tokens[i]; }
     if (cap > 0) { strncpy(out, joined.c_str(), size_t(cap) - 1); out[cap - 1] = 0; }
     return int(tokens.size());
+}
+
+/* The controller's sweep, push-out and step on caller-given colliders (mv_oracle.h: mvo_debug_sweep ...): the twins of the HIP library's
+ * mv_debug_sweep / mv_debug_recover / mv_debug_player_step.  They call sweep(), recover_from_penetration() and player_step() above as they are. */
+#pragma pack(push, 4)
+struct DbgCol { int32_t kind; float lo[3], hi[3]; };
+struct DbgQuery { float from[3], to[3], up[3], min_slope_dot; };
+struct DbgSweepOut { int32_t hit; float fraction, normal[3]; };
+struct DbgRecoverOut { int32_t pushes; float pos[5][3]; };
+struct DbgAgent { float pos[3], hvx, hvz, vvel, voffset, step_offset, jump_speed; int32_t was_jumping; float reach2; };
+#pragma pack(pop)
+
+static bool debug_colliders(const void *cols, int n_cols, Colliders &cs)
+{
+    if (!cols || n_cols < 0 || n_cols > int(sizeof cs.c / sizeof cs.c[0])) return false;
+    const DbgCol *in = static_cast<const DbgCol *>(cols);
+    cs.n = n_cols;
+    for (int i = 0; i < n_cols; ++i) {
+        Collider &c = cs.c[i];
+        c.kind = in[i].kind & 0xff;
+        c.frame = c.kind == 3 ? (in[i].kind >> 8) : -1;
+        if (c.kind < 0 || c.kind > 4 || (c.kind == 3 && (c.frame < 0 || c.frame > 2))) return false;
+        c.lo = v3(in[i].lo[0], in[i].lo[1], in[i].lo[2]);
+        c.hi = v3(in[i].hi[0], in[i].hi[1], in[i].hi[2]);
+    }
+    return true;
+}
+
+int mvo_debug_sweep(const void *cols, int n_cols, const void *queries, int n_queries, void *out)
+{
+    auto cs = std::make_unique<Colliders>();
+    if (!debug_colliders(cols, n_cols, *cs) || n_queries < 0 || (n_queries && (!queries || !out))) return -1;
+    const DbgQuery *q = static_cast<const DbgQuery *>(queries);
+    DbgSweepOut *o = static_cast<DbgSweepOut *>(out);
+    for (int i = 0; i < n_queries; ++i) {
+        float f = 1.0f;
+        V3 n = v3(0, 0, 0);
+        const bool hit = sweep(*cs, v3(q[i].from[0], q[i].from[1], q[i].from[2]), v3(q[i].to[0], q[i].to[1], q[i].to[2]),
+                               v3(q[i].up[0], q[i].up[1], q[i].up[2]), q[i].min_slope_dot, &f, &n);
+        o[i].hit = hit ? 1 : 0; o[i].fraction = f;
+        o[i].normal[0] = n.x; o[i].normal[1] = n.y; o[i].normal[2] = n.z;
+    }
+    return 0;
+}
+
+int mvo_debug_recover(const void *cols, int n_cols, const float *positions, int n, void *out)
+{
+    auto cs = std::make_unique<Colliders>();
+    if (!debug_colliders(cols, n_cols, *cs) || n < 0 || (n && (!positions || !out))) return -1;
+    DbgRecoverOut *o = static_cast<DbgRecoverOut *>(out);
+    for (int i = 0; i < n; ++i) {
+        V3 cur = v3(positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]);
+        int pushes = 0;
+        while (recover_from_penetration(*cs, cur)) {   // the controller's loop: at most five pushes
+            o[i].pos[pushes][0] = cur.x; o[i].pos[pushes][1] = cur.y; o[i].pos[pushes][2] = cur.z;
+            if (++pushes > 4) break;
+        }
+        o[i].pushes = pushes;
+        for (int k = pushes; k < 5; ++k) { o[i].pos[k][0] = cur.x; o[i].pos[k][1] = cur.y; o[i].pos[k][2] = cur.z; }
+    }
+    return 0;
+}
+
+int mvo_debug_player_step(const void *cols, int n_cols, const void *agents_in, int n, void *agents_out, int32_t *fwd_sweeps)
+{
+    auto cs = std::make_unique<Colliders>();
+    if (!debug_colliders(cols, n_cols, *cs) || n < 0 || (n && (!agents_in || !agents_out))) return -1;
+    const DbgAgent *in = static_cast<const DbgAgent *>(agents_in);
+    DbgAgent *o = static_cast<DbgAgent *>(agents_out);
+    for (int i = 0; i < n; ++i) {
+        Agent a{};
+        a.pos = v3(in[i].pos[0], in[i].pos[1], in[i].pos[2]);
+        a.hvx = in[i].hvx; a.hvz = in[i].hvz; a.vvel = in[i].vvel; a.voffset = in[i].voffset;
+        a.step_offset = in[i].step_offset; a.jump_speed = in[i].jump_speed; a.was_jumping = in[i].was_jumping;
+        float r2 = 0.0f;
+        int sweeps = 0;
+        player_step(a, *cs, DT, &r2, &sweeps);
+        o[i].pos[0] = a.pos.x; o[i].pos[1] = a.pos.y; o[i].pos[2] = a.pos.z;
+        o[i].hvx = a.hvx; o[i].hvz = a.hvz; o[i].vvel = a.vvel; o[i].voffset = a.voffset;
+        o[i].step_offset = a.step_offset; o[i].jump_speed = a.jump_speed; o[i].was_jumping = a.was_jumping; o[i].reach2 = r2;
+        if (fwd_sweeps) fwd_sweeps[i] = sweeps;
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -125,6 +125,17 @@ int mvo_triangular_number(int n);                          /* util/math_utils.hp
 float mvo_building_reward_coeff(float height);              /* scenario_tower_building.cpp:246-251 */
 void mvo_sincos(float x, float *s, float *c);               /* the fp32 polynomial both sides use */
 
+/* ---- the controller's physics on caller-given colliders: the twins of mv_debug_sweep / mv_debug_recover / mv_debug_player_step
+ * (include/megaverse_hip.h), same packed records.  cols: n_cols of {int32 kind; float lo[3]; float hi[3]} in slot order with THIS file's kinds: 0 none,
+ * 1 box (bounds grown by CAP_HH in y), 2 another agent's capsule (lo = centre, hi[0] = 2 CAP_HH), 3 | frame << 8 a box in hex wall frame 0..2,
+ * 4 the ball (lo = centre, hi[0] = CAP_HH, hi[1] = CAP_R + radius).  They run the controller's own sweep(), recover_from_penetration() loop and
+ * player_step().  0, or -1 for bad arguments. */
+int mvo_debug_sweep(const void *cols, int n_cols, const void *queries, int n_queries, void *out);     /* {from[3], to[3], up[3], minSlopeDot} -> {int32 hit; float fraction, normal[3]} */
+int mvo_debug_recover(const void *cols, int n_cols, const float *positions, int n, void *out);        /* [n][3] -> {int32 pushes; float pos_after_each[5][3]}: entries from `pushes` on repeat the last position */
+/* {pos[3], hvx, hvz, vvel, voffset, step_offset, jump_speed, int32 was_jumping, reach2} in and out (reach2 is ignored on input); fwd_sweeps (or NULL):
+ * [n] the sweeps stepForwardAndStrafe's plain ten-iteration loop ran */
+int mvo_debug_player_step(const void *cols, int n_cols, const void *agents_in, int n, void *agents_out, int32_t *fwd_sweeps);
+
 #ifdef __cplusplus
 }
 #endif

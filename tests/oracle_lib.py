@@ -94,8 +94,51 @@ def lib():
         L.mvo_building_reward_coeff.restype = C.c_float
         L.mvo_sincos.argtypes = [C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.mvo_perlin_octave2_01.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.mvo_debug_sweep.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.mvo_debug_recover.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.mvo_debug_player_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
+
+
+# ---- the controller's physics on caller-given colliders (mv_oracle.h: mvo_debug_sweep ...; records: tests/physics_reference.py)
+
+def _oracle_cols(cols):
+    """COL records with the device's kinds -> the oracle's: a hex box 3 + f becomes 3 | f << 8, the ball (7) becomes 4"""
+    import physics_reference as R
+    out = np.ascontiguousarray(cols, R.COL).copy()
+    k = out["kind"].copy()
+    hexf = (k >= 3) & (k <= 5)
+    out["kind"] = np.where(hexf, 3 | ((k - 3) << 8), np.where(k == R.KIND_BALL, 4, k))
+    assert np.isin(k, (0, 1, 2, 3, 4, 5, R.KIND_BALL)).all()
+    return out
+
+
+def debug_sweep(cols, queries):
+    """the oracle's sweep() for every QUERY against the colliders -> SWEEP_OUT [n]"""
+    import physics_reference as R
+    oc, q = _oracle_cols(cols), np.ascontiguousarray(queries, R.QUERY)
+    out = np.zeros(len(q), R.SWEEP_OUT)
+    assert lib().mvo_debug_sweep(oc.ctypes.data, len(oc), q.ctypes.data, len(q), out.ctypes.data) == 0
+    return out
+
+
+def debug_recover(cols, positions):
+    """the oracle's push-out loop from every position [n, 3] -> RECOVER_OUT [n]"""
+    import physics_reference as R
+    oc, p = _oracle_cols(cols), np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    out = np.zeros(len(p), R.RECOVER_OUT)
+    assert lib().mvo_debug_recover(oc.ctypes.data, len(oc), p.ctypes.data, len(p), out.ctypes.data) == 0
+    return out
+
+
+def debug_player_step(cols, agents):
+    """the oracle's player_step for every AGENT record -> (AGENT [n] after the step, [n] sweeps its plain forward loop ran)"""
+    import physics_reference as R
+    oc, a = _oracle_cols(cols), np.ascontiguousarray(agents, R.AGENT)
+    out, sweeps = np.zeros(len(a), R.AGENT), np.zeros(len(a), np.int32)
+    assert lib().mvo_debug_player_step(oc.ctypes.data, len(oc), a.ctypes.data, len(a), out.ctypes.data, sweeps.ctypes.data) == 0
+    return out, sweeps
 
 
 def ref_lib():
