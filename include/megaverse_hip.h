@@ -672,6 +672,14 @@ int mv_debug_launch_counts(mv_gym *g, int64_t out[2]);
  * (agent.cpp:42-46), and the controller's velocities */
 int mv_debug_set_agent_yaw(mv_gym *g, int32_t env_idx, int32_t agent_idx, float c, float s);
 int mv_debug_set_agent_velocity(mv_gym *g, int32_t env_idx, int32_t agent_idx, float hvx, float hvz, float vvel);
+/* scripted TowerBuilding cases (tests/tower_cases.py).  The pitch of an agent's record: interact points depend on it.  The movable boxes of one env of a
+ * TowerBuilding gym (others are refused): objs[i] = {x, y, z, state}, state 0 placed, 1 + k carried by agent k; 0 <= n <= 80.  Writes the records (zero
+ * beyond n) and num_objects, clears every object bit of the env's chunk and sets it for each placed object inside the chunk, sets each agent's `carrying`
+ * from the states (-1 where none) and recomputes bz_reward with the step kernel's own sum; episode_len, highest_tower, picked_up, visited_zone and the
+ * generator's ring are left alone.  Refused with a text: two objects carried by one agent, a carrier the env does not have, two placed objects in one
+ * voxel, a placed object in a solid voxel. */
+int mv_debug_set_agent_pitch(mv_gym *g, int32_t env_idx, int32_t agent_idx, float pitch);
+int mv_debug_set_objects(mv_gym *g, int32_t env_idx, const int8_t (*objs)[4], int32_t n);
 int mv_debug_snapshot_size(const mv_gym *g);
 int mv_debug_snapshot(mv_gym *g, int32_t env_idx, void *out_host);
 /* BoxAGone: env env_idx's platform table, temporary ring, timers and cell map (BoxAGoneState, mv_types.h); out_host == NULL: its size */

@@ -2,6 +2,7 @@
 // the host-side episode generators and the feeder without a device, the device's RNG helpers and single fp32 operations.  Used by tests/ only.
 #include "mv_api_internal.h"
 #include "mv_still_frames.h"
+#include "mv_tick_tower.h"
 
 __global__ void set_agent_pos_kernel(AgentState *agents, int idx, float x, float y,
                                      float z) { agents[idx].pos[0] = x; agents[idx].pos[1] = y; agents[idx].pos[2] = z; }
@@ -9,6 +10,29 @@ __global__ void set_agent_yaw_kernel(AgentState *agents, int idx, float c,
                                      float s) { agents[idx].m00 = c; agents[idx].m02 = s; agents[idx].m20 = -s; agents[idx].m22 = c; }
 __global__ void set_agent_velocity_kernel(AgentState *agents, int idx, float hvx, float hvz,
                                           float vvel) { agents[idx].hvx = hvx; agents[idx].hvz = hvz; agents[idx].vvel = vvel; }
+
+__global__ void set_agent_pitch_kernel(AgentState *agents, int idx, float pitch) { agents[idx].pitch = pitch; }
+
+// mv_debug_set_objects: the env's bz_reward from its records as they stand -- one wave holds them the way tower_tick does (lane l: objects l - 16 and
+// 48 + l) and runs the tick's own tower_reward
+__global__ void set_objects_reward_kernel(GymView gv, int env)
+{
+    const int lane = lane_id();
+    EnvHeader *gh = gv.hdr + env;
+    tick_tower::Hdr h;
+    h.num_objects = gh->num_objects;
+    h.bz0 = gh->bz[0]; h.bz1 = gh->bz[1]; h.bz2 = gh->bz[2]; h.bz3 = gh->bz[3];
+    const MovableObject *gobj = gv.objects + (size_t)env * MAX_OBJECTS;
+    const int oi[2] = {lane - 16, lane < 32 ? 48 + lane : -1};
+    tick_tower::ObjRegs ob;
+    for (int k = 0; k < 2; ++k) {
+        ob.valid[k] = oi[k] >= 0 && oi[k] < h.num_objects;
+        ob.x[k] = ob.y[k] = ob.z[k] = 0; ob.state[k] = 0;
+        if (ob.valid[k]) { const MovableObject o = gobj[oi[k]]; ob.x[k] = o.x; ob.y[k] = o.y; ob.z[k] = o.z; ob.state[k] = o.state; }
+    }
+    const float r = tick_tower::tower_reward(h, ob);
+    if (lane == 0) gh->bz_reward = r;
+}
 
 __global__ void debug_rng_kernel(uint32_t seed, int what, const int32_t *lo, const int32_t *hi, int n, void *out)
 {
@@ -109,6 +133,63 @@ int mv_debug_set_agent_velocity(mv_gym *g, int32_t env, int32_t agent, float hvx
     if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     hipLaunchKernelGGL(set_agent_velocity_kernel, dim3(1), dim3(1), 0, g->stream, g->gv.agents, env * g->A + agent, hvx, hvz, vvel);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int mv_debug_set_agent_pitch(mv_gym *g, int32_t env, int32_t agent, float pitch)
+{
+    if (check(g)) return -1;
+    if (env < 0 || env >= g->N || agent < 0 || agent >= g->A) return fail("mv_debug_set_agent_pitch: index out of range");
+    if (sim_join(g)) return -1;
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
+    hipLaunchKernelGGL(set_agent_pitch_kernel, dim3(1), dim3(1), 0, g->stream, g->gv.agents, env * g->A + agent, pitch);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// TowerBuilding: env `env`'s movable boxes as a test states them -- records, count, the chunk's VX_OBJECT bits, who carries what, bz_reward.  The episode's
+// timers, highest_tower, the agents' picked_up / visited_zone and the generator's ring stay as they are.
+int mv_debug_set_objects(mv_gym *g, int32_t env, const int8_t (*objs)[4], int32_t n)
+{
+    if (check(g)) return -1;
+    if (g->scenario != SCN_TOWER || !g->gv.chunk) return fail("mv_debug_set_objects: not a TowerBuilding gym");
+    if (env < 0 || env >= g->N || n < 0 || n > (int)MAX_OBJECTS || (n > 0 && !objs)) return fail("mv_debug_set_objects: bad arguments");
+    if (sim_join(g)) return -1;
+    if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    std::vector<uint8_t> chunk(CHUNK_BYTES);
+    std::vector<AgentState> ag(g->A);
+    HIP_TRY(hipMemcpy(chunk.data(), g->gv.chunk + (size_t)env * CHUNK_BYTES, CHUNK_BYTES, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ag.data(), g->gv.agents + (size_t)env * g->A, g->A * sizeof(AgentState), hipMemcpyDeviceToHost));
+    auto cell = [](int x, int y, int z) { return (y * CZ + z) * CX + x; };
+    auto inside = [](int x, int y, int z) { return x >= 0 && x < CX && y >= 0 && y < CY && z >= 0 && z < CZ; };
+    std::vector<MovableObject> rec(MAX_OBJECTS, MovableObject{0, 0, 0, 0});
+    std::vector<int> carried(g->A, -1);
+    for (auto &c : chunk) c &= (uint8_t)~VX_OBJECT;
+    for (int i = 0; i < n; ++i) {
+        const int x = objs[i][0], y = objs[i][1], z = objs[i][2], st = objs[i][3];
+        rec[i] = MovableObject{(int8_t)x, (int8_t)y, (int8_t)z, (int8_t)st};
+        if (st < 0) return fail("mv_debug_set_objects: an object's state is 0 (placed) or 1 + the agent that carries it");
+        if (st > 0) {
+            if (st - 1 >= g->A) return fail("mv_debug_set_objects: an object is carried by an agent the env does not have");
+            if (carried[st - 1] >= 0) return fail("mv_debug_set_objects: two objects are carried by one agent");
+            carried[st - 1] = i;
+            continue;
+        }
+        for (int j = 0; j < i; ++j)
+            if (objs[j][3] == 0 && objs[j][0] == x && objs[j][1] == y && objs[j][2] == z) return fail("mv_debug_set_objects: two placed objects share a voxel");
+        if (!inside(x, y, z)) continue;
+        if (chunk[cell(x, y, z)] & VX_SOLID) return fail("mv_debug_set_objects: a placed object is in a solid voxel");
+        chunk[cell(x, y, z)] |= VX_OBJECT;
+    }
+    for (int a = 0; a < g->A; ++a) ag[a].carrying = carried[a];
+    HIP_TRY(hipMemcpy(g->gv.objects + (size_t)env * MAX_OBJECTS, rec.data(), MAX_OBJECTS * sizeof(MovableObject), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(g->gv.chunk + (size_t)env * CHUNK_BYTES, chunk.data(), CHUNK_BYTES, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(g->gv.agents + (size_t)env * g->A, ag.data(), g->A * sizeof(AgentState), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(&g->gv.hdr[env].num_objects, &n, sizeof n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(set_objects_reward_kernel, dim3(1), dim3(64), 0, g->stream, g->gv, env);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g->stream));
     return 0;
 }
 

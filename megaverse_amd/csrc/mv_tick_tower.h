@@ -17,6 +17,11 @@
 //   Scenario::rewardAgent/rewardTeam            env/include/env/scenario.hpp:259-298
 //   done bookkeeping of VectorEnv::step         env/src/vector_env.cpp:93-105 (the reset itself: reset_kernel)
 //
+// The scenario logic behind the controllers (object_at, column_objects, tower_reward, place / pick, zone visit, rewards, highest_tower) is held twice: bit
+// parity with the CPU oracle, and an independent float64 model written from the reference (tests/tower_model.py) that judges scripted cases and dense
+// runs tick by tick -- discrete outputs exact, rewards within a derived bound.  The float addition order of tower_reward is a documented deviation (index
+// order here, set order there); that bound -- rule (R) -- holds for any order.
+//
 // Mapping: ONE WAVEFRONT PER ENV.  The env's colliders (<=16 layout slabs, <=80 movable boxes,
 // <=8 agent capsules) live in VGPRs, two per lane.  A sweep is "every lane casts against its two
 // colliders, then a 64-bit (fraction, slot) wave-min picks the winner"; depenetration and object
@@ -79,7 +84,8 @@ struct Hdr {
 
 __device__ __forceinline__ bool in_zone(const Hdr &h, int x, int z) { return x >= h.bz0 && x < h.bz1 && z >= h.bz2 && z < h.bz3; }
 
-// sum over objects in index order (float addition order is part of the contract)
+// sum over objects in index order (float addition order is part of the contract; the reference walks an unordered_set: how far ANY fp32 order lies from
+// the true sum is bounded by rule (R) of tests/tower_model.py and checked by tests/test_tower_model*.py)
 __device__ __forceinline__ float tower_reward(const Hdr &h, const ObjRegs &o)
 {
     float term[2];

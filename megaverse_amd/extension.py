@@ -76,6 +76,7 @@ SYMBOLS = [
     ("mv_profile_begin", C.c_int, [_P, _I]), ("mv_profile_end", C.c_int, [_P, _P, _P]),
     ("mv_set_pipelining", C.c_int, [_P, _I]), ("mv_get_pipelining", C.c_int, [_P]),
     ("mv_debug_set_agent_pos", C.c_int, [_P, _I, _I, _F, _F, _F]),
+    ("mv_debug_set_agent_pitch", C.c_int, [_P, _I, _I, _F]), ("mv_debug_set_objects", C.c_int, [_P, _I, _P, _I]),
     ("mv_debug_set_agent_yaw", C.c_int, [_P, _I, _I, _F, _F]), ("mv_debug_set_agent_velocity", C.c_int, [_P, _I, _I, _F, _F, _F]),
     ("mv_debug_snapshot_size", C.c_int, [_P]), ("mv_debug_snapshot", C.c_int, [_P, _I, _P]),
     ("mv_debug_boxagone_state", C.c_int, [_P, _I, _P]),
@@ -1457,6 +1458,15 @@ class MegaverseGym:
 
     def debug_set_agent_velocity(self, env_idx, agent_idx, hvx, hvz, vvel):
         self._ck(self._lib.mv_debug_set_agent_velocity(self._g, int(env_idx), int(agent_idx), float(hvx), float(hvz), float(vvel)))
+
+    def debug_set_agent_pitch(self, env_idx, agent_idx, pitch):
+        self._ck(self._lib.mv_debug_set_agent_pitch(self._g, int(env_idx), int(agent_idx), float(pitch)))
+
+    def debug_set_objects(self, env_idx, objects):
+        """TowerBuilding: env env_idx's movable boxes, int8 [n, 4] rows (x, y, z, state: 0 placed, 1 + k carried by agent k), n <= 80 -- records, count,
+        the chunk's object bits, every agent's `carrying` and bz_reward follow (include/megaverse_hip.h: mv_debug_set_objects)"""
+        o = np.ascontiguousarray(objects, dtype=np.int8).reshape(-1, 4)
+        self._ck(self._lib.mv_debug_set_objects(self._g, int(env_idx), o.ctypes.data, len(o)))
 
     def debug_boxagone_state(self, env_idx):
         """BoxAGone: env env_idx's BoxAGoneState (mv_types.h) as raw bytes -- platform table, temporary ring, timers, cell map."""

@@ -3955,6 +3955,44 @@ void mvo_debug_set_agent_velocity(mvo_gym *g, int env, int agent, float hvx, flo
     a.hvx = hvx; a.hvz = hvz; a.vvel = vvel;
 }
 
+int mvo_debug_set_agent_pitch(mvo_gym *g, int env, int agent, float pitch)
+{
+    if (!g || env < 0 || env >= g->numEnvs || agent < 0 || agent >= g->numAgents) return -1;
+    g->envs[size_t(env)]->agents[agent].pitch = pitch;
+    return 0;
+}
+/* TowerBuilding: the env's movable boxes as a test states them (include/megaverse_hip.h: mv_debug_set_objects) */
+int mvo_debug_set_objects(mvo_gym *g, int env, const int8_t (*objs)[4], int n)
+{
+    if (!g || env < 0 || env >= g->numEnvs || n < 0 || n > MAX_OBJECTS || (n > 0 && !objs)) return -1;
+    Env &e = *g->envs[size_t(env)];
+    if (e.scenario != SCN_TOWER) return -1;
+    std::vector<uint8_t> chunk = e.chunk;
+    int carried[MAX_AGENTS];
+    for (int a = 0; a < MAX_AGENTS; ++a) carried[a] = -1;
+    for (auto &c : chunk) c &= uint8_t(~VX_OBJECT);
+    for (int i = 0; i < n; ++i) {
+        const int x = objs[i][0], y = objs[i][1], z = objs[i][2], st = objs[i][3];
+        if (st < 0) return -1;
+        if (st > 0) {
+            if (st - 1 >= e.numAgents || carried[st - 1] >= 0) return -1;
+            carried[st - 1] = i;
+            continue;
+        }
+        for (int j = 0; j < i; ++j)
+            if (objs[j][3] == 0 && objs[j][0] == x && objs[j][1] == y && objs[j][2] == z) return -1;
+        if (!Env::inChunk(x, y, z)) continue;
+        if (chunk[Env::cell(x, y, z)] & VX_SOLID) return -1;
+        chunk[Env::cell(x, y, z)] |= VX_OBJECT;
+    }
+    e.chunk = chunk;
+    for (int i = 0; i < MAX_OBJECTS; ++i) e.objects[i] = i < n ? Object{objs[i][0], objs[i][1], objs[i][2], objs[i][3]} : Object{0, 0, 0, 0};
+    e.numObjects = n;
+    for (int a = 0; a < e.numAgents; ++a) e.agents[a].carrying = carried[a];
+    e.bzReward = tower_reward(e);
+    return 0;
+}
+
 int mvo_snapshot_size(mvo_gym *) { return (int)sizeof(SnapHeader); }
 
 void mvo_snapshot(mvo_gym *g, int env, void *out)

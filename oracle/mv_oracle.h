@@ -99,6 +99,9 @@ void mvo_set_reward_shaping(mvo_gym *g, int env_idx, int agent_idx, const char *
 void mvo_debug_set_agent_pos(mvo_gym *g, int env_idx, int agent_idx, float x, float y, float z); /* test hook: teleport */
 void mvo_debug_set_agent_yaw(mvo_gym *g, int env_idx, int agent_idx, float c, float s);           /* test hook: yaw basis from (cos, sin) */
 void mvo_debug_set_agent_velocity(mvo_gym *g, int env_idx, int agent_idx, float hvx, float hvz, float vvel);
+/* test hooks, twins of mv_debug_set_agent_pitch / mv_debug_set_objects (include/megaverse_hip.h): the same writes, the same refusals (-1) */
+int mvo_debug_set_agent_pitch(mvo_gym *g, int env_idx, int agent_idx, float pitch);
+int mvo_debug_set_objects(mvo_gym *g, int env_idx, const int8_t (*objs)[4], int n);
 int mvo_snapshot_size(mvo_gym *g);
 void mvo_snapshot(mvo_gym *g, int env_idx, void *out);
 /* BoxAGone: the device's BoxAGoneState record (platform table, timers, temporary platforms, cell map) derived from the oracle's own

@@ -77,6 +77,8 @@ def lib():
         L.mvo_debug_set_agent_pos.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
         L.mvo_debug_set_agent_yaw.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float]
         L.mvo_debug_set_agent_velocity.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
+        L.mvo_debug_set_agent_pitch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float]
+        L.mvo_debug_set_objects.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.mvo_set_action_masks.argtypes = [C.c_void_p, C.c_void_p]
         L.mvo_snapshot_size.argtypes = [C.c_void_p]
         L.mvo_snapshot.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -257,6 +259,16 @@ class OracleGym:
     def debug_set_agent_pos(self, env_idx, agent_idx, x, y, z): self.L.mvo_debug_set_agent_pos(self.g, env_idx, agent_idx, x, y, z)
     def debug_set_agent_yaw(self, env_idx, agent_idx, c, s): self.L.mvo_debug_set_agent_yaw(self.g, env_idx, agent_idx, c, s)
     def debug_set_agent_velocity(self, env_idx, agent_idx, hvx, hvz, vvel): self.L.mvo_debug_set_agent_velocity(self.g, env_idx, agent_idx, hvx, hvz, vvel)
+
+    def debug_set_agent_pitch(self, env_idx, agent_idx, pitch):
+        if self.L.mvo_debug_set_agent_pitch(self.g, env_idx, agent_idx, pitch) != 0:
+            raise RuntimeError("mvo_debug_set_agent_pitch: index out of range")
+
+    def debug_set_objects(self, env_idx, objects):
+        """TowerBuilding: the env's movable boxes, int8 [n, 4] rows (x, y, z, state) -- same arguments and refusals as MegaverseGym.debug_set_objects"""
+        o = np.ascontiguousarray(objects, dtype=np.int8).reshape(-1, 4)
+        if self.L.mvo_debug_set_objects(self.g, env_idx, o.ctypes.data, len(o)) != 0:
+            raise RuntimeError("mvo_debug_set_objects: refused")
 
     def snapshot(self, env_idx):
         assert self.L.mvo_snapshot_size(self.g) == SNAP.itemsize, (self.L.mvo_snapshot_size(self.g), SNAP.itemsize)
