@@ -373,6 +373,43 @@ int mv_get_depth_obs(const mv_gym *g);                               /* 0: none,
 int mv_get_depth_format(const mv_gym *g);                            /* MV_DEPTH_*; -1: none attached */
 int mv_get_depth_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, float *out_host);   /* [H][W] float32; waits for the gym's stream */
 int mv_debug_depth_pack_host(const float *t, const uint8_t *hit, int32_t n, int32_t format, void *out);   /* the pack function, on the host */
+/* Segmentation observations (no reference counterpart).  One label per pixel of every frame an observation pass draws: which drawable the pixel's nearest hit
+ * belongs to -- the hit whose t the depth plane holds.  A frame's record is ONE plane [H][W] in the frame's own pixel order -- row 0 is the bottom row --
+ * whatever mv_set_obs_layout says.  Formats: MV_SEG_CLASS_U8, one byte, the class; MV_SEG_INSTANCE_U16, one 16-bit word class << 12 | instance, instance =
+ * the index of the drawable's record within its class's record array (< 4096): the indices mv_debug_set_objects, the snapshot and the state / scene records
+ * use.  The whole word is 0 where the ray hits nothing -- exactly where the depth is 0 -- and its class nibble is the U8 byte.
+ * Classes (megaverse_amd/csrc/mv_seg_obs.h states the rule for kernels and host alike; mv_seg_class_name gives the names):
+ *   0 NONE   1 FLOOR (layout box in the layout colour; box index)   2 STRUCTURE (every other layout box, every box of the Hex scenarios, BoxAGone, Football; box
+ *   index)   3 EXIT (exit pad, Sokoban goal pad; terrain / cell index)   4 LAVA (terrain index)   5 BUILDING_ZONE (0)   6 FURNITURE (Rearrange's raised floor
+ *   and pedestals, Sokoban's wall caps; static / cell index)   7 TARGET (Rearrange's target arrangement; item index)   8 MOVABLE (a movable object at rest;
+ *   object index)   9 CARRIED (one in an agent's hands; object index)   10 COLLECTABLE (Obstacles' and Collect's +1 diamonds, every Hex collectable, all of its
+ *   parts; record index -- HexMemory's good / bad is hidden state and NOT in the label)   11 HAZARD (Collect's red -1 diamonds; reward index)   12 BALL
+ *   (Football's; 0)   13 AGENT (another agent's capsule and eye box; agent k)   14 HUD (the time bar; agent k whose camera frame it sits in).
+ * The buffer is one more ring beside mv_set_output_ring's three, [entries][N*A][H][W] of uint8_t or uint16_t (2-byte aligned), entries = the output ring's
+ * count at the moment of the call, or 1; a frame's plane goes to the entry the frame goes to.  Everything else is mv_set_depth_obs's, line for line: which passes
+ * write planes (every one that draws frames; no byte where no frame is drawn; a draw-masked env keeps its planes; mv_draw_hires ignores the option), the ordering
+ * point, NULL detaches, mv_close forgets the pointer, the refusals (groups and mv_step_many, still frames in either order, mv_set_output_ring and
+ * mv_set_render_resolution while attached, an unknown format, a misaligned buffer).  Depth and labels attach and detach independently, in either order.
+ * How: in exact pixel mode the pass itself stores every attached output, one trace and no further launch.  In fast pixel mode ONE launch per drawn tick follows
+ * the call's passes -- the depth follower, which now stores labels, or depth + labels: never two traces (counted in out[1] of mv_debug_launch_counts).  Both
+ * forms give the same bytes.  The follower repeats the EXACT trace: at silhouette pixels a fast frame's colour and its label may come from different
+ * primitives, within the fast mode's pixel rule.  Colours, rewards, dones, rows, depth planes and the log are those of a gym without labels.
+ * The label kernels read the group boundaries (the env header's counts) and a layout box's floor / wall flag from the env's records when they RUN: a frame
+ * whose env began a new episode in a later tick of the same batched call is labelled by the new episode's boundaries.
+ * mv_get_seg_observation: one agent's plane in the LAST TICK's entry as uint16 [H][W], a U8 plane widened (the class, no shift), after waiting for the gym's
+ * stream.  mv_debug_seg_bounds_host: the group boundaries {terrain, objects, rewards, agents, end} from an env header's counts.  mv_debug_seg_rule_host: the
+ * rule on the CPU, one slot -> one uint8 / uint16 in *out; subtype: LayoutBox.slot, TerrainBox.type, the Sokoban cell byte or MovableObject.state of the record
+ * the slot names.  mv_debug_seg_pack_host: n (class, instance) pairs -> n bytes / words. */
+enum { MV_SEG_CLASS_U8 = 0, MV_SEG_INSTANCE_U16 = 1 };
+int mv_set_seg_obs(mv_gym *g, void *device_buf, int32_t format);     /* [max(1, ring count)][N*A][H][W] uint8 / uint16 in device memory; NULL detaches */
+int mv_get_seg_obs(const mv_gym *g);                                 /* 0: none, else the number of entries; -1: no gym */
+int mv_get_seg_format(const mv_gym *g);                              /* MV_SEG_*; -1: none attached */
+int mv_get_seg_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, uint16_t *out_host);   /* [H][W] uint16; waits for the gym's stream */
+const char *mv_seg_class_name(int32_t cls);                          /* "FLOOR", ...; NULL outside [0, 15) */
+int mv_debug_seg_bounds_host(int32_t scenario, int32_t L, int32_t W, int32_t num_boxes, int32_t num_terrain, int32_t num_objects, int32_t num_rewards,
+                             int32_t num_agents, int32_t *out5);
+int mv_debug_seg_rule_host(int32_t scenario, int32_t slot, const int32_t *boundaries5, int32_t subtype, int32_t format, void *out);
+int mv_debug_seg_pack_host(const int32_t *cls, const int32_t *instance, int32_t n, int32_t format, void *out);
 /* Episode budgets (no reference counterpart: VectorEnv::step resets a finished env on the spot and steps on, vector_env.cpp:89-108).  Per env e the gym owns an
  * int32 left[e]:  < 0: unlimited -- what every env is without these calls;  > 0: the env may still finish that many episodes;  0: the env is HALTED.
  * Tick t, env e, left[e] as it stands before the tick (megaverse_amd/csrc/mv_episode_budget.h states the rule for kernels and host alike):

@@ -130,6 +130,7 @@ OutPtrs outputs_of(const mv_gym *g, unsigned long long tick)
         if (g->ringDone) o.done = g->ringDone + r * (size_t)g->N;
     }
     o.depth = g->depth.entry(tick);   // (mv_set_depth_obs: attached under this ring count, or under none: entry 0)
+    o.seg = g->seg.entry(tick);       // (mv_set_seg_obs: the same)
     return o;
 }
 OutPtrs last_outputs(const mv_gym *g) { return outputs_of(g, g->ringTick ? g->ringTick - 1 : 0); }   // of the last tick (reset / render / getters)
@@ -787,6 +788,7 @@ int mv_close(mv_gym *g)
     env_masks_free(g);
     obs_rows_free(g);
     g->depth = DepthObs();   // (mv_set_depth_obs: the buffer is the caller's -- forgotten, not freed)
+    g->seg = SegObs();       // (mv_set_seg_obs: likewise)
     episode_budget_free(g);
     macro_step_free(g);
     still_frames_free(g);
@@ -958,11 +960,12 @@ int mvapi::render_frames(mv_gym *g)
     GymView v = view(g, g->parity);
     // (not fill_view_options: a pass reads the draw mask alone, and mv_render draws still frames too.  Also the frame behind mv_reset and mv_reset_envs(render = 1))
     v.draw_mask = g->drawMask.live;
-    // (mv_set_depth_obs: an exact pass stores the depth planes itself, a fast pass is followed by the depth launch)
+    // (mv_set_depth_obs, mv_set_seg_obs: an exact pass stores the depth and label planes itself, a fast pass is followed by ONE launch for what is attached)
     const OutPtrs o = last_outputs(g);
-    if (launch_raster(v, o.obs, g->w, g->h, g->stream, nullptr, g->fastPixels, 0, nullptr, nullptr, g->fastPixels ? nullptr : o.depth, g->depth.format))
+    if (launch_raster(v, o.obs, g->w, g->h, g->stream, nullptr, g->fastPixels, 0, nullptr, nullptr, g->fastPixels ? nullptr : o.depth, g->depth.format,
+                      g->fastPixels ? nullptr : o.seg, g->seg.format))
         return fail("mv_render: observation size above 1024x1024");
-    if (g->fastPixels && depth_obs_follow(g, v, o.depth, "mv_render") < 0) return -1;
+    if (g->fastPixels && planes_follow(g, v, o, "mv_render") < 0) return -1;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1307,6 +1310,8 @@ int mv_set_output_ring(mv_gym *g, int32_t count, void *obs, float *rewards, uint
         return fail("mv_set_output_ring: state observations are attached (mv_set_state_obs), sized by the ring count they were attached under: detach the state observations first");
     if (g->depth.buf)
         return fail("mv_set_output_ring: depth observations are attached (mv_set_depth_obs), sized by the ring count they were attached under: detach the depth observations first");
+    if (g->seg.buf)
+        return fail("mv_set_output_ring: segmentation observations are attached (mv_set_seg_obs), sized by the ring count they were attached under: detach the segmentation observations first");
     if (g->sceneRows.buf)
         return fail("mv_set_output_ring: scene observations are attached (mv_set_scene_obs), sized by the ring count they were attached under: detach the scene observations first");
     if (count < 0 || (count > 0 && !obs && !rewards && !dones)) return fail("mv_set_output_ring: count >= 0 and at least one ring required");
@@ -1443,6 +1448,8 @@ int mv_set_render_resolution(mv_gym *g, int32_t w, int32_t h)
     if (w < 1 || h < 1) return fail("mv_set_render_resolution: bad size");
     if (g->depth.buf)   // (mv_draw_hires writes no depth: the planes stay those of the observation size they were attached under)
         return fail("mv_set_render_resolution: depth observations are attached (mv_set_depth_obs), whose planes are of the observation size: detach the depth observations first");
+    if (g->seg.buf)     // (mv_draw_hires writes no labels either)
+        return fail("mv_set_render_resolution: segmentation observations are attached (mv_set_seg_obs), whose planes are of the observation size: detach the segmentation observations first");
     if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     g->renderW = w; g->renderH = h;
     return 0;

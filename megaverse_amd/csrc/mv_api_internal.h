@@ -13,6 +13,8 @@
 //                     refresh (mv_state_obs.h, mv_scene_obs.h: the records)
 //   mv_depth_obs.hip  depth observations: attaching the caller's buffer, the launch behind a pass that gives every drawn frame its depth plane
 //                     (mv_depth_obs.h: the record; mv_raster.hip: the kernels)
+//   mv_seg_obs.hip    segmentation observations: attaching the caller's buffer, the ONE launch behind a fast pass that writes labels, or depth + labels
+//                     (mv_seg_obs.h: the record and its rule; mv_raster.hip: the kernels)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 //   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
 //   mv_still_frames.hip  still frames: switching the option, the memset behind calls that change what frames show, the carry launch (mv_still_frames.h: the rule)
@@ -136,6 +138,14 @@ struct DepthObs {
     int format = 0, entries = 0;
     size_t entryBytes = 0;
     // tick `tick`'s entry of the caller's buffer: the entry its frames go to (outputs_of)
+    void *entry(unsigned long long tick) const { return buf ? (uint8_t *)buf + (size_t)(tick % (unsigned long long)entries) * entryBytes : nullptr; }
+};
+// The label planes of a gym (mv_seg_obs.hip): the same beside them.  buf: the caller's [entries][N*A][H][W] buffer of bytes or 16-bit words;
+// format: MV_SEG_CLASS_U8 / MV_SEG_INSTANCE_U16.
+struct SegObs {
+    void *buf = nullptr;
+    int format = 0, entries = 0;
+    size_t entryBytes = 0;
     void *entry(unsigned long long tick) const { return buf ? (uint8_t *)buf + (size_t)(tick % (unsigned long long)entries) * entryBytes : nullptr; }
 };
 }  // namespace mvapi
@@ -303,6 +313,9 @@ struct mv_gym {
     ObsRows stateRows, sceneRows;
     // mv_set_depth_obs: the caller's depth planes, written by the passes of a gym in exact pixel mode and by a launch behind the passes of one in fast mode
     DepthObs depth;
+    // mv_set_seg_obs: the caller's label planes, written by the passes of a gym in exact pixel mode and -- fast mode -- by the one launch behind its passes,
+    // which then writes the depth planes too
+    SegObs seg;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
     // budgetLeft [N], what the step kernels read and write (GymView::budget, through the stepping calls' views, while budgetOn); budgetHalted, the count of
     // zeros in it; budgetMirror [N], the episode log's own copy, advanced by the log's update tick by tick.  The host form's values travel through a pool of
@@ -346,7 +359,7 @@ struct GymOption {
     const char *memberNone;   // attach_check: "whose union launches <memberNone>"
     bool (*on)(const mv_gym *);
 };
-enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_DEPTH_OBS, OPT_COUNT };
+enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_DEPTH_OBS, OPT_SEG_OBS, OPT_COUNT };
 #define MV_OPT_ON(expr) +[](const mv_gym *g) -> bool { return expr; }
 inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_step_mask", "a step mask attached", "read none", "detach it first", "detach the mask first", "read no step mask", MV_OPT_ON(g->stepMask.live)},
@@ -356,6 +369,7 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_state_obs", "state observations attached", "write none", "detach them first", "detach them first", "write no state observations", MV_OPT_ON(g->stateRows.buf)},
     {"mv_set_scene_obs", "scene observations attached", "write none", "detach them first", "detach them first", "write no scene observations", MV_OPT_ON(g->sceneRows.buf)},
     {"mv_set_depth_obs", "depth observations attached", "write none", "detach them first", "detach them first", "write no depth observations", MV_OPT_ON(g->depth.buf)},
+    {"mv_set_seg_obs", "segmentation observations attached", "write none", "detach them first", "detach them first", "write no segmentation observations", MV_OPT_ON(g->seg.buf)},
 };
 #undef MV_OPT_ON
 // What a stepping call's view of g carries of the options (the rows of the two records are fields of the per-slot views already: mv_gym::gvp); macro: the view
@@ -372,7 +386,8 @@ inline void fill_view_options(GymView &v, const mv_gym *g, bool macro)
 // Where a tick's public outputs go: the observation slab and the reward / done arrays -- or, with mv_set_output_ring, entry (tick % count)
 // of the caller's rings.  true_objective is state (only a finishing env records it, vector_env.cpp:96-101): never ringed.
 // depth (mv_set_depth_obs): the entry's depth planes, null with no buffer attached.
-struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; void *depth = nullptr; };
+// seg (mv_set_seg_obs): the entry's label planes, likewise.
+struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; void *depth = nullptr; void *seg = nullptr; };
 std::string lower(const char *s);
 int check(mv_gym *g);
 // what every form of a persistent attachment refuses: no gym, a closed one, a member of a group (the union launches read or write none of what opt attaches)
@@ -427,6 +442,14 @@ void obs_rows_free(mv_gym *g);         // mv_close
 // mv_depth_obs.hip: the depth planes of the frames a FAST pass of view v has just drawn into the entry `planes` (OutPtrs::depth), one launch on the caller's
 // stream behind the pass (an exact pass stores them itself: launch_raster's depth argument); -> 1: launched, 0: nothing attached or planes null
 int depth_obs_follow(mv_gym *g, const GymView &v, void *planes, const char *who);
+// mv_seg_obs.hip: the follower of a gym with labels attached, in depth_obs_follow's place -- the label planes (OutPtrs::seg) and, where depth observations
+// are attached too, the depth planes (OutPtrs::depth) of the frames a FAST pass of v has just drawn, with ONE launch; -> 1: launched, 0: no labels attached
+int seg_obs_follow(mv_gym *g, const GymView &v, void *depth, void *planes, const char *who);
+// the one follower behind a fast pass, whatever is attached: labels (and depth) -> seg_obs_follow, depth alone -> depth_obs_follow; -> launches made, -1
+inline int planes_follow(mv_gym *g, const GymView &v, const struct OutPtrs &o, const char *who)
+{
+    return g->seg.buf ? seg_obs_follow(g, v, o.depth, o.seg, who) : depth_obs_follow(g, v, o.depth, who);
+}
 int render_frames(mv_gym *g);          // mv_render without the state rows' refresh (mv_api.hip; mv_reset_envs refreshes the flagged envs' rows only)
 int episode_budget_seed_mirror(mv_gym *g);   // mv_set_episode_log: the log's mirror from the live array (mv_episode_budget.hip)
 // mv_fork.hip, shared with mv_env_store.hip: what every fork / resample / env-store form refuses (what: "forks", "env stores": for the text about groups)

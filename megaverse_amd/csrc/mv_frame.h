@@ -342,7 +342,7 @@ __device__ __forceinline__ void frame_setup_body(const GymView &gv, const int fr
                         const float cx = 2.0f * float(cxi) + 2.0f / 2, cy = 2.0f + hh, cz = 2.0f * float(czi) + 2.0f / 2;
                         kind = PRIM_BOX;
                         lo[0] = cx - 1.0f; lo[1] = cy - hh; lo[2] = cz - 1.0f; hi[0] = cx + 1.0f; hi[1] = cy + hh; hi[2] = cz + 1.0f;
-                        color = t == SOKO_WALL ? 0xffa770u : 0x50c878u;   // LIGHT_ORANGE / LIGHT_GREEN
+                        color = t == SOKO_WALL ? COLOR_SOKO_WALL_CAP : COLOR_SOKO_GOAL_PAD;   // LIGHT_ORANGE / LIGHT_GREEN
                     }
                 } else if (scen == SCN_TOWER) {   // building-zone slab (layout_utils.cpp:53-68)
                     kind = PRIM_BOX;
@@ -354,7 +354,7 @@ __device__ __forceinline__ void frame_setup_body(const GymView &gv, const int fr
                     kind = PRIM_BOX;
                     lo[0] = float(t.min[0]); lo[1] = float(t.min[1]); lo[2] = float(t.min[2]);
                     hi[0] = float(t.max[0]); hi[1] = float(t.min[1]) + 0.05f; hi[2] = float(t.max[2]);
-                    color = t.type == TERRAIN_EXIT ? 0x50c878u : 0xff0000u;   // platforms.hpp:47-56
+                    color = t.type == TERRAIN_EXIT ? COLOR_EXIT_PAD : COLOR_LAVA;   // platforms.hpp:47-56
                 }
             } else if (slot < slotRewards) {
                 const MovableObject o = gv.objects[(size_t)env * MAX_OBJECTS + (slot - slotObjects)];
@@ -421,7 +421,7 @@ __device__ __forceinline__ void frame_setup_body(const GymView &gv, const int fr
                     const float sx = collect ? 0.17f : 0.17f * 0.8f, sy = collect ? 0.45f : 0.45f * 0.8f;
                     const float cx = float(r.x) + 0.5f, cy = float(r.y) + (collect ? 0.8f : 0.7f), cz = float(r.z) + 0.5f;
                     kind = PRIM_CONE;
-                    color = r.state == 2 ? 0xff0000u : 0x3bb372u;
+                    color = r.state == 2 ? COLOR_DIAMOND_RED : COLOR_DIAMOND_GREEN;
                     lo[0] = cx; lo[2] = cz;
                     lo[1] = part == 0 ? cy + 0.5f * sy : cy - 1.5f * sy;
                     hi[0] = sx; hi[1] = sy; hi[2] = part == 0 ? 1.0f : -1.0f;

@@ -19,11 +19,14 @@ struct PublishTo { float *rewards; uint8_t *done; float *true_objective; };
 // instantiation that stores the nearest hit's t beside the colours: one trace, two outputs, no further launch.  A fast pass stores no depth: its kernels stay
 // what they are, and the caller follows it with launch_raster_depth.
 int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t stream, hipEvent_t between = nullptr, int fast = 1, int setup_done = 0,
-                  const PublishTo *publish = nullptr, hipEvent_t done = nullptr, void *depth = nullptr, int depth_format = 0);
+                  const PublishTo *publish = nullptr, hipEvent_t done = nullptr, void *depth = nullptr, int depth_format = 0, void *seg = nullptr, int seg_format = 0);
 
 // The depth planes of every frame of gv -- its lists already set up -- with one launch of the exact kernel's depth-only form: the trace and the depth store,
 // no shading.  Frames in identity order; an undrawn or still frame (mv_frame.h: frame_skip) writes nothing.  -1: W / H too large, no plane, unknown format.
 int launch_raster_depth(const GymView &gv, void *depth, int depth_format, int W, int H, hipStream_t stream);
+// The same with labels attached (mv_set_seg_obs; mv_seg_obs.h): the label planes of every frame of gv -- and, depth non-null, its depth planes -- with ONE launch
+// of the exact trace: never two.  seg (launch_raster, fast = 0 only): the exact pass stores the label planes itself, beside the colours and, if given, the depth.
+int launch_raster_seg(const GymView &gv, void *depth, int depth_format, void *seg, int seg_format, int W, int H, hipStream_t stream);
 
 // the fast observation pass of n gyms of one job (frame lists already built by their step kernels) with at most two launches; publish: n
 // entries or null; -1 if W / H / n are too large

@@ -41,6 +41,7 @@
 
 #include "../../include/megaverse_hip.h"
 #include "mv_depth_obs.h"
+#include "mv_seg_obs.h"
 #include "mv_frame.h"
 #include "mv_math.h"
 #include "mv_raster.h"
@@ -462,8 +463,9 @@ __device__ __forceinline__ void put_px(const PixOutT<true> &po, int px, int py, 
 
 // What the exact kernel's body leaves behind (mv_depth_obs.h: the depth record).  OUT_RGB: the frame's colours -- raster_kernel, as it always was.
 // OUT_RGBD: the same bytes, and the nearest hit's t of every pixel in the frame's depth plane: one trace, two outputs.  OUT_DEPTH: the trace and the depth
-// store alone -- no normal, no Phong, no colour tables (raster_depth_kernel).
-enum : int { OUT_RGB = 0, OUT_RGBD = 1, OUT_DEPTH = 2 };
+// store alone -- no normal, no Phong, no colour tables (raster_depth_kernel).  With mv_seg_obs.h's label record OUT is a SET of outputs -- colours, depth,
+// labels: OUT_LABEL beside any of the above, or alone (raster_seg_kernel).
+enum : int { OUT_COLOURS = 1, OUT_DEPTHS = 2, OUT_LABEL = 4, OUT_RGB = OUT_COLOURS, OUT_RGBD = OUT_COLOURS | OUT_DEPTHS, OUT_DEPTH = OUT_DEPTHS };
 
 // One pixel's depth value into its frame's plane [H][W] (the RGBA store's bounds: px < W && py < H).  Every lane of the wave takes part -- the callers reach
 // this in wave-uniform control flow, the stores are masked after the exchange.  DEPTH_F16, W even: a plane row starts dword-aligned and neighbouring lanes own
@@ -482,21 +484,49 @@ __device__ __forceinline__ void put_depth(void *plane, int format, int W, int H,
     } else if (in) reinterpret_cast<uint32_t *>(plane)[at] = depth_bits_f32(t, hit);
 }
 
+// One pixel's label into its frame's plane [H][W] (mv_seg_obs.h; the RGBA store's bounds), every lane of the wave taking part as in put_depth.  word: the
+// 16-bit word of the pixel's winner, 0: no surface.  `wide` (uniform): the plane starts at a dword.  SEG_INSTANCE_U16 is put_depth's half-precision path: at even
+// W the even lane stores its neighbour's word with its own.  SEG_CLASS_U8, W a multiple of 4: a plane row starts dword-aligned and a quad of lanes owns four
+// neighbouring columns (px & 3 == lane & 3), so quad lane 0 takes the other three's bytes (quad_perm broadcasts of lanes 1, 2, 3) and stores ONE dword; px a
+// multiple of 4 and W too mean px + 3 < W wherever px < W.  Otherwise every lane stores its own byte / two bytes.
+__device__ __forceinline__ void put_label(void *plane, int format, bool wide, int W, int H, int px, int py, unsigned word)
+{
+    const bool in = px < W && py < H;
+    const size_t at = (size_t)py * W + px;
+    if (format == SEG_INSTANCE_U16) {   // (uniform)
+        if (wide && (W & 1) == 0) {   // (uniform)
+            const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)word, 0xb1, 0xf, 0xf, false);
+            if (in && (px & 1) == 0) reinterpret_cast<uint32_t *>(plane)[at >> 1] = word | (other << 16);
+        } else if (in) reinterpret_cast<uint16_t *>(plane)[at] = (uint16_t)word;
+    } else {
+        const unsigned mine = word >> SEG_INSTANCE_BITS;
+        if (wide && (W & 3) == 0) {   // (uniform)
+            const unsigned b1 = (unsigned)__builtin_amdgcn_mov_dpp((int)mine, 0x55, 0xf, 0xf, false);
+            const unsigned b2 = (unsigned)__builtin_amdgcn_mov_dpp((int)mine, 0xaa, 0xf, 0xf, false);
+            const unsigned b3 = (unsigned)__builtin_amdgcn_mov_dpp((int)mine, 0xff, 0xf, 0xf, false);
+            if (in && (px & 3) == 0) reinterpret_cast<uint32_t *>(plane)[at >> 2] = mine | (b1 << 8) | (b2 << 16) | (b3 << 24);
+        } else if (in) reinterpret_cast<uint8_t *>(plane)[at] = (uint8_t)mine;
+    }
+}
+
 }  // namespace
 
 // The exact observation pass of one frame part: tile cull, nearest hit with the draw-order tie rule, Phong.  OUT: what it stores (above); depth / depth_format:
-// the gym's depth entry (frame f's plane at f W H values) and its format, read where OUT != OUT_RGB; order: null (OUT != OUT_RGB only): position = frame.
+// the gym's depth entry (frame f's plane at f W H values) and its format, read where OUT has OUT_DEPTHS; seg / seg_format: the same for the label planes
+// (OUT_LABEL); order: null (OUT != OUT_RGB only): position = frame.
 // CHW: the planar layout (mv_set_obs_layout; PixOutT above)
 template <int MAXVIS, bool SHAPES, bool CHW, int OUT>   // SHAPES: the frame may hold scaled spheres / capsules / cylinders (Rearrange)
-__device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, void *depth, int depth_format, int W, int H, int split, const int *order)
+__device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, void *depth, int depth_format, void *seg, int seg_format, int W, int H, int split,
+                                            const int *order)
 {
-    constexpr bool RGB = OUT != OUT_DEPTH, DEPTH = OUT != OUT_RGB;
+    constexpr bool RGB = (OUT & OUT_COLOURS) != 0, DEPTH = (OUT & OUT_DEPTHS) != 0, LABEL = (OUT & OUT_LABEL) != 0;
     constexpr int ROUNDS = MAXVIS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];   // column/row ray tables
     __shared__ Prim s_vis[MAXVIS];       // this frame's visible list
     __shared__ short4 s_rect[MAXVIS];    // x0,x1,y0,y1 (pixels)
     __shared__ CamL s_cam[MAX_CAMS];
     __shared__ float s_lutA[256], s_lutD[256];   // colour byte -> AMB * c / 255 and (DIF * c / 255) * LCOL
+    __shared__ uint16_t s_label[LABEL ? MAXVIS : 1];   // (OUT_LABEL) the word of every list position: one rule evaluation per visible primitive, none per pixel
 
     float4 *s_col = reinterpret_cast<float4 *>(s_dyn);   // per column i: (dc.x, c00*dc.x, c10*dc.x, c20*dc.x)
     float4 *s_row = s_col + W;                            // per row j:    (dc.y, c01*dc.y, c11*dc.y, c21*dc.y)
@@ -515,13 +545,15 @@ __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, vo
         const int frames = gridDim.x / split;
         if (group * 8 + 8 > frames) { const int b = blockIdx.x - group * per; const int nf = frames - group * 8; frame = group * 8 + b % nf; part = b / nf; }
     }
-    if constexpr (!DEPTH) frame = order[frame];   // `frame` so far was a position in the cost-sorted order (most expensive first)
-    else if (order) frame = order[frame];         // (the depth modes accept no order: position = frame)
+    if constexpr (OUT == OUT_RGB) frame = order[frame];   // `frame` so far was a position in the cost-sorted order (most expensive first)
+    else if (order) frame = order[frame];                 // (the depth and label modes accept no order: position = frame)
     const int env = frame / A, viewer = frame - env * A;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
     // ---- frames of reference: the cameras (and, Hex scenarios, the wall orientations) as the frame setup left them in the frame's header --
-    // the same values it built the list with, and nothing here reads simulator state that a later tick may already be changing (mv_api.hip)
+    // the same values it built the list with, and nothing here reads simulator state that a later tick may already be changing (mv_api.hip) -- with ONE
+    // exception, the OUT_LABEL instantiations below: their label table reads the env header's counts and LayoutBox.slot as they stand when the kernel runs
+    // (the frame setup stores neither in the slot), which an episode reset in a later tick changes (DESIGN.md 7 has the consequence and its bound)
     if (tid < MAX_CAMS) {
         const float *o = reinterpret_cast<const float *>(gv.vis_hdr + (size_t)frame * FRAME_HDR_BYTES) + FH_CAM + FH_CAM_STRIDE * tid;
         CamL cam;
@@ -561,8 +593,19 @@ __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, vo
             s_lutA[tid] = AMB * c;
             s_lutD[tid] = (DIF * c) * LCOL;
         }
+        if constexpr (LABEL) {   // mv_seg_obs.h: the rule, once per visible primitive -- its slot and sub-type from the list, the boundaries from the env's header
+            const Prim *gp = reinterpret_cast<const Prim *>(gv.vis_prims) + (size_t)frame * gv.vis_stride;
+            const SegBounds sb = seg_bounds(gv.hdr[env], A);
+            const bool layoutRecords = !seg_hex_records(gv.scenario);
+            for (int i = tid; i < nVis; i += 256) {
+                const uint32_t meta = gp[i].meta;
+                const int slot = (int)(meta >> 8);
+                const int layoutSlot = layoutRecords && slot < sb.terrain ? gv.boxes[(size_t)env * gv.box_stride + slot].slot : 1;
+                s_label[i] = seg_rule(gv.scenario, slot, sb, seg_subtype_of_prim(gv.scenario, slot, sb, (int)((meta >> 4) & 15), gp[i].color, layoutSlot));
+            }
+        }
     }
-    __syncthreads();   // cameras (incl. origin), ray tables, list, colour tables complete
+    __syncthreads();   // cameras (incl. origin), ray tables, list, colour tables, labels complete
 
     const CamL &cam = s_cam[viewer];
     const V3 eye = v3(cam.eye[0], cam.eye[1], cam.eye[2]);
@@ -571,6 +614,8 @@ __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, vo
     const float LIGHT[3] = {0.0f, 4.0f, 2.0f};
     uint32_t *out = RGB ? obs + (size_t)frame * W * H : nullptr;   // (depth only: no colour slab)
     void *plane = DEPTH ? reinterpret_cast<unsigned char *>(depth) + (size_t)frame * depth_plane_bytes(W, H, depth_format) : nullptr;   // (this frame's depth plane)
+    void *lplane = LABEL ? reinterpret_cast<unsigned char *>(seg) + (size_t)frame * seg_plane_bytes(W, H, seg_format) : nullptr;         // (this frame's label plane)
+    const bool lwide = LABEL && (reinterpret_cast<uintptr_t>(lplane) & 3) == 0;
 
     const float nzm[3] = {-cam.c[2], -cam.c[5], -cam.c[8]};   // c_k2 * (-1)
 
@@ -608,6 +653,7 @@ __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, vo
                     else if (px < W && pyBase + TILE_H * k < H) out[(size_t)(pyBase + TILE_H * k) * W + px] = 0xff000000u;
                 }
                 if constexpr (DEPTH) put_depth(plane, depth_format, W, H, px, pyBase + TILE_H * k, 0.0f, false);
+                if constexpr (LABEL) put_label(lplane, seg_format, lwide, W, H, px, pyBase + TILE_H * k, 0u);
             }
             continue;
         }
@@ -674,6 +720,7 @@ __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, vo
         for (int k = 0; k < PPL; ++k) {
             const int py = pyBase + TILE_H * k;
             if constexpr (DEPTH) put_depth(plane, depth_format, W, H, px, py, best[k], bestPos[k] >= 0);   // best[k]: the float the shading works from
+            if constexpr (LABEL) put_label(lplane, seg_format, lwide, W, H, px, py, bestPos[k] >= 0 ? (unsigned)s_label[bestPos[k]] : 0u);
             if constexpr (!RGB) continue;
             unsigned rgba = 0xff000000u;
             if (bestPos[k] >= 0) {
@@ -739,7 +786,7 @@ template <int MAXVIS, bool SHAPES, bool CHW = false>
 __global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : MAXVIS <= 256 ? 5 : MAXVIS <= 1024 ? 2
                              : 1) void raster_kernel(GymView gv, uint32_t *obs, int W, int H, int split, const int *order)
 {
-    raster_body<MAXVIS, SHAPES, CHW, OUT_RGB>(gv, obs, nullptr, 0, W, H, split, order);
+    raster_body<MAXVIS, SHAPES, CHW, OUT_RGB>(gv, obs, nullptr, 0, nullptr, 0, W, H, split, order);
 }
 
 // Waves per SIMD the depth kernels are built for: the occupancy the compiler reports for them when built WITHOUT a bound (min waves 1).  The figures of that
@@ -757,7 +804,25 @@ template <int MAXVIS, bool SHAPES, bool DEPTH_ONLY, bool CHW = false>
 __global__ __launch_bounds__(256, depth_waves(MAXVIS, SHAPES, DEPTH_ONLY)) void raster_depth_kernel(GymView gv, uint32_t *obs, void *depth, int depth_format,
                                                                                                    int W, int H, int split, const int *order)
 {
-    raster_body<MAXVIS, SHAPES, CHW, DEPTH_ONLY ? OUT_DEPTH : OUT_RGBD>(gv, obs, depth, depth_format, W, H, split, order);
+    raster_body<MAXVIS, SHAPES, CHW, DEPTH_ONLY ? OUT_DEPTH : OUT_RGBD>(gv, obs, depth, depth_format, nullptr, 0, W, H, split, order);
+}
+
+// Segmentation observations (mv_set_seg_obs): the exact pass with a label plane among its outputs.  MODE: the set -- OUT_COLOURS | OUT_LABEL and
+// OUT_COLOURS | OUT_DEPTHS | OUT_LABEL (the pass of a gym in exact pixel mode: one trace for all outputs), OUT_LABEL and OUT_DEPTHS | OUT_LABEL (the ONE follower
+// behind a fast pass, whatever is attached).  s_label's 2 MAXVIS bytes (4 KB at 2048) leave the long-list kernels at the occupancy their LDS gave them.
+// Launch bounds, as depth_waves: the occupancy the compiler reports for an unbounded build (min waves 1) -- labels alone 50 / 57 VGPRs with the short lists
+// (plain / scaled shapes): 8 waves; depth + labels 50 / 57 VGPRs and 103 SGPRs: 7; with colours 67..71 / 73..77 VGPRs: 7, 6 with the scaled shapes; the long
+// lists are bound by their LDS (3 waves, 1 wave).  The library's build, with these bounds: profiles/seg_obs_resources.txt.
+constexpr int seg_waves(int maxvis, bool shapes, int mode)
+{
+    return maxvis > 1024 ? 1 : maxvis > 256 ? 3 : (mode & OUT_COLOURS) != 0 ? (shapes ? 6 : 7) : (mode & OUT_DEPTHS) != 0 ? 7 : 8;
+}
+template <int MAXVIS, bool SHAPES, int MODE, bool CHW = false>
+__global__ __launch_bounds__(256, seg_waves(MAXVIS, SHAPES, MODE)) void raster_seg_kernel(GymView gv, uint32_t *obs, void *depth, int depth_format, void *seg,
+                                                                                          int seg_format, int W, int H, int split, const int *order)
+{
+    static_assert((MODE & OUT_LABEL) != 0, "raster_seg_kernel stores labels");
+    raster_body<MAXVIS, SHAPES, CHW, MODE>(gv, obs, depth, depth_format, seg, seg_format, W, H, split, order);
 }
 
 // =====================================================================================================================
@@ -2955,11 +3020,24 @@ int launch_raster_depth(const GymView &gv, void *depth, int depth_format, int W,
     return 0;
 }
 
+// The planes behind a fast pass with labels attached: ONE launch for the labels, or for depth + labels (depth: null = none).
+int launch_raster_seg(const GymView &gv, void *depth, int depth_format, void *seg, int seg_format, int W, int H, hipStream_t stream)
+{
+    if (W > MAX_W || H > MAX_H || !seg || !seg_format_known(seg_format) || (depth && !depth_format_known(depth_format))) return -1;
+    const int frames = gv.num_envs * gv.num_agents, split = exact_split(W, H);
+    const auto fn = depth ? by_list(gv, [](auto maxvis, auto shapes) { return raster_seg_kernel<decltype(maxvis)::value, decltype(shapes)::value, OUT_DEPTHS | OUT_LABEL>; })
+                          : by_list(gv, [](auto maxvis, auto shapes) { return raster_seg_kernel<decltype(maxvis)::value, decltype(shapes)::value, OUT_LABEL>; });
+    hipLaunchKernelGGL(fn, dim3(frames * split), dim3(256), exact_dyn_lds(W, H), stream, gv, (uint32_t *)nullptr, depth, depth_format, seg, seg_format, W, H, split,
+                       (const int *)nullptr);
+    return 0;
+}
+
 int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t stream, hipEvent_t between,
-                  int fast, int setup_done, const PublishTo *publish, hipEvent_t done, void *depth, int depth_format)
+                  int fast, int setup_done, const PublishTo *publish, hipEvent_t done, void *depth, int depth_format, void *seg, int seg_format)
 {
     if (W > MAX_W || H > MAX_H) return -1;
     if (!fast && depth && !depth_format_known(depth_format)) return -1;   // (before anything is enqueued; mv_set_depth_obs lets no other format through)
+    if (!fast && seg && !seg_format_known(seg_format)) return -1;
     const int frames = gv.num_envs * gv.num_agents;
     if (!setup_done) hipLaunchKernelGGL(gv.draw_mask ? frame_setup_kernel<true> : frame_setup_kernel<false>, dim3(frames), dim3(256), 0, stream, gv, W, H);
     if (!fast) hipLaunchKernelGGL(frame_order_kernel, dim3(1), dim3(1024), 0, stream, gv, frames, gv.lpt_order);   // (fast: no sort kernel)
@@ -3014,7 +3092,13 @@ int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t st
     const size_t dyn = exact_dyn_lds(W, H);
     const int split = exact_split(W, H);
     const dim3 grid(frames * split), block(256);
-    if (depth) {   // (mv_set_depth_obs: one trace, two outputs)
+    if (seg) {   // (mv_set_seg_obs: one trace, colours + labels or colours + depth + labels)
+        const auto fn = by_layout(gv.obs_layout, [&](auto chw) {
+            return depth ? by_list(gv, [](auto maxvis, auto shapes) { return raster_seg_kernel<decltype(maxvis)::value, decltype(shapes)::value, OUT_COLOURS | OUT_DEPTHS | OUT_LABEL, decltype(chw)::value>; })
+                         : by_list(gv, [](auto maxvis, auto shapes) { return raster_seg_kernel<decltype(maxvis)::value, decltype(shapes)::value, OUT_COLOURS | OUT_LABEL, decltype(chw)::value>; });
+        });
+        launch_done(fn, grid, block, dyn, stream, nullptr, gv, obs, depth, depth_format, seg, seg_format, W, H, split, (const int *)gv.lpt_order);
+    } else if (depth) {   // (mv_set_depth_obs: one trace, two outputs)
         const auto fn = by_layout(gv.obs_layout, [&](auto chw) {
             return by_list(gv, [](auto maxvis, auto shapes) { return raster_depth_kernel<decltype(maxvis)::value, decltype(shapes)::value, false, decltype(chw)::value>; });
         });

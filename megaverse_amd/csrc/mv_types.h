@@ -23,6 +23,13 @@ enum : int {
     MAX_CAMS = MAX_AGENTS + HEX_FRAMES,   // frames of reference a box can live in besides the world: agent cameras, hex wall orientations
 };
 
+// Colours (0xRRGGBB) of drawables whose colour tells two kinds of one slot group apart.  The frame setup (mv_frame.h) draws with them and the label rule
+// (mv_seg_obs.h: seg_subtype_of_prim) reads a primitive's kind back from them: named once, so that neither can change without the other.
+constexpr unsigned COLOR_EXIT_PAD = 0x50c878u, COLOR_LAVA = 0xff0000u;                  // terrain slabs, platforms.hpp:47-56
+constexpr unsigned COLOR_SOKO_WALL_CAP = 0xffa770u, COLOR_SOKO_GOAL_PAD = 0x50c878u;    // LIGHT_ORANGE / LIGHT_GREEN, scenario_sokoban.cpp:243-273
+constexpr unsigned COLOR_DIAMOND_RED = 0xff0000u, COLOR_DIAMOND_GREEN = 0x3bb372u;      // Collect's -1 / every +1 diamond, scenario_collect.cpp:192,208
+static_assert(COLOR_EXIT_PAD != COLOR_LAVA && COLOR_SOKO_WALL_CAP != COLOR_SOKO_GOAL_PAD && COLOR_DIAMOND_RED != COLOR_DIAMOND_GREEN, "the colours tell the kinds apart");
+
 enum : int { FRAME_HDR_BYTES = 1024 };
 // Pipelining (mv_api.hip): a step's hand-over buffers -- frame lists, headers, cost lists, reward / done staging -- exist once per SLOT.
 // Slots come in PIPE_GROUPS groups of `batch` slots: one call (mv_step: one tick, mv_step_n: up to `batch` ticks) takes the next group, and

@@ -115,7 +115,98 @@ SYMBOLS = [
     ("mv_debug_still_rule_host", C.c_int, [_P, _P, _P, _P, _I, _I, _P, _P]), ("mv_debug_still_carry_host", C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
     ("mv_set_depth_obs", C.c_int, [_P, _P, _I]), ("mv_get_depth_obs", C.c_int, [_P]), ("mv_get_depth_format", C.c_int, [_P]),
     ("mv_get_depth_observation", C.c_int, [_P, _I, _I, _P]), ("mv_debug_depth_pack_host", C.c_int, [_P, _P, _I, _I, _P]),
+    ("mv_set_seg_obs", C.c_int, [_P, _P, _I]), ("mv_get_seg_obs", C.c_int, [_P]), ("mv_get_seg_format", C.c_int, [_P]),
+    ("mv_get_seg_observation", C.c_int, [_P, _I, _I, _P]), ("mv_seg_class_name", C.c_char_p, [_I]),
+    ("mv_debug_seg_bounds_host", C.c_int, [_I, _I, _I, _I, _I, _I, _I, _I, _P]), ("mv_debug_seg_rule_host", C.c_int, [_I, _I, _P, _I, _I, _P]),
+    ("mv_debug_seg_pack_host", C.c_int, [_P, _P, _I, _I, _P]),
 ]
+
+# include/megaverse_hip.h: the formats of a label plane (mv_set_seg_obs), and the classes (megaverse_amd/csrc/mv_seg_obs.h has the table), name -> value
+MV_SEG_CLASS_U8, MV_SEG_INSTANCE_U16 = 0, 1
+SEG_FORMATS = {"class": MV_SEG_CLASS_U8, "instance": MV_SEG_INSTANCE_U16}
+SEG_INSTANCE_BITS = 12
+SEG_CLASSES = {name: i for i, name in enumerate((
+    "NONE", "FLOOR", "STRUCTURE", "EXIT", "LAVA", "BUILDING_ZONE", "FURNITURE", "TARGET", "MOVABLE", "CARRIED", "COLLECTABLE", "HAZARD", "BALL", "AGENT", "HUD"))}
+
+
+def seg_format_of(fmt):
+    """'class' / 'instance' (or MV_SEG_CLASS_U8 / MV_SEG_INSTANCE_U16 themselves) -> MV_SEG_* (ValueError otherwise)"""
+    if isinstance(fmt, str) and fmt in SEG_FORMATS:
+        return SEG_FORMATS[fmt]
+    if not isinstance(fmt, (str, bool)) and fmt in (MV_SEG_CLASS_U8, MV_SEG_INSTANCE_U16):
+        return int(fmt)
+    raise ValueError(f"set_seg_obs: fmt must be 'class' or 'instance', got {fmt!r}")
+
+
+def seg_split(words):
+    """the words of an 'instance' label plane (torch tensor or numpy array, any shape) -> (cls, instance): class = word >> 12 as uint8, instance = word & 4095
+    as int16 (torch has no uint16 arithmetic: an int16 tensor's bits are read as the unsigned word)"""
+    if isinstance(words, np.ndarray):
+        w = words.astype(np.uint16, copy=False) if words.dtype != np.int16 else words.view(np.uint16)
+        return (w >> SEG_INSTANCE_BITS).astype(np.uint8), (w & 4095).astype(np.int16)
+    import torch
+    w = words.to(torch.int32) & 0xffff
+    return (w >> SEG_INSTANCE_BITS).to(torch.uint8), (w & 4095).to(torch.int16)
+
+
+def seg_class_name(cls):
+    """mv_seg_class_name: the name of a class value, None outside the table (no device)"""
+    name = load_library().mv_seg_class_name(int(cls))
+    return name.decode() if name is not None else None
+
+
+def debug_seg_bounds_host(scenario, L, W, num_boxes, num_terrain, num_objects, num_rewards, num_agents):
+    """mv_debug_seg_bounds_host: an env's group boundaries (terrain, objects, rewards, agents, end) from its header's counts, on the CPU"""
+    out = np.zeros(5, np.int32)
+    lib = load_library()
+    if lib.mv_debug_seg_bounds_host(int(scenario), int(L), int(W), int(num_boxes), int(num_terrain), int(num_objects), int(num_rewards), int(num_agents),
+                                    out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return tuple(int(x) for x in out)
+
+
+def debug_seg_rule_host(scenario, slot, bounds, subtype, fmt):
+    """mv_debug_seg_rule_host: the label rule on the CPU (no device): one slot of an env with the group boundaries `bounds` (5 ints), subtype = the value of
+    the slot's record that tells its group's sub-types apart -> the byte ('class') or the word ('instance') as an int"""
+    lib = load_library()
+    fmt = seg_format_of(fmt)
+    b = np.ascontiguousarray(bounds, np.int32)
+    if b.size != 5:
+        raise ValueError("debug_seg_rule_host: bounds must hold 5 ints")
+    out = np.zeros(1, np.uint16 if fmt == MV_SEG_INSTANCE_U16 else np.uint8)
+    if lib.mv_debug_seg_rule_host(int(scenario), int(slot), b.ctypes.data, int(subtype), fmt, out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return int(out[0])
+
+
+def debug_seg_pack_host(cls, instance, fmt):
+    """mv_debug_seg_pack_host: (class, instance) pairs -> numpy uint8 [n] ('class') or uint16 [n] ('instance'), as the kernels store them (no device)"""
+    lib = load_library()
+    fmt = seg_format_of(fmt)
+    cls = np.ascontiguousarray(cls, np.int32).ravel()
+    instance = np.ascontiguousarray(instance, np.int32).ravel()
+    if cls.size != instance.size:
+        raise ValueError("debug_seg_pack_host: cls and instance differ in length")
+    out = np.empty(cls.size, np.uint16 if fmt == MV_SEG_INSTANCE_U16 else np.uint8)
+    if lib.mv_debug_seg_pack_host(cls.ctypes.data, instance.ctypes.data, int(cls.size), fmt, out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
+
+def check_seg_obs(buf, entries, num_frames, h, w, fmt, device):
+    """the argument check of MegaverseGym.set_seg_obs for a tensor: contiguous torch.uint8 ('class') or torch.int16 / torch.uint16 ('instance') of shape
+    (entries, num_frames, h, w) on CUDA device `device`; entries None: any number of entries"""
+    got = tuple(getattr(buf, 'shape', ()))
+    shape = ((got[0] if len(got) == 4 else 1) if entries is None else int(entries), int(num_frames), int(h), int(w))
+    want = ('torch.int16', 'torch.uint16') if int(fmt) == MV_SEG_INSTANCE_U16 else ('torch.uint8',)
+    contiguous = getattr(buf, 'is_contiguous', None)
+    dev = getattr(buf, 'device', None)
+    index = getattr(dev, 'index', None)
+    if not hasattr(buf, 'data_ptr') or got != shape or str(getattr(buf, 'dtype', None)) not in want \
+            or not getattr(buf, 'is_cuda', False) or not (callable(contiguous) and contiguous()) or (index is not None and int(index) != int(device)):
+        raise ValueError(f"set_seg_obs: the buffer must be a contiguous {' / '.join(x[6:] for x in want)} CUDA tensor of shape {shape} on device {int(device)}, "
+                         f"got {getattr(buf, 'dtype', type(buf).__name__)} {tuple(getattr(buf, 'shape', ()))} on {dev if dev is not None else 'no device'}")
+    return buf
 
 # include/megaverse_hip.h: the formats of a depth plane (mv_set_depth_obs), torch dtype name -> MV_DEPTH_*
 MV_DEPTH_F32, MV_DEPTH_F16 = 0, 1
@@ -808,6 +899,7 @@ class MegaverseGym:
         self._state_obs = None       # set_state_obs: the attached tensor
         self._scene_obs = None       # set_scene_obs: the attached tensor
         self._depth_obs = None       # set_depth_obs: the attached tensor
+        self._seg_obs = None         # set_seg_obs: the attached tensor
         self._ring_ticks = 0         # ticks stepped through this object since set_output_ring (the library's own count: which entry the last tick went to)
         self._macro_held = None      # macro_step: the caller's device tensors of the last call, read in stream order: kept until the next macro step
         self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
@@ -1226,6 +1318,51 @@ class MegaverseGym:
         """-> numpy float32 [H, W]: the depth plane of one agent in the last tick's entry, float16 widened (waits for the gym's stream)"""
         out = np.empty((self.h, self.w), np.float32)
         self._ck(self._lib.mv_get_depth_observation(self._g, int(env_idx), int(agent_idx), out.ctypes.data))
+        return out
+
+    def set_seg_obs(self, buf=True, fmt="class"):
+        """Segmentation observations (include/megaverse_hip.h: mv_set_seg_obs): every frame a later observation pass draws -- the passes set_depth_obs names --
+        leaves a per-pixel label of the drawable it shows (0: no surface, exactly where the depth is 0; row 0 is the bottom row) in entry t % entries of a
+        CUDA tensor [entries, num_envs * num_agents, H, W], entries = the output ring's count, or 1 without a ring.  fmt 'class': torch.uint8, a value of
+        SEG_CLASSES; fmt 'instance': torch.int16 holding the 16-bit word class << 12 | instance (seg_split takes it apart), instance = the index of the
+        drawable's record within its class's array.  True allocates the tensor on the gym's device and returns it; a tensor is checked (ValueError) and
+        attached -- fmt must name its format; None detaches.  Nothing waits on the host.  Depth and labels attach independently: with both, a fast-mode
+        tick still costs ONE launch behind its passes.
+        While attached, set_output_ring, set_render_resolution and set_still_frames(True) are refused."""
+        if buf is None:
+            self._ck(self._lib.mv_set_seg_obs(self._g, None, MV_SEG_CLASS_U8))
+            self._seg_obs = None
+            return None
+        frames = self.num_envs * self.num_agents_per_env
+        fmt = seg_format_of(fmt)
+        if buf is not True:
+            check_seg_obs(buf, None, frames, self.h, self.w, fmt, self.device)   # (what needs no gym first)
+        entries = max(1, self._ck(self._lib.mv_get_output_ring(self._g)))
+        if buf is True:
+            import torch
+            buf = torch.zeros((entries, frames, self.h, self.w), dtype=torch.int16 if fmt == MV_SEG_INSTANCE_U16 else torch.uint8, device=f'cuda:{self.device}')
+        else:
+            check_seg_obs(buf, entries, frames, self.h, self.w, fmt, self.device)
+        self._ck(self._lib.mv_set_seg_obs(self._g, _P(int(buf.data_ptr())), fmt))
+        self._seg_obs = buf
+        return buf
+
+    def seg_obs_ring(self):
+        """-> the tensor set_seg_obs attached, [entries, num_envs * num_agents, H, W] (entry t % entries: the planes of tick t's frames), or None"""
+        return self._seg_obs
+
+    def seg_obs(self):
+        """-> the entry of the last tick, (num_envs * num_agents, H, W): a view of the attached tensor, valid in the order of the gym's stream; None with
+        nothing attached.  A tick that drew no frame wrote nothing there.  With an output ring: the entry the last tick stepped through this object went to"""
+        if self._seg_obs is None:
+            return None
+        entries = int(self._seg_obs.shape[0])
+        return self._seg_obs[(max(1, self._ring_ticks) - 1) % entries]
+
+    def get_seg_observation(self, env_idx, agent_idx):
+        """-> numpy uint16 [H, W]: the label plane of one agent in the last tick's entry, a 'class' plane widened (waits for the gym's stream)"""
+        out = np.empty((self.h, self.w), np.uint16)
+        self._ck(self._lib.mv_get_seg_observation(self._g, int(env_idx), int(agent_idx), out.ctypes.data))
         return out
 
     def get_state_observation(self, env_idx, agent_idx):

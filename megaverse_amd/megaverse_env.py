@@ -69,7 +69,7 @@ def check_sequence_actions(actions, num_agents):
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
                  img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1,
-                 still_frames=False, scene_obs=False, depth_obs=False):
+                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False):
         if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
         # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
@@ -128,6 +128,13 @@ class MegaverseEnv:
         self._depth_dtype = None if depth_obs is False else "float32" if depth_obs is True else depth_obs
         if self._depth_dtype:
             self.env.set_depth_obs(True, self._depth_dtype)
+        # seg_obs (True: the class byte, "instance": class << 12 | instance): every drawn frame leaves its per-pixel labels in a CUDA tensor (mv_set_seg_obs),
+        # read with self.seg_obs(); the gym observation space stays the RGB one
+        if seg_obs is not False and seg_obs is not True and seg_obs not in ("class", "instance"):
+            raise ValueError(f"seg_obs must be False, True, 'class' or 'instance', got {seg_obs!r}")
+        self._seg_fmt = None if seg_obs is False else "class" if seg_obs is True else seg_obs
+        if self._seg_fmt:
+            self.env.set_seg_obs(True, self._seg_fmt)
         self.default_shaping_scheme = self.env.get_reward_shaping(0, 0)
         self.action_space = self.generate_action_space(self.env.action_space_sizes())
         self.observation_space = spaces.Box(0, 255, (self.channels, self.img_h, self.img_w), dtype=np.uint8)
@@ -171,6 +178,16 @@ class MegaverseEnv:
         entry = buf[self._seq[0][0] - 1 if self._seq is not None else 0]
         return entry.view(self.num_envs, self.num_agents_per_env, self.img_h, self.img_w)
 
+    def seg_obs(self):
+        """the last tick's label planes: uint8 classes (megaverse_amd.SEG_CLASSES) or int16 words class << 12 | instance (megaverse_amd.seg_split),
+        (num_envs, num_agents_per_env, H, W) on the device, 0 where a ray hits nothing, row 0 the bottom row -- a view of the attached buffer, under
+        state_obs()'s rules: ask again after every call.  A tick that drew no frame wrote nothing.  Needs MegaverseEnv(..., seg_obs=True | "instance")."""
+        buf = self.env.seg_obs_ring()
+        if buf is None:
+            raise RuntimeError("seg_obs: create the env with seg_obs=True")
+        entry = buf[self._seq[0][0] - 1 if self._seq is not None else 0]
+        return entry.view(self.num_envs, self.num_agents_per_env, self.img_h, self.img_w)
+
     def _set_output_ring(self, count, *ptrs):
         """the env's own output rings change (step_device, step_sequence): the state buffer is one more ring of the same depth and the library refuses a ring
         change while it is attached, so it is detached around the change and a buffer of the new depth attached"""
@@ -180,9 +197,13 @@ class MegaverseEnv:
             self.env.set_scene_obs(None)
         if self._depth_dtype:
             self.env.set_depth_obs(None)
+        if self._seg_fmt:
+            self.env.set_seg_obs(None)
         self.env.set_output_ring(count, *ptrs)
         if self._depth_dtype:
             self.env.set_depth_obs(True, self._depth_dtype)
+        if self._seg_fmt:
+            self.env.set_seg_obs(True, self._seg_fmt)
         if self._state_on:
             self.env.set_state_obs(True)
         if self._scene_on:

@@ -183,6 +183,11 @@ class MultiTaskGym:
         raise RuntimeError("MultiTaskGym.set_depth_obs: mv_group_create and mv_step_many refuse a gym with depth observations attached "
                            "(mv_set_depth_obs): the union launches write none; step such a gym on its own")
 
+    def set_seg_obs(self, buf=True, fmt="class"):
+        """segmentation observations (MegaverseGym.set_seg_obs) are per gym: a group's union launches write none, and the library refuses"""
+        raise RuntimeError("MultiTaskGym.set_seg_obs: mv_group_create and mv_step_many refuse a gym with segmentation observations attached "
+                           "(mv_set_seg_obs): the union launches write none; step such a gym on its own")
+
     def set_state_obs(self, buf=True):
         """state observations (MegaverseGym.set_state_obs) are per gym: a group's union launches write none, and the library refuses"""
         raise RuntimeError("MultiTaskGym.set_state_obs: mv_group_create and mv_step_many refuse a gym with state observations attached "
