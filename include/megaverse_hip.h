@@ -343,6 +343,39 @@ int mv_get_scene_obs(const mv_gym *g);                  /* 0: none, else the num
 int mv_get_scene_observation(mv_gym *g, int32_t env_idx, float *out_host32);   /* last tick's row; waits for the gym's stream */
 int mv_debug_scene_obs_host(int32_t scenario, const void *env_header, const void *terrain16, const void *rewards, int32_t rewards_len,
                             const void *football_state, float *out32);         /* the pack function on the host; unused inputs may be NULL */
+/* Entity observations (no reference counterpart): the objects themselves -- E rows of MV_ENTITY_OBS_FLOATS = 8 float32 per env, [N][E][8], taken from the env's
+ * state AFTER the tick, auto-reset included.  They are the table the instance labels of mv_set_seg_obs (MV_SEG_INSTANCE_U16) index into.
+ * E (mv_entity_obs_rows) is fixed for a gym: it depends on the scenario and the agent count alone.  Rows are slot-addressed, not compacted: every record has a
+ * fixed row for the gym's lifetime, row = its group's base + its record index (mv_entity_obs_layout), and a record that does not exist this episode is a row of
+ * eight +0.0f.  Columns (megaverse_amd/csrc/mv_entity_obs.h states them for kernels and host alike, with the table of every scenario's rows):
+ *    0  the entity's segmentation word class << 12 | instance as a float (exact: below 2^16), the value the instance plane shows for that drawable; 0: an empty
+ *    row      1..3  centre, world units      4..6  half extents, world units      7  state, by class
+ * with mv_set_scene_obs's two conversions, "copied" and "int".  Groups, in the label rule's order:
+ *    0  "terrain": TowerBuilding's building zone (1 row; state: bz_reward), Obstacles*' terrain boxes (16; EXIT / LAVA; state: type), Rearrange's target
+ *       items (8; state: shape), Sokoban's goal cells (80; compacted: row k is the k-th goal cell in cell order, the word carries the pad's instance; state 1)
+ *    1  movable objects (80: TowerBuilding, Obstacles*, Collect, Rearrange, Sokoban): MOVABLE at its voxel cell, or CARRIED at its carrier's position;
+ *       state: the object's state byte (1 + k: carried by agent k)
+ *    2  collectables: Obstacles*' diamonds (16), Collect's (96; HAZARD: a red one), the Hex scenarios' (128; state: alive ? 1 + shape : 0 -- HexMemory's good /
+ *       bad stays hidden), Football's ball (1; BALL; half extents: its radius; state: this tick's kicks); a diamond's state: 0 picked up, 2 red
+ *    3  agents (A rows, every scenario): AGENT k at its position with the capsule's radius and half height; state: the index of the object it carries, -1 none
+ * Floor, structure, furniture, BoxAGone's platforms and the HUD get no rows.
+ * mv_entity_obs_layout: out[group] = {base row, rows, the class of the group's first kind (0: the group is empty)}.
+ * Buffer, ticks, visibility, refresh, what forks / resampling / loads / seeds leave alone, ordering and refusals are mv_set_scene_obs's, with [entries][N][E][8]
+ * for [entries][N][32]; the buffer must be 16-byte aligned.  The stepping call's ONE publication launch carries whichever of the three row records are
+ * attached.  A gym that attaches none launches exactly what it launched before.  The staging rows (slots x N x E x 32 bytes) are counted in mv_arena_bytes
+ * from the first attach on.
+ * mv_debug_entity_obs_host: the record on the CPU, from the bytes of one EnvHeader (128), 16 TerrainBox (32 each), 8 ArrangementItem (32 each), 1024 Sokoban
+ * cell bytes, 80 MovableObject (4 each), rewards_len MovableObject, 128 HexRec (32 each), one FootballState (64) and num_agents AgentState (128 each) of
+ * megaverse_amd/csrc/mv_types.h -> out[E][8]; inputs the scenario does not read may be NULL: no device. */
+enum { MV_ENTITY_OBS_FLOATS = 8, MV_ENTITY_OBS_GROUPS = 4 };
+int mv_entity_obs_rows(const mv_gym *g);                                          /* E; -1: no gym */
+int mv_entity_obs_layout(const mv_gym *g, int32_t out[MV_ENTITY_OBS_GROUPS][3]);  /* per group: base row, rows, seg class of its first kind */
+int mv_set_entity_obs(mv_gym *g, float *device_buf);    /* [max(1, ring count)][N][E][8] float32 in device memory, 16-byte aligned; NULL detaches */
+int mv_get_entity_obs(const mv_gym *g);                 /* 0: none, else the number of entries; -1: no gym */
+int mv_get_entity_observation(mv_gym *g, int32_t env_idx, float *out_host);       /* last tick's E rows; waits for the gym's stream */
+int mv_debug_entity_obs_host(int32_t scenario, int32_t num_agents, const void *env_header, const void *terrain16, const void *items8, const void *soko_cells,
+                             const void *objects80, const void *rewards, int32_t rewards_len, const void *hex_objs128, const void *football_state,
+                             const void *agent_states, float *out);               /* the pack function on the host; unused inputs may be NULL */
 /* Depth observations (no reference counterpart: the reference reads colours back and leaves its depth buffer on the card).  One value per pixel of every frame
  * an observation pass draws: the ray parameter t of the pixel's nearest hit, the very float the shading works from.  Every ray has the camera-space direction
  * (x, y, -1) and every primitive frame keeps t, so t is the PLANAR camera-space depth -z_cam in world units, within [0.01, 120]; 0 where the ray hits nothing

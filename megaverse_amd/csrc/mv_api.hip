@@ -1314,6 +1314,8 @@ int mv_set_output_ring(mv_gym *g, int32_t count, void *obs, float *rewards, uint
         return fail("mv_set_output_ring: segmentation observations are attached (mv_set_seg_obs), sized by the ring count they were attached under: detach the segmentation observations first");
     if (g->sceneRows.buf)
         return fail("mv_set_output_ring: scene observations are attached (mv_set_scene_obs), sized by the ring count they were attached under: detach the scene observations first");
+    if (g->entityRows.buf)
+        return fail("mv_set_output_ring: entity observations are attached (mv_set_entity_obs), sized by the ring count they were attached under: detach the entity observations first");
     if (count < 0 || (count > 0 && !obs && !rewards && !dones)) return fail("mv_set_output_ring: count >= 0 and at least one ring required");
     if (count > 0 && obs && g->obsLayout == MV_OBS_RGB_PLANAR && (uintptr_t)obs % planar_alignment(g->w))
         return fail("mv_set_output_ring: a planar ring of this width must be " + std::to_string(planar_alignment(g->w)) + "-byte aligned");

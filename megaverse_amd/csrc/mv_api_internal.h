@@ -117,7 +117,7 @@ struct MacroCall {
 }  // namespace mvapi
 
 namespace mvapi {
-// One row record of a gym (mv_obs_rows.hip: state observations [N*A][16], scene observations [N][32]).  buf: the caller's [entries][words] float32 buffer (null:
+// One row record of a gym (mv_obs_rows.hip: state observations [N*A][16], scene observations [N][32], entity observations [N][E][8]).  buf: the caller's [entries][words] float32 buffer (null:
 // off; entries: the output ring's count when it was attached, or 1); stage: the gym's staging rows [slots][words], allocated at the first attach and kept
 // until mv_close (stageBytes; not part of the arena).  While attached, the record's field of gvp[q] points at slot q's rows: the stepping calls' views carry it
 // to the MASKED step kernels.
@@ -309,8 +309,9 @@ struct mv_gym {
     EnvMask stepMask;
     // mv_set_draw_mask: the bytes the frame setups read (GymView::draw_mask through the views of the stepping calls and of mv_render)
     EnvMask drawMask;
-    // mv_set_state_obs, mv_set_scene_obs (ObsRows).  The scene rows' staging is counted in mv_arena_bytes from its allocation on, the state rows' is not.
-    ObsRows stateRows, sceneRows;
+    // mv_set_state_obs, mv_set_scene_obs, mv_set_entity_obs (ObsRows).  The scene and entity rows' staging is counted in mv_arena_bytes from its allocation
+    // on, the state rows' is not.
+    ObsRows stateRows, sceneRows, entityRows;
     // mv_set_depth_obs: the caller's depth planes, written by the passes of a gym in exact pixel mode and by a launch behind the passes of one in fast mode
     DepthObs depth;
     // mv_set_seg_obs: the caller's label planes, written by the passes of a gym in exact pixel mode and -- fast mode -- by the one launch behind its passes,
@@ -359,7 +360,7 @@ struct GymOption {
     const char *memberNone;   // attach_check: "whose union launches <memberNone>"
     bool (*on)(const mv_gym *);
 };
-enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_DEPTH_OBS, OPT_SEG_OBS, OPT_COUNT };
+enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_DEPTH_OBS, OPT_SEG_OBS, OPT_ENTITY_OBS, OPT_COUNT };
 #define MV_OPT_ON(expr) +[](const mv_gym *g) -> bool { return expr; }
 inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_step_mask", "a step mask attached", "read none", "detach it first", "detach the mask first", "read no step mask", MV_OPT_ON(g->stepMask.live)},
@@ -370,6 +371,7 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_scene_obs", "scene observations attached", "write none", "detach them first", "detach them first", "write no scene observations", MV_OPT_ON(g->sceneRows.buf)},
     {"mv_set_depth_obs", "depth observations attached", "write none", "detach them first", "detach them first", "write no depth observations", MV_OPT_ON(g->depth.buf)},
     {"mv_set_seg_obs", "segmentation observations attached", "write none", "detach them first", "detach them first", "write no segmentation observations", MV_OPT_ON(g->seg.buf)},
+    {"mv_set_entity_obs", "entity observations attached", "write none", "detach them first", "detach them first", "write no entity observations", MV_OPT_ON(g->entityRows.buf)},
 };
 #undef MV_OPT_ON
 // What a stepping call's view of g carries of the options (the rows of the two records are fields of the per-slot views already: mv_gym::gvp); macro: the view
@@ -432,7 +434,7 @@ int still_frames_carry(mv_gym *g, const GymView *views, const OutPtrs *outs, int
 int publish_macro(mv_gym *g, int q0, const OutPtrs &o, int k, bool cont);
 // mv_api_step.hip: one chunk (<= batch ticks) of a macro step of kCall ticks; quiet: QUIET_NONE / QUIET_LAST of step_gyms
 int step_macro_chunk(mv_gym *g, int k, int kCall, bool draw_last, const MacroCall &mc);
-// mv_obs_rows.hip.  publish: the stepping call's ONE publication launch for both records -- the staged rows of the k ticks in slots q0 .. q0 + k - 1 -> the
+// mv_obs_rows.hip.  publish: the stepping call's ONE publication launch for all three row records -- the staged rows of the k ticks in slots q0 .. q0 + k - 1 -> the
 // entries of ticks tick0 .. tick0 + k - 1 of the caller's buffers, on the caller's stream; -> 1: launched, 0: no record attached.  refresh: the last tick's
 // entries gathered from the current state (mask: device bytes [N], only the flagged envs' rows; null: every row; nothing attached: no launch), on the caller's
 // stream behind sim_join

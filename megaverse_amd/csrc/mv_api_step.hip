@@ -125,7 +125,7 @@ struct StepCall {
         sideWaits = anyHostEpisodes;
         for (int i = 0; i < n; ++i)
             sideWaits = sideWaits || (gs[i]->genStream && gs[i]->ticksSinceDraw + k >= gs[i]->drawPeriod) || gs[i]->stepsSinceStatus + k >= gs[i]->statusPeriod;
-        rows = n == 1 && (L->stateRows.buf != nullptr || L->sceneRows.buf != nullptr);   // (a group's members have none)
+        rows = n == 1 && (L->stateRows.buf != nullptr || L->sceneRows.buf != nullptr || L->entityRows.buf != nullptr);   // (a group's members have none)
         // (mv_set_still_frames with an output ring: the calls run in order -- pass c + 1 on its side stream could draw into the entry that carry c, on the
         // caller's stream, is still reading when the ring is exactly two calls deep)
         carry = n == 1 && L->stillOn && L->ringObs != nullptr && (r.render || drawLast);
@@ -483,7 +483,7 @@ struct StepCall {
             if (gs[i]->logCapacity > 0 && episode_log_update(gs[i], views.data() + i, n, k)) return -1;
             gs[i]->ticksSinceReset += (uint32_t)k;
         }
-        // the row records (mv_set_state_obs, mv_set_scene_obs): ONE launch for the call's k ticks and both records, staged rows -> the caller's buffers; every
+        // the row records (mv_set_state_obs, mv_set_scene_obs, mv_set_entity_obs): ONE launch for the call's k ticks and all attached records, staged rows -> the caller's buffers; every
         // stepping call stages and publishes this way, pipelined or not.  It is counted with the call's pass launches (mv_debug_launch_counts).
         // (mv_macro_step: one entry per call -- the rows behind the call's last tick, with its last chunk)
         if (rows && (!mc || mc->last)) {
@@ -753,7 +753,7 @@ int mv_recommended_pass_overlap(const mv_gym *g)
     return 1;
 }
 
-int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMask.ownedBytes + g->drawMask.ownedBytes + g->budgetBytes + g->macroBytes + g->stillBytes + g->sceneRows.stageBytes) : 0; }
+int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMask.ownedBytes + g->drawMask.ownedBytes + g->budgetBytes + g->macroBytes + g->stillBytes + g->sceneRows.stageBytes + g->entityRows.stageBytes) : 0; }
 
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index)
 {   // several gyms of one job (MultiTaskGym: one per scenario, one stream each) stepped by one call: at eight sub-gyms the per-call cost of

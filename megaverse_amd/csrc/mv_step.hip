@@ -9,6 +9,8 @@
 #include "mv_step_kernels.h"
 #include "mv_tick_tower.h"
 
+static_assert(mv::ENTITY_CAP_R == mv::CAP_R && mv::ENTITY_CAP_HH == mv::CAP_HH, "entity observations: an agent's half extents are the capsule's of mv_physics.h");
+
 namespace mv {
 
 using S = tick_tower::Scenario;

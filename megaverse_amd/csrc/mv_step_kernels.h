@@ -8,12 +8,13 @@
 // S::tick and frozen_tick, below.  They also choose between frame_setup_body and frame_skip (mv_frame.h) for the envs a draw mask (mv_set_draw_mask) leaves out
 // and for the envs that did not change since their frames were drawn last (mv_set_still_frames: env_stale),
 // and store the agents' state rows behind every tick of a view that carries staging rows for them (mv_set_state_obs: state_obs_write), and the env's scene
-// row likewise (mv_set_scene_obs: scene_obs_write).
+// row likewise (mv_set_scene_obs: scene_obs_write), and the env's entity rows (mv_set_entity_obs: entity_obs_write).
 // Every __global__ is a one-line entry point over a body in its scenario's mv_step_<scenario>.hip (a launch bound that depends on a template
 // parameter is not applied, and the profiles name the kernels); StepKernels lists them for the launchers (mv_step.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mv_entity_obs.h"
 #include "mv_episode_budget.h"
 #include "mv_frame.h"
 #include "mv_macro_step.h"
@@ -213,8 +214,58 @@ __device__ __forceinline__ void scene_obs_write(const GymView &gv, int env)
     scene_obs_store(reinterpret_cast<uint32_t *>(gv.scene_obs) + (size_t)env * SCENE_OBS_FLOATS, gv.scenario, gv.hdr + env, gv.terrain + (size_t)env * MAX_TERRAIN,
                     gv.rewards_obj + (size_t)env * gv.reward_stride, gv.fb + env);
 }
-// whether a view carries rows of either record (uniform): the extra barriers of the ticks without frame setup
-__device__ __forceinline__ bool obs_rows_on(const GymView &gv) { return gv.state_obs != nullptr || gv.scene_obs != nullptr; }
+// ---- mv_set_entity_obs: the env's entity rows of this tick (mv_entity_obs.h has the record): E rows of 8 words per ENV, at exactly the sites of
+// scene_obs_write and under its ordering rule.  gv.entity_obs is a kernel argument, so the branch is uniform; the env's first wave writes, every lane one
+// row per round -- at most three rounds of 64 lanes (ENTITY_MAX_ROWS) -- as two 16-byte vector stores: a round is a contiguous 2 KB per wave.  Sokoban's goal
+// cells are the one compacted group: 16 rounds of 64 cells, a ballot each; a goal cell's lane takes the row its rank names (the goals of the rounds before +
+// the goal lanes below it: __popcll(ballot & lanemask_lt)) -- the integers entity_soko_goal_of's loop gives -- and the rows behind the last goal are zeroed.
+// Every row is stored by exactly one lane.  No LDS, no atomics.  The store is a call that is NOT inlined, for state_obs_store's reason.  Only the MASKED
+// instantiations call it.
+// (The two stores are plain: the optimiser keeps most of them 16 bytes wide and splits the rows of two branches into dword stores.  Forcing every row to
+// stay two 16-byte stores -- volatile vectors -- was built and measured, and removed: 1024 envs, render='none', us per tick with the rows on: TowerBuilding
+// 12.69 -> 13.78, Sokoban 16.59 -> 22.42; ObstaclesHard rendered 44.46 -> 48.27.)
+__device__ __forceinline__ void entity_row_store(uint32_t *rows, int row, const EntityRow &r)
+{
+    uint4 *dst = reinterpret_cast<uint4 *>(rows + (size_t)row * ENTITY_OBS_FLOATS);
+    dst[0] = make_uint4(r.w[0], r.w[1], r.w[2], r.w[3]);
+    dst[1] = make_uint4(r.w[4], r.w[5], r.w[6], r.w[7]);
+}
+static __device__ __attribute__((noinline)) void entity_obs_store(uint32_t *rows, int scenario, int A, const EnvHeader *hdr, const TerrainBox *terrain,
+                                                                  const ArrangementItem *items, const uint8_t *soko, const MovableObject *objects,
+                                                                  const MovableObject *rewards, const HexRec *hex_objs, const FootballState *fb,
+                                                                  const AgentState *agents)
+{
+    const int lane = threadIdx.x;   // (the env's first wave: 0..63, all of them here)
+    const EntityLayout l = entity_layout(scenario, A);
+    const EntitySrc s = {scenario, A, hdr, terrain, items, soko, objects, rewards, hex_objs, fb, agents};
+    const int first = scenario == SCN_SOKOBAN ? l.base[ENTITY_OBJECTS] : 0;   // (uniform: the goal rows are placed below)
+    for (int row = first + lane; row < l.total; row += 64) entity_row_store(rows, row, entity_obs_row(s, l, row));
+    if (scenario == SCN_SOKOBAN) {   // (uniform)
+        const int W = hdr->W;
+        int count = 0;
+        for (int base = 0; base < SOKO_DIM * SOKO_DIM; base += 64) {
+            const int cell = base + lane;
+            const bool goal = soko[cell] == SOKO_GOAL;
+            const unsigned long long m = __ballot(goal);
+            const int k = count + __popcll(m & ((1ull << lane) - 1ull));
+            if (goal && k < ENTITY_SOKO_GOALS) entity_row_store(rows, k, entity_soko_goal_row(cell, W));
+            count += __popcll(m);
+        }
+        const EntityRow zero = {};
+        for (int k = min(count, (int)ENTITY_SOKO_GOALS) + lane; k < ENTITY_SOKO_GOALS; k += 64) entity_row_store(rows, k, zero);
+    }
+}
+__device__ __forceinline__ void entity_obs_write(const GymView &gv, int env)
+{
+    if (gv.entity_obs == nullptr || threadIdx.x >= 64) return;
+    const int A = gv.num_agents;
+    entity_obs_store(reinterpret_cast<uint32_t *>(gv.entity_obs) + (size_t)env * entity_obs_rows(gv.scenario, A) * ENTITY_OBS_FLOATS, gv.scenario, A,
+                     gv.hdr + env, gv.terrain + (size_t)env * MAX_TERRAIN, gv.items + (size_t)env * MAX_ITEMS, gv.soko_cells + (size_t)env * (SOKO_DIM * SOKO_DIM),
+                     gv.objects + (size_t)env * MAX_OBJECTS, gv.rewards_obj + (size_t)env * gv.reward_stride, gv.hex_objs + (size_t)env * HEX_MAX_OBJS,
+                     gv.fb + env, gv.agents + (size_t)env * A);
+}
+// whether a view carries rows of any record (uniform): the extra barriers of the ticks without frame setup
+__device__ __forceinline__ bool obs_rows_on(const GymView &gv) { return gv.state_obs != nullptr || gv.scene_obs != nullptr || gv.entity_obs != nullptr; }
 
 // One workgroup per env: wave 0 runs the tick (one wave per env: physics, scenario logic, auto-reset), the others wait at the barrier (S::par_agents:
 // they take their share of the character controllers first); then the workgroup builds the lists of the env's frames (mv_frame.h).  `render` = 0:
@@ -247,7 +298,7 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
     [[maybe_unused]] int32_t left = -1;
     if constexpr (MASKED) if ((left = env_tl(gv, env) == 0 ? 0 : env_left(gv, env)) == 0) {   // (mv_set_step_mask, mv_set_episode_budget) the frozen tick, then the env's frames as below, from the unchanged state
         frozen_tick(gv, env);
-        state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env);   // (mv_set_state_obs: the unchanged state, as the last launch left it)
+        state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); entity_obs_write(gv, env);   // (mv_set_state_obs: the unchanged state, as the last launch left it)
         if (!render) return;
         // (mv_set_still_frames) read by every wave IN FRONT of the barrier, stored by thread 0 behind it: no wave reads what this launch stored
         const int stale = env_stale(gv, env);
@@ -286,13 +337,13 @@ __device__ __forceinline__ void step_body(const GymView &gv, const int env, int 
         if constexpr (MASKED) if (gv.still != nullptr && threadIdx.x == 0) still_store(gv.still + env, 1);   // (mv_set_still_frames: the env stepped, no pass follows)
         if constexpr (MASKED) if (obs_rows_on(gv)) {   // (mv_set_state_obs, mv_set_scene_obs; uniform) a tick without frame setup reports its rows too
             __syncthreads();   // the tick's stores before the rows' loads
-            state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env);
+            state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); entity_obs_write(gv, env);
         }
         return;
     }
     __syncthreads();   // the tick's stores (same CU: same L1) before the frame setup's loads
     MV_T(6);           // the whole tick as wave 0 saw it (incl. the generator of a finished env), up to the barrier
-    if constexpr (MASKED) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); }   // (mv_set_state_obs, mv_set_scene_obs)
+    if constexpr (MASKED) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); entity_obs_write(gv, env); }   // (mv_set_state_obs, mv_set_scene_obs)
     // (mv_set_still_frames: the env stepped -- stale where the draw mask leaves it out, drawn and fresh otherwise; nobody reads the byte in this launch)
     if constexpr (MASKED) if (!env_drawn(gv, env)) {   // (mv_set_draw_mask; uniform)
         if (gv.still != nullptr && threadIdx.x == 0) still_store(gv.still + env, 1);
@@ -421,7 +472,7 @@ __device__ __forceinline__ void step_ticks_body(const Args &a, int W, int H)
         tick_barrier<A_MAX>();
         if constexpr (MASKED) if (steps) after_tick(gv, env, o.left, o.tl);
         // (mv_set_state_obs, mv_set_scene_obs) the ticks of a launch without any frame setup reach their rows only where the view carries some (uniform)
-        if constexpr (MASKED) if (FRAMES != FRAMES_NONE || obs_rows_on(gv)) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); }
+        if constexpr (MASKED) if (FRAMES != FRAMES_NONE || obs_rows_on(gv)) { state_obs_write<A_MAX>(gv, env); scene_obs_write(gv, env); entity_obs_write(gv, env); }
         if (frames) {
             env_frames<S, A_MAX, MASKED>(gv, env, W, H, o);
             if constexpr (A_MAX > 1) __syncthreads();   // every frame of the env is set up (the state they read) before the next tick changes it
@@ -462,7 +513,7 @@ __device__ __forceinline__ void step_ticks_pipe_body(const Args &a, int W, int H
             }
             __syncthreads();                              // A(j)
             // (mv_set_state_obs, mv_set_scene_obs) tick j's rows: behind A(j), in front of tick j + 1, whose write-back comes behind B(j) and is this wave's own
-            if constexpr (MASKED) { state_obs_write<1>(a.view(j), env); scene_obs_write(a.view(j), env); }
+            if constexpr (MASKED) { state_obs_write<1>(a.view(j), env); scene_obs_write(a.view(j), env); entity_obs_write(a.view(j), env); }
         }
         __syncthreads();                                  // B(n - 1): the last frame setup's
     } else {

@@ -225,6 +225,9 @@ struct GymView {
     // state_obs: behind the tick the MASKED step bodies store the env's row here (mv_step_kernels.h: scene_obs_write), and the stepping call's one publication
     // launch carries the rows to the caller's buffer (mv_obs_rows.hip).  null: off.  A field of the per-slot views (mv_gym::gvp), like state_obs.
     float *scene_obs;
+    // mv_set_entity_obs: [N][E][8] float32, this tick's staging rows of the entity observations (mv_entity_obs.h has the record and E), written and published
+    // like scene_obs (mv_step_kernels.h: entity_obs_write).  null: off.  A field of the per-slot views (mv_gym::gvp), like state_obs.
+    float *entity_obs;
     // mv_macro_step: [N] ticks each env may still step in this call (0: its macro step is over -- its ticks are frozen ticks), written by the MASKED step
     // bodies behind every tick the env stepped in (mv_step_kernels.h: after_tick; mv_macro_step.h has the rule); null: no macro step in flight.  Set by the
     // views of a macro step's ticks only (mv_api_step.hip).
@@ -234,11 +237,11 @@ struct GymView {
     // FRAME_STILL.  null: off, every env is drawn on every pass.  Set by the stepping calls only (mv_api_step.hip); the union launches never see a non-null one.
     uint8_t *still;
 };
-// The view carries a per-gym option -- a step mask, an episode budget, a draw mask, staging rows of state or scene observations, a macro step's ticks left,
+// The view carries a per-gym option -- a step mask, an episode budget, a draw mask, staging rows of state, scene or entity observations, a macro step's ticks left,
 // stale bytes: its launches take the MASKED instantiations of the step bodies; the gyms without one launch the kernels they always launched (mv_step.hip).
 __host__ inline bool view_has_options(const GymView &gv)
 {
-    return gv.step_mask || gv.budget || gv.draw_mask || gv.state_obs || gv.scene_obs || gv.macro_tl || gv.still;
+    return gv.step_mask || gv.budget || gv.draw_mask || gv.state_obs || gv.scene_obs || gv.entity_obs || gv.macro_tl || gv.still;
 }
 
 // The n <= 8 consecutive ticks of a multi-tick step launch (mv_step.hip: step_ticks_kernel, and every mv_step_*.hip), the same envs in all of them: their views

@@ -108,6 +108,9 @@ SYMBOLS = [
     ("mv_debug_state_obs_host", C.c_int, [_P, _P, _P]), ("mv_get_output_ring", C.c_int, [_P]),
     ("mv_set_scene_obs", C.c_int, [_P, _P]), ("mv_get_scene_obs", C.c_int, [_P]), ("mv_get_scene_observation", C.c_int, [_P, _I, _P]),
     ("mv_debug_scene_obs_host", C.c_int, [_I, _P, _P, _P, _I, _P, _P]),
+    ("mv_entity_obs_rows", C.c_int, [_P]), ("mv_entity_obs_layout", C.c_int, [_P, _P]), ("mv_set_entity_obs", C.c_int, [_P, _P]),
+    ("mv_get_entity_obs", C.c_int, [_P]), ("mv_get_entity_observation", C.c_int, [_P, _I, _P]),
+    ("mv_debug_entity_obs_host", C.c_int, [_I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     ("mv_macro_step", C.c_int, [_P, _I, _P, _P, _I]), ("mv_macro_step_host", C.c_int, [_P, _I, _P, _P, _I]),
     ("mv_debug_episode_log_macro_host", C.c_int, [_P, _P, _P, _I, _I, _I, _I, _U, _P, _P, _P, C.POINTER(_U), C.POINTER(_U), _P, _P, _P]),
     ("mv_debug_macro_rule_host", C.c_int, [_P, _P, _P, _P, _I, _I, _P, _P, _P]), ("mv_debug_macro_fold_host", C.c_int, [_P, _I, _I, _P]),
@@ -312,6 +315,115 @@ def debug_scene_obs_host(scenario, env_header, terrain=None, rewards=None, footb
     if lib.mv_debug_scene_obs_host(int(scenario), ptr(h), ptr(t), ptr(r), 0 if r is None else r.size // 4, ptr(f), out.ctypes.data) != 0:
         raise RuntimeError(lib.mv_last_error().decode())
     return out
+
+
+# include/megaverse_hip.h: MV_ENTITY_OBS_FLOATS and the columns of an entity-observation row (mv_set_entity_obs; megaverse_amd/csrc/mv_entity_obs.h has the table
+# of every scenario's rows).  seg_word: the row's segmentation word class << 12 | instance as a float, 0 for an empty row; centre and half extents in world units.
+MV_ENTITY_OBS_FLOATS = 8
+ENTITY_OBS_FIELDS = {name: i for i, name in enumerate(("seg_word", "x", "y", "z", "half_x", "half_y", "half_z", "state"))}
+ENTITY_GROUPS = ("terrain", "objects", "rewards", "agents")   # mv_entity_obs_layout's order: the label rule's groups
+# mv_types.h: the SCN_* family of a scenario name, and the capacities the rows come from
+_SCN = {"towerbuilding": 0, "obstacleseasy": 1, "obstaclesmedium": 1, "obstacleshard": 1, "obstacleswalls": 1, "obstaclessteps": 1, "obstacleslava": 1,
+        "collect": 2, "rearrange": 3, "sokoban": 4, "empty": 5, "hexmemory": 6, "hexexplore": 7, "boxagone": 8, "football": 9}
+_ENTITY_TERRAIN = {0: (1, "BUILDING_ZONE"), 1: (16, "EXIT"), 3: (8, "TARGET"), 4: (80, "EXIT")}      # family -> (rows, class of the first kind)
+_ENTITY_REWARDS = {1: (16, "COLLECTABLE"), 2: (96, "COLLECTABLE"), 6: (128, "COLLECTABLE"), 7: (128, "COLLECTABLE"), 9: (1, "BALL")}
+_ENTITY_OBJECTS = (0, 1, 2, 3, 4)                                                                      # the families with movable objects (80 rows)
+
+
+def scenario_family(scenario):
+    """a scenario name (any case) or an SCN_* family id -> the family id (ValueError: unknown)"""
+    if isinstance(scenario, (int, np.integer)) and not isinstance(scenario, (bool, np.bool_)) and 0 <= int(scenario) <= 9:
+        return int(scenario)
+    fam = _SCN.get(str(scenario).casefold())
+    if fam is None:
+        raise ValueError(f"unknown scenario {scenario!r}")
+    return fam
+
+
+def _entity_groups(scenario, num_agents):
+    """-> [(name, base row, rows, class value of the group's first kind or 0)] in ENTITY_GROUPS' order"""
+    fam, A = scenario_family(scenario), int(num_agents)
+    if not 1 <= A <= 8:
+        raise ValueError(f"entity_layout: 1 <= num_agents <= 8 required, got {num_agents!r}")
+    sizes = [_ENTITY_TERRAIN.get(fam, (0, "NONE")), (80, "MOVABLE") if fam in _ENTITY_OBJECTS else (0, "NONE"), _ENTITY_REWARDS.get(fam, (0, "NONE")), (A, "AGENT")]
+    out, at = [], 0
+    for name, (rows, cls) in zip(ENTITY_GROUPS, sizes):
+        out.append((name, at, rows, SEG_CLASSES[cls]))
+        at += rows
+    return out
+
+
+def entity_layout(scenario, num_agents):
+    """the rows of an entity-observation tensor (MegaverseGym.set_entity_obs): group name ('terrain', 'objects', 'rewards', 'agents') -> slice of row indices,
+    fixed for a scenario and an agent count; an empty slice: the scenario has no such group.  sum of the lengths = MegaverseGym.entity_rows()"""
+    return {name: slice(base, base + rows) for name, base, rows, _ in _entity_groups(scenario, num_agents)}
+
+
+def entity_rows(scenario, num_agents):
+    """E: the rows per env of an entity-observation tensor"""
+    return sum(rows for _, _, rows, _ in _entity_groups(scenario, num_agents))
+
+
+def entity_row_of(words, scenario, num_agents):
+    """the words of an 'instance' label plane (int16 / int32 torch tensor, or numpy array, any shape) -> the row index of each word's entity in the env's
+    [E, 8] entity rows, same shape, int32 (numpy) / int64 (torch): rows are slot-addressed, so this is arithmetic -- group base + instance.  -1: the word's
+    class has no rows (NONE, FLOOR, STRUCTURE, FURNITURE, HUD, a class of another scenario), its instance lies beyond the group -- and Sokoban's EXIT, the one
+    compacted group: find its row by comparing the word with column 0 of the group's rows."""
+    groups = {name: (base, rows) for name, base, rows, _ in _entity_groups(scenario, num_agents)}
+    fam = scenario_family(scenario)
+    by_class = {}   # class value -> (base, rows)
+    if fam != 4:
+        for cls in {0: ("BUILDING_ZONE",), 1: ("EXIT", "LAVA"), 3: ("TARGET",)}.get(fam, ()):
+            by_class[SEG_CLASSES[cls]] = groups["terrain"]
+    for cls in ("MOVABLE", "CARRIED"):
+        by_class[SEG_CLASSES[cls]] = groups["objects"]
+    for cls in {1: ("COLLECTABLE",), 2: ("COLLECTABLE", "HAZARD"), 6: ("COLLECTABLE",), 7: ("COLLECTABLE",), 9: ("BALL",)}.get(fam, ()):
+        by_class[SEG_CLASSES[cls]] = groups["rewards"]
+    by_class[SEG_CLASSES["AGENT"]] = groups["agents"]
+    is_np = isinstance(words, np.ndarray)
+    if is_np:
+        w = (words.view(np.uint16) if words.dtype == np.int16 else words).astype(np.int32) & 0xffff
+        out = np.full(w.shape, -1, np.int32)
+    else:
+        import torch
+        w = words.to(torch.int64) & 0xffff
+        out = torch.full_like(w, -1)
+    cls, inst = w >> SEG_INSTANCE_BITS, w & 4095
+    for c, (base, rows) in by_class.items():
+        hit = (cls == c) & (inst < rows)
+        out[hit] = (base + inst[hit]).to(out.dtype) if not is_np else (base + inst[hit]).astype(out.dtype)
+    return out
+
+
+def debug_entity_obs_host(scenario, num_agents, env_header, agents, terrain=None, items=None, soko=None, objects=None, rewards=None, hex_objs=None,
+                          football_state=None):
+    """mv_debug_entity_obs_host: the entity-observation record on the CPU (no device): the SCN_* family id, the agent count, the 128 bytes of one EnvHeader,
+    128 bytes per AgentState, and -- what the scenario does not read may be None -- the 512 bytes of 16 TerrainBox, the 256 of 8 ArrangementItem, the 1024
+    Sokoban cell bytes, the 320 of 80 MovableObject, 4 bytes per MovableObject of the reward list, the 4096 of 128 HexRec, the 64 of one FootballState
+    (megaverse_amd/csrc/mv_types.h) -> the env's rows, float32 [E, 8]"""
+    lib = load_library()
+    def raw(x, size, what):
+        if x is None:
+            return None
+        b = np.ascontiguousarray(np.frombuffer(bytes(x), np.uint8))
+        if size is not None and b.size != size:
+            raise ValueError(f"debug_entity_obs_host: {what} is {size} bytes")
+        return b
+    A = int(num_agents)
+    E = entity_rows(scenario, A)
+    h, a = raw(env_header, 128, "an EnvHeader"), raw(agents, 128 * A, "num_agents AgentStates")
+    t, it, sk = raw(terrain, 512, "a terrain list"), raw(items, 256, "an item list"), raw(soko, 1024, "Sokoban's cells")
+    o, hx, f = raw(objects, 320, "an object list"), raw(hex_objs, 4096, "a HexRec list"), raw(football_state, 64, "a FootballState")
+    r = raw(rewards, None, "a reward list")
+    if h is None or a is None or (r is not None and r.size % 4):
+        raise ValueError("debug_entity_obs_host: an EnvHeader and the AgentStates are required, and a reward list is 4 bytes per object")
+    ptr = lambda b: None if b is None or b.size == 0 else b.ctypes.data   # noqa: E731
+    out = np.empty((E, MV_ENTITY_OBS_FLOATS), np.float32)
+    if lib.mv_debug_entity_obs_host(scenario_family(scenario), A, ptr(h), ptr(t), ptr(it), ptr(sk), ptr(o), ptr(r), 0 if r is None else r.size // 4, ptr(hx),
+                                    ptr(f), ptr(a), out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
 
 # mv_episode_record (include/megaverse_hip.h): one finished episode of one agent, 24 bytes
 EPISODE_RECORD_DTYPE = np.dtype({"names": ["agent", "length", "end_tick", "true_objective", "ret"],
@@ -680,6 +792,21 @@ def check_scene_obs(buf, entries, num_envs, device):
     return _check_obs_rows(buf, entries, num_envs, MV_SCENE_OBS_FLOATS, device, 'set_scene_obs')
 
 
+def check_entity_obs(buf, entries, num_envs, rows, device):
+    """the argument check of MegaverseGym.set_entity_obs for a tensor: contiguous torch.float32 of shape (entries, num_envs, rows, 8) on CUDA device `device`,
+    16-byte aligned; entries None: any number of entries (the check made before the gym is asked for its ring count)"""
+    got = tuple(getattr(buf, 'shape', ()))
+    shape = ((got[0] if len(got) == 4 else 1) if entries is None else int(entries), int(num_envs), int(rows), MV_ENTITY_OBS_FLOATS)
+    contiguous = getattr(buf, 'is_contiguous', None)
+    dev = getattr(buf, 'device', None)
+    index = getattr(dev, 'index', None)
+    if not hasattr(buf, 'data_ptr') or got != shape or str(getattr(buf, 'dtype', None)) != 'torch.float32' \
+            or not getattr(buf, 'is_cuda', False) or not (callable(contiguous) and contiguous()) or (index is not None and int(index) != int(device)):
+        raise ValueError(f'set_entity_obs: the buffer must be a contiguous float32 CUDA tensor of shape {shape} on device {int(device)}, '
+                         f"got {getattr(buf, 'dtype', type(buf).__name__)} {tuple(getattr(buf, 'shape', ()))} on {dev if dev is not None else 'no device'}")
+    return buf
+
+
 def _check_obs_rows(buf, entries, num_rows, floats, device, who):
     """check_state_obs / check_scene_obs: a row record's tensor, (entries, num_rows, floats), for the setter `who`"""
     got = tuple(getattr(buf, 'shape', ()))
@@ -898,6 +1025,7 @@ class MegaverseGym:
         self._draw_mask_held = None  # set_draw_mask: the caller's device mask, kept until it is replaced or detached
         self._state_obs = None       # set_state_obs: the attached tensor
         self._scene_obs = None       # set_scene_obs: the attached tensor
+        self._entity_obs = None      # set_entity_obs: the attached tensor
         self._depth_obs = None       # set_depth_obs: the attached tensor
         self._seg_obs = None         # set_seg_obs: the attached tensor
         self._ring_ticks = 0         # ticks stepped through this object since set_output_ring (the library's own count: which entry the last tick went to)
@@ -1272,6 +1400,58 @@ class MegaverseGym:
         """-> numpy float32 [32]: the last tick's row of one env (waits for the gym's stream)"""
         out = np.empty(MV_SCENE_OBS_FLOATS, np.float32)
         self._ck(self._lib.mv_get_scene_observation(self._g, int(env_idx), out.ctypes.data))
+        return out
+
+    def entity_rows(self):
+        """-> E: the rows per env of the entity observations (mv_entity_obs_rows), fixed for the gym's scenario and agent count"""
+        return self._ck(self._lib.mv_entity_obs_rows(self._g))
+
+    def entity_layout(self):
+        """-> {group name: slice of rows} as the library states it (mv_entity_obs_layout; megaverse_amd.entity_layout gives the same without a gym)"""
+        out = np.zeros((4, 3), np.int32)
+        self._ck(self._lib.mv_entity_obs_layout(self._g, out.ctypes.data))
+        return {name: slice(int(b), int(b + n)) for name, (b, n, _) in zip(ENTITY_GROUPS, out)}
+
+    def set_entity_obs(self, buf=True):
+        """Entity observations (include/megaverse_hip.h: mv_set_entity_obs): the objects themselves.  Every tick of every later stepping call leaves
+        entity_rows() rows of 8 float32 per ENV (ENTITY_OBS_FIELDS: the entity's segmentation word, centre, half extents, state; entity_layout: which rows are
+        terrain, movable objects, collectables, agents; the state AFTER the tick) in entry t % entries of a float32 CUDA tensor [entries, num_envs, E, 8],
+        entries = the output ring's count, or 1 without a ring.  Rows are slot-addressed: a record keeps its row, one that does not exist is all zero, and
+        entity_row_of maps the words of an 'instance' label plane (set_seg_obs) to rows.  True allocates the tensor on the gym's device and returns it; a
+        tensor is checked (ValueError) and attached; None detaches.  Nothing waits on the host.  While attached, set_output_ring is refused."""
+        if buf is None:
+            self._ck(self._lib.mv_set_entity_obs(self._g, None))
+            self._entity_obs = None
+            return None
+        rows = entity_rows(self.scenario, self.num_agents_per_env)
+        if buf is not True:
+            check_entity_obs(buf, None, self.num_envs, rows, self.device)   # (what needs no gym first)
+        entries = max(1, self._ck(self._lib.mv_get_output_ring(self._g)))
+        if buf is True:
+            import torch
+            buf = torch.zeros((entries, self.num_envs, rows, MV_ENTITY_OBS_FLOATS), dtype=torch.float32, device=f'cuda:{self.device}')
+        else:
+            check_entity_obs(buf, entries, self.num_envs, rows, self.device)
+        self._ck(self._lib.mv_set_entity_obs(self._g, _P(int(buf.data_ptr()))))
+        self._entity_obs = buf
+        return buf
+
+    def entity_obs_ring(self):
+        """-> the tensor set_entity_obs attached, [entries, num_envs, E, 8] (entry t % entries: what tick t left), or None"""
+        return self._entity_obs
+
+    def entity_obs(self):
+        """-> the entry of the last tick, (num_envs, E, 8): a view of the attached tensor, valid in the order of the gym's stream; None with nothing attached.
+        With an output ring: the entry the last tick stepped through this object went to (entity_obs_ring has them all)"""
+        if self._entity_obs is None:
+            return None
+        entries = int(self._entity_obs.shape[0])   # (ticks stepped by calling the library directly, past this object, are not counted)
+        return self._entity_obs[(max(1, self._ring_ticks) - 1) % entries]
+
+    def get_entity_observation(self, env_idx):
+        """-> numpy float32 [E, 8]: the last tick's rows of one env (waits for the gym's stream)"""
+        out = np.empty((entity_rows(self.scenario, self.num_agents_per_env), MV_ENTITY_OBS_FLOATS), np.float32)
+        self._ck(self._lib.mv_get_entity_observation(self._g, int(env_idx), out.ctypes.data))
         return out
 
     def set_depth_obs(self, buf=True, dtype=None):

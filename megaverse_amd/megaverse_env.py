@@ -18,7 +18,7 @@ Differences, all additive:
 import numpy as np
 
 from . import spaces
-from .extension import MegaverseGym, SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS, STATE_OBS_FIELDS, render_mode_of, set_megaverse_log_level
+from .extension import ENTITY_OBS_FIELDS, MegaverseGym, SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS, STATE_OBS_FIELDS, render_mode_of, set_megaverse_log_level
 
 MEGAVERSE8 = ['TowerBuilding', 'ObstaclesEasy', 'ObstaclesHard', 'Collect', 'Sokoban', 'HexMemory', 'HexExplore', 'Rearrange']
 OBSTACLES_MULTITASK = ['ObstaclesWalls', 'ObstaclesSteps', 'ObstaclesLava', 'ObstaclesEasy', 'ObstaclesHard']
@@ -69,7 +69,7 @@ def check_sequence_actions(actions, num_agents):
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
                  img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1,
-                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False):
+                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False):
         if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
         # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
@@ -121,6 +121,11 @@ class MegaverseEnv:
         self._scene_on = bool(scene_obs)
         if self._scene_on:
             self.env.set_scene_obs(True)
+        # entity_obs: every tick leaves E rows of 8 float32 per ENV (ENTITY_OBS_FIELDS: segmentation word, centre, half extents, state of every terrain box,
+        # movable object, collectable and agent; megaverse_amd.entity_layout has the rows) in a CUDA tensor (mv_set_entity_obs), read with self.entity_obs()
+        self._entity_on = bool(entity_obs)
+        if self._entity_on:
+            self.env.set_entity_obs(True)
         # depth_obs (True: float32, "float16"): every drawn frame leaves its per-pixel camera depth in a CUDA tensor (mv_set_depth_obs), read with
         # self.depth_obs(); the gym observation space stays the RGB one
         if depth_obs is not False and depth_obs is not True and depth_obs not in ("float16", "float32"):
@@ -168,6 +173,16 @@ class MegaverseEnv:
             raise RuntimeError("scene_obs: create the env with scene_obs=True")
         return buf[self._seq[0][0] - 1 if self._seq is not None else 0]
 
+    ENTITY_OBS_FIELDS = ENTITY_OBS_FIELDS   # column name -> index of an entity_obs() row
+
+    def entity_obs(self):
+        """the last tick's entity observations: float32 (num_envs, E, 8) on the device, columns ENTITY_OBS_FIELDS, rows megaverse_amd.entity_layout(scenario,
+        num_agents_per_env) -- a view of the attached buffer, under state_obs()'s rules: ask again after every call.  Needs MegaverseEnv(..., entity_obs=True)."""
+        buf = self.env.entity_obs_ring()
+        if buf is None:
+            raise RuntimeError("entity_obs: create the env with entity_obs=True")
+        return buf[self._seq[0][0] - 1 if self._seq is not None else 0]
+
     def depth_obs(self):
         """the last tick's depth planes: float32 or float16 (num_envs, num_agents_per_env, H, W) on the device -- planar camera depth in world units, 0 where a
         ray hits nothing, row 0 the bottom row -- a view of the attached buffer, under state_obs()'s rules: ask again after every call.  A tick that drew no
@@ -195,6 +210,8 @@ class MegaverseEnv:
             self.env.set_state_obs(None)
         if self._scene_on:
             self.env.set_scene_obs(None)
+        if self._entity_on:
+            self.env.set_entity_obs(None)
         if self._depth_dtype:
             self.env.set_depth_obs(None)
         if self._seg_fmt:
@@ -208,6 +225,8 @@ class MegaverseEnv:
             self.env.set_state_obs(True)
         if self._scene_on:
             self.env.set_scene_obs(True)
+        if self._entity_on:
+            self.env.set_entity_obs(True)
 
     @staticmethod
     def generate_action_space(action_space_sizes):
