@@ -670,12 +670,49 @@ int mv_get_obs_layout(const mv_gym *g);
 int mv_set_pipelining(mv_gym *g, int32_t on);
 int mv_get_pipelining(const mv_gym *g);
 
-/* setRenderResolution/drawHires/getHiresObservation (:145-178,203-207); drawOverview is a no-op
+/* setRenderResolution/drawHires/getHiresObservation (:145-178,203-207); drawOverview with no overview attached is a no-op
  * exactly like a reference build without WITH_GUI (:180-201) */
 int mv_set_render_resolution(mv_gym *g, int32_t w, int32_t h);
 int mv_draw_hires(mv_gym *g);
 int mv_get_hires_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, uint8_t *out_host);
 int mv_draw_overview(mv_gym *g);
+
+/* Overview cameras (opt-in; the reference's Overview camera, rendering/src/render_utils.cpp:34-55, without its window).  One camera per env,
+ * free in the world or attached to an agent, drawn by mv_draw_overview into a buffer of its own with the exact pass's arithmetic -- whatever the pixel mode,
+ * the observation layout, the draw mask or the still-frame option say, as mv_draw_hires.  Projection, clip range [0.01, 120] and light are the agents'
+ * (horizontal 100 degrees at aspect 128/72 whatever w and h; the reference's overview range (0.1, 600) is not adopted: DESIGN.md 7).  Nothing a stepping call
+ * launches, reads or writes changes: the overview owns its lists, rectangles, headers, counts, cost bins and cameras (csrc/mv_overview.h has the rule and the
+ * arrays, counted in mv_arena_bytes from the first attach on and freed by mv_close).
+ * mv_camera: agent = -1, FREE: eye is the world position, c the row-major 3x3 whose columns are the camera's right / up / back axes in the world, taken as
+ * given.  agent = k, AGENT: the camera is agent k's own, built from its state on the device at draw time exactly as its observation's; eye is then an offset
+ * in that camera's axes (right, up, back) -- all zero: no arithmetic at all, the agent's very eye -- and c is ignored.  MV_CAMERA_FIRST_PERSON (AGENT only):
+ * the agent's capsule and eyes box are not drawn (its time bar and what it carries are): the rule of its own observation.  Without it, and in FREE mode,
+ * every part of every agent is drawn.
+ * mv_set_overview: attach (device_rgba: the caller's [N][h][w] RGBA8, row 0 the bottom row; NULL: gym-owned), 1 <= w, h <= 1024; w = h = 0: detach.  Before
+ * any camera is set every env has the reference's pose (mv_overview_default_camera).  mv_set_overview_cameras: [N] device records, copied on the gym's stream
+ * (NULL: back to the default pose); an agent index outside [-1, A) is taken as FREE with the record's pose and counted.  mv_set_overview_cameras_host: the
+ * same from host memory (free again on return), refusing such records.  mv_draw_overview: attached, the frame setup and the pass of all N envs from the
+ * state as it stands, behind every step launch enqueued so far, on the gym's stream, no host wait; not attached: nothing, returns 0.
+ * mv_overview_dropped: low 32 bits: primitives that did not fit an env's list (capacity 256 / 1024 / 2048 by the scenario's slot count: mv_overview_capacity)
+ * since the attach; high 32 bits: clamped agent indices; one host wait.  Refused for a gym of an mv_group. */
+enum { MV_CAMERA_FIRST_PERSON = 1 };
+typedef struct mv_camera {
+    float   eye[3];   /* FREE: world position.  AGENT: offset from the agent's eye in the agent camera's axes (right, up, back) */
+    int32_t agent;    /* -1: FREE;  0 .. A-1: AGENT -- the camera is that agent's own, built from its state on the device at draw time */
+    float   c[9];     /* FREE: row-major 3x3, columns = right / up / back in world axes (taken as given, not normalised).  AGENT: ignored */
+    int32_t flags;    /* bit 0 MV_CAMERA_FIRST_PERSON (AGENT only) */
+    int32_t pad[2];   /* 0 */
+} mv_camera;
+int mv_set_overview(mv_gym *g, int32_t w, int32_t h, void *device_rgba);
+int mv_set_overview_cameras(mv_gym *g, const mv_camera *device_cams);
+int mv_set_overview_cameras_host(mv_gym *g, const mv_camera *cams);
+int mv_get_overview_observation(mv_gym *g, int32_t env_idx, uint8_t *out_host);
+void *mv_overview_device_ptr(mv_gym *g);
+int mv_overview_dropped(mv_gym *g, int64_t *out);
+int mv_overview_capacity(const mv_gym *g);                                   /* list capacity per env of this gym's scenario: 256, 1024 or 2048 */
+int mv_overview_default_camera(mv_camera *out);                              /* the derived reference pose, host only */
+/* the camera the device would build from cam (and, AGENT mode, from the 128-byte state record of its agent), on the host: eye[3] then c[9] */
+int mv_debug_overview_camera_host(const mv_camera *cam, const void *agent_state, float *out_eye3_c9);
 
 /* getRewardShaping/setRewardShaping (:208-217); one key at a time across the C boundary */
 int mv_num_reward_shaping_keys(const mv_gym *g);

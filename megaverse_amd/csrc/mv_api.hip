@@ -792,6 +792,7 @@ int mv_close(mv_gym *g)
     episode_budget_free(g);
     macro_step_free(g);
     still_frames_free(g);
+    overview_free(g);
     if (g->arena) (void)hipFree(g->arena);
     if (g->hiresObs) (void)hipFree(g->hiresObs);
     if (g->hBlobs) (void)(g->blobsOnDevice ? hipFree(g->hBlobs) : hipHostFree(g->hBlobs));
@@ -1485,8 +1486,6 @@ int mv_get_hires_observation(mv_gym *g, int32_t env, int32_t agent, uint8_t *out
     HIP_TRY(hipStreamSynchronize(g->stream));
     return 0;
 }
-
-int mv_draw_overview(mv_gym *g) { return check(g) ? -1 : 0; }
 
 int mv_num_reward_shaping_keys(const mv_gym *g) { return g ? g->numShaping : 0; }
 const char *mv_reward_shaping_key(const mv_gym *g, int32_t i) { return (g && i >= 0 && i < g->numShaping) ? g->shapingKeys[i] : nullptr; }

@@ -17,6 +17,8 @@
 //                     (mv_seg_obs.h: the record and its rule; mv_raster.hip: the kernels)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 //   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
+//   mv_overview.hip   overview cameras: attaching the buffer, the overview's own arrays, the cameras' two forms, mv_draw_overview (mv_overview.h: the rule;
+//                     mv_raster.hip: the kernels)
 //   mv_still_frames.hip  still frames: switching the option, the memset behind calls that change what frames show, the carry launch (mv_still_frames.h: the rule)
 // The persistent per-gym options are stated once, below mv_gym: gym_options (who refuses what, in which words) and fill_view_options (what a view carries).
 // mv_staging.h holds the two ways the host forms' values reach the device (StagingPool, StagingPair).
@@ -49,6 +51,7 @@
 #include "mv_episode_budget.h"
 #include "mv_macro_step.h"
 #include "mv_fork.h"
+#include "mv_overview.h"
 
 namespace mv {
 // TowerBuilding: tops every env's ring of drawn episodes up (mv_reset.hip)
@@ -147,6 +150,21 @@ struct SegObs {
     int format = 0, entries = 0;
     size_t entryBytes = 0;
     void *entry(unsigned long long tick) const { return buf ? (uint8_t *)buf + (size_t)(tick % (unsigned long long)entries) * entryBytes : nullptr; }
+};
+}  // namespace mvapi
+
+namespace mvapi {
+// The overview of a gym (mv_overview.hip).  buf: the [N][h][w] RGBA8 frames mv_draw_overview writes (null: not attached) -- the caller's, or `owned`, the gym's;
+// arrays: the overview's own lists, rectangles, headers, counts, cost bins, frame order, cameras and dropped word (mv_overview.h: overview_layout), allocated
+// by the first attach, kept until mv_close and counted in mv_arena_bytes, as the owned frames are while they exist.  The host form's records travel through the pool.
+struct OverviewState {
+    uint32_t *buf = nullptr, *owned = nullptr;
+    int w = 0, h = 0, cap = 0;
+    bool costOrder = true;   // MV_OVERVIEW_ORDER=0 at the first attach: frames are drawn in env order, no frame-order launch (profiles/overview_measured.txt)
+    size_t ownedBytes = 0;
+    uint8_t *arrays = nullptr;
+    OverviewLayout layout{};
+    StagingPool pool;
 };
 }  // namespace mvapi
 
@@ -317,6 +335,8 @@ struct mv_gym {
     // mv_set_seg_obs: the caller's label planes, written by the passes of a gym in exact pixel mode and -- fast mode -- by the one launch behind its passes,
     // which then writes the depth planes too
     SegObs seg;
+    // mv_set_overview: the overview cameras' frames and arrays
+    OverviewState overview;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
     // budgetLeft [N], what the step kernels read and write (GymView::budget, through the stepping calls' views, while budgetOn); budgetHalted, the count of
     // zeros in it; budgetMirror [N], the episode log's own copy, advanced by the log's update tick by tick.  The host form's values travel through a pool of
@@ -360,7 +380,7 @@ struct GymOption {
     const char *memberNone;   // attach_check: "whose union launches <memberNone>"
     bool (*on)(const mv_gym *);
 };
-enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_DEPTH_OBS, OPT_SEG_OBS, OPT_ENTITY_OBS, OPT_COUNT };
+enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_DEPTH_OBS, OPT_SEG_OBS, OPT_ENTITY_OBS, OPT_OVERVIEW, OPT_COUNT };
 #define MV_OPT_ON(expr) +[](const mv_gym *g) -> bool { return expr; }
 inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_step_mask", "a step mask attached", "read none", "detach it first", "detach the mask first", "read no step mask", MV_OPT_ON(g->stepMask.live)},
@@ -372,6 +392,7 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_depth_obs", "depth observations attached", "write none", "detach them first", "detach them first", "write no depth observations", MV_OPT_ON(g->depth.buf)},
     {"mv_set_seg_obs", "segmentation observations attached", "write none", "detach them first", "detach them first", "write no segmentation observations", MV_OPT_ON(g->seg.buf)},
     {"mv_set_entity_obs", "entity observations attached", "write none", "detach them first", "detach them first", "write no entity observations", MV_OPT_ON(g->entityRows.buf)},
+    {"mv_set_overview", "an overview attached", "draw none", "detach it first", "detach it first", "draw no overview", MV_OPT_ON(g->overview.buf)},
 };
 #undef MV_OPT_ON
 // What a stepping call's view of g carries of the options (the rows of the two records are fields of the per-slot views already: mv_gym::gvp); macro: the view
@@ -427,6 +448,7 @@ void macro_step_free(mv_gym *g);       // mv_close (mv_macro_step.hip)
 // draws (off: nothing).  carry: the rows of the still frames of one stepping call's n rendered ticks (views[j * stride], outs[j * stride]) from the ring
 // entries that hold them, one launch on the caller's stream behind the call's passes
 void still_frames_free(mv_gym *g);     // mv_close
+void overview_free(mv_gym *g);         // mv_close (mv_overview.hip)
 int still_frames_touch(mv_gym *g);
 int still_frames_carry(mv_gym *g, const GymView *views, const OutPtrs *outs, int stride, int n);
 // mv_macro_step.hip: the staged outputs of the k ticks in slots q0 .. q0 + k - 1 folded into ONE entry o -- rewards summed in tick order (mv_macro_step.h:

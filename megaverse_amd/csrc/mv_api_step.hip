@@ -753,7 +753,7 @@ int mv_recommended_pass_overlap(const mv_gym *g)
     return 1;
 }
 
-int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMask.ownedBytes + g->drawMask.ownedBytes + g->budgetBytes + g->macroBytes + g->stillBytes + g->sceneRows.stageBytes + g->entityRows.stageBytes) : 0; }
+int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMask.ownedBytes + g->drawMask.ownedBytes + g->budgetBytes + g->macroBytes + g->stillBytes + g->sceneRows.stageBytes + g->entityRows.stageBytes + g->overview.layout.bytes + g->overview.ownedBytes) : 0; }
 
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index)
 {   // several gyms of one job (MultiTaskGym: one per scenario, one stream each) stepped by one call: at eight sub-gyms the per-call cost of

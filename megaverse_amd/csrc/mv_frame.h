@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "mv_math.h"
+#include "mv_overview.h"
 #include "mv_rearrange.h"
 #include "mv_types.h"
 
@@ -207,21 +208,34 @@ __device__ __forceinline__ float depth_class_floor(int c) { return __uint_as_flo
 // PIPE (the software-pipelined multi-tick step kernels, mv_step_kernels.h: step_ticks_pipe_body): this wave sets tick j's frame up WHILE the env's tick wave
 // computes tick j + 1; everything read from the simulator state (header, agents, box / object / reward records) is loaded before one workgroup
 // barrier -- in the last round of slots, behind its record loads --, which the tick wave meets before it writes tick j + 1's state back.
-template <int THREADS, bool WAVE_LOCAL, bool PIPE = false>
-__device__ __forceinline__ void frame_setup_body(const GymView &gv, const int frame, const int W, const int H, FrameScratch &fs, DepthSortScratch *ds = nullptr)
+// OVERVIEW (overview_setup_kernel, mv_raster.hip; mv_overview.h has the rule): `frame` is an env, seen from its overview camera ov->cams[frame].  gv's vis_* /
+// lpt_bucket / vis_hdr fields are the overview's own arrays; the cost histograms and lists of the stepping calls' passes are neither read nor written (the
+// overview's frame order comes from its own lpt_bucket); the frames of reference live in ov_cams -- MAX_CAMS + 1 of them, the last one the overview camera's
+// where it is not an agent's very eye --; a list that overflows is counted in ov->dropped, not flagged in the gym's status words.  Everything else -- slot
+// table, drawables, rectangles, header -- is the code below, shared.  Every other instantiation passes false and compiles what it always did.
+template <int THREADS, bool WAVE_LOCAL, bool PIPE = false, bool OVERVIEW = false>
+__device__ __forceinline__ void frame_setup_body(const GymView &gv, const int frame, const int W, const int H, FrameScratch &fs, DepthSortScratch *ds = nullptr,
+                                                 const OverviewArgs *ov = nullptr, CamL *ov_cams = nullptr)
 {
     static_assert(!WAVE_LOCAL || THREADS == 64, "a wave-local frame setup is one wavefront");
     auto sync = [] { if (WAVE_LOCAL) wave_sync(); else __syncthreads(); };
 #ifdef MV_TICK_TIMING
     unsigned long long tf_last_ = __builtin_amdgcn_s_memtime();
 #endif
-    CamL *const s_cam = fs.cam;
+    CamL *const s_cam = OVERVIEW ? ov_cams : fs.cam;
     int &s_cost = fs.cost;
     int *const s_cnt = fs.cnt;
     unsigned *const s_wbits = fs.wbits;
 
     const int A = gv.num_agents;
-    const int env = frame / A, viewer = frame - env * A;
+    mv_camera ovRec{};
+    OverviewPlan ovPlan{};
+    if constexpr (OVERVIEW) {
+        ovRec = ov->cams[frame];
+        ovPlan = overview_plan(ovRec, A);
+    }
+    const int env = OVERVIEW ? frame : frame / A, viewer = OVERVIEW ? ovPlan.viewer : frame - env * A;
+    const int hidden = OVERVIEW ? ovPlan.hide : viewer;   // the agent whose capsule and eyes box are not drawn: the viewer itself (first person), or none
     const int tid = WAVE_LOCAL ? (int)(threadIdx.x & 63) : (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const EnvHeader *hdr = gv.hdr + env;
     const AgentState *agents = gv.agents + (size_t)env * A;
@@ -260,6 +274,26 @@ __device__ __forceinline__ void frame_setup_body(const GymView &gv, const int fr
     // every box); a flag of their own for the record list costs TowerBuilding's and Collect's multi-agent step kernels a VGPR each.
     const bool hex = scen == SCN_HEX_MEMORY || scen == SCN_HEX_EXPLORE || scen == SCN_BOXAGONE || scen == SCN_FOOTBALL;
     if (hex && tid >= MAX_AGENTS && tid < MAX_CAMS) s_cam[tid] = hex_frame(tid - MAX_AGENTS);
+    if constexpr (OVERVIEW) {   // the overview camera as frame of reference MAX_CAMS (mv_overview.h)
+        sync();
+        if (tid == 0) {
+            CamL cam;
+            if (ovPlan.agent >= 0) {
+                cam = s_cam[ovPlan.agent];
+                if (viewer == MAX_CAMS) {   // a non-zero offset, in the agent camera's axes
+                    const V3 d = mat_mul(cam.c, v3(ovRec.eye[0], ovRec.eye[1], ovRec.eye[2]));
+                    cam.eye[0] += d.x; cam.eye[1] += d.y; cam.eye[2] += d.z;
+                }
+            } else {
+                cam.eye[0] = ovRec.eye[0]; cam.eye[1] = ovRec.eye[1]; cam.eye[2] = ovRec.eye[2];
+#pragma unroll
+                for (int q = 0; q < 9; ++q) cam.c[q] = ovRec.c[q];
+            }
+            cam.origin[0] = cam.origin[1] = cam.origin[2] = 0.0f;
+            s_cam[MAX_CAMS] = cam;
+            if (ovPlan.clamped) atomicAdd(ov->dropped, 1ull << 32);
+        }
+    }
     sync();
     if (tid < A || (hex && tid >= MAX_AGENTS && tid < MAX_CAMS)) {
         const V3 ev = v3(s_cam[viewer].eye[0], s_cam[viewer].eye[1], s_cam[viewer].eye[2]);
@@ -429,13 +463,13 @@ __device__ __forceinline__ void frame_setup_body(const GymView &gv, const int fr
             } else {
                 const int q = slot - slotAgents;
                 const int k = q / 3, part = q - 3 * k;
-                if (part == 0 && k != viewer) {
+                if (part == 0 && k != hidden) {
                     const AgentState a = agents[k];
                     kind = PRIM_CAPSULE;
                     lo[0] = a.pos[0]; lo[1] = (a.pos[1] + 0.05f) + 0.09f; lo[2] = a.pos[2];
                     hi[0] = 0.35f; hi[1] = 0.36f; hi[2] = 0.0f;
                     color = AGENT_COLORS[k % 7];
-                } else if (part == 1 && k != viewer) {
+                } else if (part == 1 && k != hidden) {
                     kind = PRIM_BOX; fr = 1 + k;
                     lo[0] = -0.25f; lo[1] = -0.12f; lo[2] = -0.19f - 0.2f;
                     hi[0] = 0.25f; hi[1] = 0.12f; hi[2] = -0.19f + 0.2f;
@@ -488,7 +522,9 @@ __device__ __forceinline__ void frame_setup_body(const GymView &gv, const int fr
         nVis += tot;
         pos += __popcll(mV & ((1ull << lane) - 1ull));
         MV_TF(3);   // list positions (barrier)
-        if (cls != 0 && pos >= maxVis) atomicOr(&gv.episode_status[gv.num_envs + 1], (int)ST_VISIBLE);   // dropped -- and reported by mv_step
+        if constexpr (OVERVIEW) {
+            if (cls != 0 && pos >= maxVis) atomicAdd(ov->dropped, 1ull);   // dropped -- and counted (mv_overview_dropped)
+        } else if (cls != 0 && pos >= maxVis) atomicOr(&gv.episode_status[gv.num_envs + 1], (int)ST_VISIBLE);   // dropped -- and reported by mv_step
         if (cls != 0 && pos < maxVis) {   // at most vis_stride visible primitives per frame
             Prim p;
             p.meta = (uint32_t)(kind | (fr << 4) | (slot << 8));
@@ -564,7 +600,7 @@ __device__ __forceinline__ void frame_setup_body(const GymView &gv, const int fr
         // and looks its frame up -- no sort kernel, no launch boundary.  The order inside a bin is whatever the atomics made it: it only
         // schedules.  gv.lpt_hists histograms rotate: this pass's raster reads one while the setups of the next steps -- which may run
         // concurrently, on the simulation stream (mv_api.hip) -- fill the following ones, each clearing the one after its own.
-        binPlace = atomicAdd(&gv.lpt_hist[(gv.lpt_parity * LPT_BUCKETS + bin) * LPT_SUBS + (frame & (LPT_SUBS - 1))], 1);
+        if constexpr (!OVERVIEW) binPlace = atomicAdd(&gv.lpt_hist[(gv.lpt_parity * LPT_BUCKETS + bin) * LPT_SUBS + (frame & (LPT_SUBS - 1))], 1);
     }
     {   // frame header
         float *fh = reinterpret_cast<float *>(gv.vis_hdr + (size_t)frame * FRAME_HDR_BYTES);
@@ -588,10 +624,22 @@ __device__ __forceinline__ void frame_setup_body(const GymView &gv, const int fr
         // (sorted: the rounds' depth bounds, above; word 31 -- positions 992 .. 1023, which no short list has -- is the marker's place)
         if (tid < 32 && !sorted) fh[FH_WB + tid] = __uint_as_float(tid == 31 ? 0u : s_wbits[tid]);
     }
-    if (tid == 0) gv.lpt_list[(size_t)(bin * LPT_SUBS + (frame & (LPT_SUBS - 1))) * lpt_sub_capacity(gv.num_envs * gv.num_agents) + binPlace] = frame;
-    // the histogram the NEXT pass fills: last read by a raster pass as many passes ago as there are slots, which this step waited for
-    if (frame == 0 && !gv.lpt_no_clear)
-        for (int i = tid; i < LPT_BUCKETS * LPT_SUBS; i += THREADS) gv.lpt_hist[((gv.lpt_parity + 1) % gv.lpt_hists) * (LPT_BUCKETS * LPT_SUBS) + i] = 0;
+    if constexpr (OVERVIEW) {   // the camera the env was set up with, beside the header
+        if (tid == 0) {
+            OverviewCam oc{};
+            const CamL &cm = s_cam[MAX_CAMS];
+            oc.eye[0] = cm.eye[0]; oc.eye[1] = cm.eye[1]; oc.eye[2] = cm.eye[2];
+#pragma unroll
+            for (int q = 0; q < 9; ++q) oc.c[q] = cm.c[q];
+            oc.viewer = viewer; oc.hide = hidden;
+            ov->out[frame] = oc;
+        }
+    } else {
+        if (tid == 0) gv.lpt_list[(size_t)(bin * LPT_SUBS + (frame & (LPT_SUBS - 1))) * lpt_sub_capacity(gv.num_envs * gv.num_agents) + binPlace] = frame;
+        // the histogram the NEXT pass fills: last read by a raster pass as many passes ago as there are slots, which this step waited for
+        if (frame == 0 && !gv.lpt_no_clear)
+            for (int i = tid; i < LPT_BUCKETS * LPT_SUBS; i += THREADS) gv.lpt_hist[((gv.lpt_parity + 1) % gv.lpt_hists) * (LPT_BUCKETS * LPT_SUBS) + i] = 0;
+    }
     MV_TF(5);   // header, cost bin
     sync();   // the LDS scratch above is reused by the next frame of this workgroup (fused step + setup kernels)
 }

@@ -25,8 +25,8 @@ __device__ __forceinline__ float fmin_sel(float a, float b) { return (b < a) ? b
 __device__ __forceinline__ float fmax_sel(float a, float b) { return (a < b) ? b : a; }
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fmin_sel(fmax_sel(v, lo), hi); }
 
-// sin/cos on |x| <~ 8: two-step pi/2 reduction + cephes-style minimax polynomials
-__device__ __forceinline__ void sincos_poly(float x, float &s, float &c)
+// sin/cos on |x| <~ 8: two-step pi/2 reduction + cephes-style minimax polynomials (host too: mv_debug_overview_camera_host builds a camera with it)
+__host__ __device__ __forceinline__ void sincos_poly(float x, float &s, float &c)
 {
     const float TWO_OVER_PI = 0.636619772f;
     const float PIO2_HI = 1.57079625f;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mv_overview.h"
 #include "mv_types.h"
 
 namespace mv {
@@ -27,6 +28,12 @@ int launch_raster_depth(const GymView &gv, void *depth, int depth_format, int W,
 // The same with labels attached (mv_set_seg_obs; mv_seg_obs.h): the label planes of every frame of gv -- and, depth non-null, its depth planes -- with ONE launch
 // of the exact trace: never two.  seg (launch_raster, fast = 0 only): the exact pass stores the label planes itself, beside the colours and, if given, the depth.
 int launch_raster_seg(const GymView &gv, void *depth, int depth_format, void *seg, int seg_format, int W, int H, hipStream_t stream);
+
+// Overview cameras (mv_overview.h): the frame setup of every env from its camera ov.cams[env], the frame order from the overview's own cost bins and the exact
+// pass into obs [N][H][W] RGBA, three launches on `stream`.  gv: a view whose vis_prims / vis_rects / vis_count / vis_stride / lpt_bucket / lpt_order / vis_hdr
+// are the overview's own arrays -- nothing of a stepping call's passes is read or written.  -1: bad size.
+// cost_order = false: no frame-order launch -- gv.lpt_order already holds the order to draw in (the identity: MV_OVERVIEW_ORDER=0, a measurement's switch).
+int launch_overview(const GymView &gv, const OverviewArgs &ov, uint32_t *obs, int W, int H, hipStream_t stream, bool cost_order = true);
 
 // the fast observation pass of n gyms of one job (frame lists already built by their step kernels) with at most two launches; publish: n
 // entries or null; -1 if W / H / n are too large

@@ -515,16 +515,19 @@ __device__ __forceinline__ void put_label(void *plane, int format, bool wide, in
 // the gym's depth entry (frame f's plane at f W H values) and its format, read where OUT has OUT_DEPTHS; seg / seg_format: the same for the label planes
 // (OUT_LABEL); order: null (OUT != OUT_RGB only): position = frame.
 // CHW: the planar layout (mv_set_obs_layout; PixOutT above)
-template <int MAXVIS, bool SHAPES, bool CHW, int OUT>   // SHAPES: the frame may hold scaled spheres / capsules / cylinders (Rearrange)
+// OVERVIEW (overview_raster_kernel; mv_overview.h): one frame per env, seen from the camera its setup left in ovc[env] -- an agent's own frame of reference, or
+// one more, index MAX_CAMS, loaded from the record; gv's list fields are the overview's own arrays.  The arithmetic is the code below, shared; every other
+// instantiation passes false and compiles what it always did.
+template <int MAXVIS, bool SHAPES, bool CHW, int OUT, bool OVERVIEW = false>   // SHAPES: the frame may hold scaled spheres / capsules / cylinders (Rearrange)
 __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, void *depth, int depth_format, void *seg, int seg_format, int W, int H, int split,
-                                            const int *order)
+                                            const int *order, const OverviewCam *ovc = nullptr)
 {
     constexpr bool RGB = (OUT & OUT_COLOURS) != 0, DEPTH = (OUT & OUT_DEPTHS) != 0, LABEL = (OUT & OUT_LABEL) != 0;
     constexpr int ROUNDS = MAXVIS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];   // column/row ray tables
     __shared__ Prim s_vis[MAXVIS];       // this frame's visible list
     __shared__ short4 s_rect[MAXVIS];    // x0,x1,y0,y1 (pixels)
-    __shared__ CamL s_cam[MAX_CAMS];
+    __shared__ CamL s_cam[MAX_CAMS + (OVERVIEW ? 1 : 0)];
     __shared__ float s_lutA[256], s_lutD[256];   // colour byte -> AMB * c / 255 and (DIF * c / 255) * LCOL
     __shared__ uint16_t s_label[LABEL ? MAXVIS : 1];   // (OUT_LABEL) the word of every list position: one rule evaluation per visible primitive, none per pixel
 
@@ -547,7 +550,7 @@ __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, vo
     }
     if constexpr (OUT == OUT_RGB) frame = order[frame];   // `frame` so far was a position in the cost-sorted order (most expensive first)
     else if (order) frame = order[frame];                 // (the depth and label modes accept no order: position = frame)
-    const int env = frame / A, viewer = frame - env * A;
+    const int env = OVERVIEW ? frame : frame / A, viewer = OVERVIEW ? __builtin_amdgcn_readfirstlane(ovc[frame].viewer) : frame - env * A;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
     // ---- frames of reference: the cameras (and, Hex scenarios, the wall orientations) as the frame setup left them in the frame's header --
@@ -563,6 +566,16 @@ __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, vo
         cam.origin[0] = o[12]; cam.origin[1] = o[13]; cam.origin[2] = o[14];
         s_cam[tid] = cam;
     }
+    if constexpr (OVERVIEW)
+        if (tid == MAX_CAMS) {   // the overview camera (its origin: the viewer's eye in its own frame)
+            const OverviewCam oc = ovc[frame];
+            CamL cam;
+            cam.eye[0] = oc.eye[0]; cam.eye[1] = oc.eye[1]; cam.eye[2] = oc.eye[2];
+#pragma unroll
+            for (int q = 0; q < 9; ++q) cam.c[q] = oc.c[q];
+            cam.origin[0] = cam.origin[1] = cam.origin[2] = 0.0f;
+            s_cam[MAX_CAMS] = cam;
+        }
     __syncthreads();
     {   // separable ray terms: world dir = (c_k0*dc.x + c_k1*dc.y) + c_k2*(-1), dc = (xn*TAN, yn*TAN_Y, -1)
         const float *c = s_cam[viewer].c;
@@ -787,6 +800,20 @@ __global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : M
                              : 1) void raster_kernel(GymView gv, uint32_t *obs, int W, int H, int split, const int *order)
 {
     raster_body<MAXVIS, SHAPES, CHW, OUT_RGB>(gv, obs, nullptr, 0, nullptr, 0, W, H, split, order);
+}
+
+// Overview cameras (mv_set_overview; mv_overview.h): the frame setup of one env per workgroup from its overview camera, and the exact pass of those frames.
+__global__ __launch_bounds__(256) void overview_setup_kernel(GymView gv, OverviewArgs ov, int W, int H)
+{
+    __shared__ FrameScratch s_fs;
+    __shared__ CamL s_cams[MAX_CAMS + 1];
+    frame_setup_body<256, false, false, true>(gv, blockIdx.x, W, H, s_fs, nullptr, &ov, s_cams);
+}
+template <int MAXVIS, bool SHAPES>
+__global__ __launch_bounds__(256, MAXVIS <= 256 && !SHAPES ? MV_RASTER_WAVES : MAXVIS <= 256 ? 5 : MAXVIS <= 1024 ? 2
+                             : 1) void overview_raster_kernel(GymView gv, uint32_t *obs, const OverviewCam *ovc, int W, int H, int split, const int *order)
+{
+    raster_body<MAXVIS, SHAPES, false, OUT_RGB, true>(gv, obs, nullptr, 0, nullptr, 0, W, H, split, order, ovc);
 }
 
 // Waves per SIMD the depth kernels are built for: the occupancy the compiler reports for them when built WITHOUT a bound (min waves 1).  The figures of that
@@ -3029,6 +3056,21 @@ int launch_raster_seg(const GymView &gv, void *depth, int depth_format, void *se
                           : by_list(gv, [](auto maxvis, auto shapes) { return raster_seg_kernel<decltype(maxvis)::value, decltype(shapes)::value, OUT_LABEL>; });
     hipLaunchKernelGGL(fn, dim3(frames * split), dim3(256), exact_dyn_lds(W, H), stream, gv, (uint32_t *)nullptr, depth, depth_format, seg, seg_format, W, H, split,
                        (const int *)nullptr);
+    return 0;
+}
+
+// gv: a view whose list fields are the overview's own arrays (vis_stride: its capacity; mv_overview.hip builds it).  Three launches: setup, frame order from
+// the overview's own cost bins (cost_order; false: two launches, gv.lpt_order holds the identity), pass.  Kernels by capacity: 256 (no scenario that small has scaled shapes), 1024 without scaled shapes, else 2048 with them.
+int launch_overview(const GymView &gv, const OverviewArgs &ov, uint32_t *obs, int W, int H, hipStream_t stream, bool cost_order)
+{
+    if (W < 1 || H < 1 || W > MAX_W || H > MAX_H) return -1;
+    const int frames = gv.num_envs, split = exact_split(W, H);
+    const bool shapes = gv.scenario == SCN_REARRANGE || gv.scenario == SCN_FOOTBALL || gv.scenario == SCN_HEX_MEMORY || gv.scenario == SCN_HEX_EXPLORE;
+    hipLaunchKernelGGL(overview_setup_kernel, dim3(frames), dim3(256), 0, stream, gv, ov, W, H);
+    if (cost_order) hipLaunchKernelGGL(frame_order_kernel, dim3(1), dim3(1024), 0, stream, gv, frames, gv.lpt_order);   // (else: lpt_order holds the identity)
+    const auto fn = gv.vis_stride <= VIS_SMALL && !shapes ? overview_raster_kernel<VIS_SMALL, false>
+                  : gv.vis_stride <= VIS_LARGE && !shapes ? overview_raster_kernel<VIS_LARGE, false> : overview_raster_kernel<VIS_XL, true>;
+    hipLaunchKernelGGL(fn, dim3(frames * split), dim3(256), exact_dyn_lds(W, H), stream, gv, obs, (const OverviewCam *)ov.out, W, H, split, (const int *)gv.lpt_order);
     return 0;
 }
 

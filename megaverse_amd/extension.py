@@ -122,7 +122,90 @@ SYMBOLS = [
     ("mv_get_seg_observation", C.c_int, [_P, _I, _I, _P]), ("mv_seg_class_name", C.c_char_p, [_I]),
     ("mv_debug_seg_bounds_host", C.c_int, [_I, _I, _I, _I, _I, _I, _I, _I, _P]), ("mv_debug_seg_rule_host", C.c_int, [_I, _I, _P, _I, _I, _P]),
     ("mv_debug_seg_pack_host", C.c_int, [_P, _P, _I, _I, _P]),
+    ("mv_set_overview", C.c_int, [_P, _I, _I, _P]), ("mv_set_overview_cameras", C.c_int, [_P, _P]), ("mv_set_overview_cameras_host", C.c_int, [_P, _P]),
+    ("mv_get_overview_observation", C.c_int, [_P, _I, _P]), ("mv_overview_device_ptr", _P, [_P]), ("mv_overview_dropped", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("mv_overview_capacity", C.c_int, [_P]), ("mv_overview_default_camera", C.c_int, [_P]), ("mv_debug_overview_camera_host", C.c_int, [_P, _P, _P]),
 ]
+
+# include/megaverse_hip.h: mv_camera, one overview camera (mv_set_overview; megaverse_amd/csrc/mv_overview.h has the rule)
+MV_CAMERA_FIRST_PERSON = 1
+CAMERA_DTYPE = np.dtype({"names": ["eye", "agent", "c", "flags", "pad"], "formats": [("<f4", 3), "<i4", ("<f4", 9), "<i4", ("<i4", 2)],
+                         "offsets": [0, 12, 16, 52, 56], "itemsize": 64})
+
+
+def overview_default_camera():
+    """-> the reference's overview pose as one CAMERA_DTYPE record (render_utils.cpp:34-55; mv_overview_default_camera): eye about (-0.1414, 20, 0), looking
+    along about (0.5417, -0.6428, 0.5417)"""
+    out = np.zeros((), CAMERA_DTYPE)
+    if load_library().mv_overview_default_camera(out.ctypes.data) != 0:
+        raise RuntimeError(load_library().mv_last_error().decode())
+    return out
+
+
+def look_at(eye, target, up=(0, 1, 0)):
+    """-> a FREE camera record at eye looking at target.  In float32, every operation rounded once: back = (eye - target) / |eye - target|,
+    right = cross(up, back) / |cross(up, back)|, up' = cross(back, right); |v| = sqrt((x x + y y) + z z); cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z,
+    a.x b.y - a.y b.x).  c's columns are right / up' / back.  ValueError where eye == target or up is parallel to the view direction."""
+    f = np.float32
+    e, t, u = (np.asarray(v, f).reshape(3) for v in (eye, target, up))
+
+    def norm(v):
+        n = np.sqrt(f(f(v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]))
+        if not n > 0:
+            raise ValueError("look_at: eye == target, or up is parallel to the view direction")
+        return (v / n).astype(f)
+
+    def cross(a, b):
+        return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]], f)
+
+    back = norm((e - t).astype(f))
+    right = norm(cross(u, back))
+    up2 = cross(back, right)
+    out = np.zeros((), CAMERA_DTYPE)
+    out["eye"] = e
+    out["agent"] = -1
+    out["c"] = np.stack([right, up2, back], axis=1).reshape(9)
+    return out
+
+
+def follow(agent, back=0.0, up=0.0, first_person=False):
+    """-> an AGENT camera record: agent's own camera, moved `back` along its back axis and `up` along its up axis (both 0: the agent's very eye, no
+    arithmetic).  first_person: the agent's capsule and eyes box are not drawn -- the rule of its own observation"""
+    out = np.zeros((), CAMERA_DTYPE)
+    out["eye"] = (0.0, float(up), float(back))
+    out["agent"] = int(agent)
+    out["flags"] = MV_CAMERA_FIRST_PERSON if first_person else 0
+    return out
+
+
+def debug_overview_camera_host(cam, agent_state=None):
+    """mv_debug_overview_camera_host: the camera the device would build from one CAMERA_DTYPE record and (AGENT mode) the 128-byte state record of its
+    agent -> (eye float32 [3], c float32 [3, 3])"""
+    rec = np.ascontiguousarray(np.asarray(cam, CAMERA_DTYPE).reshape(()))
+    st = None if agent_state is None else np.ascontiguousarray(agent_state)
+    if st is not None and st.nbytes != 128:
+        raise ValueError("debug_overview_camera_host: an agent's state record is 128 bytes")
+    out = np.empty(12, np.float32)
+    lib = load_library()
+    if lib.mv_debug_overview_camera_host(rec.ctypes.data, None if st is None else st.ctypes.data, out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out[:3].copy(), out[3:].reshape(3, 3).copy()
+
+
+def check_overview_cameras(cams, num_envs, num_agents, who="set_overview_cameras"):
+    """-> [num_envs] CAMERA_DTYPE, contiguous: one record (given to every env) or num_envs of them; ValueError for an agent outside -1 .. num_agents - 1
+    or non-zero pad words"""
+    arr = np.asarray(cams, CAMERA_DTYPE) if not (isinstance(cams, np.ndarray) and cams.dtype == CAMERA_DTYPE) else cams
+    arr = arr.reshape(-1)
+    if arr.size == 1:
+        arr = np.repeat(arr, num_envs)
+    if arr.size != num_envs:
+        raise ValueError(f"{who}: {arr.size} records for {num_envs} envs")
+    if ((arr["agent"] < -1) | (arr["agent"] >= num_agents)).any():
+        raise ValueError(f"{who}: agent outside -1 .. {num_agents - 1}")
+    if arr["pad"].any():
+        raise ValueError(f"{who}: the pad words must be 0")
+    return np.ascontiguousarray(arr)
 
 # include/megaverse_hip.h: the formats of a label plane (mv_set_seg_obs), and the classes (megaverse_amd/csrc/mv_seg_obs.h has the table), name -> value
 MV_SEG_CLASS_U8, MV_SEG_INSTANCE_U16 = 0, 1
@@ -1032,6 +1115,8 @@ class MegaverseGym:
         self._macro_held = None      # macro_step: the caller's device tensors of the last call, read in stream order: kept until the next macro step
         self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
         self._store_held = []    # save_envs / load_envs: the caller's stores and device maps, kept until the next step has been enqueued
+        self._overview = None    # set_overview: the attached tensor (the caller's, or a view of the gym's own frames)
+        self._overview_cams_held = None  # set_overview_cameras: the caller's device records, copied in stream order: kept until they are replaced
 
     def _ck(self, rc):
         if rc < 0:
@@ -1098,7 +1183,75 @@ class MegaverseGym:
         self._ck(self._lib.mv_draw_hires(self._g))
 
     def draw_overview(self):
+        """With an overview attached (set_overview): every env drawn from its overview camera into overview_obs(), in the order of the gym's stream, no host
+        wait.  With none: nothing, as the reference's build without a window."""
         self._ck(self._lib.mv_draw_overview(self._g))
+
+    def set_overview(self, w, h, buf=True):
+        """Overview cameras (include/megaverse_hip.h: mv_set_overview): one camera per env, free in the world or attached to an agent, drawn by
+        draw_overview() with the exact pass's arithmetic into a CUDA uint8 tensor [num_envs, h, w, 4] (RGBA, row 0 the bottom row) -- the caller's (checked,
+        ValueError), or with True / None the gym's own.  1 <= w, h <= 1024; w = h = 0 detaches.  Every env starts at the reference's pose
+        (overview_default_camera).  Nothing a stepping call launches or writes changes.  -> overview_obs()"""
+        w, h = int(w), int(h)
+        if w == 0 and h == 0:
+            self._ck(self._lib.mv_set_overview(self._g, 0, 0, None))
+            self._overview = None
+            return None
+        if buf is None or buf is True:
+            self._ck(self._lib.mv_set_overview(self._g, w, h, None))
+            import torch
+            ptr = int(self._lib.mv_overview_device_ptr(self._g))
+            self._overview = torch.as_tensor(_DeviceArray(ptr, (self.num_envs, h, w, 4), "|u1"), device=f'cuda:{self.device}')
+            return self._overview
+        import torch
+        if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous()
+                and tuple(buf.shape) == (self.num_envs, h, w, 4) and (buf.device.index or 0) == self.device):
+            raise ValueError(f"set_overview: the buffer must be a contiguous CUDA uint8 tensor [{self.num_envs}, {h}, {w}, 4] on device {self.device}")
+        self._ck(self._lib.mv_set_overview(self._g, w, h, _P(int(buf.data_ptr()))))
+        self._overview = buf
+        return buf
+
+    def overview_obs(self):
+        """-> torch.uint8 [num_envs, h, w, 4]: the frames draw_overview writes, valid in the order of the gym's stream; None with no overview attached"""
+        return self._overview
+
+    def set_overview_cameras(self, cams):
+        """One camera per env (CAMERA_DTYPE; look_at, follow, overview_default_camera build records): a record or a sequence / array of num_envs records --
+        checked (ValueError) and copied in stream order, the host free again on return --; a CUDA tensor of num_envs * 16 int32 / float32 words holding the
+        same records -- copied on the gym's stream, an agent outside -1 .. A - 1 taken as FREE and counted (overview_dropped) --; None: back to the default pose."""
+        if cams is None:
+            self._ck(self._lib.mv_set_overview_cameras_host(self._g, None))
+            self._overview_cams_held = None
+            return
+        if hasattr(cams, 'data_ptr'):
+            import torch
+            if not (cams.is_cuda and cams.dtype in (torch.int32, torch.float32) and cams.is_contiguous() and cams.numel() == self.num_envs * 16
+                    and (cams.device.index or 0) == self.device):
+                raise ValueError(f"set_overview_cameras: a device form is a contiguous CUDA int32 / float32 tensor of {self.num_envs} x 16 words on device {self.device}")
+            self._ck(self._lib.mv_set_overview_cameras(self._g, _P(int(cams.data_ptr()))))
+            self._overview_cams_held = cams
+            return
+        arr = check_overview_cameras(cams, self.num_envs, self.num_agents_per_env)
+        self._ck(self._lib.mv_set_overview_cameras_host(self._g, arr.ctypes.data))
+        self._overview_cams_held = None
+
+    def get_overview_observation(self, env_idx):
+        """-> numpy uint8 [h, w, 4]: one env's overview frame as last drawn (waits for the gym's stream)"""
+        if self._overview is None:
+            raise RuntimeError("get_overview_observation: no overview attached (set_overview)")
+        out = np.empty(tuple(self._overview.shape[1:]), np.uint8)
+        self._ck(self._lib.mv_get_overview_observation(self._g, int(env_idx), out.ctypes.data))
+        return out
+
+    def overview_dropped(self):
+        """-> (primitives that did not fit an env's list, clamped agent indices of device records) since the first attach (waits for the gym's stream)"""
+        v = C.c_int64(0)
+        self._ck(self._lib.mv_overview_dropped(self._g, C.byref(v)))
+        return int(v.value) & 0xffffffff, (int(v.value) >> 32) & 0xffffffff
+
+    def overview_capacity(self):
+        """-> the list capacity per env of this gym's overview: 256, 1024 or 2048, by the scenario's slot count"""
+        return self._ck(self._lib.mv_overview_capacity(self._g))
 
     def get_hires_observation(self, env_idx, agent_idx):
         out = np.empty((self.render_h, self.render_w, 4), np.uint8)

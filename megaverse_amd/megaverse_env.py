@@ -69,7 +69,7 @@ def check_sequence_actions(actions, num_agents):
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
                  img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1,
-                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False):
+                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False, overview=None):
         if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
         # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
@@ -140,6 +140,12 @@ class MegaverseEnv:
         self._seg_fmt = None if seg_obs is False else "class" if seg_obs is True else seg_obs
         if self._seg_fmt:
             self.env.set_seg_obs(True, self._seg_fmt)
+        # overview = (w, h): one overview camera per env (mv_set_overview), every env at the reference's pose until set_overview_cameras moves them; drawn on
+        # demand by render_overview(), read with self.overview_obs(); no stepping call changes
+        if overview is not None:
+            if len(tuple(overview)) != 2:
+                raise ValueError(f"overview must be None or (w, h), got {overview!r}")
+            self.env.set_overview(int(overview[0]), int(overview[1]))
         self.default_shaping_scheme = self.env.get_reward_shaping(0, 0)
         self.action_space = self.generate_action_space(self.env.action_space_sizes())
         self.observation_space = spaces.Box(0, 255, (self.channels, self.img_h, self.img_w), dtype=np.uint8)
@@ -667,6 +673,32 @@ class MegaverseEnv:
             try:
                 import cv2  # type: ignore
                 cv2.imshow(f'agent_{id(self)}', obs_final)
+                cv2.waitKey(1)
+            except Exception:  # noqa: BLE001 - headless image
+                pass
+        return obs_final
+
+    def overview_obs(self):
+        """-> torch.uint8 [num_envs, h, w, 4] (RGBA, row 0 the bottom row): the frames the last render_overview() drew, valid in the order of the gym's stream;
+        None without overview=(w, h)"""
+        return self.env.overview_obs()
+
+    def set_overview_cameras(self, cams):
+        """one camera per env: records built with megaverse_amd.look_at / follow / overview_default_camera, a CUDA tensor of them, or None for the default
+        pose (MegaverseGym.set_overview_cameras)"""
+        self.env.set_overview_cameras(cams)
+
+    def render_overview(self, mode='rgb_array'):
+        """draws every env from its overview camera and returns the envs' frames tiled side by side as one BGR image, top row first -- the way render() tiles
+        the agents' hires frames; mode 'human' shows it if cv2 exists.  render() itself is unchanged."""
+        if self.env.overview_obs() is None:
+            raise RuntimeError("render_overview: construct the env with overview=(w, h)")
+        self.env.draw_overview()
+        obs_final = np.concatenate([self.convert_obs(self.env.get_overview_observation(env_i)) for env_i in range(self.num_envs)], axis=1)
+        if mode == 'human':
+            try:
+                import cv2  # type: ignore
+                cv2.imshow(f'overview_{id(self)}', obs_final)
                 cv2.waitKey(1)
             except Exception:  # noqa: BLE001 - headless image
                 pass

@@ -203,6 +203,11 @@ class MultiTaskGym:
         raise RuntimeError("MultiTaskGym.set_entity_obs: mv_group_create and mv_step_many refuse a gym with entity observations attached "
                            "(mv_set_entity_obs): the union launches write none; step such a gym on its own")
 
+    def set_overview(self, w, h, buf=True):
+        """overview cameras (MegaverseGym.set_overview) are per gym: a group's union launches draw none, and the library refuses"""
+        raise RuntimeError("MultiTaskGym.set_overview: mv_group_create and mv_step_many refuse a gym with an overview attached "
+                           "(mv_set_overview): the union launches draw none; step such a gym on its own")
+
     def recommended_ticks_per_call(self):
         """the k to ask step_n for: what every member recommends (mv_recommended_ticks_per_call), at most 8 -- the two-launch group call's limit"""
         return max(1, min([8] + [g.recommended_ticks_per_call() for g in self.gyms]))

@@ -5,7 +5,8 @@
 //
 // Differences a caller can see: errors raise RuntimeError (the reference logs and exit(-1)s); get_observation /
 // get_hires_observation return arrays that own a host copy of the frame (the reference returns views into renderer
-// memory that the next step() invalidates); draw_overview is the no-GUI build's no-op.  Extra, not in the reference:
+// memory that the next step() invalidates); draw_overview draws nothing until set_overview(w, h) attaches the overview cameras'
+// frames (every env from the reference's overview pose; get_overview_observation reads one back).  Extra, not in the reference:
 // obs_device_ptr() / set_actions_batched() / get_dones() for callers that want the batch without O(num_agents) calls.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -120,6 +121,18 @@ public:
     }
     void draw_hires() { check(mv_draw_hires(gym_)); }
     void draw_overview() { check(mv_draw_overview(gym_)); }
+    // overview cameras (include/megaverse_hip.h: mv_set_overview): gym-owned frames of w x h, every env at the default pose; 0, 0 detaches
+    void set_overview(int w, int h)
+    {
+        check(mv_set_overview(gym_, w, h, nullptr));
+        overview_w_ = w; overview_h_ = h;
+    }
+    py::array_t<uint8_t> get_overview_observation(int env)
+    {
+        py::array_t<uint8_t> frame({overview_h_, overview_w_, 4});
+        check(mv_get_overview_observation(gym_, env, frame.mutable_data()));
+        return frame;
+    }
     py::array_t<uint8_t> get_hires_observation(int env, int agent)
     {
         py::array_t<uint8_t> frame({render_h_, render_w_, 4});
@@ -242,6 +255,7 @@ public:
 private:
     mv_gym *gym_ = nullptr;
     int w_, h_, envs_, agents_, render_w_ = 768, render_h_ = 432;   // default hires size: megaverse.cpp:261
+    int overview_w_ = 0, overview_h_ = 0;
 };
 
 int visible_device_count() { return mv_device_count(); }
@@ -268,6 +282,8 @@ PYBIND11_MODULE(megaverse, m)
         .def("set_render_resolution", &Gym::set_render_resolution)
         .def("draw_hires", &Gym::draw_hires)
         .def("draw_overview", &Gym::draw_overview)
+        .def("set_overview", &Gym::set_overview)
+        .def("get_overview_observation", &Gym::get_overview_observation)
         .def("get_hires_observation", &Gym::get_hires_observation)
         .def("get_reward_shaping", &Gym::get_reward_shaping)
         .def("set_reward_shaping", &Gym::set_reward_shaping)
