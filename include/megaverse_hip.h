@@ -620,6 +620,12 @@ int64_t mv_arena_bytes(const mv_gym *g);
  * episodes are drawn on the device -- TowerBuilding always (tower_draw_kernel); Collect where the process's share of the host is under three cores and the gym has 256 envs and more, or
  * MV_COLLECT_DEVICE_GEN=1 (collect_draw_kernel: the host generator's episodes, byte for byte).  -1: no such gym. */
 int mv_host_generator_threads(const mv_gym *g);
+/* Are this gym's episodes drawn on the device?  1: TowerBuilding, and every gym whose feeder runs in device mode -- Collect as above; the Obstacles family
+ * (ObstaclesEasy / Medium / Hard / Walls / Steps / Lava) and Empty with MV_OBSTACLES_DEVICE_GEN=1 in the environment at mv_create (obstacles_draw_kernel,
+ * megaverse_amd/csrc/mv_obstacles_draw.h: the host generator's episodes, byte for byte; unset or 0: host-fed, no automatic choice).  0: host-fed.  -1: no gym.
+ * mv_host_generator_threads is 0 exactly where this is 1.  The device form of mv_seed_envs stays refused on a device-fed gym as on a host-fed one.
+ * Under the switch mv_create refuses an Obstacles gym whose obstacles* float parameters exceed the device generator's fixed arrays (7 platforms, heights 1..4). */
+int mv_device_generator(const mv_gym *g);
 int mv_render(mv_gym *g);                           /* observation pass only */
 
 int mv_is_done(mv_gym *g, int32_t env_idx);         /* isDone(), :123-126 -> 0/1, <0 on error */
@@ -853,6 +859,15 @@ int mv_debug_generate_football(int32_t num_agents, int32_t env_seed, int32_t n, 
  * receives the n-th of each (count x the record size), *ms_per_launch the mean duration of a launch of `count` wavefronts.  Replaces CollectScenario::reset +
  * createLandscape + addEpisodeDrawables (scenario_collect.cpp:20-161,190-214), siv::PerlinNoise (perlin_noise.hpp:118-126,315-318). */
 int mv_debug_collect_draw_host(int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes);
+/* The Obstacles family's and Empty's generator as it runs on the DEVICE (megaverse_amd/csrc/mv_obstacles_draw.h; the feeder uses it where
+ * mv_device_generator says 1 for such a gym), with the semantics of the two Collect hooks.  `scenario`: one of the six Obstacles names or "Empty".
+ * _host: the same code compiled for the CPU (the merge in its serial form), the record mv_debug_generate_episode(scenario, ...) returns (seq = n); out == NULL:
+ * the record's size.  _device: `count` envs draw their first n episodes on the GPU.  _stats_host: out[0 .. 3] = chain attempts, left turns, right turns and
+ * GEN_* capacity flags of the n-th episode as mv_gen_obstacles.cpp draws it, out[4 .. 7] = the same four of mv_obstacles_draw.h's code on the CPU. */
+int mv_debug_obstacles_draw_host(const char *scenario, int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes);
+int mv_debug_obstacles_draw_stats_host(const char *scenario, int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, int32_t *out8);
+int mv_debug_obstacles_draw_device(int32_t device, const char *scenario, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n,
+                                   float base_episode_len, void *out, int64_t out_bytes, float *ms_per_launch);
 /* Host-only (no device): the episode log's per-tick body (megaverse_amd/csrc/mv_episode_log.h, the source the kernel runs) over k ticks of N envs x A
  * agents: rewards [k][N*A], dones [k][N], true_objectives [k][N*A]; first_tick: the first tick's end_tick.  In and out: ret [N*A], len [N], *count, *dropped,
  * and records, a buffer of `capacity` mv_episode_record of which *count are valid on entry. */

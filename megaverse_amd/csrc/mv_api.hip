@@ -8,6 +8,7 @@
 //   step all envs  ->  for done envs: record trueObjective, reset  ->  draw.
 // There is NO CPU fallback: if no HIP device can be opened mv_create fails.
 #include "mv_api_internal.h"
+#include "mv_obstacles_draw.h"
 
 thread_local std::string mvapi::g_err;
 
@@ -267,16 +268,15 @@ namespace mvapi {
 bool scenario_from_name(const std::string &scen, int &scenario, ObstacleConfig &oc)
 {
     if (scen == "towerbuilding") scenario = SCN_TOWER;
-    else if (scen == "obstacleseasy") scenario = SCN_OBSTACLES;                       // scenario_obstacles.hpp:112-138
-    else if (scen == "obstaclesmedium") { scenario = SCN_OBSTACLES; oc.min_platforms = 2; oc.max_platforms = 4; oc.min_lava = 2; oc.max_lava = 5; }
-    else if (scen == "obstacleshard") {                                               // :164-189
-        scenario = SCN_OBSTACLES; oc.min_platforms = 2; oc.max_platforms = 7; oc.min_gap = 2; oc.max_gap = 3; oc.min_lava = 3; oc.max_lava = 10;
-        oc.min_height = 2; oc.max_height = 4;
-    } else if (scen == "obstacleswalls" || scen == "obstaclessteps" || scen == "obstacleslava") {   // :190-268
-        scenario = SCN_OBSTACLES; oc.min_platforms = 1; oc.max_platforms = 4; oc.min_gap = 1; oc.max_gap = 3; oc.min_lava = 2; oc.max_lava = 10;
-        oc.min_height = 1; oc.max_height = 3; oc.carried_object_to_exit = 1.0f;
-        oc.platform_types[0] = scen == "obstacleswalls" ? 1 : scen == "obstaclessteps" ? 3 : 2;
-        oc.num_platform_types = 1;
+    else if (scen.rfind("obstacles", 0) == 0) {                                       // scenario_obstacles.hpp:94-268: mv_gen.h's table
+        const ObstaclePreset *preset = nullptr;
+        for (const ObstaclePreset &p : kObstaclePresets)
+            if (scen == p.name) preset = &p;
+        if (!preset) return false;
+        scenario = SCN_OBSTACLES;
+        const float carried = oc.carried_object_to_exit;
+        oc = config_of(*preset);
+        if (preset->carried_object_to_exit == 0.0f) oc.carried_object_to_exit = carried;
     } else if (scen == "collect") scenario = SCN_COLLECT;                              // scenarios/init.hpp:45
     else if (scen == "rearrange") scenario = SCN_REARRANGE;                            // scenarios/init.hpp:49
     else if (scen == "sokoban") scenario = SCN_SOKOBAN;                                // scenarios/init.hpp:46
@@ -369,6 +369,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     g->w = cfg->obs_width; g->h = cfg->obs_height;
     g->N = cfg->num_envs; g->A = cfg->num_agents_per_env;
     g->scenario = scenario;
+    g->scenarioName = scen;
     g->numShaping = scenario == SCN_TOWER || scenario == SCN_SOKOBAN ? 4 : scenario == SCN_REARRANGE || scenario == SCN_HEX_MEMORY || scenario == SCN_BOXAGONE ? 3
                   : scenario == SCN_HEX_EXPLORE ? 2 : scenario == SCN_EMPTY || scenario == SCN_FOOTBALL ? 1 : 5;
     g->shapingKeys = scenario == SCN_TOWER ? SHAPING_KEYS_TOWER : scenario == SCN_OBSTACLES ? SHAPING_KEYS_OBST
@@ -640,6 +641,16 @@ int mv_create(const mv_config *cfg, mv_gym **out)
         // Mixed4 batch 18.0 / 19.8 M obs/s, an eighth of a Mixed batch 16.9 / 16.2: too few episodes to pay for the draw launches).  The staging slots are device memory then.
         g->blobsOnDevice = collect && (getenv("MV_COLLECT_DEVICE_GEN") ? atoi(getenv("MV_COLLECT_DEVICE_GEN")) != 0
                                                                         : cfg->num_simulation_threads <= 0 && !getenv("MV_FEEDER_THREADS") && share < 3 && N >= 256);
+        // The Obstacles family and Empty (one record, EpisodeBlob): drawn on the device (mv_obstacles_draw.h: the same episodes, byte for byte) with
+        // MV_OBSTACLES_DEVICE_GEN=1 and only then -- no rule of its own yet, Collect's was cut from measurements this generator does not have.
+        if (obstacles) g->blobsOnDevice = getenv("MV_OBSTACLES_DEVICE_GEN") && atoi(getenv("MV_OBSTACLES_DEVICE_GEN")) != 0;
+        // (the obstacles* float parameters can ask for levels beyond the device generator's fixed arrays -- 40 platforms in a row, say: said here, not drawn)
+        if (g->blobsOnDevice && scenario == SCN_OBSTACLES && !odraw::config_fits(oc)) {
+            mv_destroy(g);
+            return fail("mv_create: MV_OBSTACLES_DEVICE_GEN=1, but this gym's generator parameters are beyond what the device generator holds (at most "
+                        + std::to_string((int)odraw::LARGEST_PLATFORMS) + " platforms, heights 1 to " + std::to_string((int)odraw::LARGEST_HEIGHT)
+                        + "): unset the switch for this gym (" + scen + ")");
+        }
         bool ok = g->blobsOnDevice ? hipMalloc((void **)&g->hBlobs, N * g->blobBytes) == hipSuccess && hipMemset(g->hBlobs, 0, N * g->blobBytes) == hipSuccess
                                    : hipHostMalloc((void **)&g->hBlobs, N * g->blobBytes, hipHostMallocDefault) == hipSuccess;
         for (auto &e : g->uploadEvents) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
@@ -649,10 +660,11 @@ int mv_create(const mv_config *cfg, mv_gym **out)
         }
         g->feeder = std::make_unique<EpisodeFeeder>(scenario, oc, g->N, g->A, episodeLen, g->hBlobs, g->blobBytes, g->device, g->feederThreads, levelFiles,
                                                     g->blobsOnDevice);
-        if (g->feeder->failed()) {
+        if (g->feeder->failed() || g->feeder->device_gen() != g->blobsOnDevice) {
             mv_destroy(g);
-            return fail("mv_create: the device-side episode generator's allocations failed");
+            return fail("mv_create: the device-side episode generator's allocations failed (" + scen + ")");
         }
+        g->arenaBytes += g->feeder->device_scratch_bytes();   // (the draw kernel's grid regions, Obstacles family in device mode)
         std::vector<uint32_t> seeds(N);
         std::random_device rdev;   // unseeded envs take their seed from random_device (env.hpp:169)
         for (auto &v : seeds) v = (uint32_t)rdev();
@@ -1042,7 +1054,7 @@ static int upload_pass(mv_gym *g)
     int runFirst = -1, runLen = 0, runSlot = 0;
     size_t runBytes = 0;
     // Host-generated episodes travel on the copy stream (a DMA engine's work, ordered against the step launches by events).  Device-drawn ones are copied
-    // device to device by ONE small kernel per pass (collect_blob_copy_kernel), and that goes to the SIMULATION stream itself, in order between the step
+    // device to device by ONE small kernel per pass (collect_blob_copy_kernel, episode_blob_copy_kernel), and that goes to the SIMULATION stream itself, in order between the step
     // launches: on the copy stream it would queue behind whatever shares its hardware queue (an observation launch lasts a millisecond) with the step
     // launches waiting for it (r12a: 13.7 M obs/s; on the simulation stream as one hipMemcpyAsync per episode 15.7 M, r12b; the host feeder: 16.8 M).
     hipStream_t up = g->blobsOnDevice ? g->simStream : g->copyStream;
@@ -1051,7 +1063,7 @@ static int upload_pass(mv_gym *g)
         if (runLen <= 0) return 0;
         uint8_t *dst = g->dBlobs + ((size_t)runFirst * K + (size_t)runSlot) * g->blobBytes;
         const uint8_t *src = g->hBlobs + (size_t)runFirst * g->blobBytes;
-        const hipMemcpyKind kind = g->blobsOnDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;   // (device-drawn Collect episodes: staging is device memory)
+        const hipMemcpyKind kind = g->blobsOnDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;   // (device-drawn episodes: staging is device memory)
         if (runLen == 1) HIP_TRY(hipMemcpyAsync(dst, src, runBytes, kind, up));
         else HIP_TRY(hipMemcpy2DAsync(dst, (size_t)K * g->blobBytes, src, g->blobBytes, runBytes, (size_t)runLen, kind, up));
         runLen = 0;
@@ -1065,7 +1077,7 @@ static int upload_pass(mv_gym *g)
         if (!must && !g->feeder->is_ready(i, need)) { deficit += consumed + K - g->uploaded[i]; continue; }   // later
         size_t bytes = 0;
         const uint8_t *src = g->feeder->wait_ready(i, need, &bytes);
-        if (!src) return fail(g->feeder->failed() ? std::string(g->feeder->device_gen() ? "episode feeder: a HIP call of the device-side generator failed (Collect)"
+        if (!src) return fail(g->feeder->failed() ? std::string(g->feeder->device_gen() ? "episode feeder: a HIP call of the device-side generator failed (" + g->scenarioName + ")"
                                                                                        : "episode feeder: a level file could not be read (Sokoban)")
                                                   : "episode feeder: episode " + std::to_string(need)
                                                           + " of env " + std::to_string(i) + " was never generated");
@@ -1089,7 +1101,8 @@ static int upload_pass(mv_gym *g)
     }
     if (flush_run()) return -1;
     if (!devEnvs.empty()) {
-        launch_collect_blob_copy(devEnvs.data(), devSlots.data(), (int)devEnvs.size(), g->hBlobs, g->dBlobs, g->blobBytes, K, up);
+        if (g->scenario == SCN_COLLECT) launch_collect_blob_copy(devEnvs.data(), devSlots.data(), (int)devEnvs.size(), g->hBlobs, g->dBlobs, g->blobBytes, K, up);
+        else launch_episode_blob_copy(devEnvs.data(), devSlots.data(), (int)devEnvs.size(), g->hBlobs, g->dBlobs, g->blobBytes, K, up);
         HIP_TRY(hipGetLastError());
     }
     if (!batch.empty()) {

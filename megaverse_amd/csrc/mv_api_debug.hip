@@ -290,9 +290,9 @@ int mv_debug_generate_episode(const char *scenario_name, int32_t num_agents, int
 {
     int scenario = SCN_TOWER;
     ObstacleConfig oc;
-    if (!scenario_name || !scenario_from_name(lower(scenario_name), scenario, oc) || scenario == SCN_TOWER || scenario == SCN_SOKOBAN || scenario == SCN_EMPTY
+    if (!scenario_name || !scenario_from_name(lower(scenario_name), scenario, oc) || scenario == SCN_TOWER || scenario == SCN_SOKOBAN
         || scenario == SCN_FOOTBALL)
-        return fail("mv_debug_generate_episode: the Obstacles family, Collect, Rearrange, HexMemory, HexExplore and BoxAGone (Sokoban: mv_debug_generate_sokoban, Football: mv_debug_generate_football)");
+        return fail("mv_debug_generate_episode: the Obstacles family, Empty, Collect, Rearrange, HexMemory, HexExplore and BoxAGone (Sokoban: mv_debug_generate_sokoban, Football: mv_debug_generate_football)");
     if (num_agents < 1 || num_agents > MAX_AGENTS || n < 1) return fail("mv_debug_generate_episode: bad arguments");
     const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE;
     const size_t bytes = scenario == SCN_COLLECT ? sizeof(CollectBlob) : scenario == SCN_REARRANGE ? sizeof(RearrangeBlob)
@@ -309,6 +309,7 @@ int mv_debug_generate_episode(const char *scenario_name, int32_t num_agents, int
         else if (scenario == SCN_HEX_EXPLORE) generate_hex_explore_episode(rng, num_agents, base_episode_len, *reinterpret_cast<HexBlob *>(buf.data()));
         else if (scenario == SCN_REARRANGE) generate_rearrange_episode(rng, num_agents, base_episode_len, *reinterpret_cast<RearrangeBlob *>(buf.data()));
         else if (scenario == SCN_BOXAGONE) generate_boxagone_episode(rng, num_agents, base_episode_len, *reinterpret_cast<BoxAGoneBlob *>(buf.data()));
+        else if (scenario == SCN_EMPTY) generate_empty_episode(rng, num_agents, base_episode_len, *reinterpret_cast<EpisodeBlob *>(buf.data()));
         else generate_obstacles_episode(rng, oc, num_agents, base_episode_len, *reinterpret_cast<EpisodeBlob *>(buf.data()));
     }
     std::memcpy(out, buf.data(), bytes);

@@ -61,6 +61,9 @@ void launch_tower_seed_envs(const GymView &gv, const int32_t *seeds, hipStream_t
 // Collect, device-drawn episodes (mv_collect_draw.hip): staging slots of envs[i] -> their ring slots slots[i], one launch per 64 episodes
 void launch_collect_blob_copy(const int32_t *envs, const int32_t *slots, int count, const uint8_t *staging, uint8_t *ring, size_t blob_bytes, int spares,
                               hipStream_t stream);
+// Obstacles family and Empty, device-drawn episodes (mv_obstacles_draw.hip): the same copy for records of any size, copied whole
+void launch_episode_blob_copy(const int32_t *envs, const int32_t *slots, int count, const uint8_t *staging, uint8_t *ring, size_t blob_bytes, int spares,
+                              hipStream_t stream);
 // The step and reset kernels of gv's scenario (mv_step.hip).  One tick: one workgroup per env = the tick (wave 0) + the frame setup of the env's frames
 // for a W x H observation (render = 0: tick only); done: an event carried by the launch's dispatch packet (TowerBuilding only) -> whether it was.
 bool launch_step(const GymView &gv, hipStream_t stream, int W, int H, int render, hipEvent_t done = nullptr);
@@ -255,6 +258,7 @@ struct mv_gym {
     std::mt19937 rng{std::random_device{}()};    // megaverse.cpp:253
     // scenario
     int scenario = SCN_TOWER;
+    std::string scenarioName;                       // as given to mv_create, lower case (messages)
     int numShaping = 4;
     const char *const *shapingKeys = nullptr;
     ObstacleConfig obst;
@@ -265,7 +269,7 @@ struct mv_gym {
     std::vector<int> consumedSeen;                  // the consumed counts of the last status read-back that was looked at (host copy)
     std::vector<int> uploaded, uploadBatch;         // episodes uploaded per env; envs of the current upload batch
     uint8_t *dBlobs = nullptr, *hBlobs = nullptr;   // device [N][blobBytes], pinned feeder slots [N][blobBytes]
-    bool blobsOnDevice = false;                     // Collect with the device-side generator: hBlobs is device memory, filled by collect_draw_kernel (mv_feeder.cpp)
+    bool blobsOnDevice = false;                     // the feeder runs in device mode (Collect, the Obstacles family, Empty): hBlobs is device memory, filled by the scenario's draw kernel (mv_feeder.cpp)
     size_t blobBytes = 0;                           // sizeof(EpisodeBlob) or sizeof(CollectBlob)
     bool hostEpisodes() const { return scenario != SCN_TOWER; }
     // TowerBuilding: the episode generator's serial half (tower_draw_kernel, ~47 us of one wavefront per finished env) runs on a stream of its own,

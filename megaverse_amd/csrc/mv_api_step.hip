@@ -753,6 +753,12 @@ int mv_recommended_pass_overlap(const mv_gym *g)
     return 1;
 }
 
+int mv_device_generator(const mv_gym *g)
+{
+    if (!g || g->closed) return -1;
+    return !g->feeder || g->feeder->device_gen() ? 1 : 0;   // (no feeder: TowerBuilding, drawn by tower_draw_kernel)
+}
+
 int64_t mv_arena_bytes(const mv_gym *g) { return g ? (int64_t)(g->arenaBytes + g->logBytes + g->resampleBytes + g->stepMask.ownedBytes + g->drawMask.ownedBytes + g->budgetBytes + g->macroBytes + g->stillBytes + g->sceneRows.stageBytes + g->entityRows.stageBytes + g->overview.layout.bytes + g->overview.ownedBytes) : 0; }
 
 int mv_step_many(mv_gym *const *gyms, int32_t n, int32_t render, int32_t sample, uint32_t seed, uint32_t step_index)

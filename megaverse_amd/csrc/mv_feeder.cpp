@@ -5,24 +5,40 @@
 #include <cstddef>
 
 #include "mv_collect_draw.h"
+#include "mv_obstacles_draw.h"
 
 namespace mv {
 
 void launch_collect_draw(void *states, const int32_t *envs, int count, uint8_t *slots, size_t slot_bytes, int num_agents, float base_episode_len,
                          hipStream_t stream, int32_t *flag_word);   // mv_collect_draw.hip
+void launch_obstacles_draw(void *states, const int32_t *envs, int count, uint8_t *slots, size_t slot_bytes, int scenario, const ObstacleConfig &cfg, int num_agents,
+                           float base_episode_len, uint32_t *grids, int regions, hipStream_t stream, int32_t *flag_word);   // mv_obstacles_draw.hip
+int obstacles_draw_regions(int scenario, int num_envs);   // grid regions a feeder of num_envs envs holds (Empty: none), and one region's size
+size_t obstacles_draw_region_bytes();
+
+// the scenarios a draw kernel exists for
+static bool has_draw_kernel(int scenario, const ObstacleConfig &cfg)
+{
+    return scenario == SCN_COLLECT || scenario == SCN_EMPTY || (scenario == SCN_OBSTACLES && odraw::config_fits(cfg));
+}
 
 EpisodeFeeder::EpisodeFeeder(int scenario, const ObstacleConfig &cfg, int num_envs, int num_agents, float base_episode_len, uint8_t *slots,
                              size_t slot_bytes, int device, int num_threads, std::vector<std::string> level_files, bool device_gen)
     : scenario_{scenario}, num_envs_{num_envs}, num_agents_{num_agents}, device_{device}, cfg_{cfg}, base_len_{base_episode_len},
       slots_{slots}, slot_bytes_{slot_bytes}, rng_(num_envs), next_seq_(num_envs, 1), ready_seq_(num_envs), used_bytes_(num_envs, 0), busy_(num_envs, 0),
       soko_files_{std::move(level_files)}, soko_levels_(scenario == SCN_SOKOBAN ? num_envs : 0), soko_undo_(scenario == SCN_SOKOBAN ? num_envs : 0),
-      device_gen_{device_gen && scenario == SCN_COLLECT}, seeds_(num_envs, 0)
+      device_gen_{device_gen && has_draw_kernel(scenario, cfg)}, seeds_(num_envs, 0)
 {
     std::random_device rd;   // unseeded envs: Env::EnvState::rng{std::random_device{}()} (env.hpp:169)
     for (int i = 0; i < num_envs; ++i) { rng_[i].seed(rd()); ready_seq_[i].store(0, std::memory_order_relaxed); }
     if (device_gen_) {
         (void)hipSetDevice(device_);
-        const bool ok = hipMalloc(&d_states_, size_t(num_envs) * sizeof(cdraw::GenState)) == hipSuccess &&
+        // the Obstacles family's grids (mv_obstacles_draw.h: two bit planes over the largest bounding box a level can have), one region per episode a launch
+        // draws at a time
+        const int regions = scenario_ == SCN_OBSTACLES ? obstacles_draw_regions(scenario_, num_envs_) : 0;
+        grid_bytes_ = size_t(regions) * obstacles_draw_region_bytes();
+        grid_regions_ = regions;
+        const bool ok = (regions == 0 || hipMalloc((void **)&d_grids_, grid_bytes_) == hipSuccess) && hipMalloc(&d_states_, size_t(num_envs) * sizeof(cdraw::GenState)) == hipSuccess &&
                         hipMalloc((void **)&d_list_, size_t(num_envs) * sizeof(int32_t)) == hipSuccess &&
                         hipMalloc((void **)&d_flags_, sizeof(int32_t)) == hipSuccess && hipMemset(d_flags_, 0, sizeof(int32_t)) == hipSuccess &&
                         hipHostMalloc((void **)&h_list_, size_t(num_envs) * sizeof(int32_t), hipHostMallocDefault) == hipSuccess &&
@@ -49,6 +65,7 @@ EpisodeFeeder::~EpisodeFeeder()
     if (device_gen_) {
         if (gen_stream_) { (void)hipStreamSynchronize(gen_stream_); (void)hipStreamDestroy(gen_stream_); }
         if (d_states_) (void)hipFree(d_states_);
+        if (d_grids_) (void)hipFree(d_grids_);
         if (d_list_) (void)hipFree(d_list_);
         if (d_flags_) (void)hipFree(d_flags_);
         if (h_list_) (void)hipHostFree(h_list_);
@@ -220,8 +237,8 @@ void EpisodeFeeder::generate(int env)
     ready_seq_[env].store(seq, std::memory_order_release);
 }
 
-// Device mode's only worker: every env whose slot is free, in ONE launch of collect_draw_kernel on this feeder's stream -- while it runs (an episode is 0.7 ms
-// of one wavefront on average, 2.5 ms the slowest) the next batch gathers.  The launch is ordered behind the uploads that still read the batch's slots.
+// Device mode's only worker: every env whose slot is free, in ONE launch of the scenario's draw kernel (collect_draw_kernel, obstacles_draw_kernel) on this
+// feeder's stream -- while it runs (a Collect episode is 0.7 ms of one wavefront on average, 2.5 ms the slowest) the next batch gathers.  The launch is ordered behind the uploads that still read the batch's slots.
 void EpisodeFeeder::device_worker_main()
 {
     (void)hipSetDevice(device_);
@@ -251,7 +268,8 @@ void EpisodeFeeder::device_worker_main()
         const int count = (int)batch.size();
         ok = ok && hipMemcpyAsync(d_list_, h_list_, size_t(count) * sizeof(int32_t), hipMemcpyHostToDevice, gen_stream_) == hipSuccess;
         if (ok) {
-            launch_collect_draw(d_states_, d_list_, count, slots_, slot_bytes_, num_agents_, base_len_, gen_stream_, d_flags_);
+            if (scenario_ == SCN_COLLECT) launch_collect_draw(d_states_, d_list_, count, slots_, slot_bytes_, num_agents_, base_len_, gen_stream_, d_flags_);
+            else launch_obstacles_draw(d_states_, d_list_, count, slots_, slot_bytes_, scenario_, cfg_, num_agents_, base_len_, d_grids_, grid_regions_, gen_stream_, d_flags_);
             ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(h_flags_, d_flags_, sizeof(int32_t), hipMemcpyDeviceToHost, gen_stream_) == hipSuccess &&
                  hipStreamSynchronize(gen_stream_) == hipSuccess;
         }

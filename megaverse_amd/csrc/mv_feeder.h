@@ -27,7 +27,8 @@ class EpisodeFeeder {
 public:
     // slots: pinned host memory, num_envs * slot_bytes, owned by the caller
     // level_files: Sokoban only (the Boxoban level files found at construction, scenario_sokoban.cpp:40-78)
-    // device_gen (Collect only): `slots` is DEVICE memory and the episodes are drawn there by collect_draw_kernel (mv_collect_draw.h) -- one worker thread
+    // device_gen (Collect, the Obstacles family, Empty; ignored for the others): `slots` is DEVICE memory and the episodes are drawn there by the scenario's
+    // draw kernel (mv_collect_draw.h: collect_draw_kernel; mv_obstacles_draw.h: obstacles_draw_kernel, which takes `cfg` by value) -- one worker thread
     // gathers the envs whose slots are free into a batch, launches the kernel for them on a stream of its own and waits for it; everything else --
     // is_ready / wait_ready / recycle / reseed, the refill protocol around them -- is what it is for the host generators.
     EpisodeFeeder(int scenario, const ObstacleConfig &cfg, int num_envs, int num_agents, float base_episode_len, uint8_t *slots,
@@ -56,6 +57,7 @@ public:
 
     int num_threads() const { return int(workers_.size()); }
     bool device_gen() const { return device_gen_; }
+    size_t device_scratch_bytes() const { return grid_bytes_; }   // device mode, Obstacles family: the draw kernel's grid regions (part of mv_arena_bytes)
     bool failed() const { return failed_.load(std::memory_order_acquire); }   // a generator gave up (Sokoban: unreadable level file)
     int take_overflow() { return overflow_.exchange(0, std::memory_order_relaxed); }   // GEN_* flags this feeder's generators raised since the last call
 
@@ -96,6 +98,9 @@ private:
     void *d_states_ = nullptr;
     int32_t *h_list_ = nullptr, *d_list_ = nullptr, *h_flags_ = nullptr, *d_flags_ = nullptr;
     hipStream_t gen_stream_ = nullptr;
+    uint32_t *d_grids_ = nullptr;   // Obstacles family: grid_regions_ regions of odraw::GRID_WORDS words, one per episode a launch draws at a time
+    int grid_regions_ = 0;
+    size_t grid_bytes_ = 0;
     bool upload_states();   // next_seq_ / seeds -> d_states_ (reseed, under mu_ with no batch in flight)
     bool upload_states_of(const std::vector<uint8_t> &named);   // ... of the envs named[i] != 0 alone (reseed_envs, likewise)
     void undo_sokoban(int env, int first_seq);   // (under mu_, env idle) what env's episodes first_seq .. next_seq - 1 took from its level list is put back

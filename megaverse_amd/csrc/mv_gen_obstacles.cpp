@@ -6,11 +6,13 @@
 //   toBoundingBoxes (component_voxel_grid.hpp:73-187) and DefaultScenario::spawnAgents' random draw
 //   (scenario_default.hpp:87).
 //
-// Why on the host: the generator is branchy, retry-based code around std::map/std::set and draws from
-// std::mt19937 through libstdc++ distributions; here it uses exactly those library templates, so the RNG
-// stream is the reference's by construction.  An episode never depends on what happens during the previous
+// On the host by default: the generator draws from std::mt19937 through libstdc++ distributions and uses exactly those library templates, so the RNG
+// stream is the reference's by construction, and this file is what the oracle tests pin.  It is no longer the only form: mv_obstacles_draw.h restates
+// this file with fixed arrays in place of std::vector / std::map / std::set -- a chain has at most 16 platforms, a platform at most 8 boxes, the
+// occupancy map is an 11 x 8 table -- and draws the same episodes, byte for byte, with one wavefront per episode (MV_OBSTACLES_DEVICE_GEN=1; the
+// retries and the branches run on one lane, the voxel paint and the merge on all 64).  An episode never depends on what happens during the previous
 // one (nothing draws from the env rng while stepping), so the library always keeps ONE finished episode per
-// env resident in HBM (EpisodeBlob) and the reset kernel just swaps it in; the host refills behind the GPU
+// env resident in HBM (EpisodeBlob) and the reset kernel just swaps it in; the host -- or the draw kernel -- refills behind the GPU
 // (mv_api.hip: refill_episodes).  TowerBuilding keeps its fully on-device generator (mv_reset.hip).
 //
 // Geometry: the reference parents every platform under the previous platform's anchor in a Magnum scene
@@ -36,6 +38,8 @@ static thread_local int t_generator_overflow = 0;
 void generator_overflow_raise(int flags) { t_generator_overflow |= flags; }
 int generator_overflow_take() { const int f = t_generator_overflow; t_generator_overflow = 0; return f; }
 static inline bool fits_i8(int v) { return v >= -128 && v <= 127; }
+static thread_local ObstacleStats t_last_stats{0, 0, 0};
+ObstacleStats obstacles_last_stats() { return t_last_stats; }
 
 
 namespace {
@@ -257,7 +261,9 @@ void generate_obstacles_episode(std::mt19937 &rng, const ObstacleConfig &cfg, in
     const bool draw_walls = rand_range(0, 2, rng) != 0;
     std::vector<Platform> chain;
     int num_platforms = 0;
+    ObstacleStats stats{0, 0, 0};
     for (int attempt = 0; attempt < 20; ++attempt) {
+        stats = ObstacleStats{attempt + 1, 0, 0};
         chain.clear();
         num_platforms = rand_range(cfg.min_platforms, cfg.max_platforms + 1, rng);
         Platform first;
@@ -270,6 +276,8 @@ void generate_obstacles_episode(std::mt19937 &rng, const ObstacleConfig &cfg, in
         for (int i = 0; i < num_platforms; ++i) {
             const int turn = rand_range(0, 3, rng);   // 0 straight, 1 left, 2 right
             if (turn != 0) want_width = -1;
+            if (turn == 1) ++stats.left_turns;
+            if (turn == 2) ++stats.right_turns;
             Platform p;
             for (bool drawn = false; !drawn || (p.hardest(cfg) && hardest_so_far >= cfg.num_allowed_max_difficulty); drawn = true) {
                 p = Platform();
@@ -311,6 +319,7 @@ void generate_obstacles_episode(std::mt19937 &rng, const ObstacleConfig &cfg, in
                 if (overlap(chain[j].hull(), chain[k].hull())) { clash = true; break; }
         if (!clash) break;
     }
+    t_last_stats = stats;
     out.layout_color = (int)kLayoutColors[rand_range(0, 14, rng)];
     out.wall_color = (int)kLayoutColors[rand_range(0, 14, rng)];
     out.draw_walls = draw_walls ? 1 : 0;

@@ -57,7 +57,7 @@ SYMBOLS = [
     ("mv_set_output_ring", C.c_int, [_P, _I, _P, _P, _P]),
     ("mv_set_pass_overlap", C.c_int, [_P, _I]),
     ("mv_recommended_ticks_per_call", C.c_int, [_P]), ("mv_recommended_pass_overlap", C.c_int, [_P]), ("mv_arena_bytes", C.c_int64, [_P]),
-    ("mv_host_generator_threads", C.c_int, [_P]),
+    ("mv_host_generator_threads", C.c_int, [_P]), ("mv_device_generator", C.c_int, [_P]),
     ("mv_is_done", C.c_int, [_P, _I]), ("mv_get_dones", C.c_int, [_P, _P]),
     ("mv_get_last_rewards", C.c_int, [_P, _P]),
     ("mv_true_objective", C.c_int, [_P, _I, _I, C.POINTER(_F)]), ("mv_get_true_objectives", C.c_int, [_P, _P]),
@@ -91,6 +91,9 @@ SYMBOLS = [
     ("mv_debug_generate_football", C.c_int, [_I, _I, _I, _F, _P, _I]),
     ("mv_debug_collect_draw_host", C.c_int, [_I, _I, _I, _F, _P, _I]),
     ("mv_debug_collect_draw_device", C.c_int, [_I, _I, _P, _I, _I, _F, _P, C.c_int64, _P]),
+    ("mv_debug_obstacles_draw_host", C.c_int, [C.c_char_p, _I, _I, _I, _F, _P, _I]),
+    ("mv_debug_obstacles_draw_stats_host", C.c_int, [C.c_char_p, _I, _I, _I, _F, _P]),
+    ("mv_debug_obstacles_draw_device", C.c_int, [_I, C.c_char_p, _I, _P, _I, _I, _F, _P, C.c_int64, _P]),
     ("mv_set_episode_log", C.c_int, [_P, _I]), ("mv_get_episode_log_capacity", C.c_int, [_P]), ("mv_flush_episode_log", C.c_int, [_P]),
     ("mv_episode_log_count", C.c_int, [_P, C.POINTER(_U), C.POINTER(_U)]), ("mv_drain_episode_log", C.c_int, [_P, _P, _I, C.POINTER(_U)]),
     ("mv_episode_log_records_device_ptr", _P, [_P]), ("mv_episode_log_count_device_ptr", _P, [_P]),
@@ -1781,6 +1784,11 @@ class MegaverseGym:
     def host_generator_threads(self):
         """threads of the host-side episode feeder; 0 = the episodes are drawn on the device (TowerBuilding; Collect with the device generator)"""
         return int(self._lib.mv_host_generator_threads(self._g))
+
+    def device_generator(self):
+        """are the episodes drawn on the device?  True: TowerBuilding; Collect with the device generator; the Obstacles family and Empty with
+        MV_OBSTACLES_DEVICE_GEN=1 in the environment when the gym was made.  host_generator_threads() is 0 exactly then."""
+        return int(self._lib.mv_device_generator(self._g)) == 1
 
     def arena_bytes(self):
         return int(self._lib.mv_arena_bytes(self._g))

@@ -551,6 +551,10 @@ class MegaverseEnv:
         value: the halted envs resume."""
         self.env.set_episode_budget(budget)
 
+    def device_generator(self):
+        """are this env's episodes drawn on the device (MegaverseGym.device_generator)?"""
+        return self.env.device_generator()
+
     def halted(self):
         """bool CUDA tensor [num_envs]: the envs whose budget is spent (episode_budget() == 0), in the order of the gym's stream"""
         self._torch()

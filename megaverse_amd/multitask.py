@@ -215,6 +215,10 @@ class MultiTaskGym:
     def recommended_pass_overlap(self):
         return False
 
+    def device_generator(self):
+        """per member: are its episodes drawn on the device (MegaverseGym.device_generator)?"""
+        return [g.device_generator() for g in self.gyms]
+
     def set_pixel_mode(self, mode):
         for g in self.gyms:
             g.set_pixel_mode(mode)
