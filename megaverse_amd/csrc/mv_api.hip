@@ -112,6 +112,27 @@ int attach_check(mv_gym *g, const char *who, const GymOption &opt)
     return 0;
 }
 
+static int stream_attached(const ObsStream &s, const char *who, const std::string &clause)
+{
+    return fail(std::string(who) + ": " + s.noun + " are attached (" + gym_options[s.opt].setter + "), " + clause + ": detach the " + s.noun + " first");
+}
+
+int ring_sized_attached(const mv_gym *g, const char *who)
+{
+    for (const ObsStream &s : obs_streams)
+        if (gym_options[s.opt].on(g)) return stream_attached(s, who, "sized by the ring count they were attached under");
+    return 0;
+}
+
+int planes_attached(const mv_gym *g, const char *who, std::string (*clause)(const ObsStream &))
+{
+    for (const ObsStream &s : obs_streams)
+        if (s.plane && gym_options[s.opt].on(g)) return stream_attached(s, who, clause(s));
+    return 0;
+}
+
+std::string still_clause(const ObsStream &s) { return std::string("and a still frame's ") + s.plane + " would not be carried"; }
+
 int getter_check(const mv_gym *g, const char *who)
 {
     if (!g) return fail(std::string(who) + ": null gym handle");
@@ -799,8 +820,7 @@ int mv_close(mv_gym *g)
     g->seedEnvsPair.release();
     env_masks_free(g);
     obs_rows_free(g);
-    g->depth = DepthObs();   // (mv_set_depth_obs: the buffer is the caller's -- forgotten, not freed)
-    g->seg = SegObs();       // (mv_set_seg_obs: likewise)
+    obs_planes_free(g);
     episode_budget_free(g);
     macro_step_free(g);
     still_frames_free(g);
@@ -1320,16 +1340,7 @@ int mv_set_sample_policy(mv_gym *g, int32_t policy)
 int mv_set_output_ring(mv_gym *g, int32_t count, void *obs, float *rewards, uint8_t *dones)
 {
     if (check(g)) return -1;
-    if (g->stateRows.buf)   // (the state buffer is one more ring of the count it was attached under)
-        return fail("mv_set_output_ring: state observations are attached (mv_set_state_obs), sized by the ring count they were attached under: detach the state observations first");
-    if (g->depth.buf)
-        return fail("mv_set_output_ring: depth observations are attached (mv_set_depth_obs), sized by the ring count they were attached under: detach the depth observations first");
-    if (g->seg.buf)
-        return fail("mv_set_output_ring: segmentation observations are attached (mv_set_seg_obs), sized by the ring count they were attached under: detach the segmentation observations first");
-    if (g->sceneRows.buf)
-        return fail("mv_set_output_ring: scene observations are attached (mv_set_scene_obs), sized by the ring count they were attached under: detach the scene observations first");
-    if (g->entityRows.buf)
-        return fail("mv_set_output_ring: entity observations are attached (mv_set_entity_obs), sized by the ring count they were attached under: detach the entity observations first");
+    if (ring_sized_attached(g, "mv_set_output_ring")) return -1;   // (an attached buffer is one more ring of the count it was attached under)
     if (count < 0 || (count > 0 && !obs && !rewards && !dones)) return fail("mv_set_output_ring: count >= 0 and at least one ring required");
     if (count > 0 && obs && g->obsLayout == MV_OBS_RGB_PLANAR && (uintptr_t)obs % planar_alignment(g->w))
         return fail("mv_set_output_ring: a planar ring of this width must be " + std::to_string(planar_alignment(g->w)) + "-byte aligned");
@@ -1462,10 +1473,8 @@ int mv_set_render_resolution(mv_gym *g, int32_t w, int32_t h)
 {
     if (check(g)) return -1;
     if (w < 1 || h < 1) return fail("mv_set_render_resolution: bad size");
-    if (g->depth.buf)   // (mv_draw_hires writes no depth: the planes stay those of the observation size they were attached under)
-        return fail("mv_set_render_resolution: depth observations are attached (mv_set_depth_obs), whose planes are of the observation size: detach the depth observations first");
-    if (g->seg.buf)     // (mv_draw_hires writes no labels either)
-        return fail("mv_set_render_resolution: segmentation observations are attached (mv_set_seg_obs), whose planes are of the observation size: detach the segmentation observations first");
+    // (mv_draw_hires writes neither depth nor labels: the planes stay those of the observation size they were attached under)
+    if (planes_attached(g, "mv_set_render_resolution", +[](const ObsStream &) { return std::string("whose planes are of the observation size"); })) return -1;
     if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
     g->renderW = w; g->renderH = h;
     return 0;

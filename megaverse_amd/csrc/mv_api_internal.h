@@ -11,10 +11,8 @@
 //                     envs' frames out of the observation passes (mv_frame.h: frame_skip)
 //   mv_obs_rows.hip   state and scene observations: attaching the caller's buffers, the staging rows, the one publication launch both records share, their
 //                     refresh (mv_state_obs.h, mv_scene_obs.h: the records)
-//   mv_depth_obs.hip  depth observations: attaching the caller's buffer, the launch behind a pass that gives every drawn frame its depth plane
-//                     (mv_depth_obs.h: the record; mv_raster.hip: the kernels)
-//   mv_seg_obs.hip    segmentation observations: attaching the caller's buffer, the ONE launch behind a fast pass that writes labels, or depth + labels
-//                     (mv_seg_obs.h: the record and its rule; mv_raster.hip: the kernels)
+//   mv_obs_planes.hip  depth and segmentation observations: attaching the caller's buffers, the ONE launch behind a fast pass that writes depth, labels, or
+//                     depth + labels (mv_depth_obs.h, mv_seg_obs.h: the records and their rules; mv_raster.hip: the kernels)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 //   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
 //   mv_overview.hip   overview cameras: attaching the buffer, the overview's own arrays, the cameras' two forms, mv_draw_overview (mv_overview.h: the rule;
@@ -137,21 +135,14 @@ struct ObsRows {
 }  // namespace mvapi
 
 namespace mvapi {
-// The depth planes of a gym (mv_depth_obs.hip).  buf: the caller's [entries][N*A][H][W] buffer of float or __half (null: off; entries: the output ring's count
-// when it was attached, or 1); format: MV_DEPTH_F32 / MV_DEPTH_F16; entryBytes: one entry, the whole gym's planes.
-struct DepthObs {
+// One plane record of a gym (mv_obs_planes.hip: depth observations, segmentation observations).  buf: the caller's [entries][N*A][H][W] buffer -- depth: of
+// float or __half, labels: of bytes or 16-bit words (null: off; entries: the output ring's count when it was attached, or 1); format: MV_DEPTH_F32 /
+// MV_DEPTH_F16, MV_SEG_CLASS_U8 / MV_SEG_INSTANCE_U16; entryBytes: one entry, the whole gym's planes.
+struct ObsPlanes {
     void *buf = nullptr;
     int format = 0, entries = 0;
     size_t entryBytes = 0;
     // tick `tick`'s entry of the caller's buffer: the entry its frames go to (outputs_of)
-    void *entry(unsigned long long tick) const { return buf ? (uint8_t *)buf + (size_t)(tick % (unsigned long long)entries) * entryBytes : nullptr; }
-};
-// The label planes of a gym (mv_seg_obs.hip): the same beside them.  buf: the caller's [entries][N*A][H][W] buffer of bytes or 16-bit words;
-// format: MV_SEG_CLASS_U8 / MV_SEG_INSTANCE_U16.
-struct SegObs {
-    void *buf = nullptr;
-    int format = 0, entries = 0;
-    size_t entryBytes = 0;
     void *entry(unsigned long long tick) const { return buf ? (uint8_t *)buf + (size_t)(tick % (unsigned long long)entries) * entryBytes : nullptr; }
 };
 }  // namespace mvapi
@@ -335,10 +326,10 @@ struct mv_gym {
     // on, the state rows' is not.
     ObsRows stateRows, sceneRows, entityRows;
     // mv_set_depth_obs: the caller's depth planes, written by the passes of a gym in exact pixel mode and by a launch behind the passes of one in fast mode
-    DepthObs depth;
+    ObsPlanes depth;
     // mv_set_seg_obs: the caller's label planes, written by the passes of a gym in exact pixel mode and -- fast mode -- by the one launch behind its passes,
     // which then writes the depth planes too
-    SegObs seg;
+    ObsPlanes seg;
     // mv_set_overview: the overview cameras' frames and arrays
     OverviewState overview;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
@@ -399,6 +390,21 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_overview", "an overview attached", "draw none", "detach it first", "detach it first", "draw no overview", MV_OPT_ON(g->overview.buf)},
 };
 #undef MV_OPT_ON
+// The five per-tick observation streams, stated once, in the order mv_set_output_ring refuses them: the option that attaches the stream, the noun the refusal
+// texts name it by and, for the two plane streams (mv_obs_planes.hip), the name of one plane; null: a row stream (mv_obs_rows.hip).  A new stream is one row
+// here, one in gym_options and one descriptor in its file.
+struct ObsStream {
+    int opt;
+    const char *noun, *plane;
+};
+inline constexpr ObsStream obs_streams[] = {
+    {OPT_STATE_OBS, "state observations", nullptr},
+    {OPT_DEPTH_OBS, "depth observations", "depth plane"},
+    {OPT_SEG_OBS, "segmentation observations", "label plane"},
+    {OPT_SCENE_OBS, "scene observations", nullptr},
+    {OPT_ENTITY_OBS, "entity observations", nullptr},
+};
+constexpr const ObsStream &obs_stream(int opt, int i = 0) { return obs_streams[i].opt == opt ? obs_streams[i] : obs_stream(opt, i + 1); }
 // What a stepping call's view of g carries of the options (the rows of the two records are fields of the per-slot views already: mv_gym::gvp); macro: the view
 // belongs to a macro step's tick (mv_macro_step) and carries the envs' ticks left.  A group's members have none of them (mv_group_create).
 inline void fill_view_options(GymView &v, const mv_gym *g, bool macro)
@@ -467,17 +473,18 @@ int step_macro_chunk(mv_gym *g, int k, int kCall, bool draw_last, const MacroCal
 int obs_rows_publish(mv_gym *g, int q0, unsigned long long tick0, int k);
 int obs_rows_refresh(mv_gym *g, const uint8_t *device_mask);
 void obs_rows_free(mv_gym *g);         // mv_close
-// mv_depth_obs.hip: the depth planes of the frames a FAST pass of view v has just drawn into the entry `planes` (OutPtrs::depth), one launch on the caller's
-// stream behind the pass (an exact pass stores them itself: launch_raster's depth argument); -> 1: launched, 0: nothing attached or planes null
-int depth_obs_follow(mv_gym *g, const GymView &v, void *planes, const char *who);
-// mv_seg_obs.hip: the follower of a gym with labels attached, in depth_obs_follow's place -- the label planes (OutPtrs::seg) and, where depth observations
-// are attached too, the depth planes (OutPtrs::depth) of the frames a FAST pass of v has just drawn, with ONE launch; -> 1: launched, 0: no labels attached
-int seg_obs_follow(mv_gym *g, const GymView &v, void *depth, void *planes, const char *who);
-// the one follower behind a fast pass, whatever is attached: labels (and depth) -> seg_obs_follow, depth alone -> depth_obs_follow; -> launches made, -1
-inline int planes_follow(mv_gym *g, const GymView &v, const struct OutPtrs &o, const char *who)
-{
-    return g->seg.buf ? seg_obs_follow(g, v, o.depth, o.seg, who) : depth_obs_follow(g, v, o.depth, who);
-}
+// mv_obs_planes.hip: the one follower behind a FAST pass of view v, whatever is attached (an exact pass stores the planes itself: launch_raster's depth and
+// label arguments) -- the label planes (o.seg) and, where depth observations are attached too, the depth planes (o.depth) of the frames the pass has just
+// drawn, or the depth planes alone, with ONE launch on the caller's stream; -> launches made (0: nothing attached or planes null), -1
+int planes_follow(mv_gym *g, const GymView &v, const OutPtrs &o, const char *who);
+void obs_planes_free(mv_gym *g);       // mv_close
+// What the calls that an attached stream forbids answer (mv_api.hip), each walking obs_streams and composing "<who>: <noun> are attached (<setter>), <clause>:
+// detach the <noun> first" for the first stream that is on; -> -1 with that text, 0: none is.  ring_sized_attached: all five, sized by the ring count they
+// were attached under.  planes_attached: the two plane streams, with the caller's clause.  still_clause: why still frames and a plane stream exclude each other
+// (mv_set_still_frames; the plane setters' own refusal)
+int ring_sized_attached(const mv_gym *g, const char *who);
+int planes_attached(const mv_gym *g, const char *who, std::string (*clause)(const ObsStream &));
+std::string still_clause(const ObsStream &s);
 int render_frames(mv_gym *g);          // mv_render without the state rows' refresh (mv_api.hip; mv_reset_envs refreshes the flagged envs' rows only)
 int episode_budget_seed_mirror(mv_gym *g);   // mv_set_episode_log: the log's mirror from the live array (mv_episode_budget.hip)
 // mv_fork.hip, shared with mv_env_store.hip: what every fork / resample / env-store form refuses (what: "forks", "env stores": for the text about groups)

@@ -102,12 +102,12 @@ struct Record {
     int floats;                           // of one row; 0: E rows of ENTITY_OBS_FLOATS, E the gym's (rec_floats)
     bool perAgent;                        // a row per agent, [N*A]; else per env, [N]
 };
-const Record STATE = {gym_options[OPT_STATE_OBS], &mv_gym::stateRows, &GymView::state_obs, "mv_get_state_obs", "mv_get_state_observation", "state observations",
+const Record STATE = {gym_options[OPT_STATE_OBS], &mv_gym::stateRows, &GymView::state_obs, "mv_get_state_obs", "mv_get_state_observation", obs_stream(OPT_STATE_OBS).noun,
                       STATE_OBS_FLOATS, true};
-const Record SCENE = {gym_options[OPT_SCENE_OBS], &mv_gym::sceneRows, &GymView::scene_obs, "mv_get_scene_obs", "mv_get_scene_observation", "scene observations",
+const Record SCENE = {gym_options[OPT_SCENE_OBS], &mv_gym::sceneRows, &GymView::scene_obs, "mv_get_scene_obs", "mv_get_scene_observation", obs_stream(OPT_SCENE_OBS).noun,
                       SCENE_OBS_FLOATS, false};
 const Record ENTITY = {gym_options[OPT_ENTITY_OBS], &mv_gym::entityRows, &GymView::entity_obs, "mv_get_entity_obs", "mv_get_entity_observation",
-                       "entity observations", 0, false};
+                       obs_stream(OPT_ENTITY_OBS).noun, 0, false};
 int entity_rows_of(const mv_gym *g) { return entity_obs_rows(g->gv.scenario, g->A); }
 int rec_floats(const mv_gym *g, const Record &rec) { return rec.floats ? rec.floats : entity_rows_of(g) * (int)ENTITY_OBS_FLOATS; }
 

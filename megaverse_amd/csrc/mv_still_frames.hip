@@ -139,10 +139,8 @@ int mv_set_still_frames(mv_gym *g, int32_t on)
         g->simMustWaitUser = true;
         return 0;
     }
-    if (g->depth.buf)   // (a still frame's rows are carried from the entry that holds them; nothing carries its depth plane)
-        return fail("mv_set_still_frames: depth observations are attached (mv_set_depth_obs), and a still frame's depth plane would not be carried: detach the depth observations first");
-    if (g->seg.buf)
-        return fail("mv_set_still_frames: segmentation observations are attached (mv_set_seg_obs), and a still frame's label plane would not be carried: detach the segmentation observations first");
+    // (a still frame's rows are carried from the entry that holds them; nothing carries its depth or label plane)
+    if (planes_attached(g, "mv_set_still_frames", still_clause)) return -1;
     HIP_TRY(hipSetDevice(g->device));
     if (still_alloc(g)) return -1;
     // Every env stale, no frame has a home: on the caller's stream, behind every step launch enqueued so far; the next step launch waits for it.  This call is

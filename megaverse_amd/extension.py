@@ -5,6 +5,7 @@ Reference: class MegaverseGym, src/libs/bindings/megaverse.cpp:34-292 (pybind11 
 ``MegaverseEnv`` (megaverse_env.py here, megaverse/megaverse_env.py there) reads the same.  There is
 no CPU fallback: if the shared library or a HIP device is missing, construction raises.
 """
+import collections
 import ctypes as C
 import os
 import warnings
@@ -285,17 +286,7 @@ def debug_seg_pack_host(cls, instance, fmt):
 def check_seg_obs(buf, entries, num_frames, h, w, fmt, device):
     """the argument check of MegaverseGym.set_seg_obs for a tensor: contiguous torch.uint8 ('class') or torch.int16 / torch.uint16 ('instance') of shape
     (entries, num_frames, h, w) on CUDA device `device`; entries None: any number of entries"""
-    got = tuple(getattr(buf, 'shape', ()))
-    shape = ((got[0] if len(got) == 4 else 1) if entries is None else int(entries), int(num_frames), int(h), int(w))
-    want = ('torch.int16', 'torch.uint16') if int(fmt) == MV_SEG_INSTANCE_U16 else ('torch.uint8',)
-    contiguous = getattr(buf, 'is_contiguous', None)
-    dev = getattr(buf, 'device', None)
-    index = getattr(dev, 'index', None)
-    if not hasattr(buf, 'data_ptr') or got != shape or str(getattr(buf, 'dtype', None)) not in want \
-            or not getattr(buf, 'is_cuda', False) or not (callable(contiguous) and contiguous()) or (index is not None and int(index) != int(device)):
-        raise ValueError(f"set_seg_obs: the buffer must be a contiguous {' / '.join(x[6:] for x in want)} CUDA tensor of shape {shape} on device {int(device)}, "
-                         f"got {getattr(buf, 'dtype', type(buf).__name__)} {tuple(getattr(buf, 'shape', ()))} on {dev if dev is not None else 'no device'}")
-    return buf
+    return _check_obs_tensor(buf, entries, (int(num_frames), int(h), int(w)), OBS_STREAMS['seg'].dtypes(fmt), device, 'set_seg_obs')
 
 # include/megaverse_hip.h: the formats of a depth plane (mv_set_depth_obs), torch dtype name -> MV_DEPTH_*
 MV_DEPTH_F32, MV_DEPTH_F16 = 0, 1
@@ -328,17 +319,7 @@ def debug_depth_pack_host(t, hit, fmt):
 def check_depth_obs(buf, entries, num_frames, h, w, fmt, device):
     """the argument check of MegaverseGym.set_depth_obs for a tensor: contiguous torch.float32 / torch.float16 (as fmt says) of shape (entries, num_frames, h,
     w) on CUDA device `device`; entries None: any number of entries (the check made before the gym is asked for its ring count)"""
-    got = tuple(getattr(buf, 'shape', ()))
-    shape = ((got[0] if len(got) == 4 else 1) if entries is None else int(entries), int(num_frames), int(h), int(w))
-    want = 'torch.float16' if int(fmt) == MV_DEPTH_F16 else 'torch.float32'
-    contiguous = getattr(buf, 'is_contiguous', None)
-    dev = getattr(buf, 'device', None)
-    index = getattr(dev, 'index', None)
-    if not hasattr(buf, 'data_ptr') or got != shape or str(getattr(buf, 'dtype', None)) != want \
-            or not getattr(buf, 'is_cuda', False) or not (callable(contiguous) and contiguous()) or (index is not None and int(index) != int(device)):
-        raise ValueError(f'set_depth_obs: the buffer must be a contiguous {want[6:]} CUDA tensor of shape {shape} on device {int(device)}, '
-                         f"got {getattr(buf, 'dtype', type(buf).__name__)} {tuple(getattr(buf, 'shape', ()))} on {dev if dev is not None else 'no device'}")
-    return buf
+    return _check_obs_tensor(buf, entries, (int(num_frames), int(h), int(w)), OBS_STREAMS['depth'].dtypes(fmt), device, 'set_depth_obs')
 
 # include/megaverse_hip.h: MV_STATE_OBS_FLOATS and the columns of a state-observation row (mv_set_state_obs), name -> index
 MV_STATE_OBS_FLOATS = 16
@@ -869,42 +850,52 @@ def check_draw_mask(mask, num_envs):
 def check_state_obs(buf, entries, num_rows, device):
     """the argument check of MegaverseGym.set_state_obs for a tensor: contiguous torch.float32 of shape (entries, num_rows, 16) on CUDA device `device`;
     entries None: any number of entries (the check made before the gym is asked for its ring count)"""
-    return _check_obs_rows(buf, entries, num_rows, MV_STATE_OBS_FLOATS, device, 'set_state_obs')
+    return _check_obs_tensor(buf, entries, (int(num_rows), MV_STATE_OBS_FLOATS), OBS_STREAMS['state'].dtypes(None), device, 'set_state_obs')
 
 
 def check_scene_obs(buf, entries, num_envs, device):
     """the argument check of MegaverseGym.set_scene_obs for a tensor: contiguous torch.float32 of shape (entries, num_envs, 32) on CUDA device `device`;
     entries None: any number of entries (the check made before the gym is asked for its ring count)"""
-    return _check_obs_rows(buf, entries, num_envs, MV_SCENE_OBS_FLOATS, device, 'set_scene_obs')
+    return _check_obs_tensor(buf, entries, (int(num_envs), MV_SCENE_OBS_FLOATS), OBS_STREAMS['scene'].dtypes(None), device, 'set_scene_obs')
 
 
 def check_entity_obs(buf, entries, num_envs, rows, device):
     """the argument check of MegaverseGym.set_entity_obs for a tensor: contiguous torch.float32 of shape (entries, num_envs, rows, 8) on CUDA device `device`,
     16-byte aligned; entries None: any number of entries (the check made before the gym is asked for its ring count)"""
+    return _check_obs_tensor(buf, entries, (int(num_envs), int(rows), MV_ENTITY_OBS_FLOATS), OBS_STREAMS['entity'].dtypes(None), device, 'set_entity_obs')
+
+
+def _check_obs_tensor(buf, entries, tail, dtypes, device, who):
+    """the one tensor check of the observation streams, for the setter `who`: contiguous, one of `dtypes` (torch dtype names), of shape (entries,) + tail on
+    CUDA device `device`; entries None: any number of entries (the check made before the gym is asked for its ring count) -> buf"""
     got = tuple(getattr(buf, 'shape', ()))
-    shape = ((got[0] if len(got) == 4 else 1) if entries is None else int(entries), int(num_envs), int(rows), MV_ENTITY_OBS_FLOATS)
+    shape = ((got[0] if len(got) == len(tail) + 1 else 1) if entries is None else int(entries),) + tuple(tail)
     contiguous = getattr(buf, 'is_contiguous', None)
     dev = getattr(buf, 'device', None)
     index = getattr(dev, 'index', None)
-    if not hasattr(buf, 'data_ptr') or got != shape or str(getattr(buf, 'dtype', None)) != 'torch.float32' \
+    if not hasattr(buf, 'data_ptr') or got != shape or str(getattr(buf, 'dtype', None)) not in dtypes \
             or not getattr(buf, 'is_cuda', False) or not (callable(contiguous) and contiguous()) or (index is not None and int(index) != int(device)):
-        raise ValueError(f'set_entity_obs: the buffer must be a contiguous float32 CUDA tensor of shape {shape} on device {int(device)}, '
+        raise ValueError(f"{who}: the buffer must be a contiguous {' / '.join(x[6:] for x in dtypes)} CUDA tensor of shape {shape} on device {int(device)}, "
                          f"got {getattr(buf, 'dtype', type(buf).__name__)} {tuple(getattr(buf, 'shape', ()))} on {dev if dev is not None else 'no device'}")
     return buf
 
 
-def _check_obs_rows(buf, entries, num_rows, floats, device, who):
-    """check_state_obs / check_scene_obs: a row record's tensor, (entries, num_rows, floats), for the setter `who`"""
-    got = tuple(getattr(buf, 'shape', ()))
-    shape = ((got[0] if len(got) == 3 else 1) if entries is None else int(entries), int(num_rows), floats)
-    contiguous = getattr(buf, 'is_contiguous', None)
-    dev = getattr(buf, 'device', None)
-    index = getattr(dev, 'index', None)
-    if not hasattr(buf, 'data_ptr') or got != shape or str(getattr(buf, 'dtype', None)) != 'torch.float32' \
-            or not getattr(buf, 'is_cuda', False) or not (callable(contiguous) and contiguous()) or (index is not None and int(index) != int(device)):
-        raise ValueError(f'{who}: the buffer must be a contiguous float32 CUDA tensor of shape {shape} on device {int(device)}, '
-                         f"got {getattr(buf, 'dtype', type(buf).__name__)} {tuple(getattr(buf, 'shape', ()))} on {dev if dev is not None else 'no device'}")
-    return buf
+# The five per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
+# of the gym (a read-back's row is that shape without its first extent), format -> the torch dtype names a tensor may have (the first: what True allocates),
+# the arguments behind the null pointer of a detach, the numpy dtype a read-back hands out.  A new stream is one row here.
+_ObsStream = collections.namedtuple('_ObsStream', 'setter reader tail dtypes detach read')
+_FLOAT32 = ('torch.float32',)
+OBS_STREAMS = {
+    'state': _ObsStream('mv_set_state_obs', 'mv_get_state_observation', lambda g: (g.num_envs * g.num_agents_per_env, MV_STATE_OBS_FLOATS),
+                        lambda fmt: _FLOAT32, (), np.float32),
+    'scene': _ObsStream('mv_set_scene_obs', 'mv_get_scene_observation', lambda g: (g.num_envs, MV_SCENE_OBS_FLOATS), lambda fmt: _FLOAT32, (), np.float32),
+    'entity': _ObsStream('mv_set_entity_obs', 'mv_get_entity_observation',
+                         lambda g: (g.num_envs, entity_rows(g.scenario, g.num_agents_per_env), MV_ENTITY_OBS_FLOATS), lambda fmt: _FLOAT32, (), np.float32),
+    'depth': _ObsStream('mv_set_depth_obs', 'mv_get_depth_observation', lambda g: (g.num_envs * g.num_agents_per_env, g.h, g.w),
+                        lambda fmt: ('torch.float16',) if int(fmt) == MV_DEPTH_F16 else _FLOAT32, (MV_DEPTH_F32,), np.float32),
+    'seg': _ObsStream('mv_set_seg_obs', 'mv_get_seg_observation', lambda g: (g.num_envs * g.num_agents_per_env, g.h, g.w),
+                      lambda fmt: ('torch.int16', 'torch.uint16') if int(fmt) == MV_SEG_INSTANCE_U16 else ('torch.uint8',), (MV_SEG_CLASS_U8,), np.uint16),
+}
 
 
 def check_episode_budget(budget, num_envs):
@@ -1109,11 +1100,7 @@ class MegaverseGym:
         self._seed_held = []     # seed_envs: the caller's device seeds, likewise (calls may follow each other without a step: every tensor is kept)
         self._step_mask_held = None  # set_step_mask: the caller's device mask, kept until it is replaced or detached
         self._draw_mask_held = None  # set_draw_mask: the caller's device mask, kept until it is replaced or detached
-        self._state_obs = None       # set_state_obs: the attached tensor
-        self._scene_obs = None       # set_scene_obs: the attached tensor
-        self._entity_obs = None      # set_entity_obs: the attached tensor
-        self._depth_obs = None       # set_depth_obs: the attached tensor
-        self._seg_obs = None         # set_seg_obs: the attached tensor
+        self._obs = {}               # set_*_obs: stream name (OBS_STREAMS) -> the attached tensor
         self._ring_ticks = 0         # ticks stepped through this object since set_output_ring (the library's own count: which entry the last tick went to)
         self._macro_held = None      # macro_step: the caller's device tensors of the last call, read in stream order: kept until the next macro step
         self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
@@ -1508,28 +1495,45 @@ class MegaverseGym:
         entry the tick's rewards go to.  True allocates the tensor on the gym's device and returns it; a tensor is checked (ValueError) and attached; None
         detaches.  Nothing waits on the host; the rows are visible on the gym's stream when the call's rewards are.  While attached, set_output_ring is
         refused."""
-        self._state_obs = self._set_obs_rows(buf, 'mv_set_state_obs', check_state_obs, self.num_envs * self.num_agents_per_env, MV_STATE_OBS_FLOATS)
-        return self._state_obs
+        return self._attach_obs('state', buf)
 
-    def _set_obs_rows(self, buf, setter, checker, rows, floats):
-        """set_state_obs / set_scene_obs: attach (True: allocate) or detach (None) one row record's tensor [entries, rows, floats] -> the tensor, or None"""
+    def _attach_obs(self, name, buf, fmt=None):
+        """set_*_obs: attach (True: allocate) or detach (None) the tensor [entries, *tail] of one stream of OBS_STREAMS; fmt: the library's format word of a
+        plane stream -> the tensor, or None"""
+        s = OBS_STREAMS[name]
         if buf is None:
-            self._ck(getattr(self._lib, setter)(self._g, None))
+            self._ck(getattr(self._lib, s.setter)(self._g, None, *s.detach))
+            self._obs.pop(name, None)
             return None
+        tail, dtypes, who = s.tail(self), s.dtypes(fmt), s.setter[3:]
         if buf is not True:
-            checker(buf, None, rows, self.device)   # (what needs no gym first: the library stays untouched by a tensor that is wrong anyway)
+            _check_obs_tensor(buf, None, tail, dtypes, self.device, who)   # (what needs no gym first: the library stays untouched by a tensor that is wrong anyway)
         entries = max(1, self._ck(self._lib.mv_get_output_ring(self._g)))   # (the library's own count: the depth it will write)
         if buf is True:
             import torch
-            buf = torch.zeros((entries, rows, floats), dtype=torch.float32, device=f'cuda:{self.device}')
+            buf = torch.zeros((entries,) + tail, dtype=getattr(torch, dtypes[0][6:]), device=f'cuda:{self.device}')
         else:
-            checker(buf, entries, rows, self.device)
-        self._ck(getattr(self._lib, setter)(self._g, _P(int(buf.data_ptr()))))
+            _check_obs_tensor(buf, entries, tail, dtypes, self.device, who)
+        self._ck(getattr(self._lib, s.setter)(self._g, _P(int(buf.data_ptr())), *(() if fmt is None else (fmt,))))
+        self._obs[name] = buf
         return buf
+
+    def _obs_last(self, name):
+        """*_obs: the last tick's entry of one stream's attached tensor, or None (ticks stepped by calling the library directly, past this object, are not
+        counted)"""
+        buf = self._obs.get(name)
+        return None if buf is None else buf[(max(1, self._ring_ticks) - 1) % int(buf.shape[0])]
+
+    def _read_obs(self, name, *index):
+        """get_*_observation: one row or plane of the last tick's entry through the library's reader -> numpy"""
+        s = OBS_STREAMS[name]
+        out = np.empty(s.tail(self)[1:], s.read)
+        self._ck(getattr(self._lib, s.reader)(self._g, *(int(i) for i in index), out.ctypes.data))
+        return out
 
     def state_obs(self):
         """-> the tensor set_state_obs attached, or None"""
-        return self._state_obs
+        return self._obs.get('state')
 
     def set_scene_obs(self, buf=True):
         """Scene observations (include/megaverse_hip.h: mv_set_scene_obs), the per-env counterpart of set_state_obs: every tick of every later stepping call
@@ -1537,26 +1541,20 @@ class MegaverseGym:
         building zone, the exit pad and the diamonds left, the hex target, the ball; the state AFTER the tick) in entry t % entries of a float32 CUDA tensor
         [entries, num_envs, 32], entries = the output ring's count, or 1 without a ring.  True allocates the tensor on the gym's device and returns it; a
         tensor is checked (ValueError) and attached; None detaches.  Nothing waits on the host.  While attached, set_output_ring is refused."""
-        self._scene_obs = self._set_obs_rows(buf, 'mv_set_scene_obs', check_scene_obs, self.num_envs, MV_SCENE_OBS_FLOATS)
-        return self._scene_obs
+        return self._attach_obs('scene', buf)
 
     def scene_obs_ring(self):
         """-> the tensor set_scene_obs attached, [entries, num_envs, 32] (entry t % entries: what tick t left), or None"""
-        return self._scene_obs
+        return self._obs.get('scene')
 
     def scene_obs(self):
         """-> the entry of the last tick, (num_envs, 32): a view of the attached tensor, valid in the order of the gym's stream; None with nothing attached.
         With an output ring: the entry the last tick stepped through this object went to (scene_obs_ring has them all)"""
-        if self._scene_obs is None:
-            return None
-        entries = int(self._scene_obs.shape[0])   # (ticks stepped by calling the library directly, past this object, are not counted)
-        return self._scene_obs[(max(1, self._ring_ticks) - 1) % entries]
+        return self._obs_last('scene')
 
     def get_scene_observation(self, env_idx):
         """-> numpy float32 [32]: the last tick's row of one env (waits for the gym's stream)"""
-        out = np.empty(MV_SCENE_OBS_FLOATS, np.float32)
-        self._ck(self._lib.mv_get_scene_observation(self._g, int(env_idx), out.ctypes.data))
-        return out
+        return self._read_obs('scene', env_idx)
 
     def entity_rows(self):
         """-> E: the rows per env of the entity observations (mv_entity_obs_rows), fixed for the gym's scenario and agent count"""
@@ -1575,40 +1573,20 @@ class MegaverseGym:
         entries = the output ring's count, or 1 without a ring.  Rows are slot-addressed: a record keeps its row, one that does not exist is all zero, and
         entity_row_of maps the words of an 'instance' label plane (set_seg_obs) to rows.  True allocates the tensor on the gym's device and returns it; a
         tensor is checked (ValueError) and attached; None detaches.  Nothing waits on the host.  While attached, set_output_ring is refused."""
-        if buf is None:
-            self._ck(self._lib.mv_set_entity_obs(self._g, None))
-            self._entity_obs = None
-            return None
-        rows = entity_rows(self.scenario, self.num_agents_per_env)
-        if buf is not True:
-            check_entity_obs(buf, None, self.num_envs, rows, self.device)   # (what needs no gym first)
-        entries = max(1, self._ck(self._lib.mv_get_output_ring(self._g)))
-        if buf is True:
-            import torch
-            buf = torch.zeros((entries, self.num_envs, rows, MV_ENTITY_OBS_FLOATS), dtype=torch.float32, device=f'cuda:{self.device}')
-        else:
-            check_entity_obs(buf, entries, self.num_envs, rows, self.device)
-        self._ck(self._lib.mv_set_entity_obs(self._g, _P(int(buf.data_ptr()))))
-        self._entity_obs = buf
-        return buf
+        return self._attach_obs('entity', buf)
 
     def entity_obs_ring(self):
         """-> the tensor set_entity_obs attached, [entries, num_envs, E, 8] (entry t % entries: what tick t left), or None"""
-        return self._entity_obs
+        return self._obs.get('entity')
 
     def entity_obs(self):
         """-> the entry of the last tick, (num_envs, E, 8): a view of the attached tensor, valid in the order of the gym's stream; None with nothing attached.
         With an output ring: the entry the last tick stepped through this object went to (entity_obs_ring has them all)"""
-        if self._entity_obs is None:
-            return None
-        entries = int(self._entity_obs.shape[0])   # (ticks stepped by calling the library directly, past this object, are not counted)
-        return self._entity_obs[(max(1, self._ring_ticks) - 1) % entries]
+        return self._obs_last('entity')
 
     def get_entity_observation(self, env_idx):
         """-> numpy float32 [E, 8]: the last tick's rows of one env (waits for the gym's stream)"""
-        out = np.empty((entity_rows(self.scenario, self.num_agents_per_env), MV_ENTITY_OBS_FLOATS), np.float32)
-        self._ck(self._lib.mv_get_entity_observation(self._g, int(env_idx), out.ctypes.data))
-        return out
+        return self._read_obs('entity', env_idx)
 
     def set_depth_obs(self, buf=True, dtype=None):
         """Depth observations (include/megaverse_hip.h: mv_set_depth_obs): every frame a later observation pass draws -- step, every tick of step_n, the last
@@ -1619,42 +1597,23 @@ class MegaverseGym:
         attached -- its own dtype decides the format; None detaches.  Nothing waits on the host.
         While attached, set_output_ring, set_render_resolution and set_still_frames(True) are refused."""
         if buf is None:
-            self._ck(self._lib.mv_set_depth_obs(self._g, None, MV_DEPTH_F32))
-            self._depth_obs = None
-            return None
-        frames = self.num_envs * self.num_agents_per_env
+            return self._attach_obs('depth', None)
         if dtype is None:   # (the default: torch.float32, named without importing torch where nothing is allocated)
             dtype = "float32"
-        fmt = depth_format_of(dtype if buf is True else getattr(buf, 'dtype', dtype))
-        if buf is not True:
-            check_depth_obs(buf, None, frames, self.h, self.w, fmt, self.device)   # (what needs no gym first)
-        entries = max(1, self._ck(self._lib.mv_get_output_ring(self._g)))
-        if buf is True:
-            import torch
-            buf = torch.zeros((entries, frames, self.h, self.w), dtype=torch.float16 if fmt == MV_DEPTH_F16 else torch.float32, device=f'cuda:{self.device}')
-        else:
-            check_depth_obs(buf, entries, frames, self.h, self.w, fmt, self.device)
-        self._ck(self._lib.mv_set_depth_obs(self._g, _P(int(buf.data_ptr())), fmt))
-        self._depth_obs = buf
-        return buf
+        return self._attach_obs('depth', buf, depth_format_of(dtype if buf is True else getattr(buf, 'dtype', dtype)))
 
     def depth_obs_ring(self):
         """-> the tensor set_depth_obs attached, [entries, num_envs * num_agents, H, W] (entry t % entries: the planes of tick t's frames), or None"""
-        return self._depth_obs
+        return self._obs.get('depth')
 
     def depth_obs(self):
         """-> the entry of the last tick, (num_envs * num_agents, H, W): a view of the attached tensor, valid in the order of the gym's stream; None with
         nothing attached.  A tick that drew no frame wrote nothing there.  With an output ring: the entry the last tick stepped through this object went to"""
-        if self._depth_obs is None:
-            return None
-        entries = int(self._depth_obs.shape[0])
-        return self._depth_obs[(max(1, self._ring_ticks) - 1) % entries]
+        return self._obs_last('depth')
 
     def get_depth_observation(self, env_idx, agent_idx):
         """-> numpy float32 [H, W]: the depth plane of one agent in the last tick's entry, float16 widened (waits for the gym's stream)"""
-        out = np.empty((self.h, self.w), np.float32)
-        self._ck(self._lib.mv_get_depth_observation(self._g, int(env_idx), int(agent_idx), out.ctypes.data))
-        return out
+        return self._read_obs('depth', env_idx, agent_idx)
 
     def set_seg_obs(self, buf=True, fmt="class"):
         """Segmentation observations (include/megaverse_hip.h: mv_set_seg_obs): every frame a later observation pass draws -- the passes set_depth_obs names --
@@ -1665,47 +1624,24 @@ class MegaverseGym:
         attached -- fmt must name its format; None detaches.  Nothing waits on the host.  Depth and labels attach independently: with both, a fast-mode
         tick still costs ONE launch behind its passes.
         While attached, set_output_ring, set_render_resolution and set_still_frames(True) are refused."""
-        if buf is None:
-            self._ck(self._lib.mv_set_seg_obs(self._g, None, MV_SEG_CLASS_U8))
-            self._seg_obs = None
-            return None
-        frames = self.num_envs * self.num_agents_per_env
-        fmt = seg_format_of(fmt)
-        if buf is not True:
-            check_seg_obs(buf, None, frames, self.h, self.w, fmt, self.device)   # (what needs no gym first)
-        entries = max(1, self._ck(self._lib.mv_get_output_ring(self._g)))
-        if buf is True:
-            import torch
-            buf = torch.zeros((entries, frames, self.h, self.w), dtype=torch.int16 if fmt == MV_SEG_INSTANCE_U16 else torch.uint8, device=f'cuda:{self.device}')
-        else:
-            check_seg_obs(buf, entries, frames, self.h, self.w, fmt, self.device)
-        self._ck(self._lib.mv_set_seg_obs(self._g, _P(int(buf.data_ptr())), fmt))
-        self._seg_obs = buf
-        return buf
+        return self._attach_obs('seg', buf, None if buf is None else seg_format_of(fmt))
 
     def seg_obs_ring(self):
         """-> the tensor set_seg_obs attached, [entries, num_envs * num_agents, H, W] (entry t % entries: the planes of tick t's frames), or None"""
-        return self._seg_obs
+        return self._obs.get('seg')
 
     def seg_obs(self):
         """-> the entry of the last tick, (num_envs * num_agents, H, W): a view of the attached tensor, valid in the order of the gym's stream; None with
         nothing attached.  A tick that drew no frame wrote nothing there.  With an output ring: the entry the last tick stepped through this object went to"""
-        if self._seg_obs is None:
-            return None
-        entries = int(self._seg_obs.shape[0])
-        return self._seg_obs[(max(1, self._ring_ticks) - 1) % entries]
+        return self._obs_last('seg')
 
     def get_seg_observation(self, env_idx, agent_idx):
         """-> numpy uint16 [H, W]: the label plane of one agent in the last tick's entry, a 'class' plane widened (waits for the gym's stream)"""
-        out = np.empty((self.h, self.w), np.uint16)
-        self._ck(self._lib.mv_get_seg_observation(self._g, int(env_idx), int(agent_idx), out.ctypes.data))
-        return out
+        return self._read_obs('seg', env_idx, agent_idx)
 
     def get_state_observation(self, env_idx, agent_idx):
         """-> numpy float32 [16]: the last tick's row of one agent (waits for the gym's stream)"""
-        out = np.empty(MV_STATE_OBS_FLOATS, np.float32)
-        self._ck(self._lib.mv_get_state_observation(self._g, int(env_idx), int(agent_idx), out.ctypes.data))
-        return out
+        return self._read_obs('state', env_idx, agent_idx)
 
     def set_episode_budget(self, budget):
         """Episode budgets (include/megaverse_hip.h: mv_set_episode_budget): env e may finish budget[e] more episodes (< 0: unlimited) and then HALTS on the

@@ -107,39 +107,32 @@ class MegaverseEnv:
         self.episode_log = int(episode_log)
         if self.episode_log > 0:
             self.env.set_episode_log(self.episode_log)
-        # state_obs: every tick leaves one row of 16 float32 per agent (STATE_OBS_FIELDS: pose, velocities, carrying, episode time, total reward) in a CUDA
-        # tensor (mv_set_state_obs), read with self.state_obs() -- in every render mode, without a host wait
-        self._state_on = bool(state_obs)
-        if self._state_on:
-            self.env.set_state_obs(True)
-        # still_frames: envs that did not change -- frozen, halted by a budget, stopped inside a macro step -- are not drawn again (mv_set_still_frames); every
-        # observation byte stays what it is without the option
-        if still_frames:
-            self.env.set_still_frames(True)
-        # scene_obs: every tick leaves one row of 32 float32 per ENV (SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS: level, goal and ball) in a CUDA tensor
-        # (mv_set_scene_obs), read with self.scene_obs()
-        self._scene_on = bool(scene_obs)
-        if self._scene_on:
-            self.env.set_scene_obs(True)
-        # entity_obs: every tick leaves E rows of 8 float32 per ENV (ENTITY_OBS_FIELDS: segmentation word, centre, half extents, state of every terrain box,
-        # movable object, collectable and agent; megaverse_amd.entity_layout has the rows) in a CUDA tensor (mv_set_entity_obs), read with self.entity_obs()
-        self._entity_on = bool(entity_obs)
-        if self._entity_on:
-            self.env.set_entity_obs(True)
-        # depth_obs (True: float32, "float16"): every drawn frame leaves its per-pixel camera depth in a CUDA tensor (mv_set_depth_obs), read with
-        # self.depth_obs(); the gym observation space stays the RGB one
+        # The observation streams beside the RGB frames, each a CUDA tensor the gym writes without a host wait, read with self.<name>_obs(); the gym observation
+        # space stays the RGB one.  _streams: the wanted ones, name -> the arguments of MegaverseGym.set_<name>_obs behind True, in the order they are attached.
+        #   state_obs: every tick leaves one row of 16 float32 per agent (STATE_OBS_FIELDS: pose, velocities, carrying, episode time, total reward;
+        #     mv_set_state_obs) -- in every render mode
+        #   scene_obs: ... one row of 32 float32 per ENV (SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS: level, goal and ball; mv_set_scene_obs)
+        #   entity_obs: ... E rows of 8 float32 per ENV (ENTITY_OBS_FIELDS: segmentation word, centre, half extents, state of every terrain box, movable
+        #     object, collectable and agent; megaverse_amd.entity_layout has the rows; mv_set_entity_obs)
+        #   depth_obs (True: float32, "float16"): every drawn frame leaves its per-pixel camera depth (mv_set_depth_obs)
+        #   seg_obs (True: the class byte, "instance": class << 12 | instance): every drawn frame leaves its per-pixel labels (mv_set_seg_obs)
         if depth_obs is not False and depth_obs is not True and depth_obs not in ("float16", "float32"):
             raise ValueError(f"depth_obs must be False, True or 'float16', got {depth_obs!r}")
-        self._depth_dtype = None if depth_obs is False else "float32" if depth_obs is True else depth_obs
-        if self._depth_dtype:
-            self.env.set_depth_obs(True, self._depth_dtype)
-        # seg_obs (True: the class byte, "instance": class << 12 | instance): every drawn frame leaves its per-pixel labels in a CUDA tensor (mv_set_seg_obs),
-        # read with self.seg_obs(); the gym observation space stays the RGB one
         if seg_obs is not False and seg_obs is not True and seg_obs not in ("class", "instance"):
             raise ValueError(f"seg_obs must be False, True, 'class' or 'instance', got {seg_obs!r}")
-        self._seg_fmt = None if seg_obs is False else "class" if seg_obs is True else seg_obs
-        if self._seg_fmt:
-            self.env.set_seg_obs(True, self._seg_fmt)
+        wanted = (("state", state_obs, ()), ("scene", scene_obs, ()), ("entity", entity_obs, ()),
+                  ("depth", depth_obs, ("float32" if depth_obs is True else depth_obs,)), ("seg", seg_obs, ("class" if seg_obs is True else seg_obs,)))
+        self._streams = {name: args for name, on, args in wanted if on}
+        if "state" in self._streams:
+            self._attach_stream("state")
+        # still_frames: envs that did not change -- frozen, halted by a budget, stopped inside a macro step -- are not drawn again (mv_set_still_frames); every
+        # observation byte stays what it is without the option.  Switched on behind the state rows and before every other stream, as it always was: under
+        # still frames the plane setters refuse, in their own words
+        if still_frames:
+            self.env.set_still_frames(True)
+        for name in self._streams:
+            if name != "state":
+                self._attach_stream(name)
         # overview = (w, h): one overview camera per env (mv_set_overview), every env at the reference's pose until set_overview_cameras moves them; drawn on
         # demand by render_overview(), read with self.overview_obs(); no stepping call changes
         if overview is not None:
@@ -163,10 +156,7 @@ class MegaverseEnv:
         entries, entry j what tick j left).  Ask again after every call: when step_device or step_sequence swap the env's output rings, the buffer is
         detached and a NEW tensor of the new depth attached (_set_output_ring) -- a view held from before such a call is no longer written.  Needs
         MegaverseEnv(..., state_obs=True)."""
-        buf = self.env.state_obs()
-        if buf is None:
-            raise RuntimeError("state_obs: create the env with state_obs=True")
-        return buf[self._seq[0][0] - 1 if self._seq is not None else 0]
+        return self._stream_entry("state", self.env.state_obs())
 
     SCENE_OBS_FIELDS = SCENE_OBS_FIELDS                     # column name -> index of a scene_obs() row, columns 0..15 (the tables MegaverseGym shares)
     SCENE_OBS_SCENARIO_FIELDS = SCENE_OBS_SCENARIO_FIELDS   # scenario name -> {column name: index}, columns 16..31
@@ -174,65 +164,47 @@ class MegaverseEnv:
     def scene_obs(self):
         """the last tick's scene observations: float32 (num_envs, 32) on the device, columns SCENE_OBS_FIELDS and SCENE_OBS_SCENARIO_FIELDS[scenario] -- a view
         of the attached buffer, under state_obs()'s rules: ask again after every call.  Needs MegaverseEnv(..., scene_obs=True)."""
-        buf = self.env.scene_obs_ring()
-        if buf is None:
-            raise RuntimeError("scene_obs: create the env with scene_obs=True")
-        return buf[self._seq[0][0] - 1 if self._seq is not None else 0]
+        return self._stream_entry("scene", self.env.scene_obs_ring())
 
     ENTITY_OBS_FIELDS = ENTITY_OBS_FIELDS   # column name -> index of an entity_obs() row
 
     def entity_obs(self):
         """the last tick's entity observations: float32 (num_envs, E, 8) on the device, columns ENTITY_OBS_FIELDS, rows megaverse_amd.entity_layout(scenario,
         num_agents_per_env) -- a view of the attached buffer, under state_obs()'s rules: ask again after every call.  Needs MegaverseEnv(..., entity_obs=True)."""
-        buf = self.env.entity_obs_ring()
-        if buf is None:
-            raise RuntimeError("entity_obs: create the env with entity_obs=True")
-        return buf[self._seq[0][0] - 1 if self._seq is not None else 0]
+        return self._stream_entry("entity", self.env.entity_obs_ring())
 
     def depth_obs(self):
         """the last tick's depth planes: float32 or float16 (num_envs, num_agents_per_env, H, W) on the device -- planar camera depth in world units, 0 where a
         ray hits nothing, row 0 the bottom row -- a view of the attached buffer, under state_obs()'s rules: ask again after every call.  A tick that drew no
         frame wrote nothing.  Needs MegaverseEnv(..., depth_obs=True | "float16")."""
-        buf = self.env.depth_obs_ring()
-        if buf is None:
-            raise RuntimeError("depth_obs: create the env with depth_obs=True")
-        entry = buf[self._seq[0][0] - 1 if self._seq is not None else 0]
-        return entry.view(self.num_envs, self.num_agents_per_env, self.img_h, self.img_w)
+        return self._stream_entry("depth", self.env.depth_obs_ring(), per_agent_planes=True)
 
     def seg_obs(self):
         """the last tick's label planes: uint8 classes (megaverse_amd.SEG_CLASSES) or int16 words class << 12 | instance (megaverse_amd.seg_split),
         (num_envs, num_agents_per_env, H, W) on the device, 0 where a ray hits nothing, row 0 the bottom row -- a view of the attached buffer, under
         state_obs()'s rules: ask again after every call.  A tick that drew no frame wrote nothing.  Needs MegaverseEnv(..., seg_obs=True | "instance")."""
-        buf = self.env.seg_obs_ring()
+        return self._stream_entry("seg", self.env.seg_obs_ring(), per_agent_planes=True)
+
+    def _attach_stream(self, name, on=True):
+        """one wanted stream's tensor attached (a new one, of the output ring's depth) or detached"""
+        getattr(self.env, f"set_{name}_obs")(*((True,) + self._streams[name] if on else (None,)))
+
+    def _stream_entry(self, name, buf, per_agent_planes=False):
+        """the accessors' shared body: the last tick's entry of stream `name`'s attached tensor `buf` -- step_sequence's last tick, else entry 0;
+        per_agent_planes: viewed as (num_envs, num_agents_per_env, H, W)"""
         if buf is None:
-            raise RuntimeError("seg_obs: create the env with seg_obs=True")
+            raise RuntimeError(f"{name}_obs: create the env with {name}_obs=True")
         entry = buf[self._seq[0][0] - 1 if self._seq is not None else 0]
-        return entry.view(self.num_envs, self.num_agents_per_env, self.img_h, self.img_w)
+        return entry.view(self.num_envs, self.num_agents_per_env, self.img_h, self.img_w) if per_agent_planes else entry
 
     def _set_output_ring(self, count, *ptrs):
-        """the env's own output rings change (step_device, step_sequence): the state buffer is one more ring of the same depth and the library refuses a ring
-        change while it is attached, so it is detached around the change and a buffer of the new depth attached"""
-        if self._state_on:
-            self.env.set_state_obs(None)
-        if self._scene_on:
-            self.env.set_scene_obs(None)
-        if self._entity_on:
-            self.env.set_entity_obs(None)
-        if self._depth_dtype:
-            self.env.set_depth_obs(None)
-        if self._seg_fmt:
-            self.env.set_seg_obs(None)
+        """the env's own output rings change (step_device, step_sequence): every attached stream's buffer is one more ring of the same depth and the library
+        refuses a ring change while one is attached, so they are detached around the change and buffers of the new depth attached -- the planes first"""
+        for name in self._streams:
+            self._attach_stream(name, on=False)
         self.env.set_output_ring(count, *ptrs)
-        if self._depth_dtype:
-            self.env.set_depth_obs(True, self._depth_dtype)
-        if self._seg_fmt:
-            self.env.set_seg_obs(True, self._seg_fmt)
-        if self._state_on:
-            self.env.set_state_obs(True)
-        if self._scene_on:
-            self.env.set_scene_obs(True)
-        if self._entity_on:
-            self.env.set_entity_obs(True)
+        for name in sorted(self._streams, key=lambda name: name not in ("depth", "seg")):
+            self._attach_stream(name)
 
     @staticmethod
     def generate_action_space(action_space_sizes):

@@ -48,6 +48,12 @@ def check_action_ring(actions, num_envs, agents_per_env):
     return int(shape[0])
 
 
+def _per_gym(setter, what, verb):
+    """-> the RuntimeError of a MultiTaskGym method whose option is per gym: `what` is attached by mv_<setter>, and a group's union launches `verb` none"""
+    return RuntimeError(f"MultiTaskGym.{setter}: mv_group_create and mv_step_many refuse a gym with {what} attached "
+                        f"(mv_{setter}): the union launches {verb} none; step such a gym on its own")
+
+
 class MultiTaskGym:
     def __init__(self, scenarios, w, h, num_envs, num_agents_per_env, num_simulation_threads=4, float_params=None, device=0,
                  env_offset=0, total_envs=0, obs_layout="rgba"):
@@ -168,45 +174,37 @@ class MultiTaskGym:
         """episode budgets (MegaverseGym.set_episode_budget) are per gym: a group's union launches read none, and the library refuses"""
         if self._group is not None and budget is not None:
             self.gyms[0].set_episode_budget(budget if isinstance(budget, (int, np.integer)) else 1)   # (raises, with the library's text)
-        raise RuntimeError("MultiTaskGym.set_episode_budget: mv_group_create and mv_step_many refuse a gym with an episode budget attached "
-                           "(mv_set_episode_budget): the union launches read none; step such a gym on its own")
+        raise _per_gym("set_episode_budget", "an episode budget", "read")
 
     def set_draw_mask(self, mask):
         """draw masks (MegaverseGym.set_draw_mask) are per gym: a group's union launches read none, and the library refuses"""
         if self._group is not None and mask is not None:
             self.gyms[0].set_draw_mask(np.ones(self.gyms[0].num_envs, np.bool_))   # (raises, with the library's text)
-        raise RuntimeError("MultiTaskGym.set_draw_mask: mv_group_create and mv_step_many refuse a gym with a draw mask attached "
-                           "(mv_set_draw_mask): the union launches read none; step such a gym on its own")
+        raise _per_gym("set_draw_mask", "a draw mask", "read")
 
     def set_depth_obs(self, buf=True, dtype=None):
         """depth observations (MegaverseGym.set_depth_obs) are per gym: a group's union launches write none, and the library refuses"""
-        raise RuntimeError("MultiTaskGym.set_depth_obs: mv_group_create and mv_step_many refuse a gym with depth observations attached "
-                           "(mv_set_depth_obs): the union launches write none; step such a gym on its own")
+        raise _per_gym("set_depth_obs", "depth observations", "write")
 
     def set_seg_obs(self, buf=True, fmt="class"):
         """segmentation observations (MegaverseGym.set_seg_obs) are per gym: a group's union launches write none, and the library refuses"""
-        raise RuntimeError("MultiTaskGym.set_seg_obs: mv_group_create and mv_step_many refuse a gym with segmentation observations attached "
-                           "(mv_set_seg_obs): the union launches write none; step such a gym on its own")
+        raise _per_gym("set_seg_obs", "segmentation observations", "write")
 
     def set_state_obs(self, buf=True):
         """state observations (MegaverseGym.set_state_obs) are per gym: a group's union launches write none, and the library refuses"""
-        raise RuntimeError("MultiTaskGym.set_state_obs: mv_group_create and mv_step_many refuse a gym with state observations attached "
-                           "(mv_set_state_obs): the union launches write none; step such a gym on its own")
+        raise _per_gym("set_state_obs", "state observations", "write")
 
     def set_scene_obs(self, buf=True):
         """scene observations (MegaverseGym.set_scene_obs) are per gym: a group's union launches write none, and the library refuses"""
-        raise RuntimeError("MultiTaskGym.set_scene_obs: mv_group_create and mv_step_many refuse a gym with scene observations attached "
-                           "(mv_set_scene_obs): the union launches write none; step such a gym on its own")
+        raise _per_gym("set_scene_obs", "scene observations", "write")
 
     def set_entity_obs(self, buf=True):
         """entity observations (MegaverseGym.set_entity_obs) are per gym: a group's union launches write none, and the library refuses"""
-        raise RuntimeError("MultiTaskGym.set_entity_obs: mv_group_create and mv_step_many refuse a gym with entity observations attached "
-                           "(mv_set_entity_obs): the union launches write none; step such a gym on its own")
+        raise _per_gym("set_entity_obs", "entity observations", "write")
 
     def set_overview(self, w, h, buf=True):
         """overview cameras (MegaverseGym.set_overview) are per gym: a group's union launches draw none, and the library refuses"""
-        raise RuntimeError("MultiTaskGym.set_overview: mv_group_create and mv_step_many refuse a gym with an overview attached "
-                           "(mv_set_overview): the union launches draw none; step such a gym on its own")
+        raise _per_gym("set_overview", "an overview", "draw")
 
     def recommended_ticks_per_call(self):
         """the k to ask step_n for: what every member recommends (mv_recommended_ticks_per_call), at most 8 -- the two-launch group call's limit"""
