@@ -443,6 +443,35 @@ int mv_debug_seg_bounds_host(int32_t scenario, int32_t L, int32_t W, int32_t num
                              int32_t num_agents, int32_t *out5);
 int mv_debug_seg_rule_host(int32_t scenario, int32_t slot, const int32_t *boundaries5, int32_t subtype, int32_t format, void *out);
 int mv_debug_seg_pack_host(const int32_t *cls, const int32_t *instance, int32_t n, int32_t format, void *out);
+/* Normal observations (no reference counterpart).  One value of four components per pixel of every frame an observation pass draws: the unit outward normal of
+ * the surface the pixel shows -- of the hit whose t the depth plane holds -- in the viewer's camera frame: x right, y up, z back, the columns of the camera
+ * matrix.  It is the very vector the exact pass shades with, the same floats; only entry faces are hit, so it faces the viewer.  The 4th component is 1 where
+ * there is a surface; a pixel whose ray hits nothing is four zeros, exactly where the depth is 0 and the label is 0.  A frame's record is ONE plane [H][W][4]
+ * in the frame's own pixel order -- row 0 is the bottom row -- whatever mv_set_obs_layout says; depth and normal together unproject to oriented points.
+ * Formats: MV_NORMAL_F16, four halves (x, y, z, 1), each rounded to nearest-even, 8 bytes; MV_NORMAL_SNORM8, four signed bytes (q(x), q(y), q(z), 127) with
+ * q(v) = (int)(127 clamp(v, -1, 1) + (v >= 0 ? 0.5f : -0.5f)), 4 bytes, read back as b / 127.  megaverse_amd/csrc/mv_normal_obs.h states the rule for kernels
+ * and host alike.
+ * The buffer is one more ring beside mv_set_output_ring's three, [entries][N*A][H][W][4] of __half (8-byte aligned) or int8_t (4-byte aligned), entries = the
+ * output ring's count at the moment of the call, or 1; a frame's plane goes to the entry the frame goes to.  Everything else is mv_set_depth_obs's, line for
+ * line: which passes write planes (every one that draws frames; no byte where no frame is drawn; a draw-masked env keeps its planes; mv_draw_hires ignores the
+ * option), the ordering point, NULL detaches, mv_close forgets the pointer, the refusals (groups and mv_step_many, still frames in either order,
+ * mv_set_output_ring and mv_set_render_resolution while attached, an unknown format, a misaligned buffer).  Depth, labels and normals attach and detach
+ * independently, in any order.
+ * How: in exact pixel mode the pass itself stores every attached output, one trace and no further launch.  In fast pixel mode ONE launch per drawn tick follows
+ * the call's passes and stores every attached plane, whichever of the seven subsets of {depth, labels, normals} is attached: never two traces (counted in
+ * out[1] of mv_debug_launch_counts).  Both forms give the same bytes, and a plane's bytes do not depend on what is attached beside it.  Colours, rewards,
+ * dones, rows, the other planes and the log are those of a gym without normals.
+ * Unlike the labels, the normals read nothing outside the frame's own list and header: an env that begins a new episode in a later tick of the same batched
+ * call changes no earlier frame's normals.
+ * mv_get_normal_observation: one agent's plane in the LAST TICK's entry as float32 [H][W][4], halves widened exactly and bytes as b / 127.0f, after waiting
+ * for the gym's stream.  mv_debug_normal_pack_host: the pack rule on the CPU: n vectors xyz[3 i ..] with hit[i] != 0 where the ray hit -> n values of 8 or 4
+ * bytes; no device. */
+enum { MV_NORMAL_F16 = 0, MV_NORMAL_SNORM8 = 1 };
+int mv_set_normal_obs(mv_gym *g, void *device_buf, int32_t format);  /* [max(1, ring count)][N*A][H][W][4] __half / int8 in device memory; NULL detaches */
+int mv_get_normal_obs(const mv_gym *g);                              /* 0: none, else the number of entries; -1: no gym */
+int mv_get_normal_format(const mv_gym *g);                           /* MV_NORMAL_*; -1: none attached */
+int mv_get_normal_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, float *out_host);   /* [H][W][4] float32; waits for the gym's stream */
+int mv_debug_normal_pack_host(const float *xyz, const uint8_t *hit, int32_t n, int32_t format, void *out);   /* the pack function, on the host */
 /* Episode budgets (no reference counterpart: VectorEnv::step resets a finished env on the spot and steps on, vector_env.cpp:89-108).  Per env e the gym owns an
  * int32 left[e]:  < 0: unlimited -- what every env is without these calls;  > 0: the env may still finish that many episodes;  0: the env is HALTED.
  * Tick t, env e, left[e] as it stands before the tick (megaverse_amd/csrc/mv_episode_budget.h states the rule for kernels and host alike):

@@ -153,6 +153,7 @@ OutPtrs outputs_of(const mv_gym *g, unsigned long long tick)
     }
     o.depth = g->depth.entry(tick);   // (mv_set_depth_obs: attached under this ring count, or under none: entry 0)
     o.seg = g->seg.entry(tick);       // (mv_set_seg_obs: the same)
+    o.normal = g->normal.entry(tick); // (mv_set_normal_obs: the same)
     return o;
 }
 OutPtrs last_outputs(const mv_gym *g) { return outputs_of(g, g->ringTick ? g->ringTick - 1 : 0); }   // of the last tick (reset / render / getters)
@@ -993,10 +994,10 @@ int mvapi::render_frames(mv_gym *g)
     GymView v = view(g, g->parity);
     // (not fill_view_options: a pass reads the draw mask alone, and mv_render draws still frames too.  Also the frame behind mv_reset and mv_reset_envs(render = 1))
     v.draw_mask = g->drawMask.live;
-    // (mv_set_depth_obs, mv_set_seg_obs: an exact pass stores the depth and label planes itself, a fast pass is followed by ONE launch for what is attached)
+    // (mv_set_depth_obs, mv_set_seg_obs, mv_set_normal_obs: an exact pass stores the attached planes itself, a fast pass is followed by ONE launch for what is attached)
     const OutPtrs o = last_outputs(g);
-    if (launch_raster(v, o.obs, g->w, g->h, g->stream, nullptr, g->fastPixels, 0, nullptr, nullptr, g->fastPixels ? nullptr : o.depth, g->depth.format,
-                      g->fastPixels ? nullptr : o.seg, g->seg.format))
+    const PlaneOuts po = plane_outs(g, o);
+    if (launch_raster(v, o.obs, g->w, g->h, g->stream, nullptr, g->fastPixels, 0, nullptr, nullptr, g->fastPixels ? nullptr : &po))
         return fail("mv_render: observation size above 1024x1024");
     if (g->fastPixels && planes_follow(g, v, o, "mv_render") < 0) return -1;
     HIP_TRY(hipGetLastError());

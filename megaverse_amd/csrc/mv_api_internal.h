@@ -11,8 +11,8 @@
 //                     envs' frames out of the observation passes (mv_frame.h: frame_skip)
 //   mv_obs_rows.hip   state and scene observations: attaching the caller's buffers, the staging rows, the one publication launch both records share, their
 //                     refresh (mv_state_obs.h, mv_scene_obs.h: the records)
-//   mv_obs_planes.hip  depth and segmentation observations: attaching the caller's buffers, the ONE launch behind a fast pass that writes depth, labels, or
-//                     depth + labels (mv_depth_obs.h, mv_seg_obs.h: the records and their rules; mv_raster.hip: the kernels)
+//   mv_obs_planes.hip  depth, segmentation and normal observations: attaching the caller's buffers, the ONE launch behind a fast pass that writes whatever of
+//                     depth, labels and normals is attached (mv_depth_obs.h, mv_seg_obs.h, mv_normal_obs.h: the records and their rules; mv_raster.hip: the kernels)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 //   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
 //   mv_overview.hip   overview cameras: attaching the buffer, the overview's own arrays, the cameras' two forms, mv_draw_overview (mv_overview.h: the rule;
@@ -135,9 +135,9 @@ struct ObsRows {
 }  // namespace mvapi
 
 namespace mvapi {
-// One plane record of a gym (mv_obs_planes.hip: depth observations, segmentation observations).  buf: the caller's [entries][N*A][H][W] buffer -- depth: of
-// float or __half, labels: of bytes or 16-bit words (null: off; entries: the output ring's count when it was attached, or 1); format: MV_DEPTH_F32 /
-// MV_DEPTH_F16, MV_SEG_CLASS_U8 / MV_SEG_INSTANCE_U16; entryBytes: one entry, the whole gym's planes.
+// One plane record of a gym (mv_obs_planes.hip: depth, segmentation and normal observations).  buf: the caller's [entries][N*A][H][W] buffer -- depth: of
+// float or __half, labels: of bytes or 16-bit words, normals: of four halves or four signed bytes (null: off; entries: the output ring's count when it was attached, or 1); format: MV_DEPTH_F32 /
+// MV_DEPTH_F16, MV_SEG_CLASS_U8 / MV_SEG_INSTANCE_U16, MV_NORMAL_F16 / MV_NORMAL_SNORM8; entryBytes: one entry, the whole gym's planes.
 struct ObsPlanes {
     void *buf = nullptr;
     int format = 0, entries = 0;
@@ -330,6 +330,8 @@ struct mv_gym {
     // mv_set_seg_obs: the caller's label planes, written by the passes of a gym in exact pixel mode and -- fast mode -- by the one launch behind its passes,
     // which then writes the depth planes too
     ObsPlanes seg;
+    // mv_set_normal_obs: the caller's normal planes, written as the other two: by the exact pass itself, or by the one launch behind a fast pass
+    ObsPlanes normal;
     // mv_set_overview: the overview cameras' frames and arrays
     OverviewState overview;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
@@ -375,7 +377,7 @@ struct GymOption {
     const char *memberNone;   // attach_check: "whose union launches <memberNone>"
     bool (*on)(const mv_gym *);
 };
-enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_DEPTH_OBS, OPT_SEG_OBS, OPT_ENTITY_OBS, OPT_OVERVIEW, OPT_COUNT };
+enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_DEPTH_OBS, OPT_SEG_OBS, OPT_NORMAL_OBS, OPT_ENTITY_OBS, OPT_OVERVIEW, OPT_COUNT };
 #define MV_OPT_ON(expr) +[](const mv_gym *g) -> bool { return expr; }
 inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_step_mask", "a step mask attached", "read none", "detach it first", "detach the mask first", "read no step mask", MV_OPT_ON(g->stepMask.live)},
@@ -386,12 +388,13 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_scene_obs", "scene observations attached", "write none", "detach them first", "detach them first", "write no scene observations", MV_OPT_ON(g->sceneRows.buf)},
     {"mv_set_depth_obs", "depth observations attached", "write none", "detach them first", "detach them first", "write no depth observations", MV_OPT_ON(g->depth.buf)},
     {"mv_set_seg_obs", "segmentation observations attached", "write none", "detach them first", "detach them first", "write no segmentation observations", MV_OPT_ON(g->seg.buf)},
+    {"mv_set_normal_obs", "normal observations attached", "write none", "detach them first", "detach them first", "write no normal observations", MV_OPT_ON(g->normal.buf)},
     {"mv_set_entity_obs", "entity observations attached", "write none", "detach them first", "detach them first", "write no entity observations", MV_OPT_ON(g->entityRows.buf)},
     {"mv_set_overview", "an overview attached", "draw none", "detach it first", "detach it first", "draw no overview", MV_OPT_ON(g->overview.buf)},
 };
 #undef MV_OPT_ON
-// The five per-tick observation streams, stated once, in the order mv_set_output_ring refuses them: the option that attaches the stream, the noun the refusal
-// texts name it by and, for the two plane streams (mv_obs_planes.hip), the name of one plane; null: a row stream (mv_obs_rows.hip).  A new stream is one row
+// The six per-tick observation streams, stated once, in the order mv_set_output_ring refuses them: the option that attaches the stream, the noun the refusal
+// texts name it by and, for the three plane streams (mv_obs_planes.hip), the name of one plane; null: a row stream (mv_obs_rows.hip).  A new stream is one row
 // here, one in gym_options and one descriptor in its file.
 struct ObsStream {
     int opt;
@@ -401,10 +404,18 @@ inline constexpr ObsStream obs_streams[] = {
     {OPT_STATE_OBS, "state observations", nullptr},
     {OPT_DEPTH_OBS, "depth observations", "depth plane"},
     {OPT_SEG_OBS, "segmentation observations", "label plane"},
+    {OPT_NORMAL_OBS, "normal observations", "normal plane"},
     {OPT_SCENE_OBS, "scene observations", nullptr},
     {OPT_ENTITY_OBS, "entity observations", nullptr},
 };
 constexpr const ObsStream &obs_stream(int opt, int i = 0) { return obs_streams[i].opt == opt ? obs_streams[i] : obs_stream(opt, i + 1); }
+// a plane stream is attached: a fast pass of g is followed by the planes' launch
+inline bool any_planes_on(const mv_gym *g)
+{
+    for (const ObsStream &s : obs_streams)
+        if (s.plane && gym_options[s.opt].on(g)) return true;
+    return false;
+}
 // What a stepping call's view of g carries of the options (the rows of the two records are fields of the per-slot views already: mv_gym::gvp); macro: the view
 // belongs to a macro step's tick (mv_macro_step) and carries the envs' ticks left.  A group's members have none of them (mv_group_create).
 inline void fill_view_options(GymView &v, const mv_gym *g, bool macro)
@@ -419,8 +430,10 @@ inline void fill_view_options(GymView &v, const mv_gym *g, bool macro)
 // Where a tick's public outputs go: the observation slab and the reward / done arrays -- or, with mv_set_output_ring, entry (tick % count)
 // of the caller's rings.  true_objective is state (only a finishing env records it, vector_env.cpp:96-101): never ringed.
 // depth (mv_set_depth_obs): the entry's depth planes, null with no buffer attached.
-// seg (mv_set_seg_obs): the entry's label planes, likewise.
-struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; void *depth = nullptr; void *seg = nullptr; };
+// seg (mv_set_seg_obs), normal (mv_set_normal_obs): the entry's label planes and normal planes, likewise.
+struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; void *depth = nullptr; void *seg = nullptr; void *normal = nullptr; };
+// the planes of one tick's entry and their formats, as the observation pass takes them (mv_raster.h: PlaneOuts; null: not attached)
+PlaneOuts plane_outs(const mv_gym *g, const OutPtrs &o);
 std::string lower(const char *s);
 int check(mv_gym *g);
 // what every form of a persistent attachment refuses: no gym, a closed one, a member of a group (the union launches read or write none of what opt attaches)
@@ -473,14 +486,14 @@ int step_macro_chunk(mv_gym *g, int k, int kCall, bool draw_last, const MacroCal
 int obs_rows_publish(mv_gym *g, int q0, unsigned long long tick0, int k);
 int obs_rows_refresh(mv_gym *g, const uint8_t *device_mask);
 void obs_rows_free(mv_gym *g);         // mv_close
-// mv_obs_planes.hip: the one follower behind a FAST pass of view v, whatever is attached (an exact pass stores the planes itself: launch_raster's depth and
-// label arguments) -- the label planes (o.seg) and, where depth observations are attached too, the depth planes (o.depth) of the frames the pass has just
-// drawn, or the depth planes alone, with ONE launch on the caller's stream; -> launches made (0: nothing attached or planes null), -1
+// mv_obs_planes.hip: the one follower behind a FAST pass of view v, whatever is attached (an exact pass stores the planes itself: launch_raster's planes
+// argument) -- the depth planes (o.depth), label planes (o.seg) and normal planes (o.normal) of the frames the pass has just drawn, each where its stream
+// is attached, with ONE launch on the caller's stream; -> launches made (0: nothing attached or planes null), -1
 int planes_follow(mv_gym *g, const GymView &v, const OutPtrs &o, const char *who);
 void obs_planes_free(mv_gym *g);       // mv_close
 // What the calls that an attached stream forbids answer (mv_api.hip), each walking obs_streams and composing "<who>: <noun> are attached (<setter>), <clause>:
-// detach the <noun> first" for the first stream that is on; -> -1 with that text, 0: none is.  ring_sized_attached: all five, sized by the ring count they
-// were attached under.  planes_attached: the two plane streams, with the caller's clause.  still_clause: why still frames and a plane stream exclude each other
+// detach the <noun> first" for the first stream that is on; -> -1 with that text, 0: none is.  ring_sized_attached: all six, sized by the ring count they
+// were attached under.  planes_attached: the three plane streams, with the caller's clause.  still_clause: why still frames and a plane stream exclude each other
 // (mv_set_still_frames; the plane setters' own refusal)
 int ring_sized_attached(const mv_gym *g, const char *who);
 int planes_attached(const mv_gym *g, const char *who, std::string (*clause)(const ObsStream &));

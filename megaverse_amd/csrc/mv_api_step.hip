@@ -45,8 +45,8 @@ struct StepCall {
     bool drawLast;            // QUIET_LAST: tick k - 1 is drawn
     bool sideWaits;           // (not pipelined) a draw launch, a status read-back or an upload will wait for this call: an event behind the ticks
     bool overlap;             // the one pass launch goes to a pass stream (mv_set_pass_overlap): passOn
-    bool rows, carry, depth;  // followers: the row records' publication, the still frames' carry, the depth and label planes behind fast passes -- ONE launch per
-                              // drawn tick for whichever of the two are attached (the log: per gym, logCapacity)
+    bool rows, carry, depth;  // followers: the row records' publication, the still frames' carry, the depth, label and normal planes behind fast passes -- ONE launch per
+                              // drawn tick for whichever of the three are attached (the log: per gym, logCapacity)
     bool timeCall, timeTicks;   // timing (mv_profile_begin): ONE entry for the whole call (callEv), or one per tick for the first tickEvs ticks (tickEv);
     hipEvent_t *callEv = nullptr, *tickEv = nullptr;   // reserve_timing takes the entries, behind the checks and the refill as always
     int tickEvs = 0;
@@ -131,8 +131,8 @@ struct StepCall {
         carry = n == 1 && L->stillOn && L->ringObs != nullptr && (r.render || drawLast);
         // (mv_set_depth_obs, fast pixels: one depth launch per drawn tick behind the call's passes, reading the tick's frame lists from the call's slots -- an exact
         // pass stores the planes itself, one_pass; a group's members have none)
-        // (mv_set_seg_obs: the same follower, which then stores labels, or depth + labels)
-        depth = n == 1 && (L->depth.buf != nullptr || L->seg.buf != nullptr) && L->fastPixels != 0 && (r.render || drawLast);
+        // (mv_set_seg_obs, mv_set_normal_obs: the same follower, which then stores every attached plane)
+        depth = n == 1 && any_planes_on(L) && L->fastPixels != 0 && (r.render || drawLast);
         // overlapped passes (mv_set_pass_overlap): this call's one launch goes to an internal stream
         // (an env must not finish in two consecutive calls: their passes may publish its true objective in either order -- episodes of at least
         // baseEpisodeLen seconds, 15 ticks each)
@@ -378,12 +378,11 @@ struct StepCall {
     // ... then publication and passes, by pass path.  One gym's pass of one tick, its lists set up inside the step launch (a fast pass whose view says
     // lpt_no_clear leaves its cost histogram zero: self_clear, mv_raster.hip):
     // (mv_set_depth_obs: an EXACT pass stores the tick's depth planes itself -- planes: OutPtrs::depth of the tick; a fast pass gets none, followers_and_mark)
-    // (mv_set_seg_obs: and its label planes -- labels: OutPtrs::seg of the tick)
-    int one_pass(mv_gym *g, const GymView &v, uint32_t *obs, hipEvent_t between, const PublishTo *pub, hipEvent_t done, const char *who, void *planes = nullptr,
-                 void *labels = nullptr)
+    // (mv_set_seg_obs, mv_set_normal_obs: and its label and normal planes -- planes: the tick's OutPtrs, whose plane entries go with it)
+    int one_pass(mv_gym *g, const GymView &v, uint32_t *obs, hipEvent_t between, const PublishTo *pub, hipEvent_t done, const char *who, const OutPtrs *planes = nullptr)
     {
-        if (launch_raster(v, obs, L->w, L->h, L->stream, between, g->fastPixels, /*setup_done=*/1, pub, done, g->fastPixels ? nullptr : planes, g->depth.format,
-                          g->fastPixels ? nullptr : labels, g->seg.format))
+        const PlaneOuts po = planes ? plane_outs(g, *planes) : PlaneOuts();
+        if (launch_raster(v, obs, L->w, L->h, L->stream, between, g->fastPixels, /*setup_done=*/1, pub, done, g->fastPixels ? nullptr : &po))
             return fail(std::string(who) + ": observation size above 1024x1024");
         ++L->launchCount[1];
         if (v.lpt_no_clear && g->fastPixels) g->histClean[(size_t)v.lpt_parity] = 1;
@@ -414,7 +413,7 @@ struct StepCall {
             } else
                 for (int i = 0; i < n; ++i)
                     if (one_pass(gs[i], vj[i], obsPtrs[i], e && i == 0 ? e[3] : nullptr, pubInRaster ? &pubs[i] : nullptr, i == n - 1 ? done : nullptr, "mv_step",
-                                 outs[(size_t)j * n + i].depth, outs[(size_t)j * n + i].seg)) return -1;
+                                 &outs[(size_t)j * n + i])) return -1;
             if (e) HIP_TRY(hipEventRecord(e[4], L->stream));
         }
         return 0;
@@ -467,8 +466,7 @@ struct StepCall {
     {
         const int q0 = L->group * L->batch;
         if (staged && (r.mc ? publish_macro(L, q0, outs[0], k, !r.mc->first) : publish_ticks(L, q0, outs.data(), n, k))) return -1;
-        if (drawLast) return one_pass(L, views[(size_t)k - 1], outs[(size_t)k - 1].obs, nullptr, nullptr, mark(), "mv_step_n_render", outs[(size_t)k - 1].depth,
-                                      outs[(size_t)k - 1].seg);
+        if (drawLast) return one_pass(L, views[(size_t)k - 1], outs[(size_t)k - 1].obs, nullptr, nullptr, mark(), "mv_step_n_render", &outs[(size_t)k - 1]);
         if (own) HIP_TRY(hipEventRecord(mark(), L->stream));
         return 0;
     }

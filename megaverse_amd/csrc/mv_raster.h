@@ -16,18 +16,25 @@ namespace mv {
 struct PublishTo { float *rewards; uint8_t *done; float *true_objective; };
 // done: an event that completes when the pass does.  The fast kernels carry it as the completion signal of their own dispatch packet
 // (hipExtLaunchKernelGGL's stop event) -- a separate hipEventRecord is one more packet the queue works off between two passes, ~5 us.
-// depth (mv_set_depth_obs; fast = 0 only, null: none): the gym's depth entry [N*A][H][W] in depth_format (mv_depth_obs.h) -- the exact pass becomes the
-// instantiation that stores the nearest hit's t beside the colours: one trace, two outputs, no further launch.  A fast pass stores no depth: its kernels stay
-// what they are, and the caller follows it with launch_raster_depth.
+// The planes of one tick's entry beside its colours, each null where its stream is not attached: the gym's depth entry [N*A][H][W] in depth_format
+// (mv_set_depth_obs; mv_depth_obs.h), its label entry [N*A][H][W] in seg_format (mv_set_seg_obs; mv_seg_obs.h), its normal entry [N*A][H][W][4] in
+// normal_format (mv_set_normal_obs; mv_normal_obs.h).
+struct PlaneOuts {
+    void *depth = nullptr; int depth_format = 0;
+    void *seg = nullptr; int seg_format = 0;
+    void *normal = nullptr; int normal_format = 0;
+    bool any() const { return depth || seg || normal; }
+};
+// planes (fast = 0 only; null or all null: none): the exact pass becomes the instantiation that stores every given plane beside the colours: one trace, every
+// output, no further launch.  A fast pass stores no plane: its kernels stay what they are, and the caller follows it with launch_raster_planes.
 int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t stream, hipEvent_t between = nullptr, int fast = 1, int setup_done = 0,
-                  const PublishTo *publish = nullptr, hipEvent_t done = nullptr, void *depth = nullptr, int depth_format = 0, void *seg = nullptr, int seg_format = 0);
+                  const PublishTo *publish = nullptr, hipEvent_t done = nullptr, const PlaneOuts *planes = nullptr);
 
-// The depth planes of every frame of gv -- its lists already set up -- with one launch of the exact kernel's depth-only form: the trace and the depth store,
-// no shading.  Frames in identity order; an undrawn or still frame (mv_frame.h: frame_skip) writes nothing.  -1: W / H too large, no plane, unknown format.
-int launch_raster_depth(const GymView &gv, void *depth, int depth_format, int W, int H, hipStream_t stream);
-// The same with labels attached (mv_set_seg_obs; mv_seg_obs.h): the label planes of every frame of gv -- and, depth non-null, its depth planes -- with ONE launch
-// of the exact trace: never two.  seg (launch_raster, fast = 0 only): the exact pass stores the label planes itself, beside the colours and, if given, the depth.
-int launch_raster_seg(const GymView &gv, void *depth, int depth_format, void *seg, int seg_format, int W, int H, hipStream_t stream);
+// The planes of every frame of gv -- its lists already set up -- with ONE launch of the exact trace without the shading, whichever of the seven non-empty sets
+// of {depth, labels, normals} po names: never two.  Depth alone, labels alone and depth + labels: the kernels they always had; a set with normals: the
+// normal kernel, which takes the other two by their pointers.  Frames in identity order; an undrawn or still frame (mv_frame.h: frame_skip) writes nothing.
+// -1: W / H too large, no plane, an unknown format.
+int launch_raster_planes(const GymView &gv, const PlaneOuts &po, int W, int H, hipStream_t stream);
 
 // Overview cameras (mv_overview.h): the frame setup of every env from its camera ov.cams[env], the frame order from the overview's own cost bins and the exact
 // pass into obs [N][H][W] RGBA, three launches on `stream`.  gv: a view whose vis_prims / vis_rects / vis_count / vis_stride / lpt_bucket / lpt_order / vis_hdr

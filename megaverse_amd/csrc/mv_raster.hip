@@ -42,6 +42,7 @@
 #include "../../include/megaverse_hip.h"
 #include "mv_depth_obs.h"
 #include "mv_seg_obs.h"
+#include "mv_normal_obs.h"
 #include "mv_frame.h"
 #include "mv_math.h"
 #include "mv_raster.h"
@@ -464,8 +465,10 @@ __device__ __forceinline__ void put_px(const PixOutT<true> &po, int px, int py, 
 // What the exact kernel's body leaves behind (mv_depth_obs.h: the depth record).  OUT_RGB: the frame's colours -- raster_kernel, as it always was.
 // OUT_RGBD: the same bytes, and the nearest hit's t of every pixel in the frame's depth plane: one trace, two outputs.  OUT_DEPTH: the trace and the depth
 // store alone -- no normal, no Phong, no colour tables (raster_depth_kernel).  With mv_seg_obs.h's label record OUT is a SET of outputs -- colours, depth,
-// labels: OUT_LABEL beside any of the above, or alone (raster_seg_kernel).
-enum : int { OUT_COLOURS = 1, OUT_DEPTHS = 2, OUT_LABEL = 4, OUT_RGB = OUT_COLOURS, OUT_RGBD = OUT_COLOURS | OUT_DEPTHS, OUT_DEPTH = OUT_DEPTHS };
+// labels: OUT_LABEL beside any of the above, or alone (raster_seg_kernel).  OUT_NORMAL (mv_normal_obs.h: the normal record; raster_normal_kernel): the normal
+// plane, and with it the depth and label planes as a wave-uniform RUN-TIME choice -- such an instantiation names OUT_DEPTHS | OUT_LABEL too and stores each of
+// the two where its base pointer is not null, so that one kernel serves every set of planes that holds normals.
+enum : int { OUT_COLOURS = 1, OUT_DEPTHS = 2, OUT_LABEL = 4, OUT_NORMAL = 8, OUT_RGB = OUT_COLOURS, OUT_RGBD = OUT_COLOURS | OUT_DEPTHS, OUT_DEPTH = OUT_DEPTHS };
 
 // One pixel's depth value into its frame's plane [H][W] (the RGBA store's bounds: px < W && py < H).  Every lane of the wave takes part -- the callers reach
 // this in wave-uniform control flow, the stores are masked after the exchange.  DEPTH_F16, W even: a plane row starts dword-aligned and neighbouring lanes own
@@ -509,20 +512,41 @@ __device__ __forceinline__ void put_label(void *plane, int format, bool wide, in
     }
 }
 
+// One pixel's normal into its frame's plane [H][W][4] (mv_normal_obs.h; the RGBA store's bounds), under put_depth's conventions: every lane of the wave takes
+// part, the stores are masked.  A value is a whole 8-byte (NORMAL_F16: four conversions packed in registers) or 4-byte (NORMAL_SNORM8) word, so every lane
+// makes ONE store of its own and no lane exchange is needed: the 16 lanes of a tile row write 128 or 64 contiguous bytes.  The plane starts 8- / 4-byte aligned
+// (mv_set_normal_obs checks the buffer, a plane is a multiple of its value's size).
+__device__ __forceinline__ void put_normal(void *plane, int format, int W, int H, int px, int py, V3 N, bool hit)
+{
+    const bool in = px < W && py < H;
+    const size_t at = (size_t)py * W + px;
+    if (format == NORMAL_F16) {   // (uniform)
+        const uint64_t b = normal_bits_f16(N.x, N.y, N.z, hit);
+        if (in) reinterpret_cast<uint2 *>(plane)[at] = make_uint2((unsigned)b, (unsigned)(b >> 32));
+    } else {
+        const uint32_t b = normal_bits_snorm8(N.x, N.y, N.z, hit);
+        if (in) reinterpret_cast<uint32_t *>(plane)[at] = b;
+    }
+}
+
 }  // namespace
 
 // The exact observation pass of one frame part: tile cull, nearest hit with the draw-order tie rule, Phong.  OUT: what it stores (above); depth / depth_format:
 // the gym's depth entry (frame f's plane at f W H values) and its format, read where OUT has OUT_DEPTHS; seg / seg_format: the same for the label planes
-// (OUT_LABEL); order: null (OUT != OUT_RGB only): position = frame.
+// (OUT_LABEL); normal / normal_format: the same for the normal planes (OUT_NORMAL, where depth and seg may be null: not attached); order: null (OUT !=
+// OUT_RGB only): position = frame.
 // CHW: the planar layout (mv_set_obs_layout; PixOutT above)
 // OVERVIEW (overview_raster_kernel; mv_overview.h): one frame per env, seen from the camera its setup left in ovc[env] -- an agent's own frame of reference, or
 // one more, index MAX_CAMS, loaded from the record; gv's list fields are the overview's own arrays.  The arithmetic is the code below, shared; every other
 // instantiation passes false and compiles what it always did.
 template <int MAXVIS, bool SHAPES, bool CHW, int OUT, bool OVERVIEW = false>   // SHAPES: the frame may hold scaled spheres / capsules / cylinders (Rearrange)
 __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, void *depth, int depth_format, void *seg, int seg_format, int W, int H, int split,
-                                            const int *order, const OverviewCam *ovc = nullptr)
+                                            const int *order, const OverviewCam *ovc = nullptr, void *normal = nullptr, int normal_format = 0)
 {
-    constexpr bool RGB = (OUT & OUT_COLOURS) != 0, DEPTH = (OUT & OUT_DEPTHS) != 0, LABEL = (OUT & OUT_LABEL) != 0;
+    constexpr bool RGB = (OUT & OUT_COLOURS) != 0, DEPTH = (OUT & OUT_DEPTHS) != 0, LABEL = (OUT & OUT_LABEL) != 0, NORMAL = (OUT & OUT_NORMAL) != 0;
+    static_assert(!NORMAL || (DEPTH && LABEL), "a kernel that stores normals takes the other two planes by their pointers");
+    // (OUT_NORMAL: depth and labels are stored where attached -- uniform over the launch; every other instantiation: where OUT says, as always)
+    const bool depthOn = NORMAL ? depth != nullptr : DEPTH, labelOn = NORMAL ? seg != nullptr : LABEL;
     constexpr int ROUNDS = MAXVIS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];   // column/row ray tables
     __shared__ Prim s_vis[MAXVIS];       // this frame's visible list
@@ -606,7 +630,7 @@ __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, vo
             s_lutA[tid] = AMB * c;
             s_lutD[tid] = (DIF * c) * LCOL;
         }
-        if constexpr (LABEL) {   // mv_seg_obs.h: the rule, once per visible primitive -- its slot and sub-type from the list, the boundaries from the env's header
+        if (LABEL && labelOn) {   // mv_seg_obs.h: the rule, once per visible primitive -- its slot and sub-type from the list, the boundaries from the env's header
             const Prim *gp = reinterpret_cast<const Prim *>(gv.vis_prims) + (size_t)frame * gv.vis_stride;
             const SegBounds sb = seg_bounds(gv.hdr[env], A);
             const bool layoutRecords = !seg_hex_records(gv.scenario);
@@ -628,6 +652,7 @@ __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, vo
     uint32_t *out = RGB ? obs + (size_t)frame * W * H : nullptr;   // (depth only: no colour slab)
     void *plane = DEPTH ? reinterpret_cast<unsigned char *>(depth) + (size_t)frame * depth_plane_bytes(W, H, depth_format) : nullptr;   // (this frame's depth plane)
     void *lplane = LABEL ? reinterpret_cast<unsigned char *>(seg) + (size_t)frame * seg_plane_bytes(W, H, seg_format) : nullptr;         // (this frame's label plane)
+    void *nplane = NORMAL ? reinterpret_cast<unsigned char *>(normal) + (size_t)frame * normal_plane_bytes(W, H, normal_format) : nullptr;   // (this frame's normal plane)
     const bool lwide = LABEL && (reinterpret_cast<uintptr_t>(lplane) & 3) == 0;
 
     const float nzm[3] = {-cam.c[2], -cam.c[5], -cam.c[8]};   // c_k2 * (-1)
@@ -665,8 +690,9 @@ __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, vo
                     if constexpr (CHW) put_px(frame_out<true>(obs, frame, W, H, false), px, pyBase + TILE_H * k, 0xff000000u);
                     else if (px < W && pyBase + TILE_H * k < H) out[(size_t)(pyBase + TILE_H * k) * W + px] = 0xff000000u;
                 }
-                if constexpr (DEPTH) put_depth(plane, depth_format, W, H, px, pyBase + TILE_H * k, 0.0f, false);
-                if constexpr (LABEL) put_label(lplane, seg_format, lwide, W, H, px, pyBase + TILE_H * k, 0u);
+                if (DEPTH && depthOn) put_depth(plane, depth_format, W, H, px, pyBase + TILE_H * k, 0.0f, false);
+                if (LABEL && labelOn) put_label(lplane, seg_format, lwide, W, H, px, pyBase + TILE_H * k, 0u);
+                if constexpr (NORMAL) put_normal(nplane, normal_format, W, H, px, pyBase + TILE_H * k, v3(0, 0, 0), false);
             }
             continue;
         }
@@ -732,13 +758,18 @@ __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, vo
 #pragma unroll
         for (int k = 0; k < PPL; ++k) {
             const int py = pyBase + TILE_H * k;
-            if constexpr (DEPTH) put_depth(plane, depth_format, W, H, px, py, best[k], bestPos[k] >= 0);   // best[k]: the float the shading works from
-            if constexpr (LABEL) put_label(lplane, seg_format, lwide, W, H, px, py, bestPos[k] >= 0 ? (unsigned)s_label[bestPos[k]] : 0u);
-            if constexpr (!RGB) continue;
+            if (DEPTH && depthOn) put_depth(plane, depth_format, W, H, px, py, best[k], bestPos[k] >= 0);   // best[k]: the float the shading works from
+            if (LABEL && labelOn) put_label(lplane, seg_format, lwide, W, H, px, py, bestPos[k] >= 0 ? (unsigned)s_label[bestPos[k]] : 0u);
+            if constexpr (!RGB && !NORMAL) continue;
             unsigned rgba = 0xff000000u;
+            [[maybe_unused]] V3 stored = v3(0, 0, 0);   // (OUT_NORMAL) what the normal plane holds: N, or zeros where nothing was hit
             if (bestPos[k] >= 0) {
                 const Prim &q = s_vis[bestPos[k]];
                 const int qkind = q.meta & 15, qfr = (q.meta >> 4) & 15;
+                // The unit outward normal in the viewer's camera frame: derived ONCE, here, for the Phong term and for the normal plane (mv_normal_obs.h) alike.
+                // Leave it in the body: as a __forceinline__ function of its own (by value, by reference, with an out-parameter: all three were built) the callee
+                // is simplified before it is inlined, 14 of the exact pass's existing kernels come out one VGPR lighter, and they are required to stay what they
+                // are (profiles/normal_obs_resources.txt).
                 V3 N;
                 if (qkind != PRIM_BOX) {
                     if (!SHAPES || qfr == 0) N = mat_tmul(cam.c, capN[k]);
@@ -761,33 +792,38 @@ __device__ __forceinline__ void raster_body(const GymView &gv, uint32_t *obs, vo
                     else if (qfr == 1 + viewer) N = n;
                     else N = mat_tmul(cam.c, mat_mul(s_cam[qfr - 1].c, n));
                 }
-                const V3 P = dc[k] * best[k];
-                V3 Ld = v3(LIGHT[0] - P.x, LIGHT[1] - P.y, LIGHT[2] - P.z);
-                Ld = Ld * (1.0f / sqrtf(len2(Ld)));
-                const float intensity = fmax_sel(0.0f, dot(N, Ld));
-                float spec = 0.0f;
-                if (intensity > 0.001f) {
-                    const float k2 = 2.0f * dot(N, Ld);
-                    const V3 R = v3(k2 * N.x - Ld.x, k2 * N.y - Ld.y, k2 * N.z - Ld.z);
-                    V3 Vd = v3(-P.x, -P.y, -P.z);
-                    // shininess 300: cos^300 is below 1e-20 once cos < 0.86, i.e. far under half an ulp of the
-                    // diffuse term it is added to (>= 0.04), so the addition is an exact no-op there.  Only
-                    // pixels inside the highlight cone pay for the normalisation and the power.
-                    const float vr = dot(Vd, R);
-                    if (vr > 0.0f && vr * vr > 0.7225f * len2(Vd)) {   // cos > 0.85 (|R| == 1 up to rounding)
-                        Vd = Vd * (1.0f / sqrtf(len2(Vd)));
-                        spec = pow300(fmax_sel(0.0f, dot(Vd, R)));
-                        spec = fmin_sel(fmax_sel(spec, 0.0f), 1.0f);
+                if constexpr (NORMAL) stored = N;
+                if constexpr (RGB) {   // (planes only: no Phong, no colour tables, no highlight)
+                    const V3 P = dc[k] * best[k];
+                    V3 Ld = v3(LIGHT[0] - P.x, LIGHT[1] - P.y, LIGHT[2] - P.z);
+                    Ld = Ld * (1.0f / sqrtf(len2(Ld)));
+                    const float intensity = fmax_sel(0.0f, dot(N, Ld));
+                    float spec = 0.0f;
+                    if (intensity > 0.001f) {
+                        const float k2 = 2.0f * dot(N, Ld);
+                        const V3 R = v3(k2 * N.x - Ld.x, k2 * N.y - Ld.y, k2 * N.z - Ld.z);
+                        V3 Vd = v3(-P.x, -P.y, -P.z);
+                        // shininess 300: cos^300 is below 1e-20 once cos < 0.86, i.e. far under half an ulp of the
+                        // diffuse term it is added to (>= 0.04), so the addition is an exact no-op there.  Only
+                        // pixels inside the highlight cone pay for the normalisation and the power.
+                        const float vr = dot(Vd, R);
+                        if (vr > 0.0f && vr * vr > 0.7225f * len2(Vd)) {   // cos > 0.85 (|R| == 1 up to rounding)
+                            Vd = Vd * (1.0f / sqrtf(len2(Vd)));
+                            spec = pow300(fmax_sel(0.0f, dot(Vd, R)));
+                            spec = fmin_sel(fmax_sel(spec, 0.0f), 1.0f);
+                        }
                     }
-                }
-                unsigned ch[3];
+                    unsigned ch[3];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const unsigned byte = (q.color >> (16 - 8 * c)) & 255u;
-                    ch[c] = to_u8((s_lutA[byte] + s_lutD[byte] * intensity) + spec);
+                    for (int c = 0; c < 3; ++c) {
+                        const unsigned byte = (q.color >> (16 - 8 * c)) & 255u;
+                        ch[c] = to_u8((s_lutA[byte] + s_lutD[byte] * intensity) + spec);
+                    }
+                    rgba = ch[0] | (ch[1] << 8) | (ch[2] << 16) | 0xff000000u;
                 }
-                rgba = ch[0] | (ch[1] << 8) | (ch[2] << 16) | 0xff000000u;
             }
+            if constexpr (NORMAL) put_normal(nplane, normal_format, W, H, px, py, stored, bestPos[k] >= 0);
+            if constexpr (!RGB) continue;
             if constexpr (CHW) put_px(frame_out<true>(obs, frame, W, H, false), px, py, rgba);
             else if (px < W && py < H) out[(size_t)py * W + px] = rgba;
         }
@@ -850,6 +886,28 @@ __global__ __launch_bounds__(256, seg_waves(MAXVIS, SHAPES, MODE)) void raster_s
 {
     static_assert((MODE & OUT_LABEL) != 0, "raster_seg_kernel stores labels");
     raster_body<MAXVIS, SHAPES, CHW, MODE>(gv, obs, depth, depth_format, seg, seg_format, W, H, split, order);
+}
+
+// Normal observations (mv_set_normal_obs): the exact pass with a normal plane among its outputs.  Twelve more MODE bits over four lists and two layouts would
+// be 48 more heavy kernels; instead the kernels chosen when normals are attached take the other two planes as a RUN-TIME set, uniform over the launch -- po.depth
+// and po.seg, null: not attached -- and are templated on the list, on the colours (COLOURS = true: the pass of a gym in exact pixel mode, one trace for every
+// output; false: the ONE follower behind a fast pass, whichever of the four sets with normals is attached) and, with colours, on their layout: 4 + 8 kernels.
+// A set without labels fills no label table and reads nothing outside the frame's own list and header.
+// Launch bounds, as depth_waves: the occupancy the compiler reports for an unbounded build (min waves 1) -- the follower 68 / 74 VGPRs and 106 SGPRs with the
+// short lists (plain / scaled shapes): 7 waves, 6; with colours 70 / 76 VGPRs (RGBA): 7, 6, and 73 / 79 (planar): 6, 6; the long lists are bound by their LDS
+// (3 waves, 1 wave) at 70..75 / 82..88 VGPRs.  Those are the UNBOUNDED build's figures; built WITH these bounds -- the library's build, the table of
+// profiles/normal_obs_resources.txt -- the occupancies are the same and two figures move: the planar scaled-shape kernel takes 78 VGPRs, not 79, and the
+// two plain short-list kernels at 7 waves take 94 SGPRs, not 106.
+constexpr int normal_waves(int maxvis, bool shapes, bool colours, bool chw)
+{
+    return maxvis > 1024 ? 1 : maxvis > 256 ? 3 : shapes || (colours && chw) ? 6 : 7;
+}
+template <int MAXVIS, bool SHAPES, bool COLOURS, bool CHW = false>
+__global__ __launch_bounds__(256, normal_waves(MAXVIS, SHAPES, COLOURS, CHW)) void raster_normal_kernel(GymView gv, uint32_t *obs, PlaneOuts po, int W, int H, int split,
+                                                                                                 const int *order)
+{
+    raster_body<MAXVIS, SHAPES, CHW, (COLOURS ? OUT_COLOURS : 0) | OUT_DEPTHS | OUT_LABEL | OUT_NORMAL>(gv, obs, po.depth, po.depth_format, po.seg, po.seg_format, W, H,
+                                                                                                       split, order, nullptr, po.normal, po.normal_format);
 }
 
 // =====================================================================================================================
@@ -3038,24 +3096,30 @@ static auto by_list(const GymView &gv, Pick pick)
          : shapes ? pick(std::integral_constant<int, VIS_SMALL>{}, std::true_type{}) : pick(std::integral_constant<int, VIS_SMALL>{}, std::false_type{});
 }
 
-int launch_raster_depth(const GymView &gv, void *depth, int depth_format, int W, int H, hipStream_t stream)
+// a set of planes names known formats (before anything is enqueued; the setters let no other format through)
+static bool plane_formats_known(const PlaneOuts &po)
 {
-    if (W > MAX_W || H > MAX_H || !depth || !depth_format_known(depth_format)) return -1;
-    const int frames = gv.num_envs * gv.num_agents, split = exact_split(W, H);
-    const auto fn = by_list(gv, [](auto maxvis, auto shapes) { return raster_depth_kernel<decltype(maxvis)::value, decltype(shapes)::value, true>; });
-    hipLaunchKernelGGL(fn, dim3(frames * split), dim3(256), exact_dyn_lds(W, H), stream, gv, (uint32_t *)nullptr, depth, depth_format, W, H, split, (const int *)nullptr);
-    return 0;
+    return (!po.depth || depth_format_known(po.depth_format)) && (!po.seg || seg_format_known(po.seg_format)) && (!po.normal || normal_format_known(po.normal_format));
 }
 
-// The planes behind a fast pass with labels attached: ONE launch for the labels, or for depth + labels (depth: null = none).
-int launch_raster_seg(const GymView &gv, void *depth, int depth_format, void *seg, int seg_format, int W, int H, hipStream_t stream)
+// The planes behind a fast pass: ONE launch, whatever is attached.
+int launch_raster_planes(const GymView &gv, const PlaneOuts &po, int W, int H, hipStream_t stream)
 {
-    if (W > MAX_W || H > MAX_H || !seg || !seg_format_known(seg_format) || (depth && !depth_format_known(depth_format))) return -1;
+    if (W > MAX_W || H > MAX_H || !po.any() || !plane_formats_known(po)) return -1;
     const int frames = gv.num_envs * gv.num_agents, split = exact_split(W, H);
-    const auto fn = depth ? by_list(gv, [](auto maxvis, auto shapes) { return raster_seg_kernel<decltype(maxvis)::value, decltype(shapes)::value, OUT_DEPTHS | OUT_LABEL>; })
-                          : by_list(gv, [](auto maxvis, auto shapes) { return raster_seg_kernel<decltype(maxvis)::value, decltype(shapes)::value, OUT_LABEL>; });
-    hipLaunchKernelGGL(fn, dim3(frames * split), dim3(256), exact_dyn_lds(W, H), stream, gv, (uint32_t *)nullptr, depth, depth_format, seg, seg_format, W, H, split,
-                       (const int *)nullptr);
+    const dim3 grid(frames * split), block(256);
+    const size_t dyn = exact_dyn_lds(W, H);
+    if (po.normal) {   // (normals, and what else is attached by its pointer)
+        const auto fn = by_list(gv, [](auto maxvis, auto shapes) { return raster_normal_kernel<decltype(maxvis)::value, decltype(shapes)::value, false>; });
+        hipLaunchKernelGGL(fn, grid, block, dyn, stream, gv, (uint32_t *)nullptr, po, W, H, split, (const int *)nullptr);
+    } else if (po.seg) {   // (labels, or depth + labels)
+        const auto fn = po.depth ? by_list(gv, [](auto maxvis, auto shapes) { return raster_seg_kernel<decltype(maxvis)::value, decltype(shapes)::value, OUT_DEPTHS | OUT_LABEL>; })
+                                 : by_list(gv, [](auto maxvis, auto shapes) { return raster_seg_kernel<decltype(maxvis)::value, decltype(shapes)::value, OUT_LABEL>; });
+        hipLaunchKernelGGL(fn, grid, block, dyn, stream, gv, (uint32_t *)nullptr, po.depth, po.depth_format, po.seg, po.seg_format, W, H, split, (const int *)nullptr);
+    } else {   // (depth alone: the trace and the depth store, no shading)
+        const auto fn = by_list(gv, [](auto maxvis, auto shapes) { return raster_depth_kernel<decltype(maxvis)::value, decltype(shapes)::value, true>; });
+        hipLaunchKernelGGL(fn, grid, block, dyn, stream, gv, (uint32_t *)nullptr, po.depth, po.depth_format, W, H, split, (const int *)nullptr);
+    }
     return 0;
 }
 
@@ -3075,11 +3139,13 @@ int launch_overview(const GymView &gv, const OverviewArgs &ov, uint32_t *obs, in
 }
 
 int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t stream, hipEvent_t between,
-                  int fast, int setup_done, const PublishTo *publish, hipEvent_t done, void *depth, int depth_format, void *seg, int seg_format)
+                  int fast, int setup_done, const PublishTo *publish, hipEvent_t done, const PlaneOuts *planes)
 {
     if (W > MAX_W || H > MAX_H) return -1;
-    if (!fast && depth && !depth_format_known(depth_format)) return -1;   // (before anything is enqueued; mv_set_depth_obs lets no other format through)
-    if (!fast && seg && !seg_format_known(seg_format)) return -1;
+    const PlaneOuts po = !fast && planes ? *planes : PlaneOuts();
+    if (!plane_formats_known(po)) return -1;
+    void *const depth = po.depth, *const seg = po.seg;
+    const int depth_format = po.depth_format, seg_format = po.seg_format;
     const int frames = gv.num_envs * gv.num_agents;
     if (!setup_done) hipLaunchKernelGGL(gv.draw_mask ? frame_setup_kernel<true> : frame_setup_kernel<false>, dim3(frames), dim3(256), 0, stream, gv, W, H);
     if (!fast) hipLaunchKernelGGL(frame_order_kernel, dim3(1), dim3(1024), 0, stream, gv, frames, gv.lpt_order);   // (fast: no sort kernel)
@@ -3134,7 +3200,12 @@ int launch_raster(const GymView &gv, uint32_t *obs, int W, int H, hipStream_t st
     const size_t dyn = exact_dyn_lds(W, H);
     const int split = exact_split(W, H);
     const dim3 grid(frames * split), block(256);
-    if (seg) {   // (mv_set_seg_obs: one trace, colours + labels or colours + depth + labels)
+    if (po.normal) {   // (mv_set_normal_obs: one trace, colours + normals and whichever of depth and labels is attached)
+        const auto fn = by_layout(gv.obs_layout, [&](auto chw) {
+            return by_list(gv, [](auto maxvis, auto shapes) { return raster_normal_kernel<decltype(maxvis)::value, decltype(shapes)::value, true, decltype(chw)::value>; });
+        });
+        launch_done(fn, grid, block, dyn, stream, nullptr, gv, obs, po, W, H, split, (const int *)gv.lpt_order);
+    } else if (seg) {   // (mv_set_seg_obs: one trace, colours + labels or colours + depth + labels)
         const auto fn = by_layout(gv.obs_layout, [&](auto chw) {
             return depth ? by_list(gv, [](auto maxvis, auto shapes) { return raster_seg_kernel<decltype(maxvis)::value, decltype(shapes)::value, OUT_COLOURS | OUT_DEPTHS | OUT_LABEL, decltype(chw)::value>; })
                          : by_list(gv, [](auto maxvis, auto shapes) { return raster_seg_kernel<decltype(maxvis)::value, decltype(shapes)::value, OUT_COLOURS | OUT_LABEL, decltype(chw)::value>; });

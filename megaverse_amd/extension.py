@@ -122,6 +122,8 @@ SYMBOLS = [
     ("mv_debug_still_rule_host", C.c_int, [_P, _P, _P, _P, _I, _I, _P, _P]), ("mv_debug_still_carry_host", C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
     ("mv_set_depth_obs", C.c_int, [_P, _P, _I]), ("mv_get_depth_obs", C.c_int, [_P]), ("mv_get_depth_format", C.c_int, [_P]),
     ("mv_get_depth_observation", C.c_int, [_P, _I, _I, _P]), ("mv_debug_depth_pack_host", C.c_int, [_P, _P, _I, _I, _P]),
+    ("mv_set_normal_obs", C.c_int, [_P, _P, _I]), ("mv_get_normal_obs", C.c_int, [_P]), ("mv_get_normal_format", C.c_int, [_P]),
+    ("mv_get_normal_observation", C.c_int, [_P, _I, _I, _P]), ("mv_debug_normal_pack_host", C.c_int, [_P, _P, _I, _I, _P]),
     ("mv_set_seg_obs", C.c_int, [_P, _P, _I]), ("mv_get_seg_obs", C.c_int, [_P]), ("mv_get_seg_format", C.c_int, [_P]),
     ("mv_get_seg_observation", C.c_int, [_P, _I, _I, _P]), ("mv_seg_class_name", C.c_char_p, [_I]),
     ("mv_debug_seg_bounds_host", C.c_int, [_I, _I, _I, _I, _I, _I, _I, _I, _P]), ("mv_debug_seg_rule_host", C.c_int, [_I, _I, _P, _I, _I, _P]),
@@ -320,6 +322,56 @@ def check_depth_obs(buf, entries, num_frames, h, w, fmt, device):
     """the argument check of MegaverseGym.set_depth_obs for a tensor: contiguous torch.float32 / torch.float16 (as fmt says) of shape (entries, num_frames, h,
     w) on CUDA device `device`; entries None: any number of entries (the check made before the gym is asked for its ring count)"""
     return _check_obs_tensor(buf, entries, (int(num_frames), int(h), int(w)), OBS_STREAMS['depth'].dtypes(fmt), device, 'set_depth_obs')
+
+# include/megaverse_hip.h: the formats of a normal plane (mv_set_normal_obs), torch dtype name -> MV_NORMAL_*
+MV_NORMAL_F16, MV_NORMAL_SNORM8 = 0, 1
+NORMAL_FORMATS = {"float16": MV_NORMAL_F16, "int8": MV_NORMAL_SNORM8}
+
+
+def normal_format_of(dtype):
+    """a torch dtype, a numpy dtype or its name ('float16', 'int8', 'torch.int8', np.int8 ...) -> MV_NORMAL_F16 / MV_NORMAL_SNORM8 (ValueError otherwise)"""
+    name = getattr(dtype, "__name__", None) if isinstance(dtype, type) else None
+    name = (name or str(dtype)).replace("torch.", "").replace("half", "float16")
+    if name not in NORMAL_FORMATS:
+        raise ValueError(f"set_normal_obs: dtype must be float16 or int8, got {dtype!r}")
+    return NORMAL_FORMATS[name]
+
+
+def debug_normal_pack_host(xyz, hit, fmt):
+    """mv_debug_normal_pack_host: the pack rule of a normal plane on the CPU (no device): float32 xyz [n, 3], hit [n] (non-zero: the ray hit) -> numpy
+    float16 [n, 4] (MV_NORMAL_F16: x, y, z, 1) or int8 [n, 4] (MV_NORMAL_SNORM8: q(x), q(y), q(z), 127), four zeros where nothing was hit"""
+    lib = load_library()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    hit = np.ascontiguousarray(hit, np.uint8).ravel()
+    if xyz.shape[0] != hit.size:
+        raise ValueError("debug_normal_pack_host: xyz and hit differ in length")
+    out = np.empty((hit.size, 4), np.int8 if int(fmt) == MV_NORMAL_SNORM8 else np.float16)
+    if lib.mv_debug_normal_pack_host(xyz.ctypes.data, hit.ctypes.data, int(hit.size), int(fmt), out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
+
+def check_normal_obs(buf, entries, num_frames, h, w, fmt, device):
+    """the argument check of MegaverseGym.set_normal_obs for a tensor: contiguous torch.float16 / torch.int8 (as fmt says) of shape (entries, num_frames, h,
+    w, 4) on CUDA device `device`; entries None: any number of entries (the check made before the gym is asked for its ring count)"""
+    return _check_obs_tensor(buf, entries, (int(num_frames), int(h), int(w), 4), OBS_STREAMS['normal'].dtypes(fmt), device, 'set_normal_obs')
+
+
+def normals_to_float(planes):
+    """a normal plane of either format -- a torch tensor or numpy array [..., 4] of float16 (MV_NORMAL_F16) or int8 (MV_NORMAL_SNORM8) -> (xyz, valid): the
+    normals as float32 [..., 3] (halves widened exactly, bytes as b / 127) and a bool mask [...], True where the pixel shows a surface (w != 0)"""
+    name = str(planes.dtype).replace("torch.", "")
+    if name not in NORMAL_FORMATS or tuple(planes.shape)[-1:] != (4,):
+        raise ValueError(f"normals_to_float: a float16 or int8 array whose last extent is 4, got {planes.dtype} {tuple(planes.shape)}")
+    if isinstance(planes, np.ndarray):
+        f = planes.astype(np.float32)
+    else:
+        import torch
+        f = planes.to(torch.float32)
+    if name == "int8":
+        f = f / 127.0
+    return f[..., :3], planes[..., 3] != 0
+
 
 # include/megaverse_hip.h: MV_STATE_OBS_FLOATS and the columns of a state-observation row (mv_set_state_obs), name -> index
 MV_STATE_OBS_FLOATS = 16
@@ -880,7 +932,7 @@ def _check_obs_tensor(buf, entries, tail, dtypes, device, who):
     return buf
 
 
-# The five per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
+# The six per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
 # of the gym (a read-back's row is that shape without its first extent), format -> the torch dtype names a tensor may have (the first: what True allocates),
 # the arguments behind the null pointer of a detach, the numpy dtype a read-back hands out.  A new stream is one row here.
 _ObsStream = collections.namedtuple('_ObsStream', 'setter reader tail dtypes detach read')
@@ -895,6 +947,8 @@ OBS_STREAMS = {
                         lambda fmt: ('torch.float16',) if int(fmt) == MV_DEPTH_F16 else _FLOAT32, (MV_DEPTH_F32,), np.float32),
     'seg': _ObsStream('mv_set_seg_obs', 'mv_get_seg_observation', lambda g: (g.num_envs * g.num_agents_per_env, g.h, g.w),
                       lambda fmt: ('torch.int16', 'torch.uint16') if int(fmt) == MV_SEG_INSTANCE_U16 else ('torch.uint8',), (MV_SEG_CLASS_U8,), np.uint16),
+    'normal': _ObsStream('mv_set_normal_obs', 'mv_get_normal_observation', lambda g: (g.num_envs * g.num_agents_per_env, g.h, g.w, 4),
+                         lambda fmt: ('torch.int8',) if int(fmt) == MV_NORMAL_SNORM8 else ('torch.float16',), (MV_NORMAL_F16,), np.float32),
 }
 
 
@@ -1638,6 +1692,35 @@ class MegaverseGym:
     def get_seg_observation(self, env_idx, agent_idx):
         """-> numpy uint16 [H, W]: the label plane of one agent in the last tick's entry, a 'class' plane widened (waits for the gym's stream)"""
         return self._read_obs('seg', env_idx, agent_idx)
+
+    def set_normal_obs(self, buf=True, dtype=None):
+        """Normal observations (include/megaverse_hip.h: mv_set_normal_obs): every frame a later observation pass draws -- the passes set_depth_obs names --
+        leaves the per-pixel unit surface normal in the viewer's camera frame (x right, y up, z back; (x, y, z, 1) where there is a surface, four zeros
+        where the depth is 0; row 0 is the bottom row) in entry t % entries of a CUDA tensor [entries, num_envs * num_agents, H, W, 4] of float16 or int8
+        (signed normalised: b / 127; normals_to_float widens either), entries = the output ring's count, or 1 without a ring.  True allocates the tensor on
+        the gym's device and returns it, in dtype (torch.float16, the default, or torch.int8; their names are accepted too); a tensor is checked
+        (ValueError) and attached -- its own dtype decides the format; None detaches.  Nothing waits on the host.  Depth, labels and normals attach
+        independently: with any of them, a fast-mode tick costs ONE launch behind its passes.  Unlike the labels, the normals of a batched call's earlier
+        frames do not change when their env begins a new episode inside the call.
+        While attached, set_output_ring, set_render_resolution and set_still_frames(True) are refused."""
+        if buf is None:
+            return self._attach_obs('normal', None)
+        if dtype is None:
+            dtype = "float16"
+        return self._attach_obs('normal', buf, normal_format_of(dtype if buf is True else getattr(buf, 'dtype', dtype)))
+
+    def normal_obs_ring(self):
+        """-> the tensor set_normal_obs attached, [entries, num_envs * num_agents, H, W, 4] (entry t % entries: the planes of tick t's frames), or None"""
+        return self._obs.get('normal')
+
+    def normal_obs(self):
+        """-> the entry of the last tick, (num_envs * num_agents, H, W, 4): a view of the attached tensor, valid in the order of the gym's stream; None with
+        nothing attached.  A tick that drew no frame wrote nothing there.  With an output ring: the entry the last tick stepped through this object went to"""
+        return self._obs_last('normal')
+
+    def get_normal_observation(self, env_idx, agent_idx):
+        """-> numpy float32 [H, W, 4]: the normal plane of one agent in the last tick's entry, widened (waits for the gym's stream)"""
+        return self._read_obs('normal', env_idx, agent_idx)
 
     def get_state_observation(self, env_idx, agent_idx):
         """-> numpy float32 [16]: the last tick's row of one agent (waits for the gym's stream)"""

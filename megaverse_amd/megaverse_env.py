@@ -69,7 +69,7 @@ def check_sequence_actions(actions, num_agents):
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
                  img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1,
-                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False, overview=None):
+                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False, overview=None, normal_obs=False):
         if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
         # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
@@ -118,10 +118,14 @@ class MegaverseEnv:
         #   seg_obs (True: the class byte, "instance": class << 12 | instance): every drawn frame leaves its per-pixel labels (mv_set_seg_obs)
         if depth_obs is not False and depth_obs is not True and depth_obs not in ("float16", "float32"):
             raise ValueError(f"depth_obs must be False, True or 'float16', got {depth_obs!r}")
+        #   normal_obs (True: float16, "int8": signed normalised bytes): every drawn frame leaves its per-pixel camera-space surface normals (mv_set_normal_obs)
+        if normal_obs is not False and normal_obs is not True and normal_obs not in ("float16", "int8"):
+            raise ValueError(f"normal_obs must be False, True, 'float16' or 'int8', got {normal_obs!r}")
         if seg_obs is not False and seg_obs is not True and seg_obs not in ("class", "instance"):
             raise ValueError(f"seg_obs must be False, True, 'class' or 'instance', got {seg_obs!r}")
         wanted = (("state", state_obs, ()), ("scene", scene_obs, ()), ("entity", entity_obs, ()),
-                  ("depth", depth_obs, ("float32" if depth_obs is True else depth_obs,)), ("seg", seg_obs, ("class" if seg_obs is True else seg_obs,)))
+                  ("depth", depth_obs, ("float32" if depth_obs is True else depth_obs,)), ("seg", seg_obs, ("class" if seg_obs is True else seg_obs,)),
+                  ("normal", normal_obs, ("float16" if normal_obs is True else normal_obs,)))
         self._streams = {name: args for name, on, args in wanted if on}
         if "state" in self._streams:
             self._attach_stream("state")
@@ -185,17 +189,24 @@ class MegaverseEnv:
         state_obs()'s rules: ask again after every call.  A tick that drew no frame wrote nothing.  Needs MegaverseEnv(..., seg_obs=True | "instance")."""
         return self._stream_entry("seg", self.env.seg_obs_ring(), per_agent_planes=True)
 
+    def normal_obs(self):
+        """the last tick's normal planes: float16 (x, y, z, 1) or int8 (b / 127; megaverse_amd.normals_to_float widens either), (num_envs,
+        num_agents_per_env, H, W, 4) on the device -- unit surface normals in the viewer's camera frame, four zeros where a ray hits nothing, row 0 the
+        bottom row -- a view of the attached buffer, under state_obs()'s rules: ask again after every call.  A tick that drew no frame wrote nothing.
+        Needs MegaverseEnv(..., normal_obs=True | "int8")."""
+        return self._stream_entry("normal", self.env.normal_obs_ring(), per_agent_planes=True)
+
     def _attach_stream(self, name, on=True):
         """one wanted stream's tensor attached (a new one, of the output ring's depth) or detached"""
         getattr(self.env, f"set_{name}_obs")(*((True,) + self._streams[name] if on else (None,)))
 
     def _stream_entry(self, name, buf, per_agent_planes=False):
         """the accessors' shared body: the last tick's entry of stream `name`'s attached tensor `buf` -- step_sequence's last tick, else entry 0;
-        per_agent_planes: viewed as (num_envs, num_agents_per_env, H, W)"""
+        per_agent_planes: viewed as (num_envs, num_agents_per_env, H, W[, 4])"""
         if buf is None:
             raise RuntimeError(f"{name}_obs: create the env with {name}_obs=True")
         entry = buf[self._seq[0][0] - 1 if self._seq is not None else 0]
-        return entry.view(self.num_envs, self.num_agents_per_env, self.img_h, self.img_w) if per_agent_planes else entry
+        return entry.view(self.num_envs, self.num_agents_per_env, *entry.shape[1:]) if per_agent_planes else entry
 
     def _set_output_ring(self, count, *ptrs):
         """the env's own output rings change (step_device, step_sequence): every attached stream's buffer is one more ring of the same depth and the library
@@ -203,7 +214,7 @@ class MegaverseEnv:
         for name in self._streams:
             self._attach_stream(name, on=False)
         self.env.set_output_ring(count, *ptrs)
-        for name in sorted(self._streams, key=lambda name: name not in ("depth", "seg")):
+        for name in sorted(self._streams, key=lambda name: name not in ("depth", "seg", "normal")):
             self._attach_stream(name)
 
     @staticmethod

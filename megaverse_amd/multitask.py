@@ -190,6 +190,10 @@ class MultiTaskGym:
         """segmentation observations (MegaverseGym.set_seg_obs) are per gym: a group's union launches write none, and the library refuses"""
         raise _per_gym("set_seg_obs", "segmentation observations", "write")
 
+    def set_normal_obs(self, buf=True, dtype=None):
+        """normal observations (MegaverseGym.set_normal_obs) are per gym: a group's union launches write none, and the library refuses"""
+        raise _per_gym("set_normal_obs", "normal observations", "write")
+
     def set_state_obs(self, buf=True):
         """state observations (MegaverseGym.set_state_obs) are per gym: a group's union launches write none, and the library refuses"""
         raise _per_gym("set_state_obs", "state observations", "write")
