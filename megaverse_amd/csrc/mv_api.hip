@@ -12,32 +12,6 @@
 
 thread_local std::string mvapi::g_err;
 
-static const char *SHAPING_KEYS_TOWER[4] = {"teamSpirit", "towerPickedUpObject", "towerVisitedBuildingZoneWithObject",
-                                           "towerBuildingReward"};
-static const float SHAPING_DEFAULT_TOWER[4] = {0.1f, 0.1f, 0.1f, 1.0f};   // scenario_tower_building.hpp:44-52
-// scenario_obstacles.hpp:36-44, teamSpirit 0 from Scenario::init (scenario.hpp:94-103)
-static const char *SHAPING_KEYS_OBST[5] = {"teamSpirit", "obstaclesAgentAtExit", "obstaclesAllAgentsAtExit", "obstaclesExtraReward",
-                                          "obstaclesAgentCarriedObjectToExit"};
-static const float SHAPING_DEFAULT_OBST[5] = {0.0f, 1.0f, 5.0f, 0.5f, 0.0f};
-// scenario_collect.hpp:44-52
-// scenario_rearrange.hpp:96-102
-static const char *SHAPING_KEYS_REARRANGE[3] = {"teamSpirit", "rearrangeOneMoreObjectCorrectPosition", "rearrangeAllObjectsCorrectPosition"};
-static const float SHAPING_DEFAULT_REARRANGE[3] = {0.0f, 1.0f, 10.0f};
-// scenario_sokoban.hpp:40-47, teamSpirit 0
-static const char *SHAPING_KEYS_SOKOBAN[4] = {"teamSpirit", "sokobanBoxOnTarget", "sokobanBoxLeavesTarget", "sokobanAllBoxesOnTarget"};
-static const float SHAPING_DEFAULT_SOKOBAN[4] = {0.0f, 1.0f, -1.0f, 10.0f};
-// EmptyScenario::defaultRewardShaping() is {} (scenario_empty.hpp:28) + Scenario::init's teamSpirit
-static const char *SHAPING_KEYS_EMPTY[1] = {"teamSpirit"};
-// scenario_hex_memory.hpp:37-43, scenario_hex_explore.hpp:28-31 (+ teamSpirit 0)
-static const char *SHAPING_KEYS_HEX_MEMORY[3] = {"teamSpirit", "memoryCollectGood", "memoryCollectBad"};
-static const float SHAPING_DEFAULT_HEX_MEMORY[3] = {0.0f, 1.0f, -1.0f};
-static const char *SHAPING_KEYS_HEX_EXPLORE[2] = {"teamSpirit", "exploreSolved"};
-static const float SHAPING_DEFAULT_HEX_EXPLORE[2] = {0.0f, 5.0f};
-static const char *SHAPING_KEYS_COLLECT[5] = {"teamSpirit", "collectSingleGood", "collectSingleBad", "collectAll", "collectAbyss"};
-static const float SHAPING_DEFAULT_COLLECT[5] = {0.0f, 1.0f, -1.0f, 5.0f, -0.5f};
-// scenario_box_a_gone.hpp:92-98 (+ teamSpirit 0)
-static const char *SHAPING_KEYS_BOXAGONE[3] = {"teamSpirit", "boxagoneTouchedFloor", "boxagonePerStepReward"};
-static const float SHAPING_DEFAULT_BOXAGONE[3] = {0.0f, -0.1f, 0.01f};
 static const int ACTION_SPACE[6] = {3, 3, 3, 2, 2, 3};                          // env.cpp:33
 
 // ------------------------------------------------------------------------------------------------
@@ -285,33 +259,6 @@ int mv_action_space_sizes(int32_t *out6)
 
 }  // extern "C" (helper below has C++ linkage)
 
-// scenario name -> kernel family + generator parameters (scenarios/init.hpp:30-52)
-namespace mvapi {
-bool scenario_from_name(const std::string &scen, int &scenario, ObstacleConfig &oc)
-{
-    if (scen == "towerbuilding") scenario = SCN_TOWER;
-    else if (scen.rfind("obstacles", 0) == 0) {                                       // scenario_obstacles.hpp:94-268: mv_gen.h's table
-        const ObstaclePreset *preset = nullptr;
-        for (const ObstaclePreset &p : kObstaclePresets)
-            if (scen == p.name) preset = &p;
-        if (!preset) return false;
-        scenario = SCN_OBSTACLES;
-        const float carried = oc.carried_object_to_exit;
-        oc = config_of(*preset);
-        if (preset->carried_object_to_exit == 0.0f) oc.carried_object_to_exit = carried;
-    } else if (scen == "collect") scenario = SCN_COLLECT;                              // scenarios/init.hpp:45
-    else if (scen == "rearrange") scenario = SCN_REARRANGE;                            // scenarios/init.hpp:49
-    else if (scen == "sokoban") scenario = SCN_SOKOBAN;                                // scenarios/init.hpp:46
-    else if (scen == "empty") scenario = SCN_EMPTY;                                    // scenarios/init.hpp:34
-    else if (scen == "hexmemory") scenario = SCN_HEX_MEMORY;                           // scenarios/init.hpp:47
-    else if (scen == "hexexplore") scenario = SCN_HEX_EXPLORE;                         // scenarios/init.hpp:48
-    else if (scen == "boxagone") scenario = SCN_BOXAGONE;                              // scenarios/init.hpp:50
-    else if (scen == "football") scenario = SCN_FOOTBALL;                              // scenarios/init.hpp:51
-    else return false;
-    return true;
-}
-}  // namespace mvapi
-
 // cores this process may use: the affinity mask, capped by the cgroup's CPU quota (a container with 16 of the host's 192 cores sees all of them in the mask)
 static int usable_host_cores()
 {
@@ -364,10 +311,8 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     const std::string scen = lower(cfg->scenario);
     int scenario = SCN_TOWER;
     ObstacleConfig oc;
-    if (!scenario_from_name(scen, scenario, oc))
-        return fail("Unknown scenario " + scen
-                    + " (this build accelerates: TowerBuilding, ObstaclesEasy/Medium/Hard/Walls/Steps/Lava, Collect, Rearrange, Sokoban, HexMemory, "
-                         "HexExplore, BoxAGone, Football, Empty)");
+    if (!scenario_from_name(scen, scenario, oc)) return fail("Unknown scenario " + scen + " (this build accelerates: " + kAccelerated + ")");
+    const ScenarioRow &row = scenario_row(scenario);   // (mv_scenarios.h: what follows reads the family's facts from its row)
     std::vector<std::string> levelFiles;
     if (scenario == SCN_SOKOBAN) {   // SokobanScenario's constructor looks the level files up (scenario_sokoban.cpp:40-78); none is fatal there too
         levelFiles = find_boxoban_level_files();
@@ -392,17 +337,9 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     g->N = cfg->num_envs; g->A = cfg->num_agents_per_env;
     g->scenario = scenario;
     g->scenarioName = scen;
-    g->numShaping = scenario == SCN_TOWER || scenario == SCN_SOKOBAN ? 4 : scenario == SCN_REARRANGE || scenario == SCN_HEX_MEMORY || scenario == SCN_BOXAGONE ? 3
-                  : scenario == SCN_HEX_EXPLORE ? 2 : scenario == SCN_EMPTY || scenario == SCN_FOOTBALL ? 1 : 5;
-    g->shapingKeys = scenario == SCN_TOWER ? SHAPING_KEYS_TOWER : scenario == SCN_OBSTACLES ? SHAPING_KEYS_OBST
-                   : scenario == SCN_COLLECT ? SHAPING_KEYS_COLLECT : scenario == SCN_SOKOBAN ? SHAPING_KEYS_SOKOBAN
-                   : scenario == SCN_HEX_MEMORY ? SHAPING_KEYS_HEX_MEMORY : scenario == SCN_HEX_EXPLORE ? SHAPING_KEYS_HEX_EXPLORE
-                   : scenario == SCN_EMPTY || scenario == SCN_FOOTBALL ? SHAPING_KEYS_EMPTY : scenario == SCN_BOXAGONE ? SHAPING_KEYS_BOXAGONE : SHAPING_KEYS_REARRANGE;
-    // Resident episodes per env: two where an episode ends at its time limit only (TowerBuilding, Empty, Football); THREE where a goal can end it early (the exit pad,
-    // every diamond collected, the level solved, the arrangement matched, the maze's target found): the host's run-ahead is bounded in TICKS (refill_episodes),
-    // the status words are read back every 16th, and a lucky env can finish twice inside that window -- a third resident episode covers it where two starved
-    // (ADVICE r05).
-    g->spares = scenario == SCN_TOWER || scenario == SCN_EMPTY || scenario == SCN_FOOTBALL ? 2 : 3;
+    g->numShaping = row.num_shaping;
+    g->shapingKeys = row.shaping_keys;
+    g->spares = row.spares;
     g->envOffset = cfg->total_envs > 0 ? cfg->env_offset : 0;
     g->envStride = cfg->total_envs > 0 && cfg->env_stride > 1 ? cfg->env_stride : 1;
     g->gv.sample_on = 0; g->gv.sample_seed = g->gv.sample_step = 0;
@@ -412,34 +349,66 @@ int mv_create(const mv_config *cfg, mv_gym **out)
 
     GymView &gv = g->gv;
     gv.num_envs = g->N; gv.num_agents = g->A;
-    const bool obstacles = scenario == SCN_OBSTACLES || scenario == SCN_EMPTY, collect = scenario == SCN_COLLECT,
-            rearrange = scenario == SCN_REARRANGE, sokoban = scenario == SCN_SOKOBAN;
-    const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE, boxagone = scenario == SCN_BOXAGONE, football = scenario == SCN_FOOTBALL;
-    const bool hostEpisodes = obstacles || collect || rearrange || sokoban || hex || boxagone || football;
+    const bool hostEpisodes = row.generate != nullptr;
     gv.scenario = scenario;
-    gv.box_stride = collect ? COLLECT_MAX_BOXES : MAX_BOXES;
-    gv.reward_stride = collect ? COLLECT_MAX_REWARDS : MAX_REWARDS;
-    g->blobBytes = collect ? sizeof(CollectBlob) : obstacles ? sizeof(EpisodeBlob) : rearrange ? sizeof(RearrangeBlob)
-                                    : sokoban ? sizeof(SokobanBlob) : hex ? sizeof(HexBlob) : boxagone ? sizeof(BoxAGoneBlob) : football ? sizeof(FootballBlob) : sizeof(TowerBlob);
+    gv.box_stride = row.box_stride; gv.reward_stride = row.reward_stride;
+    g->blobBytes = row.record_bytes;
     // ONE arena for all simulator state: a step touches ~8 arrays per env, separate small allocations
     // cost a TLB miss each per wave (measured: 83 % of the physics kernel's time was spent waiting on
     // ~30 memory operations); one large allocation is backed by large pages.
     auto up = [](size_t v) { return (v + 4095) & ~size_t(4095); };
-    const size_t szHdr = up(N * sizeof(EnvHeader)), szBoxes = up(N * (size_t)gv.box_stride * sizeof(LayoutBox)),
-                 szObj = up(N * MAX_OBJECTS * sizeof(MovableObject)), szAg = up(NA * sizeof(AgentState)),
-                 szChunk = up(N * (size_t)CHUNK_BYTES), szAct = up(NA * sizeof(int32_t)), szRew = up(NA * sizeof(float)),
-                 szDone = up(N), szObjv = up(NA * sizeof(float)), szMd = up(NA * 6 * sizeof(int32_t)),
-                 szObs = up(NA * frame_bytes(g->w, g->h, MV_OBS_RGBA));   // (the larger layout: mv_set_obs_layout may come later)
-    const size_t szTerrain = obstacles ? up(N * MAX_TERRAIN * sizeof(TerrainBox)) : 0,
-                 szRewObj = hostEpisodes ? up(N * (size_t)gv.reward_stride * sizeof(MovableObject)) : 0,
-                 szHeight = collect ? up(N * (size_t)HM_BYTES) : 0, szItems = rearrange ? up(N * MAX_ITEMS * sizeof(ArrangementItem))
-                                         : 0, szCells = sokoban ? up(N * (size_t)(SOKO_DIM * SOKO_DIM)) : 0,
-                 szHexB = hex || boxagone || football ? up(N * (size_t)HEX_MAX_BOXES * sizeof(HexRec)) : 0,
-                 szHexO = hex || football ? up(N * (size_t)HEX_MAX_OBJS * sizeof(HexRec)) : 0,
-                 szBag = boxagone ? up(N * sizeof(BoxAGoneState)) : 0, szFb = football ? up(N * sizeof(FootballState)) : 0,
-                                   szBlobs = up(N * g->blobBytes * (size_t)g->spares), szCnt = up((N + 2) * sizeof(int32_t)),
-                                                szGen = hostEpisodes ? 0 : up(N * sizeof(TowerGen));
-    gv.vis_stride = hex ? 2048 : collect || boxagone ? 1024 : 256;   // (BoxAGone: <= 8 + 972 + 24 boxes, all in the world frame)
+    // The arena's regions ahead of the hand-over slots, in the order they lie in it.  state(): a per-env array of the episode state, for mv_fork_envs
+    // (mv_fork.h) -- EVERY per-env array that a tick or a frame setup reads or writes, whole strides -- of the families whose row names it (no name: of all).
+    // A new per-env array belongs here -- or, if it is part of what makes an env that env (its seed chain, its resident episodes, its place in the refill
+    // protocol: episode_status, blobs, tower_gen, and the header fields of fork::IDENTITY_DWORDS), on the identity list of DESIGN.md 3.8.  Not state:
+    // actions (a tick's input, cleared by it), rewards / done / true_objective (public outputs of the last stepped tick), the hand-over slots.
+    struct Region { void *field; size_t bytes, perEnv; bool has; };
+    auto state = [&](auto *&field, size_t perEnv, unsigned arr = 0) { return Region{&field, up(N * perEnv), perEnv, !arr || (row.arrays & arr) != 0}; };
+    auto other = [&](auto *&field, size_t bytes, bool has = true) { return Region{&field, up(bytes), 0, has}; };
+    const Region regions[] = {
+        other(gv.hdr, N * sizeof(EnvHeader)),
+        state(gv.boxes, (size_t)gv.box_stride * sizeof(LayoutBox)),
+        state(gv.objects, MAX_OBJECTS * sizeof(MovableObject)),
+        state(gv.agents, (size_t)g->A * sizeof(AgentState)),
+        other(gv.actions, NA * sizeof(int32_t)),
+        other(gv.rewards, NA * sizeof(float)),
+        other(gv.done, N),
+        other(gv.true_objective, NA * sizeof(float)),
+        other(g->dMultiDiscrete, NA * 6 * sizeof(int32_t)),
+        state(gv.chunk, CHUNK_BYTES, ARR_CHUNK),
+        other(g->ownedObs, NA * frame_bytes(g->w, g->h, MV_OBS_RGBA)),   // (the larger layout: mv_set_obs_layout may come later)
+        other(g->dStatus, (N + 2) * sizeof(int32_t)),
+        state(gv.terrain, MAX_TERRAIN * sizeof(TerrainBox), ARR_TERRAIN),
+        state(gv.rewards_obj, (size_t)gv.reward_stride * sizeof(MovableObject), ARR_REWARDS),
+        // the ring of resident next episodes: uploaded by the host's feeder, or (TowerBuilding) drawn on the device from its generators' state
+        other(g->dBlobs, N * g->blobBytes * (size_t)g->spares),
+        other(gv.tower_gen, N * sizeof(TowerGen), !hostEpisodes),
+        state(gv.heightmap, HM_BYTES, ARR_HEIGHTMAP),
+        state(gv.items, MAX_ITEMS * sizeof(ArrangementItem), ARR_ITEMS),
+        state(gv.soko_cells, SOKO_DIM * SOKO_DIM, ARR_SOKO_CELLS),
+        state(gv.hex_boxes, HEX_MAX_BOXES * sizeof(HexRec), ARR_HEX_BOXES),
+        state(gv.hex_objs, HEX_MAX_OBJS * sizeof(HexRec), ARR_HEX_OBJS),
+        state(gv.bag, sizeof(BoxAGoneState), ARR_BAG),
+        state(gv.fb, sizeof(FootballState), ARR_FB),
+    };
+    static_assert(sizeof regions / sizeof regions[0] - 10 + 2 <= fork::MAX_ARRAYS,
+                  "the table holds every per-env state array (the list but its ten other regions) and the episode log's two");
+    // base == null: the bytes the regions take; else they are carved from base -- every field set, the state arrays entered in the fork table
+    auto lay_regions = [&](uint8_t *base) {
+        size_t off = 0;
+        for (const Region &r : regions) {
+            if (!r.has) continue;
+            if (base) {
+                uint8_t *p = base + off;
+                std::memcpy(r.field, &p, sizeof p);
+                if (r.perEnv) fork::table_add(g->forkTable, p, r.perEnv);
+            }
+            off += r.bytes;
+        }
+        return off;
+    };
+    const size_t szRew = up(NA * sizeof(float)), szDone = up(N), szObjv = up(NA * sizeof(float));   // (a slot's staging copies)
+    gv.vis_stride = row.vis_stride;
     if (const char *e = getenv("MV_DEBUG_VIS_STRIDE")) gv.vis_stride = std::min(gv.vis_stride, std::max(8, atoi(e)));   // (tests: provoke ST_VISIBLE)
     gv.debug_redo = getenv("MV_DEBUG_FORCE_REDO") && atoi(getenv("MV_DEBUG_FORCE_REDO")) ? 1 : 0;   // (tests: mv_tick_tower.h's sequential redo)
     gv.spares = g->spares;
@@ -472,8 +441,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     // the observation's ray abscissae (GymView::ray_tab); MV_RAY_TABLE=0: the pass computes them per workgroup (A/B measurements, tests)
     const bool rayTabOn = !(getenv("MV_RAY_TABLE") && atoi(getenv("MV_RAY_TABLE")) == 0);
     const size_t szRay = rayTabOn ? up((size_t)(g->w + g->h) * sizeof(float)) : 0;
-    const size_t total = szSort + szHdr + szBoxes + szObj + szAg + szAct + szRew + szDone + szObjv + szMd + (hostEpisodes ? 0 : szChunk) + szObs + szTerrain +
-                         szRewObj + szHeight + szItems + szCells + szHexB + szHexO + szBag + szFb + szBlobs + szCnt + szGen + (size_t)g->slots * szParity + szHist + szRay;
+    const size_t total = lay_regions(nullptr) + szHist + szSort + szRay + (size_t)g->slots * szParity;
     {
         hipError_t e_ = hipMalloc((void **)&g->arena, total);
         if (e_ != hipSuccess) {
@@ -488,54 +456,11 @@ int mv_create(const mv_config *cfg, mv_gym **out)
         (void)hipMemset(g->arena, 0, total);
     }
     {
-        uint8_t *p = g->arena;
-        gv.hdr = (EnvHeader *)p; p += szHdr;
-        gv.boxes = (LayoutBox *)p; p += szBoxes;
-        gv.objects = (MovableObject *)p; p += szObj;
-        gv.agents = (AgentState *)p; p += szAg;
-        gv.actions = (int32_t *)p; p += szAct;
-        gv.rewards = (float *)p; p += szRew;
-        gv.done = p; p += szDone;
-        gv.true_objective = (float *)p; p += szObjv;
-        g->dMultiDiscrete = (int32_t *)p; p += szMd;
-        if (!hostEpisodes) { gv.chunk = p; p += szChunk; }
-        g->ownedObs = (uint32_t *)p; p += szObs;
-        g->dStatus = (int *)p; p += szCnt;
+        g->forkTable = fork::Table{};
+        uint8_t *p = g->arena + lay_regions(g->arena);
+        g->forkTable.hdr = gv.hdr;
         gv.episode_status = g->dStatus;
-        if (obstacles) { gv.terrain = (TerrainBox *)p; p += szTerrain; }
-        if (hostEpisodes) { gv.rewards_obj = (MovableObject *)p; p += szRewObj; }
-        g->dBlobs = p; p += szBlobs;   // the ring of resident next episodes: uploaded by the host's feeder, or (TowerBuilding) drawn on the device
         gv.blobs = g->dBlobs;
-        if (!hostEpisodes) { gv.tower_gen = (TowerGen *)p; p += szGen; }
-        if (collect) { gv.heightmap = (int8_t *)p; p += szHeight; }
-        if (rearrange) { gv.items = (ArrangementItem *)p; p += szItems; }
-        if (sokoban) { gv.soko_cells = p; p += szCells; }
-        if (hex) { gv.hex_boxes = (HexRec *)p; p += szHexB; gv.hex_objs = (HexRec *)p; p += szHexO; }
-        if (boxagone) { gv.hex_boxes = (HexRec *)p; p += szHexB; gv.bag = (BoxAGoneState *)p; p += szBag; }
-        if (football) { gv.hex_boxes = (HexRec *)p; p += szHexB; gv.hex_objs = (HexRec *)p; p += szHexO; gv.fb = (FootballState *)p; p += szFb; }
-        // The episode state of an env, for mv_fork_envs (mv_fork.h): EVERY per-env array carved above that a tick or a frame setup reads or writes, whole
-        // strides.  A new per-env array belongs here -- or, if it is part of what makes an env that env (its seed chain, its resident episodes, its place in
-        // the refill protocol: episode_status, blobs, tower_gen, and the header fields of fork::IDENTITY_DWORDS), on the identity list of DESIGN.md 3.8.  Not
-        // state: actions (a tick's input, cleared by it), rewards / done / true_objective (public outputs of the last stepped tick), the hand-over slots.
-        {
-            fork::Table &ft = g->forkTable;
-            ft = fork::Table{};
-            ft.hdr = gv.hdr;
-            fork::table_add(ft, gv.boxes, (size_t)gv.box_stride * sizeof(LayoutBox));
-            fork::table_add(ft, gv.objects, MAX_OBJECTS * sizeof(MovableObject));
-            fork::table_add(ft, gv.agents, (size_t)g->A * sizeof(AgentState));
-            fork::table_add(ft, gv.chunk, CHUNK_BYTES);
-            fork::table_add(ft, gv.terrain, MAX_TERRAIN * sizeof(TerrainBox));
-            fork::table_add(ft, gv.rewards_obj, (size_t)gv.reward_stride * sizeof(MovableObject));
-            fork::table_add(ft, gv.heightmap, HM_BYTES);
-            fork::table_add(ft, gv.items, MAX_ITEMS * sizeof(ArrangementItem));
-            fork::table_add(ft, gv.soko_cells, SOKO_DIM * SOKO_DIM);
-            fork::table_add(ft, gv.hex_boxes, HEX_MAX_BOXES * sizeof(HexRec));
-            fork::table_add(ft, gv.hex_objs, HEX_MAX_OBJS * sizeof(HexRec));
-            fork::table_add(ft, gv.bag, sizeof(BoxAGoneState));
-            fork::table_add(ft, gv.fb, sizeof(FootballState));
-            static_assert(13 + 2 <= fork::MAX_ARRAYS, "the table holds every per-env array and the episode log's two");
-        }
         gv.lpt_hist = (int32_t *)p; p += szHist;
         gv.sort_scratch = szSort ? p : nullptr; p += szSort;
         if (szRay) {
@@ -584,7 +509,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
 
     // headers: float params + unseeded envs take their seed from random_device (env.hpp:169)
     // scenario.hpp:225-232; Sokoban: scenario_sokoban.hpp:49-53; BoxAGone: scenario_box_a_gone.hpp:82-87
-    float episodeLen = sokoban ? 80.0f : boxagone ? 300.0f : 60.0f, lookLimit = boxagone ? 0.75f : 0.2f;
+    float episodeLen = row.episode_len, lookLimit = row.look_limit;
     for (int k = 0; k < cfg->num_params; ++k) {
         const char *key = cfg->param_keys[k];
         const float v = cfg->param_vals[k];
@@ -619,11 +544,10 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     {
         // An env needs a fresh resident episode at every reset.  Two are kept resident, and the consumed counts are read back
         // every 16th step -- unless episodes can time out within a few ticks (a small or negative episodeLengthSec: the Obstacles
-        // family never goes below 35 s per platform, the others take the parameter as is -- TowerBuilding adds 4 s per object), then after every step.
-        // BoxAGone ends as soon as every agent is on the floor: for a random or idle agent after 30-60 ticks, never under 20 (it lands on its spawn
-        // platform, leaves it or waits for it to vanish, falls at least 6.8 units -- 15 ticks from rest -- then doneWithTimer's 0.3 s): 1.3 s, whatever
-        // episodeLengthSec says.  With counts read back every 16th tick (and up to max(32, 4 k) ticks late) an env finished twice inside the refill window.
-        const float minLenSec = scenario == SCN_OBSTACLES ? std::max(episodeLen, 35.0f) : scenario == SCN_BOXAGONE ? std::min(episodeLen, 1.3f) : episodeLen;
+        // family never goes below 35 s per platform, BoxAGone never lasts longer than 1.3 s, the others take the parameter as is -- TowerBuilding adds 4 s
+        // per object: the rows' len_floor and len_cap), then after every step.  With counts read back every 16th tick (and up to max(32, 4 k) ticks late)
+        // an env finished twice inside the refill window.
+        const float minLenSec = std::min(std::max(episodeLen, row.len_floor), row.len_cap);
         g->statusPeriod = minLenSec * 15.0f >= 64.0f ? 16 : 1;
         if (const char *e = getenv("MV_STATUS_PERIOD")) g->statusPeriod = std::max(1, atoi(e));   // (tests: provoke starvation)
     }
@@ -661,13 +585,13 @@ int mv_create(const mv_config *cfg, mv_gym **out)
         // MV_COLLECT_DEVICE_GEN=1 / 0, otherwise where this process's share of the host is under three cores (eight ranks under a 16-CPU quota: two host
         // thread holds Collect at 15.9 M obs/s against 16.6 M) and the gym has 256 envs and more (r12n, two cores, host / device: a quarter of a
         // Mixed4 batch 18.0 / 19.8 M obs/s, an eighth of a Mixed batch 16.9 / 16.2: too few episodes to pay for the draw launches).  The staging slots are device memory then.
-        g->blobsOnDevice = collect && (getenv("MV_COLLECT_DEVICE_GEN") ? atoi(getenv("MV_COLLECT_DEVICE_GEN")) != 0
-                                                                        : cfg->num_simulation_threads <= 0 && !getenv("MV_FEEDER_THREADS") && share < 3 && N >= 256);
+        g->blobsOnDevice = row.draw == DRAW_COLLECT && (getenv("MV_COLLECT_DEVICE_GEN") ? atoi(getenv("MV_COLLECT_DEVICE_GEN")) != 0
+                                                                                         : cfg->num_simulation_threads <= 0 && !getenv("MV_FEEDER_THREADS") && share < 3 && N >= 256);
         // The Obstacles family and Empty (one record, EpisodeBlob): drawn on the device (mv_obstacles_draw.h: the same episodes, byte for byte) with
         // MV_OBSTACLES_DEVICE_GEN=1 and only then -- no rule of its own yet, Collect's was cut from measurements this generator does not have.
-        if (obstacles) g->blobsOnDevice = getenv("MV_OBSTACLES_DEVICE_GEN") && atoi(getenv("MV_OBSTACLES_DEVICE_GEN")) != 0;
+        if (row.draw == DRAW_OBSTACLES || row.draw == DRAW_EMPTY) g->blobsOnDevice = getenv("MV_OBSTACLES_DEVICE_GEN") && atoi(getenv("MV_OBSTACLES_DEVICE_GEN")) != 0;
         // (the obstacles* float parameters can ask for levels beyond the device generator's fixed arrays -- 40 platforms in a row, say: said here, not drawn)
-        if (g->blobsOnDevice && scenario == SCN_OBSTACLES && !odraw::config_fits(oc)) {
+        if (g->blobsOnDevice && row.draw == DRAW_OBSTACLES && !odraw::config_fits(oc)) {
             mv_destroy(g);
             return fail("mv_create: MV_OBSTACLES_DEVICE_GEN=1, but this gym's generator parameters are beyond what the device generator holds (at most "
                         + std::to_string((int)odraw::LARGEST_PLATFORMS) + " platforms, heights 1 to " + std::to_string((int)odraw::LARGEST_HEIGHT)
@@ -705,14 +629,7 @@ int mv_create(const mv_config *cfg, mv_gym **out)
     for (size_t i = 0; i < NA; ++i) {
         std::memset(&ha[i], 0, sizeof(AgentState));
         for (int k = 0; k < g->numShaping; ++k)
-            ha[i].shaping[k] = scenario == SCN_TOWER ? SHAPING_DEFAULT_TOWER[k] : scenario == SCN_COLLECT ? SHAPING_DEFAULT_COLLECT[k]
-                                                     : scenario == SCN_REARRANGE ? SHAPING_DEFAULT_REARRANGE[k]
-                                                     : scenario == SCN_SOKOBAN ? SHAPING_DEFAULT_SOKOBAN[k]
-                                                     : scenario == SCN_HEX_MEMORY ? SHAPING_DEFAULT_HEX_MEMORY[k]
-                                                     : scenario == SCN_HEX_EXPLORE ? SHAPING_DEFAULT_HEX_EXPLORE[k]
-                                                     : scenario == SCN_BOXAGONE ? SHAPING_DEFAULT_BOXAGONE[k]
-                                                     : scenario == SCN_EMPTY ? 0.0f
-                                                     : (k == 4 ? oc.carried_object_to_exit : SHAPING_DEFAULT_OBST[k]);
+            ha[i].shaping[k] = row.carried_default && k == row.num_shaping - 1 ? oc.carried_object_to_exit : row.shaping_defaults[k];
         ha[i].carrying = -1; ha[i].jump_speed = 10.0f; ha[i].m00 = 1.0f; ha[i].m22 = 1.0f;
     }
     {
@@ -1122,8 +1039,7 @@ static int upload_pass(mv_gym *g)
     }
     if (flush_run()) return -1;
     if (!devEnvs.empty()) {
-        if (g->scenario == SCN_COLLECT) launch_collect_blob_copy(devEnvs.data(), devSlots.data(), (int)devEnvs.size(), g->hBlobs, g->dBlobs, g->blobBytes, K, up);
-        else launch_episode_blob_copy(devEnvs.data(), devSlots.data(), (int)devEnvs.size(), g->hBlobs, g->dBlobs, g->blobBytes, K, up);
+        launch_blob_copy(scenario_row(g->scenario).draw, devEnvs.data(), devSlots.data(), (int)devEnvs.size(), g->hBlobs, g->dBlobs, g->blobBytes, K, up);
         HIP_TRY(hipGetLastError());
     }
     if (!batch.empty()) {

@@ -294,9 +294,8 @@ int mv_debug_generate_episode(const char *scenario_name, int32_t num_agents, int
         || scenario == SCN_FOOTBALL)
         return fail("mv_debug_generate_episode: the Obstacles family, Empty, Collect, Rearrange, HexMemory, HexExplore and BoxAGone (Sokoban: mv_debug_generate_sokoban, Football: mv_debug_generate_football)");
     if (num_agents < 1 || num_agents > MAX_AGENTS || n < 1) return fail("mv_debug_generate_episode: bad arguments");
-    const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE;
-    const size_t bytes = scenario == SCN_COLLECT ? sizeof(CollectBlob) : scenario == SCN_REARRANGE ? sizeof(RearrangeBlob)
-                         : hex ? sizeof(HexBlob) : scenario == SCN_BOXAGONE ? sizeof(BoxAGoneBlob) : sizeof(EpisodeBlob);
+    const ScenarioRow &row = scenario_row(scenario);
+    const size_t bytes = row.record_bytes;
     if (!out) return (int)bytes;
     if ((size_t)out_bytes < bytes) return fail("mv_debug_generate_episode: buffer too small");
     std::mt19937 rng;
@@ -304,13 +303,7 @@ int mv_debug_generate_episode(const char *scenario_name, int32_t num_agents, int
     std::vector<uint8_t> buf(bytes, 0);
     for (int i = 0; i < n; ++i) {
         std::memset(buf.data(), 0, bytes);
-        if (scenario == SCN_COLLECT) generate_collect_episode(rng, num_agents, base_episode_len, *reinterpret_cast<CollectBlob *>(buf.data()));
-        else if (scenario == SCN_HEX_MEMORY) generate_hex_memory_episode(rng, num_agents, base_episode_len, *reinterpret_cast<HexBlob *>(buf.data()));
-        else if (scenario == SCN_HEX_EXPLORE) generate_hex_explore_episode(rng, num_agents, base_episode_len, *reinterpret_cast<HexBlob *>(buf.data()));
-        else if (scenario == SCN_REARRANGE) generate_rearrange_episode(rng, num_agents, base_episode_len, *reinterpret_cast<RearrangeBlob *>(buf.data()));
-        else if (scenario == SCN_BOXAGONE) generate_boxagone_episode(rng, num_agents, base_episode_len, *reinterpret_cast<BoxAGoneBlob *>(buf.data()));
-        else if (scenario == SCN_EMPTY) generate_empty_episode(rng, num_agents, base_episode_len, *reinterpret_cast<EpisodeBlob *>(buf.data()));
-        else generate_obstacles_episode(rng, oc, num_agents, base_episode_len, *reinterpret_cast<EpisodeBlob *>(buf.data()));
+        generate_episode(row, GenContext{rng, oc, num_agents, base_episode_len, nullptr, nullptr}, 0, buf.data());   // (`seq` stays 0 here)
     }
     std::memcpy(out, buf.data(), bytes);
     return (int)bytes;
@@ -339,9 +332,8 @@ int mv_debug_feeder_selftest(const char *scenario_name, int32_t num_envs, int32_
     if (!scenario_name || !scenario_from_name(lower(scenario_name), scenario, oc) || scenario == SCN_TOWER || scenario == SCN_SOKOBAN || scenario == SCN_EMPTY
         || scenario == SCN_FOOTBALL)
         return fail("mv_debug_feeder_selftest: the Obstacles family, Collect, Rearrange, HexMemory and HexExplore");
-    const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE;
-    const size_t bytes = scenario == SCN_COLLECT ? sizeof(CollectBlob) : scenario == SCN_REARRANGE
-                                                          ? sizeof(RearrangeBlob) : hex ? sizeof(HexBlob) : sizeof(EpisodeBlob);
+    const ScenarioRow &row = scenario_row(scenario);
+    const size_t bytes = row.record_bytes;
     std::vector<uint8_t> slots((size_t)num_envs * bytes, 0), want(bytes);
     std::vector<uint32_t> seeds(num_envs);
     for (int i = 0; i < num_envs; ++i) seeds[i] = 1000u + 7u * (uint32_t)i;
@@ -356,50 +348,9 @@ int mv_debug_feeder_selftest(const char *scenario_name, int32_t num_envs, int32_
             const uint8_t *got = feeder.wait_ready(i, r, &used);
             if (!got) return fail("feeder selftest: episode not delivered");
             std::memset(want.data(), 0, bytes);
-            if (hex) {   // the box list comes last and only its used prefix is meaningful
-                HexBlob &b = *reinterpret_cast<HexBlob *>(want.data());
-                if (scenario == SCN_HEX_MEMORY) generate_hex_memory_episode(rng[i], num_agents, 60.0f, b);
-                else generate_hex_explore_episode(rng[i], num_agents, 60.0f, b);
-                b.seq = r;
-                const HexBlob &a = *reinterpret_cast<const HexBlob *>(got);
-                if (used != offsetof(HexBlob, boxes) + sizeof(HexRec) * (size_t)b.num_boxes || std::memcmp(&a, &b, offsetof(HexBlob, objs)) ||
-                    std::memcmp(a.objs, b.objs, sizeof(HexRec) * (size_t)b.num_objs) || std::memcmp(a.boxes, b.boxes, sizeof(HexRec) * (size_t)b.num_boxes))
-                    return fail("feeder selftest: Hex episode differs from sequential generation");
-                feeder.recycle(i, nullptr);
-                continue;
-            }
-            if (scenario == SCN_REARRANGE) {
-                RearrangeBlob &b = *reinterpret_cast<RearrangeBlob *>(want.data());
-                generate_rearrange_episode(rng[i], num_agents, 60.0f, b);
-                b.seq = r;
-                if (std::memcmp(got, &b, sizeof b)) return fail("feeder selftest: Rearrange episode differs from sequential generation");
-                feeder.recycle(i, nullptr);
-                continue;
-            }
-            if (scenario == SCN_COLLECT) {
-                CollectBlob &b = *reinterpret_cast<CollectBlob *>(want.data());
-                generate_collect_episode(rng[i], num_agents, 60.0f, b);
-                b.seq = r;
-            } else {
-                EpisodeBlob &b = *reinterpret_cast<EpisodeBlob *>(want.data());
-                generate_obstacles_episode(rng[i], oc, num_agents, 60.0f, b);
-                b.seq = r;
-            }
-            if (used > bytes) return fail("feeder selftest: used bytes out of range");
-            // compare the meaningful fields: counts first, then the used prefix of each array via the generators' own layout
-            if (scenario == SCN_COLLECT) {
-                const CollectBlob &a = *reinterpret_cast<const CollectBlob *>(got), &b = *reinterpret_cast<const CollectBlob *>(want.data());
-                if (a.seq != b.seq || a.num_boxes != b.num_boxes || a.num_objects != b.num_objects || a.num_rewards != b.num_rewards ||
-                    std::memcmp(a.boxes, b.boxes, sizeof(LayoutBox) * (size_t)b.num_boxes) || std::memcmp(a.heightmap, b.heightmap, HM_DIM * HM_DIM) ||
-                    std::memcmp(a.spawn, b.spawn, sizeof a.spawn) || std::memcmp(a.yaw_frand, b.yaw_frand, sizeof(float) * (size_t)num_agents))
-                    return fail("feeder selftest: Collect episode differs from sequential generation");
-            } else {
-                const EpisodeBlob &a = *reinterpret_cast<const EpisodeBlob *>(got), &b = *reinterpret_cast<const EpisodeBlob *>(want.data());
-                if (a.seq != b.seq || a.num_boxes != b.num_boxes || a.num_objects != b.num_objects || a.num_rewards != b.num_rewards ||
-                    std::memcmp(a.boxes, b.boxes, sizeof(LayoutBox) * (size_t)b.num_boxes) || std::memcmp(a.spawn, b.spawn, sizeof a.spawn) ||
-                    std::memcmp(a.yaw_frand, b.yaw_frand, sizeof(float) * (size_t)num_agents))
-                    return fail("feeder selftest: Obstacles episode differs from sequential generation");
-            }
+            generate_episode(row, GenContext{rng[i], oc, num_agents, 60.0f, nullptr, nullptr}, r, want.data());
+            if (!episodes_equal(row, got, want.data(), used, num_agents))
+                return fail(std::string("feeder selftest: ") + row.name + " episode differs from sequential generation");
             feeder.recycle(i, nullptr);
         }
     return 0;

@@ -1,5 +1,7 @@
 // megaverse_amd/csrc/mv_api_internal.h -- what the host side of libmegaverse_hip.so shares between its translation units:
 //   mv_api.hip        create / close, seeding, reset, actions, output rings, getters, reward shaping (MegaverseGym's methods but step)
+//   mv_scenarios.h / .cpp  the scenario families, one row each: names, reward shaping, episode record and generator, strides, defaults, state arrays (host-only,
+//                     needs nothing of this file: mv_feeder.cpp reads it too)
 //   mv_api_step.hip   stepping: pipelining, batched calls, overlapped passes, groups (union launches), in-stream profiling
 //   mv_api_debug.hip  test hooks: snapshots, pose setters, host-side generators, RNG / arithmetic probes
 //   mv_fork.hip       env forks: the gather-copy kernel and its entry points; the entry points of env resampling
@@ -40,6 +42,7 @@
 #include "mv_feeder.h"
 #include "mv_actions.h"
 #include "mv_gen.h"
+#include "mv_scenarios.h"
 #include "mv_raster.h"
 #include "mv_math.h"
 #include "mv_rng.h"
@@ -56,12 +59,10 @@ namespace mv {
 void launch_tower_draw(const GymView &gv, hipStream_t stream);
 void launch_tower_seed(const GymView &gv, const uint32_t *seeds, hipStream_t stream);   // Env::seed for every env's generator
 void launch_tower_seed_envs(const GymView &gv, const int32_t *seeds, hipStream_t stream);   // mv_seed_envs: ... for the envs whose seeds[env] >= 0
-// Collect, device-drawn episodes (mv_collect_draw.hip): staging slots of envs[i] -> their ring slots slots[i], one launch per 64 episodes
-void launch_collect_blob_copy(const int32_t *envs, const int32_t *slots, int count, const uint8_t *staging, uint8_t *ring, size_t blob_bytes, int spares,
-                              hipStream_t stream);
-// Obstacles family and Empty, device-drawn episodes (mv_obstacles_draw.hip): the same copy for records of any size, copied whole
-void launch_episode_blob_copy(const int32_t *envs, const int32_t *slots, int count, const uint8_t *staging, uint8_t *ring, size_t blob_bytes, int spares,
-                              hipStream_t stream);
+// Device-drawn episodes (mv_collect_draw.hip): staging slots of envs[i] -> their ring slots slots[i], one launch per 64 episodes, with the copy kernel of the
+// family's draw (mv_scenarios.h: DRAW_*) -- Collect's takes the record's used prefix, the other takes records of any size whole
+void launch_blob_copy(int draw, const int32_t *envs, const int32_t *slots, int count, const uint8_t *staging, uint8_t *ring, size_t blob_bytes, int spares,
+                      hipStream_t stream);
 // The step and reset kernels of gv's scenario (mv_step.hip).  One tick: one workgroup per env = the tick (wave 0) + the frame setup of the env's frames
 // for a W x H observation (render = 0: tick only); done: an event carried by the launch's dispatch packet (TowerBuilding only) -> whether it was.
 bool launch_step(const GymView &gv, hipStream_t stream, int W, int H, int render, hipEvent_t done = nullptr);
@@ -261,7 +262,7 @@ struct mv_gym {
     std::vector<int> uploaded, uploadBatch;         // episodes uploaded per env; envs of the current upload batch
     uint8_t *dBlobs = nullptr, *hBlobs = nullptr;   // device [N][blobBytes], pinned feeder slots [N][blobBytes]
     bool blobsOnDevice = false;                     // the feeder runs in device mode (Collect, the Obstacles family, Empty): hBlobs is device memory, filled by the scenario's draw kernel (mv_feeder.cpp)
-    size_t blobBytes = 0;                           // sizeof(EpisodeBlob) or sizeof(CollectBlob)
+    size_t blobBytes = 0;                           // the scenario's record size (mv_scenarios.h: record_bytes)
     bool hostEpisodes() const { return scenario != SCN_TOWER; }
     // TowerBuilding: the episode generator's serial half (tower_draw_kernel, ~47 us of one wavefront per finished env) runs on a stream of its own,
     // behind the step launch whose finished envs it refills and beside everything else; a stepping call waits for the draw launch BEFORE the last one
@@ -451,7 +452,6 @@ int tower_draw_after(mv_gym *g, hipEvent_t after, int ticks);
 int publish_outputs(mv_gym *g, int q, const OutPtrs &o);   // on the caller's stream
 // the staged outputs of the k ticks in slots q0 .. q0 + k - 1 -> outs[j * stride], one launch on the caller's stream (calls that draw no tick, or the last)
 int publish_ticks(mv_gym *g, int q0, const OutPtrs *outs, int stride, int k);
-bool scenario_from_name(const std::string &scen, int &scenario, ObstacleConfig &oc);
 int check_status_flags(mv_gym *g);
 int finish_with_warning(mv_gym *g);
 int refill_episodes(mv_gym *g, int k);   // k: the ticks of the stepping call that is about to be enqueued

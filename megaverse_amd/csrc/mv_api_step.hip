@@ -642,10 +642,9 @@ int mv_group_create(mv_gym *const *gyms, int32_t n, mv_group **out)
         for (const GymOption &o : gym_options)
             if (o.on(g)) return fail(std::string("mv_group_create: a gym has ") + o.has + " (" + o.setter + "): the union launches " + o.unionNone + "; " + o.detach);
         for (int j = 0; j < i; ++j) if (gyms[j] == g) return fail("mv_group_create: the same gym twice");
-        if (g->scenario == SCN_BOXAGONE)   // (its tick is not in the union kernels, mv_step_union.hip: tick_any)
-            return fail("mv_group_create: BoxAGone cannot be stepped in a group of gyms; step it as a gym of its own (MultiTaskGym: MV_MULTITASK_UNION=0)");
-        if (g->scenario == SCN_FOOTBALL)   // (nor is Football's)
-            return fail("mv_group_create: Football cannot be stepped in a group of gyms; step it as a gym of its own (MultiTaskGym: MV_MULTITASK_UNION=0)");
+        if (!scenario_row(g->scenario).in_union)   // (its tick is not in the union kernels, mv_step_union.hip: tick_any)
+            return fail(std::string("mv_group_create: ") + scenario_row(g->scenario).name
+                        + " cannot be stepped in a group of gyms; step it as a gym of its own (MultiTaskGym: MV_MULTITASK_UNION=0)");
         if (g->device != L->device || g->w != L->w || g->h != L->h || g->A != L->A || g->stream != L->stream || g->pipelined != L->pipelined)
             return fail("mv_group_create: the gyms of a group share device, observation size, agents per env, stream (mv_set_stream first) and pipelining");
         if (g->obsLayout != L->obsLayout) return fail("mv_group_create: the gyms of a group share their observation layout (mv_set_obs_layout)");

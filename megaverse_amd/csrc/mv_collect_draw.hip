@@ -183,14 +183,32 @@ __global__ __launch_bounds__(256) void collect_blob_copy_kernel(BlobCopyArgs a, 
 }
 static_assert(offsetof(CollectBlob, boxes) % 16 == 0 && sizeof(LayoutBox) % 16 == 0, "the record's used prefix is copied in 16-byte words");
 
-void launch_collect_blob_copy(const int32_t *envs, const int32_t *slots, int count, const uint8_t *staging, uint8_t *ring, size_t blob_bytes, int spares,
-                              hipStream_t stream)
+// Device-drawn episodes of any record size, staging slot -> ring slot (collect_blob_copy_kernel's sibling for records without a variable tail): one workgroup
+// per episode, the whole record in 16-byte words, the first of them -- `seq` and the counts -- last of all.
+__global__ __launch_bounds__(256) void episode_blob_copy_kernel(BlobCopyArgs a, const uint8_t *staging, uint8_t *ring, size_t blob_bytes, int spares)
 {
+    const int k = blockIdx.x;
+    if (k >= a.count) return;
+    const int env = a.env[k];
+    const uint4 *s4 = reinterpret_cast<const uint4 *>(staging + (size_t)env * blob_bytes);
+    uint4 *d4 = reinterpret_cast<uint4 *>(ring + ((size_t)env * spares + (size_t)a.slot[k]) * blob_bytes);
+    const int words = (int)(blob_bytes / 16);
+    for (int i = (int)threadIdx.x + 1; i < words; i += 256) d4[i] = s4[i];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    if (threadIdx.x == 0) d4[0] = s4[0];
+}
+static_assert(sizeof(EpisodeBlob) % 16 == 0 && alignof(EpisodeBlob) == 16 && offsetof(EpisodeBlob, seq) == 0, "the record is copied in 16-byte words, seq's word last");
+
+void launch_blob_copy(int draw, const int32_t *envs, const int32_t *slots, int count, const uint8_t *staging, uint8_t *ring, size_t blob_bytes, int spares,
+                      hipStream_t stream)
+{
+    const auto kernel = draw == DRAW_COLLECT ? collect_blob_copy_kernel : episode_blob_copy_kernel;
     for (int first = 0; first < count; first += 64) {
         BlobCopyArgs a;
         a.count = std::min(64, count - first);
         for (int i = 0; i < a.count; ++i) { a.env[i] = envs[first + i]; a.slot[i] = slots[first + i]; }
-        hipLaunchKernelGGL(collect_blob_copy_kernel, dim3(a.count), dim3(256), 0, stream, a, staging, ring, blob_bytes, spares);
+        hipLaunchKernelGGL(kernel, dim3(a.count), dim3(256), 0, stream, a, staging, ring, blob_bytes, spares);
     }
 }
 

@@ -6,6 +6,7 @@
 
 #include "mv_collect_draw.h"
 #include "mv_obstacles_draw.h"
+#include "mv_scenarios.h"
 
 namespace mv {
 
@@ -19,7 +20,8 @@ size_t obstacles_draw_region_bytes();
 // the scenarios a draw kernel exists for
 static bool has_draw_kernel(int scenario, const ObstacleConfig &cfg)
 {
-    return scenario == SCN_COLLECT || scenario == SCN_EMPTY || (scenario == SCN_OBSTACLES && odraw::config_fits(cfg));
+    const int draw = scenario_row(scenario).draw;
+    return draw == DRAW_COLLECT || draw == DRAW_EMPTY || (draw == DRAW_OBSTACLES && odraw::config_fits(cfg));
 }
 
 EpisodeFeeder::EpisodeFeeder(int scenario, const ObstacleConfig &cfg, int num_envs, int num_agents, float base_episode_len, uint8_t *slots,
@@ -35,7 +37,7 @@ EpisodeFeeder::EpisodeFeeder(int scenario, const ObstacleConfig &cfg, int num_en
         (void)hipSetDevice(device_);
         // the Obstacles family's grids (mv_obstacles_draw.h: two bit planes over the largest bounding box a level can have), one region per episode a launch
         // draws at a time
-        const int regions = scenario_ == SCN_OBSTACLES ? obstacles_draw_regions(scenario_, num_envs_) : 0;
+        const int regions = scenario_row(scenario_).draw == DRAW_OBSTACLES ? obstacles_draw_regions(scenario_, num_envs_) : 0;
         grid_bytes_ = size_t(regions) * obstacles_draw_region_bytes();
         grid_regions_ = regions;
         const bool ok = (regions == 0 || hipMalloc((void **)&d_grids_, grid_bytes_) == hipSuccess) && hipMalloc(&d_states_, size_t(num_envs) * sizeof(cdraw::GenState)) == hipSuccess &&
@@ -185,52 +187,22 @@ void EpisodeFeeder::recycle(int env, hipEvent_t copied)
 
 void EpisodeFeeder::generate(int env)
 {
-    uint8_t *slot = slots_ + size_t(env) * slot_bytes_;
     const int seq = next_seq_[env]++;
-    size_t used = slot_bytes_;
-    if (scenario_ == SCN_OBSTACLES || scenario_ == SCN_EMPTY) {
-        EpisodeBlob &b = *reinterpret_cast<EpisodeBlob *>(slot);
-        if (scenario_ == SCN_EMPTY) generate_empty_episode(rng_[env], num_agents_, base_len_, b);
-        else generate_obstacles_episode(rng_[env], cfg_, num_agents_, base_len_, b);
-        b.seq = seq;
-    } else if (scenario_ == SCN_REARRANGE) {
-        RearrangeBlob &b = *reinterpret_cast<RearrangeBlob *>(slot);
-        generate_rearrange_episode(rng_[env], num_agents_, base_len_, b);
-        b.seq = seq;
-    } else if (scenario_ == SCN_SOKOBAN) {
-        SokobanBlob &b = *reinterpret_cast<SokobanBlob *>(slot);
-        SokobanLevels &levels = soko_levels_[env];
-        SokoUndo undo;
-        undo.reloaded = levels.pending.empty();
-        if (!undo.reloaded) undo.level = levels.pending.back();
-        if (!generate_sokoban_episode(rng_[env], levels, soko_files_, num_agents_, base_len_, b)) {
-            failed_.store(true, std::memory_order_release);
-            return;
-        }
-        b.seq = seq;
+    SokobanLevels *levels = scenario_ == SCN_SOKOBAN ? &soko_levels_[env] : nullptr;   // (what this episode takes from the level list can be put back)
+    SokoUndo undo;
+    if (levels) {
+        undo.reloaded = levels->pending.empty();
+        if (!undo.reloaded) undo.level = levels->pending.back();
+    }
+    const size_t used = generate_episode(scenario_row(scenario_), GenContext{rng_[env], cfg_, num_agents_, base_len_, levels, &soko_files_}, seq,
+                                         slots_ + size_t(env) * slot_bytes_);
+    if (!used) {
+        failed_.store(true, std::memory_order_release);
+        return;
+    }
+    if (levels) {
         soko_undo_[env].push_back(std::move(undo));
         while (soko_undo_[env].size() > 8) soko_undo_[env].pop_front();   // never more than spares + 1 episodes ahead
-    } else if (scenario_ == SCN_HEX_MEMORY || scenario_ == SCN_HEX_EXPLORE) {
-        HexBlob &b = *reinterpret_cast<HexBlob *>(slot);
-        if (scenario_ == SCN_HEX_MEMORY) generate_hex_memory_episode(rng_[env], num_agents_, base_len_, b);
-        else generate_hex_explore_episode(rng_[env], num_agents_, base_len_, b);
-        b.seq = seq;
-        used = offsetof(HexBlob, boxes) + size_t(b.num_boxes) * sizeof(HexRec);   // the box list is last: used prefix only
-    } else if (scenario_ == SCN_BOXAGONE) {
-        BoxAGoneBlob &b = *reinterpret_cast<BoxAGoneBlob *>(slot);
-        generate_boxagone_episode(rng_[env], num_agents_, base_len_, b);
-        b.seq = seq;
-        used = offsetof(BoxAGoneBlob, platforms) + size_t(b.num_platforms) * sizeof(BagPlatform);   // the platform list is last: used prefix only
-    } else if (scenario_ == SCN_FOOTBALL) {
-        FootballBlob &b = *reinterpret_cast<FootballBlob *>(slot);
-        generate_football_episode(rng_[env], num_agents_, base_len_, b);
-        b.seq = seq;
-        used = sizeof(FootballBlob);
-    } else {
-        CollectBlob &b = *reinterpret_cast<CollectBlob *>(slot);
-        generate_collect_episode(rng_[env], num_agents_, base_len_, b);
-        b.seq = seq;
-        used = offsetof(CollectBlob, boxes) + size_t(b.num_boxes) * sizeof(LayoutBox);   // the slab list is last: used prefix only
     }
     if (const int f = generator_overflow_take()) overflow_.fetch_or(f, std::memory_order_relaxed);   // (raised on this worker thread)
     used_bytes_[env] = used;
@@ -268,7 +240,7 @@ void EpisodeFeeder::device_worker_main()
         const int count = (int)batch.size();
         ok = ok && hipMemcpyAsync(d_list_, h_list_, size_t(count) * sizeof(int32_t), hipMemcpyHostToDevice, gen_stream_) == hipSuccess;
         if (ok) {
-            if (scenario_ == SCN_COLLECT) launch_collect_draw(d_states_, d_list_, count, slots_, slot_bytes_, num_agents_, base_len_, gen_stream_, d_flags_);
+            if (scenario_row(scenario_).draw == DRAW_COLLECT) launch_collect_draw(d_states_, d_list_, count, slots_, slot_bytes_, num_agents_, base_len_, gen_stream_, d_flags_);
             else launch_obstacles_draw(d_states_, d_list_, count, slots_, slot_bytes_, scenario_, cfg_, num_agents_, base_len_, d_grids_, grid_regions_, gen_stream_, d_flags_);
             ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(h_flags_, d_flags_, sizeof(int32_t), hipMemcpyDeviceToHost, gen_stream_) == hipSuccess &&
                  hipStreamSynchronize(gen_stream_) == hipSuccess;

@@ -17,7 +17,7 @@ struct ObstacleConfig {
     float carried_object_to_exit = 0.0f;    // default of the obstaclesAgentCarriedObjectToExit shaping key
 };
 
-// The registered Obstacles scenarios (scenario_obstacles.hpp:94-268), lower-case names: the one table scenario_from_name (mv_api.hip) reads its values from, and
+// The registered Obstacles scenarios (scenario_obstacles.hpp:94-268), lower-case names: the one table scenario_from_name (mv_scenarios.cpp) reads its values from, and
 // the one the device generator's capacities are asserted against at compile time (mv_obstacles_draw.h).  platform_type 0: all four types.
 struct ObstaclePreset {
     const char *name;

@@ -264,7 +264,7 @@ int mv_debug_entity_obs_host(int32_t scenario, int32_t num_agents, const void *e
 {
     const char *who = "mv_debug_entity_obs_host";
     if (!env_header || !agent_states || !out) return fail(std::string(who) + ": null pointer (an EnvHeader, num_agents AgentStates and the output are required)");
-    if (scenario < SCN_TOWER || scenario > SCN_FOOTBALL) return fail(std::string(who) + ": unknown scenario");
+    if (scenario < 0 || scenario >= SCN_COUNT) return fail(std::string(who) + ": unknown scenario");
     if (num_agents < 1 || num_agents > (int)MAX_AGENTS) return fail(std::string(who) + ": 1 <= num_agents <= 8 required");
     const EntityLayout l = entity_layout(scenario, num_agents);
     EnvHeader h;   // (the caller's bytes need not be aligned)

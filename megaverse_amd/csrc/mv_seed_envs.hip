@@ -106,10 +106,8 @@ int mv_debug_feeder_reseed_script(const char *scenario_name, int32_t num_envs, i
     ObstacleConfig oc;
     if (!scenario_name || !scenario_from_name(lower(scenario_name), scenario, oc) || scenario == SCN_TOWER)
         return fail("mv_debug_feeder_reseed_script: a host-generated scenario");
-    const bool hex = scenario == SCN_HEX_MEMORY || scenario == SCN_HEX_EXPLORE;
-    const size_t bytes = scenario == SCN_COLLECT ? sizeof(CollectBlob) : scenario == SCN_REARRANGE ? sizeof(RearrangeBlob) : scenario == SCN_SOKOBAN
-                         ? sizeof(SokobanBlob) : hex ? sizeof(HexBlob) : scenario == SCN_BOXAGONE ? sizeof(BoxAGoneBlob) : scenario == SCN_FOOTBALL
-                         ? sizeof(FootballBlob) : sizeof(EpisodeBlob);
+    const ScenarioRow &row = scenario_row(scenario);
+    const size_t bytes = row.record_bytes;
     if (!script && !out) return (int)bytes;
     if (num_envs < 1 || num_agents < 1 || num_agents > MAX_AGENTS || !env_seeds || !script || n_ops < 0)
         return fail("mv_debug_feeder_reseed_script: bad arguments");
@@ -153,40 +151,10 @@ int mv_debug_feeder_reseed_script(const char *scenario_name, int32_t num_envs, i
         if (!got) return fail("mv_debug_feeder_reseed_script: episode not delivered");
         if (used > bytes) return fail("mv_debug_feeder_reseed_script: used bytes out of range");
         std::memset(want.data(), 0, bytes);
-        std::mt19937 &r = rng[(size_t)env];
-        bool same = false;
-        if (hex) {   // the box list comes last and only its used prefix is meaningful
-            HexBlob &b = *reinterpret_cast<HexBlob *>(want.data());
-            if (scenario == SCN_HEX_MEMORY) generate_hex_memory_episode(r, num_agents, len, b);
-            else generate_hex_explore_episode(r, num_agents, len, b);
-            b.seq = seq;
-            const HexBlob &a = *reinterpret_cast<const HexBlob *>(got);
-            same = used == offsetof(HexBlob, boxes) + sizeof(HexRec) * (size_t)b.num_boxes && !std::memcmp(&a, &b, offsetof(HexBlob, objs)) &&
-                   !std::memcmp(a.objs, b.objs, sizeof(HexRec) * (size_t)b.num_objs) && !std::memcmp(a.boxes, b.boxes, sizeof(HexRec) * (size_t)b.num_boxes);
-        } else if (scenario == SCN_COLLECT) {   // (its generator clears what it uses: the counts, then the used prefix of every list)
-            CollectBlob &b = *reinterpret_cast<CollectBlob *>(want.data());
-            generate_collect_episode(r, num_agents, len, b);
-            b.seq = seq;
-            const CollectBlob &a = *reinterpret_cast<const CollectBlob *>(got);
-            same = a.seq == b.seq && a.num_boxes == b.num_boxes && a.num_objects == b.num_objects && a.num_rewards == b.num_rewards &&
-                   a.num_positive == b.num_positive && a.layout_color == b.layout_color && a.wall_color == b.wall_color &&
-                   !std::memcmp(a.dim, b.dim, sizeof a.dim) && !std::memcmp(&a.episode_len, &b.episode_len, sizeof(float)) &&
-                   !std::memcmp(a.boxes, b.boxes, sizeof(LayoutBox) * (size_t)b.num_boxes) && !std::memcmp(a.heightmap, b.heightmap, sizeof a.heightmap) &&
-                   !std::memcmp(a.objects, b.objects, sizeof(MovableObject) * (size_t)b.num_objects) &&
-                   !std::memcmp(a.rewards, b.rewards, sizeof(MovableObject) * (size_t)b.num_rewards) &&
-                   !std::memcmp(a.spawn, b.spawn, sizeof a.spawn) && !std::memcmp(a.yaw_frand, b.yaw_frand, sizeof(float) * (size_t)num_agents);
-        } else {   // (these generators clear the whole record first: every byte compares)
-            if (scenario == SCN_REARRANGE) generate_rearrange_episode(r, num_agents, len, *reinterpret_cast<RearrangeBlob *>(want.data()));
-            else if (scenario == SCN_BOXAGONE) generate_boxagone_episode(r, num_agents, len, *reinterpret_cast<BoxAGoneBlob *>(want.data()));
-            else if (scenario == SCN_FOOTBALL) generate_football_episode(r, num_agents, len, *reinterpret_cast<FootballBlob *>(want.data()));
-            else if (scenario == SCN_EMPTY) generate_empty_episode(r, num_agents, len, *reinterpret_cast<EpisodeBlob *>(want.data()));
-            else if (scenario == SCN_SOKOBAN) {
-                if (!generate_sokoban_episode(r, levels[(size_t)env], files, num_agents, len, *reinterpret_cast<SokobanBlob *>(want.data())))
-                    return fail("mv_debug_feeder_reseed_script: unreadable level file");
-            } else generate_obstacles_episode(r, oc, num_agents, len, *reinterpret_cast<EpisodeBlob *>(want.data()));
-            *reinterpret_cast<int32_t *>(want.data()) = seq;
-            same = !std::memcmp(got, want.data(), bytes);
-        }
+        SokobanLevels *lv = levels.empty() ? nullptr : &levels[(size_t)env];
+        if (!generate_episode(row, GenContext{rng[(size_t)env], oc, num_agents, len, lv, &files}, seq, want.data()))
+            return fail("mv_debug_feeder_reseed_script: unreadable level file");
+        const bool same = episodes_equal(row, got, want.data(), used, num_agents);
         if (!same)
             return fail("mv_debug_feeder_reseed_script: episode " + std::to_string(seq) + " of env " + std::to_string(env) +
                         " differs from sequential generation (script entry " + std::to_string(k) + ")");

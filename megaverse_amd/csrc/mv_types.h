@@ -52,7 +52,8 @@ enum : int { SCN_TOWER = 0, SCN_OBSTACLES = 1, SCN_COLLECT = 2, SCN_REARRANGE = 
              SCN_EMPTY = 5,     // Empty runs on the Obstacles kernels (one slab, no terrain) with fall detection off
              SCN_HEX_MEMORY = 6, SCN_HEX_EXPLORE = 7,
              SCN_BOXAGONE = 8,     // its drawables are world-space HexRec records like the Hex scenarios' (mv_tick_boxagone.h)
-             SCN_FOOTBALL = 9 };   // the same: the room's boxes and the ball (mv_tick_football.h)
+             SCN_FOOTBALL = 9,     // the same: the room's boxes and the ball (mv_tick_football.h)
+             SCN_COUNT };          // (the host's row per family: mv_scenarios.h)
 enum : int { HEX_PILLAR = 0, HEX_DIAMOND = 1, HEX_SPHERE = 2 };                       // scenario_hex_memory.cpp:163-168 ShapeType
 enum : int { SOKO_DIM = 32, SOKO_WALL = 1, SOKO_GOAL = 2 };                            // Sokoban level cells (scenario_sokoban.cpp:28-33)
 enum : int { MAX_ITEMS = 8, NUM_STATIC = 9 };                                         // Rearrange: arrangement items, static colliding boxes

@@ -441,9 +441,14 @@ def debug_scene_obs_host(scenario, env_header, terrain=None, rewards=None, footb
 MV_ENTITY_OBS_FLOATS = 8
 ENTITY_OBS_FIELDS = {name: i for i, name in enumerate(("seg_word", "x", "y", "z", "half_x", "half_y", "half_z", "state"))}
 ENTITY_GROUPS = ("terrain", "objects", "rewards", "agents")   # mv_entity_obs_layout's order: the label rule's groups
-# mv_types.h: the SCN_* family of a scenario name, and the capacities the rows come from
-_SCN = {"towerbuilding": 0, "obstacleseasy": 1, "obstaclesmedium": 1, "obstacleshard": 1, "obstacleswalls": 1, "obstaclessteps": 1, "obstacleslava": 1,
-        "collect": 2, "rearrange": 3, "sokoban": 4, "empty": 5, "hexmemory": 6, "hexexplore": 7, "boxagone": 8, "football": 9}
+# What libmegaverse_hip.so can construct (mv_create; mv_scenarios.h has the library's row per family): every scenario of the reference's multi-task sets,
+# Empty, BoxAGone and Football -- display name -> SCN_* family id (mv_types.h).  megaverse_env.SUPPORTED_SCENARIOS is this table's names, in this order.
+SCENARIOS = {"TowerBuilding": 0, "ObstaclesEasy": 1, "ObstaclesMedium": 1, "ObstaclesHard": 1, "ObstaclesWalls": 1, "ObstaclesSteps": 1, "ObstaclesLava": 1,
+             "Collect": 2, "Sokoban": 4, "HexMemory": 6, "HexExplore": 7, "Rearrange": 3, "Empty": 5, "BoxAGone": 8, "Football": 9}
+_SCN = {name.casefold(): fam for name, fam in SCENARIOS.items()}
+# the reference's eight-scenario multi-task set (megaverse_env.py:17): defined here, once, for megaverse_env, multitask and rl
+MEGAVERSE8 = ["TowerBuilding", "ObstaclesEasy", "ObstaclesHard", "Collect", "Sokoban", "HexMemory", "HexExplore", "Rearrange"]
+# the capacities the entity rows come from (mv_types.h)
 _ENTITY_TERRAIN = {0: (1, "BUILDING_ZONE"), 1: (16, "EXIT"), 3: (8, "TARGET"), 4: (80, "EXIT")}      # family -> (rows, class of the first kind)
 _ENTITY_REWARDS = {1: (16, "COLLECTABLE"), 2: (96, "COLLECTABLE"), 6: (128, "COLLECTABLE"), 7: (128, "COLLECTABLE"), 9: (1, "BALL")}
 _ENTITY_OBJECTS = (0, 1, 2, 3, 4)                                                                      # the families with movable objects (80 rows)
@@ -451,7 +456,7 @@ _ENTITY_OBJECTS = (0, 1, 2, 3, 4)                                               
 
 def scenario_family(scenario):
     """a scenario name (any case) or an SCN_* family id -> the family id (ValueError: unknown)"""
-    if isinstance(scenario, (int, np.integer)) and not isinstance(scenario, (bool, np.bool_)) and 0 <= int(scenario) <= 9:
+    if isinstance(scenario, (int, np.integer)) and not isinstance(scenario, (bool, np.bool_)) and 0 <= int(scenario) <= max(SCENARIOS.values()):
         return int(scenario)
     fam = _SCN.get(str(scenario).casefold())
     if fam is None:

@@ -18,13 +18,12 @@ Differences, all additive:
 import numpy as np
 
 from . import spaces
-from .extension import ENTITY_OBS_FIELDS, MegaverseGym, SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS, STATE_OBS_FIELDS, render_mode_of, set_megaverse_log_level
+from .extension import ENTITY_OBS_FIELDS, MEGAVERSE8, MegaverseGym, SCENARIOS, SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS, STATE_OBS_FIELDS, render_mode_of, \
+    set_megaverse_log_level
 
-MEGAVERSE8 = ['TowerBuilding', 'ObstaclesEasy', 'ObstaclesHard', 'Collect', 'Sokoban', 'HexMemory', 'HexExplore', 'Rearrange']
 OBSTACLES_MULTITASK = ['ObstaclesWalls', 'ObstaclesSteps', 'ObstaclesLava', 'ObstaclesEasy', 'ObstaclesHard']
 # what libmegaverse_hip.so can construct (mv_create): every scenario of the reference's multi-task sets, Empty, BoxAGone and Football
-SUPPORTED_SCENARIOS = ['TowerBuilding', 'ObstaclesEasy', 'ObstaclesMedium', 'ObstaclesHard', 'ObstaclesWalls', 'ObstaclesSteps', 'ObstaclesLava',
-                       'Collect', 'Sokoban', 'HexMemory', 'HexExplore', 'Rearrange', 'Empty', 'BoxAGone', 'Football']
+SUPPORTED_SCENARIOS = list(SCENARIOS)
 _warned_unsupported = False
 
 

@@ -17,14 +17,13 @@ import os
 
 import numpy as np
 
-from .extension import EPISODE_RECORD_DTYPE, GymGroup, MegaverseGym, check_env_seeds
+from .extension import EPISODE_RECORD_DTYPE, MEGAVERSE8, GymGroup, MegaverseGym, check_env_seeds
 
 # MultiTaskGym.drain_episode_log: a sub-gym's record (extension.EPISODE_RECORD_DTYPE) + the task it came from; agent in the batch's numbering
 MULTITASK_EPISODE_DTYPE = np.dtype([("task", "<i4")] + [(n, EPISODE_RECORD_DTYPE.fields[n][0]) for n in EPISODE_RECORD_DTYPE.names])
 
 # megaverse_env.py:18-21 of the reference: the eight scenarios of its multi-task benchmark, all available on the HIP path
 # (Sokoban reads Boxoban level files: $BOXOBAN_LEVELS, as in the reference)
-MEGAVERSE8 = ["TowerBuilding", "ObstaclesEasy", "ObstaclesHard", "Collect", "Sokoban", "HexMemory", "HexExplore", "Rearrange"]
 MEGAVERSE_IN_SCOPE = MEGAVERSE8   # (older name)
 
 

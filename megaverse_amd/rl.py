@@ -10,7 +10,7 @@ wrote (a CUDA uint8 tensor view, zero copies), which is what a PyTorch-ROCm lear
 from types import SimpleNamespace
 from typing import Optional
 
-from .megaverse_env import MegaverseEnv, make_env_multitask
+from .megaverse_env import MEGAVERSE8, MegaverseEnv, make_env_multitask
 
 
 class MegaverseSpec:
@@ -18,9 +18,7 @@ class MegaverseSpec:
         self.name = name
 
 
-MEGAVERSE_ENVS = [MegaverseSpec(n) for n in (
-    "TowerBuilding", "ObstaclesEasy", "ObstaclesHard", "Collect", "Sokoban", "HexMemory", "HexExplore", "Rearrange",
-    "multitask_Obstacles", "multitask_megaverse8")]
+MEGAVERSE_ENVS = [MegaverseSpec(n) for n in (*MEGAVERSE8, "multitask_Obstacles", "multitask_megaverse8")]
 
 # megaverse_params.py:23-54 defaults
 DEFAULT_CFG = SimpleNamespace(megaverse_num_envs_per_instance=1, megaverse_num_agents_per_env=4, megaverse_num_simulation_threads=1,
