@@ -90,17 +90,12 @@ def test_default_reward_shaping_and_episode_length_param():
     g.close()
 
 
-def test_boxes_move_one_cell_at_a_time_never_into_walls_or_each_other_and_rewards_follow_the_goals():
-    n, A = 8, 1
-    g = oracle_lib.OracleGym("Sokoban", 16, 16, n, A, 4)
-    g.seed(4); g.reset()
+def follow_boxes(g, n, ticks):
+    """one agent per env: after every tick of `ticks` (an iterable that steps g) the boxes of every env against the tick before -- one box at most moved, by
+    one cell, never into a wall or another box, and the reward follows the goals -> (moves, solving pushes: the ticks that paid 11.0)"""
     prev = [g.snapshot(e) for e in range(n)]
-    moved = 0
-    for st in range(1250):
-        m = action_masks(sample_actions(6, st, n * A))
-        for e in range(n):
-            g.set_action_mask(e, 0, int(m[e]))
-        g.step_norender()
+    moved = elevens = 0
+    for _ in ticks:
         rew = g.get_last_rewards()
         for e in range(n):
             s = g.snapshot(e)
@@ -124,13 +119,44 @@ def test_boxes_move_one_cell_at_a_time_never_into_walls_or_each_other_and_reward
                 delta = int(y == 1 and grid[x, z] == 2) - int(by == 1 and grid[bx, bz] == 2)
             on_goal = sum(1 for (x, y, z) in cells if y == 1 and grid[x, z] == 2)
             if delta == 1:
-                assert rew[e] == (11.0 if on_goal == no and prev[e]["solved"] == 0 and int(s["highest_tower"]) == no else 1.0)
+                solving = on_goal == no and prev[e]["solved"] == 0 and int(s["highest_tower"]) == no
+                assert rew[e] == (11.0 if solving else 1.0)
+                elevens += solving
             elif delta == -1:
                 assert rew[e] == -1.0
             else:
                 assert rew[e] == 0.0
             prev[e] = s
+    return moved, elevens
+
+
+def test_boxes_move_one_cell_at_a_time_never_into_walls_or_each_other_and_rewards_follow_the_goals():
+    n, A = 8, 1
+    g = oracle_lib.OracleGym("Sokoban", 16, 16, n, A, 4)
+    g.seed(4); g.reset()
+
+    def ticks():
+        for st in range(1250):
+            m = action_masks(sample_actions(6, st, n * A))
+            for e in range(n):
+                g.set_action_mask(e, 0, int(m[e]))
+            g.step_norender()
+            yield st
+    moved, _ = follow_boxes(g, n, ticks())
     assert moved > 10
+    g.close()
+
+
+def test_the_solving_push_pays_eleven_on_the_solvable_levels(monkeypatch):
+    """the same properties on the hand-written levels of tests/golden/boxoban_solvable under the pusher's script (tests/sokoban_cases.py): the 11.0 branch
+    above is reached"""
+    import sokoban_cases as SC
+    import tower_cases as TC
+    monkeypatch.setenv("BOXOBAN_LEVELS", SC.LEVEL_DIR)
+    case = SC.CASES["pusher_a1"]
+    g = case.make(oracle_lib.OracleGym)
+    moved, elevens = follow_boxes(g, case.N, (1 for what, _ in TC.play(case, g) if what == "tick"))
+    assert moved >= 100 and elevens >= 1, (moved, elevens)
     g.close()
 
 

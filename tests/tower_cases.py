@@ -67,13 +67,15 @@ def dones_of(g, N):
 
 
 class Case:
+    scenario = "TowerBuilding"   # (tests/rearrange_cases.py and tests/sokoban_cases.py state theirs)
+
     def __init__(self, name, N, A, build, params=None, seed=42, scripted=True, replay=0):
         """replay = k > 0: the GPU tests also replay the case through an action ring, one call per segment; its segments are padded to k ticks with idle ones"""
         self.name, self.N, self.A, self.build, self.params, self.seed = name, N, A, build, dict(params or {}), seed
         self.scripted, self.replay = scripted, replay
 
     def make(self, cls, **kw):
-        g = cls("TowerBuilding", W, H, self.N, self.A, 1, False, self.params, **kw)
+        g = cls(self.scenario, W, H, self.N, self.A, 1, False, self.params, **kw)
         g.seed(self.seed)
         g.reset()
         return g
