@@ -651,7 +651,8 @@ int64_t mv_arena_bytes(const mv_gym *g);
 int mv_host_generator_threads(const mv_gym *g);
 /* Are this gym's episodes drawn on the device?  1: TowerBuilding, and every gym whose feeder runs in device mode -- Collect as above; the Obstacles family
  * (ObstaclesEasy / Medium / Hard / Walls / Steps / Lava) and Empty with MV_OBSTACLES_DEVICE_GEN=1 in the environment at mv_create (obstacles_draw_kernel,
- * megaverse_amd/csrc/mv_obstacles_draw.h: the host generator's episodes, byte for byte; unset or 0: host-fed, no automatic choice).  0: host-fed.  -1: no gym.
+ * megaverse_amd/csrc/mv_obstacles_draw.h: the host generator's episodes, byte for byte; unset or 0: host-fed, no automatic choice); HexMemory
+ * and HexExplore with MV_HEX_DEVICE_GEN=1 in the same way (hex_draw_kernel, megaverse_amd/csrc/mv_hex_draw.h).  0: host-fed.  -1: no gym.
  * mv_host_generator_threads is 0 exactly where this is 1.  The device form of mv_seed_envs stays refused on a device-fed gym as on a host-fed one.
  * Under the switch mv_create refuses an Obstacles gym whose obstacles* float parameters exceed the device generator's fixed arrays (7 platforms, heights 1..4). */
 int mv_device_generator(const mv_gym *g);
@@ -897,6 +898,13 @@ int mv_debug_obstacles_draw_host(const char *scenario, int32_t num_agents, int32
 int mv_debug_obstacles_draw_stats_host(const char *scenario, int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, int32_t *out8);
 int mv_debug_obstacles_draw_device(int32_t device, const char *scenario, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n,
                                    float base_episode_len, void *out, int64_t out_bytes, float *ms_per_launch);
+/* HexMemory's and HexExplore's generator as it runs on the DEVICE (megaverse_amd/csrc/mv_hex_draw.h; the feeder uses it where mv_device_generator says 1
+ * for such a gym), with the semantics of the Obstacles hooks.  `scenario`: "HexMemory" or "HexExplore".  _host: the same code compiled for the CPU (the
+ * lay-out, the prefix sum and the geometry in their serial form), the record mv_debug_generate_episode(scenario, ...) returns (seq = n; the boxes beyond
+ * num_boxes are zero here); out == NULL: the record's size.  _device: `count` envs draw their first n episodes on the GPU (hex_draw_kernel). */
+int mv_debug_hex_draw_host(const char *scenario, int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes);
+int mv_debug_hex_draw_device(int32_t device, const char *scenario, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n,
+                             float base_episode_len, void *out, int64_t out_bytes, float *ms_per_launch);
 /* Host-only (no device): the episode log's per-tick body (megaverse_amd/csrc/mv_episode_log.h, the source the kernel runs) over k ticks of N envs x A
  * agents: rewards [k][N*A], dones [k][N], true_objectives [k][N*A]; first_tick: the first tick's end_tick.  In and out: ret [N*A], len [N], *count, *dropped,
  * and records, a buffer of `capacity` mv_episode_record of which *count are valid on entry. */

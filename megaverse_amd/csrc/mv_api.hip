@@ -590,6 +590,8 @@ int mv_create(const mv_config *cfg, mv_gym **out)
         // The Obstacles family and Empty (one record, EpisodeBlob): drawn on the device (mv_obstacles_draw.h: the same episodes, byte for byte) with
         // MV_OBSTACLES_DEVICE_GEN=1 and only then -- no rule of its own yet, Collect's was cut from measurements this generator does not have.
         if (row.draw == DRAW_OBSTACLES || row.draw == DRAW_EMPTY) g->blobsOnDevice = getenv("MV_OBSTACLES_DEVICE_GEN") && atoi(getenv("MV_OBSTACLES_DEVICE_GEN")) != 0;
+        // HexMemory and HexExplore (HexBlob): drawn on the device (mv_hex_draw.h: the same episodes, byte for byte) with MV_HEX_DEVICE_GEN=1 and only then.
+        if (row.draw == DRAW_HEX) g->blobsOnDevice = getenv("MV_HEX_DEVICE_GEN") && atoi(getenv("MV_HEX_DEVICE_GEN")) != 0;
         // (the obstacles* float parameters can ask for levels beyond the device generator's fixed arrays -- 40 platforms in a row, say: said here, not drawn)
         if (g->blobsOnDevice && row.draw == DRAW_OBSTACLES && !odraw::config_fits(oc)) {
             mv_destroy(g);

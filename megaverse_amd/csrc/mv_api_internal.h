@@ -261,7 +261,7 @@ struct mv_gym {
     std::vector<int> consumedSeen;                  // the consumed counts of the last status read-back that was looked at (host copy)
     std::vector<int> uploaded, uploadBatch;         // episodes uploaded per env; envs of the current upload batch
     uint8_t *dBlobs = nullptr, *hBlobs = nullptr;   // device [N][blobBytes], pinned feeder slots [N][blobBytes]
-    bool blobsOnDevice = false;                     // the feeder runs in device mode (Collect, the Obstacles family, Empty): hBlobs is device memory, filled by the scenario's draw kernel (mv_feeder.cpp)
+    bool blobsOnDevice = false;                     // the feeder runs in device mode (Collect, the Obstacles family, Empty, HexMemory, HexExplore): hBlobs is device memory, filled by the scenario's draw kernel (mv_feeder.cpp)
     size_t blobBytes = 0;                           // the scenario's record size (mv_scenarios.h: record_bytes)
     bool hostEpisodes() const { return scenario != SCN_TOWER; }
     // TowerBuilding: the episode generator's serial half (tower_draw_kernel, ~47 us of one wavefront per finished env) runs on a stream of its own,

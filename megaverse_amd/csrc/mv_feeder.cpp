@@ -16,12 +16,14 @@ void launch_obstacles_draw(void *states, const int32_t *envs, int count, uint8_t
                            float base_episode_len, uint32_t *grids, int regions, hipStream_t stream, int32_t *flag_word);   // mv_obstacles_draw.hip
 int obstacles_draw_regions(int scenario, int num_envs);   // grid regions a feeder of num_envs envs holds (Empty: none), and one region's size
 size_t obstacles_draw_region_bytes();
+bool launch_hex_draw(void *states, const int32_t *envs, int count, uint8_t *slots, size_t slot_bytes, int scenario, int num_agents, float base_episode_len,
+                     hipStream_t stream, int32_t *flag_word);   // mv_hex_draw.hip; false: arguments it cannot take, nothing launched
 
 // the scenarios a draw kernel exists for
 static bool has_draw_kernel(int scenario, const ObstacleConfig &cfg)
 {
     const int draw = scenario_row(scenario).draw;
-    return draw == DRAW_COLLECT || draw == DRAW_EMPTY || (draw == DRAW_OBSTACLES && odraw::config_fits(cfg));
+    return draw == DRAW_COLLECT || draw == DRAW_EMPTY || draw == DRAW_HEX || (draw == DRAW_OBSTACLES && odraw::config_fits(cfg));
 }
 
 EpisodeFeeder::EpisodeFeeder(int scenario, const ObstacleConfig &cfg, int num_envs, int num_agents, float base_episode_len, uint8_t *slots,
@@ -209,7 +211,7 @@ void EpisodeFeeder::generate(int env)
     ready_seq_[env].store(seq, std::memory_order_release);
 }
 
-// Device mode's only worker: every env whose slot is free, in ONE launch of the scenario's draw kernel (collect_draw_kernel, obstacles_draw_kernel) on this
+// Device mode's only worker: every env whose slot is free, in ONE launch of the scenario's draw kernel (collect_draw_kernel, obstacles_draw_kernel, hex_draw_kernel) on this
 // feeder's stream -- while it runs (a Collect episode is 0.7 ms of one wavefront on average, 2.5 ms the slowest) the next batch gathers.  The launch is ordered behind the uploads that still read the batch's slots.
 void EpisodeFeeder::device_worker_main()
 {
@@ -240,9 +242,11 @@ void EpisodeFeeder::device_worker_main()
         const int count = (int)batch.size();
         ok = ok && hipMemcpyAsync(d_list_, h_list_, size_t(count) * sizeof(int32_t), hipMemcpyHostToDevice, gen_stream_) == hipSuccess;
         if (ok) {
-            if (scenario_row(scenario_).draw == DRAW_COLLECT) launch_collect_draw(d_states_, d_list_, count, slots_, slot_bytes_, num_agents_, base_len_, gen_stream_, d_flags_);
+            const int draw = scenario_row(scenario_).draw;
+            if (draw == DRAW_COLLECT) launch_collect_draw(d_states_, d_list_, count, slots_, slot_bytes_, num_agents_, base_len_, gen_stream_, d_flags_);
+            else if (draw == DRAW_HEX) ok = launch_hex_draw(d_states_, d_list_, count, slots_, slot_bytes_, scenario_, num_agents_, base_len_, gen_stream_, d_flags_);
             else launch_obstacles_draw(d_states_, d_list_, count, slots_, slot_bytes_, scenario_, cfg_, num_agents_, base_len_, d_grids_, grid_regions_, gen_stream_, d_flags_);
-            ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(h_flags_, d_flags_, sizeof(int32_t), hipMemcpyDeviceToHost, gen_stream_) == hipSuccess &&
+            ok = ok && hipGetLastError() == hipSuccess &&hipMemcpyAsync(h_flags_, d_flags_, sizeof(int32_t), hipMemcpyDeviceToHost, gen_stream_) == hipSuccess &&
                  hipStreamSynchronize(gen_stream_) == hipSuccess;
         }
         if (ok && *h_flags_) {

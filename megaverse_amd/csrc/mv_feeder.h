@@ -27,8 +27,8 @@ class EpisodeFeeder {
 public:
     // slots: pinned host memory, num_envs * slot_bytes, owned by the caller
     // level_files: Sokoban only (the Boxoban level files found at construction, scenario_sokoban.cpp:40-78)
-    // device_gen (Collect, the Obstacles family, Empty; ignored for the others): `slots` is DEVICE memory and the episodes are drawn there by the scenario's
-    // draw kernel (mv_collect_draw.h: collect_draw_kernel; mv_obstacles_draw.h: obstacles_draw_kernel, which takes `cfg` by value) -- one worker thread
+    // device_gen (Collect, the Obstacles family, Empty, HexMemory, HexExplore; ignored for the others): `slots` is DEVICE memory and the episodes are drawn there by the scenario's
+    // draw kernel (mv_collect_draw.h: collect_draw_kernel; mv_obstacles_draw.h: obstacles_draw_kernel, which takes `cfg` by value; mv_hex_draw.h: hex_draw_kernel) -- one worker thread
     // gathers the envs whose slots are free into a batch, launches the kernel for them on a stream of its own and waits for it; everything else --
     // is_ready / wait_ready / recycle / reseed, the refill protocol around them -- is what it is for the host generators.
     EpisodeFeeder(int scenario, const ObstacleConfig &cfg, int num_envs, int num_agents, float base_episode_len, uint8_t *slots,

@@ -33,6 +33,7 @@ enum : int {
     DRAW_COLLECT,     // collect_draw_kernel (mv_collect_draw.h); its copy to the ring takes the record's used prefix
     DRAW_OBSTACLES,   // obstacles_draw_kernel over its grid regions (mv_obstacles_draw.h), for the configurations odraw::config_fits holds
     DRAW_EMPTY,       // the same kernel's one-slab form: no grids, whatever the configuration
+    DRAW_HEX,         // hex_draw_kernel (mv_hex_draw.h): HexMemory and HexExplore, no grids; the whole record travels
 };
 
 // the per-env state arrays of GymView a family has besides boxes, objects and agents, which every family has (mv_api.hip: the arena's one list)
@@ -135,10 +136,10 @@ constexpr ScenarioRow kScenarios[] = {
     // scenario_hex_memory.hpp:37-43, scenario_hex_explore.hpp:28-31 (+ teamSpirit 0); scenarios/init.hpp:47-48
     {SCN_HEX_MEMORY, "HexMemory", "hexmemory", false, 3, {"teamSpirit", "memoryCollectGood", "memoryCollectBad"}, {0.0f, 1.0f, -1.0f}, false,
      3, sizeof(HexBlob), used_hex, same_hex, generate_as<HexBlob, generate_hex_memory_episode>,
-     MAX_BOXES, MAX_REWARDS, 2048, 60.0f, 0.2f, -LEN_ANY, LEN_ANY, true, DRAW_NONE, ARR_HEX},
+     MAX_BOXES, MAX_REWARDS, 2048, 60.0f, 0.2f, -LEN_ANY, LEN_ANY, true, DRAW_HEX, ARR_HEX},
     {SCN_HEX_EXPLORE, "HexExplore", "hexexplore", false, 2, {"teamSpirit", "exploreSolved"}, {0.0f, 5.0f}, false,
      3, sizeof(HexBlob), used_hex, same_hex, generate_as<HexBlob, generate_hex_explore_episode>,
-     MAX_BOXES, MAX_REWARDS, 2048, 60.0f, 0.2f, -LEN_ANY, LEN_ANY, true, DRAW_NONE, ARR_HEX},
+     MAX_BOXES, MAX_REWARDS, 2048, 60.0f, 0.2f, -LEN_ANY, LEN_ANY, true, DRAW_HEX, ARR_HEX},
     // scenario_box_a_gone.hpp:82-98 (+ teamSpirit 0); scenarios/init.hpp:50.  At most 8 + 972 + 24 boxes, all in the world frame.  It ends as soon as every
     // agent is on the floor: for a random or idle agent after 30-60 ticks, never under 20 (it lands on its spawn platform, leaves it or waits for it to
     // vanish, falls at least 6.8 units -- 15 ticks from rest -- then doneWithTimer's 0.3 s): 1.3 s, whatever episodeLengthSec says

@@ -95,6 +95,8 @@ SYMBOLS = [
     ("mv_debug_obstacles_draw_host", C.c_int, [C.c_char_p, _I, _I, _I, _F, _P, _I]),
     ("mv_debug_obstacles_draw_stats_host", C.c_int, [C.c_char_p, _I, _I, _I, _F, _P]),
     ("mv_debug_obstacles_draw_device", C.c_int, [_I, C.c_char_p, _I, _P, _I, _I, _F, _P, C.c_int64, _P]),
+    ("mv_debug_hex_draw_host", C.c_int, [C.c_char_p, _I, _I, _I, _F, _P, _I]),
+    ("mv_debug_hex_draw_device", C.c_int, [_I, C.c_char_p, _I, _P, _I, _I, _F, _P, C.c_int64, _P]),
     ("mv_set_episode_log", C.c_int, [_P, _I]), ("mv_get_episode_log_capacity", C.c_int, [_P]), ("mv_flush_episode_log", C.c_int, [_P]),
     ("mv_episode_log_count", C.c_int, [_P, C.POINTER(_U), C.POINTER(_U)]), ("mv_drain_episode_log", C.c_int, [_P, _P, _I, C.POINTER(_U)]),
     ("mv_episode_log_records_device_ptr", _P, [_P]), ("mv_episode_log_count_device_ptr", _P, [_P]),
@@ -1811,7 +1813,8 @@ class MegaverseGym:
 
     def device_generator(self):
         """are the episodes drawn on the device?  True: TowerBuilding; Collect with the device generator; the Obstacles family and Empty with
-        MV_OBSTACLES_DEVICE_GEN=1 in the environment when the gym was made.  host_generator_threads() is 0 exactly then."""
+        MV_OBSTACLES_DEVICE_GEN=1, HexMemory and HexExplore with MV_HEX_DEVICE_GEN=1, in the environment when the gym was made.
+        host_generator_threads() is 0 exactly then."""
         return int(self._lib.mv_device_generator(self._g)) == 1
 
     def arena_bytes(self):
