@@ -883,28 +883,20 @@ int mv_debug_generate_sokoban(int32_t num_agents, int32_t env_seed, int32_t n, f
    size.  Returns n. */
 int mv_debug_generate_football(int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes);
 
-/* Collect's episode generator as it runs on the DEVICE (megaverse_amd/csrc/mv_collect_draw.h; the product's feeder uses it where mv_host_generator_threads
- * says 0 for a Collect gym).  _host: the same code compiled for the CPU, no device needed -- the n-th episode of an env seeded
- * with env_seed, the record mv_debug_generate_episode("Collect", ...) returns (seq = n).  _device: `count` envs draw their first n episodes on the GPU, out
- * receives the n-th of each (count x the record size), *ms_per_launch the mean duration of a launch of `count` wavefronts.  Replaces CollectScenario::reset +
- * createLandscape + addEpisodeDrawables (scenario_collect.cpp:20-161,190-214), siv::PerlinNoise (perlin_noise.hpp:118-126,315-318). */
-int mv_debug_collect_draw_host(int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes);
-/* The Obstacles family's and Empty's generator as it runs on the DEVICE (megaverse_amd/csrc/mv_obstacles_draw.h; the feeder uses it where
- * mv_device_generator says 1 for such a gym), with the semantics of the two Collect hooks.  `scenario`: one of the six Obstacles names or "Empty".
- * _host: the same code compiled for the CPU (the merge in its serial form), the record mv_debug_generate_episode(scenario, ...) returns (seq = n); out == NULL:
- * the record's size.  _device: `count` envs draw their first n episodes on the GPU.  _stats_host: out[0 .. 3] = chain attempts, left turns, right turns and
- * GEN_* capacity flags of the n-th episode as mv_gen_obstacles.cpp draws it, out[4 .. 7] = the same four of mv_obstacles_draw.h's code on the CPU. */
-int mv_debug_obstacles_draw_host(const char *scenario, int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes);
+/* The episode generators as they run on the DEVICE (megaverse_amd/csrc/mv_collect_draw.h, mv_obstacles_draw.h, mv_hex_draw.h; the feeder uses them where
+ * mv_device_generator says 1 for a gym), one pair of hooks over the table of draw kinds (megaverse_amd/csrc/mv_draw.h).  `scenario`: "Collect", one of the
+ * six Obstacles names, "Empty", "HexMemory" or "HexExplore"; any other name fails with a message that lists these.
+ * _host: the same code compiled for the CPU, no device needed (the phases the kernels spread over a wave in their serial form) -- the n-th episode of an env
+ * seeded with env_seed, the record mv_debug_generate_episode(scenario, ...) returns (seq = n; what the generator leaves unused is zero); out == NULL: the
+ * record's size.  _device: `count` envs draw their first n episodes on the GPU (n launches of the kind's kernel), out receives the n-th of each (count x the
+ * record size), *ms_per_launch (may be NULL) the mean duration of a launch.  Collect replaces CollectScenario::reset + createLandscape +
+ * addEpisodeDrawables (scenario_collect.cpp:20-161,190-214), siv::PerlinNoise (perlin_noise.hpp:118-126,315-318). */
+int mv_debug_draw_host(const char *scenario, int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes);
+int mv_debug_draw_device(int32_t device, const char *scenario, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n,
+                         float base_episode_len, void *out, int64_t out_bytes, float *ms_per_launch);
+/* The Obstacles family's own: out[0 .. 3] = chain attempts, left turns, right turns and GEN_* capacity flags of the n-th episode as mv_gen_obstacles.cpp
+ * draws it, out[4 .. 7] = the same four of mv_obstacles_draw.h's code on the CPU. */
 int mv_debug_obstacles_draw_stats_host(const char *scenario, int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, int32_t *out8);
-int mv_debug_obstacles_draw_device(int32_t device, const char *scenario, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n,
-                                   float base_episode_len, void *out, int64_t out_bytes, float *ms_per_launch);
-/* HexMemory's and HexExplore's generator as it runs on the DEVICE (megaverse_amd/csrc/mv_hex_draw.h; the feeder uses it where mv_device_generator says 1
- * for such a gym), with the semantics of the Obstacles hooks.  `scenario`: "HexMemory" or "HexExplore".  _host: the same code compiled for the CPU (the
- * lay-out, the prefix sum and the geometry in their serial form), the record mv_debug_generate_episode(scenario, ...) returns (seq = n; the boxes beyond
- * num_boxes are zero here); out == NULL: the record's size.  _device: `count` envs draw their first n episodes on the GPU (hex_draw_kernel). */
-int mv_debug_hex_draw_host(const char *scenario, int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes);
-int mv_debug_hex_draw_device(int32_t device, const char *scenario, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n,
-                             float base_episode_len, void *out, int64_t out_bytes, float *ms_per_launch);
 /* Host-only (no device): the episode log's per-tick body (megaverse_amd/csrc/mv_episode_log.h, the source the kernel runs) over k ticks of N envs x A
  * agents: rewards [k][N*A], dones [k][N], true_objectives [k][N*A]; first_tick: the first tick's end_tick.  In and out: ret [N*A], len [N], *count, *dropped,
  * and records, a buffer of `capacity` mv_episode_record of which *count are valid on entry. */
@@ -978,8 +970,6 @@ int mv_debug_env_record_unpack_host(const uint32_t *array_bytes, int32_t count, 
                                     uint8_t *env_state_inout);
 /* out_host [N]: how many episodes of its own sequence every env has taken so far (a fork leaves the destination's count alone) */
 int mv_debug_episodes_consumed(mv_gym *g, int32_t *out_host);
-int mv_debug_collect_draw_device(int32_t device, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n, float base_episode_len, void *out,
-                                 int64_t out_bytes, float *ms_per_launch);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@
 //   step all envs  ->  for done envs: record trueObjective, reset  ->  draw.
 // There is NO CPU fallback: if no HIP device can be opened mv_create fails.
 #include "mv_api_internal.h"
-#include "mv_obstacles_draw.h"
+#include "mv_draw.h"
 
 thread_local std::string mvapi::g_err;
 
@@ -281,6 +281,15 @@ static int usable_host_cores()
         break;
     }
     return std::max(1, n);
+}
+
+// Collect, MV_COLLECT_DEVICE_GEN unset: the episodes are drawn on the DEVICE where nobody chose the feeder's thread count and this process's share of the
+// host is under three cores (eight ranks under a 16-CPU quota: two host thread holds Collect at 15.9 M obs/s against 16.6 M) and the gym has
+// 256 envs and more (r12n, two cores, host / device: a quarter of a Mixed4 batch 18.0 / 19.8 M obs/s, an eighth of a Mixed batch 16.9 / 16.2: too few episodes
+// to pay for the draw launches).  The other kinds have no rule of their own yet: this one was cut from measurements their generators do not have.
+static bool device_gen_by_default(int draw, int threads_asked_for, int share, size_t num_envs)
+{
+    return draw == DRAW_COLLECT && threads_asked_for <= 0 && !getenv("MV_FEEDER_THREADS") && share < 3 && num_envs >= 256;
 }
 
 // the simulation stream (another queue priority than the caller's was measured, low and high: no gain, r06k)
@@ -581,19 +590,16 @@ int mv_create(const mv_config *cfg, mv_gym **out)
         g->feederThreads = cfg->num_simulation_threads > 0 ? std::min(32, (int)cfg->num_simulation_threads) : std::max(1, std::min(16, share - 1));
         if (const char *e = getenv("MV_FEEDER_THREADS")) g->feederThreads = std::min(64, std::max(1, atoi(e)));
         g->uploadEvents.assign(64, nullptr);
-        // Collect: the episodes may be drawn on the DEVICE (mv_collect_draw.h: the same episodes, byte for byte) instead of by the host's worker threads --
-        // MV_COLLECT_DEVICE_GEN=1 / 0, otherwise where this process's share of the host is under three cores (eight ranks under a 16-CPU quota: two host
-        // thread holds Collect at 15.9 M obs/s against 16.6 M) and the gym has 256 envs and more (r12n, two cores, host / device: a quarter of a
-        // Mixed4 batch 18.0 / 19.8 M obs/s, an eighth of a Mixed batch 16.9 / 16.2: too few episodes to pay for the draw launches).  The staging slots are device memory then.
-        g->blobsOnDevice = row.draw == DRAW_COLLECT && (getenv("MV_COLLECT_DEVICE_GEN") ? atoi(getenv("MV_COLLECT_DEVICE_GEN")) != 0
-                                                                                         : cfg->num_simulation_threads <= 0 && !getenv("MV_FEEDER_THREADS") && share < 3 && N >= 256);
-        // The Obstacles family and Empty (one record, EpisodeBlob): drawn on the device (mv_obstacles_draw.h: the same episodes, byte for byte) with
-        // MV_OBSTACLES_DEVICE_GEN=1 and only then -- no rule of its own yet, Collect's was cut from measurements this generator does not have.
-        if (row.draw == DRAW_OBSTACLES || row.draw == DRAW_EMPTY) g->blobsOnDevice = getenv("MV_OBSTACLES_DEVICE_GEN") && atoi(getenv("MV_OBSTACLES_DEVICE_GEN")) != 0;
-        // HexMemory and HexExplore (HexBlob): drawn on the device (mv_hex_draw.h: the same episodes, byte for byte) with MV_HEX_DEVICE_GEN=1 and only then.
-        if (row.draw == DRAW_HEX) g->blobsOnDevice = getenv("MV_HEX_DEVICE_GEN") && atoi(getenv("MV_HEX_DEVICE_GEN")) != 0;
+        // A family with a draw kind (mv_draw.h) may have its episodes drawn on the DEVICE -- the same episodes, byte for byte -- instead of by the host's worker
+        // threads: where the kind's switch (MV_COLLECT_DEVICE_GEN, MV_OBSTACLES_DEVICE_GEN, MV_HEX_DEVICE_GEN) is set and not 0; unset: host-fed, but for
+        // Collect's automatic rule.  The staging slots are device memory then.
+        const DrawKind &kind = draw_kind(row.draw);
+        if (kind.launch) {
+            const char *e = getenv(kind.switch_name);
+            g->blobsOnDevice = e ? atoi(e) != 0 : device_gen_by_default(row.draw, cfg->num_simulation_threads, share, N);
+        }
         // (the obstacles* float parameters can ask for levels beyond the device generator's fixed arrays -- 40 platforms in a row, say: said here, not drawn)
-        if (g->blobsOnDevice && row.draw == DRAW_OBSTACLES && !odraw::config_fits(oc)) {
+        if (g->blobsOnDevice && kind.config_fits && !kind.config_fits(oc)) {
             mv_destroy(g);
             return fail("mv_create: MV_OBSTACLES_DEVICE_GEN=1, but this gym's generator parameters are beyond what the device generator holds (at most "
                         + std::to_string((int)odraw::LARGEST_PLATFORMS) + " platforms, heights 1 to " + std::to_string((int)odraw::LARGEST_HEIGHT)

@@ -7,12 +7,10 @@
 //
 // mv_gen_collect.cpp reaches the reference's draws through libstdc++ (11.4 in this image): std::mt19937, std::minstd_rand0, uniform_int_distribution,
 // generate_canonical, std::shuffle and -- for the diamonds on the highest ground -- an UNSTABLE std::sort.  Those are third-party; their published algorithms
-// are restated here so that one GPU lane can run them:
-//   * MT19937 (Matsumoto & Nishimura 1998), sequential form;
+// are restated so that one GPU lane can run them -- MT19937, Lemire's bounded draw and std::shuffle's walk in mv_draw_common.h, which every device generator
+// stands on, and here what only Collect draws through:
 //   * minstd_rand0: x <- 16807 x mod (2^31 - 1) (Lewis, Goodman, Miller 1969), seed 0 -> 1;
-//   * uniform_int_distribution: Lemire's nearly-divisionless method on the 32-bit generator (bits/uniform_int_dist.h, _S_nd), the two-division
-//     rejection form on any other generator range (same file, "fallback case");
-//   * std::shuffle: one draw for two swap positions while range^2 fits the generator's range (bits/stl_algo.h);
+//   * uniform_int_distribution on a generator whose range is not 2^32: the two-division rejection form (bits/uniform_int_dist.h, "fallback case");
 //   * std::sort: introsort -- median-of-three quicksort down to 16 elements under a depth limit of 2 lg n, heapsort beyond it, one final insertion
 //     sort (bits/stl_algo.h, bits/stl_heap.h).  The order of equal keys is part of the episode (which cells the diamonds take), so the restatement
 //     follows the element moves exactly, not just the result's sortedness.
@@ -26,15 +24,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mv_draw_common.h"
 #include "mv_types.h"
 
 namespace mv {
 namespace cdraw {
 
-#define MV_HD __host__ __device__ inline
+using namespace draw;
 
 enum : int { MAX_CELLS = (HM_DIM - 2) * (HM_DIM - 2), TAKEN_WORDS = (HM_DIM * HM_DIM * 20 + 31) / 32, SORT_STACK = 128 };
-enum : int { FLAG_SLABS = 1, FLAG_OBJECTS = 4, FLAG_REWARDS = 8 };   // = GEN_SLABS, GEN_OBJECTS, GEN_REWARDS (mv_gen.h)
 
 // scratch of one episode: LDS on the device, plain memory on the host
 struct Scratch {
@@ -46,74 +44,12 @@ struct Scratch {
     int8_t hm[HM_BYTES];
 };
 
-// where an env's generator stands (TowerGen's twin): the seed the NEXT episode's Env::reset re-seeds with, and the sequence number it will get
-struct alignas(16) GenState {
-    uint32_t seed;
-    int32_t seed_is_env_seed;   // 1: `seed` is the Env::seed() value, the reset draws its seed from it first
-    int32_t next_seq;
-    int32_t flags;              // FLAG_* raised by this env's generator since the host last looked
-};
-
 struct Params {
     int nx, nz, octaves, intensity;
     double step;
     float ground;
     unsigned land_color, floor_color;
 };
-
-// ---- MT19937, sequential -----------------------------------------------------------------------------------------------------------------
-struct Mt {
-    uint32_t *s;
-    int idx;
-};
-MV_HD void mt_seed1(Mt &g, uint32_t seed)
-{
-    uint32_t x = seed;
-    g.s[0] = x;
-    for (int i = 1; i < 624; ++i) {
-        x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)i;
-        g.s[i] = x;
-    }
-    g.idx = 624;
-}
-MV_HD uint32_t mt_next1(Mt &g)
-{
-    if (g.idx >= 624) {
-        uint32_t *s = g.s;
-        for (int k = 0; k < 624; ++k) {
-            const uint32_t y = (s[k] & 0x80000000u) | (s[k == 623 ? 0 : k + 1] & 0x7fffffffu);
-            s[k] = s[k < 227 ? k + 397 : k - 227] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-        }
-        g.idx = 0;
-    }
-    uint32_t y = g.s[g.idx++];
-    y ^= y >> 11;
-    y ^= (y << 7) & 0x9d2c5680u;
-    y ^= (y << 15) & 0xefc60000u;
-    y ^= y >> 18;
-    return y;
-}
-// unbiased integer in [0, range), range >= 1 (Lemire)
-MV_HD uint32_t mt_below1(Mt &g, uint32_t range)
-{
-    uint64_t product = (uint64_t)mt_next1(g) * (uint64_t)range;
-    uint32_t low = (uint32_t)product;
-    if (low < range) {
-        const uint32_t threshold = (0u - range) % range;
-        while (low < threshold) {
-            product = (uint64_t)mt_next1(g) * (uint64_t)range;
-            low = (uint32_t)product;
-        }
-    }
-    return (uint32_t)(product >> 32);
-}
-MV_HD int rand_range1(Mt &g, int lo, int hi) { return lo + (int)mt_below1(g, (uint32_t)(hi - lo)); }   // util.hpp:30-33
-MV_HD float frand1(Mt &g)                                                                                 // util.hpp:46-49
-{
-    float ret = (float)mt_next1(g) / 4294967296.0f;
-    if (ret >= 1.0f) ret = 0.99999994f;
-    return ret;
-}
 
 // ---- minstd_rand0 through uniform_int_distribution's two-division form ----------------------------------------------------------------------
 struct Minstd {
@@ -126,27 +62,6 @@ MV_HD uint64_t minstd_below(Minstd &g, uint64_t range)   // integer in [0, range
     uint64_t ret;
     do ret = minstd_next(g) - 1ull; while (ret >= past);
     return ret / scaling;
-}
-
-// std::shuffle's walk, two swap positions per draw; `below(range)` draws, `swap(i, j)` exchanges
-template <class Below, class Swap>
-MV_HD void shuffle_walk(int n, Below below, Swap swap)
-{
-    if (n <= 0) return;
-    int i = 1;
-    if ((n % 2) == 0) {
-        const int j = (int)below(2u);
-        swap(i, j);
-        ++i;
-    }
-    while (i < n) {
-        const uint32_t r = (uint32_t)i + 1u;
-        const uint32_t x = (uint32_t)below(r * (r + 1u));
-        swap(i, (int)(x / (r + 1u)));
-        ++i;
-        swap(i, (int)(x % (r + 1u)));
-        ++i;
-    }
 }
 
 // ---- std::sort of cells by DESCENDING y -------------------------------------------------------------------------------------------------

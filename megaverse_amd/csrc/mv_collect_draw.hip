@@ -1,12 +1,13 @@
-// megaverse_amd/csrc/mv_collect_draw.hip -- Collect episodes generated on the device (mv_collect_draw.h): the kernel, its launcher, and the test hooks that
-// hold it against mv_gen_collect.cpp (the host generator, which tests/test_host_generators.py holds against the oracle and tests/test_oracle_collect.py
+// megaverse_amd/csrc/mv_collect_draw.hip -- Collect episodes generated on the device (mv_collect_draw.h): the kernel, its launcher, the staging-to-ring copies and the host
+// twin that the test hooks (mv_draw.hip) hold against mv_gen_collect.cpp (the host generator, which tests/test_host_generators.py holds against the oracle and tests/test_oracle_collect.py
 // against the reference's perlin_noise.hpp).
+#include <cstdio>
 #include <cstring>
-#include <string>
-#include <vector>
+#include <memory>
 
 #include "mv_api_internal.h"
 #include "mv_collect_draw.h"
+#include "mv_draw.h"
 #include "mv_math.h"
 
 namespace mv {
@@ -19,7 +20,6 @@ using namespace cdraw;
 // takes 64 cells per round (a ballot), a box's growth along x, then z, then y one ballot each (lane k tests the k-th cell / row / layer beyond the seed, the run
 // of ones from lane 0 is the growth), the box's cells are marked by the lanes together.  The serial form scanned up to 25 k cells one LDS round trip at a time:
 // 880 us of an episode's 1.4 ms (r12c).
-__device__ __forceinline__ int trailing_ones(unsigned long long m) { return m == ~0ull ? 64 : __ffsll((long long)~m) - 1; }
 __device__ __forceinline__ void draw_slabs_wave(const Params &p, Scratch &w, int top, CollectBlob *out, int &flags)
 {
     const int lane = lane_id();
@@ -141,22 +141,16 @@ __global__ __launch_bounds__(64 * DRAW_WAVES) void collect_draw_kernel(GenState 
     }
     if (tm && lane == 0) tm[6] = wall_clock64();
     for (int i = lane; i < HM_BYTES / 16; i += 64) reinterpret_cast<uint4 *>(out->heightmap)[i] = reinterpret_cast<const uint4 *>(w.hm)[i];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    wave_sync();
-    if (lane == 0) {
-        __hip_atomic_store(&out->seq, st.next_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        st.seed = nextSeed; st.seed_is_env_seed = 0; st.next_seq += 1; st.flags |= flags;
-        states[env] = st;
-        if (flags && flag_word) atomicOr(flag_word, flags);   // (a capacity of the episode record was hit: reported once by the next stepping call)
-    }
+    publish_episode(&out->seq, states, env, st, nextSeed, flags, flag_word, lane);
 }
 
-void launch_collect_draw(void *states, const int32_t *envs, int count, uint8_t *slots, size_t slot_bytes, int num_agents, float base_episode_len,
-                         hipStream_t stream, int32_t *flag_word)
+bool launch_collect_draw(const DrawLaunch &a)
 {
-    if (count <= 0) return;
-    hipLaunchKernelGGL(collect_draw_kernel, dim3((count + DRAW_WAVES - 1) / DRAW_WAVES), dim3(64 * DRAW_WAVES), 0, stream, static_cast<GenState *>(states), envs, count, slots, slot_bytes, num_agents,
-                       base_episode_len, flag_word);
+    if (a.count == 0) return true;
+    if (!draw_launch_ok(a, sizeof(CollectBlob))) return false;
+    hipLaunchKernelGGL(collect_draw_kernel, dim3((a.count + DRAW_WAVES - 1) / DRAW_WAVES), dim3(64 * DRAW_WAVES), 0, a.stream, a.states, a.envs, a.count, a.slots, a.slot_bytes,
+                       a.num_agents, a.base_episode_len, a.flag_word, a.timing);
+    return true;
 }
 
 // Device-drawn episodes, staging slot -> ring slot: one workgroup per episode, the record's used prefix (the slab list comes last), `seq` last of all --
@@ -213,8 +207,9 @@ void launch_blob_copy(int draw, const int32_t *envs, const int32_t *slots, int c
 }
 
 // the same episode on the host: the code of mv_collect_draw.h compiled for the CPU
-static uint32_t collect_draw_host(GenState &st, Scratch &w, int num_agents, float base_episode_len, CollectBlob &out)
+static void collect_draw_host1(GenState &st, Scratch &w, int num_agents, float base_episode_len, CollectBlob &out)
 {
+    std::memset(&out, 0, sizeof out);
     Mt g{w.mt, 624};
     Params p;
     draw_head(g, st, w, p);
@@ -231,84 +226,24 @@ static uint32_t collect_draw_host(GenState &st, Scratch &w, int num_agents, floa
     std::memcpy(out.heightmap, w.hm, sizeof out.heightmap);
     out.seq = st.next_seq;
     st.seed = next; st.seed_is_env_seed = 0; st.next_seq += 1; st.flags |= flags;
-    return next;
+}
+
+void collect_draw_host(int, const ObstacleConfig &, int num_agents, uint32_t env_seed, int n, float base_episode_len, void *record)
+{
+    auto w = std::make_unique<Scratch>();
+    GenState st{env_seed, 1, 1, 0};
+    for (int i = 0; i < n; ++i) collect_draw_host1(st, *w, num_agents, base_episode_len, *static_cast<CollectBlob *>(record));
+}
+
+void print_collect_draw_timing(const long long *tm, int count)
+{
+    double ph[6] = {0, 0, 0, 0, 0, 0}, worst = 0;
+    for (int e = 0; e < count; ++e) {
+        for (int q = 0; q < 6; ++q) ph[q] += double(tm[(size_t)e * 8 + q + 1] - tm[(size_t)e * 8 + q]) * 0.01;
+        worst = std::max(worst, double(tm[(size_t)e * 8 + 6] - tm[(size_t)e * 8]) * 0.01);
+    }
+    std::fprintf(stderr, "[mv draw timing] %d episodes, us per episode: head %.0f, heights %.0f, slabs %.0f, cells + shuffle %.0f, sort %.0f, rest %.0f; "
+                 "slowest episode %.0f\n", count, ph[0] / count, ph[1] / count, ph[2] / count, ph[3] / count, ph[4] / count, ph[5] / count, worst);
 }
 
 }  // namespace mv
-
-using namespace mv;
-using namespace mvapi;
-
-extern "C" {
-
-// Host-only test hook (no device needed): the n-th episode of an env seeded with `env_seed` as mv_collect_draw.h's code generates it ON THE HOST -- the
-// same record mv_debug_generate_episode("Collect", ...) returns (its `seq` is n here, 0 there; the records' unused tails are zero here).
-int mv_debug_collect_draw_host(int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes)
-{
-    if (!out) return (int)sizeof(CollectBlob);
-    if (num_agents < 1 || num_agents > MAX_AGENTS || n < 1) return fail("mv_debug_collect_draw_host: bad arguments");
-    if ((size_t)out_bytes < sizeof(CollectBlob)) return fail("mv_debug_collect_draw_host: buffer too small");
-    std::vector<uint8_t> buf(sizeof(CollectBlob), 0);
-    auto w = std::make_unique<cdraw::Scratch>();
-    cdraw::GenState st{(uint32_t)env_seed, 1, 1, 0};
-    for (int i = 0; i < n; ++i) {
-        std::memset(buf.data(), 0, buf.size());
-        collect_draw_host(st, *w, num_agents, base_episode_len, *reinterpret_cast<CollectBlob *>(buf.data()));
-    }
-    std::memcpy(out, buf.data(), buf.size());
-    return (int)buf.size();
-}
-
-// Test hook: `count` envs seeded with env_seeds[i], each drawing its first n episodes ON THE DEVICE (n launches of collect_draw_kernel, `count` wavefronts
-// each); out receives the envs' n-th episodes, count x sizeof(CollectBlob) bytes; *ms_per_launch (may be null) the mean time of a launch.
-int mv_debug_collect_draw_device(int32_t device, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n, float base_episode_len, void *out,
-                                 int64_t out_bytes, float *ms_per_launch)
-{
-    if (num_agents < 1 || num_agents > MAX_AGENTS || n < 1 || count < 1 || !env_seeds || !out) return fail("mv_debug_collect_draw_device: bad arguments");
-    if ((size_t)out_bytes < (size_t)count * sizeof(CollectBlob)) return fail("mv_debug_collect_draw_device: buffer too small");
-    HIP_TRY(hipSetDevice(device));
-    std::vector<cdraw::GenState> st((size_t)count);
-    for (int i = 0; i < count; ++i) st[(size_t)i] = cdraw::GenState{(uint32_t)env_seeds[i], 1, 1, 0};
-    cdraw::GenState *dSt = nullptr;
-    uint8_t *dSlots = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const size_t bytes = (size_t)count * sizeof(CollectBlob);
-    bool ok = hipMalloc((void **)&dSt, (size_t)count * sizeof(cdraw::GenState)) == hipSuccess && hipMalloc((void **)&dSlots, bytes) == hipSuccess &&
-              hipMemset(dSlots, 0, bytes) == hipSuccess &&
-              hipMemcpy(dSt, st.data(), (size_t)count * sizeof(cdraw::GenState), hipMemcpyHostToDevice) == hipSuccess &&
-              hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-    if (ok) {
-        ok = hipEventRecord(e0, nullptr) == hipSuccess;
-        long long *dTm = nullptr;
-        const bool timing = getenv("MV_DRAW_TIMING") != nullptr;   // phases of the LAST launch's episodes to stderr (100 MHz clock)
-        if (timing) ok = hipMalloc((void **)&dTm, (size_t)count * 8 * sizeof(long long)) == hipSuccess;
-        for (int i = 0; i < n && ok; ++i) {
-            if (timing) hipLaunchKernelGGL(collect_draw_kernel, dim3((count + DRAW_WAVES - 1) / DRAW_WAVES), dim3(64 * DRAW_WAVES), 0, nullptr, dSt, (const int32_t *)nullptr, count, dSlots, sizeof(CollectBlob),
-                                           num_agents, base_episode_len, (int32_t *)nullptr, dTm);
-            else launch_collect_draw(dSt, nullptr, count, dSlots, sizeof(CollectBlob), num_agents, base_episode_len, nullptr, nullptr);
-        }
-        if (timing && ok) {
-            std::vector<long long> tm((size_t)count * 8);
-            ok = hipMemcpy(tm.data(), dTm, tm.size() * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess;
-            double ph[6] = {0, 0, 0, 0, 0, 0}, worst = 0;
-            for (int e = 0; e < count && ok; ++e) {
-                for (int q = 0; q < 6; ++q) ph[q] += double(tm[(size_t)e * 8 + q + 1] - tm[(size_t)e * 8 + q]) * 0.01;
-                worst = std::max(worst, double(tm[(size_t)e * 8 + 6] - tm[(size_t)e * 8]) * 0.01);
-            }
-            std::fprintf(stderr, "[mv draw timing] %d episodes, us per episode: head %.0f, heights %.0f, slabs %.0f, cells + shuffle %.0f, sort %.0f, rest %.0f; "
-                         "slowest episode %.0f\n", count, ph[0] / count, ph[1] / count, ph[2] / count, ph[3] / count, ph[4] / count, ph[5] / count, worst);
-            (void)hipFree(dTm);
-        }
-        ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-             hipMemcpy(out, dSlots, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-        float ms = 0.0f;
-        if (ok && ms_per_launch && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *ms_per_launch = ms / float(n);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (dSt) (void)hipFree(dSt);
-    if (dSlots) (void)hipFree(dSlots);
-    return ok ? 0 : fail("mv_debug_collect_draw_device: a HIP call failed");
-}
-
-}  // extern "C"

@@ -4,26 +4,16 @@
 #include <chrono>
 #include <cstddef>
 
-#include "mv_collect_draw.h"
-#include "mv_obstacles_draw.h"
+#include "mv_draw.h"
 #include "mv_scenarios.h"
 
 namespace mv {
 
-void launch_collect_draw(void *states, const int32_t *envs, int count, uint8_t *slots, size_t slot_bytes, int num_agents, float base_episode_len,
-                         hipStream_t stream, int32_t *flag_word);   // mv_collect_draw.hip
-void launch_obstacles_draw(void *states, const int32_t *envs, int count, uint8_t *slots, size_t slot_bytes, int scenario, const ObstacleConfig &cfg, int num_agents,
-                           float base_episode_len, uint32_t *grids, int regions, hipStream_t stream, int32_t *flag_word);   // mv_obstacles_draw.hip
-int obstacles_draw_regions(int scenario, int num_envs);   // grid regions a feeder of num_envs envs holds (Empty: none), and one region's size
-size_t obstacles_draw_region_bytes();
-bool launch_hex_draw(void *states, const int32_t *envs, int count, uint8_t *slots, size_t slot_bytes, int scenario, int num_agents, float base_episode_len,
-                     hipStream_t stream, int32_t *flag_word);   // mv_hex_draw.hip; false: arguments it cannot take, nothing launched
-
-// the scenarios a draw kernel exists for
+// the scenarios a draw kernel exists for (mv_draw.h: the table of draw kinds), with a configuration it can draw
 static bool has_draw_kernel(int scenario, const ObstacleConfig &cfg)
 {
-    const int draw = scenario_row(scenario).draw;
-    return draw == DRAW_COLLECT || draw == DRAW_EMPTY || draw == DRAW_HEX || (draw == DRAW_OBSTACLES && odraw::config_fits(cfg));
+    const DrawKind &kind = draw_kind(scenario_row(scenario).draw);
+    return kind.launch && (!kind.config_fits || kind.config_fits(cfg));
 }
 
 EpisodeFeeder::EpisodeFeeder(int scenario, const ObstacleConfig &cfg, int num_envs, int num_agents, float base_episode_len, uint8_t *slots,
@@ -37,12 +27,13 @@ EpisodeFeeder::EpisodeFeeder(int scenario, const ObstacleConfig &cfg, int num_en
     for (int i = 0; i < num_envs; ++i) { rng_[i].seed(rd()); ready_seq_[i].store(0, std::memory_order_relaxed); }
     if (device_gen_) {
         (void)hipSetDevice(device_);
-        // the Obstacles family's grids (mv_obstacles_draw.h: two bit planes over the largest bounding box a level can have), one region per episode a launch
-        // draws at a time
-        const int regions = scenario_row(scenario_).draw == DRAW_OBSTACLES ? obstacles_draw_regions(scenario_, num_envs_) : 0;
-        grid_bytes_ = size_t(regions) * obstacles_draw_region_bytes();
+        // the kind's grid regions (the Obstacles family's: two bit planes over the largest bounding box a level can have), one per episode a launch draws at
+        // a time
+        const DrawKind &kind = draw_kind(scenario_row(scenario_).draw);
+        const int regions = kind.regions(num_envs_);
+        grid_bytes_ = size_t(regions) * kind.region_bytes;
         grid_regions_ = regions;
-        const bool ok = (regions == 0 || hipMalloc((void **)&d_grids_, grid_bytes_) == hipSuccess) && hipMalloc(&d_states_, size_t(num_envs) * sizeof(cdraw::GenState)) == hipSuccess &&
+        const bool ok = (regions == 0 || hipMalloc((void **)&d_grids_, grid_bytes_) == hipSuccess) && hipMalloc((void **)&d_states_, size_t(num_envs) * sizeof(draw::GenState)) == hipSuccess &&
                         hipMalloc((void **)&d_list_, size_t(num_envs) * sizeof(int32_t)) == hipSuccess &&
                         hipMalloc((void **)&d_flags_, sizeof(int32_t)) == hipSuccess && hipMemset(d_flags_, 0, sizeof(int32_t)) == hipSuccess &&
                         hipHostMalloc((void **)&h_list_, size_t(num_envs) * sizeof(int32_t), hipHostMallocDefault) == hipSuccess &&
@@ -79,20 +70,20 @@ EpisodeFeeder::~EpisodeFeeder()
 
 bool EpisodeFeeder::upload_states()
 {
-    std::vector<cdraw::GenState> st((size_t)num_envs_);
-    for (int i = 0; i < num_envs_; ++i) st[(size_t)i] = cdraw::GenState{seeds_[i], 1, next_seq_[i], 0};
-    return hipMemcpy(d_states_, st.data(), st.size() * sizeof(cdraw::GenState), hipMemcpyHostToDevice) == hipSuccess;
+    std::vector<draw::GenState> st((size_t)num_envs_);
+    for (int i = 0; i < num_envs_; ++i) st[(size_t)i] = draw::GenState{seeds_[i], 1, next_seq_[i], 0};
+    return hipMemcpy(d_states_, st.data(), st.size() * sizeof(draw::GenState), hipMemcpyHostToDevice) == hipSuccess;
 }
 
 bool EpisodeFeeder::upload_states_of(const std::vector<uint8_t> &named)
 {   // one copy per run of consecutive named envs (every env named: one copy); the other envs' states are the device's, the host holds no copy of them
-    std::vector<cdraw::GenState> st;
+    std::vector<draw::GenState> st;
     for (int i = 0; i < num_envs_;) {
         if (!named[(size_t)i]) { ++i; continue; }
         const int first = i;
         st.clear();
-        for (; i < num_envs_ && named[(size_t)i]; ++i) st.push_back(cdraw::GenState{seeds_[i], 1, next_seq_[i], 0});
-        if (hipMemcpy(static_cast<cdraw::GenState *>(d_states_) + first, st.data(), st.size() * sizeof(cdraw::GenState), hipMemcpyHostToDevice) != hipSuccess)
+        for (; i < num_envs_ && named[(size_t)i]; ++i) st.push_back(draw::GenState{seeds_[i], 1, next_seq_[i], 0});
+        if (hipMemcpy(d_states_ + first, st.data(), st.size() * sizeof(draw::GenState), hipMemcpyHostToDevice) != hipSuccess)
             return false;
     }
     return true;
@@ -211,8 +202,9 @@ void EpisodeFeeder::generate(int env)
     ready_seq_[env].store(seq, std::memory_order_release);
 }
 
-// Device mode's only worker: every env whose slot is free, in ONE launch of the scenario's draw kernel (collect_draw_kernel, obstacles_draw_kernel, hex_draw_kernel) on this
-// feeder's stream -- while it runs (a Collect episode is 0.7 ms of one wavefront on average, 2.5 ms the slowest) the next batch gathers.  The launch is ordered behind the uploads that still read the batch's slots.
+// Device mode's only worker: every env whose slot is free, in ONE launch of the scenario's draw kernel (mv_draw.h: its kind's launcher) on this feeder's
+// stream -- while it runs (a Collect episode is 0.7 ms of one wavefront on average, 2.5 ms the slowest) the next batch gathers.  The launch is ordered behind
+// the uploads that still read the batch's slots.
 void EpisodeFeeder::device_worker_main()
 {
     (void)hipSetDevice(device_);
@@ -222,10 +214,10 @@ void EpisodeFeeder::device_worker_main()
         {
             std::unique_lock<std::mutex> lk(mu_);
             cv_task_.wait(lk, [this] { return stop_ || !tasks_.empty(); });
-            // A launch lasts as long as its slowest episode -- 2 to 3 ms (5 to 7 before the slab merge went to all lanes), however few it draws -- and while ANY kernel of another queue is in flight the
-            // observation launches run 9 % slower (r12h / r12j: with the draws back to back, in flight 84 % of the time, 1014 -> 1105 us; the same with a launch
-            // that only sleeps).  So the batch gathers for a while -- an env's ring holds two more episodes -- unless somebody is waiting for one (wait_ready:
-            // a forced reset, a re-seed, episodes of a few ticks).
+            // A launch lasts as long as its slowest episode -- 2 to 3 ms (5 to 7 before the slab merge went to all lanes), however few it draws -- and while
+            // ANY kernel of another queue is in flight the observation launches run 9 % slower (r12h / r12j: with the draws back to back, in flight 84 % of
+            // the time, 1014 -> 1105 us; the same with a launch that only sleeps).  So the batch gathers for a while -- an env's ring holds two more episodes
+            // -- unless somebody is waiting for one (wait_ready: a forced reset, a re-seed, episodes of a few ticks).
             if (!stop_ && !urgent_) cv_task_.wait_for(lk, std::chrono::milliseconds(linger_ms_), [this] { return stop_ || urgent_; });
             if (stop_) return;
             urgent_ = false;
@@ -242,11 +234,10 @@ void EpisodeFeeder::device_worker_main()
         const int count = (int)batch.size();
         ok = ok && hipMemcpyAsync(d_list_, h_list_, size_t(count) * sizeof(int32_t), hipMemcpyHostToDevice, gen_stream_) == hipSuccess;
         if (ok) {
-            const int draw = scenario_row(scenario_).draw;
-            if (draw == DRAW_COLLECT) launch_collect_draw(d_states_, d_list_, count, slots_, slot_bytes_, num_agents_, base_len_, gen_stream_, d_flags_);
-            else if (draw == DRAW_HEX) ok = launch_hex_draw(d_states_, d_list_, count, slots_, slot_bytes_, scenario_, num_agents_, base_len_, gen_stream_, d_flags_);
-            else launch_obstacles_draw(d_states_, d_list_, count, slots_, slot_bytes_, scenario_, cfg_, num_agents_, base_len_, d_grids_, grid_regions_, gen_stream_, d_flags_);
-            ok = ok && hipGetLastError() == hipSuccess &&hipMemcpyAsync(h_flags_, d_flags_, sizeof(int32_t), hipMemcpyDeviceToHost, gen_stream_) == hipSuccess &&
+            // (false: arguments the kernel cannot take, nothing launched -- this feeder has failed, nobody waits for the episodes)
+            ok = draw_kind(scenario_row(scenario_).draw).launch(DrawLaunch{d_states_, d_list_, count, slots_, slot_bytes_, scenario_, &cfg_, num_agents_, base_len_, d_grids_,
+                                                                            grid_regions_, gen_stream_, d_flags_, nullptr});
+            ok = ok && hipGetLastError() == hipSuccess && hipMemcpyAsync(h_flags_, d_flags_, sizeof(int32_t), hipMemcpyDeviceToHost, gen_stream_) == hipSuccess &&
                  hipStreamSynchronize(gen_stream_) == hipSuccess;
         }
         if (ok && *h_flags_) {

@@ -1,5 +1,5 @@
-// megaverse_amd/csrc/mv_feeder.h -- background episode generation for the host-generated scenarios
-// (Obstacles family, Collect).
+// megaverse_amd/csrc/mv_feeder.h -- background episode generation for every scenario whose episodes come from a feeder (mv_scenarios.h: every family but
+// TowerBuilding), by the host generators or -- device mode -- by the family's draw kernel (mv_draw.h: the table of draw kinds).
 //
 // The reference generates an env's next episode inside VectorEnv::step, serially, on the thread that is
 // stepping (vector_env.cpp:93-105 -> Env::reset): "reset is the serial straggler" (SURVEY.md 8a row E).
@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "mv_draw_common.h"
 #include "mv_gen.h"
 
 namespace mv {
@@ -27,8 +28,8 @@ class EpisodeFeeder {
 public:
     // slots: pinned host memory, num_envs * slot_bytes, owned by the caller
     // level_files: Sokoban only (the Boxoban level files found at construction, scenario_sokoban.cpp:40-78)
-    // device_gen (Collect, the Obstacles family, Empty, HexMemory, HexExplore; ignored for the others): `slots` is DEVICE memory and the episodes are drawn there by the scenario's
-    // draw kernel (mv_collect_draw.h: collect_draw_kernel; mv_obstacles_draw.h: obstacles_draw_kernel, which takes `cfg` by value; mv_hex_draw.h: hex_draw_kernel) -- one worker thread
+    // device_gen (the scenarios whose draw kind has a launcher, mv_draw.h: kDrawKinds; ignored for the others): `slots` is DEVICE memory and the episodes are
+    // drawn there by the kind's kernel -- one worker thread
     // gathers the envs whose slots are free into a batch, launches the kernel for them on a stream of its own and waits for it; everything else --
     // is_ready / wait_ready / recycle / reseed, the refill protocol around them -- is what it is for the host generators.
     EpisodeFeeder(int scenario, const ObstacleConfig &cfg, int num_envs, int num_agents, float base_episode_len, uint8_t *slots,
@@ -91,14 +92,14 @@ private:
     std::vector<std::string> soko_files_;
     std::vector<SokobanLevels> soko_levels_;
     std::vector<std::deque<SokoUndo>> soko_undo_;
-    // device mode: the generators' states on the device (cdraw::GenState per env), a batch's env list (pinned + device), the flag word its kernels raise
+    // device mode: the generators' states on the device (draw::GenState per env), a batch's env list (pinned + device), the flag word its kernels raise
     const bool device_gen_;
     bool urgent_ = false;       // under mu_: somebody waits for an episode, launch what is there
     int linger_ms_ = 15;        // how long a batch gathers otherwise (MV_DRAW_LINGER_MS; r12k: 0 / 10 / 25 / 50 / 100 ms: 16.4 / 16.6 / 16.5 / 16.0 / 14.7 M obs/s)
-    void *d_states_ = nullptr;
+    draw::GenState *d_states_ = nullptr;
     int32_t *h_list_ = nullptr, *d_list_ = nullptr, *h_flags_ = nullptr, *d_flags_ = nullptr;
     hipStream_t gen_stream_ = nullptr;
-    uint32_t *d_grids_ = nullptr;   // Obstacles family: grid_regions_ regions of odraw::GRID_WORDS words, one per episode a launch draws at a time
+    uint32_t *d_grids_ = nullptr;   // grid_regions_ regions of the draw kind's region_bytes (Obstacles family), one per episode a launch draws at a time
     int grid_regions_ = 0;
     size_t grid_bytes_ = 0;
     bool upload_states();   // next_seq_ / seeds -> d_states_ (reseed, under mu_ with no batch in flight)

@@ -5,8 +5,8 @@
 // -- Honeycomb::lay_out and carve, draw_maze_look, build_maze_boxes, object_record, store -- with the std::vector / std::set members replaced by fixed arrays;
 // what it stands for in the reference is listed there.
 //
-// The random stream is mt19937 through uniform_int_distribution, uniform_real_distribution<float> and std::shuffle; their restatements are mv_collect_draw.h's
-// (cdraw::Mt, mt_seed1, mt_below1, rand_range1, frand1, shuffle_walk), used unchanged.  The arithmetic is the host's, operation for operation: double where
+// The random stream is mt19937 through uniform_int_distribution, uniform_real_distribution<float> and std::shuffle; their restatements are mv_draw_common.h's
+// (draw::Mt, mt_seed1, mt_below1, rand_range1, frand1, shuffle_walk), used unchanged.  The arithmetic is the host's, operation for operation: double where
 // the host uses double, float where it rounds to float, in the host's order (the library is built with -ffp-contract=off); the corner offsets and SQRT3 are
 // the same hex literals.  What is not an IEEE basic operation:
 //   * sqrtf and float division go through double (sqrt_f, div_f): a double has more than 2 x 24 + 2 bits, so the second rounding changes nothing, and the
@@ -43,20 +43,14 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "mv_collect_draw.h"
+#include "mv_draw_common.h"
 #include "mv_gen.h"
 #include "mv_types.h"
 
 namespace mv {
 namespace hdraw {
 
-using cdraw::frand1;
-using cdraw::GenState;
-using cdraw::Mt;
-using cdraw::mt_below1;
-using cdraw::mt_seed1;
-using cdraw::rand_range1;
-using cdraw::shuffle_walk;
+using namespace draw;
 
 enum : int {
     MIN_SIZE = 2, MAX_SIZE = 7,   // rand_range(2, 8)
@@ -69,7 +63,6 @@ enum : int {
 static_assert(MAX_CELLS == 127 && MAX_INNER == 342 && MAX_WALLS == 294, "the bounds DESIGN.md states");
 static_assert(MAX_CELLS < 255, "a cell and 'outside' fit the low byte of a wall entry");
 static_assert(1 + MAX_WALLS * (2 + MAX_LANDMARKS) <= HEX_MAX_BOXES && MAX_CELLS <= HEX_MAX_OBJS, "the largest maze fits the record");
-enum : int { FLAG_SLABS = GEN_SLABS, FLAG_REWARDS = GEN_REWARDS };
 
 // a cell's wall entry: what is on the far side, the side of the cell that OWNS the geometry (the cell whose turn pushed it), and two bits
 enum : unsigned { OUTSIDE = 255u, E_OTHER = 255u, E_SIDE_SHIFT = 8, E_OWNER_IS_OTHER = 1u << 11, E_STANDING = 1u << 12, E_EMITTED = 1u << 13 };

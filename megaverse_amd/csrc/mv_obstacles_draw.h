@@ -5,7 +5,7 @@
 // tests/test_obstacles_draw_gpu.py).  This file restates THAT generator -- its platform classes, rigid motions, voxel paint, greedy merge, spawn cells and
 // object scatter -- with the std::vector / std::map / std::set members replaced by fixed arrays; what it stands for in the reference is listed there.
 //
-// The random stream is mt19937 through uniform_int_distribution and uniform_real_distribution<float>; their restatements are mv_collect_draw.h's (cdraw::Mt,
+// The random stream is mt19937 through uniform_int_distribution and uniform_real_distribution<float>; their restatements are mv_draw_common.h's (draw::Mt,
 // mt_seed1, mt_next1, rand_range1, frand1), used unchanged.  The one library algorithm restated here and not there:
 //   * std::lround(float), round half AWAY from zero on both sides of zero: lround_half_away below.  floor(v + 0.5f) in float is not it -- 0.49999997f + 0.5f
 //     rounds to 1.0f -- so the sum is taken in double, where it is exact for every float below 2^29.
@@ -35,18 +35,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mv_collect_draw.h"
+#include "mv_draw_common.h"
 #include "mv_gen.h"
 #include "mv_types.h"
 
 namespace mv {
 namespace odraw {
 
-using cdraw::frand1;
-using cdraw::GenState;
-using cdraw::Mt;
-using cdraw::mt_seed1;
-using cdraw::rand_range1;
+using namespace draw;
 
 // the largest ObstacleConfig scenario_from_name returns, from the table it reads (mv_gen.h: kObstaclePresets -- ObstaclesHard: 7 platforms, heights up to 4);
 // a gym's float parameters can ask for more: config_fits below is checked where a config arrives
@@ -67,7 +63,6 @@ static_assert(MAX_CHAIN >= 2 * largest_preset_platforms() + 2, "a chain: start, 
 static_assert(MAX_CHAIN == 16 && GRID_SIDES == 304 && GRID_NY == 37 && GRID_CELLS == 854848, "the bounds DESIGN.md 3.2 states");
 static_assert(MAX_CHAIN <= 64, "the hull clash test and the share table index chain members with small integers");
 static_assert(MAX_CHAIN * MAX_FLOOR_BOXES + MAX_CHAIN * MAX_WALL_BOXES < 256, "a level's painted boxes");
-enum : int { FLAG_SLABS = GEN_SLABS, FLAG_TERRAIN = GEN_TERRAIN, FLAG_OBJECTS = GEN_OBJECTS, FLAG_REWARDS = GEN_REWARDS, FLAG_COORDS = GEN_COORDS };
 
 MV_HD bool config_fits(const ObstacleConfig &c)
 {

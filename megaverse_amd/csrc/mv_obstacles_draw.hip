@@ -1,12 +1,13 @@
 // megaverse_amd/csrc/mv_obstacles_draw.hip -- Obstacles-family and Empty episodes generated on the device (mv_obstacles_draw.h): the kernel, its launcher, the
-// staging-to-ring copy of EpisodeBlob records, and the test hooks that hold the kernel against mv_gen_obstacles.cpp (the host generator, which
-// tests/test_host_generators.py holds against the oracle).
+// host twin that the test hooks (mv_draw.hip) hold against mv_gen_obstacles.cpp (the host generator, which tests/test_host_generators.py holds against the
+// oracle), and the family's own hook: how an episode came about, on both sides.
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "mv_api_internal.h"
+#include "mv_draw.h"
 #include "mv_math.h"
 #include "mv_obstacles_draw.h"
 
@@ -54,7 +55,6 @@ __device__ __forceinline__ void run_clear(uint32_t *plane, int id, int len)
         id += n; len -= n;
     }
 }
-__device__ __forceinline__ int trailing_ones64(unsigned long long m) { return m == ~0ull ? 64 : __ffsll((long long)~m) - 1; }
 
 // draw_slabs_serial (mv_obstacles_draw.h) by all 64 lanes of the episode's wave -- the same paint and the same greedy walk, box for box.
 //   paint: the boxes one after the other (later boxes overwrite), a box's rows (y, z) spread over the lanes, a row one run of bits set in its plane and
@@ -114,7 +114,7 @@ __device__ __forceinline__ void draw_slabs_wave(const Scratch &w, uint32_t *grid
                 for (;;) {
                     const int zz = zEnd + lane;
                     const bool ok = zz < nz && ones_from(pl, (y * nz + zz) * nx + x, wx) == wx;
-                    const int grown = trailing_ones64(__ballot(ok));
+                    const int grown = trailing_ones(__ballot(ok));
                     zEnd += grown;
                     if (grown < 64) break;
                 }
@@ -122,7 +122,7 @@ __device__ __forceinline__ void draw_slabs_wave(const Scratch &w, uint32_t *grid
                     const int yy = yEnd + lane;
                     bool ok = yy < ny;
                     for (int zz = z; ok && zz < zEnd; ++zz) ok = ones_from(pl, (yy * nz + zz) * nx + x, wx) == wx;
-                    const int grown = trailing_ones64(__ballot(ok));
+                    const int grown = trailing_ones(__ballot(ok));
                     yEnd += grown;
                     if (grown < 64) break;
                 }
@@ -174,6 +174,7 @@ __global__ __launch_bounds__(64 * ODRAW_WAVES) void obstacles_draw_kernel(GenSta
         const int env = envs ? envs[k] : k;
         EpisodeBlob *out = reinterpret_cast<EpisodeBlob *>(slots + (size_t)env * slot_bytes);
         GenState st = states[env];
+        // (draw::clear_record, written out: inside this loop the inline form compiled to other code -- one branch's polarity -- and the kernels stay as they are)
         for (int i = lane; i < (int)(sizeof(EpisodeBlob) / 16); i += 64) reinterpret_cast<uint4 *>(out)[i] = uint4{0u, 0u, 0u, 0u};
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // (the zeros are in place before lane 0 writes fields over them)
         wave_sync();
@@ -189,30 +190,21 @@ __global__ __launch_bounds__(64 * ODRAW_WAVES) void obstacles_draw_kernel(GenSta
             wave_sync();
             if (lane == 0) nextSeed = draw_tail(g, w, num_agents, base_episode_len, out, flags);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        wave_sync();
-        if (lane == 0) {
-            __hip_atomic_store(&out->seq, st.next_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            st.seed = nextSeed; st.seed_is_env_seed = 0; st.next_seq += 1; st.flags |= flags;
-            states[env] = st;
-            if (flags && flag_word) atomicOr(flag_word, flags);   // (a capacity of the episode record was hit: reported once by the next stepping call)
-        }
+        publish_episode(&out->seq, states, env, st, nextSeed, flags, flag_word, lane);
         wave_sync();   // (lane 0 is done with the wave's scratch before the next episode's chain goes there)
     }
 }
 
-int obstacles_draw_regions(int scenario, int num_envs) { return scenario == SCN_EMPTY ? 0 : std::min(num_envs, (int)DRAW_REGIONS); }
-size_t obstacles_draw_region_bytes() { return (size_t)GRID_WORDS * sizeof(uint32_t); }
-
-void launch_obstacles_draw(void *states, const int32_t *envs, int count, uint8_t *slots, size_t slot_bytes, int scenario, const ObstacleConfig &cfg, int num_agents,
-                           float base_episode_len, uint32_t *grids, int regions, hipStream_t stream, int32_t *flag_word)
+bool launch_obstacles_draw(const DrawLaunch &a)
 {
-    if (count <= 0) return;
-    const int empty = scenario == SCN_EMPTY ? 1 : 0;
-    const int waves = empty ? count : std::min(count, regions);
-    if (waves <= 0) return;
-    hipLaunchKernelGGL(obstacles_draw_kernel, dim3((waves + ODRAW_WAVES - 1) / ODRAW_WAVES), dim3(64 * ODRAW_WAVES), 0, stream, static_cast<GenState *>(states), envs, count,
-                       slots, slot_bytes, empty, cfg, num_agents, base_episode_len, empty ? nullptr : grids, waves, flag_word);
+    if (a.count == 0) return true;
+    if (!draw_launch_ok(a, sizeof(EpisodeBlob)) || !a.cfg) return false;
+    const int empty = a.scenario == SCN_EMPTY ? 1 : 0;
+    const int waves = empty ? a.count : std::min(a.count, a.regions);
+    if (waves <= 0) return false;   // (the Obstacles family without a grid region to draw in)
+    hipLaunchKernelGGL(obstacles_draw_kernel, dim3((waves + ODRAW_WAVES - 1) / ODRAW_WAVES), dim3(64 * ODRAW_WAVES), 0, a.stream, a.states, a.envs, a.count, a.slots,
+                       a.slot_bytes, empty, *a.cfg, a.num_agents, a.base_episode_len, empty ? nullptr : a.grids, waves, a.flag_word);
+    return true;
 }
 
 // the same episode on the host: the code of mv_obstacles_draw.h compiled for the CPU, the merge in its serial form
@@ -220,8 +212,8 @@ struct HostDraw {
     Scratch w;
     std::vector<uint32_t> grid = std::vector<uint32_t>((size_t)GRID_WORDS, 0u);
 };
-static void obstacles_draw_host(int scenario, const ObstacleConfig &cfg, GenState &st, HostDraw &h, int num_agents, float base_episode_len, EpisodeBlob &out,
-                                Stats *stats)
+static void obstacles_draw_host1(int scenario, const ObstacleConfig &cfg, GenState &st, HostDraw &h, int num_agents, float base_episode_len, EpisodeBlob &out,
+                                 Stats *stats)
 {
     std::memset(&out, 0, sizeof out);
     Mt g{h.w.mt, 624};
@@ -239,6 +231,13 @@ static void obstacles_draw_host(int scenario, const ObstacleConfig &cfg, GenStat
     st.seed = next; st.seed_is_env_seed = 0; st.next_seq += 1; st.flags |= flags;
 }
 
+void obstacles_draw_host(int scenario, const ObstacleConfig &cfg, int num_agents, uint32_t env_seed, int n, float base_episode_len, void *record)
+{
+    auto h = std::make_unique<HostDraw>();
+    GenState st{env_seed, 1, 1, 0};
+    for (int i = 0; i < n; ++i) obstacles_draw_host1(scenario, cfg, st, *h, num_agents, base_episode_len, *static_cast<EpisodeBlob *>(record), nullptr);
+}
+
 }  // namespace mv
 
 using namespace mv;
@@ -250,24 +249,6 @@ static bool obstacles_scenario(const char *name, int &scenario, ObstacleConfig &
 }
 
 extern "C" {
-
-// Host-only test hook (no device needed): the n-th episode of an env seeded with `env_seed` as mv_obstacles_draw.h's code generates it ON THE HOST -- the
-// same record mv_debug_generate_episode(scenario, ...) returns (its `seq` is n here, 0 there).
-int mv_debug_obstacles_draw_host(const char *scenario_name, int32_t num_agents, int32_t env_seed, int32_t n, float base_episode_len, void *out, int32_t out_bytes)
-{
-    int scenario = SCN_TOWER;
-    ObstacleConfig oc;
-    if (!obstacles_scenario(scenario_name, scenario, oc)) return fail("mv_debug_obstacles_draw_host: the Obstacles family and Empty");
-    if (!out) return (int)sizeof(EpisodeBlob);
-    if (num_agents < 1 || num_agents > MAX_AGENTS || n < 1) return fail("mv_debug_obstacles_draw_host: bad arguments");
-    if ((size_t)out_bytes < sizeof(EpisodeBlob)) return fail("mv_debug_obstacles_draw_host: buffer too small");
-    auto h = std::make_unique<HostDraw>();
-    auto blob = std::make_unique<EpisodeBlob>();
-    cdraw::GenState st{(uint32_t)env_seed, 1, 1, 0};
-    for (int i = 0; i < n; ++i) obstacles_draw_host(scenario, oc, st, *h, num_agents, base_episode_len, *blob, nullptr);
-    std::memcpy(out, blob.get(), sizeof(EpisodeBlob));
-    return (int)sizeof(EpisodeBlob);
-}
 
 // Host-only test hook: how the n-th episode came about, on both sides.  out[0 .. 3]: the host generator's chain attempts, left turns, right turns and the
 // capacity flags (GEN_*) it raised for that episode; out[4 .. 7]: the same four of mv_obstacles_draw.h's code on the host.
@@ -289,55 +270,14 @@ int mv_debug_obstacles_draw_stats_host(const char *scenario_name, int32_t num_ag
     const ObstacleStats hs = scenario == SCN_EMPTY ? ObstacleStats{1, 0, 0} : obstacles_last_stats();
     out[0] = hs.attempts; out[1] = hs.left_turns; out[2] = hs.right_turns; out[3] = generator_overflow_take();
     auto h = std::make_unique<HostDraw>();
-    cdraw::GenState st{(uint32_t)env_seed, 1, 1, 0};
+    draw::GenState st{(uint32_t)env_seed, 1, 1, 0};
     odraw::Stats ds{0, 0, 0};
     for (int i = 0; i < n; ++i) {
         st.flags = 0;
-        obstacles_draw_host(scenario, oc, st, *h, num_agents, base_episode_len, *blob, &ds);
+        obstacles_draw_host1(scenario, oc, st, *h, num_agents, base_episode_len, *blob, &ds);
     }
     out[4] = ds.attempts; out[5] = ds.left_turns; out[6] = ds.right_turns; out[7] = st.flags;
     return 0;
-}
-
-// Test hook: `count` envs seeded with env_seeds[i], each drawing its first n episodes ON THE DEVICE (n launches of obstacles_draw_kernel); out receives the
-// envs' n-th episodes, count x sizeof(EpisodeBlob) bytes; *ms_per_launch (may be null) the mean time of a launch.
-int mv_debug_obstacles_draw_device(int32_t device, const char *scenario_name, int32_t num_agents, const int32_t *env_seeds, int32_t count, int32_t n,
-                                   float base_episode_len, void *out, int64_t out_bytes, float *ms_per_launch)
-{
-    int scenario = SCN_TOWER;
-    ObstacleConfig oc;
-    if (!obstacles_scenario(scenario_name, scenario, oc)) return fail("mv_debug_obstacles_draw_device: the Obstacles family and Empty");
-    if (num_agents < 1 || num_agents > MAX_AGENTS || n < 1 || count < 1 || !env_seeds || !out) return fail("mv_debug_obstacles_draw_device: bad arguments");
-    if ((size_t)out_bytes < (size_t)count * sizeof(EpisodeBlob)) return fail("mv_debug_obstacles_draw_device: buffer too small");
-    HIP_TRY(hipSetDevice(device));
-    std::vector<cdraw::GenState> st((size_t)count);
-    for (int i = 0; i < count; ++i) st[(size_t)i] = cdraw::GenState{(uint32_t)env_seeds[i], 1, 1, 0};
-    cdraw::GenState *dSt = nullptr;
-    uint8_t *dSlots = nullptr;
-    uint32_t *dGrids = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const size_t bytes = (size_t)count * sizeof(EpisodeBlob);
-    const int regions = obstacles_draw_regions(scenario, count);
-    bool ok = hipMalloc((void **)&dSt, (size_t)count * sizeof(cdraw::GenState)) == hipSuccess && hipMalloc((void **)&dSlots, bytes) == hipSuccess &&
-              (regions == 0 || hipMalloc((void **)&dGrids, (size_t)regions * obstacles_draw_region_bytes()) == hipSuccess) &&
-              hipMemset(dSlots, 0, bytes) == hipSuccess &&
-              hipMemcpy(dSt, st.data(), (size_t)count * sizeof(cdraw::GenState), hipMemcpyHostToDevice) == hipSuccess &&
-              hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-    if (ok) {
-        ok = hipEventRecord(e0, nullptr) == hipSuccess;
-        for (int i = 0; i < n && ok; ++i)
-            launch_obstacles_draw(dSt, nullptr, count, dSlots, sizeof(EpisodeBlob), scenario, oc, num_agents, base_episode_len, dGrids, regions, nullptr, nullptr);
-        ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-             hipMemcpy(out, dSlots, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-        float ms = 0.0f;
-        if (ok && ms_per_launch && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *ms_per_launch = ms / float(n);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (dSt) (void)hipFree(dSt);
-    if (dSlots) (void)hipFree(dSlots);
-    if (dGrids) (void)hipFree(dGrids);
-    return ok ? 0 : fail("mv_debug_obstacles_draw_device: a HIP call failed");
 }
 
 }  // extern "C"

@@ -34,6 +34,7 @@ enum : int {
     DRAW_OBSTACLES,   // obstacles_draw_kernel over its grid regions (mv_obstacles_draw.h), for the configurations odraw::config_fits holds
     DRAW_EMPTY,       // the same kernel's one-slab form: no grids, whatever the configuration
     DRAW_HEX,         // hex_draw_kernel (mv_hex_draw.h): HexMemory and HexExplore, no grids; the whole record travels
+    DRAW_COUNT        // (mv_draw.h: one row per kind -- launcher, host twin, record, regions, switch)
 };
 
 // the per-env state arrays of GymView a family has besides boxes, objects and agents, which every family has (mv_api.hip: the arena's one list)

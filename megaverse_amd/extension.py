@@ -90,13 +90,9 @@ SYMBOLS = [
     ("mv_debug_feeder_selftest", C.c_int, [C.c_char_p, _I, _I, _I, _I]),
     ("mv_debug_generate_sokoban", C.c_int, [_I, _I, _I, _F, _P, _I]),
     ("mv_debug_generate_football", C.c_int, [_I, _I, _I, _F, _P, _I]),
-    ("mv_debug_collect_draw_host", C.c_int, [_I, _I, _I, _F, _P, _I]),
-    ("mv_debug_collect_draw_device", C.c_int, [_I, _I, _P, _I, _I, _F, _P, C.c_int64, _P]),
-    ("mv_debug_obstacles_draw_host", C.c_int, [C.c_char_p, _I, _I, _I, _F, _P, _I]),
+    ("mv_debug_draw_host", C.c_int, [C.c_char_p, _I, _I, _I, _F, _P, _I]),
+    ("mv_debug_draw_device", C.c_int, [_I, C.c_char_p, _I, _P, _I, _I, _F, _P, C.c_int64, _P]),
     ("mv_debug_obstacles_draw_stats_host", C.c_int, [C.c_char_p, _I, _I, _I, _F, _P]),
-    ("mv_debug_obstacles_draw_device", C.c_int, [_I, C.c_char_p, _I, _P, _I, _I, _F, _P, C.c_int64, _P]),
-    ("mv_debug_hex_draw_host", C.c_int, [C.c_char_p, _I, _I, _I, _F, _P, _I]),
-    ("mv_debug_hex_draw_device", C.c_int, [_I, C.c_char_p, _I, _P, _I, _I, _F, _P, C.c_int64, _P]),
     ("mv_set_episode_log", C.c_int, [_P, _I]), ("mv_get_episode_log_capacity", C.c_int, [_P]), ("mv_flush_episode_log", C.c_int, [_P]),
     ("mv_episode_log_count", C.c_int, [_P, C.POINTER(_U), C.POINTER(_U)]), ("mv_drain_episode_log", C.c_int, [_P, _P, _I, C.POINTER(_U)]),
     ("mv_episode_log_records_device_ptr", _P, [_P]), ("mv_episode_log_count_device_ptr", _P, [_P]),

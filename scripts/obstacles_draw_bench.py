@@ -2,7 +2,7 @@
 """What drawing the Obstacles family's episodes on the device costs and buys (megaverse_amd/csrc/mv_obstacles_draw.h, MV_OBSTACLES_DEVICE_GEN=1).  Needs a GPU;
 reads nothing outside the tree but --parent.
 
-  draws    obstacles_draw_kernel alone (mv_debug_obstacles_draw_device): ms per launch of --envs episodes and episodes per second, ObstaclesEasy and
+  draws    obstacles_draw_kernel alone (mv_debug_draw_device): ms per launch of --envs episodes and episodes per second, ObstaclesEasy and
            ObstaclesHard, --runs runs of 3 launches each (HIP events around the launches); min, median and max over the runs.
   seed     mv_seed_envs_host of ALL --envs ObstaclesEasy envs, host-fed against device-fed (this tree, the switch set before the gym is made): every call timed
            on its own with the host's clock, the device idle before it, from the call to the end of a synchronise behind it (scripts/seed_envs_bench.py's
@@ -30,7 +30,7 @@ sys.path.insert(0, ROOT)
 SIZE = 128
 HEADER = """# Obstacles-family episodes drawn on the device (obstacles_draw_kernel, MV_OBSTACLES_DEVICE_GEN=1) on one MI355X, written by scripts/obstacles_draw_bench.py:
 # one JSON line per figure.
-# what = draws: mv_debug_obstacles_draw_device, {envs} env seeds, 1 agent; one run = 3 launches of {envs} episodes between two HIP events, ms = the mean launch
+# what = draws: mv_debug_draw_device, {envs} env seeds, 1 agent; one run = 3 launches of {envs} episodes between two HIP events, ms = the mean launch
 #   of the run; min / median / max over the runs of the line.  A launch of {envs} episodes has 256 waves draw 4 episodes each (one grid region per wave).
 # what = seed: ONE mv_seed_envs_host call naming all {envs} ObstaclesEasy envs, {size} x {size}, timed on its own with the host's clock from the call to the end
 #   of a synchronise behind it, the device idle before it; every call gets fresh seeds and is followed by one untimed step.  mean / min over the calls.
@@ -49,14 +49,14 @@ def bench_draws(args, emit):
     import numpy as np
     from megaverse_amd import extension as ext
     lib = ext.load_library()
-    record = lib.mv_debug_obstacles_draw_host(b"ObstaclesHard", 1, 0, 1, 60.0, None, 0)
+    record = lib.mv_debug_draw_host(b"ObstaclesHard", 1, 0, 1, 60.0, None, 0)
     seeds = (np.arange(args.envs, dtype=np.int64) * 7919 + 13).astype(np.int32)
     out = np.zeros(args.envs * record, np.uint8)
     ms = np.zeros(1, np.float32)
     for name in ("ObstaclesEasy", "ObstaclesHard"):
         runs = []
         for r in range(args.runs + 1):
-            rc = lib.mv_debug_obstacles_draw_device(0, name.encode(), 1, seeds.ctypes.data, args.envs, 3, 60.0, out.ctypes.data, out.nbytes, ms.ctypes.data)
+            rc = lib.mv_debug_draw_device(0, name.encode(), 1, seeds.ctypes.data, args.envs, 3, 60.0, out.ctypes.data, out.nbytes, ms.ctypes.data)
             if rc != 0:
                 emit({"what": "draws", "scenario": name, "failed": rc})
                 return False   # (a failed HIP call can be a device fault: nothing more is started on this GPU)

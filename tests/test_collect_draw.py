@@ -1,4 +1,4 @@
-"""The Collect generator that runs on the device (megaverse_amd/csrc/mv_collect_draw.h), compiled for the CPU (mv_debug_collect_draw_host: no GPU involved),
+"""The Collect generator that runs on the device (megaverse_amd/csrc/mv_collect_draw.h), compiled for the CPU (mv_debug_draw_host: no GPU involved),
 against the product's host generator (mv_gen_collect.cpp through mv_debug_generate_episode, which test_host_generators.py holds against the oracle and
 test_oracle_collect.py against the reference's perlin_noise.hpp): the same env seed -> byte-identical episodes -- slabs, height map, spawn cells and rotations,
 movable boxes, diamonds and their values, colours, episode length -- over consecutive episodes of one env's stream.  The host generator draws through
@@ -7,17 +7,12 @@ pinned (the unstable std::sort's order of equal keys decides which cells the dia
 import numpy as np
 import pytest
 
-from megaverse_amd import extension as ext
-from test_host_generators import COLLECT_BLOB, generate
+import draw_util
+from test_host_generators import generate
 
 
 def draw_host(agents, env_seed, n, base_len=60.0):
-    lib = ext.load_library()
-    size = lib.mv_debug_collect_draw_host(agents, env_seed, n, base_len, None, 0)
-    assert size == COLLECT_BLOB.itemsize
-    buf = np.zeros(1, COLLECT_BLOB)
-    assert lib.mv_debug_collect_draw_host(agents, env_seed, n, base_len, buf.ctypes.data, size) == size
-    return buf[0]
+    return draw_util.draw_host("Collect", agents, env_seed, n, base_len)
 
 
 def assert_same_episode(got, want, agents, what):

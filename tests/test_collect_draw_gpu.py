@@ -5,22 +5,16 @@ mid-run, batched calls with the host far ahead."""
 import numpy as np
 import pytest
 
+import draw_util
 from hip_util import diff_snapshots, hip_snapshot, make_pair, set_same_actions
-from megaverse_amd import extension as ext
 from test_collect_draw import assert_same_episode
-from test_host_generators import COLLECT_BLOB, generate
+from test_host_generators import generate
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(900)]
 
 
 def draw_device(agents, seeds, n, base_len=60.0):
-    lib = ext.load_library()
-    seeds = np.asarray(seeds, np.int32)
-    out = np.zeros(len(seeds), COLLECT_BLOB)
-    ms = np.zeros(1, np.float32)
-    rc = lib.mv_debug_collect_draw_device(0, agents, seeds.ctypes.data, len(seeds), n, base_len, out.ctypes.data, out.nbytes, ms.ctypes.data)
-    assert rc == 0, ext.last_error() if hasattr(ext, "last_error") else rc
-    return out, float(ms[0])
+    return draw_util.draw_device("Collect", agents, seeds, n, base_len)
 
 
 @pytest.mark.parametrize("agents,n", [(1, 1), (2, 3), (8, 2)])

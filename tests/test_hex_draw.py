@@ -1,26 +1,17 @@
-"""HexMemory's and HexExplore's generator that runs on the device (megaverse_amd/csrc/mv_hex_draw.h), compiled for the CPU (mv_debug_hex_draw_host: no GPU
+"""HexMemory's and HexExplore's generator that runs on the device (megaverse_amd/csrc/mv_hex_draw.h), compiled for the CPU (mv_debug_draw_host: no GPU
 involved, the parallel phases in their serial form), against the product's host generator (mv_gen_hex.cpp through mv_debug_generate_episode, which
 test_host_generators.py holds against the oracle): the same env seed -> the same record, field for field -- the header, the first num_agents spawn points and
 rotations, objs[:num_objs], boxes[:num_boxes] -- over consecutive episodes of one env's stream."""
 import numpy as np
 import pytest
 
-from megaverse_amd import extension as ext
-from test_host_generators import HEX_BLOB, generate
+from draw_util import draw_host
+from test_host_generators import generate
 
 NAMES = ["HexMemory", "HexExplore"]
 # 0, 1, 42, the largest seed, and 196 drawn once from np.random.default_rng(20261)
 SEEDS = [0, 1, 42, (1 << 30) - 1] + [int(s) for s in np.random.default_rng(20261).integers(0, 1 << 30, 196)]
 HEADER = ("num_boxes", "num_colliders", "num_objs", "num_good", "episode_len", "target")
-
-
-def draw_host(name, agents, env_seed, n, base_len=60.0):
-    lib = ext.load_library()
-    size = lib.mv_debug_hex_draw_host(name.encode(), agents, env_seed, n, base_len, None, 0)
-    assert size == HEX_BLOB.itemsize, size
-    buf = np.zeros(1, HEX_BLOB)
-    assert lib.mv_debug_hex_draw_host(name.encode(), agents, env_seed, n, base_len, buf.ctypes.data, size) == size
-    return buf[0]
 
 
 def assert_same_episode(got, want, agents, what):

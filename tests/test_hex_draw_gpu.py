@@ -4,10 +4,10 @@ auto-resets, forced resets and a re-seed in mid-run, batched calls with the host
 import numpy as np
 import pytest
 
+from draw_util import draw_device
 from hip_util import diff_snapshots, hip_snapshot, make_pair, set_same_actions
-from megaverse_amd import extension as ext
 from test_hex_draw import NAMES, assert_same_episode
-from test_host_generators import HEX_BLOB, generate
+from test_host_generators import generate
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(900)]
 
@@ -31,11 +31,8 @@ def same_state(og, hg, N, A, tag):
 @pytest.mark.parametrize("agents,n", [(1, 1), (4, 2), (8, 3)])
 @pytest.mark.parametrize("name", NAMES)
 def test_kernel_draws_the_host_generators_episodes(hip, seeds, name, agents, n):
-    arr = np.asarray(seeds, np.int32)
-    got, ms = np.zeros(len(arr), HEX_BLOB), np.zeros(1, np.float32)
-    rc = ext.load_library().mv_debug_hex_draw_device(0, name.encode(), agents, arr.ctypes.data, len(arr), n, 60.0, got.ctypes.data, got.nbytes, ms.ctypes.data)
-    assert rc == 0, rc
-    print(f"hex_draw_kernel {name}: {len(arr)} episodes per launch, {float(ms[0]):.2f} ms per launch")
+    got, ms = draw_device(name, agents, seeds, n)
+    print(f"hex_draw_kernel {name}: {len(seeds)} episodes per launch, {ms:.2f} ms per launch")
     for i, s in enumerate(seeds):
         assert got[i]["seq"] == n, (s, got[i]["seq"])
         assert_same_episode(got[i], generate(name, agents, s, n), agents, (name, s, n))

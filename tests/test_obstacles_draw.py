@@ -1,13 +1,14 @@
 """The Obstacles family's and Empty's generator that runs on the device (megaverse_amd/csrc/mv_obstacles_draw.h), compiled for the CPU
-(mv_debug_obstacles_draw_host: no GPU involved), against the product's host generator (mv_gen_obstacles.cpp through mv_debug_generate_episode, which
+(mv_debug_draw_host: no GPU involved), against the product's host generator (mv_gen_obstacles.cpp through mv_debug_generate_episode, which
 test_host_generators.py holds against the oracle): the same env seed -> byte-identical episodes -- merged slabs, terrain, movable boxes, reward objects, spawn
 cells and rotations, colours, episode length -- over consecutive episodes of one env's stream.  The host generator keeps its chain in std::vector / std::map /
 std::set and draws through libstdc++; the device code keeps it in fixed arrays and two bit planes, so this is where the restatement is pinned."""
 import numpy as np
 import pytest
 
+from draw_util import draw_host
 from megaverse_amd import extension as ext
-from test_host_generators import EPISODE_BLOB, generate
+from test_host_generators import generate
 
 NAMES = ["ObstaclesEasy", "ObstaclesMedium", "ObstaclesHard", "ObstaclesWalls", "ObstaclesSteps", "ObstaclesLava", "Empty"]
 # The committed seed set: the four corner values, 40 drawn once from np.random.default_rng(20260) and two added by a search over the host generator
@@ -16,15 +17,6 @@ NAMES = ["ObstaclesEasy", "ObstaclesMedium", "ObstaclesHard", "ObstaclesWalls", 
 CLASH_SEEDS = [28, 67]
 SEEDS = [0, 1, 42, (1 << 30) - 1] + [int(s) for s in np.random.default_rng(20260).integers(0, 1 << 30, 40)] + CLASH_SEEDS
 GEN_FLAG_NAMES = {1: "GEN_SLABS", 2: "GEN_TERRAIN", 4: "GEN_OBJECTS", 8: "GEN_REWARDS", 16: "GEN_COORDS"}
-
-
-def draw_host(name, agents, env_seed, n, base_len=60.0):
-    lib = ext.load_library()
-    size = lib.mv_debug_obstacles_draw_host(name.encode(), agents, env_seed, n, base_len, None, 0)
-    assert size == EPISODE_BLOB.itemsize, (size, ext.last_error() if hasattr(ext, "last_error") else "")
-    buf = np.zeros(1, EPISODE_BLOB)
-    assert lib.mv_debug_obstacles_draw_host(name.encode(), agents, env_seed, n, base_len, buf.ctypes.data, size) == size
-    return buf[0]
 
 
 def draw_stats(name, agents, env_seed, n, base_len=60.0):

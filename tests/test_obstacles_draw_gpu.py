@@ -5,25 +5,16 @@ resets with level seeds, a group of four scenarios."""
 import numpy as np
 import pytest
 
+from draw_util import draw_device
 from hip_util import diff_snapshots, hip_snapshot, make_pair, set_same_actions
 from megaverse_amd import extension as ext
-from test_host_generators import EPISODE_BLOB, generate
+from test_host_generators import generate
 from test_obstacles_draw import CLASH_SEEDS, assert_same_episode, draw_stats
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(900)]
 
 # env seeds whose first ObstaclesHard episode turns left AND right (found on the CPU, test_obstacles_draw.py's hook: the widest grids), beside the clash seeds
 TWO_TURN_SEEDS = [0, 3, 4, 5]
-
-
-def draw_device(name, agents, seeds, n, base_len=60.0):
-    lib = ext.load_library()
-    seeds = np.asarray(seeds, np.int32)
-    out = np.zeros(len(seeds), EPISODE_BLOB)
-    ms = np.zeros(1, np.float32)
-    rc = lib.mv_debug_obstacles_draw_device(0, name.encode(), agents, seeds.ctypes.data, len(seeds), n, base_len, out.ctypes.data, out.nbytes, ms.ctypes.data)
-    assert rc == 0, ext.last_error() if hasattr(ext, "last_error") else rc
-    return out, float(ms[0])
 
 
 def test_the_seed_set_holds_what_it_is_chosen_for():
