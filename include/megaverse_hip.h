@@ -472,6 +472,30 @@ int mv_get_normal_obs(const mv_gym *g);                              /* 0: none,
 int mv_get_normal_format(const mv_gym *g);                           /* MV_NORMAL_*; -1: none attached */
 int mv_get_normal_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, float *out_host);   /* [H][W][4] float32; waits for the gym's stream */
 int mv_debug_normal_pack_host(const float *xyz, const uint8_t *hit, int32_t n, int32_t format, void *out);   /* the pack function, on the host */
+/* Visible-entity observations (no reference counterpart): what each AGENT sees of the entity rows.  The entity rows (mv_set_entity_obs) list every object,
+ * seen or not; the instance label plane (mv_set_seg_obs with MV_SEG_INSTANCE_U16) says what every pixel shows.  This record joins them on the device: per
+ * drawn frame E = mv_entity_obs_rows rows of MV_VISIBLE_OBS_INTS = 5 int32, [N*A][E][5]; row r = {count, x_min, x_max, y_min, y_max} over the pixels of the
+ * frame's label plane whose word names entity row r -- its class names the row's group, base + instance the row (mv_entity_obs_layout); Sokoban's compacted
+ * EXIT group is resolved from the env's goal cells (row k: the k-th goal cell in ascending x * 32 + z; the word's instance: x * W + z).  The bounds are
+ * inclusive pixel coordinates, row 0 the bottom row as in the plane; a row with count 0 is five zeros.  megaverse_amd/csrc/mv_visible_obs.h states the rule
+ * for the kernel and the host alike.  The values are whatever the plane holds: the labels' caveat for frames whose env begins a new episode later in the same
+ * batched call carries over, and Sokoban's goal cells are read when the launch runs, as the labels' group boundaries are.
+ * mv_set_visible_obs: device_buf is int32 [entries][N*A][E][5], 4-byte aligned, entries = the output ring's count at the moment of the call, or 1; a frame's
+ * rows go to the entry the frame goes to.  It needs an instance-format label plane attached and is refused without one; while it is attached, detaching the
+ * label plane or changing its format is refused.  Otherwise a plane stream's rules: every pass that draws frames is followed by ONE launch per drawn tick,
+ * on the gym's stream behind whatever wrote the tick's labels (the exact pass, or the planes' follower; counted in out[1] of mv_debug_launch_counts), with
+ * no host wait; no byte where no frame is drawn (mv_step_no_render, MV_RENDER_NONE, draw-masked envs); the call is an ordering point; NULL detaches;
+ * mv_close forgets the pointer; refused for the gyms of an mv_group or an mv_step_many call, and mv_set_output_ring / mv_set_render_resolution are refused
+ * while it is attached (still frames exclude the label plane it needs).  A gym without it launches exactly what it launched.
+ * mv_get_visible_observation: one agent's [E][5] rows in the LAST TICK's entry, after waiting for the gym's stream.  mv_debug_visible_host: the rule on the
+ * CPU: one plane's words [h][w] -> [E][5] for a scenario family (SCN_* id) and an agent count; room_w and soko_cells (1024 bytes) are read for Sokoban
+ * only; no device. */
+enum { MV_VISIBLE_OBS_INTS = 5 };   /* count, x_min, x_max, y_min, y_max */
+int mv_set_visible_obs(mv_gym *g, void *device_buf);      /* int32 [max(1, ring count)][N*A][E][5] in device memory; NULL detaches */
+int mv_get_visible_obs(const mv_gym *g);                  /* 0: none, else the number of entries; -1: no gym */
+int mv_get_visible_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, int32_t *out_host);   /* [E][5] int32; waits for the gym's stream */
+int mv_debug_visible_host(int32_t scenario, int32_t num_agents, int32_t room_w, const uint8_t *soko_cells, const uint16_t *words, int32_t w, int32_t h,
+                          int32_t *out);                  /* the rule on the CPU, no device */
 /* Episode budgets (no reference counterpart: VectorEnv::step resets a finished env on the spot and steps on, vector_env.cpp:89-108).  Per env e the gym owns an
  * int32 left[e]:  < 0: unlimited -- what every env is without these calls;  > 0: the env may still finish that many episodes;  0: the env is HALTED.
  * Tick t, env e, left[e] as it stands before the tick (megaverse_amd/csrc/mv_episode_budget.h states the rule for kernels and host alike):

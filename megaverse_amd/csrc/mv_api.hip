@@ -128,6 +128,7 @@ OutPtrs outputs_of(const mv_gym *g, unsigned long long tick)
     o.depth = g->depth.entry(tick);   // (mv_set_depth_obs: attached under this ring count, or under none: entry 0)
     o.seg = g->seg.entry(tick);       // (mv_set_seg_obs: the same)
     o.normal = g->normal.entry(tick); // (mv_set_normal_obs: the same)
+    o.visible = g->visible.entry(tick);   // (mv_set_visible_obs: the same)
     return o;
 }
 OutPtrs last_outputs(const mv_gym *g) { return outputs_of(g, g->ringTick ? g->ringTick - 1 : 0); }   // of the last tick (reset / render / getters)
@@ -747,6 +748,7 @@ int mv_close(mv_gym *g)
     env_masks_free(g);
     obs_rows_free(g);
     obs_planes_free(g);
+    visible_obs_free(g);
     episode_budget_free(g);
     macro_step_free(g);
     still_frames_free(g);
@@ -925,6 +927,7 @@ int mvapi::render_frames(mv_gym *g)
     if (launch_raster(v, o.obs, g->w, g->h, g->stream, nullptr, g->fastPixels, 0, nullptr, nullptr, g->fastPixels ? nullptr : &po))
         return fail("mv_render: observation size above 1024x1024");
     if (g->fastPixels && planes_follow(g, v, o, "mv_render") < 0) return -1;
+    if (visible_follow(g, v, o) < 0) return -1;   // (mv_set_visible_obs: behind the frame's label planes, whichever launch wrote them)
     HIP_TRY(hipGetLastError());
     return 0;
 }

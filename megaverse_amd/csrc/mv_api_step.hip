@@ -47,6 +47,7 @@ struct StepCall {
     bool overlap;             // the one pass launch goes to a pass stream (mv_set_pass_overlap): passOn
     bool rows, carry, depth;  // followers: the row records' publication, the still frames' carry, the depth, label and normal planes behind fast passes -- ONE launch per
                               // drawn tick for whichever of the three are attached (the log: per gym, logCapacity)
+    bool visible;             // ... and the visible-entity rows behind the label planes of a drawn tick, in either pixel mode (mv_set_visible_obs)
     bool timeCall, timeTicks;   // timing (mv_profile_begin): ONE entry for the whole call (callEv), or one per tick for the first tickEvs ticks (tickEv);
     hipEvent_t *callEv = nullptr, *tickEv = nullptr;   // reserve_timing takes the entries, behind the checks and the refill as always
     int tickEvs = 0;
@@ -133,6 +134,9 @@ struct StepCall {
         // pass stores the planes itself, one_pass; a group's members have none)
         // (mv_set_seg_obs, mv_set_normal_obs: the same follower, which then stores every attached plane)
         depth = n == 1 && any_planes_on(L) && L->fastPixels != 0 && (r.render || drawLast);
+        // (mv_set_visible_obs, either pixel mode: one launch per drawn tick behind the tick's label planes; no overlapped passes either -- fast pixels: the labels'
+        // follower rules them out already, exact pixels: PASS_BATCH is not taken)
+        visible = n == 1 && L->visible.buf != nullptr && (r.render || drawLast);
         // overlapped passes (mv_set_pass_overlap): this call's one launch goes to an internal stream
         // (an env must not finish in two consecutive calls: their passes may publish its true objective in either order -- episodes of at least
         // baseEpisodeLen seconds, 15 ticks each)
@@ -505,8 +509,16 @@ struct StepCall {
                 if (rc < 0) return -1;
                 L->launchCount[1] += rc;
             }
+        // the visible-entity rows (mv_set_visible_obs): one launch per drawn tick behind the tick's label planes -- the exact pass's own, or the follower's above --
+        // into the entry the tick's frames went to; it reads the tick's list lengths from the call's slots (which frames were drawn)
+        if (visible)
+            for (int j = r.render ? 0 : k - 1; j < k; ++j) {
+                const int rc = visible_follow(L, views[(size_t)j], outs[(size_t)j]);
+                if (rc < 0) return -1;
+                L->launchCount[1] += rc;
+            }
         if (mc && mc->last) ++L->ringTick;
-        if ((anyLog || rows || carry || depth) && own) HIP_TRY(hipEventRecord(mark(), L->stream));
+        if ((anyLog || rows || carry || depth || visible) && own) HIP_TRY(hipEventRecord(mark(), L->stream));
         if (own) {
             ++L->markCount;
             for (int i = 0; i < n; ++i) gs[i]->markCount = L->markCount;

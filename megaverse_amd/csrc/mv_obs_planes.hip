@@ -62,6 +62,10 @@ int planes_attach(mv_gym *g, const Planes &rec, void *device_buf, int format)
     const std::string who = rec.opt().setter;
     if (attach_check(g, rec.opt().setter, rec.opt())) return -1;
     ObsPlanes &p = g->*rec.planes;
+    // (mv_set_visible_obs counts its rows in the instance-format label planes: they stay as they are while it is attached)
+    if (rec.planes == &mv_gym::seg && g->visible.buf && (!device_buf || format != SEG_INSTANCE_U16))
+        return fail(who + ": " + obs_stream(OPT_VISIBLE_OBS).noun + " are attached (" + gym_options[OPT_VISIBLE_OBS].setter
+                    + "), which are counted in the instance-format label planes: detach the " + obs_stream(OPT_VISIBLE_OBS).noun + " first");
     if (!device_buf) {
         // No launch, no copy: the launches enqueued so far keep the pointers they were given; the next pass writes no plane.
         p = ObsPlanes();

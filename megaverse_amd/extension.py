@@ -126,6 +126,8 @@ SYMBOLS = [
     ("mv_get_seg_observation", C.c_int, [_P, _I, _I, _P]), ("mv_seg_class_name", C.c_char_p, [_I]),
     ("mv_debug_seg_bounds_host", C.c_int, [_I, _I, _I, _I, _I, _I, _I, _I, _P]), ("mv_debug_seg_rule_host", C.c_int, [_I, _I, _P, _I, _I, _P]),
     ("mv_debug_seg_pack_host", C.c_int, [_P, _P, _I, _I, _P]),
+    ("mv_set_visible_obs", C.c_int, [_P, _P]), ("mv_get_visible_obs", C.c_int, [_P]), ("mv_get_visible_observation", C.c_int, [_P, _I, _I, _P]),
+    ("mv_debug_visible_host", C.c_int, [_I, _I, _I, _P, _P, _I, _I, _P]),
     ("mv_set_overview", C.c_int, [_P, _I, _I, _P]), ("mv_set_overview_cameras", C.c_int, [_P, _P]), ("mv_set_overview_cameras_host", C.c_int, [_P, _P]),
     ("mv_get_overview_observation", C.c_int, [_P, _I, _P]), ("mv_overview_device_ptr", _P, [_P]), ("mv_overview_dropped", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("mv_overview_capacity", C.c_int, [_P]), ("mv_overview_default_camera", C.c_int, [_P]), ("mv_debug_overview_camera_host", C.c_int, [_P, _P, _P]),
@@ -514,6 +516,30 @@ def entity_row_of(words, scenario, num_agents):
     for c, (base, rows) in by_class.items():
         hit = (cls == c) & (inst < rows)
         out[hit] = (base + inst[hit]).to(out.dtype) if not is_np else (base + inst[hit]).astype(out.dtype)
+    return out
+
+
+# include/megaverse_hip.h: MV_VISIBLE_OBS_INTS and the columns of a visible-entity row (mv_set_visible_obs; megaverse_amd/csrc/mv_visible_obs.h has the rule):
+# how many pixels of one agent's frame show the entity of that row, and their inclusive pixel bounds (row 0 is the bottom row); five zeros: not in view
+MV_VISIBLE_OBS_INTS = 5
+VISIBLE_OBS_FIELDS = {name: i for i, name in enumerate(("count", "x_min", "x_max", "y_min", "y_max"))}
+
+
+def debug_visible_host(scenario, num_agents, words, room_w=0, soko_cells=None):
+    """mv_debug_visible_host: the visible-entity rule on the CPU (no device): the words of one 'instance' label plane, uint16 [h, w], for a scenario (name or
+    SCN_* family id) and an agent count -> the frame's rows, int32 [E, 5] (VISIBLE_OBS_FIELDS).  Sokoban reads room_w (the room's width in cells) and
+    soko_cells (its 1024 cell bytes, [x * 32 + z]) to place the goal pads' rows"""
+    lib = load_library()
+    words = np.ascontiguousarray(words, np.uint16)
+    if words.ndim != 2:
+        raise ValueError("debug_visible_host: words must be a plane [h, w]")
+    cells = None if soko_cells is None else np.ascontiguousarray(soko_cells, np.uint8).ravel()
+    if cells is not None and cells.size != 1024:
+        raise ValueError("debug_visible_host: soko_cells is 1024 bytes")
+    out = np.empty((entity_rows(scenario, num_agents), MV_VISIBLE_OBS_INTS), np.int32)
+    if lib.mv_debug_visible_host(scenario_family(scenario), int(num_agents), int(room_w), None if cells is None else cells.ctypes.data, words.ctypes.data,
+                                 int(words.shape[1]), int(words.shape[0]), out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
     return out
 
 
@@ -920,6 +946,12 @@ def check_entity_obs(buf, entries, num_envs, rows, device):
     return _check_obs_tensor(buf, entries, (int(num_envs), int(rows), MV_ENTITY_OBS_FLOATS), OBS_STREAMS['entity'].dtypes(None), device, 'set_entity_obs')
 
 
+def check_visible_obs(buf, entries, num_frames, rows, device):
+    """the argument check of MegaverseGym.set_visible_obs for a tensor: contiguous torch.int32 of shape (entries, num_frames, rows, 5) on CUDA device `device`;
+    entries None: any number of entries (the check made before the gym is asked for its ring count)"""
+    return _check_obs_tensor(buf, entries, (int(num_frames), int(rows), MV_VISIBLE_OBS_INTS), OBS_STREAMS['visible'].dtypes(None), device, 'set_visible_obs')
+
+
 def _check_obs_tensor(buf, entries, tail, dtypes, device, who):
     """the one tensor check of the observation streams, for the setter `who`: contiguous, one of `dtypes` (torch dtype names), of shape (entries,) + tail on
     CUDA device `device`; entries None: any number of entries (the check made before the gym is asked for its ring count) -> buf"""
@@ -935,7 +967,7 @@ def _check_obs_tensor(buf, entries, tail, dtypes, device, who):
     return buf
 
 
-# The six per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
+# The seven per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
 # of the gym (a read-back's row is that shape without its first extent), format -> the torch dtype names a tensor may have (the first: what True allocates),
 # the arguments behind the null pointer of a detach, the numpy dtype a read-back hands out.  A new stream is one row here.
 _ObsStream = collections.namedtuple('_ObsStream', 'setter reader tail dtypes detach read')
@@ -952,6 +984,9 @@ OBS_STREAMS = {
                       lambda fmt: ('torch.int16', 'torch.uint16') if int(fmt) == MV_SEG_INSTANCE_U16 else ('torch.uint8',), (MV_SEG_CLASS_U8,), np.uint16),
     'normal': _ObsStream('mv_set_normal_obs', 'mv_get_normal_observation', lambda g: (g.num_envs * g.num_agents_per_env, g.h, g.w, 4),
                          lambda fmt: ('torch.int8',) if int(fmt) == MV_NORMAL_SNORM8 else ('torch.float16',), (MV_NORMAL_F16,), np.float32),
+    'visible': _ObsStream('mv_set_visible_obs', 'mv_get_visible_observation',
+                          lambda g: (g.num_envs * g.num_agents_per_env, entity_rows(g.scenario, g.num_agents_per_env), MV_VISIBLE_OBS_INTS),
+                          lambda fmt: ('torch.int32',), (), np.int32),
 }
 
 
@@ -1724,6 +1759,29 @@ class MegaverseGym:
     def get_normal_observation(self, env_idx, agent_idx):
         """-> numpy float32 [H, W, 4]: the normal plane of one agent in the last tick's entry, widened (waits for the gym's stream)"""
         return self._read_obs('normal', env_idx, agent_idx)
+
+    def set_visible_obs(self, buf=True):
+        """Visible-entity observations (include/megaverse_hip.h: mv_set_visible_obs): what each agent sees of the entity rows.  Every frame a later observation
+        pass draws -- the passes set_depth_obs names -- leaves entity_rows() rows of 5 int32 per AGENT (VISIBLE_OBS_FIELDS: count, x_min, x_max, y_min, y_max
+        of the pixels of its 'instance' label plane that show the entity of that row, entity_row_of's rows with Sokoban's goal pads resolved; bounds
+        inclusive, row 0 the bottom row; five zeros: not in view) in entry t % entries of an int32 CUDA tensor [entries, num_envs * num_agents, E, 5],
+        entries = the output ring's count, or 1 without a ring.  Needs set_seg_obs(fmt='instance') first, and the label plane stays attached as it is while
+        this is.  True allocates the tensor on the gym's device and returns it; a tensor is checked (ValueError) and attached; None detaches.  One launch per
+        drawn tick behind the labels; nothing waits on the host.  While attached, set_output_ring and set_render_resolution are refused."""
+        return self._attach_obs('visible', buf)
+
+    def visible_obs_ring(self):
+        """-> the tensor set_visible_obs attached, [entries, num_envs * num_agents, E, 5] (entry t % entries: the rows of tick t's frames), or None"""
+        return self._obs.get('visible')
+
+    def visible_obs(self):
+        """-> the entry of the last tick, (num_envs * num_agents, E, 5): a view of the attached tensor, valid in the order of the gym's stream; None with
+        nothing attached.  A tick that drew no frame wrote nothing there.  With an output ring: the entry the last tick stepped through this object went to"""
+        return self._obs_last('visible')
+
+    def get_visible_observation(self, env_idx, agent_idx):
+        """-> numpy int32 [E, 5]: the visible-entity rows of one agent in the last tick's entry (waits for the gym's stream)"""
+        return self._read_obs('visible', env_idx, agent_idx)
 
     def get_state_observation(self, env_idx, agent_idx):
         """-> numpy float32 [16]: the last tick's row of one agent (waits for the gym's stream)"""

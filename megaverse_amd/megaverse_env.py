@@ -18,8 +18,8 @@ Differences, all additive:
 import numpy as np
 
 from . import spaces
-from .extension import ENTITY_OBS_FIELDS, MEGAVERSE8, MegaverseGym, SCENARIOS, SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS, STATE_OBS_FIELDS, render_mode_of, \
-    set_megaverse_log_level
+from .extension import ENTITY_OBS_FIELDS, MEGAVERSE8, MegaverseGym, SCENARIOS, SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS, STATE_OBS_FIELDS, VISIBLE_OBS_FIELDS, \
+    render_mode_of, set_megaverse_log_level
 
 OBSTACLES_MULTITASK = ['ObstaclesWalls', 'ObstaclesSteps', 'ObstaclesLava', 'ObstaclesEasy', 'ObstaclesHard']
 # what libmegaverse_hip.so can construct (mv_create): every scenario of the reference's multi-task sets, Empty, BoxAGone and Football
@@ -68,7 +68,7 @@ def check_sequence_actions(actions, num_agents):
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
                  img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1,
-                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False, overview=None, normal_obs=False):
+                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False, overview=None, normal_obs=False, visible_obs=False):
         if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
         # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
@@ -122,9 +122,15 @@ class MegaverseEnv:
             raise ValueError(f"normal_obs must be False, True, 'float16' or 'int8', got {normal_obs!r}")
         if seg_obs is not False and seg_obs is not True and seg_obs not in ("class", "instance"):
             raise ValueError(f"seg_obs must be False, True, 'class' or 'instance', got {seg_obs!r}")
+        #   visible_obs: every drawn frame leaves E rows of 5 int32 per AGENT (VISIBLE_OBS_FIELDS: how many pixels of its instance label plane show each entity
+        #     row, and their bounds; mv_set_visible_obs).  It counts in an 'instance' label plane: one is attached if seg_obs asks for none
+        if visible_obs:
+            if seg_obs in (True, "class"):
+                raise ValueError("visible_obs=True counts its rows in an 'instance' label plane: pass seg_obs='instance' (or leave seg_obs out), not 'class'")
+            seg_obs = "instance"
         wanted = (("state", state_obs, ()), ("scene", scene_obs, ()), ("entity", entity_obs, ()),
                   ("depth", depth_obs, ("float32" if depth_obs is True else depth_obs,)), ("seg", seg_obs, ("class" if seg_obs is True else seg_obs,)),
-                  ("normal", normal_obs, ("float16" if normal_obs is True else normal_obs,)))
+                  ("normal", normal_obs, ("float16" if normal_obs is True else normal_obs,)), ("visible", bool(visible_obs), ()))   # (behind "seg")
         self._streams = {name: args for name, on, args in wanted if on}
         if "state" in self._streams:
             self._attach_stream("state")
@@ -195,6 +201,14 @@ class MegaverseEnv:
         Needs MegaverseEnv(..., normal_obs=True | "int8")."""
         return self._stream_entry("normal", self.env.normal_obs_ring(), per_agent_planes=True)
 
+    VISIBLE_OBS_FIELDS = VISIBLE_OBS_FIELDS   # column name -> index of a visible_obs() row
+
+    def visible_obs(self):
+        """the last tick's visible-entity rows: int32 (num_envs, num_agents_per_env, E, 5) on the device, columns VISIBLE_OBS_FIELDS, rows as entity_obs()'s --
+        per agent, how many pixels of its frame show each entity and their inclusive bounds, five zeros for an entity out of view -- a view of the attached
+        buffer, under state_obs()'s rules: ask again after every call.  A tick that drew no frame wrote nothing.  Needs MegaverseEnv(..., visible_obs=True)."""
+        return self._stream_entry("visible", self.env.visible_obs_ring(), per_agent_planes=True)
+
     def _attach_stream(self, name, on=True):
         """one wanted stream's tensor attached (a new one, of the output ring's depth) or detached"""
         getattr(self.env, f"set_{name}_obs")(*((True,) + self._streams[name] if on else (None,)))
@@ -210,7 +224,7 @@ class MegaverseEnv:
     def _set_output_ring(self, count, *ptrs):
         """the env's own output rings change (step_device, step_sequence): every attached stream's buffer is one more ring of the same depth and the library
         refuses a ring change while one is attached, so they are detached around the change and buffers of the new depth attached -- the planes first"""
-        for name in self._streams:
+        for name in reversed(list(self._streams)):   # (the visible rows before the label plane they count in)
             self._attach_stream(name, on=False)
         self.env.set_output_ring(count, *ptrs)
         for name in sorted(self._streams, key=lambda name: name not in ("depth", "seg", "normal")):

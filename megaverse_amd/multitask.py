@@ -205,6 +205,10 @@ class MultiTaskGym:
         """entity observations (MegaverseGym.set_entity_obs) are per gym: a group's union launches write none, and the library refuses"""
         raise _per_gym("set_entity_obs", "entity observations", "write")
 
+    def set_visible_obs(self, buf=True):
+        """visible-entity observations (MegaverseGym.set_visible_obs) are per gym: a group's union launches write none, and the library refuses"""
+        raise _per_gym("set_visible_obs", "visible-entity observations", "write")
+
     def set_overview(self, w, h, buf=True):
         """overview cameras (MegaverseGym.set_overview) are per gym: a group's union launches draw none, and the library refuses"""
         raise _per_gym("set_overview", "an overview", "draw")
