@@ -496,6 +496,42 @@ int mv_get_visible_obs(const mv_gym *g);                  /* 0: none, else the n
 int mv_get_visible_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, int32_t *out_host);   /* [E][5] int32; waits for the gym's stream */
 int mv_debug_visible_host(int32_t scenario, int32_t num_agents, int32_t room_w, const uint8_t *soko_cells, const uint16_t *words, int32_t w, int32_t h,
                           int32_t *out);                  /* the rule on the CPU, no device */
+/* Map observations (no reference counterpart): an egocentric top-down grid per AGENT, binned on the device out of the frame's depth plane (mv_set_depth_obs,
+ * either format) and label plane (mv_set_seg_obs, either format).  Per drawn frame MV_MAP_OBS_PLANES = 3 planes of M x M int16, [N*A][3][M][M], M = cells, a
+ * cell being cell_size x cell_size world units of the ground plane.  The eye sits at the middle of the grid's bottom edge: row 0 is the nearest row, rows grow
+ * along the viewer's horizontal heading, columns along its right axis, column M/2 begins at lateral 0.  Every pixel whose depth t is not 0 and whose class is
+ * not HUD is unprojected with the camera the pass drew it with -- pc = (x t, y t, -t) for the pixel's ray (x, y, -1), d = c pc with the viewer's basis c of
+ * the frame, lateral u = d.x R.x + d.z R.z and forward f = d.x R.z - d.z R.x for the right axis R (no roll: R is horizontal and of length 1), height over the
+ * eye d.y -- and lands in col = floor(u / cell_size) + M/2, row = floor(f / cell_size); a pixel outside the grid is dropped.  Per cell:
+ *   plane 0  count: the pixels that fell in it, saturated at 32767
+ *   plane 1  height: the greatest floor(32 d.y) among them, clamped to [-32767, 32767] -- 1/32 world units over the eye
+ *   plane 2  class: the class of a pixel of that greatest height; among equals the greatest class
+ * and a cell no pixel fell in is three zeros.  Sums and maxima: the grids do not depend on any order and are reproducible byte for byte.
+ * megaverse_amd/csrc/mv_map_obs.h states the rule, with the order of its fp32 operations, for the kernel and the host alike.  The values are whatever the
+ * planes hold: the labels' caveat for frames whose env begins a new episode later in the same batched call carries over.
+ * mv_set_map_obs: device_buf is int16 [entries][N*A][3][M][M], 16-byte aligned, entries = the output ring's count at the moment of the call, or 1; cells is a
+ * multiple of 8 in [8, 64], cell_size a finite float > 0.  It needs depth observations AND segmentation observations attached and is refused without either;
+ * while it is attached, mv_set_depth_obs and mv_set_seg_obs are refused (the planes stay as they are).  Otherwise a plane stream's rules: every pass that draws
+ * frames is followed by ONE launch per drawn tick, on the gym's stream behind whatever wrote the tick's planes (the exact pass, or the planes' follower;
+ * counted in out[1] of mv_debug_launch_counts), with no host wait; no byte where no frame is drawn (mv_step_no_render, MV_RENDER_NONE, draw-masked envs); the
+ * call is an ordering point; NULL detaches (cells and cell_size are then not read); mv_close forgets the pointer; refused for the gyms of an mv_group or an
+ * mv_step_many call and beside still frames, and mv_set_output_ring / mv_set_render_resolution are refused while it is attached.  mv_draw_hires and the
+ * overview ignore it.  A gym without it launches exactly what it launched.
+ * mv_get_map_observation: one agent's [3][M][M] in the LAST TICK's entry, after waiting for the gym's stream.  mv_debug_map_host: the rule on the CPU for one
+ * frame: planes [h][w] of the given formats and cam12 = eye(3) c(9) (c row-major, columns right / up / back) -> out [3][cells][cells]; no device.
+ * mv_debug_map_device: the same arguments as DEVICE pointers (out 16-byte aligned): the very kernel on that one frame, on the current device's null stream,
+ * waited for.  mv_debug_map_camera: eye(3) c(9) of one agent's frame as the tick the latest map launch followed drew it; waits for the gym's stream. */
+enum { MV_MAP_OBS_PLANES = 3, MV_MAP_HEIGHT_SCALE = 32 };   /* count, height, class; height values per world unit */
+int mv_set_map_obs(mv_gym *g, void *device_buf, int32_t cells, float cell_size);   /* int16 [max(1, ring count)][N*A][3][cells][cells]; NULL detaches */
+int mv_get_map_obs(const mv_gym *g);                      /* 0: none, else the number of entries; -1: no gym */
+int mv_map_obs_cells(const mv_gym *g);                    /* M; 0: none attached */
+float mv_map_obs_cell_size(const mv_gym *g);              /* world units; 0: none attached */
+int mv_get_map_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, int16_t *out_host);   /* [3][M][M] int16; waits for the gym's stream */
+int mv_debug_map_host(const void *depth, int32_t depth_format, const void *seg, int32_t seg_format, int32_t w, int32_t h, const float *cam12, int32_t cells,
+                      float cell_size, int16_t *out);     /* the rule on the CPU, no device */
+int mv_debug_map_device(const void *depth, int32_t depth_format, const void *seg, int32_t seg_format, int32_t w, int32_t h, const float *cam12, int32_t cells,
+                        float cell_size, int16_t *out);   /* the kernel on one frame; every pointer a device pointer */
+int mv_debug_map_camera(mv_gym *g, int32_t env_idx, int32_t agent_idx, float out12[12]);   /* eye(3) c(9) of the latest drawn frame's header */
 /* Episode budgets (no reference counterpart: VectorEnv::step resets a finished env on the spot and steps on, vector_env.cpp:89-108).  Per env e the gym owns an
  * int32 left[e]:  < 0: unlimited -- what every env is without these calls;  > 0: the env may still finish that many episodes;  0: the env is HALTED.
  * Tick t, env e, left[e] as it stands before the tick (megaverse_amd/csrc/mv_episode_budget.h states the rule for kernels and host alike):

@@ -129,6 +129,7 @@ OutPtrs outputs_of(const mv_gym *g, unsigned long long tick)
     o.seg = g->seg.entry(tick);       // (mv_set_seg_obs: the same)
     o.normal = g->normal.entry(tick); // (mv_set_normal_obs: the same)
     o.visible = g->visible.entry(tick);   // (mv_set_visible_obs: the same)
+    o.map = g->map.entry(tick);           // (mv_set_map_obs: the same)
     return o;
 }
 OutPtrs last_outputs(const mv_gym *g) { return outputs_of(g, g->ringTick ? g->ringTick - 1 : 0); }   // of the last tick (reset / render / getters)
@@ -749,6 +750,7 @@ int mv_close(mv_gym *g)
     obs_rows_free(g);
     obs_planes_free(g);
     visible_obs_free(g);
+    map_obs_free(g);
     episode_budget_free(g);
     macro_step_free(g);
     still_frames_free(g);
@@ -928,6 +930,7 @@ int mvapi::render_frames(mv_gym *g)
         return fail("mv_render: observation size above 1024x1024");
     if (g->fastPixels && planes_follow(g, v, o, "mv_render") < 0) return -1;
     if (visible_follow(g, v, o) < 0) return -1;   // (mv_set_visible_obs: behind the frame's label planes, whichever launch wrote them)
+    if (map_follow(g, v, o) < 0) return -1;       // (mv_set_map_obs: behind the frame's depth and label planes, likewise)
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -17,6 +17,7 @@
 //                     depth, labels and normals is attached (mv_depth_obs.h, mv_seg_obs.h, mv_normal_obs.h: the records and their rules; mv_raster.hip: the kernels)
 //   mv_visible_obs.hip  visible-entity observations: the reduction kernel behind a drawn tick's label planes, its launch, the entry points (mv_visible_obs.h: the
 //                     rule)
+//   mv_map_obs.hip    map observations: the binning kernel behind a drawn tick's depth and label planes, its launch, the entry points (mv_map_obs.h: the rule)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 //   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
 //   mv_overview.hip   overview cameras: attaching the buffer, the overview's own arrays, the cameras' two forms, mv_draw_overview (mv_overview.h: the rule;
@@ -337,6 +338,12 @@ struct mv_gym {
     ObsPlanes normal;
     // mv_set_visible_obs: the caller's rows [entries][N*A][E][5] int32, counted out of the label planes by one launch behind whatever wrote them (format: unused)
     ObsPlanes visible;
+    // mv_set_map_obs: the caller's grids [entries][N*A][3][M][M] int16, binned out of the depth and label planes by one launch behind whatever wrote them (format:
+    // unused); mapCells = M, mapCellSize: the cell's edge in world units; mapLastHdr: the frame headers of the tick the last such launch followed (mv_debug_map_camera)
+    ObsPlanes map;
+    int mapCells = 0;
+    float mapCellSize = 0.0f;
+    const void *mapLastHdr = nullptr;
     // mv_set_overview: the overview cameras' frames and arrays
     OverviewState overview;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
@@ -382,7 +389,7 @@ struct GymOption {
     const char *memberNone;   // attach_check: "whose union launches <memberNone>"
     bool (*on)(const mv_gym *);
 };
-enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_DEPTH_OBS, OPT_VISIBLE_OBS, OPT_SEG_OBS, OPT_NORMAL_OBS, OPT_ENTITY_OBS, OPT_OVERVIEW, OPT_COUNT };
+enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_MAP_OBS, OPT_DEPTH_OBS, OPT_VISIBLE_OBS, OPT_SEG_OBS, OPT_NORMAL_OBS, OPT_ENTITY_OBS, OPT_OVERVIEW, OPT_COUNT };
 #define MV_OPT_ON(expr) +[](const mv_gym *g) -> bool { return expr; }
 inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_step_mask", "a step mask attached", "read none", "detach it first", "detach the mask first", "read no step mask", MV_OPT_ON(g->stepMask.live)},
@@ -391,6 +398,7 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_episode_budget", "an episode budget attached", "read none", "detach it first", "detach the budget first", "read no episode budget", MV_OPT_ON(g->budgetOn)},
     {"mv_set_state_obs", "state observations attached", "write none", "detach them first", "detach them first", "write no state observations", MV_OPT_ON(g->stateRows.buf)},
     {"mv_set_scene_obs", "scene observations attached", "write none", "detach them first", "detach them first", "write no scene observations", MV_OPT_ON(g->sceneRows.buf)},
+    {"mv_set_map_obs", "map observations attached", "write none", "detach them first", "detach them first", "write no map observations", MV_OPT_ON(g->map.buf)},   // (in front of the depth and the labels it needs: named first, detached first)
     {"mv_set_depth_obs", "depth observations attached", "write none", "detach them first", "detach them first", "write no depth observations", MV_OPT_ON(g->depth.buf)},
     {"mv_set_visible_obs", "visible-entity observations attached", "write none", "detach them first", "detach them first", "write no visible-entity observations", MV_OPT_ON(g->visible.buf)},   // (in front of the labels it needs: named first, detached first)
     {"mv_set_seg_obs", "segmentation observations attached", "write none", "detach them first", "detach them first", "write no segmentation observations", MV_OPT_ON(g->seg.buf)},
@@ -399,8 +407,8 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_overview", "an overview attached", "draw none", "detach it first", "detach it first", "draw no overview", MV_OPT_ON(g->overview.buf)},
 };
 #undef MV_OPT_ON
-// The seven per-tick observation streams, stated once, in the order mv_set_output_ring refuses them: the option that attaches the stream, the noun the refusal
-// texts name it by and, for the three plane streams (mv_obs_planes.hip) and the rows counted out of the label planes (mv_visible_obs.hip: in front of the labels, which they need), the name of one plane; null: a row stream (mv_obs_rows.hip).  A new stream is one row
+// The eight per-tick observation streams, stated once, in the order mv_set_output_ring refuses them: the option that attaches the stream, the noun the refusal
+// texts name it by and, for the three plane streams (mv_obs_planes.hip) and the rows counted out of the label planes (mv_visible_obs.hip: in front of the labels, which they need) and the grids binned out of the depth and label planes (mv_map_obs.hip: in front of both), the name of one plane; null: a row stream (mv_obs_rows.hip).  A new stream is one row
 // here, one in gym_options and one descriptor in its file.
 struct ObsStream {
     int opt;
@@ -408,6 +416,7 @@ struct ObsStream {
 };
 inline constexpr ObsStream obs_streams[] = {
     {OPT_STATE_OBS, "state observations", nullptr},
+    {OPT_MAP_OBS, "map observations", "map grid"},
     {OPT_DEPTH_OBS, "depth observations", "depth plane"},
     {OPT_VISIBLE_OBS, "visible-entity observations", "visible rows"},
     {OPT_SEG_OBS, "segmentation observations", "label plane"},
@@ -439,7 +448,8 @@ inline void fill_view_options(GymView &v, const mv_gym *g, bool macro)
 // depth (mv_set_depth_obs): the entry's depth planes, null with no buffer attached.
 // seg (mv_set_seg_obs), normal (mv_set_normal_obs): the entry's label planes and normal planes, likewise.
 // visible (mv_set_visible_obs): the entry's visible-entity rows, likewise.
-struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; void *depth = nullptr; void *seg = nullptr; void *normal = nullptr; void *visible = nullptr; };
+// map (mv_set_map_obs): the entry's map grids, likewise.
+struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; void *depth = nullptr; void *seg = nullptr; void *normal = nullptr; void *visible = nullptr; void *map = nullptr; };
 // the planes of one tick's entry and their formats, as the observation pass takes them (mv_raster.h: PlaneOuts; null: not attached)
 PlaneOuts plane_outs(const mv_gym *g, const OutPtrs &o);
 std::string lower(const char *s);
@@ -502,8 +512,12 @@ void obs_planes_free(mv_gym *g);       // mv_close
 // the planes (an exact pass, or planes_follow); v: the tick's view; -> launches made (0: nothing attached), -1
 int visible_follow(mv_gym *g, const GymView &v, const OutPtrs &o);
 void visible_obs_free(mv_gym *g);      // mv_close
+// mv_map_obs.hip: the map grids of the frames whose planes o.depth and o.seg hold -> o.map, ONE launch on the caller's stream behind whatever wrote the planes
+// (an exact pass, or planes_follow); v: the tick's view; -> launches made (0: nothing attached), -1
+int map_follow(mv_gym *g, const GymView &v, const OutPtrs &o);
+void map_obs_free(mv_gym *g);          // mv_close
 // What the calls that an attached stream forbids answer (mv_api.hip), each walking obs_streams and composing "<who>: <noun> are attached (<setter>), <clause>:
-// detach the <noun> first" for the first stream that is on; -> -1 with that text, 0: none is.  ring_sized_attached: all seven, sized by the ring count they
+// detach the <noun> first" for the first stream that is on; -> -1 with that text, 0: none is.  ring_sized_attached: all eight, sized by the ring count they
 // were attached under.  planes_attached: the three plane streams, with the caller's clause.  still_clause: why still frames and a plane stream exclude each other
 // (mv_set_still_frames; the plane setters' own refusal)
 int ring_sized_attached(const mv_gym *g, const char *who);

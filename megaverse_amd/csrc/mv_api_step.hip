@@ -48,6 +48,7 @@ struct StepCall {
     bool rows, carry, depth;  // followers: the row records' publication, the still frames' carry, the depth, label and normal planes behind fast passes -- ONE launch per
                               // drawn tick for whichever of the three are attached (the log: per gym, logCapacity)
     bool visible;             // ... and the visible-entity rows behind the label planes of a drawn tick, in either pixel mode (mv_set_visible_obs)
+    bool map;                 // ... and the map grids behind the depth and label planes of a drawn tick, likewise (mv_set_map_obs)
     bool timeCall, timeTicks;   // timing (mv_profile_begin): ONE entry for the whole call (callEv), or one per tick for the first tickEvs ticks (tickEv);
     hipEvent_t *callEv = nullptr, *tickEv = nullptr;   // reserve_timing takes the entries, behind the checks and the refill as always
     int tickEvs = 0;
@@ -137,6 +138,7 @@ struct StepCall {
         // (mv_set_visible_obs, either pixel mode: one launch per drawn tick behind the tick's label planes; no overlapped passes either -- fast pixels: the labels'
         // follower rules them out already, exact pixels: PASS_BATCH is not taken)
         visible = n == 1 && L->visible.buf != nullptr && (r.render || drawLast);
+        map = n == 1 && L->map.buf != nullptr && (r.render || drawLast);   // (mv_set_map_obs: the same)
         // overlapped passes (mv_set_pass_overlap): this call's one launch goes to an internal stream
         // (an env must not finish in two consecutive calls: their passes may publish its true objective in either order -- episodes of at least
         // baseEpisodeLen seconds, 15 ticks each)
@@ -517,8 +519,15 @@ struct StepCall {
                 if (rc < 0) return -1;
                 L->launchCount[1] += rc;
             }
+        // the map grids (mv_set_map_obs): the same, behind the tick's depth and label planes; the tick's slot also holds the cameras its frames were drawn with
+        if (map)
+            for (int j = r.render ? 0 : k - 1; j < k; ++j) {
+                const int rc = map_follow(L, views[(size_t)j], outs[(size_t)j]);
+                if (rc < 0) return -1;
+                L->launchCount[1] += rc;
+            }
         if (mc && mc->last) ++L->ringTick;
-        if ((anyLog || rows || carry || depth || visible) && own) HIP_TRY(hipEventRecord(mark(), L->stream));
+        if ((anyLog || rows || carry || depth || visible || map) && own) HIP_TRY(hipEventRecord(mark(), L->stream));
         if (own) {
             ++L->markCount;
             for (int i = 0; i < n; ++i) gs[i]->markCount = L->markCount;

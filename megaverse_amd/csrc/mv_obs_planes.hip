@@ -66,6 +66,10 @@ int planes_attach(mv_gym *g, const Planes &rec, void *device_buf, int format)
     if (rec.planes == &mv_gym::seg && g->visible.buf && (!device_buf || format != SEG_INSTANCE_U16))
         return fail(who + ": " + obs_stream(OPT_VISIBLE_OBS).noun + " are attached (" + gym_options[OPT_VISIBLE_OBS].setter
                     + "), which are counted in the instance-format label planes: detach the " + obs_stream(OPT_VISIBLE_OBS).noun + " first");
+    // (mv_set_map_obs bins the depth planes by the label planes' classes: both stay as they are while it is attached)
+    if ((rec.planes == &mv_gym::seg || rec.planes == &mv_gym::depth) && g->map.buf)
+        return fail(who + ": " + obs_stream(OPT_MAP_OBS).noun + " are attached (" + gym_options[OPT_MAP_OBS].setter
+                    + "), which are binned out of the depth and label planes as they stand: detach the " + obs_stream(OPT_MAP_OBS).noun + " first");
     if (!device_buf) {
         // No launch, no copy: the launches enqueued so far keep the pointers they were given; the next pass writes no plane.
         p = ObsPlanes();

@@ -128,6 +128,10 @@ SYMBOLS = [
     ("mv_debug_seg_pack_host", C.c_int, [_P, _P, _I, _I, _P]),
     ("mv_set_visible_obs", C.c_int, [_P, _P]), ("mv_get_visible_obs", C.c_int, [_P]), ("mv_get_visible_observation", C.c_int, [_P, _I, _I, _P]),
     ("mv_debug_visible_host", C.c_int, [_I, _I, _I, _P, _P, _I, _I, _P]),
+    ("mv_set_map_obs", C.c_int, [_P, _P, _I, C.c_float]), ("mv_get_map_obs", C.c_int, [_P]), ("mv_map_obs_cells", C.c_int, [_P]),
+    ("mv_map_obs_cell_size", C.c_float, [_P]), ("mv_get_map_observation", C.c_int, [_P, _I, _I, _P]),
+    ("mv_debug_map_host", C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, C.c_float, _P]),
+    ("mv_debug_map_device", C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, C.c_float, _P]), ("mv_debug_map_camera", C.c_int, [_P, _I, _I, _P]),
     ("mv_set_overview", C.c_int, [_P, _I, _I, _P]), ("mv_set_overview_cameras", C.c_int, [_P, _P]), ("mv_set_overview_cameras_host", C.c_int, [_P, _P]),
     ("mv_get_overview_observation", C.c_int, [_P, _I, _P]), ("mv_overview_device_ptr", _P, [_P]), ("mv_overview_dropped", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("mv_overview_capacity", C.c_int, [_P]), ("mv_overview_default_camera", C.c_int, [_P]), ("mv_debug_overview_camera_host", C.c_int, [_P, _P, _P]),
@@ -539,6 +543,56 @@ def debug_visible_host(scenario, num_agents, words, room_w=0, soko_cells=None):
     out = np.empty((entity_rows(scenario, num_agents), MV_VISIBLE_OBS_INTS), np.int32)
     if lib.mv_debug_visible_host(scenario_family(scenario), int(num_agents), int(room_w), None if cells is None else cells.ctypes.data, words.ctypes.data,
                                  int(words.shape[1]), int(words.shape[0]), out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
+
+# include/megaverse_hip.h: MV_MAP_OBS_PLANES and the planes of a map observation (mv_set_map_obs; megaverse_amd/csrc/mv_map_obs.h has the rule): per cell of
+# one agent's egocentric grid the pixels that fell in it (saturated at 32767), the greatest height over the eye among them in units of MAP_HEIGHT_UNIT, and
+# the class (SEG_CLASSES) of a pixel of that height; three zeros: nothing seen there
+MV_MAP_OBS_PLANES = 3
+MAP_OBS_FIELDS = ("count", "height", "class")
+MAP_HEIGHT_UNIT = 1 / 32
+
+
+def debug_map_host(depth, seg, cam12, cells, cell_size, depth_format=None, seg_format=None):
+    """mv_debug_map_host: the map rule on the CPU (no device): one frame's depth plane [h, w] (float32, or float16 / its uint16 bits) and label plane [h, w]
+    (uint8 classes, or uint16 'instance' words) and the camera's 12 floats eye(3) c(9) -> int16 [3, cells, cells] (MAP_OBS_FIELDS).  The formats follow the
+    arrays' dtypes unless given (the library's words, for the refusal tests)"""
+    lib = load_library()
+    depth, seg = np.ascontiguousarray(depth), np.ascontiguousarray(seg)
+    if depth.ndim != 2 or seg.shape != depth.shape:
+        raise ValueError("debug_map_host: depth and seg must be planes [h, w] of one shape")
+    if depth.dtype not in (np.float32, np.float16, np.uint16) or seg.dtype not in (np.uint8, np.uint16):
+        raise ValueError("debug_map_host: depth is float32 / float16 / uint16 bits, seg uint8 / uint16")
+    cam = np.ascontiguousarray(cam12, np.float32).ravel()
+    if cam.size != 12:
+        raise ValueError("debug_map_host: cam12 is eye(3) c(9)")
+    dfmt = (MV_DEPTH_F32 if depth.dtype == np.float32 else MV_DEPTH_F16) if depth_format is None else int(depth_format)
+    sfmt = (MV_SEG_CLASS_U8 if seg.dtype == np.uint8 else MV_SEG_INSTANCE_U16) if seg_format is None else int(seg_format)
+    out = np.empty((MV_MAP_OBS_PLANES, max(int(cells), 0), max(int(cells), 0)), np.int16)
+    if lib.mv_debug_map_host(depth.ctypes.data, dfmt, seg.ctypes.data, sfmt, int(depth.shape[1]), int(depth.shape[0]), cam.ctypes.data, int(cells),
+                             float(cell_size), out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
+
+def debug_map_device(depth, seg, cam12, cells, cell_size):
+    """mv_debug_map_device: the map KERNEL on one frame: depth [h, w] (torch.float32 / float16) and seg [h, w] (torch.uint8 / int16 / uint16) contiguous CUDA
+    tensors, cam12 a float32 CUDA tensor of 12 -> a new int16 CUDA tensor [3, cells, cells]; waits for the launch"""
+    import torch
+    lib = load_library()
+    if depth.dim() != 2 or seg.shape != depth.shape or not (depth.is_cuda and seg.is_cuda and cam12.is_cuda) or not (depth.is_contiguous() and seg.is_contiguous()) \
+            or depth.dtype not in (torch.float32, torch.float16) or seg.dtype not in (torch.uint8, torch.int16, torch.uint16) \
+            or cam12.dtype != torch.float32 or cam12.numel() != 12 or not cam12.is_contiguous():
+        raise ValueError("debug_map_device: depth [h, w] float32 / float16, seg [h, w] uint8 / int16 / uint16, cam12 float32 [12], contiguous CUDA tensors")
+    out = torch.zeros((MV_MAP_OBS_PLANES, int(cells), int(cells)), dtype=torch.int16, device=depth.device)
+    torch.cuda.synchronize(depth.device)   # (the hook launches on the null stream: behind what torch's stream holds)
+    with torch.cuda.device(depth.device):
+        rc = lib.mv_debug_map_device(_P(int(depth.data_ptr())), MV_DEPTH_F32 if depth.dtype == torch.float32 else MV_DEPTH_F16, _P(int(seg.data_ptr())),
+                                     MV_SEG_CLASS_U8 if seg.dtype == torch.uint8 else MV_SEG_INSTANCE_U16, int(depth.shape[1]), int(depth.shape[0]),
+                                     _P(int(cam12.data_ptr())), int(cells), float(cell_size), _P(int(out.data_ptr())))
+    if rc != 0:
         raise RuntimeError(lib.mv_last_error().decode())
     return out
 
@@ -967,7 +1021,7 @@ def _check_obs_tensor(buf, entries, tail, dtypes, device, who):
     return buf
 
 
-# The seven per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
+# The eight per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
 # of the gym (a read-back's row is that shape without its first extent), format -> the torch dtype names a tensor may have (the first: what True allocates),
 # the arguments behind the null pointer of a detach, the numpy dtype a read-back hands out.  A new stream is one row here.
 _ObsStream = collections.namedtuple('_ObsStream', 'setter reader tail dtypes detach read')
@@ -987,6 +1041,8 @@ OBS_STREAMS = {
     'visible': _ObsStream('mv_set_visible_obs', 'mv_get_visible_observation',
                           lambda g: (g.num_envs * g.num_agents_per_env, entity_rows(g.scenario, g.num_agents_per_env), MV_VISIBLE_OBS_INTS),
                           lambda fmt: ('torch.int32',), (), np.int32),
+    'map': _ObsStream('mv_set_map_obs', 'mv_get_map_observation',
+                      lambda g: (g.num_envs * g.num_agents_per_env, MV_MAP_OBS_PLANES, g._map_cells, g._map_cells), lambda fmt: ('torch.int16',), (0, 0.0), np.int16),
 }
 
 
@@ -1193,6 +1249,7 @@ class MegaverseGym:
         self._step_mask_held = None  # set_step_mask: the caller's device mask, kept until it is replaced or detached
         self._draw_mask_held = None  # set_draw_mask: the caller's device mask, kept until it is replaced or detached
         self._obs = {}               # set_*_obs: stream name (OBS_STREAMS) -> the attached tensor
+        self._map_cells = 0          # set_map_obs: the grid's edge in cells (the 'map' stream's shape)
         self._ring_ticks = 0         # ticks stepped through this object since set_output_ring (the library's own count: which entry the last tick went to)
         self._macro_held = None      # macro_step: the caller's device tensors of the last call, read in stream order: kept until the next macro step
         self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
@@ -1606,7 +1663,7 @@ class MegaverseGym:
             buf = torch.zeros((entries,) + tail, dtype=getattr(torch, dtypes[0][6:]), device=f'cuda:{self.device}')
         else:
             _check_obs_tensor(buf, entries, tail, dtypes, self.device, who)
-        self._ck(getattr(self._lib, s.setter)(self._g, _P(int(buf.data_ptr())), *(() if fmt is None else (fmt,))))
+        self._ck(getattr(self._lib, s.setter)(self._g, _P(int(buf.data_ptr())), *(() if fmt is None else fmt if isinstance(fmt, tuple) else (fmt,))))
         self._obs[name] = buf
         return buf
 
@@ -1782,6 +1839,43 @@ class MegaverseGym:
     def get_visible_observation(self, env_idx, agent_idx):
         """-> numpy int32 [E, 5]: the visible-entity rows of one agent in the last tick's entry (waits for the gym's stream)"""
         return self._read_obs('visible', env_idx, agent_idx)
+
+    def set_map_obs(self, buf=True, cells=32, cell_size=0.5):
+        """Map observations (include/megaverse_hip.h: mv_set_map_obs): an egocentric top-down grid per agent.  Every frame a later observation pass draws --
+        the passes set_depth_obs names -- leaves 3 planes of cells x cells int16 per AGENT (MAP_OBS_FIELDS: count, height, class): the frame's pixels
+        unprojected with its camera and binned into square cells of cell_size world units, the eye at the middle of the bottom edge, row 0 nearest, rows along
+        the heading, columns to the right; per cell how many pixels fell in it (saturated at 32767), the greatest height over the eye in units of
+        MAP_HEIGHT_UNIT, and the class of a pixel of that height; three zeros: nothing seen.  Entry t % entries of an int16 CUDA tensor [entries, num_envs *
+        num_agents, 3, cells, cells], entries = the output ring's count, or 1 without a ring.  Needs set_depth_obs and set_seg_obs first (either format each),
+        and both stay attached as they are while this is.  cells: a multiple of 8 in [8, 64]; cell_size: a finite float > 0.  True allocates the tensor on the
+        gym's device and returns it; a tensor is checked (ValueError) and attached; None detaches.  One launch per drawn tick behind the planes; nothing waits
+        on the host.  While attached, set_output_ring and set_render_resolution are refused."""
+        if buf is not None:
+            if isinstance(cells, (bool, np.bool_)) or not isinstance(cells, (int, np.integer)) or not 8 <= int(cells) <= 64 or int(cells) % 8:
+                raise ValueError(f"set_map_obs: cells must be a multiple of 8 in [8, 64], got {cells!r}")
+            if not np.isfinite(float(cell_size)) or not float(cell_size) > 0:
+                raise ValueError(f"set_map_obs: cell_size must be a finite number > 0, got {cell_size!r}")
+            self._map_cells = int(cells)
+        return self._attach_obs('map', buf, None if buf is None else (int(cells), float(cell_size)))
+
+    def map_obs_ring(self):
+        """-> the tensor set_map_obs attached, [entries, num_envs * num_agents, 3, cells, cells] (entry t % entries: the grids of tick t's frames), or None"""
+        return self._obs.get('map')
+
+    def map_obs(self):
+        """-> the entry of the last tick, (num_envs * num_agents, 3, cells, cells): a view of the attached tensor, valid in the order of the gym's stream; None
+        with nothing attached.  A tick that drew no frame wrote nothing there.  With an output ring: the entry the last tick stepped through this object went to"""
+        return self._obs_last('map')
+
+    def get_map_observation(self, env_idx, agent_idx):
+        """-> numpy int16 [3, cells, cells]: the map of one agent in the last tick's entry (waits for the gym's stream)"""
+        return self._read_obs('map', env_idx, agent_idx)
+
+    def debug_map_camera(self, env_idx, agent_idx):
+        """mv_debug_map_camera -> numpy float32 [12]: eye(3) c(9) of one agent's frame as the latest tick with a map drew it (waits for the gym's stream)"""
+        out = np.empty(12, np.float32)
+        self._ck(self._lib.mv_debug_map_camera(self._g, int(env_idx), int(agent_idx), out.ctypes.data))
+        return out
 
     def get_state_observation(self, env_idx, agent_idx):
         """-> numpy float32 [16]: the last tick's row of one agent (waits for the gym's stream)"""

@@ -18,7 +18,7 @@ Differences, all additive:
 import numpy as np
 
 from . import spaces
-from .extension import ENTITY_OBS_FIELDS, MEGAVERSE8, MegaverseGym, SCENARIOS, SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS, STATE_OBS_FIELDS, VISIBLE_OBS_FIELDS, \
+from .extension import ENTITY_OBS_FIELDS, MAP_OBS_FIELDS, MEGAVERSE8, MegaverseGym, SCENARIOS, SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS, STATE_OBS_FIELDS, VISIBLE_OBS_FIELDS, \
     render_mode_of, set_megaverse_log_level
 
 OBSTACLES_MULTITASK = ['ObstaclesWalls', 'ObstaclesSteps', 'ObstaclesLava', 'ObstaclesEasy', 'ObstaclesHard']
@@ -68,7 +68,7 @@ def check_sequence_actions(actions, num_agents):
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
                  img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1,
-                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False, overview=None, normal_obs=False, visible_obs=False):
+                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False, overview=None, normal_obs=False, visible_obs=False, map_obs=False):
         if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
         # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
@@ -128,9 +128,19 @@ class MegaverseEnv:
             if seg_obs in (True, "class"):
                 raise ValueError("visible_obs=True counts its rows in an 'instance' label plane: pass seg_obs='instance' (or leave seg_obs out), not 'class'")
             seg_obs = "instance"
+        #   map_obs (True: 32 cells of 0.5 world units; (cells, cell_size)): every drawn frame leaves an egocentric top-down grid per AGENT, 3 planes of cells x
+        #     cells int16 (MAP_OBS_FIELDS: count, height, class; mv_set_map_obs).  It is binned out of the depth and label planes: a float16 depth plane and a
+        #     class label plane are attached if depth_obs / seg_obs ask for none
+        if map_obs is not False:
+            if map_obs is not True and not (isinstance(map_obs, (tuple, list)) and len(map_obs) == 2):
+                raise ValueError(f"map_obs must be False, True or (cells, cell_size), got {map_obs!r}")
+            map_obs = (32, 0.5) if map_obs is True else (map_obs[0], float(map_obs[1]))
+            depth_obs = depth_obs or "float16"
+            seg_obs = seg_obs or "class"
         wanted = (("state", state_obs, ()), ("scene", scene_obs, ()), ("entity", entity_obs, ()),
                   ("depth", depth_obs, ("float32" if depth_obs is True else depth_obs,)), ("seg", seg_obs, ("class" if seg_obs is True else seg_obs,)),
-                  ("normal", normal_obs, ("float16" if normal_obs is True else normal_obs,)), ("visible", bool(visible_obs), ()))   # (behind "seg")
+                  ("normal", normal_obs, ("float16" if normal_obs is True else normal_obs,)), ("visible", bool(visible_obs), ()),   # (behind "seg")
+                  ("map", map_obs is not False, map_obs))   # (behind "depth" and "seg")
         self._streams = {name: args for name, on, args in wanted if on}
         if "state" in self._streams:
             self._attach_stream("state")
@@ -209,6 +219,15 @@ class MegaverseEnv:
         buffer, under state_obs()'s rules: ask again after every call.  A tick that drew no frame wrote nothing.  Needs MegaverseEnv(..., visible_obs=True)."""
         return self._stream_entry("visible", self.env.visible_obs_ring(), per_agent_planes=True)
 
+    MAP_OBS_FIELDS = MAP_OBS_FIELDS   # the planes of a map_obs() grid, in order
+
+    def map_obs(self):
+        """the last tick's maps: int16 (num_envs, num_agents_per_env, 3, cells, cells) on the device, planes MAP_OBS_FIELDS -- per agent an egocentric
+        top-down grid, the eye at the middle of the bottom edge, row 0 nearest: per cell the pixels that fell in it, the greatest height over the eye in units
+        of megaverse_amd.MAP_HEIGHT_UNIT and the class seen at that height, three zeros where nothing was seen -- a view of the attached buffer, under
+        state_obs()'s rules: ask again after every call.  A tick that drew no frame wrote nothing.  Needs MegaverseEnv(..., map_obs=True | (cells, cell_size))."""
+        return self._stream_entry("map", self.env.map_obs_ring(), per_agent_planes=True)
+
     def _attach_stream(self, name, on=True):
         """one wanted stream's tensor attached (a new one, of the output ring's depth) or detached"""
         getattr(self.env, f"set_{name}_obs")(*((True,) + self._streams[name] if on else (None,)))
@@ -224,7 +243,7 @@ class MegaverseEnv:
     def _set_output_ring(self, count, *ptrs):
         """the env's own output rings change (step_device, step_sequence): every attached stream's buffer is one more ring of the same depth and the library
         refuses a ring change while one is attached, so they are detached around the change and buffers of the new depth attached -- the planes first"""
-        for name in reversed(list(self._streams)):   # (the visible rows before the label plane they count in)
+        for name in reversed(list(self._streams)):   # (the visible rows and the maps before the planes they are made from)
             self._attach_stream(name, on=False)
         self.env.set_output_ring(count, *ptrs)
         for name in sorted(self._streams, key=lambda name: name not in ("depth", "seg", "normal")):

@@ -209,6 +209,10 @@ class MultiTaskGym:
         """visible-entity observations (MegaverseGym.set_visible_obs) are per gym: a group's union launches write none, and the library refuses"""
         raise _per_gym("set_visible_obs", "visible-entity observations", "write")
 
+    def set_map_obs(self, buf=True, cells=32, cell_size=0.5):
+        """map observations (MegaverseGym.set_map_obs) are per gym: a group's union launches write none, and the library refuses"""
+        raise _per_gym("set_map_obs", "map observations", "write")
+
     def set_overview(self, w, h, buf=True):
         """overview cameras (MegaverseGym.set_overview) are per gym: a group's union launches draw none, and the library refuses"""
         raise _per_gym("set_overview", "an overview", "draw")
