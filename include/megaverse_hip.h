@@ -532,6 +532,44 @@ int mv_debug_map_host(const void *depth, int32_t depth_format, const void *seg, 
 int mv_debug_map_device(const void *depth, int32_t depth_format, const void *seg, int32_t seg_format, int32_t w, int32_t h, const float *cam12, int32_t cells,
                         float cell_size, int16_t *out);   /* the kernel on one frame; every pointer a device pointer */
 int mv_debug_map_camera(mv_gym *g, int32_t env_idx, int32_t agent_idx, float out12[12]);   /* eye(3) c(9) of the latest drawn frame's header */
+/* World map observations (no reference counterpart): an ALLOCENTRIC top-down grid per AGENT that is kept over an episode -- everything the agent has seen since
+ * its episode began.  ONE grid per agent, MV_MAP_OBS_PLANES = 3 planes of M x M int16, [N*A][3][M][M], M = cells, and NO entries dimension: every tick of every
+ * call merges into the same grid, in stream order, whatever the output ring's count.  The orientation is fixed: columns grow along world x from origin_x, rows
+ * along world z from origin_z, the grid covers M * cell_size world units each way, and nothing depends on the agent's heading.  Every pixel of a drawn frame whose
+ * depth t is not 0 and whose class is not HUD is unprojected as for mv_set_map_obs -- pc = (x t, y t, -t), d = c pc -- and placed in the world: P = eye + d, col
+ * = floor((P.x - origin_x) / cell_size), row = floor((P.z - origin_z) / cell_size); a pixel outside [0, M) on either axis is dropped.  Per cell:
+ *   plane 0  count: the pixels that fell in it since the grid was cleared, saturated at 32767
+ *   plane 1  height: the greatest floor(32 P.y) among them, clamped to [-32767, 32767] -- WORLD height in 1/32 world units, not height over the eye
+ *   plane 2  class: the class of a pixel of that greatest height; among equals the greatest class
+ * and a cell no pixel fell in is three zeros.  megaverse_amd/csrc/mv_world_map_obs.h states the rule with the order of its fp32 operations.
+ * THE BUFFER IS THE WHOLE STATE: merging a frame reads each cell's count and (height, class) back from the buffer, adds the frame's pixels (count = min(old +
+ * new, 32767), (height, class) = the greater of old and new) and stores the cell again; sums and maxima, exact under saturation: reproducible byte for byte.
+ * So a caller who zeroes an agent's grid on the gym's stream has cleared it, and a caller who copies one grid onto another has moved it (what a user of
+ * mv_fork_envs does for the destination envs): there is no clear or copy entry point.
+ * A grid is cleared before a frame is merged exactly when that frame is the first of a new episode: the tick's own done[env] was set (in a batched call the
+ * tick's staged value, as the episode log reads it); the frame is the one mv_reset draws; the frame is the one mv_reset_envs*(render = 1) draws and the env was
+ * flagged and took its next episode.  mv_render merges its frame again and clears nothing.  Forks, resampling, loads and seeds touch no grid.
+ * A tick that is not drawn could hide an episode's end, so while world maps are attached mv_step_no_render, mv_step_n_render with MV_RENDER_LAST or
+ * MV_RENDER_NONE, mv_macro_step* and mv_reset_envs*(render = 0) are refused, the attach is refused beside a draw mask and mv_set_draw_mask* while attached.
+ * Step masks and episode budgets are fine: a frozen env reports done 0 and its frame merges again.
+ * mv_set_world_map_obs: device_buf is int16 [N*A][3][M][M], 16-byte aligned; cells a multiple of 8 in [8, 64]; cell_size a finite float > 0; the origin finite.
+ * It needs depth observations AND segmentation observations attached (either format each) and keeps them as they are, as mv_set_map_obs does, and attaches
+ * independently of it.  ONE launch per drawn tick on the gym's stream behind the tick's planes (counted in out[1] of mv_debug_launch_counts), no host wait; the
+ * call is an ordering point; NULL detaches (the other arguments are then not read); mv_close forgets the pointer; refused for the gyms of an mv_group or an
+ * mv_step_many call; mv_set_output_ring / mv_set_render_resolution are refused while it is attached.  The buffer is NOT cleared by the attach: a caller
+ * who attaches in the middle of an episode decides what the grids hold.  The values are whatever the planes hold, the labels' batched-call caveat included.
+ * mv_get_world_map_observation: one agent's [3][M][M], after waiting for the gym's stream.  mv_debug_world_map_host: ONE frame merged into the caller's grid
+ * [3][cells][cells] on the CPU by the rule's loops (clear != 0: the grid is read as zeros); no device.  mv_debug_world_map_device: the same arguments as DEVICE
+ * pointers (the grid 16-byte aligned): the very kernel on that one frame, on the current device's null stream, waited for.  mv_debug_map_camera serves this
+ * stream too: the camera of the frame the latest map or world map launch followed. */
+int mv_set_world_map_obs(mv_gym *g, void *device_buf, int32_t cells, float cell_size, float origin_x, float origin_z);   /* int16 [N*A][3][cells][cells]; NULL detaches */
+int mv_get_world_map_obs(const mv_gym *g);                /* 0: none, 1: attached; -1: no gym */
+int mv_world_map_obs_cells(const mv_gym *g);              /* M; 0: none attached */
+int mv_get_world_map_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, int16_t *out_host);   /* [3][M][M] int16; waits for the gym's stream */
+int mv_debug_world_map_host(const void *depth, int32_t depth_format, const void *seg, int32_t seg_format, int32_t w, int32_t h, const float *cam12, int32_t cells,
+                            float cell_size, float origin_x, float origin_z, int32_t clear, int16_t *grid_inout);   /* the rule on the CPU, no device */
+int mv_debug_world_map_device(const void *depth, int32_t depth_format, const void *seg, int32_t seg_format, int32_t w, int32_t h, const float *cam12, int32_t cells,
+                              float cell_size, float origin_x, float origin_z, int32_t clear, int16_t *grid_inout);   /* the kernel on one frame; device pointers */
 /* Episode budgets (no reference counterpart: VectorEnv::step resets a finished env on the spot and steps on, vector_env.cpp:89-108).  Per env e the gym owns an
  * int32 left[e]:  < 0: unlimited -- what every env is without these calls;  > 0: the env may still finish that many episodes;  0: the env is HALTED.
  * Tick t, env e, left[e] as it stands before the tick (megaverse_amd/csrc/mv_episode_budget.h states the rule for kernels and host alike):

@@ -751,6 +751,7 @@ int mv_close(mv_gym *g)
     obs_planes_free(g);
     visible_obs_free(g);
     map_obs_free(g);
+    world_map_obs_free(g);
     episode_budget_free(g);
     macro_step_free(g);
     still_frames_free(g);
@@ -914,7 +915,7 @@ int mv_render(mv_gym *g)
 
 }  // extern "C"
 
-int mvapi::render_frames(mv_gym *g)
+int mvapi::render_frames(mv_gym *g, const WorldMapClear &clear)
 {
     HIP_TRY(hipSetDevice(g->device));
     if (sim_join(g)) return -1;
@@ -931,6 +932,7 @@ int mvapi::render_frames(mv_gym *g)
     if (g->fastPixels && planes_follow(g, v, o, "mv_render") < 0) return -1;
     if (visible_follow(g, v, o) < 0) return -1;   // (mv_set_visible_obs: behind the frame's label planes, whichever launch wrote them)
     if (map_follow(g, v, o) < 0) return -1;       // (mv_set_map_obs: behind the frame's depth and label planes, likewise)
+    if (world_map_follow(g, v, o, clear) < 0) return -1;   // (mv_set_world_map_obs: the same frame merged into the agents' grids, cleared first where the caller says)
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1198,7 +1200,10 @@ int mv_reset(mv_gym *g)
     if (episode_log_reset(g)) return -1;   // (episodes cut by a reset are not logged)
     g->wasReset = true;
     g->mirrorsFresh = false;
-    if (mv_render(g)) return -1;
+    // (mv_render's two halves; mv_set_world_map_obs: the frame behind a reset is the first of every env's new episode -- every grid is cleared before the merge)
+    WorldMapClear clear;
+    clear.all = true;
+    if (render_frames(g, clear) || obs_rows_refresh(g, nullptr)) return -1;
     return finish_with_warning(g);
 }
 

@@ -18,6 +18,8 @@
 //   mv_visible_obs.hip  visible-entity observations: the reduction kernel behind a drawn tick's label planes, its launch, the entry points (mv_visible_obs.h: the
 //                     rule)
 //   mv_map_obs.hip    map observations: the binning kernel behind a drawn tick's depth and label planes, its launch, the entry points (mv_map_obs.h: the rule)
+//   mv_world_map_obs.hip  world map observations: the merging kernel behind a drawn tick's depth and label planes, its launch, the entry points
+//                     (mv_world_map_obs.h: the rule)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 //   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
 //   mv_overview.hip   overview cameras: attaching the buffer, the overview's own arrays, the cameras' two forms, mv_draw_overview (mv_overview.h: the rule;
@@ -344,6 +346,12 @@ struct mv_gym {
     int mapCells = 0;
     float mapCellSize = 0.0f;
     const void *mapLastHdr = nullptr;
+    // mv_set_world_map_obs: the caller's grids [N*A][3][M][M] int16, ONE per agent and no entries: every drawn tick's frame is merged into them by one launch behind
+    // map_follow (the buffer is the whole state, mv_world_map_obs.h); worldMapCells = M, worldMapCellSize: the cell's edge, worldMapOrigin: world x and z of cell (0, 0)
+    void *worldMap = nullptr;
+    int worldMapCells = 0;
+    float worldMapCellSize = 0.0f;
+    float worldMapOrigin[2] = {0.0f, 0.0f};
     // mv_set_overview: the overview cameras' frames and arrays
     OverviewState overview;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
@@ -389,7 +397,7 @@ struct GymOption {
     const char *memberNone;   // attach_check: "whose union launches <memberNone>"
     bool (*on)(const mv_gym *);
 };
-enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_MAP_OBS, OPT_DEPTH_OBS, OPT_VISIBLE_OBS, OPT_SEG_OBS, OPT_NORMAL_OBS, OPT_ENTITY_OBS, OPT_OVERVIEW, OPT_COUNT };
+enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_MAP_OBS, OPT_WORLD_MAP_OBS, OPT_DEPTH_OBS, OPT_VISIBLE_OBS, OPT_SEG_OBS, OPT_NORMAL_OBS, OPT_ENTITY_OBS, OPT_OVERVIEW, OPT_COUNT };
 #define MV_OPT_ON(expr) +[](const mv_gym *g) -> bool { return expr; }
 inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_step_mask", "a step mask attached", "read none", "detach it first", "detach the mask first", "read no step mask", MV_OPT_ON(g->stepMask.live)},
@@ -399,6 +407,7 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_state_obs", "state observations attached", "write none", "detach them first", "detach them first", "write no state observations", MV_OPT_ON(g->stateRows.buf)},
     {"mv_set_scene_obs", "scene observations attached", "write none", "detach them first", "detach them first", "write no scene observations", MV_OPT_ON(g->sceneRows.buf)},
     {"mv_set_map_obs", "map observations attached", "write none", "detach them first", "detach them first", "write no map observations", MV_OPT_ON(g->map.buf)},   // (in front of the depth and the labels it needs: named first, detached first)
+    {"mv_set_world_map_obs", "world map observations attached", "write none", "detach them first", "detach them first", "write no world map observations", MV_OPT_ON(g->worldMap)},   // (likewise)
     {"mv_set_depth_obs", "depth observations attached", "write none", "detach them first", "detach them first", "write no depth observations", MV_OPT_ON(g->depth.buf)},
     {"mv_set_visible_obs", "visible-entity observations attached", "write none", "detach them first", "detach them first", "write no visible-entity observations", MV_OPT_ON(g->visible.buf)},   // (in front of the labels it needs: named first, detached first)
     {"mv_set_seg_obs", "segmentation observations attached", "write none", "detach them first", "detach them first", "write no segmentation observations", MV_OPT_ON(g->seg.buf)},
@@ -407,8 +416,8 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_overview", "an overview attached", "draw none", "detach it first", "detach it first", "draw no overview", MV_OPT_ON(g->overview.buf)},
 };
 #undef MV_OPT_ON
-// The eight per-tick observation streams, stated once, in the order mv_set_output_ring refuses them: the option that attaches the stream, the noun the refusal
-// texts name it by and, for the three plane streams (mv_obs_planes.hip) and the rows counted out of the label planes (mv_visible_obs.hip: in front of the labels, which they need) and the grids binned out of the depth and label planes (mv_map_obs.hip: in front of both), the name of one plane; null: a row stream (mv_obs_rows.hip).  A new stream is one row
+// The nine per-tick observation streams, stated once, in the order mv_set_output_ring refuses them: the option that attaches the stream, the noun the refusal
+// texts name it by and, for the three plane streams (mv_obs_planes.hip) and the rows counted out of the label planes (mv_visible_obs.hip: in front of the labels, which they need) and the grids binned out of the depth and label planes (mv_map_obs.hip, mv_world_map_obs.hip: in front of both), the name of one plane; null: a row stream (mv_obs_rows.hip).  A new stream is one row
 // here, one in gym_options and one descriptor in its file.
 struct ObsStream {
     int opt;
@@ -417,6 +426,7 @@ struct ObsStream {
 inline constexpr ObsStream obs_streams[] = {
     {OPT_STATE_OBS, "state observations", nullptr},
     {OPT_MAP_OBS, "map observations", "map grid"},
+    {OPT_WORLD_MAP_OBS, "world map observations", "world map grid"},
     {OPT_DEPTH_OBS, "depth observations", "depth plane"},
     {OPT_VISIBLE_OBS, "visible-entity observations", "visible rows"},
     {OPT_SEG_OBS, "segmentation observations", "label plane"},
@@ -516,14 +526,24 @@ void visible_obs_free(mv_gym *g);      // mv_close
 // (an exact pass, or planes_follow); v: the tick's view; -> launches made (0: nothing attached), -1
 int map_follow(mv_gym *g, const GymView &v, const OutPtrs &o);
 void map_obs_free(mv_gym *g);          // mv_close
+// mv_world_map_obs.hip: the frames whose planes o.depth and o.seg hold, merged into the agents' world map grids: ONE launch on the caller's stream, called
+// wherever map_follow is, behind it.  clear: which grids are read as zeros first -- all: every one (mv_reset); done: the tick's staged done[env] (a stepping
+// call); mask (and applied): the envs a masked reset flagged and that took their next episode; nothing set: none (mv_render).  -> launches made (0: nothing
+// attached), -1
+struct WorldMapClear { bool all = false; const uint8_t *done = nullptr, *mask = nullptr, *applied = nullptr; };
+int world_map_follow(mv_gym *g, const GymView &v, const OutPtrs &o, const WorldMapClear &clear);
+// what a call that would leave a tick undrawn answers while world maps are attached: "<who>: world map observations are attached (mv_set_world_map_obs),
+// <clause>: detach the world map observations first" -> -1; 0: none attached
+int world_map_refuses(const mv_gym *g, const std::string &who, const char *clause);
+void world_map_obs_free(mv_gym *g);    // mv_close
 // What the calls that an attached stream forbids answer (mv_api.hip), each walking obs_streams and composing "<who>: <noun> are attached (<setter>), <clause>:
-// detach the <noun> first" for the first stream that is on; -> -1 with that text, 0: none is.  ring_sized_attached: all eight, sized by the ring count they
+// detach the <noun> first" for the first stream that is on; -> -1 with that text, 0: none is.  ring_sized_attached: all nine, sized by the ring count they
 // were attached under.  planes_attached: the three plane streams, with the caller's clause.  still_clause: why still frames and a plane stream exclude each other
 // (mv_set_still_frames; the plane setters' own refusal)
 int ring_sized_attached(const mv_gym *g, const char *who);
 int planes_attached(const mv_gym *g, const char *who, std::string (*clause)(const ObsStream &));
 std::string still_clause(const ObsStream &s);
-int render_frames(mv_gym *g);          // mv_render without the state rows' refresh (mv_api.hip; mv_reset_envs refreshes the flagged envs' rows only)
+int render_frames(mv_gym *g, const WorldMapClear &clear = WorldMapClear());   // mv_render without the state rows' refresh (mv_api.hip; mv_reset_envs refreshes the flagged envs' rows only); clear: world_map_follow's
 int episode_budget_seed_mirror(mv_gym *g);   // mv_set_episode_log: the log's mirror from the live array (mv_episode_budget.hip)
 // mv_fork.hip, shared with mv_env_store.hip: what every fork / resample / env-store form refuses (what: "forks", "env stores": for the text about groups)
 int fork_check(mv_gym *g, const void *map, const char *who, const char *what = "forks");

@@ -49,6 +49,7 @@ struct StepCall {
                               // drawn tick for whichever of the three are attached (the log: per gym, logCapacity)
     bool visible;             // ... and the visible-entity rows behind the label planes of a drawn tick, in either pixel mode (mv_set_visible_obs)
     bool map;                 // ... and the map grids behind the depth and label planes of a drawn tick, likewise (mv_set_map_obs)
+    bool worldMap;            // ... and the same frames merged into the agents' world map grids (mv_set_world_map_obs)
     bool timeCall, timeTicks;   // timing (mv_profile_begin): ONE entry for the whole call (callEv), or one per tick for the first tickEvs ticks (tickEv);
     hipEvent_t *callEv = nullptr, *tickEv = nullptr;   // reserve_timing takes the entries, behind the checks and the refill as always
     int tickEvs = 0;
@@ -88,7 +89,8 @@ struct StepCall {
         // The step kernels stage rewards / dones / true objectives in their hand-over slot and the caller's stream publishes them -- or, not pipelined, write the
         // public arrays themselves.  With an episode log (mv_set_episode_log) they always stage: the log reads every tick of the call from the slots.
         // A macro step always stages: its publication folds the slots of the call's ticks into one entry.
-        staged = own || anyLog || r.mc != nullptr;
+        // With world maps (mv_set_world_map_obs) too: the merge behind tick j reads tick j's own done flags, which only the slots keep apart in a batched call.
+        staged = own || anyLog || r.mc != nullptr || (n == 1 && L->worldMap != nullptr);
         drawLast = r.quiet == QUIET_LAST;
         // A batched call hands over ONCE: all k step kernels, then all k observation passes.  (Handing over tick by tick when the caller's stream is
         // found idle -- the first call after a synchronisation -- was built and measured on 20-step runs: 15.0-15.6 M obs/s against 16.2 M without;
@@ -139,6 +141,7 @@ struct StepCall {
         // follower rules them out already, exact pixels: PASS_BATCH is not taken)
         visible = n == 1 && L->visible.buf != nullptr && (r.render || drawLast);
         map = n == 1 && L->map.buf != nullptr && (r.render || drawLast);   // (mv_set_map_obs: the same)
+        worldMap = n == 1 && L->worldMap != nullptr && r.render;   // (mv_set_world_map_obs: every tick is drawn -- the entry points refuse the other calls)
         // overlapped passes (mv_set_pass_overlap): this call's one launch goes to an internal stream
         // (an env must not finish in two consecutive calls: their passes may publish its true objective in either order -- episodes of at least
         // baseEpisodeLen seconds, 15 ticks each)
@@ -420,8 +423,22 @@ struct StepCall {
                 for (int i = 0; i < n; ++i)
                     if (one_pass(gs[i], vj[i], obsPtrs[i], e && i == 0 ? e[3] : nullptr, pubInRaster ? &pubs[i] : nullptr, i == n - 1 ? done : nullptr, "mv_step",
                                  &outs[(size_t)j * n + i])) return -1;
+            // (mv_set_world_map_obs, exact pixels: the pass stored the tick's planes itself -- merged before the next tick's pass overwrites them)
+            if (worldMap && !depth && world_map_tick(j)) return -1;
             if (e) HIP_TRY(hipEventRecord(e[4], L->stream));
         }
+        return 0;
+    }
+
+    // the world map grids (mv_set_world_map_obs): tick j's frames merged into the agents' grids by one launch, a grid cleared first where the tick's staged
+    // done[env] is set -- the frame is then the first of the env's next episode
+    int world_map_tick(int j)
+    {
+        WorldMapClear clear;
+        clear.done = views[(size_t)j].done;
+        const int rc = world_map_follow(L, views[(size_t)j], outs[(size_t)j], clear);
+        if (rc < 0) return -1;
+        L->launchCount[1] += rc;
         return 0;
     }
 
@@ -505,29 +522,38 @@ struct StepCall {
         }
         // the depth planes behind fast passes (mv_set_depth_obs): one launch per drawn tick, the exact trace without the shading over the tick's frame lists in
         // the call's slots, into the entry the tick's frames went to
-        if (depth)
-            for (int j = r.render ? 0 : k - 1; j < k; ++j) {
-                const int rc = planes_follow(L, views[(size_t)j], outs[(size_t)j], "mv_step");
-                if (rc < 0) return -1;
-                L->launchCount[1] += rc;
-            }
-        // the visible-entity rows (mv_set_visible_obs): one launch per drawn tick behind the tick's label planes -- the exact pass's own, or the follower's above --
-        // into the entry the tick's frames went to; it reads the tick's list lengths from the call's slots (which frames were drawn)
-        if (visible)
-            for (int j = r.render ? 0 : k - 1; j < k; ++j) {
-                const int rc = visible_follow(L, views[(size_t)j], outs[(size_t)j]);
-                if (rc < 0) return -1;
-                L->launchCount[1] += rc;
-            }
-        // the map grids (mv_set_map_obs): the same, behind the tick's depth and label planes; the tick's slot also holds the cameras its frames were drawn with
-        if (map)
-            for (int j = r.render ? 0 : k - 1; j < k; ++j) {
-                const int rc = map_follow(L, views[(size_t)j], outs[(size_t)j]);
-                if (rc < 0) return -1;
-                L->launchCount[1] += rc;
-            }
+        // (mv_set_world_map_obs, fast pixels: the three followers below and the world map's go TICK BY TICK -- one round of the loop per tick -- because the
+        // grids merge every tick's frame, and with fewer plane entries than ticks, no ring or a short one, tick j's planes must be read before tick j + 1's
+        // follower overwrites them; otherwise ONE round: every tick per follower, as always)
+        const bool tickOrder = worldMap && depth;
+        for (int j0 = r.render ? 0 : k - 1; j0 < k; j0 = tickOrder ? j0 + 1 : k) {
+            const int j1 = tickOrder ? j0 + 1 : k;
+            if (depth)
+                for (int j = j0; j < j1; ++j) {
+                    const int rc = planes_follow(L, views[(size_t)j], outs[(size_t)j], "mv_step");
+                    if (rc < 0) return -1;
+                    L->launchCount[1] += rc;
+                }
+            // the visible-entity rows (mv_set_visible_obs): one launch per drawn tick behind the tick's label planes -- the exact pass's own, or the follower's above --
+            // into the entry the tick's frames went to; it reads the tick's list lengths from the call's slots (which frames were drawn)
+            if (visible)
+                for (int j = j0; j < j1; ++j) {
+                    const int rc = visible_follow(L, views[(size_t)j], outs[(size_t)j]);
+                    if (rc < 0) return -1;
+                    L->launchCount[1] += rc;
+                }
+            // the map grids (mv_set_map_obs): the same, behind the tick's depth and label planes; the tick's slot also holds the cameras its frames were drawn with
+            if (map)
+                for (int j = j0; j < j1; ++j) {
+                    const int rc = map_follow(L, views[(size_t)j], outs[(size_t)j]);
+                    if (rc < 0) return -1;
+                    L->launchCount[1] += rc;
+                }
+            // the world map grids (mv_set_world_map_obs; exact pixels: behind each tick's pass, passes_tick)
+            if (tickOrder && world_map_tick(j0)) return -1;
+        }
         if (mc && mc->last) ++L->ringTick;
-        if ((anyLog || rows || carry || depth || visible || map) && own) HIP_TRY(hipEventRecord(mark(), L->stream));
+        if ((anyLog || rows || carry || depth || visible || map || worldMap) && own) HIP_TRY(hipEventRecord(mark(), L->stream));
         if (own) {
             ++L->markCount;
             for (int i = 0; i < n; ++i) gs[i]->markCount = L->markCount;
@@ -584,7 +610,11 @@ int step_impl(mv_gym *g, bool render, int k, int policy, uint32_t seed, uint32_t
 extern "C" {
 
 int mv_step(mv_gym *g) { return step_impl(g, true, 1, POLICY_NONE, 0, 0); }
-int mv_step_no_render(mv_gym *g) { return step_impl(g, false, 1, POLICY_NONE, 0, 0); }
+int mv_step_no_render(mv_gym *g)
+{
+    if (g && !g->closed && world_map_refuses(g, "mv_step_no_render", "and a tick that is not drawn could hide an episode's end")) return -1;   // (mv_set_world_map_obs)
+    return step_impl(g, false, 1, POLICY_NONE, 0, 0);
+}
 
 int mv_step_n(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32_t first_step_index)
 {
@@ -603,6 +633,8 @@ int mv_step_n_render(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32
     if (!every) {
         if (g->inGroup) return fail("mv_step_n_render: this gym belongs to an mv_group: step the group (mv_group_step keeps its own render flag)");
         if (!g->wasReset) return fail("mv_step_n_render: call mv_reset first");
+        // (mv_set_world_map_obs: MV_RENDER_LAST, MV_RENDER_NONE)
+        if (world_map_refuses(g, "mv_step_n_render", "and a tick that is not drawn could hide an episode's end")) return -1;
     }
     int rc = 0;
     // Episodes that can end within a few ticks (statusPeriod 1: the refill protocol looks at the consumed counts after every tick) are

@@ -292,7 +292,9 @@ int mv_debug_map_camera(mv_gym *g, int32_t env, int32_t agent, float *out12)
     if (check(g)) { g_err = who + ": " + g_err; return -1; }
     if (!out12) return fail(who + ": null pointer");
     if (env < 0 || env >= g->N || agent < 0 || agent >= g->A) return fail(who + ": index out of range");
-    if (!g->mapLastHdr) return fail(who + ": no frame has been drawn with " + obs_stream(OPT_MAP_OBS).noun + " attached (" + opt().setter + ")");
+    if (!g->mapLastHdr)   // (either map stream's launch leaves the headers it followed: mv_world_map_obs.hip)
+        return fail(who + ": no frame has been drawn with " + obs_stream(OPT_MAP_OBS).noun + " or " + obs_stream(OPT_WORLD_MAP_OBS).noun + " attached (" + opt().setter
+                    + ", " + gym_options[OPT_WORLD_MAP_OBS].setter + ")");
     HIP_TRY(hipSetDevice(g->device));
     const uint8_t *src = (const uint8_t *)g->mapLastHdr + ((size_t)env * g->A + agent) * FRAME_HDR_BYTES + (size_t)(FH_CAM + FH_CAM_STRIDE * agent) * sizeof(float);
     HIP_TRY(hipMemcpyAsync(out12, src, MAP_CAM_FLOATS * sizeof(float), hipMemcpyDeviceToHost, g->stream));

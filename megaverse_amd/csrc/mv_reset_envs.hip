@@ -6,11 +6,13 @@
 namespace {
 
 // what both forms refuse: no gym, a closed one, a null mask, a gym that was never reset
-int reset_envs_check(mv_gym *g, const void *mask, const char *who)
+int reset_envs_check(mv_gym *g, const void *mask, const char *who, int render)
 {
     if (check(g)) return -1;
     if (!mask) return fail(std::string(who) + ": null mask");
     if (!g->wasReset) return fail(std::string(who) + ": call mv_reset first (there is no episode to leave)");
+    // (mv_set_world_map_obs: the flagged envs' grids are cleared by the launch behind the frame this call draws)
+    if (!render && world_map_refuses(g, who, "and with render = 0 no frame would clear the flagged envs' grids")) return -1;
     return 0;
 }
 
@@ -70,7 +72,10 @@ int reset_envs_launch(mv_gym *g, const uint8_t *device_mask, const uint8_t *host
     g->mirrorsFresh = false;
     // every frame of the gym: the unflagged envs' state did not change, so their frames come out as they were; of the state rows (mv_set_state_obs) and scene rows (mv_set_scene_obs) only the
     // flagged envs' are refreshed (device_mask: the caller's, or the half this call's copy went to -- read in stream order)
-    if (render && (render_frames(g) || obs_rows_refresh(g, device_mask))) return -1;
+    // (mv_set_world_map_obs: the flagged envs that took their next episode have their grids cleared before this frame is merged)
+    WorldMapClear clear;
+    clear.mask = device_mask; clear.applied = g->resetApplied;
+    if (render && (render_frames(g, clear) || obs_rows_refresh(g, device_mask))) return -1;
     return finish_with_warning(g);
 }
 
@@ -80,13 +85,13 @@ extern "C" {
 
 int mv_reset_envs(mv_gym *g, const uint8_t *device_mask, int32_t render)
 {
-    if (reset_envs_check(g, device_mask, "mv_reset_envs")) return -1;
+    if (reset_envs_check(g, device_mask, "mv_reset_envs", render)) return -1;
     return reset_envs_launch(g, device_mask, nullptr, render);
 }
 
 int mv_reset_envs_host(mv_gym *g, const uint8_t *mask, int32_t render)
 {
-    if (reset_envs_check(g, mask, "mv_reset_envs_host")) return -1;
+    if (reset_envs_check(g, mask, "mv_reset_envs_host", render)) return -1;
     return reset_envs_launch(g, nullptr, mask, render);
 }
 

@@ -132,6 +132,10 @@ SYMBOLS = [
     ("mv_map_obs_cell_size", C.c_float, [_P]), ("mv_get_map_observation", C.c_int, [_P, _I, _I, _P]),
     ("mv_debug_map_host", C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, C.c_float, _P]),
     ("mv_debug_map_device", C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, C.c_float, _P]), ("mv_debug_map_camera", C.c_int, [_P, _I, _I, _P]),
+    ("mv_set_world_map_obs", C.c_int, [_P, _P, _I, C.c_float, C.c_float, C.c_float]), ("mv_get_world_map_obs", C.c_int, [_P]),
+    ("mv_world_map_obs_cells", C.c_int, [_P]), ("mv_get_world_map_observation", C.c_int, [_P, _I, _I, _P]),
+    ("mv_debug_world_map_host", C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, C.c_float, C.c_float, C.c_float, _I, _P]),
+    ("mv_debug_world_map_device", C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, C.c_float, C.c_float, C.c_float, _I, _P]),
     ("mv_set_overview", C.c_int, [_P, _I, _I, _P]), ("mv_set_overview_cameras", C.c_int, [_P, _P]), ("mv_set_overview_cameras_host", C.c_int, [_P, _P]),
     ("mv_get_overview_observation", C.c_int, [_P, _I, _P]), ("mv_overview_device_ptr", _P, [_P]), ("mv_overview_dropped", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("mv_overview_capacity", C.c_int, [_P]), ("mv_overview_default_camera", C.c_int, [_P]), ("mv_debug_overview_camera_host", C.c_int, [_P, _P, _P]),
@@ -597,6 +601,53 @@ def debug_map_device(depth, seg, cam12, cells, cell_size):
     return out
 
 
+def debug_world_map_host(depth, seg, cam12, cells, cell_size, origin=(0.0, 0.0), grid=None, clear=False):
+    """mv_debug_world_map_host: the world map rule on the CPU (no device): one frame -- debug_map_host's depth [h, w], seg [h, w] and cam12 -- merged into an
+    agent's grid, int16 [3, cells, cells] (MAP_OBS_FIELDS; columns along world x from origin[0], rows along world z from origin[1], heights over world 0).
+    grid None: an empty one; clear: the grid is read as zeros.  -> the merged grid, a new array"""
+    lib = load_library()
+    depth, seg = np.ascontiguousarray(depth), np.ascontiguousarray(seg)
+    if depth.ndim != 2 or seg.shape != depth.shape:
+        raise ValueError("debug_world_map_host: depth and seg must be planes [h, w] of one shape")
+    if depth.dtype not in (np.float32, np.float16, np.uint16) or seg.dtype not in (np.uint8, np.uint16):
+        raise ValueError("debug_world_map_host: depth is float32 / float16 / uint16 bits, seg uint8 / uint16")
+    cam = np.ascontiguousarray(cam12, np.float32).ravel()
+    if cam.size != 12:
+        raise ValueError("debug_world_map_host: cam12 is eye(3) c(9)")
+    shape = (MV_MAP_OBS_PLANES, max(int(cells), 0), max(int(cells), 0))
+    out = np.zeros(shape, np.int16) if grid is None else np.array(grid, np.int16, order="C")
+    if out.shape != shape:
+        raise ValueError(f"debug_world_map_host: grid must be int16 {shape}")
+    if lib.mv_debug_world_map_host(depth.ctypes.data, MV_DEPTH_F32 if depth.dtype == np.float32 else MV_DEPTH_F16, seg.ctypes.data,
+                                   MV_SEG_CLASS_U8 if seg.dtype == np.uint8 else MV_SEG_INSTANCE_U16, int(depth.shape[1]), int(depth.shape[0]), cam.ctypes.data,
+                                   int(cells), float(cell_size), float(origin[0]), float(origin[1]), int(bool(clear)), out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
+
+def debug_world_map_device(depth, seg, cam12, cells, cell_size, origin, grid, clear=False):
+    """mv_debug_world_map_device: the world map KERNEL on one frame: debug_map_device's depth, seg and cam12 (contiguous CUDA tensors) merged IN PLACE into
+    grid, a contiguous int16 CUDA tensor [3, cells, cells]; clear: the grid is read as zeros.  Waits for the launch -> grid"""
+    import torch
+    lib = load_library()
+    if depth.dim() != 2 or seg.shape != depth.shape or not (depth.is_cuda and seg.is_cuda and cam12.is_cuda and grid.is_cuda) \
+            or not (depth.is_contiguous() and seg.is_contiguous() and grid.is_contiguous()) \
+            or depth.dtype not in (torch.float32, torch.float16) or seg.dtype not in (torch.uint8, torch.int16, torch.uint16) \
+            or cam12.dtype != torch.float32 or cam12.numel() != 12 or not cam12.is_contiguous() \
+            or grid.dtype != torch.int16 or tuple(grid.shape) != (MV_MAP_OBS_PLANES, int(cells), int(cells)):
+        raise ValueError("debug_world_map_device: depth [h, w] float32 / float16, seg [h, w] uint8 / int16 / uint16, cam12 float32 [12], grid int16 "
+                         "[3, cells, cells], contiguous CUDA tensors")
+    torch.cuda.synchronize(depth.device)   # (the hook launches on the null stream: behind what torch's stream holds)
+    with torch.cuda.device(depth.device):
+        rc = lib.mv_debug_world_map_device(_P(int(depth.data_ptr())), MV_DEPTH_F32 if depth.dtype == torch.float32 else MV_DEPTH_F16, _P(int(seg.data_ptr())),
+                                           MV_SEG_CLASS_U8 if seg.dtype == torch.uint8 else MV_SEG_INSTANCE_U16, int(depth.shape[1]), int(depth.shape[0]),
+                                           _P(int(cam12.data_ptr())), int(cells), float(cell_size), float(origin[0]), float(origin[1]), int(bool(clear)),
+                                           _P(int(grid.data_ptr())))
+    if rc != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return grid
+
+
 def debug_entity_obs_host(scenario, num_agents, env_header, agents, terrain=None, items=None, soko=None, objects=None, rewards=None, hex_objs=None,
                           football_state=None):
     """mv_debug_entity_obs_host: the entity-observation record on the CPU (no device): the SCN_* family id, the agent count, the 128 bytes of one EnvHeader,
@@ -1006,6 +1057,12 @@ def check_visible_obs(buf, entries, num_frames, rows, device):
     return _check_obs_tensor(buf, entries, (int(num_frames), int(rows), MV_VISIBLE_OBS_INTS), OBS_STREAMS['visible'].dtypes(None), device, 'set_visible_obs')
 
 
+def check_world_map_obs(buf, num_frames, cells, device):
+    """the argument check of MegaverseGym.set_world_map_obs for a tensor: contiguous torch.int16 of shape (num_frames, 3, cells, cells) on CUDA device `device`
+    -- one grid per agent and no entries extent: the shared check with the frames in the place of the entries"""
+    return _check_obs_tensor(buf, int(num_frames), (MV_MAP_OBS_PLANES, int(cells), int(cells)), OBS_STREAMS['world_map'].dtypes(None), device, 'set_world_map_obs')
+
+
 def _check_obs_tensor(buf, entries, tail, dtypes, device, who):
     """the one tensor check of the observation streams, for the setter `who`: contiguous, one of `dtypes` (torch dtype names), of shape (entries,) + tail on
     CUDA device `device`; entries None: any number of entries (the check made before the gym is asked for its ring count) -> buf"""
@@ -1021,7 +1078,7 @@ def _check_obs_tensor(buf, entries, tail, dtypes, device, who):
     return buf
 
 
-# The eight per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
+# The nine per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
 # of the gym (a read-back's row is that shape without its first extent), format -> the torch dtype names a tensor may have (the first: what True allocates),
 # the arguments behind the null pointer of a detach, the numpy dtype a read-back hands out.  A new stream is one row here.
 _ObsStream = collections.namedtuple('_ObsStream', 'setter reader tail dtypes detach read')
@@ -1043,6 +1100,10 @@ OBS_STREAMS = {
                           lambda fmt: ('torch.int32',), (), np.int32),
     'map': _ObsStream('mv_set_map_obs', 'mv_get_map_observation',
                       lambda g: (g.num_envs * g.num_agents_per_env, MV_MAP_OBS_PLANES, g._map_cells, g._map_cells), lambda fmt: ('torch.int16',), (0, 0.0), np.int16),
+    # (one grid per agent, kept over an episode: the tensor IS the tail -- no entries extent in front of it, set_world_map_obs)
+    'world_map': _ObsStream('mv_set_world_map_obs', 'mv_get_world_map_observation',
+                            lambda g: (g.num_envs * g.num_agents_per_env, MV_MAP_OBS_PLANES, g._world_map_cells, g._world_map_cells), lambda fmt: ('torch.int16',),
+                            (0, 0.0, 0.0, 0.0), np.int16),
 }
 
 
@@ -1250,6 +1311,7 @@ class MegaverseGym:
         self._draw_mask_held = None  # set_draw_mask: the caller's device mask, kept until it is replaced or detached
         self._obs = {}               # set_*_obs: stream name (OBS_STREAMS) -> the attached tensor
         self._map_cells = 0          # set_map_obs: the grid's edge in cells (the 'map' stream's shape)
+        self._world_map_cells = 0    # set_world_map_obs: the same of the 'world_map' stream
         self._ring_ticks = 0         # ticks stepped through this object since set_output_ring (the library's own count: which entry the last tick went to)
         self._macro_held = None      # macro_step: the caller's device tensors of the last call, read in stream order: kept until the next macro step
         self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
@@ -1872,10 +1934,52 @@ class MegaverseGym:
         return self._read_obs('map', env_idx, agent_idx)
 
     def debug_map_camera(self, env_idx, agent_idx):
-        """mv_debug_map_camera -> numpy float32 [12]: eye(3) c(9) of one agent's frame as the latest tick with a map drew it (waits for the gym's stream)"""
+        """mv_debug_map_camera -> numpy float32 [12]: eye(3) c(9) of one agent's frame as the latest tick with a map or a world map drew it (waits for the
+        gym's stream)"""
         out = np.empty(12, np.float32)
         self._ck(self._lib.mv_debug_map_camera(self._g, int(env_idx), int(agent_idx), out.ctypes.data))
         return out
+
+    def set_world_map_obs(self, buf=True, cells=64, cell_size=0.5, origin=(0.0, 0.0)):
+        """World map observations (include/megaverse_hip.h: mv_set_world_map_obs): an ALLOCENTRIC top-down grid per agent, kept over an episode.  ONE int16 CUDA
+        tensor [num_envs * num_agents, 3, cells, cells] (MAP_OBS_FIELDS: count, height, class) and no entries extent: every frame a later stepping call, reset or
+        render draws is merged into its agent's grid in stream order -- its pixels unprojected into the world and binned into square cells of cell_size world
+        units, columns along world x from origin[0], rows along world z from origin[1], whatever the agent's heading; per cell the pixels seen since the grid
+        was cleared (saturated at 32767), the greatest WORLD height in units of MAP_HEIGHT_UNIT and the class seen there.  A grid is cleared before the first
+        frame of a new episode: the tick's done was set, reset(), or reset_envs(mask, render=True) for a flagged env.  The tensor is the whole state: zero a
+        grid on the gym's stream and it is cleared, copy one onto another and it has moved (after fork_envs).  Needs set_depth_obs and set_seg_obs first
+        (either format each), which stay as they are.  cells: a multiple of 8 in [8, 64]; cell_size: a finite float > 0.  True allocates a zeroed tensor on the
+        gym's device and returns it; a tensor is checked (ValueError) and attached as it is; None detaches.  While attached: step_no_render, render='last' /
+        'none', macro_step, reset_envs(render=False), set_draw_mask, set_output_ring and set_render_resolution are refused."""
+        s = OBS_STREAMS['world_map']
+        if buf is None:
+            self._ck(self._lib.mv_set_world_map_obs(self._g, None, *s.detach))
+            self._obs.pop('world_map', None)
+            return None
+        if isinstance(cells, (bool, np.bool_)) or not isinstance(cells, (int, np.integer)) or not 8 <= int(cells) <= 64 or int(cells) % 8:
+            raise ValueError(f"set_world_map_obs: cells must be a multiple of 8 in [8, 64], got {cells!r}")
+        if not np.isfinite(float(cell_size)) or not float(cell_size) > 0:
+            raise ValueError(f"set_world_map_obs: cell_size must be a finite number > 0, got {cell_size!r}")
+        if len(origin) != 2 or not all(np.isfinite(float(x)) for x in origin):
+            raise ValueError(f"set_world_map_obs: origin must be two finite numbers (world x, world z), got {origin!r}")
+        frames = self.num_envs * self.num_agents_per_env
+        if buf is True:
+            import torch
+            buf = torch.zeros((frames, MV_MAP_OBS_PLANES, int(cells), int(cells)), dtype=torch.int16, device=f'cuda:{self.device}')
+        else:
+            check_world_map_obs(buf, frames, cells, self.device)
+        self._ck(self._lib.mv_set_world_map_obs(self._g, _P(int(buf.data_ptr())), int(cells), float(cell_size), float(origin[0]), float(origin[1])))
+        self._world_map_cells = int(cells)
+        self._obs['world_map'] = buf
+        return buf
+
+    def world_map_obs(self):
+        """-> the tensor set_world_map_obs attached, [num_envs * num_agents, 3, cells, cells], valid in the order of the gym's stream; None with nothing attached"""
+        return self._obs.get('world_map')
+
+    def get_world_map_observation(self, env_idx, agent_idx):
+        """-> numpy int16 [3, cells, cells]: one agent's world map as it stands (waits for the gym's stream)"""
+        return self._read_obs('world_map', env_idx, agent_idx)
 
     def get_state_observation(self, env_idx, agent_idx):
         """-> numpy float32 [16]: the last tick's row of one agent (waits for the gym's stream)"""

@@ -68,7 +68,8 @@ def check_sequence_actions(actions, num_agents):
 class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
                  img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1,
-                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False, overview=None, normal_obs=False, visible_obs=False, map_obs=False):
+                 still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False, overview=None, normal_obs=False, visible_obs=False, map_obs=False,
+                 world_map_obs=False):
         if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
         # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
@@ -137,11 +138,20 @@ class MegaverseEnv:
             map_obs = (32, 0.5) if map_obs is True else (map_obs[0], float(map_obs[1]))
             depth_obs = depth_obs or "float16"
             seg_obs = seg_obs or "class"
+        #   world_map_obs (True: 64 cells of 0.5 world units from origin (0, 0); (cells, cell_size, origin)): every drawn frame is merged into an allocentric
+        #     top-down grid per AGENT that is kept over the episode (mv_set_world_map_obs); planes as map_obs's, attached likewise
+        if world_map_obs is not False:
+            if world_map_obs is not True and not (isinstance(world_map_obs, (tuple, list)) and len(world_map_obs) == 3):
+                raise ValueError(f"world_map_obs must be False, True or (cells, cell_size, origin), got {world_map_obs!r}")
+            world_map_obs = (64, 0.5, (0.0, 0.0)) if world_map_obs is True else (world_map_obs[0], float(world_map_obs[1]), tuple(world_map_obs[2]))
+            depth_obs = depth_obs or "float16"
+            seg_obs = seg_obs or "class"
         wanted = (("state", state_obs, ()), ("scene", scene_obs, ()), ("entity", entity_obs, ()),
                   ("depth", depth_obs, ("float32" if depth_obs is True else depth_obs,)), ("seg", seg_obs, ("class" if seg_obs is True else seg_obs,)),
                   ("normal", normal_obs, ("float16" if normal_obs is True else normal_obs,)), ("visible", bool(visible_obs), ()),   # (behind "seg")
-                  ("map", map_obs is not False, map_obs))   # (behind "depth" and "seg")
+                  ("map", map_obs is not False, map_obs), ("world_map", world_map_obs is not False, world_map_obs))   # (behind "depth" and "seg")
         self._streams = {name: args for name, on, args in wanted if on}
+        self._world_map = None   # world_map_obs: the one tensor of grids (_attach_stream)
         if "state" in self._streams:
             self._attach_stream("state")
         # still_frames: envs that did not change -- frozen, halted by a budget, stopped inside a macro step -- are not drawn again (mv_set_still_frames); every
@@ -228,8 +238,22 @@ class MegaverseEnv:
         state_obs()'s rules: ask again after every call.  A tick that drew no frame wrote nothing.  Needs MegaverseEnv(..., map_obs=True | (cells, cell_size))."""
         return self._stream_entry("map", self.env.map_obs_ring(), per_agent_planes=True)
 
+    def world_map_obs(self):
+        """the agents' world maps: int16 (num_envs, num_agents_per_env, 3, cells, cells) on the device, planes MAP_OBS_FIELDS -- per agent an allocentric
+        top-down grid of everything it has seen this episode, columns along world x and rows along world z from the origin: per cell the pixels that fell in
+        it, the greatest world height in units of megaverse_amd.MAP_HEIGHT_UNIT and the class seen there -- a view of the attached buffer, ONE tensor for the
+        env's lifetime: it has no entries, and when step_device / step_sequence change the output rings the same grids are attached again as they stand.
+        Needs MegaverseEnv(..., world_map_obs=True | (cells, cell_size, origin))."""
+        buf = self.env.world_map_obs()
+        if buf is None:
+            raise RuntimeError("world_map_obs(): created without world_map_obs")
+        return buf.view(self.num_envs, self.num_agents_per_env, *buf.shape[1:])
+
     def _attach_stream(self, name, on=True):
         """one wanted stream's tensor attached (a new one, of the output ring's depth) or detached"""
+        if name == "world_map" and on:   # (the grids are kept over episodes, not sized by a ring: the tensor of the first attach, as it stands)
+            self._world_map = self.env.set_world_map_obs(True if self._world_map is None else self._world_map, *self._streams[name])
+            return
         getattr(self.env, f"set_{name}_obs")(*((True,) + self._streams[name] if on else (None,)))
 
     def _stream_entry(self, name, buf, per_agent_planes=False):

@@ -213,6 +213,10 @@ class MultiTaskGym:
         """map observations (MegaverseGym.set_map_obs) are per gym: a group's union launches write none, and the library refuses"""
         raise _per_gym("set_map_obs", "map observations", "write")
 
+    def set_world_map_obs(self, buf=True, cells=64, cell_size=0.5, origin=(0.0, 0.0)):
+        """world map observations (MegaverseGym.set_world_map_obs) are per gym: a group's union launches write none, and the library refuses"""
+        raise _per_gym("set_world_map_obs", "world map observations", "write")
+
     def set_overview(self, w, h, buf=True):
         """overview cameras (MegaverseGym.set_overview) are per gym: a group's union launches draw none, and the library refuses"""
         raise _per_gym("set_overview", "an overview", "draw")
