@@ -570,6 +570,40 @@ int mv_debug_world_map_host(const void *depth, int32_t depth_format, const void 
                             float cell_size, float origin_x, float origin_z, int32_t clear, int16_t *grid_inout);   /* the rule on the CPU, no device */
 int mv_debug_world_map_device(const void *depth, int32_t depth_format, const void *seg, int32_t seg_format, int32_t w, int32_t h, const float *cam12, int32_t cells,
                               float cell_size, float origin_x, float origin_z, int32_t clear, int16_t *grid_inout);   /* the kernel on one frame; device pointers */
+/* Scan observations (no reference counterpart): a 1-D range fan per AGENT, binned on the device out of the frame's depth plane (mv_set_depth_obs, either
+ * format) and label plane (mv_set_seg_obs, either format) -- what a depth-image-to-laser-scan node makes of a depth camera.  No ray is cast: a scan sees what
+ * the agent's camera sees, its horizontal field of view (100 degrees) and nothing behind an occluder the frame does not show; it is NOT a 360-degree sensor.
+ * Per drawn frame MV_SCAN_OBS_PLANES = 3 planes of K int16, [N*A][3][K], K = beams, beam 0 leftmost.  Every pixel whose depth t is not 0 and whose class is
+ * not HUD is unprojected as a map observation's -- lateral u, forward f, height over the eye hgt = d.y -- and kept iff f > 0 and h_lo <= hgt <= h_hi (the
+ * height band: it takes the floor and the ceiling out).  Its beam is floor((u / f) (K/2) / tan(50 deg)) + K/2 -- the beams are evenly spaced on the image
+ * plane, uniform in the TANGENT of the bearing; with a level camera and K equal to the frame's width beam i is pixel column i -- and a pixel outside [0, K) is
+ * dropped.  Per beam:
+ *   plane 0  range: the least floor(64 sqrt(u u + f f)) among its pixels, clamped at 32767 -- the horizontal distance from the eye in 1/64 world units;
+ *            -1 where no pixel was kept
+ *   plane 1  class: the class of a pixel of that least range; among equals the greatest class; 0 where none
+ *   plane 2  count: the pixels kept, saturated at 32767
+ * One minimum and one sum: the fans do not depend on any order and are reproducible byte for byte.  megaverse_amd/csrc/mv_scan_obs.h states the rule, with
+ * the order of its fp32 operations, for the kernel and the host alike.  The values are whatever the planes hold: the labels' caveat for frames whose env
+ * begins a new episode later in the same batched call carries over.
+ * mv_set_scan_obs: device_buf is int16 [entries][N*A][3][K], 16-byte aligned, entries = the output ring's count at the moment of the call, or 1; beams is a
+ * multiple of 8 in [8, 256], h_lo < h_hi two finite floats.  Everything else is mv_set_map_obs's: it needs depth observations AND segmentation observations
+ * attached and is refused without either; while it is attached, mv_set_depth_obs and mv_set_seg_obs are refused; every pass that draws frames is followed by
+ * ONE launch per drawn tick on the gym's stream behind whatever wrote the tick's planes (counted in out[1] of mv_debug_launch_counts), with no host wait; no
+ * byte where no frame is drawn; the call is an ordering point; NULL detaches (the other arguments are then not read); mv_close forgets the pointer; refused
+ * for the gyms of an mv_group or an mv_step_many call and beside still frames, and mv_set_output_ring / mv_set_render_resolution are refused while it is
+ * attached.  mv_draw_hires and the overview ignore it.  A gym without it launches exactly what it launched.
+ * mv_get_scan_observation: one agent's [3][K] in the LAST TICK's entry, after waiting for the gym's stream.  mv_debug_scan_host: the rule on the CPU for one
+ * frame: planes [h][w] of the given formats and cam12 = eye(3) c(9) -> out [3][beams]; no device.  mv_debug_scan_device: the same arguments as DEVICE pointers
+ * (out 16-byte aligned): the very kernel on that one frame, on the current device's null stream, waited for.  mv_debug_map_camera serves scans too. */
+enum { MV_SCAN_OBS_PLANES = 3, MV_SCAN_RANGE_SCALE = 64 };   /* range, class, count; range values per world unit */
+int mv_set_scan_obs(mv_gym *g, void *device_buf, int32_t beams, float h_lo, float h_hi);   /* int16 [max(1, ring count)][N*A][3][beams]; NULL detaches */
+int mv_get_scan_obs(const mv_gym *g);                     /* 0: none, else the number of entries; -1: no gym */
+int mv_scan_obs_beams(const mv_gym *g);                   /* K; 0: none attached */
+int mv_get_scan_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, int16_t *out_host);   /* [3][K] int16; waits for the gym's stream */
+int mv_debug_scan_host(const void *depth, int32_t depth_format, const void *seg, int32_t seg_format, int32_t w, int32_t h, const float *cam12, int32_t beams,
+                       float h_lo, float h_hi, int16_t *out);   /* the rule on the CPU, no device */
+int mv_debug_scan_device(const void *depth, int32_t depth_format, const void *seg, int32_t seg_format, int32_t w, int32_t h, const float *cam12, int32_t beams,
+                         float h_lo, float h_hi, int16_t *out);   /* the kernel on one frame; every pointer a device pointer */
 /* Episode budgets (no reference counterpart: VectorEnv::step resets a finished env on the spot and steps on, vector_env.cpp:89-108).  Per env e the gym owns an
  * int32 left[e]:  < 0: unlimited -- what every env is without these calls;  > 0: the env may still finish that many episodes;  0: the env is HALTED.
  * Tick t, env e, left[e] as it stands before the tick (megaverse_amd/csrc/mv_episode_budget.h states the rule for kernels and host alike):

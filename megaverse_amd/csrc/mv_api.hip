@@ -130,6 +130,7 @@ OutPtrs outputs_of(const mv_gym *g, unsigned long long tick)
     o.normal = g->normal.entry(tick); // (mv_set_normal_obs: the same)
     o.visible = g->visible.entry(tick);   // (mv_set_visible_obs: the same)
     o.map = g->map.entry(tick);           // (mv_set_map_obs: the same)
+    o.scan = g->scan.entry(tick);         // (mv_set_scan_obs: the same)
     return o;
 }
 OutPtrs last_outputs(const mv_gym *g) { return outputs_of(g, g->ringTick ? g->ringTick - 1 : 0); }   // of the last tick (reset / render / getters)
@@ -752,6 +753,7 @@ int mv_close(mv_gym *g)
     visible_obs_free(g);
     map_obs_free(g);
     world_map_obs_free(g);
+    scan_obs_free(g);
     episode_budget_free(g);
     macro_step_free(g);
     still_frames_free(g);
@@ -932,6 +934,7 @@ int mvapi::render_frames(mv_gym *g, const WorldMapClear &clear)
     if (g->fastPixels && planes_follow(g, v, o, "mv_render") < 0) return -1;
     if (visible_follow(g, v, o) < 0) return -1;   // (mv_set_visible_obs: behind the frame's label planes, whichever launch wrote them)
     if (map_follow(g, v, o) < 0) return -1;       // (mv_set_map_obs: behind the frame's depth and label planes, likewise)
+    if (scan_follow(g, v, o) < 0) return -1;      // (mv_set_scan_obs: the same two planes binned into the agents' fans)
     if (world_map_follow(g, v, o, clear) < 0) return -1;   // (mv_set_world_map_obs: the same frame merged into the agents' grids, cleared first where the caller says)
     HIP_TRY(hipGetLastError());
     return 0;

@@ -20,6 +20,7 @@
 //   mv_map_obs.hip    map observations: the binning kernel behind a drawn tick's depth and label planes, its launch, the entry points (mv_map_obs.h: the rule)
 //   mv_world_map_obs.hip  world map observations: the merging kernel behind a drawn tick's depth and label planes, its launch, the entry points
 //                     (mv_world_map_obs.h: the rule)
+//   mv_scan_obs.hip   scan observations: the beam-binning kernel behind a drawn tick's depth and label planes, its launch, the entry points (mv_scan_obs.h: the rule)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 //   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
 //   mv_overview.hip   overview cameras: attaching the buffer, the overview's own arrays, the cameras' two forms, mv_draw_overview (mv_overview.h: the rule;
@@ -352,6 +353,11 @@ struct mv_gym {
     int worldMapCells = 0;
     float worldMapCellSize = 0.0f;
     float worldMapOrigin[2] = {0.0f, 0.0f};
+    // mv_set_scan_obs: the caller's fans [entries][N*A][3][K] int16, binned out of the depth and label planes by one launch behind whatever wrote them (format:
+    // unused); scanBeams = K, scanBand: the height band over the eye, h_lo and h_hi in world units
+    ObsPlanes scan;
+    int scanBeams = 0;
+    float scanBand[2] = {0.0f, 0.0f};
     // mv_set_overview: the overview cameras' frames and arrays
     OverviewState overview;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
@@ -397,7 +403,7 @@ struct GymOption {
     const char *memberNone;   // attach_check: "whose union launches <memberNone>"
     bool (*on)(const mv_gym *);
 };
-enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_MAP_OBS, OPT_WORLD_MAP_OBS, OPT_DEPTH_OBS, OPT_VISIBLE_OBS, OPT_SEG_OBS, OPT_NORMAL_OBS, OPT_ENTITY_OBS, OPT_OVERVIEW, OPT_COUNT };
+enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_MAP_OBS, OPT_WORLD_MAP_OBS, OPT_SCAN_OBS, OPT_DEPTH_OBS, OPT_VISIBLE_OBS, OPT_SEG_OBS, OPT_NORMAL_OBS, OPT_ENTITY_OBS, OPT_OVERVIEW, OPT_COUNT };
 #define MV_OPT_ON(expr) +[](const mv_gym *g) -> bool { return expr; }
 inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_step_mask", "a step mask attached", "read none", "detach it first", "detach the mask first", "read no step mask", MV_OPT_ON(g->stepMask.live)},
@@ -408,6 +414,7 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_scene_obs", "scene observations attached", "write none", "detach them first", "detach them first", "write no scene observations", MV_OPT_ON(g->sceneRows.buf)},
     {"mv_set_map_obs", "map observations attached", "write none", "detach them first", "detach them first", "write no map observations", MV_OPT_ON(g->map.buf)},   // (in front of the depth and the labels it needs: named first, detached first)
     {"mv_set_world_map_obs", "world map observations attached", "write none", "detach them first", "detach them first", "write no world map observations", MV_OPT_ON(g->worldMap)},   // (likewise)
+    {"mv_set_scan_obs", "scan observations attached", "write none", "detach them first", "detach them first", "write no scan observations", MV_OPT_ON(g->scan.buf)},   // (likewise)
     {"mv_set_depth_obs", "depth observations attached", "write none", "detach them first", "detach them first", "write no depth observations", MV_OPT_ON(g->depth.buf)},
     {"mv_set_visible_obs", "visible-entity observations attached", "write none", "detach them first", "detach them first", "write no visible-entity observations", MV_OPT_ON(g->visible.buf)},   // (in front of the labels it needs: named first, detached first)
     {"mv_set_seg_obs", "segmentation observations attached", "write none", "detach them first", "detach them first", "write no segmentation observations", MV_OPT_ON(g->seg.buf)},
@@ -416,8 +423,8 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_overview", "an overview attached", "draw none", "detach it first", "detach it first", "draw no overview", MV_OPT_ON(g->overview.buf)},
 };
 #undef MV_OPT_ON
-// The nine per-tick observation streams, stated once, in the order mv_set_output_ring refuses them: the option that attaches the stream, the noun the refusal
-// texts name it by and, for the three plane streams (mv_obs_planes.hip) and the rows counted out of the label planes (mv_visible_obs.hip: in front of the labels, which they need) and the grids binned out of the depth and label planes (mv_map_obs.hip, mv_world_map_obs.hip: in front of both), the name of one plane; null: a row stream (mv_obs_rows.hip).  A new stream is one row
+// The ten per-tick observation streams, stated once, in the order mv_set_output_ring refuses them: the option that attaches the stream, the noun the refusal
+// texts name it by and, for the three plane streams (mv_obs_planes.hip) and the rows counted out of the label planes (mv_visible_obs.hip: in front of the labels, which they need) and the grids binned out of the depth and label planes (mv_map_obs.hip, mv_world_map_obs.hip: in front of both) and the fans binned out of the same two (mv_scan_obs.hip: likewise), the name of one plane; null: a row stream (mv_obs_rows.hip).  A new stream is one row
 // here, one in gym_options and one descriptor in its file.
 struct ObsStream {
     int opt;
@@ -427,6 +434,7 @@ inline constexpr ObsStream obs_streams[] = {
     {OPT_STATE_OBS, "state observations", nullptr},
     {OPT_MAP_OBS, "map observations", "map grid"},
     {OPT_WORLD_MAP_OBS, "world map observations", "world map grid"},
+    {OPT_SCAN_OBS, "scan observations", "scan fan"},
     {OPT_DEPTH_OBS, "depth observations", "depth plane"},
     {OPT_VISIBLE_OBS, "visible-entity observations", "visible rows"},
     {OPT_SEG_OBS, "segmentation observations", "label plane"},
@@ -459,7 +467,8 @@ inline void fill_view_options(GymView &v, const mv_gym *g, bool macro)
 // seg (mv_set_seg_obs), normal (mv_set_normal_obs): the entry's label planes and normal planes, likewise.
 // visible (mv_set_visible_obs): the entry's visible-entity rows, likewise.
 // map (mv_set_map_obs): the entry's map grids, likewise.
-struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; void *depth = nullptr; void *seg = nullptr; void *normal = nullptr; void *visible = nullptr; void *map = nullptr; };
+// scan (mv_set_scan_obs): the entry's scan fans, likewise.
+struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; void *depth = nullptr; void *seg = nullptr; void *normal = nullptr; void *visible = nullptr; void *map = nullptr; void *scan = nullptr; };
 // the planes of one tick's entry and their formats, as the observation pass takes them (mv_raster.h: PlaneOuts; null: not attached)
 PlaneOuts plane_outs(const mv_gym *g, const OutPtrs &o);
 std::string lower(const char *s);
@@ -536,8 +545,12 @@ int world_map_follow(mv_gym *g, const GymView &v, const OutPtrs &o, const WorldM
 // <clause>: detach the world map observations first" -> -1; 0: none attached
 int world_map_refuses(const mv_gym *g, const std::string &who, const char *clause);
 void world_map_obs_free(mv_gym *g);    // mv_close
+// mv_scan_obs.hip: the scan fans of the frames whose planes o.depth and o.seg hold -> o.scan, ONE launch on the caller's stream, called wherever map_follow is
+// (an exact pass, or planes_follow, wrote the planes); v: the tick's view; -> launches made (0: nothing attached), -1
+int scan_follow(mv_gym *g, const GymView &v, const OutPtrs &o);
+void scan_obs_free(mv_gym *g);         // mv_close
 // What the calls that an attached stream forbids answer (mv_api.hip), each walking obs_streams and composing "<who>: <noun> are attached (<setter>), <clause>:
-// detach the <noun> first" for the first stream that is on; -> -1 with that text, 0: none is.  ring_sized_attached: all nine, sized by the ring count they
+// detach the <noun> first" for the first stream that is on; -> -1 with that text, 0: none is.  ring_sized_attached: all ten, sized by the ring count they
 // were attached under.  planes_attached: the three plane streams, with the caller's clause.  still_clause: why still frames and a plane stream exclude each other
 // (mv_set_still_frames; the plane setters' own refusal)
 int ring_sized_attached(const mv_gym *g, const char *who);

@@ -49,6 +49,7 @@ struct StepCall {
                               // drawn tick for whichever of the three are attached (the log: per gym, logCapacity)
     bool visible;             // ... and the visible-entity rows behind the label planes of a drawn tick, in either pixel mode (mv_set_visible_obs)
     bool map;                 // ... and the map grids behind the depth and label planes of a drawn tick, likewise (mv_set_map_obs)
+    bool scan;                // ... and the scan fans behind the same two planes, likewise (mv_set_scan_obs)
     bool worldMap;            // ... and the same frames merged into the agents' world map grids (mv_set_world_map_obs)
     bool timeCall, timeTicks;   // timing (mv_profile_begin): ONE entry for the whole call (callEv), or one per tick for the first tickEvs ticks (tickEv);
     hipEvent_t *callEv = nullptr, *tickEv = nullptr;   // reserve_timing takes the entries, behind the checks and the refill as always
@@ -141,6 +142,7 @@ struct StepCall {
         // follower rules them out already, exact pixels: PASS_BATCH is not taken)
         visible = n == 1 && L->visible.buf != nullptr && (r.render || drawLast);
         map = n == 1 && L->map.buf != nullptr && (r.render || drawLast);   // (mv_set_map_obs: the same)
+        scan = n == 1 && L->scan.buf != nullptr && (r.render || drawLast);   // (mv_set_scan_obs: the same)
         worldMap = n == 1 && L->worldMap != nullptr && r.render;   // (mv_set_world_map_obs: every tick is drawn -- the entry points refuse the other calls)
         // overlapped passes (mv_set_pass_overlap): this call's one launch goes to an internal stream
         // (an env must not finish in two consecutive calls: their passes may publish its true objective in either order -- episodes of at least
@@ -549,11 +551,18 @@ struct StepCall {
                     if (rc < 0) return -1;
                     L->launchCount[1] += rc;
                 }
+            // the scan fans (mv_set_scan_obs): the same again, out of the same two planes
+            if (scan)
+                for (int j = j0; j < j1; ++j) {
+                    const int rc = scan_follow(L, views[(size_t)j], outs[(size_t)j]);
+                    if (rc < 0) return -1;
+                    L->launchCount[1] += rc;
+                }
             // the world map grids (mv_set_world_map_obs; exact pixels: behind each tick's pass, passes_tick)
             if (tickOrder && world_map_tick(j0)) return -1;
         }
         if (mc && mc->last) ++L->ringTick;
-        if ((anyLog || rows || carry || depth || visible || map || worldMap) && own) HIP_TRY(hipEventRecord(mark(), L->stream));
+        if ((anyLog || rows || carry || depth || visible || map || scan || worldMap) && own) HIP_TRY(hipEventRecord(mark(), L->stream));
         if (own) {
             ++L->markCount;
             for (int i = 0; i < n; ++i) gs[i]->markCount = L->markCount;

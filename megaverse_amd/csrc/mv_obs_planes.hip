@@ -73,6 +73,10 @@ int planes_attach(mv_gym *g, const Planes &rec, void *device_buf, int format)
     // (mv_set_world_map_obs: the same)
     if ((rec.planes == &mv_gym::seg || rec.planes == &mv_gym::depth) && world_map_refuses(g, who, "which are merged out of the depth and label planes as they stand"))
         return -1;
+    // (mv_set_scan_obs: the same)
+    if ((rec.planes == &mv_gym::seg || rec.planes == &mv_gym::depth) && g->scan.buf)
+        return fail(who + ": " + obs_stream(OPT_SCAN_OBS).noun + " are attached (" + gym_options[OPT_SCAN_OBS].setter
+                    + "), which are binned out of the depth and label planes as they stand: detach the " + obs_stream(OPT_SCAN_OBS).noun + " first");
     if (!device_buf) {
         // No launch, no copy: the launches enqueued so far keep the pointers they were given; the next pass writes no plane.
         p = ObsPlanes();

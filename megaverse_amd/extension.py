@@ -136,6 +136,10 @@ SYMBOLS = [
     ("mv_world_map_obs_cells", C.c_int, [_P]), ("mv_get_world_map_observation", C.c_int, [_P, _I, _I, _P]),
     ("mv_debug_world_map_host", C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, C.c_float, C.c_float, C.c_float, _I, _P]),
     ("mv_debug_world_map_device", C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, C.c_float, C.c_float, C.c_float, _I, _P]),
+    ("mv_set_scan_obs", C.c_int, [_P, _P, _I, C.c_float, C.c_float]), ("mv_get_scan_obs", C.c_int, [_P]), ("mv_scan_obs_beams", C.c_int, [_P]),
+    ("mv_get_scan_observation", C.c_int, [_P, _I, _I, _P]),
+    ("mv_debug_scan_host", C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, C.c_float, C.c_float, _P]),
+    ("mv_debug_scan_device", C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, C.c_float, C.c_float, _P]),
     ("mv_set_overview", C.c_int, [_P, _I, _I, _P]), ("mv_set_overview_cameras", C.c_int, [_P, _P]), ("mv_set_overview_cameras_host", C.c_int, [_P, _P]),
     ("mv_get_overview_observation", C.c_int, [_P, _I, _P]), ("mv_overview_device_ptr", _P, [_P]), ("mv_overview_dropped", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("mv_overview_capacity", C.c_int, [_P]), ("mv_overview_default_camera", C.c_int, [_P]), ("mv_debug_overview_camera_host", C.c_int, [_P, _P, _P]),
@@ -596,6 +600,71 @@ def debug_map_device(depth, seg, cam12, cells, cell_size):
         rc = lib.mv_debug_map_device(_P(int(depth.data_ptr())), MV_DEPTH_F32 if depth.dtype == torch.float32 else MV_DEPTH_F16, _P(int(seg.data_ptr())),
                                      MV_SEG_CLASS_U8 if seg.dtype == torch.uint8 else MV_SEG_INSTANCE_U16, int(depth.shape[1]), int(depth.shape[0]),
                                      _P(int(cam12.data_ptr())), int(cells), float(cell_size), _P(int(out.data_ptr())))
+    if rc != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
+
+# include/megaverse_hip.h: MV_SCAN_OBS_PLANES and the planes of a scan observation (mv_set_scan_obs; megaverse_amd/csrc/mv_scan_obs.h has the rule): per beam
+# of one agent's fan the horizontal distance to the nearest kept pixel in units of SCAN_RANGE_UNIT (-1: none), that pixel's class (SEG_CLASSES; 0: none) and
+# the pixels kept (saturated at 32767).  SCAN_DEFAULT_BAND: set_scan_obs's height band over the eye (its docstring derives the numbers)
+MV_SCAN_OBS_PLANES = 3
+SCAN_OBS_FIELDS = ("range", "class", "count")
+SCAN_RANGE_UNIT = 1 / 64
+SCAN_DEFAULT_BAND = (-1.0, 0.5)
+_SCAN_TAN_HALF_FOV = 1.19175359   # (mv_frame.h: TAN_HALF_FOV, tan(100 deg / 2))
+
+
+def scan_beam_tangents(beams):
+    """-> float64 [beams]: u / f at the centre of every beam of a scan of `beams` beams, left to right (mv_scan_obs.h: beam i holds the pixels with
+    i - beams/2 <= (u / f) (beams/2) / TAN_HALF_FOV < i + 1 - beams/2).  numpy.arctan of it is the beams' bearings, positive to the right; they are evenly
+    spaced in the tangent, not in the angle"""
+    beams = int(beams)
+    return (np.arange(beams) + 0.5 - beams // 2) * (_SCAN_TAN_HALF_FOV / (beams // 2))
+
+
+def _scan_planes(who, depth, seg, cam12):
+    """the shared argument check of the two numpy-side scan hooks -> contiguous depth, seg, cam"""
+    depth, seg = np.ascontiguousarray(depth), np.ascontiguousarray(seg)
+    if depth.ndim != 2 or seg.shape != depth.shape:
+        raise ValueError(f"{who}: depth and seg must be planes [h, w] of one shape")
+    if depth.dtype not in (np.float32, np.float16, np.uint16) or seg.dtype not in (np.uint8, np.uint16):
+        raise ValueError(f"{who}: depth is float32 / float16 / uint16 bits, seg uint8 / uint16")
+    cam = np.ascontiguousarray(cam12, np.float32).ravel()
+    if cam.size != 12:
+        raise ValueError(f"{who}: cam12 is eye(3) c(9)")
+    return depth, seg, cam
+
+
+def debug_scan_host(depth, seg, cam12, beams, h_lo, h_hi, depth_format=None, seg_format=None):
+    """mv_debug_scan_host: the scan rule on the CPU (no device): debug_map_host's depth [h, w], seg [h, w] and cam12 -> int16 [3, beams] (SCAN_OBS_FIELDS).  The
+    formats follow the arrays' dtypes unless given (the library's words, for the refusal tests)"""
+    lib = load_library()
+    depth, seg, cam = _scan_planes("debug_scan_host", depth, seg, cam12)
+    dfmt = (MV_DEPTH_F32 if depth.dtype == np.float32 else MV_DEPTH_F16) if depth_format is None else int(depth_format)
+    sfmt = (MV_SEG_CLASS_U8 if seg.dtype == np.uint8 else MV_SEG_INSTANCE_U16) if seg_format is None else int(seg_format)
+    out = np.empty((MV_SCAN_OBS_PLANES, max(int(beams), 0)), np.int16)
+    if lib.mv_debug_scan_host(depth.ctypes.data, dfmt, seg.ctypes.data, sfmt, int(depth.shape[1]), int(depth.shape[0]), cam.ctypes.data, int(beams), float(h_lo),
+                              float(h_hi), out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
+
+def debug_scan_device(depth, seg, cam12, beams, h_lo, h_hi):
+    """mv_debug_scan_device: the scan KERNEL on one frame: debug_map_device's depth, seg and cam12 (contiguous CUDA tensors) -> a new int16 CUDA tensor
+    [3, beams]; waits for the launch"""
+    import torch
+    lib = load_library()
+    if depth.dim() != 2 or seg.shape != depth.shape or not (depth.is_cuda and seg.is_cuda and cam12.is_cuda) or not (depth.is_contiguous() and seg.is_contiguous()) \
+            or depth.dtype not in (torch.float32, torch.float16) or seg.dtype not in (torch.uint8, torch.int16, torch.uint16) \
+            or cam12.dtype != torch.float32 or cam12.numel() != 12 or not cam12.is_contiguous():
+        raise ValueError("debug_scan_device: depth [h, w] float32 / float16, seg [h, w] uint8 / int16 / uint16, cam12 float32 [12], contiguous CUDA tensors")
+    out = torch.zeros((MV_SCAN_OBS_PLANES, int(beams)), dtype=torch.int16, device=depth.device)
+    torch.cuda.synchronize(depth.device)   # (the hook launches on the null stream: behind what torch's stream holds)
+    with torch.cuda.device(depth.device):
+        rc = lib.mv_debug_scan_device(_P(int(depth.data_ptr())), MV_DEPTH_F32 if depth.dtype == torch.float32 else MV_DEPTH_F16, _P(int(seg.data_ptr())),
+                                      MV_SEG_CLASS_U8 if seg.dtype == torch.uint8 else MV_SEG_INSTANCE_U16, int(depth.shape[1]), int(depth.shape[0]),
+                                      _P(int(cam12.data_ptr())), int(beams), float(h_lo), float(h_hi), _P(int(out.data_ptr())))
     if rc != 0:
         raise RuntimeError(lib.mv_last_error().decode())
     return out
@@ -1063,6 +1132,12 @@ def check_world_map_obs(buf, num_frames, cells, device):
     return _check_obs_tensor(buf, int(num_frames), (MV_MAP_OBS_PLANES, int(cells), int(cells)), OBS_STREAMS['world_map'].dtypes(None), device, 'set_world_map_obs')
 
 
+def check_scan_obs(buf, entries, num_frames, beams, device):
+    """the argument check of MegaverseGym.set_scan_obs for a tensor: contiguous torch.int16 of shape (entries, num_frames, 3, beams) on CUDA device `device`;
+    entries None: any number of entries (the check made before the gym is asked for its ring count)"""
+    return _check_obs_tensor(buf, entries, (int(num_frames), MV_SCAN_OBS_PLANES, int(beams)), OBS_STREAMS['scan'].dtypes(None), device, 'set_scan_obs')
+
+
 def _check_obs_tensor(buf, entries, tail, dtypes, device, who):
     """the one tensor check of the observation streams, for the setter `who`: contiguous, one of `dtypes` (torch dtype names), of shape (entries,) + tail on
     CUDA device `device`; entries None: any number of entries (the check made before the gym is asked for its ring count) -> buf"""
@@ -1078,7 +1153,7 @@ def _check_obs_tensor(buf, entries, tail, dtypes, device, who):
     return buf
 
 
-# The nine per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
+# The ten per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
 # of the gym (a read-back's row is that shape without its first extent), format -> the torch dtype names a tensor may have (the first: what True allocates),
 # the arguments behind the null pointer of a detach, the numpy dtype a read-back hands out.  A new stream is one row here.
 _ObsStream = collections.namedtuple('_ObsStream', 'setter reader tail dtypes detach read')
@@ -1104,6 +1179,8 @@ OBS_STREAMS = {
     'world_map': _ObsStream('mv_set_world_map_obs', 'mv_get_world_map_observation',
                             lambda g: (g.num_envs * g.num_agents_per_env, MV_MAP_OBS_PLANES, g._world_map_cells, g._world_map_cells), lambda fmt: ('torch.int16',),
                             (0, 0.0, 0.0, 0.0), np.int16),
+    'scan': _ObsStream('mv_set_scan_obs', 'mv_get_scan_observation',
+                       lambda g: (g.num_envs * g.num_agents_per_env, MV_SCAN_OBS_PLANES, g._scan_beams), lambda fmt: ('torch.int16',), (0, 0.0, 0.0), np.int16),
 }
 
 
@@ -1312,6 +1389,7 @@ class MegaverseGym:
         self._obs = {}               # set_*_obs: stream name (OBS_STREAMS) -> the attached tensor
         self._map_cells = 0          # set_map_obs: the grid's edge in cells (the 'map' stream's shape)
         self._world_map_cells = 0    # set_world_map_obs: the same of the 'world_map' stream
+        self._scan_beams = 0         # set_scan_obs: the fan's beams (the 'scan' stream's shape)
         self._ring_ticks = 0         # ticks stepped through this object since set_output_ring (the library's own count: which entry the last tick went to)
         self._macro_held = None      # macro_step: the caller's device tensors of the last call, read in stream order: kept until the next macro step
         self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
@@ -1939,6 +2017,42 @@ class MegaverseGym:
         out = np.empty(12, np.float32)
         self._ck(self._lib.mv_debug_map_camera(self._g, int(env_idx), int(agent_idx), out.ctypes.data))
         return out
+
+    def set_scan_obs(self, buf=True, beams=64, band=SCAN_DEFAULT_BAND):
+        """Scan observations (include/megaverse_hip.h: mv_set_scan_obs): a 1-D range fan per agent, the compact input of a navigation policy.  Every frame a
+        later observation pass draws -- the passes set_depth_obs names -- leaves 3 planes of `beams` int16 per AGENT (SCAN_OBS_FIELDS: range, class, count):
+        the frame's pixels unprojected with its camera, those inside the height band kept, and binned by bearing into beams that are evenly spaced on the
+        image plane (scan_beam_tangents), beam 0 leftmost; per beam the horizontal distance from the eye to the nearest kept pixel in units of SCAN_RANGE_UNIT
+        (-1: none), that pixel's class (0: none) and how many pixels were kept (saturated at 32767).  No ray is cast: a scan sees what the agent's camera
+        sees -- its 100-degree horizontal field of view, nothing behind an occluder the frame does not show; it is not a 360-degree sensor.  Entry
+        t % entries of an int16 CUDA tensor [entries, num_envs * num_agents, 3, beams], entries = the output ring's count, or 1 without a ring.  Needs
+        set_depth_obs and set_seg_obs first (either format each), and both stay attached as they are while this is.  beams: a multiple of 8 in [8, 256];
+        band = (h_lo, h_hi): two finite heights over the EYE in world units, h_lo < h_hi.  The default (-1.0, 0.5): an agent's eye is 0.05 + 0.41 = 0.46 over
+        its capsule's centre (mv_frame.h: the cameras) and the centre rests CAP_HH + CAP_R = 0.525 + 0.33 = 0.855 over the floor it stands on
+        (mv_physics.h), so the floor lies at -1.315 and a wall one voxel (1.0) high spans [-1.315, -0.315]: h_lo = -1.0 is 0.315 above the floor and 0.685
+        below that wall's top; h_hi = 0.5 keeps what reaches up to 1.815 over the floor and drops the room's upper walls' far tops and anything overhead.
+        True allocates the tensor on the gym's device and returns it; a tensor is checked (ValueError) and attached; None detaches.  One launch per drawn tick
+        behind the planes; nothing waits on the host.  While attached, set_output_ring and set_render_resolution are refused."""
+        if buf is not None:
+            if isinstance(beams, (bool, np.bool_)) or not isinstance(beams, (int, np.integer)) or not 8 <= int(beams) <= 256 or int(beams) % 8:
+                raise ValueError(f"set_scan_obs: beams must be a multiple of 8 in [8, 256], got {beams!r}")
+            if not isinstance(band, (tuple, list)) or len(band) != 2 or not all(np.isfinite(float(x)) for x in band) or not float(band[0]) < float(band[1]):
+                raise ValueError(f"set_scan_obs: band must be two finite numbers (h_lo, h_hi) with h_lo < h_hi, got {band!r}")
+            self._scan_beams = int(beams)
+        return self._attach_obs('scan', buf, None if buf is None else (int(beams), float(band[0]), float(band[1])))
+
+    def scan_obs_ring(self):
+        """-> the tensor set_scan_obs attached, [entries, num_envs * num_agents, 3, beams] (entry t % entries: the fans of tick t's frames), or None"""
+        return self._obs.get('scan')
+
+    def scan_obs(self):
+        """-> the entry of the last tick, (num_envs * num_agents, 3, beams): a view of the attached tensor, valid in the order of the gym's stream; None with
+        nothing attached.  A tick that drew no frame wrote nothing there.  With an output ring: the entry the last tick stepped through this object went to"""
+        return self._obs_last('scan')
+
+    def get_scan_observation(self, env_idx, agent_idx):
+        """-> numpy int16 [3, beams]: the scan of one agent in the last tick's entry (waits for the gym's stream)"""
+        return self._read_obs('scan', env_idx, agent_idx)
 
     def set_world_map_obs(self, buf=True, cells=64, cell_size=0.5, origin=(0.0, 0.0)):
         """World map observations (include/megaverse_hip.h: mv_set_world_map_obs): an ALLOCENTRIC top-down grid per agent, kept over an episode.  ONE int16 CUDA

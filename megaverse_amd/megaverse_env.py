@@ -18,7 +18,7 @@ Differences, all additive:
 import numpy as np
 
 from . import spaces
-from .extension import ENTITY_OBS_FIELDS, MAP_OBS_FIELDS, MEGAVERSE8, MegaverseGym, SCENARIOS, SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS, STATE_OBS_FIELDS, VISIBLE_OBS_FIELDS, \
+from .extension import ENTITY_OBS_FIELDS, MAP_OBS_FIELDS, MEGAVERSE8, MegaverseGym, SCAN_DEFAULT_BAND, SCAN_OBS_FIELDS, SCENARIOS, SCENE_OBS_FIELDS, SCENE_OBS_SCENARIO_FIELDS, STATE_OBS_FIELDS, VISIBLE_OBS_FIELDS, \
     render_mode_of, set_megaverse_log_level
 
 OBSTACLES_MULTITASK = ['ObstaclesWalls', 'ObstaclesSteps', 'ObstaclesLava', 'ObstaclesEasy', 'ObstaclesHard']
@@ -69,7 +69,7 @@ class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
                  img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1,
                  still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False, overview=None, normal_obs=False, visible_obs=False, map_obs=False,
-                 world_map_obs=False):
+                 world_map_obs=False, scan_obs=False):
         if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
         # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
@@ -146,10 +146,19 @@ class MegaverseEnv:
             world_map_obs = (64, 0.5, (0.0, 0.0)) if world_map_obs is True else (world_map_obs[0], float(world_map_obs[1]), tuple(world_map_obs[2]))
             depth_obs = depth_obs or "float16"
             seg_obs = seg_obs or "class"
+        #   scan_obs (True: 64 beams, the default height band; (beams, h_lo, h_hi)): every drawn frame leaves a 1-D range fan per AGENT, 3 planes of `beams`
+        #     int16 (SCAN_OBS_FIELDS: range, class, count; mv_set_scan_obs) out of the same two planes, attached likewise
+        if scan_obs is not False:
+            if scan_obs is not True and not (isinstance(scan_obs, (tuple, list)) and len(scan_obs) == 3):
+                raise ValueError(f"scan_obs must be False, True or (beams, h_lo, h_hi), got {scan_obs!r}")
+            scan_obs = (64, SCAN_DEFAULT_BAND) if scan_obs is True else (scan_obs[0], (float(scan_obs[1]), float(scan_obs[2])))
+            depth_obs = depth_obs or "float16"
+            seg_obs = seg_obs or "class"
         wanted = (("state", state_obs, ()), ("scene", scene_obs, ()), ("entity", entity_obs, ()),
                   ("depth", depth_obs, ("float32" if depth_obs is True else depth_obs,)), ("seg", seg_obs, ("class" if seg_obs is True else seg_obs,)),
                   ("normal", normal_obs, ("float16" if normal_obs is True else normal_obs,)), ("visible", bool(visible_obs), ()),   # (behind "seg")
-                  ("map", map_obs is not False, map_obs), ("world_map", world_map_obs is not False, world_map_obs))   # (behind "depth" and "seg")
+                  ("map", map_obs is not False, map_obs), ("world_map", world_map_obs is not False, world_map_obs),
+                  ("scan", scan_obs is not False, scan_obs))   # (behind "depth" and "seg")
         self._streams = {name: args for name, on, args in wanted if on}
         self._world_map = None   # world_map_obs: the one tensor of grids (_attach_stream)
         if "state" in self._streams:
@@ -248,6 +257,15 @@ class MegaverseEnv:
         if buf is None:
             raise RuntimeError("world_map_obs(): created without world_map_obs")
         return buf.view(self.num_envs, self.num_agents_per_env, *buf.shape[1:])
+
+    SCAN_OBS_FIELDS = SCAN_OBS_FIELDS   # the planes of a scan_obs() fan, in order
+
+    def scan_obs(self):
+        """the last tick's scans: int16 (num_envs, num_agents_per_env, 3, beams) on the device, planes SCAN_OBS_FIELDS -- per agent a fan of beams over its
+        camera's horizontal field of view, beam 0 leftmost (megaverse_amd.scan_beam_tangents): per beam the horizontal distance to the nearest pixel inside
+        the height band in units of megaverse_amd.SCAN_RANGE_UNIT (-1: none), that pixel's class and the pixels kept -- a view of the attached buffer, under
+        state_obs()'s rules: ask again after every call.  A tick that drew no frame wrote nothing.  Needs MegaverseEnv(..., scan_obs=True | (beams, h_lo, h_hi))."""
+        return self._stream_entry("scan", self.env.scan_obs_ring(), per_agent_planes=True)
 
     def _attach_stream(self, name, on=True):
         """one wanted stream's tensor attached (a new one, of the output ring's depth) or detached"""

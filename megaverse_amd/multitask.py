@@ -217,6 +217,10 @@ class MultiTaskGym:
         """world map observations (MegaverseGym.set_world_map_obs) are per gym: a group's union launches write none, and the library refuses"""
         raise _per_gym("set_world_map_obs", "world map observations", "write")
 
+    def set_scan_obs(self, buf=True, beams=64, band=None):
+        """scan observations (MegaverseGym.set_scan_obs) are per gym: a group's union launches write none, and the library refuses"""
+        raise _per_gym("set_scan_obs", "scan observations", "write")
+
     def set_overview(self, w, h, buf=True):
         """overview cameras (MegaverseGym.set_overview) are per gym: a group's union launches draw none, and the library refuses"""
         raise _per_gym("set_overview", "an overview", "draw")
