@@ -604,6 +604,42 @@ int mv_debug_scan_host(const void *depth, int32_t depth_format, const void *seg,
                        float h_lo, float h_hi, int16_t *out);   /* the rule on the CPU, no device */
 int mv_debug_scan_device(const void *depth, int32_t depth_format, const void *seg, int32_t seg_format, int32_t w, int32_t h, const float *cam12, int32_t beams,
                          float h_lo, float h_hi, int16_t *out);   /* the kernel on one frame; every pointer a device pointer */
+/* Stack observations (no reference counterpart): the FRAME STACK a pixel policy without a recurrent core puts in front of its CNN, kept on the device: per
+ * AGENT the last S = frames drawn frames, each downsampled by `factor` and -- MV_STACK_GRAY_U8 -- made grey, oldest first.  uint8 [N*A][S][C][h][w], h = H /
+ * factor, w = W / factor, C = 1 (MV_STACK_GRAY_U8) or 3 (MV_STACK_RGB_U8: planes R, G, B); plane-set S - 1 is the newest frame; row 0 is the bottom row, as in
+ * the frames.  It reads nothing but the colour frames the pass writes, in either layout (mv_set_obs_layout) and either pixel mode, so it needs no other stream.
+ * The image of a frame, in integers (megaverse_amd/csrc/mv_stack_obs.h states the rule for the kernel and the host alike): R, G, B = the sums of the colour
+ * bytes over the factor x factor block of frame pixels under an output pixel (alpha is not read);
+ *   MV_STACK_RGB_U8   c_out = (sum_c + factor^2 / 2) / factor^2 per channel
+ *   MV_STACK_GRAY_U8  (77 R + 150 G + 29 B + 128 factor^2) >> (8 + 2 log2 factor) -- the weights sum to 256; ONE rounding
+ * so a stack is reproducible byte for byte.  The stack of a drawn frame: if the frame is the first of a new episode all S plane-sets are the image; otherwise
+ * out[i] = prev[i + 1] for i < S - 1 and out[S - 1] = the image, prev being the agent's stack in the entry the previous drawn tick wrote (with one entry the
+ * same memory: shifted in place).  A stack never mixes the frames of two episodes.  "First of a new episode" is the world map's condition (mv_set_world_map_obs):
+ * the tick's own done[env] -- in a batched call the tick's staged value --; the frame mv_reset draws; the frame mv_reset_envs*(render = 1) draws, for a
+ * flagged env that took its next episode (the other envs' stacks shift: the frame is drawn for them too).  mv_render images the newest plane-set again and
+ * shifts nothing.  An undrawn frame writes nothing.
+ * A tick that is not drawn would tear the stack, so while stacks are attached mv_step_no_render, mv_step_n_render with MV_RENDER_LAST or MV_RENDER_NONE,
+ * mv_macro_step*, mv_reset_envs*(render = 0), mv_set_draw_mask* and mv_set_still_frames are refused, and the attach is refused beside a draw mask or still
+ * frames; so are mv_set_output_ring, mv_set_render_resolution and mv_set_obs_layout.  Each refusal names mv_set_stack_obs.
+ * mv_set_stack_obs: device_buf is uint8 [entries][N*A][S][C][h][w], 16-byte aligned, entries = the output ring's count at the moment of the call, or 1;
+ * frames in [1, 8]; factor 1, 2 or 4; the observation's width and height multiples of factor, and w a multiple of 4; anything else is refused with a text that
+ * says so.  ONE launch per drawn tick on the gym's stream behind the pass that drew the tick's frames (counted in out[1] of mv_debug_launch_counts), no host
+ * wait; the call is an ordering point; NULL detaches (the other arguments are then not read); mv_close forgets the pointer; refused for the gyms of an mv_group
+ * or an mv_step_many call.  The buffer is NOT cleared by the attach: the first launch behind it shifts this entry's own bytes unless it refills (mv_reset
+ * does).  mv_draw_hires and the overview ignore it.  A gym without it launches exactly what it launched.
+ * mv_stack_obs_shape: S, C, h, w (zeros: none attached).  mv_get_stack_observation: one agent's [S][C][h][w] in the LAST TICK's entry, after waiting for the
+ * gym's stream.  mv_debug_stack_host: the rule on the CPU for ONE frame of w x h pixels in `layout` (MV_OBS_RGBA / MV_OBS_RGB_PLANAR): prev [S][C][h/f][w/f]
+ * -> out, clear != 0: the frame is the first of a new episode; prev == out: in place; no device.  mv_debug_stack_device: the same arguments as DEVICE
+ * pointers (the frame 4-byte, the stacks 16-byte aligned): the very kernel on that one frame, on the current device's null stream, waited for. */
+enum { MV_STACK_GRAY_U8 = 0, MV_STACK_RGB_U8 = 1 };
+int mv_set_stack_obs(mv_gym *g, void *device_buf, int32_t frames, int32_t factor, int32_t format);   /* uint8 [max(1, ring count)][N*A][S][C][h][w]; NULL detaches */
+int mv_get_stack_obs(const mv_gym *g);                    /* 0: none, else the number of entries; -1: no gym */
+int mv_stack_obs_shape(const mv_gym *g, int32_t out4[4]); /* S, C, h, w; zeros: none attached */
+int mv_get_stack_observation(mv_gym *g, int32_t env_idx, int32_t agent_idx, uint8_t *out_host);   /* [S][C][h][w] uint8; waits for the gym's stream */
+int mv_debug_stack_host(const void *frame, int32_t layout, int32_t w, int32_t h, int32_t frames, int32_t factor, int32_t format, int32_t clear, const uint8_t *prev,
+                        uint8_t *out);   /* the rule on the CPU, no device */
+int mv_debug_stack_device(const void *frame, int32_t layout, int32_t w, int32_t h, int32_t frames, int32_t factor, int32_t format, int32_t clear, const uint8_t *prev,
+                          uint8_t *out);   /* the kernel on one frame; every pointer a device pointer */
 /* Episode budgets (no reference counterpart: VectorEnv::step resets a finished env on the spot and steps on, vector_env.cpp:89-108).  Per env e the gym owns an
  * int32 left[e]:  < 0: unlimited -- what every env is without these calls;  > 0: the env may still finish that many episodes;  0: the env is HALTED.
  * Tick t, env e, left[e] as it stands before the tick (megaverse_amd/csrc/mv_episode_budget.h states the rule for kernels and host alike):

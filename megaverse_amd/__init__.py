@@ -7,6 +7,7 @@ Python surface (megaverse/megaverse_env.py) plus batched / multi-GPU helpers.
 from .extension import MegaverseGym, set_megaverse_log_level, load_library, SEG_CLASSES, seg_split, normals_to_float  # noqa: F401
 from .extension import ENTITY_OBS_FIELDS, MAP_HEIGHT_UNIT, MAP_OBS_FIELDS, VISIBLE_OBS_FIELDS, entity_layout, entity_row_of, entity_rows  # noqa: F401
 from .extension import SCAN_DEFAULT_BAND, SCAN_OBS_FIELDS, SCAN_RANGE_UNIT, scan_beam_tangents  # noqa: F401
+from .extension import STACK_FORMATS, STACK_GRAY_WEIGHTS, stack_shape  # noqa: F401
 from .extension import CAMERA_DTYPE, MV_CAMERA_FIRST_PERSON, follow, look_at, overview_default_camera  # noqa: F401
 from .megaverse_env import MegaverseEnv, MEGAVERSE8, OBSTACLES_MULTITASK, make_env_multitask  # noqa: F401
 from .multitask import MultiTaskGym, MEGAVERSE_IN_SCOPE  # noqa: F401

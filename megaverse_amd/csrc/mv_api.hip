@@ -131,6 +131,7 @@ OutPtrs outputs_of(const mv_gym *g, unsigned long long tick)
     o.visible = g->visible.entry(tick);   // (mv_set_visible_obs: the same)
     o.map = g->map.entry(tick);           // (mv_set_map_obs: the same)
     o.scan = g->scan.entry(tick);         // (mv_set_scan_obs: the same)
+    o.stack = g->stack.entry(tick);       // (mv_set_stack_obs: the same)
     return o;
 }
 OutPtrs last_outputs(const mv_gym *g) { return outputs_of(g, g->ringTick ? g->ringTick - 1 : 0); }   // of the last tick (reset / render / getters)
@@ -754,6 +755,7 @@ int mv_close(mv_gym *g)
     map_obs_free(g);
     world_map_obs_free(g);
     scan_obs_free(g);
+    stack_obs_free(g);
     episode_budget_free(g);
     macro_step_free(g);
     still_frames_free(g);
@@ -834,6 +836,7 @@ int mv_set_obs_layout(mv_gym *g, int32_t layout)
     if (check(g)) return -1;
     if (layout != MV_OBS_RGBA && layout != MV_OBS_RGB_PLANAR) return fail("mv_set_obs_layout: layout must be MV_OBS_RGBA (0) or MV_OBS_RGB_PLANAR (1)");
     if (g->inGroup) return fail("mv_set_obs_layout: the gym belongs to a group (set the layout before mv_group_create)");
+    if (stack_refuses(g, "mv_set_obs_layout", "which are made of the frames in the layout they were attached under")) return -1;   // (mv_set_stack_obs)
     if (g->layoutFixed)
         return fail("mv_set_obs_layout: call it before the gym's first mv_reset, mv_render, mv_set_obs_buffer or mv_set_output_ring");
     if (still_frames_touch(g)) return -1;   // (mv_set_still_frames: every env stale)
@@ -931,6 +934,7 @@ int mvapi::render_frames(mv_gym *g, const WorldMapClear &clear)
     const PlaneOuts po = plane_outs(g, o);
     if (launch_raster(v, o.obs, g->w, g->h, g->stream, nullptr, g->fastPixels, 0, nullptr, nullptr, g->fastPixels ? nullptr : &po))
         return fail("mv_render: observation size above 1024x1024");
+    if (stack_follow(g, v, o, clear) < 0) return -1;   // (mv_set_stack_obs: behind the pass itself -- the colour frames are all it reads; refilled where the caller says)
     if (g->fastPixels && planes_follow(g, v, o, "mv_render") < 0) return -1;
     if (visible_follow(g, v, o) < 0) return -1;   // (mv_set_visible_obs: behind the frame's label planes, whichever launch wrote them)
     if (map_follow(g, v, o) < 0) return -1;       // (mv_set_map_obs: behind the frame's depth and label planes, likewise)

@@ -21,6 +21,8 @@
 //   mv_world_map_obs.hip  world map observations: the merging kernel behind a drawn tick's depth and label planes, its launch, the entry points
 //                     (mv_world_map_obs.h: the rule)
 //   mv_scan_obs.hip   scan observations: the beam-binning kernel behind a drawn tick's depth and label planes, its launch, the entry points (mv_scan_obs.h: the rule)
+//   mv_stack_obs.hip  stack observations: the kernel that downsamples a drawn tick's colour frames into the agents' frame stacks, its launch, the entry points
+//                     (mv_stack_obs.h: the rule)
 //   mv_episode_budget.hip  episode budgets: attaching, detaching and reading the per-env counts that halt envs (mv_episode_budget.h: the rule)
 //   mv_macro_step.hip macro steps: the launch that starts a call's per-env tick counts, the accumulating publication, the entry points (mv_macro_step.h: the rule)
 //   mv_overview.hip   overview cameras: attaching the buffer, the overview's own arrays, the cameras' two forms, mv_draw_overview (mv_overview.h: the rule;
@@ -358,6 +360,12 @@ struct mv_gym {
     ObsPlanes scan;
     int scanBeams = 0;
     float scanBand[2] = {0.0f, 0.0f};
+    // mv_set_stack_obs: the caller's frame stacks [entries][N*A][S][C][h][w] uint8, written out of the tick's colour frames by one launch behind the pass that drew
+    // them (format: MV_STACK_GRAY_U8 / MV_STACK_RGB_U8); stackFrames = S, stackFactor: the downsampling factor; stackLast: the entry the latest drawn tick wrote,
+    // which the next launch shifts from (null: none since the attach)
+    ObsPlanes stack;
+    int stackFrames = 0, stackFactor = 0;
+    void *stackLast = nullptr;
     // mv_set_overview: the overview cameras' frames and arrays
     OverviewState overview;
     // mv_set_episode_budget: one gym-owned allocation (mv_episode_budget.h: episode_budget_words), made at first use and counted in mv_arena_bytes --
@@ -403,7 +411,7 @@ struct GymOption {
     const char *memberNone;   // attach_check: "whose union launches <memberNone>"
     bool (*on)(const mv_gym *);
 };
-enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_MAP_OBS, OPT_WORLD_MAP_OBS, OPT_SCAN_OBS, OPT_DEPTH_OBS, OPT_VISIBLE_OBS, OPT_SEG_OBS, OPT_NORMAL_OBS, OPT_ENTITY_OBS, OPT_OVERVIEW, OPT_COUNT };
+enum : int { OPT_STEP_MASK = 0, OPT_DRAW_MASK, OPT_STILL_FRAMES, OPT_EPISODE_BUDGET, OPT_STATE_OBS, OPT_SCENE_OBS, OPT_MAP_OBS, OPT_WORLD_MAP_OBS, OPT_SCAN_OBS, OPT_STACK_OBS, OPT_DEPTH_OBS, OPT_VISIBLE_OBS, OPT_SEG_OBS, OPT_NORMAL_OBS, OPT_ENTITY_OBS, OPT_OVERVIEW, OPT_COUNT };
 #define MV_OPT_ON(expr) +[](const mv_gym *g) -> bool { return expr; }
 inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_step_mask", "a step mask attached", "read none", "detach it first", "detach the mask first", "read no step mask", MV_OPT_ON(g->stepMask.live)},
@@ -415,6 +423,7 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_map_obs", "map observations attached", "write none", "detach them first", "detach them first", "write no map observations", MV_OPT_ON(g->map.buf)},   // (in front of the depth and the labels it needs: named first, detached first)
     {"mv_set_world_map_obs", "world map observations attached", "write none", "detach them first", "detach them first", "write no world map observations", MV_OPT_ON(g->worldMap)},   // (likewise)
     {"mv_set_scan_obs", "scan observations attached", "write none", "detach them first", "detach them first", "write no scan observations", MV_OPT_ON(g->scan.buf)},   // (likewise)
+    {"mv_set_stack_obs", "stack observations attached", "write none", "detach them first", "detach them first", "write no stack observations", MV_OPT_ON(g->stack.buf)},
     {"mv_set_depth_obs", "depth observations attached", "write none", "detach them first", "detach them first", "write no depth observations", MV_OPT_ON(g->depth.buf)},
     {"mv_set_visible_obs", "visible-entity observations attached", "write none", "detach them first", "detach them first", "write no visible-entity observations", MV_OPT_ON(g->visible.buf)},   // (in front of the labels it needs: named first, detached first)
     {"mv_set_seg_obs", "segmentation observations attached", "write none", "detach them first", "detach them first", "write no segmentation observations", MV_OPT_ON(g->seg.buf)},
@@ -423,8 +432,8 @@ inline constexpr GymOption gym_options[OPT_COUNT] = {
     {"mv_set_overview", "an overview attached", "draw none", "detach it first", "detach it first", "draw no overview", MV_OPT_ON(g->overview.buf)},
 };
 #undef MV_OPT_ON
-// The ten per-tick observation streams, stated once, in the order mv_set_output_ring refuses them: the option that attaches the stream, the noun the refusal
-// texts name it by and, for the three plane streams (mv_obs_planes.hip) and the rows counted out of the label planes (mv_visible_obs.hip: in front of the labels, which they need) and the grids binned out of the depth and label planes (mv_map_obs.hip, mv_world_map_obs.hip: in front of both) and the fans binned out of the same two (mv_scan_obs.hip: likewise), the name of one plane; null: a row stream (mv_obs_rows.hip).  A new stream is one row
+// The eleven per-tick observation streams, stated once, in the order mv_set_output_ring refuses them: the option that attaches the stream, the noun the refusal
+// texts name it by and, for the three plane streams (mv_obs_planes.hip) and the rows counted out of the label planes (mv_visible_obs.hip: in front of the labels, which they need) and the grids binned out of the depth and label planes (mv_map_obs.hip, mv_world_map_obs.hip: in front of both) and the fans binned out of the same two (mv_scan_obs.hip: likewise) and the frame stacks made of the colour frames (mv_stack_obs.hip), the name of one plane; null: a row stream (mv_obs_rows.hip).  A new stream is one row
 // here, one in gym_options and one descriptor in its file.
 struct ObsStream {
     int opt;
@@ -435,6 +444,7 @@ inline constexpr ObsStream obs_streams[] = {
     {OPT_MAP_OBS, "map observations", "map grid"},
     {OPT_WORLD_MAP_OBS, "world map observations", "world map grid"},
     {OPT_SCAN_OBS, "scan observations", "scan fan"},
+    {OPT_STACK_OBS, "stack observations", "stack"},
     {OPT_DEPTH_OBS, "depth observations", "depth plane"},
     {OPT_VISIBLE_OBS, "visible-entity observations", "visible rows"},
     {OPT_SEG_OBS, "segmentation observations", "label plane"},
@@ -468,7 +478,8 @@ inline void fill_view_options(GymView &v, const mv_gym *g, bool macro)
 // visible (mv_set_visible_obs): the entry's visible-entity rows, likewise.
 // map (mv_set_map_obs): the entry's map grids, likewise.
 // scan (mv_set_scan_obs): the entry's scan fans, likewise.
-struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; void *depth = nullptr; void *seg = nullptr; void *normal = nullptr; void *visible = nullptr; void *map = nullptr; void *scan = nullptr; };
+// stack (mv_set_stack_obs): the entry's frame stacks, likewise.
+struct OutPtrs { uint32_t *obs; float *rewards; uint8_t *done; void *depth = nullptr; void *seg = nullptr; void *normal = nullptr; void *visible = nullptr; void *map = nullptr; void *scan = nullptr; void *stack = nullptr; };
 // the planes of one tick's entry and their formats, as the observation pass takes them (mv_raster.h: PlaneOuts; null: not attached)
 PlaneOuts plane_outs(const mv_gym *g, const OutPtrs &o);
 std::string lower(const char *s);
@@ -549,8 +560,17 @@ void world_map_obs_free(mv_gym *g);    // mv_close
 // (an exact pass, or planes_follow, wrote the planes); v: the tick's view; -> launches made (0: nothing attached), -1
 int scan_follow(mv_gym *g, const GymView &v, const OutPtrs &o);
 void scan_obs_free(mv_gym *g);         // mv_close
+// mv_stack_obs.hip: the frame stacks of the colour frames o.obs holds -> o.stack, ONE launch on the caller's stream behind the pass that drew them, in either pixel
+// mode; it shifts from the entry the previous drawn tick wrote (mv_gym::stackLast) and remembers this one.  clear: world_map_follow's -- which frames are the
+// first of a new episode, whose stacks are refilled with the frame; nothing set (mv_render): the newest plane-set is imaged again and nothing shifts.
+// -> launches made (0: nothing attached), -1
+int stack_follow(mv_gym *g, const GymView &v, const OutPtrs &o, const WorldMapClear &clear);
+// what a call that would leave a tick undrawn, or change the frames under the stacks, answers while they are attached: "<who>: stack observations are attached
+// (mv_set_stack_obs), <clause>: detach the stack observations first" -> -1; 0: none attached
+int stack_refuses(const mv_gym *g, const std::string &who, const char *clause);
+void stack_obs_free(mv_gym *g);        // mv_close
 // What the calls that an attached stream forbids answer (mv_api.hip), each walking obs_streams and composing "<who>: <noun> are attached (<setter>), <clause>:
-// detach the <noun> first" for the first stream that is on; -> -1 with that text, 0: none is.  ring_sized_attached: all ten, sized by the ring count they
+// detach the <noun> first" for the first stream that is on; -> -1 with that text, 0: none is.  ring_sized_attached: all eleven, sized by the ring count they
 // were attached under.  planes_attached: the three plane streams, with the caller's clause.  still_clause: why still frames and a plane stream exclude each other
 // (mv_set_still_frames; the plane setters' own refusal)
 int ring_sized_attached(const mv_gym *g, const char *who);

@@ -51,6 +51,7 @@ struct StepCall {
     bool map;                 // ... and the map grids behind the depth and label planes of a drawn tick, likewise (mv_set_map_obs)
     bool scan;                // ... and the scan fans behind the same two planes, likewise (mv_set_scan_obs)
     bool worldMap;            // ... and the same frames merged into the agents' world map grids (mv_set_world_map_obs)
+    bool stack;               // ... and the tick's colour frames downsampled into the agents' frame stacks (mv_set_stack_obs)
     bool timeCall, timeTicks;   // timing (mv_profile_begin): ONE entry for the whole call (callEv), or one per tick for the first tickEvs ticks (tickEv);
     hipEvent_t *callEv = nullptr, *tickEv = nullptr;   // reserve_timing takes the entries, behind the checks and the refill as always
     int tickEvs = 0;
@@ -91,7 +92,8 @@ struct StepCall {
         // public arrays themselves.  With an episode log (mv_set_episode_log) they always stage: the log reads every tick of the call from the slots.
         // A macro step always stages: its publication folds the slots of the call's ticks into one entry.
         // With world maps (mv_set_world_map_obs) too: the merge behind tick j reads tick j's own done flags, which only the slots keep apart in a batched call.
-        staged = own || anyLog || r.mc != nullptr || (n == 1 && L->worldMap != nullptr);
+        // With frame stacks (mv_set_stack_obs) likewise: the launch behind tick j refills the stacks of the envs whose tick-j done is set.
+        staged = own || anyLog || r.mc != nullptr || (n == 1 && (L->worldMap != nullptr || L->stack.buf != nullptr));
         drawLast = r.quiet == QUIET_LAST;
         // A batched call hands over ONCE: all k step kernels, then all k observation passes.  (Handing over tick by tick when the caller's stream is
         // found idle -- the first call after a synchronisation -- was built and measured on 20-step runs: 15.0-15.6 M obs/s against 16.2 M without;
@@ -144,6 +146,7 @@ struct StepCall {
         map = n == 1 && L->map.buf != nullptr && (r.render || drawLast);   // (mv_set_map_obs: the same)
         scan = n == 1 && L->scan.buf != nullptr && (r.render || drawLast);   // (mv_set_scan_obs: the same)
         worldMap = n == 1 && L->worldMap != nullptr && r.render;   // (mv_set_world_map_obs: every tick is drawn -- the entry points refuse the other calls)
+        stack = n == 1 && L->stack.buf != nullptr && r.render;     // (mv_set_stack_obs: the same)
         // overlapped passes (mv_set_pass_overlap): this call's one launch goes to an internal stream
         // (an env must not finish in two consecutive calls: their passes may publish its true objective in either order -- episodes of at least
         // baseEpisodeLen seconds, 15 ticks each)
@@ -151,7 +154,8 @@ struct StepCall {
         // what the consumer of the previous CALL -- enqueued after both of its chunks -- may still be reading), and rewards / dones have rings of
         // their own (two passes in flight would both publish the single arrays, in either order).
         // (no depth follower either: its reads of the call's slots and the next call's reuse of them stay ordered by the mark on the caller's stream)
-        overlap = pass == PASS_BATCH && own && !timeCall && !carry && !depth && L->passOverlap && L->passStream[0]
+        // (no frame stacks either, for the depth follower's reason: the stack launches read the call's slots -- the drawn flags, the staged dones)
+        overlap = pass == PASS_BATCH && own && !timeCall && !carry && !depth && !stack && L->passOverlap && L->passStream[0]
                 && L->ringCount >= 2 * std::max(k, r.kCall) && L->ringRewards && L->ringDone && L->baseEpisodeLen * 15.0f > float(2 * k + 2);
         views.resize((size_t)n * k); outs.resize((size_t)n * k);
         return 0;
@@ -427,8 +431,23 @@ struct StepCall {
                                  &outs[(size_t)j * n + i])) return -1;
             // (mv_set_world_map_obs, exact pixels: the pass stored the tick's planes itself -- merged before the next tick's pass overwrites them)
             if (worldMap && !depth && world_map_tick(j)) return -1;
+            // (mv_set_stack_obs, either pixel mode: the colour frames are all it reads -- stacked before the next tick's pass draws over them, which without a
+            // ring at least k deep is the same slab)
+            if (stack && stack_tick(j)) return -1;
             if (e) HIP_TRY(hipEventRecord(e[4], L->stream));
         }
+        return 0;
+    }
+
+    // the frame stacks (mv_set_stack_obs): tick j's colour frames downsampled into the agents' stacks by one launch, a stack refilled where the tick's staged
+    // done[env] is set, shifted from the entry tick j - 1's launch wrote otherwise (stack_follow keeps the chain)
+    int stack_tick(int j)
+    {
+        WorldMapClear clear;
+        clear.done = views[(size_t)j].done;
+        const int rc = stack_follow(L, views[(size_t)j], outs[(size_t)j], clear);
+        if (rc < 0) return -1;
+        L->launchCount[1] += rc;
         return 0;
     }
 
@@ -522,6 +541,11 @@ struct StepCall {
             if (still_frames_carry(L, views.data() + first, outs.data() + first, 1, k - first)) return -1;
             ++L->launchCount[1];
         }
+        // the frame stacks behind the one-launch passes (mv_set_stack_obs; PASS_BATCH: every tick's frames lie in a ring entry of their own; PASS_TICK: behind
+        // each tick's pass, passes_tick): one launch per tick, in tick order -- each shifts from the entry the one before wrote
+        if (stack && pass == PASS_BATCH)
+            for (int j = 0; j < k; ++j)
+                if (stack_tick(j)) return -1;
         // the depth planes behind fast passes (mv_set_depth_obs): one launch per drawn tick, the exact trace without the shading over the tick's frame lists in
         // the call's slots, into the entry the tick's frames went to
         // (mv_set_world_map_obs, fast pixels: the three followers below and the world map's go TICK BY TICK -- one round of the loop per tick -- because the
@@ -562,7 +586,7 @@ struct StepCall {
             if (tickOrder && world_map_tick(j0)) return -1;
         }
         if (mc && mc->last) ++L->ringTick;
-        if ((anyLog || rows || carry || depth || visible || map || scan || worldMap) && own) HIP_TRY(hipEventRecord(mark(), L->stream));
+        if ((anyLog || rows || carry || depth || visible || map || scan || worldMap || stack) && own) HIP_TRY(hipEventRecord(mark(), L->stream));
         if (own) {
             ++L->markCount;
             for (int i = 0; i < n; ++i) gs[i]->markCount = L->markCount;
@@ -622,6 +646,7 @@ int mv_step(mv_gym *g) { return step_impl(g, true, 1, POLICY_NONE, 0, 0); }
 int mv_step_no_render(mv_gym *g)
 {
     if (g && !g->closed && world_map_refuses(g, "mv_step_no_render", "and a tick that is not drawn could hide an episode's end")) return -1;   // (mv_set_world_map_obs)
+    if (g && !g->closed && stack_refuses(g, "mv_step_no_render", "and a tick that is not drawn would tear the stack")) return -1;   // (mv_set_stack_obs)
     return step_impl(g, false, 1, POLICY_NONE, 0, 0);
 }
 
@@ -644,6 +669,7 @@ int mv_step_n_render(mv_gym *g, int32_t k, int32_t policy, uint32_t seed, uint32
         if (!g->wasReset) return fail("mv_step_n_render: call mv_reset first");
         // (mv_set_world_map_obs: MV_RENDER_LAST, MV_RENDER_NONE)
         if (world_map_refuses(g, "mv_step_n_render", "and a tick that is not drawn could hide an episode's end")) return -1;
+        if (stack_refuses(g, "mv_step_n_render", "and a tick that is not drawn would tear the stack")) return -1;   // (mv_set_stack_obs: the same)
     }
     int rc = 0;
     // Episodes that can end within a few ticks (statusPeriod 1: the refill protocol looks at the consumed counts after every tick) are

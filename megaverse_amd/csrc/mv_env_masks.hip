@@ -80,6 +80,7 @@ int mv_set_draw_mask(mv_gym *g, const uint8_t *device_mask)
 {
     if (attach_check(g, "mv_set_draw_mask", gym_options[OPT_DRAW_MASK])) return -1;
     if (device_mask && world_map_refuses(g, "mv_set_draw_mask", "and a frame that is not drawn could hide an episode's end")) return -1;   // (mv_set_world_map_obs)
+    if (device_mask && stack_refuses(g, "mv_set_draw_mask", "and a frame that is not drawn would tear the stack")) return -1;   // (mv_set_stack_obs)
     // No launch, no copy: the frame setups read the caller's buffer.  This call is the ordering point, as mv_set_step_mask is: what the caller's stream holds
     // now -- the kernel that wrote the mask -- comes before the next step launch (the frame setups of mv_render and of the frame behind a reset run on the
     // caller's stream itself); the calls after that one pipeline freely.
@@ -90,6 +91,7 @@ int mv_set_draw_mask_host(mv_gym *g, const uint8_t *mask)
 {
     if (attach_check(g, "mv_set_draw_mask_host", gym_options[OPT_DRAW_MASK])) return -1;
     if (mask && world_map_refuses(g, "mv_set_draw_mask_host", "and a frame that is not drawn could hide an episode's end")) return -1;
+    if (mask && stack_refuses(g, "mv_set_draw_mask_host", "and a frame that is not drawn would tear the stack")) return -1;
     return mask ? set_host(g, g->drawMask, mask, "mv_set_draw_mask_host") : set_device(g, g->drawMask, nullptr);
 }
 

@@ -77,6 +77,7 @@ int macro_check(mv_gym *g, const char *who, int32_t k, const void *actions, int3
     if (g->inGroup) return fail(std::string(who) + ": this gym belongs to an mv_group, whose union launches know no macro steps");
     if (!g->wasReset) return fail(std::string(who) + ": call mv_reset first");
     if (world_map_refuses(g, who, "and a tick that is not drawn could hide an episode's end")) return -1;   // (mv_set_world_map_obs)
+    if (stack_refuses(g, who, "and a tick that is not drawn would tear the stack")) return -1;   // (mv_set_stack_obs)
     return 0;
 }
 

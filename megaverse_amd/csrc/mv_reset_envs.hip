@@ -13,6 +13,8 @@ int reset_envs_check(mv_gym *g, const void *mask, const char *who, int render)
     if (!g->wasReset) return fail(std::string(who) + ": call mv_reset first (there is no episode to leave)");
     // (mv_set_world_map_obs: the flagged envs' grids are cleared by the launch behind the frame this call draws)
     if (!render && world_map_refuses(g, who, "and with render = 0 no frame would clear the flagged envs' grids")) return -1;
+    // (mv_set_stack_obs: likewise, the flagged envs' stacks are refilled with that frame)
+    if (!render && stack_refuses(g, who, "and with render = 0 no frame would refill the flagged envs' stacks")) return -1;
     return 0;
 }
 

@@ -140,6 +140,9 @@ SYMBOLS = [
     ("mv_get_scan_observation", C.c_int, [_P, _I, _I, _P]),
     ("mv_debug_scan_host", C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, C.c_float, C.c_float, _P]),
     ("mv_debug_scan_device", C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, C.c_float, C.c_float, _P]),
+    ("mv_set_stack_obs", C.c_int, [_P, _P, _I, _I, _I]), ("mv_get_stack_obs", C.c_int, [_P]), ("mv_stack_obs_shape", C.c_int, [_P, _P]),
+    ("mv_get_stack_observation", C.c_int, [_P, _I, _I, _P]),
+    ("mv_debug_stack_host", C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]), ("mv_debug_stack_device", C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     ("mv_set_overview", C.c_int, [_P, _I, _I, _P]), ("mv_set_overview_cameras", C.c_int, [_P, _P]), ("mv_set_overview_cameras_host", C.c_int, [_P, _P]),
     ("mv_get_overview_observation", C.c_int, [_P, _I, _P]), ("mv_overview_device_ptr", _P, [_P]), ("mv_overview_dropped", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("mv_overview_capacity", C.c_int, [_P]), ("mv_overview_default_camera", C.c_int, [_P]), ("mv_debug_overview_camera_host", C.c_int, [_P, _P, _P]),
@@ -670,6 +673,73 @@ def debug_scan_device(depth, seg, cam12, beams, h_lo, h_hi):
     return out
 
 
+# include/megaverse_hip.h: the formats of a stack observation (mv_set_stack_obs; megaverse_amd/csrc/mv_stack_obs.h has the rule) -> (format word, channels), and
+# the grey image's integer weights of R, G, B, which sum to 256: grey = (77 R + 150 G + 29 B + 128 factor^2) >> (8 + 2 log2 factor) over the block's sums
+MV_STACK_GRAY_U8, MV_STACK_RGB_U8 = 0, 1
+STACK_FORMATS = {"gray": (MV_STACK_GRAY_U8, 1), "rgb": (MV_STACK_RGB_U8, 3)}
+STACK_GRAY_WEIGHTS = (77, 150, 29)
+
+
+def stack_shape(w, h, frames=4, factor=2, fmt="gray"):
+    """-> (S, C, h / factor, w / factor): one agent's stack for frames of w x h pixels; ValueError for what mv_set_stack_obs refuses of these arguments"""
+    if fmt not in STACK_FORMATS:
+        raise ValueError(f"stack observations: fmt must be 'gray' or 'rgb', got {fmt!r}")
+    for name, v in (("frames", frames), ("factor", factor)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"stack observations: {name} must be an int, got {v!r}")
+    if not 1 <= int(frames) <= 8:
+        raise ValueError(f"stack observations: frames must lie in [1, 8], got {frames!r}")
+    if int(factor) not in (1, 2, 4):
+        raise ValueError(f"stack observations: factor must be 1, 2 or 4, got {factor!r}")
+    if int(w) % int(factor) or int(h) % int(factor) or (int(w) // int(factor)) % 4:
+        raise ValueError(f"stack observations: {w}x{h} frames over factor {factor}: the width and height must be multiples of factor and the stack's width a "
+                         f"multiple of 4")
+    return int(frames), STACK_FORMATS[fmt][1], int(h) // int(factor), int(w) // int(factor)
+
+
+def debug_stack_host(frame, frames, factor, fmt="gray", prev=None, clear=False, out=None, layout=None, size=None):
+    """mv_debug_stack_host: the stack rule on the CPU (no device) for ONE frame: uint8 [h, w, 4] RGBA or [3, h, w] planes (layout follows the array's shape unless
+    given as the library's word, size as (w, h): for the refusal tests) -> uint8 [frames, C, h / factor, w / factor].  prev: the agent's stack before the frame
+    (None: zeros); clear: the frame is the first of a new episode; out: where the stack goes -- `prev` itself shifts in place; None: a new array.  The library's
+    refusals come back as RuntimeError"""
+    lib = load_library()
+    frame = np.ascontiguousarray(frame, np.uint8)
+    chw = frame.ndim == 3 and frame.shape[0] == 3 and frame.shape[2] != 4
+    w, h = size if size is not None else (frame.shape[2], frame.shape[1]) if chw else (frame.shape[1], frame.shape[0])
+    f = max(int(factor), 1)
+    shape = (max(int(frames), 1), STACK_FORMATS[fmt][1], max(h // f, 1), max(w // f, 1))
+    prev = np.zeros(shape, np.uint8) if prev is None else prev
+    out = np.empty(shape, np.uint8) if out is None else out
+    if lib.mv_debug_stack_host(frame.ctypes.data, int(chw) if layout is None else int(layout), int(w), int(h), int(frames), int(factor), STACK_FORMATS[fmt][0],
+                               int(bool(clear)), prev.ctypes.data, out.ctypes.data) != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
+
+def debug_stack_device(frame, frames, factor, fmt="gray", prev=None, clear=False, out=None):
+    """mv_debug_stack_device: the stack KERNEL on one frame: a contiguous uint8 CUDA tensor [h, w, 4] or [3, h, w]; prev, out: uint8 CUDA tensors [frames, C,
+    h / factor, w / factor] (prev None: zeros; out None: a new tensor; out is prev: in place) -> out; waits for the launch"""
+    import torch
+    lib = load_library()
+    if frame.dim() != 3 or frame.dtype != torch.uint8 or not frame.is_cuda or not frame.is_contiguous():
+        raise ValueError("debug_stack_device: frame is a contiguous uint8 CUDA tensor [h, w, 4] or [3, h, w]")
+    chw = frame.shape[0] == 3 and frame.shape[2] != 4
+    w, h = (int(frame.shape[2]), int(frame.shape[1])) if chw else (int(frame.shape[1]), int(frame.shape[0]))
+    shape = stack_shape(w, h, frames, factor, fmt)
+    prev = torch.zeros(shape, dtype=torch.uint8, device=frame.device) if prev is None else prev
+    out = torch.zeros(shape, dtype=torch.uint8, device=frame.device) if out is None else out
+    for t in (prev, out):
+        if tuple(t.shape) != shape or t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"debug_stack_device: prev and out are contiguous uint8 CUDA tensors {shape}")
+    torch.cuda.synchronize(frame.device)   # (the hook launches on the null stream: behind what torch's stream holds)
+    with torch.cuda.device(frame.device):
+        rc = lib.mv_debug_stack_device(_P(int(frame.data_ptr())), int(chw), w, h, int(frames), int(factor), STACK_FORMATS[fmt][0], int(bool(clear)),
+                                       _P(int(prev.data_ptr())), _P(int(out.data_ptr())))
+    if rc != 0:
+        raise RuntimeError(lib.mv_last_error().decode())
+    return out
+
+
 def debug_world_map_host(depth, seg, cam12, cells, cell_size, origin=(0.0, 0.0), grid=None, clear=False):
     """mv_debug_world_map_host: the world map rule on the CPU (no device): one frame -- debug_map_host's depth [h, w], seg [h, w] and cam12 -- merged into an
     agent's grid, int16 [3, cells, cells] (MAP_OBS_FIELDS; columns along world x from origin[0], rows along world z from origin[1], heights over world 0).
@@ -1153,7 +1223,7 @@ def _check_obs_tensor(buf, entries, tail, dtypes, device, who):
     return buf
 
 
-# The ten per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
+# The eleven per-tick observation streams of a MegaverseGym, stated once: the library's setter and single-row reader, the shape behind `entries` as a function
 # of the gym (a read-back's row is that shape without its first extent), format -> the torch dtype names a tensor may have (the first: what True allocates),
 # the arguments behind the null pointer of a detach, the numpy dtype a read-back hands out.  A new stream is one row here.
 _ObsStream = collections.namedtuple('_ObsStream', 'setter reader tail dtypes detach read')
@@ -1181,6 +1251,8 @@ OBS_STREAMS = {
                             (0, 0.0, 0.0, 0.0), np.int16),
     'scan': _ObsStream('mv_set_scan_obs', 'mv_get_scan_observation',
                        lambda g: (g.num_envs * g.num_agents_per_env, MV_SCAN_OBS_PLANES, g._scan_beams), lambda fmt: ('torch.int16',), (0, 0.0, 0.0), np.int16),
+    'stack': _ObsStream('mv_set_stack_obs', 'mv_get_stack_observation', lambda g: (g.num_envs * g.num_agents_per_env,) + g._stack_shape,
+                        lambda fmt: ('torch.uint8',), (0, 0, 0), np.uint8),
 }
 
 
@@ -1390,6 +1462,7 @@ class MegaverseGym:
         self._map_cells = 0          # set_map_obs: the grid's edge in cells (the 'map' stream's shape)
         self._world_map_cells = 0    # set_world_map_obs: the same of the 'world_map' stream
         self._scan_beams = 0         # set_scan_obs: the fan's beams (the 'scan' stream's shape)
+        self._stack_shape = (0, 0, 0, 0)   # set_stack_obs: (S, C, h, w) of one agent's stack (the 'stack' stream's shape)
         self._ring_ticks = 0         # ticks stepped through this object since set_output_ring (the library's own count: which entry the last tick went to)
         self._macro_held = None      # macro_step: the caller's device tensors of the last call, read in stream order: kept until the next macro step
         self._budget_held = None     # set_episode_budget: the caller's device tensor, read in stream order: kept until the next step has been enqueued
@@ -2053,6 +2126,36 @@ class MegaverseGym:
     def get_scan_observation(self, env_idx, agent_idx):
         """-> numpy int16 [3, beams]: the scan of one agent in the last tick's entry (waits for the gym's stream)"""
         return self._read_obs('scan', env_idx, agent_idx)
+
+    def set_stack_obs(self, buf=True, frames=4, factor=2, fmt="gray"):
+        """Stack observations (include/megaverse_hip.h: mv_set_stack_obs): the frame stack a pixel policy puts in front of its CNN, kept on the device.  Every
+        frame a later stepping call, reset or reset_envs(render=True) draws leaves, per AGENT, its last `frames` frames, each downsampled by `factor` (the
+        rounded mean of factor x factor blocks) and, fmt 'gray', weighted into one channel (STACK_GRAY_WEIGHTS / 256, rounded once), oldest first: entry
+        t % entries of a uint8 CUDA tensor [entries, num_envs * num_agents, frames, C, h / factor, w / factor], C = 1 ('gray') or 3 ('rgb': planes R, G, B),
+        entries = the output ring's count, or 1 without a ring; plane-set frames - 1 is the newest, row 0 the bottom row.  The first frame of a new episode
+        (the tick's done was set, reset(), reset_envs for a flagged env) fills all of an agent's plane-sets: a stack never mixes two episodes.  render() images
+        the newest plane-set again.  Integers only: byte-reproducible.  It reads the colour frames alone -- either layout, either pixel mode -- and needs no
+        other stream.  frames in [1, 8]; factor 1, 2 or 4; w and h multiples of factor and w / factor a multiple of 4.  True allocates a zeroed tensor on the
+        gym's device and returns it; a tensor is checked (ValueError) and attached as it is; None detaches.  One launch per drawn tick behind the pass; nothing
+        waits on the host.  While attached: step_no_render, render='last' / 'none', macro_step, reset_envs(render=False), set_draw_mask, set_still_frames,
+        set_output_ring, set_render_resolution and set_obs_layout are refused."""
+        if buf is not None:
+            self._stack_shape = stack_shape(self.w, self.h, frames, factor, fmt)
+        return self._attach_obs('stack', buf, None if buf is None else (int(frames), int(factor), STACK_FORMATS[fmt][0]))
+
+    def stack_obs_ring(self):
+        """-> the tensor set_stack_obs attached, [entries, num_envs * num_agents, frames, C, h / factor, w / factor] (entry t % entries: the stacks behind tick
+        t's frames), or None"""
+        return self._obs.get('stack')
+
+    def stack_obs(self):
+        """-> the entry of the last tick, (num_envs * num_agents, frames, C, h / factor, w / factor): a view of the attached tensor, valid in the order of the
+        gym's stream; None with nothing attached.  With an output ring: the entry the last tick stepped through this object went to"""
+        return self._obs_last('stack')
+
+    def get_stack_observation(self, env_idx, agent_idx):
+        """-> numpy uint8 [frames, C, h / factor, w / factor]: the stack of one agent in the last tick's entry (waits for the gym's stream)"""
+        return self._read_obs('stack', env_idx, agent_idx)
 
     def set_world_map_obs(self, buf=True, cells=64, cell_size=0.5, origin=(0.0, 0.0)):
         """World map observations (include/megaverse_hip.h: mv_set_world_map_obs): an ALLOCENTRIC top-down grid per agent, kept over an episode.  ONE int16 CUDA

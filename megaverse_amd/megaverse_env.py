@@ -69,7 +69,7 @@ class MegaverseEnv:
     def __init__(self, scenario_name, num_envs, num_agents_per_env, num_simulation_threads=1, use_vulkan=False, params=None,
                  img_w=128, img_h=72, device=0, env_offset=0, total_envs=0, obs_layout="rgba", episode_log=0, state_obs=False, frame_skip=1,
                  still_frames=False, scene_obs=False, depth_obs=False, seg_obs=False, entity_obs=False, overview=None, normal_obs=False, visible_obs=False, map_obs=False,
-                 world_map_obs=False, scan_obs=False):
+                 world_map_obs=False, scan_obs=False, stack_obs=False):
         if isinstance(frame_skip, (bool, np.bool_)) or not isinstance(frame_skip, (int, np.integer)) or int(frame_skip) < 1:
             raise ValueError(f"frame_skip must be an int >= 1, got {frame_skip!r}")
         # frame_skip = k > 1: step, step_batched and step_device hold their actions for up to k ticks -- one macro step (MegaverseGym.macro_step) per call: every
@@ -154,11 +154,21 @@ class MegaverseEnv:
             scan_obs = (64, SCAN_DEFAULT_BAND) if scan_obs is True else (scan_obs[0], (float(scan_obs[1]), float(scan_obs[2])))
             depth_obs = depth_obs or "float16"
             seg_obs = seg_obs or "class"
+        #   stack_obs (True: 4 frames, factor 2, 'gray'; (frames, factor, fmt)): every drawn frame leaves, per AGENT, its last `frames` frames downsampled by
+        #     `factor`, grey or RGB, oldest first, refilled with the first frame of every new episode (mv_set_stack_obs).  It reads the colour frames alone.
+        #     Every tick must be drawn: not beside frame_skip > 1 or still_frames, which the library refuses in its own words at the first such call
+        if stack_obs is not False:
+            if stack_obs is not True and not (isinstance(stack_obs, (tuple, list)) and len(stack_obs) == 3):
+                raise ValueError(f"stack_obs must be False, True or (frames, factor, fmt), got {stack_obs!r}")
+            stack_obs = (4, 2, "gray") if stack_obs is True else tuple(stack_obs)
+            if frame_skip > 1 or still_frames:
+                raise ValueError("stack_obs needs every tick drawn: not beside frame_skip > 1 or still_frames")
         wanted = (("state", state_obs, ()), ("scene", scene_obs, ()), ("entity", entity_obs, ()),
                   ("depth", depth_obs, ("float32" if depth_obs is True else depth_obs,)), ("seg", seg_obs, ("class" if seg_obs is True else seg_obs,)),
                   ("normal", normal_obs, ("float16" if normal_obs is True else normal_obs,)), ("visible", bool(visible_obs), ()),   # (behind "seg")
                   ("map", map_obs is not False, map_obs), ("world_map", world_map_obs is not False, world_map_obs),
-                  ("scan", scan_obs is not False, scan_obs))   # (behind "depth" and "seg")
+                  ("scan", scan_obs is not False, scan_obs),   # (behind "depth" and "seg")
+                  ("stack", stack_obs is not False, stack_obs))
         self._streams = {name: args for name, on, args in wanted if on}
         self._world_map = None   # world_map_obs: the one tensor of grids (_attach_stream)
         if "state" in self._streams:
@@ -266,6 +276,14 @@ class MegaverseEnv:
         the height band in units of megaverse_amd.SCAN_RANGE_UNIT (-1: none), that pixel's class and the pixels kept -- a view of the attached buffer, under
         state_obs()'s rules: ask again after every call.  A tick that drew no frame wrote nothing.  Needs MegaverseEnv(..., scan_obs=True | (beams, h_lo, h_hi))."""
         return self._stream_entry("scan", self.env.scan_obs_ring(), per_agent_planes=True)
+
+    def stack_obs(self):
+        """the last tick's frame stacks: uint8 (num_envs, num_agents_per_env, frames, C, h / factor, w / factor) on the device -- per agent its last `frames`
+        frames, downsampled and grey (C = 1) or RGB (C = 3), oldest first, all of them the first frame right after an episode began -- a view of the attached
+        buffer, under state_obs()'s rules: ask again after every call.  When step_device / step_sequence change the output rings a NEW zeroed tensor is
+        attached: the stacks fill again from there, and are whole from each env's next episode on.  Needs MegaverseEnv(..., stack_obs=True | (frames, factor,
+        fmt))."""
+        return self._stream_entry("stack", self.env.stack_obs_ring(), per_agent_planes=True)
 
     def _attach_stream(self, name, on=True):
         """one wanted stream's tensor attached (a new one, of the output ring's depth) or detached"""

@@ -221,6 +221,10 @@ class MultiTaskGym:
         """scan observations (MegaverseGym.set_scan_obs) are per gym: a group's union launches write none, and the library refuses"""
         raise _per_gym("set_scan_obs", "scan observations", "write")
 
+    def set_stack_obs(self, buf=True, frames=4, factor=2, fmt="gray"):
+        """stack observations (MegaverseGym.set_stack_obs) are per gym: a group's union launches write none, and the library refuses"""
+        raise _per_gym("set_stack_obs", "stack observations", "write")
+
     def set_overview(self, w, h, buf=True):
         """overview cameras (MegaverseGym.set_overview) are per gym: a group's union launches draw none, and the library refuses"""
         raise _per_gym("set_overview", "an overview", "draw")
